@@ -8,8 +8,15 @@ reference's 32 x render(), each = Sobol update + one sample per pixel, enqueued 
 launch (result-identical to 32 calls: tests/test_parity_gpu.py::test_batching_does_not_change_the_film) --
 followed by FilmTable.get_image(): the resolve AND the read-back of the 4 MiB image into a host array.  The scene, BVH, Sobol tables and film are
 resident in HBM before the timed region starts.  `value` is that D2H-inclusive rate (the metric
-SURVEY.md 8d defines); `value_resolve_only` (stops at the resolved image in HBM, consecutive steps
-overlapped) is reported beside it.
+SURVEY.md 8d defines), `ms_per_step` the wall time of one timed step.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what that line needs: set-up, the warm-up
+frame, W warm-up steps, K timed steps, the line.  `--dump-outputs DIR` writes the image the last timed step
+returned (DIR/image.npy); the inputs are fixed (synthetic scene, Sobol sequence), so two builds run with the
+same arguments can be compared output for output.  Everything else runs only with `--full` (the rocprofv3
+passes before the GPU is touched, the rest after the timed steps): a counting pass, `value_resolve_only`
+(stops at the resolved image in HBM, consecutive steps overlapped), `roofline` / `hbm` / `algorithmic`, the
+other BASELINE configurations (`configs`), the CPU baseline and, for N > 1, the c3 leg.
 
 N > 1, one rank per GPU: launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the
 environment) or -- when WORLD_SIZE is not set -- by this script itself, which then only spawns N
@@ -18,13 +25,13 @@ rank 0's line.  The film columns are dealt out in stripes of 16, rank r renders 
 of the replicated scene and the stripes are gathered to rank 0 -- each rank's share packed into ONE
 message, one ncclSend per rank / N - 1 ncclRecv on the root (RCCL over xGMI), scattered into the film in
 front of the resolve: strong scaling of the same 512x512x32 job (`value`, `config`: unchanged by N).
-After the headline steps an N > 1 run also times BASELINE configs[2]'s film -- s978 2048x2048, 32 spp per
+After the headline steps an N > 1 run with --full also times BASELINE configs[2]'s film -- s978 2048x2048, 32 spp per
 step, striped and gathered the same way -- and adds `c3` to the line: the configuration on which
 near-linear scaling is reachable (16 x the work per launch; the headline film is 3.6 ms of work for ONE GPU).
 No PyTorch in the process; the RCCL unique id travels through a file, barriers and the max-over-ranks are
 RCCL all-reduces.
 
-Roofline (N = 1): the dominant kernel is bound by VALU issue at partial lane occupancy, not by HBM
+Roofline (--full, N = 1): the dominant kernel is bound by VALU issue at partial lane occupancy, not by HBM
 and not by MFMA -- its scene lives in LDS.  The `roofline` object therefore prices VALU lane-operations
 per second against the chip's f32 vector lane rate (256 CUs x 4 SIMD-32 x clock), with the counters
 collected IN THIS RUN: before the parent touches the GPU it runs itself twice under `rocprofv3 --pmc`
@@ -164,6 +171,13 @@ def collect_pmc(argv_tail, budget_s=150, passes=None, role='pmc-child'):
         return out, 'rocprofv3 --pmc in this run (%d passes, %s)' % (len(passes), os.path.basename(exe))
     finally:
         shutil.rmtree(work, ignore_errors=True)
+
+
+def dump_outputs(d, img):
+    '''what the timed path returned in its last step: the resolved image get_image() hands its caller'''
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, 'image.npy'), np.ascontiguousarray(img, dtype=np.float32))
 
 
 def committed_pmc(kernel):
@@ -516,11 +530,17 @@ def parse_args(argv=None):
     ap.add_argument('--scene', default='s978')
     ap.add_argument('--mode', default='fast')
     ap.add_argument('--chunk', type=int, default=-1)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-configs', action='store_true', help='N = 1: do not time the other BASELINE configurations (`configs`)')
-    ap.add_argument('--no-pmc', action='store_true', help='do not run the rocprofv3 --pmc passes (counters from profiles/)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline: the counting pass, resolve-only steps, roofline / hbm / algorithmic figures, the rocprofv3 '
+                         '--pmc passes, the other BASELINE configurations, the CPU baseline and (N > 1) the c3 leg; a plain run times the '
+                         'headline steps only')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='rank 0 writes the image the last timed step returned to DIR/image.npy (float32, [512, 512, 4])')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: no CPU baseline')
+    ap.add_argument('--no-configs', action='store_true', help='--full, N = 1: do not time the other BASELINE configurations (`configs`)')
+    ap.add_argument('--no-pmc', action='store_true', help='--full: do not run the rocprofv3 --pmc passes (counters from profiles/)')
     ap.add_argument('--force-comm', action='store_true', help='create the RCCL communicator even for one rank')
-    ap.add_argument('--c3-steps', type=int, default=2, help='N > 1: timed steps of the 2048x2048 leg, each --c3-spp samples per pixel (0 = skip it)')
+    ap.add_argument('--c3-steps', type=int, default=2, help='--full, N > 1: timed steps of the 2048x2048 leg, each --c3-spp samples per pixel (0 = skip it)')
     ap.add_argument('--c3-spp', type=int, default=C3_SPP, help='samples per pixel of one c3 step (BASELINE configs[2]: 256)')
     ap.add_argument('--host-gather', action='store_true',
                     help='dress rehearsal on ONE GPU: every rank renders its stripes on device 0 at the same time and the shares travel '
@@ -533,7 +553,10 @@ def parse_args(argv=None):
                     help='pmc-child: the same render steps with nothing else around them (run under rocprofv3); pmc-config-child: the '
                          'render launches of one of the other configurations (--config)')
     ap.add_argument('--config', default='', help='pmc-config-child: which of OTHER_CONFIGS (c4, c5)')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 class _Stub:
@@ -680,19 +703,12 @@ def _run_rank(args, rank, world, pmc, pmc_source, phases):
         barrier()
         return
 
-    # warm-up steps double as the counting pass (algorithmic counters of the traversal actually run)
-    c.set_option('count', 1)
-    c.call('mpt_reset_counters')
+    # warm-up steps of the production kernel
     W = max(args.warmup, 1)
-    phases.enter('warm-up steps (counting kernel)')
+    phases.enter('warm-up steps')
     for _ in range(W):
         step(True)
     barrier('after warm-up')
-    cnt = c.counters()
-    c.set_option('count', 0)
-    c.kernel_time()
-    step(True)                                # one untimed step of the production (non-counting) kernel
-    barrier()
     c.kernel_time()
 
     # ---- timed region: K steps, each ending with the image in host memory (max over ranks)
@@ -706,18 +722,34 @@ def _run_rank(args, rank, world, pmc, pmc_source, phases):
     kms, nlaunch = c.kernel_time()
     if comm:
         dt = comm.allreduce_max(dt)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, img)
 
-    # ---- the same K steps stopping at the resolved image in HBM (consecutive launches overlap)
-    barrier()
-    phases.enter('resolve-only steps')
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step(False)
-    barrier('after the resolve-only steps')
-    dt_resolve = time.perf_counter() - t1
-    c.kernel_time()
-    if comm:
-        dt_resolve = comm.allreduce_max(dt_resolve)
+    if args.full:
+        # the counting pass: algorithmic counters of the traversal actually run, over W steps of the counting kernel
+        phases.enter('counting steps (counting kernel)')
+        c.set_option('count', 1)
+        c.call('mpt_reset_counters')
+        for _ in range(W):
+            step(True)
+        barrier('after the counting steps')
+        cnt = c.counters()
+        c.set_option('count', 0)
+        step(True)                            # one untimed step of the production (non-counting) kernel
+        barrier()
+        c.kernel_time()
+
+        # ---- the same K steps stopping at the resolved image in HBM (consecutive launches overlap)
+        barrier()
+        phases.enter('resolve-only steps')
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step(False)
+        barrier('after the resolve-only steps')
+        dt_resolve = time.perf_counter() - t1
+        c.kernel_time()
+        if comm:
+            dt_resolve = comm.allreduce_max(dt_resolve)
 
     if args.save_film and rank == 0:
         # (tests: the film after every step so far -- the assembled one of a rehearsal, the device's otherwise)
@@ -728,7 +760,7 @@ def _run_rank(args, rank, world, pmc, pmc_source, phases):
 
     # ---- N > 1: BASELINE configs[2] as stated: 2048 x 2048 film, 256 spp per step, striped and gathered the same way
     c3 = None
-    if comm and world > 1 and args.c3_steps > 0:
+    if args.full and comm and world > 1 and args.c3_steps > 0:
         phases.enter('c3: set-up')
         c3_spp = max(args.c3_spp, 1)
 
@@ -776,6 +808,23 @@ def _run_rank(args, rank, world, pmc, pmc_source, phases):
     if rank == 0:
         assert img is not None and img.shape == (NX, NY, 4) and (args.host_gather or float(img[..., 3].min()) == 1.0)
         total = NX * NY * SPP * args.steps
+        out = {
+            'metric': ('STUB, NOT A MEASUREMENT: ' if args.stub else '') + 'Msamples/sec (pixels x spp / s), 512x512x32spp cornell-monkey (978 tri)',
+            'value': round(total / dt / 1e6, 3), 'unit': 'Msamples/s', 'n_gpus': n_gpus, 'steps': args.steps,
+            'warmup': W, 'ms_per_step': round(dt / args.steps * 1e3, 4), 'higher_is_better': True,
+            'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f32', 'data': 'STUB (no GPU, tests only)' if args.stub else 'synthetic',
+            'config': {'workload': f'{args.scene}: 978-tri synthetic cornell + bumpy sphere, {NX}x{NY}, {SPP} spp, '
+                                   'unidirectional MIS path tracer, depth<=5; step = 32 x render() + get_image() '
+                                   '(resolve + D2H), exams/benchmark.py:29-36', 'film': [NX, NY], 'spp': SPP,
+                       'mode': args.mode,
+                       'parallelism': (f'REHEARSAL: {n_gpus} processes on ONE GPU, film columns in 16-wide stripes, shares over files (--host-gather)'
+                                       if args.host_gather else
+                                       f'film columns in 16-wide stripes over {n_gpus} GPUs, RCCL gather' if n_gpus > 1 else 'single GPU')},
+            # hardware queues the HIP runtime multiplexes this process's streams onto: the library asks for 12 before
+            # the runtime starts; under rocprofv3 --pmc the GPU is initialised first and the request has no effect
+            'hw_queues': c.get_option('hw_queues') or None,
+        }
+    if rank == 0 and args.full:
         avg_kernel_s = kms / 1e3 / max(nlaunch, 1)
         # small launches (N > 1 shares) take 1/G of the CUs each and G of them are resident at once
         concurrent = max(c.get_option('last_div'), 1)
@@ -798,18 +847,7 @@ def _run_rank(args, rank, world, pmc, pmc_source, phases):
             roof, hbm = roofline_blocks(None, f'counters unusable ({type(e).__name__}: {e})', kernel, avg_kernel_s,
                                         clock_hz, concurrent)
         samples_per_launch = cnt['samples'] / W
-        out = {
-            'metric': ('STUB, NOT A MEASUREMENT: ' if args.stub else '') + 'Msamples/sec (pixels x spp / s), 512x512x32spp cornell-monkey (978 tri)',
-            'value': round(total / dt / 1e6, 3), 'unit': 'Msamples/s', 'n_gpus': n_gpus, 'steps': args.steps,
-            'warmup': W, 'ms_per_step': round(dt / args.steps * 1e3, 4), 'higher_is_better': True,
-            'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f32', 'data': 'STUB (no GPU, tests only)' if args.stub else 'synthetic',
-            'config': {'workload': f'{args.scene}: 978-tri synthetic cornell + bumpy sphere, {NX}x{NY}, {SPP} spp, '
-                                   'unidirectional MIS path tracer, depth<=5; step = 32 x render() + get_image() '
-                                   '(resolve + D2H), exams/benchmark.py:29-36', 'film': [NX, NY], 'spp': SPP,
-                       'mode': args.mode,
-                       'parallelism': (f'REHEARSAL: {n_gpus} processes on ONE GPU, film columns in 16-wide stripes, shares over files (--host-gather)'
-                                       if args.host_gather else
-                                       f'film columns in 16-wide stripes over {n_gpus} GPUs, RCCL gather' if n_gpus > 1 else 'single GPU')},
+        out.update({
             'value_resolve_only': round(total / dt_resolve / 1e6, 3),
             'ms_per_step_resolve_only': round(dt_resolve / args.steps * 1e3, 4),
             'roofline': roof,
@@ -829,10 +867,7 @@ def _run_rank(args, rank, world, pmc, pmc_source, phases):
             'counters_per_sample': {k: round(v / max(cnt['samples'], 1), 3) for k, v in cnt.items() if k != 'samples'},
             'mrays_per_s': round(cnt['rays'] / W * concurrent / avg_kernel_s / 1e6, 1),
             'samples_per_launch': int(samples_per_launch),
-            # hardware queues the HIP runtime multiplexes this process's streams onto: the library asks for 12 before
-            # the runtime starts; under rocprofv3 --pmc the GPU is initialised first and the request has no effect
-            'hw_queues': c.get_option('hw_queues') or None,
-        }
+        })
         if n_gpus > 1:
             m = MODEL['headline']
             out['model_ms_per_step'] = round(m['a_ms'] / n_gpus + m['b_ms'], 3)
@@ -844,6 +879,7 @@ def _run_rank(args, rank, world, pmc, pmc_source, phases):
         if world == 1 and not args.no_cpu_baseline and not args.stub:
             from ptina_amd import scenes
             out['cpu_baseline'] = cpu_baseline(scene, scenes.BENCH_CAMERA)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if comm:
         comm.barrier()
@@ -872,7 +908,7 @@ def main():
     if world != args.gpus:
         raise SystemExit(f'--gpus {args.gpus} but WORLD_SIZE={world}')
     pmc, pmc_source = None, 'not collected'
-    if args.role == 'main' and world == 1 and args.mode == 'fast' and not args.no_pmc and not args.stub \
+    if args.role == 'main' and args.full and world == 1 and args.mode == 'fast' and not args.no_pmc and not args.stub \
             and os.environ.get('MIPTINA_BENCH_PMC', '1') != '0':
         # before anything in this process touches the GPU
         tail = ['--steps', '3', '--warmup', '1', '--scene', args.scene, '--mode', args.mode, '--no-cpu-baseline']

@@ -129,7 +129,9 @@ def _worker(rank, world, port, out):
 
 
 def test_two_rank_slab_gather_is_bit_identical(tmp_path, oracle_mod):
-    import torch.multiprocessing as mp
+    # torch is imported by the two rank processes only: loaded into the test process, its bundled HIP runtime and RCCL
+    # would be the ones libmiptina binds to (same sonames) for every GPU test that runs after this one
+    import multiprocessing as mp
     from ptina_amd import scenes
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
     from helpers import setup_oracle
@@ -138,7 +140,16 @@ def test_two_rank_slab_gather_is_bit_identical(tmp_path, oracle_mod):
     port = s.getsockname()[1]
     s.close()
     out = str(tmp_path / 'film.npy')
-    mp.spawn(_worker, args=(2, port, out), nprocs=2, join=True)
+    ctxm = mp.get_context('spawn')
+    ps = [ctxm.Process(target=_worker, args=(r, 2, port, out)) for r in range(2)]
+    for p in ps:
+        p.start()
+    for p in ps:
+        p.join(240)
+        if p.is_alive():
+            p.kill()
+            p.join()
+    assert [p.exitcode for p in ps] == [0, 0]
     tiled = np.load(out)
     o = setup_oracle(oracle_mod, scenes.scene_s34(), 30, 20, threads=1)
     o.render(2)
@@ -286,7 +297,7 @@ def test_bench_n_gpu_line_carries_the_config3_leg(tmp_path):
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MIPTINA_RDZV_DIR'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                        '--stub', '--c3-steps', '2'], env=env, capture_output=True, text=True, timeout=120)
+                        '--stub', '--full', '--c3-steps', '2'], env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line['n_gpus'] == 2 and line['steps'] == 2 and line['scaling'] == 'strong'
@@ -305,7 +316,7 @@ def test_bench_n_gpu_line_carries_the_config3_leg(tmp_path):
     assert roof['frac'] is not None and roof['avg_kernel_ms'] > 0 and 'x 0.5000' in roof['counters_from']
     assert 'NOT collected in this run' in roof['counters_from'] and line['hbm']['traffic_bytes'] > 0
     # one GPU: no c3 leg, no model keys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '1', '--warmup', '1', '--stub'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '1', '--warmup', '1', '--stub', '--full'],
                        env=env, capture_output=True, text=True, timeout=120)
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert r.returncode == 0 and line['n_gpus'] == 1 and 'c3' not in line and 'model_ms_per_step' not in line
@@ -314,6 +325,29 @@ def test_bench_n_gpu_line_carries_the_config3_leg(tmp_path):
     for key, v in line['configs'].items():
         assert {'workload', 'msamples_s', 'ms_per_step', 'kernel', 'avg_kernel_ms'} <= set(v), key
     assert 'build_tree_ms' in line['configs']['c5'] and '256 spp' in line['configs']['c3_film_1gpu']['workload']
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_image(tmp_path):
+    '''without --full the line holds the headline figures and nothing measured besides them; --steps sets the timed steps,
+    --dump-outputs writes the image of the last timed step (stand-in renderer: no GPU)'''
+    import json
+    import subprocess
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MIPTINA_RDZV_DIR'):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '2', '--stub',
+                        '--dump-outputs', str(tmp_path / 'out')], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line['steps'] == 3 and line['warmup'] == 2 and line['ms_per_step'] > 0
+    assert line['unit'] == 'Msamples/s' and line['higher_is_better'] is True and line['dtype'] == 'f32'
+    assert abs(line['value'] - 512 * 512 * 32 / (line['ms_per_step'] * 1e3)) <= 1e-3 * line['value']
+    assert not {'roofline', 'hbm', 'algorithmic', 'value_resolve_only', 'configs', 'cpu_baseline', 'c3'} & set(line)
+    img = np.load(tmp_path / 'out' / 'image.npy')
+    assert img.dtype == np.float32 and img.shape == (512, 512, 4)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0', '--stub'], env=env, capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode != 0 and '--steps' in r.stderr
 
 
 def test_bench_rank_that_never_returns_is_reported_with_every_ranks_phase():

@@ -2343,6 +2343,30 @@ def test_bench_refuses_more_gpus_than_the_box_has(fresh):
     assert '"n_gpus"' not in p.stdout
 
 
+def test_bench_dumps_the_same_image_run_after_run(fresh, tmp_path):
+    '''bench.py --dump-outputs: the image of the last timed step, the same bit for bit from two runs with the same arguments (the
+    inputs are fixed), a resolved film of the benchmark view'''
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    from ptina_amd.common import reset_all
+    reset_all()
+    got = []
+    for k in range(2):
+        d = tmp_path / f'run{k}'
+        p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+                            '--dump-outputs', str(d)], capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        assert line['steps'] == 2 and line['ms_per_step'] > 0 and 'roofline' not in line
+        got.append(np.load(d / 'image.npy'))
+    a, b = got
+    assert a.dtype == np.float32 and a.shape == (512, 512, 4) and np.all(a[..., 3] == 1.0)
+    assert np.all(np.isfinite(a)) and float(a[..., :3].mean()) > 0.0
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
 @pytest.mark.parametrize('world', [2, 4])
 def test_processes_render_their_stripes_concurrently_on_one_gpu(fresh, tmp_path, world):
     '''a dress rehearsal of the N-GPU run with real HIP contexts.  `bench.py --gpus R --host-gather` starts R
@@ -2359,7 +2383,7 @@ def test_processes_render_their_stripes_concurrently_on_one_gpu(fresh, tmp_path,
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     from ptina_amd.common import reset_all
     reset_all()                                          # (this process keeps its HIP context but holds no film / slabs meanwhile)
-    common = ['--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-pmc', '--no-configs']
+    common = ['--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-pmc', '--no-configs']
     env = dict(os.environ, MIPTINA_PHASE_TIMEOUT='240', MIPTINA_LAUNCH_TIMEOUT='500')
     ref = tmp_path / 'ref.npy'
     one = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--save-film', str(ref)] + common,
