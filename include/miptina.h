@@ -183,6 +183,24 @@ int mpt_sobol_get(mpt_ctx *ctx, int32_t *X, float *P, int32_t *time);
 int mpt_render(mpt_ctx *ctx, int nframes);
 /* PreviewEngine.render, ptina/engine/preview.py:18-41 : albedo -> pass 1, normal -> pass 2 */
 int mpt_render_preview(mpt_ctx *ctx, int nframes);
+/* MLTPathEngine, ptina/engine/mltpath.py (Metropolis light transport over the path integrator; single GPU: a slab / stripe
+ * split or a communicator makes mpt_mlt_render fail).  Its ti.random() is a stateless hash of (seed, chain, iteration, slot)
+ * here (ptina_amd/csrc/mlt_kernel.hip), so runs repeat bit for bit.
+ * reset, mltpath.py:31-37: nchains chains of 32 dims, X_old = random(), L_old = 0, iteration counter 0 */
+int mpt_mlt_reset(mpt_ctx *ctx, int nchains, uint32_t seed);
+/* LSP[None] / Sigma[None], mltpath.py:18-27 (defaults 0.25 / 0.01) */
+int mpt_mlt_set_param(mpt_ctx *ctx, float lsp, float sigma);
+/* render, mltpath.py:85-87 x iterations: each chain proposes, traces, splats (w += 1) into film pass 0 and accepts or rejects.
+ * Enqueued; consecutive calls are fused into one launch at the next read-back, like mpt_render's frames */
+int mpt_mlt_render(mpt_ctx *ctx, int iterations);
+/* Test doors: the chain state (X [nchains][32] = X_old, L [nchains][3] = L_old, the number of iterations done); set_state
+ * makes the given vectors current */
+int mpt_mlt_get_state(mpt_ctx *ctx, float *X, float *L, int *iteration);
+int mpt_mlt_set_state(mpt_ctx *ctx, const float *X, const float *L, int iteration);
+/* Test door: camera + path_trace (mltpath.py:66-69) of n given 32-vectors by the context's build; rgb [n][3] */
+int mpt_mlt_trace(mpt_ctx *ctx, const float *X, float *rgb, int n);
+/* HIP-event times (ms) of the chain kernels and of the splat passes launched since the last call, and their launch count */
+int mpt_mlt_kernel_time(mpt_ctx *ctx, double *chain_ms, double *splat_ms, int *launches);
 /* launch everything enqueued so far (does not wait) */
 int mpt_flush(mpt_ctx *ctx);
 /* worker.synchronize, ptina/worker.py:17-18 */

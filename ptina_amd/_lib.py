@@ -77,6 +77,13 @@ SIGNATURES = {
     'mpt_sobol_get': (_i, [_vp, _ip, _fp, _ip]),
     'mpt_render': (_i, [_vp, _i]),
     'mpt_render_preview': (_i, [_vp, _i]),
+    'mpt_mlt_reset': (_i, [_vp, _i, C.c_uint32]),
+    'mpt_mlt_set_param': (_i, [_vp, C.c_float, C.c_float]),
+    'mpt_mlt_render': (_i, [_vp, _i]),
+    'mpt_mlt_get_state': (_i, [_vp, _fp, _fp, C.POINTER(_i)]),
+    'mpt_mlt_set_state': (_i, [_vp, _fp, _fp, _i]),
+    'mpt_mlt_trace': (_i, [_vp, _fp, _fp, _i]),
+    'mpt_mlt_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     'mpt_flush': (_i, [_vp]),
     'mpt_synchronize': (_i, [_vp]),
     'mpt_clear': (_i, [_vp, _i]),

@@ -203,6 +203,9 @@ extern "C" void mpt_destroy(mpt_ctx *c) {
     hipFree(c->onode); hipFree(c->tfast8); hipFree(c->tshade8); hipFree(c->d_perm8);
     for (auto &pr : c->events) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
     for (auto &ev : c->event_pool) hipEventDestroy(ev);
+    for (auto &ev : c->mlt_events) hipEventDestroy(ev);
+    hipFree(c->mlt_X); hipFree(c->mlt_L); hipFree(c->mlt_bit); hipFree(c->mlt_keys); hipFree(c->mlt_keys2);
+    hipFree(c->mlt_vals); hipFree(c->mlt_vals2); hipFree(c->mlt_tmp); hipFree(c->mlt_runs);
     for (int p = 0; p < 3; p++) hipFree(c->film[p]);
     hipFree(c->resolved); hipFree(c->exported);
     hipFree(c->snode); hipFree(c->fnode); hipFree(c->tgeo); hipFree(c->tshade); hipFree(c->wnode); hipFree(c->qnode); hipFree(c->tfast); hipFree(c->fnode_soa);
@@ -769,8 +772,11 @@ static hipEvent_t get_event(mpt_ctx *c) {
     return e;
 }
 
+static int mlt_flush(mpt_ctx *c);
+
 extern "C" int mpt_flush(mpt_ctx *c) {
     if (!c) return fail("null context");
+    if (c->mlt_pending && mlt_flush(c)) return 1;    // (Metropolis iterations and PathEngine frames are never pending together)
     if (c->pending == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
     int B = c->pending;
@@ -1114,6 +1120,7 @@ extern "C" int mpt_render(mpt_ctx *c, int nframes) {                           /
     if (c->nx <= 0) return fail("film size not set: call set_size() first");
     if (!c->sV) return fail("sobol sampler not initialised");
     if (!c->tree_valid) return fail("BVH not built: call build_tree() after load_model()");
+    if (c->mlt_pending && mlt_flush(c)) return 1;     // the film sum follows call order: Metropolis iterations enqueued before go first
     while (nframes > 0) {
         int room = c->batch - c->pending;
         int take = std::min(room, nframes);
@@ -1139,6 +1146,184 @@ extern "C" int mpt_render_preview(mpt_ctx *c, int nframes) {                   /
         }
         nframes -= B;
     }
+    return 0;
+}
+
+// ------------------------------------------------------------------ Metropolis engine (MLTPathEngine, engine/mltpath.py)
+// Everything runs on the main stream, which every PathEngine launch is ordered behind (mpt_flush) and which the next one waits
+// for (main_dirty -> ev_main), so PathEngine frames and Metropolis iterations add to film pass 0 in call order.
+enum { MPT_MLT_SLAB_RECORDS = 1 << 24 };      // splat records per launch (20 B each, twice for the sort): larger requests are split
+
+static int mlt_check(mpt_ctx *c) {
+    if (c->mlt_n <= 0) return fail("Metropolis engine not reset: call mpt_mlt_reset first");
+    return 0;
+}
+
+static int mlt_stack(const mpt_ctx *c) {
+    return ((c->mode == MPT_MODE_STRICT ? c->tree_depth : c->fast_depth) + 2 <= 32) ? 32 : 64;
+}
+
+// launch the enqueued iterations: chain kernel + splat pass per slab-sized piece, in iteration order
+static int mlt_flush(mpt_ctx *c) {
+    int n = c->mlt_pending;
+    c->mlt_pending = 0;
+    if (n <= 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    MptRenderParams p;
+    if (fill_params(c, p, 1)) return 1;
+    const int nch = c->mlt_n;
+    const int kmax = std::max(1, (int)(MPT_MLT_SLAB_RECORDS / nch));
+    const int K0 = std::min(n, kmax);
+    const size_t recs = (size_t)K0 * nch, npix = (size_t)c->nx * c->ny;
+    if (recs > c->mlt_cap || npix > c->mlt_runs_cap) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        const size_t cap = std::max(recs, c->mlt_cap), rcap = std::max(npix, c->mlt_runs_cap);
+        size_t tmp = 0;
+        HIP_TRY(mpt_mlt_sort_bytes((int)cap, (int)rcap, &tmp));
+        hipFree(c->mlt_keys); hipFree(c->mlt_keys2); hipFree(c->mlt_vals); hipFree(c->mlt_vals2); hipFree(c->mlt_tmp); hipFree(c->mlt_runs);
+        c->mlt_keys = c->mlt_keys2 = nullptr; c->mlt_vals = c->mlt_vals2 = nullptr; c->mlt_tmp = nullptr; c->mlt_runs = nullptr;
+        c->mlt_cap = c->mlt_runs_cap = 0;
+        HIP_TRY(hipMalloc(&c->mlt_keys, cap * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&c->mlt_keys2, cap * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&c->mlt_vals, cap * sizeof(MptVec4)));
+        HIP_TRY(hipMalloc(&c->mlt_vals2, cap * sizeof(MptVec4)));
+        HIP_TRY(hipMalloc(&c->mlt_tmp, std::max(tmp, (size_t)16)));
+        HIP_TRY(hipMalloc(&c->mlt_runs, rcap * 2 * sizeof(uint32_t)));
+        c->mlt_cap = cap; c->mlt_runs_cap = rcap; c->mlt_tmp_bytes = std::max(tmp, (size_t)16);
+    }
+    const int stack = mlt_stack(c);
+    while (n > 0) {
+        const int K = std::min(n, kmax);
+        MptMltArgs a;
+        a.X = c->mlt_X; a.L = c->mlt_L; a.bit = c->mlt_bit; a.keys = c->mlt_keys; a.vals = c->mlt_vals;
+        a.nchains = nch; a.t0 = c->mlt_iter; a.K = K; a.seed = c->mlt_seed; a.lsp = c->mlt_lsp; a.sigma = c->mlt_sigma;
+        hipEvent_t e0 = get_event(c), e1 = get_event(c), e2 = get_event(c);
+        HIP_TRY(hipEventRecord(e0, c->stream));
+        if (c->mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_mlt_chain_strict(&p, &a, stack, c->stream));
+        else HIP_TRY(mpt_launch_mlt_chain_fast(&p, &a, stack, c->stream));
+        HIP_TRY(hipEventRecord(e1, c->stream));
+        HIP_TRY(mpt_launch_mlt_splat(c->film[0], c->mlt_keys, c->mlt_vals, c->mlt_keys2, c->mlt_vals2, c->mlt_tmp, c->mlt_tmp_bytes,
+                                     c->mlt_runs, K * nch, (int)npix, c->stream));
+        HIP_TRY(hipEventRecord(e2, c->stream));
+        c->mlt_events.push_back(e0); c->mlt_events.push_back(e1); c->mlt_events.push_back(e2);
+        if (c->mlt_events.size() > 3 * 4096) {       // nobody asks for the times: keep the newest half
+            for (size_t q = 0; q < 3 * 2048; q++) c->event_pool.push_back(c->mlt_events[q]);
+            c->mlt_events.erase(c->mlt_events.begin(), c->mlt_events.begin() + 3 * 2048);
+        }
+        c->mlt_iter += K;
+        n -= K;
+    }
+    c->film_version++;           // pass 0 has changed: an early image of an earlier PathEngine launch is stale
+    c->main_dirty = true;        // the next PathEngine launch waits for these
+    return 0;
+}
+
+extern "C" int mpt_mlt_reset(mpt_ctx *c, int nchains, uint32_t seed) {         // mltpath.py:31-37
+    if (use(c)) return 1;
+    if (nchains <= 0 || nchains > (1 << 24)) return fail("nchains %d outside [1, 2^24]", nchains);
+    if (nchains != c->mlt_n) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        hipFree(c->mlt_X); hipFree(c->mlt_L); hipFree(c->mlt_bit);
+        c->mlt_X = c->mlt_L = nullptr; c->mlt_bit = nullptr; c->mlt_n = 0;
+        HIP_TRY(hipMalloc(&c->mlt_X, (size_t)nchains * 2 * 32 * sizeof(float)));
+        HIP_TRY(hipMalloc(&c->mlt_L, (size_t)nchains * 3 * sizeof(float)));
+        HIP_TRY(hipMalloc(&c->mlt_bit, (size_t)nchains * sizeof(int32_t)));
+        c->mlt_n = nchains;
+    }
+    c->mlt_seed = seed; c->mlt_iter = 0; c->mlt_pending = 0;
+    HIP_TRY(mpt_launch_mlt_reset(c->mlt_X, c->mlt_L, c->mlt_bit, nchains, seed, c->stream));
+    return 0;
+}
+
+extern "C" int mpt_mlt_set_param(mpt_ctx *c, float lsp, float sigma) {       // mltpath.py:18-27: LSP[None], Sigma[None]
+    if (use(c)) return 1;                   // iterations enqueued so far run with the parameters they were enqueued under
+    c->mlt_lsp = lsp; c->mlt_sigma = sigma;
+    return 0;
+}
+
+extern "C" int mpt_mlt_render(mpt_ctx *c, int iterations) {                    // mltpath.py:85-87
+    if (!c) return fail("null context");
+    if (iterations < 0) return fail("iterations must be >= 0");
+    if (mlt_check(c)) return 1;
+    if (c->nx <= 0) return fail("film size not set: call set_size() first");
+    if (!c->tree_valid) return fail("BVH not built: call build_tree() after load_model()");
+    if (c->stripe_w != 0 || c->x0 != 0 || c->x1 != c->nx || c->comm)
+        return fail("the Metropolis engine renders the whole film on one GPU: no slab / stripe split or communicator may be set");
+    if ((long long)c->mlt_iter + c->mlt_pending + iterations >= (1ll << 31)) return fail("Metropolis iteration counter would overflow");
+    if (c->pending && mpt_flush(c)) return 1;      // PathEngine frames enqueued before go first
+    c->mlt_pending += iterations;
+    return 0;
+}
+
+extern "C" int mpt_mlt_get_state(mpt_ctx *c, float *X, float *L, int *iteration) {
+    if (use_ro(c)) return 1;
+    if (mpt_flush(c)) return 1;
+    if (mlt_check(c)) return 1;
+    const size_t n = (size_t)c->mlt_n;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (X) {
+        std::vector<float> both(n * 2 * 32);
+        std::vector<int32_t> bit(n);
+        HIP_TRY(hipMemcpy(both.data(), c->mlt_X, both.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(bit.data(), c->mlt_bit, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; i++) memcpy(X + i * 32, both.data() + ((size_t)(bit[i] & 1) * n + i) * 32, 32 * sizeof(float));
+    }
+    if (L) HIP_TRY(hipMemcpy(L, c->mlt_L, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (iteration) *iteration = c->mlt_iter;
+    return 0;
+}
+
+extern "C" int mpt_mlt_set_state(mpt_ctx *c, const float *X, const float *L, int iteration) {
+    if (use(c)) return 1;
+    if (mlt_check(c)) return 1;
+    if (!X || !L || iteration < 0) return fail("mpt_mlt_set_state: X and L must be given and iteration >= 0");
+    const size_t n = (size_t)c->mlt_n;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(c->mlt_X, X, n * 32 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->mlt_L, L, n * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(c->mlt_bit, 0, n * sizeof(int32_t)));
+    HIP_TRY(hipDeviceSynchronize());
+    c->mlt_iter = iteration;
+    return 0;
+}
+
+extern "C" int mpt_mlt_trace(mpt_ctx *c, const float *X, float *rgb, int n) {
+    if (use_ro(c)) return 1;
+    if (mpt_flush(c)) return 1;
+    if (n < 0 || (n > 0 && (!X || !rgb))) return fail("mpt_mlt_trace: bad arguments");
+    if (n == 0) return 0;
+    MptRenderParams p;
+    if (fill_params(c, p, 1)) return 1;
+    float *dX = nullptr, *drgb = nullptr;
+    HIP_TRY(hipMalloc(&dX, (size_t)n * 32 * sizeof(float)));
+    if (hipMalloc(&drgb, (size_t)n * 3 * sizeof(float)) != hipSuccess) { hipFree(dX); return fail("mpt_mlt_trace: out of device memory"); }
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(dX, X, (size_t)n * 32 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = c->mode == MPT_MODE_STRICT ? mpt_launch_mlt_trace_strict(&p, dX, drgb, n, mlt_stack(c), c->stream)
+                                                        : mpt_launch_mlt_trace_fast(&p, dX, drgb, n, mlt_stack(c), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(rgb, drgb, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost);
+    hipFree(dX); hipFree(drgb);
+    if (e != hipSuccess) return fail("mpt_mlt_trace: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int mpt_mlt_kernel_time(mpt_ctx *c, double *chain_ms, double *splat_ms, int *launches) {
+    if (use_ro(c)) return 1;
+    if (mpt_flush(c)) return 1;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    double tc = 0, ts = 0;
+    for (size_t q = 0; q + 2 < c->mlt_events.size(); q += 3) {
+        float a = 0, b = 0;
+        HIP_TRY(hipEventElapsedTime(&a, c->mlt_events[q], c->mlt_events[q + 1]));
+        HIP_TRY(hipEventElapsedTime(&b, c->mlt_events[q + 1], c->mlt_events[q + 2]));
+        tc += a; ts += b;
+    }
+    if (chain_ms) *chain_ms = tc;
+    if (splat_ms) *splat_ms = ts;
+    if (launches) *launches = (int)(c->mlt_events.size() / 3);
+    for (auto e : c->mlt_events) c->event_pool.push_back(e);
+    c->mlt_events.clear();
     return 0;
 }
 

@@ -28,6 +28,15 @@ MPT_KERNEL_API hipError_t mpt_launch_render_wide(const MptRenderParams *, int bl
 MPT_KERNEL_API hipError_t mpt_launch_render_lds(const MptRenderParams *, int grid, int block, size_t lds_bytes, int count, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_render_lds4(const MptRenderParams *, int grid, int block, size_t lds_bytes, int count, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_render_pool(const MptRenderParams *, int grid, int block, size_t lds_bytes, int count, hipStream_t);
+// mlt_kernel.hip: the Metropolis engine's chain kernel (both builds), its test door, and the build-independent passes
+MPT_KERNEL_API hipError_t mpt_launch_mlt_chain_fast(const MptRenderParams *, const MptMltArgs *, int stack, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_launch_mlt_chain_strict(const MptRenderParams *, const MptMltArgs *, int stack, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_launch_mlt_trace_fast(const MptRenderParams *, const float *X, float *rgb, int n, int stack, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_launch_mlt_trace_strict(const MptRenderParams *, const float *X, float *rgb, int n, int stack, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_launch_mlt_reset(float *X, float *L, int *bit, int nchains, unsigned seed, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_mlt_sort_bytes(int n, int npix, size_t *bytes);
+MPT_KERNEL_API hipError_t mpt_launch_mlt_splat(MptVec4 *film, const unsigned *keys, const MptVec4 *vals, unsigned *keys2, MptVec4 *vals2,
+                                               void *tmp, size_t tmp_bytes, unsigned *runs, int n, int npix, hipStream_t);
 MPT_KERNEL_API size_t mpt_pool_lds_overhead(void);
 MPT_KERNEL_API hipError_t mpt_launch_preview_fast(const MptRenderParams *, int grid, int stack, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_preview_strict(const MptRenderParams *, int grid, int stack, hipStream_t);
@@ -195,6 +204,18 @@ struct mpt_ctx {
     int *sX_spec = nullptr;              // the state the batch whose points were computed ahead of time will leave behind (swapped with sX when it is launched)
     float *sP = nullptr;                 // [MPT_MAX_BATCH][sdim]
 
+    // Metropolis engine (mlt_kernel.hip, mpt_mlt_*): chain state, splat slab and the iterations enqueued but not launched
+    int mlt_n = 0, mlt_iter = 0, mlt_pending = 0;
+    uint32_t mlt_seed = 0;
+    float mlt_lsp = 0.25f, mlt_sigma = 0.01f;
+    float *mlt_X = nullptr, *mlt_L = nullptr;            // [2][n][32], [n][3]
+    int32_t *mlt_bit = nullptr;                          // [n]
+    size_t mlt_cap = 0, mlt_tmp_bytes = 0, mlt_runs_cap = 0;   // records the slab holds; sort scratch; film elements of the run table
+    uint32_t *mlt_keys = nullptr, *mlt_keys2 = nullptr;
+    MptVec4 *mlt_vals = nullptr, *mlt_vals2 = nullptr;
+    void *mlt_tmp = nullptr;
+    uint32_t *mlt_runs = nullptr;
+    std::vector<hipEvent_t> mlt_events;                  // {chain start, chain end = splat start, splat end} per launch
     // command batching
     int pending = 0;
 

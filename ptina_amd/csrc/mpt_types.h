@@ -175,3 +175,15 @@ struct MptRenderParams {
     unsigned long long *timeline;            // diagnostics: per wave {start, scene ready, queue empty, exit} in
                                              // 100 MHz ticks, or null
 };
+
+// one launch of the Metropolis chain kernel (mlt_kernel.hip): chain state, splat records, the engine's parameters
+struct MptMltArgs {
+    float *X;                                // [2][nchains][32] chain vectors; bit[c] names chain c's current half
+    float *L;                                // [nchains][3] the current path's radiance (L_old)
+    int32_t *bit;
+    uint32_t *keys;                          // [K][nchains] film element of iteration t0 + k's proposal
+    MptVec4 *vals;                           // [K][nchains] its radiance (r, g, b, 0)
+    int32_t nchains, t0, K;
+    uint32_t seed;
+    float lsp, sigma;                        // MLTPathEngine.LSP / Sigma
+};

@@ -52,31 +52,7 @@ DEV int xcd_remap(int b, int nb) {
     return xcd * q + (xcd < r ? xcd : r) + k;
 }
 
-#if MPT_STRICT
-struct StrictTracer {
-    const MptRenderParams *p;
-    int *lds;
-    template <bool COUNT>
-    DEV Hit closest(V3 ro, V3 rd, int avoid, Cnt &cnt) const { return bvh_closest<COUNT>(*p, lds, ro, rd, avoid, cnt); }
-    template <bool COUNT>
-    DEV bool occluded(V3 ro, V3 rd, int avoid, float dis, Cnt &cnt) const {
-        return bvh_occluded<COUNT>(*p, lds, ro, rd, avoid, dis, cnt);
-    }
-};
-typedef StrictTracer BlockTracer;
-DEV BlockTracer make_block_tracer(const MptRenderParams &p, int *lds) {
-    BlockTracer t; t.p = &p; t.lds = lds; return t;
-}
-#else
-typedef Tracer<GlobalScene, Stack> BlockTracer;
-DEV BlockTracer make_block_tracer(const MptRenderParams &p, int *lds) {
-    BlockTracer t;
-    t.sc.fnode = p.fnode; t.sc.tgeo = p.tfast; t.sc.soa_n = p.fnode_soa_n;
-    t.st.base = lds; t.st.sp = 0;
-    t.n = p.n;
-    return t;
-}
-#endif
+#include "path_common.h"
 
 template <bool COUNT>
 DEV void flush_counters(const MptRenderParams &p, const Cnt &c) {
@@ -91,79 +67,6 @@ DEV void flush_counters(const MptRenderParams &p, const Cnt &c) {
         for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
         if ((threadIdx.x & 63) == 0 && x) atomicAdd(p.counters + k, (unsigned long long)x);
     }
-}
-
-// ---------------------------------------------------------------- one path = do_render + path_trace (path.py:18-93)
-struct PathState {
-    Rng rng;
-    V3 ro, rd, result, throughput;
-    float last_brdf_pdf;
-    int avoid, depth;
-};
-
-// do_render up to the camera ray, path.py:82-90, for pixel (i, j) and batch frame f
-template <bool COUNT>
-DEV void path_begin(const MptRenderParams &p, PathState &s, int i, int j, int f, Cnt &cnt) {
-    s.rng.dim = p.sobol_dim;
-    s.rng.P = p.P + (size_t)f * p.sobol_dim;
-    s.rng.i = wanghash2(i, j);                                               // path.py:72-73
-    float dx = rng_random(s.rng), dy = rng_random(s.rng);
-    float x = m_div((float)i + dx, (float)p.nx) * 2.0f - 1.0f;
-    float y = m_div((float)j + dy, (float)p.ny) * 2.0f - 1.0f;
-    camera_generate(p, x, y, &s.ro, &s.rd);
-    s.avoid = -1; s.depth = 0;
-    s.result = v3s(0.0f); s.throughput = v3s(1.0f); s.last_brdf_pdf = 0.0f;
-    if (COUNT) { cnt.samples++; cnt.n_draws += 2; }
-}
-
-// one iteration of the path_trace loop, path.py:25-62; returns true when the path has ended
-template <bool COUNT, class TR>
-DEV bool path_step(const MptRenderParams &p, const TR &tr, PathState &s, Cnt &cnt) {
-    if (!(s.depth < 5 && any_gt0(s.throughput) && any_ne0(s.rd))) return true;   // loop head, path.py:25
-    s.depth += 1;
-    if (COUNT) cnt.bounces++;
-
-    s.rd = normalized(s.rd);
-    Hit hit = tr.template closest<COUNT>(s.ro, s.rd, s.avoid, cnt);
-
-    LightHit lit = lights_hit(p, s.ro, s.rd);
-    if (lit.hit && (hit.hit == 0 || lit.dis < hit.depth)) {
-        float mis = power_heuristic(s.last_brdf_pdf, lit.pdf);
-        s.result = s.result + s.throughput * (lit.color * mis);
-    }
-
-    if (hit.hit == 0) {
-        s.result = s.result + s.throughput * world_at(p, s.rd);
-        return true;                                                         // break, path.py:39
-    }
-    s.avoid = hit.index;
-    V3 hitpos, normal; Disney material;
-    get_geometries(p, hit, s.ro, s.rd, &hitpos, &normal, material);
-    if (COUNT) { cnt.n_shade++; cnt.n_draws += 6; }
-
-    float sign = -dot(s.rd, normal);                                         // path.py:44-46 (never negative)
-    if (sign < 0.0f) normal = -normal;
-
-    LightSample li = lights_sample(p, hitpos, random3(s.rng));
-    if (any_gt0(li.color)) {
-        // (the candidate is a pure function of the bounce: evaluated before the shadow ray so that option "skip_dark" can
-        //  leave out a ray whose candidate is exactly zero; the reference traces first and evaluates if unoccluded -- same values)
-        V3 brdf_clr = disney_brdf(material, normal, sign, -s.rd, li.dir);
-        float brdf_pdf = vavg(brdf_clr);
-        float mis = power_heuristic(li.pdf, brdf_pdf);
-        V3 direct_li = li.color * mis * brdf_clr * dot_or_zero(normal, li.dir);
-        V3 direct = s.throughput * direct_li;
-        if (p.skip_dark == 0 || any_ne0(direct))
-            if (!tr.template occluded<COUNT>(hitpos, li.dir, s.avoid, li.dis, cnt))
-                s.result = s.result + direct;
-    }
-
-    BsdfSample brdf = disney_bounce(material, normal, sign, -s.rd, random3(s.rng));
-    s.throughput = s.throughput * brdf.color;
-    s.ro = hitpos;
-    s.rd = brdf.outdir;
-    s.last_brdf_pdf = brdf.pdf;
-    return false;
 }
 
 // Strict build: a lane owns ONE pixel and walks the batch's frames in order; the film sum is
