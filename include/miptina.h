@@ -56,15 +56,16 @@ typedef struct {
     uint64_t it_leaf;        /* wave-level LEAF steps issued             */
     uint64_t it_shade;       /* wave-level SHADE stages issued           */
     uint64_t it_new;         /* wave-level NEW stages issued             */
-    /* the pooled LDS kernel (option "pool"): how its two kinds of waves spent the launch */
-    uint64_t pl_local;       /* bounces a tracer wave did itself because the shade pool was full (lanes)        */
-    uint64_t pl_batches;     /* SHADE batches of the shader waves                                               */
-    uint64_t pl_batch_lanes; /* requests in those batches (pl_batch_lanes / (64 pl_batches) = SHADE lane use)   */
-    uint64_t pl_prim;        /* batches of primary rays made by the shader waves                                */
-    uint64_t pl_tidle;       /* polls of a tracer wave that held no path and found no ray                       */
-    uint64_t pl_sidle;       /* polls of a shader wave that found nothing to do                                 */
-    uint64_t pl_trips;       /* trips of a tracer wave from its traversal loop to the pools                     */
-    uint64_t pl_taken;       /* rays taken out of the ray pool by tracer lanes                                  */
+    /* spare counters: zero in the product library; the diagnostic builds MPT_X_STAMPS, MPT_X_PAIRS and MPT_X_LEAFPAIRS
+     * (render_kernel.hip) fill them with their own measurements (tools/gpu_diag.py, tools/pairs.py, tools/scratch/leafpairs.py) */
+    uint64_t pl_local;
+    uint64_t pl_batches;
+    uint64_t pl_batch_lanes;
+    uint64_t pl_prim;
+    uint64_t pl_tidle;
+    uint64_t pl_sidle;
+    uint64_t pl_trips;
+    uint64_t pl_taken;
 } mpt_counters;
 
 #define MPT_LIGHT_POINT 1    /* LightPool.TYPES, ptina/light/__init__.py:11 */
@@ -101,21 +102,16 @@ void mpt_destroy(mpt_ctx *ctx);
  * "zero_copy" (1, default: mpt_get_image into an mpt_host_alloc array has the resolve pass write the image straight into it over
  * PCIe; 0: device buffer + DMA -- same image, 20 us more per call),
  * "skip_dark" (1 = a shadow ray whose candidate direct light is exactly zero -- the light behind the surface -- is not traced:
- * adding zero or not is the same sum; 0 = traced like the reference does; -1 = on in the production build, off in the strict build: default), "pool" /
- * "pool_shaders" (the LDS kernel with its waves specialised into tracers and shaders and two path pools in LDS between them:
- * measured slower, default off),
+ * adding zero or not is the same sum; 0 = traced like the reference does; -1 = on in the production build, off in the strict build: default),
  * "spin_us" (how long mpt_get_image polls a finalising launch before it blocks; default 20000, 0 = block at once),
- * "wide8" (1: scenes that do not fit LDS walk the 8-wide octant-ordered tree instead of the 4-wide one; only in the A/B build `make oct` ->
- * libmiptina_oct.so since round 5 -- the product library refuses it; takes effect at the
- * next mpt_build_tree),
  * "finalise" (1, default: a render launch that finds no other launch in flight adds its frames to the film, resolves and
  * writes out finished tiles itself while its last paths drain; 0: always the combine pass after the launch; same film bit for bit),
  * "timeline" (1 = record mpt_get_timeline data), "reserve_cus" (CUs every persistent render launch leaves
  * unclaimed, default 0; measured to be of no use to foreign kernels while launches overlap, kept for experiments).
  * read-only: "tree_depth", "fast_depth", "wide_nodes", "wide_depth", "wide_stack" (stack levels a traversal of the 4-wide tree can
  * ask for), "wide_ratio_permille", "pending", "last_kernel" (0 = gather over the binary tree, 1 = LDS-resident over the binary
- * nodes, 2 = gather over 4-wide nodes, 3 = pooled LDS kernel (A/B library), 4 = gather over 8-wide nodes, 5 = LDS-resident over
- * the 4-wide nodes), "num_cus",
+ * nodes, 2 = gather over 4-wide nodes, 5 = LDS-resident over the 4-wide nodes; 3 and 4 are retired numbers of kernels since
+ * removed and never returned), "num_cus",
  * "cur_div", "cur_depth" (the ring the last launch belonged to: G launches of 1/G of the CUs, that many batches in
  * flight), "last_div" (what the last launch really took: 1 when it found the ring idle, else cur_div), "hw_queues"
  * (GPU_MAX_HW_QUEUES as the HIP runtime was asked for it -- the library requests 12 at load time unless the variable is
@@ -149,11 +145,6 @@ int mpt_get_tree(mpt_ctx *ctx, int32_t *child /*[n-1][2]*/, int32_t *leaf /*[n]*
 /* test/inspection: the 4-wide records the gather kernels walk (no reference counterpart): wnode [nw][8][4] f32 with the exact
  * child boxes, qnode [nw][4][4] with 8-bit boxes; any pointer may be NULL; *nw = wide nodes built (0: none) */
 int mpt_get_wide(mpt_ctx *ctx, float *wnode, float *qnode, int cap_nodes, int *nw);
-
-/* test/inspection: the 8-wide octant-ordered records the option "wide8" kernel walks (no reference counterpart; layout in
- * ptina_amd/csrc/oct_build.cpp): onode [nw][5][4] f32, perm [n] = the leaf slot of the triangle at place t of that tree's leaf
- * order; any pointer may be NULL; *nw = 8-wide nodes built (0: none) */
-int mpt_get_oct8(mpt_ctx *ctx, float *onode, int32_t *perm, int cap_nodes, int *nw);
 
 /* Pure sizing rule of the on-device SAH re-partition's workspace (no context, no GPU; the reference has no counterpart: its
  * tree is the LBVH of ptina/tree/lbvh.py:297-305).  For a model of n faces: out[0] = segments a level can hold, out[1] = words

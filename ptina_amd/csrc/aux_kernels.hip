@@ -121,20 +121,6 @@ __global__ void probe_kernel(double *out) {
     if (threadIdx.x == 0) out[0] = (double)probe_lds[blockDim.x - 1];
 }
 
-// layout A/B (option "node_soa"): the 64-B node records transposed into four arrays of float4
-__global__ __launch_bounds__(256) void transpose_nodes_kernel(const MptVec4 *__restrict__ in, MptVec4 *__restrict__ out, int ni) {
-    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (size_t)ni * 4) return;
-    size_t i = t >> 2, k = t & 3;
-    out[k * (size_t)ni + i] = in[t];
-}
-
-MPT_KERNEL_API hipError_t mpt_launch_transpose_nodes(const MptVec4 *in, MptVec4 *out, int ni, hipStream_t stream) {
-    if (ni <= 0) return hipSuccess;
-    hipLaunchKernelGGL(transpose_nodes_kernel, dim3((unsigned)(((size_t)ni * 4 + 255) / 256)), dim3(256), 0, stream, in, out, ni);
-    return hipGetLastError();
-}
-
 MPT_KERNEL_API hipError_t mpt_launch_probe(double *out, int threads, size_t lds_bytes, hipStream_t stream) {
     hipLaunchKernelGGL(probe_kernel, dim3(1), dim3(threads), lds_bytes, stream, out);
     return hipGetLastError();
@@ -206,25 +192,5 @@ __global__ __launch_bounds__(256) void derive_tfast_kernel(const MptVec4 *__rest
 MPT_KERNEL_API hipError_t mpt_launch_derive_tfast(const MptVec4 *tgeo, MptVec4 *tfast, int n, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(derive_tfast_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, tgeo, tfast, n);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------- triangle records in the 8-wide tree's leaf order
-// tfast8[t] = tfast[perm[t]] (48 B), tshade8[t] = tshade[perm[t]] (64 B): the leaf children of an 8-wide node name their
-// triangles by one base index (oct_build.cpp)
-__global__ __launch_bounds__(256) void permute_tris_kernel(const MptVec4 *__restrict__ tfast, const MptVec4 *__restrict__ tshade,
-                                                           const int32_t *__restrict__ perm, MptVec4 *__restrict__ tfast8,
-                                                           MptVec4 *__restrict__ tshade8, int n) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
-    const size_t s = (size_t)perm[t];
-    for (int k = 0; k < 3; k++) tfast8[(size_t)t * 3 + k] = tfast[s * 3 + k];
-    for (int k = 0; k < 4; k++) tshade8[(size_t)t * 4 + k] = tshade[s * 4 + k];
-}
-
-MPT_KERNEL_API hipError_t mpt_launch_permute_tris(const MptVec4 *tfast, const MptVec4 *tshade, const int32_t *perm, MptVec4 *tfast8,
-                                              MptVec4 *tshade8, int n, hipStream_t stream) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(permute_tris_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, tfast, tshade, perm, tfast8, tshade8, n);
     return hipGetLastError();
 }

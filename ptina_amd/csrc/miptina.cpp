@@ -200,7 +200,6 @@ extern "C" void mpt_destroy(mpt_ctx *c) {
     }
     if (c->ev_main) hipEventDestroy(c->ev_main);
     if (c->ev_film) hipEventDestroy(c->ev_film);
-    hipFree(c->onode); hipFree(c->tfast8); hipFree(c->tshade8); hipFree(c->d_perm8);
     for (auto &pr : c->events) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
     for (auto &ev : c->event_pool) hipEventDestroy(ev);
     for (auto &ev : c->mlt_events) hipEventDestroy(ev);
@@ -208,7 +207,7 @@ extern "C" void mpt_destroy(mpt_ctx *c) {
     hipFree(c->mlt_vals); hipFree(c->mlt_vals2); hipFree(c->mlt_tmp); hipFree(c->mlt_runs);
     for (int p = 0; p < 3; p++) hipFree(c->film[p]);
     hipFree(c->resolved); hipFree(c->exported);
-    hipFree(c->snode); hipFree(c->fnode); hipFree(c->tgeo); hipFree(c->tshade); hipFree(c->wnode); hipFree(c->qnode); hipFree(c->tfast); hipFree(c->fnode_soa);
+    hipFree(c->snode); hipFree(c->fnode); hipFree(c->tgeo); hipFree(c->tshade); hipFree(c->wnode); hipFree(c->qnode); hipFree(c->tfast);
     for (int k = 0; k < MPT_MAX_PIPE; k++) hipFree(c->stack_spill2[k]);
     hipFree(c->mats); hipFree(c->images); hipFree(c->texels); hipFree(c->lights);
     hipFree(c->sV); hipFree(c->sX); hipFree(c->sX_spec); hipFree(c->sP);
@@ -306,12 +305,6 @@ extern "C" int mpt_set_option(mpt_ctx *c, const char *key, int value) {
     } else if (k == "skip_dark") {
         if (value < -1 || value > 1) return fail("skip_dark must be -1 (auto), 0 or 1");
         c->skip_dark = value;
-    } else if (k == "wide8") {
-        if (value != 0 && value != 1) return fail("wide8 must be 0 or 1");
-#if !MPT_WITH_OCT
-        if (value) return fail("this library is built without the 8-wide octant-ordered kernel (an A/B build: make -C ptina_amd/csrc oct)");
-#endif
-        if (value != c->use_wide8) { c->use_wide8 = value; c->tree_valid = false; }    // (built by the next mpt_build_tree)
     } else if (k == "spin_us") {
         if (value < 0) return fail("spin_us must be >= 0");
         c->spin_us = value;
@@ -327,14 +320,6 @@ extern "C" int mpt_set_option(mpt_ctx *c, const char *key, int value) {
         // the slabs may hold entries with any tag of the old numbering: an epoch no launch number maps to makes the next
         // finalising launch zero them all (round-5 ADVICE: a jump inside an epoch, or to one whose tags overlap, met stale entries)
         c->tag_epoch = 0xffffffffu;
-    } else if (k == "pool") {
-#if !MPT_WITH_POOL
-        if (value) return fail("this library is built without the pooled LDS kernel (an A/B build: make -C ptina_amd/csrc pool)");
-#endif
-        c->use_pool = value ? 1 : 0;
-    } else if (k == "pool_shaders") {
-        if (value < 1 || value > 8) return fail("pool_shaders must be in 1..8");
-        c->pool_shaders = value;
     } else if (k == "timeline") {
         c->timeline = value ? 1 : 0;
     } else if (k == "pipe_depth") {
@@ -350,8 +335,6 @@ extern "C" int mpt_set_option(mpt_ctx *c, const char *key, int value) {
     } else if (k == "reserve_cus") {
         if (value < 0 || value >= c->num_cus) return fail("reserve_cus must be in 0..%d", c->num_cus - 1);
         c->reserve_cus = value;
-    } else if (k == "node_soa") {
-        c->node_soa = value ? 1 : 0;
     } else if (k == "wide") {
         c->use_wide = value ? 1 : 0;
     } else if (k == "sah_exact_max") {
@@ -402,17 +385,12 @@ extern "C" int mpt_get_option(mpt_ctx *c, const char *key, int *value) {
     else if (k == "lds_wide") *value = c->lds_wide;
     else if (k == "lds_block") *value = c->lds_block;
     else if (k == "zero_copy") *value = c->zero_copy;
-    else if (k == "wide8") *value = c->use_wide8;
-    else if (k == "oct_nodes") *value = c->oct_nodes;
-    else if (k == "oct_depth") *value = c->oct_depth;
     else if (k == "spin_us") *value = c->spin_us;
     else if (k == "finalise") *value = c->finalise;
     else if (k == "last_finalised") *value = c->last_finalised;
     else if (k == "launch_seq") *value = (int)(c->launch_seq & 0x7fffffffu);
     else if (k == "tag_wraps") *value = (int)c->tag_wraps;
-    else if (k == "pool") *value = c->use_pool;
     else if (k == "skip_dark") *value = c->skip_dark;
-    else if (k == "pool_shaders") *value = c->pool_shaders;
     else if (k == "pipe_depth") *value = c->pipe_depth;
     else if (k == "grid_div") *value = c->grid_div;
     else if (k == "cur_depth") *value = c->cur_depth;
@@ -750,7 +728,7 @@ static int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes) {
         p.t_scale = (float)std::ldexp(1.0, -e);
         p.t_unscale = (float)std::ldexp(1.0, e);
     }
-    p.wnode = c->wnode; p.qnode = c->qnode; p.nwide = c->wide_nodes; p.onode = nullptr; p.stack_spill = nullptr;
+    p.wnode = c->wnode; p.qnode = c->qnode; p.nwide = c->wide_nodes; p.stack_spill = nullptr;
     p.snode = c->snode; p.fnode = c->fnode; p.tgeo = c->tgeo; p.tshade = c->tshade; p.tfast = c->tfast;
     p.default_mtl = c->caps.max_materials;
     p.skip_dark = c->skip_dark >= 0 ? c->skip_dark : (c->mode == MPT_MODE_FAST ? 1 : 0);
@@ -851,30 +829,14 @@ extern "C" int mpt_flush(mpt_ctx *c) {
     const int lds4_nmats = c->max_mtlid + 1;
     const size_t lds4_bytes = ((size_t)c->wide_nodes * (MPT_LDS4_NODE_STRIDE / 16) + ((size_t)c->nfaces + 1) * 3 + (size_t)(lds4_nmats + 1) * 6) * sizeof(MptVec4) +
                               (((size_t)c->nfaces + 15) & ~(size_t)15) + (size_t)c->wide_stack * 1024 * sizeof(short);
-    const bool lds4_kernel = fast && c->use_lds && c->lds_wide && c->use_wide && !c->use_pool && c->wide_nodes > 0 && c->wide_stack > 0 && c->wnode &&
+    const bool lds4_kernel = fast && c->use_lds && c->lds_wide && c->use_wide && c->wide_nodes > 0 && c->wide_stack > 0 && c->wnode &&
                              c->nfaces >= 2 && c->nfaces < 4095 && lds4_nmats < 255 && lds4_bytes <= 160 * 1024 &&
                              (size_t)c->wide_nodes * MPT_LDS4_NODE_STRIDE < 65536;   // (16-bit ids: a node's is its record's LDS address, a leaf's 16 * slot + 1)
     const bool lds_kernel = lds4_kernel ||
                             (fast && c->use_lds && c->nfaces >= 2 && c->nfaces < 32768 && c->caps.max_materials < 256 &&
                              lds_bytes <= 160 * 1024 &&
                              (size_t)(c->nfaces - 1) * (MPT_LDS_NODE_STRIDE / 8) < 32768);   // (the LDS copy's node ids are byte offsets / 8 in an int16 stack)
-    // the same scene with the waves of the workgroup specialised and two path pools in LDS (render_pool.h): only the material
-    // records the model uses, stacks for the tracer waves only, node records 72 bytes apart where that fits and 64 where not
-    size_t pool_bytes = 0;
-    int pool_stride = 0;
-    const int pool_nmats = c->max_mtlid + 1;
-#if MPT_WITH_POOL
-    if (lds_kernel && c->use_pool && c->sdim <= 32768 && c->lds_block == 0) {
-        for (int stride : { MPT_LDS_NODE_STRIDE, 64 }) {
-            const size_t b = ((((size_t)(c->nfaces - 1) * stride + 15) >> 4) + (size_t)c->nfaces * 3 + (size_t)(pool_nmats + 1) * 6) * sizeof(MptVec4) +
-                             (((size_t)c->nfaces + 15) & ~(size_t)15) + mpt_pool_lds_overhead() +
-                             (size_t)lds_stack * (size_t)(16 - c->pool_shaders) * 64 * sizeof(short);
-            if (b <= 160 * 1024) { pool_bytes = b; pool_stride = stride; break; }
-        }
-    }
-#endif
-    const bool pool_kernel = pool_bytes != 0;
-    p.lds_node_stride = pool_stride; p.lds_nmats = pool_nmats; p.pool_shaders = c->pool_shaders;
+    p.lds_nmats = lds4_nmats;                           // (render_kernel_lds4: the material records it keeps in LDS)
     int chunk = B, nchunks = 1;
     const int tw = 1 << c->tile_w_shift, th = 1 << c->tile_h_shift;
     int tile_cols = 0;
@@ -960,16 +922,9 @@ extern "C" int mpt_flush(mpt_ctx *c) {
     // half the dependent fetches; with the planes picked by direction sign it wins on both big configurations
     // (MI355X: C4 963 -> 1135 Msamples/s, C5 494 -> 520), so it is the default wherever the collapse was built.
     const bool wide_pays = c->use_wide != 0;
-    // ... or the 8-wide octant-ordered nodes (option "wide8", oct_build.cpp) with the triangle records in that tree's leaf order
-    const bool oct_kernel = fast && !lds_kernel && c->use_wide8 && c->oct_nodes > 0;
-    const bool wide_kernel = oct_kernel || (fast && !lds_kernel && wide_pays && c->wide_nodes > 0);
+    const bool wide_kernel = fast && !lds_kernel && wide_pays && c->wide_nodes > 0;
     int wide_blocks = 0;
-    if (oct_kernel) { p.onode = c->onode; p.tfast = c->tfast8; p.tshade = c->tshade8; }
     if (wide_kernel) {
-#if MPT_WITH_OCT
-        if (oct_kernel) HIP_TRY(mpt_oct_blocks(launch_cus, c->count, &wide_blocks));
-        else
-#endif
         HIP_TRY(mpt_wide_blocks(launch_cus, c->count, c->use_quant, &wide_blocks));
         const size_t need_spill = (size_t)wide_blocks * MPT_BLOCK * 128;   // >= SpillStack::SPILL entries per lane (128 - LDS levels)
         // every slot of the ring at once (an allocation synchronises the device), and one strip PER SLOT: the launches of
@@ -983,22 +938,6 @@ extern "C" int mpt_flush(mpt_ctx *c) {
             }
         p.stack_spill = c->stack_spill2[k];
     }
-    if (fast && !lds_kernel && !wide_kernel && c->node_soa && c->nfaces >= 2) {
-        // layout A/B: the same records as four arrays (one 16-B gather per array instead of one 64-B record)
-        const size_t ni = (size_t)c->nfaces - 1;
-        if (!c->fnode_soa_valid) {
-            if (ni > c->fnode_soa_cap) {
-                HIP_TRY(hipDeviceSynchronize());
-                hipFree(c->fnode_soa); c->fnode_soa = nullptr; c->fnode_soa_cap = 0;
-                if (dev_alloc(&c->fnode_soa, ni * 4)) return 1;
-                c->fnode_soa_cap = ni;
-            }
-            HIP_TRY(mpt_launch_transpose_nodes(c->fnode, c->fnode_soa, (int)ni, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            c->fnode_soa_valid = true;
-        }
-        p.fnode = c->fnode_soa; p.fnode_soa_n = (int)ni;
-    }
     // Lanes per persistent workgroup of the LDS-resident kernel.  A launch that gives a lane fewer than six samples (an eighth
     // of the benchmark film: four) is over before a steady state forms: its length is a few path latencies, and a path is
     // faster with three waves per SIMD than with four (MI355X, 1/8 share: 0.78 ms at 768 lanes against 0.84 at 1024; from a
@@ -1006,7 +945,7 @@ extern "C" int mpt_flush(mpt_ctx *c) {
     // (The kernel over the 4-wide nodes is fastest with 1024 lanes at every size: solo launch of a 1/8 share 0.49 ms against 0.53
     // at 768, 0.64 at 512; whole film 2.59 / 2.97 / 3.94.)
     int lds_block_used = c->lds_block ? c->lds_block : 1024;
-    if (lds_kernel && !lds4_kernel && !pool_kernel && c->lds_block == 0 &&
+    if (lds_kernel && !lds4_kernel && c->lds_block == 0 &&
         ((long long)p.nitems * chunk << (c->tile_w_shift + c->tile_h_shift)) < 6ll * launch_cus * 1024) lds_block_used = 768;
     p.timeline = nullptr;
     if (c->timeline && lds_kernel) {
@@ -1026,7 +965,7 @@ extern "C" int mpt_flush(mpt_ctx *c) {
     // its frames to the film, resolves and writes the image out by itself, in the shadow of its own drain (finalise_tiles).  A
     // launch issued while another is in flight keeps the combine pass on the main stream: two launches must not add to the same
     // film pixels at the same time, and the main stream is what orders them.
-    const bool fin = fast && c->finalise && ring_idle && !pool_kernel && p.nitems > 0;
+    const bool fin = fast && c->finalise && ring_idle && p.nitems > 0;
     c->launch_seq++;
     p.fin_counter = nullptr; p.image_out = nullptr; p.slab_tag = MPT_TAG_COMBINE;
     c->film_version++;                           // this batch changes pass 0, whoever adds it
@@ -1069,17 +1008,11 @@ extern "C" int mpt_flush(mpt_ctx *c) {
     hipEvent_t e0 = get_event(c), e1 = get_event(c);
     HIP_TRY(hipEventRecord(e0, rs));
     if (!fast) HIP_TRY(mpt_launch_render_strict(&p, p.ntiles, stack, c->count, rs));
-#if MPT_WITH_POOL
-    else if (pool_kernel) HIP_TRY(mpt_launch_render_pool(&p, launch_cus, 1024, pool_bytes, c->count, rs));
-#endif
     else if (lds4_kernel) HIP_TRY(mpt_launch_render_lds4(&p, launch_cus, lds_block_used, lds4_bytes, c->count, rs));
     else if (lds_kernel) HIP_TRY(mpt_launch_render_lds(&p, launch_cus, lds_block_used, lds_bytes, c->count, rs));
-#if MPT_WITH_OCT
-    else if (oct_kernel) HIP_TRY(mpt_launch_render_oct(&p, wide_blocks, c->count, rs));
-#endif
     else if (wide_kernel) HIP_TRY(mpt_launch_render_wide(&p, wide_blocks, c->count, c->use_quant, rs));
     else HIP_TRY(mpt_launch_render_fast(&p, launch_cus, stack, c->count, rs));
-    c->last_kernel = pool_kernel ? 3 : lds4_kernel ? 5 : lds_kernel ? 1 : oct_kernel ? 4 : wide_kernel ? 2 : 0;
+    c->last_kernel = lds4_kernel ? 5 : lds_kernel ? 1 : wide_kernel ? 2 : 0;      // (3 and 4 are retired: include/miptina.h)
     HIP_TRY(hipEventRecord(e1, rs));
     c->events.push_back({ e0, e1 });
     if (c->events.size() > 4096) {

@@ -27,7 +27,6 @@ MPT_KERNEL_API hipError_t mpt_wide_blocks(int grid, int count, int quant, int *b
 MPT_KERNEL_API hipError_t mpt_launch_render_wide(const MptRenderParams *, int blocks, int count, int quant, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_render_lds(const MptRenderParams *, int grid, int block, size_t lds_bytes, int count, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_render_lds4(const MptRenderParams *, int grid, int block, size_t lds_bytes, int count, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_render_pool(const MptRenderParams *, int grid, int block, size_t lds_bytes, int count, hipStream_t);
 // mlt_kernel.hip: the Metropolis engine's chain kernel (both builds), its test door, and the build-independent passes
 MPT_KERNEL_API hipError_t mpt_launch_mlt_chain_fast(const MptRenderParams *, const MptMltArgs *, int stack, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_mlt_chain_strict(const MptRenderParams *, const MptMltArgs *, int stack, hipStream_t);
@@ -37,7 +36,6 @@ MPT_KERNEL_API hipError_t mpt_launch_mlt_reset(float *X, float *L, int *bit, int
 MPT_KERNEL_API hipError_t mpt_mlt_sort_bytes(int n, int npix, size_t *bytes);
 MPT_KERNEL_API hipError_t mpt_launch_mlt_splat(MptVec4 *film, const unsigned *keys, const MptVec4 *vals, unsigned *keys2, MptVec4 *vals2,
                                                void *tmp, size_t tmp_bytes, unsigned *runs, int n, int npix, hipStream_t);
-MPT_KERNEL_API size_t mpt_pool_lds_overhead(void);
 MPT_KERNEL_API hipError_t mpt_launch_preview_fast(const MptRenderParams *, int grid, int stack, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_preview_strict(const MptRenderParams *, int grid, int stack, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_sobol_update(const int *X, int *Xout, const int *V, float *P, int dim, int rows, int time0,
@@ -45,7 +43,6 @@ MPT_KERNEL_API hipError_t mpt_launch_sobol_update(const int *X, int *Xout, const
 MPT_KERNEL_API hipError_t mpt_launch_combine(MptVec4 *film, const MptVec4 *partial, int ny, int x0, int x1,
                                          int stripe_w, int stripe_pitch, int ccols, int nframes, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_resolve(const MptVec4 *film, MptVec4 *out, size_t npix, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_transpose_nodes(const MptVec4 *in, MptVec4 *out, int ni, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_probe(double *out, int threads, size_t lds_bytes, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_unit_eval_fast(int kind, const float *in, int in_cols, float *out, int out_cols, int n, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_unit_eval_strict(int kind, const float *in, int in_cols, float *out, int out_cols, int n, hipStream_t);
@@ -77,21 +74,12 @@ MPT_KERNEL_API hipError_t mpt_wide_scan_bytes(int ni, size_t *bytes);
 MPT_KERNEL_API hipError_t mpt_wide_build(const MptVec4 *fnode, int n, MptVec4 *wnode, MptVec4 *qnode, int *bin_of, int *ncount,
                                      int *offset, void *scan_tmp, size_t scan_bytes, double *d_area, int *nwide, int *depth,
                                      double area[2], hipStream_t stream, volatile int *mail_host, int *mail_dev);
-MPT_KERNEL_API hipError_t mpt_launch_permute_tris(const MptVec4 *tfast, const MptVec4 *tshade, const int32_t *perm, MptVec4 *tfast8,
-                                              MptVec4 *tshade8, int n, hipStream_t stream);
-MPT_KERNEL_API hipError_t mpt_oct_blocks(int grid, int count, int *blocks);
-MPT_KERNEL_API hipError_t mpt_launch_render_oct(const MptRenderParams *p, int blocks, int count, hipStream_t stream);
 MPT_KERNEL_API hipError_t mpt_lbvh_sort_bytes(int n, size_t *bytes);
 MPT_KERNEL_API hipError_t mpt_lbvh_build(const MptLbvhBuffers *b, hipStream_t stream);
 
 // ------------------------------------------------------------------ errors (miptina.cpp)
-#ifndef MPT_WITH_POOL
-#define MPT_WITH_POOL 0          // 1: the pooled LDS kernel (render_pool.h) is compiled in (A/B build `make pool`)
-#endif
 #define MPT_INTERNAL __attribute__((visibility("hidden")))   // shared between the .cpp files, not exported
 MPT_INTERNAL int fail(const char *fmt, ...);
-struct mpt_ctx;
-MPT_INTERNAL int make_oct8(mpt_ctx *c);          // oct_build.cpp
 
 #define HIP_TRY(expr)                                                                     \
     do {                                                                                  \
@@ -112,7 +100,6 @@ struct mpt_ctx {
     int lds_wide = 1;                                 // 1: scenes that fit LDS beside them walk the 4-wide nodes there (render_kernel_lds4), 0: the binary ones (render_kernel_lds)
     int skip_dark = -1;                  // -1 auto (production build on, strict build off), 0 / 1 as set: do not trace shadow rays whose candidate direct light is exactly zero (production build: default;
                                          // the strict build traces them like the reference unless the option is set explicitly to 1 there)
-    int use_pool = 0, pool_shaders = 3;  // LDS kernel with specialised waves and path pools (render_pool.h)
     int max_mtlid = -1;                  // largest material id of the model (-1: only the default material)
     int num_cus = 256;
     int clock_khz = 0;                   // hipDeviceProp_t.clockRate: peak shader clock (roofline peaks in bench.py)
@@ -181,8 +168,6 @@ struct mpt_ctx {
     // overflow strips of the wide kernel's per-lane stacks: one per ring slot, because launches of different slots
     // are resident together and index their strips by block and lane only
     int *stack_spill2[MPT_MAX_PIPE] = {}; size_t stack_spill2_cap[MPT_MAX_PIPE] = {};
-    int node_soa = 0;                                 // option "node_soa" (layout A/B): binary gather kernel reads an SoA transpose
-    MptVec4 *fnode_soa = nullptr; size_t fnode_soa_cap = 0; bool fnode_soa_valid = false;
     size_t node_cap = 0, tri_cap = 0;
 
     // materials / images / lights / world / camera
@@ -262,13 +247,6 @@ struct mpt_ctx {
     size_t partial2_cap[MPT_MAX_PIPE] = {};           // float4 elements per buffer
     float *sP2[MPT_MAX_PIPE] = {};
     unsigned int *d_work2[MPT_MAX_PIPE] = {};
-
-    // 8-wide octant-ordered tree (oct_build.cpp, render_kernel_oct): option "wide8" = 1 builds and walks it for scenes that do
-    // not fit LDS; onode [oct_nodes][5], the triangle records in its leaf order (tfast8 / tshade8), d_perm8 [n]: t8 -> leaf slot
-    int use_wide8 = 0;
-    MptVec4 *onode = nullptr; size_t onode_cap = 0;
-    MptVec4 *tfast8 = nullptr, *tshade8 = nullptr; int32_t *d_perm8 = nullptr; size_t tri8_cap = 0;
-    int oct_nodes = 0, oct_depth = 0;
 
     // measurement
     int timeline = 0;                    // 1: the LDS kernel records per-wave timestamps of its last launch

@@ -121,25 +121,21 @@ struct MptRenderParams {
     int32_t nframes, chunk, nchunks, n;     // batch frames; frames per work item; items per tile; #triangles
     int32_t sobol_dim, nlights, world_tex, tiles_x;   // tiles_* : 16x16 tiles of the slab (strict build)
     int32_t tiles_y, ntiles;
-    int32_t fnode_soa_n;                    // 0, or the node count when fnode holds the SoA transpose (layout A/B)
     float sobol_inv_dim;                    // 1 / sobol_dim (quotient estimate of the draw index reduction)
     int32_t nitems, tile_w_shift, tile_h_shift;   // fast build: (2^w x 2^h tile, chunk) work items of this launch
     int32_t nwide;                          // records of qnode (render_kernel_lds4 copies them into LDS)
     // columns rendered: x = x0 + s*stripe_pitch + w, w < stripe_w, x < x1 (one contiguous slab: stripe_w = 2^30)
     int32_t stripe_w, stripe_pitch;
-    int32_t partial_stride;
-    // pooled LDS kernel (render_pool.h): bytes between node records in LDS, material records kept in LDS besides the
-    // default one, shader waves of the 16
-    int32_t lds_node_stride, lds_nmats, pool_shaders;
+    int32_t partial_stride;                 // float4 per frame of the sample slab = (tile-padded columns of the share) * ny
+    int32_t lds_nmats;                      // material records render_kernel_lds4 keeps in LDS besides the default one
     int32_t skip_dark;                      // 1: shadow rays whose candidate direct light is exactly zero are not traced (production build)
-    int32_t default_mtl;                    // index of the default material's record in mats (fast build)           // float4 per frame of the sample slab = (tile-padded columns of the share) * ny
+    int32_t default_mtl;                    // index of the default material's record in mats (fast build)
     float world_fac[4];
     float v2w[16];
     const MptVec4 *snode;
     const MptVec4 *fnode;
     const MptVec4 *wnode;                    // 4-wide traversal nodes (scenes that do not fit LDS), or null
     const MptVec4 *qnode;                    // the same nodes with the child boxes quantised to 8 bits (64-B records), or null
-    const MptVec4 *onode;                    // 8-wide octant-ordered nodes (80-B records, oct_build.cpp), or null; tfast / tshade then hold the records in ITS leaf order
     const MptVec4 *tgeo;
     const MptVec4 *tshade;
     const MptVec4 *tfast;                    // production build: 48-byte triangle records {n, v0.x}{a, v0.y}{c, v0.z} derived from tgeo

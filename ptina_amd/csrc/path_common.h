@@ -25,7 +25,7 @@ DEV BlockTracer make_block_tracer(const MptRenderParams &p, int *lds) {
 typedef Tracer<GlobalScene, Stack> BlockTracer;
 DEV BlockTracer make_block_tracer(const MptRenderParams &p, int *lds) {
     BlockTracer t;
-    t.sc.fnode = p.fnode; t.sc.tgeo = p.tfast; t.sc.soa_n = p.fnode_soa_n;
+    t.sc.fnode = p.fnode; t.sc.tgeo = p.tfast;
     t.st.base = lds; t.st.sp = 0;
     t.n = p.n;
     return t;

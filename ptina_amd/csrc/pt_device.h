@@ -144,9 +144,8 @@ DEV V3 random3(Rng &r) { float a = rng_random(r), b = rng_random(r), c = rng_ran
 
 // ---------------------------------------------------------------- counters
 struct Cnt { unsigned rays, n_box, n_tri, n_shade, n_draws, bounces, n_node, samples, it_node, it_leaf, it_shade, it_new;
-             // pooled kernel (render_pool.h): bounces a tracer did itself because the shade pool was full; shader batches and the
-             // requests in them; primary-ray batches; tracer / shader polls with nothing to do; trips of a tracer to the pools;
-             // rays taken by tracers
+             // spare counters that the diagnostic builds fill with their own measurements (MPT_X_STAMPS, MPT_X_PAIRS,
+             // MPT_X_LEAFPAIRS in render_kernel.hip; read by tools/gpu_diag.py, tools/pairs.py, tools/scratch/leafpairs.py)
              unsigned pl_local, pl_batches, pl_batch_lanes, pl_prim, pl_tidle, pl_sidle, pl_trips, pl_taken; };
 
 // ---------------------------------------------------------------- geometry
@@ -287,19 +286,12 @@ struct GlobalScene {
     static constexpr bool AVOID_IN_LEAF = false;
     static constexpr int SHADE_MIN = 0;                // (render_kernel.hip trace_stream: lanes SHADE waits for)
     static constexpr int NODE_REP = MPT_NODE_REP;
-    static constexpr bool WIDE = false, QUANT = false, SIGNED_PLANES = false, LDS_MATS = false, OCT = false;
+    static constexpr bool WIDE = false, QUANT = false, SIGNED_PLANES = false, LDS_MATS = false;
     static constexpr bool ODD_IDS = false, T_SCALED = false;
     const MptVec4 *fnode, *tgeo;
-    int soa_n;                 // node count, for the layout A/B build below
     DEV void node(int i, MptVec4 &a, MptVec4 &b, MptVec4 &c, MptVec4 &d) const {
-#if MPT_X_NODE_SOA
-        // layout A/B build only (option "node_soa" = 1 hands it the transposed arrays): four arrays of float4
-        const MptVec4 *nd = fnode + i;
-        a = nd[0]; b = nd[soa_n]; c = nd[2 * (size_t)soa_n]; d = nd[3 * (size_t)soa_n];
-#else
         const MptVec4 *nd = fnode + (size_t)i * 4;
         a = nd[0]; b = nd[1]; c = nd[2]; d = nd[3];
-#endif
     }
     DEV void tri(int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) const {       // tfast: 48-byte records
         const MptVec4 *g = tgeo + (size_t)slot * 3;
@@ -310,19 +302,16 @@ struct GlobalScene {
 // The triangle a ray left from is filtered by the LEAF step (one compare) instead of by the 4-wide NODE step (four compares and
 // four mask merges): its own leaf is then visited once per ray that starts on a surface -- three gathers -- and it is still
 // cheaper: MI355X C4 1583 -> 1607, C5 804 -> 824 Msamples/s (alternated twice)
-#ifndef MPT_WIDE_AVOID_IN_LEAF
-#define MPT_WIDE_AVOID_IN_LEAF 1
-#endif
 // 4-wide nodes gathered from HBM / L2 / Infinity Cache (scenes that do not fit LDS): a traversal step is one
 // 128-B record and four box tests, and a ray makes half as many DEPENDENT fetches as through the binary tree --
 // those fetches, not their bytes, are what bounds the big scenes (measured: binary16 boxes at half the bytes
 // bought 3-7 %)
 struct WideScene {
     static constexpr int LEAF_REP = MPT_WIDE_LEAF_REP;
-    static constexpr bool AVOID_IN_LEAF = MPT_WIDE_AVOID_IN_LEAF != 0;
+    static constexpr bool AVOID_IN_LEAF = true;
     static constexpr int SHADE_MIN = 0;                // (render_kernel.hip trace_stream: lanes SHADE waits for)
     static constexpr int NODE_REP = MPT_WIDE_REP;
-    static constexpr bool WIDE = true, QUANT = false, SIGNED_PLANES = false, LDS_MATS = false, OCT = false;
+    static constexpr bool WIDE = true, QUANT = false, SIGNED_PLANES = false, LDS_MATS = false;
     static constexpr bool ODD_IDS = false, T_SCALED = false;
     const MptVec4 *wnode, *tgeo;
     // entry (n*) and exit (f*) planes of the four children, picked by the ray's direction signs: o* is 0 for a ray
@@ -337,28 +326,6 @@ struct WideScene {
         ny = *(const MptVec4 *)(base + 32 + (o + (unsigned)oy)); fy = *(const MptVec4 *)(base + 32 + (o + (unsigned)(oy ^ 16)));
         nz = *(const MptVec4 *)(base + 64 + (o + (unsigned)oz)); fz = *(const MptVec4 *)(base + 64 + (o + (unsigned)(oz ^ 16)));
         id = *(const MptVec4 *)(base + 96 + o);
-#if MPT_X_DUP_NODE_LOADS
-        // sensitivity A/B (same film): three of the seven gathers issued twice (ordinary cached loads through an
-        // offset the compiler cannot see through) -- what do the gathers themselves cost?
-        // (1: as 16-byte gathers; 2: as 4-byte gathers of their first word)
-        {
-            unsigned o2 = o;
-            asm volatile("" : "+v"(o2));
-#if MPT_X_DUP_NODE_LOADS == 1
-            const MptVec4 a = *(const MptVec4 *)(base + (o2 + (unsigned)(ox ^ 16)));
-            const MptVec4 b = *(const MptVec4 *)(base + 32 + (o2 + (unsigned)(oy ^ 16)));
-            const MptVec4 c = *(const MptVec4 *)(base + 64 + (o2 + (unsigned)(oz ^ 16)));
-            fx.x = a.x == fx.x ? fx.x : a.x; fx.y = a.y == fx.y ? fx.y : a.y; fx.z = a.z == fx.z ? fx.z : a.z; fx.w = a.w == fx.w ? fx.w : a.w;
-            fy.x = b.x == fy.x ? fy.x : b.x; fy.y = b.y == fy.y ? fy.y : b.y; fy.z = b.z == fy.z ? fy.z : b.z; fy.w = b.w == fy.w ? fy.w : b.w;
-            fz.x = c.x == fz.x ? fz.x : c.x; fz.y = c.y == fz.y ? fz.y : c.y; fz.z = c.z == fz.z ? fz.z : c.z; fz.w = c.w == fz.w ? fz.w : c.w;
-#else
-            const float a = *(const float *)(base + (o2 + (unsigned)(ox ^ 16)));
-            const float b = *(const float *)(base + 32 + (o2 + (unsigned)(oy ^ 16)));
-            const float c = *(const float *)(base + 64 + (o2 + (unsigned)(oz ^ 16)));
-            fx.x = a == fx.x ? fx.x : a; fy.x = b == fy.x ? fy.x : b; fz.x = c == fz.x ? fz.x : c;
-#endif
-        }
-#endif
     }
     DEV void tri(int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) const {       // tfast: 48-byte records
         const MptVec4 *g = tgeo + (size_t)slot * 3;
@@ -373,48 +340,20 @@ struct WideScene {
 // at 34-43 % issue utilisation.
 struct QuantScene {
     static constexpr int LEAF_REP = MPT_WIDE_LEAF_REP;
-    static constexpr bool AVOID_IN_LEAF = MPT_WIDE_AVOID_IN_LEAF != 0;
+    static constexpr bool AVOID_IN_LEAF = true;
 #ifndef MPT_WIDE_SHADE_MIN
 #define MPT_WIDE_SHADE_MIN 0
 #endif
     static constexpr int SHADE_MIN = MPT_WIDE_SHADE_MIN;   // (render_kernel.hip trace_stream: lanes SHADE waits for; 0: it never waits)
     static constexpr int NODE_REP = MPT_WIDE_REP;      // extra NODE steps per scheduling decision
-    static constexpr bool WIDE = true, QUANT = true, SIGNED_PLANES = false, LDS_MATS = false, OCT = false;
+    static constexpr bool WIDE = true, QUANT = true, SIGNED_PLANES = false, LDS_MATS = false;
     static constexpr bool ODD_IDS = false, T_SCALED = false;
     const MptVec4 *qnode, *tgeo;
-#if MPT_X_TOPCACHE
-    // A/B build (-DMPT_X_TOPCACHE=N): the first N records (the 4-wide nodes are numbered breadth first: the top of the tree) are kept
-    // in the workgroup's LDS; a lane whose node is among them reads it there
-    typedef float top_f4 __attribute__((ext_vector_type(4)));
-    __attribute__((address_space(3))) const top_f4 *top;
-#endif
     DEV void node4q(int i, MptVec4 &a, MptVec4 &b, MptVec4 &c, MptVec4 &id) const {
         const char *base = (const char *)qnode;
         const unsigned o = (unsigned)i << 6;
-#if MPT_X_TOPCACHE
-        if (i < MPT_X_TOPCACHE) {
-            const top_f4 v0 = top[i * 4], v1 = top[i * 4 + 1], v2 = top[i * 4 + 2], v3 = top[i * 4 + 3];
-            a = { v0.x, v0.y, v0.z, v0.w }; b = { v1.x, v1.y, v1.z, v1.w }; c = { v2.x, v2.y, v2.z, v2.w }; id = { v3.x, v3.y, v3.z, v3.w };
-            return;
-        }
-#endif
         a = *(const MptVec4 *)(base + o); b = *(const MptVec4 *)(base + 16 + o);
         c = *(const MptVec4 *)(base + 32 + o); id = *(const MptVec4 *)(base + 48 + o);
-#if MPT_X_DUP_QNODE
-        // sensitivity A/B (same film): MPT_X_DUP_QNODE extra 4-byte gathers per step -- what is one gather more or less worth?
-        {
-            unsigned o2 = o;
-            asm volatile("" : "+v"(o2));
-            const float e0 = *(const float *)(base + 4 + o2);
-            a.y = e0 == a.y ? a.y : e0;
-#if MPT_X_DUP_QNODE > 1
-            unsigned o3 = o;
-            asm volatile("" : "+v"(o3));
-            const float e1 = *(const float *)(base + 20 + o3);
-            b.y = e1 == b.y ? b.y : e1;
-#endif
-        }
-#endif
     }
     DEV void tri(int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) const {       // tfast: 48-byte records
         const MptVec4 *g = tgeo + (size_t)slot * 3;
@@ -454,64 +393,6 @@ struct SpillStack {
     static constexpr int SP_STEP = 1;
 };
 
-// 8-wide nodes with octant-ordered child slots and 8-bit boxes (oct_build.cpp): 80-byte records, FIVE 16-B gathers per step for
-// eight box tests; the order the children are met in is slot XOR the ray's direction octant -- no sort -- and a node leaves at most
-// two stack entries behind (its other internal hits, its other leaf hits), each a (base | mask, slots to go) pair
-struct OctScene {
-    static constexpr int LEAF_REP = MPT_WIDE_LEAF_REP;
-    static constexpr bool AVOID_IN_LEAF = false;
-    static constexpr int SHADE_MIN = 0;
-    static constexpr int NODE_REP = 0;
-    static constexpr bool WIDE = true, QUANT = true, SIGNED_PLANES = false, LDS_MATS = false, OCT = true;
-    static constexpr bool ODD_IDS = false, T_SCALED = false;
-    const MptVec4 *onode, *tgeo;                       // tgeo: tfast8, the 48-byte records in the 8-wide tree's leaf order
-    DEV void node8(int i, MptVec4 &h0, MptVec4 &h1, MptVec4 &px, MptVec4 &py, MptVec4 &pz) const {
-        const char *base = (const char *)onode;
-        const unsigned o = (unsigned)i * 80u;            // (the host keeps the array below 2 GiB)
-        h0 = *(const MptVec4 *)(base + o); h1 = *(const MptVec4 *)(base + 16 + o);
-        px = *(const MptVec4 *)(base + 32 + o); py = *(const MptVec4 *)(base + 48 + o); pz = *(const MptVec4 *)(base + 64 + o);
-    }
-    DEV void tri(int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) const {
-        const MptVec4 *g = tgeo + (size_t)slot * 3;
-        g0 = g[0]; g1 = g[1]; g2 = g[2];
-    }
-};
-
-// LIFO of the 8-wide traversal: entries are PAIRS (a, b) -- a = first child or triangle | mask of the node's slots of that kind
-// << 24, b = the slots still to visit (internal: in met-order positions; leaves: bit 31 set) -- two words per level in LDS,
-// [level][lane] each, the (rare) levels beyond CAP in a per-lane strip of global memory like SpillStack's
-struct OctStack {
-    static constexpr int SENTINEL = 0x40000000;        // the b word of the bottom entry: traversal over
-    static constexpr bool ONE_TEST = false;
-    static constexpr int PLANE_OFF = 0;
-    static constexpr bool PEEK = false;
-    static constexpr bool SP_ADDR = false, ODD_IDS = false, T_SCALED = false;
-    static constexpr int SP_STEP = 1;
-#ifndef MPT_OCT_CAP
-#define MPT_OCT_CAP 14
-#endif
-    static constexpr int CAP = MPT_OCT_CAP, SPILL = 64 - CAP;   // 2 x 14 levels x 256 lanes x 4 B = 28 KiB of LDS: five workgroups per CU
-    int *base;                 // &lds[threadIdx.x]
-    int *spill;
-    unsigned lane_off;         // this lane's first word in the strips (2 x SPILL words per lane)
-    int sp;
-    DEV void put(int at, int a, int b) {
-        if (at < CAP) { base[at * MPT_BLOCK] = a; base[(CAP + at) * MPT_BLOCK] = b; }
-        else { spill[lane_off + 2u * (unsigned)(at - CAP)] = a; spill[lane_off + 2u * (unsigned)(at - CAP) + 1u] = b; }
-    }
-    DEV void get(int at, int &a, int &b) const {
-        if (at < CAP) { a = base[at * MPT_BLOCK]; b = base[(CAP + at) * MPT_BLOCK]; }
-        else { a = spill[lane_off + 2u * (unsigned)(at - CAP)]; b = spill[lane_off + 2u * (unsigned)(at - CAP) + 1u]; }
-    }
-    DEV void setb(int at, int b) {
-        if (at < CAP) base[(CAP + at) * MPT_BLOCK] = b;
-        else spill[lane_off + 2u * (unsigned)(at - CAP) + 1u] = b;
-    }
-    DEV void push(int v) { put(sp, 0, v); sp++; }      // (lane_start_ray: the sentinel)
-    DEV int pop() { sp--; return 0; }
-    DEV int peek(int) const { return 0; }
-};
-
 // scene records resident in the CU's LDS (small scenes): ds_read_b128 instead of divergent
 // global gathers -- one copy per CU, shared by the 16 waves of a 1024-lane workgroup
 typedef float mpt_f4 __attribute__((ext_vector_type(4)));
@@ -528,20 +409,18 @@ typedef __attribute__((address_space(3))) const char *LdsBytePtr;
 typedef __attribute__((address_space(3))) const unsigned char *LdsU8Ptr;
 #define MPT_LDS_MAT_VEC4 6      // float4 of a material record kept in LDS: p[0..15] and the derived terms d[0..7]
 
-// PRESCALED: the internal-node ids of the LDS copy (in the records and therefore on the stack) are the node's byte offset / 8, so
-// a NODE step forms its record address with one shift instead of a 32-bit integer multiply (quarter rate: four issue slots of the
-// ~50 a step has).  render_kernel_lds scales the ids while it copies the records (stride 72 -> id x 9 <= 32767: scenes that fit LDS do).
-template <bool PRESCALED>
-struct LdsSceneT {
+// The internal-node ids of the LDS copy (in the records and therefore on the stack) are the node's byte offset / 8, so a NODE
+// step forms its record address with one shift instead of a 32-bit integer multiply (quarter rate: four issue slots of the ~50 a
+// step has).  render_kernel_lds scales the ids while it copies the records (stride 72 -> id x 9 <= 32767: scenes that fit LDS do).
+struct LdsScene {
 #ifndef MPT_SHADE_MIN_LDS
 #define MPT_SHADE_MIN_LDS 24
 #endif
-    static constexpr bool PRESCALED_IDS = PRESCALED;
     static constexpr int LEAF_REP = MPT_LEAF_REP;
     static constexpr bool AVOID_IN_LEAF = false;
     static constexpr int NODE_REP = MPT_NODE_REP;
     static constexpr int SHADE_MIN = MPT_SHADE_MIN_LDS; // SHADE waits until this many lanes want it (render_kernel.hip trace_stream)
-    static constexpr bool WIDE = false, QUANT = false, SIGNED_PLANES = true, LDS_MATS = true, OCT = false;
+    static constexpr bool WIDE = false, QUANT = false, SIGNED_PLANES = true, LDS_MATS = true;
     static constexpr bool ODD_IDS = false, T_SCALED = false;
     LdsVec4Ptr fnode, tgeo;
     // The material records (parameters + derived terms, 96 B each, the default material last) and one byte per
@@ -549,9 +428,7 @@ struct LdsSceneT {
     // still on its way from L2, instead of gathering it from L2 after that record has arrived (it holds the id).
     LdsVec4Ptr mats;
     LdsU8Ptr mtl;
-    int nstride;               // bytes from one node record to the next (MPT_LDS_NODE_STRIDE; 64 where 72 does not fit)
-    int mat_last, mat_default; // LDS record mat_last is the default material = record mat_default of the global table
-                               // (the pooled kernel keeps only the records the model uses; else both are default_mtl)
+    int mat_last, mat_default; // LDS record mat_last is the default material = record mat_default of the global table (both default_mtl)
     // The slab planes of both children picked by the ray's direction signs instead of by min / max: a node
     // record holds {lo, lo, hi, hi} (child 0, child 1) per axis, so the entry planes of an axis are the 8 bytes at
     // offset 0 for a ray going up that axis and at offset 8 for one going down, and the exit planes are the
@@ -559,16 +436,12 @@ struct LdsSceneT {
     // and 12 v_min / v_max fewer per step.
     DEV void node_planes(int i, int ox, int oy, int oz, mpt_f2 &nx, mpt_f2 &fx, mpt_f2 &ny, mpt_f2 &fy,
                          mpt_f2 &nz, mpt_f2 &fz, mpt_f2 &ids) const {
-        LdsBytePtr nd = (LdsBytePtr)fnode + (PRESCALED ? (i << 3) : i * nstride);
+        LdsBytePtr nd = (LdsBytePtr)fnode + (i << 3);
         LdsBytePtr ax = nd + ox, ay = nd + oy, az = nd + oz;
         nx = *(LdsVec2Ptr)ax;        fx = *(LdsVec2Ptr)(nd + (ox ^ 8));
         ny = *(LdsVec2Ptr)(ay + 16); fy = *(LdsVec2Ptr)(nd + 16 + (oy ^ 8));
         nz = *(LdsVec2Ptr)(az + 32); fz = *(LdsVec2Ptr)(nd + 32 + (oz ^ 8));
         ids = *(LdsVec2Ptr)(nd + 48);
-    }
-    DEV void node(int i, MptVec4 &a, MptVec4 &b, MptVec4 &c, MptVec4 &d) const {
-        LdsVec4Ptr nd = fnode + i * 4;
-        a = lds_ld(nd); b = lds_ld(nd + 1); c = lds_ld(nd + 2); d = lds_ld(nd + 3);
     }
     DEV void tri(int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) const {
         // (`tgeo + slot * 3` is compiled into a 64-bit multiply-add, v_mad_u64_u32 -- gfx950 has no 32-bit integer mad -- for a 32-bit LDS
@@ -577,12 +450,6 @@ struct LdsSceneT {
         g0 = lds_ld(g); g1 = lds_ld(g + 1); g2 = lds_ld(g + 2);
     }
 };
-
-typedef LdsSceneT<false> LdsScene;       // (the pooled A/B kernel: a run-time stride)
-#ifndef MPT_LDS_PRESCALED
-#define MPT_LDS_PRESCALED 1
-#endif
-typedef LdsSceneT<MPT_LDS_PRESCALED != 0> LdsSceneP;
 
 // 16-bit LIFO for the LDS-resident kernel (node ids fit in int16 there), [level][lane of 1024]
 #define MPT_LDS_BLOCK 1024
@@ -606,16 +473,12 @@ struct Stack16 {
 // internal ids as byte offset / 8.  The entry planes of an axis are the 16 bytes at offset 0 for a ray going up the axis and at 16
 // for one going down, the exit planes the other 16: no decode, no min / max, no select -- what the 8-bit nodes of the gather
 // kernels pay 39 VALU instructions a step for, to save gathers this kernel does not make
-#ifndef MPT_LDS4_AVOID_IN_LEAF
-#define MPT_LDS4_AVOID_IN_LEAF 1   // the triangle a ray left from is filtered by the LEAF step (one compare) instead of by the NODE step (four)
-#endif
 struct LdsWideScene {
     static constexpr int LEAF_REP = MPT_LEAF_REP;
-    static constexpr bool PRESCALED_IDS = true;
-    static constexpr bool AVOID_IN_LEAF = MPT_LDS4_AVOID_IN_LEAF != 0;
+    static constexpr bool AVOID_IN_LEAF = true;        // the triangle a ray left from is filtered by the LEAF step (one compare) instead of by the NODE step (four)
     static constexpr int NODE_REP = MPT_LDS4_REP;
     static constexpr int SHADE_MIN = MPT_SHADE_MIN_LDS;
-    static constexpr bool WIDE = true, QUANT = false, SIGNED_PLANES = false, LDS_MATS = true, OCT = false;
+    static constexpr bool WIDE = true, QUANT = false, SIGNED_PLANES = false, LDS_MATS = true;
     // ids as the LDS copy of the node records holds them (render_kernel_lds4 rewrites them while it copies): a node's is its record's
     // byte offset in LDS -- the address itself, no shift -- and a leaf's (slot << 4) | 1; records are 16-byte aligned, so bit 0 tells
     // them apart with a full-rate v_and where the sign needed a shift or a sign extension (half rate on gfx950)
@@ -646,15 +509,12 @@ struct LdsWideScene {
 
 // its LIFO: 16-bit entries, [level][lane of 1024], as many levels as the tree can ask for (3 x depth + 2, the host checks): a
 // step's three pushes are plain stores, nothing spills
-#ifndef MPT_LDS4_PLANE_OFF
-#define MPT_LDS4_PLANE_OFF 0       // 16: the ray carries the offsets of its entry planes (three registers); 0: the step reads the signs off 1/d
-#endif
 struct Stack16W {
     static constexpr bool ODD_IDS = true;              // entries are ids as LdsWideScene holds them (16 bits, unsigned)
     static constexpr bool ONE_TEST = true;             // (render_kernel.hip lane_start_ray / stage_leaf)
     static constexpr int SENTINEL = 2;                 // the two low bits of an entry are the lane's next state: 0 a node (ST_NODE), 1 a leaf
                                                        // (ST_LEAF), 2 -- only this -- the bottom of the stack (ST_DONE)
-    static constexpr int PLANE_OFF = MPT_LDS4_PLANE_OFF;
+    static constexpr int PLANE_OFF = 0;                // (the step reads the entry planes off the signs of 1/d: no per-ray offsets to carry)
     static constexpr int CAP = 1 << 20, STRIDE = MPT_LDS_BLOCK;
     static constexpr bool NO_SPILL = true;
     typedef short entry_t;
@@ -680,22 +540,6 @@ struct Stack16W {
     DEV int sp_at(int level) const { return (int)(unsigned)(unsigned long long)(base + level * MPT_LDS_BLOCK); }
     DEV static void st(int sp, int v) { *(LdsShortPtr)(unsigned long long)(unsigned)sp = (short)v; }
     DEV static int ld(int sp) { return (int)*(LdsUShortPtr)(unsigned long long)(unsigned)sp; }
-};
-
-// the same LIFO for the tracer waves of the pooled kernel: [level][tracer lane], the lane count a launch parameter
-struct Stack16V {
-    static constexpr int SENTINEL = -32768;
-    static constexpr bool ONE_TEST = true;             // one depth question in the LEAF step for both kinds of ray (render_kernel.hip lane_start_ray / stage_leaf)
-    static constexpr int PLANE_OFF = 8;
-    LdsShortPtr base;          // &lds16[tracer lane]
-    int stride;                // tracer lanes of the workgroup (wave-uniform)
-    int sp;
-    DEV void push(int v) { base[sp * stride] = (short)v; sp++; }
-    DEV int pop() { sp--; return (int)base[sp * stride]; }
-    static constexpr bool PEEK = true;
-    DEV int peek(int at) const { return (int)base[at * stride]; }
-    static constexpr bool SP_ADDR = false, ODD_IDS = false, T_SCALED = false;
-    static constexpr int SP_STEP = 1;
 };
 
 #if MPT_STRICT

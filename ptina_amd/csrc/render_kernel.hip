@@ -17,9 +17,7 @@
 //     from HBM / L2 / Infinity Cache, per-lane int32 traversal stack in LDS, [level][lane].
 //   After the loop a wave that has run out of work finalises finished tiles of the film -- sum of the frames, resolve, the image's
 //     write-out -- while the others drain (finalise_tiles): a launch that has the GPU to itself needs no combine pass.
-//   render_kernel_wide: 4-wide nodes with 8-bit child boxes (the product path for scenes that do not fit LDS); render_kernel_oct
-//     (render_oct.h, -DMPT_WITH_OCT=1: `make oct`): 8-wide octant-ordered nodes, an A/B that lost 17-19 %, kept with its tests
-//     outside the product library.
+//   render_kernel_wide: 4-wide nodes with 8-bit child boxes (the product path for scenes that do not fit LDS).
 //   render_kernel_lds (scenes whose node + triangle records fit the CU's 160 KiB LDS): measured on
 //     MI355X the gather version spends its time in the vector L1 -- a wave's node fetch touches up to 64
 //     different cache lines per load instruction, four instructions per node -- so one persistent
@@ -32,13 +30,6 @@
 #include "film_ops.h"
 #include <atomic>
 
-#ifndef MPT_SPEC_POP
-#define MPT_SPEC_POP 1        // the stack entry a step may pop is read together with the step's node / triangle record
-#endif
-
-#ifndef MPT_ONE_START
-#define MPT_ONE_START 1       // one ray-start block per shading pass (0: each stage starts its own lanes' rays, as before)
-#endif
 #if MPT_STRICT
 #define MPT_SUFFIX(x) x##_strict
 #else
@@ -104,7 +95,7 @@ DEV void trace_pixel(const MptRenderParams &p, const TR &tr, int i, int j, int f
 // reference's (path.py:31-56).  Rays, samples and sums do not depend on the schedule: each sample's
 // radiance goes to p.partial[frame][column of the share][y] and the combine pass adds frames in order.
 enum { ST_NODE = 0, ST_LEAF = 1, ST_DONE = 2, ST_NEW = 3, ST_DEAD = 4,     // DONE: this lane's ray is finished
-       // inside one shading pass only (MPT_ONE_START): the lane's next ray starts in the pass's common block, from L.to --
+       // inside one shading pass only: the lane's next ray starts in the pass's common block, from L.to --
        // a closest-hit ray along L.prd (head of the path_trace loop first) | a shadow ray along L.td up to L.tbest
        ST_BOUNCE = 5, ST_SHADOW = 6 };
 
@@ -122,7 +113,7 @@ struct LaneState {
     V3 direct;                 // shadow ray in flight: candidate direct light, added if unoccluded
     // ray being traversed (closest: the path ray; shadow: hitpos -> light)
     V3 to, td, inv, oinv;
-    int offx, offy, offz;      // byte offset of the entry planes of each axis in a node record (LDS and wide kernels)
+    int offx, offy, offz;      // byte offset of the entry planes of each axis in a node record (binary LDS kernel: STACK::PLANE_OFF)
     float tbest;               // closest: best depth so far; shadow: li.dis, moved up one float where STACK::ONE_TEST; x t_scale while traversed (T_SCALED)
     int curr, sp, hidx;        // hidx: leaf slot of the hit so far, -1 = none (closest) / any occluder found (shadow); in the 4-wide LDS kernel
                                // curr / hidx hold ids as its LDS node records do (LdsWideScene::ODD_IDS) and sp is the LDS address of the
@@ -189,11 +180,6 @@ DEV void lane_draws(const MptRenderParams &p, LaneState &L, float *out) {
 #pragma unroll
         for (int t = 0; t < N; t++) {
             out[t] = P[k];
-#if MPT_X_DUP_P_LOADS
-            // A/B build: every Sobol load issued twice (same film): the slowdown bounds what the loads cost
-            float dup = __builtin_nontemporal_load(P + k);
-            out[t] = dup == out[t] ? out[t] : dup;
-#endif
             k = (k + 1 == dim) ? 0 : k + 1;
         }
         L.rng_k = k;
@@ -216,24 +202,14 @@ DEV void lane_draws(const MptRenderParams &p, LaneState &L, float *out) {
 // cdna_hip_programming.md Guideline 16, Pitfall 8 "ONE aligned 8-B store").  Every launch stores that way, finalising or not: a
 // wave-uniform choice between two store flavours in the shading pass cost the whole kernel 4 % (it is short of scalar registers).
 // Measured (MI355X, same box, three alternations, profiles/r05_ab_experiments.json): 2.603-2.613 ms per launch against 2.582-2.584
-// with the same entry behind ONE 16-byte sc1 store (-DMPT_SC1_STORES=16, round 4's shape, whose halves are only observed to land
-// together): the second store instruction costs 0.9 %, and buys a hand-off that rests on nothing but 64-bit atomicity.
-// (-DMPT_SC1_STORES=0: plain stores, an A/B build whose tail finalisation must stay off.)
-#ifndef MPT_SC1_STORES
-#define MPT_SC1_STORES 1
-#endif
+// with the same entry behind ONE 16-byte sc1 store (round 4's shape, whose halves are only observed to land together): the
+// second store instruction costs 0.9 %, and buys a hand-off that rests on nothing but 64-bit atomicity.
 DEV void store_sample(const MptRenderParams &p, int frame, int pix, V3 radiance) {
     MptVec4 *dst = p.partial + ((size_t)frame * (size_t)p.partial_stride + pix);
     const mpt_u4 v = slab_pack(radiance.x, radiance.y, radiance.z, p.slab_tag);
-#if MPT_SC1_STORES == 16
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory");
-#elif MPT_SC1_STORES
     unsigned long long *d64 = (unsigned long long *)dst;
     __hip_atomic_store(d64, ((unsigned long long)v.y << 32) | v.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(d64 + 1, ((unsigned long long)v.w << 32) | v.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    *(mpt_u4 *)dst = v;
-#endif
 }
 
 // the bottom entry of every ray's LIFO is a sentinel, so "pop" never needs an emptiness test:
@@ -271,30 +247,13 @@ DEV void lane_start_ray(LaneState &L, STACK &stk, V3 o, V3 d, float tmax, bool s
     L.st = ST_NODE;
 }
 
-// head of the path_trace loop, path.py:25-29: either the path is over or a closest-hit ray
-// starts from `ro` along L.prd
-template <bool COUNT, class STACK>
-DEV void lane_next_bounce(const MptRenderParams &p, LaneState &L, STACK &stk, V3 ro, Cnt &cnt) {
-    if (L.depth < 5 && any_gt0(L.throughput) && any_ne0(L.prd)) {
-        L.depth += 1;
-        if (COUNT) cnt.bounces++;
-        L.prd = normalized_unfused(L.prd);
-        lane_start_ray<COUNT>(L, stk, ro, L.prd, MPT_INF, false, cnt);
-        // lbvh.py:218,319: with fewer than two faces the root box is never written: no hit
-        if (p.n < 2) L.st = ST_DONE;
-    } else {
-        store_sample(p, L.frame, L.pix, L.result);                          // path.py:93, summed by combine
-        L.st = ST_NEW;
-    }
-}
-
 // The loop head alone (path.py:25): a lane about to bounce whose path is over stores its sample and waits for a new one
 DEV bool path_continues(const LaneState &L) { return L.depth < 5 && any_gt0(L.throughput) && any_ne0(L.prd); }
 DEV void lane_store_sample(const MptRenderParams &p, LaneState &L) {
     store_sample(p, L.frame, L.pix, L.result);                              // path.py:93, summed by combine
     L.st = ST_NEW;
 }
-// The one place of a shading pass where rays start (MPT_ONE_START): the lanes whose shadow ray just ended, the lanes that
+// The one place of a shading pass where rays start: the lanes whose shadow ray just ended, the lanes that
 // shaded and the lanes that took a new sample all come here, so the direction set-up (a normalisation, three reciprocals,
 // the stack reset) is issued once per pass at the width of all of them, not three times at a third each
 template <bool COUNT, class STACK>
@@ -325,10 +284,8 @@ DEV void stage_node(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
     float tn0, tn1;
     bool h0, h1;
     if (COUNT) { cnt.n_node++; cnt.n_box += 2; }
-#if MPT_SPEC_POP
     int spec = 0;
     if constexpr (STACK::PEEK) spec = stk.peek(L.sp - 1);      // (the sentinel sits at level 0: sp >= 1 while a ray is traversed)
-#endif
     if constexpr (SCENE::SIGNED_PLANES) {
         mpt_f2 nx, fx, ny, fy, nz, fz, ids;
         sc.node_planes(L.curr, L.offx, L.offy, L.offz, nx, fx, ny, fy, nz, fz, ids);
@@ -355,7 +312,6 @@ DEV void stage_node(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
     bool swap = tn1 < tn0;
     int nearid = swap ? id1 : id0, farid = swap ? id0 : id1;
     int next = h0 ? (h1 ? nearid : id0) : id1;
-#if MPT_SPEC_POP
     if constexpr (STACK::PEEK) {
         // the entry a pop would return was asked for with the node record (spec, below the function's head): a step that
         // pops does not wait a second LDS round trip behind the box tests.  Push (both hit) and pop (both missed) exclude
@@ -364,9 +320,7 @@ DEV void stage_node(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
         if (h0 && h1) { stk.sp = sp; stk.push(farid); sp++; }
         if (!(h0 || h1)) { next = spec; sp--; }
         L.sp = sp;
-    } else
-#endif
-    {
+    } else {
         stk.sp = L.sp;
         if (h0 && h1) stk.push(farid);
         if (!(h0 || h1)) next = stk.pop();
@@ -394,9 +348,6 @@ DEV float exit_min(float a, float b, float c, float tbest) { return exit_min_asm
 // record, the children that are hit sorted
 // by entry distance (a five-comparator network on (distance bits, id) pairs; a miss sorts last), the nearest
 // taken next and the others pushed farthest first.
-#ifndef MPT_SORT_PACKED
-#define MPT_SORT_PACKED 1     // the 4-wide step of the LDS-resident kernel sorts (distance bits | 16-bit id) words (0: (key, id) pairs)
-#endif
 template <bool COUNT, class SCENE, class STACK>
 DEV void stage_node4(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
     int id0, id1, id2, id3;
@@ -434,9 +385,8 @@ DEV void stage_node4(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
 #undef MPT_UB
     } else {
         MptVec4 nx, fx, ny, fy, nz, fz, idv;
-        if constexpr (STACK::PLANE_OFF != 0) sc.node4(L.curr, L.offx, L.offy, L.offz, nx, fx, ny, fy, nz, fz, idv);     // (per-ray constants)
-        else sc.node4(L.curr, __float_as_int(L.inv.x) < 0 ? 16 : 0, __float_as_int(L.inv.y) < 0 ? 16 : 0, __float_as_int(L.inv.z) < 0 ? 16 : 0,
-                      nx, fx, ny, fy, nz, fz, idv);
+        sc.node4(L.curr, __float_as_int(L.inv.x) < 0 ? 16 : 0, __float_as_int(L.inv.y) < 0 ? 16 : 0, __float_as_int(L.inv.z) < 0 ? 16 : 0,
+                 nx, fx, ny, fy, nz, fz, idv);
         id0 = __float_as_int(idv.x); id1 = __float_as_int(idv.y); id2 = __float_as_int(idv.z); id3 = __float_as_int(idv.w);
 #define MPT_SLAB(c, tn, h)                                                                                              \
         tn = fmaxf(fmaxf(__builtin_fmaf(nx.c, L.inv.x, -L.oinv.x), __builtin_fmaf(ny.c, L.inv.y, -L.oinv.y)),            \
@@ -451,12 +401,11 @@ DEV void stage_node4(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
     // left from, lbvh.py:329) gets the largest key
     const unsigned MISS = 0xffffffffu;
     unsigned k0, k1, k2, k3;
-    if constexpr (MPT_SORT_PACKED && sizeof(typename STACK::entry_t) == 2) {
+    if constexpr (sizeof(typename STACK::entry_t) == 2) {
         // 16-bit ids (the LDS-resident kernel): the upper half of the distance's bits over the id is ONE word that sorts with
         // v_min_u32 / v_max_u32 -- ten instructions instead of the 25 of five compare-and-swaps on (key, id) pairs; distances that
         // agree in their first 8 mantissa bits are met in id order, which costs a step now and then and never a hit (the
         // order only decides what is looked at first)
-        if constexpr (!SCENE::AVOID_IN_LEAF) { h0 = h0 && id0 != L.navoid; h1 = h1 && id1 != L.navoid; h2 = h2 && id2 != L.navoid; h3 = h3 && id3 != L.navoid; }
         k0 = h0 ? __builtin_amdgcn_perm((unsigned)__float_as_int(t0), (unsigned)id0, 0x07060100u) : MISS;
         k1 = h1 ? __builtin_amdgcn_perm((unsigned)__float_as_int(t1), (unsigned)id1, 0x07060100u) : MISS;
         k2 = h2 ? __builtin_amdgcn_perm((unsigned)__float_as_int(t2), (unsigned)id2, 0x07060100u) : MISS;
@@ -468,7 +417,6 @@ DEV void stage_node4(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
         id0 = STACK::ODD_IDS ? (int)(k0 & 0xffffu) : (int)(short)(k0 & 0xffffu);
         id1 = (int)k1; id2 = (int)k2; id3 = (int)k3;                                         // (the pushes store the low halves)
     } else {
-        if constexpr (!SCENE::AVOID_IN_LEAF) { h0 = h0 && id0 != L.navoid; h1 = h1 && id1 != L.navoid; h2 = h2 && id2 != L.navoid; h3 = h3 && id3 != L.navoid; }
         k0 = h0 ? (unsigned)__float_as_int(t0) : MISS;
         k1 = h1 ? (unsigned)__float_as_int(t1) : MISS;
         k2 = h2 ? (unsigned)__float_as_int(t2) : MISS;
@@ -510,21 +458,15 @@ DEV void stage_node4(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
     L.st = classify<STACK>(next);
 }
 
-#if MPT_WITH_OCT
-#include "render_oct.h"      // stage_node8 / stage_leaf8 / oct_next: the 8-wide octant-ordered tree's steps (A/B build)
-#endif
-
 template <bool COUNT, class SCENE, class STACK>
 DEV void stage_leaf(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
     int slot = SCENE::ODD_IDS ? L.curr : ~L.curr;      // (ODD_IDS: the leaf's id stands for the slot until a shading pass needs it)
     bool stop = false;
     // (the counters count the reference's work: it never tests the triangle a ray left from, lbvh.py:329)
     if (COUNT) cnt.n_tri += (SCENE::AVOID_IN_LEAF && L.curr == L.navoid) ? 0u : 1u;
-#if MPT_SPEC_POP
     int spec = 0;
     if constexpr (STACK::SP_ADDR) spec = STACK::ld(L.sp - STACK::SP_STEP + STACK::SP_BIAS);
     else if constexpr (STACK::PEEK) spec = stk.peek(L.sp - 1);      // a leaf step always pops: asked for with the triangle record
-#endif
     MptVec4 g0, g1, g2;
     sc.tri(slot, g0, g1, g2);
     float dd, su, sv;
@@ -544,15 +486,12 @@ DEV void stage_leaf(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
         }
     }
     int next;
-#if MPT_SPEC_POP
     if constexpr (STACK::PEEK) {
 #if MPT_X_LEAFPAIRS      // diagnostic build (counting kernels): how often the entry under a leaf is another leaf (what a two-triangle LEAF step could take along)
         if (COUNT) { cnt.pl_trips++; if (classify<STACK>(spec) == ST_LEAF && !stop) cnt.pl_local++; }
 #endif
         next = spec; L.sp = L.sp - (STACK::SP_ADDR ? STACK::SP_STEP : 1);
-    } else
-#endif
-    {
+    } else {
         stk.sp = L.sp;
         next = stk.pop();
         L.sp = stk.sp;
@@ -561,18 +500,9 @@ DEV void stage_leaf(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
     L.st = stop ? ST_DONE : classify<STACK>(next);
 }
 
-// a shadow ray has finished: add the candidate direct light if nothing was hit (path.py:51,56),
-// then the next bounce starts from hitpos (= the shadow ray's origin), path.py:60
-template <bool COUNT, class STACK>
-DEV void stage_shadow_done(const MptRenderParams &p, LaneState &L, STACK &stk, Cnt &cnt) {
-    if (L.hidx < 0) L.result = L.result + L.direct;
-    lane_next_bounce<COUNT>(p, L, stk, L.to, cnt);
-}
-
 // path.py:31-62 for one bounce.  On entry L.to / L.prd are the path ray r.o / r.d and
 // (L.hidx >= 0, L.tbest, L.hidx, L.hu, L.hv) the closest hit.  shade_core is the bounce itself; what follows it --
-// a shadow ray from hitpos towards the sampled light, or the next bounce from hitpos -- is the caller's: the wave that
-// shaded starts it in the same lane (stage_shade), or hands it to another wave through the workgroup's ray pool.
+// a shadow ray from hitpos towards the sampled light, or the next bounce from hitpos -- is the caller's (trace_stream).
 enum { SH_END = 0, SH_BOUNCE = 1, SH_SHADOW = 2 };
 // Diagnostic build -DMPT_X_STAMPS=2 (counting kernels): shader-clock cycles (units of 16) of the segments of SHADE, added by the
 // first active lane into the pl_* counters: lights hit | geometry + material (waits for the gathers) | light sample |
@@ -651,26 +581,14 @@ DEV int shade_core(const MptRenderParams &p, const SCENE &sc, LaneState &L, Cnt 
     // an exact elimination (x + 0 == x; a NaN is != 0 and still takes the ray).  On the benchmark scene that is every
     // surface that faces away from the light: 3.5 % of all rays, 8 % of the node fetches (they are the long ones), -5 % time.
     // Option "skip_dark" = 0 traces them like the reference does.  In the strict build (no contraction) the two settings give the
-    // same film bit for bit (tested); in this build a handful of pixels differ in the last bits, because the bounce that follows
-    // a skipped ray starts from another inlined copy of lane_next_bounce than the one behind stage_shadow_done, and
-    // -ffp-contract=fast fuses normalized()'s multiply-adds differently in the two copies.
+    // same film bit for bit (tested); in this build a handful of pixels may differ in the last bits: -ffp-contract=fast is
+    // free to fuse the multiply-adds of the two paths' ray set-up differently.
     if (want_shadow && p.n >= 2 && (p.skip_dark == 0 || any_ne0(L.direct))) {
         sdir = li.dir; sdis = li.dis;
         return SH_SHADOW;
     }
     if (want_shadow && p.n < 2) { L.result = L.result + L.direct; if (COUNT) cnt.rays++; }   // no geometry to occlude
     return SH_BOUNCE;
-}
-
-template <bool COUNT, class SCENE, class STACK>
-DEV void stage_shade(const MptRenderParams &p, const SCENE &sc, LaneState &L, STACK &stk, Cnt &cnt) {
-    V3 hitpos, sdir;
-    float sdis;
-    const int next = shade_core<COUNT>(p, sc, L, cnt, hitpos, sdir, sdis);
-    MPT_SEG_BEGIN
-    if (next == SH_SHADOW) lane_start_ray<COUNT>(L, stk, hitpos, sdir, sdis, true, cnt);
-    else lane_next_bounce<COUNT>(p, L, stk, hitpos, cnt);                    // SH_END: depth is 5, the sample is stored
-    MPT_SEG(pl_sidle)
 }
 
 // do_render up to the camera ray, path.py:82-90, in two halves.  A wave prepares the primary rays of the next 64
@@ -745,20 +663,6 @@ DEV int wave_count32(bool pred) {            // a count that stays on the scalar
     int n;                                   // one s_bcnt1_i32_b64, written out: the compiler's own 64-bit popcount ends up compared on the VALU, and
     asm("s_bcnt1_i32_b64 %0, %1" : "=s"(n) : "s"(m) : "scc");     // two 32-bit ones are three scalar instructions in the chain in front of every step
     return n;                                // (MI355X: 2.462 / 2.464 / 2.463 ms per launch -> 2.449 / 2.453 / 2.460; the gather kernels +0.8 %)
-}
-
-// (SCENE::OCT is only ever true in the A/B build with the 8-wide kernel: render_oct.h)
-template <bool COUNT, class SCENE, class STACK>
-DEV void stage_node8_if_built(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
-#if MPT_WITH_OCT
-    stage_node8<COUNT>(sc, stk, L, cnt);
-#endif
-}
-template <bool COUNT, class SCENE, class STACK>
-DEV void stage_leaf8_if_built(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
-#if MPT_WITH_OCT
-    stage_leaf8<COUNT>(sc, stk, L, cnt);
-#endif
 }
 
 // Work items = (8x8 pixel tile, chunk of frames), tile-major, split into 8 contiguous ranges with
@@ -856,8 +760,7 @@ DEV void trace_stream(const MptRenderParams &p, const SCENE &sc, STACK stk, Work
                 if (COUNT && p.lane_hist) lane_hist_add(p, 0, L.st == ST_NODE, L.depth, L.shadow);
                 if constexpr (!STACK::ODD_IDS) { if (COUNT && p.lane_hist) node_id_hist_add(p, L.st == ST_NODE, L.curr); }
                 if (L.st == ST_NODE) {
-                    if constexpr (SCENE::OCT) stage_node8_if_built<COUNT>(sc, stk, L, cnt);
-                    else if constexpr (SCENE::WIDE) stage_node4<COUNT>(sc, stk, L, cnt);
+                    if constexpr (SCENE::WIDE) stage_node4<COUNT>(sc, stk, L, cnt);
                     else stage_node<COUNT>(sc, stk, L, cnt);
                 }
                 // further steps for the lanes that are still at a node, without counting again: the three ballots
@@ -871,8 +774,7 @@ DEV void trace_stream(const MptRenderParams &p, const SCENE &sc, STACK stk, Work
                     if (COUNT && p.lane_hist) lane_hist_add(p, 0, L.st == ST_NODE, L.depth, L.shadow);
                     if constexpr (!STACK::ODD_IDS) { if (COUNT && p.lane_hist) node_id_hist_add(p, L.st == ST_NODE, L.curr); }
                     if (L.st == ST_NODE) {
-                        if constexpr (SCENE::OCT) stage_node8_if_built<COUNT>(sc, stk, L, cnt);
-                        else if constexpr (SCENE::WIDE) stage_node4<COUNT>(sc, stk, L, cnt);
+                        if constexpr (SCENE::WIDE) stage_node4<COUNT>(sc, stk, L, cnt);
                         else stage_node<COUNT>(sc, stk, L, cnt);
                     }
                 }
@@ -880,25 +782,18 @@ DEV void trace_stream(const MptRenderParams &p, const SCENE &sc, STACK stk, Work
             } else {
                 if (COUNT && (threadIdx.x & 63) == 0) cnt.it_leaf++;
                 if (COUNT && p.lane_hist) lane_hist_add(p, 1, L.st == ST_LEAF, L.depth, L.shadow);
-                if (L.st == ST_LEAF) {
-                    if constexpr (SCENE::OCT) stage_leaf8_if_built<COUNT>(sc, stk, L, cnt);
-                    else stage_leaf<COUNT>(sc, stk, L, cnt);
-                }
+                if (L.st == ST_LEAF) stage_leaf<COUNT>(sc, stk, L, cnt);
 #pragma unroll
                 for (int rep = 0; rep < SCENE::LEAF_REP; rep++) {
                     if (__ballot(L.st == ST_LEAF) == 0ull) break;
                     if (COUNT && (threadIdx.x & 63) == 0) cnt.it_leaf++;
                     if (COUNT && p.lane_hist) lane_hist_add(p, 1, L.st == ST_LEAF, L.depth, L.shadow);
-                    if (L.st == ST_LEAF) {
-                        if constexpr (SCENE::OCT) stage_leaf8_if_built<COUNT>(sc, stk, L, cnt);
-                        else stage_leaf<COUNT>(sc, stk, L, cnt);
-                    }
+                    if (L.st == ST_LEAF) stage_leaf<COUNT>(sc, stk, L, cnt);
                 }
                 MPT_STAMP_END(acc_leaf)
             }
         }
         // ---- shading mode
-#if MPT_ONE_START
         bool shade_now = wave_count(L.st == ST_DONE && !L.shadow) != 0;
         if constexpr (SCENE::SHADE_MIN > 0) {
             // SHADE costs a wave the same whatever the number of lanes in it (8 400 cycles; a NODE step 575): with fewer than
@@ -942,19 +837,6 @@ DEV void trace_stream(const MptRenderParams &p, const SCENE &sc, STACK stk, Work
             if (L.st == ST_BOUNCE && !path_continues(L)) lane_store_sample(p, L);   // path.py:25,93: these lanes take a new sample below
             MPT_STAMP_END(acc_sdone)
         }
-#else
-        if (wave_count(L.st == ST_DONE && L.shadow) != 0) {
-            MPT_STAMP_BEGIN
-            if (L.st == ST_DONE && L.shadow) stage_shadow_done<COUNT>(p, L, stk, cnt);
-            MPT_STAMP_END(acc_sdone)
-        }
-        if (wave_count(L.st == ST_DONE && !L.shadow) != 0) {
-            if (COUNT && (threadIdx.x & 63) == 0) cnt.it_shade++;
-            MPT_STAMP_BEGIN
-            if (L.st == ST_DONE && !L.shadow) stage_shade<COUNT>(p, sc, L, stk, cnt);
-            MPT_STAMP_END(acc_shade)
-        }
-#endif
         MPT_STAMP_BEGIN
         unsigned long long m_new = __ballot(L.st == ST_NEW);
         if (m_new != 0ull) {
@@ -1027,13 +909,9 @@ DEV void trace_stream(const MptRenderParams &p, const SCENE &sc, STACK stk, Work
                     L.navoid = 0; L.depth = 0;
                     L.result = v3s(0.0f); L.throughput = v3s(1.0f); L.last_brdf_pdf = 0.0f;
                     if (COUNT) { cnt.samples++; cnt.n_draws += 2; }
-#if MPT_ONE_START
                     L.to = ro;
                     L.st = ST_BOUNCE;
                     if (!path_continues(L)) lane_store_sample(p, L);          // (a camera ray of zero length: path.py:25)
-#else
-                    lane_next_bounce<COUNT>(p, L, stk, ro, cnt);
-#endif
                 }
                 // NEW lanes beyond the pool's end keep waiting: the next pass prepares the next 64 samples
                 next = min(next + (int)__builtin_popcountll(m_new), pool_end);
@@ -1043,13 +921,11 @@ DEV void trace_stream(const MptRenderParams &p, const SCENE &sc, STACK stk, Work
             }
         }
         MPT_STAMP_END(acc_new)
-#if MPT_ONE_START
         {
             MPT_STAMP_BEGIN
             if (L.st == ST_BOUNCE || L.st == ST_SHADOW) lane_begin_ray<COUNT>(p, L, stk, cnt);
             MPT_STAMP_END(acc_sdone)
         }
-#endif
 #if MPT_X_TIMELINE2
         if (!more) tl_passes++;
         if (ndead == 64 && tl && (threadIdx.x & 63) == 0) tl[7] = (unsigned long long)tl_passes;
@@ -1092,12 +968,9 @@ DEV mpt_u4 slab_load_sc1(const MptVec4 *frame_base, unsigned frame_bytes, unsign
 #define MPT_FIN_GROUP_LDS 8       // slab loads in flight per lane: the LDS-resident kernel has 128 VGPRs to lend ...
 #define MPT_FIN_GROUP_GATHER 6    // ... the gather kernels 96 (with eight the function needs 102 and they would lose their fifth wave per SIMD)
 #endif
-#ifndef MPT_FIN_INLINE
-// 0: out of line.  Inlined into the render kernels the finalisation moved their register allocation and the traversal loop ran
+// Out of line: inlined into the render kernels the finalisation moved their register allocation and the traversal loop ran
 // 3 % slower (MI355X, same box: 3.21 against 3.13 ms per launch, profiles/r04_ab_experiments.json); as a function of its own it
 // leaves them alone, at the price of its registers counting for every kernel that calls it (MPT_FIN_GROUP_*).
-#define MPT_FIN_INLINE 0
-#endif
 // what finalise_tiles reads of the launch parameters.  Out of line, its arguments arrive in vector registers: the ones a buffer
 // descriptor is made of are made scalar again (readfirstlane; they are wave-uniform)
 struct FinArgs {
@@ -1114,11 +987,7 @@ template <class T> DEV T *uniform_p(T *ptr) {
 }
 // (individual parameters, not a struct by value: that one would travel through scratch memory)
 template <int GROUP>
-#if MPT_FIN_INLINE
-DEV int finalise_tiles_impl(
-#else
 __device__ __attribute__((noinline)) int finalise_tiles_impl(
-#endif
         MptVec4 *a_partial, MptVec4 *a_film0, MptVec4 *a_image_out, unsigned int *a_fin_counter, unsigned int *a_watchdog,
         int a_tws, int a_ths, int a_ny, int a_nitems, int a_nchunks, int a_nframes, int a_partial_stride, int a_stripe_w,
         int a_stripe_pitch, int a_x0, int a_x1, unsigned a_slab_tag) {
@@ -1127,10 +996,8 @@ __device__ __attribute__((noinline)) int finalise_tiles_impl(
     p.tile_w_shift = a_tws; p.tile_h_shift = a_ths; p.ny = a_ny; p.nitems = a_nitems; p.nchunks = a_nchunks; p.nframes = a_nframes;
     p.partial_stride = a_partial_stride; p.stripe_w = a_stripe_w; p.stripe_pitch = a_stripe_pitch; p.x0 = a_x0; p.x1 = a_x1;
     p.slab_tag = a_slab_tag;
-#if !MPT_FIN_INLINE
     p.partial = uniform_p(p.partial); p.partial_stride = uniform_i(p.partial_stride); p.nframes = uniform_i(p.nframes);
     p.tile_w_shift = uniform_i(p.tile_w_shift); p.tile_h_shift = uniform_i(p.tile_h_shift);
-#endif
     const int lane = threadIdx.x & 63;
     const int tws = p.tile_w_shift, ths = p.tile_h_shift, tps = tws + ths;
     const int t8y = (p.ny + (1 << ths) - 1) >> ths;
@@ -1187,10 +1054,9 @@ __device__ __attribute__((noinline)) int finalise_tiles_impl(
     return done;
 }
 
-// GROUP = slab loads in flight per lane: what the calling kernel's register budget allows (see MPT_FIN_INLINE)
+// GROUP = slab loads in flight per lane: what the calling kernel's register budget allows (see finalise_tiles_impl)
 template <int GROUP>
 DEV int finalise_tiles(const MptRenderParams &p) {
-#if MPT_FIN_INLINE >= 0          // (-1: A/B build without the call: the render kernels as they were before the tail finalisation)
     // In a workgroup of three or four waves per SIMD only the younger two finalise.  The hardware issues the oldest wave of a
     // SIMD first, so the old waves finish tracing first -- and, finalising, stayed in front of the waves still tracing behind
     // them: with all four at it the launch took 3.15 ms, with the younger two 3.12 (the combine pass after the launch: 3.10 + 0.1;
@@ -1202,7 +1068,6 @@ DEV int finalise_tiles(const MptRenderParams &p) {
     if (p.fin_counter)
         return finalise_tiles_impl<GROUP>(p.partial, p.film0, p.image_out, p.fin_counter, p.watchdog, p.tile_w_shift, p.tile_h_shift, p.ny,
                                           p.nitems, p.nchunks, p.nframes, p.partial_stride, p.stripe_w, p.stripe_pitch, p.x0, p.x1, p.slab_tag);
-#endif
     return 0;
 }
 #endif
@@ -1264,12 +1129,6 @@ __global__ __launch_bounds__(MPT_BLOCK, MPT_WIDE_WAVES) void render_kernel_wide(
     WorkQueue wq; wq.ctr = p.work_counter; wq.nitems = p.nitems; wq.q0 = blockIdx.x & 7; wq.qoff = 0;
     if constexpr (QUANT) {
         QuantScene sc; sc.qnode = p.qnode; sc.tgeo = p.tfast;
-#if MPT_X_TOPCACHE
-        __shared__ __attribute__((aligned(16))) float s_top[MPT_X_TOPCACHE * 16];
-        for (int k = threadIdx.x; k < min(p.nwide, MPT_X_TOPCACHE) * 4; k += MPT_BLOCK) ((MptVec4 *)s_top)[k] = p.qnode[k];
-        __syncthreads();
-        sc.top = (__attribute__((address_space(3))) const QuantScene::top_f4 *)(void *)s_top;
-#endif
         trace_stream<COUNT>(p, sc, stk, wq, cnt);
     } else {
         WideScene sc; sc.wnode = p.wnode; sc.tgeo = p.tfast;
@@ -1293,7 +1152,7 @@ __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds(const MptRend
     {   // one copy of the scene per CU: coalesced 16-B loads, ds_write_b128
         for (int k = threadIdx.x; k < (p.n - 1) * 4; k += blockDim.x) {          // 8-byte stores: the records are 8-byte aligned
             MptVec4 v = p.fnode[k];
-            if (LdsSceneP::PRESCALED_IDS && (k & 3) == 3) {                        // {id0, id1, -, -}: internal ids become byte offset / 8
+            if ((k & 3) == 3) {                        // {id0, id1, -, -}: internal ids become byte offset / 8
                 const int i0 = __float_as_int(v.x), i1 = __float_as_int(v.y);
                 v.x = __int_as_float(i0 >= 0 ? i0 * (MPT_LDS_NODE_STRIDE / 8) : i0);
                 v.y = __int_as_float(i1 >= 0 ? i1 * (MPT_LDS_NODE_STRIDE / 8) : i1);
@@ -1315,12 +1174,11 @@ __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds(const MptRend
     __syncthreads();
     if (tl && (threadIdx.x & 63) == 0) tl[1] = wall_clock64();
 
-    LdsSceneP sc;
+    LdsScene sc;
     sc.fnode = (LdsVec4Ptr)(void *)smem;
     sc.tgeo = (LdsVec4Ptr)(void *)(smem + nnode4);
     sc.mats = (LdsVec4Ptr)(void *)(smem + nnode4 + ntri4);
     sc.mtl = (LdsU8Ptr)(void *)(smem + nnode4 + ntri4 + nmat4);
-    sc.nstride = MPT_LDS_NODE_STRIDE;
     sc.mat_last = p.default_mtl; sc.mat_default = p.default_mtl;
     Stack16 stk;
     stk.base = (LdsShortPtr)(void *)(smem + nnode4 + ntri4 + nmat4 + nmtl4) + threadIdx.x;
@@ -1519,17 +1377,6 @@ MPT_KERNEL_API hipError_t mpt_launch_render_lds(const MptRenderParams *p, int gr
                                             hipStream_t stream) {
     return count ? launch_lds<true>(p, grid, block, lds_bytes, stream) : launch_lds<false>(p, grid, block, lds_bytes, stream);
 }
-#endif
-
-#if !MPT_STRICT && MPT_WITH_OCT
-#define MPT_OCT_KERNELS 1
-#include "render_oct.h"      // render_kernel_oct + its launchers (second pass over the header)
-#endif
-
-#if !MPT_STRICT && MPT_WITH_POOL
-// The pooled LDS kernel (waves specialised into tracers and shaders, paths traded through LDS pools) measured 15-50 % slower
-// than render_kernel_lds: it is an A/B build (make pool -> libmiptina_pool.so), not part of the product library
-#include "render_pool.h"
 #endif
 
 #if !MPT_STRICT

@@ -799,7 +799,6 @@ extern "C" int mpt_get_wide(mpt_ctx *c, float *wnode, float *qnode, int cap_node
 
 extern "C" int mpt_build_tree(mpt_ctx *c) {
     if (use(c)) return 1;
-    c->fnode_soa_valid = false;
     BuildClock clk(c);
     if (c->gpu_build ? build_tree_gpu(c, clk) : build_tree_host(c)) return 1;
     clk.mark(2);
@@ -817,8 +816,6 @@ extern "C" int mpt_build_tree(mpt_ctx *c) {
     clk.mark(3);
     if (make_wide(c)) return 1;
     clk.mark(4);
-    c->oct_nodes = 0; c->oct_depth = 0;
-    if (c->use_wide8 && c->tree_kind == 1) return make_oct8(c);     // option "wide8": the same tree 8-wide, octant-ordered (oct_build.cpp)
     return 0;
 }
 

@@ -591,29 +591,27 @@ def test_pipelined_wide_launches_keep_their_own_spill_strips(fresh, tmp_path):
     assert 'EQUAL' in r.stdout, r.stdout + r.stderr
 
 
-def test_pooled_lds_kernel_gives_the_same_film_bit_for_bit(fresh, tmp_path):
-    '''option "pool": the LDS-resident kernel with its waves specialised (tracer waves traverse, shader waves run the bounces
-    64 at a time) and paths migrating between lanes and waves through two LDS pools at every bounce.  Nothing observable may
-    depend on where a path ran: the unspecialised kernel's film up to the last bits (see below) and its work counters, for
-    ragged films, several batches, 1 to 5 shader waves, the benchmark scene and a scene with every kind of light and lobe
-    (with fewer shader waves more bounces are done by the tracers' own copy of the code, so even the shader count moves last bits)'''
-    # The pooled kernel is an A/B build of the library since round 4 (measured 15-50 % slower than the product kernel):
-    # libmiptina_pool.so (make -C ptina_amd/csrc pool; __graft_entry__.build() does), loaded by a process of its own
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, 'ptina_amd', 'libmiptina_pool.so')
-    assert os.path.exists(lib), 'build it with make -C ptina_amd/csrc pool (__graft_entry__.build() does)'
+def test_retired_kernel_options_are_refused(fresh):
+    '''the options of the retired A/B kernels and layouts -- "pool" / "pool_shaders" (the pooled LDS kernel), "wide8" (the 8-wide
+    octant-ordered tree and kernel) and "node_soa" (the SoA node layout) -- are refused loudly with any value instead of silently
+    running another kernel, and a context that was asked for them still renders the film it rendered before, bit for bit'''
     from ptina_amd.common import ctx, reset_all
-    _engine(None, scenes.scene_s34(), 16, 16, mode='fast')
-    with pytest.raises(RuntimeError, match='built without the pooled'):
-        ctx().set_option('pool', 1)                # the product library says so instead of silently running another kernel
-    reset_all()
-    r = subprocess.run([sys.executable, os.path.join(root, 'tests', 'pool_check_script.py'), root], env=dict(os.environ, MIPTINA_LIB=lib),
-                       capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert 'POOL-OK' in r.stdout
+    from ptina_amd.things import FilmTable
+
+    def film(ask):
+        eng = _engine(None, scenes.scene_s34(), 16, 16, mode='fast')
+        if ask:
+            for key in ('pool', 'pool_shaders', 'wide8', 'node_soa'):
+                for value in (1, 0):
+                    with pytest.raises(RuntimeError, match="unknown option '%s'" % key):
+                        ctx().set_option(key, value)
+        eng.render()
+        img = FilmTable().get_image().copy()
+        reset_all()
+        return img
+
+    want = film(False)
+    assert np.array_equal(film(True), want)
 
 
 def test_shadow_rays_that_cannot_matter_are_not_traced(fresh, oracle_mod):
@@ -1303,33 +1301,6 @@ def test_device_wide_collapse_equals_the_host_pass(fresh, name, kw):
         assert np.array_equal(np.sort(ids[ids > 0]), np.arange(1, nw))             # every wide node but the root has one parent
         leaves = ~ids[(ids < 0) & (ids != ~n)]
         assert np.array_equal(np.sort(leaves), np.arange(n))                       # every triangle in exactly one slot
-
-
-def test_octant_ordered_8wide_tree_and_kernel(fresh, oracle_mod, tmp_path):
-    '''option "wide8" (VERDICT r03 next #3): the fast tree collapsed 8-wide with octant-ordered child slots and 8-bit boxes
-    (oct_build.cpp), walked without a sort by render_kernel_oct.  Structure: every 8-wide node but the root is the child of
-    exactly one slot, internal children and leaf triangles are numbered consecutively in slot order, every triangle sits in
-    exactly one leaf slot (the permutation is one), every child's quantised box holds the boxes of everything below it (checked
-    from the leaves up), empty slots are inverted boxes.  Films: 60 000 random triangles and the benchmark scene forced off LDS,
-    against the 4-wide kernel (the same hits; equal-depth ties may be met in another order) and against the oracle.
-    Since round 5 the 8-wide tree and kernel are an A/B build of the library (measured 17-19 % slower than the 4-wide node):
-    libmiptina_oct.so (make -C ptina_amd/csrc oct; __graft_entry__.build() does), loaded by a process of its own
-    (tests/oct_check_script.py); the product library refuses the option loudly'''
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, 'ptina_amd', 'libmiptina_oct.so')
-    assert os.path.exists(lib), 'build it with make -C ptina_amd/csrc oct (__graft_entry__.build() does)'
-    from ptina_amd.common import ctx, reset_all
-    _engine(None, scenes.scene_s34(), 16, 16, mode='fast')
-    with pytest.raises(RuntimeError, match='built without the 8-wide'):
-        ctx().set_option('wide8', 1)
-    reset_all()
-    r = subprocess.run([sys.executable, os.path.join(root, 'tests', 'oct_check_script.py'), root], env=dict(os.environ, MIPTINA_LIB=lib),
-                       capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert 'OCT-OK' in r.stdout
 
 
 def _sah_tree(c, n, dev):
