@@ -192,6 +192,14 @@ int mpt_mlt_set_state(mpt_ctx *ctx, const float *X, const float *L, int iteratio
 int mpt_mlt_trace(mpt_ctx *ctx, const float *X, float *rgb, int n);
 /* HIP-event times (ms) of the chain kernels and of the splat passes launched since the last call, and their launch count */
 int mpt_mlt_kernel_time(mpt_ctx *ctx, double *chain_ms, double *splat_ms, int *launches);
+/* BruteEngine.render, ptina/engine/brute.py:24-26 x nframes : the walk of path_trace with no light sampling and no MIS (a light
+ * counts only when a bounce ray hits it; one random3 per bounce; loop head throughput > 1e-6), one sample per pixel and frame
+ * into film pass 0 with weight 1, on the Sobol sampler mpt_render and mpt_render_preview advance.  Launched at the call (not
+ * deferred), behind every frame and Metropolis iteration enqueued before it: all three add to the film in call order.  Honours
+ * mpt_set_slab / mpt_set_stripes as mpt_render_preview does.  For testing: see DESIGN.md section 3.8 */
+int mpt_render_brute(mpt_ctx *ctx, int nframes);
+/* HIP-event time (ms) of the brute-force kernels launched since the last call, and their launch count */
+int mpt_brute_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
 /* launch everything enqueued so far (does not wait) */
 int mpt_flush(mpt_ctx *ctx);
 /* worker.synchronize, ptina/worker.py:17-18 */

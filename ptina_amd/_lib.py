@@ -83,6 +83,8 @@ SIGNATURES = {
     'mpt_mlt_set_state': (_i, [_vp, _fp, _fp, _i]),
     'mpt_mlt_trace': (_i, [_vp, _fp, _fp, _i]),
     'mpt_mlt_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_render_brute': (_i, [_vp, _i]),
+    'mpt_brute_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
     'mpt_flush': (_i, [_vp]),
     'mpt_synchronize': (_i, [_vp]),
     'mpt_clear': (_i, [_vp, _i]),

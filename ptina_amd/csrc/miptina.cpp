@@ -203,6 +203,7 @@ extern "C" void mpt_destroy(mpt_ctx *c) {
     for (auto &pr : c->events) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
     for (auto &ev : c->event_pool) hipEventDestroy(ev);
     for (auto &ev : c->mlt_events) hipEventDestroy(ev);
+    for (auto &ev : c->brute_events) hipEventDestroy(ev);
     hipFree(c->mlt_X); hipFree(c->mlt_L); hipFree(c->mlt_bit); hipFree(c->mlt_keys); hipFree(c->mlt_keys2);
     hipFree(c->mlt_vals); hipFree(c->mlt_vals2); hipFree(c->mlt_tmp); hipFree(c->mlt_runs);
     for (int p = 0; p < 3; p++) hipFree(c->film[p]);
@@ -1257,6 +1258,60 @@ extern "C" int mpt_mlt_kernel_time(mpt_ctx *c, double *chain_ms, double *splat_m
     if (launches) *launches = (int)(c->mlt_events.size() / 3);
     for (auto e : c->mlt_events) c->event_pool.push_back(e);
     c->mlt_events.clear();
+    return 0;
+}
+
+// ------------------------------------------------------------------ brute-force engine (BruteEngine, engine/brute.py)
+// Launched at the call, on the main stream like the Metropolis passes: use() has flushed the PathEngine frames and Metropolis
+// iterations enqueued before (the main stream waits for their render streams), and the next PathEngine launch waits for
+// this one (main_dirty -> ev_main), so frames of all three engines add to film pass 0 in call order.
+extern "C" int mpt_render_brute(mpt_ctx *c, int nframes) {                     // brute.py:24-26
+    if (!c) return fail("null context");
+    if (nframes < 0) return fail("nframes must be >= 0");
+    if (c->nx <= 0) return fail("film size not set: call set_size() first");
+    if (!c->sV) return fail("sobol sampler not initialised");
+    if (!c->tree_valid) return fail("BVH not built: call build_tree() after load_model()");
+    if (use(c)) return 1;
+    while (nframes > 0) {
+        int B = std::min(nframes, (int)MPT_MAX_BATCH);
+        MptRenderParams p;
+        if (fill_params(c, p, B)) return 1;
+        if (sobol_advance(c, B, B)) return 1;
+        p.chunk = B; p.nchunks = 1;
+        const int stack = ((c->mode == MPT_MODE_STRICT ? c->tree_depth : c->fast_depth) + 2 <= 32) ? 32 : 64;
+        if (p.ntiles) {
+            hipEvent_t e0 = get_event(c), e1 = get_event(c);
+            HIP_TRY(hipEventRecord(e0, c->stream));
+            if (c->mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_brute_strict(&p, p.ntiles, stack, c->stream));
+            else HIP_TRY(mpt_launch_brute_fast(&p, p.ntiles, stack, c->stream));
+            HIP_TRY(hipEventRecord(e1, c->stream));
+            c->brute_events.push_back(e0); c->brute_events.push_back(e1);
+            if (c->brute_events.size() > 2 * 4096) {     // nobody asks for the times: keep the newest half
+                for (size_t q = 0; q < 2 * 2048; q++) c->event_pool.push_back(c->brute_events[q]);
+                c->brute_events.erase(c->brute_events.begin(), c->brute_events.begin() + 2 * 2048);
+            }
+            c->film_version++;       // pass 0 has changed: an early image of an earlier PathEngine launch is stale
+        }
+        nframes -= B;
+    }
+    c->main_dirty = true;            // the next PathEngine launch waits for these
+    return 0;
+}
+
+extern "C" int mpt_brute_kernel_time(mpt_ctx *c, double *ms, int *launches) {
+    if (use_ro(c)) return 1;
+    if (mpt_flush(c)) return 1;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    double total = 0;
+    for (size_t q = 0; q + 1 < c->brute_events.size(); q += 2) {
+        float t = 0;
+        HIP_TRY(hipEventElapsedTime(&t, c->brute_events[q], c->brute_events[q + 1]));
+        total += t;
+    }
+    if (ms) *ms = total;
+    if (launches) *launches = (int)(c->brute_events.size() / 2);
+    for (auto e : c->brute_events) c->event_pool.push_back(e);
+    c->brute_events.clear();
     return 0;
 }
 

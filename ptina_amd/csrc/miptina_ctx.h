@@ -36,6 +36,9 @@ MPT_KERNEL_API hipError_t mpt_launch_mlt_reset(float *X, float *L, int *bit, int
 MPT_KERNEL_API hipError_t mpt_mlt_sort_bytes(int n, int npix, size_t *bytes);
 MPT_KERNEL_API hipError_t mpt_launch_mlt_splat(MptVec4 *film, const unsigned *keys, const MptVec4 *vals, unsigned *keys2, MptVec4 *vals2,
                                                void *tmp, size_t tmp_bytes, unsigned *runs, int n, int npix, hipStream_t);
+// brute_kernel.hip: the brute-force engine's kernel (both builds)
+MPT_KERNEL_API hipError_t mpt_launch_brute_fast(const MptRenderParams *, int grid, int stack, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_launch_brute_strict(const MptRenderParams *, int grid, int stack, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_preview_fast(const MptRenderParams *, int grid, int stack, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_preview_strict(const MptRenderParams *, int grid, int stack, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_sobol_update(const int *X, int *Xout, const int *V, float *P, int dim, int rows, int time0,
@@ -201,6 +204,7 @@ struct mpt_ctx {
     void *mlt_tmp = nullptr;
     uint32_t *mlt_runs = nullptr;
     std::vector<hipEvent_t> mlt_events;                  // {chain start, chain end = splat start, splat end} per launch
+    std::vector<hipEvent_t> brute_events;                // brute-force engine: {kernel start, kernel end} per launch
     // command batching
     int pending = 0;
 

@@ -1,9 +1,29 @@
 // path_common.h -- one path of the unidirectional integrator (do_render + path_trace, engine/path.py:18-93) and the
 // per-lane tracer each build walks it with.  Shared by the PathEngine kernels (render_kernel.hip) and the Metropolis chain
 // kernel (mlt_kernel.hip): one definition of the path, so that a chain's path and a PathEngine sample given the same
-// draws are the same path.  Included once per translation unit, after pt_device.h; MPT_STRICT selects the build.
+// draws are the same path.  Also here: the brute-force engine's loop body (brute_step, engine/brute.py:29-60; brute_kernel.hip)
+// and the 16x16-tile pixel mapping of the one-lane-per-pixel kernels.
+// Included once per translation unit, after pt_device.h; MPT_STRICT selects the build.
 #pragma once
 #include "pt_device.h"
+
+// ---------------------------------------------------------------- one lane per pixel of a 16x16 tile (strict render, preview, brute)
+DEV int xcd_remap(int b, int nb) {
+    // blocks are dealt round-robin over the 8 XCDs: give XCD k the k-th contiguous run of work
+    int q = nb >> 3, r = nb & 7;
+    int xcd = b & 7, k = b >> 3;
+    return xcd * q + (xcd < r ? xcd : r) + k;
+}
+
+DEV bool tile_pixel(const MptRenderParams &p, int tile, int *pi, int *pj) {
+    int tx = tile / p.tiles_y, ty = tile - tx * p.tiles_y;
+    int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int tps_x = p.stripe_w / MPT_TILE, st = tx / tps_x;                       // stripe of this tile column
+    int i = p.x0 + st * p.stripe_pitch + (tx - st * tps_x) * MPT_TILE + (wave >> 1) * 8 + (lane >> 3);
+    int j = ty * MPT_TILE + (wave & 1) * 8 + (lane & 7);
+    *pi = i; *pj = j;
+    return i < p.x1 && j < p.ny;
+}
 
 
 #if MPT_STRICT
@@ -117,5 +137,42 @@ DEV bool path_step(const MptRenderParams &p, const TR &tr, PathState &s, Cnt &cn
     s.ro = hitpos;
     s.rd = brdf.outdir;
     s.last_brdf_pdf = brdf.pdf;
+    return false;
+}
+
+// one iteration of BruteEngine.trace's loop, brute.py:35-58; returns true when the path has ended.  path_trace without light
+// sampling: no LightPool().sample, no shadow ray, no MIS weight (a light counts only when a bounce ray hits it), ONE random3
+// per bounce, and the loop head compares the throughput with eps = 1e-6 (common.py:32) and does not look at r.d.
+// PathState's last_brdf_pdf is not used.
+template <bool COUNT, class TR>
+DEV bool brute_step(const MptRenderParams &p, const TR &tr, PathState &s, Cnt &cnt) {
+    const float eps = 1e-6f;
+    if (!(s.depth < 5 && (s.throughput.x > eps || s.throughput.y > eps || s.throughput.z > eps))) return true;   // brute.py:35
+    s.depth += 1;
+    if (COUNT) cnt.bounces++;
+
+    s.rd = normalized(s.rd);
+    Hit hit = tr.template closest<COUNT>(s.ro, s.rd, s.avoid, cnt);
+
+    LightHit lit = lights_hit(p, s.ro, s.rd);
+    if (lit.hit && (hit.hit == 0 || lit.dis < hit.depth))
+        s.result = s.result + s.throughput * lit.color;                      // brute.py:41-43
+
+    if (hit.hit == 0) {
+        s.result = s.result + s.throughput * world_at(p, s.rd);
+        return true;                                                         // break, brute.py:47
+    }
+    s.avoid = hit.index;
+    V3 hitpos, normal; Disney material;
+    get_geometries(p, hit, s.ro, s.rd, &hitpos, &normal, material);
+    if (COUNT) { cnt.n_shade++; cnt.n_draws += 3; }
+
+    float sign = -dot(s.rd, normal);                                         // brute.py:52-54
+    if (sign < 0.0f) normal = -normal;
+
+    BsdfSample brdf = disney_bounce(material, normal, sign, -s.rd, random3(s.rng));
+    s.throughput = s.throughput * brdf.color;
+    s.ro = hitpos;
+    s.rd = brdf.outdir;
     return false;
 }

@@ -36,13 +36,6 @@
 #define MPT_SUFFIX(x) x##_fast
 #endif
 
-DEV int xcd_remap(int b, int nb) {
-    // blocks are dealt round-robin over the 8 XCDs: give XCD k the k-th contiguous run of work
-    int q = nb >> 3, r = nb & 7;
-    int xcd = b & 7, k = b >> 3;
-    return xcd * q + (xcd < r ? xcd : r) + k;
-}
-
 #include "path_common.h"
 
 template <bool COUNT>
@@ -1073,16 +1066,6 @@ DEV int finalise_tiles(const MptRenderParams &p) {
 #endif
 
 // ---------------------------------------------------------------- gather kernel: 16x16 tile x chunk per workgroup
-DEV bool tile_pixel(const MptRenderParams &p, int tile, int *pi, int *pj) {
-    int tx = tile / p.tiles_y, ty = tile - tx * p.tiles_y;
-    int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int tps_x = p.stripe_w / MPT_TILE, st = tx / tps_x;                       // stripe of this tile column
-    int i = p.x0 + st * p.stripe_pitch + (tx - st * tps_x) * MPT_TILE + (wave >> 1) * 8 + (lane >> 3);
-    int j = ty * MPT_TILE + (wave & 1) * 8 + (lane & 7);
-    *pi = i; *pj = j;
-    return i < p.x1 && j < p.ny;
-}
-
 #if MPT_STRICT
 #define MPT_RENDER_BOUNDS __launch_bounds__(MPT_BLOCK)
 #else

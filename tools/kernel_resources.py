@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
 '''Prints VGPRs / AGPRs / SGPRs / scratch / occupancy / LDS of every kernel of the production render object
-(the compiler's own -Rpass-analysis=kernel-resource-usage remarks).
-usage: tools/kernel_resources.py [extra hipcc flags]'''
+(the compiler's own -Rpass-analysis=kernel-resource-usage remarks), or of another translation unit of csrc/.
+usage: tools/kernel_resources.py [source.hip] [extra hipcc flags]
+   e.g. tools/kernel_resources.py brute_kernel.hip
+        tools/kernel_resources.py brute_kernel.hip -UMPT_STRICT -DMPT_STRICT=1 -ffp-contract=off -fslp-vectorize   (the strict build)'''
 import os
 import re
 import subprocess
 import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'ptina_amd', 'csrc')
+SRC = ([a for a in sys.argv[1:] if a.endswith('.hip')] or ['render_kernel.hip'])[-1]
 cmd = ['/opt/rocm/bin/hipcc', '-c', '-O3', '-fPIC', '-std=c++17', '--offload-arch=gfx950', '-DMPT_STRICT=0',
-       '-ffp-contract=fast', '-fno-slp-vectorize', '-Rpass-analysis=kernel-resource-usage', *sys.argv[1:],
-       'render_kernel.hip', '-o', '/tmp/_kres.o']
+       '-ffp-contract=fast', '-fno-slp-vectorize', '-Rpass-analysis=kernel-resource-usage', *[a for a in sys.argv[1:] if not a.endswith('.hip')],
+       SRC, '-o', '/tmp/_kres.o']
 out = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True).stderr
 cur, rows = None, {}
 for line in out.splitlines():
