@@ -281,7 +281,17 @@ enum {
     MPT_UNIT_POWER_HEURISTIC = 18,/* engine/path.py:11-15           in: a, b                                 out: 1 */
     MPT_UNIT_WANGHASH = 19,       /* sampling/__init__.py:9-16      in: i32                                  out: i32 */
     MPT_UNIT_WANGHASH2 = 20,      /* sampling/__init__.py:20-23     in: i32, i32                             out: i32 */
-    MPT_UNIT_KINDS = 21
+    /* The kinds below read the context's SCENE (lights, images, materials, world light, camera) as the render kernels do,
+     * through the launch parameters; vectors: tests/golden/reference_scene_units.npz.  A kind whose rows name something the
+     * context does not hold (an image that is not loaded, a material id outside the table) fails with a message. */
+    MPT_UNIT_LIGHT_HIT = 21,      /* light/__init__.py:51-81        in: ro3, rd3                             out: hit, dis, pdf, color3 */
+    MPT_UNIT_LIGHT_SAMPLE = 22,   /* light/__init__.py:83-121       in: hitpos3, samp3                       out: dis, dir3, pdf, color3 */
+    MPT_UNIT_IMAGE_SAMPLE = 23,   /* image.py:137-148 + common.py:183-192  in: id (as a float), x, y         out: rgba */
+    MPT_UNIT_WORLD_AT = 24,       /* light/world.py:22-29           in: dir3                                 out: rgb */
+    MPT_UNIT_MATERIAL_GET = 25,   /* mtllib.py:30-38,79-95 + materials/disney.py:13-50  in: mtlid (as a float), tu, tv  out: 14 parameters, speccolor3, sheencolor3, alpha, clearcoatAlpha (22) */
+    MPT_UNIT_CAMERA_GENERATE = 26,/* camera.py:34-39                in: x, y                                 out: ro3, rd3 */
+    MPT_UNIT_FACE_SIDE = 27,      /* model.py:88-101                in: rd3, vn0 vn1 vn2, s, t (14)          out: the normal get_geometries returns, 1 if it flipped Face.normal; the shading record is packed by the door, not by mpt_load_model: only the flip is under test */
+    MPT_UNIT_KINDS = 28
 };
 int mpt_unit_eval(mpt_ctx *ctx, int kind, const void *in, int in_cols, void *out, int out_cols, int n);
 

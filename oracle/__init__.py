@@ -111,6 +111,12 @@ def load(f64=False):
     sig('orc_trace_pixel', None, vp, C.c_int, C.c_int, rp)
     sig('orc_camera_generate', None, vp, real, real, rp, rp)
     sig('orc_intersect', C.c_int, vp, rp, rp, C.c_int, rp)
+    sig('orc_unit_light_hit', None, vp, rp, rp, rp)
+    sig('orc_unit_light_sample', None, vp, rp, rp, rp)
+    sig('orc_unit_image_sample', C.c_int, vp, C.c_int, real, real, rp)
+    sig('orc_unit_world_at', C.c_int, vp, rp, rp)
+    sig('orc_unit_material_get', C.c_int, vp, C.c_int, real, real, rp)
+    sig('orc_unit_face_side', C.c_int, vp, C.c_int, real, real, rp, rp, rp)
     lib._real = real
     lib._np_real = np.float64 if f64 else np.float32
     _libs[key] = lib

@@ -1513,3 +1513,61 @@ void orc_unit_face_shading(const real vn[9], const real vt[6], real u, real v, r
                  &n, &tex[0], &tex[1]);
     nrm[0] = n.x; nrm[1] = n.y; nrm[2] = n.z;
 }
+
+/* ------------------------------------------------------------------ */
+/* unit exports: the functions that read the scene, one by one, on the context as orc_render reads it          */
+/* (tests/test_reference_scene_units_cpu.py; vectors of tests/golden/make_reference_scene_units_golden.py)     */
+
+void orc_unit_light_hit(orc_ctx *c, const real ro[3], const real rd[3], real out[6]) {   /* light/__init__.py:51-81 */
+    lighthit h = lights_hit(c, V3(ro[0], ro[1], ro[2]), V3(rd[0], rd[1], rd[2]));
+    out[0] = (real)h.hit; out[1] = h.dis; out[2] = h.pdf; out[3] = h.color.x; out[4] = h.color.y; out[5] = h.color.z;
+}
+
+void orc_unit_light_sample(orc_ctx *c, const real hitpos[3], const real samp[3], real out[8]) {   /* light/__init__.py:83-121 */
+    lightsample s = lights_sample(c, V3(hitpos[0], hitpos[1], hitpos[2]), V3(samp[0], samp[1], samp[2]));
+    out[0] = s.dis; out[1] = s.dir.x; out[2] = s.dir.y; out[3] = s.dir.z; out[4] = s.pdf;
+    out[5] = s.color.x; out[6] = s.color.y; out[7] = s.color.z;
+}
+
+int orc_unit_image_sample(orc_ctx *c, int id, real x, real y, real out[4]) {   /* image.py:137-148, common.py:183-192 */
+    if (id < 0 || id >= c->nimg) return -1;
+    v4 t = image_sample(c, id, x, y);
+    out[0] = t.x; out[1] = t.y; out[2] = t.z; out[3] = t.w;
+    return 0;
+}
+
+int orc_unit_world_at(orc_ctx *c, const real dir[3], real out[3]) {            /* light/world.py:22-29 */
+    if (c->wtex != -1 && (c->wtex < 0 || c->wtex >= c->nimg)) return -1;
+    v3 r = world_at(c, V3(dir[0], dir[1], dir[2]));
+    out[0] = r.x; out[1] = r.y; out[2] = r.z;
+    return 0;
+}
+
+/* mtllib.py:30-38,79-95 + disney.py:13-50: out = the 12 parameters (14 values), speccolor, sheencolor, alpha, clearcoatAlpha */
+int orc_unit_material_get(orc_ctx *c, int mtlid, real tu, real tv, real out[22]) {
+    if (mtlid < -1 || mtlid >= c->nmat) return -1;
+    disney m;
+    material_get(c, mtlid, tu, tv, &m);
+    const real v[22] = { m.basecolor.x, m.basecolor.y, m.basecolor.z, m.metallic, m.roughness, m.specular, m.specularTint,
+                         m.subsurface, m.sheen, m.sheenTint, m.clearcoat, m.clearcoatGloss, m.transmission, m.ior,
+                         m.speccolor.x, m.speccolor.y, m.speccolor.z, m.sheencolor.x, m.sheencolor.y, m.sheencolor.z,
+                         m.alpha, m.clearcoatAlpha };
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+/* model.py:88-101 on face `index` of the loaded model: out = the normal as get_geometries leaves it, then 1 if it is the
+ * flipped Face.normal, 0 if not */
+int orc_unit_face_side(orc_ctx *c, int index, real u, real v, const real ro[3], const real rd[3], real out[4]) {
+    if (index < 0 || index >= c->nfaces) return -1;
+    bvhhit hit; hit.hit = 1; hit.depth = (real)1; hit.index = index; hit.u = u; hit.v = v;
+    v3 hitpos, normal, plain;
+    disney m;
+    get_geometries(c, &hit, V3(ro[0], ro[1], ro[2]), V3(rd[0], rd[1], rd[2]), &hitpos, &normal, &m);
+    real tu, tv;
+    face_shading(vert_nrm(c, index * 3), vert_nrm(c, index * 3 + 1), vert_nrm(c, index * 3 + 2), c->vertices + (size_t)(index * 3) * 8 + 6,
+                 c->vertices + (size_t)(index * 3 + 1) * 8 + 6, c->vertices + (size_t)(index * 3 + 2) * 8 + 6, u, v, &plain, &tu, &tv);
+    out[0] = normal.x; out[1] = normal.y; out[2] = normal.z;
+    out[3] = vdot(plain, normal) < 0 ? (real)1 : (real)0;
+    return 0;
+}

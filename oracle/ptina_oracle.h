@@ -137,6 +137,22 @@ void orc_camera_generate(orc_ctx *c, orc_real x, orc_real y, orc_real o[3], orc_
 /* lbvh.py:314-347: returns hit; out = [depth, index, u, v] */
 int orc_intersect(orc_ctx *c, const orc_real o[3], const orc_real d[3], int avoid, orc_real out[4]);
 
+/* ---- the functions that read the scene, one by one, on the context as orc_render reads it (the functions orc_render
+ * calls, not copies; tests/test_reference_scene_units_cpu.py holds them to tests/golden/reference_scene_units.npz).
+ * The int ones return -1 for an id the context does not hold. ---- */
+/* light/__init__.py:51-81: out = hit, dis, pdf, color */
+void orc_unit_light_hit(orc_ctx *c, const orc_real ro[3], const orc_real rd[3], orc_real out[6]);
+/* light/__init__.py:83-121: out = dis, dir, pdf, color */
+void orc_unit_light_sample(orc_ctx *c, const orc_real hitpos[3], const orc_real samp[3], orc_real out[8]);
+/* image.py:137-148 + common.py:183-192 */
+int orc_unit_image_sample(orc_ctx *c, int id, orc_real x, orc_real y, orc_real out[4]);
+/* light/world.py:22-29 */
+int orc_unit_world_at(orc_ctx *c, const orc_real dir[3], orc_real out[3]);
+/* mtllib.py:30-38,79-95 + disney.py:13-50: out = the 12 parameters (14 values), speccolor, sheencolor, alpha, clearcoatAlpha */
+int orc_unit_material_get(orc_ctx *c, int mtlid, orc_real tu, orc_real tv, orc_real out[22]);
+/* model.py:88-101 on face `index` of the loaded model: out = the normal get_geometries returns, then 1 if it was flipped */
+int orc_unit_face_side(orc_ctx *c, int index, orc_real u, orc_real v, const orc_real ro[3], const orc_real rd[3], orc_real out[4]);
+
 #ifdef __cplusplus
 }
 #endif

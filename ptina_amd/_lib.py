@@ -25,6 +25,9 @@ UNIT_KINDS = {
     'dir2tex': (9, 3, 2), 'reflect': (10, 6, 3), 'refract': (11, 7, 4), 'box': (12, 12, 3), 'face': (13, 30, 9),
     'sphere': (14, 10, 1), 'area': (15, 15, 4), 'disney_brdf': (16, 24, 3), 'disney_bounce': (17, 24, 7),
     'power_heuristic': (18, 2, 1), 'wanghash': (19, 1, 1), 'wanghash2': (20, 2, 1),
+    # the kinds that read the context's scene (lights, images, materials, world light, camera)
+    'light_hit': (21, 6, 6), 'light_sample': (22, 6, 8), 'image_sample': (23, 3, 4), 'world_at': (24, 3, 3),
+    'material_get': (25, 3, 22), 'camera_generate': (26, 2, 6), 'face_side': (27, 14, 4),
 }
 
 

@@ -541,6 +541,7 @@ extern "C" int mpt_load_materials(mpt_ctx *c, const float *fac, const int32_t *t
     if (use(c)) return 1;
     if (m < 0 || m > c->caps.max_materials) return fail("%d materials exceed max_materials=%d", m, c->caps.max_materials);
     std::vector<MptMaterial> h(std::max(m, 1));
+    int max_tex = -1;
     for (int i = 0; i < m; i++) {
         MptMaterial &M = h[i];
         memset(&M, 0, sizeof M);
@@ -553,8 +554,11 @@ extern "C" int mpt_load_materials(mpt_ctx *c, const float *fac, const int32_t *t
             if (t < -1 || t >= c->caps.max_textures) return fail("texture id %d outside [-1, %d)", t, c->caps.max_textures);
             M.tex[k] = t;
             if (t != -1) M.any_tex = 1;
+            max_tex = std::max(max_tex, t);
         }
     }
+    c->max_mat_tex = max_tex;
+    c->nmats = m;
     if (m) HIP_TRY(hipMemcpyAsync(c->mats, h.data(), (size_t)m * sizeof(MptMaterial), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(mpt_launch_derive_materials(c->mats, m, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -689,6 +693,20 @@ extern "C" int mpt_sobol_get(mpt_ctx *c, int32_t *X, float *P, int32_t *time) {
 }
 
 // ------------------------------------------------------------------ rendering
+// the part of the launch parameters that describes the scene's lights, world light, camera, materials and images: what lights_hit,
+// lights_sample, image_sample, world_at, material_get and camera_generate read (fill_params; mpt_unit_eval, which needs no film,
+// sampler or tree)
+static int fill_scene_params(mpt_ctx *c, MptRenderParams &p) {
+    p.nlights = (int)c->h_lights.size(); p.world_tex = c->world_tex;
+    memcpy(p.world_fac, c->world_fac, sizeof p.world_fac);
+    memcpy(p.v2w, c->v2w, sizeof p.v2w);
+    p.default_mtl = c->caps.max_materials;
+    p.mats = c->mats; p.lights = c->lights; p.images = c->images; p.texels = c->texels;
+    if (p.world_tex != -1 && (p.world_tex < 0 || p.world_tex >= (int)c->h_images.size()))
+        return fail("world light texture %d is not a loaded image", p.world_tex);
+    return 0;
+}
+
 static int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes) {
     if (c->nx <= 0) return fail("film size not set: call set_size() first");
     if (!c->sV) return fail("sobol sampler not initialised");
@@ -702,14 +720,12 @@ static int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes) {
     p.nx = c->nx; p.ny = c->ny; p.x0 = c->x0; p.x1 = c->x1;
     p.nframes = nframes; p.n = c->nfaces;
     p.sobol_inv_dim = 1.0f / (float)c->sdim;
-    p.sobol_dim = c->sdim; p.nlights = (int)c->h_lights.size(); p.world_tex = c->world_tex;
+    p.sobol_dim = c->sdim;
     share_extent(c, MPT_TILE, nullptr, &p.tiles_x);
     p.stripe_w = c->stripe_w ? c->stripe_w : (1 << 30);
     p.stripe_pitch = c->stripe_w ? c->stripe_w * c->stripe_mod : (1 << 30);
     p.tiles_y = (c->ny + MPT_TILE - 1) / MPT_TILE;
     p.ntiles = p.tiles_x * p.tiles_y;
-    memcpy(p.world_fac, c->world_fac, sizeof p.world_fac);
-    memcpy(p.v2w, c->v2w, sizeof p.v2w);
     {   // t_scale: 2^-e with 2^e no less than the farthest a ray origin -- a point of the camera's near plane or of a surface -- can be
         // from any point of the scene's bounding sphere (mpt_load_model)
         double reach = c->nfaces > 0 ? 2.0 * c->scene_rad : 1.0;
@@ -731,17 +747,13 @@ static int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes) {
     }
     p.wnode = c->wnode; p.qnode = c->qnode; p.nwide = c->wide_nodes; p.stack_spill = nullptr;
     p.snode = c->snode; p.fnode = c->fnode; p.tgeo = c->tgeo; p.tshade = c->tshade; p.tfast = c->tfast;
-    p.default_mtl = c->caps.max_materials;
     p.skip_dark = c->skip_dark >= 0 ? c->skip_dark : (c->mode == MPT_MODE_FAST ? 1 : 0);
-    p.mats = c->mats; p.lights = c->lights; p.images = c->images; p.texels = c->texels;
     p.P = c->sP;
     p.film0 = c->film[0]; p.film1 = c->film[1]; p.film2 = c->film[2];
     p.counters = c->d_counters;
     p.lane_hist = c->lane_hist;
     p.watchdog = c->d_watchdog;
-    if (p.world_tex != -1 && (p.world_tex < 0 || p.world_tex >= (int)c->h_images.size()))
-        return fail("world light texture %d is not a loaded image", p.world_tex);
-    return 0;
+    return fill_scene_params(c, p);
 }
 
 static hipEvent_t get_event(mpt_ctx *c) {
@@ -1514,24 +1526,66 @@ extern "C" int mpt_unit_eval(mpt_ctx *c, int kind, const void *in, int in_cols, 
     if (use_ro(c)) return 1;
     static const int cols[MPT_UNIT_KINDS][2] = {
         { 1, 1 }, { 3, 1 }, { 2, 1 }, { 2, 1 }, { 2, 1 }, { 3, 3 }, { 3, 3 }, { 6, 3 }, { 2, 3 }, { 3, 2 }, { 6, 3 }, { 7, 4 },
-        { 12, 3 }, { 30, 9 }, { 10, 1 }, { 15, 4 }, { 24, 3 }, { 24, 7 }, { 2, 1 }, { 1, 1 }, { 2, 1 } };
+        { 12, 3 }, { 30, 9 }, { 10, 1 }, { 15, 4 }, { 24, 3 }, { 24, 7 }, { 2, 1 }, { 1, 1 }, { 2, 1 },
+        { 6, 6 }, { 6, 8 }, { 3, 4 }, { 3, 3 }, { 3, 22 }, { 2, 6 }, { 14, 4 } };
     if (kind < 0 || kind >= MPT_UNIT_KINDS) return fail("unit kind %d outside [0, %d)", kind, (int)MPT_UNIT_KINDS);
     if (in_cols != cols[kind][0] || out_cols != cols[kind][1])
         return fail("unit kind %d takes %d input and %d output columns, got %d and %d", kind, cols[kind][0], cols[kind][1],
                     in_cols, out_cols);
     if (n < 0 || (n > 0 && (!in || !out))) return fail("bad unit_eval arguments");
     if (n == 0) return 0;
+    // the scene as a render launch would see it (the scene-free kinds ignore it); film, sampler and tree stay unset
+    MptRenderParams p;
+    memset(&p, 0, sizeof p);
+    p.world_tex = -1;
+    // MPT_UNIT_FACE_SIDE: one tshade record (mpt_types.h) per row, material id -1, packed HERE -- the kind tests the normal flip of
+    // get_geometries only; mpt_load_model's packing of tshade is covered by the render-level tests, not by this door
+    std::vector<MptVec4> shade;
+    if (kind >= MPT_UNIT_LIGHT_HIT) {
+        const float *rows = (const float *)in;
+        if (fill_scene_params(c, p)) return 1;
+        if (kind == MPT_UNIT_IMAGE_SAMPLE)
+            for (int i = 0; i < n; i++) {
+                const float id = rows[(size_t)i * in_cols];
+                if (!(id >= 0.f && id < (float)c->h_images.size() && id == (float)(int)id))
+                    return fail("unit_eval: row %d samples image %g, and %d images are loaded", i, (double)id, (int)c->h_images.size());
+            }
+        if (kind == MPT_UNIT_MATERIAL_GET) {
+            if (c->max_mat_tex >= (int)c->h_images.size())
+                return fail("unit_eval: a material names texture %d, and %d images are loaded", c->max_mat_tex, (int)c->h_images.size());
+            for (int i = 0; i < n; i++) {
+                const float id = rows[(size_t)i * in_cols];
+                if (!(id >= -1.f && id < (float)c->nmats && id == (float)(int)id))
+                    return fail("unit_eval: row %d asks for material %g outside [-1, %d), the records loaded", i, (double)id, c->nmats);
+            }
+        }
+        if (kind == MPT_UNIT_FACE_SIDE) {
+            shade.resize((size_t)n * 4);
+            const int none = -1;
+            for (int i = 0; i < n; i++) {
+                const float *vn = rows + (size_t)i * in_cols + 3;
+                MptVec4 *s = &shade[(size_t)i * 4];
+                s[0] = { vn[0], vn[1], vn[2], vn[3] }; s[1] = { vn[4], vn[5], vn[6], vn[7] };
+                s[2] = { vn[8], 0.f, 0.f, 0.f }; s[3] = { 0.f, 0.f, 0.f, 0.f };
+                memcpy(&s[3].w, &none, 4);
+            }
+        }
+    }
     float *d_in = nullptr, *d_out = nullptr;
+    MptVec4 *d_shade = nullptr;
     if (dev_alloc(&d_in, (size_t)n * in_cols)) return 1;
     if (dev_alloc(&d_out, (size_t)n * out_cols)) { hipFree(d_in); return 1; }
+    if (!shade.empty() && dev_alloc(&d_shade, shade.size())) { hipFree(d_in); hipFree(d_out); return 1; }
     hipError_t e = hipMemcpyAsync(d_in, in, (size_t)n * in_cols * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && d_shade) e = hipMemcpyAsync(d_shade, shade.data(), shade.size() * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream);
+    p.tshade = d_shade;
     if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, (size_t)n * out_cols * 4, c->stream);
     if (e == hipSuccess)
-        e = c->mode == MPT_MODE_STRICT ? mpt_launch_unit_eval_strict(kind, d_in, in_cols, d_out, out_cols, n, c->stream)
-                                       : mpt_launch_unit_eval_fast(kind, d_in, in_cols, d_out, out_cols, n, c->stream);
+        e = c->mode == MPT_MODE_STRICT ? mpt_launch_unit_eval_strict(&p, kind, d_in, in_cols, d_out, out_cols, n, c->stream)
+                                       : mpt_launch_unit_eval_fast(&p, kind, d_in, in_cols, d_out, out_cols, n, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * out_cols * 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d_in); hipFree(d_out);
+    hipFree(d_in); hipFree(d_out); hipFree(d_shade);
     if (e != hipSuccess) return fail("mpt_unit_eval: %s", hipGetErrorString(e));
     return 0;
 }

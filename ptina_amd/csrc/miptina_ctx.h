@@ -47,8 +47,8 @@ MPT_KERNEL_API hipError_t mpt_launch_combine(MptVec4 *film, const MptVec4 *parti
                                          int stripe_w, int stripe_pitch, int ccols, int nframes, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_resolve(const MptVec4 *film, MptVec4 *out, size_t npix, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_probe(double *out, int threads, size_t lds_bytes, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_unit_eval_fast(int kind, const float *in, int in_cols, float *out, int out_cols, int n, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_unit_eval_strict(int kind, const float *in, int in_cols, float *out, int out_cols, int n, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_launch_unit_eval_fast(const MptRenderParams *, int kind, const float *in, int in_cols, float *out, int out_cols, int n, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_launch_unit_eval_strict(const MptRenderParams *, int kind, const float *in, int in_cols, float *out, int out_cols, int n, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_copy_pieces(const MptVec4 *src, MptVec4 *dst, const MptPiece *tab, int npieces,
                                              long long max_count, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_export(const MptVec4 *film, float *out, int nx, int ny, hipStream_t);
@@ -175,6 +175,8 @@ struct mpt_ctx {
 
     // materials / images / lights / world / camera
     MptMaterial *mats = nullptr;
+    int nmats = 0;                       // material records mpt_load_materials last loaded (mpt_unit_eval refuses ids beyond them)
+    int max_mat_tex = -1;                // largest texture id a loaded material names (-1: none): mpt_unit_eval checks it against the loaded images
     MptImage *images = nullptr;
     std::vector<MptImage> h_images;
     MptVec4 *texels = nullptr;

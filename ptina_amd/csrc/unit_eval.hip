@@ -7,6 +7,11 @@
 // inputs of tests/golden/reference_l1.npz -- vectors computed by the reference's own function bodies -- so the HIP
 // code is held to the reference's source directly, not through the CPU oracle.
 //
+// The kinds from MPT_UNIT_LIGHT_HIT on read the context's scene through the launch parameters (mpt_unit_eval fills the part of
+// MptRenderParams that names lights, world light, camera, materials and images, and checks the ids the rows name): lights_hit,
+// lights_sample, image_sample, world_at, material_get, camera_generate and the normal flip of get_geometries, held to
+// tests/golden/reference_scene_units.npz by tests/test_reference_scene_units_gpu.py.
+//
 // Rows are 4-byte words: f32, except the two hash kinds (i32).  Kinds and columns: include/miptina.h.
 
 #include "pt_device.h"
@@ -32,8 +37,12 @@ DEV Disney disney_from14(const float *p) {                                   // 
     return m;
 }
 
-__global__ __launch_bounds__(64) void MPT_SUFFIX(unit_eval_kernel)(int kind, const float *__restrict__ in, int in_cols,
-                                                                   float *__restrict__ out, int out_cols, int n) {
+#if !MPT_STRICT
+struct UnitScene { static constexpr bool LDS_MATS = false; };        // get_geometries_rec: the material comes from the record's id
+#endif
+
+__global__ __launch_bounds__(64) void MPT_SUFFIX(unit_eval_kernel)(const MptRenderParams p, int kind, const float *__restrict__ in,
+                                                                   int in_cols, float *__restrict__ out, int out_cols, int n) {
     const int row = blockIdx.x * 64 + threadIdx.x;
     if (row >= n) return;
     const float *r = in + (size_t)row * in_cols;
@@ -113,14 +122,62 @@ __global__ __launch_bounds__(64) void MPT_SUFFIX(unit_eval_kernel)(int kind, con
     case MPT_UNIT_POWER_HEURISTIC: o[0] = power_heuristic(r[0], r[1]); break;                // path.py:11-15
     case MPT_UNIT_WANGHASH: o[0] = __int_as_float(wanghash(__float_as_int(r[0]))); break;    // sampling/__init__.py:9-16
     case MPT_UNIT_WANGHASH2: o[0] = __int_as_float(wanghash2(__float_as_int(r[0]), __float_as_int(r[1]))); break;   // :20-23
+    case MPT_UNIT_LIGHT_HIT: {                                                               // light/__init__.py:51-81
+        const LightHit h = lights_hit(p, ld(r, 0), ld(r, 3));
+        o[0] = h.hit ? 1.0f : 0.0f; o[1] = h.dis; o[2] = h.pdf; st(o, 3, h.color);
+        break;
+    }
+    case MPT_UNIT_LIGHT_SAMPLE: {                                                            // light/__init__.py:83-121
+        const LightSample s = lights_sample(p, ld(r, 0), ld(r, 3));
+        o[0] = s.dis; st(o, 1, s.dir); o[4] = s.pdf; st(o, 5, s.color);
+        break;
+    }
+    case MPT_UNIT_IMAGE_SAMPLE: {                                                            // image.py:137-148, common.py:183-192
+        const MptVec4 t = image_sample(p, (int)r[0], r[1], r[2]);
+        o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
+        break;
+    }
+    case MPT_UNIT_WORLD_AT: st(o, 0, world_at(p, ld(r, 0))); break;                          // light/world.py:22-29
+    case MPT_UNIT_MATERIAL_GET: {                           // mtllib.py:30-38,79-95 + disney.py:13-50
+        Disney m;
+        material_get(p, (int)r[0], r[1], r[2], m);
+        st(o, 0, m.basecolor);
+        o[3] = m.metallic; o[4] = m.roughness; o[5] = m.specular; o[6] = m.specularTint; o[7] = m.subsurface; o[8] = m.sheen;
+        o[9] = m.sheenTint; o[10] = m.clearcoat; o[11] = m.clearcoatGloss; o[12] = m.transmission; o[13] = m.ior;
+        st(o, 14, m.speccolor); st(o, 17, m.sheencolor); o[20] = m.alpha; o[21] = m.clearcoatAlpha;
+        break;
+    }
+    case MPT_UNIT_CAMERA_GENERATE: {                                                         // camera.py:34-39
+        V3 ro, rd;
+        camera_generate(p, r[0], r[1], &ro, &rd);
+        st(o, 0, ro); st(o, 3, rd);
+        break;
+    }
+    case MPT_UNIT_FACE_SIDE: {                              // model.py:88-101; p.tshade holds one shading record per row (mpt_unit_eval)
+        Hit hit;
+        hit.index = row; hit.depth = 1.0f; hit.u = r[12]; hit.v = r[13];
+        V3 hitpos, normal;
+        Disney m;
+#if MPT_STRICT
+        get_geometries(p, hit, v3s(0.0f), ld(r, 0), &hitpos, &normal, m);
+#else
+        const UnitScene sc;
+        get_geometries_rec(p, sc, shade_rec_load<false>(p, row), hit, v3s(0.0f), ld(r, 0), &hitpos, &normal, m);
+#endif
+        const MptVec4 *s = p.tshade + (size_t)row * 4;
+        V3 plain; float tu, tv;
+        face_shading(s[0], s[1], s[2], s[3], hit.u, hit.v, &plain, &tu, &tv);
+        st(o, 0, normal); o[3] = dot(plain, normal) < 0.0f ? 1.0f : 0.0f;
+        break;
+    }
     default: break;
     }
 }
 
-MPT_KERNEL_API hipError_t MPT_SUFFIX(mpt_launch_unit_eval)(int kind, const float *in, int in_cols, float *out, int out_cols,
-                                                         int n, hipStream_t stream) {
+MPT_KERNEL_API hipError_t MPT_SUFFIX(mpt_launch_unit_eval)(const MptRenderParams *p, int kind, const float *in, int in_cols, float *out,
+                                                         int out_cols, int n, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(MPT_SUFFIX(unit_eval_kernel), dim3((n + 63) / 64), dim3(64), 0, stream, kind, in, in_cols, out,
+    hipLaunchKernelGGL(MPT_SUFFIX(unit_eval_kernel), dim3((n + 63) / 64), dim3(64), 0, stream, *p, kind, in, in_cols, out,
                        out_cols, n);
     return hipGetLastError();
 }

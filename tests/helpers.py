@@ -287,3 +287,43 @@ def stress_compare(seed, log=print):
         f'fireflies {flies} of at most {kmax} | kernels {kernels}')
     reset_all()
     return ok and same, flies, msgs
+
+
+# ---- function-level comparisons against the reference's own vectors (tests/test_reference_units_gpu.py,
+# tests/test_reference_scene_units_*.py)
+def report(msg):
+    print(msg)
+    _report(msg)
+
+
+def close(got, want, rel, what, abs_=0.0, allow=0, slack=None):
+    '''|got - want| <= rel |want| + abs_ (+ slack) element-wise; NaN / infinity patterns equal; up to `allow` rows may
+    fail.  slack: an array like `want` added to the bound -- used with spread() below for ill-conditioned inputs'''
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    assert got.shape == want.shape, what
+    g2, w2 = got.reshape(got.shape[0], -1), want.reshape(want.shape[0], -1)
+    sl = 0.0 if slack is None else np.nan_to_num(np.asarray(slack, np.float64).reshape(w2.shape), nan=0.0, posinf=0.0, neginf=0.0)
+    nan_ok = np.isnan(g2) == np.isnan(w2)
+    inf = np.isinf(w2)
+    inf_ok = np.where(inf, g2 == w2, ~np.isinf(g2))
+    fin = ~(np.isnan(w2) | inf | np.isnan(g2) | np.isinf(g2))
+    err = np.where(fin, np.abs(g2 - w2), 0.0)
+    bound = rel * np.abs(np.where(fin, w2, 0.0)) + abs_ + sl
+    ratio = np.where(fin, err / np.maximum(bound, 1e-300), 0.0)
+    row_bad = (~nan_ok | ~inf_ok | (ratio > 1.0)).any(axis=1)
+    worst = float(ratio.max()) if ratio.size else 0.0
+    report(f'{what}: worst error {worst:.3f} x the bound (rel {rel:g}, abs {abs_:g}); rows outside {int(row_bad.sum())} of {len(row_bad)} (allowed {allow})')
+    assert int(row_bad.sum()) <= allow, f'{what}: {int(row_bad.sum())} rows outside the bound (worst {worst:.2f} x; rel {rel:g}, abs {abs_:g}); first bad rows {np.nonzero(row_bad)[0][:8]}'
+
+
+def spread(gold, key, k=4.0):
+    '''k x |f32 run - f64 run| of the reference's own function on (to 1e-7) the same inputs: how ill-conditioned each
+    output is.  The production build's different rounding (FMA, v_rcp) may move such an output as far as the
+    reference's own precision does -- e.g. GTR2's t = 1 + (a^2 - 1) cos^2 at alpha = 0.001 (the mirror material: the
+    reference's two runs differ by 57 %), or sqrt(1 - h^2) for h -> 1'''
+    a, b = gold[f'f32/{key}'].astype(np.float64), gold[f'f64/{key}'].astype(np.float64)
+    return k * np.abs(a - b)
+
+
+def pick(mode, strict, fast):
+    return strict if mode == 'strict' else fast
