@@ -170,6 +170,12 @@ extern "C" mpt_ctx *mpt_create(const mpt_caps *caps, int device) {
         // record max_materials: the default material of mtllib.py:82-93 (mtlid -1)
         const float dflt[14] = { 0.8f, 0.8f, 0.8f, 0.0f, 0.4f, 0.5f, 0.4f, 0.0f, 0.0f, 0.4f, 0.0f, 0.5f, 0.0f, 1.45f };
         memcpy(z.back().p, dflt, sizeof dflt);
+        {   // its feature bits (none: no clearcoat, no transmission, no texture), from the same function as a loaded material's
+            float fac[48] = {};
+            fac[0] = dflt[0]; fac[1] = dflt[1]; fac[2] = dflt[2];
+            for (int k = 1; k < 12; k++) fac[k * 4] = dflt[2 + k];
+            c->default_feat = shade_feat_material(fac, nullptr);
+        }
         hipMemcpyAsync(c->mats, z.data(), z.size() * sizeof(MptMaterial), hipMemcpyHostToDevice, c->stream);
         mpt_launch_derive_materials(c->mats, (int)z.size(), c->stream);
         hipStreamSynchronize(c->stream);
@@ -281,6 +287,8 @@ static int read_back(mpt_ctx *c, void *out, const void *dev, size_t bytes) {
     return 0;
 }
 
+static int scene_feat_now(const mpt_ctx *c);
+
 // ------------------------------------------------------------------ options
 extern "C" int mpt_set_option(mpt_ctx *c, const char *key, int value) {
     if (use(c)) return 1;
@@ -303,6 +311,9 @@ extern "C" int mpt_set_option(mpt_ctx *c, const char *key, int value) {
         c->lds_wide = value;
     } else if (k == "zero_copy") {
         c->zero_copy = value ? 1 : 0;
+    } else if (k == "shade_spec") {
+        if (value != 0 && value != 1) return fail("shade_spec must be 0 (always the generic SHADE) or 1 (the plain one for plain scenes)");
+        c->shade_spec = value;
     } else if (k == "skip_dark") {
         if (value < -1 || value > 1) return fail("skip_dark must be -1 (auto), 0 or 1");
         c->skip_dark = value;
@@ -392,6 +403,9 @@ extern "C" int mpt_get_option(mpt_ctx *c, const char *key, int *value) {
     else if (k == "launch_seq") *value = (int)(c->launch_seq & 0x7fffffffu);
     else if (k == "tag_wraps") *value = (int)c->tag_wraps;
     else if (k == "skip_dark") *value = c->skip_dark;
+    else if (k == "shade_spec") *value = c->shade_spec;
+    else if (k == "scene_feat") *value = scene_feat_now(c);            // read-only: the scene's feature mask as loaded (shade_feat.h)
+    else if (k == "shade_inst") *value = c->last_shade_feat;           // read-only: the mask the last render launch was compiled for (0 plain, 31 generic)
     else if (k == "pipe_depth") *value = c->pipe_depth;
     else if (k == "grid_div") *value = c->grid_div;
     else if (k == "cur_depth") *value = c->cur_depth;
@@ -537,10 +551,18 @@ extern "C" int mpt_load_model(mpt_ctx *c, const float *verts, const int32_t *mtl
     return 0;
 }
 
+// The feature mask of the scene as it stands (shade_feat.h): the materials the model uses -- the records the LDS-resident kernel
+// packs, 0 .. max_mtlid and the default one -- the light list and the world light.  Formed where it is used (a launch, the
+// "scene_feat" option), so it follows every reload of materials, model, lights or world without a cache to invalidate.
+static int scene_feat_now(const mpt_ctx *c) {
+    return shade_feat_scene(c->mat_feat.data(), (int)c->mat_feat.size(), c->max_mtlid, c->default_feat, (int)c->h_lights.size(), c->world_tex);
+}
+
 extern "C" int mpt_load_materials(mpt_ctx *c, const float *fac, const int32_t *tex, int m) {
     if (use(c)) return 1;
     if (m < 0 || m > c->caps.max_materials) return fail("%d materials exceed max_materials=%d", m, c->caps.max_materials);
     std::vector<MptMaterial> h(std::max(m, 1));
+    std::vector<unsigned char> feat((size_t)m);
     int max_tex = -1;
     for (int i = 0; i < m; i++) {
         MptMaterial &M = h[i];
@@ -556,8 +578,13 @@ extern "C" int mpt_load_materials(mpt_ctx *c, const float *fac, const int32_t *t
             if (t != -1) M.any_tex = 1;
             max_tex = std::max(max_tex, t);
         }
+        feat[i] = (unsigned char)shade_feat_material(f, M.tex);
     }
     c->max_mat_tex = max_tex;
+    // records beyond m keep what an earlier call left in them on the device, so their bits are kept as well
+    // (the scene's mask is formed from these at every launch: scene_feat_now)
+    if (c->mat_feat.size() < feat.size()) c->mat_feat.resize(feat.size(), 0);
+    std::copy(feat.begin(), feat.end(), c->mat_feat.begin());
     c->nmats = m;
     if (m) HIP_TRY(hipMemcpyAsync(c->mats, h.data(), (size_t)m * sizeof(MptMaterial), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(mpt_launch_derive_materials(c->mats, m, c->stream));
@@ -1018,13 +1045,16 @@ extern "C" int mpt_flush(mpt_ctx *c) {
         }
     }
     c->last_finalised = fin ? 1 : 0;
+    // SHADE compiled for what the scene uses: the LDS-resident 4-wide kernel has a plain instantiation, every other kernel the generic code
+    const int shade_feat = lds4_kernel ? shade_feat_instantiation(scene_feat_now(c), c->shade_spec) : MPT_FEAT_GENERIC;
     hipEvent_t e0 = get_event(c), e1 = get_event(c);
     HIP_TRY(hipEventRecord(e0, rs));
     if (!fast) HIP_TRY(mpt_launch_render_strict(&p, p.ntiles, stack, c->count, rs));
-    else if (lds4_kernel) HIP_TRY(mpt_launch_render_lds4(&p, launch_cus, lds_block_used, lds4_bytes, c->count, rs));
+    else if (lds4_kernel) HIP_TRY(mpt_launch_render_lds4(&p, launch_cus, lds_block_used, lds4_bytes, c->count, shade_feat, rs));
     else if (lds_kernel) HIP_TRY(mpt_launch_render_lds(&p, launch_cus, lds_block_used, lds_bytes, c->count, rs));
     else if (wide_kernel) HIP_TRY(mpt_launch_render_wide(&p, wide_blocks, c->count, c->use_quant, rs));
     else HIP_TRY(mpt_launch_render_fast(&p, launch_cus, stack, c->count, rs));
+    c->last_shade_feat = shade_feat;
     c->last_kernel = lds4_kernel ? 5 : lds_kernel ? 1 : wide_kernel ? 2 : 0;      // (3 and 4 are retired: include/miptina.h)
     HIP_TRY(hipEventRecord(e1, rs));
     c->events.push_back({ e0, e1 });

@@ -4,6 +4,7 @@
 
 #include "../../include/miptina.h"
 #include "mpt_types.h"
+#include "shade_feat.h"
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -26,7 +27,7 @@ MPT_KERNEL_API hipError_t mpt_launch_derive_tfast(const MptVec4 *tgeo, MptVec4 *
 MPT_KERNEL_API hipError_t mpt_wide_blocks(int grid, int count, int quant, int *blocks);
 MPT_KERNEL_API hipError_t mpt_launch_render_wide(const MptRenderParams *, int blocks, int count, int quant, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_render_lds(const MptRenderParams *, int grid, int block, size_t lds_bytes, int count, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_render_lds4(const MptRenderParams *, int grid, int block, size_t lds_bytes, int count, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_launch_render_lds4(const MptRenderParams *, int grid, int block, size_t lds_bytes, int count, int feat, hipStream_t);
 // mlt_kernel.hip: the Metropolis engine's chain kernel (both builds), its test door, and the build-independent passes
 MPT_KERNEL_API hipError_t mpt_launch_mlt_chain_fast(const MptRenderParams *, const MptMltArgs *, int stack, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_mlt_chain_strict(const MptRenderParams *, const MptMltArgs *, int stack, hipStream_t);
@@ -109,6 +110,8 @@ struct mpt_ctx {
     int tile_w_shift = 3, tile_h_shift = 3;   // work-item tile 2^w x 2^h pixels
     int last_div = 1;                    // share of the chip the last launch took: 1/last_div of the CUs
     int last_kernel = 0;                 // 0 gather kernel, 1 LDS-resident kernel (what the last flush launched)
+    int shade_spec = 1;                  // 1: a scene whose feature mask (shade_feat.h) is empty runs the plain instantiation of render_kernel_lds4; 0: always the generic one (A/B, tests)
+    int last_shade_feat = -1;            // the mask the last render launch was compiled for (MPT_FEAT_PLAIN / MPT_FEAT_GENERIC; -1: none yet)
 
     // film
     int nx = 0, ny = 0, x0 = 0, x1 = 0;
@@ -175,6 +178,8 @@ struct mpt_ctx {
 
     // materials / images / lights / world / camera
     MptMaterial *mats = nullptr;
+    std::vector<unsigned char> mat_feat; // shade_feat_material of every record mpt_load_materials last loaded
+    int default_feat = 0;                // ... and of the default material (mpt_create)
     int nmats = 0;                       // material records mpt_load_materials last loaded (mpt_unit_eval refuses ids beyond them)
     int max_mat_tex = -1;                // largest texture id a loaded material names (-1: none): mpt_unit_eval checks it against the loaded images
     MptImage *images = nullptr;

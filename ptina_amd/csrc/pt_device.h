@@ -14,6 +14,7 @@
 
 #include <hip/hip_runtime.h>
 #include "mpt_types.h"
+#include "shade_feat.h"
 
 #ifndef MPT_STRICT
 #define MPT_STRICT 0
@@ -810,10 +811,14 @@ DEV void disney_init(Disney &m) {                                            // 
 // device function filled them in), so a bounce costs six 16-B gathers and no per-hit re-derivation.
 // q0..q3, d0, d1: the record's float4 0-3 and 8-9, from wherever the caller keeps them; mt: the record in
 // global memory (texture ids, read by textured materials only)
+// FEAT (shade_feat.h): what the scene uses, decided on the host; a kernel compiled for a mask without a bit holds none of that
+// bit's code, and what is left is the same operations in the same order
+template <int FEAT = MPT_FEAT_GENERIC>
 DEV void material_from(const MptRenderParams &p, const MptMaterial *mt, MptVec4 q0, MptVec4 q1, MptVec4 q2, MptVec4 q3,
                        MptVec4 d0, MptVec4 d1, float tu, float tv, Disney &m) {
     float v[14] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y };
-    const bool textured = __float_as_int(q3.z) != 0;                           // p[14] mirrors any_tex
+    bool textured = false;
+    if constexpr ((FEAT & MPT_FEAT_TEXTURED_MATS) != 0) textured = __float_as_int(q3.z) != 0;   // p[14] mirrors any_tex
     if (textured) {
 #pragma unroll 1
         for (int k = 0; k < 12; k++) {
@@ -887,7 +892,11 @@ DEV void material_get(const MptRenderParams &p, int mtlid, float tu, float tv, D
 }
 #endif
 
+template <int FEAT = MPT_FEAT_GENERIC>
 DEV V3 disney_brdf(const Disney &m, V3 normal, float sign, V3 indir, V3 outdir) {   // disney.py:53-106
+    // (a scene without the lobe has the parameter exactly zero in every material: the regions below are the ones the
+    //  production build already skips per hit on "parameter == 0", and the half below the surface is a product with it)
+    constexpr bool COAT = (FEAT & MPT_FEAT_CLEARCOAT) != 0, TRANS = (FEAT & MPT_FEAT_TRANSMISSION) != 0;
     float etai = 1.0f, etao = m.ior;
     if (sign < 0.0f) { etai = m.ior; etao = 1.0f; }
 
@@ -899,7 +908,7 @@ DEV V3 disney_brdf(const Disney &m, V3 normal, float sign, V3 indir, V3 outdir) 
 
     V3 result = v3s(0.0f);
     if (coso < 0.0f) {
-        if (cosi >= 0.0f) {
+        if (TRANS && cosi >= 0.0f) {
             float Ds = GTR2(cosh_, m.alpha);
             float fdf = dielectricFresnel(etao, etai, cosoh);
             V3 transmit = m.basecolor * MPT_INV_PI * (1.0f - fdf) * Ds;
@@ -933,7 +942,7 @@ DEV V3 disney_brdf(const Disney &m, V3 normal, float sign, V3 indir, V3 outdir) 
         // the clearcoat and transmission lobes are multiplied by their parameter: when that is
         // exactly zero the term is skipped (identical result whenever the skipped factor is finite)
         float coat = 0.0f;
-        if (m.clearcoat != 0.0f) {
+        if (COAT && m.clearcoat != 0.0f) {
             float Dr = GTR1(cosh_, m.clearcoatAlpha);
             float Gr = smithGGX(cosi, 0.25f) * smithGGX(coso, 0.25f);
             float Fr = lerpf(Foh, 0.04f, 1.0f);
@@ -941,7 +950,7 @@ DEV V3 disney_brdf(const Disney &m, V3 normal, float sign, V3 indir, V3 outdir) 
         }
         V3 specular = Fs * Gs * Ds + v3s(coat);
         V3 transmit = v3s(0.0f);
-        if (m.transmission != 0.0f) transmit = m.basecolor * (MPT_INV_PI * dielectricFresnel(etao, etai, cosoh) * Ds);
+        if (TRANS && m.transmission != 0.0f) transmit = m.basecolor * (MPT_INV_PI * dielectricFresnel(etao, etai, cosoh) * Ds);
 #endif
 
         result = diffuse * (1.0f - m.metallic) * (1.0f - m.transmission);
@@ -970,7 +979,9 @@ struct Choice {                                                               //
     }
 };
 
+template <int FEAT = MPT_FEAT_GENERIC>
 DEV BsdfSample disney_bounce(const Disney &m, V3 normal, float sign, V3 indir, V3 samp) {   // disney.py:115-233
+    constexpr bool COAT = (FEAT & MPT_FEAT_CLEARCOAT) != 0, TRANS = (FEAT & MPT_FEAT_TRANSMISSION) != 0;
     BsdfSample result;
     result.outdir = v3s(0.0f); result.pdf = 0.0f; result.color = v3s(0.0f);
 
@@ -1083,7 +1094,7 @@ DEV BsdfSample disney_bounce(const Disney &m, V3 normal, float sign, V3 indir, V
     // and their order are those of the branches above; a wave whose lanes sit in two lobes issues the shared part
     // once instead of twice.
     // without a clearcoat the first Choice is the identity (w < 0 never holds, w = (w - 0) / (1 - 0), pdf *= 1)
-    const bool coat = coatrate != 0.0f && choice(coatrate);
+    const bool coat = COAT && coatrate != 0.0f && choice(coatrate);
     const bool spec = !coat && choice(specrate);
     float hz;                                                                 // cosine of the sampled direction to the normal
     if (coat) {                                                               // sample_GTR1, microfacet.py:69-71
@@ -1115,7 +1126,9 @@ DEV BsdfSample disney_bounce(const Disney &m, V3 normal, float sign, V3 indir, V
         const float coso = fmaxf(0.0f, coso_raw);
         if (cosoh > 0.0f && coso > 0.0f && cosh_ > 0.0f) {
             float Ds = GTR2(cosh_, m.alpha);
-            if (choice(m.transmission)) {
+            // without transmission the third Choice is the identity as well: in this branch w is w / r >= 0 of the second, so
+            // "w < 0" never holds, and pdf *= 1 - 0
+            if (TRANS && choice(m.transmission)) {
                 float fdf = dielectricFresnel(etao, etai, cosoh);
                 float reflrate = lerpf(fdf, 0.2f, 1.0f);
                 if (choice(reflrate)) {
@@ -1186,9 +1199,11 @@ DEV V3 axes_mul(const MptLight &L, V3 v) {
 
 struct LightHit { bool hit; float dis, pdf; V3 color; };
 
+template <int FEAT = MPT_FEAT_GENERIC>
 DEV LightHit lights_hit(const MptRenderParams &p, V3 ro, V3 rd) {            // light/__init__.py:51-81
     LightHit ret; ret.hit = false; ret.dis = MPT_INF; ret.pdf = 0.0f; ret.color = v3s(0.0f);
-    for (int i = 0; i < p.nlights; i++) {
+    const int nlights = (FEAT & MPT_FEAT_MANY_LIGHTS) != 0 ? p.nlights : 1;    // (a mask without the bit: exactly one light)
+    for (int i = 0; i < nlights; i++) {
         MptLight L = MPT_LIGHTS(p)[i];
         int type = __float_as_int(L.pos_type.w);
         V3 pos = ld3(L.pos_type);
@@ -1257,17 +1272,18 @@ DEV LightSample light_sample_one(const MptLight &L, V3 hitpos, V3 samp) {      /
     return ret;
 }
 
+template <int FEAT = MPT_FEAT_GENERIC>
 DEV LightSample lights_sample(const MptRenderParams &p, V3 hitpos, V3 samp) {   // light/__init__.py:83-121
     LightSample ret; ret.dis = MPT_INF; ret.dir = v3s(0.0f); ret.pdf = 0.0f; ret.color = v3s(0.0f);
 #if !MPT_STRICT
     // one light: samp.z < 1 (a Sobol point), so floor(samp.z * 1) is 0 -- the record is read with scalar loads and
     // its fields are scalar operands of the arithmetic (own copy of the code, so that nothing merges the two reads)
-    if (p.nlights == 1) {
+    if ((FEAT & MPT_FEAT_MANY_LIGHTS) == 0 || p.nlights == 1) {
         const MptLight L = MPT_LIGHTS(p)[0];
         return light_sample_one(L, hitpos, samp);
     }
 #endif
-    if (p.nlights != 0) {
+    if ((FEAT & MPT_FEAT_MANY_LIGHTS) != 0 && p.nlights != 0) {
         int i = (int)floorf(samp.z * (float)p.nlights);
         i = min(max(i, 0), min(p.nlights, MPT_MAX_LIGHTS - 1));
         const MptLight L = MPT_LIGHTS(p)[i];
@@ -1282,9 +1298,10 @@ DEV void dir2tex(V3 dir, float *s, float *t) {                               // 
     *t = atan2f(dn.y, sqrtf(dn.x * dn.x + dn.z * dn.z)) / MPT_PI + 0.5f;
 }
 
+template <int FEAT = MPT_FEAT_GENERIC>
 DEV V3 world_at(const MptRenderParams &p, V3 dir) {                          // light/world.py:22-29
     V3 fac = v3(p.world_fac[0], p.world_fac[1], p.world_fac[2]);
-    if (p.world_tex != -1) {
+    if ((FEAT & MPT_FEAT_WORLD_TEXTURE) != 0 && p.world_tex != -1) {
         V3 d2 = v3(dir.x, dir.z, -dir.y);                                    // dir.y, dir.z = dir.z, -dir.y
         float s, t;
         dir2tex(d2, &s, &t);
@@ -1347,7 +1364,7 @@ DEV ShadeRec shade_rec_load(const MptRenderParams &p, int slot) {
     ShadeRec r; r.s0 = s[0]; r.s1 = s[1]; r.s2 = s[2]; r.s3 = s[3];
     return r;
 }
-template <class SCENE>
+template <int FEAT, class SCENE>
 DEV void get_geometries_rec(const MptRenderParams &p, const SCENE &sc, const ShadeRec &r, const Hit &hit, V3 ro, V3 rd,
                             V3 *hitpos, V3 *normal, Disney &mat) {
     const MptVec4 s0 = r.s0, s1 = r.s1, s2 = r.s2, s3 = r.s3;
@@ -1361,8 +1378,9 @@ DEV void get_geometries_rec(const MptRenderParams &p, const SCENE &sc, const Sha
         const int rec = sc.mtl[hit.index];
         LdsVec4Ptr q = sc.mats + rec * MPT_LDS_MAT_VEC4;
         MptVec4 q0 = lds_ld(q), q1 = lds_ld(q + 1), q2 = lds_ld(q + 2), q3 = lds_ld(q + 3), d0 = lds_ld(q + 4), d1 = lds_ld(q + 5);
-        material_from(p, p.mats + (rec == sc.mat_last ? sc.mat_default : rec), q0, q1, q2, q3, d0, d1, tu, tv, mat);
+        material_from<FEAT>(p, p.mats + (rec == sc.mat_last ? sc.mat_default : rec), q0, q1, q2, q3, d0, d1, tu, tv, mat);
     } else {
+        static_assert(FEAT == MPT_FEAT_GENERIC, "the gather kernels are built for the generic mask only");
         material_get(p, __float_as_int(s3.w), tu, tv, mat);
     }
 }

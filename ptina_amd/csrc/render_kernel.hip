@@ -510,7 +510,8 @@ enum { SH_END = 0, SH_BOUNCE = 1, SH_SHADOW = 2 };
 #define MPT_SEG_BEGIN
 #define MPT_SEG(field)
 #endif   // path over (miss: world light added) | next bounce from hitpos | shadow ray first
-template <bool COUNT, class SCENE>
+// FEAT: the scene's feature mask the kernel is compiled for (shade_feat.h; wave-uniform by construction: the host picks it per launch)
+template <bool COUNT, int FEAT, class SCENE>
 DEV int shade_core(const MptRenderParams &p, const SCENE &sc, LaneState &L, Cnt &cnt, V3 &hitpos, V3 &sdir, float &sdis) {
     V3 ro = L.to, rd = L.prd;
     const bool was_hit = L.hidx >= 0;
@@ -530,7 +531,7 @@ DEV int shade_core(const MptRenderParams &p, const SCENE &sc, LaneState &L, Cnt 
         lane_draws<6, SCENE::LDS_MATS>(p, L, u);
     }
     MPT_SEG(pl_trips)            // (the entry of the stage -- reloads of what the traversal loop had parked -- and the issue of its gathers)
-    LightHit lit = lights_hit(p, ro, rd);
+    LightHit lit = lights_hit<FEAT>(p, ro, rd);
     if (lit.hit && (!was_hit || lit.dis < hdepth)) {
         float mis = power_heuristic(L.last_brdf_pdf, lit.pdf);
         L.result = L.result + L.throughput * (lit.color * mis);
@@ -538,33 +539,33 @@ DEV int shade_core(const MptRenderParams &p, const SCENE &sc, LaneState &L, Cnt 
     hitpos = ro; sdir = v3s(0.0f); sdis = 0.0f;
     MPT_SEG(pl_local)
     if (!was_hit) {
-        L.result = L.result + L.throughput * world_at(p, rd);
+        L.result = L.result + L.throughput * world_at<FEAT>(p, rd);
         L.depth = 5;                                                         // break, path.py:39
         return SH_END;
     }
     L.navoid = SCENE::ODD_IDS ? L.hidx : ~L.hidx;
     Hit hit; hit.hit = 1; hit.depth = hdepth; hit.index = hslot; hit.u = L.hu; hit.v = L.hv;
     V3 normal; Disney mat;
-    get_geometries_rec(p, sc, rec, hit, ro, rd, &hitpos, &normal, mat);
+    get_geometries_rec<FEAT>(p, sc, rec, hit, ro, rd, &hitpos, &normal, mat);
     if (COUNT) { cnt.n_shade++; cnt.n_draws += 6; }
     float sign = -dot(rd, normal);                                           // path.py:44-46 (never negative)
     if (sign < 0.0f) normal = -normal;
     MPT_SEG(pl_batches)
 
-    LightSample li = lights_sample(p, hitpos, v3(u[0], u[1], u[2]));
+    LightSample li = lights_sample<FEAT>(p, hitpos, v3(u[0], u[1], u[2]));
     bool want_shadow = any_gt0(li.color);
     MPT_SEG(pl_batch_lanes)
     L.direct = v3s(0.0f);
     if (want_shadow) {
         // evaluated before the visibility is known; dropped if the shadow ray hits (path.py:50-56)
-        V3 brdf_clr = disney_brdf(mat, normal, sign, -rd, li.dir);
+        V3 brdf_clr = disney_brdf<FEAT>(mat, normal, sign, -rd, li.dir);
         float brdf_pdf = vavg(brdf_clr);
         float mis = power_heuristic(li.pdf, brdf_pdf);
         V3 direct_li = li.color * mis * brdf_clr * dot_or_zero(normal, li.dir);
         L.direct = L.throughput * direct_li;
     }
     MPT_SEG(pl_prim)
-    BsdfSample brdf = disney_bounce(mat, normal, sign, -rd, v3(u[3], u[4], u[5]));
+    BsdfSample brdf = disney_bounce<FEAT>(mat, normal, sign, -rd, v3(u[3], u[4], u[5]));
     L.throughput = L.throughput * brdf.color;
     L.prd = brdf.outdir;
     L.last_brdf_pdf = brdf.pdf;
@@ -685,7 +686,7 @@ struct WorkQueue {
     }
 };
 
-template <bool COUNT, class SCENE, class STACK>
+template <bool COUNT, int FEAT, class SCENE, class STACK>
 DEV void trace_stream(const MptRenderParams &p, const SCENE &sc, STACK stk, WorkQueue wq, Cnt &cnt,
                       unsigned long long *tl = nullptr) {
     // work-item tiles are 2^tw_shift x 2^th_shift pixels (8x8 by default; smaller tiles shorten the
@@ -812,7 +813,7 @@ DEV void trace_stream(const MptRenderParams &p, const SCENE &sc, STACK stk, Work
             if (L.st == ST_DONE && !L.shadow) {
                 V3 hitpos, sdir;
                 float sdis;
-                const int nk = shade_core<COUNT>(p, sc, L, cnt, hitpos, sdir, sdis);
+                const int nk = shade_core<COUNT, FEAT>(p, sc, L, cnt, hitpos, sdir, sdis);
                 L.to = hitpos;
                 if (nk == SH_SHADOW) { L.td = sdir; L.tbest = sdis; L.st = ST_SHADOW; }
                 else L.st = ST_BOUNCE;                                       // SH_END: depth is 5, the sample is stored below
@@ -1086,7 +1087,7 @@ __global__ MPT_RENDER_BOUNDS void MPT_SUFFIX(render_kernel)(const MptRenderParam
 #else
     // persistent workgroups pulling (8x8 tile, chunk) items; see WorkQueue
     WorkQueue wq; wq.ctr = p.work_counter; wq.nitems = p.nitems; wq.q0 = blockIdx.x & 7; wq.qoff = 0;
-    trace_stream<COUNT>(p, tr.sc, tr.st, wq, cnt);
+    trace_stream<COUNT, MPT_FEAT_GENERIC>(p, tr.sc, tr.st, wq, cnt);
     finalise_tiles<MPT_FIN_GROUP_GATHER>(p);
 #endif
     flush_counters<COUNT>(p, cnt);
@@ -1112,10 +1113,10 @@ __global__ __launch_bounds__(MPT_BLOCK, MPT_WIDE_WAVES) void render_kernel_wide(
     WorkQueue wq; wq.ctr = p.work_counter; wq.nitems = p.nitems; wq.q0 = blockIdx.x & 7; wq.qoff = 0;
     if constexpr (QUANT) {
         QuantScene sc; sc.qnode = p.qnode; sc.tgeo = p.tfast;
-        trace_stream<COUNT>(p, sc, stk, wq, cnt);
+        trace_stream<COUNT, MPT_FEAT_GENERIC>(p, sc, stk, wq, cnt);
     } else {
         WideScene sc; sc.wnode = p.wnode; sc.tgeo = p.tfast;
-        trace_stream<COUNT>(p, sc, stk, wq, cnt);
+        trace_stream<COUNT, MPT_FEAT_GENERIC>(p, sc, stk, wq, cnt);
     }
     finalise_tiles<MPT_FIN_GROUP_GATHER>(p);
     flush_counters<COUNT>(p, cnt);
@@ -1168,7 +1169,7 @@ __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds(const MptRend
     stk.sp = 0;
     Cnt cnt = {};
     WorkQueue wq; wq.ctr = p.work_counter; wq.nitems = p.nitems; wq.q0 = blockIdx.x & 7; wq.qoff = 0;
-    trace_stream<COUNT>(p, sc, stk, wq, cnt, tl);
+    trace_stream<COUNT, MPT_FEAT_GENERIC>(p, sc, stk, wq, cnt, tl);
     if (tl && (threadIdx.x & 63) == 0) tl[3] = wall_clock64();
     const int fin_tiles = finalise_tiles<MPT_FIN_GROUP_LDS>(p);
 #if !MPT_X_TIMELINE2
@@ -1181,7 +1182,10 @@ __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds(const MptRend
 // dynamic LDS: [ nwide node records of MPT_LDS4_NODE_STRIDE bytes | (n+1)*3 triangle float4 (tfast; record n: the unused slots' NaNs) |
 //                (lds_nmats+1)*6 material float4 (the records the model uses, then the default one) | n material-record bytes,
 //                padded to 16 | lds_stack x 1024 int16 ]
-template <bool COUNT>
+// Two instantiations per COUNT: FEAT = MPT_FEAT_GENERIC (every region of SHADE) and MPT_FEAT_PLAIN_KERNEL, launched for a plain scene
+// (untextured materials without clearcoat or transmission, one light, no environment map: the headline scene and BASELINE's
+// configs 1, 2, 3, 5): without the texture, environment-map and light-list regions (shade_feat.h says why the two lobes stay)
+template <bool COUNT, int FEAT>
 __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds4(const MptRenderParams p) {
     extern __shared__ __attribute__((aligned(16))) MptVec4 smem[];
     const int nnode4 = p.nwide * (MPT_LDS4_NODE_STRIDE / 16), ntri4 = (p.n + 1) * 3, nmat4 = (p.lds_nmats + 1) * MPT_LDS_MAT_VEC4;
@@ -1235,7 +1239,7 @@ __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds4(const MptRen
     stk.ts = p.t_scale;
     Cnt cnt = {};
     WorkQueue wq; wq.ctr = p.work_counter; wq.nitems = p.nitems; wq.q0 = blockIdx.x & 7; wq.qoff = 0;
-    trace_stream<COUNT>(p, sc, stk, wq, cnt, tl);
+    trace_stream<COUNT, FEAT>(p, sc, stk, wq, cnt, tl);
     if (tl && (threadIdx.x & 63) == 0) tl[3] = wall_clock64();
     const int fin_tiles = finalise_tiles<MPT_FIN_GROUP_LDS>(p);
 #if !MPT_X_TIMELINE2
@@ -1334,25 +1338,31 @@ static hipError_t launch_lds(const MptRenderParams *p, int grid, int block, size
     return hipGetLastError();
 }
 
-template <bool COUNT>
+template <bool COUNT, int FEAT>
 static hipError_t launch_lds4(const MptRenderParams *p, int grid, int block, size_t lds_bytes, hipStream_t stream) {
     static std::atomic<bool> configured[MPT_MAX_DEVICES];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MPT_MAX_DEVICES) return hipErrorInvalidDevice;
     if (!configured[dev].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute((const void *)render_kernel_lds4<COUNT>,
+        hipError_t e = hipFuncSetAttribute((const void *)render_kernel_lds4<COUNT, FEAT>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
         configured[dev].store(true, std::memory_order_release);
     }
-    hipLaunchKernelGGL((render_kernel_lds4<COUNT>), dim3(grid), dim3(block), lds_bytes, stream, *p);
+    hipLaunchKernelGGL((render_kernel_lds4<COUNT, FEAT>), dim3(grid), dim3(block), lds_bytes, stream, *p);
     return hipGetLastError();
 }
 
-// the same over the 4-wide nodes (p->wnode, p->nwide)
-MPT_KERNEL_API hipError_t mpt_launch_render_lds4(const MptRenderParams *p, int grid, int block, size_t lds_bytes, int count,
+// the same over the 4-wide nodes (p->wnode, p->nwide); feat: the instantiation (shade_feat.h: MPT_FEAT_PLAIN or MPT_FEAT_GENERIC --
+// there is no kernel for any other mask, and asking for one is an error, not a fall-back)
+MPT_KERNEL_API hipError_t mpt_launch_render_lds4(const MptRenderParams *p, int grid, int block, size_t lds_bytes, int count, int feat,
                                              hipStream_t stream) {
-    return count ? launch_lds4<true>(p, grid, block, lds_bytes, stream) : launch_lds4<false>(p, grid, block, lds_bytes, stream);
+    if (feat == MPT_FEAT_PLAIN)
+        return count ? launch_lds4<true, MPT_FEAT_PLAIN_KERNEL>(p, grid, block, lds_bytes, stream)
+                     : launch_lds4<false, MPT_FEAT_PLAIN_KERNEL>(p, grid, block, lds_bytes, stream);
+    if (feat != MPT_FEAT_GENERIC) return hipErrorInvalidValue;
+    return count ? launch_lds4<true, MPT_FEAT_GENERIC>(p, grid, block, lds_bytes, stream)
+                 : launch_lds4<false, MPT_FEAT_GENERIC>(p, grid, block, lds_bytes, stream);
 }
 
 // lds_bytes = scene records + 2 KiB per stack level; grid = one persistent workgroup per CU

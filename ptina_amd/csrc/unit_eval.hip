@@ -162,7 +162,7 @@ __global__ __launch_bounds__(64) void MPT_SUFFIX(unit_eval_kernel)(const MptRend
         get_geometries(p, hit, v3s(0.0f), ld(r, 0), &hitpos, &normal, m);
 #else
         const UnitScene sc;
-        get_geometries_rec(p, sc, shade_rec_load<false>(p, row), hit, v3s(0.0f), ld(r, 0), &hitpos, &normal, m);
+        get_geometries_rec<MPT_FEAT_GENERIC>(p, sc, shade_rec_load<false>(p, row), hit, v3s(0.0f), ld(r, 0), &hitpos, &normal, m);
 #endif
         const MptVec4 *s = p.tshade + (size_t)row * 4;
         V3 plain; float tu, tv;
