@@ -768,7 +768,13 @@ DEV float GTR1(float cosh_, float alpha) {                                   // 
 }
 DEV float GTR2(float cosh_, float alpha) {                                   // :38-41
     float alpha2 = alpha * alpha;
+#if MPT_STRICT
     float t = 1.0f + (alpha2 - 1.0f) * (cosh_ * cosh_);
+#else
+    // pinned (seam 1 of profiles/r08_ab_experiments.json): every production kernel forms alpha^2 - 1 as one fma; left to
+    // -ffp-contract=fast, a SHADE compiled without the clearcoat region found alpha * alpha in another block and subtracted
+    float t = 1.0f + __builtin_fmaf(alpha, alpha, -1.0f) * (cosh_ * cosh_);
+#endif
     return m_div(alpha2, MPT_PI * (t * t));
 }
 DEV float smithGGX(float cosi, float alpha) {                                // :45-48
@@ -776,6 +782,27 @@ DEV float smithGGX(float cosi, float alpha) {                                // 
     float b = cosi * cosi;
     return m_rcp(cosi + m_sqrt(a + b - a * b));
 }
+// the same as Disney.brdf evaluates it (four calls: two lobes x two directions)
+#if MPT_STRICT
+DEV float smithGGX_eval(float cosi, float alpha) { return smithGGX(cosi, alpha); }
+#else
+// a + b as one rounded v_add_f32 whatever a and b are.  (Not "#pragma clang fp contract(off)": with -ffp-contract=fast on the command
+// line the back end fuses globally and a product still goes into the sum -- seen in the ISA.)
+DEV float add_unfused(float a, float b) {
+    float s;
+    asm("v_add_f32 %0, %1, %2" : "=v"(s) : "v"(a), "v"(b));
+    return s;
+}
+// pinned (seam 2): with the clearcoat lobe next to it, cosi * cosi serves smithGGX(cosi, 0.25) and smithGGX(cosi, alpha) and the
+// production kernels round both squares, add them, and fuse only a * b into the difference.  Compiled without one of the two
+// lobes, -ffp-contract=fast fused one of the squares into the sum instead (cosi * cosi without the clearcoat region, alpha *
+// alpha without the transmission region): 181 film elements of s978 at 128 x 128 x 16 moved by one ulp.
+DEV float smithGGX_eval(float cosi, float alpha) {
+    const float a = alpha * alpha;
+    const float b = cosi * cosi;
+    return m_rcp(cosi + m_sqrt(__builtin_fmaf(-a, b, add_unfused(a, b))));
+}
+#endif
 DEV V3 sample_GTR1(float u, float v, float alpha) {                          // :69-71 (NaN for alpha < 1, like the reference)
     u = m_div(m_sqrt(m_pow(alpha, 2.0f - 2.0f * u) - 1.0f), alpha * alpha - 1.0f);
     return spherical(u, v);
@@ -929,7 +956,7 @@ DEV V3 disney_brdf(const Disney &m, V3 normal, float sign, V3 indir, V3 outdir) 
 
         float Ds = GTR2(cosh_, m.alpha);
         V3 Fs = lerpv(Foh, m.speccolor, v3s(1.0f));
-        float Gs = smithGGX(cosi, m.alpha) * smithGGX(coso, m.alpha);
+        float Gs = smithGGX_eval(cosi, m.alpha) * smithGGX_eval(coso, m.alpha);
         V3 diffuse = m.basecolor * (MPT_INV_PI * lerpf(m.subsurface, Fd, ss)) + Fsheen;
 #if MPT_STRICT
         float fdf = dielectricFresnel(etao, etai, cosoh);
@@ -944,7 +971,7 @@ DEV V3 disney_brdf(const Disney &m, V3 normal, float sign, V3 indir, V3 outdir) 
         float coat = 0.0f;
         if (COAT && m.clearcoat != 0.0f) {
             float Dr = GTR1(cosh_, m.clearcoatAlpha);
-            float Gr = smithGGX(cosi, 0.25f) * smithGGX(coso, 0.25f);
+            float Gr = smithGGX_eval(cosi, 0.25f) * smithGGX_eval(coso, 0.25f);
             float Fr = lerpf(Foh, 0.04f, 1.0f);
             coat = 0.25f * m.clearcoat * Gr * Fr * Dr;
         }

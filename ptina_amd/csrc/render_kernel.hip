@@ -1182,9 +1182,10 @@ __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds(const MptRend
 // dynamic LDS: [ nwide node records of MPT_LDS4_NODE_STRIDE bytes | (n+1)*3 triangle float4 (tfast; record n: the unused slots' NaNs) |
 //                (lds_nmats+1)*6 material float4 (the records the model uses, then the default one) | n material-record bytes,
 //                padded to 16 | lds_stack x 1024 int16 ]
-// Two instantiations per COUNT: FEAT = MPT_FEAT_GENERIC (every region of SHADE) and MPT_FEAT_PLAIN_KERNEL, launched for a plain scene
+// Two instantiations per COUNT: FEAT = MPT_FEAT_GENERIC (every region of SHADE) and MPT_FEAT_PLAIN, launched for a plain scene
 // (untextured materials without clearcoat or transmission, one light, no environment map: the headline scene and BASELINE's
-// configs 1, 2, 3, 5): without the texture, environment-map and light-list regions (shade_feat.h says why the two lobes stay)
+// configs 1, 2, 3, 5): without the texture, environment-map and light-list regions and without the clearcoat and transmission
+// lobes (shade_feat.h: what keeps its film the generic one's bit for bit)
 template <bool COUNT, int FEAT>
 __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds4(const MptRenderParams p) {
     extern __shared__ __attribute__((aligned(16))) MptVec4 smem[];
@@ -1358,8 +1359,8 @@ static hipError_t launch_lds4(const MptRenderParams *p, int grid, int block, siz
 MPT_KERNEL_API hipError_t mpt_launch_render_lds4(const MptRenderParams *p, int grid, int block, size_t lds_bytes, int count, int feat,
                                              hipStream_t stream) {
     if (feat == MPT_FEAT_PLAIN)
-        return count ? launch_lds4<true, MPT_FEAT_PLAIN_KERNEL>(p, grid, block, lds_bytes, stream)
-                     : launch_lds4<false, MPT_FEAT_PLAIN_KERNEL>(p, grid, block, lds_bytes, stream);
+        return count ? launch_lds4<true, MPT_FEAT_PLAIN>(p, grid, block, lds_bytes, stream)
+                     : launch_lds4<false, MPT_FEAT_PLAIN>(p, grid, block, lds_bytes, stream);
     if (feat != MPT_FEAT_GENERIC) return hipErrorInvalidValue;
     return count ? launch_lds4<true, MPT_FEAT_GENERIC>(p, grid, block, lds_bytes, stream)
                  : launch_lds4<false, MPT_FEAT_GENERIC>(p, grid, block, lds_bytes, stream);

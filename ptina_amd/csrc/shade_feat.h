@@ -20,12 +20,12 @@ enum {
     MPT_FEAT_WORLD_TEXTURE = 8,     /* the world light has an environment map */
     MPT_FEAT_MANY_LIGHTS = 16,      /* the light list does not hold exactly one light */
     MPT_FEAT_PLAIN = 0,
-    MPT_FEAT_GENERIC = 31,
-    /* What the kernel selected for a plain scene is compiled WITH: the clearcoat and transmission regions stay in it.  Compiled
-     * without them the film of the benchmark scene differs from the generic kernel's in last bits (MI355X, s978 128 x 128 x 16:
-     * 181 of 16384 film elements without the clearcoat code, 5 without the transmission code; none without each of the other
-     * three) -- -ffp-contract=fast fuses the multiply-adds around the removed branches differently -- and results come first. */
-    MPT_FEAT_PLAIN_KERNEL = MPT_FEAT_CLEARCOAT | MPT_FEAT_TRANSMISSION
+    MPT_FEAT_GENERIC = 31
+    /* The plain kernel is compiled without all five regions and renders the generic kernel's film bit for bit.  That is not free:
+     * -ffp-contract=fast fuses the multiply-adds AROUND a removed branch as it pleases, and without the clearcoat and transmission
+     * regions a few film elements moved by one ulp (MI355X, s978 128 x 128 x 16: 181 of 16384 without the clearcoat code, 5 without
+     * the transmission code) until the two places where the fusing differed were written out -- pt_device.h GTR2 and smithGGX_eval;
+     * profiles/r08_ab_experiments.json lists them and how they were found.  A new region compiled out wants the same check. */
 };
 
 /* One material as mpt_load_materials receives it: fac[12][4] (parameter k's factor in fac[k*4], basecolor in
