@@ -206,10 +206,9 @@ extern "C" void mpt_destroy(mpt_ctx *c) {
     }
     if (c->ev_main) hipEventDestroy(c->ev_main);
     if (c->ev_film) hipEventDestroy(c->ev_film);
-    for (auto &pr : c->events) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
+    for (MptLaunchTimer *t : { &c->render_timer, &c->mlt_timer, &c->brute_timer })
+        for (auto &ev : t->events) hipEventDestroy(ev);
     for (auto &ev : c->event_pool) hipEventDestroy(ev);
-    for (auto &ev : c->mlt_events) hipEventDestroy(ev);
-    for (auto &ev : c->brute_events) hipEventDestroy(ev);
     hipFree(c->mlt_X); hipFree(c->mlt_L); hipFree(c->mlt_bit); hipFree(c->mlt_keys); hipFree(c->mlt_keys2);
     hipFree(c->mlt_vals); hipFree(c->mlt_vals2); hipFree(c->mlt_tmp); hipFree(c->mlt_runs);
     for (int p = 0; p < 3; p++) hipFree(c->film[p]);
@@ -734,10 +733,16 @@ static int fill_scene_params(mpt_ctx *c, MptRenderParams &p) {
     return 0;
 }
 
-static int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes) {
+// "not set up yet": fails at the call, not at the deferred launch
+static int check_ready(const mpt_ctx *c) {
     if (c->nx <= 0) return fail("film size not set: call set_size() first");
     if (!c->sV) return fail("sobol sampler not initialised");
     if (!c->tree_valid) return fail("BVH not built: call build_tree() after load_model()");
+    return 0;
+}
+
+static int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes) {
+    if (check_ready(c)) return 1;
     // the production kernels address a frame's Sobol row and a triangle's shading record by 32-bit offsets from a scalar base, and
     // multiply frame x dimension in 24 bits (lane_draws, shade_rec_load)
     if ((long long)nframes * c->sdim >= (1ll << 30) || nframes >= (1 << 24) || c->sdim >= (1 << 24))
@@ -790,93 +795,94 @@ static hipEvent_t get_event(mpt_ctx *c) {
     return e;
 }
 
+// levels of the per-lane traversal stack of the gather, preview, Metropolis and brute-force kernels (two instantiations each)
+static int gather_stack_levels(const mpt_ctx *c) {
+    return ((c->mode == MPT_MODE_STRICT ? c->tree_depth : c->fast_depth) + 2 <= 32) ? 32 : 64;
+}
+
 static int mlt_flush(mpt_ctx *c);
 
-extern "C" int mpt_flush(mpt_ctx *c) {
-    if (!c) return fail("null context");
-    if (c->mlt_pending && mlt_flush(c)) return 1;    // (Metropolis iterations and PathEngine frames are never pending together)
-    if (c->pending == 0) return 0;
-    HIP_TRY(hipSetDevice(c->device));
-    int B = c->pending;
-    c->pending = 0;
-    MptRenderParams p;
-    if (fill_params(c, p, B)) return 1;
-    const bool fast = c->mode == MPT_MODE_FAST;
-    // fast build: this batch runs on its own stream; strict build: everything stays on the main stream
-    if (fast) {
-        // A launch ends with a drain of about one path latency (~0.4 ms on MI355X for depth-5 paths)
-        // in which its lanes run empty one by one; a persistent workgroup leaves only when its
-        // slowest lane has.  A launch that owns every CU pays that on every CU.  Small launches
-        // therefore take 1/G of the CUs each and G of them are resident at once, in different
-        // phases: the drain then idles 1/G of the chip.  (Measured, 1/8 film slab of 512x512x32:
-        // 1.03 ms per step with G=1, 0.78 with G=2, 0.73 with G=4; whole film: 4.69 / 4.62 / 4.84.)
-        long long cols = 0;
-        share_extent(c, 1, &cols, nullptr);
-        const double per_lane = (double)B * cols * c->ny / ((double)c->num_cus * 1024.0);
-        int div = c->grid_div > 0 ? c->grid_div : (per_lane >= 24.0 ? 1 : per_lane >= 6.0 ? 2 : 4);
-        int depth = c->pipe_depth > 0 ? c->pipe_depth : (div == 1 ? 2 : std::min(div + 2, (int)MPT_MAX_PIPE));
-        if (depth != c->cur_depth) {
-            // slots are reused round-robin: let everything in flight finish before the ring changes size
-            HIP_TRY(hipStreamSynchronize(c->aux));
-            for (int q = 0; q < MPT_MAX_PIPE; q++) HIP_TRY(hipStreamSynchronize(c->rstream[q]));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            c->flip = 0;
-        }
-        c->cur_depth = depth; c->cur_div = div;
+// ------------------------------------------------------------------ mpt_flush, step by step
+// where a batch runs: its slot of the ring, the stream of its render kernel and the stream its points are prepared on
+struct BatchSlot {
+    bool fast;         // fast build: this batch runs on its own stream; strict build: everything stays on the main stream
+    int k;
+    hipStream_t rs;    // the render
+    hipStream_t ss;    // fast build: the Sobol points and the zeroed queue heads of this batch are prepared on the aux
+                       // stream (never behind a render kernel), the render itself goes to rstream[k]
+};
+
+// step 1 (fast build): how many launches share the chip and how many ring slots they rotate through
+static int ring_policy(mpt_ctx *c, int B) {
+    // A launch ends with a drain of about one path latency (~0.4 ms on MI355X for depth-5 paths)
+    // in which its lanes run empty one by one; a persistent workgroup leaves only when its
+    // slowest lane has.  A launch that owns every CU pays that on every CU.  Small launches
+    // therefore take 1/G of the CUs each and G of them are resident at once, in different
+    // phases: the drain then idles 1/G of the chip.  (Measured, 1/8 film slab of 512x512x32:
+    // 1.03 ms per step with G=1, 0.78 with G=2, 0.73 with G=4; whole film: 4.69 / 4.62 / 4.84.)
+    long long cols = 0;
+    share_extent(c, 1, &cols, nullptr);
+    const double per_lane = (double)B * cols * c->ny / ((double)c->num_cus * 1024.0);
+    int div = c->grid_div > 0 ? c->grid_div : (per_lane >= 24.0 ? 1 : per_lane >= 6.0 ? 2 : 4);
+    int depth = c->pipe_depth > 0 ? c->pipe_depth : (div == 1 ? 2 : std::min(div + 2, (int)MPT_MAX_PIPE));
+    if (depth != c->cur_depth) {
+        // slots are reused round-robin: let everything in flight finish before the ring changes size
+        HIP_TRY(hipStreamSynchronize(c->aux));
+        for (int q = 0; q < MPT_MAX_PIPE; q++) HIP_TRY(hipStreamSynchronize(c->rstream[q]));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->flip = 0;
     }
-    const int k = fast ? (c->flip++ % c->cur_depth) : 0;
-    hipStream_t rs = fast ? c->rstream[k] : c->stream;
-    // fast build: the Sobol points and the zeroed queue heads of this batch are prepared on the aux
-    // stream (never behind a render kernel), the render itself goes to rstream[k]
-    hipStream_t ss = fast ? c->aux : c->stream;
-    if (fast) {
+    c->cur_depth = depth; c->cur_div = div;
+    return 0;
+}
+
+// step 2: the batch's Sobol points (p.P) and, if they were made ahead of time, its zeroed queue heads (*use_spec).  A batch
+// without tiles (p.ntiles == 0: an empty share) only moves the sampler.
+static int batch_points(mpt_ctx *c, MptRenderParams &p, const BatchSlot &s, int B, bool *use_spec) {
+    const int k = s.k;
+    if (s.fast) {
         if (c->main_dirty) {       // uploads / resets / option changes enqueued on the main stream come first
             HIP_TRY(hipEventRecord(c->ev_main, c->stream));
             c->main_dirty = false;
         }
-        HIP_TRY(hipStreamWaitEvent(ss, c->ev_main, 0));
-        HIP_TRY(hipStreamWaitEvent(ss, c->ev_render[k], 0));   // the batch that last read sP2[k] / d_work2[k]
-        HIP_TRY(hipStreamWaitEvent(rs, c->ev_main, 0));
+        HIP_TRY(hipStreamWaitEvent(s.ss, c->ev_main, 0));
+        HIP_TRY(hipStreamWaitEvent(s.ss, c->ev_render[k], 0));   // the batch that last read sP2[k] / d_work2[k]
+        HIP_TRY(hipStreamWaitEvent(s.rs, c->ev_main, 0));
         p.P = c->sP2[k];
     }
     // the points (and zeroed queue heads) of this batch may have been prepared when the previous one was launched
-    const bool use_spec = fast && p.ntiles != 0 && c->spec_valid && c->spec_slot == k && c->spec_B == B &&
-                          c->spec_time == c->stime;
+    *use_spec = s.fast && p.ntiles != 0 && c->spec_valid && c->spec_slot == k && c->spec_B == B && c->spec_time == c->stime;
     c->spec_valid = false;
     if (p.ntiles == 0) {
-        if (sobol_advance(c, B, 0, ss, fast ? c->sP2[k] : nullptr)) return 1;
-        if (fast) { HIP_TRY(hipEventRecord(c->ev_sobol2[k], ss)); HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_sobol2[k], 0)); }
+        if (sobol_advance(c, B, 0, s.ss, s.fast ? c->sP2[k] : nullptr)) return 1;
+        if (s.fast) { HIP_TRY(hipEventRecord(c->ev_sobol2[k], s.ss)); HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_sobol2[k], 0)); }
         return 0;
     }
-    if (use_spec) {
+    if (*use_spec) {
         // the points AND the state this batch leaves behind were computed when the previous batch was launched: the sampler moves by
         // a swap of two pointers -- no kernel at launch time (round 3 ran an X-only update here, whose 83 small workgroups took
         // CUs just when the persistent render workgroups wanted them: half the workgroups of a 1/8-share launch started 35 us late)
         std::swap(c->sX, c->sX_spec);
         c->stime = (int32_t)((uint32_t)c->stime + (uint32_t)B);
-    } else if (sobol_advance(c, B, B, ss, fast ? c->sP2[k] : nullptr)) return 1;
+    } else if (sobol_advance(c, B, B, s.ss, s.fast ? c->sP2[k] : nullptr)) return 1;
+    return 0;
+}
 
-    const int stack = ((c->mode == MPT_MODE_STRICT ? c->tree_depth : c->fast_depth) + 2 <= 32) ? 32 : 64;
-    // LDS-resident kernel: node (64 B, MPT_LDS_NODE_STRIDE apart) + triangle (48 B) records + a 16-bit stack of (depth+1) levels x 1024
-    // lanes must fit the CU's 160 KiB; ids must fit int16
-    const int lds_stack = c->fast_depth + 1;            // sentinel + one pending sibling (node or leaf) per level
-    // + the material records (96 B each, the default one last) and one byte per triangle naming its record
-    const size_t lds_bytes = ((((size_t)(c->nfaces - 1) * MPT_LDS_NODE_STRIDE + 15) >> 4) + (size_t)c->nfaces * 3 + (size_t)(c->caps.max_materials + 1) * 6) * sizeof(MptVec4) +
-                             (((size_t)c->nfaces + 15) & ~(size_t)15) + (size_t)lds_stack * 1024 * sizeof(short);
-    // ... or the 4-wide nodes with exact boxes (option "lds_wide"): seven float4 of a wnode record MPT_LDS4_NODE_STRIDE apart, one
-    // triangle record more (the unused slots' leaf), only the material records the model uses (+ the default one), and every
-    // stack level the tree can ask for (a step leaves up to three entries behind)
-    const int lds4_nmats = c->max_mtlid + 1;
-    const size_t lds4_bytes = ((size_t)c->wide_nodes * (MPT_LDS4_NODE_STRIDE / 16) + ((size_t)c->nfaces + 1) * 3 + (size_t)(lds4_nmats + 1) * 6) * sizeof(MptVec4) +
-                              (((size_t)c->nfaces + 15) & ~(size_t)15) + (size_t)c->wide_stack * 1024 * sizeof(short);
-    const bool lds4_kernel = fast && c->use_lds && c->lds_wide && c->use_wide && c->wide_nodes > 0 && c->wide_stack > 0 && c->wnode &&
-                             c->nfaces >= 2 && c->nfaces < 4095 && lds4_nmats < 255 && lds4_bytes <= 160 * 1024 &&
-                             (size_t)c->wide_nodes * MPT_LDS4_NODE_STRIDE < 65536;   // (16-bit ids: a node's is its record's LDS address, a leaf's 16 * slot + 1)
-    const bool lds_kernel = lds4_kernel ||
-                            (fast && c->use_lds && c->nfaces >= 2 && c->nfaces < 32768 && c->caps.max_materials < 256 &&
-                             lds_bytes <= 160 * 1024 &&
-                             (size_t)(c->nfaces - 1) * (MPT_LDS_NODE_STRIDE / 8) < 32768);   // (the LDS copy's node ids are byte offsets / 8 in an int16 stack)
-    p.lds_nmats = lds4_nmats;                           // (render_kernel_lds4: the material records it keeps in LDS)
+// step 3a: which kernel serves the scene, and the dynamic LDS it asks for (lds_layout.h: the layout, the fit rule and the choice)
+static MptKernelChoice choose_kernel(const mpt_ctx *c) {
+    MptKernelFacts f;
+    f.fast = c->mode == MPT_MODE_FAST;
+    f.use_lds = c->use_lds; f.lds_wide = c->lds_wide; f.use_wide = c->use_wide;
+    f.nfaces = c->nfaces;
+    f.wide_nodes = c->wide_nodes; f.wide_stack = c->wide_stack; f.have_wnode = c->wnode != nullptr;
+    f.max_mtlid = c->max_mtlid; f.max_materials = c->caps.max_materials;
+    f.fast_depth = c->fast_depth;
+    return mpt_choose_kernel(&f);
+}
+
+// step 3b: the work items of the launch -- (tile, chunk of frames) -- into p; returns the columns of this context's share, padded
+// to whole work-item tiles
+static int work_items(const mpt_ctx *c, MptRenderParams &p, int B, bool fast) {
     int chunk = B, nchunks = 1;
     const int tw = 1 << c->tile_w_shift, th = 1 << c->tile_h_shift;
     int tile_cols = 0;
@@ -898,40 +904,55 @@ extern "C" int mpt_flush(mpt_ctx *c) {
     p.chunk = chunk; p.nchunks = nchunks;
     p.nitems = tiles8 * nchunks;
     p.tile_w_shift = c->tile_w_shift; p.tile_h_shift = c->tile_h_shift;
-    if (fast) {
-        // one float4 per sample: [frame][pixel]; the combine pass sums frames in order
-        // ... of this context's share only: its columns packed side by side, padded to whole work-item tiles
-        const int ccols = tile_cols * tw;
-        p.partial_stride = ccols * c->ny;
-        size_t need = (size_t)B * (size_t)ccols * c->ny;
-        // every slot of the ring at once: an allocation synchronises the device, so it must not
-        // happen again on the second, third, ... batch of a run
-        bool zeroed = false;
-        for (int q = 0; q < c->cur_depth; q++)
-            if (need > c->partial2_cap[q]) {
-                HIP_TRY(hipDeviceSynchronize());
-                hipFree(c->partial2[q]); c->partial2[q] = nullptr; c->partial2_cap[q] = 0;
-                if (dev_alloc(&c->partial2[q], need)) return 1;
-                c->partial2_cap[q] = need;
-                // the w of a slab entry is its ready flag for the tail finalisation (the launch's tag): fresh memory must not
-                // hold one by accident -- and it does: the allocator hands back the slab of an earlier context, whose first
-                // finalising launch used the very tag this context's first one will use
-                HIP_TRY(hipMemsetAsync(c->partial2[q], 0, need * sizeof(MptVec4), c->stream));
-                zeroed = true;
-            }
-        // ... and the zeros must be there before any launch of the ring writes or reads the slab: the render streams are not
-        // ordered behind the stream that zeroes, and a memset may return before it is done.  (Seen in the full GPU test run as a
-        // 2048 x 2048 film with single samples of an earlier test's render in it: its 2 GiB slabs take a millisecond to zero.)
-        if (zeroed) HIP_TRY(hipStreamSynchronize(c->stream));
-        p.partial = c->partial2[k];
-        p.work_counter = c->d_work2[k];
-        if (!use_spec) {
-            HIP_TRY(hipMemsetAsync(c->d_work2[k], 0, MPT_QUEUE_WORDS * sizeof(unsigned int), ss));   // 8 queue heads + the finalisation's tile counter
-            HIP_TRY(hipEventRecord(c->ev_sobol2[k], ss));
+    return tile_cols * tw;
+}
+
+// Grow a per-slot buffer of the ring to `need` elements -- every slot of the ring at once: an allocation synchronises the
+// device, so it must not happen again on the second, third, ... batch of a run.  zero: fresh memory is zeroed on the main
+// stream; *grown: a slot was replaced.
+template <class T>
+static int grow_ring(mpt_ctx *c, T *(&buf)[MPT_MAX_PIPE], size_t (&cap)[MPT_MAX_PIPE], size_t need, bool zero, bool *grown) {
+    for (int q = 0; q < c->cur_depth; q++)
+        if (need > cap[q]) {
+            HIP_TRY(hipDeviceSynchronize());
+            hipFree(buf[q]); buf[q] = nullptr; cap[q] = 0;
+            if (dev_alloc(&buf[q], need)) return 1;
+            cap[q] = need;
+            if (zero) HIP_TRY(hipMemsetAsync(buf[q], 0, need * sizeof(T), c->stream));
+            *grown = true;
         }
-        HIP_TRY(hipStreamWaitEvent(rs, c->ev_sobol2[k], 0));
-        HIP_TRY(hipStreamWaitEvent(rs, c->ev_free[k], 0));   // combine of the batch that last used partial[k]
+    return 0;
+}
+
+// step 4 (fast build): the sample slab of the ring's slots, this batch's queue heads, and what its render stream waits for
+static int slab_and_queue_heads(mpt_ctx *c, MptRenderParams &p, const BatchSlot &s, int B, int ccols, bool use_spec) {
+    const int k = s.k;
+    // one float4 per sample: [frame][pixel]; the combine pass sums frames in order
+    // ... of this context's share only: its columns packed side by side, padded to whole work-item tiles
+    p.partial_stride = ccols * c->ny;
+    const size_t need = (size_t)B * (size_t)ccols * c->ny;
+    // the w of a slab entry is its ready flag for the tail finalisation (the launch's tag): fresh memory must not
+    // hold one by accident -- and it does: the allocator hands back the slab of an earlier context, whose first
+    // finalising launch used the very tag this context's first one will use
+    bool zeroed = false;
+    if (grow_ring(c, c->partial2, c->partial2_cap, need, true, &zeroed)) return 1;
+    // ... and the zeros must be there before any launch of the ring writes or reads the slab: the render streams are not
+    // ordered behind the stream that zeroes, and a memset may return before it is done.  (Seen in the full GPU test run as a
+    // 2048 x 2048 film with single samples of an earlier test's render in it: its 2 GiB slabs take a millisecond to zero.)
+    if (zeroed) HIP_TRY(hipStreamSynchronize(c->stream));
+    p.partial = c->partial2[k];
+    p.work_counter = c->d_work2[k];
+    if (!use_spec) {
+        HIP_TRY(hipMemsetAsync(c->d_work2[k], 0, MPT_QUEUE_WORDS * sizeof(unsigned int), s.ss));   // 8 queue heads + the finalisation's tile counter
+        HIP_TRY(hipEventRecord(c->ev_sobol2[k], s.ss));
     }
+    HIP_TRY(hipStreamWaitEvent(s.rs, c->ev_sobol2[k], 0));
+    HIP_TRY(hipStreamWaitEvent(s.rs, c->ev_free[k], 0));   // combine of the batch that last used partial[k]
+    return 0;
+}
+
+// step 5: is the ring idle, and how many CUs does this launch take (c->last_div: the share)
+static int launch_share(mpt_ctx *c, bool fast, bool *ring_idle, int *launch_cus) {
     // Persistent workgroups hold their CUs for a whole launch, and the launches of the ring keep every CU taken
     // all the time: a foreign kernel -- RCCL's send/recv kernel of the film gather -- waits for a launch to end
     // (measured with mpt_probe_kernel on MI355X: median 0.13-0.47 ms, up to 2.2 ms beside a 1/8 share's launches,
@@ -946,51 +967,45 @@ extern "C" int mpt_flush(mpt_ctx *c) {
     // read-back (bench.py's `value`, an interactive frame) is one launch at a time -- so it takes every CU; 1/G of
     // them would only make it G times longer.  Launches issued while others are still in flight take 1/G each.
     int launch_div = std::max(c->cur_div, 1);
-    bool ring_idle = fast;
+    *ring_idle = fast;
     if (fast && ((launch_div > 1 && c->grid_div <= 0) || c->finalise)) {
-        for (int q = 0; q < c->cur_depth && ring_idle; q++) {
+        for (int q = 0; q < c->cur_depth && *ring_idle; q++) {
             hipError_t st = hipEventQuery(c->ev_render[q]);
-            if (st == hipErrorNotReady) ring_idle = false;
+            if (st == hipErrorNotReady) *ring_idle = false;
             else if (st != hipSuccess) HIP_TRY(st);
         }
     }
-    if (fast && launch_div > 1 && c->grid_div <= 0 && ring_idle) launch_div = 1;
+    if (fast && launch_div > 1 && c->grid_div <= 0 && *ring_idle) launch_div = 1;
     c->last_div = launch_div;
-    const int launch_cus = std::max(usable_cus / launch_div, 1);   // G launches never claim more than usable_cus
-    // scenes that do not fit LDS walk the 4-wide nodes (option "wide"; built by mpt_build_tree unless too deep)
-    // A wide step costs ~2x the VALU instructions of a binary one (four slab tests and a sorting network) and makes
-    // half the dependent fetches; with the planes picked by direction sign it wins on both big configurations
-    // (MI355X: C4 963 -> 1135 Msamples/s, C5 494 -> 520), so it is the default wherever the collapse was built.
-    const bool wide_pays = c->use_wide != 0;
-    const bool wide_kernel = fast && !lds_kernel && wide_pays && c->wide_nodes > 0;
-    int wide_blocks = 0;
-    if (wide_kernel) {
-        HIP_TRY(mpt_wide_blocks(launch_cus, c->count, c->use_quant, &wide_blocks));
-        const size_t need_spill = (size_t)wide_blocks * MPT_BLOCK * 128;   // >= SpillStack::SPILL entries per lane (128 - LDS levels)
-        // every slot of the ring at once (an allocation synchronises the device), and one strip PER SLOT: the launches of
-        // different slots overlap, and a strip is indexed by block and lane only
-        for (int q = 0; q < c->cur_depth; q++)
-            if (need_spill > c->stack_spill2_cap[q]) {
-                HIP_TRY(hipDeviceSynchronize());
-                hipFree(c->stack_spill2[q]); c->stack_spill2[q] = nullptr; c->stack_spill2_cap[q] = 0;
-                if (dev_alloc(&c->stack_spill2[q], need_spill)) return 1;
-                c->stack_spill2_cap[q] = need_spill;
-            }
+    *launch_cus = std::max(usable_cus / launch_div, 1);   // G launches never claim more than usable_cus
+    return 0;
+}
+
+// step 6: what depends on launch_cus -- the spill strips of the 4-wide gather kernel (*wide_blocks: its workgroups), the lanes
+// per workgroup of the LDS-resident kernels (*lds_block), the timeline buffer
+static int size_launch_buffers(mpt_ctx *c, MptRenderParams &p, int k, int kernel, int launch_cus, int *wide_blocks, int *lds_block) {
+    *wide_blocks = 0;
+    if (kernel == MPT_KERNEL_WIDE) {
+        HIP_TRY(mpt_wide_blocks(launch_cus, c->count, c->use_quant, wide_blocks));
+        const size_t need_spill = (size_t)*wide_blocks * MPT_BLOCK * 128;   // >= SpillStack::SPILL entries per lane (128 - LDS levels)
+        // one strip PER SLOT: the launches of different slots overlap, and a strip is indexed by block and lane only
+        bool grown = false;
+        if (grow_ring(c, c->stack_spill2, c->stack_spill2_cap, need_spill, false, &grown)) return 1;
         p.stack_spill = c->stack_spill2[k];
     }
+    const bool lds_kernel = kernel == MPT_KERNEL_LDS || kernel == MPT_KERNEL_LDS4;
     // Lanes per persistent workgroup of the LDS-resident kernel.  A launch that gives a lane fewer than six samples (an eighth
     // of the benchmark film: four) is over before a steady state forms: its length is a few path latencies, and a path is
     // faster with three waves per SIMD than with four (MI355X, 1/8 share: 0.78 ms at 768 lanes against 0.84 at 1024; from a
     // quarter share upwards 1024 is as good or better).  Same film either way.
     // (The kernel over the 4-wide nodes is fastest with 1024 lanes at every size: solo launch of a 1/8 share 0.49 ms against 0.53
     // at 768, 0.64 at 512; whole film 2.59 / 2.97 / 3.94.)
-    int lds_block_used = c->lds_block ? c->lds_block : 1024;
-    if (lds_kernel && !lds4_kernel && c->lds_block == 0 &&
-        ((long long)p.nitems * chunk << (c->tile_w_shift + c->tile_h_shift)) < 6ll * launch_cus * 1024) lds_block_used = 768;
+    *lds_block = c->lds_block ? c->lds_block : 1024;
+    if (kernel == MPT_KERNEL_LDS && c->lds_block == 0 &&
+        ((long long)p.nitems * p.chunk << (c->tile_w_shift + c->tile_h_shift)) < 6ll * launch_cus * 1024) *lds_block = 768;
     p.timeline = nullptr;
     if (c->timeline && lds_kernel) {
-        const int block = lds_block_used;
-        const int waves = launch_cus * (block / 64);
+        const int waves = launch_cus * (*lds_block / 64);
         if (waves != c->timeline_waves) {
             HIP_TRY(hipDeviceSynchronize());
             hipFree(c->d_timeline); c->d_timeline = nullptr;
@@ -1001,101 +1016,143 @@ extern "C" int mpt_flush(mpt_ctx *c) {
         }
         p.timeline = c->d_timeline;
     }
-    // Tail finalisation: a launch that has the chip to itself -- a step that ends with a read-back, an interactive frame -- adds
-    // its frames to the film, resolves and writes the image out by itself, in the shadow of its own drain (finalise_tiles).  A
-    // launch issued while another is in flight keeps the combine pass on the main stream: two launches must not add to the same
-    // film pixels at the same time, and the main stream is what orders them.
-    const bool fin = fast && c->finalise && ring_idle && p.nitems > 0;
+    return 0;
+}
+
+// step 7: number the launch and, if it finalises its tiles itself (fin), give it its slab tag, order it behind the main stream's
+// work on the film and tell it where the early image goes
+// Tail finalisation: a launch that has the chip to itself -- a step that ends with a read-back, an interactive frame -- adds
+// its frames to the film, resolves and writes the image out by itself, in the shadow of its own drain (finalise_tiles).  A
+// launch issued while another is in flight keeps the combine pass on the main stream: two launches must not add to the same
+// film pixels at the same time, and the main stream is what orders them.
+static int setup_finalisation(mpt_ctx *c, MptRenderParams &p, const BatchSlot &s, bool fin) {
     c->launch_seq++;
     p.fin_counter = nullptr; p.image_out = nullptr; p.slab_tag = MPT_TAG_COMBINE;
     c->film_version++;                           // this batch changes pass 0, whoever adds it
-    if (fin) {
-        // the 16-bit tag both halves of every sample entry of this launch carry (film_ops.h): never 0 (fresh memory) or 1 (a launch
-        // that keeps the combine pass).  When the tags come round again no entry of any slab may still carry an old one: every slab
-        // is zeroed -- behind whatever still reads one (the ring is idle here, so only a combine pass of an earlier batch on the main
-        // stream can be pending: round-4 ADVICE), and in front of this launch AND of every later one: the next pipelined launch runs
-        // on another stream and writes another slab, which nothing would order behind that slab's memset, so the host waits for the
-        // memsets here (round-5 ADVICE; a wrap comes once in 65 534 launches)
-        const unsigned phase = c->launch_seq % (unsigned)MPT_TAG_PERIOD, epoch = c->launch_seq / (unsigned)MPT_TAG_PERIOD;
-        if (epoch != c->tag_epoch) {             // (told by the epoch, not by phase == 0: the launch with that number may have kept the combine pass)
-            c->tag_epoch = epoch;
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            for (int q = 0; q < MPT_MAX_PIPE; q++)
-                if (c->partial2[q]) HIP_TRY(hipMemsetAsync(c->partial2[q], 0, c->partial2_cap[q] * sizeof(MptVec4), rs));
-            HIP_TRY(hipStreamSynchronize(rs));
-            c->tag_wraps++;
-        }
-        p.fin_counter = c->d_work2[k] + 8 * MPT_QUEUE_STRIDE;
-        p.slab_tag = (unsigned)MPT_TAG_FIRST + phase;
-        // everything the main stream still has to do to the film (an earlier batch's combine, a clear, a gather) comes first --
-        // nothing, when the stream is idle (a step that ended with a read-back): then the event pair (8 us of API calls in front of
-        // the launch, HIP trace of bench.py) is left out
-        const hipError_t main_busy = hipStreamQuery(c->stream);
-        if (main_busy == hipErrorNotReady) {
-            HIP_TRY(hipEventRecord(c->ev_film, c->stream));
-            HIP_TRY(hipStreamWaitEvent(rs, c->ev_film, 0));
-        } else if (main_busy != hipSuccess) HIP_TRY(main_busy);
-        // the resolved image as well, if the caller has said where get_image() will want it and this share is the whole film
-        const size_t img_bytes = (size_t)c->nx * c->ny * sizeof(MptVec4);
-        void *mapped = nullptr;
-        if (c->hint_image && c->finalise == 1 && c->zero_copy && c->x0 == 0 && c->x1 == c->nx && c->stripe_w == 0 && is_locked_range(c->hint_image, img_bytes) &&
-            hipHostGetDevicePointer(&mapped, c->hint_image, 0) == hipSuccess && mapped) {
-            p.image_out = (MptVec4 *)mapped;
-            c->early_ptr = c->hint_image; c->early_version = c->film_version; c->early_stream = rs;
-        }
-    }
     c->last_finalised = fin ? 1 : 0;
-    // SHADE compiled for what the scene uses: the LDS-resident 4-wide kernel has a plain instantiation, every other kernel the generic code
-    const int shade_feat = lds4_kernel ? shade_feat_instantiation(scene_feat_now(c), c->shade_spec) : MPT_FEAT_GENERIC;
-    hipEvent_t e0 = get_event(c), e1 = get_event(c);
-    HIP_TRY(hipEventRecord(e0, rs));
-    if (!fast) HIP_TRY(mpt_launch_render_strict(&p, p.ntiles, stack, c->count, rs));
-    else if (lds4_kernel) HIP_TRY(mpt_launch_render_lds4(&p, launch_cus, lds_block_used, lds4_bytes, c->count, shade_feat, rs));
-    else if (lds_kernel) HIP_TRY(mpt_launch_render_lds(&p, launch_cus, lds_block_used, lds_bytes, c->count, rs));
-    else if (wide_kernel) HIP_TRY(mpt_launch_render_wide(&p, wide_blocks, c->count, c->use_quant, rs));
-    else HIP_TRY(mpt_launch_render_fast(&p, launch_cus, stack, c->count, rs));
-    c->last_shade_feat = shade_feat;
-    c->last_kernel = lds4_kernel ? 5 : lds_kernel ? 1 : wide_kernel ? 2 : 0;      // (3 and 4 are retired: include/miptina.h)
-    HIP_TRY(hipEventRecord(e1, rs));
-    c->events.push_back({ e0, e1 });
-    if (c->events.size() > 4096) {
-        // nobody has asked for kernel times for a long while (an interactive session renders frame after
-        // frame): keep the newest half.  The dropped pairs were recorded at least 2048 launches ago.
-        for (size_t q = 0; q < 2048; q++) { c->event_pool.push_back(c->events[q].first); c->event_pool.push_back(c->events[q].second); }
-        c->events.erase(c->events.begin(), c->events.begin() + 2048);
+    if (!fin) return 0;
+    // the 16-bit tag both halves of every sample entry of this launch carry (film_ops.h): never 0 (fresh memory) or 1 (a launch
+    // that keeps the combine pass).  When the tags come round again no entry of any slab may still carry an old one: every slab
+    // is zeroed -- behind whatever still reads one (the ring is idle here, so only a combine pass of an earlier batch on the main
+    // stream can be pending: round-4 ADVICE), and in front of this launch AND of every later one: the next pipelined launch runs
+    // on another stream and writes another slab, which nothing would order behind that slab's memset, so the host waits for the
+    // memsets here (round-5 ADVICE; a wrap comes once in 65 534 launches)
+    const unsigned phase = c->launch_seq % (unsigned)MPT_TAG_PERIOD, epoch = c->launch_seq / (unsigned)MPT_TAG_PERIOD;
+    if (epoch != c->tag_epoch) {             // (told by the epoch, not by phase == 0: the launch with that number may have kept the combine pass)
+        c->tag_epoch = epoch;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (int q = 0; q < MPT_MAX_PIPE; q++)
+            if (c->partial2[q]) HIP_TRY(hipMemsetAsync(c->partial2[q], 0, c->partial2_cap[q] * sizeof(MptVec4), s.rs));
+        HIP_TRY(hipStreamSynchronize(s.rs));
+        c->tag_wraps++;
     }
-    if (fast) {
-        // everything later on the main stream (combine, gather, resolve, read-backs, scene changes) is
-        // ordered after this render; the next batch, on the other stream, is not
-        HIP_TRY(hipEventRecord(c->ev_render[k], rs));
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_render[k], 0));
-        if (!fin)
-            HIP_TRY(mpt_launch_combine(c->film[0], c->partial2[k], c->ny, c->x0, c->x1, p.stripe_w, p.stripe_pitch,
-                                       p.partial_stride / std::max(c->ny, 1), B, c->stream));
-        HIP_TRY(hipEventRecord(c->ev_free[k], c->stream));      // (a finalising launch has consumed its slab itself)
-        // Ahead of time, on the aux stream: the Sobol points and zeroed queue heads of the NEXT batch, assuming it
-        // has as many frames as this one and uses the next ring slot (the sampler's future is deterministic; its
-        // state X moves only when that batch is really launched).  Takes 25 us of Sobol kernel + memset off the
-        // head of every step.
-        const int k2 = c->flip % c->cur_depth;
-        if (k2 != k) {
-            HIP_TRY(hipStreamWaitEvent(ss, c->ev_render[k2], 0));   // the batch that last read sP2[k2] / d_work2[k2]
-            HIP_TRY(mpt_launch_sobol_update(c->sX, c->sX_spec, c->sV, c->sP2[k2], c->sdim, c->srows, c->stime, B, B, 1, ss));
-            HIP_TRY(hipMemsetAsync(c->d_work2[k2], 0, MPT_QUEUE_WORDS * sizeof(unsigned int), ss));
-            HIP_TRY(hipEventRecord(c->ev_sobol2[k2], ss));
-            c->spec_valid = true; c->spec_slot = k2; c->spec_B = B; c->spec_time = c->stime;
-        }
+    p.fin_counter = c->d_work2[s.k] + 8 * MPT_QUEUE_STRIDE;
+    p.slab_tag = (unsigned)MPT_TAG_FIRST + phase;
+    // everything the main stream still has to do to the film (an earlier batch's combine, a clear, a gather) comes first --
+    // nothing, when the stream is idle (a step that ended with a read-back): then the event pair (8 us of API calls in front of
+    // the launch, HIP trace of bench.py) is left out
+    const hipError_t main_busy = hipStreamQuery(c->stream);
+    if (main_busy == hipErrorNotReady) {
+        HIP_TRY(hipEventRecord(c->ev_film, c->stream));
+        HIP_TRY(hipStreamWaitEvent(s.rs, c->ev_film, 0));
+    } else if (main_busy != hipSuccess) HIP_TRY(main_busy);
+    // the resolved image as well, if the caller has said where get_image() will want it and this share is the whole film
+    const size_t img_bytes = (size_t)c->nx * c->ny * sizeof(MptVec4);
+    void *mapped = nullptr;
+    if (c->hint_image && c->finalise == 1 && c->zero_copy && c->x0 == 0 && c->x1 == c->nx && c->stripe_w == 0 && is_locked_range(c->hint_image, img_bytes) &&
+        hipHostGetDevicePointer(&mapped, c->hint_image, 0) == hipSuccess && mapped) {
+        p.image_out = (MptVec4 *)mapped;
+        c->early_ptr = c->hint_image; c->early_version = c->film_version; c->early_stream = s.rs;
     }
     return 0;
+}
+
+// step 8: the launch, between the two events of its timer
+static int launch_render(mpt_ctx *c, const MptRenderParams &p, const BatchSlot &s, MptKernelChoice kc, int launch_cus, int lds_block,
+                         int wide_blocks) {
+    // SHADE compiled for what the scene uses: the LDS-resident 4-wide kernel has a plain instantiation, every other kernel the generic code
+    const int shade_feat = kc.kernel == MPT_KERNEL_LDS4 ? shade_feat_instantiation(scene_feat_now(c), c->shade_spec) : MPT_FEAT_GENERIC;
+    const int stack = gather_stack_levels(c);
+    hipEvent_t e0 = get_event(c), e1 = get_event(c);
+    HIP_TRY(hipEventRecord(e0, s.rs));
+    switch (kc.kernel) {
+    case MPT_KERNEL_LDS4: HIP_TRY(mpt_launch_render_lds4(&p, launch_cus, lds_block, (size_t)kc.lds_bytes, c->count, shade_feat, s.rs)); break;
+    case MPT_KERNEL_LDS: HIP_TRY(mpt_launch_render_lds(&p, launch_cus, lds_block, (size_t)kc.lds_bytes, c->count, s.rs)); break;
+    case MPT_KERNEL_WIDE: HIP_TRY(mpt_launch_render_wide(&p, wide_blocks, c->count, c->use_quant, s.rs)); break;
+    default:    // MPT_KERNEL_GATHER: the binary tree, in either build
+        if (!s.fast) HIP_TRY(mpt_launch_render_strict(&p, p.ntiles, stack, c->count, s.rs));
+        else HIP_TRY(mpt_launch_render_fast(&p, launch_cus, stack, c->count, s.rs));
+    }
+    c->last_shade_feat = shade_feat;
+    c->last_kernel = kc.kernel;
+    HIP_TRY(hipEventRecord(e1, s.rs));
+    c->render_timer.record({ e0, e1 }, c->event_pool);
+    return 0;
+}
+
+// step 9 (fast build), behind the launch: the main stream is ordered after it, the combine pass, the next batch's points
+static int behind_launch(mpt_ctx *c, const MptRenderParams &p, const BatchSlot &s, int B, bool fin) {
+    const int k = s.k;
+    // everything later on the main stream (combine, gather, resolve, read-backs, scene changes) is
+    // ordered after this render; the next batch, on the other stream, is not
+    HIP_TRY(hipEventRecord(c->ev_render[k], s.rs));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_render[k], 0));
+    if (!fin)
+        HIP_TRY(mpt_launch_combine(c->film[0], c->partial2[k], c->ny, c->x0, c->x1, p.stripe_w, p.stripe_pitch,
+                                   p.partial_stride / std::max(c->ny, 1), B, c->stream));
+    HIP_TRY(hipEventRecord(c->ev_free[k], c->stream));      // (a finalising launch has consumed its slab itself)
+    // Ahead of time, on the aux stream: the Sobol points and zeroed queue heads of the NEXT batch, assuming it
+    // has as many frames as this one and uses the next ring slot (the sampler's future is deterministic; its
+    // state X moves only when that batch is really launched).  Takes 25 us of Sobol kernel + memset off the
+    // head of every step.
+    const int k2 = c->flip % c->cur_depth;
+    if (k2 != k) {
+        HIP_TRY(hipStreamWaitEvent(s.ss, c->ev_render[k2], 0));   // the batch that last read sP2[k2] / d_work2[k2]
+        HIP_TRY(mpt_launch_sobol_update(c->sX, c->sX_spec, c->sV, c->sP2[k2], c->sdim, c->srows, c->stime, B, B, 1, s.ss));
+        HIP_TRY(hipMemsetAsync(c->d_work2[k2], 0, MPT_QUEUE_WORDS * sizeof(unsigned int), s.ss));
+        HIP_TRY(hipEventRecord(c->ev_sobol2[k2], s.ss));
+        c->spec_valid = true; c->spec_slot = k2; c->spec_B = B; c->spec_time = c->stime;
+    }
+    return 0;
+}
+
+extern "C" int mpt_flush(mpt_ctx *c) {
+    if (!c) return fail("null context");
+    if (c->mlt_pending && mlt_flush(c)) return 1;    // (Metropolis iterations and PathEngine frames are never pending together)
+    if (c->pending == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    const int B = c->pending;
+    c->pending = 0;
+    MptRenderParams p;
+    if (fill_params(c, p, B)) return 1;
+    const bool fast = c->mode == MPT_MODE_FAST;
+    if (fast && ring_policy(c, B)) return 1;                                               // 1
+    BatchSlot s;
+    s.fast = fast;
+    s.k = fast ? (c->flip++ % c->cur_depth) : 0;
+    s.rs = fast ? c->rstream[s.k] : c->stream;
+    s.ss = fast ? c->aux : c->stream;
+    bool use_spec = false;
+    if (batch_points(c, p, s, B, &use_spec)) return 1;                                     // 2
+    if (p.ntiles == 0) return 0;                     // nothing to render: the sampler has moved
+    const MptKernelChoice kc = choose_kernel(c);                                           // 3
+    p.lds_nmats = c->max_mtlid + 1;                  // (render_kernel_lds4: the material records it keeps in LDS)
+    const int ccols = work_items(c, p, B, fast);
+    if (fast && slab_and_queue_heads(c, p, s, B, ccols, use_spec)) return 1;               // 4
+    bool ring_idle = false;
+    int launch_cus = 0, wide_blocks = 0, lds_block = 0;
+    if (launch_share(c, fast, &ring_idle, &launch_cus)) return 1;                          // 5
+    if (size_launch_buffers(c, p, s.k, kc.kernel, launch_cus, &wide_blocks, &lds_block)) return 1;   // 6
+    const bool fin = fast && c->finalise && ring_idle && p.nitems > 0;
+    if (setup_finalisation(c, p, s, fin)) return 1;                                        // 7
+    if (launch_render(c, p, s, kc, launch_cus, lds_block, wide_blocks)) return 1;          // 8
+    return fast ? behind_launch(c, p, s, B, fin) : 0;                                      // 9
 }
 
 extern "C" int mpt_render(mpt_ctx *c, int nframes) {                           // path.py:75-77
     if (!c) return fail("null context");
     if (nframes < 0) return fail("nframes must be >= 0");
-    // fail at the call, not at the deferred launch
-    if (c->nx <= 0) return fail("film size not set: call set_size() first");
-    if (!c->sV) return fail("sobol sampler not initialised");
-    if (!c->tree_valid) return fail("BVH not built: call build_tree() after load_model()");
+    if (check_ready(c)) return 1;                     // fail at the call, not at the deferred launch
     if (c->mlt_pending && mlt_flush(c)) return 1;     // the film sum follows call order: Metropolis iterations enqueued before go first
     while (nframes > 0) {
         int room = c->batch - c->pending;
@@ -1115,7 +1172,7 @@ extern "C" int mpt_render_preview(mpt_ctx *c, int nframes) {                   /
         if (fill_params(c, p, B)) return 1;
         if (sobol_advance(c, B, B)) return 1;
         p.chunk = B; p.nchunks = 1;
-        const int stack = ((c->mode == MPT_MODE_STRICT ? c->tree_depth : c->fast_depth) + 2 <= 32) ? 32 : 64;
+        const int stack = gather_stack_levels(c);
         if (p.ntiles) {
             if (c->mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_preview_strict(&p, p.ntiles, stack, c->stream));
             else HIP_TRY(mpt_launch_preview_fast(&p, p.ntiles, stack, c->stream));
@@ -1133,10 +1190,6 @@ enum { MPT_MLT_SLAB_RECORDS = 1 << 24 };      // splat records per launch (20 B 
 static int mlt_check(mpt_ctx *c) {
     if (c->mlt_n <= 0) return fail("Metropolis engine not reset: call mpt_mlt_reset first");
     return 0;
-}
-
-static int mlt_stack(const mpt_ctx *c) {
-    return ((c->mode == MPT_MODE_STRICT ? c->tree_depth : c->fast_depth) + 2 <= 32) ? 32 : 64;
 }
 
 // launch the enqueued iterations: chain kernel + splat pass per slab-sized piece, in iteration order
@@ -1167,7 +1220,7 @@ static int mlt_flush(mpt_ctx *c) {
         HIP_TRY(hipMalloc(&c->mlt_runs, rcap * 2 * sizeof(uint32_t)));
         c->mlt_cap = cap; c->mlt_runs_cap = rcap; c->mlt_tmp_bytes = std::max(tmp, (size_t)16);
     }
-    const int stack = mlt_stack(c);
+    const int stack = gather_stack_levels(c);
     while (n > 0) {
         const int K = std::min(n, kmax);
         MptMltArgs a;
@@ -1181,11 +1234,7 @@ static int mlt_flush(mpt_ctx *c) {
         HIP_TRY(mpt_launch_mlt_splat(c->film[0], c->mlt_keys, c->mlt_vals, c->mlt_keys2, c->mlt_vals2, c->mlt_tmp, c->mlt_tmp_bytes,
                                      c->mlt_runs, K * nch, (int)npix, c->stream));
         HIP_TRY(hipEventRecord(e2, c->stream));
-        c->mlt_events.push_back(e0); c->mlt_events.push_back(e1); c->mlt_events.push_back(e2);
-        if (c->mlt_events.size() > 3 * 4096) {       // nobody asks for the times: keep the newest half
-            for (size_t q = 0; q < 3 * 2048; q++) c->event_pool.push_back(c->mlt_events[q]);
-            c->mlt_events.erase(c->mlt_events.begin(), c->mlt_events.begin() + 3 * 2048);
-        }
+        c->mlt_timer.record({ e0, e1, e2 }, c->event_pool);
         c->mlt_iter += K;
         n -= K;
     }
@@ -1275,8 +1324,8 @@ extern "C" int mpt_mlt_trace(mpt_ctx *c, const float *X, float *rgb, int n) {
     if (hipMalloc(&drgb, (size_t)n * 3 * sizeof(float)) != hipSuccess) { hipFree(dX); return fail("mpt_mlt_trace: out of device memory"); }
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(dX, X, (size_t)n * 32 * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = c->mode == MPT_MODE_STRICT ? mpt_launch_mlt_trace_strict(&p, dX, drgb, n, mlt_stack(c), c->stream)
-                                                        : mpt_launch_mlt_trace_fast(&p, dX, drgb, n, mlt_stack(c), c->stream);
+    if (e == hipSuccess) e = c->mode == MPT_MODE_STRICT ? mpt_launch_mlt_trace_strict(&p, dX, drgb, n, gather_stack_levels(c), c->stream)
+                                                        : mpt_launch_mlt_trace_fast(&p, dX, drgb, n, gather_stack_levels(c), c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(rgb, drgb, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost);
     hipFree(dX); hipFree(drgb);
@@ -1288,18 +1337,10 @@ extern "C" int mpt_mlt_kernel_time(mpt_ctx *c, double *chain_ms, double *splat_m
     if (use_ro(c)) return 1;
     if (mpt_flush(c)) return 1;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    double tc = 0, ts = 0;
-    for (size_t q = 0; q + 2 < c->mlt_events.size(); q += 3) {
-        float a = 0, b = 0;
-        HIP_TRY(hipEventElapsedTime(&a, c->mlt_events[q], c->mlt_events[q + 1]));
-        HIP_TRY(hipEventElapsedTime(&b, c->mlt_events[q + 1], c->mlt_events[q + 2]));
-        tc += a; ts += b;
-    }
-    if (chain_ms) *chain_ms = tc;
-    if (splat_ms) *splat_ms = ts;
-    if (launches) *launches = (int)(c->mlt_events.size() / 3);
-    for (auto e : c->mlt_events) c->event_pool.push_back(e);
-    c->mlt_events.clear();
+    double seg[2] = { 0, 0 };            // chain, splat
+    if (c->mlt_timer.drain(seg, launches, c->event_pool)) return 1;
+    if (chain_ms) *chain_ms = seg[0];
+    if (splat_ms) *splat_ms = seg[1];
     return 0;
 }
 
@@ -1310,9 +1351,7 @@ extern "C" int mpt_mlt_kernel_time(mpt_ctx *c, double *chain_ms, double *splat_m
 extern "C" int mpt_render_brute(mpt_ctx *c, int nframes) {                     // brute.py:24-26
     if (!c) return fail("null context");
     if (nframes < 0) return fail("nframes must be >= 0");
-    if (c->nx <= 0) return fail("film size not set: call set_size() first");
-    if (!c->sV) return fail("sobol sampler not initialised");
-    if (!c->tree_valid) return fail("BVH not built: call build_tree() after load_model()");
+    if (check_ready(c)) return 1;
     if (use(c)) return 1;
     while (nframes > 0) {
         int B = std::min(nframes, (int)MPT_MAX_BATCH);
@@ -1320,18 +1359,14 @@ extern "C" int mpt_render_brute(mpt_ctx *c, int nframes) {                     /
         if (fill_params(c, p, B)) return 1;
         if (sobol_advance(c, B, B)) return 1;
         p.chunk = B; p.nchunks = 1;
-        const int stack = ((c->mode == MPT_MODE_STRICT ? c->tree_depth : c->fast_depth) + 2 <= 32) ? 32 : 64;
+        const int stack = gather_stack_levels(c);
         if (p.ntiles) {
             hipEvent_t e0 = get_event(c), e1 = get_event(c);
             HIP_TRY(hipEventRecord(e0, c->stream));
             if (c->mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_brute_strict(&p, p.ntiles, stack, c->stream));
             else HIP_TRY(mpt_launch_brute_fast(&p, p.ntiles, stack, c->stream));
             HIP_TRY(hipEventRecord(e1, c->stream));
-            c->brute_events.push_back(e0); c->brute_events.push_back(e1);
-            if (c->brute_events.size() > 2 * 4096) {     // nobody asks for the times: keep the newest half
-                for (size_t q = 0; q < 2 * 2048; q++) c->event_pool.push_back(c->brute_events[q]);
-                c->brute_events.erase(c->brute_events.begin(), c->brute_events.begin() + 2 * 2048);
-            }
+            c->brute_timer.record({ e0, e1 }, c->event_pool);
             c->film_version++;       // pass 0 has changed: an early image of an earlier PathEngine launch is stale
         }
         nframes -= B;
@@ -1345,15 +1380,8 @@ extern "C" int mpt_brute_kernel_time(mpt_ctx *c, double *ms, int *launches) {
     if (mpt_flush(c)) return 1;
     HIP_TRY(hipStreamSynchronize(c->stream));
     double total = 0;
-    for (size_t q = 0; q + 1 < c->brute_events.size(); q += 2) {
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, c->brute_events[q], c->brute_events[q + 1]));
-        total += t;
-    }
+    if (c->brute_timer.drain(&total, launches, c->event_pool)) return 1;
     if (ms) *ms = total;
-    if (launches) *launches = (int)(c->brute_events.size() / 2);
-    for (auto e : c->brute_events) c->event_pool.push_back(e);
-    c->brute_events.clear();
     return 0;
 }
 
@@ -1633,15 +1661,7 @@ extern "C" int mpt_kernel_time(mpt_ctx *c, double *ms, int *launches) {
     for (int k = 0; k < MPT_MAX_PIPE; k++) HIP_TRY(hipStreamSynchronize(c->rstream[k]));
     HIP_TRY(hipStreamSynchronize(c->stream));
     double total = 0;
-    for (auto &pr : c->events) {
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, pr.first, pr.second));
-        total += t;
-        c->event_pool.push_back(pr.first);
-        c->event_pool.push_back(pr.second);
-    }
+    if (c->render_timer.drain(&total, launches, c->event_pool)) return 1;
     if (ms) *ms = total;
-    if (launches) *launches = (int)c->events.size();
-    c->events.clear();
     return 0;
 }

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <chrono>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -91,6 +92,40 @@ MPT_INTERNAL int fail(const char *fmt, ...);
         if (e_ != hipSuccess) return fail("%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// ------------------------------------------------------------------ launch timers
+// The events recorded around the kernels of an engine's launches (per launch: `per_launch` events bounding per_launch - 1
+// segments, in stream order), kept until somebody asks for the times.  Events come from and go back to the context's pool.
+struct MPT_INTERNAL MptLaunchTimer {
+    const int per_launch;
+    std::vector<hipEvent_t> events;
+    explicit MptLaunchTimer(int n) : per_launch(n) {}
+
+    void record(std::initializer_list<hipEvent_t> launch, std::vector<hipEvent_t> &pool) {
+        for (hipEvent_t e : launch) events.push_back(e);
+        if (events.size() > (size_t)per_launch * 4096) trim(pool);
+    }
+    // nobody has asked for kernel times for a long while (an interactive session renders frame after
+    // frame): keep the newest half.  The dropped events were recorded at least 2048 launches ago.
+    void trim(std::vector<hipEvent_t> &pool) {
+        const size_t half = (size_t)per_launch * 2048;
+        for (size_t q = 0; q < half; q++) pool.push_back(events[q]);
+        events.erase(events.begin(), events.begin() + half);
+    }
+    // seg_ms[per_launch - 1] += every launch's segments; the caller has synchronised the streams the events were recorded on
+    int drain(double *seg_ms, int *launches, std::vector<hipEvent_t> &pool) {
+        for (size_t q = 0; q + per_launch <= events.size(); q += per_launch)
+            for (int g = 0; g + 1 < per_launch; g++) {
+                float t = 0;
+                HIP_TRY(hipEventElapsedTime(&t, events[q + g], events[q + g + 1]));
+                seg_ms[g] += t;
+            }
+        if (launches) *launches = (int)(events.size() / per_launch);
+        for (hipEvent_t e : events) pool.push_back(e);
+        events.clear();
+        return 0;
+    }
+};
+
 // ------------------------------------------------------------------ context
 enum { MPT_MAX_PIPE = 6 };
 
@@ -109,7 +144,7 @@ struct mpt_ctx {
     int clock_khz = 0;                   // hipDeviceProp_t.clockRate: peak shader clock (roofline peaks in bench.py)
     int tile_w_shift = 3, tile_h_shift = 3;   // work-item tile 2^w x 2^h pixels
     int last_div = 1;                    // share of the chip the last launch took: 1/last_div of the CUs
-    int last_kernel = 0;                 // 0 gather kernel, 1 LDS-resident kernel (what the last flush launched)
+    int last_kernel = 0;                 // what the last flush launched: MPT_KERNEL_* of lds_layout.h (0 binary gather, 1 LDS binary, 2 4-wide gather, 5 LDS 4-wide)
     int shade_spec = 1;                  // 1: a scene whose feature mask (shade_feat.h) is empty runs the plain instantiation of render_kernel_lds4; 0: always the generic one (A/B, tests)
     int last_shade_feat = -1;            // the mask the last render launch was compiled for (MPT_FEAT_PLAIN / MPT_FEAT_GENERIC; -1: none yet)
 
@@ -210,13 +245,14 @@ struct mpt_ctx {
     MptVec4 *mlt_vals = nullptr, *mlt_vals2 = nullptr;
     void *mlt_tmp = nullptr;
     uint32_t *mlt_runs = nullptr;
-    std::vector<hipEvent_t> mlt_events;                  // {chain start, chain end = splat start, splat end} per launch
-    std::vector<hipEvent_t> brute_events;                // brute-force engine: {kernel start, kernel end} per launch
+    MptLaunchTimer mlt_timer{3};                         // {chain start, chain end = splat start, splat end} per launch
+    MptLaunchTimer brute_timer{2};                       // brute-force engine: {kernel start, kernel end} per launch
     // command batching
     int pending = 0;
 
-    // launch pipelining (fast build): batch i renders on rstream[i & 1] into partial[i & 1] while the main
-    // stream still combines / gathers / resolves batch i-1, so one launch's tail overlaps the next one's head
+    // launch pipelining (fast build): batch i renders on rstream[k] into partial2[k], k = i mod cur_depth (a ring of 2 to
+    // MPT_MAX_PIPE slots), while the main stream still combines / gathers / resolves batch i-1, so one launch's tail
+    // overlaps the next one's head
     hipStream_t rstream[MPT_MAX_PIPE] = {};
     hipEvent_t ev_render[MPT_MAX_PIPE] = {};          // render of the batch on rstream[k] finished
     hipEvent_t ev_free[MPT_MAX_PIPE] = {};            // combine has consumed partial[k]
@@ -267,7 +303,7 @@ struct mpt_ctx {
     unsigned int *d_work = nullptr;
     unsigned int *h_watchdog = nullptr, *d_watchdog = nullptr;   // host-pinned, device-mapped: raised by a render kernel's watchdog
     void *h_stage = nullptr; size_t h_stage_bytes = 0;           // page-locked staging for read-backs into pageable buffers
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    MptLaunchTimer render_timer{2};      // PathEngine launches: {kernel start, kernel end}
     std::vector<hipEvent_t> event_pool;
 
     // comm

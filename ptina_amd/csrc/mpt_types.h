@@ -101,15 +101,8 @@ struct MptSahBuffers {
 
 struct MptImage { int32_t nx, ny, base, pad; };   // image.py:14-16
 
-// LDS-resident kernel: bytes from one node record to the next in LDS.  72, not 64: a ds_read_b64 is served in two
-// groups of 32 lanes over 64 banks of 4 bytes, and with 64-byte records every lane's read of a given plane lands
-// on one of FOUR bank pairs (16 i mod 64); with 72-byte records on one of 32 (18 i mod 64) -- reads stay 8-byte aligned
-#ifndef MPT_LDS_NODE_STRIDE
-#define MPT_LDS_NODE_STRIDE 72
-#endif
-#ifndef MPT_LDS4_NODE_STRIDE
-#define MPT_LDS4_NODE_STRIDE 112     // bytes between the 4-wide node records in LDS (render_kernel_lds4: seven float4 of a wnode record)
-#endif
+// the LDS-resident kernels' record strides, region sizes and fit rule
+#include "lds_layout.h"
 
 // 16-bit tags of a launch's sample entries (film_ops.h): 0 = zeroed memory, 1 = a launch that keeps the combine pass, 2 ... 65535 =
 // finalising launches in turn

@@ -408,7 +408,6 @@ typedef __attribute__((address_space(3))) const mpt_f2 *LdsVec2Ptr;
 typedef __attribute__((address_space(3))) const char *LdsBytePtr;
 
 typedef __attribute__((address_space(3))) const unsigned char *LdsU8Ptr;
-#define MPT_LDS_MAT_VEC4 6      // float4 of a material record kept in LDS: p[0..15] and the derived terms d[0..7]
 
 // The internal-node ids of the LDS copy (in the records and therefore on the stack) are the node's byte offset / 8, so a NODE
 // step forms its record address with one shift instead of a 32-bit integer multiply (quarter rate: four issue slots of the ~50 a

@@ -1124,13 +1124,12 @@ __global__ __launch_bounds__(MPT_BLOCK, MPT_WIDE_WAVES) void render_kernel_wide(
 
 // ---------------------------------------------------------------- LDS-resident persistent kernel
 // dynamic LDS: [ (n-1) node records of MPT_LDS_NODE_STRIDE bytes, padded to 16 | n*3 triangle float4 (tfast) | (default_mtl+1)*6 material float4 |
-//                n material-record bytes, padded to 16 | lds_stack x 1024 int16 ]     (mpt_lds_scene_bytes)
+//                n material-record bytes, padded to 16 | lds_stack x 1024 int16 ]     (lds_layout.h mpt_lds_regions: the host sizes the launch by it)
 template <bool COUNT>
 __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds(const MptRenderParams p) {
     extern __shared__ __attribute__((aligned(16))) MptVec4 smem[];
-    // node records MPT_LDS_NODE_STRIDE bytes apart (bank spreading), the region rounded up to whole float4
-    const int nnode4 = ((p.n - 1) * MPT_LDS_NODE_STRIDE + 15) >> 4, ntri4 = p.n * 3, nmat4 = (p.default_mtl + 1) * MPT_LDS_MAT_VEC4;
-    const int nmtl4 = (p.n + 15) >> 4;
+    const MptLdsRegions lay = mpt_lds_regions(p.n, p.default_mtl);
+    const int nnode4 = lay.nnode4, ntri4 = lay.ntri4, nmat4 = lay.nmat4, nmtl4 = lay.nmtl4;
     unsigned long long *tl = p.timeline ? p.timeline + MPT_TIMELINE_WORDS * (size_t)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) : nullptr;
     if (tl && (threadIdx.x & 63) == 0) tl[0] = wall_clock64();
     {   // one copy of the scene per CU: coalesced 16-B loads, ds_write_b128
@@ -1181,7 +1180,7 @@ __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds(const MptRend
 // ---------------------------------------------------------------- LDS-resident persistent kernel over the 4-wide nodes
 // dynamic LDS: [ nwide node records of MPT_LDS4_NODE_STRIDE bytes | (n+1)*3 triangle float4 (tfast; record n: the unused slots' NaNs) |
 //                (lds_nmats+1)*6 material float4 (the records the model uses, then the default one) | n material-record bytes,
-//                padded to 16 | lds_stack x 1024 int16 ]
+//                padded to 16 | lds_stack x 1024 int16 ]     (lds_layout.h mpt_lds4_regions)
 // Two instantiations per COUNT: FEAT = MPT_FEAT_GENERIC (every region of SHADE) and MPT_FEAT_PLAIN, launched for a plain scene
 // (untextured materials without clearcoat or transmission, one light, no environment map: the headline scene and BASELINE's
 // configs 1, 2, 3, 5): without the texture, environment-map and light-list regions and without the clearcoat and transmission
@@ -1189,8 +1188,8 @@ __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds(const MptRend
 template <bool COUNT, int FEAT>
 __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds4(const MptRenderParams p) {
     extern __shared__ __attribute__((aligned(16))) MptVec4 smem[];
-    const int nnode4 = p.nwide * (MPT_LDS4_NODE_STRIDE / 16), ntri4 = (p.n + 1) * 3, nmat4 = (p.lds_nmats + 1) * MPT_LDS_MAT_VEC4;
-    const int nmtl4 = (p.n + 15) >> 4;
+    const MptLdsRegions lay = mpt_lds4_regions(p.n, p.nwide, p.lds_nmats);
+    const int nnode4 = lay.nnode4, ntri4 = lay.ntri4, nmat4 = lay.nmat4, nmtl4 = lay.nmtl4;
     unsigned long long *tl = p.timeline ? p.timeline + MPT_TIMELINE_WORDS * (size_t)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) : nullptr;
     if (tl && (threadIdx.x & 63) == 0) tl[0] = wall_clock64();
     {
@@ -1291,24 +1290,31 @@ static int blocks_per_cu(K kernel) {
     return nb;
 }
 
+#if !MPT_STRICT
+// occupancy answers are per device (the C ABI allows one context per GPU in a process): asked once per device and kernel variant
+typedef void (*RenderKernelFn)(const MptRenderParams);
+static hipError_t cached_blocks_per_cu(std::atomic<int> (*cache)[4], const RenderKernelFn (&variants)[4], int v, int *occ) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MPT_MAX_DEVICES) return hipErrorInvalidDevice;
+    *occ = cache[dev][v].load(std::memory_order_relaxed);
+    if (!*occ) {
+        *occ = blocks_per_cu(variants[v]);
+        cache[dev][v].store(*occ, std::memory_order_relaxed);
+    }
+    return hipSuccess;
+}
+#endif
+
 // strict build: grid = number of 16x16 tiles.  fast build: persistent workgroups, `grid` = number of CUs
 // (scaled here by the blocks each CU can hold); the work items come from p->work_counter.
 MPT_KERNEL_API hipError_t MPT_SUFFIX(mpt_launch_render)(const MptRenderParams *p, int grid, int stack, int count,
                                                      hipStream_t stream) {
 #if !MPT_STRICT
-    // occupancy answers are per device (the C ABI allows one context per GPU in a process)
     static std::atomic<int> occ_cache[MPT_MAX_DEVICES][4];
-    int v = (stack <= 32 ? 0 : 2) + (count ? 1 : 0);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MPT_MAX_DEVICES) return hipErrorInvalidDevice;
-    int occ = occ_cache[dev][v].load(std::memory_order_relaxed);
-    if (!occ) {
-        occ = v == 0 ? blocks_per_cu(MPT_SUFFIX(render_kernel)<32, false>)
-            : v == 1 ? blocks_per_cu(MPT_SUFFIX(render_kernel)<32, true>)
-            : v == 2 ? blocks_per_cu(MPT_SUFFIX(render_kernel)<64, false>)
-                     : blocks_per_cu(MPT_SUFFIX(render_kernel)<64, true>);
-        occ_cache[dev][v].store(occ, std::memory_order_relaxed);
-    }
+    static const RenderKernelFn variants[4] = { MPT_SUFFIX(render_kernel)<32, false>, MPT_SUFFIX(render_kernel)<32, true>,
+                                                MPT_SUFFIX(render_kernel)<64, false>, MPT_SUFFIX(render_kernel)<64, true> };
+    int occ = 0;
+    if (hipError_t e = cached_blocks_per_cu(occ_cache, variants, (stack <= 32 ? 0 : 2) + (count ? 1 : 0), &occ)) return e;
     grid *= occ;
 #endif
     if (stack <= 32) {
@@ -1322,35 +1328,20 @@ MPT_KERNEL_API hipError_t MPT_SUFFIX(mpt_launch_render)(const MptRenderParams *p
 }
 
 #if !MPT_STRICT
-// lds_bytes = scene records + 2 KiB per stack level; grid = one persistent workgroup per CU
-template <bool COUNT>
-static hipError_t launch_lds(const MptRenderParams *p, int grid, int block, size_t lds_bytes, hipStream_t stream) {
+// a kernel that takes the whole dynamic LDS of a CU (lds_layout.h): lds_bytes = scene records + 2 KiB per stack level; grid = one
+// persistent workgroup per CU.  One instance -- and one "attribute set" flag -- per kernel instantiation.
+template <auto KERNEL>
+static hipError_t launch_whole_lds(const MptRenderParams *p, int grid, int block, size_t lds_bytes, hipStream_t stream) {
     // function attributes are per device: remember which devices have been told about the 160 KiB
     static std::atomic<bool> configured[MPT_MAX_DEVICES];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MPT_MAX_DEVICES) return hipErrorInvalidDevice;
     if (!configured[dev].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute((const void *)render_kernel_lds<COUNT>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, MPT_LDS_BUDGET);
         if (e != hipSuccess) return e;
         configured[dev].store(true, std::memory_order_release);
     }
-    hipLaunchKernelGGL((render_kernel_lds<COUNT>), dim3(grid), dim3(block), lds_bytes, stream, *p);
-    return hipGetLastError();
-}
-
-template <bool COUNT, int FEAT>
-static hipError_t launch_lds4(const MptRenderParams *p, int grid, int block, size_t lds_bytes, hipStream_t stream) {
-    static std::atomic<bool> configured[MPT_MAX_DEVICES];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MPT_MAX_DEVICES) return hipErrorInvalidDevice;
-    if (!configured[dev].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute((const void *)render_kernel_lds4<COUNT, FEAT>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        configured[dev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((render_kernel_lds4<COUNT, FEAT>), dim3(grid), dim3(block), lds_bytes, stream, *p);
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), lds_bytes, stream, *p);
     return hipGetLastError();
 }
 
@@ -1359,17 +1350,17 @@ static hipError_t launch_lds4(const MptRenderParams *p, int grid, int block, siz
 MPT_KERNEL_API hipError_t mpt_launch_render_lds4(const MptRenderParams *p, int grid, int block, size_t lds_bytes, int count, int feat,
                                              hipStream_t stream) {
     if (feat == MPT_FEAT_PLAIN)
-        return count ? launch_lds4<true, MPT_FEAT_PLAIN>(p, grid, block, lds_bytes, stream)
-                     : launch_lds4<false, MPT_FEAT_PLAIN>(p, grid, block, lds_bytes, stream);
+        return count ? launch_whole_lds<render_kernel_lds4<true, MPT_FEAT_PLAIN>>(p, grid, block, lds_bytes, stream)
+                     : launch_whole_lds<render_kernel_lds4<false, MPT_FEAT_PLAIN>>(p, grid, block, lds_bytes, stream);
     if (feat != MPT_FEAT_GENERIC) return hipErrorInvalidValue;
-    return count ? launch_lds4<true, MPT_FEAT_GENERIC>(p, grid, block, lds_bytes, stream)
-                 : launch_lds4<false, MPT_FEAT_GENERIC>(p, grid, block, lds_bytes, stream);
+    return count ? launch_whole_lds<render_kernel_lds4<true, MPT_FEAT_GENERIC>>(p, grid, block, lds_bytes, stream)
+                 : launch_whole_lds<render_kernel_lds4<false, MPT_FEAT_GENERIC>>(p, grid, block, lds_bytes, stream);
 }
 
-// lds_bytes = scene records + 2 KiB per stack level; grid = one persistent workgroup per CU
 MPT_KERNEL_API hipError_t mpt_launch_render_lds(const MptRenderParams *p, int grid, int block, size_t lds_bytes, int count,
                                             hipStream_t stream) {
-    return count ? launch_lds<true>(p, grid, block, lds_bytes, stream) : launch_lds<false>(p, grid, block, lds_bytes, stream);
+    return count ? launch_whole_lds<render_kernel_lds<true>>(p, grid, block, lds_bytes, stream)
+                 : launch_whole_lds<render_kernel_lds<false>>(p, grid, block, lds_bytes, stream);
 }
 #endif
 
@@ -1402,15 +1393,10 @@ MPT_KERNEL_API hipError_t mpt_launch_derive_materials(MptMaterial *mats, int cou
 // *blocks = workgroups launched (the spill strip must hold blocks x 256 lanes x SpillStack::SPILL entries)
 MPT_KERNEL_API hipError_t mpt_wide_blocks(int grid, int count, int quant, int *blocks) {
     static std::atomic<int> occ_cache[MPT_MAX_DEVICES][4];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MPT_MAX_DEVICES) return hipErrorInvalidDevice;
-    const int v = (count ? 1 : 0) + (quant ? 2 : 0);
-    int occ = occ_cache[dev][v].load(std::memory_order_relaxed);
-    if (!occ) {
-        occ = v == 0 ? blocks_per_cu(render_kernel_wide<false, false>) : v == 1 ? blocks_per_cu(render_kernel_wide<true, false>)
-            : v == 2 ? blocks_per_cu(render_kernel_wide<false, true>) : blocks_per_cu(render_kernel_wide<true, true>);
-        occ_cache[dev][v].store(occ, std::memory_order_relaxed);
-    }
+    static const RenderKernelFn variants[4] = { render_kernel_wide<false, false>, render_kernel_wide<true, false>,
+                                                render_kernel_wide<false, true>, render_kernel_wide<true, true> };
+    int occ = 0;
+    if (hipError_t e = cached_blocks_per_cu(occ_cache, variants, (count ? 1 : 0) + (quant ? 2 : 0), &occ)) return e;
     *blocks = grid * occ;
     return hipSuccess;
 }
