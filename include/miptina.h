@@ -56,8 +56,8 @@ typedef struct {
     uint64_t it_leaf;        /* wave-level LEAF steps issued             */
     uint64_t it_shade;       /* wave-level SHADE stages issued           */
     uint64_t it_new;         /* wave-level NEW stages issued             */
-    /* spare counters: zero in the product library; the diagnostic builds MPT_X_STAMPS, MPT_X_PAIRS and MPT_X_LEAFPAIRS
-     * (render_kernel.hip) fill them with their own measurements (tools/gpu_diag.py, tools/pairs.py, tools/scratch/leafpairs.py) */
+    /* spare counters: zero in the product library; the diagnostic build -DMPT_X_STAMPS=2 fills them with the cycles of the
+     * segments of SHADE (render_shade.h; read by tools/gpu_diag.py stamps) */
     uint64_t pl_local;
     uint64_t pl_batches;
     uint64_t pl_batch_lanes;
@@ -233,8 +233,8 @@ void  mpt_host_free(void *p);
 /* measurement */
 int mpt_get_counters(mpt_ctx *ctx, mpt_counters *out);
 /* Diagnostics (option "timeline" = 1): per wave of the last LDS-kernel launch, eight words: four 100 MHz timestamps
- * {start, scene copied to LDS, work queues found empty, exit} and, in a -DMPT_X_TIMELINE2 build only (else 0), {time of the
- * last work item pulled, items pulled, lanes in flight when the queues were found empty, shading passes after that}.
+ * {start, scene copied to LDS, work queues found empty, exit}, then {time the wave left the tail finalisation, tiles it
+ * finalised} and two words that are zero.
  * *nwaves = waves recorded. */
 int mpt_get_timeline(mpt_ctx *ctx, unsigned long long *out /* [cap_waves][8] */, int cap_waves, int *nwaves);
 int mpt_reset_counters(mpt_ctx *ctx);

@@ -145,8 +145,8 @@ DEV V3 random3(Rng &r) { float a = rng_random(r), b = rng_random(r), c = rng_ran
 
 // ---------------------------------------------------------------- counters
 struct Cnt { unsigned rays, n_box, n_tri, n_shade, n_draws, bounces, n_node, samples, it_node, it_leaf, it_shade, it_new;
-             // spare counters that the diagnostic builds fill with their own measurements (MPT_X_STAMPS, MPT_X_PAIRS,
-             // MPT_X_LEAFPAIRS in render_kernel.hip; read by tools/gpu_diag.py, tools/pairs.py, tools/scratch/leafpairs.py)
+             // spare counters: zero in the product library; the diagnostic build -DMPT_X_STAMPS=2 fills them with the cycles of the
+             // segments of SHADE (render_shade.h; read by tools/gpu_diag.py stamps)
              unsigned pl_local, pl_batches, pl_batch_lanes, pl_prim, pl_tidle, pl_sidle, pl_trips, pl_taken; };
 
 // ---------------------------------------------------------------- geometry

@@ -366,7 +366,7 @@ def timeline(name='s978', spp=32, n=512):
         np.save(os.path.join(ROOT, 'gpurun_out', f'timeline_raw_{parts}.npy'), t)
         t0 = t[:, 0].min()
         us = (t[:, :4] - t0) / 100.0
-        if t[:, 6].max() == 0 and t[:, 4].max() > 0:     # product build with the tail finalisation: when each wave left it, tiles it did
+        if t[:, 4].max() > 0:     # words 4 and 5: when each wave left the tail finalisation, tiles it did
             fin_end = (t[:, 4] - t0) / 100.0
             extra = {'fin_end': [round(float(x), 1) for x in np.percentile(fin_end, [0, 10, 50, 90, 100])],
                      'fin_us_per_wave': [round(float(x), 1) for x in np.percentile(fin_end - us[:, 3], [0, 10, 50, 90, 100])],
@@ -374,14 +374,6 @@ def timeline(name='s978', spp=32, n=512):
                      'waves_that_finalised': int((t[:, 5] > 0).sum()), 'tiles': int(t[:, 5].sum()),
                      'last_trace_exit': round(float(us[:, 3].max()), 1), 'last_fin_exit': round(float(fin_end.max()), 1)}
             print('timeline_fin', parts, json.dumps(extra), flush=True)
-        elif t[:, 5].max() > 0:            # diagnostic build -DMPT_X_TIMELINE2: last pull, items, lanes in flight at empty, passes after
-            lastpull = (t[:, 4] - t0) / 100.0
-            extra = {'last_pull': [round(float(x), 1) for x in np.percentile(lastpull, [0, 10, 50, 90, 100])],
-                     'last_item_us': [round(float(x), 1) for x in np.percentile(us[:, 2] - lastpull, [0, 10, 50, 90, 100])],
-                     'items_per_wave': [int(x) for x in np.percentile(t[:, 5], [0, 10, 50, 90, 100])],
-                     'lanes_in_flight_at_empty': [int(x) for x in np.percentile(t[:, 6], [0, 10, 50, 90, 100])],
-                     'passes_after_empty': [int(x) for x in np.percentile(t[:, 7], [0, 10, 50, 90, 100])]}
-            print('timeline2', parts, json.dumps(extra), flush=True)
         wg_exit = us[:, 3].reshape(-1, 16).max(axis=1)
         q = lambda a: [round(float(x), 1) for x in np.percentile(a, [0, 10, 50, 90, 100])]
         res[str(parts)] = {'start': q(us[:, 0]), 'ready': q(us[:, 1]), 'queue_empty': q(us[:, 2]),
@@ -617,10 +609,7 @@ def stamps(name='s978', spp=32, n=512):
     res['rest'] = 1.0 - sum(res.values())
     res['stages_per_64_samples'] = {s: k['it_' + s] / k['samples'] * 64 for s in ('node', 'leaf', 'shade', 'new')}
     res['cycles_per_stage'] = {s: v * 256 / max(k['it_' + s], 1) for s, v in (('node', k['n_box']), ('leaf', k['n_tri']), ('shade', k['n_shade']), ('new', k['bounces']))}
-    if os.environ.get('STAMPS3'):     # -DMPT_X_STAMPS=3: of NEW's cycles, the pull (once per work item) and the preparation of 64 primary rays
-        res['new_segments_cycles_per_64_samples'] = {'pull': k['pl_local'] * 16 / k['samples'] * 64, 'prepare': k['pl_batches'] * 16 / k['samples'] * 64,
-                                                     'new_total': k['bounces'] * 256 / k['samples'] * 64}
-    elif k.get('pl_local', 0):         # -DMPT_X_STAMPS=2: the segments of SHADE, cycles per SHADE stage
+    if k.get('pl_local', 0):         # -DMPT_X_STAMPS=2: the segments of SHADE, cycles per SHADE stage
         seg = (('entry_and_gather_issue', 'pl_trips'), ('lights_hit', 'pl_local'), ('geometry_material_after_gathers', 'pl_batches'), ('light_sample', 'pl_batch_lanes'),
                ('bsdf_eval_mis', 'pl_prim'), ('bsdf_sample', 'pl_tidle'), ('ray_start', 'pl_sidle'))
         res['shade_segments_cycles'] = {a: k[b] * 16 / max(k['it_shade'], 1) for a, b in seg}
