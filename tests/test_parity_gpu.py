@@ -1312,13 +1312,18 @@ def _sah_tree(c, n, dev):
     return w, q, c.get_option('fast_depth'), c.get_option('wide_nodes')
 
 
-def _check_wide_tree(w, n, nw):
+def _check_wide_tree(w, n, nw, v, q):
+    # against the model (tests/tree_checks.py): a leaf child's box is its triangle's, an internal child's the union of the boxes
+    # below it, exactly (E1, E2: every box encloses every triangle below it and is no larger), an unused slot is out of reach
+    # (E3), the topology (E4), and the 8-bit boxes lie outside the exact ones by no more than 1.26 steps (Q1-Q6)
+    import tree_checks
+    from ptina_amd.things import BVHTree
+    tree_checks.check_all(np.asarray(v, np.float32).reshape(n, 3, 8)[:, :, :3], BVHTree().to_numpy()['leaf'], w, q, n)
     ids = w[:, 6, :].view(np.int32)
     assert nw > 0
     assert np.array_equal(np.sort(ids[ids > 0]), np.arange(1, nw)), 'every wide node but the root has exactly one parent'
     assert np.array_equal(np.sort(~ids[(ids < 0) & (ids != ~n)]), np.arange(n)), 'every triangle sits in exactly one slot'
-    # every child box lies inside ... the boxes of a leaf child are its triangle's (checked against the model by the films);
-    # here: finite, lo <= hi for every used slot
+    # finite, lo <= hi for every used slot
     lo = w[:, 0:6:2, :].view(np.float32)
     hi = w[:, 1:6:2, :].view(np.float32)
     used = np.broadcast_to((ids != ~n)[:, None, :], lo.shape)
@@ -1345,7 +1350,7 @@ def test_device_sah_finish_kernel_is_the_host_pass_node_for_node(fresh, n):
     host = _sah_tree(c, n, 0)
     assert dev[2] == host[2] and dev[3] == host[3]
     assert np.array_equal(dev[0], host[0]) and np.array_equal(dev[1], host[1])
-    _check_wide_tree(dev[0], n, dev[3])
+    _check_wide_tree(dev[0], n, dev[3], v, dev[1])
 
 
 @pytest.mark.parametrize('n', [1025, 1100, 2049, 2100, 5000, 20000, 99382])
@@ -1364,7 +1369,7 @@ def test_device_sah_pass_is_a_valid_deterministic_tree(fresh, n):
     a = _sah_tree(c, n, 1)
     b = _sah_tree(c, n, 1)
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2]
-    _check_wide_tree(a[0], n, a[3])
+    _check_wide_tree(a[0], n, a[3], v, a[1])
     assert 2 < a[2] <= 62
 
     def cost(w):
