@@ -101,6 +101,8 @@ void mpt_destroy(mpt_ctx *ctx);
  * 2..6; 0 = auto), "lds_block" (lanes per persistent workgroup of the LDS kernel, diagnostics),
  * "zero_copy" (1, default: mpt_get_image into an mpt_host_alloc array has the resolve pass write the image straight into it over
  * PCIe; 0: device buffer + DMA -- same image, 20 us more per call),
+ * "denoise_lds" (1, default: mpt_get_denoised's iterations of stride 1 and 2 filter from a tile held in LDS; 0: every stride gathers
+ * from memory -- same image bit for bit),
  * "skip_dark" (1 = a shadow ray whose candidate direct light is exactly zero -- the light behind the surface -- is not traced:
  * adding zero or not is the same sum; 0 = traced like the reference does; -1 = on in the production build, off in the strict build: default),
  * "spin_us" (how long mpt_get_image polls a finalising launch before it blocks; default 20000, 0 = block at once),
@@ -222,6 +224,31 @@ int mpt_fast_export_image(mpt_ctx *ctx, int pass, float *out);
 int mpt_get_film_raw(mpt_ctx *ctx, int pass, float *out);
 /* device-side resolve only (no read-back): what get_image does before the copy */
 int mpt_resolve(mpt_ctx *ctx, int pass);
+
+/* Film pass 0 denoised on the device by an edge-avoiding A-Trous wavelet filter (Dammertz et al. 2010), guided by the albedo and
+ * normal passes (1 and 2) that PreviewEngine renders (ptina/engine/preview.py:18-41; the reference exports them as denoiser AOVs and
+ * leaves the filter to Blender's compositor, so the call has no counterpart there).  With F0, F1, F2 the raw accumulators of the
+ * passes (film index x*ny + y):
+ *   valid(p) = F0.w != 0;  c = F0.rgb / F0.w;  a = F1.rgb / F1.w, n = F2.rgb / F2.w (0 where that pass is empty);
+ *   m = max(a, 1e-2) per channel when `demodulate`, else 1;  e_0 = c / m;  h = [1/16, 1/4, 3/8, 1/4, 1/16];
+ *   for i = 0 .. iterations-1, s = 2^i, every valid p, over dx, dy in -2..2 with q = p + s (dx, dy) inside the film and valid:
+ *       w(q) = h[dx] h[dy] exp(-(|e_i(p)-e_i(q)|^2 / (sigma_color 2^-i)^2 + |a(p)-a(q)|^2 / sigma_albedo^2 + |n(p)-n(q)|^2 / sigma_normal^2))
+ *       e_{i+1}(p) = sum w e_i(q) / sum w
+ *   out = (e_final m, 1) for valid pixels and (0.9, 0.4, 0.9, 0) for the others, as mpt_get_image gives them.
+ * f32 arithmetic, a gather without atomics: repeats bit for bit.  iterations = 0 is exactly mpt_get_image(ctx, 0, out).  With passes
+ * 1 and 2 empty the filter is guided by colour alone.  Columns a slab or stripe split did not render are not valid.  Flushes what is
+ * enqueued, reads whatever film the context holds, writes no film pass and neither uses nor disturbs an mpt_hint_image hint.
+ * Fails for iterations outside 0..8 and for a sigma that is not finite and positive. */
+typedef struct {
+    int32_t iterations;      /* 5   */
+    float sigma_color;       /* 1.0 */
+    float sigma_albedo;      /* 0.1 */
+    float sigma_normal;      /* 0.3 */
+    int32_t demodulate;      /* 1   */
+} mpt_denoise_params;
+int mpt_get_denoised(mpt_ctx *ctx, const mpt_denoise_params *params /* NULL = the defaults above */, float *out /* [nx][ny][4] */);
+/* HIP-event time (ms) of the filter's kernels (prologue to epilogue) of the mpt_get_denoised calls since the last call, and their count */
+int mpt_denoise_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
 
 /* Page-locked host buffers for the read-backs above: into such a buffer mpt_get_image /
  * mpt_fast_export_image / mpt_get_film_raw are one DMA; any other buffer is served through a

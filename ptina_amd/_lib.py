@@ -37,6 +37,11 @@ class Caps(C.Structure):
                  'max_filmsize', 'max_filmpasses')]
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [('iterations', C.c_int32), ('sigma_color', C.c_float), ('sigma_albedo', C.c_float), ('sigma_normal', C.c_float),
+                ('demodulate', C.c_int32)]
+
+
 class Counters(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in
                 ('samples', 'rays', 'n_box', 'n_tri', 'n_shade', 'n_draws', 'bounces', 'n_node',
@@ -96,6 +101,8 @@ SIGNATURES = {
     'mpt_fast_export_image': (_i, [_vp, _i, _fp]),
     'mpt_get_film_raw': (_i, [_vp, _i, _fp]),
     'mpt_resolve': (_i, [_vp, _i]),
+    'mpt_get_denoised': (_i, [_vp, C.POINTER(DenoiseParams), _fp]),
+    'mpt_denoise_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
     'mpt_host_alloc': (_vp, [C.c_size_t]),
     'mpt_host_free': (None, [_vp]),
     'mpt_get_counters': (_i, [_vp, C.POINTER(Counters)]),

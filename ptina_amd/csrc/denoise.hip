@@ -1,0 +1,203 @@
+// denoise.hip -- edge-avoiding A-Trous wavelet filter of film pass 0, guided by the albedo and normal passes the PreviewEngine
+// renders into passes 1 and 2 (Dammertz, Sewtz, Hanika, Lensch: "Edge-Avoiding A-Trous Wavelet Transform for fast Global
+// Illumination Filtering", HPG 2010).  The reference renders those two passes as denoiser AOVs and leaves the filter to Blender's
+// compositor; here it runs on the device.  The definition (include/miptina.h, mpt_get_denoised):
+//
+//   prologue   e_0 = (F0.rgb / F0.w) / m, valid = F0.w != 0;  a = F1.rgb / F1.w, n = F2.rgb / F2.w (0 where the pass is empty);
+//              m = max(a, 1e-2) per channel when demodulating, else 1
+//   iteration  i = 0 .. iterations - 1, s = 2^i: for every valid p, over the 25 taps q = p + s (dx, dy), dx outer, dy inner, both
+//              ascending, skipping q outside the film or not valid:
+//                  w = h[dx] h[dy] exp(-((|e(p) - e(q)|^2 kc + |a(p) - a(q)|^2 ka) + |n(p) - n(q)|^2 kn)),  |d|^2 = (dx dx + dy dy) + dz dz
+//                  e'(p) = (sum w e(q)) / (sum w)
+//   epilogue   (e m, 1) for valid pixels, FilmTable's empty marker otherwise
+//
+// All f32, compiled without contraction, a pure gather: the result repeats bit for bit, and the two stencil kernels below (tile in
+// LDS for the strides 1 and 2, 16-byte gathers for the larger ones) run the same arithmetic in the same order, so which of them
+// serves an iteration never changes a bit (option "denoise_lds"; tests/test_denoise_gpu.py).
+// Film element x * ny + y: lanes run along y, so every tap of a wave is one contiguous run of 64 float4.
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include "mpt_types.h"
+#include "film_ops.h"
+
+static_assert(sizeof(MptVec4) == sizeof(float4), "the film's records are read as float4");
+
+enum { DN_LANES = 64, DN_ROWS = 4, DN_TILE_X = 8 };     // a block is 64 lanes along y times 4 film columns; the LDS kernel's tile is 8 columns
+
+__device__ __forceinline__ float dn_tap_weight(int d) {      // h = [1/16, 1/4, 3/8, 1/4, 1/16] at d = 0 .. 4 (all products exact in f32)
+    return d == 2 ? 0.375f : ((d == 1 || d == 3) ? 0.25f : 0.0625f);
+}
+
+__device__ __forceinline__ float dn_dist2(const float4 p, const float4 q) {
+    const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+struct DnSum { float w, r, g, b; };
+
+// one tap: `ok` = q lies in the film and is valid (e.w is the valid flag)
+__device__ __forceinline__ void dn_tap(DnSum &s, float hw, bool ok, const float4 ep, const float4 ap, const float4 np,
+                                       const float4 eq, const float4 aq, const float4 nq, float kc, float ka, float kn) {
+    const float arg = (dn_dist2(ep, eq) * kc + dn_dist2(ap, aq) * ka) + dn_dist2(np, nq) * kn;
+    const float w = ok ? hw * expf(-arg) : 0.0f;
+    s.w += w; s.r += w * eq.x; s.g += w * eq.y; s.b += w * eq.z;
+}
+
+__device__ __forceinline__ float4 dn_finish(const DnSum s) {      // the centre tap alone gives s.w >= 9/64
+    return make_float4(s.r / s.w, s.g / s.w, s.b / s.w, 1.0f);
+}
+
+// ---------------------------------------------------------------- prologue / epilogue: streaming passes like resolve_kernel
+__global__ __launch_bounds__(256) void dn_prologue_kernel(const float4 *__restrict__ f0, const float4 *__restrict__ f1,
+                                                          const float4 *__restrict__ f2, float4 *__restrict__ e,
+                                                          float4 *__restrict__ a, float4 *__restrict__ n, size_t npix, int demodulate) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= npix) return;
+    const float4 c = f0[t], g1 = f1[t], g2 = f2[t];
+    float4 av = make_float4(0.f, 0.f, 0.f, 0.f), nv = av, ev = av;
+    if (g1.w != 0.0f) { av.x = g1.x / g1.w; av.y = g1.y / g1.w; av.z = g1.z / g1.w; }
+    if (g2.w != 0.0f) { nv.x = g2.x / g2.w; nv.y = g2.y / g2.w; nv.z = g2.z / g2.w; }
+    if (c.w != 0.0f) {
+        ev.x = c.x / c.w; ev.y = c.y / c.w; ev.z = c.z / c.w; ev.w = 1.0f;
+        if (demodulate) { ev.x = ev.x / fmaxf(av.x, 1e-2f); ev.y = ev.y / fmaxf(av.y, 1e-2f); ev.z = ev.z / fmaxf(av.z, 1e-2f); }
+    }
+    e[t] = ev; a[t] = av; n[t] = nv;
+}
+
+__global__ __launch_bounds__(256) void dn_epilogue_kernel(const float4 *__restrict__ e, const float4 *__restrict__ a,
+                                                          float4 *__restrict__ out, size_t npix, int demodulate) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= npix) return;
+    float4 v = e[t];
+    if (v.w != 0.0f) {
+        if (demodulate) {
+            const float4 av = a[t];
+            v.x = v.x * fmaxf(av.x, 1e-2f); v.y = v.y * fmaxf(av.y, 1e-2f); v.z = v.z * fmaxf(av.z, 1e-2f);
+        }
+        v.w = 1.0f;
+    } else {
+        v = make_float4(0.9f, 0.4f, 0.9f, 0.0f);               // FilmTable._get_image's empty pixel, filmtable.py:53-63
+    }
+    out[t] = v;
+}
+
+// ---------------------------------------------------------------- stencil, any stride: 75 coalesced 16-byte gathers per pixel
+// Block b covers columns [4 (b / by), +4) and rows [64 (b % by), +64), by = blocks along y (a one-dimensional grid: a film may be
+// wider than a grid's y extent allows).
+__global__ __launch_bounds__(256) void dn_atrous_gather_kernel(const float4 *__restrict__ e_in, float4 *__restrict__ e_out,
+                                                               const float4 *__restrict__ a, const float4 *__restrict__ n,
+                                                               int nx, int ny, int by, int s, float kc, float ka, float kn) {
+    const int x = (int)(blockIdx.x / by) * DN_ROWS + (int)threadIdx.y;
+    const int y = (int)(blockIdx.x % by) * DN_LANES + (int)threadIdx.x;
+    if (x >= nx || y >= ny) return;
+    const size_t p = (size_t)x * ny + y;
+    const float4 ep = e_in[p];
+    if (ep.w == 0.0f) { e_out[p] = ep; return; }
+    const float4 ap = a[p], np = n[p];
+    DnSum sum = { 0.f, 0.f, 0.f, 0.f };
+#pragma unroll 1
+    for (int dx = 0; dx < 5; dx++) {
+        const int qx = x + (dx - 2) * s;
+        const bool okx = qx >= 0 && qx < nx;
+        const float hx = dn_tap_weight(dx);
+#pragma unroll
+        for (int dy = 0; dy < 5; dy++) {
+            const int qy = y + (dy - 2) * s;
+            const bool in = okx && qy >= 0 && qy < ny;
+            const size_t q = in ? (size_t)qx * ny + qy : p;    // a tap outside the film reads the centre and weighs nothing
+            const float4 eq = e_in[q], aq = a[q], nq = n[q];
+            dn_tap(sum, hx * dn_tap_weight(dy), in && eq.w != 0.0f, ep, ap, np, eq, aq, nq, kc, ka, kn);
+        }
+    }
+    e_out[p] = dn_finish(sum);
+}
+
+// ---------------------------------------------------------------- stencil, strides 1 and 2: the tile and its halo in LDS
+// Tile: 8 columns x 64 rows; with the halo of 2 S on every side (8 + 4 S) x (64 + 4 S) records of e, a, n: 38 KiB at S = 1, 54 KiB at
+// S = 2.  Lanes read consecutive 16-byte records (ds_read_b128 over a contiguous run: no bank conflict).  Records outside the film
+// are written as zeros, whose valid flag is 0.
+template <int S>
+__global__ __launch_bounds__(256) void dn_atrous_lds_kernel(const float4 *__restrict__ e_in, float4 *__restrict__ e_out,
+                                                            const float4 *__restrict__ a, const float4 *__restrict__ n,
+                                                            int nx, int ny, int by, float kc, float ka, float kn) {
+    constexpr int R = 2 * S, W = DN_LANES + 2 * R, H = DN_TILE_X + 2 * R;
+    __shared__ float4 se[H * W], sa[H * W], sn[H * W];
+    const int x0 = (int)(blockIdx.x / by) * DN_TILE_X, y0 = (int)(blockIdx.x % by) * DN_LANES;
+    const int tid = (int)threadIdx.y * DN_LANES + (int)threadIdx.x;
+    for (int t = tid; t < H * W; t += DN_LANES * DN_ROWS) {
+        const int lx = t / W, ly = t - lx * W;
+        const int gx = x0 - R + lx, gy = y0 - R + ly;
+        float4 ev = make_float4(0.f, 0.f, 0.f, 0.f), av = ev, nv = ev;
+        if (gx >= 0 && gx < nx && gy >= 0 && gy < ny) {
+            const size_t q = (size_t)gx * ny + gy;
+            ev = e_in[q]; av = a[q]; nv = n[q];
+        }
+        se[t] = ev; sa[t] = av; sn[t] = nv;
+    }
+    __syncthreads();
+    const int y = y0 + (int)threadIdx.x;
+    if (y >= ny) return;
+#pragma unroll 1
+    for (int k = 0; k < DN_TILE_X / DN_ROWS; k++) {
+        const int lx = (int)threadIdx.y + DN_ROWS * k, x = x0 + lx;
+        if (x >= nx) break;
+        const size_t p = (size_t)x * ny + y;
+        const int c = (lx + R) * W + (int)threadIdx.x + R;
+        const float4 ep = se[c];
+        if (ep.w == 0.0f) { e_out[p] = ep; continue; }
+        const float4 ap = sa[c], np = sn[c];
+        DnSum sum = { 0.f, 0.f, 0.f, 0.f };
+#pragma unroll 1
+        for (int dx = 0; dx < 5; dx++) {
+            const float hx = dn_tap_weight(dx);
+            const int row = c + (dx - 2) * S * W;
+#pragma unroll
+            for (int dy = 0; dy < 5; dy++) {
+                const int t = row + (dy - 2) * S;
+                const float4 eq = se[t], aq = sa[t], nq = sn[t];
+                dn_tap(sum, hx * dn_tap_weight(dy), eq.w != 0.0f, ep, ap, np, eq, aq, nq, kc, ka, kn);
+            }
+        }
+        e_out[p] = dn_finish(sum);
+    }
+}
+
+// ---------------------------------------------------------------- launchers
+MPT_KERNEL_API hipError_t mpt_launch_denoise_prologue(const MptVec4 *f0, const MptVec4 *f1, const MptVec4 *f2, MptVec4 *e, MptVec4 *a,
+                                                      MptVec4 *n, size_t npix, int demodulate, hipStream_t stream) {
+    if (npix == 0) return hipSuccess;
+    const int grid = (int)((npix + 255) / 256);
+    hipLaunchKernelGGL(dn_prologue_kernel, dim3(grid), dim3(256), 0, stream, (const float4 *)f0, (const float4 *)f1, (const float4 *)f2,
+                       (float4 *)e, (float4 *)a, (float4 *)n, npix, demodulate);
+    return hipGetLastError();
+}
+
+// one iteration at stride s; use_lds: the strides 1 and 2 run the LDS kernel (same bits either way)
+MPT_KERNEL_API hipError_t mpt_launch_denoise_atrous(const MptVec4 *e_in, MptVec4 *e_out, const MptVec4 *a, const MptVec4 *n, int nx, int ny,
+                                                    int s, float kc, float ka, float kn, int use_lds, hipStream_t stream) {
+    if (nx <= 0 || ny <= 0) return hipSuccess;
+    const int by = (ny + DN_LANES - 1) / DN_LANES;
+    const dim3 block(DN_LANES, DN_ROWS);
+    const float4 *ei = (const float4 *)e_in, *ap = (const float4 *)a, *np = (const float4 *)n;
+    float4 *eo = (float4 *)e_out;
+    if (use_lds && s <= 2) {
+        const long long blocks = (long long)((nx + DN_TILE_X - 1) / DN_TILE_X) * by;
+        if (blocks > 0x7fffffffLL) return hipErrorInvalidConfiguration;
+        if (s == 1) hipLaunchKernelGGL(dn_atrous_lds_kernel<1>, dim3((unsigned)blocks), block, 0, stream, ei, eo, ap, np, nx, ny, by, kc, ka, kn);
+        else hipLaunchKernelGGL(dn_atrous_lds_kernel<2>, dim3((unsigned)blocks), block, 0, stream, ei, eo, ap, np, nx, ny, by, kc, ka, kn);
+    } else {
+        const long long blocks = (long long)((nx + DN_ROWS - 1) / DN_ROWS) * by;
+        if (blocks > 0x7fffffffLL) return hipErrorInvalidConfiguration;
+        hipLaunchKernelGGL(dn_atrous_gather_kernel, dim3((unsigned)blocks), block, 0, stream, ei, eo, ap, np, nx, ny, by, s, kc, ka, kn);
+    }
+    return hipGetLastError();
+}
+
+MPT_KERNEL_API hipError_t mpt_launch_denoise_epilogue(const MptVec4 *e, const MptVec4 *a, MptVec4 *out, size_t npix, int demodulate,
+                                                      hipStream_t stream) {
+    if (npix == 0) return hipSuccess;
+    const int grid = (int)((npix + 255) / 256);
+    hipLaunchKernelGGL(dn_epilogue_kernel, dim3(grid), dim3(256), 0, stream, (const float4 *)e, (const float4 *)a, (float4 *)out, npix, demodulate);
+    return hipGetLastError();
+}

@@ -206,13 +206,14 @@ extern "C" void mpt_destroy(mpt_ctx *c) {
     }
     if (c->ev_main) hipEventDestroy(c->ev_main);
     if (c->ev_film) hipEventDestroy(c->ev_film);
-    for (MptLaunchTimer *t : { &c->render_timer, &c->mlt_timer, &c->brute_timer })
+    for (MptLaunchTimer *t : { &c->render_timer, &c->mlt_timer, &c->brute_timer, &c->denoise_timer })
         for (auto &ev : t->events) hipEventDestroy(ev);
     for (auto &ev : c->event_pool) hipEventDestroy(ev);
     hipFree(c->mlt_X); hipFree(c->mlt_L); hipFree(c->mlt_bit); hipFree(c->mlt_keys); hipFree(c->mlt_keys2);
     hipFree(c->mlt_vals); hipFree(c->mlt_vals2); hipFree(c->mlt_tmp); hipFree(c->mlt_runs);
     for (int p = 0; p < 3; p++) hipFree(c->film[p]);
     hipFree(c->resolved); hipFree(c->exported);
+    hipFree(c->dn_e[0]); hipFree(c->dn_e[1]); hipFree(c->dn_a); hipFree(c->dn_n);
     hipFree(c->snode); hipFree(c->fnode); hipFree(c->tgeo); hipFree(c->tshade); hipFree(c->wnode); hipFree(c->qnode); hipFree(c->tfast);
     for (int k = 0; k < MPT_MAX_PIPE; k++) hipFree(c->stack_spill2[k]);
     hipFree(c->mats); hipFree(c->images); hipFree(c->texels); hipFree(c->lights);
@@ -310,6 +311,8 @@ extern "C" int mpt_set_option(mpt_ctx *c, const char *key, int value) {
         c->lds_wide = value;
     } else if (k == "zero_copy") {
         c->zero_copy = value ? 1 : 0;
+    } else if (k == "denoise_lds") {
+        c->denoise_lds = value ? 1 : 0;
     } else if (k == "shade_spec") {
         if (value != 0 && value != 1) return fail("shade_spec must be 0 (always the generic SHADE) or 1 (the plain one for plain scenes)");
         c->shade_spec = value;
@@ -396,6 +399,7 @@ extern "C" int mpt_get_option(mpt_ctx *c, const char *key, int *value) {
     else if (k == "lds_wide") *value = c->lds_wide;
     else if (k == "lds_block") *value = c->lds_block;
     else if (k == "zero_copy") *value = c->zero_copy;
+    else if (k == "denoise_lds") *value = c->denoise_lds;
     else if (k == "spin_us") *value = c->spin_us;
     else if (k == "finalise") *value = c->finalise;
     else if (k == "last_finalised") *value = c->last_finalised;
@@ -458,12 +462,15 @@ extern "C" int mpt_set_size(mpt_ctx *c, int nx, int ny) {
         for (int p = 0; p < 3; p++) { hipFree(c->film[p]); c->film[p] = nullptr; }
         hipFree(c->resolved); c->resolved = nullptr;
         hipFree(c->exported); c->exported = nullptr;
+        for (MptVec4 **b : { &c->dn_e[0], &c->dn_e[1], &c->dn_a, &c->dn_n }) { hipFree(*b); *b = nullptr; }
         for (int p = 0; p < 3; p++) {
             if (dev_alloc(&c->film[p], npix)) return 1;
             HIP_TRY(hipMemsetAsync(c->film[p], 0, npix * sizeof(MptVec4), c->stream));
         }
         if (dev_alloc(&c->resolved, npix)) return 1;
         if (dev_alloc(&c->exported, npix * 3)) return 1;
+        for (MptVec4 **b : { &c->dn_e[0], &c->dn_e[1], &c->dn_a, &c->dn_n })
+            if (dev_alloc(b, npix)) return 1;
         c->film_cap = npix;
     }
     // the reference keeps one flat buffer and only changes `res` (filmtable.py:41-42): stale sums
@@ -1501,6 +1508,56 @@ extern "C" int mpt_get_film_raw(mpt_ctx *c, int pass, float *out) {
     if (check_pass(c, pass)) return 1;
     if (read_back(c, out, c->film[pass], (size_t)c->nx * c->ny * sizeof(MptVec4))) return 1;
     return check_watchdog(c);
+}
+
+// ------------------------------------------------------------------ denoised read-back (denoise.hip)
+// Film pass 0 filtered by the edge-avoiding A-Trous wavelet, guided by passes 1 and 2, read back like mpt_get_image.  Runs on the
+// main stream behind everything enqueued (the flush makes that stream wait for the render launches, as for mpt_get_film_raw);
+// reads the three passes, writes only the context's working buffers, and knows nothing of mpt_hint_image's array.
+extern "C" int mpt_get_denoised(mpt_ctx *c, const mpt_denoise_params *params, float *out) {
+    if (use_ro(c)) return 1;
+    mpt_denoise_params p = { 5, 1.0f, 0.1f, 0.3f, 1 };
+    if (params) p = *params;
+    if (!out) return fail("mpt_get_denoised: null output");
+    if (p.iterations < 0 || p.iterations > 8) return fail("denoise: iterations must be in 0..8, got %d", p.iterations);
+    const struct { const char *name; float v; } sig[3] = { { "sigma_color", p.sigma_color }, { "sigma_albedo", p.sigma_albedo }, { "sigma_normal", p.sigma_normal } };
+    for (const auto &s : sig)
+        if (!(std::isfinite(s.v) && s.v > 0.0f)) return fail("denoise: %s must be finite and positive, got %g", s.name, (double)s.v);
+    if (mpt_flush(c)) return 1;
+    if (check_pass(c, 0)) return 1;
+    const size_t npix = (size_t)c->nx * c->ny;
+    const MptVec4 *img = c->dn_e[0];
+    hipEvent_t e0 = get_event(c), e1 = get_event(c);
+    HIP_TRY(hipEventRecord(e0, c->stream));
+    if (p.iterations == 0) {
+        // nothing to filter: the resolve pass itself, so that the image is mpt_get_image(0)'s bit for bit
+        HIP_TRY(mpt_launch_resolve(c->film[0], c->dn_e[0], npix, c->stream));
+    } else {
+        HIP_TRY(mpt_launch_denoise_prologue(c->film[0], c->film[1], c->film[2], c->dn_e[0], c->dn_a, c->dn_n, npix, p.demodulate ? 1 : 0, c->stream));
+        const float ka = 1.0f / (p.sigma_albedo * p.sigma_albedo), kn = 1.0f / (p.sigma_normal * p.sigma_normal);
+        for (int i = 0; i < p.iterations; i++) {
+            const float sc = p.sigma_color * std::ldexp(1.0f, -i);             // the colour edge-stopping narrows as the stencil widens
+            HIP_TRY(mpt_launch_denoise_atrous(c->dn_e[i & 1], c->dn_e[(i + 1) & 1], c->dn_a, c->dn_n, c->nx, c->ny, 1 << i,
+                                              1.0f / (sc * sc), ka, kn, c->denoise_lds, c->stream));
+        }
+        const int last = p.iterations & 1;
+        HIP_TRY(mpt_launch_denoise_epilogue(c->dn_e[last], c->dn_a, c->dn_e[last ^ 1], npix, p.demodulate ? 1 : 0, c->stream));
+        img = c->dn_e[last ^ 1];
+    }
+    HIP_TRY(hipEventRecord(e1, c->stream));
+    c->denoise_timer.record({ e0, e1 }, c->event_pool);
+    if (read_back(c, out, img, npix * sizeof(MptVec4))) return 1;
+    return check_watchdog(c);
+}
+
+extern "C" int mpt_denoise_kernel_time(mpt_ctx *c, double *ms, int *launches) {
+    if (use_ro(c)) return 1;
+    if (mpt_flush(c)) return 1;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    double total = 0;
+    if (c->denoise_timer.drain(&total, launches, c->event_pool)) return 1;
+    if (ms) *ms = total;
+    return 0;
 }
 
 // ------------------------------------------------------------------ measurement

@@ -54,6 +54,12 @@ MPT_KERNEL_API hipError_t mpt_launch_unit_eval_strict(const MptRenderParams *, i
 MPT_KERNEL_API hipError_t mpt_launch_copy_pieces(const MptVec4 *src, MptVec4 *dst, const MptPiece *tab, int npieces,
                                              long long max_count, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_export(const MptVec4 *film, float *out, int nx, int ny, hipStream_t);
+// denoise.hip: the A-Trous filter of pass 0 guided by passes 1 and 2 (mpt_get_denoised)
+MPT_KERNEL_API hipError_t mpt_launch_denoise_prologue(const MptVec4 *f0, const MptVec4 *f1, const MptVec4 *f2, MptVec4 *e, MptVec4 *a,
+                                                      MptVec4 *n, size_t npix, int demodulate, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_launch_denoise_atrous(const MptVec4 *e_in, MptVec4 *e_out, const MptVec4 *a, const MptVec4 *n, int nx, int ny,
+                                                    int s, float kc, float ka, float kn, int use_lds, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_launch_denoise_epilogue(const MptVec4 *e, const MptVec4 *a, MptVec4 *out, size_t npix, int demodulate, hipStream_t);
 
 // on-GPU LBVH build (lbvh_build.hip)
 struct MptLbvhBuffers {
@@ -155,6 +161,10 @@ struct mpt_ctx {
     size_t film_cap = 0;                 // pixels allocated per pass
     MptVec4 *resolved = nullptr;         // nx*ny float4 (get_image staging on device)
     float *exported = nullptr;           // nx*ny*3
+    // mpt_get_denoised's working buffers, nx*ny float4 each, allocated with the film: the filtered colour e (rgb, valid flag) in
+    // two copies the iterations alternate between (the one left over takes the image), and the guides a (albedo) and n (normal)
+    MptVec4 *dn_e[2] = { nullptr, nullptr }, *dn_a = nullptr, *dn_n = nullptr;
+    int denoise_lds = 1;                 // option "denoise_lds": the strides 1 and 2 filter from a tile in LDS (same bits as the gathers)
 
     // model (host copy kept for the tree build)
     int nfaces = 0;
@@ -246,6 +256,7 @@ struct mpt_ctx {
     void *mlt_tmp = nullptr;
     uint32_t *mlt_runs = nullptr;
     MptLaunchTimer mlt_timer{3};                         // {chain start, chain end = splat start, splat end} per launch
+    MptLaunchTimer denoise_timer{2};                     // mpt_get_denoised: {before the prologue, after the epilogue} per call
     MptLaunchTimer brute_timer{2};                       // brute-force engine: {kernel start, kernel end} per launch
     // command batching
     int pending = 0;

@@ -76,6 +76,23 @@ class FilmTable(metaclass=Singleton):
             raise
         return arr
 
+    def get_denoised(self, iterations=5, sigma_color=1.0, sigma_albedo=0.1, sigma_normal=0.3, demodulate=True):
+        '''pass 0 filtered on the device by the edge-avoiding A-Trous wavelet, guided by the albedo and normal passes the
+        PreviewEngine renders (mpt_get_denoised, include/miptina.h): [nx, ny, 4] f32 like get_image, a fresh array.  No reference
+        counterpart: its add-on hands the Albedo pass to Blender's denoiser'''
+        from ._lib import DenoiseParams
+        nx, ny = self._res()
+        arr = host_array((nx, ny, 4))
+        p = DenoiseParams(int(iterations), float(sigma_color), float(sigma_albedo), float(sigma_normal), 1 if demodulate else 0)
+        ctx().call('mpt_get_denoised', C.byref(p), fptr(arr))
+        return arr
+
+    def denoise_kernel_time(self):
+        '''(ms, calls): HIP-event time of the filter's kernels in the get_denoised calls since the last call'''
+        ms, n = C.c_double(0), C.c_int(0)
+        ctx().call('mpt_denoise_kernel_time', C.byref(ms), C.byref(n))
+        return ms.value, n.value
+
     def fast_export_image(self, out, id=0):
         '''reference filmtable.py:66-79: flat RGB f32 at (y * nx + x) * 3 into the caller's buffer'''
         nx, ny = self._res()
