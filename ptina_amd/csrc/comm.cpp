@@ -172,33 +172,24 @@ extern "C" int mpt_comm_gather_film(mpt_ctx *c, int pass, int root) {
         for (int k = 0; k < 6; k++) c->plan_key[k] = -1;
         c->plan_npieces = 0; c->plan_max_count = 0;
         if (tab.size() > 65535) return fail("film gather: %zu pieces exceed the 65535 the pack kernel's grid takes (wider stripes)", tab.size());
-        if ((size_t)total > c->gather_cap) {
-            hipFree(c->gather_buf); c->gather_buf = nullptr; c->gather_cap = 0;
-            if (dev_alloc(&c->gather_buf, (size_t)total)) return 1;
-            c->gather_cap = (size_t)total;
-        }
-        if (tab.size() > c->pieces_cap) {
-            hipFree(c->d_pieces); c->d_pieces = nullptr; c->pieces_cap = 0;
-            if (dev_alloc(&c->d_pieces, tab.size())) return 1;
-            c->pieces_cap = tab.size();
-        }
+        if (c->gather_buf.reserve((size_t)total) || c->d_pieces.reserve(tab.size())) return 1;
         if (!tab.empty()) HIP_TRY(hipMemcpy(c->d_pieces, tab.data(), tab.size() * sizeof(MptPiece), hipMemcpyHostToDevice));
         memcpy(c->plan_key, key, sizeof key);
         c->plan_npieces = (int)tab.size(); c->plan_max_count = max_count;
     }
     // ---- sender: pack, then one send
     if (!is_root && msg_pieces[c->rank] > 1)
-        HIP_TRY(mpt_launch_copy_pieces(c->film[pass], c->gather_buf, c->d_pieces, c->plan_npieces, c->plan_max_count, c->stream));
+        HIP_TRY(mpt_launch_copy_pieces(c->fb.film[pass], c->gather_buf, c->d_pieces, c->plan_npieces, c->plan_max_count, c->stream));
     NCCL_TRY(g_rccl.GroupStart());
     ncclResult_t bad = ncclSuccess;                // a failing call must not leave the group open
     if (is_root) {
         for (int r = 0; r < R && bad == ncclSuccess; r++) {
             if (r == root || msg_elems[r] == 0) continue;
-            MptVec4 *dst = msg_pieces[r] > 1 ? c->gather_buf + msg_base[r] : c->film[pass] + first_off[r];
+            MptVec4 *dst = msg_pieces[r] > 1 ? c->gather_buf + msg_base[r] : c->fb.film[pass] + first_off[r];
             bad = g_rccl.Recv(dst, (size_t)msg_elems[r] * 4, ncclFloat, r, c->comm, c->stream);
         }
     } else if (msg_elems[c->rank] > 0) {
-        const MptVec4 *src = msg_pieces[c->rank] > 1 ? c->gather_buf : c->film[pass] + first_off[c->rank];
+        const MptVec4 *src = msg_pieces[c->rank] > 1 ? c->gather_buf : c->fb.film[pass] + first_off[c->rank];
         bad = g_rccl.Send(src, (size_t)msg_elems[c->rank] * 4, ncclFloat, root, c->comm, c->stream);
     }
     ncclResult_t ended = g_rccl.GroupEnd();
@@ -206,7 +197,7 @@ extern "C" int mpt_comm_gather_film(mpt_ctx *c, int pass, int root) {
     NCCL_TRY(ended);
     // ---- root: scatter every packed message into the film
     if (is_root && c->plan_npieces > 0)
-        HIP_TRY(mpt_launch_copy_pieces(c->gather_buf, c->film[pass], c->d_pieces, c->plan_npieces, c->plan_max_count, c->stream));
+        HIP_TRY(mpt_launch_copy_pieces(c->gather_buf, c->fb.film[pass], c->d_pieces, c->plan_npieces, c->plan_max_count, c->stream));
     return 0;
 }
 
@@ -231,12 +222,12 @@ extern "C" int mpt_comm_selftest(mpt_ctx *c, int as_rank, int nranks, int root, 
         scatter.push_back({ at, off[i], cnt[i] });
         at += cnt[i]; max_count = std::max<long long>(max_count, cnt[i]);
     }
-    MptVec4 *d_in = nullptr, *d_out = nullptr, *d_msg = nullptr, *d_msg2 = nullptr;
-    MptPiece *d_tab = nullptr;
+    DevBuf<MptVec4> d_in, d_out, d_msg, d_msg2;
+    DevBuf<MptPiece> d_tab;
     int rc = 1;
     do {
-        if (dev_alloc(&d_in, npix) || dev_alloc(&d_out, npix) || dev_alloc(&d_msg, (size_t)at) || dev_alloc(&d_msg2, (size_t)at) ||
-            dev_alloc(&d_tab, (size_t)std::max(np, 1) * 2)) break;
+        if (d_in.reserve(npix) || d_out.reserve(npix) || d_msg.reserve(std::max<size_t>(at, 1)) || d_msg2.reserve(std::max<size_t>(at, 1)) ||
+            d_tab.reserve((size_t)std::max(np, 1) * 2)) break;
         // every copy on the context's own stream, the one the pack / scatter kernels run on: ordered by the stream itself and
         // not by what a blocking copy on the null stream happens to have finished when it returns
         if (hipMemcpyAsync(d_in, film_in, npix * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream) != hipSuccess) { fail("selftest upload"); break; }
@@ -255,7 +246,6 @@ extern "C" int mpt_comm_selftest(mpt_ctx *c, int as_rank, int nranks, int root, 
             hipStreamSynchronize(c->stream) != hipSuccess) { fail("selftest download"); break; }
         rc = 0;
     } while (0);
-    hipFree(d_in); hipFree(d_out); hipFree(d_msg); hipFree(d_msg2); hipFree(d_tab);
     return rc;
 }
 

@@ -120,23 +120,23 @@ extern "C" mpt_ctx *mpt_create(const mpt_caps *caps, int device) {
     if (c->caps.max_filmpasses < 3) c->caps.max_filmpasses = 3;
     auto bail = [&](const char *what) -> mpt_ctx * {
         std::string m = g_err;
+        mpt_destroy(c);              // what was allocated and created so far goes back
         fail("mpt_create: %s: %s", what, m.c_str());
-        delete c;
         return nullptr;
     };
     if (hipSetDevice(device) != hipSuccess) return bail("hipSetDevice");
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail("stream");
-    if (dev_alloc(&c->mats, (size_t)c->caps.max_materials + 1)) return bail("materials");   // + the default material's record
-    if (dev_alloc(&c->images, c->caps.max_textures)) return bail("images");
-    if (dev_alloc(&c->lights, MPT_MAX_LIGHTS)) return bail("lights");
-    if (dev_alloc(&c->d_counters, MPT_COUNTER_WORDS)) return bail("counters");
-    if (dev_alloc(&c->d_scratch, 2)) return bail("scratch");
-    if (dev_alloc(&c->d_work, MPT_QUEUE_WORDS)) return bail("work counters");   // 8 queue heads, a cache line each
+    if (c->mats.reserve((size_t)c->caps.max_materials + 1)) return bail("materials");   // + the default material's record
+    if (c->images.reserve(std::max<size_t>(c->caps.max_textures, 1))) return bail("images");
+    if (c->lights.reserve(MPT_MAX_LIGHTS)) return bail("lights");
+    if (c->d_counters.reserve(MPT_COUNTER_WORDS)) return bail("counters");
+    if (c->d_scratch.reserve(2)) return bail("scratch");
+    if (c->d_work.reserve(MPT_QUEUE_WORDS)) return bail("work counters");   // 8 queue heads, a cache line each
     for (int k = 0; k < MPT_MAX_PIPE; k++) {
         if (hipEventCreateWithFlags(&c->ev_sobol2[k], hipEventDisableTiming) != hipSuccess) return bail("event");
         if (hipEventCreateWithFlags(&c->ev_render[k], hipEventDisableTiming) != hipSuccess) return bail("event");
         if (hipEventCreateWithFlags(&c->ev_free[k], hipEventDisableTiming) != hipSuccess) return bail("event");
-        if (dev_alloc(&c->d_work2[k], MPT_QUEUE_WORDS)) return bail("work counters");
+        if (c->d_work2[k].reserve(MPT_QUEUE_WORDS)) return bail("work counters");
         hipMemsetAsync(c->d_work2[k], 0, MPT_QUEUE_WORDS * sizeof(unsigned int), c->stream);
     }
     if (hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking) != hipSuccess) return bail("aux stream");
@@ -152,12 +152,12 @@ extern "C" mpt_ctx *mpt_create(const mpt_caps *caps, int device) {
     if (make_render_streams(c)) return bail("render streams");
     {
         void *dp = nullptr;
-        if (hipHostMalloc((void **)&c->h_watchdog, sizeof(unsigned int), hipHostMallocMapped) != hipSuccess ||
+        if (c->h_watchdog.reserve(1, hipHostMallocMapped) ||
             hipHostGetDevicePointer(&dp, c->h_watchdog, 0) != hipSuccess) return bail("pinned watchdog flag");
         *c->h_watchdog = 0;
         c->d_watchdog = (unsigned int *)dp;
         void *dm = nullptr;
-        if (hipHostMalloc((void **)&c->h_sahmeta, 32 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
+        if (c->h_sahmeta.reserve(32, hipHostMallocMapped) ||
             hipHostGetDevicePointer(&dm, c->h_sahmeta, 0) != hipSuccess) return bail("pinned build mailbox");
         c->d_sahmeta = (int *)dm;
         memset(c->h_sahmeta, 0, 32 * sizeof(int));
@@ -186,49 +186,31 @@ extern "C" mpt_ctx *mpt_create(const mpt_caps *caps, int device) {
     return c;
 }
 
+// Everything the device and the streams still do for this context is waited for, the communicator, the streams and the events go,
+// and `delete` gives the memory back: every buffer is a DevBuf / PinnedBuf member.  Also the way out of a failed mpt_create, so
+// whatever was not created yet is skipped.
 extern "C" void mpt_destroy(mpt_ctx *c) {
     if (!c) return;
     hipSetDevice(c->device);
     for (int k = 0; k < MPT_MAX_PIPE; k++) if (c->rstream[k]) hipStreamSynchronize(c->rstream[k]);
     if (c->aux) { hipStreamSynchronize(c->aux); }
-    hipStreamSynchronize(c->stream);
+    if (c->stream) hipStreamSynchronize(c->stream);
     mpt_comm_release(c);
     if (c->aux) hipStreamDestroy(c->aux);
     if (c->probe_stream) hipStreamDestroy(c->probe_stream);
     if (c->stress_stream) { hipStreamSynchronize(c->stress_stream); hipStreamDestroy(c->stress_stream); }
-    hipFree(c->stress_buf);
     for (int k = 0; k < MPT_MAX_PIPE; k++) {
         if (c->rstream[k]) hipStreamDestroy(c->rstream[k]);
         if (c->ev_render[k]) hipEventDestroy(c->ev_render[k]);
         if (c->ev_free[k]) hipEventDestroy(c->ev_free[k]);
         if (c->ev_sobol2[k]) hipEventDestroy(c->ev_sobol2[k]);
-        hipFree(c->partial2[k]); hipFree(c->sP2[k]); hipFree(c->d_work2[k]);
     }
     if (c->ev_main) hipEventDestroy(c->ev_main);
     if (c->ev_film) hipEventDestroy(c->ev_film);
     for (MptLaunchTimer *t : { &c->render_timer, &c->mlt_timer, &c->brute_timer, &c->denoise_timer })
         for (auto &ev : t->events) hipEventDestroy(ev);
     for (auto &ev : c->event_pool) hipEventDestroy(ev);
-    hipFree(c->mlt_X); hipFree(c->mlt_L); hipFree(c->mlt_bit); hipFree(c->mlt_keys); hipFree(c->mlt_keys2);
-    hipFree(c->mlt_vals); hipFree(c->mlt_vals2); hipFree(c->mlt_tmp); hipFree(c->mlt_runs);
-    for (int p = 0; p < 3; p++) hipFree(c->film[p]);
-    hipFree(c->resolved); hipFree(c->exported);
-    hipFree(c->dn_e[0]); hipFree(c->dn_e[1]); hipFree(c->dn_a); hipFree(c->dn_n);
-    hipFree(c->snode); hipFree(c->fnode); hipFree(c->tgeo); hipFree(c->tshade); hipFree(c->wnode); hipFree(c->qnode); hipFree(c->tfast);
-    for (int k = 0; k < MPT_MAX_PIPE; k++) hipFree(c->stack_spill2[k]);
-    hipFree(c->mats); hipFree(c->images); hipFree(c->texels); hipFree(c->lights);
-    hipFree(c->sV); hipFree(c->sX); hipFree(c->sX_spec); hipFree(c->sP);
-    hipFree(c->gather_buf); hipFree(c->d_pieces); hipFree(c->sah_ws);
-    hipFree(c->wb_bin_of); hipFree(c->wb_ncount); hipFree(c->wb_offset); hipFree(c->wb_scan); hipFree(c->wb_area);
-    hipFree(c->d_counters); hipFree(c->d_scratch); hipFree(c->d_work); hipFree(c->d_timeline);
-    if (c->h_watchdog) hipHostFree(c->h_watchdog);
-    if (c->h_sahmeta) hipHostFree(c->h_sahmeta);
-    if (c->h_stage) hipHostFree(c->h_stage);
-    hipFree(c->d_verts); hipFree(c->d_mtlids); hipFree(c->d_cen); hipFree(c->d_bounds); hipFree(c->d_depth);
-    hipFree(c->d_keys_in); hipFree(c->d_keys_out); hipFree(c->d_sort_tmp);
-    hipFree(c->d_child); hipFree(c->d_parent); hipFree(c->d_leaf); hipFree(c->d_mc);
-    hipFree(c->d_bmin); hipFree(c->d_bmax); hipFree(c->d_arrive);
-    hipStreamDestroy(c->stream);
+    if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -275,12 +257,7 @@ static int read_back(mpt_ctx *c, void *out, const void *dev, size_t bytes) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         return 0;
     }
-    if (bytes > c->h_stage_bytes) {
-        if (c->h_stage) hipHostFree(c->h_stage);
-        c->h_stage = nullptr; c->h_stage_bytes = 0;
-        HIP_TRY(hipHostMalloc(&c->h_stage, bytes, hipHostMallocDefault));
-        c->h_stage_bytes = bytes;
-    }
+    if (c->h_stage.reserve(bytes, hipHostMallocDefault)) return 1;
     HIP_TRY(hipMemcpyAsync(c->h_stage, dev, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     memcpy(out, c->h_stage, bytes);
@@ -457,21 +434,9 @@ extern "C" int mpt_set_size(mpt_ctx *c, int nx, int ny) {
     size_t npix = (size_t)nx * ny;
     if (npix > (size_t)c->caps.max_filmsize)
         return fail("film %dx%d exceeds max_filmsize=%d (init_things(max_filmsize=...))", nx, ny, c->caps.max_filmsize);
-    if (npix > c->film_cap) {
+    if (npix > c->fb.cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        for (int p = 0; p < 3; p++) { hipFree(c->film[p]); c->film[p] = nullptr; }
-        hipFree(c->resolved); c->resolved = nullptr;
-        hipFree(c->exported); c->exported = nullptr;
-        for (MptVec4 **b : { &c->dn_e[0], &c->dn_e[1], &c->dn_a, &c->dn_n }) { hipFree(*b); *b = nullptr; }
-        for (int p = 0; p < 3; p++) {
-            if (dev_alloc(&c->film[p], npix)) return 1;
-            HIP_TRY(hipMemsetAsync(c->film[p], 0, npix * sizeof(MptVec4), c->stream));
-        }
-        if (dev_alloc(&c->resolved, npix)) return 1;
-        if (dev_alloc(&c->exported, npix * 3)) return 1;
-        for (MptVec4 **b : { &c->dn_e[0], &c->dn_e[1], &c->dn_a, &c->dn_n })
-            if (dev_alloc(b, npix)) return 1;
-        c->film_cap = npix;
+        if (c->fb.reserve(npix, c->stream)) return 1;
     }
     // the reference keeps one flat buffer and only changes `res` (filmtable.py:41-42): stale sums
     // of another resolution are the caller's to clear(); same here.
@@ -610,7 +575,7 @@ extern "C" int mpt_load_image(mpt_ctx *c, const float *rgba, int nx, int ny, int
     if ((int)c->h_images.size() >= c->caps.max_textures) return fail("Out of ID!");       // allocator.py:53
     size_t need = (size_t)nx * ny;
     if (c->texels_used + need > (size_t)c->caps.max_texels) return fail("Out of memory!"); // allocator.py:24
-    if (!c->texels) { if (dev_alloc(&c->texels, (size_t)c->caps.max_texels)) return 1; }
+    if (!c->texels && c->texels.reserve(std::max<size_t>(c->caps.max_texels, 1))) return 1;
     HIP_TRY(hipMemcpyAsync(c->texels + c->texels_used, rgba, need * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
     MptImage im = { nx, ny, (int32_t)c->texels_used, 0 };
     c->h_images.push_back(im);
@@ -664,14 +629,13 @@ extern "C" int mpt_sobol_init(mpt_ctx *c, const int32_t *V, int rows, int dim) {
     if (use(c)) return 1;
     if (rows < 2 || dim < 1 || !V) return fail("bad sobol grid %dx%d", rows, dim);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    hipFree(c->sV); hipFree(c->sX); hipFree(c->sX_spec); hipFree(c->sP);
-    c->sV = c->sX = c->sX_spec = nullptr; c->sP = nullptr;
+    c->sV.release(); c->sX.release(); c->sX_spec.release(); c->sP.release();
     HIP_TRY(hipStreamSynchronize(c->aux));
-    for (int k = 0; k < MPT_MAX_PIPE; k++) { HIP_TRY(hipStreamSynchronize(c->rstream[k])); hipFree(c->sP2[k]); c->sP2[k] = nullptr; }
-    if (dev_alloc(&c->sV, (size_t)rows * dim) || dev_alloc(&c->sX, (size_t)dim) || dev_alloc(&c->sX_spec, (size_t)dim) ||
-        dev_alloc(&c->sP, (size_t)MPT_MAX_BATCH * dim)) return 1;
+    for (int k = 0; k < MPT_MAX_PIPE; k++) { HIP_TRY(hipStreamSynchronize(c->rstream[k])); c->sP2[k].release(); }
+    if (c->sV.reserve((size_t)rows * dim) || c->sX.reserve((size_t)dim) || c->sX_spec.reserve((size_t)dim) ||
+        c->sP.reserve((size_t)MPT_MAX_BATCH * dim)) return 1;
     for (int k = 0; k < MPT_MAX_PIPE; k++)
-        if (dev_alloc(&c->sP2[k], (size_t)MPT_MAX_BATCH * dim)) return 1;
+        if (c->sP2[k].reserve((size_t)MPT_MAX_BATCH * dim)) return 1;
     HIP_TRY(hipMemcpyAsync(c->sV, V, (size_t)rows * dim * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->sX, 0, (size_t)dim * sizeof(int), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -785,10 +749,10 @@ static int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes) {
         p.t_unscale = (float)std::ldexp(1.0, e);
     }
     p.wnode = c->wnode; p.qnode = c->qnode; p.nwide = c->wide_nodes; p.stack_spill = nullptr;
-    p.snode = c->snode; p.fnode = c->fnode; p.tgeo = c->tgeo; p.tshade = c->tshade; p.tfast = c->tfast;
+    p.snode = c->nodes.snode; p.fnode = c->nodes.fnode; p.tgeo = c->tris.tgeo; p.tshade = c->tris.tshade; p.tfast = c->tfast;
     p.skip_dark = c->skip_dark >= 0 ? c->skip_dark : (c->mode == MPT_MODE_FAST ? 1 : 0);
     p.P = c->sP;
-    p.film0 = c->film[0]; p.film1 = c->film[1]; p.film2 = c->film[2];
+    p.film0 = c->fb.film[0]; p.film1 = c->fb.film[1]; p.film2 = c->fb.film[2];
     p.counters = c->d_counters;
     p.lane_hist = c->lane_hist;
     p.watchdog = c->d_watchdog;
@@ -869,7 +833,7 @@ static int batch_points(mpt_ctx *c, MptRenderParams &p, const BatchSlot &s, int 
         // the points AND the state this batch leaves behind were computed when the previous batch was launched: the sampler moves by
         // a swap of two pointers -- no kernel at launch time (round 3 ran an X-only update here, whose 83 small workgroups took
         // CUs just when the persistent render workgroups wanted them: half the workgroups of a 1/8-share launch started 35 us late)
-        std::swap(c->sX, c->sX_spec);
+        c->sX.swap(c->sX_spec);
         c->stime = (int32_t)((uint32_t)c->stime + (uint32_t)B);
     } else if (sobol_advance(c, B, B, s.ss, s.fast ? c->sP2[k] : nullptr)) return 1;
     return 0;
@@ -918,15 +882,12 @@ static int work_items(const mpt_ctx *c, MptRenderParams &p, int B, bool fast) {
 // device, so it must not happen again on the second, third, ... batch of a run.  zero: fresh memory is zeroed on the main
 // stream; *grown: a slot was replaced.
 template <class T>
-static int grow_ring(mpt_ctx *c, T *(&buf)[MPT_MAX_PIPE], size_t (&cap)[MPT_MAX_PIPE], size_t need, bool zero, bool *grown) {
+static int grow_ring(mpt_ctx *c, DevBuf<T> (&buf)[MPT_MAX_PIPE], size_t need, bool zero, bool *grown) {
     for (int q = 0; q < c->cur_depth; q++)
-        if (need > cap[q]) {
+        if (need > buf[q].cap) {
             HIP_TRY(hipDeviceSynchronize());
-            hipFree(buf[q]); buf[q] = nullptr; cap[q] = 0;
-            if (dev_alloc(&buf[q], need)) return 1;
-            cap[q] = need;
+            if (buf[q].reserve(need, grown)) return 1;
             if (zero) HIP_TRY(hipMemsetAsync(buf[q], 0, need * sizeof(T), c->stream));
-            *grown = true;
         }
     return 0;
 }
@@ -942,7 +903,7 @@ static int slab_and_queue_heads(mpt_ctx *c, MptRenderParams &p, const BatchSlot 
     // hold one by accident -- and it does: the allocator hands back the slab of an earlier context, whose first
     // finalising launch used the very tag this context's first one will use
     bool zeroed = false;
-    if (grow_ring(c, c->partial2, c->partial2_cap, need, true, &zeroed)) return 1;
+    if (grow_ring(c, c->partial2, need, true, &zeroed)) return 1;
     // ... and the zeros must be there before any launch of the ring writes or reads the slab: the render streams are not
     // ordered behind the stream that zeroes, and a memset may return before it is done.  (Seen in the full GPU test run as a
     // 2048 x 2048 film with single samples of an earlier test's render in it: its 2 GiB slabs take a millisecond to zero.)
@@ -997,7 +958,7 @@ static int size_launch_buffers(mpt_ctx *c, MptRenderParams &p, int k, int kernel
         const size_t need_spill = (size_t)*wide_blocks * MPT_BLOCK * 128;   // >= SpillStack::SPILL entries per lane (128 - LDS levels)
         // one strip PER SLOT: the launches of different slots overlap, and a strip is indexed by block and lane only
         bool grown = false;
-        if (grow_ring(c, c->stack_spill2, c->stack_spill2_cap, need_spill, false, &grown)) return 1;
+        if (grow_ring(c, c->stack_spill2, need_spill, false, &grown)) return 1;
         p.stack_spill = c->stack_spill2[k];
     }
     const bool lds_kernel = kernel == MPT_KERNEL_LDS || kernel == MPT_KERNEL_LDS4;
@@ -1015,8 +976,8 @@ static int size_launch_buffers(mpt_ctx *c, MptRenderParams &p, int k, int kernel
         const int waves = launch_cus * (*lds_block / 64);
         if (waves != c->timeline_waves) {
             HIP_TRY(hipDeviceSynchronize());
-            hipFree(c->d_timeline); c->d_timeline = nullptr;
-            if (dev_alloc(&c->d_timeline, (size_t)waves * MPT_TIMELINE_WORDS)) return 1;
+            c->d_timeline.release();
+            if (c->d_timeline.reserve((size_t)waves * MPT_TIMELINE_WORDS)) return 1;
             HIP_TRY(hipMemsetAsync(c->d_timeline, 0, (size_t)waves * MPT_TIMELINE_WORDS * sizeof(unsigned long long), c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
             c->timeline_waves = waves;
@@ -1049,7 +1010,7 @@ static int setup_finalisation(mpt_ctx *c, MptRenderParams &p, const BatchSlot &s
         c->tag_epoch = epoch;
         HIP_TRY(hipStreamSynchronize(c->stream));
         for (int q = 0; q < MPT_MAX_PIPE; q++)
-            if (c->partial2[q]) HIP_TRY(hipMemsetAsync(c->partial2[q], 0, c->partial2_cap[q] * sizeof(MptVec4), s.rs));
+            if (c->partial2[q]) HIP_TRY(hipMemsetAsync(c->partial2[q], 0, c->partial2[q].cap * sizeof(MptVec4), s.rs));
         HIP_TRY(hipStreamSynchronize(s.rs));
         c->tag_wraps++;
     }
@@ -1105,7 +1066,7 @@ static int behind_launch(mpt_ctx *c, const MptRenderParams &p, const BatchSlot &
     HIP_TRY(hipEventRecord(c->ev_render[k], s.rs));
     HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_render[k], 0));
     if (!fin)
-        HIP_TRY(mpt_launch_combine(c->film[0], c->partial2[k], c->ny, c->x0, c->x1, p.stripe_w, p.stripe_pitch,
+        HIP_TRY(mpt_launch_combine(c->fb.film[0], c->partial2[k], c->ny, c->x0, c->x1, p.stripe_w, p.stripe_pitch,
                                    p.partial_stride / std::max(c->ny, 1), B, c->stream));
     HIP_TRY(hipEventRecord(c->ev_free[k], c->stream));      // (a finalising launch has consumed its slab itself)
     // Ahead of time, on the aux stream: the Sobol points and zeroed queue heads of the NEXT batch, assuming it
@@ -1211,35 +1172,23 @@ static int mlt_flush(mpt_ctx *c) {
     const int kmax = std::max(1, (int)(MPT_MLT_SLAB_RECORDS / nch));
     const int K0 = std::min(n, kmax);
     const size_t recs = (size_t)K0 * nch, npix = (size_t)c->nx * c->ny;
-    if (recs > c->mlt_cap || npix > c->mlt_runs_cap) {
+    if (recs > c->slab.cap || npix > c->slab.runs_cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        const size_t cap = std::max(recs, c->mlt_cap), rcap = std::max(npix, c->mlt_runs_cap);
-        size_t tmp = 0;
-        HIP_TRY(mpt_mlt_sort_bytes((int)cap, (int)rcap, &tmp));
-        hipFree(c->mlt_keys); hipFree(c->mlt_keys2); hipFree(c->mlt_vals); hipFree(c->mlt_vals2); hipFree(c->mlt_tmp); hipFree(c->mlt_runs);
-        c->mlt_keys = c->mlt_keys2 = nullptr; c->mlt_vals = c->mlt_vals2 = nullptr; c->mlt_tmp = nullptr; c->mlt_runs = nullptr;
-        c->mlt_cap = c->mlt_runs_cap = 0;
-        HIP_TRY(hipMalloc(&c->mlt_keys, cap * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&c->mlt_keys2, cap * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&c->mlt_vals, cap * sizeof(MptVec4)));
-        HIP_TRY(hipMalloc(&c->mlt_vals2, cap * sizeof(MptVec4)));
-        HIP_TRY(hipMalloc(&c->mlt_tmp, std::max(tmp, (size_t)16)));
-        HIP_TRY(hipMalloc(&c->mlt_runs, rcap * 2 * sizeof(uint32_t)));
-        c->mlt_cap = cap; c->mlt_runs_cap = rcap; c->mlt_tmp_bytes = std::max(tmp, (size_t)16);
+        if (c->slab.reserve(recs, npix)) return 1;
     }
     const int stack = gather_stack_levels(c);
     while (n > 0) {
         const int K = std::min(n, kmax);
         MptMltArgs a;
-        a.X = c->mlt_X; a.L = c->mlt_L; a.bit = c->mlt_bit; a.keys = c->mlt_keys; a.vals = c->mlt_vals;
+        a.X = c->mlt_X; a.L = c->mlt_L; a.bit = c->mlt_bit; a.keys = c->slab.keys; a.vals = c->slab.vals;
         a.nchains = nch; a.t0 = c->mlt_iter; a.K = K; a.seed = c->mlt_seed; a.lsp = c->mlt_lsp; a.sigma = c->mlt_sigma;
         hipEvent_t e0 = get_event(c), e1 = get_event(c), e2 = get_event(c);
         HIP_TRY(hipEventRecord(e0, c->stream));
         if (c->mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_mlt_chain_strict(&p, &a, stack, c->stream));
         else HIP_TRY(mpt_launch_mlt_chain_fast(&p, &a, stack, c->stream));
         HIP_TRY(hipEventRecord(e1, c->stream));
-        HIP_TRY(mpt_launch_mlt_splat(c->film[0], c->mlt_keys, c->mlt_vals, c->mlt_keys2, c->mlt_vals2, c->mlt_tmp, c->mlt_tmp_bytes,
-                                     c->mlt_runs, K * nch, (int)npix, c->stream));
+        HIP_TRY(mpt_launch_mlt_splat(c->fb.film[0], c->slab.keys, c->slab.vals, c->slab.keys2, c->slab.vals2, c->slab.tmp, c->slab.tmp.cap,
+                                     c->slab.runs, K * nch, (int)npix, c->stream));
         HIP_TRY(hipEventRecord(e2, c->stream));
         c->mlt_timer.record({ e0, e1, e2 }, c->event_pool);
         c->mlt_iter += K;
@@ -1255,11 +1204,8 @@ extern "C" int mpt_mlt_reset(mpt_ctx *c, int nchains, uint32_t seed) {         /
     if (nchains <= 0 || nchains > (1 << 24)) return fail("nchains %d outside [1, 2^24]", nchains);
     if (nchains != c->mlt_n) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->mlt_X); hipFree(c->mlt_L); hipFree(c->mlt_bit);
-        c->mlt_X = c->mlt_L = nullptr; c->mlt_bit = nullptr; c->mlt_n = 0;
-        HIP_TRY(hipMalloc(&c->mlt_X, (size_t)nchains * 2 * 32 * sizeof(float)));
-        HIP_TRY(hipMalloc(&c->mlt_L, (size_t)nchains * 3 * sizeof(float)));
-        HIP_TRY(hipMalloc(&c->mlt_bit, (size_t)nchains * sizeof(int32_t)));
+        c->mlt_X.release(); c->mlt_L.release(); c->mlt_bit.release(); c->mlt_n = 0;
+        if (c->mlt_X.reserve((size_t)nchains * 2 * 32) || c->mlt_L.reserve((size_t)nchains * 3) || c->mlt_bit.reserve((size_t)nchains)) return 1;
         c->mlt_n = nchains;
     }
     c->mlt_seed = seed; c->mlt_iter = 0; c->mlt_pending = 0;
@@ -1326,16 +1272,14 @@ extern "C" int mpt_mlt_trace(mpt_ctx *c, const float *X, float *rgb, int n) {
     if (n == 0) return 0;
     MptRenderParams p;
     if (fill_params(c, p, 1)) return 1;
-    float *dX = nullptr, *drgb = nullptr;
-    HIP_TRY(hipMalloc(&dX, (size_t)n * 32 * sizeof(float)));
-    if (hipMalloc(&drgb, (size_t)n * 3 * sizeof(float)) != hipSuccess) { hipFree(dX); return fail("mpt_mlt_trace: out of device memory"); }
+    DevBuf<float> dX, drgb;
+    if (dX.reserve((size_t)n * 32) || drgb.reserve((size_t)n * 3)) return 1;
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(dX, X, (size_t)n * 32 * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = c->mode == MPT_MODE_STRICT ? mpt_launch_mlt_trace_strict(&p, dX, drgb, n, gather_stack_levels(c), c->stream)
                                                         : mpt_launch_mlt_trace_fast(&p, dX, drgb, n, gather_stack_levels(c), c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(rgb, drgb, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost);
-    hipFree(dX); hipFree(drgb);
     if (e != hipSuccess) return fail("mpt_mlt_trace: %s", hipGetErrorString(e));
     return 0;
 }
@@ -1397,7 +1341,7 @@ extern "C" int mpt_brute_kernel_time(mpt_ctx *c, double *ms, int *launches) {
 int check_watchdog(mpt_ctx *c) {
     // read and re-arm: the failure is reported once, by the first read-back after it (the film holds
     // incomplete sums until the caller clears it)
-    if (__atomic_exchange_n(c->h_watchdog, 0u, __ATOMIC_ACQ_REL))
+    if (__atomic_exchange_n(c->h_watchdog.p, 0u, __ATOMIC_ACQ_REL))
         return fail("render kernel stopped by its watchdog (scheduler made no progress): film is incomplete");
     return 0;
 }
@@ -1416,14 +1360,14 @@ extern "C" int mpt_clear(mpt_ctx *c, int pass) {                               /
     if (use(c)) return 1;
     size_t npix = (size_t)c->nx * c->ny;
     for (int p = 0; p < 3; p++)
-        if (c->film[p]) HIP_TRY(hipMemsetAsync(c->film[p], 0, npix * sizeof(MptVec4), c->stream));
+        if (c->fb.film[p]) HIP_TRY(hipMemsetAsync(c->fb.film[p], 0, npix * sizeof(MptVec4), c->stream));
     c->film_version++;
     return 0;
 }
 
 int check_pass(mpt_ctx *c, int pass) {
     if (pass < 0 || pass >= 3) return fail("film pass %d out of range", pass);
-    if (!c->film[pass]) return fail("film size not set: call set_size() first");
+    if (!c->fb.film[pass]) return fail("film size not set: call set_size() first");
     return 0;
 }
 
@@ -1431,7 +1375,7 @@ extern "C" int mpt_resolve(mpt_ctx *c, int pass) {
     if (use_ro(c)) return 1;
     if (mpt_flush(c)) return 1;
     if (check_pass(c, pass)) return 1;
-    HIP_TRY(mpt_launch_resolve(c->film[pass], c->resolved, (size_t)c->nx * c->ny, c->stream));
+    HIP_TRY(mpt_launch_resolve(c->fb.film[pass], c->fb.resolved, (size_t)c->nx * c->ny, c->stream));
     return 0;
 }
 
@@ -1484,12 +1428,12 @@ extern "C" int mpt_get_image(mpt_ctx *c, int pass, float *out) {               /
         // instead of into a device buffer that a DMA then copies (one dependent hop and the copy engine's start-up less)
         if (mpt_flush(c)) return 1;
         if (check_pass(c, pass)) return 1;
-        HIP_TRY(mpt_launch_resolve(c->film[pass], (MptVec4 *)mapped, (size_t)c->nx * c->ny, c->stream));
+        HIP_TRY(mpt_launch_resolve(c->fb.film[pass], (MptVec4 *)mapped, (size_t)c->nx * c->ny, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         return check_watchdog(c);
     }
     if (mpt_resolve(c, pass)) return 1;
-    if (read_back(c, out, c->resolved, bytes)) return 1;
+    if (read_back(c, out, c->fb.resolved, bytes)) return 1;
     return check_watchdog(c);
 }
 
@@ -1497,8 +1441,8 @@ extern "C" int mpt_fast_export_image(mpt_ctx *c, int pass, float *out) {       /
     if (use_ro(c)) return 1;
     if (mpt_flush(c)) return 1;
     if (check_pass(c, pass)) return 1;
-    HIP_TRY(mpt_launch_export(c->film[pass], c->exported, c->nx, c->ny, c->stream));
-    if (read_back(c, out, c->exported, (size_t)c->nx * c->ny * 3 * sizeof(float))) return 1;
+    HIP_TRY(mpt_launch_export(c->fb.film[pass], c->fb.exported, c->nx, c->ny, c->stream));
+    if (read_back(c, out, c->fb.exported, (size_t)c->nx * c->ny * 3 * sizeof(float))) return 1;
     return check_watchdog(c);
 }
 
@@ -1506,7 +1450,7 @@ extern "C" int mpt_get_film_raw(mpt_ctx *c, int pass, float *out) {
     if (use_ro(c)) return 1;
     if (mpt_flush(c)) return 1;
     if (check_pass(c, pass)) return 1;
-    if (read_back(c, out, c->film[pass], (size_t)c->nx * c->ny * sizeof(MptVec4))) return 1;
+    if (read_back(c, out, c->fb.film[pass], (size_t)c->nx * c->ny * sizeof(MptVec4))) return 1;
     return check_watchdog(c);
 }
 
@@ -1526,23 +1470,23 @@ extern "C" int mpt_get_denoised(mpt_ctx *c, const mpt_denoise_params *params, fl
     if (mpt_flush(c)) return 1;
     if (check_pass(c, 0)) return 1;
     const size_t npix = (size_t)c->nx * c->ny;
-    const MptVec4 *img = c->dn_e[0];
+    const MptVec4 *img = c->fb.dn_e[0];
     hipEvent_t e0 = get_event(c), e1 = get_event(c);
     HIP_TRY(hipEventRecord(e0, c->stream));
     if (p.iterations == 0) {
         // nothing to filter: the resolve pass itself, so that the image is mpt_get_image(0)'s bit for bit
-        HIP_TRY(mpt_launch_resolve(c->film[0], c->dn_e[0], npix, c->stream));
+        HIP_TRY(mpt_launch_resolve(c->fb.film[0], c->fb.dn_e[0], npix, c->stream));
     } else {
-        HIP_TRY(mpt_launch_denoise_prologue(c->film[0], c->film[1], c->film[2], c->dn_e[0], c->dn_a, c->dn_n, npix, p.demodulate ? 1 : 0, c->stream));
+        HIP_TRY(mpt_launch_denoise_prologue(c->fb.film[0], c->fb.film[1], c->fb.film[2], c->fb.dn_e[0], c->fb.dn_a, c->fb.dn_n, npix, p.demodulate ? 1 : 0, c->stream));
         const float ka = 1.0f / (p.sigma_albedo * p.sigma_albedo), kn = 1.0f / (p.sigma_normal * p.sigma_normal);
         for (int i = 0; i < p.iterations; i++) {
             const float sc = p.sigma_color * std::ldexp(1.0f, -i);             // the colour edge-stopping narrows as the stencil widens
-            HIP_TRY(mpt_launch_denoise_atrous(c->dn_e[i & 1], c->dn_e[(i + 1) & 1], c->dn_a, c->dn_n, c->nx, c->ny, 1 << i,
+            HIP_TRY(mpt_launch_denoise_atrous(c->fb.dn_e[i & 1], c->fb.dn_e[(i + 1) & 1], c->fb.dn_a, c->fb.dn_n, c->nx, c->ny, 1 << i,
                                               1.0f / (sc * sc), ka, kn, c->denoise_lds, c->stream));
         }
         const int last = p.iterations & 1;
-        HIP_TRY(mpt_launch_denoise_epilogue(c->dn_e[last], c->dn_a, c->dn_e[last ^ 1], npix, p.demodulate ? 1 : 0, c->stream));
-        img = c->dn_e[last ^ 1];
+        HIP_TRY(mpt_launch_denoise_epilogue(c->fb.dn_e[last], c->fb.dn_a, c->fb.dn_e[last ^ 1], npix, p.demodulate ? 1 : 0, c->stream));
+        img = c->fb.dn_e[last ^ 1];
     }
     HIP_TRY(hipEventRecord(e1, c->stream));
     c->denoise_timer.record({ e0, e1 }, c->event_pool);
@@ -1626,8 +1570,8 @@ extern "C" int mpt_stress_copies(mpt_ctx *c, int mbytes, int count) {
     const size_t bytes = (size_t)mbytes << 20;
     if (bytes != c->stress_bytes) {
         HIP_TRY(hipStreamSynchronize(c->stress_stream));
-        hipFree(c->stress_buf); c->stress_buf = nullptr; c->stress_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&c->stress_buf, 2 * bytes));
+        c->stress_buf.release(); c->stress_bytes = 0;
+        if (c->stress_buf.reserve(2 * bytes)) return 1;
         HIP_TRY(hipMemsetAsync(c->stress_buf, 0x5a, 2 * bytes, c->stress_stream));
         c->stress_bytes = bytes;
     }
@@ -1686,11 +1630,9 @@ extern "C" int mpt_unit_eval(mpt_ctx *c, int kind, const void *in, int in_cols, 
             }
         }
     }
-    float *d_in = nullptr, *d_out = nullptr;
-    MptVec4 *d_shade = nullptr;
-    if (dev_alloc(&d_in, (size_t)n * in_cols)) return 1;
-    if (dev_alloc(&d_out, (size_t)n * out_cols)) { hipFree(d_in); return 1; }
-    if (!shade.empty() && dev_alloc(&d_shade, shade.size())) { hipFree(d_in); hipFree(d_out); return 1; }
+    DevBuf<float> d_in, d_out;
+    DevBuf<MptVec4> d_shade;
+    if (d_in.reserve((size_t)n * in_cols) || d_out.reserve((size_t)n * out_cols) || d_shade.reserve(shade.size())) return 1;
     hipError_t e = hipMemcpyAsync(d_in, in, (size_t)n * in_cols * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && d_shade) e = hipMemcpyAsync(d_shade, shade.data(), shade.size() * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream);
     p.tshade = d_shade;
@@ -1700,7 +1642,6 @@ extern "C" int mpt_unit_eval(mpt_ctx *c, int kind, const void *in, int in_cols, 
                                        : mpt_launch_unit_eval_fast(&p, kind, d_in, in_cols, d_out, out_cols, n, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * out_cols * 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d_in); hipFree(d_out); hipFree(d_shade);
     if (e != hipSuccess) return fail("mpt_unit_eval: %s", hipGetErrorString(e));
     return 0;
 }

@@ -83,7 +83,7 @@ MPT_KERNEL_API int mpt_sah_task_max(void);
 MPT_KERNEL_API hipError_t mpt_sah_build(const MptSahBuffers *B, int *depth, hipStream_t stream);
 MPT_KERNEL_API hipError_t mpt_wide_scan_bytes(int ni, size_t *bytes);
 MPT_KERNEL_API hipError_t mpt_wide_build(const MptVec4 *fnode, int n, MptVec4 *wnode, MptVec4 *qnode, int *bin_of, int *ncount,
-                                     int *offset, void *scan_tmp, size_t scan_bytes, double *d_area, int *nwide, int *depth,
+                                     void *scan_tmp, size_t scan_bytes, double *d_area, int *nwide, int *depth,
                                      double area[2], hipStream_t stream, volatile int *mail_host, int *mail_dev);
 MPT_KERNEL_API hipError_t mpt_lbvh_sort_bytes(int n, size_t *bytes);
 MPT_KERNEL_API hipError_t mpt_lbvh_build(const MptLbvhBuffers *b, hipStream_t stream);
@@ -97,6 +97,179 @@ MPT_INTERNAL int fail(const char *fmt, ...);
         hipError_t e_ = (expr);                                                           \
         if (e_ != hipSuccess) return fail("%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+
+// ------------------------------------------------------------------ owned memory
+// A device allocation and its capacity in elements.  reserve() grows only and does not synchronise: the caller orders the free
+// behind whatever still uses the old buffer.  A failed allocation leaves {nullptr, 0}, so the next call tries again instead of
+// trusting a stale capacity.  Converts to T*, so launches and parameter structs take it as they took the raw pointer.
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    operator T *() const { return p; }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(cap, o.cap); }
+    int reserve(size_t n, bool *replaced = nullptr) {
+        if (n <= cap) return 0;
+        release();
+        const hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
+        if (e != hipSuccess) { p = nullptr; return fail("hipMalloc(%zu bytes) failed: %s", n * sizeof(T), hipGetErrorString(e)); }
+        cap = n;
+        if (replaced) *replaced = true;
+        return 0;
+    }
+};
+
+// The same for page-locked host memory (flags: hipHostMallocDefault, or hipHostMallocMapped for what a kernel writes)
+template <class T>
+struct PinnedBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { release(); }
+    operator T *() const { return p; }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+    int reserve(size_t n, unsigned flags) {
+        if (n <= cap) return 0;
+        release();
+        const hipError_t e = hipHostMalloc((void **)&p, n * sizeof(T), flags);
+        if (e != hipSuccess) { p = nullptr; return fail("hipHostMalloc(%zu bytes) failed: %s", n * sizeof(T), hipGetErrorString(e)); }
+        cap = n;
+        return 0;
+    }
+};
+
+// Buffers that are sized together share one capacity and one reserve(): everything is freed, then allocated in the order
+// written; `cap` is set only when all of it is there.
+struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set so far
+    DevBuf<MptVec4> film[3];
+    DevBuf<MptVec4> resolved;            // nx*ny float4 (get_image staging on device)
+    DevBuf<float> exported;              // nx*ny*3
+    // mpt_get_denoised's working buffers, nx*ny float4 each: the filtered colour e (rgb, valid flag) in two copies the
+    // iterations alternate between (the one left over takes the image), and the guides a (albedo) and n (normal)
+    DevBuf<MptVec4> dn_e[2], dn_a, dn_n;
+    size_t cap = 0;
+    int reserve(size_t npix, hipStream_t stream) {     // the passes come back zeroed on `stream`
+        if (npix <= cap) return 0;
+        cap = 0;
+        for (auto &b : film) b.release();
+        resolved.release(); exported.release();
+        for (DevBuf<MptVec4> *b : { &dn_e[0], &dn_e[1], &dn_a, &dn_n }) b->release();
+        for (auto &b : film) {
+            if (b.reserve(npix)) return 1;
+            HIP_TRY(hipMemsetAsync(b, 0, npix * sizeof(MptVec4), stream));
+        }
+        if (resolved.reserve(npix) || exported.reserve(npix * 3)) return 1;
+        for (DevBuf<MptVec4> *b : { &dn_e[0], &dn_e[1], &dn_a, &dn_n })
+            if (b->reserve(npix)) return 1;
+        cap = npix;
+        return 0;
+    }
+};
+
+struct MPT_INTERNAL MptModelBufs {         // the device copy of the model
+    DevBuf<float> d_verts; DevBuf<int> d_mtlids;
+    size_t cap = 0;
+    int reserve(size_t n, bool *replaced) {
+        if (n <= cap) return 0;
+        cap = 0;
+        d_verts.release(); d_mtlids.release();
+        if (d_verts.reserve(n * 24) || d_mtlids.reserve(n)) return 1;
+        cap = n; *replaced = true;
+        return 0;
+    }
+};
+
+struct MPT_INTERNAL MptLbvhBufs {          // workspace and result of the device LBVH build (lbvh_build.hip)
+    DevBuf<float> d_cen; DevBuf<int> d_bounds, d_depth;
+    DevBuf<unsigned long long> d_keys_in, d_keys_out;
+    DevBuf<char> d_sort_tmp; size_t d_sort_bytes = 0;
+    DevBuf<int> d_child, d_parent, d_leaf, d_mc;
+    DevBuf<float> d_bmin, d_bmax;
+    DevBuf<unsigned> d_arrive;
+    size_t cap = 0;
+    int reserve(size_t m) {
+        if (m <= cap) return 0;
+        cap = 0;
+        d_cen.release(); d_bounds.release(); d_depth.release(); d_keys_in.release(); d_keys_out.release();
+        d_sort_tmp.release(); d_child.release(); d_parent.release(); d_leaf.release(); d_mc.release();
+        d_bmin.release(); d_bmax.release(); d_arrive.release();
+        HIP_TRY(mpt_lbvh_sort_bytes((int)m, &d_sort_bytes));
+        if (d_cen.reserve(m * 3) || d_bounds.reserve(6) || d_depth.reserve(1) || d_keys_in.reserve(m) || d_keys_out.reserve(m) ||
+            d_sort_tmp.reserve(std::max<size_t>(d_sort_bytes, 16)) || d_child.reserve(m * 2) || d_parent.reserve(m * 2) ||
+            d_leaf.reserve(m) || d_mc.reserve(m) || d_bmin.reserve(m * 3) || d_bmax.reserve(m * 3) || d_arrive.reserve(m)) return 1;
+        cap = m;
+        return 0;
+    }
+};
+
+struct MPT_INTERNAL MptNodeBufs {          // per internal node: the reference tree's records and the fast build's
+    DevBuf<MptVec4> snode, fnode;
+    size_t cap = 0;
+    int reserve(size_t ni) {
+        if (ni <= cap) return 0;
+        cap = 0;
+        snode.release(); fnode.release();
+        if (snode.reserve(ni * 2) || fnode.reserve(ni * 4)) return 1;
+        cap = ni;
+        return 0;
+    }
+};
+
+struct MPT_INTERNAL MptTriBufs {           // per leaf slot: the reference-order triangle records
+    DevBuf<MptVec4> tgeo, tshade;
+    size_t cap = 0;
+    int reserve(size_t n) {
+        if (n <= cap) return 0;
+        cap = 0;
+        tgeo.release(); tshade.release();
+        if (tgeo.reserve(n * 4) || tshade.reserve(n * 4)) return 1;
+        cap = n;
+        return 0;
+    }
+};
+
+struct MPT_INTERNAL MptWideBufs {          // workspace of the device 4-wide collapse (wide_build.hip), per internal node
+    DevBuf<int> bin_of, ncount;          // (the nodes' offsets within their workgroup live in ncount, the workgroups' in scan)
+    DevBuf<char> scan; size_t scan_bytes = 0;
+    DevBuf<double> area;
+    size_t cap = 0;
+    int reserve(size_t ni) {
+        if (ni <= cap) return 0;
+        cap = 0;
+        bin_of.release(); ncount.release(); scan.release(); area.release();
+        HIP_TRY(mpt_wide_scan_bytes((int)ni, &scan_bytes));
+        if (bin_of.reserve(ni + 4) || ncount.reserve(ni) || scan.reserve(std::max<size_t>(scan_bytes, 16)) || area.reserve(2)) return 1;
+        cap = ni;
+        return 0;
+    }
+};
+
+struct MPT_INTERNAL MptMltSlab {           // the Metropolis engine's splat records and the scratch of their sort
+    DevBuf<uint32_t> keys, keys2;
+    DevBuf<MptVec4> vals, vals2;
+    DevBuf<char> tmp;                    // sort scratch: tmp.cap bytes
+    DevBuf<uint32_t> runs;
+    size_t cap = 0, runs_cap = 0;        // records the slab holds; film elements of the run table
+    int reserve(size_t recs, size_t npix) {            // neither capacity shrinks when the other grows
+        if (recs <= cap && npix <= runs_cap) return 0;
+        const size_t ncap = std::max(recs, cap), nrcap = std::max(npix, runs_cap);
+        size_t bytes = 0;
+        HIP_TRY(mpt_mlt_sort_bytes((int)ncap, (int)nrcap, &bytes));
+        cap = runs_cap = 0;
+        keys.release(); keys2.release(); vals.release(); vals2.release(); tmp.release(); runs.release();
+        if (keys.reserve(ncap) || keys2.reserve(ncap) || vals.reserve(ncap) || vals2.reserve(ncap) ||
+            tmp.reserve(std::max(bytes, (size_t)16)) || runs.reserve(nrcap * 2)) return 1;
+        cap = ncap; runs_cap = nrcap;
+        return 0;
+    }
+};
 
 // ------------------------------------------------------------------ launch timers
 // The events recorded around the kernels of an engine's launches (per launch: `per_launch` events bounding per_launch - 1
@@ -157,13 +330,7 @@ struct mpt_ctx {
     // film
     int nx = 0, ny = 0, x0 = 0, x1 = 0;
     int stripe_w = 0, stripe_idx = 0, stripe_mod = 1;   // stripe_w > 0: columns dealt out in stripes (mpt_set_stripes)
-    MptVec4 *film[3] = { nullptr, nullptr, nullptr };
-    size_t film_cap = 0;                 // pixels allocated per pass
-    MptVec4 *resolved = nullptr;         // nx*ny float4 (get_image staging on device)
-    float *exported = nullptr;           // nx*ny*3
-    // mpt_get_denoised's working buffers, nx*ny float4 each, allocated with the film: the filtered colour e (rgb, valid flag) in
-    // two copies the iterations alternate between (the one left over takes the image), and the guides a (albedo) and n (normal)
-    MptVec4 *dn_e[2] = { nullptr, nullptr }, *dn_a = nullptr, *dn_n = nullptr;
+    MptFilmBufs fb;                      // the passes, the image staging and the denoiser's buffers; fb.cap: pixels allocated per pass
     int denoise_lds = 1;                 // option "denoise_lds": the strides 1 and 2 filter from a tile in LDS (same bits as the gathers)
 
     // model (host copy kept for the tree build)
@@ -180,27 +347,22 @@ struct mpt_ctx {
                                          // SAH pass takes ~0.2 s at 1 M faces; it was 1.5 s on one core, hence 2^18 in round 1)
     bool host_tree_valid = false;        // h_child/h_leaf/... mirror the device tree (lazily downloaded)
     // device-side build workspace
-    float *d_verts = nullptr; int *d_mtlids = nullptr; size_t d_model_cap = 0;
-    float *d_cen = nullptr; int *d_bounds = nullptr; int *d_depth = nullptr;
-    unsigned long long *d_keys_in = nullptr, *d_keys_out = nullptr;
-    void *d_sort_tmp = nullptr; size_t d_sort_bytes = 0;
-    int *d_child = nullptr, *d_parent = nullptr, *d_leaf = nullptr, *d_mc = nullptr;
-    float *d_bmin = nullptr, *d_bmax = nullptr;
-    unsigned *d_arrive = nullptr;
-    size_t d_build_cap = 0;
+    MptModelBufs dmodel;
+    MptLbvhBufs lbvh;
     std::vector<int32_t> h_child, h_leaf, h_mc;
     std::vector<float> h_bmin, h_bmax;
-    MptVec4 *snode = nullptr, *fnode = nullptr, *tgeo = nullptr, *tshade = nullptr;
-    MptVec4 *tfast = nullptr; size_t tfast_cap = 0;   // production triangle records, 3 float4 each (derived from tgeo)
-    MptVec4 *qnode = nullptr; size_t qnode_cap = 0;   // the same nodes, child boxes quantised to 8 bits, 4 float4 each
+    MptNodeBufs nodes;
+    MptTriBufs tris;
+    DevBuf<MptVec4> tfast;                            // production triangle records, 3 float4 each (derived from tgeo)
+    DevBuf<MptVec4> qnode;                            // the same nodes, child boxes quantised to 8 bits, 4 float4 each
     int use_quant = 1;
-    MptVec4 *wnode = nullptr; size_t wnode_cap = 0;   // 4-wide nodes of the fast tree (gather kernel), 8 float4 each
+    DevBuf<MptVec4> wnode;                            // 4-wide nodes of the fast tree (gather kernel), 8 float4 each
     int wide_nodes = 0, wide_depth = 0;               // 0 nodes: not built (too deep)
     int wide_stack = 0;                               // stack levels a traversal of the 4-wide tree can ask for (exact from the host pass, 3 x depth + 2 from the device pass)
     float wide_ratio = 1.f;                           // expected fetches per ray, wide / binary (surface-area sums)
     int sah_exact_max = 8192;                         // host SAH pass: ranges up to this size are swept exactly (diagnostics)
     int sah_inject_fail = 0;                          // test door: treat the device SAH pass as failed after it ran
-    int *h_sahmeta = nullptr, *d_sahmeta = nullptr;   // host-pinned, device-mapped [32]: the SAH pass's per-level hand-back (sah_build.hip plan kernel)
+    PinnedBuf<int> h_sahmeta; int *d_sahmeta = nullptr;   // host-pinned, device-mapped [32]: the SAH pass's per-level hand-back (sah_build.hip plan kernel)
     MptSahStats sah_stats{};                          // what the last device SAH pass did
     bool d_model_stale = true;                        // the device copy of the model (d_verts, d_mtlids) is behind the host's: the next device build uploads
     int lane_hist = 0;                                // diagnostics: counting kernels fill the lane histogram (mpt_get_lane_hist)
@@ -210,28 +372,26 @@ struct mpt_ctx {
     int sah_build = -1;                               // SAH re-partition: 1 on the device (sah_build.hip), 0 host pass, -1 auto
                                                       // (device above 8192 faces; below, all of the host pass's splits are exact
                                                       // sweeps and it costs a millisecond)
-    void *sah_ws = nullptr; size_t sah_ws_bytes = 0;  // one allocation, carved up in build_sah_device
+    DevBuf<char> sah_ws;                              // one allocation (sah_ws.cap bytes), carved up in build_sah_device
     int wide_build = 1;                               // 1: the 4-wide collapse runs on the device (wide_build.hip), 0: host pass
-    int *wb_bin_of = nullptr, *wb_ncount = nullptr, *wb_offset = nullptr; void *wb_scan = nullptr; size_t wb_scan_bytes = 0;
-    double *wb_area = nullptr; size_t wb_cap = 0;
+    MptWideBufs wb;
     int use_wide = 1;                                 // option "wide": 1 walk the 4-wide nodes when the scene does not fit LDS
                                                       // (default), 0 the binary tree
     // overflow strips of the wide kernel's per-lane stacks: one per ring slot, because launches of different slots
     // are resident together and index their strips by block and lane only
-    int *stack_spill2[MPT_MAX_PIPE] = {}; size_t stack_spill2_cap[MPT_MAX_PIPE] = {};
-    size_t node_cap = 0, tri_cap = 0;
+    DevBuf<int> stack_spill2[MPT_MAX_PIPE];
 
     // materials / images / lights / world / camera
-    MptMaterial *mats = nullptr;
+    DevBuf<MptMaterial> mats;
     std::vector<unsigned char> mat_feat; // shade_feat_material of every record mpt_load_materials last loaded
     int default_feat = 0;                // ... and of the default material (mpt_create)
     int nmats = 0;                       // material records mpt_load_materials last loaded (mpt_unit_eval refuses ids beyond them)
     int max_mat_tex = -1;                // largest texture id a loaded material names (-1: none): mpt_unit_eval checks it against the loaded images
-    MptImage *images = nullptr;
+    DevBuf<MptImage> images;
     std::vector<MptImage> h_images;
-    MptVec4 *texels = nullptr;
+    DevBuf<MptVec4> texels;
     size_t texels_used = 0;
-    MptLight *lights = nullptr;
+    DevBuf<MptLight> lights;
     std::vector<MptLight> h_lights;
     float world_fac[4] = { 0.1f, 0.1f, 0.1f, 0.1f };   // light/world.py:14-16
     int world_tex = -1;                                 // documented deviation Q6 (reference default 0)
@@ -240,21 +400,17 @@ struct mpt_ctx {
     // sobol
     int sdim = 0, srows = 0;
     int32_t stime = 0;
-    int *sV = nullptr, *sX = nullptr;
-    int *sX_spec = nullptr;              // the state the batch whose points were computed ahead of time will leave behind (swapped with sX when it is launched)
-    float *sP = nullptr;                 // [MPT_MAX_BATCH][sdim]
+    DevBuf<int> sV, sX;
+    DevBuf<int> sX_spec;                 // the state the batch whose points were computed ahead of time will leave behind (swapped with sX when it is launched)
+    DevBuf<float> sP;                    // [MPT_MAX_BATCH][sdim]
 
     // Metropolis engine (mlt_kernel.hip, mpt_mlt_*): chain state, splat slab and the iterations enqueued but not launched
     int mlt_n = 0, mlt_iter = 0, mlt_pending = 0;
     uint32_t mlt_seed = 0;
     float mlt_lsp = 0.25f, mlt_sigma = 0.01f;
-    float *mlt_X = nullptr, *mlt_L = nullptr;            // [2][n][32], [n][3]
-    int32_t *mlt_bit = nullptr;                          // [n]
-    size_t mlt_cap = 0, mlt_tmp_bytes = 0, mlt_runs_cap = 0;   // records the slab holds; sort scratch; film elements of the run table
-    uint32_t *mlt_keys = nullptr, *mlt_keys2 = nullptr;
-    MptVec4 *mlt_vals = nullptr, *mlt_vals2 = nullptr;
-    void *mlt_tmp = nullptr;
-    uint32_t *mlt_runs = nullptr;
+    DevBuf<float> mlt_X, mlt_L;                          // [2][n][32], [n][3]
+    DevBuf<int32_t> mlt_bit;                             // [n]
+    MptMltSlab slab;
     MptLaunchTimer mlt_timer{3};                         // {chain start, chain end = splat start, splat end} per launch
     MptLaunchTimer denoise_timer{2};                     // mpt_get_denoised: {before the prologue, after the epilogue} per call
     MptLaunchTimer brute_timer{2};                       // brute-force engine: {kernel start, kernel end} per launch
@@ -269,7 +425,7 @@ struct mpt_ctx {
     hipEvent_t ev_free[MPT_MAX_PIPE] = {};            // combine has consumed partial[k]
     hipStream_t probe_stream = nullptr;               // mpt_probe_kernel
     hipStream_t stress_stream = nullptr;              // mpt_stress_copies: a stream of device-to-device copies beside the render
-    char *stress_buf = nullptr;                       // 2 x stress_bytes
+    DevBuf<char> stress_buf;                          // 2 x stress_bytes
     size_t stress_bytes = 0;
     hipStream_t aux = nullptr;                        // Sobol advances + queue resets of the pipelined batches
     hipEvent_t ev_sobol2[MPT_MAX_PIPE] = {};          // Sobol points + zeroed queue heads of the batch on rstream[k] ready
@@ -301,29 +457,28 @@ struct mpt_ctx {
     bool spec_valid = false;
     int spec_slot = -1, spec_B = 0;
     int32_t spec_time = 0;
-    MptVec4 *partial2[MPT_MAX_PIPE] = {};
-    size_t partial2_cap[MPT_MAX_PIPE] = {};           // float4 elements per buffer
-    float *sP2[MPT_MAX_PIPE] = {};
-    unsigned int *d_work2[MPT_MAX_PIPE] = {};
+    DevBuf<MptVec4> partial2[MPT_MAX_PIPE];
+    DevBuf<float> sP2[MPT_MAX_PIPE];
+    DevBuf<unsigned int> d_work2[MPT_MAX_PIPE];
 
     // measurement
     int timeline = 0;                    // 1: the LDS kernel records per-wave timestamps of its last launch
-    unsigned long long *d_timeline = nullptr;
+    DevBuf<unsigned long long> d_timeline;
     int timeline_waves = 0;
-    unsigned long long *d_counters = nullptr;
-    unsigned int *d_work = nullptr;
-    unsigned int *h_watchdog = nullptr, *d_watchdog = nullptr;   // host-pinned, device-mapped: raised by a render kernel's watchdog
-    void *h_stage = nullptr; size_t h_stage_bytes = 0;           // page-locked staging for read-backs into pageable buffers
+    DevBuf<unsigned long long> d_counters;
+    DevBuf<unsigned int> d_work;
+    PinnedBuf<unsigned int> h_watchdog; unsigned int *d_watchdog = nullptr;   // host-pinned, device-mapped: raised by a render kernel's watchdog
+    PinnedBuf<char> h_stage;                                     // page-locked staging (h_stage.cap bytes) for read-backs into pageable buffers
     MptLaunchTimer render_timer{2};      // PathEngine launches: {kernel start, kernel end}
     std::vector<hipEvent_t> event_pool;
 
     // comm
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
-    double *d_scratch = nullptr;
+    DevBuf<double> d_scratch;
     // film gather of a striped split (comm.cpp): the share packed into one message per peer
-    MptVec4 *gather_buf = nullptr; size_t gather_cap = 0;   // sender: its packed share; root: every peer's, back to back
-    MptPiece *d_pieces = nullptr; size_t pieces_cap = 0;     // the plan's piece table on the device
+    DevBuf<MptVec4> gather_buf;                              // sender: its packed share; root: every peer's, back to back
+    DevBuf<MptPiece> d_pieces;                               // the plan's piece table on the device
     int plan_key[6] = { -1, -1, -1, -1, -1, -1 };            // (nx, ny, stripe_w, R, rank, root) the table was made for
     int plan_npieces = 0; long long plan_max_count = 0;
 };
@@ -333,12 +488,6 @@ MPT_INTERNAL int use_ro(mpt_ctx *c);   // calls that only read results
 MPT_INTERNAL int use(mpt_ctx *c);      // calls that may change what the next render launch reads
 MPT_INTERNAL int check_pass(mpt_ctx *c, int pass);
 MPT_INTERNAL int check_watchdog(mpt_ctx *c);   // after a synchronise: did a persistent kernel give up?
-
-template <class T>
-static int dev_alloc(T **p, size_t count) {
-    HIP_TRY(hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T)));
-    return 0;
-}
 
 // comm.cpp
 MPT_INTERNAL void mpt_comm_release(mpt_ctx *c);   // mpt_destroy: drop the communicator, if any

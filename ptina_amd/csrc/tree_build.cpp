@@ -211,6 +211,59 @@ struct SahBuild {
     }
 };
 
+static inline float asf(int32_t v) { float f; memcpy(&f, &v, 4); return f; }
+static inline int32_t asi(float f) { int32_t v; memcpy(&v, &f, 4); return v; }
+
+// the box of the triangle in a leaf slot, from the model's vertices (lbvh.py:155-158)
+static void leaf_box(const mpt_ctx *c, int slot, float *lo, float *hi) {
+    const float *p0 = c->verts.data() + (size_t)c->h_leaf[slot] * 24, *p1 = p0 + 8, *p2 = p0 + 16;
+    for (int a = 0; a < 3; a++) {
+        lo[a] = fminf(fminf(p0[a], p1[a]), p2[a]);
+        hi[a] = fmaxf(fmaxf(p0[a], p1[a]), p2[a]);
+    }
+}
+
+// SAH re-partition of the leaves in the order of c->h_leaf (exact sweep up to sah_exact_max leaves)
+static void run_sah(const mpt_ctx *c, SahBuild &sb) {
+    const int n = c->nfaces;
+    sb.n = n;
+    sb.exact_max = c->sah_exact_max;
+    sb.lo.resize((size_t)n * 3); sb.hi.resize((size_t)n * 3); sb.ctr.resize((size_t)n * 3);
+    for (int slot = 0; slot < n; slot++) {
+        float l[3], h[3];
+        leaf_box(c, slot, l, h);
+        for (int a = 0; a < 3; a++) {
+            sb.lo[(size_t)slot * 3 + a] = l[a]; sb.hi[(size_t)slot * 3 + a] = h[a];
+            sb.ctr[(size_t)slot * 3 + a] = 0.5f * (l[a] + h[a]);
+        }
+    }
+    sb.run();
+}
+
+// fnode records for the fast build from a (child, box) description over leaf slots: child ids >= 0 internal, ~slot leaf; a node
+// record holds its two children's boxes
+static void pack_fnode(const mpt_ctx *c, int n, const std::vector<int32_t> &fchild, const std::vector<float> &flo,
+                       const std::vector<float> &fhi, std::vector<MptVec4> &fnode) {
+    const int ni = n > 1 ? n - 1 : 0;
+    fnode.assign((size_t)std::max(ni, 1) * 4, MptVec4{ 0, 0, 0, 0 });
+    for (int i = 0; i < ni; i++) {
+        float l[2][3], h[2][3];
+        int id[2];
+        for (int k = 0; k < 2; k++) {
+            id[k] = fchild[(size_t)i * 2 + k];
+            if (id[k] < 0) leaf_box(c, ~id[k], l[k], h[k]);
+            else for (int a = 0; a < 3; a++) { l[k][a] = flo[(size_t)id[k] * 3 + a]; h[k][a] = fhi[(size_t)id[k] * 3 + a]; }
+        }
+        for (int a = 0; a < 3; a++) fnode[(size_t)i * 4 + a] = { l[0][a], l[1][a], h[0][a], h[1][a] };
+        fnode[(size_t)i * 4 + 3] = { asf(id[0]), asf(id[1]), 0.f, 0.f };
+    }
+}
+
+// Device room for the node and triangle records of a tree over n faces.  The caller has synchronised the stream.
+static int reserve_records(mpt_ctx *c, int n) {
+    return c->nodes.reserve(std::max(n - 1, 1)) || c->tris.reserve(std::max(n, 1));
+}
+
 static int build_tree_host(mpt_ctx *c) {
     const int n = c->nfaces;
     const float *V = c->verts.data();
@@ -271,13 +324,6 @@ static int build_tree_host(mpt_ctx *c) {
     }
 
     // boxes: iterative post-order from the root (also yields the depth the LDS stack must hold)
-    auto leaf_box = [&](int slot, float *lo, float *hi) {                       // lbvh.py:155-158
-        int f = c->h_leaf[slot];
-        for (int a = 0; a < 3; a++) {
-            lo[a] = fminf(fminf(pos(f, 0)[a], pos(f, 1)[a]), pos(f, 2)[a]);
-            hi[a] = fmaxf(fmaxf(pos(f, 0)[a], pos(f, 1)[a]), pos(f, 2)[a]);
-        }
-    };
     int depth = 0;
     if (ni > 0) {
         std::vector<int> order; order.reserve(ni);
@@ -300,7 +346,7 @@ static int build_tree_host(mpt_ctx *c) {
             float lo[2][3], hi[2][3];
             for (int k = 0; k < 2; k++) {
                 int ch = c->h_child[(size_t)i * 2 + k];
-                if (ch < n) leaf_box(ch, lo[k], hi[k]);
+                if (ch < n) leaf_box(c, ch, lo[k], hi[k]);
                 else for (int a = 0; a < 3; a++) { lo[k][a] = c->h_bmin[(size_t)(ch - n) * 3 + a]; hi[k][a] = c->h_bmax[(size_t)(ch - n) * 3 + a]; }
             }
             for (int a = 0; a < 3; a++) {
@@ -313,33 +359,20 @@ static int build_tree_host(mpt_ctx *c) {
     if (depth + 2 > 64) return fail("LBVH depth %d exceeds the 64-entry traversal stack", depth);
 
     // pack device records
-    std::vector<MptVec4> snode((size_t)std::max(ni, 1) * 2), fnode((size_t)std::max(ni, 1) * 4);
+    std::vector<MptVec4> snode((size_t)std::max(ni, 1) * 2), fnode;
     std::vector<MptVec4> tgeo((size_t)std::max(n, 1) * 4), tshade((size_t)std::max(n, 1) * 4);
-    auto asf = [](int32_t v) { float f; memcpy(&f, &v, 4); return f; };
     for (int i = 0; i < ni; i++) {
         const float *lo = &c->h_bmin[(size_t)i * 3], *hi = &c->h_bmax[(size_t)i * 3];
         int c0 = c->h_child[(size_t)i * 2], c1 = c->h_child[(size_t)i * 2 + 1];
         snode[(size_t)i * 2 + 0] = { lo[0], lo[1], lo[2], asf(c0) };
         snode[(size_t)i * 2 + 1] = { hi[0], hi[1], hi[2], asf(c1) };
     }
-    // the tree the fast build walks: child ids >= 0 internal, ~slot leaf; a node record holds its
-    // two children's boxes
+    // the tree the fast build walks
     std::vector<int32_t> fchild((size_t)std::max(ni, 1) * 2, 0);
     std::vector<float> flo((size_t)std::max(ni, 1) * 3, 0.f), fhi((size_t)std::max(ni, 1) * 3, 0.f);
     if (c->tree_kind == 1 && ni > 0) {
         SahBuild sb;
-        sb.n = n;
-        sb.exact_max = c->sah_exact_max;
-        sb.lo.resize((size_t)n * 3); sb.hi.resize((size_t)n * 3); sb.ctr.resize((size_t)n * 3);
-        for (int slot = 0; slot < n; slot++) {
-            float l[3], h[3];
-            leaf_box(slot, l, h);
-            for (int a = 0; a < 3; a++) {
-                sb.lo[(size_t)slot * 3 + a] = l[a]; sb.hi[(size_t)slot * 3 + a] = h[a];
-                sb.ctr[(size_t)slot * 3 + a] = 0.5f * (l[a] + h[a]);
-            }
-        }
-        sb.run();
+        run_sah(c, sb);
         fchild = sb.child; flo = sb.blo; fhi = sb.bhi;
         c->fast_depth = sb.depth;
     } else {
@@ -353,17 +386,7 @@ static int build_tree_host(mpt_ctx *c) {
         c->fast_depth = depth;
     }
     if (c->fast_depth + 2 > 64) return fail("BVH depth %d exceeds the 64-entry traversal stack", c->fast_depth);
-    for (int i = 0; i < ni; i++) {
-        float l[2][3], h[2][3];
-        int id[2];
-        for (int k = 0; k < 2; k++) {
-            id[k] = fchild[(size_t)i * 2 + k];
-            if (id[k] < 0) leaf_box(~id[k], l[k], h[k]);
-            else for (int a = 0; a < 3; a++) { l[k][a] = flo[(size_t)id[k] * 3 + a]; h[k][a] = fhi[(size_t)id[k] * 3 + a]; }
-        }
-        for (int a = 0; a < 3; a++) fnode[(size_t)i * 4 + a] = { l[0][a], l[1][a], h[0][a], h[1][a] };
-        fnode[(size_t)i * 4 + 3] = { asf(id[0]), asf(id[1]), 0.f, 0.f };
-    }
+    pack_fnode(c, n, fchild, flo, fhi, fnode);
     for (int slot = 0; slot < n; slot++) {
         int f = c->h_leaf[slot];
         const float *p0 = pos(f, 0), *p1 = pos(f, 1), *p2 = pos(f, 2);
@@ -372,50 +395,15 @@ static int build_tree_host(mpt_ctx *c) {
         tri_make_tshade(p0, p1, p2, asf(c->mtlids[f]), &tshade[(size_t)slot * 4]);
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if ((size_t)std::max(ni, 1) > c->node_cap) {
-        hipFree(c->snode); hipFree(c->fnode); c->snode = c->fnode = nullptr;
-        if (dev_alloc(&c->snode, snode.size()) || dev_alloc(&c->fnode, fnode.size())) return 1;
-        c->node_cap = std::max(ni, 1);
-    }
-    if ((size_t)std::max(n, 1) > c->tri_cap) {
-        hipFree(c->tgeo); hipFree(c->tshade); c->tgeo = c->tshade = nullptr;
-        if (dev_alloc(&c->tgeo, tgeo.size()) || dev_alloc(&c->tshade, tshade.size())) return 1;
-        c->tri_cap = std::max(n, 1);
-    }
-    HIP_TRY(hipMemcpyAsync(c->snode, snode.data(), snode.size() * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->fnode, fnode.data(), fnode.size() * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->tgeo, tgeo.data(), tgeo.size() * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->tshade, tshade.data(), tshade.size() * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
+    if (reserve_records(c, n)) return 1;
+    HIP_TRY(hipMemcpyAsync(c->nodes.snode, snode.data(), snode.size() * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->nodes.fnode, fnode.data(), fnode.size() * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->tris.tgeo, tgeo.data(), tgeo.size() * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->tris.tshade, tshade.data(), tshade.size() * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->tree_valid = true;
     c->host_tree_valid = true;
     return 0;
-}
-
-// fnode records for the fast build from a (child, box) description over leaf slots
-static void pack_fnode(mpt_ctx *c, int n, const std::vector<int32_t> &fchild, const std::vector<float> &flo,
-                       const std::vector<float> &fhi, std::vector<MptVec4> &fnode) {
-    const int ni = n > 1 ? n - 1 : 0;
-    const float *V = c->verts.data();
-    auto asf = [](int32_t v) { float f; memcpy(&f, &v, 4); return f; };
-    fnode.assign((size_t)std::max(ni, 1) * 4, MptVec4{ 0, 0, 0, 0 });
-    for (int i = 0; i < ni; i++) {
-        float l[2][3], h[2][3];
-        int id[2];
-        for (int k = 0; k < 2; k++) {
-            id[k] = fchild[(size_t)i * 2 + k];
-            if (id[k] < 0) {
-                int f = c->h_leaf[~id[k]];
-                for (int a = 0; a < 3; a++) {
-                    const float *p0 = V + ((size_t)f * 3) * 8, *p1 = p0 + 8, *p2 = p0 + 16;
-                    l[k][a] = fminf(fminf(p0[a], p1[a]), p2[a]);
-                    h[k][a] = fmaxf(fmaxf(p0[a], p1[a]), p2[a]);
-                }
-            } else for (int a = 0; a < 3; a++) { l[k][a] = flo[(size_t)id[k] * 3 + a]; h[k][a] = fhi[(size_t)id[k] * 3 + a]; }
-        }
-        for (int a = 0; a < 3; a++) fnode[(size_t)i * 4 + a] = { l[0][a], l[1][a], h[0][a], h[1][a] };
-        fnode[(size_t)i * 4 + 3] = { asf(id[0]), asf(id[1]), 0.f, 0.f };
-    }
 }
 
 extern "C" int mpt_sah_workspace(int n, int64_t nseg, int64_t out[4]) {
@@ -435,16 +423,14 @@ static int build_sah_device(mpt_ctx *c) {
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t SW = mpt_sah_segbin_words(n);
     const size_t total = 2 * al((size_t)n * 32) + 2 * al(SC * 64) + al(SC * 32) + al(2 * CC * 4) + al(CC * 4) + al(PW * 4) + al(SW * 4) + al(TC * 32) + al(64);
-    if (total > c->sah_ws_bytes) {
+    if (total > c->sah_ws.cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->sah_ws); c->sah_ws = nullptr; c->sah_ws_bytes = 0;
-        HIP_TRY(hipMalloc(&c->sah_ws, total));
-        c->sah_ws_bytes = total;
+        if (c->sah_ws.reserve(total)) return 1;
     }
     char *q = (char *)c->sah_ws;
     auto take = [&](size_t b) { char *r = q; q += al(b); return r; };
     MptSahBuffers B{};
-    B.verts = c->d_verts; B.leaf = c->d_leaf; B.n = n;
+    B.verts = c->dmodel.d_verts; B.leaf = c->lbvh.d_leaf; B.n = n;
     for (int k = 0; k < 2; k++) B.prim[k] = (MptVec4 *)take((size_t)n * 32);
     for (int k = 0; k < 2; k++) B.seg[k] = (int *)take(SC * 64);
     B.seg_cap = SC;
@@ -456,12 +442,12 @@ static int build_sah_device(mpt_ctx *c) {
     B.meta = (int *)take(64);
     B.stats = &c->sah_stats;
     B.mail_host = c->h_sahmeta; B.mail_dev = c->d_sahmeta;
-    B.fnode = c->fnode;
+    B.fnode = c->nodes.fnode;
     int depth = 0;
     hipError_t e = mpt_sah_build(&B, &depth, c->stream);
-    // Neither is fatal: the caller falls back to the host pass, which re-packs c->fnode from the LBVH leaf order (a failed
+    // Neither is fatal: the caller falls back to the host pass, which re-packs c->nodes.fnode from the LBVH leaf order (a failed
     // device pass may have overwritten part of it) and has its own depth handling (round-3 ADVICE)
-    if (c->sah_inject_fail) e = hipErrorInvalidValue;       // test door: the device pass ran (and wrote c->fnode), then "failed"
+    if (c->sah_inject_fail) e = hipErrorInvalidValue;       // test door: the device pass ran (and wrote c->nodes.fnode), then "failed"
     if (e != hipSuccess) { (void)hipGetLastError(); c->sah_fallback = 1; return 2; }
     if (depth + 2 > 64) { c->sah_fallback = 2; return 2; }
     c->fast_depth = depth;
@@ -472,25 +458,13 @@ static int build_sah_device(mpt_ctx *c) {
 static int build_sah_host(mpt_ctx *c) {
     const int n = c->nfaces, ni = n - 1;
     c->h_leaf.resize(n);
-    HIP_TRY(hipMemcpy(c->h_leaf.data(), c->d_leaf, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c->h_leaf.data(), c->lbvh.d_leaf, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     SahBuild sb;
-    sb.n = n;
-    sb.exact_max = c->sah_exact_max;
-    sb.lo.resize((size_t)n * 3); sb.hi.resize((size_t)n * 3); sb.ctr.resize((size_t)n * 3);
-    const float *V = c->verts.data();
-    for (int slot = 0; slot < n; slot++) {
-        int f = c->h_leaf[slot];
-        const float *p0 = V + ((size_t)f * 3) * 8, *p1 = p0 + 8, *p2 = p0 + 16;
-        for (int a = 0; a < 3; a++) {
-            float l = fminf(fminf(p0[a], p1[a]), p2[a]), h = fmaxf(fmaxf(p0[a], p1[a]), p2[a]);
-            sb.lo[(size_t)slot * 3 + a] = l; sb.hi[(size_t)slot * 3 + a] = h; sb.ctr[(size_t)slot * 3 + a] = 0.5f * (l + h);
-        }
-    }
-    sb.run();
+    run_sah(c, sb);
     if (sb.depth + 2 > 64) return fail("BVH depth %d exceeds the 64-entry traversal stack", sb.depth);
     std::vector<MptVec4> fnode;
     pack_fnode(c, n, sb.child, sb.blo, sb.bhi, fnode);
-    HIP_TRY(hipMemcpy(c->fnode, fnode.data(), (size_t)ni * 4 * sizeof(MptVec4), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->nodes.fnode, fnode.data(), (size_t)ni * 4 * sizeof(MptVec4), hipMemcpyHostToDevice));
     c->fast_depth = sb.depth;
     return 0;
 }
@@ -501,57 +475,26 @@ static int build_tree_gpu(mpt_ctx *c, BuildClock &clk) {
     const int n = c->nfaces;
     const int ni = n > 1 ? n - 1 : 0;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if ((size_t)std::max(n, 1) > c->d_model_cap) {
-        hipFree(c->d_verts); hipFree(c->d_mtlids); c->d_verts = nullptr; c->d_mtlids = nullptr;
-        if (dev_alloc(&c->d_verts, (size_t)std::max(n, 1) * 24) || dev_alloc(&c->d_mtlids, (size_t)std::max(n, 1))) return 1;
-        c->d_model_cap = std::max(n, 1);
-        c->d_model_stale = true;
-    }
-    if ((size_t)std::max(n, 1) > c->d_build_cap) {
-        hipFree(c->d_cen); hipFree(c->d_bounds); hipFree(c->d_depth); hipFree(c->d_keys_in); hipFree(c->d_keys_out);
-        hipFree(c->d_sort_tmp); hipFree(c->d_child); hipFree(c->d_parent); hipFree(c->d_leaf); hipFree(c->d_mc);
-        hipFree(c->d_bmin); hipFree(c->d_bmax); hipFree(c->d_arrive);
-        c->d_cen = nullptr; c->d_bounds = nullptr; c->d_depth = nullptr; c->d_keys_in = c->d_keys_out = nullptr;
-        c->d_sort_tmp = nullptr; c->d_child = c->d_parent = c->d_leaf = c->d_mc = nullptr;
-        c->d_bmin = c->d_bmax = nullptr; c->d_arrive = nullptr;
-        size_t m = std::max(n, 1);
-        HIP_TRY(mpt_lbvh_sort_bytes((int)m, &c->d_sort_bytes));
-        if (dev_alloc(&c->d_cen, m * 3) || dev_alloc(&c->d_bounds, 6) || dev_alloc(&c->d_depth, 1) ||
-            dev_alloc(&c->d_keys_in, m) || dev_alloc(&c->d_keys_out, m) ||
-            dev_alloc((char **)&c->d_sort_tmp, std::max<size_t>(c->d_sort_bytes, 16)) ||
-            dev_alloc(&c->d_child, m * 2) || dev_alloc(&c->d_parent, m * 2) || dev_alloc(&c->d_leaf, m) ||
-            dev_alloc(&c->d_mc, m) || dev_alloc(&c->d_bmin, m * 3) || dev_alloc(&c->d_bmax, m * 3) ||
-            dev_alloc(&c->d_arrive, m)) return 1;
-        c->d_build_cap = m;
-    }
-    if ((size_t)std::max(ni, 1) > c->node_cap) {
-        hipFree(c->snode); hipFree(c->fnode); c->snode = c->fnode = nullptr;
-        if (dev_alloc(&c->snode, (size_t)std::max(ni, 1) * 2) || dev_alloc(&c->fnode, (size_t)std::max(ni, 1) * 4)) return 1;
-        c->node_cap = std::max(ni, 1);
-    }
-    if ((size_t)std::max(n, 1) > c->tri_cap) {
-        hipFree(c->tgeo); hipFree(c->tshade); c->tgeo = c->tshade = nullptr;
-        if (dev_alloc(&c->tgeo, (size_t)std::max(n, 1) * 4) || dev_alloc(&c->tshade, (size_t)std::max(n, 1) * 4)) return 1;
-        c->tri_cap = std::max(n, 1);
-    }
+    if (c->dmodel.reserve(std::max(n, 1), &c->d_model_stale)) return 1;      // replaced: the next lines upload the model again
+    if (c->lbvh.reserve(std::max(n, 1)) || reserve_records(c, n)) return 1;
     // the model travels to the device once per ModelPool.load (the reference's load is that copy too, model.py:71-86): a rebuild of
     // the tree -- another option, another tree kind -- finds it there (1.8 of 5.5 ms at a million triangles)
     if (n > 0 && c->d_model_stale) {
-        HIP_TRY(hipMemcpyAsync(c->d_verts, c->verts.data(), (size_t)n * 24 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->d_mtlids, c->mtlids.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->dmodel.d_verts, c->verts.data(), (size_t)n * 24 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->dmodel.d_mtlids, c->mtlids.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     }
     c->d_model_stale = false;
     clk.mark(0);
     MptLbvhBuffers b{};
-    b.verts = c->d_verts; b.mtlids = c->d_mtlids; b.n = n;
-    b.cen = c->d_cen; b.bounds = c->d_bounds; b.keys_in = c->d_keys_in; b.keys_out = c->d_keys_out;
-    b.sort_tmp = c->d_sort_tmp; b.sort_tmp_bytes = c->d_sort_bytes;
-    b.child = c->d_child; b.parent = c->d_parent; b.leaf = c->d_leaf; b.mc = c->d_mc;
-    b.bmin = c->d_bmin; b.bmax = c->d_bmax; b.arrive = c->d_arrive; b.depth = c->d_depth;
-    b.snode = c->snode; b.fnode = c->fnode; b.tgeo = c->tgeo; b.tshade = c->tshade;
+    b.verts = c->dmodel.d_verts; b.mtlids = c->dmodel.d_mtlids; b.n = n;
+    b.cen = c->lbvh.d_cen; b.bounds = c->lbvh.d_bounds; b.keys_in = c->lbvh.d_keys_in; b.keys_out = c->lbvh.d_keys_out;
+    b.sort_tmp = c->lbvh.d_sort_tmp; b.sort_tmp_bytes = c->lbvh.d_sort_bytes;
+    b.child = c->lbvh.d_child; b.parent = c->lbvh.d_parent; b.leaf = c->lbvh.d_leaf; b.mc = c->lbvh.d_mc;
+    b.bmin = c->lbvh.d_bmin; b.bmax = c->lbvh.d_bmax; b.arrive = c->lbvh.d_arrive; b.depth = c->lbvh.d_depth;
+    b.snode = c->nodes.snode; b.fnode = c->nodes.fnode; b.tgeo = c->tris.tgeo; b.tshade = c->tris.tshade;
     HIP_TRY(mpt_lbvh_build(&b, c->stream));
     int depth = 0;
-    if (ni > 0) HIP_TRY(hipMemcpyAsync(&depth, c->d_depth, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (ni > 0) HIP_TRY(hipMemcpyAsync(&depth, c->lbvh.d_depth, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (depth + 2 > 64) return fail("LBVH depth %d exceeds the 64-entry traversal stack", depth);
     clk.mark(1);
@@ -575,7 +518,7 @@ static int build_tree_gpu(mpt_ctx *c, BuildClock &clk) {
     return 0;
 }
 
-// The binary tree the fast build walks (c->fnode: a node record holds its two children's boxes), collapsed into
+// The binary tree the fast build walks (c->nodes.fnode: a node record holds its two children's boxes), collapsed into
 // 4-wide nodes for the gather kernel: starting from a node's two children, the internal child with the largest
 // surface area is replaced by its own two children until four are held (or only leaves are left).  A ray then
 // makes about half as many dependent record fetches, which is what the scenes that do not fit LDS wait for.
@@ -584,7 +527,6 @@ static int build_tree_gpu(mpt_ctx *c, BuildClock &clk) {
 // node with k children leaves up to k - 1 entries behind and goes on with one child; children come after their parents in the
 // array.  ids: the id vector of node w at ids[w * stride]; an unused slot names leaf n
 static int wide_stack_levels(const MptVec4 *ids, size_t stride, size_t nw, int n) {
-    auto asi = [](float f) { int32_t v; memcpy(&v, &f, 4); return v; };
     std::vector<int> need(nw, 0);
     for (size_t w = nw; w-- > 0;) {
         const MptVec4 &idv = ids[w * stride];
@@ -599,15 +541,22 @@ static int wide_stack_levels(const MptVec4 *ids, size_t stride, size_t nw, int n
     return 1 + (nw ? need[0] : 0) + 1;      // the sentinel below, and the level the step's last (unwanted) plain store lands on
 }
 
+// The two limits of the collapse, outside which the gather kernel keeps walking the binary tree.  A step pushes up to three
+// entries: 3 x depth + sentinel must fit the LDS levels plus the spill strip (40 + 88); and the kernel addresses the records
+// with 32-bit byte offsets.
+static int wide_stack_bound(int depth) { return 3 * depth + 2; }
+static bool wide_fits(int depth, size_t nw) { return wide_stack_bound(depth) <= 128 && nw * 8 * sizeof(MptVec4) < ((size_t)1 << 31); }
+
+// device room for nw 4-wide nodes, exact and quantised
+static int reserve_wide(mpt_ctx *c, size_t nw) { return c->wnode.reserve(nw * 8) || c->qnode.reserve(nw * 4); }
+
 static int make_wide_host(mpt_ctx *c) {
     c->wide_nodes = 0; c->wide_depth = 0; c->wide_stack = 0;
     const int n = c->nfaces, ni = n > 1 ? n - 1 : 0;
     if (ni < 1) return 0;
     std::vector<MptVec4> fnode((size_t)ni * 4);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(fnode.data(), c->fnode, fnode.size() * sizeof(MptVec4), hipMemcpyDeviceToHost));
-    auto asi = [](float f) { int32_t v; memcpy(&v, &f, 4); return v; };
-    auto asf = [](int32_t v) { float f; memcpy(&f, &v, 4); return f; };
+    HIP_TRY(hipMemcpy(fnode.data(), c->nodes.fnode, fnode.size() * sizeof(MptVec4), hipMemcpyDeviceToHost));
     struct Child { int32_t id; float lo[3], hi[3]; };
     auto children_of = [&](int b, Child out[2]) {
         const MptVec4 *r = &fnode[(size_t)b * 4];
@@ -716,21 +665,10 @@ static int make_wide_host(mpt_ctx *c) {
             qnode.push_back(rec[6]);
         }
     }
-    // a step pushes up to three entries: 3 x depth + sentinel must fit the LDS levels plus the spill strip
-    if (3 * depth + 2 > 128) return 0;      // too deep (40 LDS levels + 88 spilled): the gather kernel keeps walking the binary tree
     const size_t nw = bin_of.size();
-    if (nw * 8 * sizeof(MptVec4) >= ((size_t)1 << 31)) return 0;   // the kernel addresses the records with 32-bit byte offsets
-    if (nw > c->wnode_cap) {
-        hipFree(c->wnode); c->wnode = nullptr; c->wnode_cap = 0;
-        if (dev_alloc(&c->wnode, nw * 8)) return 1;
-        c->wnode_cap = nw;
-    }
+    if (!wide_fits(depth, nw)) return 0;
+    if (reserve_wide(c, nw)) return 1;
     HIP_TRY(hipMemcpy(c->wnode, wnode.data(), nw * 8 * sizeof(MptVec4), hipMemcpyHostToDevice));
-    if (nw > c->qnode_cap) {
-        hipFree(c->qnode); c->qnode = nullptr; c->qnode_cap = 0;
-        if (dev_alloc(&c->qnode, nw * 4)) return 1;
-        c->qnode_cap = nw;
-    }
     HIP_TRY(hipMemcpy(c->qnode, qnode.data(), nw * 4 * sizeof(MptVec4), hipMemcpyHostToDevice));
     c->wide_nodes = (int)nw; c->wide_depth = depth;
     c->wide_stack = wide_stack_levels(wnode.data() + 6, 8, nw, n);
@@ -744,34 +682,15 @@ static int make_wide_device(mpt_ctx *c) {
     c->wide_nodes = 0; c->wide_depth = 0; c->wide_stack = 0;
     const int n = c->nfaces, ni = n > 1 ? n - 1 : 0;
     if (ni < 1) return 0;
-    if ((size_t)ni * 8 * sizeof(MptVec4) >= ((size_t)1 << 31)) return 0;   // the kernel addresses the records with 32-bit byte offsets
-    if ((size_t)ni > c->wnode_cap) {
-        hipFree(c->wnode); c->wnode = nullptr; c->wnode_cap = 0;
-        if (dev_alloc(&c->wnode, (size_t)ni * 8)) return 1;
-        c->wnode_cap = ni;
-    }
-    if ((size_t)ni > c->qnode_cap) {
-        hipFree(c->qnode); c->qnode = nullptr; c->qnode_cap = 0;
-        if (dev_alloc(&c->qnode, (size_t)ni * 4)) return 1;
-        c->qnode_cap = ni;
-    }
-    if ((size_t)ni > c->wb_cap) {
-        hipFree(c->wb_bin_of); hipFree(c->wb_ncount); hipFree(c->wb_offset); hipFree(c->wb_scan); hipFree(c->wb_area);
-        c->wb_bin_of = c->wb_ncount = c->wb_offset = nullptr; c->wb_scan = nullptr; c->wb_area = nullptr; c->wb_cap = 0;
-        HIP_TRY(mpt_wide_scan_bytes(ni, &c->wb_scan_bytes));
-        // (wb_offset: not used since round 6 -- the nodes' offsets within their workgroup live in wb_ncount, the workgroups' in wb_scan)
-        if (dev_alloc(&c->wb_bin_of, (size_t)ni + 4) || dev_alloc(&c->wb_ncount, (size_t)ni) ||
-            dev_alloc((char **)&c->wb_scan, std::max<size_t>(c->wb_scan_bytes, 16)) || dev_alloc(&c->wb_area, 2)) return 1;
-        c->wb_cap = ni;
-    }
+    if (!wide_fits(0, (size_t)ni)) return 0;                // (at most one wide node per binary node)
+    if (reserve_wide(c, (size_t)ni) || c->wb.reserve((size_t)ni)) return 1;
     int nw = 0, depth = 0;
     double area[2] = { 0.0, 0.0 };
-    HIP_TRY(mpt_wide_build(c->fnode, n, c->wnode, c->qnode, c->wb_bin_of, c->wb_ncount, c->wb_offset, c->wb_scan, c->wb_scan_bytes,
-                           c->wb_area, &nw, &depth, area, c->stream, c->h_sahmeta, c->d_sahmeta));
-    // a step pushes up to three entries: 3 x depth + sentinel must fit the LDS levels plus the spill strip
-    if (3 * depth + 2 > 128) return 0;      // too deep: the gather kernel keeps walking the binary tree
+    HIP_TRY(mpt_wide_build(c->nodes.fnode, n, c->wnode, c->qnode, c->wb.bin_of, c->wb.ncount, c->wb.scan, c->wb.scan_bytes,
+                           c->wb.area, &nw, &depth, area, c->stream, c->h_sahmeta, c->d_sahmeta));
+    if (!wide_fits(depth, (size_t)nw)) return 0;
     c->wide_nodes = nw; c->wide_depth = depth;
-    c->wide_stack = 3 * depth + 2;          // the bound ...
+    c->wide_stack = wide_stack_bound(depth);   // the bound ...
     if (nw > 0 && nw <= 4096) {             // ... and for a tree that may be walked out of LDS the exact count, from its id vectors (64 KiB at most)
         std::vector<MptVec4> ids((size_t)nw);
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -805,13 +724,11 @@ extern "C" int mpt_build_tree(mpt_ctx *c) {
     // the production kernels' 48-byte triangle records, from the reference-order ones
     // (+ 1: record n is all NaNs -- the leaf an unused slot of a 4-wide node names; no ray can hit it)
     const size_t nt = (size_t)std::max(c->nfaces, 1) + 1;
-    if (nt > c->tfast_cap) {
+    if (nt * 3 > c->tfast.cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->tfast); c->tfast = nullptr; c->tfast_cap = 0;
-        if (dev_alloc(&c->tfast, nt * 3)) return 1;
-        c->tfast_cap = nt;
+        if (c->tfast.reserve(nt * 3)) return 1;
     }
-    HIP_TRY(mpt_launch_derive_tfast(c->tgeo, c->tfast, c->nfaces, c->stream));
+    HIP_TRY(mpt_launch_derive_tfast(c->tris.tgeo, c->tfast, c->nfaces, c->stream));
     HIP_TRY(hipMemsetAsync(c->tfast + (size_t)c->nfaces * 3, 0xff, 3 * sizeof(MptVec4), c->stream));   // 0xffffffff: a NaN
     clk.mark(3);
     if (make_wide(c)) return 1;
@@ -826,13 +743,13 @@ static int download_tree(mpt_ctx *c) {
     c->h_bmin.assign((size_t)std::max(ni, 1) * 3, 0.f); c->h_bmax.assign((size_t)std::max(ni, 1) * 3, 0.f);
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (n > 0) {
-        HIP_TRY(hipMemcpy(c->h_leaf.data(), c->d_leaf, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(c->h_mc.data(), c->d_mc, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c->h_leaf.data(), c->lbvh.d_leaf, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c->h_mc.data(), c->lbvh.d_mc, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     }
     if (ni > 0) {
-        HIP_TRY(hipMemcpy(c->h_child.data(), c->d_child, (size_t)ni * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(c->h_bmin.data(), c->d_bmin, (size_t)ni * 3 * sizeof(float), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(c->h_bmax.data(), c->d_bmax, (size_t)ni * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c->h_child.data(), c->lbvh.d_child, (size_t)ni * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c->h_bmin.data(), c->lbvh.d_bmin, (size_t)ni * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c->h_bmax.data(), c->lbvh.d_bmax, (size_t)ni * 3 * sizeof(float), hipMemcpyDeviceToHost));
     }
     c->host_tree_valid = true;
     return 0;

@@ -244,14 +244,13 @@ MPT_KERNEL_API hipError_t mpt_wide_scan_bytes(int ni, size_t *bytes) {      // (
 // Builds the wide records of the binary tree in fnode (ni = n - 1 internal nodes) into wnode [ni][8] / qnode [ni][4]
 // (capacity: one wide node per binary node, the worst case).  Outputs: *nwide, *depth (levels), area sums [0] over the wide
 // nodes' source nodes, [1] over all binary nodes.  `ncount` [ni] holds the nodes' offsets within their workgroup, `scan_tmp`
-// (mpt_wide_scan_bytes) the level table and the workgroups' totals; `offset` is not used any more.  One read-back per eight levels.
+// (mpt_wide_scan_bytes) the level table and the workgroups' totals.  One read-back per eight levels.
 MPT_KERNEL_API hipError_t mpt_wide_build(const MptVec4 *fnode, int n, MptVec4 *wnode, MptVec4 *qnode, int *bin_of, int *ncount,
-                                     int *offset, void *scan_tmp, size_t scan_bytes, double *d_area, int *nwide, int *depth,
+                                     void *scan_tmp, size_t scan_bytes, double *d_area, int *nwide, int *depth,
                                      double area[2], hipStream_t stream, volatile int *mail_host, int *mail_dev) {
     const int ni = n > 1 ? n - 1 : 0;
     *nwide = 0; *depth = 0; area[0] = area[1] = 0.0;
     if (ni < 1) return hipSuccess;
-    (void)offset;
     hipError_t e;
     size_t need = 0;
     mpt_wide_scan_bytes(ni, &need);
