@@ -158,7 +158,7 @@ struct MptRenderParams {
     int32_t lane_hist;
     // render_kernel_lds4 measures distances along a ray in units of 1 / t_scale (a power of two, so every comparison comes out as it
     // would unscaled): no box of the scene is entered farther than 1 / t_scale from any ray origin, which lets the clamp bit of an
-    // FMA stand for max(t, 0) (pt_device.h Stack16W::T_SCALED).  t_unscale = 1 / t_scale
+    // FMA stand for max(t, 0) (pt_device.h LdsWalk4::T_SCALED).  t_unscale = 1 / t_scale
     float t_scale, t_unscale;
     int32_t pad3;
     unsigned long long *timeline;            // diagnostics: per wave {start, scene ready, queue empty, exit} in

@@ -42,11 +42,11 @@ DEV BlockTracer make_block_tracer(const MptRenderParams &p, int *lds) {
     BlockTracer t; t.p = &p; t.lds = lds; return t;
 }
 #else
-typedef Tracer<GlobalScene, Stack> BlockTracer;
+typedef Tracer<GatherWalk> BlockTracer;
 DEV BlockTracer make_block_tracer(const MptRenderParams &p, int *lds) {
     BlockTracer t;
-    t.sc.fnode = p.fnode; t.sc.tgeo = p.tfast;
-    t.st.base = lds; t.st.sp = 0;
+    t.w.fnode = p.fnode; t.w.tgeo = p.tfast;
+    t.st.stack = lds; t.st.sp = 0;
     t.n = p.n;
     return t;
 }

@@ -248,23 +248,41 @@ DEV bool box_strict(V3 lo, V3 hi, V3 ro, V3 rd, float *near_ = nullptr, float *f
     return hit;
 }
 
-// per-lane LIFO in LDS: element [level][thread], so a wave's push/pop touches 64 consecutive
-// dwords (conflict-free); replaces GlobalStack's [thread][level] rows in global memory, stack.py:10-60
-struct Stack {
-    static constexpr int SENTINEL = (int)0x80000000;   // bottom-of-stack marker (never a node or leaf id)
-    static constexpr bool ONE_TEST = false;
-    static constexpr int PLANE_OFF = 0;                // (the binary gather kernel takes min / max of both planes)
-    int *base;                 // &lds[threadIdx.x]
-    int sp;
-    DEV void push(int v) { base[sp * MPT_BLOCK] = v; sp++; }
-    DEV int pop() { sp--; return base[sp * MPT_BLOCK]; }
-    static constexpr bool PEEK = true;                 // the entry a pop would return can be read ahead of the decision
-    static constexpr bool SP_ADDR = false, ODD_IDS = false, T_SCALED = false;
-    static constexpr int SP_STEP = 1;
-    DEV int peek(int at) const { return base[at * MPT_BLOCK]; }
-};
+// ---------------------------------------------------------------- traversal: one walk type per kernel
+// A walk type is everything a kernel's traversal is compiled from: where the node and triangle records live and how they are read
+// (node / node_planes / node4 / node4q, tri), where the lane's LIFO lives and how it is moved (its Lifo: push / pop / peek, or sp_at /
+// st / ld; the one part of a walk that a traversal changes, so the kernels hand it on by value), and ONE block of compile-time
+// traits, which bvh_walk, the steps of render_lane.h and trace_stream / shade_core of render_shade.h read as WALK::NAME.
+// There are five:
+//   GatherWalk          binary nodes gathered from HBM / L2, int32 LIFO in LDS            render_kernel_fast, BlockTracer (path_common.h)
+//   GatherWalk4<false>  4-wide nodes with exact boxes, gathered; LIFO in LDS that spills  render_kernel_wide<., false>
+//   GatherWalk4<true>   4-wide nodes with 8-bit boxes, gathered; the same LIFO            render_kernel_wide<., true>
+//   LdsWalk             binary nodes in LDS, int16 LIFO                                   render_kernel_lds
+//   LdsWalk4            4-wide nodes in LDS, 16-bit LIFO moved by its LDS address         render_kernel_lds4 (the headline kernel)
+// The traits (every type states each once; QUANT and IDS16 are read by the 4-wide NODE step alone and stated by the 4-wide types):
+//   SENTINEL      the bottom-of-stack marker: never a node or leaf id
+//   WIDE          4-wide nodes (stage_node4).  With them the triangle a ray left from is filtered by the LEAF step, not by the NODE step
+//   QUANT         the child boxes are 8-bit offsets from the node's own box (node4q)
+//   PLANE_OFF     != 0: the node record holds its planes so that a ray picks entry and exit planes by its direction signs, PLANE_OFF bytes
+//                 apart (node_planes), and carries the three offsets in LaneState::off*; 0: no per-ray offsets
+//   LDS_RESIDENT  one persistent 1024-lane workgroup per CU with the scene's records in LDS: one depth question in the LEAF step for both
+//                 kinds of ray, 32-bit offsets into the Sobol table and the shading records, no initialisers in SHADE
+//   LDS_MATS      SHADE reads its material record out of LDS.  A name of its own: a gather kernel with the material records in LDS is a
+//                 sensible kernel (built and measured, profiles/r05_ab_experiments.json material_records_in_lds_gather_kernels), and the
+//                 unit-evaluation kernel states it for a scene that is no walk (unit_eval.hip UnitScene)
+//   ODD_IDS       ids are LDS addresses with the lane's next state in their low bits (LdsWalk4)
+//   T_SCALED      ray distances are held multiplied by `ts` while a ray is traversed (LdsWalk4)
+//   SP_ADDR       LaneState::sp is the LDS address of the lane's top entry, not a level (LdsWalk4).  An address has no spilled form: every
+//                 level of such a LIFO is in LDS, and the 4-wide NODE step's pushes never ask whether one spills
+//     (three names for three things a kernel can have one without the other: each was built and measured on its own, and the gather
+//      kernels were tried with ODD_IDS alone, tools/scratch/r05_gather_ids_attempt.patch)
+//   IDS16         ids are 16 bits: a child's entry distance and its id sort as one word.  (A name beside SP_ADDR: LdsWalk's ids are 16
+//                 bits too, on a LIFO moved by level)
+//   PEEK          the entry a pop would return can be read ahead of the decision (every level in LDS)
+//   NODE_REP, LEAF_REP   extra NODE / LEAF steps behind one scheduling decision of trace_stream
+//   SHADE_MIN     lanes SHADE waits for (trace_stream); 0: it never waits
 
-// extra NODE steps behind one scheduling decision of trace_stream (render_kernel.hip), per kind of scene (SCENE::NODE_REP)
+// The tuning knobs of the walk types (A/B builds: tools/ab_build.sh NAME "-DMPT_LDS4_REP=2"; the spill-test build: Makefile spilltest)
 #ifndef MPT_NODE_REP
 #define MPT_NODE_REP 2        // extra NODE steps per decision (MI355X: 0 / 1 / 2 / 3 -> 4.03 / 3.85 / 3.72 / 3.72 ms with one extra LEAF step)
 #endif
@@ -280,41 +298,74 @@ struct Stack {
 #ifndef MPT_LDS4_REP
 #define MPT_LDS4_REP 1        // ... of the LDS-resident 4-wide kernel
 #endif
+#ifndef MPT_WIDE_SHADE_MIN
+#define MPT_WIDE_SHADE_MIN 0  // lanes SHADE waits for in the 8-bit 4-wide gather kernel; 0: it never waits (render_shade.h trace_stream: they lose 5-14 % with it)
+#endif
+#ifndef MPT_SHADE_MIN_LDS
+#define MPT_SHADE_MIN_LDS 24  // SHADE waits until this many lanes want it, LDS-resident kernels (render_shade.h trace_stream)
+#endif
+#ifndef MPT_X_SPILL_CAP
+#define MPT_X_SPILL_CAP 24    // levels of the 4-wide gather kernels' LIFO that live in LDS (a test build sets it to a handful of levels so that
+                              // every ray uses the global strip)
+#endif
 
-// scene records served from HBM/L2 through the vector L1 (any scene size)
-struct GlobalScene {
-    static constexpr int LEAF_REP = MPT_WIDE_LEAF_REP;
-    static constexpr bool AVOID_IN_LEAF = false;
-    static constexpr int SHADE_MIN = 0;                // (render_kernel.hip trace_stream: lanes SHADE waits for)
-    static constexpr int NODE_REP = MPT_NODE_REP;
-    static constexpr bool WIDE = false, QUANT = false, SIGNED_PLANES = false, LDS_MATS = false;
-    static constexpr bool ODD_IDS = false, T_SCALED = false;
+// a triangle's 48-byte tfast record, from global memory
+DEV void tri_global(const MptVec4 *tgeo, int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) {
+    const MptVec4 *g = tgeo + (size_t)slot * 3;
+    g0 = g[0]; g1 = g[1]; g2 = g[2];
+}
+
+// Binary nodes and triangles served from HBM / L2 through the vector L1 (any scene size).  Its LIFO is per lane in LDS: element
+// [level][thread], so a wave's push/pop touches 64 consecutive dwords (conflict-free); replaces GlobalStack's [thread][level] rows
+// in global memory, stack.py:10-60
+struct GatherWalk {
+    static constexpr int SENTINEL = (int)0x80000000;
+    static constexpr bool WIDE = false;
+    static constexpr int PLANE_OFF = 0;                // (the binary gather kernel takes min / max of both planes)
+    static constexpr bool LDS_RESIDENT = false, LDS_MATS = false;
+    static constexpr bool ODD_IDS = false, T_SCALED = false, SP_ADDR = false;
+    static constexpr bool PEEK = true;
+    static constexpr int NODE_REP = MPT_NODE_REP, LEAF_REP = MPT_WIDE_LEAF_REP, SHADE_MIN = 0;
     const MptVec4 *fnode, *tgeo;
     DEV void node(int i, MptVec4 &a, MptVec4 &b, MptVec4 &c, MptVec4 &d) const {
         const MptVec4 *nd = fnode + (size_t)i * 4;
         a = nd[0]; b = nd[1]; c = nd[2]; d = nd[3];
     }
-    DEV void tri(int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) const {       // tfast: 48-byte records
-        const MptVec4 *g = tgeo + (size_t)slot * 3;
-        g0 = g[0]; g1 = g[1]; g2 = g[2];
-    }
+    DEV void tri(int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) const { tri_global(tgeo, slot, g0, g1, g2); }
+    struct Lifo {
+        int *stack;            // &lds[threadIdx.x]
+        int sp;
+        DEV void push(int v) { stack[sp * MPT_BLOCK] = v; sp++; }
+        DEV int pop() { sp--; return stack[sp * MPT_BLOCK]; }
+        DEV int peek(int at) const { return stack[at * MPT_BLOCK]; }
+    };
 };
 
-// The triangle a ray left from is filtered by the LEAF step (one compare) instead of by the 4-wide NODE step (four compares and
-// four mask merges): its own leaf is then visited once per ray that starts on a surface -- three gathers -- and it is still
-// cheaper: MI355X C4 1583 -> 1607, C5 804 -> 824 Msamples/s (alternated twice)
 // 4-wide nodes gathered from HBM / L2 / Infinity Cache (scenes that do not fit LDS): a traversal step is one
 // 128-B record and four box tests, and a ray makes half as many DEPENDENT fetches as through the binary tree --
 // those fetches, not their bytes, are what bounds the big scenes (measured: binary16 boxes at half the bytes
 // bought 3-7 %)
-struct WideScene {
-    static constexpr int LEAF_REP = MPT_WIDE_LEAF_REP;
-    static constexpr bool AVOID_IN_LEAF = true;
-    static constexpr int SHADE_MIN = 0;                // (render_kernel.hip trace_stream: lanes SHADE waits for)
-    static constexpr int NODE_REP = MPT_WIDE_REP;
-    static constexpr bool WIDE = true, QUANT = false, SIGNED_PLANES = false, LDS_MATS = false;
-    static constexpr bool ODD_IDS = false, T_SCALED = false;
-    const MptVec4 *wnode, *tgeo;
+// QUANT: the same 4-wide nodes in 64 bytes: the child boxes as 8-bit offsets from the node's own box (rounded outwards by
+// the builder), so a step is FOUR 16-B gathers instead of seven.  Measured on MI355X with duplicated gathers: every
+// extra gather instruction per step costs these kernels 7-9 % whatever its width (4 B or 16 B) -- what they wait
+// for is the number of divergent gathers, not bytes -- and the 36 extra VALU instructions of the decode are free
+// at 34-43 % issue utilisation.
+// The LIFO: a step may push three entries, so the worst case is 3 x depth; the first CAP levels live in LDS like GatherWalk's, the
+// (rare) rest in a per-lane strip of global memory
+template <bool QUANT_>
+struct GatherWalk4 {
+    static constexpr int SENTINEL = (int)0x80000000;
+    // The triangle a ray left from is filtered by the LEAF step (one compare) instead of by the 4-wide NODE step (four compares and
+    // four mask merges): its own leaf is then visited once per ray that starts on a surface -- three gathers -- and it is still
+    // cheaper: MI355X C4 1583 -> 1607, C5 804 -> 824 Msamples/s (alternated twice)
+    static constexpr bool WIDE = true, QUANT = QUANT_;
+    static constexpr int PLANE_OFF = 0;                // (the 4-wide steps pick the entry planes by the sign of L.inv themselves: no per-ray offsets to carry)
+    static constexpr bool LDS_RESIDENT = false, LDS_MATS = false;
+    static constexpr bool ODD_IDS = false, T_SCALED = false, SP_ADDR = false, IDS16 = false;
+    static constexpr bool PEEK = false;                // (the top entry may sit in the global strip)
+    static constexpr int NODE_REP = MPT_WIDE_REP, LEAF_REP = MPT_WIDE_LEAF_REP, SHADE_MIN = QUANT ? MPT_WIDE_SHADE_MIN : 0;
+    static constexpr int CAP = MPT_X_SPILL_CAP, SPILL = 128 - CAP;    // 24 levels x 256 lanes x 4 B = 24 KiB of LDS: the five workgroups per CU the registers allow (and a sixth)
+    const MptVec4 *wnode, *tgeo;   // wnode: the 128-B records, or the 64-B ones (QUANT)
     // entry (n*) and exit (f*) planes of the four children, picked by the ray's direction signs: o* is 0 for a ray
     // going up the axis and 16 (bytes: the next float4) for one going down -- still seven dwordx4 gathers
     DEV void node4(int i, int ox, int oy, int oz, MptVec4 &nx, MptVec4 &fx, MptVec4 &ny, MptVec4 &fy, MptVec4 &nz,
@@ -328,74 +379,33 @@ struct WideScene {
         nz = *(const MptVec4 *)(base + 64 + (o + (unsigned)oz)); fz = *(const MptVec4 *)(base + 64 + (o + (unsigned)(oz ^ 16)));
         id = *(const MptVec4 *)(base + 96 + o);
     }
-    DEV void tri(int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) const {       // tfast: 48-byte records
-        const MptVec4 *g = tgeo + (size_t)slot * 3;
-        g0 = g[0]; g1 = g[1]; g2 = g[2];
-    }
-};
-
-// The same 4-wide nodes in 64 bytes: the child boxes as 8-bit offsets from the node's own box (rounded outwards by
-// the builder), so a step is FOUR 16-B gathers instead of seven.  Measured on MI355X with duplicated gathers: every
-// extra gather instruction per step costs these kernels 7-9 % whatever its width (4 B or 16 B) -- what they wait
-// for is the number of divergent gathers, not bytes -- and the 36 extra VALU instructions of the decode are free
-// at 34-43 % issue utilisation.
-struct QuantScene {
-    static constexpr int LEAF_REP = MPT_WIDE_LEAF_REP;
-    static constexpr bool AVOID_IN_LEAF = true;
-#ifndef MPT_WIDE_SHADE_MIN
-#define MPT_WIDE_SHADE_MIN 0
-#endif
-    static constexpr int SHADE_MIN = MPT_WIDE_SHADE_MIN;   // (render_kernel.hip trace_stream: lanes SHADE waits for; 0: it never waits)
-    static constexpr int NODE_REP = MPT_WIDE_REP;      // extra NODE steps per scheduling decision
-    static constexpr bool WIDE = true, QUANT = true, SIGNED_PLANES = false, LDS_MATS = false;
-    static constexpr bool ODD_IDS = false, T_SCALED = false;
-    const MptVec4 *qnode, *tgeo;
     DEV void node4q(int i, MptVec4 &a, MptVec4 &b, MptVec4 &c, MptVec4 &id) const {
-        const char *base = (const char *)qnode;
+        const char *base = (const char *)wnode;
         const unsigned o = (unsigned)i << 6;
         a = *(const MptVec4 *)(base + o); b = *(const MptVec4 *)(base + 16 + o);
         c = *(const MptVec4 *)(base + 32 + o); id = *(const MptVec4 *)(base + 48 + o);
     }
-    DEV void tri(int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) const {       // tfast: 48-byte records
-        const MptVec4 *g = tgeo + (size_t)slot * 3;
-        g0 = g[0]; g1 = g[1]; g2 = g[2];
-    }
-};
-
-// LIFO of the wide traversal: a step may push three entries, so the worst case is 3 x depth; the first CAP
-// levels live in LDS like Stack's, the (rare) rest in a per-lane strip of global memory
-struct SpillStack {
-    static constexpr int SENTINEL = (int)0x80000000;
-    static constexpr bool ONE_TEST = false;
-    static constexpr int PLANE_OFF = 0;                // (the 4-wide steps pick the entry planes by the sign of L.inv themselves: no per-ray offsets to carry)
-#ifndef MPT_X_SPILL_CAP
-#define MPT_X_SPILL_CAP 24     // (a test build sets it to a handful of levels so that every ray uses the global strip)
-#endif
-    static constexpr int CAP = MPT_X_SPILL_CAP, SPILL = 128 - CAP;    // 24 levels x 256 lanes x 4 B = 24 KiB of LDS: the five workgroups per CU the registers allow (and a sixth)
-    static constexpr int STRIDE = MPT_BLOCK;           // entries from one level of a lane's stack to the next
-    typedef int entry_t;
-    static constexpr bool NO_SPILL = false;
-    int *base;                 // &lds[threadIdx.x]
-    int *spill;                // the launch's strips (wave-uniform: stays in scalar registers) ...
-    unsigned lane_off;         // ... and this lane's first entry in them: one register instead of a 64-bit pointer per lane
-    int sp;
-    DEV void push(int v) {
-        if (sp < CAP) base[sp * MPT_BLOCK] = v;
-        else spill[lane_off + (unsigned)(sp - CAP)] = v;
-        sp++;
-    }
-    DEV int pop() {
-        sp--;
-        return sp < CAP ? base[sp * MPT_BLOCK] : spill[lane_off + (unsigned)(sp - CAP)];
-    }
-    static constexpr bool PEEK = false;
-    DEV int peek(int) const { return 0; }
-    static constexpr bool SP_ADDR = false, ODD_IDS = false, T_SCALED = false;
-    static constexpr int SP_STEP = 1;
+    DEV void tri(int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) const { tri_global(tgeo, slot, g0, g1, g2); }
+    struct Lifo {
+        int *stack;            // &lds[threadIdx.x]; entries from one level of a lane's stack to the next: MPT_BLOCK
+        int *spill;            // the launch's strips (wave-uniform: stays in scalar registers) ...
+        unsigned lane_off;     // ... and this lane's first entry in them: one register instead of a 64-bit pointer per lane
+        int sp;
+        DEV void push(int v) {
+            if (sp < CAP) stack[sp * MPT_BLOCK] = v;
+            else spill[lane_off + (unsigned)(sp - CAP)] = v;
+            sp++;
+        }
+        DEV int pop() {
+            sp--;
+            return sp < CAP ? stack[sp * MPT_BLOCK] : spill[lane_off + (unsigned)(sp - CAP)];
+        }
+    };
 };
 
 // scene records resident in the CU's LDS (small scenes): ds_read_b128 instead of divergent
 // global gathers -- one copy per CU, shared by the 16 waves of a 1024-lane workgroup
+#define MPT_LDS_BLOCK 1024
 typedef float mpt_f4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) const mpt_f4 *LdsVec4Ptr;
 typedef __attribute__((address_space(3))) short *LdsShortPtr;
@@ -409,19 +419,29 @@ typedef __attribute__((address_space(3))) const char *LdsBytePtr;
 
 typedef __attribute__((address_space(3))) const unsigned char *LdsU8Ptr;
 
-// The internal-node ids of the LDS copy (in the records and therefore on the stack) are the node's byte offset / 8, so a NODE
-// step forms its record address with one shift instead of a 32-bit integer multiply (quarter rate: four issue slots of the ~50 a
-// step has).  render_kernel_lds scales the ids while it copies the records (stride 72 -> id x 9 <= 32767: scenes that fit LDS do).
-struct LdsScene {
-#ifndef MPT_SHADE_MIN_LDS
-#define MPT_SHADE_MIN_LDS 24
-#endif
-    static constexpr int LEAF_REP = MPT_LEAF_REP;
-    static constexpr bool AVOID_IN_LEAF = false;
-    static constexpr int NODE_REP = MPT_NODE_REP;
-    static constexpr int SHADE_MIN = MPT_SHADE_MIN_LDS; // SHADE waits until this many lanes want it (render_kernel.hip trace_stream)
-    static constexpr bool WIDE = false, QUANT = false, SIGNED_PLANES = true, LDS_MATS = true;
-    static constexpr bool ODD_IDS = false, T_SCALED = false;
+// a triangle's 48-byte tfast record, from LDS
+template <bool ODD_IDS>
+DEV void tri_lds(LdsVec4Ptr tgeo, int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) {
+    // (`tgeo + slot * 3` is compiled into a 64-bit multiply-add, v_mad_u64_u32 -- gfx950 has no 32-bit integer mad -- for a 32-bit LDS
+    //  address; the 24-bit multiply is one instruction, v_mad_u32_u24: -0.25 % per launch.  Slots are below 2^15)
+    // with ODD_IDS `slot` is the leaf's id, 16 * slot + 1: three times that is the record's offset plus three
+    LdsVec4Ptr g = ODD_IDS ? (LdsVec4Ptr)((LdsBytePtr)tgeo - 3 + __umul24((unsigned)slot, 3u))
+                           : (LdsVec4Ptr)((LdsBytePtr)tgeo + __umul24((unsigned)slot, 48u));
+    g0 = lds_ld(g); g1 = lds_ld(g + 1); g2 = lds_ld(g + 2);
+}
+
+// Binary nodes in LDS (render_kernel_lds).  The internal-node ids of the LDS copy (in the records and therefore on the stack) are the
+// node's byte offset / 8, so a NODE step forms its record address with one shift instead of a 32-bit integer multiply (quarter rate:
+// four issue slots of the ~50 a step has).  render_kernel_lds scales the ids while it copies the records (stride 72 -> id x 9 <= 32767:
+// scenes that fit LDS do).  The LIFO: 16-bit entries (node ids fit in int16 there), [level][lane of 1024]
+struct LdsWalk {
+    static constexpr int SENTINEL = -32768;            // leaf ids are ~slot >= -32767 (n < 32768)
+    static constexpr bool WIDE = false;
+    static constexpr int PLANE_OFF = 8;                // bytes between the {lo, lo} and {hi, hi} pairs of an axis in LDS
+    static constexpr bool LDS_RESIDENT = true, LDS_MATS = true;
+    static constexpr bool ODD_IDS = false, T_SCALED = false, SP_ADDR = false;
+    static constexpr bool PEEK = true;
+    static constexpr int NODE_REP = MPT_NODE_REP, LEAF_REP = MPT_LEAF_REP, SHADE_MIN = MPT_SHADE_MIN_LDS;
     LdsVec4Ptr fnode, tgeo;
     // The material records (parameters + derived terms, 96 B each, the default material last) and one byte per
     // leaf slot naming the record: SHADE reads its material out of LDS while the shading record of the triangle is
@@ -443,103 +463,72 @@ struct LdsScene {
         nz = *(LdsVec2Ptr)(az + 32); fz = *(LdsVec2Ptr)(nd + 32 + (oz ^ 8));
         ids = *(LdsVec2Ptr)(nd + 48);
     }
-    DEV void tri(int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) const {
-        // (`tgeo + slot * 3` is compiled into a 64-bit multiply-add, v_mad_u64_u32 -- gfx950 has no 32-bit integer mad -- for a 32-bit LDS
-        //  address; the 24-bit multiply is one instruction, v_mad_u32_u24: -0.25 % per launch.  Slots are below 2^15)
-        LdsVec4Ptr g = (LdsVec4Ptr)((LdsBytePtr)tgeo + __umul24((unsigned)slot, 48u));
-        g0 = lds_ld(g); g1 = lds_ld(g + 1); g2 = lds_ld(g + 2);
-    }
-};
-
-// 16-bit LIFO for the LDS-resident kernel (node ids fit in int16 there), [level][lane of 1024]
-#define MPT_LDS_BLOCK 1024
-struct Stack16 {
-    static constexpr int SENTINEL = -32768;            // leaf ids are ~slot >= -32767 (n < 32768)
-    static constexpr bool ONE_TEST = true;             // one depth question in the LEAF step for both kinds of ray (render_kernel.hip lane_start_ray / stage_leaf)
-    static constexpr int PLANE_OFF = 8;                // bytes between the {lo, lo} and {hi, hi} pairs of an axis in LDS
-    LdsShortPtr base;          // &lds16[threadIdx.x]
-    int sp;
-    DEV void push(int v) { base[sp * MPT_LDS_BLOCK] = (short)v; sp++; }
-    DEV int pop() { sp--; return (int)base[sp * MPT_LDS_BLOCK]; }
-    static constexpr bool PEEK = true;
-    DEV int peek(int at) const { return (int)base[at * MPT_LDS_BLOCK]; }
-    static constexpr bool SP_ADDR = false, ODD_IDS = false, T_SCALED = false;
-    static constexpr int SP_STEP = 1;
+    DEV void tri(int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) const { tri_lds<ODD_IDS>(tgeo, slot, g0, g1, g2); }
+    struct Lifo {
+        LdsShortPtr stack;     // &lds16[threadIdx.x]
+        int sp;
+        DEV void push(int v) { stack[sp * MPT_LDS_BLOCK] = (short)v; sp++; }
+        DEV int peek(int at) const { return (int)stack[at * MPT_LDS_BLOCK]; }
+    };
 };
 
 // The 4-wide nodes with exact boxes resident in LDS (render_kernel_lds4): the first seven float4 of a wnode record -- {lo.x[4]}
 // {hi.x[4]}{lo.y[4]}{hi.y[4]}{lo.z[4]}{hi.z[4]}{id[4]} -- MPT_LDS4_NODE_STRIDE = 112 bytes apart (a ds_read_b128 is served sixteen
-// lanes at a time over sixteen 16-byte bank groups: piece k of record i starts on group (7 i + k) mod 16, sixteen positions), the
-// internal ids as byte offset / 8.  The entry planes of an axis are the 16 bytes at offset 0 for a ray going up the axis and at 16
+// lanes at a time over sixteen 16-byte bank groups: piece k of record i starts on group (7 i + k) mod 16, sixteen positions).
+// The entry planes of an axis are the 16 bytes at offset 0 for a ray going up the axis and at 16
 // for one going down, the exit planes the other 16: no decode, no min / max, no select -- what the 8-bit nodes of the gather
-// kernels pay 39 VALU instructions a step for, to save gathers this kernel does not make
-struct LdsWideScene {
-    static constexpr int LEAF_REP = MPT_LEAF_REP;
-    static constexpr bool AVOID_IN_LEAF = true;        // the triangle a ray left from is filtered by the LEAF step (one compare) instead of by the NODE step (four)
-    static constexpr int NODE_REP = MPT_LDS4_REP;
-    static constexpr int SHADE_MIN = MPT_SHADE_MIN_LDS;
-    static constexpr bool WIDE = true, QUANT = false, SIGNED_PLANES = false, LDS_MATS = true;
-    // ids as the LDS copy of the node records holds them (render_kernel_lds4 rewrites them while it copies): a node's is its record's
-    // byte offset in LDS -- the address itself, no shift -- and a leaf's (slot << 4) | 1; records are 16-byte aligned, so bit 0 tells
-    // them apart with a full-rate v_and where the sign needed a shift or a sign extension (half rate on gfx950)
-    static constexpr bool ODD_IDS = true;
-    static constexpr bool T_SCALED = true;                  // (Stack16W::ts)
-    LdsVec4Ptr wnode, tgeo, mats;
-    LdsU8Ptr mtl;
-    int mat_last, mat_default;
-    DEV void node4(int i, int ox, int oy, int oz, MptVec4 &nx, MptVec4 &fx, MptVec4 &ny, MptVec4 &fy, MptVec4 &nz, MptVec4 &fz,
-                   MptVec4 &id) const {
-        // (ODD_IDS: the id is the record's LDS address -- the records start at the workgroup's LDS address 0, which the kernel checks;
-        //  written as wnode + i the compiler keeps a v_add_u32 of the constant 0 in every step)
-        LdsBytePtr nd = ODD_IDS ? (LdsBytePtr)(unsigned long long)(unsigned)i : (LdsBytePtr)wnode + (i << 3);
-        nx = lds_ld((LdsVec4Ptr)(nd + ox));      fx = lds_ld((LdsVec4Ptr)(nd + (ox ^ 16)));
-        ny = lds_ld((LdsVec4Ptr)(nd + 32 + oy)); fy = lds_ld((LdsVec4Ptr)(nd + 32 + (oy ^ 16)));
-        nz = lds_ld((LdsVec4Ptr)(nd + 64 + oz)); fz = lds_ld((LdsVec4Ptr)(nd + 64 + (oz ^ 16)));
-        id = lds_ld((LdsVec4Ptr)(nd + 96));
-    }
-    DEV void tri(int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) const {
-        // (`tgeo + slot * 3` is compiled into a 64-bit multiply-add, v_mad_u64_u32 -- gfx950 has no 32-bit integer mad -- for a 32-bit LDS
-        //  address; the 24-bit multiply is one instruction, v_mad_u32_u24: -0.25 % per launch.  Slots are below 2^15)
-        // with ODD_IDS `slot` is the leaf's id, 16 * slot + 1: three times that is the record's offset plus three
-        LdsVec4Ptr g = ODD_IDS ? (LdsVec4Ptr)((LdsBytePtr)tgeo - 3 + __umul24((unsigned)slot, 3u))
-                               : (LdsVec4Ptr)((LdsBytePtr)tgeo + __umul24((unsigned)slot, 48u));
-        g0 = lds_ld(g); g1 = lds_ld(g + 1); g2 = lds_ld(g + 2);
-    }
-};
-
-// its LIFO: 16-bit entries, [level][lane of 1024], as many levels as the tree can ask for (3 x depth + 2, the host checks): a
+// kernels pay 39 VALU instructions a step for, to save gathers this kernel does not make.
+// Its LIFO: 16-bit entries, [level][lane of 1024], as many levels as the tree can ask for (3 x depth + 2, the host checks): a
 // step's three pushes are plain stores, nothing spills
-struct Stack16W {
-    static constexpr bool ODD_IDS = true;              // entries are ids as LdsWideScene holds them (16 bits, unsigned)
-    static constexpr bool ONE_TEST = true;             // (render_kernel.hip lane_start_ray / stage_leaf)
+struct LdsWalk4 {
     static constexpr int SENTINEL = 2;                 // the two low bits of an entry are the lane's next state: 0 a node (ST_NODE), 1 a leaf
                                                        // (ST_LEAF), 2 -- only this -- the bottom of the stack (ST_DONE)
+    static constexpr bool WIDE = true, QUANT = false;  // (WIDE: the LEAF step's one compare instead of the NODE step's four)
     static constexpr int PLANE_OFF = 0;                // (the step reads the entry planes off the signs of 1/d: no per-ray offsets to carry)
-    static constexpr int CAP = 1 << 20, STRIDE = MPT_LDS_BLOCK;
-    static constexpr bool NO_SPILL = true;
-    typedef short entry_t;
-    LdsShortPtr base;          // &lds16[threadIdx.x]
-    int sp;
+    static constexpr bool LDS_RESIDENT = true, LDS_MATS = true;
+    // ids as the LDS copy of the node records holds them (render_kernel_lds4 rewrites them while it copies), and as the stack holds
+    // them (16 bits, unsigned): a node's is its record's byte offset in LDS -- the address itself, no shift -- and a leaf's
+    // (slot << 4) | 1; records are 16-byte aligned, so bit 0 tells them apart with a full-rate v_and where the sign needed a shift
+    // or a sign extension (half rate on gfx950)
+    static constexpr bool ODD_IDS = true;
     // T_SCALED: while a ray is traversed its 1/d, o/d and tbest are held multiplied by ts = MptRenderParams::t_scale, a power of two
     // small enough that no box is entered beyond distance 1 / ts: every t of a slab test is the unscaled one times ts bit for bit
     // (so is every comparison between them), and the entry side's max(t, 0) becomes the clamp bit of one of its FMAs -- four
     // half-rate v_max_f32 less per step.  (A t beyond 1 / ts -- a plane nearly parallel to the ray -- clamps to 1: the box test
     // can only pass where it failed, never fail where it passed.)
     static constexpr bool T_SCALED = true;
-    float ts;
-    DEV void push(int v) { base[sp * MPT_LDS_BLOCK] = (short)v; sp++; }        // (by level: the sentinel at a ray's start)
-    DEV int pop() { sp--; return (int)base[sp * MPT_LDS_BLOCK]; }
-    static constexpr bool PEEK = true;                 // (the LEAF step reads the entry it will pop together with its triangle)
-    DEV int peek(int at) const { return (int)base[at * MPT_LDS_BLOCK]; }
     // SP_ADDR: LaneState::sp is the LDS byte ADDRESS of the lane's TOP entry, not a level: the entry a step may pop is read at the
     // register itself, a push goes to the register + SP_STEP -- the instruction's offset field -- and moving it is a full-rate add of
     // SP_STEP, where level * 2048 + base was a v_lshl_add_u32 per access (shifts and three-operand integer forms issue at half the
     // rate of adds on gfx950: tools/microbench/exec_microbench)
     static constexpr bool SP_ADDR = true;
     static constexpr int SP_STEP = MPT_LDS_BLOCK * 2, SP_BIAS = SP_STEP;       // st / ld address the slot at (sp + SP_BIAS - SP_STEP * k)
-    DEV int sp_at(int level) const { return (int)(unsigned)(unsigned long long)(base + level * MPT_LDS_BLOCK); }
-    DEV static void st(int sp, int v) { *(LdsShortPtr)(unsigned long long)(unsigned)sp = (short)v; }
-    DEV static int ld(int sp) { return (int)*(LdsUShortPtr)(unsigned long long)(unsigned)sp; }
+    static constexpr bool IDS16 = true;
+    static constexpr bool PEEK = true;                 // (the LEAF step reads the entry it will pop together with its triangle)
+    static constexpr int NODE_REP = MPT_LDS4_REP, LEAF_REP = MPT_LEAF_REP, SHADE_MIN = MPT_SHADE_MIN_LDS;
+    LdsVec4Ptr tgeo, mats;     // (the node records start at LDS address 0: node4)
+    LdsU8Ptr mtl;
+    int mat_last, mat_default; // (as LdsWalk's; mat_last = lds_nmats: the records the model uses come first)
+    DEV void node4(int i, int ox, int oy, int oz, MptVec4 &nx, MptVec4 &fx, MptVec4 &ny, MptVec4 &fy, MptVec4 &nz, MptVec4 &fz,
+                   MptVec4 &id) const {
+        // (the id is the record's LDS address -- the records start at the workgroup's LDS address 0, which the kernel checks;
+        //  written as wnode + i the compiler keeps a v_add_u32 of the constant 0 in every step)
+        LdsBytePtr nd = (LdsBytePtr)(unsigned long long)(unsigned)i;
+        nx = lds_ld((LdsVec4Ptr)(nd + ox));      fx = lds_ld((LdsVec4Ptr)(nd + (ox ^ 16)));
+        ny = lds_ld((LdsVec4Ptr)(nd + 32 + oy)); fy = lds_ld((LdsVec4Ptr)(nd + 32 + (oy ^ 16)));
+        nz = lds_ld((LdsVec4Ptr)(nd + 64 + oz)); fz = lds_ld((LdsVec4Ptr)(nd + 64 + (oz ^ 16)));
+        id = lds_ld((LdsVec4Ptr)(nd + 96));
+    }
+    DEV void tri(int slot, MptVec4 &g0, MptVec4 &g1, MptVec4 &g2) const { tri_lds<ODD_IDS>(tgeo, slot, g0, g1, g2); }
+    struct Lifo {
+        LdsShortPtr stack;     // &lds16[threadIdx.x]
+        int sp;
+        float ts;              // (T_SCALED)
+        DEV void push(int v) { stack[sp * MPT_LDS_BLOCK] = (short)v; sp++; }    // (by level: the sentinel at a ray's start)
+        DEV int sp_at(int level) const { return (int)(unsigned)(unsigned long long)(stack + level * MPT_LDS_BLOCK); }
+        DEV static void st(int sp, int v) { *(LdsShortPtr)(unsigned long long)(unsigned)sp = (short)v; }
+        DEV static int ld(int sp) { return (int)*(LdsUShortPtr)(unsigned long long)(unsigned)sp; }
+    };
 };
 
 #if MPT_STRICT
@@ -547,7 +536,7 @@ struct Stack16W {
 template <bool COUNT>
 DEV Hit bvh_closest(const MptRenderParams &p, int *lds, V3 ro, V3 rd, int avoid, Cnt &cnt) {
     const int n = p.n;
-    Stack st; st.base = lds; st.sp = 0;
+    GatherWalk::Lifo st; st.stack = lds; st.sp = 0;
     st.push(n);
     Hit ret; ret.hit = 0; ret.depth = MPT_INF; ret.index = -1; ret.u = 0.0f; ret.v = 0.0f;
     if (COUNT) cnt.rays++;
@@ -601,8 +590,8 @@ DEV bool box_fast(float lox, float loy, float loz, float hix, float hiy, float h
 // before the best depth is tested); the order differs: near child first, far child pushed,
 // subtrees beyond the best depth skipped.  ANY = stop at the first hit with depth <= tmax
 // (path.py:51: occluded iff the closest hit is within li.dis).
-template <bool ANY, bool COUNT, class SCENE, class STACK>
-DEV Hit bvh_walk(const SCENE &sc, int n, STACK st, V3 ro, V3 rd, int avoid, float tmax, Cnt &cnt) {
+template <bool ANY, bool COUNT, class WALK>
+DEV Hit bvh_walk(const WALK &w, int n, typename WALK::Lifo st, V3 ro, V3 rd, int avoid, float tmax, Cnt &cnt) {
     Hit ret; ret.hit = 0; ret.depth = tmax; ret.index = -1; ret.u = 0.0f; ret.v = 0.0f;
     if (COUNT) cnt.rays++;
     if (n < 2) return ret;     // lbvh.py:218,319: with one face the root box is never written
@@ -612,7 +601,7 @@ DEV Hit bvh_walk(const SCENE &sc, int n, STACK st, V3 ro, V3 rd, int avoid, floa
     int curr = 0;
     for (;;) {
         MptVec4 a, b, c, d;
-        sc.node(curr, a, b, c, d);
+        w.node(curr, a, b, c, d);
         int id0 = __float_as_int(d.x), id1 = __float_as_int(d.y);
         if (COUNT) { cnt.n_node++; cnt.n_box += 2; }
         float tn0, tn1;
@@ -625,7 +614,7 @@ DEV Hit bvh_walk(const SCENE &sc, int n, STACK st, V3 ro, V3 rd, int avoid, floa
                 if (COUNT) cnt.n_tri++;
                 float dd, s, t;
                 MptVec4 g0, g1, g2;
-                sc.tri(slot, g0, g1, g2);
+                w.tri(slot, g0, g1, g2);
                 if (tri_test_fast(g0, g1, g2, ro, rd, &dd, &s, &t) && (ANY ? dd <= ret.depth : dd < ret.depth)) {
                     ret.depth = dd; ret.index = slot; ret.u = s; ret.v = t; ret.hit = 1;
                     if (ANY) return ret;
@@ -639,7 +628,7 @@ DEV Hit bvh_walk(const SCENE &sc, int n, STACK st, V3 ro, V3 rd, int avoid, floa
                 if (COUNT) cnt.n_tri++;
                 float dd, s, t;
                 MptVec4 g0, g1, g2;
-                sc.tri(slot, g0, g1, g2);
+                w.tri(slot, g0, g1, g2);
                 if (tri_test_fast(g0, g1, g2, ro, rd, &dd, &s, &t) && (ANY ? dd <= ret.depth : dd < ret.depth)) {
                     ret.depth = dd; ret.index = slot; ret.u = s; ret.v = t; ret.hit = 1;
                     if (ANY) return ret;
@@ -662,21 +651,21 @@ DEV Hit bvh_walk(const SCENE &sc, int n, STACK st, V3 ro, V3 rd, int avoid, floa
     return ret;
 }
 
-// what a traversal needs besides the ray: where the scene records and this lane's stack live
-template <class SCENE, class STACK>
+// what a traversal needs besides the ray: the walk (where the scene records and this lane's stack live) and the number of faces
+template <class WALK>
 struct Tracer {
-    SCENE sc;
-    STACK st;
+    WALK w;
+    typename WALK::Lifo st;
     int n;
     template <bool COUNT>
     DEV Hit closest(V3 ro, V3 rd, int avoid, Cnt &cnt) const {
-        Hit h = bvh_walk<false, COUNT>(sc, n, st, ro, rd, avoid, MPT_INF, cnt);
+        Hit h = bvh_walk<false, COUNT>(w, n, st, ro, rd, avoid, MPT_INF, cnt);
         if (!h.hit) h.depth = MPT_INF;
         return h;
     }
     template <bool COUNT>
     DEV bool occluded(V3 ro, V3 rd, int avoid, float dis, Cnt &cnt) const {
-        return bvh_walk<true, COUNT>(sc, n, st, ro, rd, avoid, dis, cnt).hit != 0;
+        return bvh_walk<true, COUNT>(w, n, st, ro, rd, avoid, dis, cnt).hit != 0;
     }
 };
 #endif
@@ -1381,7 +1370,7 @@ DEV void get_geometries(const MptRenderParams &p, const Hit &hit, V3 ro, V3 rd, 
 // round trip to L2 then overlaps the light tests instead of following them), the material comes from the scene
 // (LDS-resident kernel) or from the record's material id
 struct ShadeRec { MptVec4 s0, s1, s2, s3; };
-// OFF32 (the LDS-resident kernels): a 32-bit byte offset from the (scalar) base -- one shift and the instruction's own address add, where
+// OFF32 (the LDS-resident kernels: WALK::LDS_RESIDENT): a 32-bit byte offset from the (scalar) base -- one shift and the instruction's own address add, where
 // base + (size_t)slot * 4 is a 64-bit shift and a 64-bit add per lane (slots are below 2^26: fill_params refuses more faces).  The
 // gather kernels keep the 64-bit form: with the short one their 96-register allocation comes out 5-13 % slower (profiles/r05_ab_experiments.json)
 template <bool OFF32>
@@ -1390,8 +1379,9 @@ DEV ShadeRec shade_rec_load(const MptRenderParams &p, int slot) {
     ShadeRec r; r.s0 = s[0]; r.s1 = s[1]; r.s2 = s[2]; r.s3 = s[3];
     return r;
 }
-template <int FEAT, class SCENE>
-DEV void get_geometries_rec(const MptRenderParams &p, const SCENE &sc, const ShadeRec &r, const Hit &hit, V3 ro, V3 rd,
+// (WALK: a walk type, or the unit-evaluation kernel's stand-in for one: LDS_MATS is all it reads of a type without material records)
+template <int FEAT, class WALK>
+DEV void get_geometries_rec(const MptRenderParams &p, const WALK &w, const ShadeRec &r, const Hit &hit, V3 ro, V3 rd,
                             V3 *hitpos, V3 *normal, Disney &mat) {
     const MptVec4 s0 = r.s0, s1 = r.s1, s2 = r.s2, s3 = r.s3;
     V3 nrm; float tu, tv;
@@ -1400,11 +1390,11 @@ DEV void get_geometries_rec(const MptRenderParams &p, const SCENE &sc, const Sha
     float sign = -dot(rd, nrm);
     if (sign < 0.0f) nrm = -nrm;
     *normal = nrm;
-    if constexpr (SCENE::LDS_MATS) {
-        const int rec = sc.mtl[hit.index];
-        LdsVec4Ptr q = sc.mats + rec * MPT_LDS_MAT_VEC4;
+    if constexpr (WALK::LDS_MATS) {
+        const int rec = w.mtl[hit.index];
+        LdsVec4Ptr q = w.mats + rec * MPT_LDS_MAT_VEC4;
         MptVec4 q0 = lds_ld(q), q1 = lds_ld(q + 1), q2 = lds_ld(q + 2), q3 = lds_ld(q + 3), d0 = lds_ld(q + 4), d1 = lds_ld(q + 5);
-        material_from<FEAT>(p, p.mats + (rec == sc.mat_last ? sc.mat_default : rec), q0, q1, q2, q3, d0, d1, tu, tv, mat);
+        material_from<FEAT>(p, p.mats + (rec == w.mat_last ? w.mat_default : rec), q0, q1, q2, q3, d0, d1, tu, tv, mat);
     } else {
         static_assert(FEAT == MPT_FEAT_GENERIC, "the gather kernels are built for the generic mask only");
         material_get(p, __float_as_int(s3.w), tu, tv, mat);

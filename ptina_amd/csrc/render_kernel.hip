@@ -96,7 +96,7 @@ __global__ MPT_RENDER_BOUNDS void MPT_SUFFIX(render_kernel)(const MptRenderParam
 #else
     // persistent workgroups pulling (8x8 tile, chunk) items; see WorkQueue
     WorkQueue wq; wq.ctr = p.work_counter; wq.nitems = p.nitems; wq.q0 = blockIdx.x & 7; wq.qoff = 0;
-    trace_stream<COUNT, MPT_FEAT_GENERIC>(p, tr.sc, tr.st, wq, cnt);
+    trace_stream<COUNT, MPT_FEAT_GENERIC>(p, tr.w, tr.st, wq, cnt);
     finalise_tiles<MPT_FIN_GROUP_GATHER>(p);
 #endif
     flush_counters<COUNT>(p, cnt);
@@ -112,21 +112,17 @@ __global__ MPT_RENDER_BOUNDS void MPT_SUFFIX(render_kernel)(const MptRenderParam
 #endif
 template <bool COUNT, bool QUANT>
 __global__ __launch_bounds__(MPT_BLOCK, MPT_WIDE_WAVES) void render_kernel_wide(const MptRenderParams p) {
-    __shared__ int s_stack[SpillStack::CAP * MPT_BLOCK];
-    SpillStack stk;
-    stk.base = s_stack + threadIdx.x;
+    typedef GatherWalk4<QUANT> Walk;
+    __shared__ int s_stack[Walk::CAP * MPT_BLOCK];
+    typename Walk::Lifo stk;
+    stk.stack = s_stack + threadIdx.x;
     stk.spill = p.stack_spill;
-    stk.lane_off = (blockIdx.x * MPT_BLOCK + threadIdx.x) * (unsigned)SpillStack::SPILL;   // (grid x 256 x 88 entries: far below 2^32)
+    stk.lane_off = (blockIdx.x * MPT_BLOCK + threadIdx.x) * (unsigned)Walk::SPILL;   // (grid x 256 x 88 entries: far below 2^32)
     stk.sp = 0;
     Cnt cnt = {};
     WorkQueue wq; wq.ctr = p.work_counter; wq.nitems = p.nitems; wq.q0 = blockIdx.x & 7; wq.qoff = 0;
-    if constexpr (QUANT) {
-        QuantScene sc; sc.qnode = p.qnode; sc.tgeo = p.tfast;
-        trace_stream<COUNT, MPT_FEAT_GENERIC>(p, sc, stk, wq, cnt);
-    } else {
-        WideScene sc; sc.wnode = p.wnode; sc.tgeo = p.tfast;
-        trace_stream<COUNT, MPT_FEAT_GENERIC>(p, sc, stk, wq, cnt);
-    }
+    Walk w; w.wnode = QUANT ? p.qnode : p.wnode; w.tgeo = p.tfast;
+    trace_stream<COUNT, MPT_FEAT_GENERIC>(p, w, stk, wq, cnt);
     finalise_tiles<MPT_FIN_GROUP_GATHER>(p);
     flush_counters<COUNT>(p, cnt);
 }
@@ -137,6 +133,18 @@ __global__ __launch_bounds__(MPT_BLOCK, MPT_WIDE_WAVES) void render_kernel_wide(
 // the wave's record of the launch timeline (option "timeline"; include/miptina.h mpt_get_timeline), or null
 DEV unsigned long long *lds_timeline(const MptRenderParams &p) {
     return p.timeline ? p.timeline + MPT_TIMELINE_WORDS * (size_t)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) : nullptr;
+}
+
+// What both walks hold besides their node records, from the kernel's regions: the triangles, the material records and bytes; and the
+// lane's column of the int16 stack region
+template <class WALK>
+DEV void lds_walk_regions(WALK &w, typename WALK::Lifo &stk, MptVec4 *smem, const MptLdsRegions &lay) {
+    const int nnode4 = lay.nnode4, ntri4 = lay.ntri4, nmat4 = lay.nmat4, nmtl4 = lay.nmtl4;
+    w.tgeo = (LdsVec4Ptr)(void *)(smem + nnode4);
+    w.mats = (LdsVec4Ptr)(void *)(smem + nnode4 + ntri4);
+    w.mtl = (LdsU8Ptr)(void *)(smem + nnode4 + ntri4 + nmat4);
+    stk.stack = (LdsShortPtr)(void *)(smem + nnode4 + ntri4 + nmat4 + nmtl4) + threadIdx.x;
+    stk.sp = 0;
 }
 
 // The copy-in both kernels make behind their node records: the triangles, the material records (DEFAULT_LAST: the records the model
@@ -161,7 +169,6 @@ template <bool COUNT>
 __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds(const MptRenderParams p) {
     extern __shared__ __attribute__((aligned(16))) MptVec4 smem[];
     const MptLdsRegions lay = mpt_lds_regions(p.n, p.default_mtl);
-    const int nnode4 = lay.nnode4, ntri4 = lay.ntri4, nmat4 = lay.nmat4, nmtl4 = lay.nmtl4;
     unsigned long long *tl = lds_timeline(p);
     if (tl && (threadIdx.x & 63) == 0) tl[0] = wall_clock64();
     {   // one copy of the scene per CU: coalesced 16-B loads, ds_write_b128
@@ -180,18 +187,14 @@ __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds(const MptRend
     __syncthreads();
     if (tl && (threadIdx.x & 63) == 0) tl[1] = wall_clock64();
 
-    LdsScene sc;
-    sc.fnode = (LdsVec4Ptr)(void *)smem;
-    sc.tgeo = (LdsVec4Ptr)(void *)(smem + nnode4);
-    sc.mats = (LdsVec4Ptr)(void *)(smem + nnode4 + ntri4);
-    sc.mtl = (LdsU8Ptr)(void *)(smem + nnode4 + ntri4 + nmat4);
-    sc.mat_last = p.default_mtl; sc.mat_default = p.default_mtl;
-    Stack16 stk;
-    stk.base = (LdsShortPtr)(void *)(smem + nnode4 + ntri4 + nmat4 + nmtl4) + threadIdx.x;
-    stk.sp = 0;
+    LdsWalk w;
+    LdsWalk::Lifo stk;
+    w.fnode = (LdsVec4Ptr)(void *)smem;
+    lds_walk_regions(w, stk, smem, lay);
+    w.mat_last = p.default_mtl; w.mat_default = p.default_mtl;
     Cnt cnt = {};
     WorkQueue wq; wq.ctr = p.work_counter; wq.nitems = p.nitems; wq.q0 = blockIdx.x & 7; wq.qoff = 0;
-    trace_stream<COUNT, MPT_FEAT_GENERIC>(p, sc, stk, wq, cnt, tl);
+    trace_stream<COUNT, MPT_FEAT_GENERIC>(p, w, stk, wq, cnt, tl);
     if (tl && (threadIdx.x & 63) == 0) tl[3] = wall_clock64();
     const int fin_tiles = finalise_tiles<MPT_FIN_GROUP_LDS>(p);
     if (tl && (threadIdx.x & 63) == 0) { tl[4] = wall_clock64(); tl[5] = (unsigned long long)fin_tiles; }   // left the finalisation; tiles it did
@@ -210,7 +213,6 @@ template <bool COUNT, int FEAT>
 __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds4(const MptRenderParams p) {
     extern __shared__ __attribute__((aligned(16))) MptVec4 smem[];
     const MptLdsRegions lay = mpt_lds4_regions(p.n, p.nwide, p.lds_nmats);
-    const int nnode4 = lay.nnode4, ntri4 = lay.ntri4, nmat4 = lay.nmat4, nmtl4 = lay.nmtl4;
     unsigned long long *tl = lds_timeline(p);
     if (tl && (threadIdx.x & 63) == 0) tl[0] = wall_clock64();
     {
@@ -218,10 +220,9 @@ __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds4(const MptRen
             const int rec = k / 7, w = k - rec * 7;
             MptVec4 v = p.wnode[rec * 8 + w];
             if (w == 6) {
-                // the four ids: internal ones become the record's byte offset (/ 8 without ODD_IDS), leaves (slot << 4) | 1 (~slot)
+                // the four ids (LdsWalk4::ODD_IDS): internal ones become the record's byte offset, leaves (slot << 4) | 1
                 const int i0 = __float_as_int(v.x), i1 = __float_as_int(v.y), i2 = __float_as_int(v.z), i3 = __float_as_int(v.w);
-                const int scale = LdsWideScene::ODD_IDS ? MPT_LDS4_NODE_STRIDE : MPT_LDS4_NODE_STRIDE / 8;
-#define MPT_LDS_ID(i) __int_as_float((i) >= 0 ? (i) * scale : (LdsWideScene::ODD_IDS ? ((~(i)) << 4) | 1 : (i)))
+#define MPT_LDS_ID(i) __int_as_float((i) >= 0 ? (i) * MPT_LDS4_NODE_STRIDE : ((~(i)) << 4) | 1)
                 v.x = MPT_LDS_ID(i0); v.y = MPT_LDS_ID(i1); v.z = MPT_LDS_ID(i2); v.w = MPT_LDS_ID(i3);
 #undef MPT_LDS_ID
             }
@@ -232,25 +233,20 @@ __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds4(const MptRen
     __syncthreads();
     if (tl && (threadIdx.x & 63) == 0) tl[1] = wall_clock64();
 
-    LdsWideScene sc;
-    sc.wnode = (LdsVec4Ptr)(void *)smem;
-    if (LdsWideScene::ODD_IDS && (unsigned)(unsigned long long)(LdsBytePtr)sc.wnode != 0u) {
+    if ((unsigned)(unsigned long long)(LdsBytePtr)(LdsVec4Ptr)(void *)smem != 0u) {
         // node ids are LDS addresses counted from 0: the dynamic LDS must be all the LDS this kernel has (it is; a static __shared__
         // object added to it one day would move smem)
         if (threadIdx.x == 0) __hip_atomic_store(p.watchdog, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         return;
     }
-    sc.tgeo = (LdsVec4Ptr)(void *)(smem + nnode4);
-    sc.mats = (LdsVec4Ptr)(void *)(smem + nnode4 + ntri4);
-    sc.mtl = (LdsU8Ptr)(void *)(smem + nnode4 + ntri4 + nmat4);
-    sc.mat_last = p.lds_nmats; sc.mat_default = p.default_mtl;
-    Stack16W stk;
-    stk.base = (LdsShortPtr)(void *)(smem + nnode4 + ntri4 + nmat4 + nmtl4) + threadIdx.x;
-    stk.sp = 0;
+    LdsWalk4 w;
+    LdsWalk4::Lifo stk;
+    lds_walk_regions(w, stk, smem, lay);
+    w.mat_last = p.lds_nmats; w.mat_default = p.default_mtl;
     stk.ts = p.t_scale;
     Cnt cnt = {};
     WorkQueue wq; wq.ctr = p.work_counter; wq.nitems = p.nitems; wq.q0 = blockIdx.x & 7; wq.qoff = 0;
-    trace_stream<COUNT, FEAT>(p, sc, stk, wq, cnt, tl);
+    trace_stream<COUNT, FEAT>(p, w, stk, wq, cnt, tl);
     if (tl && (threadIdx.x & 63) == 0) tl[3] = wall_clock64();
     const int fin_tiles = finalise_tiles<MPT_FIN_GROUP_LDS>(p);
     if (tl && (threadIdx.x & 63) == 0) { tl[4] = wall_clock64(); tl[5] = (unsigned long long)fin_tiles; }
@@ -404,7 +400,7 @@ static const RenderKernelFn wide_variants[4] = { render_kernel_wide<false, false
 static int wide_variant(int count, int quant) { return (quant ? 2 : 0) + (count ? 1 : 0); }
 
 // persistent workgroups over 4-wide nodes; `grid` = number of CUs (scaled here by the blocks each CU can hold);
-// *blocks = workgroups launched (the spill strip must hold blocks x 256 lanes x SpillStack::SPILL entries)
+// *blocks = workgroups launched (the spill strip must hold blocks x 256 lanes x GatherWalk4::SPILL entries)
 MPT_KERNEL_API hipError_t mpt_wide_blocks(int grid, int count, int quant, int *blocks) {
     static std::atomic<int> occ_cache[MPT_MAX_DEVICES][4];
     int occ = 0;

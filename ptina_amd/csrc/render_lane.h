@@ -39,11 +39,11 @@ struct LaneState {
     V3 direct;                 // shadow ray in flight: candidate direct light, added if unoccluded
     // ray being traversed (closest: the path ray; shadow: hitpos -> light)
     V3 to, td, inv, oinv;
-    int offx, offy, offz;      // byte offset of the entry planes of each axis in a node record (binary LDS kernel: STACK::PLANE_OFF)
-    float tbest;               // closest: best depth so far; shadow: li.dis, moved up one float where STACK::ONE_TEST; x t_scale while traversed (T_SCALED)
+    int offx, offy, offz;      // byte offset of the entry planes of each axis in a node record (binary LDS kernel: WALK::PLANE_OFF)
+    float tbest;               // closest: best depth so far; shadow: li.dis, moved up one float where WALK::LDS_RESIDENT; x t_scale while traversed (T_SCALED)
     int curr, sp, hidx;        // hidx: leaf slot of the hit so far, -1 = none (closest) / any occluder found (shadow); in the 4-wide LDS kernel
-                               // curr / hidx hold ids as its LDS node records do (LdsWideScene::ODD_IDS) and sp is the LDS address of the
-                               // lane's top stack entry (Stack16W::SP_ADDR), everywhere else a level
+                               // curr / hidx hold ids as its LDS node records do (LdsWalk4::ODD_IDS) and sp is the LDS address of the
+                               // lane's top stack entry (LdsWalk4::SP_ADDR), everywhere else a level
     float hu, hv;
     int shadow;                // 1: the ray in flight is a shadow ray.  An int in a VGPR on purpose: as a bool the
                                // compiler keeps it in a scalar lane mask and re-merges that mask (s_andn2 / s_and /
@@ -75,7 +75,7 @@ DEV int reduce_mod_dim(int h, int dim, float inv_dim) {
 // along with the counter, so a draw costs a load and a compare.  The wrapping case takes the literal path.
 template <int N, bool OFF32 = false>
 DEV void lane_draws(const MptRenderParams &p, LaneState &L, float *out) {
-    // OFF32 (the LDS-resident kernels): the frame's row as a 32-bit word offset from the scalar base (frames x dim stays below 2^30,
+    // OFF32 (WALK::LDS_RESIDENT): the frame's row as a 32-bit word offset from the scalar base (frames x dim stays below 2^30,
     // fill_params checks) instead of 64-bit arithmetic per lane; the gather kernels keep the long form (pt_device.h shade_rec_load)
 #define MPT_ROW(k_) (OFF32 ? (const float *)((const char *)p.P + ((__umul24((unsigned)L.frame, (unsigned)p.sobol_dim) + (unsigned)(k_)) << 2)) \
                            : p.P + (size_t)L.frame * p.sobol_dim + (k_))
@@ -140,35 +140,35 @@ DEV void store_sample(const MptRenderParams &p, int frame, int pix, V3 radiance)
 
 // the bottom entry of every ray's LIFO is a sentinel, so "pop" never needs an emptiness test:
 // popping the sentinel means the traversal is over
-template <class STACK>
+template <class WALK>
 DEV int classify(int v) {      // what a popped / chosen entry means for the lane's state
-    if constexpr (STACK::ODD_IDS) return v & 3;      // node ids are multiples of 16 (ST_NODE == 0), leaf ids 16 * slot + 1 (ST_LEAF == 1), the sentinel is 2 (ST_DONE)
-    else return v == STACK::SENTINEL ? ST_DONE : (v < 0 ? ST_LEAF : ST_NODE);
+    if constexpr (WALK::ODD_IDS) return v & 3;      // node ids are multiples of 16 (ST_NODE == 0), leaf ids 16 * slot + 1 (ST_LEAF == 1), the sentinel is 2 (ST_DONE)
+    else return v == WALK::SENTINEL ? ST_DONE : (v < 0 ? ST_LEAF : ST_NODE);
 }
 
-template <bool COUNT, class STACK>
-DEV void lane_start_ray(LaneState &L, STACK &stk, V3 o, V3 d, float tmax, bool shadow, Cnt &cnt) {
+template <bool COUNT, class WALK>
+DEV void lane_start_ray(LaneState &L, typename WALK::Lifo &stk, V3 o, V3 d, float tmax, bool shadow, Cnt &cnt) {
     L.to = o; L.td = d;
     L.inv = v3(m_rcp(d.x), m_rcp(d.y), m_rcp(d.z));
-    if constexpr (STACK::T_SCALED) { L.inv = L.inv * stk.ts; tmax *= stk.ts; }
+    if constexpr (WALK::T_SCALED) { L.inv = L.inv * stk.ts; tmax *= stk.ts; }
     L.oinv = o * L.inv;
     // which of an axis' two planes the ray enters through: offset of that plane in the node record
-    if constexpr (STACK::PLANE_OFF != 0) {     // (the 4-wide gather kernels read the signs off L.inv in the step: three registers less to carry)
-        L.offx = __float_as_int(L.inv.x) < 0 ? STACK::PLANE_OFF : 0;
-        L.offy = __float_as_int(L.inv.y) < 0 ? STACK::PLANE_OFF : 0;
-        L.offz = __float_as_int(L.inv.z) < 0 ? STACK::PLANE_OFF : 0;
+    if constexpr (WALK::PLANE_OFF != 0) {     // (the 4-wide gather kernels read the signs off L.inv in the step: three registers less to carry)
+        L.offx = __float_as_int(L.inv.x) < 0 ? WALK::PLANE_OFF : 0;
+        L.offy = __float_as_int(L.inv.y) < 0 ? WALK::PLANE_OFF : 0;
+        L.offz = __float_as_int(L.inv.z) < 0 ? WALK::PLANE_OFF : 0;
     }
     // a shadow ray takes any occluder with depth <= li.dis (path.py:51), a closest-hit ray a strictly nearer hit (lbvh.py:331): with
-    // the shadow ray's bound moved up to the next float the LEAF step asks both the same question, depth < tbest (STACK::ONE_TEST: the
+    // the shadow ray's bound moved up to the next float the LEAF step asks both the same question, depth < tbest (the
     // LDS-resident kernels, -0.5 %; the gather kernels lose 1-2 % with it and keep the two tests)
-    if constexpr (STACK::ONE_TEST) {
+    if constexpr (WALK::LDS_RESIDENT) {
         if (shadow) { const int b = __float_as_int(tmax); tmax = __int_as_float(b + (b < 0x7f800000 ? 1 : 0)); }
     }
     L.tbest = tmax; L.shadow = shadow ? 1 : 0; L.hidx = -1; L.hu = 0.0f; L.hv = 0.0f;
     stk.sp = 0;
-    stk.push(STACK::SENTINEL);
+    stk.push(WALK::SENTINEL);
     L.curr = 0;
-    if constexpr (STACK::SP_ADDR) L.sp = stk.sp_at(1) - STACK::SP_BIAS; else L.sp = 1;
+    if constexpr (WALK::SP_ADDR) L.sp = stk.sp_at(1) - WALK::SP_BIAS; else L.sp = 1;
     if (COUNT) cnt.rays++;
     L.st = ST_NODE;
 }
@@ -182,8 +182,8 @@ DEV void lane_store_sample(const MptRenderParams &p, LaneState &L) {
 // The one place of a shading pass where rays start: the lanes whose shadow ray just ended, the lanes that
 // shaded and the lanes that took a new sample all come here, so the direction set-up (a normalisation, three reciprocals,
 // the stack reset) is issued once per pass at the width of all of them, not three times at a third each
-template <bool COUNT, class STACK>
-DEV void lane_begin_ray(const MptRenderParams &p, LaneState &L, STACK &stk, Cnt &cnt) {
+template <bool COUNT, class WALK>
+DEV void lane_begin_ray(const MptRenderParams &p, LaneState &L, typename WALK::Lifo &stk, Cnt &cnt) {
     const bool sh = L.st == ST_SHADOW;
     const V3 n = normalized_unfused(L.prd);
     if (!sh) {
@@ -192,7 +192,7 @@ DEV void lane_begin_ray(const MptRenderParams &p, LaneState &L, STACK &stk, Cnt 
         L.prd = n;
     }
     const V3 d = sh ? L.td : n;
-    lane_start_ray<COUNT>(L, stk, L.to, d, sh ? L.tbest : MPT_INF, sh, cnt);
+    lane_start_ray<COUNT, WALK>(L, stk, L.to, d, sh ? L.tbest : MPT_INF, sh, cnt);
     // lbvh.py:218,319: with fewer than two faces the root box is never written: no hit
     if (!sh && p.n < 2) L.st = ST_DONE;
 }
@@ -204,17 +204,17 @@ DEV void lane_begin_ray(const MptRenderParams &p, LaneState &L, STACK &stk, Cnt 
 // (Measured in-process A/B on MI355X and not kept: the twelve plane distances as six v_pk_fma_f32 --
 //  5 % slower, packed f32 is not double-rate here; filtering the origin triangle in the leaf stage
 //  instead of here -- within noise; per-stage instead of ratio scheduler thresholds -- within +-1 %.)
-template <bool COUNT, class SCENE, class STACK>
-DEV void stage_node(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
+template <bool COUNT, class WALK>
+DEV void stage_node(const WALK &w, typename WALK::Lifo &stk, LaneState &L, Cnt &cnt) {
     int id0, id1;
     float tn0, tn1;
     bool h0, h1;
     if (COUNT) { cnt.n_node++; cnt.n_box += 2; }
     int spec = 0;
-    if constexpr (STACK::PEEK) spec = stk.peek(L.sp - 1);      // (the sentinel sits at level 0: sp >= 1 while a ray is traversed)
-    if constexpr (SCENE::SIGNED_PLANES) {
+    if constexpr (WALK::PEEK) spec = stk.peek(L.sp - 1);      // (the sentinel sits at level 0: sp >= 1 while a ray is traversed)
+    if constexpr (WALK::PLANE_OFF != 0) {
         mpt_f2 nx, fx, ny, fy, nz, fz, ids;
-        sc.node_planes(L.curr, L.offx, L.offy, L.offz, nx, fx, ny, fy, nz, fz, ids);
+        w.node_planes(L.curr, L.offx, L.offy, L.offz, nx, fx, ny, fy, nz, fz, ids);
         id0 = __float_as_int(ids.x); id1 = __float_as_int(ids.y);
         tn0 = fmaxf(fmaxf(__builtin_fmaf(nx.x, L.inv.x, -L.oinv.x), __builtin_fmaf(ny.x, L.inv.y, -L.oinv.y)),
                     fmaxf(__builtin_fmaf(nz.x, L.inv.z, -L.oinv.z), 0.0f));
@@ -227,7 +227,7 @@ DEV void stage_node(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
         h0 = tn0 <= tf0; h1 = tn1 <= tf1;
     } else {
         MptVec4 a, b, c, d;
-        sc.node(L.curr, a, b, c, d);
+        w.node(L.curr, a, b, c, d);
         id0 = __float_as_int(d.x); id1 = __float_as_int(d.y);
         h0 = box_fast(a.x, b.x, c.x, a.z, b.z, c.z, L.inv, L.oinv, L.tbest, &tn0);
         h1 = box_fast(a.y, b.y, c.y, a.w, b.w, c.w, L.inv, L.oinv, L.tbest, &tn1);
@@ -238,7 +238,7 @@ DEV void stage_node(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
     bool swap = tn1 < tn0;
     int nearid = swap ? id1 : id0, farid = swap ? id0 : id1;
     int next = h0 ? (h1 ? nearid : id0) : id1;
-    if constexpr (STACK::PEEK) {
+    if constexpr (WALK::PEEK) {
         // the entry a pop would return was asked for with the node record (spec, below the function's head): a step that
         // pops does not wait a second LDS round trip behind the box tests.  Push (both hit) and pop (both missed) exclude
         // each other, and a push goes to level sp, not sp - 1
@@ -253,7 +253,7 @@ DEV void stage_node(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
         L.sp = stk.sp;
     }
     L.curr = next;
-    L.st = classify<STACK>(next);
+    L.st = classify<WALK>(next);
 }
 
 // min(a, b, c, tbest) of a slab test's exit side.  Written as the two instructions themselves: through fminf the compiler first
@@ -262,20 +262,20 @@ DEV void stage_node(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
 // input that is not a signalling NaN, and nothing in the kernel makes one.  MI355X, same box, alternated three times
 // (profiles/r05_ab_experiments.json): 2.593 / 2.566 / 2.554 ms per launch -> 2.560 / 2.537 / 2.526.  (The 8-bit step of the
 // gather kernels, which wait for their gathers as much as for the issue port, did not move with it: C4 1547 / 1543 against 1546 / 1549.)
-DEV float exit_min_asm(float a, float b, float c, float tbest) {
+DEV float exit_min(float a, float b, float c, float tbest) {
     float m, r;
     asm("v_min_f32 %0, %1, %2" : "=v"(m) : "v"(c), "v"(tbest));
     asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(m));
     return r;
 }
-DEV float exit_min(float a, float b, float c, float tbest) { return exit_min_asm(a, b, c, tbest); }
 
 // The same step through a 4-wide node: four slab tests (planes picked by the ray's direction signs) on one 128-B
 // record, the children that are hit sorted
 // by entry distance (a five-comparator network on (distance bits, id) pairs; a miss sorts last), the nearest
 // taken next and the others pushed farthest first.
-template <bool COUNT, class SCENE, class STACK>
-DEV void stage_node4(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
+template <bool COUNT, class WALK>
+DEV void stage_node4(const WALK &w, typename WALK::Lifo &stk, LaneState &L, Cnt &cnt) {
+    typedef typename WALK::Lifo LIFO;
     int id0, id1, id2, id3;
     float t0, t1, t2, t3;
     bool h0, h1, h2, h3;
@@ -283,10 +283,10 @@ DEV void stage_node4(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
     // the entry a step without a hit pops is asked for together with the node record: some lane of the wave pops in nearly every
     // step, and the wave then waited a second LDS round trip behind the sort (pushes go above the top entry, never onto it)
     int spec = 0;
-    if constexpr (STACK::SP_ADDR) spec = STACK::ld(L.sp - STACK::SP_STEP + STACK::SP_BIAS);
-    if constexpr (SCENE::QUANT) {
+    if constexpr (WALK::SP_ADDR) spec = LIFO::ld(L.sp - WALK::SP_STEP + WALK::SP_BIAS);
+    if constexpr (WALK::QUANT) {
         MptVec4 ra, rb, rc, idv;
-        sc.node4q(L.curr, ra, rb, rc, idv);
+        w.node4q(L.curr, ra, rb, rc, idv);
         id0 = __float_as_int(idv.x); id1 = __float_as_int(idv.y); id2 = __float_as_int(idv.z); id3 = __float_as_int(idv.w);
         // plane = origin + q * scale, so its distance along the ray is q * (scale * inv) + (origin * inv - o * inv)
         const float sx = ra.w * L.inv.x, sy = rb.x * L.inv.y, sz = rb.y * L.inv.z;
@@ -311,12 +311,12 @@ DEV void stage_node4(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
 #undef MPT_UB
     } else {
         MptVec4 nx, fx, ny, fy, nz, fz, idv;
-        sc.node4(L.curr, __float_as_int(L.inv.x) < 0 ? 16 : 0, __float_as_int(L.inv.y) < 0 ? 16 : 0, __float_as_int(L.inv.z) < 0 ? 16 : 0,
+        w.node4(L.curr, __float_as_int(L.inv.x) < 0 ? 16 : 0, __float_as_int(L.inv.y) < 0 ? 16 : 0, __float_as_int(L.inv.z) < 0 ? 16 : 0,
                  nx, fx, ny, fy, nz, fz, idv);
         id0 = __float_as_int(idv.x); id1 = __float_as_int(idv.y); id2 = __float_as_int(idv.z); id3 = __float_as_int(idv.w);
 #define MPT_SLAB(c, tn, h)                                                                                              \
         tn = fmaxf(fmaxf(__builtin_fmaf(nx.c, L.inv.x, -L.oinv.x), __builtin_fmaf(ny.c, L.inv.y, -L.oinv.y)),            \
-                   STACK::T_SCALED ? __builtin_amdgcn_fmed3f(__builtin_fmaf(nz.c, L.inv.z, -L.oinv.z), 0.0f, 1.0f)       \
+                   WALK::T_SCALED ? __builtin_amdgcn_fmed3f(__builtin_fmaf(nz.c, L.inv.z, -L.oinv.z), 0.0f, 1.0f)       \
                                    : fmaxf(__builtin_fmaf(nz.c, L.inv.z, -L.oinv.z), 0.0f));                             \
         h = tn <= exit_min(__builtin_fmaf(fx.c, L.inv.x, -L.oinv.x), __builtin_fmaf(fy.c, L.inv.y, -L.oinv.y),          \
                            __builtin_fmaf(fz.c, L.inv.z, -L.oinv.z), L.tbest);
@@ -327,7 +327,7 @@ DEV void stage_node4(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
     // left from, lbvh.py:329) gets the largest key
     const unsigned MISS = 0xffffffffu;
     unsigned k0, k1, k2, k3;
-    if constexpr (sizeof(typename STACK::entry_t) == 2) {
+    if constexpr (WALK::IDS16) {
         // 16-bit ids (the LDS-resident kernel): the upper half of the distance's bits over the id is ONE word that sorts with
         // v_min_u32 / v_max_u32 -- ten instructions instead of the 25 of five compare-and-swaps on (key, id) pairs; distances that
         // agree in their first 8 mantissa bits are met in id order, which costs a step now and then and never a hit (the
@@ -340,7 +340,7 @@ DEV void stage_node4(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
         const unsigned m0 = max(a0, b0), m1 = min(a1, b1);
         k0 = min(a0, b0); k3 = max(a1, b1); k1 = min(m0, m1); k2 = max(m0, m1);    // (measured and not kept: without this fifth
         // comparator -- the middle pair in whatever order the network leaves it -- the step is two instructions shorter and the launch 1.8 % longer)
-        id0 = STACK::ODD_IDS ? (int)(k0 & 0xffffu) : (int)(short)(k0 & 0xffffu);
+        id0 = (int)(k0 & 0xffffu);                                                           // (ODD_IDS: unsigned)
         id1 = (int)k1; id2 = (int)k2; id3 = (int)k3;                                         // (the pushes store the low halves)
     } else {
         k0 = h0 ? (unsigned)__float_as_int(t0) : MISS;
@@ -354,23 +354,23 @@ DEV void stage_node4(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
 #undef MPT_CSWAP
     }
     int next = id0;
-    if (STACK::NO_SPILL || __ballot(L.sp > STACK::CAP - 3) == 0ull) {
-        // no lane of the wave is within three entries of the LDS part of its stack (the rule, not the exception; the LDS-resident
-        // kernel's stack holds every level the tree can ask for): the three pushes are plain stores at a running index -- a store
-        // that is not wanted lands on the slot the next one overwrites -- instead of three divergent regions with a spill test each
-        typedef typename STACK::entry_t entry_t;
+    // The three pushes are plain stores at a running index -- a store that is not wanted lands on the slot the next one overwrites --
+    // instead of three divergent regions with a spill test each: always where the stack holds every level the tree can ask for in
+    // LDS (SP_ADDR: an address has no spilled form), else while no lane of the wave is within three entries of the LDS part of its
+    // stack (the rule, not the exception)
+    if constexpr (WALK::SP_ADDR) {                                                    // (sp: the address of the top entry)
         int sp = L.sp;
-        if constexpr (STACK::SP_ADDR) {                                               // (sp: the address of the top entry, Stack16W)
-            STACK::st(sp + STACK::SP_BIAS, id3); sp += k3 != MISS ? STACK::SP_STEP : 0;
-            STACK::st(sp + STACK::SP_BIAS, id2); sp += k2 != MISS ? STACK::SP_STEP : 0;
-            STACK::st(sp + STACK::SP_BIAS, id1); sp += k1 != MISS ? STACK::SP_STEP : 0;
-            if (k0 == MISS) { sp -= STACK::SP_STEP; next = spec; }
-        } else {
-            stk.base[sp * STACK::STRIDE] = (entry_t)id3; sp += k3 != MISS ? 1 : 0;
-            stk.base[sp * STACK::STRIDE] = (entry_t)id2; sp += k2 != MISS ? 1 : 0;
-            stk.base[sp * STACK::STRIDE] = (entry_t)id1; sp += k1 != MISS ? 1 : 0;
-            if (k0 == MISS) { sp--; next = (int)stk.base[sp * STACK::STRIDE]; }       // sorted: then nothing was pushed
-        }
+        LIFO::st(sp + WALK::SP_BIAS, id3); sp += k3 != MISS ? WALK::SP_STEP : 0;
+        LIFO::st(sp + WALK::SP_BIAS, id2); sp += k2 != MISS ? WALK::SP_STEP : 0;
+        LIFO::st(sp + WALK::SP_BIAS, id1); sp += k1 != MISS ? WALK::SP_STEP : 0;
+        if (k0 == MISS) { sp -= WALK::SP_STEP; next = spec; }
+        L.sp = sp;
+    } else if (__ballot(L.sp > WALK::CAP - 3) == 0ull) {
+        int sp = L.sp;
+        stk.stack[sp * MPT_BLOCK] = id3; sp += k3 != MISS ? 1 : 0;
+        stk.stack[sp * MPT_BLOCK] = id2; sp += k2 != MISS ? 1 : 0;
+        stk.stack[sp * MPT_BLOCK] = id1; sp += k1 != MISS ? 1 : 0;
+        if (k0 == MISS) { sp--; next = stk.stack[sp * MPT_BLOCK]; }                     // sorted: then nothing was pushed
         L.sp = sp;
     } else {
         stk.sp = L.sp;
@@ -381,25 +381,25 @@ DEV void stage_node4(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
         L.sp = stk.sp;
     }
     L.curr = next;
-    L.st = classify<STACK>(next);
+    L.st = classify<WALK>(next);
 }
 
-template <bool COUNT, class SCENE, class STACK>
-DEV void stage_leaf(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
-    int slot = SCENE::ODD_IDS ? L.curr : ~L.curr;      // (ODD_IDS: the leaf's id stands for the slot until a shading pass needs it)
+template <bool COUNT, class WALK>
+DEV void stage_leaf(const WALK &w, typename WALK::Lifo &stk, LaneState &L, Cnt &cnt) {
+    int slot = WALK::ODD_IDS ? L.curr : ~L.curr;      // (ODD_IDS: the leaf's id stands for the slot until a shading pass needs it)
     bool stop = false;
     // (the counters count the reference's work: it never tests the triangle a ray left from, lbvh.py:329)
-    if (COUNT) cnt.n_tri += (SCENE::AVOID_IN_LEAF && L.curr == L.navoid) ? 0u : 1u;
+    if (COUNT) cnt.n_tri += (WALK::WIDE && L.curr == L.navoid) ? 0u : 1u;
     int spec = 0;
-    if constexpr (STACK::SP_ADDR) spec = STACK::ld(L.sp - STACK::SP_STEP + STACK::SP_BIAS);
-    else if constexpr (STACK::PEEK) spec = stk.peek(L.sp - 1);      // a leaf step always pops: asked for with the triangle record
+    if constexpr (WALK::SP_ADDR) spec = WALK::Lifo::ld(L.sp - WALK::SP_STEP + WALK::SP_BIAS);
+    else if constexpr (WALK::PEEK) spec = stk.peek(L.sp - 1);      // a leaf step always pops: asked for with the triangle record
     MptVec4 g0, g1, g2;
-    sc.tri(slot, g0, g1, g2);
+    w.tri(slot, g0, g1, g2);
     float dd, su, sv;
     bool hit = tri_test_fast(g0, g1, g2, L.to, L.td, &dd, &su, &sv);
-    if constexpr (STACK::T_SCALED) dd *= stk.ts;                            // (L.tbest is held scaled while the ray is traversed)
-    if constexpr (SCENE::AVOID_IN_LEAF) hit = hit && L.curr != L.navoid;    // the triangle the ray left from (lbvh.py:329): the NODE step let it through
-    if constexpr (STACK::ONE_TEST) {
+    if constexpr (WALK::T_SCALED) dd *= stk.ts;                            // (L.tbest is held scaled while the ray is traversed)
+    if constexpr (WALK::WIDE) hit = hit && L.curr != L.navoid;              // the triangle the ray left from (lbvh.py:329): the 4-wide NODE step let it through
+    if constexpr (WALK::LDS_RESIDENT) {
         if (hit && dd < L.tbest) {                                          // lbvh.py:331; path.py:51 (lane_start_ray)
             L.tbest = dd; L.hidx = slot; L.hu = su; L.hv = sv;
             stop = L.shadow != 0;
@@ -412,13 +412,15 @@ DEV void stage_leaf(const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
         }
     }
     int next;
-    if constexpr (STACK::PEEK) {
-        next = spec; L.sp = L.sp - (STACK::SP_ADDR ? STACK::SP_STEP : 1);
+    if constexpr (WALK::SP_ADDR) {
+        next = spec; L.sp = L.sp - WALK::SP_STEP;
+    } else if constexpr (WALK::PEEK) {
+        next = spec; L.sp = L.sp - 1;
     } else {
         stk.sp = L.sp;
         next = stk.pop();
         L.sp = stk.sp;
     }
     L.curr = next;
-    L.st = stop ? ST_DONE : classify<STACK>(next);
+    L.st = stop ? ST_DONE : classify<WALK>(next);
 }

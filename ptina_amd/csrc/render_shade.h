@@ -20,11 +20,11 @@ enum { SH_END = 0, SH_BOUNCE = 1, SH_SHADOW = 2 };
 #define MPT_SEG(field)
 #endif   // path over (miss: world light added) | next bounce from hitpos | shadow ray first
 // FEAT: the scene's feature mask the kernel is compiled for (shade_feat.h; wave-uniform by construction: the host picks it per launch)
-template <bool COUNT, int FEAT, class SCENE>
-DEV int shade_core(const MptRenderParams &p, const SCENE &sc, LaneState &L, Cnt &cnt, V3 &hitpos, V3 &sdir, float &sdis) {
+template <bool COUNT, int FEAT, class WALK>
+DEV int shade_core(const MptRenderParams &p, const WALK &w, LaneState &L, Cnt &cnt, V3 &hitpos, V3 &sdir, float &sdis) {
     V3 ro = L.to, rd = L.prd;
     const bool was_hit = L.hidx >= 0;
-    float hdepth = was_hit ? (SCENE::T_SCALED ? L.tbest * p.t_unscale : L.tbest) : MPT_INF;
+    float hdepth = was_hit ? (WALK::T_SCALED ? L.tbest * p.t_unscale : L.tbest) : MPT_INF;
     // everything the stage gathers from L2 is asked for first: the shading record of the triangle and the six
     // Sobol numbers of the bounce (path.py:48,58: light triple, then BSDF triple) -- one round trip, under the
     // light tests, instead of three in a row
@@ -32,12 +32,12 @@ DEV int shade_core(const MptRenderParams &p, const SCENE &sc, LaneState &L, Cnt 
     //  gather kernels keep them: without, their register allocation spills 16 bytes more and loses 2 %)
     ShadeRec rec;
     float u[6];
-    if constexpr (!SCENE::LDS_MATS) { rec = ShadeRec{}; for (int k = 0; k < 6; k++) u[k] = 0.0f; }
+    if constexpr (!WALK::LDS_RESIDENT) { rec = ShadeRec{}; for (int k = 0; k < 6; k++) u[k] = 0.0f; }
     MPT_SEG_BEGIN
-    const int hslot = SCENE::ODD_IDS ? (L.hidx >> 4) : L.hidx;
+    const int hslot = WALK::ODD_IDS ? (L.hidx >> 4) : L.hidx;
     if (was_hit) {
-        rec = shade_rec_load<SCENE::LDS_MATS>(p, hslot);
-        lane_draws<6, SCENE::LDS_MATS>(p, L, u);
+        rec = shade_rec_load<WALK::LDS_RESIDENT>(p, hslot);
+        lane_draws<6, WALK::LDS_RESIDENT>(p, L, u);
     }
     MPT_SEG(pl_trips)            // (the entry of the stage -- reloads of what the traversal loop had parked -- and the issue of its gathers)
     LightHit lit = lights_hit<FEAT>(p, ro, rd);
@@ -52,10 +52,10 @@ DEV int shade_core(const MptRenderParams &p, const SCENE &sc, LaneState &L, Cnt 
         L.depth = 5;                                                         // break, path.py:39
         return SH_END;
     }
-    L.navoid = SCENE::ODD_IDS ? L.hidx : ~L.hidx;
+    L.navoid = WALK::ODD_IDS ? L.hidx : ~L.hidx;
     Hit hit; hit.hit = 1; hit.depth = hdepth; hit.index = hslot; hit.u = L.hu; hit.v = L.hv;
     V3 normal; Disney mat;
-    get_geometries_rec<FEAT>(p, sc, rec, hit, ro, rd, &hitpos, &normal, mat);
+    get_geometries_rec<FEAT>(p, w, rec, hit, ro, rd, &hitpos, &normal, mat);
     if (COUNT) { cnt.n_shade++; cnt.n_draws += 6; }
     float sign = -dot(rd, normal);                                           // path.py:44-46 (never negative)
     if (sign < 0.0f) normal = -normal;
@@ -198,15 +198,15 @@ struct WorkQueue {
 // One issued LEAF step of the traversal loop for the lanes that are ready for it: its counter, the optional histogram, the step.
 // (The NODE body is still written out at its two places in trace_stream: as a function of its own it compiled to the same
 //  instructions in another order in the binary LDS kernel.)
-template <bool COUNT, class SCENE, class STACK>
-DEV void step_leaf(const MptRenderParams &p, const SCENE &sc, STACK &stk, LaneState &L, Cnt &cnt) {
+template <bool COUNT, class WALK>
+DEV void step_leaf(const MptRenderParams &p, const WALK &w, typename WALK::Lifo &stk, LaneState &L, Cnt &cnt) {
     if (COUNT && (threadIdx.x & 63) == 0) cnt.it_leaf++;
     if (COUNT && p.lane_hist) lane_hist_add(p, 1, L.st == ST_LEAF, L.depth, L.shadow);
-    if (L.st == ST_LEAF) stage_leaf<COUNT>(sc, stk, L, cnt);
+    if (L.st == ST_LEAF) stage_leaf<COUNT>(w, stk, L, cnt);
 }
 
-template <bool COUNT, int FEAT, class SCENE, class STACK>
-DEV void trace_stream(const MptRenderParams &p, const SCENE &sc, STACK stk, WorkQueue wq, Cnt &cnt,
+template <bool COUNT, int FEAT, class WALK>
+DEV void trace_stream(const MptRenderParams &p, const WALK &w, typename WALK::Lifo stk, WorkQueue wq, Cnt &cnt,
                       unsigned long long *tl = nullptr) {
     // work-item tiles are 2^tw_shift x 2^th_shift pixels (8x8 by default; smaller tiles shorten the
     // end-of-launch skew between waves at the price of primary-ray coherence)
@@ -257,40 +257,40 @@ DEV void trace_stream(const MptRenderParams &p, const SCENE &sc, STACK stk, Work
             if (cn * MPT_PREF_NODE >= cl * MPT_PREF_LEAF) {
                 if (COUNT && (threadIdx.x & 63) == 0) cnt.it_node++;
                 if (COUNT && p.lane_hist) lane_hist_add(p, 0, L.st == ST_NODE, L.depth, L.shadow);
-                if constexpr (!STACK::ODD_IDS) { if (COUNT && p.lane_hist) node_id_hist_add(p, L.st == ST_NODE, L.curr); }
+                if constexpr (!WALK::ODD_IDS) { if (COUNT && p.lane_hist) node_id_hist_add(p, L.st == ST_NODE, L.curr); }
                 if (L.st == ST_NODE) {
-                    if constexpr (SCENE::WIDE) stage_node4<COUNT>(sc, stk, L, cnt);
-                    else stage_node<COUNT>(sc, stk, L, cnt);
+                    if constexpr (WALK::WIDE) stage_node4<COUNT>(w, stk, L, cnt);
+                    else stage_node<COUNT>(w, stk, L, cnt);
                 }
                 // further steps for the lanes that are still at a node, without counting again: the three ballots
                 // and the decision chain in front of every step cost a wave about as many cycles as half a step.
                 // (Measured and not kept, tools/scratch/r05_node_prefetch_attempt.patch: the second step's node record asked for
                 //  the moment the first knows where the lane goes, before its pushes and the ballot in between: +1.6 % per launch.)
 #pragma unroll
-                for (int rep = 0; rep < SCENE::NODE_REP; rep++) {
+                for (int rep = 0; rep < WALK::NODE_REP; rep++) {
                     if (__ballot(L.st == ST_NODE) == 0ull) break;
                     if (COUNT && (threadIdx.x & 63) == 0) cnt.it_node++;
                     if (COUNT && p.lane_hist) lane_hist_add(p, 0, L.st == ST_NODE, L.depth, L.shadow);
-                    if constexpr (!STACK::ODD_IDS) { if (COUNT && p.lane_hist) node_id_hist_add(p, L.st == ST_NODE, L.curr); }
+                    if constexpr (!WALK::ODD_IDS) { if (COUNT && p.lane_hist) node_id_hist_add(p, L.st == ST_NODE, L.curr); }
                     if (L.st == ST_NODE) {
-                        if constexpr (SCENE::WIDE) stage_node4<COUNT>(sc, stk, L, cnt);
-                        else stage_node<COUNT>(sc, stk, L, cnt);
+                        if constexpr (WALK::WIDE) stage_node4<COUNT>(w, stk, L, cnt);
+                        else stage_node<COUNT>(w, stk, L, cnt);
                     }
                 }
                 MPT_STAMP_END(acc_node)
             } else {
-                step_leaf<COUNT>(p, sc, stk, L, cnt);
+                step_leaf<COUNT>(p, w, stk, L, cnt);
 #pragma unroll
-                for (int rep = 0; rep < SCENE::LEAF_REP; rep++) {
+                for (int rep = 0; rep < WALK::LEAF_REP; rep++) {
                     if (__ballot(L.st == ST_LEAF) == 0ull) break;
-                    step_leaf<COUNT>(p, sc, stk, L, cnt);
+                    step_leaf<COUNT>(p, w, stk, L, cnt);
                 }
                 MPT_STAMP_END(acc_leaf)
             }
         }
         // ---- shading mode
         bool shade_now = wave_count(L.st == ST_DONE && !L.shadow) != 0;
-        if constexpr (SCENE::SHADE_MIN > 0) {
+        if constexpr (WALK::SHADE_MIN > 0) {
             // SHADE costs a wave the same whatever the number of lanes in it (8 400 cycles; a NODE step 575): with fewer than
             // SHADE_MIN lanes waiting for it, and other lanes still traversing, the pass serves the cheap stages only and the
             // lanes wait for company (they are left out of the traversal loop's leave test meanwhile).  LDS-resident kernel:
@@ -298,7 +298,7 @@ DEV void trace_stream(const MptRenderParams &p, const SCENE &sc, STACK stk, Work
             // an idle lane with it, lose 5-14 % and keep SHADE_MIN = 0.
             const int ns = wave_count(L.st == ST_DONE && !L.shadow);
             const int ntrav = wave_count(L.st == ST_NODE || L.st == ST_LEAF);
-            shade_now = ns != 0 && (ns >= SCENE::SHADE_MIN || ns * 2 >= 64 - ndead || ntrav == 0);
+            shade_now = ns != 0 && (ns >= WALK::SHADE_MIN || ns * 2 >= 64 - ndead || ntrav == 0);
             deferred = shade_now ? 0 : ns;
         }
         if (shade_now) {
@@ -308,7 +308,7 @@ DEV void trace_stream(const MptRenderParams &p, const SCENE &sc, STACK stk, Work
             if (L.st == ST_DONE && !L.shadow) {
                 V3 hitpos, sdir;
                 float sdis;
-                const int nk = shade_core<COUNT, FEAT>(p, sc, L, cnt, hitpos, sdir, sdis);
+                const int nk = shade_core<COUNT, FEAT>(p, w, L, cnt, hitpos, sdir, sdis);
                 L.to = hitpos;
                 if (nk == SH_SHADOW) { L.td = sdir; L.tbest = sdis; L.st = ST_SHADOW; }
                 else L.st = ST_BOUNCE;                                       // SH_END: depth is 5, the sample is stored below
@@ -385,7 +385,7 @@ DEV void trace_stream(const MptRenderParams &p, const SCENE &sc, STACK stk, Work
         MPT_STAMP_END(acc_new)
         {
             MPT_STAMP_BEGIN
-            if (L.st == ST_BOUNCE || L.st == ST_SHADOW) lane_begin_ray<COUNT>(p, L, stk, cnt);
+            if (L.st == ST_BOUNCE || L.st == ST_SHADOW) lane_begin_ray<COUNT, WALK>(p, L, stk, cnt);
             MPT_STAMP_END(acc_sdone)
         }
         if (ndead == 64) break;
