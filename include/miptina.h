@@ -250,6 +250,72 @@ int mpt_get_denoised(mpt_ctx *ctx, const mpt_denoise_params *params /* NULL = th
 /* HIP-event time (ms) of the filter's kernels (prologue to epilogue) of the mpt_get_denoised calls since the last call, and their count */
 int mpt_denoise_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
 
+/* The film as a screen, a PNG or a viewport wants it: metered, tone-mapped, transfer-encoded, dithered and quantised to 8-bit RGBA on
+ * the device, a quarter of mpt_get_image's bytes (no reference counterpart: its scripts end in ti.imshow of linear radiance; the
+ * operator it sketched and never wired in is ptina/wip/tonemapping.py:15-18).  With F the raw accumulators of the source (film index
+ * x*ny + y), f32 arithmetic without contraction unless said otherwise:
+ *   valid(p) = F.w != 0
+ *   c = F.rgb / F.w                              (source = a film pass)
+ *       or the denoised colour, exactly the floats mpt_get_denoised would return          (source = MPT_DISPLAY_DENOISED)
+ *   c = fminf(fmaxf(c, 0), 3.0e38f) per channel  (fmaxf's NaN rule: NaN -> 0; -x -> 0; +inf -> 3e38)
+ *   Y = (0.2126 r + 0.7152 g) + 0.0722 b
+ *   metering over the valid pixels, N of them:
+ *       Lavg = exp((1/N) sum log(1e-4 + Y))      (1e-4 + Y in f32; the logarithms, their sum, the mean, the exponential and the
+ *                                                 division into `key` in f64, E rounded to f32 once: neither a rounded log nor
+ *                                                 the order of the sum then reaches an f32 ulp)
+ *       E = exposure if exposure > 0;  key / Lavg if exposure == 0 (auto);  1 if auto and N == 0
+ *   v = fminf(E c, 1e18f) per channel            (every operator has saturated long before; keeps v v finite)
+ *       MPT_TONE_LINEAR    t = v
+ *       MPT_TONE_PTINA     t = v / (v + 0.155) * 1.019                                    (ptina/wip/tonemapping.py:15-18)
+ *       MPT_TONE_REINHARD  t = v (1 + v / white^2) / (1 + v)
+ *       MPT_TONE_ACES      t = v (2.51 v + 0.03) / (v (2.43 v + 0.59) + 0.14)
+ *   t = fminf(fmaxf(t, 0), 1)
+ *       MPT_TRANSFER_SRGB  s = t <= 0.0031308 ? 12.92 t : 1.055 t^(1/2.4) - 0.055
+ *       MPT_TRANSFER_GAMMA s = t^(1/gamma)
+ *   byte = clamp(floor(255 s + B), 0, 255);  B = 0.5 without dither, (M(x, y) + 0.5) / 64 with it, M the 8x8 Bayer index of
+ *       (x & 7, y & 7): M = sum over i = 0..2 of (((x^y) >> i) & 1) << (2(2-i)+1) | ((y >> i) & 1) << (2(2-i))   (its 2x2 corner
+ *       is [[0,2],[3,1]])
+ *   alpha = 255;  a pixel that is not valid = the bytes (230, 102, 230, 0), mpt_get_image's marker at 8 bits, whatever the parameters.
+ * op = PTINA, exposure = 0.3, transfer = GAMMA, gamma = 2.2 is the reference's functor as written.
+ * Layouts: MPT_LAYOUT_FILM is [nx][ny][4] u8, x-major like mpt_get_image; MPT_LAYOUT_DISPLAY is [ny][nx][4] with rows top-down --
+ * pixel (x, y) at ((ny-1-y) nx + x) 4 -- what a PNG or a GL blit reads (numpy: swapaxes(film layout, 0, 1)[::-1]).
+ * The metering is a two-stage sum whose shape depends on nx*ny alone and uses no atomics: the exposure and every byte repeat bit
+ * for bit; a manual exposure skips it.  Like mpt_get_denoised the call flushes what is enqueued, reads whatever film the context
+ * holds, writes no film pass, neither uses nor disturbs an mpt_hint_image hint, and treats columns a slab or stripe split did not
+ * render as not valid (in the bytes and in the metering).  Into an mpt_host_alloc array the conversion writes the bytes straight
+ * over PCIe when option "zero_copy" is 1.  Fails, the film untouched, for an unknown op / transfer / layout, a pass out of range, a
+ * null `out`, an exposure that is negative or not finite, and a key, white or gamma that is not finite and positive. */
+#define MPT_DISPLAY_DENOISED (-1)
+#define MPT_TONE_LINEAR   0
+#define MPT_TONE_PTINA    1
+#define MPT_TONE_REINHARD 2
+#define MPT_TONE_ACES     3
+#define MPT_TRANSFER_SRGB  0
+#define MPT_TRANSFER_GAMMA 1
+#define MPT_LAYOUT_FILM    0
+#define MPT_LAYOUT_DISPLAY 1
+typedef struct {
+    int32_t source;     /* 0..max_filmpasses-1 = that film pass; MPT_DISPLAY_DENOISED = pass 0 through the filter; default 0 */
+    int32_t op;         /* MPT_TONE_*;      default ACES */
+    int32_t transfer;   /* MPT_TRANSFER_*;  default SRGB */
+    int32_t layout;     /* MPT_LAYOUT_*;    default FILM */
+    int32_t dither;     /* default 1 */
+    float exposure;     /* 0 = auto (default) */
+    float key;          /* 0.18 */
+    float white;        /* 4.0  */
+    float gamma;        /* 2.2  */
+} mpt_display_params;
+int mpt_get_display(mpt_ctx *ctx, const mpt_display_params *params /* NULL = the defaults above */,
+                    const mpt_denoise_params *denoise /* used when source is denoised; NULL = its defaults */,
+                    uint8_t *out /* [nx][ny][4] or [ny][nx][4] */, float *exposure_used /* may be NULL */);
+/* HIP-event time (ms) of the kernels (the filter's for a denoised source, metering, conversion) of the mpt_get_display calls since the
+ * last call, and their count */
+int mpt_display_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
+/* Test door in the mpt_unit_eval / mpt_comm_selftest idiom: the SAME metering and conversion kernels on a caller-supplied accumulator
+ * array raw[nx*ny][4], any nx, ny >= 1 with nx*ny <= max_filmsize; touches no film pass (params->source is ignored) */
+int mpt_display_eval(mpt_ctx *ctx, const mpt_display_params *params, const float *raw, int nx, int ny,
+                     uint8_t *out, float *exposure_used);
+
 /* Page-locked host buffers for the read-backs above: into such a buffer mpt_get_image /
  * mpt_fast_export_image / mpt_get_film_raw are one DMA; any other buffer is served through a
  * page-locked staging copy.  (The reference's get_image returns a fresh numpy array,

@@ -42,6 +42,18 @@ class DenoiseParams(C.Structure):
                 ('demodulate', C.c_int32)]
 
 
+class DisplayParams(C.Structure):
+    '''mpt_display_params (include/miptina.h): what FilmTable.get_display hands to mpt_get_display'''
+    _fields_ = [('source', C.c_int32), ('op', C.c_int32), ('transfer', C.c_int32), ('layout', C.c_int32), ('dither', C.c_int32),
+                ('exposure', C.c_float), ('key', C.c_float), ('white', C.c_float), ('gamma', C.c_float)]
+
+
+DISPLAY_DENOISED = -1
+TONE_OPS = {'linear': 0, 'ptina': 1, 'reinhard': 2, 'aces': 3}
+TRANSFERS = {'srgb': 0, 'gamma': 1}
+LAYOUTS = {'film': 0, 'display': 1}
+
+
 class Counters(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in
                 ('samples', 'rays', 'n_box', 'n_tri', 'n_shade', 'n_draws', 'bounces', 'n_node',
@@ -103,6 +115,9 @@ SIGNATURES = {
     'mpt_resolve': (_i, [_vp, _i]),
     'mpt_get_denoised': (_i, [_vp, C.POINTER(DenoiseParams), _fp]),
     'mpt_denoise_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_get_display': (_i, [_vp, C.POINTER(DisplayParams), C.POINTER(DenoiseParams), C.POINTER(C.c_uint8), _fp]),
+    'mpt_display_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_display_eval': (_i, [_vp, C.POINTER(DisplayParams), _fp, _i, _i, C.POINTER(C.c_uint8), _fp]),
     'mpt_host_alloc': (_vp, [C.c_size_t]),
     'mpt_host_free': (None, [_vp]),
     'mpt_get_counters': (_i, [_vp, C.POINTER(Counters)]),
@@ -191,6 +206,19 @@ def host_array(shape, dtype=np.float32):
     return np.frombuffer(buf, dtype=dtype, count=count).reshape(shape)
 
 
+def display_params(source=0, op='aces', transfer='srgb', layout='film', dither=True, exposure=None, key=0.18, white=4.0, gamma=2.2):
+    '''DisplayParams from the names FilmTable.get_display takes (an integer is passed through, so that a test can name an
+    operator the library does not know); exposure None = auto'''
+    def code(table, v, what):
+        if isinstance(v, str):
+            if v.lower() not in table:
+                raise ValueError('unknown %s %r: one of %s' % (what, v, sorted(table)))
+            return table[v.lower()]
+        return int(v)
+    return DisplayParams(int(source), code(TONE_OPS, op, 'op'), code(TRANSFERS, transfer, 'transfer'), code(LAYOUTS, layout, 'layout'),
+                         1 if dither else 0, 0.0 if exposure is None else float(exposure), float(key), float(white), float(gamma))
+
+
 def fptr(a):
     return a.ctypes.data_as(_fp)
 
@@ -267,6 +295,18 @@ class Context:
         out = np.zeros((a.shape[0], nout), dt)
         self.call('mpt_unit_eval', kind, a.ctypes.data_as(C.c_void_p), nin, out.ctypes.data_as(C.c_void_p), nout, a.shape[0])
         return out
+
+    def display_eval(self, raw, nx, ny, **kw):
+        '''test door (mpt_display_eval): get_display's metering and conversion kernels on the accumulators raw [nx*ny][4]; the
+        keywords of display_params; returns (uint8 [nx, ny, 4] or, for layout='display', [ny, nx, 4]; the exposure used)'''
+        p = display_params(**kw)
+        a = np.ascontiguousarray(np.asarray(raw, np.float32).reshape(-1, 4))
+        if a.shape[0] != int(nx) * int(ny):
+            raise ValueError('raw holds %d accumulators, the film %dx%d' % (a.shape[0], nx, ny))
+        out = np.zeros((ny, nx, 4) if p.layout == LAYOUTS['display'] else (nx, ny, 4), np.uint8)
+        used = C.c_float(0)
+        self.call('mpt_display_eval', C.byref(p), fptr(a), int(nx), int(ny), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(used))
+        return out, np.float32(used.value)
 
     def counters(self):
         cnt = Counters()

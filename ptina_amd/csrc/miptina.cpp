@@ -161,6 +161,11 @@ extern "C" mpt_ctx *mpt_create(const mpt_caps *caps, int device) {
             hipHostGetDevicePointer(&dm, c->h_sahmeta, 0) != hipSuccess) return bail("pinned build mailbox");
         c->d_sahmeta = (int *)dm;
         memset(c->h_sahmeta, 0, 32 * sizeof(int));
+        void *de = nullptr;
+        if (c->h_exposure.reserve(1, hipHostMallocMapped) ||
+            hipHostGetDevicePointer(&de, c->h_exposure, 0) != hipSuccess) return bail("pinned exposure word");
+        *c->h_exposure = 1.0f;
+        c->d_exposure = (float *)de;
     }
     hipMemsetAsync(c->d_counters, 0, MPT_COUNTER_WORDS * sizeof(unsigned long long), c->stream);
     hipMemsetAsync(c->d_work, 0, MPT_QUEUE_WORDS * sizeof(unsigned int), c->stream);
@@ -207,7 +212,7 @@ extern "C" void mpt_destroy(mpt_ctx *c) {
     }
     if (c->ev_main) hipEventDestroy(c->ev_main);
     if (c->ev_film) hipEventDestroy(c->ev_film);
-    for (MptLaunchTimer *t : { &c->render_timer, &c->mlt_timer, &c->brute_timer, &c->denoise_timer })
+    for (MptLaunchTimer *t : { &c->render_timer, &c->mlt_timer, &c->brute_timer, &c->denoise_timer, &c->display_timer })
         for (auto &ev : t->events) hipEventDestroy(ev);
     for (auto &ev : c->event_pool) hipEventDestroy(ev);
     if (c->stream) hipStreamDestroy(c->stream);
@@ -1458,36 +1463,51 @@ extern "C" int mpt_get_film_raw(mpt_ctx *c, int pass, float *out) {
 // Film pass 0 filtered by the edge-avoiding A-Trous wavelet, guided by passes 1 and 2, read back like mpt_get_image.  Runs on the
 // main stream behind everything enqueued (the flush makes that stream wait for the render launches, as for mpt_get_film_raw);
 // reads the three passes, writes only the context's working buffers, and knows nothing of mpt_hint_image's array.
-extern "C" int mpt_get_denoised(mpt_ctx *c, const mpt_denoise_params *params, float *out) {
-    if (use_ro(c)) return 1;
-    mpt_denoise_params p = { 5, 1.0f, 0.1f, 0.3f, 1 };
+static int denoise_params(const mpt_denoise_params *params, mpt_denoise_params &p) {
+    p = { 5, 1.0f, 0.1f, 0.3f, 1 };
     if (params) p = *params;
-    if (!out) return fail("mpt_get_denoised: null output");
     if (p.iterations < 0 || p.iterations > 8) return fail("denoise: iterations must be in 0..8, got %d", p.iterations);
     const struct { const char *name; float v; } sig[3] = { { "sigma_color", p.sigma_color }, { "sigma_albedo", p.sigma_albedo }, { "sigma_normal", p.sigma_normal } };
     for (const auto &s : sig)
         if (!(std::isfinite(s.v) && s.v > 0.0f)) return fail("denoise: %s must be finite and positive, got %g", s.name, (double)s.v);
-    if (mpt_flush(c)) return 1;
-    if (check_pass(c, 0)) return 1;
+    return 0;
+}
+
+// the filter's launches on the main stream (mpt_get_denoised and mpt_get_display's denoised source); *img = the working buffer that
+// holds the image behind them
+static int denoise_launches(mpt_ctx *c, const mpt_denoise_params &p, const MptVec4 **img) {
     const size_t npix = (size_t)c->nx * c->ny;
-    const MptVec4 *img = c->fb.dn_e[0];
-    hipEvent_t e0 = get_event(c), e1 = get_event(c);
-    HIP_TRY(hipEventRecord(e0, c->stream));
     if (p.iterations == 0) {
         // nothing to filter: the resolve pass itself, so that the image is mpt_get_image(0)'s bit for bit
         HIP_TRY(mpt_launch_resolve(c->fb.film[0], c->fb.dn_e[0], npix, c->stream));
-    } else {
-        HIP_TRY(mpt_launch_denoise_prologue(c->fb.film[0], c->fb.film[1], c->fb.film[2], c->fb.dn_e[0], c->fb.dn_a, c->fb.dn_n, npix, p.demodulate ? 1 : 0, c->stream));
-        const float ka = 1.0f / (p.sigma_albedo * p.sigma_albedo), kn = 1.0f / (p.sigma_normal * p.sigma_normal);
-        for (int i = 0; i < p.iterations; i++) {
-            const float sc = p.sigma_color * std::ldexp(1.0f, -i);             // the colour edge-stopping narrows as the stencil widens
-            HIP_TRY(mpt_launch_denoise_atrous(c->fb.dn_e[i & 1], c->fb.dn_e[(i + 1) & 1], c->fb.dn_a, c->fb.dn_n, c->nx, c->ny, 1 << i,
-                                              1.0f / (sc * sc), ka, kn, c->denoise_lds, c->stream));
-        }
-        const int last = p.iterations & 1;
-        HIP_TRY(mpt_launch_denoise_epilogue(c->fb.dn_e[last], c->fb.dn_a, c->fb.dn_e[last ^ 1], npix, p.demodulate ? 1 : 0, c->stream));
-        img = c->fb.dn_e[last ^ 1];
+        *img = c->fb.dn_e[0];
+        return 0;
     }
+    HIP_TRY(mpt_launch_denoise_prologue(c->fb.film[0], c->fb.film[1], c->fb.film[2], c->fb.dn_e[0], c->fb.dn_a, c->fb.dn_n, npix, p.demodulate ? 1 : 0, c->stream));
+    const float ka = 1.0f / (p.sigma_albedo * p.sigma_albedo), kn = 1.0f / (p.sigma_normal * p.sigma_normal);
+    for (int i = 0; i < p.iterations; i++) {
+        const float sc = p.sigma_color * std::ldexp(1.0f, -i);             // the colour edge-stopping narrows as the stencil widens
+        HIP_TRY(mpt_launch_denoise_atrous(c->fb.dn_e[i & 1], c->fb.dn_e[(i + 1) & 1], c->fb.dn_a, c->fb.dn_n, c->nx, c->ny, 1 << i,
+                                          1.0f / (sc * sc), ka, kn, c->denoise_lds, c->stream));
+    }
+    const int last = p.iterations & 1;
+    HIP_TRY(mpt_launch_denoise_epilogue(c->fb.dn_e[last], c->fb.dn_a, c->fb.dn_e[last ^ 1], npix, p.demodulate ? 1 : 0, c->stream));
+    *img = c->fb.dn_e[last ^ 1];
+    return 0;
+}
+
+extern "C" int mpt_get_denoised(mpt_ctx *c, const mpt_denoise_params *params, float *out) {
+    if (use_ro(c)) return 1;
+    mpt_denoise_params p;
+    if (!out) return fail("mpt_get_denoised: null output");
+    if (denoise_params(params, p)) return 1;
+    if (mpt_flush(c)) return 1;
+    if (check_pass(c, 0)) return 1;
+    const size_t npix = (size_t)c->nx * c->ny;
+    const MptVec4 *img = nullptr;
+    hipEvent_t e0 = get_event(c), e1 = get_event(c);
+    HIP_TRY(hipEventRecord(e0, c->stream));
+    if (denoise_launches(c, p, &img)) return 1;
     HIP_TRY(hipEventRecord(e1, c->stream));
     c->denoise_timer.record({ e0, e1 }, c->event_pool);
     if (read_back(c, out, img, npix * sizeof(MptVec4))) return 1;
@@ -1502,6 +1522,100 @@ extern "C" int mpt_denoise_kernel_time(mpt_ctx *c, double *ms, int *launches) {
     if (c->denoise_timer.drain(&total, launches, c->event_pool)) return 1;
     if (ms) *ms = total;
     return 0;
+}
+
+// ------------------------------------------------------------------ 8-bit display read-back (display.hip)
+// The source tone-mapped, transfer-encoded, dithered and packed to RGBA8 on the device, read back like mpt_get_image: straight into an
+// mpt_host_alloc array through its mapped pointer (option "zero_copy"), else into the film owner's image and one copy.  On the main
+// stream behind everything enqueued, like mpt_get_denoised; reads film passes, writes only the context's working buffers.
+static int display_params(const mpt_display_params *params, mpt_display_params &p, MptDisplayArgs &a) {
+    p = { 0, MPT_TONE_ACES, MPT_TRANSFER_SRGB, MPT_LAYOUT_FILM, 1, 0.0f, 0.18f, 4.0f, 2.2f };
+    if (params) p = *params;
+    if (p.op < MPT_TONE_LINEAR || p.op > MPT_TONE_ACES) return fail("display: unknown op %d", p.op);
+    if (p.transfer != MPT_TRANSFER_SRGB && p.transfer != MPT_TRANSFER_GAMMA) return fail("display: unknown transfer %d", p.transfer);
+    if (p.layout != MPT_LAYOUT_FILM && p.layout != MPT_LAYOUT_DISPLAY) return fail("display: unknown layout %d", p.layout);
+    if (!(std::isfinite(p.exposure) && p.exposure >= 0.0f)) return fail("display: exposure must be finite and not negative (0 = auto), got %g", (double)p.exposure);
+    const struct { const char *name; float v; } pos[3] = { { "key", p.key }, { "white", p.white }, { "gamma", p.gamma } };
+    for (const auto &s : pos)
+        if (!(std::isfinite(s.v) && s.v > 0.0f)) return fail("display: %s must be finite and positive, got %g", s.name, (double)s.v);
+    a = { p.op, p.transfer, p.layout, p.dither ? 1 : 0, p.exposure, p.white * p.white, 1.0f / p.gamma };
+    return 0;
+}
+
+// metering (auto exposure only) and conversion of `src` [nx*ny] into `dst` on the main stream; `dst` may be a mapped host pointer
+static int display_launches(mpt_ctx *c, const mpt_display_params &p, const MptDisplayArgs &a, const MptVec4 *src, int nx, int ny,
+                            MptDisplayBufs &b, uint32_t *dst) {
+    const float *e_dev = nullptr;
+    if (p.exposure == 0.0f) {
+        HIP_TRY(mpt_launch_display_meter(src, (size_t)nx * ny, b.part, p.key, b.exposure, c->d_exposure, c->stream));
+        e_dev = b.exposure;
+    }
+    HIP_TRY(mpt_launch_display_convert(src, dst, nx, ny, &a, e_dev, c->stream));
+    return 0;
+}
+
+// the bytes to the caller (zero-copy: they are there once the stream is idle) and the exposure used
+static int display_finish(mpt_ctx *c, const mpt_display_params &p, bool direct, uint8_t *out, const uint32_t *dev, size_t npix, float *exposure_used) {
+    if (direct) HIP_TRY(hipStreamSynchronize(c->stream));
+    else if (read_back(c, out, dev, npix * 4)) return 1;
+    if (exposure_used) *exposure_used = p.exposure == 0.0f ? *(volatile float *)c->h_exposure.p : p.exposure;
+    return 0;
+}
+
+extern "C" int mpt_get_display(mpt_ctx *c, const mpt_display_params *params, const mpt_denoise_params *denoise, uint8_t *out, float *exposure_used) {
+    if (use_ro(c)) return 1;
+    mpt_display_params p;
+    MptDisplayArgs a;
+    mpt_denoise_params dp;
+    if (!out) return fail("mpt_get_display: null output");
+    if (display_params(params, p, a)) return 1;
+    const bool denoised = p.source == MPT_DISPLAY_DENOISED;
+    if (!denoised && (p.source < 0 || p.source >= 3)) return fail("display: film pass %d out of range", p.source);
+    if (denoised && denoise_params(denoise, dp)) return 1;
+    if (mpt_flush(c)) return 1;
+    if (check_pass(c, denoised ? 0 : p.source)) return 1;
+    const size_t npix = (size_t)c->nx * c->ny;
+    void *mapped = nullptr;
+    const bool direct = c->zero_copy && is_locked_range(out, npix * 4) && hipHostGetDevicePointer(&mapped, out, 0) == hipSuccess && mapped;
+    const MptVec4 *src = denoised ? nullptr : c->fb.film[p.source].p;
+    hipEvent_t e0 = get_event(c), e1 = get_event(c);
+    HIP_TRY(hipEventRecord(e0, c->stream));
+    if (denoised && denoise_launches(c, dp, &src)) return 1;       // the float image stays on the device
+    if (display_launches(c, p, a, src, c->nx, c->ny, c->fb.disp, direct ? (uint32_t *)mapped : c->fb.disp.rgba8.p)) return 1;
+    HIP_TRY(hipEventRecord(e1, c->stream));
+    c->display_timer.record({ e0, e1 }, c->event_pool);
+    if (display_finish(c, p, direct, out, c->fb.disp.rgba8, npix, exposure_used)) return 1;
+    return check_watchdog(c);
+}
+
+extern "C" int mpt_display_kernel_time(mpt_ctx *c, double *ms, int *launches) {
+    if (use_ro(c)) return 1;
+    if (mpt_flush(c)) return 1;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    double total = 0;
+    if (c->display_timer.drain(&total, launches, c->event_pool)) return 1;
+    if (ms) *ms = total;
+    return 0;
+}
+
+// test door: the same launches on the caller's accumulators, in buffers of its own (no film pass, no film-owner buffer is touched)
+extern "C" int mpt_display_eval(mpt_ctx *c, const mpt_display_params *params, const float *raw, int nx, int ny, uint8_t *out, float *exposure_used) {
+    if (use_ro(c)) return 1;
+    mpt_display_params p;
+    MptDisplayArgs a;
+    if (!out || !raw) return fail("mpt_display_eval: null %s", out ? "input" : "output");
+    if (display_params(params, p, a)) return 1;
+    if (nx < 1 || ny < 1 || (long long)nx * ny > (long long)c->caps.max_filmsize)
+        return fail("mpt_display_eval: film %dx%d outside 1 .. max_filmsize=%d pixels", nx, ny, c->caps.max_filmsize);
+    const size_t npix = (size_t)nx * ny;
+    if (npix > c->door_raw.cap || npix > c->door_disp.cap) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->door_raw.reserve(npix) || c->door_disp.reserve(npix)) return 1;
+    }
+    HIP_TRY(hipMemcpyAsync(c->door_raw, raw, npix * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                      // (`raw` is pageable: the copy is staged, the caller's array is free again)
+    if (display_launches(c, p, a, c->door_raw, nx, ny, c->door_disp, c->door_disp.rgba8)) return 1;
+    return display_finish(c, p, false, out, c->door_disp.rgba8, npix, exposure_used);
 }
 
 // ------------------------------------------------------------------ measurement

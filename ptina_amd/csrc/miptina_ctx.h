@@ -60,6 +60,11 @@ MPT_KERNEL_API hipError_t mpt_launch_denoise_prologue(const MptVec4 *f0, const M
 MPT_KERNEL_API hipError_t mpt_launch_denoise_atrous(const MptVec4 *e_in, MptVec4 *e_out, const MptVec4 *a, const MptVec4 *n, int nx, int ny,
                                                     int s, float kc, float ka, float kn, int use_lds, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_denoise_epilogue(const MptVec4 *e, const MptVec4 *a, MptVec4 *out, size_t npix, int demodulate, hipStream_t);
+// display.hip: metering and the conversion to 8-bit RGBA (mpt_get_display); part holds 2 * mpt_display_parts(npix) doubles
+MPT_KERNEL_API size_t mpt_display_parts(size_t npix);
+MPT_KERNEL_API hipError_t mpt_launch_display_meter(const MptVec4 *src, size_t npix, double *part, float key, float *e_dev, float *e_host, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_launch_display_convert(const MptVec4 *src, uint32_t *out, int nx, int ny, const MptDisplayArgs *a,
+                                                     const float *e_dev /* NULL: a->exposure */, hipStream_t);
 
 // on-GPU LBVH build (lbvh_build.hip)
 struct MptLbvhBuffers {
@@ -147,6 +152,21 @@ struct PinnedBuf {
 
 // Buffers that are sized together share one capacity and one reserve(): everything is freed, then allocated in the order
 // written; `cap` is set only when all of it is there.
+struct MPT_INTERNAL MptDisplayBufs {       // what mpt_get_display's kernels write, for a film of up to `cap` pixels
+    DevBuf<uint32_t> rgba8;              // the packed image
+    DevBuf<double> part;                 // the metering's partial sums: (sum, count) per workgroup of the first stage
+    DevBuf<float> exposure;              // the metered exposure, where the conversion reads it
+    size_t cap = 0;
+    void release() { rgba8.release(); part.release(); exposure.release(); cap = 0; }
+    int reserve(size_t npix) {
+        if (npix <= cap) return 0;
+        release();
+        if (rgba8.reserve(npix) || part.reserve(2 * std::max<size_t>(mpt_display_parts(npix), 1)) || exposure.reserve(1)) return 1;
+        cap = npix;
+        return 0;
+    }
+};
+
 struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set so far
     DevBuf<MptVec4> film[3];
     DevBuf<MptVec4> resolved;            // nx*ny float4 (get_image staging on device)
@@ -154,6 +174,7 @@ struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set 
     // mpt_get_denoised's working buffers, nx*ny float4 each: the filtered colour e (rgb, valid flag) in two copies the
     // iterations alternate between (the one left over takes the image), and the guides a (albedo) and n (normal)
     DevBuf<MptVec4> dn_e[2], dn_a, dn_n;
+    MptDisplayBufs disp;                 // mpt_get_display's 8-bit image and metering partials
     size_t cap = 0;
     int reserve(size_t npix, hipStream_t stream) {     // the passes come back zeroed on `stream`
         if (npix <= cap) return 0;
@@ -161,6 +182,7 @@ struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set 
         for (auto &b : film) b.release();
         resolved.release(); exported.release();
         for (DevBuf<MptVec4> *b : { &dn_e[0], &dn_e[1], &dn_a, &dn_n }) b->release();
+        disp.release();
         for (auto &b : film) {
             if (b.reserve(npix)) return 1;
             HIP_TRY(hipMemsetAsync(b, 0, npix * sizeof(MptVec4), stream));
@@ -168,6 +190,7 @@ struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set 
         if (resolved.reserve(npix) || exported.reserve(npix * 3)) return 1;
         for (DevBuf<MptVec4> *b : { &dn_e[0], &dn_e[1], &dn_a, &dn_n })
             if (b->reserve(npix)) return 1;
+        if (disp.reserve(npix)) return 1;
         cap = npix;
         return 0;
     }
@@ -414,6 +437,9 @@ struct mpt_ctx {
     MptLaunchTimer mlt_timer{3};                         // {chain start, chain end = splat start, splat end} per launch
     MptLaunchTimer denoise_timer{2};                     // mpt_get_denoised: {before the prologue, after the epilogue} per call
     MptLaunchTimer brute_timer{2};                       // brute-force engine: {kernel start, kernel end} per launch
+    MptLaunchTimer display_timer{2};                     // mpt_get_display: {before the first kernel, after the conversion} per call
+    PinnedBuf<float> h_exposure; float *d_exposure = nullptr;   // host-pinned, device-mapped: the metered exposure of the last mpt_get_display / mpt_display_eval
+    DevBuf<MptVec4> door_raw; MptDisplayBufs door_disp;  // mpt_display_eval: the caller's accumulators and what the kernels write for them (grown on demand)
     // command batching
     int pending = 0;
 

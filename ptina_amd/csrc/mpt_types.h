@@ -176,3 +176,10 @@ struct MptMltArgs {
     uint32_t seed;
     float lsp, sigma;                        // MLTPathEngine.LSP / Sigma
 };
+
+// one conversion launch of mpt_get_display (display.hip): mpt_display_params as the kernels take it
+struct MptDisplayArgs {
+    int32_t op, transfer, layout, dither;    // MPT_TONE_*, MPT_TRANSFER_*, MPT_LAYOUT_* of include/miptina.h
+    float exposure;                          // a manual exposure (the metered one is read from the device)
+    float white2, inv_gamma;                 // white * white and 1 / gamma, in f32
+};

@@ -16,6 +16,7 @@ class FilmTable(metaclass=Singleton):
         self.count = count
         self._next = None             # the array the next get_image(0) will return, already known to the library (_hint)
         self._size = None
+        self.last_exposure = None     # the exposure the last get_display used (metered, or the one given)
 
     def _res(self):
         # (the size only changes through set_size below: remembered, so that render() / get_image() do not ask the library twice a step)
@@ -91,6 +92,42 @@ class FilmTable(metaclass=Singleton):
         '''(ms, calls): HIP-event time of the filter's kernels in the get_denoised calls since the last call'''
         ms, n = C.c_double(0), C.c_int(0)
         ctx().call('mpt_denoise_kernel_time', C.byref(ms), C.byref(n))
+        return ms.value, n.value
+
+    def get_display(self, id=0, denoised=False, op='aces', transfer='srgb', layout='film', dither=True, exposure=None, key=0.18,
+                    white=4.0, gamma=2.2, **denoise_kw):
+        '''film pass `id` -- or, with denoised=True, pass 0 through get_denoised's filter (its keywords in denoise_kw) -- as a screen
+        or a PNG wants it: metered (exposure=None: log-average luminance to `key`) or exposed by `exposure`, tone-mapped (op: 'linear',
+        'ptina', 'reinhard', 'aces'), transfer-encoded ('srgb', or 'gamma' with `gamma`), ordered-dithered and quantised on the device
+        (mpt_get_display, include/miptina.h).  A fresh page-locked uint8 array: [nx, ny, 4] for layout='film' (indexed like
+        get_image), [ny, nx, 4] with rows top-down for layout='display' (what image.write_png takes).  The exposure used is kept as
+        last_exposure.  No reference counterpart: its scripts show linear radiance (ptina/wip/tonemapping.py was never wired in)'''
+        from ._lib import DenoiseParams, display_params, DISPLAY_DENOISED, LAYOUTS
+        nx, ny = self._res()
+        if not denoised and int(id) < 0:
+            raise RuntimeError('display: film pass %d out of range' % int(id))
+        p = display_params(DISPLAY_DENOISED if denoised else id, op, transfer, layout, dither, exposure, key, white, gamma)
+        dn = None
+        if denoised:
+            d = dict(iterations=5, sigma_color=1.0, sigma_albedo=0.1, sigma_normal=0.3, demodulate=True)
+            unknown = set(denoise_kw) - set(d)
+            if unknown:
+                raise TypeError('get_display: unknown keyword(s) %s' % sorted(unknown))
+            d.update(denoise_kw)
+            dn = C.byref(DenoiseParams(int(d['iterations']), float(d['sigma_color']), float(d['sigma_albedo']), float(d['sigma_normal']),
+                                       1 if d['demodulate'] else 0))
+        elif denoise_kw:
+            raise TypeError('get_display: %s only apply with denoised=True' % sorted(denoise_kw))
+        arr = host_array((ny, nx, 4) if p.layout == LAYOUTS['display'] else (nx, ny, 4), np.uint8)
+        used = C.c_float(0)
+        ctx().call('mpt_get_display', C.byref(p), dn, arr.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(used))
+        self.last_exposure = float(used.value)
+        return arr
+
+    def display_kernel_time(self):
+        '''(ms, calls): HIP-event time of the kernels of the get_display calls since the last call'''
+        ms, n = C.c_double(0), C.c_int(0)
+        ctx().call('mpt_display_kernel_time', C.byref(ms), C.byref(n))
         return ms.value, n.value
 
     def fast_export_image(self, out, id=0):

@@ -69,3 +69,23 @@ class Image:
     @property
     def ny(self):
         return ImagePool().ny(self.id)
+
+
+def write_png(path, rgba8):
+    '''an 8-bit [rows, columns, 4] (RGBA) or [rows, columns, 3] (RGB) array, rows top-down -- FilmTable.get_display(layout='display')
+    -- as a PNG file, with zlib and struct alone (ti.imwrite needs PIL)'''
+    import struct
+    import zlib
+    a = np.ascontiguousarray(rgba8)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError('write_png takes a uint8 array shaped [rows, columns, 3 or 4], got %s %s' % (a.dtype, a.shape))
+    rows, cols, ch = a.shape
+
+    def chunk(tag, data):
+        return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xffffffff)
+    lines = np.empty((rows, 1 + cols * ch), np.uint8)
+    lines[:, 0] = 0                                      # filter type 0 (none) in front of every scanline
+    lines[:, 1:] = a.reshape(rows, cols * ch)
+    head = struct.pack('>IIBBBBB', cols, rows, 8, 6 if ch == 4 else 2, 0, 0, 0)
+    with open(path, 'wb') as f:
+        f.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', head) + chunk(b'IDAT', zlib.compress(lines.tobytes(), 6)) + chunk(b'IEND', b''))

@@ -76,6 +76,12 @@ def get_denoised(**kw):
     return FilmTable().get_denoised(**kw)
 
 
+def get_display(**kw):
+    '''FilmTable().get_display(id=0, denoised=False, op='aces', transfer='srgb', layout='film', dither=True, exposure=None, key=0.18,
+    white=4.0, gamma=2.2, **denoise_kw): the film tone-mapped and quantised to 8-bit RGBA on the device (no reference counterpart)'''
+    return FilmTable().get_display(**kw)
+
+
 def get_size():
     film = FilmTable()
     return film.nx, film.ny
