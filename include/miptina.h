@@ -83,41 +83,102 @@ int  mpt_version(void);
 mpt_ctx *mpt_create(const mpt_caps *caps, int device);
 void mpt_destroy(mpt_ctx *ctx);
 
-/* "mode" (MPT_MODE_*), "batch" (max frames per launch, 1..64), "chunk" (frames per work item,
- * 0 = auto), "count" (1 = accumulate mpt_counters, slower), "lds" (1 = use the LDS-resident
- * persistent kernel when the scene fits a CU's 160 KiB LDS, default; 0 = always gather from HBM/L2),
- * "lds_wide" (what that kernel walks: 1 = the 4-wide nodes with exact boxes, 112 bytes apart in LDS, default -- needs "wide" = 1;
- * 0 = the binary nodes; the same film up to ties between equally distant hits).
- * "tree" (fast build: 1 = SAH re-partition of the LBVH's leaves, default; 0 = walk the LBVH itself;
- * takes effect at the next mpt_build_tree), "tile_w_shift"/"tile_h_shift" (work-item tile 2^w x 2^h pixels),
- * "wide" (scenes that do not fit LDS: 1 = walk the fast tree collapsed into 4-wide nodes, default; 0 = the
- * binary tree), "wide_quant" (1 = the 4-wide nodes as 64-byte records with 8-bit child boxes rounded outwards: four
- * gathers per step, default; 0 = 128-byte records with the exact boxes: seven), "wide_build" (1 = that collapse runs on the
- * device, default; 0 = host pass over downloaded records: same bytes), "sah_build" (where the SAH
- * re-partition runs: 1 = on the device, binned above 32 triangles and exact below; 0 = host pass, exact up to 8192; -1 = auto: the
- * device above 131072 faces, default), "gpu_build" (1 = LBVH built on the device, default), "sah_max" (faces above which the fast build
- * walks the LBVH itself; default 2^22), "grid_div" (each launch takes 1/G of the CUs so that G launches are resident
- * in different phases; 0 = choose by samples per lane, and the whole chip for a launch that finds nothing else in flight: default), "pipe_depth" (batches in flight,
- * 2..6; 0 = auto), "lds_block" (lanes per persistent workgroup of the LDS kernel, diagnostics),
- * "zero_copy" (1, default: mpt_get_image into an mpt_host_alloc array has the resolve pass write the image straight into it over
- * PCIe; 0: device buffer + DMA -- same image, 20 us more per call),
- * "denoise_lds" (1, default: mpt_get_denoised's iterations of stride 1 and 2 filter from a tile held in LDS; 0: every stride gathers
- * from memory -- same image bit for bit),
- * "skip_dark" (1 = a shadow ray whose candidate direct light is exactly zero -- the light behind the surface -- is not traced:
- * adding zero or not is the same sum; 0 = traced like the reference does; -1 = on in the production build, off in the strict build: default),
- * "spin_us" (how long mpt_get_image polls a finalising launch before it blocks; default 20000, 0 = block at once),
- * "finalise" (1, default: a render launch that finds no other launch in flight adds its frames to the film, resolves and
- * writes out finished tiles itself while its last paths drain; 0: always the combine pass after the launch; same film bit for bit),
- * "timeline" (1 = record mpt_get_timeline data), "reserve_cus" (CUs every persistent render launch leaves
- * unclaimed, default 0; measured to be of no use to foreign kernels while launches overlap, kept for experiments).
- * read-only: "tree_depth", "fast_depth", "wide_nodes", "wide_depth", "wide_stack" (stack levels a traversal of the 4-wide tree can
- * ask for), "wide_ratio_permille", "pending", "last_kernel" (0 = gather over the binary tree, 1 = LDS-resident over the binary
- * nodes, 2 = gather over 4-wide nodes, 5 = LDS-resident over the 4-wide nodes; 3 and 4 are retired numbers of kernels since
- * removed and never returned), "num_cus",
- * "cur_div", "cur_depth" (the ring the last launch belonged to: G launches of 1/G of the CUs, that many batches in
- * flight), "last_div" (what the last launch really took: 1 when it found the ring idle, else cur_div), "hw_queues"
- * (GPU_MAX_HW_QUEUES as the HIP runtime was asked for it -- the library requests 12 at load time unless the variable is
- * set; NEGATIVE when that request came after a preloaded profiler tool may already have initialised HIP) */
+/* Options of a context.  mpt_set_option first launches the frames enqueued so far, which render with the options they were enqueued
+ * under; it refuses a value outside the domain ("<key> must be <domain>") and a key it does not know ("unknown option '<key>'") and
+ * then leaves the context as it was.  mpt_get_option reads every key below; it launches and waits for nothing.
+ * One entry per key -- default; domain; meaning.  "flag": any int is taken, non-zero is stored (and read back) as 1.
+ * Settable -- what a render launch reads:
+ *   "mode"            0; 0, 1; MPT_MODE_FAST / MPT_MODE_STRICT: which build of the kernels renders
+ *   "batch"           32; 1..64; most frames per launch
+ *   "chunk"           0; >= 0; frames per work item, 0 = auto
+ *   "count"           0; flag; 1 = accumulate mpt_counters (slower)
+ *   "lds"             1; flag; 1 = use the LDS-resident persistent kernel when the scene fits a CU's 160 KiB LDS, 0 = always gather from
+ *                     HBM/L2
+ *   "lds_wide"        1; 0, 1; what that kernel walks: 1 = the 4-wide nodes with exact boxes, 112 bytes apart in LDS -- needs "wide" = 1;
+ *                     0 = the binary nodes; the same film up to ties between equally distant hits
+ *   "lds_block"       0; 0, 256, 512, 768, 1024; lanes per persistent workgroup of the LDS kernel, 0 = auto (diagnostics)
+ *   "wide"            1; flag; scenes that do not fit LDS: 1 = walk the fast tree collapsed into 4-wide nodes, 0 = the binary tree
+ *   "wide_quant"      1; flag; 1 = the 4-wide nodes as 64-byte records with 8-bit child boxes rounded outwards: four gathers per step;
+ *                     0 = 128-byte records with the exact boxes: seven
+ *   "shade_spec"      1; 0, 1; 1 = a scene whose feature mask is empty (no clearcoat, no transmission, no texture) runs the plain
+ *                     instantiation of the LDS 4-wide kernel's SHADE, 0 = always the generic one (A/B, tests); same film bit for bit
+ *   "skip_dark"       -1; -1..1; 1 = a shadow ray whose candidate direct light is exactly zero -- the light behind the surface -- is not
+ *                     traced: adding zero or not is the same sum; 0 = traced like the reference does; -1 = on in the production build,
+ *                     off in the strict build
+ *   "tile_w_shift"    3; 0..3; a work item's tile is 2^w pixels wide ...
+ *   "tile_h_shift"    3; 0..3; ... and 2^h high
+ *   "pipe_depth"      0; 0, 2..6; batches in flight, 0 = auto
+ *   "grid_div"        0; 0..8; each launch takes 1/G of the CUs so that G launches are resident in different phases; 0 = choose by
+ *                     samples per lane, and the whole chip for a launch that finds nothing else in flight
+ *   "reserve_cus"     0; 0..num_cus - 1; CUs every persistent render launch leaves unclaimed; measured to be of no use to foreign
+ *                     kernels while launches overlap, kept for experiments
+ *   "finalise"        1; 0..2; 1 = a render launch that finds no other launch in flight adds its frames to the film, resolves and writes
+ *                     out finished tiles itself while its last paths drain; 2 = the same without the early image (A/B); 0 = always the
+ *                     combine pass after the launch; same film bit for bit
+ * -- read-backs:
+ *   "zero_copy"       1; flag; 1 = mpt_get_image into an mpt_host_alloc array has the resolve pass write the image straight into it
+ *                     over PCIe; 0 = device buffer + DMA -- same image, 20 us more per call
+ *   "spin_us"         20000; >= 0; how long mpt_get_image polls a finalising launch before it blocks, 0 = block at once
+ *   "denoise_lds"     1; flag; 1 = mpt_get_denoised's iterations of stride 1 and 2 filter from a tile held in LDS; 0 = every stride
+ *                     gathers from memory -- same image bit for bit
+ * -- what mpt_build_tree reads.  These leave a built tree invalid (rendering fails with "BVH not built" until the next
+ *    mpt_build_tree): the first four when the stored value changes, the last three at every set, even of the same value:
+ *   "tree"            1; 0, 1; fast build: 1 = SAH re-partition of the LBVH's leaves, 0 = walk the LBVH itself
+ *   "gpu_build"       1; flag; 1 = LBVH built on the device, 0 = on the host
+ *   "sah_build"       -1; -1..1; where the SAH re-partition runs: 1 = on the device, binned above 32 triangles and exact below; 0 = host
+ *                     pass, exact up to "sah_exact_max"; -1 = auto: the device above 8192 faces, the host pass up to there
+ *   "wide_build"      1; flag; 1 = the 4-wide collapse runs on the device, 0 = host pass over downloaded records: same bytes
+ *   "sah_max"         4194304 (2^22); any int; faces above which the fast build walks the LBVH itself
+ *   "sah_exact_max"   8192; >= 2; host SAH pass: ranges up to this many leaves are swept exactly, larger ones binned (diagnostics)
+ *   "sah_inject_fail" 0; flag; test door: 1 = treat the device SAH pass as failed after it ran, so that the host pass takes over
+ * -- diagnostics:
+ *   "timeline"        0; flag; 1 = record mpt_get_timeline data
+ *   "lane_hist"       0; flag; 1 = counting kernels ("count" = 1) fill the lane histogram (mpt_get_lane_hist)
+ *   "build_phases"    0; flag; 1 = mpt_build_tree synchronises at the end of every phase and times it (read-only keys below)
+ *   "launch_seq"      0; >= 0; test door, state rather than an option: the number of the next render launch minus one (its slab tag
+ *                     is 2 + number mod 65534), so that a test can walk the launches across the point where the tags come round;
+ *                     reads back masked to 31 bits
+ * Read-only -- the last build:
+ *   "tree_depth"      depth of the reference LBVH (strict build)
+ *   "fast_depth"      depth of the tree the fast build walks (SAH or LBVH)
+ *   "wide_nodes"      nodes of the 4-wide tree, 0 = not built (too deep)
+ *   "wide_depth"      its depth
+ *   "wide_stack"      stack levels a traversal of the 4-wide tree can ask for
+ *   "wide_ratio_permille"  expected fetches per ray, 4-wide / binary, in thousandths (surface-area sums)
+ *   "sah_fallback"    the device SAH pass gave up (1 = error, 2 = depth) and the host pass ran; 0 = not
+ *   "build_phase_us_N"  N = 0..5, with "build_phases" = 1: microseconds (host clock) of upload | LBVH | SAH pass | triangle records |
+ *                     4-wide collapse | total
+ *   "sah_levels"      what the last device SAH pass did (diagnostics): binned levels
+ *   "sah_kelems"      positions streamed, summed over the binned levels, in thousands
+ *   "sah_chunks"      chunks, summed over the binned levels
+ *   "sah_segments"    segments, summed over the binned levels
+ *   "sah_part_kwords" words of chunk bins written, summed over the levels, in thousands
+ *   "sah_tasks_small" ranges finished in LDS of up to 512 triangles
+ *   "sah_tasks_big"   ... and of 513 to 1024
+ *   "sah_t_sort_k"    the finish kernels' time in units of 1024 clock ticks: summed over the tasks in the sort,
+ *   "sah_t_loop_k"    ... in the level loop,
+ *   "sah_t_max_k"     ... and the longest task
+ *   "sah_task_levels" levels the tasks ran, summed
+ *   "sah_task_levels_max"  ... and the most of one task
+ * -- the last launch:
+ *   "pending"         frames enqueued and not yet launched
+ *   "last_kernel"     0 = gather over the binary tree, 1 = LDS-resident over the binary nodes, 2 = gather over 4-wide nodes, 5 = LDS-
+ *                     resident over the 4-wide nodes; 3 and 4 are retired numbers of kernels since removed and never returned
+ *   "cur_div"         the ring the last launch belonged to: G launches of 1/G of the CUs,
+ *   "cur_depth"       that many batches in flight
+ *   "last_div"        what the last launch really took: 1 when it found the ring idle, else cur_div
+ *   "last_finalised"  1 = the last launch finalised its tiles itself ("finalise")
+ *   "tag_wraps"       times the slab tags came round and every slab was zeroed ("launch_seq")
+ *   "scene_feat"      the scene's feature mask as loaded
+ *   "shade_inst"      the mask the last render launch was compiled for (0 plain, 31 generic; -1: none yet)
+ * -- the device and the process:
+ *   "num_cus"         compute units of the device
+ *   "clock_khz"       its peak shader clock
+ *   "device"          the device the context was created on
+ *   "nranks"          size of the communicator, 1 without one,
+ *   "rank"            and this context's rank in it
+ *   "hw_queues"       GPU_MAX_HW_QUEUES as the HIP runtime was asked for it -- the library requests 12 at load time unless the variable
+ *                     is set; NEGATIVE when that request came after a preloaded profiler tool may already have initialised HIP */
 int mpt_set_option(mpt_ctx *ctx, const char *key, int value);
 int mpt_get_option(mpt_ctx *ctx, const char *key, int *value);
 

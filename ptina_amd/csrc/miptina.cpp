@@ -272,42 +272,10 @@ static int read_back(mpt_ctx *c, void *out, const void *dev, size_t bytes) {
 static int scene_feat_now(const mpt_ctx *c);
 
 // ------------------------------------------------------------------ options
+// The settable options are the rows of MPT_OPTION_TABLE (mpt_options.h); what follows adds what needs the context.
 extern "C" int mpt_set_option(mpt_ctx *c, const char *key, int value) {
     if (use(c)) return 1;
-    std::string k = key ? key : "";
-    if (k == "mode") {
-        if (value != MPT_MODE_FAST && value != MPT_MODE_STRICT) return fail("mode must be 0 (fast) or 1 (strict)");
-        c->mode = value;
-    } else if (k == "batch") {
-        if (value < 1 || value > MPT_MAX_BATCH) return fail("batch must be in 1..%d", MPT_MAX_BATCH);
-        c->batch = value;
-    } else if (k == "chunk") {
-        if (value < 0) return fail("chunk must be >= 0");
-        c->chunk = value;
-    } else if (k == "count") {
-        c->count = value ? 1 : 0;
-    } else if (k == "lds") {
-        c->use_lds = value ? 1 : 0;
-    } else if (k == "lds_wide") {
-        if (value != 0 && value != 1) return fail("lds_wide must be 0 or 1");
-        c->lds_wide = value;
-    } else if (k == "zero_copy") {
-        c->zero_copy = value ? 1 : 0;
-    } else if (k == "denoise_lds") {
-        c->denoise_lds = value ? 1 : 0;
-    } else if (k == "shade_spec") {
-        if (value != 0 && value != 1) return fail("shade_spec must be 0 (always the generic SHADE) or 1 (the plain one for plain scenes)");
-        c->shade_spec = value;
-    } else if (k == "skip_dark") {
-        if (value < -1 || value > 1) return fail("skip_dark must be -1 (auto), 0 or 1");
-        c->skip_dark = value;
-    } else if (k == "spin_us") {
-        if (value < 0) return fail("spin_us must be >= 0");
-        c->spin_us = value;
-    } else if (k == "finalise") {
-        if (value < 0 || value > 2) return fail("finalise must be 0 (combine pass), 1 (tail finalisation) or 2 (the same without the early image: A/B)");
-        c->finalise = value;
-    } else if (k == "launch_seq") {
+    if (key && !strcmp(key, "launch_seq")) {
         // test door: the number of the next launch minus one (its slab tag is 2 + number mod 65534), so that a test can walk
         // the launches across the point where the tags come round and every slab is zeroed
         if (value < 0) return fail("launch_seq must be >= 0");
@@ -316,120 +284,72 @@ extern "C" int mpt_set_option(mpt_ctx *c, const char *key, int value) {
         // the slabs may hold entries with any tag of the old numbering: an epoch no launch number maps to makes the next
         // finalising launch zero them all (round-5 ADVICE: a jump inside an epoch, or to one whose tags overlap, met stale entries)
         c->tag_epoch = 0xffffffffu;
-    } else if (k == "timeline") {
-        c->timeline = value ? 1 : 0;
-    } else if (k == "pipe_depth") {
-        if (value != 0 && (value < 2 || value > MPT_MAX_PIPE)) return fail("pipe_depth must be 0 (auto) or 2..%d", MPT_MAX_PIPE);
-        c->pipe_depth = value;
-    } else if (k == "grid_div") {
-        if (value < 0 || value > 8) return fail("grid_div must be 0 (auto) or 1..8");
-        c->grid_div = value;
-    } else if (k == "lds_block") {
-        if (value != 0 && value != 256 && value != 512 && value != 768 && value != 1024)
-            return fail("lds_block must be 0 (auto), 256, 512, 768 or 1024");
-        c->lds_block = value;
-    } else if (k == "reserve_cus") {
-        if (value < 0 || value >= c->num_cus) return fail("reserve_cus must be in 0..%d", c->num_cus - 1);
-        c->reserve_cus = value;
-    } else if (k == "wide") {
-        c->use_wide = value ? 1 : 0;
-    } else if (k == "sah_exact_max") {
-        if (value < 2) return fail("sah_exact_max must be >= 2");
-        c->sah_exact_max = value; c->tree_valid = false;
-    } else if (k == "sah_build") {
-        if (value < -1 || value > 1) return fail("sah_build must be -1 (auto), 0 (host) or 1 (device)");
-        if (value != c->sah_build) { c->sah_build = value; c->tree_valid = false; }
-    } else if (k == "wide_build") {
-        if ((value ? 1 : 0) != c->wide_build) { c->wide_build = value ? 1 : 0; c->tree_valid = false; }
-    } else if (k == "wide_quant") {
-        c->use_quant = value ? 1 : 0;
-    } else if (k == "tree") {
-        if (value != 0 && value != 1) return fail("tree must be 0 (LBVH) or 1 (SAH)");
-        if (value != c->tree_kind) { c->tree_kind = value; c->tree_valid = false; }
-    } else if (k == "tile_w_shift" || k == "tile_h_shift") {
-        if (value < 0 || value > 3) return fail("%s must be in 0..3", k.c_str());
-        (k == "tile_w_shift" ? c->tile_w_shift : c->tile_h_shift) = value;
-    } else if (k == "gpu_build") {
-        if ((value ? 1 : 0) != c->gpu_build) { c->gpu_build = value ? 1 : 0; c->tree_valid = false; }
-    } else if (k == "sah_inject_fail") {
-        c->sah_inject_fail = value != 0; c->tree_valid = false;
-    } else if (k == "build_phases") {
-        c->build_phases = value ? 1 : 0;
-    } else if (k == "lane_hist") {
-        c->lane_hist = value ? 1 : 0;
-    } else if (k == "sah_max") {
-        c->sah_max = value; c->tree_valid = false;
-    } else {
-        return fail("unknown option '%s'", k.c_str());
+        return 0;
     }
+    const MptOptionRow *row = mpt_option_row(key);
+    if (!row) return fail("unknown option '%s'", key ? key : "");
+    MptOptionRow r = *row;
+    if (r.member == &MptOptions::reserve_cus) r.hi = c->num_cus - 1;     // the one bound that is no constant
+    char why[160];
+    bool tree_invalid = false;
+    if (mpt_option_set_row(c->opt, r, value, why, sizeof why, &tree_invalid) != MPT_OPT_OK) return fail("%s", why);
+    if (tree_invalid) c->tree_valid = false;
     return 0;
 }
 
+// What can be read and not set: results of the last build and the last launch, and facts of the device.
+struct MptReadOnly { const char *key; int (*read)(const mpt_ctx *c); };
+static const MptReadOnly g_read_only[] = {
+    { "tree_depth", [](const mpt_ctx *c) { return c->tree_depth; } },
+    { "fast_depth", [](const mpt_ctx *c) { return c->fast_depth; } },
+    { "pending", [](const mpt_ctx *c) { return c->pending; } },
+    { "last_finalised", [](const mpt_ctx *c) { return c->last_finalised; } },
+    { "launch_seq", [](const mpt_ctx *c) { return (int)(c->launch_seq & 0x7fffffffu); } },
+    { "tag_wraps", [](const mpt_ctx *c) { return (int)c->tag_wraps; } },
+    { "scene_feat", [](const mpt_ctx *c) { return scene_feat_now(c); } },             // the scene's feature mask as loaded (shade_feat.h)
+    { "shade_inst", [](const mpt_ctx *c) { return c->last_shade_feat; } },            // the mask the last render launch was compiled for (0 plain, 31 generic)
+    { "cur_depth", [](const mpt_ctx *c) { return c->cur_depth; } },
+    { "cur_div", [](const mpt_ctx *c) { return c->cur_div; } },
+    { "last_div", [](const mpt_ctx *c) { return c->last_div; } },
+    { "last_kernel", [](const mpt_ctx *c) { return c->last_kernel; } },
+    { "num_cus", [](const mpt_ctx *c) { return c->num_cus; } },
+    { "sah_fallback", [](const mpt_ctx *c) { return c->sah_fallback; } },
+    { "sah_levels", [](const mpt_ctx *c) { return c->sah_stats.levels; } },
+    { "sah_kelems", [](const mpt_ctx *c) { return (int)(c->sah_stats.elems / 1000); } },
+    { "sah_chunks", [](const mpt_ctx *c) { return (int)c->sah_stats.chunks; } },
+    { "sah_segments", [](const mpt_ctx *c) { return (int)c->sah_stats.segments; } },
+    { "sah_part_kwords", [](const mpt_ctx *c) { return (int)(c->sah_stats.part_words / 1000); } },
+    { "sah_tasks_small", [](const mpt_ctx *c) { return c->sah_stats.tasks_small; } },
+    { "sah_tasks_big", [](const mpt_ctx *c) { return c->sah_stats.tasks_big; } },
+    { "sah_t_sort_k", [](const mpt_ctx *c) { return c->sah_stats.t_sort_k; } },
+    { "sah_t_loop_k", [](const mpt_ctx *c) { return c->sah_stats.t_loop_k; } },
+    { "sah_t_max_k", [](const mpt_ctx *c) { return c->sah_stats.t_max_k; } },
+    { "sah_task_levels", [](const mpt_ctx *c) { return c->sah_stats.task_levels; } },
+    { "sah_task_levels_max", [](const mpt_ctx *c) { return c->sah_stats.task_levels_max; } },
+    { "wide_nodes", [](const mpt_ctx *c) { return c->wide_nodes; } },
+    { "wide_stack", [](const mpt_ctx *c) { return c->wide_stack; } },
+    { "wide_ratio_permille", [](const mpt_ctx *c) { return (int)(c->wide_ratio * 1000.f + 0.5f); } },
+    { "wide_depth", [](const mpt_ctx *c) { return c->wide_depth; } },
+    { "nranks", [](const mpt_ctx *c) { return c->nranks; } },
+    { "rank", [](const mpt_ctx *c) { return c->rank; } },
+    { "device", [](const mpt_ctx *c) { return c->device; } },
+    { "clock_khz", [](const mpt_ctx *c) { return c->clock_khz; } },
+    { "hw_queues", [](const mpt_ctx *) { return g_hwq_late ? -g_hwq : g_hwq; } },
+};
+
 extern "C" int mpt_get_option(mpt_ctx *c, const char *key, int *value) {
     if (!c || !value) return fail("null argument");
-    std::string k = key ? key : "";
-    if (k == "mode") *value = c->mode;
-    else if (k == "batch") *value = c->batch;
-    else if (k == "chunk") *value = c->chunk;
-    else if (k == "count") *value = c->count;
-    else if (k == "tree_depth") *value = c->tree_depth;
-    else if (k == "fast_depth") *value = c->fast_depth;
-    else if (k == "tree") *value = c->tree_kind;
-    else if (k == "gpu_build") *value = c->gpu_build;
-    else if (k == "pending") *value = c->pending;
-    else if (k == "lds") *value = c->use_lds;
-    else if (k == "lds_wide") *value = c->lds_wide;
-    else if (k == "lds_block") *value = c->lds_block;
-    else if (k == "zero_copy") *value = c->zero_copy;
-    else if (k == "denoise_lds") *value = c->denoise_lds;
-    else if (k == "spin_us") *value = c->spin_us;
-    else if (k == "finalise") *value = c->finalise;
-    else if (k == "last_finalised") *value = c->last_finalised;
-    else if (k == "launch_seq") *value = (int)(c->launch_seq & 0x7fffffffu);
-    else if (k == "tag_wraps") *value = (int)c->tag_wraps;
-    else if (k == "skip_dark") *value = c->skip_dark;
-    else if (k == "shade_spec") *value = c->shade_spec;
-    else if (k == "scene_feat") *value = scene_feat_now(c);            // read-only: the scene's feature mask as loaded (shade_feat.h)
-    else if (k == "shade_inst") *value = c->last_shade_feat;           // read-only: the mask the last render launch was compiled for (0 plain, 31 generic)
-    else if (k == "pipe_depth") *value = c->pipe_depth;
-    else if (k == "grid_div") *value = c->grid_div;
-    else if (k == "cur_depth") *value = c->cur_depth;
-    else if (k == "cur_div") *value = c->cur_div;
-    else if (k == "last_div") *value = c->last_div;
-    else if (k == "last_kernel") *value = c->last_kernel;
-    else if (k == "num_cus") *value = c->num_cus;
-    else if (k == "reserve_cus") *value = c->reserve_cus;
-    else if (k == "wide") *value = c->use_wide;
-    else if (k == "wide_quant") *value = c->use_quant;
-    else if (k == "wide_build") *value = c->wide_build;
-    else if (k == "sah_build") *value = c->sah_build;
-    else if (k == "sah_fallback") *value = c->sah_fallback;
-    else if (k == "build_phases") *value = c->build_phases;
-    else if (k == "lane_hist") *value = c->lane_hist;
-    else if (k == "sah_levels") *value = c->sah_stats.levels;
-    else if (k == "sah_kelems") *value = (int)(c->sah_stats.elems / 1000);
-    else if (k == "sah_chunks") *value = (int)c->sah_stats.chunks;
-    else if (k == "sah_segments") *value = (int)c->sah_stats.segments;
-    else if (k == "sah_part_kwords") *value = (int)(c->sah_stats.part_words / 1000);
-    else if (k == "sah_tasks_small") *value = c->sah_stats.tasks_small;
-    else if (k == "sah_tasks_big") *value = c->sah_stats.tasks_big;
-    else if (k == "sah_t_sort_k") *value = c->sah_stats.t_sort_k;
-    else if (k == "sah_t_loop_k") *value = c->sah_stats.t_loop_k;
-    else if (k == "sah_t_max_k") *value = c->sah_stats.t_max_k;
-    else if (k == "sah_task_levels") *value = c->sah_stats.task_levels;
-    else if (k == "sah_task_levels_max") *value = c->sah_stats.task_levels_max;
-    else if (k.rfind("build_phase_us_", 0) == 0 && k.size() == 16 && k[15] >= '0' && k[15] <= '5') *value = (int)(c->build_phase_us[k[15] - '0'] + 0.5);
-    else if (k == "wide_nodes") *value = c->wide_nodes;
-    else if (k == "wide_stack") *value = c->wide_stack;
-    else if (k == "wide_ratio_permille") *value = (int)(c->wide_ratio * 1000.f + 0.5f);
-    else if (k == "wide_depth") *value = c->wide_depth;
-    else if (k == "nranks") *value = c->nranks;
-    else if (k == "rank") *value = c->rank;
-    else if (k == "device") *value = c->device;
-    else if (k == "clock_khz") *value = c->clock_khz;
-    else if (k == "hw_queues") *value = g_hwq_late ? -g_hwq : g_hwq;
-    else return fail("unknown option '%s'", k.c_str());
-    return 0;
+    const char *k = key ? key : "";
+    if (mpt_option_get(c->opt, k, value) == MPT_OPT_OK) return 0;
+    for (const MptReadOnly &r : g_read_only)
+        if (!strcmp(k, r.key)) { *value = r.read(c); return 0; }
+    static const char stem[] = "build_phase_us_";                   // ... 0 to 5: the phases of the last mpt_build_tree
+    const size_t n = sizeof stem - 1;
+    if (!strncmp(k, stem, n) && k[n] >= '0' && k[n] <= '5' && !k[n + 1]) {
+        *value = (int)(c->build_phase_us[k[n] - '0'] + 0.5);
+        return 0;
+    }
+    return fail("unknown option '%s'", k);
 }
 
 // ------------------------------------------------------------------ film
@@ -755,11 +675,11 @@ static int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes) {
     }
     p.wnode = c->wnode; p.qnode = c->qnode; p.nwide = c->wide_nodes; p.stack_spill = nullptr;
     p.snode = c->nodes.snode; p.fnode = c->nodes.fnode; p.tgeo = c->tris.tgeo; p.tshade = c->tris.tshade; p.tfast = c->tfast;
-    p.skip_dark = c->skip_dark >= 0 ? c->skip_dark : (c->mode == MPT_MODE_FAST ? 1 : 0);
+    p.skip_dark = c->opt.skip_dark >= 0 ? c->opt.skip_dark : (c->opt.mode == MPT_MODE_FAST ? 1 : 0);
     p.P = c->sP;
     p.film0 = c->fb.film[0]; p.film1 = c->fb.film[1]; p.film2 = c->fb.film[2];
     p.counters = c->d_counters;
-    p.lane_hist = c->lane_hist;
+    p.lane_hist = c->opt.lane_hist;
     p.watchdog = c->d_watchdog;
     return fill_scene_params(c, p);
 }
@@ -773,7 +693,7 @@ static hipEvent_t get_event(mpt_ctx *c) {
 
 // levels of the per-lane traversal stack of the gather, preview, Metropolis and brute-force kernels (two instantiations each)
 static int gather_stack_levels(const mpt_ctx *c) {
-    return ((c->mode == MPT_MODE_STRICT ? c->tree_depth : c->fast_depth) + 2 <= 32) ? 32 : 64;
+    return ((c->opt.mode == MPT_MODE_STRICT ? c->tree_depth : c->fast_depth) + 2 <= 32) ? 32 : 64;
 }
 
 static int mlt_flush(mpt_ctx *c);
@@ -799,8 +719,8 @@ static int ring_policy(mpt_ctx *c, int B) {
     long long cols = 0;
     share_extent(c, 1, &cols, nullptr);
     const double per_lane = (double)B * cols * c->ny / ((double)c->num_cus * 1024.0);
-    int div = c->grid_div > 0 ? c->grid_div : (per_lane >= 24.0 ? 1 : per_lane >= 6.0 ? 2 : 4);
-    int depth = c->pipe_depth > 0 ? c->pipe_depth : (div == 1 ? 2 : std::min(div + 2, (int)MPT_MAX_PIPE));
+    int div = c->opt.grid_div > 0 ? c->opt.grid_div : (per_lane >= 24.0 ? 1 : per_lane >= 6.0 ? 2 : 4);
+    int depth = c->opt.pipe_depth > 0 ? c->opt.pipe_depth : (div == 1 ? 2 : std::min(div + 2, (int)MPT_MAX_PIPE));
     if (depth != c->cur_depth) {
         // slots are reused round-robin: let everything in flight finish before the ring changes size
         HIP_TRY(hipStreamSynchronize(c->aux));
@@ -847,8 +767,8 @@ static int batch_points(mpt_ctx *c, MptRenderParams &p, const BatchSlot &s, int 
 // step 3a: which kernel serves the scene, and the dynamic LDS it asks for (lds_layout.h: the layout, the fit rule and the choice)
 static MptKernelChoice choose_kernel(const mpt_ctx *c) {
     MptKernelFacts f;
-    f.fast = c->mode == MPT_MODE_FAST;
-    f.use_lds = c->use_lds; f.lds_wide = c->lds_wide; f.use_wide = c->use_wide;
+    f.fast = c->opt.mode == MPT_MODE_FAST;
+    f.use_lds = c->opt.lds; f.lds_wide = c->opt.lds_wide; f.use_wide = c->opt.wide;
     f.nfaces = c->nfaces;
     f.wide_nodes = c->wide_nodes; f.wide_stack = c->wide_stack; f.have_wnode = c->wnode != nullptr;
     f.max_mtlid = c->max_mtlid; f.max_materials = c->caps.max_materials;
@@ -860,12 +780,12 @@ static MptKernelChoice choose_kernel(const mpt_ctx *c) {
 // to whole work-item tiles
 static int work_items(const mpt_ctx *c, MptRenderParams &p, int B, bool fast) {
     int chunk = B, nchunks = 1;
-    const int tw = 1 << c->tile_w_shift, th = 1 << c->tile_h_shift;
+    const int tw = 1 << c->opt.tile_w_shift, th = 1 << c->opt.tile_h_shift;
     int tile_cols = 0;
     share_extent(c, tw, nullptr, &tile_cols);
     const int tiles8 = tile_cols * ((c->ny + th - 1) / th);
     if (fast) {
-        chunk = c->chunk;
+        chunk = c->opt.chunk;
         if (chunk <= 0) {
             // Work items are (8x8 tile, chunk of frames).  Persistent waves refill from the queue the moment their
             // pool drains, so small items cost one returning atomic each and nothing else, and the launch ends
@@ -879,7 +799,7 @@ static int work_items(const mpt_ctx *c, MptRenderParams &p, int B, bool fast) {
     }
     p.chunk = chunk; p.nchunks = nchunks;
     p.nitems = tiles8 * nchunks;
-    p.tile_w_shift = c->tile_w_shift; p.tile_h_shift = c->tile_h_shift;
+    p.tile_w_shift = c->opt.tile_w_shift; p.tile_h_shift = c->opt.tile_h_shift;
     return tile_cols * tw;
 }
 
@@ -934,21 +854,21 @@ static int launch_share(mpt_ctx *c, bool fast, bool *ring_idle, int *launch_cus)
     // once (same waits measured with 2 CUs left out) -- so "reserve_cus" defaults to 0 and the gather of batch i
     // simply completes one launch late; nothing waits for it but the read-back, and a step that ends with a
     // read-back (bench.py's `value`) has no other launch in flight when its gather starts.
-    const int reserve = std::max(c->reserve_cus, 0);
+    const int reserve = std::max(c->opt.reserve_cus, 0);
     const int usable_cus = std::max(c->num_cus - reserve, 1);
     // A launch that finds the ring idle has no other launch to share the chip with -- a step that ends with a
     // read-back (bench.py's `value`, an interactive frame) is one launch at a time -- so it takes every CU; 1/G of
     // them would only make it G times longer.  Launches issued while others are still in flight take 1/G each.
     int launch_div = std::max(c->cur_div, 1);
     *ring_idle = fast;
-    if (fast && ((launch_div > 1 && c->grid_div <= 0) || c->finalise)) {
+    if (fast && ((launch_div > 1 && c->opt.grid_div <= 0) || c->opt.finalise)) {
         for (int q = 0; q < c->cur_depth && *ring_idle; q++) {
             hipError_t st = hipEventQuery(c->ev_render[q]);
             if (st == hipErrorNotReady) *ring_idle = false;
             else if (st != hipSuccess) HIP_TRY(st);
         }
     }
-    if (fast && launch_div > 1 && c->grid_div <= 0 && *ring_idle) launch_div = 1;
+    if (fast && launch_div > 1 && c->opt.grid_div <= 0 && *ring_idle) launch_div = 1;
     c->last_div = launch_div;
     *launch_cus = std::max(usable_cus / launch_div, 1);   // G launches never claim more than usable_cus
     return 0;
@@ -959,7 +879,7 @@ static int launch_share(mpt_ctx *c, bool fast, bool *ring_idle, int *launch_cus)
 static int size_launch_buffers(mpt_ctx *c, MptRenderParams &p, int k, int kernel, int launch_cus, int *wide_blocks, int *lds_block) {
     *wide_blocks = 0;
     if (kernel == MPT_KERNEL_WIDE) {
-        HIP_TRY(mpt_wide_blocks(launch_cus, c->count, c->use_quant, wide_blocks));
+        HIP_TRY(mpt_wide_blocks(launch_cus, c->opt.count, c->opt.wide_quant, wide_blocks));
         const size_t need_spill = (size_t)*wide_blocks * MPT_BLOCK * 128;   // >= SpillStack::SPILL entries per lane (128 - LDS levels)
         // one strip PER SLOT: the launches of different slots overlap, and a strip is indexed by block and lane only
         bool grown = false;
@@ -973,11 +893,11 @@ static int size_launch_buffers(mpt_ctx *c, MptRenderParams &p, int k, int kernel
     // quarter share upwards 1024 is as good or better).  Same film either way.
     // (The kernel over the 4-wide nodes is fastest with 1024 lanes at every size: solo launch of a 1/8 share 0.49 ms against 0.53
     // at 768, 0.64 at 512; whole film 2.59 / 2.97 / 3.94.)
-    *lds_block = c->lds_block ? c->lds_block : 1024;
-    if (kernel == MPT_KERNEL_LDS && c->lds_block == 0 &&
-        ((long long)p.nitems * p.chunk << (c->tile_w_shift + c->tile_h_shift)) < 6ll * launch_cus * 1024) *lds_block = 768;
+    *lds_block = c->opt.lds_block ? c->opt.lds_block : 1024;
+    if (kernel == MPT_KERNEL_LDS && c->opt.lds_block == 0 &&
+        ((long long)p.nitems * p.chunk << (c->opt.tile_w_shift + c->opt.tile_h_shift)) < 6ll * launch_cus * 1024) *lds_block = 768;
     p.timeline = nullptr;
-    if (c->timeline && lds_kernel) {
+    if (c->opt.timeline && lds_kernel) {
         const int waves = launch_cus * (*lds_block / 64);
         if (waves != c->timeline_waves) {
             HIP_TRY(hipDeviceSynchronize());
@@ -1032,7 +952,7 @@ static int setup_finalisation(mpt_ctx *c, MptRenderParams &p, const BatchSlot &s
     // the resolved image as well, if the caller has said where get_image() will want it and this share is the whole film
     const size_t img_bytes = (size_t)c->nx * c->ny * sizeof(MptVec4);
     void *mapped = nullptr;
-    if (c->hint_image && c->finalise == 1 && c->zero_copy && c->x0 == 0 && c->x1 == c->nx && c->stripe_w == 0 && is_locked_range(c->hint_image, img_bytes) &&
+    if (c->hint_image && c->opt.finalise == 1 && c->opt.zero_copy && c->x0 == 0 && c->x1 == c->nx && c->stripe_w == 0 && is_locked_range(c->hint_image, img_bytes) &&
         hipHostGetDevicePointer(&mapped, c->hint_image, 0) == hipSuccess && mapped) {
         p.image_out = (MptVec4 *)mapped;
         c->early_ptr = c->hint_image; c->early_version = c->film_version; c->early_stream = s.rs;
@@ -1044,17 +964,17 @@ static int setup_finalisation(mpt_ctx *c, MptRenderParams &p, const BatchSlot &s
 static int launch_render(mpt_ctx *c, const MptRenderParams &p, const BatchSlot &s, MptKernelChoice kc, int launch_cus, int lds_block,
                          int wide_blocks) {
     // SHADE compiled for what the scene uses: the LDS-resident 4-wide kernel has a plain instantiation, every other kernel the generic code
-    const int shade_feat = kc.kernel == MPT_KERNEL_LDS4 ? shade_feat_instantiation(scene_feat_now(c), c->shade_spec) : MPT_FEAT_GENERIC;
+    const int shade_feat = kc.kernel == MPT_KERNEL_LDS4 ? shade_feat_instantiation(scene_feat_now(c), c->opt.shade_spec) : MPT_FEAT_GENERIC;
     const int stack = gather_stack_levels(c);
     hipEvent_t e0 = get_event(c), e1 = get_event(c);
     HIP_TRY(hipEventRecord(e0, s.rs));
     switch (kc.kernel) {
-    case MPT_KERNEL_LDS4: HIP_TRY(mpt_launch_render_lds4(&p, launch_cus, lds_block, (size_t)kc.lds_bytes, c->count, shade_feat, s.rs)); break;
-    case MPT_KERNEL_LDS: HIP_TRY(mpt_launch_render_lds(&p, launch_cus, lds_block, (size_t)kc.lds_bytes, c->count, s.rs)); break;
-    case MPT_KERNEL_WIDE: HIP_TRY(mpt_launch_render_wide(&p, wide_blocks, c->count, c->use_quant, s.rs)); break;
+    case MPT_KERNEL_LDS4: HIP_TRY(mpt_launch_render_lds4(&p, launch_cus, lds_block, (size_t)kc.lds_bytes, c->opt.count, shade_feat, s.rs)); break;
+    case MPT_KERNEL_LDS: HIP_TRY(mpt_launch_render_lds(&p, launch_cus, lds_block, (size_t)kc.lds_bytes, c->opt.count, s.rs)); break;
+    case MPT_KERNEL_WIDE: HIP_TRY(mpt_launch_render_wide(&p, wide_blocks, c->opt.count, c->opt.wide_quant, s.rs)); break;
     default:    // MPT_KERNEL_GATHER: the binary tree, in either build
-        if (!s.fast) HIP_TRY(mpt_launch_render_strict(&p, p.ntiles, stack, c->count, s.rs));
-        else HIP_TRY(mpt_launch_render_fast(&p, launch_cus, stack, c->count, s.rs));
+        if (!s.fast) HIP_TRY(mpt_launch_render_strict(&p, p.ntiles, stack, c->opt.count, s.rs));
+        else HIP_TRY(mpt_launch_render_fast(&p, launch_cus, stack, c->opt.count, s.rs));
     }
     c->last_shade_feat = shade_feat;
     c->last_kernel = kc.kernel;
@@ -1098,7 +1018,7 @@ extern "C" int mpt_flush(mpt_ctx *c) {
     c->pending = 0;
     MptRenderParams p;
     if (fill_params(c, p, B)) return 1;
-    const bool fast = c->mode == MPT_MODE_FAST;
+    const bool fast = c->opt.mode == MPT_MODE_FAST;
     if (fast && ring_policy(c, B)) return 1;                                               // 1
     BatchSlot s;
     s.fast = fast;
@@ -1116,7 +1036,7 @@ extern "C" int mpt_flush(mpt_ctx *c) {
     int launch_cus = 0, wide_blocks = 0, lds_block = 0;
     if (launch_share(c, fast, &ring_idle, &launch_cus)) return 1;                          // 5
     if (size_launch_buffers(c, p, s.k, kc.kernel, launch_cus, &wide_blocks, &lds_block)) return 1;   // 6
-    const bool fin = fast && c->finalise && ring_idle && p.nitems > 0;
+    const bool fin = fast && c->opt.finalise && ring_idle && p.nitems > 0;
     if (setup_finalisation(c, p, s, fin)) return 1;                                        // 7
     if (launch_render(c, p, s, kc, launch_cus, lds_block, wide_blocks)) return 1;          // 8
     return fast ? behind_launch(c, p, s, B, fin) : 0;                                      // 9
@@ -1128,11 +1048,11 @@ extern "C" int mpt_render(mpt_ctx *c, int nframes) {                           /
     if (check_ready(c)) return 1;                     // fail at the call, not at the deferred launch
     if (c->mlt_pending && mlt_flush(c)) return 1;     // the film sum follows call order: Metropolis iterations enqueued before go first
     while (nframes > 0) {
-        int room = c->batch - c->pending;
+        int room = c->opt.batch - c->pending;
         int take = std::min(room, nframes);
         c->pending += take;
         nframes -= take;
-        if (c->pending >= c->batch && mpt_flush(c)) return 1;
+        if (c->pending >= c->opt.batch && mpt_flush(c)) return 1;
     }
     return 0;
 }
@@ -1147,7 +1067,7 @@ extern "C" int mpt_render_preview(mpt_ctx *c, int nframes) {                   /
         p.chunk = B; p.nchunks = 1;
         const int stack = gather_stack_levels(c);
         if (p.ntiles) {
-            if (c->mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_preview_strict(&p, p.ntiles, stack, c->stream));
+            if (c->opt.mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_preview_strict(&p, p.ntiles, stack, c->stream));
             else HIP_TRY(mpt_launch_preview_fast(&p, p.ntiles, stack, c->stream));
         }
         nframes -= B;
@@ -1189,7 +1109,7 @@ static int mlt_flush(mpt_ctx *c) {
         a.nchains = nch; a.t0 = c->mlt_iter; a.K = K; a.seed = c->mlt_seed; a.lsp = c->mlt_lsp; a.sigma = c->mlt_sigma;
         hipEvent_t e0 = get_event(c), e1 = get_event(c), e2 = get_event(c);
         HIP_TRY(hipEventRecord(e0, c->stream));
-        if (c->mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_mlt_chain_strict(&p, &a, stack, c->stream));
+        if (c->opt.mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_mlt_chain_strict(&p, &a, stack, c->stream));
         else HIP_TRY(mpt_launch_mlt_chain_fast(&p, &a, stack, c->stream));
         HIP_TRY(hipEventRecord(e1, c->stream));
         HIP_TRY(mpt_launch_mlt_splat(c->fb.film[0], c->slab.keys, c->slab.vals, c->slab.keys2, c->slab.vals2, c->slab.tmp, c->slab.tmp.cap,
@@ -1281,7 +1201,7 @@ extern "C" int mpt_mlt_trace(mpt_ctx *c, const float *X, float *rgb, int n) {
     if (dX.reserve((size_t)n * 32) || drgb.reserve((size_t)n * 3)) return 1;
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(dX, X, (size_t)n * 32 * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = c->mode == MPT_MODE_STRICT ? mpt_launch_mlt_trace_strict(&p, dX, drgb, n, gather_stack_levels(c), c->stream)
+    if (e == hipSuccess) e = c->opt.mode == MPT_MODE_STRICT ? mpt_launch_mlt_trace_strict(&p, dX, drgb, n, gather_stack_levels(c), c->stream)
                                                         : mpt_launch_mlt_trace_fast(&p, dX, drgb, n, gather_stack_levels(c), c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(rgb, drgb, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost);
@@ -1289,15 +1209,25 @@ extern "C" int mpt_mlt_trace(mpt_ctx *c, const float *X, float *rgb, int n) {
     return 0;
 }
 
-extern "C" int mpt_mlt_kernel_time(mpt_ctx *c, double *chain_ms, double *splat_ms, int *launches) {
+// The read-out of an engine's launch timer: what is enqueued is launched, the main stream (and, for launches recorded on them, the
+// aux and render streams) waited for, and the launches' segments summed: ms0, and ms1 where a launch has two.
+static int timer_readout(mpt_ctx *c, MptLaunchTimer mpt_ctx::*timer, double *ms0, double *ms1, int *launches, bool render_streams = false) {
     if (use_ro(c)) return 1;
     if (mpt_flush(c)) return 1;
+    if (render_streams) {
+        HIP_TRY(hipStreamSynchronize(c->aux));
+        for (int k = 0; k < MPT_MAX_PIPE; k++) HIP_TRY(hipStreamSynchronize(c->rstream[k]));
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    double seg[2] = { 0, 0 };            // chain, splat
-    if (c->mlt_timer.drain(seg, launches, c->event_pool)) return 1;
-    if (chain_ms) *chain_ms = seg[0];
-    if (splat_ms) *splat_ms = seg[1];
+    double seg[2] = { 0, 0 };
+    if ((c->*timer).drain(seg, launches, c->event_pool)) return 1;
+    if (ms0) *ms0 = seg[0];
+    if (ms1) *ms1 = seg[1];
     return 0;
+}
+
+extern "C" int mpt_mlt_kernel_time(mpt_ctx *c, double *chain_ms, double *splat_ms, int *launches) {
+    return timer_readout(c, &mpt_ctx::mlt_timer, chain_ms, splat_ms, launches);
 }
 
 // ------------------------------------------------------------------ brute-force engine (BruteEngine, engine/brute.py)
@@ -1319,7 +1249,7 @@ extern "C" int mpt_render_brute(mpt_ctx *c, int nframes) {                     /
         if (p.ntiles) {
             hipEvent_t e0 = get_event(c), e1 = get_event(c);
             HIP_TRY(hipEventRecord(e0, c->stream));
-            if (c->mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_brute_strict(&p, p.ntiles, stack, c->stream));
+            if (c->opt.mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_brute_strict(&p, p.ntiles, stack, c->stream));
             else HIP_TRY(mpt_launch_brute_fast(&p, p.ntiles, stack, c->stream));
             HIP_TRY(hipEventRecord(e1, c->stream));
             c->brute_timer.record({ e0, e1 }, c->event_pool);
@@ -1332,13 +1262,7 @@ extern "C" int mpt_render_brute(mpt_ctx *c, int nframes) {                     /
 }
 
 extern "C" int mpt_brute_kernel_time(mpt_ctx *c, double *ms, int *launches) {
-    if (use_ro(c)) return 1;
-    if (mpt_flush(c)) return 1;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    double total = 0;
-    if (c->brute_timer.drain(&total, launches, c->event_pool)) return 1;
-    if (ms) *ms = total;
-    return 0;
+    return timer_readout(c, &mpt_ctx::brute_timer, ms, nullptr, launches);
 }
 
 // a persistent render kernel that had to be stopped by its watchdog leaves a flag behind (in host-pinned
@@ -1415,20 +1339,20 @@ extern "C" int mpt_get_image(mpt_ctx *c, int pass, float *out) {               /
             // ... and polled, for a while, instead of slept on: the runtime's blocking wait returned 18 us after the kernel's end
             // (HIP trace), a query loop sees the completion signal within a few; a launch that runs longer than the poll window
             // falls back to the blocking wait (option "spin_us", 0 = always block)
-            if (c->spin_us > 0) {
+            if (c->opt.spin_us > 0) {
                 const auto t0 = std::chrono::steady_clock::now();
                 for (;;) {
                     const hipError_t q = hipStreamQuery(c->early_stream);
                     if (q == hipSuccess) return check_watchdog(c);
                     if (q != hipErrorNotReady) HIP_TRY(q);
-                    if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > (double)c->spin_us) break;
+                    if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > (double)c->opt.spin_us) break;
                 }
             }
             HIP_TRY(hipStreamSynchronize(c->early_stream));
             return check_watchdog(c);
         }
     }
-    if (c->zero_copy && is_locked_range(out, bytes) && hipHostGetDevicePointer(&mapped, out, 0) == hipSuccess && mapped) {
+    if (c->opt.zero_copy && is_locked_range(out, bytes) && hipHostGetDevicePointer(&mapped, out, 0) == hipSuccess && mapped) {
         // the caller's array is page-locked memory of ours: the resolve pass writes the image straight into it over PCIe,
         // instead of into a device buffer that a DMA then copies (one dependent hop and the copy engine's start-up less)
         if (mpt_flush(c)) return 1;
@@ -1488,7 +1412,7 @@ static int denoise_launches(mpt_ctx *c, const mpt_denoise_params &p, const MptVe
     for (int i = 0; i < p.iterations; i++) {
         const float sc = p.sigma_color * std::ldexp(1.0f, -i);             // the colour edge-stopping narrows as the stencil widens
         HIP_TRY(mpt_launch_denoise_atrous(c->fb.dn_e[i & 1], c->fb.dn_e[(i + 1) & 1], c->fb.dn_a, c->fb.dn_n, c->nx, c->ny, 1 << i,
-                                          1.0f / (sc * sc), ka, kn, c->denoise_lds, c->stream));
+                                          1.0f / (sc * sc), ka, kn, c->opt.denoise_lds, c->stream));
     }
     const int last = p.iterations & 1;
     HIP_TRY(mpt_launch_denoise_epilogue(c->fb.dn_e[last], c->fb.dn_a, c->fb.dn_e[last ^ 1], npix, p.demodulate ? 1 : 0, c->stream));
@@ -1515,13 +1439,7 @@ extern "C" int mpt_get_denoised(mpt_ctx *c, const mpt_denoise_params *params, fl
 }
 
 extern "C" int mpt_denoise_kernel_time(mpt_ctx *c, double *ms, int *launches) {
-    if (use_ro(c)) return 1;
-    if (mpt_flush(c)) return 1;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    double total = 0;
-    if (c->denoise_timer.drain(&total, launches, c->event_pool)) return 1;
-    if (ms) *ms = total;
-    return 0;
+    return timer_readout(c, &mpt_ctx::denoise_timer, ms, nullptr, launches);
 }
 
 // ------------------------------------------------------------------ 8-bit display read-back (display.hip)
@@ -1576,7 +1494,7 @@ extern "C" int mpt_get_display(mpt_ctx *c, const mpt_display_params *params, con
     if (check_pass(c, denoised ? 0 : p.source)) return 1;
     const size_t npix = (size_t)c->nx * c->ny;
     void *mapped = nullptr;
-    const bool direct = c->zero_copy && is_locked_range(out, npix * 4) && hipHostGetDevicePointer(&mapped, out, 0) == hipSuccess && mapped;
+    const bool direct = c->opt.zero_copy && is_locked_range(out, npix * 4) && hipHostGetDevicePointer(&mapped, out, 0) == hipSuccess && mapped;
     const MptVec4 *src = denoised ? nullptr : c->fb.film[p.source].p;
     hipEvent_t e0 = get_event(c), e1 = get_event(c);
     HIP_TRY(hipEventRecord(e0, c->stream));
@@ -1589,13 +1507,7 @@ extern "C" int mpt_get_display(mpt_ctx *c, const mpt_display_params *params, con
 }
 
 extern "C" int mpt_display_kernel_time(mpt_ctx *c, double *ms, int *launches) {
-    if (use_ro(c)) return 1;
-    if (mpt_flush(c)) return 1;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    double total = 0;
-    if (c->display_timer.drain(&total, launches, c->event_pool)) return 1;
-    if (ms) *ms = total;
-    return 0;
+    return timer_readout(c, &mpt_ctx::display_timer, ms, nullptr, launches);
 }
 
 // test door: the same launches on the caller's accumulators, in buffers of its own (no film pass, no film-owner buffer is touched)
@@ -1752,7 +1664,7 @@ extern "C" int mpt_unit_eval(mpt_ctx *c, int kind, const void *in, int in_cols, 
     p.tshade = d_shade;
     if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, (size_t)n * out_cols * 4, c->stream);
     if (e == hipSuccess)
-        e = c->mode == MPT_MODE_STRICT ? mpt_launch_unit_eval_strict(&p, kind, d_in, in_cols, d_out, out_cols, n, c->stream)
+        e = c->opt.mode == MPT_MODE_STRICT ? mpt_launch_unit_eval_strict(&p, kind, d_in, in_cols, d_out, out_cols, n, c->stream)
                                        : mpt_launch_unit_eval_fast(&p, kind, d_in, in_cols, d_out, out_cols, n, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * out_cols * 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1767,13 +1679,5 @@ extern "C" int mpt_reset_counters(mpt_ctx *c) {
 }
 
 extern "C" int mpt_kernel_time(mpt_ctx *c, double *ms, int *launches) {
-    if (use_ro(c)) return 1;
-    if (mpt_flush(c)) return 1;
-    HIP_TRY(hipStreamSynchronize(c->aux));
-    for (int k = 0; k < MPT_MAX_PIPE; k++) HIP_TRY(hipStreamSynchronize(c->rstream[k]));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    double total = 0;
-    if (c->render_timer.drain(&total, launches, c->event_pool)) return 1;
-    if (ms) *ms = total;
-    return 0;
+    return timer_readout(c, &mpt_ctx::render_timer, ms, nullptr, launches, true);
 }

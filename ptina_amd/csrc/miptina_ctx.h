@@ -4,6 +4,7 @@
 
 #include "../../include/miptina.h"
 #include "mpt_types.h"
+#include "mpt_options.h"
 #include "shade_feat.h"
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
@@ -329,32 +330,23 @@ struct MPT_INTERNAL MptLaunchTimer {
 };
 
 // ------------------------------------------------------------------ context
-enum { MPT_MAX_PIPE = 6 };
-
 struct mpt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     mpt_caps caps{};
 
-    // options
-    int mode = MPT_MODE_FAST, batch = 32, chunk = 0, count = 0, use_lds = 1, lds_block = 0, zero_copy = 1;
-    int lds_wide = 1;                                 // 1: scenes that fit LDS beside them walk the 4-wide nodes there (render_kernel_lds4), 0: the binary ones (render_kernel_lds)
-    int skip_dark = -1;                  // -1 auto (production build on, strict build off), 0 / 1 as set: do not trace shadow rays whose candidate direct light is exactly zero (production build: default;
-                                         // the strict build traces them like the reference unless the option is set explicitly to 1 there)
+    MptOptions opt;                      // everything mpt_set_option sets (mpt_options.h)
     int max_mtlid = -1;                  // largest material id of the model (-1: only the default material)
     int num_cus = 256;
     int clock_khz = 0;                   // hipDeviceProp_t.clockRate: peak shader clock (roofline peaks in bench.py)
-    int tile_w_shift = 3, tile_h_shift = 3;   // work-item tile 2^w x 2^h pixels
     int last_div = 1;                    // share of the chip the last launch took: 1/last_div of the CUs
     int last_kernel = 0;                 // what the last flush launched: MPT_KERNEL_* of lds_layout.h (0 binary gather, 1 LDS binary, 2 4-wide gather, 5 LDS 4-wide)
-    int shade_spec = 1;                  // 1: a scene whose feature mask (shade_feat.h) is empty runs the plain instantiation of render_kernel_lds4; 0: always the generic one (A/B, tests)
     int last_shade_feat = -1;            // the mask the last render launch was compiled for (MPT_FEAT_PLAIN / MPT_FEAT_GENERIC; -1: none yet)
 
     // film
     int nx = 0, ny = 0, x0 = 0, x1 = 0;
     int stripe_w = 0, stripe_idx = 0, stripe_mod = 1;   // stripe_w > 0: columns dealt out in stripes (mpt_set_stripes)
     MptFilmBufs fb;                      // the passes, the image staging and the denoiser's buffers; fb.cap: pixels allocated per pass
-    int denoise_lds = 1;                 // option "denoise_lds": the strides 1 and 2 filter from a tile in LDS (same bits as the gathers)
 
     // model (host copy kept for the tree build)
     int nfaces = 0;
@@ -364,10 +356,6 @@ struct mpt_ctx {
     bool tree_valid = false;
     int tree_depth = 0;                  // reference LBVH (strict build)
     int fast_depth = 0;                  // tree the fast build walks (SAH or LBVH)
-    int tree_kind = 1;                   // fast build: 1 = SAH re-partition of the LBVH's leaves, 0 = the LBVH itself
-    int gpu_build = 1;                   // 1 = LBVH built on the device (lbvh_build.hip), 0 = host build
-    int sah_max = 1 << 22;               // above this many faces the fast build walks the LBVH itself (the threaded host
-                                         // SAH pass takes ~0.2 s at 1 M faces; it was 1.5 s on one core, hence 2^18 in round 1)
     bool host_tree_valid = false;        // h_child/h_leaf/... mirror the device tree (lazily downloaded)
     // device-side build workspace
     MptModelBufs dmodel;
@@ -378,28 +366,17 @@ struct mpt_ctx {
     MptTriBufs tris;
     DevBuf<MptVec4> tfast;                            // production triangle records, 3 float4 each (derived from tgeo)
     DevBuf<MptVec4> qnode;                            // the same nodes, child boxes quantised to 8 bits, 4 float4 each
-    int use_quant = 1;
     DevBuf<MptVec4> wnode;                            // 4-wide nodes of the fast tree (gather kernel), 8 float4 each
     int wide_nodes = 0, wide_depth = 0;               // 0 nodes: not built (too deep)
     int wide_stack = 0;                               // stack levels a traversal of the 4-wide tree can ask for (exact from the host pass, 3 x depth + 2 from the device pass)
     float wide_ratio = 1.f;                           // expected fetches per ray, wide / binary (surface-area sums)
-    int sah_exact_max = 8192;                         // host SAH pass: ranges up to this size are swept exactly (diagnostics)
-    int sah_inject_fail = 0;                          // test door: treat the device SAH pass as failed after it ran
     PinnedBuf<int> h_sahmeta; int *d_sahmeta = nullptr;   // host-pinned, device-mapped [32]: the SAH pass's per-level hand-back (sah_build.hip plan kernel)
     MptSahStats sah_stats{};                          // what the last device SAH pass did
     bool d_model_stale = true;                        // the device copy of the model (d_verts, d_mtlids) is behind the host's: the next device build uploads
-    int lane_hist = 0;                                // diagnostics: counting kernels fill the lane histogram (mpt_get_lane_hist)
-    int build_phases = 0;                             // diagnostics: synchronise at the end of every phase of mpt_build_tree and time it
     double build_phase_us[6] = { 0, 0, 0, 0, 0, 0 };   // upload | LBVH | SAH pass | triangle records | 4-wide collapse | total (host clock)
     int sah_fallback = 0;                             // last build: the device SAH pass gave up (1: error, 2: depth) and the host pass ran
-    int sah_build = -1;                               // SAH re-partition: 1 on the device (sah_build.hip), 0 host pass, -1 auto
-                                                      // (device above 8192 faces; below, all of the host pass's splits are exact
-                                                      // sweeps and it costs a millisecond)
     DevBuf<char> sah_ws;                              // one allocation (sah_ws.cap bytes), carved up in build_sah_device
-    int wide_build = 1;                               // 1: the 4-wide collapse runs on the device (wide_build.hip), 0: host pass
     MptWideBufs wb;
-    int use_wide = 1;                                 // option "wide": 1 walk the 4-wide nodes when the scene does not fit LDS
-                                                      // (default), 0 the binary tree
     // overflow strips of the wide kernel's per-lane stacks: one per ring slot, because launches of different slots
     // are resident together and index their strips by block and lane only
     DevBuf<int> stack_spill2[MPT_MAX_PIPE];
@@ -455,17 +432,11 @@ struct mpt_ctx {
     size_t stress_bytes = 0;
     hipStream_t aux = nullptr;                        // Sobol advances + queue resets of the pipelined batches
     hipEvent_t ev_sobol2[MPT_MAX_PIPE] = {};          // Sobol points + zeroed queue heads of the batch on rstream[k] ready
-    int pipe_depth = 0;                               // batches in flight (slots of P / partial / queue heads); 0 = auto
-    int reserve_cus = 0;                              // CUs no persistent workgroup claims (experiments: see mpt_flush)
-    int grid_div = 0;                                 // each launch takes 1/grid_div of the CUs; 0 = auto
     int cur_depth = 2, cur_div = 1;                   // what the last launch used
     hipEvent_t ev_film = nullptr;                     // main-stream work on the film (combine, clear, gather) a finalising launch must see
-    // tail finalisation (render_kernel.hip finalise_tiles): option "finalise" (1 = launches that find the ring idle sum, resolve and
-    // write out their tiles themselves; 0 = always the combine pass); launch_seq numbers the launches (slab tags);
+    // tail finalisation (render_kernel.hip finalise_tiles, option "finalise"): launch_seq numbers the launches (slab tags);
     // film_version counts the changes of pass 0; hint_image = where the next mpt_get_image(0) wants the image (mpt_hint_image);
     // early_* = the image a finalising launch has written (or is writing) and the film version it shows
-    int finalise = 1;
-    int spin_us = 20000;                              // mpt_get_image polls a finalising launch for this long before it blocks
     unsigned launch_seq = 0;
     unsigned tag_epoch = 0;                           // launch_seq / MPT_TAG_PERIOD when the slabs were last zeroed
     unsigned tag_wraps = 0;                           // times the slab tags came round (every slab zeroed): a test reads it
@@ -488,7 +459,6 @@ struct mpt_ctx {
     DevBuf<unsigned int> d_work2[MPT_MAX_PIPE];
 
     // measurement
-    int timeline = 0;                    // 1: the LDS kernel records per-wave timestamps of its last launch
     DevBuf<unsigned long long> d_timeline;
     int timeline_waves = 0;
     DevBuf<unsigned long long> d_counters;

@@ -16,7 +16,7 @@ struct BuildClock {
         t0 = t = std::chrono::steady_clock::now();
     }
     void mark(int k) {
-        if (c->build_phases) (void)hipStreamSynchronize(c->stream);
+        if (c->opt.build_phases) (void)hipStreamSynchronize(c->stream);
         const auto now = std::chrono::steady_clock::now();
         c->build_phase_us[k] += std::chrono::duration<double, std::micro>(now - t).count();
         c->build_phase_us[5] = std::chrono::duration<double, std::micro>(now - t0).count();
@@ -227,7 +227,7 @@ static void leaf_box(const mpt_ctx *c, int slot, float *lo, float *hi) {
 static void run_sah(const mpt_ctx *c, SahBuild &sb) {
     const int n = c->nfaces;
     sb.n = n;
-    sb.exact_max = c->sah_exact_max;
+    sb.exact_max = c->opt.sah_exact_max;
     sb.lo.resize((size_t)n * 3); sb.hi.resize((size_t)n * 3); sb.ctr.resize((size_t)n * 3);
     for (int slot = 0; slot < n; slot++) {
         float l[3], h[3];
@@ -370,7 +370,7 @@ static int build_tree_host(mpt_ctx *c) {
     // the tree the fast build walks
     std::vector<int32_t> fchild((size_t)std::max(ni, 1) * 2, 0);
     std::vector<float> flo((size_t)std::max(ni, 1) * 3, 0.f), fhi((size_t)std::max(ni, 1) * 3, 0.f);
-    if (c->tree_kind == 1 && ni > 0) {
+    if (c->opt.tree == 1 && ni > 0) {
         SahBuild sb;
         run_sah(c, sb);
         fchild = sb.child; flo = sb.blo; fhi = sb.bhi;
@@ -447,7 +447,7 @@ static int build_sah_device(mpt_ctx *c) {
     hipError_t e = mpt_sah_build(&B, &depth, c->stream);
     // Neither is fatal: the caller falls back to the host pass, which re-packs c->nodes.fnode from the LBVH leaf order (a failed
     // device pass may have overwritten part of it) and has its own depth handling (round-3 ADVICE)
-    if (c->sah_inject_fail) e = hipErrorInvalidValue;       // test door: the device pass ran (and wrote c->nodes.fnode), then "failed"
+    if (c->opt.sah_inject_fail) e = hipErrorInvalidValue;       // test door: the device pass ran (and wrote c->nodes.fnode), then "failed"
     if (e != hipSuccess) { (void)hipGetLastError(); c->sah_fallback = 1; return 2; }
     if (depth + 2 > 64) { c->sah_fallback = 2; return 2; }
     c->fast_depth = depth;
@@ -504,9 +504,9 @@ static int build_tree_gpu(mpt_ctx *c, BuildClock &clk) {
     // auto: the host pass up to 8192 faces (all of its splits are exact sweeps there and it costs a millisecond or two: the trees
     // of the small scenes stay what they were), the device pass above (exact sweeps up to 512 triangles, up to 1024 bins per
     // axis above: sah_build.hip)
-    const bool sah_on_device = c->sah_build == 1 || (c->sah_build < 0 && n > 8192);
+    const bool sah_on_device = c->opt.sah_build == 1 || (c->opt.sah_build < 0 && n > 8192);
     c->sah_fallback = 0;
-    if (c->tree_kind == 1 && ni > 0 && n <= c->sah_max) {
+    if (c->opt.tree == 1 && ni > 0 && n <= c->opt.sah_max) {
         // SAH re-partition of the leaves: on the device (sah_build.hip: nothing comes back but the depth), or the host pass --
         // also when the device pass gives up (workspace, level or depth limits): both start from the LBVH's leaf order
         int r = (sah_on_device && n >= 2) ? build_sah_device(c) : 2;
@@ -701,7 +701,7 @@ static int make_wide_device(mpt_ctx *c) {
     return 0;
 }
 
-static int make_wide(mpt_ctx *c) { return c->wide_build ? make_wide_device(c) : make_wide_host(c); }
+static int make_wide(mpt_ctx *c) { return c->opt.wide_build ? make_wide_device(c) : make_wide_host(c); }
 
 // test / inspection: the 4-wide records the gather kernels walk -- wnode [nw][8] float4 (exact boxes), qnode [nw][4] float4
 // (8-bit boxes); any pointer may be NULL; *nw = number of wide nodes (0: not built)
@@ -719,7 +719,7 @@ extern "C" int mpt_get_wide(mpt_ctx *c, float *wnode, float *qnode, int cap_node
 extern "C" int mpt_build_tree(mpt_ctx *c) {
     if (use(c)) return 1;
     BuildClock clk(c);
-    if (c->gpu_build ? build_tree_gpu(c, clk) : build_tree_host(c)) return 1;
+    if (c->opt.gpu_build ? build_tree_gpu(c, clk) : build_tree_host(c)) return 1;
     clk.mark(2);
     // the production kernels' 48-byte triangle records, from the reference-order ones
     // (+ 1: record n is all NaNs -- the leaf an unused slot of a 4-wide node names; no ray can hit it)

@@ -605,6 +605,8 @@ def test_retired_kernel_options_are_refused(fresh):
                 for value in (1, 0):
                     with pytest.raises(RuntimeError, match="unknown option '%s'" % key):
                         ctx().set_option(key, value)
+                with pytest.raises(RuntimeError, match="unknown option '%s'" % key):
+                    ctx().get_option(key)
         eng.render()
         img = FilmTable().get_image().copy()
         reset_all()
