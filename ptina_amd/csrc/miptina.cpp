@@ -6,7 +6,6 @@
 // gather in comm.cpp.  No PyTorch, no Python: plain HIP runtime calls.
 
 #include "miptina_ctx.h"
-#include <chrono>
 
 // Up to MPT_MAX_PIPE render streams, the main stream and the aux stream carry work at the same time.
 // The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (4 unless told
@@ -50,7 +49,6 @@ int fail(const char *fmt, ...) {
     return 1;
 }
 
-
 extern "C" const char *mpt_last_error(void) { return g_err.c_str(); }
 extern "C" int mpt_version(void) { return 100; }
 
@@ -74,7 +72,7 @@ int use(mpt_ctx *c) {      // entry of calls that may change what the next rende
     // about to enqueue on the main stream (a Sobol reset, an upload, a film clear) must be behind the
     // ev_main the NEXT batch's aux / render streams wait for.
     c->main_dirty = true;
-    c->spec_valid = false;     // whatever this call changes, the points computed ahead are not trusted across it
+    c->spec.valid = false;     // whatever this call changes, the points computed ahead are not trusted across it
     return 0;
 }
 
@@ -97,9 +95,13 @@ static int upload_lights(mpt_ctx *c) {
     return 0;
 }
 
-static int make_render_streams(mpt_ctx *c) {
-    for (int k = 0; k < MPT_MAX_PIPE; k++)
-        if (!c->rstream[k]) HIP_TRY(hipStreamCreateWithFlags(&c->rstream[k], hipStreamNonBlocking));
+// Wait for everything the context has in flight: the aux stream, the ring's streams (ring = false: nothing the caller is about to
+// read was recorded on those, so the main stream alone) and the main stream.  mpt_destroy: a stream not made yet is skipped.
+static int wait_all(mpt_ctx *c, bool ring = true) {
+    if (ring && c->aux) HIP_TRY(hipStreamSynchronize(c->aux));
+    for (auto &slot : c->ring)
+        if (ring && slot.stream) HIP_TRY(hipStreamSynchronize(slot.stream));
+    if (c->stream) HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -125,50 +127,30 @@ extern "C" mpt_ctx *mpt_create(const mpt_caps *caps, int device) {
         return nullptr;
     };
     if (hipSetDevice(device) != hipSuccess) return bail("hipSetDevice");
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail("stream");
+    if (c->stream.create()) return bail("stream");
     if (c->mats.reserve((size_t)c->caps.max_materials + 1)) return bail("materials");   // + the default material's record
     if (c->images.reserve(std::max<size_t>(c->caps.max_textures, 1))) return bail("images");
     if (c->lights.reserve(MPT_MAX_LIGHTS)) return bail("lights");
     if (c->d_counters.reserve(MPT_COUNTER_WORDS)) return bail("counters");
     if (c->d_scratch.reserve(2)) return bail("scratch");
-    if (c->d_work.reserve(MPT_QUEUE_WORDS)) return bail("work counters");   // 8 queue heads, a cache line each
-    for (int k = 0; k < MPT_MAX_PIPE; k++) {
-        if (hipEventCreateWithFlags(&c->ev_sobol2[k], hipEventDisableTiming) != hipSuccess) return bail("event");
-        if (hipEventCreateWithFlags(&c->ev_render[k], hipEventDisableTiming) != hipSuccess) return bail("event");
-        if (hipEventCreateWithFlags(&c->ev_free[k], hipEventDisableTiming) != hipSuccess) return bail("event");
-        if (c->d_work2[k].reserve(MPT_QUEUE_WORDS)) return bail("work counters");
-        hipMemsetAsync(c->d_work2[k], 0, MPT_QUEUE_WORDS * sizeof(unsigned int), c->stream);
+    for (auto &slot : c->ring) {
+        if (slot.ready.create() || slot.rendered.create() || slot.consumed.create()) return bail("event");
+        if (slot.heads.reserve(MPT_QUEUE_WORDS)) return bail("work counters");
+        hipMemsetAsync(slot.heads, 0, MPT_QUEUE_WORDS * sizeof(unsigned int), c->stream);
     }
-    if (hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking) != hipSuccess) return bail("aux stream");
-    if (hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming) != hipSuccess) return bail("event");
-    if (hipEventCreateWithFlags(&c->ev_film, hipEventDisableTiming) != hipSuccess) return bail("event");
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
-            if (prop.multiProcessorCount > 0) c->num_cus = prop.multiProcessorCount;
-            c->clock_khz = prop.clockRate;
-        }
+    if (c->aux.create() || c->ev_main.create() || c->ev_film.create()) return bail("aux stream and events");
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
+        if (prop.multiProcessorCount > 0) c->num_cus = prop.multiProcessorCount;
+        c->clock_khz = prop.clockRate;
     }
-    if (make_render_streams(c)) return bail("render streams");
-    {
-        void *dp = nullptr;
-        if (c->h_watchdog.reserve(1, hipHostMallocMapped) ||
-            hipHostGetDevicePointer(&dp, c->h_watchdog, 0) != hipSuccess) return bail("pinned watchdog flag");
-        *c->h_watchdog = 0;
-        c->d_watchdog = (unsigned int *)dp;
-        void *dm = nullptr;
-        if (c->h_sahmeta.reserve(32, hipHostMallocMapped) ||
-            hipHostGetDevicePointer(&dm, c->h_sahmeta, 0) != hipSuccess) return bail("pinned build mailbox");
-        c->d_sahmeta = (int *)dm;
-        memset(c->h_sahmeta, 0, 32 * sizeof(int));
-        void *de = nullptr;
-        if (c->h_exposure.reserve(1, hipHostMallocMapped) ||
-            hipHostGetDevicePointer(&de, c->h_exposure, 0) != hipSuccess) return bail("pinned exposure word");
-        *c->h_exposure = 1.0f;
-        c->d_exposure = (float *)de;
-    }
+    for (auto &slot : c->ring)       // (made after the aux stream, as ever: the runtime deals its hardware queues out in this order)
+        if (slot.stream.create()) return bail("render streams");
+    if (c->watchdog.create(1)) return bail("pinned watchdog flag");
+    if (c->sah_mail.create(32)) return bail("pinned build mailbox");
+    if (c->display.exposure.create(1)) return bail("pinned exposure word");
+    *c->display.exposure.host = 1.0f;
     hipMemsetAsync(c->d_counters, 0, MPT_COUNTER_WORDS * sizeof(unsigned long long), c->stream);
-    hipMemsetAsync(c->d_work, 0, MPT_QUEUE_WORDS * sizeof(unsigned int), c->stream);
     {   // unset materials: factor 0 (field-zero, mtllib.py:12-13), texture -1 (deviation Q6)
         std::vector<MptMaterial> z((size_t)c->caps.max_materials + 1);
         for (auto &m : z) { memset(&m, 0, sizeof m); for (int k = 0; k < 12; k++) m.tex[k] = -1; }
@@ -191,31 +173,15 @@ extern "C" mpt_ctx *mpt_create(const mpt_caps *caps, int device) {
     return c;
 }
 
-// Everything the device and the streams still do for this context is waited for, the communicator, the streams and the events go,
-// and `delete` gives the memory back: every buffer is a DevBuf / PinnedBuf member.  Also the way out of a failed mpt_create, so
-// whatever was not created yet is skipped.
+// Everything the streams still do for this context is waited for, the communicator goes while the main stream still exists, and
+// `delete` gives everything else back: every buffer, stream and event is a member that owns it (miptina_ctx.h).  Also the way out
+// of a failed mpt_create: what was not made yet is skipped.
 extern "C" void mpt_destroy(mpt_ctx *c) {
     if (!c) return;
     hipSetDevice(c->device);
-    for (int k = 0; k < MPT_MAX_PIPE; k++) if (c->rstream[k]) hipStreamSynchronize(c->rstream[k]);
-    if (c->aux) { hipStreamSynchronize(c->aux); }
-    if (c->stream) hipStreamSynchronize(c->stream);
+    (void)wait_all(c);
+    if (c->stress_stream) hipStreamSynchronize(c->stress_stream);
     mpt_comm_release(c);
-    if (c->aux) hipStreamDestroy(c->aux);
-    if (c->probe_stream) hipStreamDestroy(c->probe_stream);
-    if (c->stress_stream) { hipStreamSynchronize(c->stress_stream); hipStreamDestroy(c->stress_stream); }
-    for (int k = 0; k < MPT_MAX_PIPE; k++) {
-        if (c->rstream[k]) hipStreamDestroy(c->rstream[k]);
-        if (c->ev_render[k]) hipEventDestroy(c->ev_render[k]);
-        if (c->ev_free[k]) hipEventDestroy(c->ev_free[k]);
-        if (c->ev_sobol2[k]) hipEventDestroy(c->ev_sobol2[k]);
-    }
-    if (c->ev_main) hipEventDestroy(c->ev_main);
-    if (c->ev_film) hipEventDestroy(c->ev_film);
-    for (MptLaunchTimer *t : { &c->render_timer, &c->mlt_timer, &c->brute_timer, &c->denoise_timer, &c->display_timer })
-        for (auto &ev : t->events) hipEventDestroy(ev);
-    for (auto &ev : c->event_pool) hipEventDestroy(ev);
-    if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -253,6 +219,13 @@ static bool is_locked_range(const void *p, size_t bytes) {
     if (it == g_host_bufs.begin()) return false;
     --it;
     return (uintptr_t)p + bytes <= it->first + it->second;
+}
+
+// the device alias of a caller array that is page-locked memory of ours, for kernels to write straight into (option "zero_copy"), or null
+static void *caller_alias(const mpt_ctx *c, void *p, size_t bytes) {
+    void *mapped = nullptr;
+    if (c->opt.zero_copy && is_locked_range(p, bytes) && hipHostGetDevicePointer(&mapped, p, 0) == hipSuccess) return mapped;
+    return nullptr;
 }
 
 // device -> caller buffer on the main stream, blocking
@@ -553,14 +526,13 @@ extern "C" int mpt_set_world_light(mpt_ctx *c, const float fac[4], int tex) {
 extern "C" int mpt_sobol_init(mpt_ctx *c, const int32_t *V, int rows, int dim) {
     if (use(c)) return 1;
     if (rows < 2 || dim < 1 || !V) return fail("bad sobol grid %dx%d", rows, dim);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->sV.release(); c->sX.release(); c->sX_spec.release(); c->sP.release();
-    HIP_TRY(hipStreamSynchronize(c->aux));
-    for (int k = 0; k < MPT_MAX_PIPE; k++) { HIP_TRY(hipStreamSynchronize(c->rstream[k])); c->sP2[k].release(); }
-    if (c->sV.reserve((size_t)rows * dim) || c->sX.reserve((size_t)dim) || c->sX_spec.reserve((size_t)dim) ||
+    if (wait_all(c)) return 1;
+    c->sV.release(); c->sX.release(); c->spec.X.release(); c->sP.release();
+    for (auto &slot : c->ring) slot.points.release();
+    if (c->sV.reserve((size_t)rows * dim) || c->sX.reserve((size_t)dim) || c->spec.X.reserve((size_t)dim) ||
         c->sP.reserve((size_t)MPT_MAX_BATCH * dim)) return 1;
-    for (int k = 0; k < MPT_MAX_PIPE; k++)
-        if (c->sP2[k].reserve((size_t)MPT_MAX_BATCH * dim)) return 1;
+    for (auto &slot : c->ring)
+        if (slot.points.reserve((size_t)MPT_MAX_BATCH * dim)) return 1;
     HIP_TRY(hipMemcpyAsync(c->sV, V, (size_t)rows * dim * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->sX, 0, (size_t)dim * sizeof(int), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -680,15 +652,8 @@ static int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes) {
     p.film0 = c->fb.film[0]; p.film1 = c->fb.film[1]; p.film2 = c->fb.film[2];
     p.counters = c->d_counters;
     p.lane_hist = c->opt.lane_hist;
-    p.watchdog = c->d_watchdog;
+    p.watchdog = c->watchdog.dev;
     return fill_scene_params(c, p);
-}
-
-static hipEvent_t get_event(mpt_ctx *c) {
-    hipEvent_t e = nullptr;
-    if (!c->event_pool.empty()) { e = c->event_pool.back(); c->event_pool.pop_back(); }
-    else hipEventCreate(&e);
-    return e;
 }
 
 // levels of the per-lane traversal stack of the gather, preview, Metropolis and brute-force kernels (two instantiations each)
@@ -705,7 +670,7 @@ struct BatchSlot {
     int k;
     hipStream_t rs;    // the render
     hipStream_t ss;    // fast build: the Sobol points and the zeroed queue heads of this batch are prepared on the aux
-                       // stream (never behind a render kernel), the render itself goes to rstream[k]
+                       // stream (never behind a render kernel), the render itself goes to the slot's own
 };
 
 // step 1 (fast build): how many launches share the chip and how many ring slots they rotate through
@@ -723,9 +688,7 @@ static int ring_policy(mpt_ctx *c, int B) {
     int depth = c->opt.pipe_depth > 0 ? c->opt.pipe_depth : (div == 1 ? 2 : std::min(div + 2, (int)MPT_MAX_PIPE));
     if (depth != c->cur_depth) {
         // slots are reused round-robin: let everything in flight finish before the ring changes size
-        HIP_TRY(hipStreamSynchronize(c->aux));
-        for (int q = 0; q < MPT_MAX_PIPE; q++) HIP_TRY(hipStreamSynchronize(c->rstream[q]));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (wait_all(c)) return 1;
         c->flip = 0;
     }
     c->cur_depth = depth; c->cur_div = div;
@@ -735,32 +698,32 @@ static int ring_policy(mpt_ctx *c, int B) {
 // step 2: the batch's Sobol points (p.P) and, if they were made ahead of time, its zeroed queue heads (*use_spec).  A batch
 // without tiles (p.ntiles == 0: an empty share) only moves the sampler.
 static int batch_points(mpt_ctx *c, MptRenderParams &p, const BatchSlot &s, int B, bool *use_spec) {
-    const int k = s.k;
+    MptRingSlot &slot = c->ring[s.k];
     if (s.fast) {
         if (c->main_dirty) {       // uploads / resets / option changes enqueued on the main stream come first
             HIP_TRY(hipEventRecord(c->ev_main, c->stream));
             c->main_dirty = false;
         }
         HIP_TRY(hipStreamWaitEvent(s.ss, c->ev_main, 0));
-        HIP_TRY(hipStreamWaitEvent(s.ss, c->ev_render[k], 0));   // the batch that last read sP2[k] / d_work2[k]
+        HIP_TRY(hipStreamWaitEvent(s.ss, slot.rendered, 0));   // the batch that last read the slot's points and queue heads
         HIP_TRY(hipStreamWaitEvent(s.rs, c->ev_main, 0));
-        p.P = c->sP2[k];
+        p.P = slot.points;
     }
     // the points (and zeroed queue heads) of this batch may have been prepared when the previous one was launched
-    *use_spec = s.fast && p.ntiles != 0 && c->spec_valid && c->spec_slot == k && c->spec_B == B && c->spec_time == c->stime;
-    c->spec_valid = false;
+    *use_spec = s.fast && p.ntiles != 0 && c->spec.valid && c->spec.slot == s.k && c->spec.B == B && c->spec.time == c->stime;
+    c->spec.valid = false;
     if (p.ntiles == 0) {
-        if (sobol_advance(c, B, 0, s.ss, s.fast ? c->sP2[k] : nullptr)) return 1;
-        if (s.fast) { HIP_TRY(hipEventRecord(c->ev_sobol2[k], s.ss)); HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_sobol2[k], 0)); }
+        if (sobol_advance(c, B, 0, s.ss, s.fast ? slot.points.p : nullptr)) return 1;
+        if (s.fast) { HIP_TRY(hipEventRecord(slot.ready, s.ss)); HIP_TRY(hipStreamWaitEvent(c->stream, slot.ready, 0)); }
         return 0;
     }
     if (*use_spec) {
         // the points AND the state this batch leaves behind were computed when the previous batch was launched: the sampler moves by
         // a swap of two pointers -- no kernel at launch time (round 3 ran an X-only update here, whose 83 small workgroups took
         // CUs just when the persistent render workgroups wanted them: half the workgroups of a 1/8-share launch started 35 us late)
-        c->sX.swap(c->sX_spec);
+        c->sX.swap(c->spec.X);
         c->stime = (int32_t)((uint32_t)c->stime + (uint32_t)B);
-    } else if (sobol_advance(c, B, B, s.ss, s.fast ? c->sP2[k] : nullptr)) return 1;
+    } else if (sobol_advance(c, B, B, s.ss, s.fast ? slot.points.p : nullptr)) return 1;
     return 0;
 }
 
@@ -807,19 +770,19 @@ static int work_items(const mpt_ctx *c, MptRenderParams &p, int B, bool fast) {
 // device, so it must not happen again on the second, third, ... batch of a run.  zero: fresh memory is zeroed on the main
 // stream; *grown: a slot was replaced.
 template <class T>
-static int grow_ring(mpt_ctx *c, DevBuf<T> (&buf)[MPT_MAX_PIPE], size_t need, bool zero, bool *grown) {
+static int grow_ring(mpt_ctx *c, DevBuf<T> MptRingSlot::*member, size_t need, bool zero, bool *grown) {
     for (int q = 0; q < c->cur_depth; q++)
-        if (need > buf[q].cap) {
+        if (DevBuf<T> &buf = c->ring[q].*member; need > buf.cap) {
             HIP_TRY(hipDeviceSynchronize());
-            if (buf[q].reserve(need, grown)) return 1;
-            if (zero) HIP_TRY(hipMemsetAsync(buf[q], 0, need * sizeof(T), c->stream));
+            if (buf.reserve(need, grown)) return 1;
+            if (zero) HIP_TRY(hipMemsetAsync(buf, 0, need * sizeof(T), c->stream));
         }
     return 0;
 }
 
 // step 4 (fast build): the sample slab of the ring's slots, this batch's queue heads, and what its render stream waits for
 static int slab_and_queue_heads(mpt_ctx *c, MptRenderParams &p, const BatchSlot &s, int B, int ccols, bool use_spec) {
-    const int k = s.k;
+    MptRingSlot &slot = c->ring[s.k];
     // one float4 per sample: [frame][pixel]; the combine pass sums frames in order
     // ... of this context's share only: its columns packed side by side, padded to whole work-item tiles
     p.partial_stride = ccols * c->ny;
@@ -828,19 +791,19 @@ static int slab_and_queue_heads(mpt_ctx *c, MptRenderParams &p, const BatchSlot 
     // hold one by accident -- and it does: the allocator hands back the slab of an earlier context, whose first
     // finalising launch used the very tag this context's first one will use
     bool zeroed = false;
-    if (grow_ring(c, c->partial2, need, true, &zeroed)) return 1;
+    if (grow_ring(c, &MptRingSlot::slab, need, true, &zeroed)) return 1;
     // ... and the zeros must be there before any launch of the ring writes or reads the slab: the render streams are not
     // ordered behind the stream that zeroes, and a memset may return before it is done.  (Seen in the full GPU test run as a
     // 2048 x 2048 film with single samples of an earlier test's render in it: its 2 GiB slabs take a millisecond to zero.)
     if (zeroed) HIP_TRY(hipStreamSynchronize(c->stream));
-    p.partial = c->partial2[k];
-    p.work_counter = c->d_work2[k];
+    p.partial = slot.slab;
+    p.work_counter = slot.heads;
     if (!use_spec) {
-        HIP_TRY(hipMemsetAsync(c->d_work2[k], 0, MPT_QUEUE_WORDS * sizeof(unsigned int), s.ss));   // 8 queue heads + the finalisation's tile counter
-        HIP_TRY(hipEventRecord(c->ev_sobol2[k], s.ss));
+        HIP_TRY(hipMemsetAsync(slot.heads, 0, MPT_QUEUE_WORDS * sizeof(unsigned int), s.ss));   // 8 queue heads + the finalisation's tile counter
+        HIP_TRY(hipEventRecord(slot.ready, s.ss));
     }
-    HIP_TRY(hipStreamWaitEvent(s.rs, c->ev_sobol2[k], 0));
-    HIP_TRY(hipStreamWaitEvent(s.rs, c->ev_free[k], 0));   // combine of the batch that last used partial[k]
+    HIP_TRY(hipStreamWaitEvent(s.rs, slot.ready, 0));
+    HIP_TRY(hipStreamWaitEvent(s.rs, slot.consumed, 0));   // combine of the batch that last used this slab
     return 0;
 }
 
@@ -863,7 +826,7 @@ static int launch_share(mpt_ctx *c, bool fast, bool *ring_idle, int *launch_cus)
     *ring_idle = fast;
     if (fast && ((launch_div > 1 && c->opt.grid_div <= 0) || c->opt.finalise)) {
         for (int q = 0; q < c->cur_depth && *ring_idle; q++) {
-            hipError_t st = hipEventQuery(c->ev_render[q]);
+            hipError_t st = hipEventQuery(c->ring[q].rendered);
             if (st == hipErrorNotReady) *ring_idle = false;
             else if (st != hipSuccess) HIP_TRY(st);
         }
@@ -883,8 +846,8 @@ static int size_launch_buffers(mpt_ctx *c, MptRenderParams &p, int k, int kernel
         const size_t need_spill = (size_t)*wide_blocks * MPT_BLOCK * 128;   // >= SpillStack::SPILL entries per lane (128 - LDS levels)
         // one strip PER SLOT: the launches of different slots overlap, and a strip is indexed by block and lane only
         bool grown = false;
-        if (grow_ring(c, c->stack_spill2, need_spill, false, &grown)) return 1;
-        p.stack_spill = c->stack_spill2[k];
+        if (grow_ring(c, &MptRingSlot::spill, need_spill, false, &grown)) return 1;
+        p.stack_spill = c->ring[k].spill;
     }
     const bool lds_kernel = kernel == MPT_KERNEL_LDS || kernel == MPT_KERNEL_LDS4;
     // Lanes per persistent workgroup of the LDS-resident kernel.  A launch that gives a lane fewer than six samples (an eighth
@@ -934,12 +897,12 @@ static int setup_finalisation(mpt_ctx *c, MptRenderParams &p, const BatchSlot &s
     if (epoch != c->tag_epoch) {             // (told by the epoch, not by phase == 0: the launch with that number may have kept the combine pass)
         c->tag_epoch = epoch;
         HIP_TRY(hipStreamSynchronize(c->stream));
-        for (int q = 0; q < MPT_MAX_PIPE; q++)
-            if (c->partial2[q]) HIP_TRY(hipMemsetAsync(c->partial2[q], 0, c->partial2[q].cap * sizeof(MptVec4), s.rs));
+        for (auto &slot : c->ring)
+            if (slot.slab) HIP_TRY(hipMemsetAsync(slot.slab, 0, slot.slab.cap * sizeof(MptVec4), s.rs));
         HIP_TRY(hipStreamSynchronize(s.rs));
         c->tag_wraps++;
     }
-    p.fin_counter = c->d_work2[s.k] + 8 * MPT_QUEUE_STRIDE;
+    p.fin_counter = c->ring[s.k].heads + 8 * MPT_QUEUE_STRIDE;
     p.slab_tag = (unsigned)MPT_TAG_FIRST + phase;
     // everything the main stream still has to do to the film (an earlier batch's combine, a clear, a gather) comes first --
     // nothing, when the stream is idle (a step that ended with a read-back): then the event pair (8 us of API calls in front of
@@ -951,11 +914,9 @@ static int setup_finalisation(mpt_ctx *c, MptRenderParams &p, const BatchSlot &s
     } else if (main_busy != hipSuccess) HIP_TRY(main_busy);
     // the resolved image as well, if the caller has said where get_image() will want it and this share is the whole film
     const size_t img_bytes = (size_t)c->nx * c->ny * sizeof(MptVec4);
-    void *mapped = nullptr;
-    if (c->hint_image && c->opt.finalise == 1 && c->opt.zero_copy && c->x0 == 0 && c->x1 == c->nx && c->stripe_w == 0 && is_locked_range(c->hint_image, img_bytes) &&
-        hipHostGetDevicePointer(&mapped, c->hint_image, 0) == hipSuccess && mapped) {
-        p.image_out = (MptVec4 *)mapped;
-        c->early_ptr = c->hint_image; c->early_version = c->film_version; c->early_stream = s.rs;
+    if (c->early.hint && c->opt.finalise == 1 && c->x0 == 0 && c->x1 == c->nx && c->stripe_w == 0 &&
+        (p.image_out = (MptVec4 *)caller_alias(c, c->early.hint, img_bytes)) != nullptr) {
+        c->early.ptr = c->early.hint; c->early.version = c->film_version; c->early.stream = s.rs;
     }
     return 0;
 }
@@ -966,8 +927,8 @@ static int launch_render(mpt_ctx *c, const MptRenderParams &p, const BatchSlot &
     // SHADE compiled for what the scene uses: the LDS-resident 4-wide kernel has a plain instantiation, every other kernel the generic code
     const int shade_feat = kc.kernel == MPT_KERNEL_LDS4 ? shade_feat_instantiation(scene_feat_now(c), c->opt.shade_spec) : MPT_FEAT_GENERIC;
     const int stack = gather_stack_levels(c);
-    hipEvent_t e0 = get_event(c), e1 = get_event(c);
-    HIP_TRY(hipEventRecord(e0, s.rs));
+    MptTimedSpan span(c->render_timer, s.rs);
+    HIP_TRY(span.begun);
     switch (kc.kernel) {
     case MPT_KERNEL_LDS4: HIP_TRY(mpt_launch_render_lds4(&p, launch_cus, lds_block, (size_t)kc.lds_bytes, c->opt.count, shade_feat, s.rs)); break;
     case MPT_KERNEL_LDS: HIP_TRY(mpt_launch_render_lds(&p, launch_cus, lds_block, (size_t)kc.lds_bytes, c->opt.count, s.rs)); break;
@@ -978,40 +939,40 @@ static int launch_render(mpt_ctx *c, const MptRenderParams &p, const BatchSlot &
     }
     c->last_shade_feat = shade_feat;
     c->last_kernel = kc.kernel;
-    HIP_TRY(hipEventRecord(e1, s.rs));
-    c->render_timer.record({ e0, e1 }, c->event_pool);
+    HIP_TRY(span.end());
     return 0;
 }
 
 // step 9 (fast build), behind the launch: the main stream is ordered after it, the combine pass, the next batch's points
 static int behind_launch(mpt_ctx *c, const MptRenderParams &p, const BatchSlot &s, int B, bool fin) {
-    const int k = s.k;
+    MptRingSlot &slot = c->ring[s.k];
     // everything later on the main stream (combine, gather, resolve, read-backs, scene changes) is
     // ordered after this render; the next batch, on the other stream, is not
-    HIP_TRY(hipEventRecord(c->ev_render[k], s.rs));
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_render[k], 0));
+    HIP_TRY(hipEventRecord(slot.rendered, s.rs));
+    HIP_TRY(hipStreamWaitEvent(c->stream, slot.rendered, 0));
     if (!fin)
-        HIP_TRY(mpt_launch_combine(c->fb.film[0], c->partial2[k], c->ny, c->x0, c->x1, p.stripe_w, p.stripe_pitch,
+        HIP_TRY(mpt_launch_combine(c->fb.film[0], slot.slab, c->ny, c->x0, c->x1, p.stripe_w, p.stripe_pitch,
                                    p.partial_stride / std::max(c->ny, 1), B, c->stream));
-    HIP_TRY(hipEventRecord(c->ev_free[k], c->stream));      // (a finalising launch has consumed its slab itself)
+    HIP_TRY(hipEventRecord(slot.consumed, c->stream));      // (a finalising launch has consumed its slab itself)
     // Ahead of time, on the aux stream: the Sobol points and zeroed queue heads of the NEXT batch, assuming it
     // has as many frames as this one and uses the next ring slot (the sampler's future is deterministic; its
     // state X moves only when that batch is really launched).  Takes 25 us of Sobol kernel + memset off the
     // head of every step.
     const int k2 = c->flip % c->cur_depth;
-    if (k2 != k) {
-        HIP_TRY(hipStreamWaitEvent(s.ss, c->ev_render[k2], 0));   // the batch that last read sP2[k2] / d_work2[k2]
-        HIP_TRY(mpt_launch_sobol_update(c->sX, c->sX_spec, c->sV, c->sP2[k2], c->sdim, c->srows, c->stime, B, B, 1, s.ss));
-        HIP_TRY(hipMemsetAsync(c->d_work2[k2], 0, MPT_QUEUE_WORDS * sizeof(unsigned int), s.ss));
-        HIP_TRY(hipEventRecord(c->ev_sobol2[k2], s.ss));
-        c->spec_valid = true; c->spec_slot = k2; c->spec_B = B; c->spec_time = c->stime;
+    if (k2 != s.k) {
+        MptRingSlot &next = c->ring[k2];
+        HIP_TRY(hipStreamWaitEvent(s.ss, next.rendered, 0));   // the batch that last read that slot's points and queue heads
+        HIP_TRY(mpt_launch_sobol_update(c->sX, c->spec.X, c->sV, next.points, c->sdim, c->srows, c->stime, B, B, 1, s.ss));
+        HIP_TRY(hipMemsetAsync(next.heads, 0, MPT_QUEUE_WORDS * sizeof(unsigned int), s.ss));
+        HIP_TRY(hipEventRecord(next.ready, s.ss));
+        c->spec.valid = true; c->spec.slot = k2; c->spec.B = B; c->spec.time = c->stime;
     }
     return 0;
 }
 
 extern "C" int mpt_flush(mpt_ctx *c) {
     if (!c) return fail("null context");
-    if (c->mlt_pending && mlt_flush(c)) return 1;    // (Metropolis iterations and PathEngine frames are never pending together)
+    if (c->mlt.pending && mlt_flush(c)) return 1;    // (Metropolis iterations and PathEngine frames are never pending together)
     if (c->pending == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
     const int B = c->pending;
@@ -1023,7 +984,7 @@ extern "C" int mpt_flush(mpt_ctx *c) {
     BatchSlot s;
     s.fast = fast;
     s.k = fast ? (c->flip++ % c->cur_depth) : 0;
-    s.rs = fast ? c->rstream[s.k] : c->stream;
+    s.rs = fast ? c->ring[s.k].stream : c->stream;
     s.ss = fast ? c->aux : c->stream;
     bool use_spec = false;
     if (batch_points(c, p, s, B, &use_spec)) return 1;                                     // 2
@@ -1046,7 +1007,7 @@ extern "C" int mpt_render(mpt_ctx *c, int nframes) {                           /
     if (!c) return fail("null context");
     if (nframes < 0) return fail("nframes must be >= 0");
     if (check_ready(c)) return 1;                     // fail at the call, not at the deferred launch
-    if (c->mlt_pending && mlt_flush(c)) return 1;     // the film sum follows call order: Metropolis iterations enqueued before go first
+    if (c->mlt.pending && mlt_flush(c)) return 1;     // the film sum follows call order: Metropolis iterations enqueued before go first
     while (nframes > 0) {
         int room = c->opt.batch - c->pending;
         int take = std::min(room, nframes);
@@ -1081,42 +1042,41 @@ extern "C" int mpt_render_preview(mpt_ctx *c, int nframes) {                   /
 enum { MPT_MLT_SLAB_RECORDS = 1 << 24 };      // splat records per launch (20 B each, twice for the sort): larger requests are split
 
 static int mlt_check(mpt_ctx *c) {
-    if (c->mlt_n <= 0) return fail("Metropolis engine not reset: call mpt_mlt_reset first");
+    if (c->mlt.n <= 0) return fail("Metropolis engine not reset: call mpt_mlt_reset first");
     return 0;
 }
 
 // launch the enqueued iterations: chain kernel + splat pass per slab-sized piece, in iteration order
 static int mlt_flush(mpt_ctx *c) {
-    int n = c->mlt_pending;
-    c->mlt_pending = 0;
+    int n = c->mlt.pending;
+    c->mlt.pending = 0;
     if (n <= 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
     MptRenderParams p;
     if (fill_params(c, p, 1)) return 1;
-    const int nch = c->mlt_n;
+    const int nch = c->mlt.n;
     const int kmax = std::max(1, (int)(MPT_MLT_SLAB_RECORDS / nch));
     const int K0 = std::min(n, kmax);
     const size_t recs = (size_t)K0 * nch, npix = (size_t)c->nx * c->ny;
-    if (recs > c->slab.cap || npix > c->slab.runs_cap) {
+    if (recs > c->mlt.slab.cap || npix > c->mlt.slab.runs_cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->slab.reserve(recs, npix)) return 1;
+        if (c->mlt.slab.reserve(recs, npix)) return 1;
     }
     const int stack = gather_stack_levels(c);
     while (n > 0) {
         const int K = std::min(n, kmax);
         MptMltArgs a;
-        a.X = c->mlt_X; a.L = c->mlt_L; a.bit = c->mlt_bit; a.keys = c->slab.keys; a.vals = c->slab.vals;
-        a.nchains = nch; a.t0 = c->mlt_iter; a.K = K; a.seed = c->mlt_seed; a.lsp = c->mlt_lsp; a.sigma = c->mlt_sigma;
-        hipEvent_t e0 = get_event(c), e1 = get_event(c), e2 = get_event(c);
-        HIP_TRY(hipEventRecord(e0, c->stream));
+        a.X = c->mlt.X; a.L = c->mlt.L; a.bit = c->mlt.bit; a.keys = c->mlt.slab.keys; a.vals = c->mlt.slab.vals;
+        a.nchains = nch; a.t0 = c->mlt.iter; a.K = K; a.seed = c->mlt.seed; a.lsp = c->mlt.lsp; a.sigma = c->mlt.sigma;
+        MptTimedSpan span(c->mlt.timer, c->stream);
+        HIP_TRY(span.begun);
         if (c->opt.mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_mlt_chain_strict(&p, &a, stack, c->stream));
         else HIP_TRY(mpt_launch_mlt_chain_fast(&p, &a, stack, c->stream));
-        HIP_TRY(hipEventRecord(e1, c->stream));
-        HIP_TRY(mpt_launch_mlt_splat(c->fb.film[0], c->slab.keys, c->slab.vals, c->slab.keys2, c->slab.vals2, c->slab.tmp, c->slab.tmp.cap,
-                                     c->slab.runs, K * nch, (int)npix, c->stream));
-        HIP_TRY(hipEventRecord(e2, c->stream));
-        c->mlt_timer.record({ e0, e1, e2 }, c->event_pool);
-        c->mlt_iter += K;
+        HIP_TRY(span.mark());
+        HIP_TRY(mpt_launch_mlt_splat(c->fb.film[0], c->mlt.slab.keys, c->mlt.slab.vals, c->mlt.slab.keys_sorted, c->mlt.slab.vals_sorted,
+                                     c->mlt.slab.tmp, c->mlt.slab.tmp.cap, c->mlt.slab.runs, K * nch, (int)npix, c->stream));
+        HIP_TRY(span.end());
+        c->mlt.iter += K;
         n -= K;
     }
     c->film_version++;           // pass 0 has changed: an early image of an earlier PathEngine launch is stale
@@ -1127,20 +1087,20 @@ static int mlt_flush(mpt_ctx *c) {
 extern "C" int mpt_mlt_reset(mpt_ctx *c, int nchains, uint32_t seed) {         // mltpath.py:31-37
     if (use(c)) return 1;
     if (nchains <= 0 || nchains > (1 << 24)) return fail("nchains %d outside [1, 2^24]", nchains);
-    if (nchains != c->mlt_n) {
+    if (nchains != c->mlt.n) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        c->mlt_X.release(); c->mlt_L.release(); c->mlt_bit.release(); c->mlt_n = 0;
-        if (c->mlt_X.reserve((size_t)nchains * 2 * 32) || c->mlt_L.reserve((size_t)nchains * 3) || c->mlt_bit.reserve((size_t)nchains)) return 1;
-        c->mlt_n = nchains;
+        c->mlt.X.release(); c->mlt.L.release(); c->mlt.bit.release(); c->mlt.n = 0;
+        if (c->mlt.X.reserve((size_t)nchains * 2 * 32) || c->mlt.L.reserve((size_t)nchains * 3) || c->mlt.bit.reserve((size_t)nchains)) return 1;
+        c->mlt.n = nchains;
     }
-    c->mlt_seed = seed; c->mlt_iter = 0; c->mlt_pending = 0;
-    HIP_TRY(mpt_launch_mlt_reset(c->mlt_X, c->mlt_L, c->mlt_bit, nchains, seed, c->stream));
+    c->mlt.seed = seed; c->mlt.iter = 0; c->mlt.pending = 0;
+    HIP_TRY(mpt_launch_mlt_reset(c->mlt.X, c->mlt.L, c->mlt.bit, nchains, seed, c->stream));
     return 0;
 }
 
 extern "C" int mpt_mlt_set_param(mpt_ctx *c, float lsp, float sigma) {       // mltpath.py:18-27: LSP[None], Sigma[None]
     if (use(c)) return 1;                   // iterations enqueued so far run with the parameters they were enqueued under
-    c->mlt_lsp = lsp; c->mlt_sigma = sigma;
+    c->mlt.lsp = lsp; c->mlt.sigma = sigma;
     return 0;
 }
 
@@ -1152,9 +1112,9 @@ extern "C" int mpt_mlt_render(mpt_ctx *c, int iterations) {                    /
     if (!c->tree_valid) return fail("BVH not built: call build_tree() after load_model()");
     if (c->stripe_w != 0 || c->x0 != 0 || c->x1 != c->nx || c->comm)
         return fail("the Metropolis engine renders the whole film on one GPU: no slab / stripe split or communicator may be set");
-    if ((long long)c->mlt_iter + c->mlt_pending + iterations >= (1ll << 31)) return fail("Metropolis iteration counter would overflow");
+    if ((long long)c->mlt.iter + c->mlt.pending + iterations >= (1ll << 31)) return fail("Metropolis iteration counter would overflow");
     if (c->pending && mpt_flush(c)) return 1;      // PathEngine frames enqueued before go first
-    c->mlt_pending += iterations;
+    c->mlt.pending += iterations;
     return 0;
 }
 
@@ -1162,17 +1122,17 @@ extern "C" int mpt_mlt_get_state(mpt_ctx *c, float *X, float *L, int *iteration)
     if (use_ro(c)) return 1;
     if (mpt_flush(c)) return 1;
     if (mlt_check(c)) return 1;
-    const size_t n = (size_t)c->mlt_n;
+    const size_t n = (size_t)c->mlt.n;
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (X) {
         std::vector<float> both(n * 2 * 32);
         std::vector<int32_t> bit(n);
-        HIP_TRY(hipMemcpy(both.data(), c->mlt_X, both.size() * sizeof(float), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(bit.data(), c->mlt_bit, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(both.data(), c->mlt.X, both.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(bit.data(), c->mlt.bit, n * sizeof(int32_t), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; i++) memcpy(X + i * 32, both.data() + ((size_t)(bit[i] & 1) * n + i) * 32, 32 * sizeof(float));
     }
-    if (L) HIP_TRY(hipMemcpy(L, c->mlt_L, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (iteration) *iteration = c->mlt_iter;
+    if (L) HIP_TRY(hipMemcpy(L, c->mlt.L, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (iteration) *iteration = c->mlt.iter;
     return 0;
 }
 
@@ -1180,13 +1140,13 @@ extern "C" int mpt_mlt_set_state(mpt_ctx *c, const float *X, const float *L, int
     if (use(c)) return 1;
     if (mlt_check(c)) return 1;
     if (!X || !L || iteration < 0) return fail("mpt_mlt_set_state: X and L must be given and iteration >= 0");
-    const size_t n = (size_t)c->mlt_n;
+    const size_t n = (size_t)c->mlt.n;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(c->mlt_X, X, n * 32 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->mlt_L, L, n * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(c->mlt_bit, 0, n * sizeof(int32_t)));
+    HIP_TRY(hipMemcpy(c->mlt.X, X, n * 32 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->mlt.L, L, n * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(c->mlt.bit, 0, n * sizeof(int32_t)));
     HIP_TRY(hipDeviceSynchronize());
-    c->mlt_iter = iteration;
+    c->mlt.iter = iteration;
     return 0;
 }
 
@@ -1211,23 +1171,18 @@ extern "C" int mpt_mlt_trace(mpt_ctx *c, const float *X, float *rgb, int n) {
 
 // The read-out of an engine's launch timer: what is enqueued is launched, the main stream (and, for launches recorded on them, the
 // aux and render streams) waited for, and the launches' segments summed: ms0, and ms1 where a launch has two.
-static int timer_readout(mpt_ctx *c, MptLaunchTimer mpt_ctx::*timer, double *ms0, double *ms1, int *launches, bool render_streams = false) {
-    if (use_ro(c)) return 1;
+static int timer_readout(mpt_ctx *c, MptLaunchTimer &timer, double *ms0, double *ms1, int *launches, bool render_streams = false) {
     if (mpt_flush(c)) return 1;
-    if (render_streams) {
-        HIP_TRY(hipStreamSynchronize(c->aux));
-        for (int k = 0; k < MPT_MAX_PIPE; k++) HIP_TRY(hipStreamSynchronize(c->rstream[k]));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (wait_all(c, render_streams)) return 1;
     double seg[2] = { 0, 0 };
-    if ((c->*timer).drain(seg, launches, c->event_pool)) return 1;
+    if (timer.drain(seg, launches)) return 1;
     if (ms0) *ms0 = seg[0];
     if (ms1) *ms1 = seg[1];
     return 0;
 }
 
 extern "C" int mpt_mlt_kernel_time(mpt_ctx *c, double *chain_ms, double *splat_ms, int *launches) {
-    return timer_readout(c, &mpt_ctx::mlt_timer, chain_ms, splat_ms, launches);
+    return use_ro(c) || timer_readout(c, c->mlt.timer, chain_ms, splat_ms, launches);
 }
 
 // ------------------------------------------------------------------ brute-force engine (BruteEngine, engine/brute.py)
@@ -1247,12 +1202,11 @@ extern "C" int mpt_render_brute(mpt_ctx *c, int nframes) {                     /
         p.chunk = B; p.nchunks = 1;
         const int stack = gather_stack_levels(c);
         if (p.ntiles) {
-            hipEvent_t e0 = get_event(c), e1 = get_event(c);
-            HIP_TRY(hipEventRecord(e0, c->stream));
+            MptTimedSpan span(c->brute_timer, c->stream);
+            HIP_TRY(span.begun);
             if (c->opt.mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_brute_strict(&p, p.ntiles, stack, c->stream));
             else HIP_TRY(mpt_launch_brute_fast(&p, p.ntiles, stack, c->stream));
-            HIP_TRY(hipEventRecord(e1, c->stream));
-            c->brute_timer.record({ e0, e1 }, c->event_pool);
+            HIP_TRY(span.end());
             c->film_version++;       // pass 0 has changed: an early image of an earlier PathEngine launch is stale
         }
         nframes -= B;
@@ -1262,7 +1216,7 @@ extern "C" int mpt_render_brute(mpt_ctx *c, int nframes) {                     /
 }
 
 extern "C" int mpt_brute_kernel_time(mpt_ctx *c, double *ms, int *launches) {
-    return timer_readout(c, &mpt_ctx::brute_timer, ms, nullptr, launches);
+    return use_ro(c) || timer_readout(c, c->brute_timer, ms, nullptr, launches);
 }
 
 // a persistent render kernel that had to be stopped by its watchdog leaves a flag behind (in host-pinned
@@ -1270,7 +1224,7 @@ extern "C" int mpt_brute_kernel_time(mpt_ctx *c, double *ms, int *launches) {
 int check_watchdog(mpt_ctx *c) {
     // read and re-arm: the failure is reported once, by the first read-back after it (the film holds
     // incomplete sums until the caller clears it)
-    if (__atomic_exchange_n(c->h_watchdog.p, 0u, __ATOMIC_ACQ_REL))
+    if (__atomic_exchange_n(c->watchdog.host.p, 0u, __ATOMIC_ACQ_REL))
         return fail("render kernel stopped by its watchdog (scheduler made no progress): film is incomplete");
     return 0;
 }
@@ -1278,9 +1232,7 @@ int check_watchdog(mpt_ctx *c) {
 extern "C" int mpt_synchronize(mpt_ctx *c) {                                   // worker.py:17-18
     if (use_ro(c)) return 1;
     if (mpt_flush(c)) return 1;
-    HIP_TRY(hipStreamSynchronize(c->aux));
-    for (int k = 0; k < MPT_MAX_PIPE; k++) HIP_TRY(hipStreamSynchronize(c->rstream[k]));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (wait_all(c)) return 1;
     return check_watchdog(c);
 }
 
@@ -1311,26 +1263,25 @@ extern "C" int mpt_resolve(mpt_ctx *c, int pass) {
 extern "C" int mpt_hint_image(mpt_ctx *c, int pass, float *out) {
     if (use_ro(c)) return 1;
     if (pass != 0) return 0;                   // only the path pass is finalised inside the render launch
-    if (c->hint_image == out) return 0;
+    if (c->early.hint == out) return 0;
     // the old array may be the one a launch in flight is writing its image into: the caller is free to let go of it after this call
-    if (c->early_ptr && c->early_ptr == c->hint_image) HIP_TRY(hipStreamSynchronize(c->stream));
-    c->hint_image = out;
-    c->early_ptr = nullptr;
+    if (c->early.ptr && c->early.ptr == c->early.hint) HIP_TRY(hipStreamSynchronize(c->stream));
+    c->early.hint = out;
+    c->early.ptr = nullptr;
     return 0;
 }
 
 extern "C" int mpt_get_image(mpt_ctx *c, int pass, float *out) {               // filmtable.py:47-63
     if (use_ro(c)) return 1;                   // validates the handle and makes the context's device current (round-3 ADVICE)
     const size_t bytes = (size_t)c->nx * c->ny * sizeof(MptVec4);
-    void *mapped = nullptr;
     if (pass == 0) {
         // The launch that rendered the frames may have written this very image already (tail finalisation, mpt_hint_image): then
         // there is nothing left to do but wait for it.  The hint is spent either way: the array is the caller's from here on.
         if (mpt_flush(c)) return 1;
-        const bool early = out && c->early_ptr == out && c->early_version == c->film_version;
-        if (c->hint_image == out || c->early_ptr == out) {
-            if (!early && c->early_ptr == out) HIP_TRY(hipStreamSynchronize(c->stream));    // (a stale image still being written)
-            c->hint_image = nullptr; c->early_ptr = nullptr;
+        const bool early = out && c->early.ptr == out && c->early.version == c->film_version;
+        if (c->early.hint == out || c->early.ptr == out) {
+            if (!early && c->early.ptr == out) HIP_TRY(hipStreamSynchronize(c->stream));    // (a stale image still being written)
+            c->early.hint = nullptr; c->early.ptr = nullptr;
         }
         if (early) {
             if (check_pass(c, pass)) return 1;
@@ -1342,17 +1293,17 @@ extern "C" int mpt_get_image(mpt_ctx *c, int pass, float *out) {               /
             if (c->opt.spin_us > 0) {
                 const auto t0 = std::chrono::steady_clock::now();
                 for (;;) {
-                    const hipError_t q = hipStreamQuery(c->early_stream);
+                    const hipError_t q = hipStreamQuery(c->early.stream);
                     if (q == hipSuccess) return check_watchdog(c);
                     if (q != hipErrorNotReady) HIP_TRY(q);
                     if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > (double)c->opt.spin_us) break;
                 }
             }
-            HIP_TRY(hipStreamSynchronize(c->early_stream));
+            HIP_TRY(hipStreamSynchronize(c->early.stream));
             return check_watchdog(c);
         }
     }
-    if (c->opt.zero_copy && is_locked_range(out, bytes) && hipHostGetDevicePointer(&mapped, out, 0) == hipSuccess && mapped) {
+    if (void *mapped = caller_alias(c, out, bytes)) {
         // the caller's array is page-locked memory of ours: the resolve pass writes the image straight into it over PCIe,
         // instead of into a device buffer that a DMA then copies (one dependent hop and the copy engine's start-up less)
         if (mpt_flush(c)) return 1;
@@ -1429,17 +1380,16 @@ extern "C" int mpt_get_denoised(mpt_ctx *c, const mpt_denoise_params *params, fl
     if (check_pass(c, 0)) return 1;
     const size_t npix = (size_t)c->nx * c->ny;
     const MptVec4 *img = nullptr;
-    hipEvent_t e0 = get_event(c), e1 = get_event(c);
-    HIP_TRY(hipEventRecord(e0, c->stream));
+    MptTimedSpan span(c->denoise_timer, c->stream);
+    HIP_TRY(span.begun);
     if (denoise_launches(c, p, &img)) return 1;
-    HIP_TRY(hipEventRecord(e1, c->stream));
-    c->denoise_timer.record({ e0, e1 }, c->event_pool);
+    HIP_TRY(span.end());
     if (read_back(c, out, img, npix * sizeof(MptVec4))) return 1;
     return check_watchdog(c);
 }
 
 extern "C" int mpt_denoise_kernel_time(mpt_ctx *c, double *ms, int *launches) {
-    return timer_readout(c, &mpt_ctx::denoise_timer, ms, nullptr, launches);
+    return use_ro(c) || timer_readout(c, c->denoise_timer, ms, nullptr, launches);
 }
 
 // ------------------------------------------------------------------ 8-bit display read-back (display.hip)
@@ -1465,7 +1415,7 @@ static int display_launches(mpt_ctx *c, const mpt_display_params &p, const MptDi
                             MptDisplayBufs &b, uint32_t *dst) {
     const float *e_dev = nullptr;
     if (p.exposure == 0.0f) {
-        HIP_TRY(mpt_launch_display_meter(src, (size_t)nx * ny, b.part, p.key, b.exposure, c->d_exposure, c->stream));
+        HIP_TRY(mpt_launch_display_meter(src, (size_t)nx * ny, b.part, p.key, b.exposure, c->display.exposure.dev, c->stream));
         e_dev = b.exposure;
     }
     HIP_TRY(mpt_launch_display_convert(src, dst, nx, ny, &a, e_dev, c->stream));
@@ -1476,7 +1426,7 @@ static int display_launches(mpt_ctx *c, const mpt_display_params &p, const MptDi
 static int display_finish(mpt_ctx *c, const mpt_display_params &p, bool direct, uint8_t *out, const uint32_t *dev, size_t npix, float *exposure_used) {
     if (direct) HIP_TRY(hipStreamSynchronize(c->stream));
     else if (read_back(c, out, dev, npix * 4)) return 1;
-    if (exposure_used) *exposure_used = p.exposure == 0.0f ? *(volatile float *)c->h_exposure.p : p.exposure;
+    if (exposure_used) *exposure_used = p.exposure == 0.0f ? *(volatile float *)c->display.exposure.host.p : p.exposure;
     return 0;
 }
 
@@ -1493,21 +1443,19 @@ extern "C" int mpt_get_display(mpt_ctx *c, const mpt_display_params *params, con
     if (mpt_flush(c)) return 1;
     if (check_pass(c, denoised ? 0 : p.source)) return 1;
     const size_t npix = (size_t)c->nx * c->ny;
-    void *mapped = nullptr;
-    const bool direct = c->opt.zero_copy && is_locked_range(out, npix * 4) && hipHostGetDevicePointer(&mapped, out, 0) == hipSuccess && mapped;
+    void *const direct = caller_alias(c, out, npix * 4);
     const MptVec4 *src = denoised ? nullptr : c->fb.film[p.source].p;
-    hipEvent_t e0 = get_event(c), e1 = get_event(c);
-    HIP_TRY(hipEventRecord(e0, c->stream));
+    MptTimedSpan span(c->display.timer, c->stream);
+    HIP_TRY(span.begun);
     if (denoised && denoise_launches(c, dp, &src)) return 1;       // the float image stays on the device
-    if (display_launches(c, p, a, src, c->nx, c->ny, c->fb.disp, direct ? (uint32_t *)mapped : c->fb.disp.rgba8.p)) return 1;
-    HIP_TRY(hipEventRecord(e1, c->stream));
-    c->display_timer.record({ e0, e1 }, c->event_pool);
-    if (display_finish(c, p, direct, out, c->fb.disp.rgba8, npix, exposure_used)) return 1;
+    if (display_launches(c, p, a, src, c->nx, c->ny, c->fb.disp, direct ? (uint32_t *)direct : c->fb.disp.rgba8.p)) return 1;
+    HIP_TRY(span.end());
+    if (display_finish(c, p, direct != nullptr, out, c->fb.disp.rgba8, npix, exposure_used)) return 1;
     return check_watchdog(c);
 }
 
 extern "C" int mpt_display_kernel_time(mpt_ctx *c, double *ms, int *launches) {
-    return timer_readout(c, &mpt_ctx::display_timer, ms, nullptr, launches);
+    return use_ro(c) || timer_readout(c, c->display.timer, ms, nullptr, launches);
 }
 
 // test door: the same launches on the caller's accumulators, in buffers of its own (no film pass, no film-owner buffer is touched)
@@ -1520,14 +1468,14 @@ extern "C" int mpt_display_eval(mpt_ctx *c, const mpt_display_params *params, co
     if (nx < 1 || ny < 1 || (long long)nx * ny > (long long)c->caps.max_filmsize)
         return fail("mpt_display_eval: film %dx%d outside 1 .. max_filmsize=%d pixels", nx, ny, c->caps.max_filmsize);
     const size_t npix = (size_t)nx * ny;
-    if (npix > c->door_raw.cap || npix > c->door_disp.cap) {
+    if (npix > c->display.raw.cap || npix > c->display.bufs.cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->door_raw.reserve(npix) || c->door_disp.reserve(npix)) return 1;
+        if (c->display.raw.reserve(npix) || c->display.bufs.reserve(npix)) return 1;
     }
-    HIP_TRY(hipMemcpyAsync(c->door_raw, raw, npix * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->display.raw, raw, npix * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));                      // (`raw` is pageable: the copy is staged, the caller's array is free again)
-    if (display_launches(c, p, a, c->door_raw, nx, ny, c->door_disp, c->door_disp.rgba8)) return 1;
-    return display_finish(c, p, false, out, c->door_disp.rgba8, npix, exposure_used);
+    if (display_launches(c, p, a, c->display.raw, nx, ny, c->display.bufs, c->display.bufs.rgba8)) return 1;
+    return display_finish(c, p, false, out, c->display.bufs.rgba8, npix, exposure_used);
 }
 
 // ------------------------------------------------------------------ measurement
@@ -1576,7 +1524,7 @@ extern "C" int mpt_probe_kernel(mpt_ctx *c, int threads, int lds_bytes, double *
     if (use_ro(c)) return 1;
     if (threads < 64 || threads > 1024 || lds_bytes < 4 * threads || lds_bytes > 64 * 1024)
         return fail("probe: threads in 64..1024, lds_bytes in 4*threads..65536");
-    if (!c->probe_stream) HIP_TRY(hipStreamCreateWithFlags(&c->probe_stream, hipStreamNonBlocking));
+    if (c->probe_stream.create()) return 1;
     auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(mpt_launch_probe(c->d_scratch + 1, threads, (size_t)lds_bytes, c->probe_stream));
     HIP_TRY(hipStreamSynchronize(c->probe_stream));
@@ -1591,7 +1539,7 @@ extern "C" int mpt_probe_kernel(mpt_ctx *c, int threads, int lds_bytes, double *
 extern "C" int mpt_stress_copies(mpt_ctx *c, int mbytes, int count) {
     if (use_ro(c)) return 1;
     if (mbytes < 1 || mbytes > 4096 || count < 0 || count > 100000) return fail("stress_copies: mbytes in 1..4096, count in 0..100000");
-    if (!c->stress_stream) HIP_TRY(hipStreamCreateWithFlags(&c->stress_stream, hipStreamNonBlocking));
+    if (c->stress_stream.create()) return 1;
     if (count == 0) { HIP_TRY(hipStreamSynchronize(c->stress_stream)); return 0; }
     const size_t bytes = (size_t)mbytes << 20;
     if (bytes != c->stress_bytes) {
@@ -1679,5 +1627,5 @@ extern "C" int mpt_reset_counters(mpt_ctx *c) {
 }
 
 extern "C" int mpt_kernel_time(mpt_ctx *c, double *ms, int *launches) {
-    return timer_readout(c, &mpt_ctx::render_timer, ms, nullptr, launches, true);
+    return use_ro(c) || timer_readout(c, c->render_timer, ms, nullptr, launches, true);
 }

@@ -15,7 +15,6 @@
 #include <cstdio>
 #include <chrono>
 #include <cstring>
-#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -105,16 +104,14 @@ MPT_INTERNAL int fail(const char *fmt, ...);
     } while (0)
 
 // ------------------------------------------------------------------ owned memory
+struct MptNoCopy { MptNoCopy() = default; MptNoCopy(const MptNoCopy &) = delete; MptNoCopy &operator=(const MptNoCopy &) = delete; };
+
 // A device allocation and its capacity in elements.  reserve() grows only and does not synchronise: the caller orders the free
 // behind whatever still uses the old buffer.  A failed allocation leaves {nullptr, 0}, so the next call tries again instead of
 // trusting a stale capacity.  Converts to T*, so launches and parameter structs take it as they took the raw pointer.
 template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
+struct DevBuf : MptNoCopy {
+    T *p = nullptr; size_t cap = 0;
     ~DevBuf() { release(); }
     operator T *() const { return p; }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
@@ -132,12 +129,8 @@ struct DevBuf {
 
 // The same for page-locked host memory (flags: hipHostMallocDefault, or hipHostMallocMapped for what a kernel writes)
 template <class T>
-struct PinnedBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    PinnedBuf() = default;
-    PinnedBuf(const PinnedBuf &) = delete;
-    PinnedBuf &operator=(const PinnedBuf &) = delete;
+struct PinnedBuf : MptNoCopy {
+    T *p = nullptr; size_t cap = 0;
     ~PinnedBuf() { release(); }
     operator T *() const { return p; }
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
@@ -149,6 +142,33 @@ struct PinnedBuf {
         cap = n;
         return 0;
     }
+};
+
+// Page-locked words a kernel writes and the host reads without a copy: the memory and its device alias, zeroed when made
+template <class T>
+struct MPT_INTERNAL MappedBuf {
+    PinnedBuf<T> host; T *dev = nullptr;
+    int create(size_t n) {
+        if (host.reserve(n, hipHostMallocMapped)) return 1;
+        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+        memset(host, 0, n * sizeof(T));
+        return 0;
+    }
+};
+
+// A stream (non-blocking) and an event, made on demand and destroyed with their owner.  They convert to the raw handle.
+struct MPT_INTERNAL MptStream : MptNoCopy {
+    hipStream_t s = nullptr;
+    ~MptStream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+    int create() { if (!s) HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); return 0; }
+};
+
+struct MPT_INTERNAL MptEvent : MptNoCopy {
+    hipEvent_t e = nullptr;
+    ~MptEvent() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+    int create(unsigned flags = hipEventDisableTiming) { if (!e) HIP_TRY(hipEventCreateWithFlags(&e, flags)); return 0; }   // (default: ordering only)
 };
 
 // Buffers that are sized together share one capacity and one reserve(): everything is freed, then allocated in the order
@@ -276,8 +296,8 @@ struct MPT_INTERNAL MptWideBufs {          // workspace of the device 4-wide col
 };
 
 struct MPT_INTERNAL MptMltSlab {           // the Metropolis engine's splat records and the scratch of their sort
-    DevBuf<uint32_t> keys, keys2;
-    DevBuf<MptVec4> vals, vals2;
+    DevBuf<uint32_t> keys, keys_sorted;
+    DevBuf<MptVec4> vals, vals_sorted;
     DevBuf<char> tmp;                    // sort scratch: tmp.cap bytes
     DevBuf<uint32_t> runs;
     size_t cap = 0, runs_cap = 0;        // records the slab holds; film elements of the run table
@@ -287,8 +307,8 @@ struct MPT_INTERNAL MptMltSlab {           // the Metropolis engine's splat reco
         size_t bytes = 0;
         HIP_TRY(mpt_mlt_sort_bytes((int)ncap, (int)nrcap, &bytes));
         cap = runs_cap = 0;
-        keys.release(); keys2.release(); vals.release(); vals2.release(); tmp.release(); runs.release();
-        if (keys.reserve(ncap) || keys2.reserve(ncap) || vals.reserve(ncap) || vals2.reserve(ncap) ||
+        keys.release(); keys_sorted.release(); vals.release(); vals_sorted.release(); tmp.release(); runs.release();
+        if (keys.reserve(ncap) || keys_sorted.reserve(ncap) || vals.reserve(ncap) || vals_sorted.reserve(ncap) ||
             tmp.reserve(std::max(bytes, (size_t)16)) || runs.reserve(nrcap * 2)) return 1;
         cap = ncap; runs_cap = nrcap;
         return 0;
@@ -297,25 +317,37 @@ struct MPT_INTERNAL MptMltSlab {           // the Metropolis engine's splat reco
 
 // ------------------------------------------------------------------ launch timers
 // The events recorded around the kernels of an engine's launches (per launch: `per_launch` events bounding per_launch - 1
-// segments, in stream order), kept until somebody asks for the times.  Events come from and go back to the context's pool.
+// segments, in stream order), kept until somebody asks for the times.  Events come from and go back to the context's pool,
+// which owns every timing event that no timer and no span holds.
+struct MPT_INTERNAL MptEventPool : MptNoCopy {
+    std::vector<hipEvent_t> idle;
+    ~MptEventPool() { for (hipEvent_t e : idle) (void)hipEventDestroy(e); }
+    hipEvent_t get() {
+        hipEvent_t e = nullptr;
+        if (idle.empty()) (void)hipEventCreate(&e);
+        else { e = idle.back(); idle.pop_back(); }
+        return e;
+    }
+    void put(hipEvent_t e) { if (e) idle.push_back(e); }
+};
+
 struct MPT_INTERNAL MptLaunchTimer {
     const int per_launch;
+    MptEventPool &pool;
     std::vector<hipEvent_t> events;
-    explicit MptLaunchTimer(int n) : per_launch(n) {}
-
-    void record(std::initializer_list<hipEvent_t> launch, std::vector<hipEvent_t> &pool) {
-        for (hipEvent_t e : launch) events.push_back(e);
-        if (events.size() > (size_t)per_launch * 4096) trim(pool);
-    }
-    // nobody has asked for kernel times for a long while (an interactive session renders frame after
-    // frame): keep the newest half.  The dropped events were recorded at least 2048 launches ago.
-    void trim(std::vector<hipEvent_t> &pool) {
+    MptLaunchTimer(int n, MptEventPool &p) : per_launch(n), pool(p) {}
+    ~MptLaunchTimer() { for (hipEvent_t e : events) pool.put(e); }      // (the pool is declared first, so it goes last)
+    void record(const hipEvent_t *launch) {
+        for (int q = 0; q < per_launch; q++) events.push_back(launch[q]);
+        // nobody has asked for kernel times for a long while (an interactive session renders frame after
+        // frame): keep the newest half.  The dropped events were recorded at least 2048 launches ago.
         const size_t half = (size_t)per_launch * 2048;
-        for (size_t q = 0; q < half; q++) pool.push_back(events[q]);
+        if (events.size() <= 2 * half) return;
+        for (size_t q = 0; q < half; q++) pool.put(events[q]);
         events.erase(events.begin(), events.begin() + half);
     }
     // seg_ms[per_launch - 1] += every launch's segments; the caller has synchronised the streams the events were recorded on
-    int drain(double *seg_ms, int *launches, std::vector<hipEvent_t> &pool) {
+    int drain(double *seg_ms, int *launches) {
         for (size_t q = 0; q + per_launch <= events.size(); q += per_launch)
             for (int g = 0; g + 1 < per_launch; g++) {
                 float t = 0;
@@ -323,16 +355,52 @@ struct MPT_INTERNAL MptLaunchTimer {
                 seg_ms[g] += t;
             }
         if (launches) *launches = (int)(events.size() / per_launch);
-        for (hipEvent_t e : events) pool.push_back(e);
+        for (hipEvent_t e : events) pool.put(e);
         events.clear();
         return 0;
     }
 };
 
+// One timed section of a stream.  Takes the timer's events from the pool and records the first (`begun`: how that went); mark()
+// records the next, end() the last and files them all with the timer.  A span that goes out of scope before end() -- any error
+// return in between -- gives its events back to the pool.
+struct MPT_INTERNAL MptTimedSpan : MptNoCopy {
+    MptLaunchTimer &timer;
+    const hipStream_t stream;
+    hipEvent_t ev[3] = {};                     // (no timer has more per launch)
+    int next = 0;
+    hipError_t begun;
+    MptTimedSpan(MptLaunchTimer &t, hipStream_t s) : timer(t), stream(s) {
+        for (int q = 0; q < timer.per_launch; q++) ev[q] = timer.pool.get();
+        begun = mark();
+    }
+    ~MptTimedSpan() { for (hipEvent_t e : ev) timer.pool.put(e); }
+    hipError_t mark() { return hipEventRecord(ev[next++], stream); }
+    hipError_t end() {
+        const hipError_t e = mark();
+        if (e == hipSuccess) { timer.record(ev); for (hipEvent_t &q : ev) q = nullptr; }
+        return e;
+    }
+};
+
+// ------------------------------------------------------------------ the launch ring
+// Launch pipelining (fast build): batch i renders in slot i mod cur_depth of the ring (2 to MPT_MAX_PIPE slots in use), on the slot's
+// stream into its slab, while the main stream still combines / gathers / resolves batch i-1: one launch's tail overlaps the next one's head
+struct MPT_INTERNAL MptRingSlot {
+    MptStream stream;                             // the render
+    MptEvent rendered;                            // ... of the batch in this slot has finished
+    MptEvent consumed;                            // the combine pass has consumed the slab
+    MptEvent ready;                               // Sobol points + zeroed queue heads of the batch are there
+    DevBuf<MptVec4> slab;                         // one float4 per sample, [frame][pixel of the share]
+    DevBuf<float> points;                         // [MPT_MAX_BATCH][sdim]
+    DevBuf<unsigned int> heads;                   // 8 queue heads, a cache line each, and the finalisation's tile counter
+    DevBuf<int> spill;                            // overflow strip of the wide kernel's per-lane stacks (launches of different slots are resident together and index theirs by block and lane only)
+};
+
 // ------------------------------------------------------------------ context
 struct mpt_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
+    MptStream stream;
     mpt_caps caps{};
 
     MptOptions opt;                      // everything mpt_set_option sets (mpt_options.h)
@@ -370,16 +438,13 @@ struct mpt_ctx {
     int wide_nodes = 0, wide_depth = 0;               // 0 nodes: not built (too deep)
     int wide_stack = 0;                               // stack levels a traversal of the 4-wide tree can ask for (exact from the host pass, 3 x depth + 2 from the device pass)
     float wide_ratio = 1.f;                           // expected fetches per ray, wide / binary (surface-area sums)
-    PinnedBuf<int> h_sahmeta; int *d_sahmeta = nullptr;   // host-pinned, device-mapped [32]: the SAH pass's per-level hand-back (sah_build.hip plan kernel)
+    MappedBuf<int> sah_mail;                          // [32]: the SAH pass's per-level hand-back (sah_build.hip plan kernel)
     MptSahStats sah_stats{};                          // what the last device SAH pass did
     bool d_model_stale = true;                        // the device copy of the model (d_verts, d_mtlids) is behind the host's: the next device build uploads
     double build_phase_us[6] = { 0, 0, 0, 0, 0, 0 };   // upload | LBVH | SAH pass | triangle records | 4-wide collapse | total (host clock)
     int sah_fallback = 0;                             // last build: the device SAH pass gave up (1: error, 2: depth) and the host pass ran
     DevBuf<char> sah_ws;                              // one allocation (sah_ws.cap bytes), carved up in build_sah_device
     MptWideBufs wb;
-    // overflow strips of the wide kernel's per-lane stacks: one per ring slot, because launches of different slots
-    // are resident together and index their strips by block and lane only
-    DevBuf<int> stack_spill2[MPT_MAX_PIPE];
 
     // materials / images / lights / world / camera
     DevBuf<MptMaterial> mats;
@@ -401,72 +466,59 @@ struct mpt_ctx {
     int sdim = 0, srows = 0;
     int32_t stime = 0;
     DevBuf<int> sV, sX;
-    DevBuf<int> sX_spec;                 // the state the batch whose points were computed ahead of time will leave behind (swapped with sX when it is launched)
     DevBuf<float> sP;                    // [MPT_MAX_BATCH][sdim]
 
-    // Metropolis engine (mlt_kernel.hip, mpt_mlt_*): chain state, splat slab and the iterations enqueued but not launched
-    int mlt_n = 0, mlt_iter = 0, mlt_pending = 0;
-    uint32_t mlt_seed = 0;
-    float mlt_lsp = 0.25f, mlt_sigma = 0.01f;
-    DevBuf<float> mlt_X, mlt_L;                          // [2][n][32], [n][3]
-    DevBuf<int32_t> mlt_bit;                             // [n]
-    MptMltSlab slab;
-    MptLaunchTimer mlt_timer{3};                         // {chain start, chain end = splat start, splat end} per launch
-    MptLaunchTimer denoise_timer{2};                     // mpt_get_denoised: {before the prologue, after the epilogue} per call
-    MptLaunchTimer brute_timer{2};                       // brute-force engine: {kernel start, kernel end} per launch
-    MptLaunchTimer display_timer{2};                     // mpt_get_display: {before the first kernel, after the conversion} per call
-    PinnedBuf<float> h_exposure; float *d_exposure = nullptr;   // host-pinned, device-mapped: the metered exposure of the last mpt_get_display / mpt_display_eval
-    DevBuf<MptVec4> door_raw; MptDisplayBufs door_disp;  // mpt_display_eval: the caller's accumulators and what the kernels write for them (grown on demand)
-    // command batching
-    int pending = 0;
+    MptEventPool events;                 // the timing events at rest (declared before the timers, which hand theirs back to it)
+    // Metropolis engine (mlt_kernel.hip, mpt_mlt_*): chain state, parameters, the iterations enqueued but not launched, splat slab
+    struct MPT_INTERNAL Mlt {
+        int n = 0, iter = 0, pending = 0; uint32_t seed = 0; float lsp = 0.25f, sigma = 0.01f;
+        DevBuf<float> X, L; DevBuf<int32_t> bit;         // [2][n][32], [n][3], [n]
+        MptMltSlab slab;
+        MptLaunchTimer timer;                            // {chain start, chain end = splat start, splat end} per launch
+        explicit Mlt(MptEventPool &ev) : timer(3, ev) {}
+    } mlt{events};
+    struct MPT_INTERNAL Display {                        // the display door (mpt_get_display, mpt_display_eval)
+        MappedBuf<float> exposure;                       // the metered exposure of the last call
+        DevBuf<MptVec4> raw; MptDisplayBufs bufs;        // mpt_display_eval: the caller's accumulators and what the kernels write for them (grown on demand)
+        MptLaunchTimer timer;                            // mpt_get_display: {before the first kernel, after the conversion} per call
+        explicit Display(MptEventPool &ev) : timer(2, ev) {}
+    } display{events};
+    MptLaunchTimer render_timer{2, events};              // PathEngine launches: {kernel start, kernel end}
+    MptLaunchTimer denoise_timer{2, events};             // mpt_get_denoised: {before the prologue, after the epilogue} per call
+    MptLaunchTimer brute_timer{2, events};               // brute-force engine: {kernel start, kernel end} per launch
+    int pending = 0;                                     // command batching: frames enqueued and not launched yet
 
-    // launch pipelining (fast build): batch i renders on rstream[k] into partial2[k], k = i mod cur_depth (a ring of 2 to
-    // MPT_MAX_PIPE slots), while the main stream still combines / gathers / resolves batch i-1, so one launch's tail
-    // overlaps the next one's head
-    hipStream_t rstream[MPT_MAX_PIPE] = {};
-    hipEvent_t ev_render[MPT_MAX_PIPE] = {};          // render of the batch on rstream[k] finished
-    hipEvent_t ev_free[MPT_MAX_PIPE] = {};            // combine has consumed partial[k]
-    hipStream_t probe_stream = nullptr;               // mpt_probe_kernel
-    hipStream_t stress_stream = nullptr;              // mpt_stress_copies: a stream of device-to-device copies beside the render
-    DevBuf<char> stress_buf;                          // 2 x stress_bytes
-    size_t stress_bytes = 0;
-    hipStream_t aux = nullptr;                        // Sobol advances + queue resets of the pipelined batches
-    hipEvent_t ev_sobol2[MPT_MAX_PIPE] = {};          // Sobol points + zeroed queue heads of the batch on rstream[k] ready
+    MptRingSlot ring[MPT_MAX_PIPE];
+    MptStream probe_stream;                           // mpt_probe_kernel
+    MptStream stress_stream;                          // mpt_stress_copies: a stream of device-to-device copies beside the render
+    DevBuf<char> stress_buf; size_t stress_bytes = 0;   // 2 x stress_bytes
+    MptStream aux;                                    // Sobol advances + queue resets of the pipelined batches
     int cur_depth = 2, cur_div = 1;                   // what the last launch used
-    hipEvent_t ev_film = nullptr;                     // main-stream work on the film (combine, clear, gather) a finalising launch must see
+    MptEvent ev_film;                                 // main-stream work on the film (combine, clear, gather) a finalising launch must see
     // tail finalisation (render_kernel.hip finalise_tiles, option "finalise"): launch_seq numbers the launches (slab tags);
-    // film_version counts the changes of pass 0; hint_image = where the next mpt_get_image(0) wants the image (mpt_hint_image);
-    // early_* = the image a finalising launch has written (or is writing) and the film version it shows
+    // film_version counts the changes of pass 0
     unsigned launch_seq = 0;
     unsigned tag_epoch = 0;                           // launch_seq / MPT_TAG_PERIOD when the slabs were last zeroed
     unsigned tag_wraps = 0;                           // times the slab tags came round (every slab zeroed): a test reads it
     unsigned long long film_version = 0;
-    float *hint_image = nullptr;
-    float *early_ptr = nullptr;
-    hipStream_t early_stream = nullptr;               // the stream of the launch that writes early_ptr
-    unsigned long long early_version = 0;
+    // the early image: hint = where the next mpt_get_image(0) wants the image (mpt_hint_image); ptr = the image a finalising
+    // launch has written (or is writing), with the stream of that launch and the film version it shows
+    struct { float *hint = nullptr, *ptr = nullptr; hipStream_t stream = nullptr; unsigned long long version = 0; } early;
     int last_finalised = 0;                           // the last launch finalised its tiles itself (diagnostics, option "last_finalised")
-    hipEvent_t ev_main = nullptr;                     // main-stream work a render must see (uploads, resets, ...)
+    MptEvent ev_main;                                 // main-stream work a render must see (uploads, resets, ...)
     bool main_dirty = true;
     int flip = 0;
     // Sobol points of the NEXT batch, computed ahead of time into the ring slot it will use (the sequence is
-    // deterministic): valid while nothing has touched the sampler or the ring since
-    bool spec_valid = false;
-    int spec_slot = -1, spec_B = 0;
-    int32_t spec_time = 0;
-    DevBuf<MptVec4> partial2[MPT_MAX_PIPE];
-    DevBuf<float> sP2[MPT_MAX_PIPE];
-    DevBuf<unsigned int> d_work2[MPT_MAX_PIPE];
+    // deterministic): valid while nothing has touched the sampler or the ring since; X = the sampler state that batch will leave
+    // behind (swapped with sX when it is launched)
+    struct { bool valid = false; int slot = -1, B = 0; int32_t time = 0; DevBuf<int> X; } spec;
 
     // measurement
     DevBuf<unsigned long long> d_timeline;
     int timeline_waves = 0;
     DevBuf<unsigned long long> d_counters;
-    DevBuf<unsigned int> d_work;
-    PinnedBuf<unsigned int> h_watchdog; unsigned int *d_watchdog = nullptr;   // host-pinned, device-mapped: raised by a render kernel's watchdog
+    MappedBuf<unsigned int> watchdog;                            // raised by a render kernel's watchdog
     PinnedBuf<char> h_stage;                                     // page-locked staging (h_stage.cap bytes) for read-backs into pageable buffers
-    MptLaunchTimer render_timer{2};      // PathEngine launches: {kernel start, kernel end}
-    std::vector<hipEvent_t> event_pool;
 
     // comm
     ncclComm_t comm = nullptr;

@@ -11,7 +11,7 @@
 #include <cstring>
 #include "mpt_types.h"    // MPT_MAX_BATCH (plain structures; wants size_t declared)
 
-enum { MPT_MAX_PIPE = 6 };     // slots of the launch ring (mpt_ctx::rstream, partial2, ...): the most batches in flight
+enum { MPT_MAX_PIPE = 6 };     // slots of the launch ring (mpt_ctx::ring): the most batches in flight
 
 struct MptOptions {
     // ---- what a render launch reads

@@ -441,7 +441,7 @@ static int build_sah_device(mpt_ctx *c) {
     B.tasks = (int *)take(TC * 32); B.task_cap = TC;
     B.meta = (int *)take(64);
     B.stats = &c->sah_stats;
-    B.mail_host = c->h_sahmeta; B.mail_dev = c->d_sahmeta;
+    B.mail_host = c->sah_mail.host; B.mail_dev = c->sah_mail.dev;
     B.fnode = c->nodes.fnode;
     int depth = 0;
     hipError_t e = mpt_sah_build(&B, &depth, c->stream);
@@ -687,7 +687,7 @@ static int make_wide_device(mpt_ctx *c) {
     int nw = 0, depth = 0;
     double area[2] = { 0.0, 0.0 };
     HIP_TRY(mpt_wide_build(c->nodes.fnode, n, c->wnode, c->qnode, c->wb.bin_of, c->wb.ncount, c->wb.scan, c->wb.scan_bytes,
-                           c->wb.area, &nw, &depth, area, c->stream, c->h_sahmeta, c->d_sahmeta));
+                           c->wb.area, &nw, &depth, area, c->stream, c->sah_mail.host, c->sah_mail.dev));
     if (!wide_fits(depth, (size_t)nw)) return 0;
     c->wide_nodes = nw; c->wide_depth = depth;
     c->wide_stack = wide_stack_bound(depth);   // the bound ...

@@ -1,7 +1,8 @@
 '''
-One context walked through growing and shrinking sizes (-m gpu): models, films and the Metropolis slab.  Every buffer of
-the context is grown in place (csrc/miptina_ctx.h: DevBuf and the capacity groups), so what a reused context computes
-must be what a fresh context computes at that size, bit for bit -- and a destroyed context must give its memory back.
+One context walked through growing and shrinking sizes (-m gpu): models, films, the Metropolis slab and the launch ring.  Every
+buffer of the context is grown in place (csrc/miptina_ctx.h: DevBuf and the capacity groups), so what a reused context computes
+must be what a fresh context computes at that size, bit for bit -- and a destroyed context must give its memory back, with
+every stream, event and mapped word it made on the way (the owners of csrc/miptina_ctx.h).
 Failed allocations are not provoked here.
 '''
 
@@ -189,3 +190,101 @@ def test_destroy_gives_the_memory_back(fresh):
     print(f'free memory lost over {LEAK_CYCLES} cycles: {lost} bytes; one cycle allocates at least {film} + {tree} bytes; allowed {LEAK_ALLOWED}')
     assert LEAK_ALLOWED < LEAK_CYCLES * film // 4 < LEAK_CYCLES * (film + tree) // 4
     assert lost <= LEAK_ALLOWED, f'{lost} bytes of device memory did not come back after {LEAK_CYCLES} contexts'
+
+
+# ---------------------------------------------------------------- 5. ring sizes through one context
+# (pipe_depth, grid_div): two slots, all six with the smallest launches, three, what the library picks, two again
+RING_WALK = [(2, 1), (6, 4), (3, 2), (0, 0), (2, 1)]
+RING_FRAMES = (2, 2, 1, 2, 2, 1, 2, 2)                # eight launches of `batch` = 2 frames at the most: a ring of six slots wraps
+
+
+def _ring_film(eng, depth, div):
+    from ptina_amd.common import ctx
+    from ptina_amd.things import FilmTable
+    from ptina_amd.sampling.sobol import SobolSampler
+    c = ctx()
+    c.set_option('pipe_depth', depth)
+    c.set_option('grid_div', div)
+    SobolSampler().reset()
+    FilmTable().clear()
+    for frames in RING_FRAMES:
+        eng.render(frames)
+        c.call('mpt_flush')
+    return FilmTable().get_raw().copy()
+
+
+@pytest.mark.parametrize('lds', [1, 0])
+def test_ring_sizes_through_one_context(fresh, lds):
+    '''The slots of the launch ring (csrc/miptina_ctx.h MptRingSlot: stream, events, slab, points, queue heads, spill strip) are
+    grown when a launch first needs them; the other tests give every ring configuration a context of its own.  Here one
+    context walks through them, and every film must be the film of a fresh context with two slots, word for word.
+    lds = 0: the 4-wide gather kernel, whose per-slot spill strips are then the ones grown; its wanted film is a fresh
+    context's under the same option.'''
+    from ptina_amd.common import ctx, reset_all
+    scene = scenes.scene_s34()
+
+    def context():
+        reset_all()
+        eng = setup_engine(scene, 64, 48, mode='fast')
+        ctx().set_option('batch', 2)
+        ctx().set_option('lds', lds)
+        return eng
+
+    want = _ring_film(context(), 2, 1)
+    assert np.all(want[:, 3] == sum(RING_FRAMES))
+    eng = context()
+    for depth, div in RING_WALK:
+        got = _ring_film(eng, depth, div)
+        if not lds:
+            assert ctx().get_option('last_kernel') == 2
+        assert got.shape == want.shape and np.array_equal(_bits(got), _bits(want)), \
+            f'lds {lds}, pipe_depth {depth}, grid_div {div}: {int((_bits(got) != _bits(want)).sum())} words differ from a fresh context\'s film'
+        assert np.all(got[:, 3] == sum(RING_FRAMES))
+
+
+# ---------------------------------------------------------------- 6. every lazily made resource, then destroy
+def test_every_lazily_made_resource_then_destroy(fresh):
+    '''Three contexts that each make everything a context makes on demand -- the probe and the stress stream, the Metropolis
+    engine's state and slab, the denoiser's and the display's buffers, timing events of all five launch timers -- and are then
+    destroyed.  Cycles 2 and 3 compute what cycle 1 computed, bit for bit, and the device's free memory after cycle 3 is not
+    below its value after cycle 2 (cycle 1 settles the runtime's own pools: test_destroy_gives_the_memory_back).
+    The probe is the smallest the library accepts: 64 lanes with the 4 bytes of LDS per lane it asks for.'''
+    from ptina_amd.common import ctx, reset_all
+    from ptina_amd.things import FilmTable
+    from ptina_amd.engine.mltpath import MLTPathEngine
+    from ptina_amd.engine.brute import BruteEngine
+    from ptina_amd.engine.preview import PreviewEngine
+    scene = scenes.scene_s34()
+
+    def cycle():
+        eng = setup_engine(scene, 32, 32, mode='fast')
+        c, f = ctx(), FilmTable()
+        eng.render(2)
+        c.call('mpt_probe_kernel', 64, 256, None)
+        c.call('mpt_stress_copies', 1, 2)
+        c.call('mpt_stress_copies', 1, 0)                # ... waited for
+        mlt = MLTPathEngine(nchains=2**10, seed=1)
+        mlt.reset()
+        mlt.render(2)
+        brute = BruteEngine()
+        brute.render(1)
+        PreviewEngine().render(1)
+        out = [np.array(f.get_denoised()), np.array(f.get_display())]
+        out += [np.float32(f.last_exposure), f.get_raw().copy()]
+        a, b, n = C.c_double(0), C.c_double(0), C.c_int(0)
+        c.call('mpt_mlt_kernel_time', C.byref(a), C.byref(b), C.byref(n))
+        launches = {'path': c.kernel_time()[1], 'mlt': n.value, 'brute': brute.kernel_time()[1],
+                    'denoise': f.denoise_kernel_time()[1], 'display': f.display_kernel_time()[1]}
+        assert all(v >= 1 for v in launches.values()), launches
+        reset_all()
+        return out, _free_bytes()
+
+    first, _ = cycle()
+    second, free2 = cycle()
+    third, free3 = cycle()
+    assert first[2] > 0 and first[3][:, 3].sum() >= 32 * 32 * 2 + 2 * 2**10      # (the path frames and the Metropolis splats at least)
+    for n, got in ((2, second), (3, third)):
+        for what, g, w in zip(('get_denoised', 'get_display', 'exposure_used', 'get_raw'), got, first):
+            assert g.shape == w.shape and g.dtype == w.dtype and g.tobytes() == w.tobytes(), f'cycle {n}: {what} differs from cycle 1'
+    print(f'free memory after cycle 2: {free2} bytes, after cycle 3: {free3} bytes')
+    assert free3 >= free2, f'{free2 - free3} bytes of device memory did not come back with the third context'
