@@ -377,6 +377,54 @@ int mpt_display_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
 int mpt_display_eval(mpt_ctx *ctx, const mpt_display_params *params, const float *raw, int nx, int ny,
                      uint8_t *out, float *exposure_used);
 
+/* Is the image converged?  A noise estimate of film pass 0 on the device, from the film and a copy of it taken earlier, so that a
+ * progressive render can stop at a noise threshold instead of a hand-picked sample count (no reference counterpart: its scripts and
+ * its Blender loop count samples).  With F the raw accumulator of pass 0 (film index x*ny + y, rgb sums, w the sample weight) and M
+ * the mark -- the device copy of F that mpt_film_mark took -- f32 arithmetic without contraction, IEEE division and square root:
+ *   nA = M.w;  n = F.w;  nB = n - nA                 (the samples fall into two groups: those of the mark, those added since)
+ *   valid(p) = nA > 0 and nB > 0
+ *   a = clamp0(M.rgb / nA);  m = clamp0(F.rgb / n)   clamp0(x) = fminf(fmaxf(x, 0), 3.0e38f) per channel
+ *                                                    (mpt_get_display's rule: NaN -> 0, -x -> 0, +inf -> 3e38)
+ *   k = sqrtf(nA / nB)                               (exactly 1 for equal halves)
+ *   d = |m - a| k   per channel                      (the standard error of m from the two groups' means a and b:
+ *                                                     |a - b| sqrt(nA nB) / n, written through m and a)
+ *   e(p) = clamp0((((d.r + d.g) + d.b) / 3) / (1e-4f + sqrtf(((m.r + m.g) + m.b) / 3)))
+ *                                                    (the last clamp0 moves only a value that is not finite -- saturated channels
+ *                                                     whose sums overflow -- so that e is finite whatever the film holds)
+ * With equal halves this is the convergence criterion of Cycles' adaptive sampling as written, so `threshold` is the "noise
+ * threshold" a Blender user knows (Cycles: 0.01 final, 0.1 viewport).  Results:
+ *   map    e as [nx][ny] f32 in film order, 0 where the pixel is not valid                               (optional)
+ *   stats  over the valid pixels: valid = their count, above = the count of e > threshold, max = the largest e (exact), sum = the
+ *          sum of the f32 values e, taken in f64; threshold echoes the argument.  The sum is two-stage with a shape that depends
+ *          on nx*ny alone and uses no atomics: every field repeats bit for bit.
+ * mpt_film_mark: flushes what is enqueued, then M := F on the main stream behind it.  The mark is 16 bytes per pixel, allocated at
+ *   the first mark and released with the film.  mpt_clear and mpt_set_size drop the mark; a scene, camera or light change does not.
+ * mpt_get_noise: map may be NULL, stats may be NULL, not both.  remark != 0 also sets M := F, in the same pass over the film: a
+ *   loop that doubles the sample count between checks pays one pass per check.
+ * mpt_get_mark: test door; out [nx*ny][4] = the mark's raw accumulators.
+ * Like mpt_get_denoised the calls flush what is enqueued, read whatever film the context holds, write no film pass and neither use
+ * nor disturb an mpt_hint_image hint; columns a slab or stripe split did not render have w = 0 and are not valid.  mpt_get_noise
+ * and mpt_get_mark fail without a mark, mpt_get_noise and mpt_noise_eval for a threshold that is negative or not finite,
+ * mpt_get_noise with both outputs NULL; a failed call leaves film and mark untouched.
+ * The estimate means what it says for the engines that add one sample of weight 1 per pixel and frame (mpt_render,
+ * mpt_render_brute).  On the Metropolis engine's splats it is defined and computed, and is not a noise estimate. */
+typedef struct {
+    int64_t valid, above;
+    double sum;
+    float max;
+    float threshold;
+} mpt_noise_stats;
+int mpt_film_mark(mpt_ctx *ctx);
+int mpt_get_noise(mpt_ctx *ctx, float threshold, int remark, float *map /* [nx][ny] or NULL */, mpt_noise_stats *stats /* or NULL */);
+int mpt_get_mark(mpt_ctx *ctx, float *out /* [nx*ny][4] */);
+/* Test door in the mpt_display_eval idiom: the SAME kernels on caller-supplied accumulators film_raw and mark_raw [nx*ny][4], any
+ * nx, ny >= 1 with nx*ny <= max_filmsize; touches no film pass and not the context's mark.  map [nx*ny] and new_mark [nx*ny][4] (the
+ * mark the re-mark mode leaves: film_raw) may be NULL */
+int mpt_noise_eval(mpt_ctx *ctx, float threshold, const float *film_raw, const float *mark_raw, int nx, int ny,
+                   float *map, float *new_mark, mpt_noise_stats *stats);
+/* HIP-event time (ms) of the kernels (estimate, fold) of the mpt_get_noise calls since the last call, and their count */
+int mpt_noise_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
+
 /* Page-locked host buffers for the read-backs above: into such a buffer mpt_get_image /
  * mpt_fast_export_image / mpt_get_film_raw are one DMA; any other buffer is served through a
  * page-locked staging copy.  (The reference's get_image returns a fresh numpy array,

@@ -48,6 +48,33 @@ class DisplayParams(C.Structure):
                 ('exposure', C.c_float), ('key', C.c_float), ('white', C.c_float), ('gamma', C.c_float)]
 
 
+class NoiseStats(C.Structure):
+    '''mpt_noise_stats (include/miptina.h): what mpt_get_noise and mpt_noise_eval hand back'''
+    _fields_ = [('valid', C.c_int64), ('above', C.c_int64), ('sum', C.c_double), ('max', C.c_float), ('threshold', C.c_float)]
+
+
+class NoiseResult:
+    '''FilmTable.get_noise's answer: over the `valid` pixels, `above` of them with e > threshold, the `mean` of e (sum / valid, 0.0
+    when nothing is valid), its `max`, `fraction` = above / valid (0.0 when nothing is valid), and the `map` [nx, ny] or None'''
+    __slots__ = ('valid', 'above', 'sum', 'max', 'threshold', 'map')
+
+    def __init__(self, stats, map=None):
+        self.valid, self.above, self.sum = int(stats.valid), int(stats.above), float(stats.sum)
+        self.max, self.threshold, self.map = float(stats.max), float(stats.threshold), map
+
+    @property
+    def mean(self):
+        return self.sum / self.valid if self.valid else 0.0
+
+    @property
+    def fraction(self):
+        return self.above / self.valid if self.valid else 0.0
+
+    def __repr__(self):
+        return 'NoiseResult(valid=%d, above=%d, mean=%.6g, max=%.6g, fraction=%.6g, threshold=%.6g)' % (
+            self.valid, self.above, self.mean, self.max, self.fraction, self.threshold)
+
+
 DISPLAY_DENOISED = -1
 TONE_OPS = {'linear': 0, 'ptina': 1, 'reinhard': 2, 'aces': 3}
 TRANSFERS = {'srgb': 0, 'gamma': 1}
@@ -118,6 +145,11 @@ SIGNATURES = {
     'mpt_get_display': (_i, [_vp, C.POINTER(DisplayParams), C.POINTER(DenoiseParams), C.POINTER(C.c_uint8), _fp]),
     'mpt_display_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
     'mpt_display_eval': (_i, [_vp, C.POINTER(DisplayParams), _fp, _i, _i, C.POINTER(C.c_uint8), _fp]),
+    'mpt_film_mark': (_i, [_vp]),
+    'mpt_get_noise': (_i, [_vp, C.c_float, _i, _fp, C.POINTER(NoiseStats)]),
+    'mpt_get_mark': (_i, [_vp, _fp]),
+    'mpt_noise_eval': (_i, [_vp, C.c_float, _fp, _fp, _i, _i, _fp, _fp, C.POINTER(NoiseStats)]),
+    'mpt_noise_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
     'mpt_host_alloc': (_vp, [C.c_size_t]),
     'mpt_host_free': (None, [_vp]),
     'mpt_get_counters': (_i, [_vp, C.POINTER(Counters)]),
@@ -307,6 +339,20 @@ class Context:
         used = C.c_float(0)
         self.call('mpt_display_eval', C.byref(p), fptr(a), int(nx), int(ny), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(used))
         return out, np.float32(used.value)
+
+    def noise_eval(self, film_raw, mark_raw, nx, ny, threshold, map=True, remark=True):
+        '''test door (mpt_noise_eval): get_noise's kernels on the accumulators film_raw and mark_raw [nx*ny][4]; returns
+        (NoiseResult with the map [nx, ny] or None, the mark the re-mark mode leaves [nx*ny, 4] or None)'''
+        f = np.ascontiguousarray(np.asarray(film_raw, np.float32).reshape(-1, 4))
+        m = np.ascontiguousarray(np.asarray(mark_raw, np.float32).reshape(-1, 4))
+        if f.shape[0] != int(nx) * int(ny) or m.shape != f.shape:
+            raise ValueError('film and mark hold %d and %d accumulators, the film %dx%d' % (f.shape[0], m.shape[0], nx, ny))
+        e = np.empty((nx, ny), np.float32) if map else None
+        new = np.empty_like(f) if remark else None
+        st = NoiseStats()
+        self.call('mpt_noise_eval', float(threshold), fptr(f), fptr(m), int(nx), int(ny), None if e is None else fptr(e),
+                  None if new is None else fptr(new), C.byref(st))
+        return NoiseResult(st, e), new
 
     def counters(self):
         cnt = Counters()

@@ -150,6 +150,7 @@ extern "C" mpt_ctx *mpt_create(const mpt_caps *caps, int device) {
     if (c->sah_mail.create(32)) return bail("pinned build mailbox");
     if (c->display.exposure.create(1)) return bail("pinned exposure word");
     *c->display.exposure.host = 1.0f;
+    if (c->noise.stats.create(1)) return bail("pinned noise statistics");
     hipMemsetAsync(c->d_counters, 0, MPT_COUNTER_WORDS * sizeof(unsigned long long), c->stream);
     {   // unset materials: factor 0 (field-zero, mtllib.py:12-13), texture -1 (deviation Q6)
         std::vector<MptMaterial> z((size_t)c->caps.max_materials + 1);
@@ -340,6 +341,7 @@ extern "C" int mpt_set_size(mpt_ctx *c, int nx, int ny) {
     // of another resolution are the caller's to clear(); same here.
     c->nx = nx; c->ny = ny; c->x0 = 0; c->x1 = nx; c->stripe_w = 0; c->stripe_idx = 0; c->stripe_mod = 1;
     c->film_version++;
+    c->noise.marked = false;                     // a mark is a copy of the film as it was sized
     return 0;
 }
 
@@ -1243,6 +1245,7 @@ extern "C" int mpt_clear(mpt_ctx *c, int pass) {                               /
     for (int p = 0; p < 3; p++)
         if (c->fb.film[p]) HIP_TRY(hipMemsetAsync(c->fb.film[p], 0, npix * sizeof(MptVec4), c->stream));
     c->film_version++;
+    c->noise.marked = false;                     // the samples the mark counted are gone
     return 0;
 }
 
@@ -1476,6 +1479,85 @@ extern "C" int mpt_display_eval(mpt_ctx *c, const mpt_display_params *params, co
     HIP_TRY(hipStreamSynchronize(c->stream));                      // (`raw` is pageable: the copy is staged, the caller's array is free again)
     if (display_launches(c, p, a, c->display.raw, nx, ny, c->display.bufs, c->display.bufs.rgba8)) return 1;
     return display_finish(c, p, false, out, c->display.bufs.rgba8, npix, exposure_used);
+}
+
+// ------------------------------------------------------------------ noise estimate (noise.hip)
+// The mark is a device copy of film pass 0; the estimate compares the film with it.  Everything runs on the main stream behind
+// what is enqueued (the flush makes that stream wait for the render launches, as for mpt_get_film_raw); reads pass 0, writes only the
+// mark and the context's working buffers, and knows nothing of mpt_hint_image's array.
+extern "C" int mpt_film_mark(mpt_ctx *c) {
+    if (use_ro(c)) return 1;
+    if (mpt_flush(c)) return 1;
+    if (check_pass(c, 0)) return 1;
+    if (c->fb.reserve_mark()) return 1;
+    HIP_TRY(hipMemcpyAsync(c->fb.mark, c->fb.film[0], (size_t)c->nx * c->ny * sizeof(MptVec4), hipMemcpyDeviceToDevice, c->stream));
+    c->noise.marked = true;
+    return 0;
+}
+
+static int noise_threshold(const char *who, float threshold) {
+    if (!(std::isfinite(threshold) && threshold >= 0.0f)) return fail("%s: threshold must be finite and not negative, got %g", who, (double)threshold);
+    return 0;
+}
+
+// the map and the statistics of the launches just enqueued to the caller (each may be null)
+static int noise_finish(mpt_ctx *c, const MptNoiseBufs &b, size_t npix, float *map, mpt_noise_stats *stats) {
+    if (map) { if (read_back(c, map, b.map, npix * sizeof(float))) return 1; }
+    else HIP_TRY(hipStreamSynchronize(c->stream));
+    if (stats) memcpy(stats, (const void *)c->noise.stats.host.p, sizeof *stats);
+    return 0;
+}
+
+extern "C" int mpt_get_noise(mpt_ctx *c, float threshold, int remark, float *map, mpt_noise_stats *stats) {
+    if (use_ro(c)) return 1;
+    if (!map && !stats) return fail("mpt_get_noise: null map and null statistics");
+    if (noise_threshold("mpt_get_noise", threshold)) return 1;
+    if (!c->noise.marked) return fail("mpt_get_noise: no mark: call mpt_film_mark() first (mpt_clear and mpt_set_size drop the mark)");
+    if (mpt_flush(c)) return 1;
+    if (check_pass(c, 0)) return 1;
+    const size_t npix = (size_t)c->nx * c->ny;
+    MptTimedSpan span(c->noise.timer, c->stream);
+    HIP_TRY(span.begun);
+    HIP_TRY(mpt_launch_noise(c->fb.film[0], c->fb.mark, npix, threshold, remark ? 1 : 0, map ? c->fb.noise.map.p : nullptr, c->fb.noise.part,
+                             c->noise.stats.dev, c->stream));
+    HIP_TRY(span.end());
+    if (noise_finish(c, c->fb.noise, npix, map, stats)) return 1;
+    return check_watchdog(c);
+}
+
+extern "C" int mpt_get_mark(mpt_ctx *c, float *out) {
+    if (use_ro(c)) return 1;
+    if (!out) return fail("mpt_get_mark: null output");
+    if (!c->noise.marked) return fail("mpt_get_mark: no mark: call mpt_film_mark() first (mpt_clear and mpt_set_size drop the mark)");
+    if (mpt_flush(c)) return 1;
+    return read_back(c, out, c->fb.mark, (size_t)c->nx * c->ny * sizeof(MptVec4));
+}
+
+extern "C" int mpt_noise_kernel_time(mpt_ctx *c, double *ms, int *launches) {
+    return use_ro(c) || timer_readout(c, c->noise.timer, ms, nullptr, launches);
+}
+
+// test door: the same launches on the caller's film and mark, in buffers of its own (no film pass and not the context's mark)
+extern "C" int mpt_noise_eval(mpt_ctx *c, float threshold, const float *film_raw, const float *mark_raw, int nx, int ny, float *map,
+                              float *new_mark, mpt_noise_stats *stats) {
+    if (use_ro(c)) return 1;
+    if (!film_raw || !mark_raw) return fail("mpt_noise_eval: null input");
+    if (noise_threshold("mpt_noise_eval", threshold)) return 1;
+    if (nx < 1 || ny < 1 || (long long)nx * ny > (long long)c->caps.max_filmsize)
+        return fail("mpt_noise_eval: film %dx%d outside 1 .. max_filmsize=%d pixels", nx, ny, c->caps.max_filmsize);
+    const size_t npix = (size_t)nx * ny;
+    auto &d = c->noise;
+    if (npix > d.film.cap || npix > d.mark.cap || npix > d.bufs.cap) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (d.film.reserve(npix) || d.mark.reserve(npix) || d.bufs.reserve(npix)) return 1;
+    }
+    HIP_TRY(hipMemcpyAsync(d.film, film_raw, npix * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d.mark, mark_raw, npix * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                      // (the arrays are pageable: the copies are staged, the caller's arrays are free again)
+    HIP_TRY(mpt_launch_noise(d.film, d.mark, npix, threshold, new_mark ? 1 : 0, map ? d.bufs.map.p : nullptr, d.bufs.part, d.stats.dev, c->stream));
+    if (noise_finish(c, d.bufs, npix, map, stats)) return 1;
+    if (new_mark && read_back(c, new_mark, d.mark, npix * sizeof(MptVec4))) return 1;
+    return 0;
 }
 
 // ------------------------------------------------------------------ measurement

@@ -65,6 +65,10 @@ MPT_KERNEL_API size_t mpt_display_parts(size_t npix);
 MPT_KERNEL_API hipError_t mpt_launch_display_meter(const MptVec4 *src, size_t npix, double *part, float key, float *e_dev, float *e_host, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_display_convert(const MptVec4 *src, uint32_t *out, int nx, int ny, const MptDisplayArgs *a,
                                                      const float *e_dev /* NULL: a->exposure */, hipStream_t);
+// noise.hip: the noise estimate of a film against its mark (mpt_get_noise); part holds max(mpt_noise_parts(npix), 1) records
+MPT_KERNEL_API size_t mpt_noise_parts(size_t npix);
+MPT_KERNEL_API hipError_t mpt_launch_noise(const MptVec4 *film, MptVec4 *mark, size_t npix, float threshold, int remark, float *map /* or NULL */,
+                                           mpt_noise_stats *part, mpt_noise_stats *stats_host, hipStream_t);
 
 // on-GPU LBVH build (lbvh_build.hip)
 struct MptLbvhBuffers {
@@ -188,6 +192,20 @@ struct MPT_INTERNAL MptDisplayBufs {       // what mpt_get_display's kernels wri
     }
 };
 
+struct MPT_INTERNAL MptNoiseBufs {         // what mpt_get_noise's kernels write, for a film of up to `cap` pixels
+    DevBuf<float> map;                   // the estimate per pixel
+    DevBuf<mpt_noise_stats> part;        // the first stage's partial statistics, one record per workgroup
+    size_t cap = 0;
+    void release() { map.release(); part.release(); cap = 0; }
+    int reserve(size_t npix) {
+        if (npix <= cap) return 0;
+        release();
+        if (map.reserve(npix) || part.reserve(std::max<size_t>(mpt_noise_parts(npix), 1))) return 1;
+        cap = npix;
+        return 0;
+    }
+};
+
 struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set so far
     DevBuf<MptVec4> film[3];
     DevBuf<MptVec4> resolved;            // nx*ny float4 (get_image staging on device)
@@ -196,7 +214,11 @@ struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set 
     // iterations alternate between (the one left over takes the image), and the guides a (albedo) and n (normal)
     DevBuf<MptVec4> dn_e[2], dn_a, dn_n;
     MptDisplayBufs disp;                 // mpt_get_display's 8-bit image and metering partials
+    // mpt_film_mark's copy of pass 0 and what mpt_get_noise's kernels write: made by the first mark (reserve_mark), for `cap`
+    // pixels, and released with the rest
+    DevBuf<MptVec4> mark; MptNoiseBufs noise;
     size_t cap = 0;
+    int reserve_mark() { return mark.reserve(cap) || noise.reserve(cap); }
     int reserve(size_t npix, hipStream_t stream) {     // the passes come back zeroed on `stream`
         if (npix <= cap) return 0;
         cap = 0;
@@ -204,6 +226,7 @@ struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set 
         resolved.release(); exported.release();
         for (DevBuf<MptVec4> *b : { &dn_e[0], &dn_e[1], &dn_a, &dn_n }) b->release();
         disp.release();
+        mark.release(); noise.release();
         for (auto &b : film) {
             if (b.reserve(npix)) return 1;
             HIP_TRY(hipMemsetAsync(b, 0, npix * sizeof(MptVec4), stream));
@@ -483,6 +506,13 @@ struct mpt_ctx {
         MptLaunchTimer timer;                            // mpt_get_display: {before the first kernel, after the conversion} per call
         explicit Display(MptEventPool &ev) : timer(2, ev) {}
     } display{events};
+    struct MPT_INTERNAL Noise {                          // the noise estimate (mpt_film_mark, mpt_get_noise, mpt_noise_eval)
+        bool marked = false;                             // fb.mark holds a mark of the film as it is sized now (mpt_clear and mpt_set_size drop it)
+        MappedBuf<mpt_noise_stats> stats;                // the statistics of the last call
+        DevBuf<MptVec4> film, mark; MptNoiseBufs bufs;   // mpt_noise_eval: the caller's film and mark and what the kernels write for them (grown on demand)
+        MptLaunchTimer timer;                            // mpt_get_noise: {before the estimate, after the fold} per call
+        explicit Noise(MptEventPool &ev) : timer(2, ev) {}
+    } noise{events};
     MptLaunchTimer render_timer{2, events};              // PathEngine launches: {kernel start, kernel end}
     MptLaunchTimer denoise_timer{2, events};             // mpt_get_denoised: {before the prologue, after the epilogue} per call
     MptLaunchTimer brute_timer{2, events};               // brute-force engine: {kernel start, kernel end} per launch

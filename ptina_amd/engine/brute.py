@@ -25,6 +25,10 @@ class BruteEngine(metaclass=Singleton):
         '''brute.py:24-26, `nframes` times'''
         ctx().call('mpt_render_brute', int(nframes))
 
+    def render_until(self, noise, max_spp, min_spp=16, fraction=0.0):
+        '''render until the film's noise estimate passes `noise` or `max_spp` frames are spent (engine.render_until)'''
+        return render_until(self, noise, max_spp, min_spp, fraction)
+
     def kernel_time(self):
         '''(milliseconds, launches) of the brute kernels since the last call (HIP events)'''
         ms, n = C.c_double(0), C.c_int(0)

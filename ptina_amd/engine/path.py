@@ -24,3 +24,7 @@ class PathEngine(metaclass=Singleton):
             self._film_cls = FilmTable
         self._film_cls()._hint()          # (where get_image() will want the image: a launch may write it while it drains)
         ctx().call('mpt_render', int(nframes))
+
+    def render_until(self, noise, max_spp, min_spp=16, fraction=0.0):
+        '''render until the film's noise estimate passes `noise` or `max_spp` frames are spent (engine.render_until)'''
+        return render_until(self, noise, max_spp, min_spp, fraction)

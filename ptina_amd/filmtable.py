@@ -130,6 +130,38 @@ class FilmTable(metaclass=Singleton):
         ctx().call('mpt_display_kernel_time', C.byref(ms), C.byref(n))
         return ms.value, n.value
 
+    def mark(self):
+        '''remember pass 0 as it is now, on the device (mpt_film_mark): the samples rendered from here on are the second group
+        get_noise() compares with the first.  clear() and set_size() drop the mark'''
+        ctx().call('mpt_film_mark')
+
+    def get_noise(self, threshold, map=False, remark=False):
+        '''how noisy pass 0 still is, estimated on the device from the film and the mark (mpt_get_noise, include/miptina.h): per
+        pixel e = the standard error of the mean from the two groups of samples, relative to the brightness -- Cycles' adaptive
+        sampling criterion when the groups are equal halves, so `threshold` is Blender's noise threshold.  Returns a NoiseResult:
+        valid, above (pixels with e > threshold), mean, max, fraction and, with map=True, map [nx, ny] f32 (0 where not valid).
+        remark=True also moves the mark to the film as it is now, in the same pass.  Only the statistics cross PCIe unless the
+        map is asked for.  No reference counterpart'''
+        from ._lib import NoiseStats, NoiseResult
+        nx, ny = self._res()
+        e = host_array((nx, ny)) if map else None
+        st = NoiseStats()
+        ctx().call('mpt_get_noise', float(threshold), 1 if remark else 0, None if e is None else fptr(e), C.byref(st))
+        return NoiseResult(st, e)
+
+    def get_mark(self):
+        '''test door (mpt_get_mark): the mark's raw accumulators [nx*ny, 4], like get_raw'''
+        nx, ny = self._res()
+        arr = np.empty((nx * ny, 4), np.float32)
+        ctx().call('mpt_get_mark', fptr(arr))
+        return arr
+
+    def noise_kernel_time(self):
+        '''(ms, calls): HIP-event time of the kernels of the get_noise calls since the last call'''
+        ms, n = C.c_double(0), C.c_int(0)
+        ctx().call('mpt_noise_kernel_time', C.byref(ms), C.byref(n))
+        return ms.value, n.value
+
     def fast_export_image(self, out, id=0):
         '''reference filmtable.py:66-79: flat RGB f32 at (y * nx + x) * 3 into the caller's buffer'''
         nx, ny = self._res()

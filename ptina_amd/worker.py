@@ -82,6 +82,18 @@ def get_display(**kw):
     return FilmTable().get_display(**kw)
 
 
+def get_noise(threshold, **kw):
+    '''FilmTable().get_noise(threshold, map=False, remark=False): the film's noise estimate against the mark FilmTable().mark() took,
+    on the device (no reference counterpart)'''
+    return FilmTable().get_noise(threshold, **kw)
+
+
+def render_until(noise, max_spp, **kw):
+    '''DefaultEngine().render_until(noise, max_spp, min_spp=16, fraction=0.0): render on a doubling schedule until the noise
+    estimate passes or max_spp frames are spent; expects a cleared film (no reference counterpart: its loop counts samples)'''
+    return DefaultEngine().render_until(noise, max_spp, **kw)
+
+
 def get_size():
     film = FilmTable()
     return film.nx, film.ny
