@@ -251,6 +251,18 @@ def display_params(source=0, op='aces', transfer='srgb', layout='film', dither=T
                          1 if dither else 0, 0.0 if exposure is None else float(exposure), float(key), float(white), float(gamma))
 
 
+def denoise_params(*args, who='get_denoised', **kw):
+    '''DenoiseParams from the arguments FilmTable.get_denoised takes (in this order, or by name), and their defaults (include/miptina.h states the same ones for
+    a NULL mpt_denoise_params); `who` names the caller in the TypeError an unknown keyword raises'''
+    d = dict(iterations=5, sigma_color=1.0, sigma_albedo=0.1, sigma_normal=0.3, demodulate=True)
+    unknown = set(kw) - set(d)
+    if unknown or len(args) > len(d):
+        raise TypeError('%s: unknown keyword(s) %s' % (who, sorted(unknown)) if unknown else '%s: too many arguments' % who)
+    d.update(zip(d, args), **kw)
+    return DenoiseParams(int(d['iterations']), float(d['sigma_color']), float(d['sigma_albedo']), float(d['sigma_normal']),
+                         1 if d['demodulate'] else 0)
+
+
 def fptr(a):
     return a.ctypes.data_as(_fp)
 
@@ -359,10 +371,15 @@ class Context:
         self.call('mpt_get_counters', C.byref(cnt))
         return cnt.asdict()
 
+    def timer(self, symbol, segments=1):
+        '''read out and reset one of the library's launch timers (mpt_*_kernel_time): (ms, launches) -- HIP-event time of the
+        kernels of the launches since the last read-out -- or, for a timer of several segments, (ms0, ms1, ..., launches)'''
+        ms, n = [C.c_double(0) for _ in range(segments)], C.c_int(0)
+        self.call(symbol, *map(C.byref, ms), C.byref(n))
+        return (*(m.value for m in ms), n.value)
+
     def kernel_time(self):
-        ms, n = C.c_double(0), C.c_int(0)
-        self.call('mpt_kernel_time', C.byref(ms), C.byref(n))
-        return ms.value, n.value
+        return self.timer('mpt_kernel_time')
 
 
 _ctx = None

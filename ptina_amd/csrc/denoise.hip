@@ -21,8 +21,6 @@
 #include "mpt_types.h"
 #include "film_ops.h"
 
-static_assert(sizeof(MptVec4) == sizeof(float4), "the film's records are read as float4");
-
 enum { DN_LANES = 64, DN_ROWS = 4, DN_TILE_X = 8 };     // a block is 64 lanes along y times 4 film columns; the LDS kernel's tile is 8 columns
 
 __device__ __forceinline__ float dn_tap_weight(int d) {      // h = [1/16, 1/4, 3/8, 1/4, 1/16] at d = 0 .. 4 (all products exact in f32)

@@ -4,11 +4,10 @@
 // linear radiance on the host.
 //
 //   metering    two launches, no float atomics.  Workgroup b of display_meter_kernel takes the film elements [4096 b, 4096 (b + 1)):
-//               lane t adds log(1e-4 + Y) of the valid ones among 4096 b + t + 256 k, k = 0 .. 15 ascending, the 256 lanes fold in a
-//               fixed binary tree in LDS, and the workgroup leaves (sum, count).  ONE workgroup of display_expose_kernel then folds the
-//               partials: lane t takes t, t + 256, ... ascending, the same tree, and lane 0 writes the exposure.  The shape of the
-//               sum is a function of the number of pixels alone -- not of how many CUs the launch got -- so the exposure, and with it
-//               every byte, repeats bit for bit.  The luminances are f32; their logarithms are taken and summed in f64 (free in a pass
+//               lane t adds log(1e-4 + Y) of the valid ones among 4096 b + t + 256 k, k = 0 .. 15 ascending, and the workgroup
+//               leaves (sum, count).  ONE workgroup of display_expose_kernel then folds the partials and lane 0 writes the exposure.
+//               Both stages are film_fold.h's, which says why the exposure, and with it every byte, repeats bit for bit.
+//               The luminances are f32; their logarithms are taken and summed in f64 (free in a pass
 //               that waits for memory: an f32 log's rounding does not average out over the film, it moved the exposure by two to
 //               three f32 ulps), and the exposure is rounded to f32 once: the order of the sum moves it by 1e-16, far below an ulp.
 //   conversion  one pass: sanitise, expose, operator, transfer, dither, pack, one 32-bit store per pixel.  The FILM layout streams
@@ -25,18 +24,15 @@
 #include <stdint.h>
 #include "../../include/miptina.h"
 #include "mpt_types.h"
+#include "film_ops.h"
+#include "film_fold.h"
 
-static_assert(sizeof(MptVec4) == sizeof(float4), "the film's records are read as float4");
-
-enum { DP_BLOCK = 256, DP_PER_LANE = 16, DP_RUN = DP_BLOCK * DP_PER_LANE };   // metering: 4096 consecutive film elements per workgroup
+enum { DP_BLOCK = FILM_FOLD_BLOCK, DP_PER_LANE = 16, DP_RUN = DP_BLOCK * DP_PER_LANE };   // metering: 4096 consecutive film elements per workgroup
 enum { DP_TILE_X = 64, DP_TILE_Y = 16, DP_PITCH = DP_TILE_Y + 1 };            // DISPLAY layout: tile of packed pixels, rows padded by one word
 static_assert(DP_TILE_X * DP_TILE_Y % DP_BLOCK == 0 && DP_BLOCK % DP_TILE_Y == 0 && DP_BLOCK % DP_TILE_X == 0, "tile and block");
 
 #define DP_MARKER 0x00E666E6u          // the bytes (230, 102, 230, 0): get_image's empty pixel (0.9, 0.4, 0.9, 0) at 8 bits
 #define DP_VMAX 1.0e18f                // exposed radiance is capped here: every operator has saturated long before, and v * v stays finite
-
-// c = rgb / w, then fminf(fmaxf(c, 0), 3e38): NaN -> 0 (fmaxf returns its other argument), negative -> 0, +inf -> 3e38
-__device__ __forceinline__ float dp_sanitise(float c) { return fminf(fmaxf(c, 0.0f), 3.0e38f); }
 
 __device__ __forceinline__ float dp_luma(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 
@@ -74,7 +70,7 @@ __device__ __forceinline__ unsigned dp_pixel(const float4 f, int x, int y, float
     unsigned px = 0xff000000u;
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        const float v = fminf(E * dp_sanitise(c[k]), DP_VMAX);
+        const float v = fminf(E * film_sanitise(c[k]), DP_VMAX);
         const float s = dp_transfer(dp_operator(v, a.op, a.white2), a.transfer, a.inv_gamma);
         px |= dp_quantise(s, bias) << (8 * k);
     }
@@ -82,48 +78,39 @@ __device__ __forceinline__ unsigned dp_pixel(const float4 f, int x, int y, float
 }
 
 // ---------------------------------------------------------------- metering
-struct DpAcc { double sum, n; };
+struct DpAcc {                                            // a partial: the sum of the logarithms and the count of the pixels in it
+    double sum, n;
+    static __device__ __forceinline__ DpAcc zero() { return { 0.0, 0.0 }; }
+    __device__ __forceinline__ void add(const DpAcc &o) { sum += o.sum; n += o.n; }
+    __device__ __forceinline__ DpAcc across(int h) const { return { film_lane_xor(sum, h), film_lane_xor(n, h) }; }
+};
+static_assert(sizeof(DpAcc) == 2 * sizeof(double), "mpt_launch_display_meter's `part` holds two doubles per partial");
 
-// the 256 lanes' accumulators folded in a fixed binary tree: lane t takes lane t + h for h = 128, 64, ..., 1
-__device__ __forceinline__ DpAcc dp_fold(DpAcc v, double *s_sum, double *s_n) {
-    const int t = (int)threadIdx.x;
-    s_sum[t] = v.sum; s_n[t] = v.n;
-    __syncthreads();
-#pragma unroll
-    for (int h = DP_BLOCK / 2; h > 0; h >>= 1) {
-        if (t < h) { s_sum[t] += s_sum[t + h]; s_n[t] += s_n[t + h]; }
-        __syncthreads();
-    }
-    return { s_sum[0], s_n[0] };
-}
-
-__global__ __launch_bounds__(DP_BLOCK) void display_meter_kernel(const float4 *__restrict__ src, size_t npix, double *__restrict__ part) {
-    __shared__ double s_sum[DP_BLOCK], s_n[DP_BLOCK];
+__global__ __launch_bounds__(DP_BLOCK) void display_meter_kernel(const float4 *__restrict__ src, size_t npix, DpAcc *__restrict__ part) {
+    __shared__ DpAcc s_wave[FILM_FOLD_WAVES];
     const size_t base = (size_t)blockIdx.x * DP_RUN + threadIdx.x;
-    DpAcc acc = { 0.0, 0.0 };
+    DpAcc acc = DpAcc::zero();
 #pragma unroll 4
     for (int k = 0; k < DP_PER_LANE; k++) {
         const size_t p = base + (size_t)k * DP_BLOCK;
         if (p < npix) {
             const float4 f = src[p];
             if (f.w != 0.0f) {
-                const float Y = dp_luma(dp_sanitise(f.x / f.w), dp_sanitise(f.y / f.w), dp_sanitise(f.z / f.w));
+                const float Y = dp_luma(film_sanitise(f.x / f.w), film_sanitise(f.y / f.w), film_sanitise(f.z / f.w));
                 acc.sum += log((double)(1e-4f + Y));
                 acc.n += 1.0;
             }
         }
     }
-    const DpAcc tot = dp_fold(acc, s_sum, s_n);
-    if (threadIdx.x == 0) { part[2 * (size_t)blockIdx.x] = tot.sum; part[2 * (size_t)blockIdx.x + 1] = tot.n; }
+    const DpAcc tot = film_block_fold(acc, s_wave);
+    if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
 // E = key / exp(sum / N), 1 for a film without a valid pixel; to the device word the conversion reads and to the host's mapped word
-__global__ __launch_bounds__(DP_BLOCK) void display_expose_kernel(const double *__restrict__ part, int nparts, float key,
+__global__ __launch_bounds__(DP_BLOCK) void display_expose_kernel(const DpAcc *__restrict__ part, int nparts, float key,
                                                                   float *__restrict__ e_dev, float *__restrict__ e_host) {
-    __shared__ double s_sum[DP_BLOCK], s_n[DP_BLOCK];
-    DpAcc acc = { 0.0, 0.0 };
-    for (int q = (int)threadIdx.x; q < nparts; q += DP_BLOCK) { acc.sum += part[2 * (size_t)q]; acc.n += part[2 * (size_t)q + 1]; }
-    const DpAcc tot = dp_fold(acc, s_sum, s_n);
+    __shared__ DpAcc s_wave[FILM_FOLD_WAVES];
+    const DpAcc tot = film_fold_parts(part, nparts, s_wave);
     if (threadIdx.x == 0) {
         const float E = tot.n > 0.0 ? (float)((double)key / exp(tot.sum / tot.n)) : 1.0f;
         *e_dev = E;
@@ -167,15 +154,15 @@ __global__ __launch_bounds__(DP_BLOCK) void display_transpose_kernel(const float
 }
 
 // ---------------------------------------------------------------- launchers
-MPT_KERNEL_API size_t mpt_display_parts(size_t npix) { return (npix + DP_RUN - 1) / DP_RUN; }
+MPT_KERNEL_API size_t mpt_display_parts(size_t npix) { return film_fold_count(npix, DP_RUN); }
 
 // part: 2 * mpt_display_parts(npix) doubles
 MPT_KERNEL_API hipError_t mpt_launch_display_meter(const MptVec4 *src, size_t npix, double *part, float key, float *e_dev, float *e_host,
                                                    hipStream_t stream) {
-    const size_t nparts = mpt_display_parts(npix);
-    if (nparts > 0x7fffffffULL) return hipErrorInvalidConfiguration;
-    if (nparts) hipLaunchKernelGGL(display_meter_kernel, dim3((unsigned)nparts), dim3(DP_BLOCK), 0, stream, (const float4 *)src, npix, part);
-    hipLaunchKernelGGL(display_expose_kernel, dim3(1), dim3(DP_BLOCK), 0, stream, (const double *)part, (int)nparts, key, e_dev, e_host);
+    unsigned nparts;
+    if (const hipError_t e = film_fold_grid(npix, DP_RUN, &nparts)) return e;
+    if (nparts) hipLaunchKernelGGL(display_meter_kernel, dim3(nparts), dim3(DP_BLOCK), 0, stream, (const float4 *)src, npix, (DpAcc *)part);
+    hipLaunchKernelGGL(display_expose_kernel, dim3(1), dim3(DP_BLOCK), 0, stream, (const DpAcc *)part, (int)nparts, key, e_dev, e_host);
     return hipGetLastError();
 }
 

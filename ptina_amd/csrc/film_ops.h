@@ -1,8 +1,15 @@
-// film_ops.h -- the per-pixel film operations and the sample slab's entry format, shared by the small kernels (aux_kernels.hip) and
-// the render kernel's tail finalisation (render_kernel.hip): ONE definition each, so that a film finalised inside the render launch
-// is bit for bit the film the combine + resolve passes produce.  Plain IEEE adds and divides (no contraction can touch them).
+// film_ops.h -- the per-pixel film operations and the sample slab's entry format, shared by the small kernels (aux_kernels.hip), the
+// render kernel's tail finalisation (render_kernel.hip) and the read-back kernels (denoise.hip, display.hip, noise.hip): ONE
+// definition each, so that a film finalised inside the render launch is bit for bit the film the combine + resolve passes produce.
+// Plain IEEE adds and divides (no contraction can touch them).
 #pragma once
 #include "mpt_types.h"
+
+static_assert(sizeof(MptVec4) == sizeof(float4), "the film's records are read as float4");
+
+// what a read-back makes of a mean c = rgb / w before it looks at it (display.hip, noise.hip): fminf(fmaxf(c, 0), 3e38), so
+// NaN -> 0 (fmaxf returns its other argument), negative -> 0, +inf -> 3e38
+__device__ __forceinline__ float film_sanitise(float c) { return fminf(fmaxf(c, 0.0f), 3.0e38f); }
 
 // film[pix] += sample: one frame of FilmTable's running sum, reference filmtable.py:37-39 / path.py:93 ((r, g, b, 1) per sample)
 __device__ __forceinline__ void film_add_sample(MptVec4 &a, float r, float g, float b) {

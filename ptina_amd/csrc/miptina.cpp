@@ -2,8 +2,8 @@
 //
 // Owns the device state of one PTina "scene" (the singletons of ptina/things.py:20-28 collapsed
 // into one context), uploads the scene, advances the Sobol sampler, batches enqueued frames into
-// single launches and reads the film back.  The BVH builders are in tree_build.cpp, the RCCL film
-// gather in comm.cpp.  No PyTorch, no Python: plain HIP runtime calls.
+// single launches.  The film's read-backs are in film_read.cpp, the BVH builders in tree_build.cpp,
+// the RCCL film gather in comm.cpp.  No PyTorch, no Python: plain HIP runtime calls.
 
 #include "miptina_ctx.h"
 
@@ -223,14 +223,14 @@ static bool is_locked_range(const void *p, size_t bytes) {
 }
 
 // the device alias of a caller array that is page-locked memory of ours, for kernels to write straight into (option "zero_copy"), or null
-static void *caller_alias(const mpt_ctx *c, void *p, size_t bytes) {
+void *caller_alias(const mpt_ctx *c, void *p, size_t bytes) {
     void *mapped = nullptr;
     if (c->opt.zero_copy && is_locked_range(p, bytes) && hipHostGetDevicePointer(&mapped, p, 0) == hipSuccess) return mapped;
     return nullptr;
 }
 
 // device -> caller buffer on the main stream, blocking
-static int read_back(mpt_ctx *c, void *out, const void *dev, size_t bytes) {
+int read_back(mpt_ctx *c, void *out, const void *dev, size_t bytes) {
     if (is_locked_range(out, bytes)) {
         HIP_TRY(hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1173,7 +1173,7 @@ extern "C" int mpt_mlt_trace(mpt_ctx *c, const float *X, float *rgb, int n) {
 
 // The read-out of an engine's launch timer: what is enqueued is launched, the main stream (and, for launches recorded on them, the
 // aux and render streams) waited for, and the launches' segments summed: ms0, and ms1 where a launch has two.
-static int timer_readout(mpt_ctx *c, MptLaunchTimer &timer, double *ms0, double *ms1, int *launches, bool render_streams = false) {
+int timer_readout(mpt_ctx *c, MptLaunchTimer &timer, double *ms0, double *ms1, int *launches, bool render_streams) {
     if (mpt_flush(c)) return 1;
     if (wait_all(c, render_streams)) return 1;
     double seg[2] = { 0, 0 };
@@ -1236,328 +1236,6 @@ extern "C" int mpt_synchronize(mpt_ctx *c) {                                   /
     if (mpt_flush(c)) return 1;
     if (wait_all(c)) return 1;
     return check_watchdog(c);
-}
-
-extern "C" int mpt_clear(mpt_ctx *c, int pass) {                               // filmtable.py:44-45: every pass, `id` ignored
-    (void)pass;
-    if (use(c)) return 1;
-    size_t npix = (size_t)c->nx * c->ny;
-    for (int p = 0; p < 3; p++)
-        if (c->fb.film[p]) HIP_TRY(hipMemsetAsync(c->fb.film[p], 0, npix * sizeof(MptVec4), c->stream));
-    c->film_version++;
-    c->noise.marked = false;                     // the samples the mark counted are gone
-    return 0;
-}
-
-int check_pass(mpt_ctx *c, int pass) {
-    if (pass < 0 || pass >= 3) return fail("film pass %d out of range", pass);
-    if (!c->fb.film[pass]) return fail("film size not set: call set_size() first");
-    return 0;
-}
-
-extern "C" int mpt_resolve(mpt_ctx *c, int pass) {
-    if (use_ro(c)) return 1;
-    if (mpt_flush(c)) return 1;
-    if (check_pass(c, pass)) return 1;
-    HIP_TRY(mpt_launch_resolve(c->fb.film[pass], c->fb.resolved, (size_t)c->nx * c->ny, c->stream));
-    return 0;
-}
-
-extern "C" int mpt_hint_image(mpt_ctx *c, int pass, float *out) {
-    if (use_ro(c)) return 1;
-    if (pass != 0) return 0;                   // only the path pass is finalised inside the render launch
-    if (c->early.hint == out) return 0;
-    // the old array may be the one a launch in flight is writing its image into: the caller is free to let go of it after this call
-    if (c->early.ptr && c->early.ptr == c->early.hint) HIP_TRY(hipStreamSynchronize(c->stream));
-    c->early.hint = out;
-    c->early.ptr = nullptr;
-    return 0;
-}
-
-extern "C" int mpt_get_image(mpt_ctx *c, int pass, float *out) {               // filmtable.py:47-63
-    if (use_ro(c)) return 1;                   // validates the handle and makes the context's device current (round-3 ADVICE)
-    const size_t bytes = (size_t)c->nx * c->ny * sizeof(MptVec4);
-    if (pass == 0) {
-        // The launch that rendered the frames may have written this very image already (tail finalisation, mpt_hint_image): then
-        // there is nothing left to do but wait for it.  The hint is spent either way: the array is the caller's from here on.
-        if (mpt_flush(c)) return 1;
-        const bool early = out && c->early.ptr == out && c->early.version == c->film_version;
-        if (c->early.hint == out || c->early.ptr == out) {
-            if (!early && c->early.ptr == out) HIP_TRY(hipStreamSynchronize(c->stream));    // (a stale image still being written)
-            c->early.hint = nullptr; c->early.ptr = nullptr;
-        }
-        if (early) {
-            if (check_pass(c, pass)) return 1;
-            // the launch's own stream: one completion signal (the main stream, which waits for the same launch before anything else
-            // it is given, would add a cross-stream hop in front of the host's wake-up)
-            // ... and polled, for a while, instead of slept on: the runtime's blocking wait returned 18 us after the kernel's end
-            // (HIP trace), a query loop sees the completion signal within a few; a launch that runs longer than the poll window
-            // falls back to the blocking wait (option "spin_us", 0 = always block)
-            if (c->opt.spin_us > 0) {
-                const auto t0 = std::chrono::steady_clock::now();
-                for (;;) {
-                    const hipError_t q = hipStreamQuery(c->early.stream);
-                    if (q == hipSuccess) return check_watchdog(c);
-                    if (q != hipErrorNotReady) HIP_TRY(q);
-                    if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > (double)c->opt.spin_us) break;
-                }
-            }
-            HIP_TRY(hipStreamSynchronize(c->early.stream));
-            return check_watchdog(c);
-        }
-    }
-    if (void *mapped = caller_alias(c, out, bytes)) {
-        // the caller's array is page-locked memory of ours: the resolve pass writes the image straight into it over PCIe,
-        // instead of into a device buffer that a DMA then copies (one dependent hop and the copy engine's start-up less)
-        if (mpt_flush(c)) return 1;
-        if (check_pass(c, pass)) return 1;
-        HIP_TRY(mpt_launch_resolve(c->fb.film[pass], (MptVec4 *)mapped, (size_t)c->nx * c->ny, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return check_watchdog(c);
-    }
-    if (mpt_resolve(c, pass)) return 1;
-    if (read_back(c, out, c->fb.resolved, bytes)) return 1;
-    return check_watchdog(c);
-}
-
-extern "C" int mpt_fast_export_image(mpt_ctx *c, int pass, float *out) {       // filmtable.py:66-79
-    if (use_ro(c)) return 1;
-    if (mpt_flush(c)) return 1;
-    if (check_pass(c, pass)) return 1;
-    HIP_TRY(mpt_launch_export(c->fb.film[pass], c->fb.exported, c->nx, c->ny, c->stream));
-    if (read_back(c, out, c->fb.exported, (size_t)c->nx * c->ny * 3 * sizeof(float))) return 1;
-    return check_watchdog(c);
-}
-
-extern "C" int mpt_get_film_raw(mpt_ctx *c, int pass, float *out) {
-    if (use_ro(c)) return 1;
-    if (mpt_flush(c)) return 1;
-    if (check_pass(c, pass)) return 1;
-    if (read_back(c, out, c->fb.film[pass], (size_t)c->nx * c->ny * sizeof(MptVec4))) return 1;
-    return check_watchdog(c);
-}
-
-// ------------------------------------------------------------------ denoised read-back (denoise.hip)
-// Film pass 0 filtered by the edge-avoiding A-Trous wavelet, guided by passes 1 and 2, read back like mpt_get_image.  Runs on the
-// main stream behind everything enqueued (the flush makes that stream wait for the render launches, as for mpt_get_film_raw);
-// reads the three passes, writes only the context's working buffers, and knows nothing of mpt_hint_image's array.
-static int denoise_params(const mpt_denoise_params *params, mpt_denoise_params &p) {
-    p = { 5, 1.0f, 0.1f, 0.3f, 1 };
-    if (params) p = *params;
-    if (p.iterations < 0 || p.iterations > 8) return fail("denoise: iterations must be in 0..8, got %d", p.iterations);
-    const struct { const char *name; float v; } sig[3] = { { "sigma_color", p.sigma_color }, { "sigma_albedo", p.sigma_albedo }, { "sigma_normal", p.sigma_normal } };
-    for (const auto &s : sig)
-        if (!(std::isfinite(s.v) && s.v > 0.0f)) return fail("denoise: %s must be finite and positive, got %g", s.name, (double)s.v);
-    return 0;
-}
-
-// the filter's launches on the main stream (mpt_get_denoised and mpt_get_display's denoised source); *img = the working buffer that
-// holds the image behind them
-static int denoise_launches(mpt_ctx *c, const mpt_denoise_params &p, const MptVec4 **img) {
-    const size_t npix = (size_t)c->nx * c->ny;
-    if (p.iterations == 0) {
-        // nothing to filter: the resolve pass itself, so that the image is mpt_get_image(0)'s bit for bit
-        HIP_TRY(mpt_launch_resolve(c->fb.film[0], c->fb.dn_e[0], npix, c->stream));
-        *img = c->fb.dn_e[0];
-        return 0;
-    }
-    HIP_TRY(mpt_launch_denoise_prologue(c->fb.film[0], c->fb.film[1], c->fb.film[2], c->fb.dn_e[0], c->fb.dn_a, c->fb.dn_n, npix, p.demodulate ? 1 : 0, c->stream));
-    const float ka = 1.0f / (p.sigma_albedo * p.sigma_albedo), kn = 1.0f / (p.sigma_normal * p.sigma_normal);
-    for (int i = 0; i < p.iterations; i++) {
-        const float sc = p.sigma_color * std::ldexp(1.0f, -i);             // the colour edge-stopping narrows as the stencil widens
-        HIP_TRY(mpt_launch_denoise_atrous(c->fb.dn_e[i & 1], c->fb.dn_e[(i + 1) & 1], c->fb.dn_a, c->fb.dn_n, c->nx, c->ny, 1 << i,
-                                          1.0f / (sc * sc), ka, kn, c->opt.denoise_lds, c->stream));
-    }
-    const int last = p.iterations & 1;
-    HIP_TRY(mpt_launch_denoise_epilogue(c->fb.dn_e[last], c->fb.dn_a, c->fb.dn_e[last ^ 1], npix, p.demodulate ? 1 : 0, c->stream));
-    *img = c->fb.dn_e[last ^ 1];
-    return 0;
-}
-
-extern "C" int mpt_get_denoised(mpt_ctx *c, const mpt_denoise_params *params, float *out) {
-    if (use_ro(c)) return 1;
-    mpt_denoise_params p;
-    if (!out) return fail("mpt_get_denoised: null output");
-    if (denoise_params(params, p)) return 1;
-    if (mpt_flush(c)) return 1;
-    if (check_pass(c, 0)) return 1;
-    const size_t npix = (size_t)c->nx * c->ny;
-    const MptVec4 *img = nullptr;
-    MptTimedSpan span(c->denoise_timer, c->stream);
-    HIP_TRY(span.begun);
-    if (denoise_launches(c, p, &img)) return 1;
-    HIP_TRY(span.end());
-    if (read_back(c, out, img, npix * sizeof(MptVec4))) return 1;
-    return check_watchdog(c);
-}
-
-extern "C" int mpt_denoise_kernel_time(mpt_ctx *c, double *ms, int *launches) {
-    return use_ro(c) || timer_readout(c, c->denoise_timer, ms, nullptr, launches);
-}
-
-// ------------------------------------------------------------------ 8-bit display read-back (display.hip)
-// The source tone-mapped, transfer-encoded, dithered and packed to RGBA8 on the device, read back like mpt_get_image: straight into an
-// mpt_host_alloc array through its mapped pointer (option "zero_copy"), else into the film owner's image and one copy.  On the main
-// stream behind everything enqueued, like mpt_get_denoised; reads film passes, writes only the context's working buffers.
-static int display_params(const mpt_display_params *params, mpt_display_params &p, MptDisplayArgs &a) {
-    p = { 0, MPT_TONE_ACES, MPT_TRANSFER_SRGB, MPT_LAYOUT_FILM, 1, 0.0f, 0.18f, 4.0f, 2.2f };
-    if (params) p = *params;
-    if (p.op < MPT_TONE_LINEAR || p.op > MPT_TONE_ACES) return fail("display: unknown op %d", p.op);
-    if (p.transfer != MPT_TRANSFER_SRGB && p.transfer != MPT_TRANSFER_GAMMA) return fail("display: unknown transfer %d", p.transfer);
-    if (p.layout != MPT_LAYOUT_FILM && p.layout != MPT_LAYOUT_DISPLAY) return fail("display: unknown layout %d", p.layout);
-    if (!(std::isfinite(p.exposure) && p.exposure >= 0.0f)) return fail("display: exposure must be finite and not negative (0 = auto), got %g", (double)p.exposure);
-    const struct { const char *name; float v; } pos[3] = { { "key", p.key }, { "white", p.white }, { "gamma", p.gamma } };
-    for (const auto &s : pos)
-        if (!(std::isfinite(s.v) && s.v > 0.0f)) return fail("display: %s must be finite and positive, got %g", s.name, (double)s.v);
-    a = { p.op, p.transfer, p.layout, p.dither ? 1 : 0, p.exposure, p.white * p.white, 1.0f / p.gamma };
-    return 0;
-}
-
-// metering (auto exposure only) and conversion of `src` [nx*ny] into `dst` on the main stream; `dst` may be a mapped host pointer
-static int display_launches(mpt_ctx *c, const mpt_display_params &p, const MptDisplayArgs &a, const MptVec4 *src, int nx, int ny,
-                            MptDisplayBufs &b, uint32_t *dst) {
-    const float *e_dev = nullptr;
-    if (p.exposure == 0.0f) {
-        HIP_TRY(mpt_launch_display_meter(src, (size_t)nx * ny, b.part, p.key, b.exposure, c->display.exposure.dev, c->stream));
-        e_dev = b.exposure;
-    }
-    HIP_TRY(mpt_launch_display_convert(src, dst, nx, ny, &a, e_dev, c->stream));
-    return 0;
-}
-
-// the bytes to the caller (zero-copy: they are there once the stream is idle) and the exposure used
-static int display_finish(mpt_ctx *c, const mpt_display_params &p, bool direct, uint8_t *out, const uint32_t *dev, size_t npix, float *exposure_used) {
-    if (direct) HIP_TRY(hipStreamSynchronize(c->stream));
-    else if (read_back(c, out, dev, npix * 4)) return 1;
-    if (exposure_used) *exposure_used = p.exposure == 0.0f ? *(volatile float *)c->display.exposure.host.p : p.exposure;
-    return 0;
-}
-
-extern "C" int mpt_get_display(mpt_ctx *c, const mpt_display_params *params, const mpt_denoise_params *denoise, uint8_t *out, float *exposure_used) {
-    if (use_ro(c)) return 1;
-    mpt_display_params p;
-    MptDisplayArgs a;
-    mpt_denoise_params dp;
-    if (!out) return fail("mpt_get_display: null output");
-    if (display_params(params, p, a)) return 1;
-    const bool denoised = p.source == MPT_DISPLAY_DENOISED;
-    if (!denoised && (p.source < 0 || p.source >= 3)) return fail("display: film pass %d out of range", p.source);
-    if (denoised && denoise_params(denoise, dp)) return 1;
-    if (mpt_flush(c)) return 1;
-    if (check_pass(c, denoised ? 0 : p.source)) return 1;
-    const size_t npix = (size_t)c->nx * c->ny;
-    void *const direct = caller_alias(c, out, npix * 4);
-    const MptVec4 *src = denoised ? nullptr : c->fb.film[p.source].p;
-    MptTimedSpan span(c->display.timer, c->stream);
-    HIP_TRY(span.begun);
-    if (denoised && denoise_launches(c, dp, &src)) return 1;       // the float image stays on the device
-    if (display_launches(c, p, a, src, c->nx, c->ny, c->fb.disp, direct ? (uint32_t *)direct : c->fb.disp.rgba8.p)) return 1;
-    HIP_TRY(span.end());
-    if (display_finish(c, p, direct != nullptr, out, c->fb.disp.rgba8, npix, exposure_used)) return 1;
-    return check_watchdog(c);
-}
-
-extern "C" int mpt_display_kernel_time(mpt_ctx *c, double *ms, int *launches) {
-    return use_ro(c) || timer_readout(c, c->display.timer, ms, nullptr, launches);
-}
-
-// test door: the same launches on the caller's accumulators, in buffers of its own (no film pass, no film-owner buffer is touched)
-extern "C" int mpt_display_eval(mpt_ctx *c, const mpt_display_params *params, const float *raw, int nx, int ny, uint8_t *out, float *exposure_used) {
-    if (use_ro(c)) return 1;
-    mpt_display_params p;
-    MptDisplayArgs a;
-    if (!out || !raw) return fail("mpt_display_eval: null %s", out ? "input" : "output");
-    if (display_params(params, p, a)) return 1;
-    if (nx < 1 || ny < 1 || (long long)nx * ny > (long long)c->caps.max_filmsize)
-        return fail("mpt_display_eval: film %dx%d outside 1 .. max_filmsize=%d pixels", nx, ny, c->caps.max_filmsize);
-    const size_t npix = (size_t)nx * ny;
-    if (npix > c->display.raw.cap || npix > c->display.bufs.cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->display.raw.reserve(npix) || c->display.bufs.reserve(npix)) return 1;
-    }
-    HIP_TRY(hipMemcpyAsync(c->display.raw, raw, npix * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));                      // (`raw` is pageable: the copy is staged, the caller's array is free again)
-    if (display_launches(c, p, a, c->display.raw, nx, ny, c->display.bufs, c->display.bufs.rgba8)) return 1;
-    return display_finish(c, p, false, out, c->display.bufs.rgba8, npix, exposure_used);
-}
-
-// ------------------------------------------------------------------ noise estimate (noise.hip)
-// The mark is a device copy of film pass 0; the estimate compares the film with it.  Everything runs on the main stream behind
-// what is enqueued (the flush makes that stream wait for the render launches, as for mpt_get_film_raw); reads pass 0, writes only the
-// mark and the context's working buffers, and knows nothing of mpt_hint_image's array.
-extern "C" int mpt_film_mark(mpt_ctx *c) {
-    if (use_ro(c)) return 1;
-    if (mpt_flush(c)) return 1;
-    if (check_pass(c, 0)) return 1;
-    if (c->fb.reserve_mark()) return 1;
-    HIP_TRY(hipMemcpyAsync(c->fb.mark, c->fb.film[0], (size_t)c->nx * c->ny * sizeof(MptVec4), hipMemcpyDeviceToDevice, c->stream));
-    c->noise.marked = true;
-    return 0;
-}
-
-static int noise_threshold(const char *who, float threshold) {
-    if (!(std::isfinite(threshold) && threshold >= 0.0f)) return fail("%s: threshold must be finite and not negative, got %g", who, (double)threshold);
-    return 0;
-}
-
-// the map and the statistics of the launches just enqueued to the caller (each may be null)
-static int noise_finish(mpt_ctx *c, const MptNoiseBufs &b, size_t npix, float *map, mpt_noise_stats *stats) {
-    if (map) { if (read_back(c, map, b.map, npix * sizeof(float))) return 1; }
-    else HIP_TRY(hipStreamSynchronize(c->stream));
-    if (stats) memcpy(stats, (const void *)c->noise.stats.host.p, sizeof *stats);
-    return 0;
-}
-
-extern "C" int mpt_get_noise(mpt_ctx *c, float threshold, int remark, float *map, mpt_noise_stats *stats) {
-    if (use_ro(c)) return 1;
-    if (!map && !stats) return fail("mpt_get_noise: null map and null statistics");
-    if (noise_threshold("mpt_get_noise", threshold)) return 1;
-    if (!c->noise.marked) return fail("mpt_get_noise: no mark: call mpt_film_mark() first (mpt_clear and mpt_set_size drop the mark)");
-    if (mpt_flush(c)) return 1;
-    if (check_pass(c, 0)) return 1;
-    const size_t npix = (size_t)c->nx * c->ny;
-    MptTimedSpan span(c->noise.timer, c->stream);
-    HIP_TRY(span.begun);
-    HIP_TRY(mpt_launch_noise(c->fb.film[0], c->fb.mark, npix, threshold, remark ? 1 : 0, map ? c->fb.noise.map.p : nullptr, c->fb.noise.part,
-                             c->noise.stats.dev, c->stream));
-    HIP_TRY(span.end());
-    if (noise_finish(c, c->fb.noise, npix, map, stats)) return 1;
-    return check_watchdog(c);
-}
-
-extern "C" int mpt_get_mark(mpt_ctx *c, float *out) {
-    if (use_ro(c)) return 1;
-    if (!out) return fail("mpt_get_mark: null output");
-    if (!c->noise.marked) return fail("mpt_get_mark: no mark: call mpt_film_mark() first (mpt_clear and mpt_set_size drop the mark)");
-    if (mpt_flush(c)) return 1;
-    return read_back(c, out, c->fb.mark, (size_t)c->nx * c->ny * sizeof(MptVec4));
-}
-
-extern "C" int mpt_noise_kernel_time(mpt_ctx *c, double *ms, int *launches) {
-    return use_ro(c) || timer_readout(c, c->noise.timer, ms, nullptr, launches);
-}
-
-// test door: the same launches on the caller's film and mark, in buffers of its own (no film pass and not the context's mark)
-extern "C" int mpt_noise_eval(mpt_ctx *c, float threshold, const float *film_raw, const float *mark_raw, int nx, int ny, float *map,
-                              float *new_mark, mpt_noise_stats *stats) {
-    if (use_ro(c)) return 1;
-    if (!film_raw || !mark_raw) return fail("mpt_noise_eval: null input");
-    if (noise_threshold("mpt_noise_eval", threshold)) return 1;
-    if (nx < 1 || ny < 1 || (long long)nx * ny > (long long)c->caps.max_filmsize)
-        return fail("mpt_noise_eval: film %dx%d outside 1 .. max_filmsize=%d pixels", nx, ny, c->caps.max_filmsize);
-    const size_t npix = (size_t)nx * ny;
-    auto &d = c->noise;
-    if (npix > d.film.cap || npix > d.mark.cap || npix > d.bufs.cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (d.film.reserve(npix) || d.mark.reserve(npix) || d.bufs.reserve(npix)) return 1;
-    }
-    HIP_TRY(hipMemcpyAsync(d.film, film_raw, npix * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d.mark, mark_raw, npix * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));                      // (the arrays are pageable: the copies are staged, the caller's arrays are free again)
-    HIP_TRY(mpt_launch_noise(d.film, d.mark, npix, threshold, new_mark ? 1 : 0, map ? d.bufs.map.p : nullptr, d.bufs.part, d.stats.dev, c->stream));
-    if (noise_finish(c, d.bufs, npix, map, stats)) return 1;
-    if (new_mark && read_back(c, new_mark, d.mark, npix * sizeof(MptVec4))) return 1;
-    return 0;
 }
 
 // ------------------------------------------------------------------ measurement

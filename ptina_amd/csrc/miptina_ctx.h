@@ -206,6 +206,19 @@ struct MPT_INTERNAL MptNoiseBufs {         // what mpt_get_noise's kernels write
     }
 };
 
+struct MPT_INTERNAL MptDoorInput {         // the test doors' input: the caller's accumulators for a film of up to `cap` pixels
+    DevBuf<MptVec4> acc[2];              // mpt_display_eval uses the first; mpt_noise_eval both: the film, and the mark it may rewrite
+    size_t cap = 0;
+    int reserve(size_t npix) {
+        if (npix <= cap) return 0;
+        cap = 0;
+        acc[0].release(); acc[1].release();
+        if (acc[0].reserve(npix) || acc[1].reserve(npix)) return 1;
+        cap = npix;
+        return 0;
+    }
+};
+
 struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set so far
     DevBuf<MptVec4> film[3];
     DevBuf<MptVec4> resolved;            // nx*ny float4 (get_image staging on device)
@@ -502,17 +515,18 @@ struct mpt_ctx {
     } mlt{events};
     struct MPT_INTERNAL Display {                        // the display door (mpt_get_display, mpt_display_eval)
         MappedBuf<float> exposure;                       // the metered exposure of the last call
-        DevBuf<MptVec4> raw; MptDisplayBufs bufs;        // mpt_display_eval: the caller's accumulators and what the kernels write for them (grown on demand)
+        MptDisplayBufs bufs;                             // mpt_display_eval: what the kernels write for the caller's accumulators (grown on demand)
         MptLaunchTimer timer;                            // mpt_get_display: {before the first kernel, after the conversion} per call
         explicit Display(MptEventPool &ev) : timer(2, ev) {}
     } display{events};
     struct MPT_INTERNAL Noise {                          // the noise estimate (mpt_film_mark, mpt_get_noise, mpt_noise_eval)
         bool marked = false;                             // fb.mark holds a mark of the film as it is sized now (mpt_clear and mpt_set_size drop it)
         MappedBuf<mpt_noise_stats> stats;                // the statistics of the last call
-        DevBuf<MptVec4> film, mark; MptNoiseBufs bufs;   // mpt_noise_eval: the caller's film and mark and what the kernels write for them (grown on demand)
+        MptNoiseBufs bufs;                               // mpt_noise_eval: what the kernels write for the caller's film and mark (grown on demand)
         MptLaunchTimer timer;                            // mpt_get_noise: {before the estimate, after the fold} per call
         explicit Noise(MptEventPool &ev) : timer(2, ev) {}
     } noise{events};
+    MptDoorInput door;                                   // mpt_display_eval, mpt_noise_eval: the caller's accumulators on the device (grown on demand)
     MptLaunchTimer render_timer{2, events};              // PathEngine launches: {kernel start, kernel end}
     MptLaunchTimer denoise_timer{2, events};             // mpt_get_denoised: {before the prologue, after the epilogue} per call
     MptLaunchTimer brute_timer{2, events};               // brute-force engine: {kernel start, kernel end} per launch
@@ -564,8 +578,14 @@ struct mpt_ctx {
 // entry checks of the API calls (miptina.cpp)
 MPT_INTERNAL int use_ro(mpt_ctx *c);   // calls that only read results
 MPT_INTERNAL int use(mpt_ctx *c);      // calls that may change what the next render launch reads
-MPT_INTERNAL int check_pass(mpt_ctx *c, int pass);
 MPT_INTERNAL int check_watchdog(mpt_ctx *c);   // after a synchronise: did a persistent kernel give up?
+// what the read-backs (film_read.cpp) take from miptina.cpp, beside mpt_flush
+MPT_INTERNAL int read_back(mpt_ctx *c, void *out, const void *dev, size_t bytes);   // device -> caller buffer on the main stream, blocking
+MPT_INTERNAL void *caller_alias(const mpt_ctx *c, void *p, size_t bytes);           // the device alias of a page-locked caller array of ours, or null
+MPT_INTERNAL int timer_readout(mpt_ctx *c, MptLaunchTimer &timer, double *ms0, double *ms1, int *launches, bool render_streams = false);
+
+// film_read.cpp
+MPT_INTERNAL int check_pass(mpt_ctx *c, int pass);
 
 // comm.cpp
 MPT_INTERNAL void mpt_comm_release(mpt_ctx *c);   // mpt_destroy: drop the communicator, if any

@@ -13,7 +13,6 @@ from ..sampling import *              # noqa: F401,F403  (the reference star-imp
 from ..sampling.sobol import *        # noqa: F401,F403
 from ..common import Singleton, register, ctx, np
 from ..sampling.sobol import SobolSampler
-import ctypes as C
 
 
 @register
@@ -31,6 +30,4 @@ class BruteEngine(metaclass=Singleton):
 
     def kernel_time(self):
         '''(milliseconds, launches) of the brute kernels since the last call (HIP events)'''
-        ms, n = C.c_double(0), C.c_int(0)
-        ctx().call('mpt_brute_kernel_time', C.byref(ms), C.byref(n))
-        return ms.value, n.value
+        return ctx().timer('mpt_brute_kernel_time')

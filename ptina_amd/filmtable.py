@@ -77,22 +77,20 @@ class FilmTable(metaclass=Singleton):
             raise
         return arr
 
-    def get_denoised(self, iterations=5, sigma_color=1.0, sigma_albedo=0.1, sigma_normal=0.3, demodulate=True):
+    def get_denoised(self, *denoise_args, **denoise_kw):
         '''pass 0 filtered on the device by the edge-avoiding A-Trous wavelet, guided by the albedo and normal passes the
-        PreviewEngine renders (mpt_get_denoised, include/miptina.h): [nx, ny, 4] f32 like get_image, a fresh array.  No reference
+        PreviewEngine renders (mpt_get_denoised, include/miptina.h): [nx, ny, 4] f32 like get_image, a fresh array.  The arguments
+        and their defaults are _lib.denoise_params': iterations, sigma_color, sigma_albedo, sigma_normal, demodulate.  No reference
         counterpart: its add-on hands the Albedo pass to Blender's denoiser'''
-        from ._lib import DenoiseParams
+        from ._lib import denoise_params
         nx, ny = self._res()
         arr = host_array((nx, ny, 4))
-        p = DenoiseParams(int(iterations), float(sigma_color), float(sigma_albedo), float(sigma_normal), 1 if demodulate else 0)
-        ctx().call('mpt_get_denoised', C.byref(p), fptr(arr))
+        ctx().call('mpt_get_denoised', C.byref(denoise_params(*denoise_args, **denoise_kw)), fptr(arr))
         return arr
 
     def denoise_kernel_time(self):
         '''(ms, calls): HIP-event time of the filter's kernels in the get_denoised calls since the last call'''
-        ms, n = C.c_double(0), C.c_int(0)
-        ctx().call('mpt_denoise_kernel_time', C.byref(ms), C.byref(n))
-        return ms.value, n.value
+        return ctx().timer('mpt_denoise_kernel_time')
 
     def get_display(self, id=0, denoised=False, op='aces', transfer='srgb', layout='film', dither=True, exposure=None, key=0.18,
                     white=4.0, gamma=2.2, **denoise_kw):
@@ -102,20 +100,14 @@ class FilmTable(metaclass=Singleton):
         (mpt_get_display, include/miptina.h).  A fresh page-locked uint8 array: [nx, ny, 4] for layout='film' (indexed like
         get_image), [ny, nx, 4] with rows top-down for layout='display' (what image.write_png takes).  The exposure used is kept as
         last_exposure.  No reference counterpart: its scripts show linear radiance (ptina/wip/tonemapping.py was never wired in)'''
-        from ._lib import DenoiseParams, display_params, DISPLAY_DENOISED, LAYOUTS
+        from ._lib import denoise_params, display_params, DISPLAY_DENOISED, LAYOUTS
         nx, ny = self._res()
         if not denoised and int(id) < 0:
             raise RuntimeError('display: film pass %d out of range' % int(id))
         p = display_params(DISPLAY_DENOISED if denoised else id, op, transfer, layout, dither, exposure, key, white, gamma)
         dn = None
         if denoised:
-            d = dict(iterations=5, sigma_color=1.0, sigma_albedo=0.1, sigma_normal=0.3, demodulate=True)
-            unknown = set(denoise_kw) - set(d)
-            if unknown:
-                raise TypeError('get_display: unknown keyword(s) %s' % sorted(unknown))
-            d.update(denoise_kw)
-            dn = C.byref(DenoiseParams(int(d['iterations']), float(d['sigma_color']), float(d['sigma_albedo']), float(d['sigma_normal']),
-                                       1 if d['demodulate'] else 0))
+            dn = C.byref(denoise_params(who='get_display', **denoise_kw))
         elif denoise_kw:
             raise TypeError('get_display: %s only apply with denoised=True' % sorted(denoise_kw))
         arr = host_array((ny, nx, 4) if p.layout == LAYOUTS['display'] else (nx, ny, 4), np.uint8)
@@ -126,9 +118,7 @@ class FilmTable(metaclass=Singleton):
 
     def display_kernel_time(self):
         '''(ms, calls): HIP-event time of the kernels of the get_display calls since the last call'''
-        ms, n = C.c_double(0), C.c_int(0)
-        ctx().call('mpt_display_kernel_time', C.byref(ms), C.byref(n))
-        return ms.value, n.value
+        return ctx().timer('mpt_display_kernel_time')
 
     def mark(self):
         '''remember pass 0 as it is now, on the device (mpt_film_mark): the samples rendered from here on are the second group
@@ -158,9 +148,7 @@ class FilmTable(metaclass=Singleton):
 
     def noise_kernel_time(self):
         '''(ms, calls): HIP-event time of the kernels of the get_noise calls since the last call'''
-        ms, n = C.c_double(0), C.c_int(0)
-        ctx().call('mpt_noise_kernel_time', C.byref(ms), C.byref(n))
-        return ms.value, n.value
+        return ctx().timer('mpt_noise_kernel_time')
 
     def fast_export_image(self, out, id=0):
         '''reference filmtable.py:66-79: flat RGB f32 at (y * nx + x) * 3 into the caller's buffer'''

@@ -71,8 +71,7 @@ def render_preview(aa=True):
 
 
 def get_denoised(**kw):
-    '''FilmTable().get_denoised(iterations=5, sigma_color=1.0, sigma_albedo=0.1, sigma_normal=0.3, demodulate=True): pass 0 filtered
-    on the device, guided by the passes render_preview() fills (no reference counterpart: its add-on leaves that to Blender)'''
+    '''FilmTable().get_denoised(**kw), the keywords and defaults of _lib.denoise_params: pass 0 filtered on the device, guided by the passes render_preview() fills (no reference counterpart: its add-on leaves that to Blender)'''
     return FilmTable().get_denoised(**kw)
 
 

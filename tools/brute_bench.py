@@ -17,26 +17,14 @@ import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib
+from benchlib import ROOT, median
 
 
 def setup(scene, size, lights=None, world=None):
-    from ptina_amd import scenes
-    from ptina_amd.common import reset_all
-    from ptina_amd.things import init_things, FilmTable, ModelPool, MaterialPool, ImagePool, BVHTree, Camera, LightPool, WorldLight
-    from ptina_amd.engine.path import PathEngine
+    from ptina_amd.things import LightPool, WorldLight
     from ptina_amd.engine.brute import BruteEngine
-    reset_all()
-    init_things()
-    path = PathEngine()
-    FilmTable().set_size(size, size)
-    vertices, mtlids, materials, images = scene
-    ModelPool().load(vertices, mtlids)
-    MaterialPool().load(materials)
-    ImagePool().load(images)
-    BVHTree().build()
-    Camera().set_perspective(scenes.BENCH_CAMERA)
+    path, _ = benchlib.setup(size, scene)
     if lights is not None:
         LightPool().clear()
         for l in lights:
@@ -47,10 +35,9 @@ def setup(scene, size, lights=None, world=None):
 
 
 def rate(args):
-    from ptina_amd import scenes
     from ptina_amd.common import ctx
     from ptina_amd.things import FilmTable
-    path, brute = setup(scenes.get_scene(args.scene), args.size)
+    path, brute = setup(args.scene, args.size)
     samples = args.size * args.size * args.frames
     brute.render(args.frames)
     FilmTable().get_raw()
@@ -75,8 +62,8 @@ def rate(args):
         pwall = time.perf_counter() - t0
         pms, _ = ctx().kernel_time()
         pruns.append((pms, pwall))
-    ms = sorted(r[0] for r in runs)[len(runs) // 2]
-    pms = sorted(r[0] for r in pruns)[len(pruns) // 2]
+    ms = median([r[0] for r in runs])
+    pms = median([r[0] for r in pruns])
     print(json.dumps({
         'metric': 'brute_samples_per_s', 'scene': args.scene, 'size': args.size, 'frames': args.frames, 'launches': runs[0][2],
         'brute_kernel_ms': [round(r[0], 3) for r in runs], 'brute_Msamples_per_s': round(samples / (ms / 1e3) / 1e6, 1),

@@ -18,37 +18,11 @@ in its place.
 '''
 import argparse
 import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from benchlib import setup, median
 
 HBM_SPEC, HBM_COPY = 8.0e12, 6.29e12
-
-
-def setup(size):
-    from ptina_amd import scenes
-    from ptina_amd.common import reset_all
-    from ptina_amd.things import init_things, FilmTable, ModelPool, MaterialPool, ImagePool, BVHTree, Camera
-    from ptina_amd.engine.path import PathEngine
-    from ptina_amd.engine.preview import PreviewEngine
-    reset_all()
-    init_things(max_filmsize=max(size * size, 2**21))
-    path = PathEngine()
-    FilmTable().set_size(size, size)
-    vertices, mtlids, materials, images = scenes.get_scene('s978')
-    ModelPool().load(vertices, mtlids)
-    MaterialPool().load(materials)
-    ImagePool().load(images)
-    BVHTree().build()
-    Camera().set_perspective(scenes.BENCH_CAMERA)
-    return path, PreviewEngine(), FilmTable()
-
-
-def median(v):
-    return sorted(v)[len(v) // 2]
 
 
 def call_ms(film, repeat, **kw):
@@ -66,7 +40,7 @@ def call_ms(film, repeat, **kw):
 
 def kernels(size, repeat):
     from ptina_amd.common import ctx
-    path, preview, film = setup(size)
+    path, preview, film = setup(size, preview=True)
     path.render(4)
     preview.render(2)
     film.get_image()
@@ -94,7 +68,7 @@ def kernels(size, repeat):
 
 
 def headline(steps):
-    path, preview, film = setup(512)
+    path, preview, film = setup(512, preview=True)
     preview.render(2)
     out = {'metric': 'headline_step_ms', 'scene': 's978', 'size': 512, 'spp': 32, 'steps': steps}
     for name, read in (('get_image', film.get_image), ('get_denoised', film.get_denoised), ('get_image_again', film.get_image)):

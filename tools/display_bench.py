@@ -12,37 +12,10 @@ calls after two warm-up calls and, for get_display, the HIP-event time of its ke
 '''
 import argparse
 import json
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def setup(size):
-    from ptina_amd import scenes
-    from ptina_amd.common import reset_all
-    from ptina_amd.things import init_things, FilmTable, ModelPool, MaterialPool, ImagePool, BVHTree, Camera
-    from ptina_amd.engine.path import PathEngine
-    from ptina_amd.engine.preview import PreviewEngine
-    reset_all()
-    init_things(max_filmsize=max(size * size, 2**21))
-    path = PathEngine()
-    FilmTable().set_size(size, size)
-    vertices, mtlids, materials, images = scenes.get_scene('s978')
-    ModelPool().load(vertices, mtlids)
-    MaterialPool().load(materials)
-    ImagePool().load(images)
-    BVHTree().build()
-    Camera().set_perspective(scenes.BENCH_CAMERA)
-    return path, PreviewEngine(), FilmTable()
-
-
-def median(v):
-    return sorted(v)[len(v) // 2]
+from benchlib import setup, median, wall_ms
 
 
 def numpy_display(img):
@@ -51,19 +24,8 @@ def numpy_display(img):
     return (np.swapaxes(a, 0, 1)[::-1] * 255).astype(np.uint8)
 
 
-def wall_ms(call, repeat):
-    for _ in range(2):
-        call()
-    ms = []
-    for _ in range(repeat):
-        t0 = time.perf_counter()
-        call()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return round(median(ms), 4), round(min(ms), 4)
-
-
 def bench(size, repeat):
-    path, preview, film = setup(size)
+    path, preview, film = setup(size, preview=True)
     path.render(4)
     preview.render(2)
     film.get_image()
@@ -78,12 +40,8 @@ def bench(size, repeat):
     }
     for name, kw in variants.items():
         kern = []
-
-        def call():
-            film.get_display(**kw)
-            kern.append(film.display_kernel_time()[0])
         film.display_kernel_time()
-        w = wall_ms(call, repeat)
+        w = wall_ms(lambda: film.get_display(**kw), repeat, after=lambda: kern.append(film.display_kernel_time()[0]))
         out['get_display ' + name] = list(w) + [round(median(kern[2:]), 4)]
     # the same run's get_image once more, behind everything: drift of the yardstick itself
     out['get_image_again'] = list(wall_ms(lambda: film.get_image(0), repeat))

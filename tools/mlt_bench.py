@@ -8,12 +8,9 @@ splat passes, and the PathEngine's samples/s on the same scene in the same proce
 '''
 import argparse
 import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from benchlib import setup
 
 
 def main():
@@ -26,30 +23,14 @@ def main():
     ap.add_argument('--scene', default='s978')
     args = ap.parse_args()
 
-    import ctypes as C
-    from ptina_amd import scenes
+    eng, _ = setup(args.size, args.scene)
     from ptina_amd.common import ctx
     from ptina_amd.things import FilmTable
-    from ptina_amd.things import init_things, ModelPool, MaterialPool, ImagePool, BVHTree, Camera
-    from ptina_amd.engine.path import PathEngine
     from ptina_amd.engine.mltpath import MLTPathEngine
-
-    # the scene set up as exams/benchmark_amd.py does (production build, the library's default mode)
-    init_things()
-    eng = PathEngine()
-    FilmTable().set_size(args.size, args.size)
-    vertices, mtlids, materials, images = scenes.get_scene(args.scene)
-    ModelPool().load(vertices, mtlids)
-    MaterialPool().load(materials)
-    ImagePool().load(images)
-    BVHTree().build()
-    Camera().set_perspective(scenes.BENCH_CAMERA)
     mlt = MLTPathEngine(nchains=args.nchains)
 
     def mlt_times():
-        a, b, n = C.c_double(0), C.c_double(0), C.c_int(0)
-        ctx().call('mpt_mlt_kernel_time', C.byref(a), C.byref(b), C.byref(n))
-        return a.value, b.value, n.value
+        return ctx().timer('mpt_mlt_kernel_time', segments=2)
 
     mlt.render(args.warmup)
     FilmTable().get_raw()

@@ -15,47 +15,10 @@ import argparse
 import json
 import os
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from benchlib import ROOT, setup, median, wall_ms
+
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
-
-
-def setup(size):
-    from ptina_amd import scenes
-    from ptina_amd.common import reset_all
-    from ptina_amd.things import init_things, FilmTable, ModelPool, MaterialPool, ImagePool, BVHTree, Camera
-    from ptina_amd.engine.path import PathEngine
-    reset_all()
-    init_things(max_filmsize=max(size * size, 2**21))
-    path = PathEngine()
-    FilmTable().set_size(size, size)
-    vertices, mtlids, materials, images = scenes.get_scene('s978')
-    ModelPool().load(vertices, mtlids)
-    MaterialPool().load(materials)
-    ImagePool().load(images)
-    BVHTree().build()
-    Camera().set_perspective(scenes.BENCH_CAMERA)
-    return path, FilmTable()
-
-
-def median(v):
-    return sorted(v)[len(v) // 2]
-
-
-def wall_ms(call, repeat, prepare=None, after=None):
-    ms = []
-    for i in range(repeat + 2):                 # two warm-up calls
-        if prepare:
-            prepare()
-        t0 = time.perf_counter()
-        call()
-        ms.append((time.perf_counter() - t0) * 1e3)
-        if after:
-            after()
-    ms = ms[2:]
-    return round(median(ms), 4), round(min(ms), 4)
 
 
 def bench(size, repeat):
