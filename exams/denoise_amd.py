@@ -4,9 +4,10 @@ A low-sample render and its denoised image: the benchmark scene (exams/benchmark
 of the PreviewEngine (albedo into film pass 1, shading normal into pass 2: the reference's denoiser AOVs, engine/preview.py),
 then FilmTable.get_image() and FilmTable.get_denoised() -- the edge-avoiding A-Trous filter run on the device, guided by those two
 passes.  The reference leaves this step to Blender's compositor; here it is one call.  Writes noisy.npy and denoised.npy
-([size][size][4] f32).
+([size][size][4] f32).  --variance SIGMA (try 4) also guides the filter by every pixel's own noise: the film is marked after half of
+the samples, and get_denoised(variance=SIGMA) takes its colour tolerance from the two halves' difference.
 
-    python exams/denoise_amd.py [--scene s978|s34] [--size 512] [--spp 4] [--preview 2] [--iterations 5] [--out DIR]
+    python exams/denoise_amd.py [--scene s978|s34] [--size 512] [--spp 4] [--preview 2] [--iterations 5] [--variance SIGMA] [--out DIR]
 '''
 import argparse
 import os
@@ -25,6 +26,7 @@ ap.add_argument('--size', type=int, default=512)
 ap.add_argument('--spp', type=int, default=4)
 ap.add_argument('--preview', type=int, default=2)
 ap.add_argument('--iterations', type=int, default=5)
+ap.add_argument('--variance', type=float, default=None)
 ap.add_argument('--out', default='.')
 args = ap.parse_args()
 
@@ -43,10 +45,12 @@ Camera().set_perspective(scenes.BENCH_CAMERA)
 
 for i in range(args.spp):
     PathEngine().render()
+    if args.variance and i + 1 == max(args.spp // 2, 1):
+        FilmTable().mark()
 for i in range(args.preview):
     PreviewEngine().render()
 noisy = FilmTable().get_image()
-denoised = FilmTable().get_denoised(iterations=args.iterations)
+denoised = FilmTable().get_denoised(iterations=args.iterations, variance=args.variance)
 
 os.makedirs(args.out, exist_ok=True)
 np.save(os.path.join(args.out, 'noisy.npy'), noisy)

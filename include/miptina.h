@@ -310,6 +310,38 @@ typedef struct {
 int mpt_get_denoised(mpt_ctx *ctx, const mpt_denoise_params *params /* NULL = the defaults above */, float *out /* [nx][ny][4] */);
 /* HIP-event time (ms) of the filter's kernels (prologue to epilogue) of the mpt_get_denoised calls since the last call, and their count */
 int mpt_denoise_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
+/* Variance guidance, an opt-in mode of the denoised read-backs (the spatial half of spatiotemporal variance-guided filtering,
+ * Schied et al. 2017): the colour tolerance of every pixel follows that pixel's own standard error, which the film's mark
+ * (mpt_film_mark, below) measures, instead of one global sigma_color -- converged detail the guides cannot see (shadow edges,
+ * caustics, reflections) is kept, and noise is still filtered where there is noise.  With M the mark, F0 and m as above, all
+ * arithmetic f32 without contraction, IEEE division, expf:
+ *   nA = M.w;  n = F0.w;  nB = n - nA;  has(p) = valid(p) and nA > 0 and nB > 0
+ *   d = (F0.rgb / n - M.rgb / nA) / m  per channel
+ *   v_0(p) = fminf(fmaxf(((d.r d.r + d.g d.g) + d.b d.b) (nA / nB), 0), 3.0e38f) if has(p), else 0
+ *            (mpt_get_noise's standard error of the mean, squared, in the filter's demodulated space; a valid pixel without two
+ *             groups carries no evidence of noise)
+ *   for i = 0 .. iterations-1, s = 2^i, every valid p:
+ *       g(p) = (sum b[dx] b[dy] v_i(q)) / (sum b[dx] b[dy])  over the 3x3 taps q = p + (dx, dy) at stride 1 inside the film and
+ *              valid, b = [1/4, 1/2, 1/4], dx outer, dy inner, both ascending
+ *       kc(p) = 1 / (sigma_variance^2 g(p) + 1e-10f)         (sigma_variance^2 = sigma_variance sigma_variance, rounded once)
+ *       w(q) as above with |e_i(p)-e_i(q)|^2 kc(p) for the colour term; the albedo and normal terms and the order of the sums unchanged
+ *       e_{i+1}(p) = sum w e_i(q) / sum w
+ *       v_{i+1}(p) = (sum (w w) v_i(q)) / ((sum w) (sum w))  (0 where p is not valid)
+ *   and the epilogue as above.  sigma_color is validated and otherwise unused: the variance narrows by itself as it is filtered.
+ * mpt_denoise_set_variance: context state like mpt_mlt_set_param's; 0 (the default) = off, the filter above bit for bit; a positive
+ *   finite value = on (4 is a good start); anything else fails and changes nothing.  While on, mpt_get_denoised and mpt_get_display
+ *   with the denoised source run the guided filter and fail without a mark -- checked before anything else, also for iterations = 0,
+ *   which otherwise stays mpt_get_image(ctx, 0, out).  The two variance planes, 4 bytes per pixel each, are allocated at the first
+ *   guided read-back and released with the film.  No film pass and not the mark is written.
+ * mpt_denoise_eval: test door in the mpt_noise_eval idiom: the SAME launches on caller-supplied accumulators f0, f1, f2 and mark
+ *   [nx*ny][4], any nx, ny >= 1 with nx*ny <= max_filmsize, in buffers of its own; touches no film pass, not the context's mark and
+ *   not the context's variance setting.  sigma_variance == 0 is the fixed filter; mark must be NULL then and given otherwise.
+ *   var_out [nx][ny] (NULL, or guided only) = v_final, 0 where not valid; v_0 for iterations = 0. */
+int mpt_denoise_set_variance(mpt_ctx *ctx, float sigma_variance);
+int mpt_denoise_get_variance(mpt_ctx *ctx, float *out);
+int mpt_denoise_eval(mpt_ctx *ctx, const mpt_denoise_params *params, float sigma_variance, const float *f0, const float *f1,
+                     const float *f2, const float *mark /* NULL iff sigma_variance == 0 */, int nx, int ny,
+                     float *out /* [nx][ny][4] */, float *var_out /* [nx][ny] or NULL */);
 
 /* The film as a screen, a PNG or a viewport wants it: metered, tone-mapped, transfer-encoded, dithered and quantised to 8-bit RGBA on
  * the device, a quarter of mpt_get_image's bytes (no reference counterpart: its scripts end in ti.imshow of linear radiance; the

@@ -142,6 +142,9 @@ SIGNATURES = {
     'mpt_resolve': (_i, [_vp, _i]),
     'mpt_get_denoised': (_i, [_vp, C.POINTER(DenoiseParams), _fp]),
     'mpt_denoise_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_denoise_set_variance': (_i, [_vp, C.c_float]),
+    'mpt_denoise_get_variance': (_i, [_vp, _fp]),
+    'mpt_denoise_eval': (_i, [_vp, C.POINTER(DenoiseParams), C.c_float, _fp, _fp, _fp, _fp, _i, _i, _fp, _fp]),
     'mpt_get_display': (_i, [_vp, C.POINTER(DisplayParams), C.POINTER(DenoiseParams), C.POINTER(C.c_uint8), _fp]),
     'mpt_display_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
     'mpt_display_eval': (_i, [_vp, C.POINTER(DisplayParams), _fp, _i, _i, C.POINTER(C.c_uint8), _fp]),
@@ -351,6 +354,28 @@ class Context:
         used = C.c_float(0)
         self.call('mpt_display_eval', C.byref(p), fptr(a), int(nx), int(ny), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(used))
         return out, np.float32(used.value)
+
+    def set_denoise_variance(self, variance):
+        '''sigma_variance of the denoised read-backs that follow (mpt_denoise_set_variance): None or 0 = the fixed filter.
+        FilmTable.get_denoised and get_display(denoised=True) set it before every call, so their callers never see the state'''
+        self.call('mpt_denoise_set_variance', 0.0 if variance is None else float(variance))
+
+    def get_denoise_variance(self):
+        v = C.c_float(0)
+        self.call('mpt_denoise_get_variance', C.byref(v))
+        return v.value
+
+    def denoise_eval(self, f0, f1, f2, mark, nx, ny, variance=None, var=False, **denoise_kw):
+        '''test door (mpt_denoise_eval): get_denoised's launches on the accumulators f0, f1, f2 and -- guided, variance > 0 --
+        mark [nx*ny][4]; the keywords of denoise_params.  Returns the image [nx, ny, 4], or with var=True (image, v_final [nx, ny])'''
+        acc = [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, 4)) for a in (f0, f1, f2, mark)]
+        if any(a is not None and a.shape[0] != int(nx) * int(ny) for a in acc):
+            raise ValueError('the accumulators do not hold the %d pixels of the film %dx%d' % (int(nx) * int(ny), nx, ny))
+        out = np.empty((nx, ny, 4), np.float32)
+        v = np.empty((nx, ny), np.float32) if var else None
+        self.call('mpt_denoise_eval', C.byref(denoise_params(who='denoise_eval', **denoise_kw)), 0.0 if variance is None else float(variance),
+                  *(None if a is None else fptr(a) for a in acc), int(nx), int(ny), fptr(out), None if v is None else fptr(v))
+        return (out, v) if var else out
 
     def noise_eval(self, film_raw, mark_raw, nx, ny, threshold, map=True, remark=True):
         '''test door (mpt_noise_eval): get_noise's kernels on the accumulators film_raw and mark_raw [nx*ny][4]; returns

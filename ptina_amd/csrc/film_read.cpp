@@ -1,6 +1,6 @@
 // film_read.cpp -- the film's read-backs behind the C ABI of include/miptina.h: clear, resolve, the image and its hint, export, the
 // raw passes; the denoised image (denoise.hip), the 8-bit display image (display.hip), the mark and the noise estimate (noise.hip),
-// the two test doors and the three features' kernel timers.  Everything here runs on the main stream behind what is enqueued: of the
+// the three test doors and the three features' kernel timers.  Everything here runs on the main stream behind what is enqueued: of the
 // launch ring (miptina.cpp) it takes mpt_flush, read_back, caller_alias and timer_readout, and it knows the early image only in
 // mpt_hint_image and mpt_get_image.
 
@@ -40,15 +40,17 @@ static int door_film(const mpt_ctx *c, const char *who, int nx, int ny) {
 }
 
 // ... and its accumulators on the device: room for npix of them and for what the kernels write (`bufs`), then the caller's arrays
-// (acc1 may be null) into c->door.acc
+// (acc1 may be null) into c->door.acc, and `more` of them into buffers of `bufs`
 template <class Bufs>
-static int door_stage(mpt_ctx *c, size_t npix, Bufs &bufs, const float *acc0, const float *acc1) {
+static int door_stage(mpt_ctx *c, size_t npix, Bufs &bufs, const float *acc0, const float *acc1,
+                      std::initializer_list<std::pair<DevBuf<MptVec4> *, const float *>> more = {}) {
     if (npix > c->door.cap || npix > bufs.cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (c->door.reserve(npix) || bufs.reserve(npix)) return 1;
     }
     HIP_TRY(hipMemcpyAsync(c->door.acc[0], acc0, npix * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
     if (acc1) HIP_TRY(hipMemcpyAsync(c->door.acc[1], acc1, npix * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
+    for (const auto &m : more) HIP_TRY(hipMemcpyAsync(m.first->p, m.second, npix * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));                      // (the arrays are pageable: the copies are staged, the caller's arrays are free again)
     return 0;
 }
@@ -153,26 +155,70 @@ static int denoise_params(const mpt_denoise_params *params, mpt_denoise_params &
            finite_arg("denoise", "sigma_normal", p.sigma_normal);
 }
 
-// the filter's launches on the main stream (mpt_get_denoised and mpt_get_display's denoised source); *img = the working buffer that
-// holds the image behind them
-static int denoise_launches(mpt_ctx *c, const mpt_denoise_params &p, const MptVec4 **img) {
-    const size_t npix = (size_t)c->nx * c->ny;
+// the buffers the filter's launches work in: the film owner's (the read-backs) or the door's
+struct DnWork { MptVec4 *e[2], *a, *n; float *v[2]; };
+
+// The filter's launches on the main stream for the accumulators f[0..2] of an nx x ny film; sigma_variance > 0: guided by the
+// variance from `mark`.  *img = the working buffer that holds the image behind them; var (the door, guided): *var = the one that
+// holds v_final
+static int denoise_launches(mpt_ctx *c, const mpt_denoise_params &p, float sigma_variance, const MptVec4 *const f[3], const MptVec4 *mark,
+                            int nx, int ny, const DnWork &w, const MptVec4 **img, const float **var = nullptr) {
+    const size_t npix = (size_t)nx * ny;
+    const bool guided = sigma_variance > 0.0f;
+    const int demodulate = p.demodulate ? 1 : 0;
     if (p.iterations == 0) {
         // nothing to filter: the resolve pass itself, so that the image is mpt_get_image(0)'s bit for bit
-        HIP_TRY(mpt_launch_resolve(c->fb.film[0], c->fb.dn_e[0], npix, c->stream));
-        *img = c->fb.dn_e[0];
+        HIP_TRY(mpt_launch_resolve(f[0], w.e[0], npix, c->stream));
+        *img = w.e[0];
+        if (var) {                                                         // v_final is v_0: the prologue beside it
+            HIP_TRY(mpt_launch_denoise_prologue(f[0], f[1], f[2], w.e[1], w.a, w.n, npix, demodulate, mark, w.v[0], c->stream));
+            *var = w.v[0];
+        }
         return 0;
     }
-    HIP_TRY(mpt_launch_denoise_prologue(c->fb.film[0], c->fb.film[1], c->fb.film[2], c->fb.dn_e[0], c->fb.dn_a, c->fb.dn_n, npix, p.demodulate ? 1 : 0, c->stream));
+    HIP_TRY(mpt_launch_denoise_prologue(f[0], f[1], f[2], w.e[0], w.a, w.n, npix, demodulate, guided ? mark : nullptr,
+                                        guided ? w.v[0] : nullptr, c->stream));
     const float ka = 1.0f / (p.sigma_albedo * p.sigma_albedo), kn = 1.0f / (p.sigma_normal * p.sigma_normal);
     for (int i = 0; i < p.iterations; i++) {
         const float sc = p.sigma_color * std::ldexp(1.0f, -i);             // the colour edge-stopping narrows as the stencil widens
-        HIP_TRY(mpt_launch_denoise_atrous(c->fb.dn_e[i & 1], c->fb.dn_e[(i + 1) & 1], c->fb.dn_a, c->fb.dn_n, c->nx, c->ny, 1 << i,
-                                          1.0f / (sc * sc), ka, kn, c->opt.denoise_lds, c->stream));
+        // (guided: every pixel's own tolerance, from sigma_variance^2 and the variance around it; the variance narrows by itself)
+        HIP_TRY(mpt_launch_denoise_atrous(w.e[i & 1], w.e[(i + 1) & 1], w.a, w.n, nx, ny, 1 << i, guided ? sigma_variance * sigma_variance : 1.0f / (sc * sc),
+                                          ka, kn, c->opt.denoise_lds, guided ? w.v[i & 1] : nullptr, guided ? w.v[(i + 1) & 1] : nullptr, c->stream));
     }
     const int last = p.iterations & 1;
-    HIP_TRY(mpt_launch_denoise_epilogue(c->fb.dn_e[last], c->fb.dn_a, c->fb.dn_e[last ^ 1], npix, p.demodulate ? 1 : 0, c->stream));
-    *img = c->fb.dn_e[last ^ 1];
+    HIP_TRY(mpt_launch_denoise_epilogue(w.e[last], w.a, w.e[last ^ 1], npix, demodulate, c->stream));
+    *img = w.e[last ^ 1];
+    if (var) *var = w.v[last];
+    return 0;
+}
+
+// mpt_get_denoised and mpt_get_display's denoised source.  In front of everything else: the guided filter needs a mark ...
+static int denoise_mark(const mpt_ctx *c, const char *who) {
+    if (c->denoise_variance > 0.0f && !c->noise.marked)
+        return fail("%s: no mark: call mpt_film_mark() first (mpt_clear and mpt_set_size drop the mark)", who);
+    return 0;
+}
+
+// ... and, once the film is ready and before the timed span, its two variance planes
+static int denoise_planes(mpt_ctx *c) { return c->denoise_variance > 0.0f ? c->fb.reserve_variance() : 0; }
+
+static int film_denoise(mpt_ctx *c, const mpt_denoise_params &p, const MptVec4 **img) {
+    const MptVec4 *const f[3] = { c->fb.film[0], c->fb.film[1], c->fb.film[2] };
+    const DnWork w = { { c->fb.dn_e[0], c->fb.dn_e[1] }, c->fb.dn_a, c->fb.dn_n, { c->fb.dn_v[0], c->fb.dn_v[1] } };
+    return denoise_launches(c, p, c->denoise_variance, f, c->fb.mark, c->nx, c->ny, w, img);
+}
+
+extern "C" int mpt_denoise_set_variance(mpt_ctx *c, float sigma_variance) {
+    if (use_ro(c)) return 1;                   // (no render launch reads it)
+    if (finite_arg("mpt_denoise_set_variance", "sigma_variance", sigma_variance, true, " (0 = off)")) return 1;
+    c->denoise_variance = sigma_variance;
+    return 0;
+}
+
+extern "C" int mpt_denoise_get_variance(mpt_ctx *c, float *out) {
+    if (use_ro(c)) return 1;
+    if (!out) return fail("mpt_denoise_get_variance: null output");
+    *out = c->denoise_variance;
     return 0;
 }
 
@@ -180,15 +226,41 @@ extern "C" int mpt_get_denoised(mpt_ctx *c, const mpt_denoise_params *params, fl
     if (use_ro(c)) return 1;
     mpt_denoise_params p;
     if (!out) return fail("mpt_get_denoised: null output");
-    if (denoise_params(params, p)) return 1;
+    if (denoise_params(params, p) || denoise_mark(c, "mpt_get_denoised")) return 1;
     return film_read(c, 0, [&] {
         const MptVec4 *img = nullptr;
+        if (denoise_planes(c)) return 1;
         MptTimedSpan span(c->denoise_timer, c->stream);
         HIP_TRY(span.begun);
-        if (denoise_launches(c, p, &img)) return 1;
+        if (film_denoise(c, p, &img)) return 1;
         HIP_TRY(span.end());
         return read_back(c, out, img, (size_t)c->nx * c->ny * sizeof(MptVec4));
     });
+}
+
+// test door: the same launches on the caller's accumulators, in buffers of its own (no film pass, not the context's mark, not its
+// variance setting and no film-owner buffer is touched)
+extern "C" int mpt_denoise_eval(mpt_ctx *c, const mpt_denoise_params *params, float sigma_variance, const float *f0, const float *f1,
+                                const float *f2, const float *mark, int nx, int ny, float *out, float *var_out) {
+    if (use_ro(c)) return 1;
+    mpt_denoise_params p;
+    if (!out || !f0 || !f1 || !f2) return fail("mpt_denoise_eval: null %s", out ? "input" : "output");
+    if (denoise_params(params, p) || finite_arg("mpt_denoise_eval", "sigma_variance", sigma_variance, true, " (0 = off)")) return 1;
+    const bool guided = sigma_variance > 0.0f;
+    if (guided != (mark != nullptr)) return fail("mpt_denoise_eval: the mark must be given when sigma_variance > 0 and only then");
+    if (var_out && !guided) return fail("mpt_denoise_eval: var_out needs sigma_variance > 0");
+    if (door_film(c, "mpt_denoise_eval", nx, ny)) return 1;
+    const size_t npix = (size_t)nx * ny;
+    MptDenoiseBufs &b = c->denoise_bufs;
+    if (door_stage(c, npix, b, f0, mark, { { &b.f1, f1 }, { &b.f2, f2 } })) return 1;
+    const MptVec4 *const f[3] = { c->door.acc[0], b.f1, b.f2 };
+    const DnWork w = { { b.e[0], b.e[1] }, b.a, b.n, { b.v[0], b.v[1] } };
+    const MptVec4 *img = nullptr;
+    const float *var = nullptr;
+    if (denoise_launches(c, p, sigma_variance, f, c->door.acc[1], nx, ny, w, &img, var_out ? &var : nullptr)) return 1;
+    if (read_back(c, out, img, npix * sizeof(MptVec4))) return 1;
+    if (var_out && read_back(c, var_out, var, npix * sizeof(float))) return 1;
+    return 0;
 }
 
 extern "C" int mpt_denoise_kernel_time(mpt_ctx *c, double *ms, int *launches) {
@@ -240,14 +312,15 @@ extern "C" int mpt_get_display(mpt_ctx *c, const mpt_display_params *params, con
     if (display_params(params, p, a)) return 1;
     const bool denoised = p.source == MPT_DISPLAY_DENOISED;
     if (!denoised && (p.source < 0 || p.source >= 3)) return fail("display: film pass %d out of range", p.source);
-    if (denoised && denoise_params(denoise, dp)) return 1;
+    if (denoised && (denoise_params(denoise, dp) || denoise_mark(c, "mpt_get_display"))) return 1;
     return film_read(c, denoised ? 0 : p.source, [&] {
         const size_t npix = (size_t)c->nx * c->ny;
+        if (denoised && denoise_planes(c)) return 1;
         void *const direct = caller_alias(c, out, npix * 4);
         const MptVec4 *src = denoised ? nullptr : c->fb.film[p.source].p;
         MptTimedSpan span(c->display.timer, c->stream);
         HIP_TRY(span.begun);
-        if (denoised && denoise_launches(c, dp, &src)) return 1;       // the float image stays on the device
+        if (denoised && film_denoise(c, dp, &src)) return 1;           // the float image stays on the device
         if (display_launches(c, p, a, src, c->nx, c->ny, c->fb.disp, direct ? (uint32_t *)direct : c->fb.disp.rgba8.p)) return 1;
         HIP_TRY(span.end());
         return display_finish(c, p, direct != nullptr, out, c->fb.disp.rgba8, npix, exposure_used);

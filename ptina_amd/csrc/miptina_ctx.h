@@ -55,10 +55,11 @@ MPT_KERNEL_API hipError_t mpt_launch_copy_pieces(const MptVec4 *src, MptVec4 *ds
                                              long long max_count, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_export(const MptVec4 *film, float *out, int nx, int ny, hipStream_t);
 // denoise.hip: the A-Trous filter of pass 0 guided by passes 1 and 2 (mpt_get_denoised)
+// (guided by variance: mark and v, v_in and v_out given, kc = sigma_variance^2; the fixed filter: all four null)
 MPT_KERNEL_API hipError_t mpt_launch_denoise_prologue(const MptVec4 *f0, const MptVec4 *f1, const MptVec4 *f2, MptVec4 *e, MptVec4 *a,
-                                                      MptVec4 *n, size_t npix, int demodulate, hipStream_t);
+                                                      MptVec4 *n, size_t npix, int demodulate, const MptVec4 *mark, float *v, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_denoise_atrous(const MptVec4 *e_in, MptVec4 *e_out, const MptVec4 *a, const MptVec4 *n, int nx, int ny,
-                                                    int s, float kc, float ka, float kn, int use_lds, hipStream_t);
+                                                    int s, float kc, float ka, float kn, int use_lds, const float *v_in, float *v_out, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_denoise_epilogue(const MptVec4 *e, const MptVec4 *a, MptVec4 *out, size_t npix, int demodulate, hipStream_t);
 // display.hip: metering and the conversion to 8-bit RGBA (mpt_get_display); part holds 2 * mpt_display_parts(npix) doubles
 MPT_KERNEL_API size_t mpt_display_parts(size_t npix);
@@ -206,8 +207,25 @@ struct MPT_INTERNAL MptNoiseBufs {         // what mpt_get_noise's kernels write
     }
 };
 
+struct MPT_INTERNAL MptDenoiseBufs {       // mpt_denoise_eval: the caller's guide passes and what the filter's kernels write, for a film of up to `cap` pixels
+    DevBuf<MptVec4> f1, f2;              // the accumulators of passes 1 and 2 (pass 0 and the mark go through MptDoorInput)
+    DevBuf<MptVec4> e[2], a, n;          // as MptFilmBufs' dn_e, dn_a, dn_n
+    DevBuf<float> v[2];                  // ... and dn_v
+    size_t cap = 0;
+    void release() { for (DevBuf<MptVec4> *b : { &f1, &f2, &e[0], &e[1], &a, &n }) b->release(); v[0].release(); v[1].release(); cap = 0; }
+    int reserve(size_t npix) {
+        if (npix <= cap) return 0;
+        release();
+        for (DevBuf<MptVec4> *b : { &f1, &f2, &e[0], &e[1], &a, &n })
+            if (b->reserve(npix)) return 1;
+        if (v[0].reserve(npix) || v[1].reserve(npix)) return 1;
+        cap = npix;
+        return 0;
+    }
+};
+
 struct MPT_INTERNAL MptDoorInput {         // the test doors' input: the caller's accumulators for a film of up to `cap` pixels
-    DevBuf<MptVec4> acc[2];              // mpt_display_eval uses the first; mpt_noise_eval both: the film, and the mark it may rewrite
+    DevBuf<MptVec4> acc[2];              // mpt_display_eval uses the first; mpt_noise_eval and mpt_denoise_eval both: the film, and the mark (which mpt_noise_eval may rewrite)
     size_t cap = 0;
     int reserve(size_t npix) {
         if (npix <= cap) return 0;
@@ -230,8 +248,12 @@ struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set 
     // mpt_film_mark's copy of pass 0 and what mpt_get_noise's kernels write: made by the first mark (reserve_mark), for `cap`
     // pixels, and released with the rest
     DevBuf<MptVec4> mark; MptNoiseBufs noise;
+    // the variance-guided filter's plane v, nx*ny floats in two copies like dn_e: made by the first guided read-back
+    // (reserve_variance), for `cap` pixels, and released with the rest
+    DevBuf<float> dn_v[2];
     size_t cap = 0;
     int reserve_mark() { return mark.reserve(cap) || noise.reserve(cap); }
+    int reserve_variance() { return dn_v[0].reserve(cap) || dn_v[1].reserve(cap); }
     int reserve(size_t npix, hipStream_t stream) {     // the passes come back zeroed on `stream`
         if (npix <= cap) return 0;
         cap = 0;
@@ -240,6 +262,7 @@ struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set 
         for (DevBuf<MptVec4> *b : { &dn_e[0], &dn_e[1], &dn_a, &dn_n }) b->release();
         disp.release();
         mark.release(); noise.release();
+        dn_v[0].release(); dn_v[1].release();
         for (auto &b : film) {
             if (b.reserve(npix)) return 1;
             HIP_TRY(hipMemsetAsync(b, 0, npix * sizeof(MptVec4), stream));
@@ -526,9 +549,11 @@ struct mpt_ctx {
         MptLaunchTimer timer;                            // mpt_get_noise: {before the estimate, after the fold} per call
         explicit Noise(MptEventPool &ev) : timer(2, ev) {}
     } noise{events};
-    MptDoorInput door;                                   // mpt_display_eval, mpt_noise_eval: the caller's accumulators on the device (grown on demand)
+    MptDoorInput door;                                   // mpt_display_eval, mpt_noise_eval, mpt_denoise_eval: the caller's accumulators on the device (grown on demand)
     MptLaunchTimer render_timer{2, events};              // PathEngine launches: {kernel start, kernel end}
     MptLaunchTimer denoise_timer{2, events};             // mpt_get_denoised: {before the prologue, after the epilogue} per call
+    float denoise_variance = 0.0f;                       // mpt_denoise_set_variance: sigma_variance of the denoised read-backs (0: the fixed filter)
+    MptDenoiseBufs denoise_bufs;                         // mpt_denoise_eval: the filter's buffers for the caller's accumulators (grown on demand)
     MptLaunchTimer brute_timer{2, events};               // brute-force engine: {kernel start, kernel end} per launch
     int pending = 0;                                     // command batching: frames enqueued and not launched yet
 

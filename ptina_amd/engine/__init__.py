@@ -19,7 +19,7 @@ from collections import namedtuple as _namedtuple
 RenderUntil = _namedtuple('RenderUntil', 'spp converged history')
 
 
-def render_until(engine, noise, max_spp, min_spp=16, fraction=0.0, film=None):
+def render_until(engine, noise, max_spp, min_spp=16, fraction=0.0, film=None, keep_mark=False):
     '''render with `engine` (PathEngine, BruteEngine: one sample per pixel and frame) until the film's noise estimate passes
     (FilmTable.get_noise) or `max_spp` frames are spent, on a doubling schedule: `min_spp` frames and a mark; then, per check, as
     many frames again as the film holds -- capped so that the total never exceeds `max_spp` -- and get_noise(noise, remark=True).
@@ -29,7 +29,11 @@ def render_until(engine, noise, max_spp, min_spp=16, fraction=0.0, film=None):
     check.  The loop counts the frames itself and expects a cleared film (FilmTable.clear()): then every check but a capped last
     one compares two equal halves -- the first spp / 2 samples against the second -- for which the estimate is exactly Cycles'
     criterion and `noise` its noise threshold; a capped last check compares unequal groups by the general form (the factor k of
-    include/miptina.h).  One kernel pass and 32 bytes over PCIe per check.  `film`: the film table (default FilmTable())'''
+    include/miptina.h).  One kernel pass and 32 bytes over PCIe per check.  `film`: the film table (default FilmTable()).
+
+    keep_mark=True (here and in worker.render_until; the engines' methods keep their four arguments): the checks leave the mark alone (get_noise(noise, remark=False)) and mark() is called only when the loop goes on,
+    so at return the mark still holds the first group of the last comparison and FilmTable.get_denoised(variance=...) works at once.
+    Same film, spp and history; one device copy of pass 0 more per check that does not end the loop'''
     noise, max_spp, min_spp, fraction = float(noise), int(max_spp), int(min_spp), float(fraction)
     if min_spp < 1:
         raise ValueError('render_until: min_spp must be at least 1, got %d' % min_spp)
@@ -44,8 +48,10 @@ def render_until(engine, noise, max_spp, min_spp=16, fraction=0.0, film=None):
         frames = min(spp, max_spp - spp)
         engine.render(frames)
         spp += frames
-        stats = film.get_noise(noise, remark=True)
+        stats = film.get_noise(noise, remark=not keep_mark)
         history.append((spp, stats))
         converged = stats.above <= fraction * stats.valid
         if converged or spp >= max_spp:
             return RenderUntil(spp, converged, history)
+        if keep_mark:
+            film.mark()

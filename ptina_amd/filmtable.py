@@ -77,13 +77,16 @@ class FilmTable(metaclass=Singleton):
             raise
         return arr
 
-    def get_denoised(self, *denoise_args, **denoise_kw):
+    def get_denoised(self, *denoise_args, variance=None, **denoise_kw):
         '''pass 0 filtered on the device by the edge-avoiding A-Trous wavelet, guided by the albedo and normal passes the
         PreviewEngine renders (mpt_get_denoised, include/miptina.h): [nx, ny, 4] f32 like get_image, a fresh array.  The arguments
-        and their defaults are _lib.denoise_params': iterations, sigma_color, sigma_albedo, sigma_normal, demodulate.  No reference
-        counterpart: its add-on hands the Albedo pass to Blender's denoiser'''
+        and their defaults are _lib.denoise_params': iterations, sigma_color, sigma_albedo, sigma_normal, demodulate.
+        variance=sigma (4 is a good start) guides the colour tolerance by every pixel's own standard error instead of sigma_color:
+        it needs a mark() with samples rendered since (render_until(..., keep_mark=True) leaves one); None = the fixed filter.  No
+        reference counterpart: its add-on hands the Albedo pass to Blender's denoiser'''
         from ._lib import denoise_params
         nx, ny = self._res()
+        ctx().set_denoise_variance(variance)
         arr = host_array((nx, ny, 4))
         ctx().call('mpt_get_denoised', C.byref(denoise_params(*denoise_args, **denoise_kw)), fptr(arr))
         return arr
@@ -93,8 +96,8 @@ class FilmTable(metaclass=Singleton):
         return ctx().timer('mpt_denoise_kernel_time')
 
     def get_display(self, id=0, denoised=False, op='aces', transfer='srgb', layout='film', dither=True, exposure=None, key=0.18,
-                    white=4.0, gamma=2.2, **denoise_kw):
-        '''film pass `id` -- or, with denoised=True, pass 0 through get_denoised's filter (its keywords in denoise_kw) -- as a screen
+                    white=4.0, gamma=2.2, variance=None, **denoise_kw):
+        '''film pass `id` -- or, with denoised=True, pass 0 through get_denoised's filter (its keywords in denoise_kw, and variance) -- as a screen
         or a PNG wants it: metered (exposure=None: log-average luminance to `key`) or exposed by `exposure`, tone-mapped (op: 'linear',
         'ptina', 'reinhard', 'aces'), transfer-encoded ('srgb', or 'gamma' with `gamma`), ordered-dithered and quantised on the device
         (mpt_get_display, include/miptina.h).  A fresh page-locked uint8 array: [nx, ny, 4] for layout='film' (indexed like
@@ -108,8 +111,9 @@ class FilmTable(metaclass=Singleton):
         dn = None
         if denoised:
             dn = C.byref(denoise_params(who='get_display', **denoise_kw))
-        elif denoise_kw:
-            raise TypeError('get_display: %s only apply with denoised=True' % sorted(denoise_kw))
+            ctx().set_denoise_variance(variance)
+        elif denoise_kw or variance is not None:
+            raise TypeError('get_display: %s only apply with denoised=True' % sorted(list(denoise_kw) + ['variance'] * (variance is not None)))
         arr = host_array((ny, nx, 4) if p.layout == LAYOUTS['display'] else (nx, ny, 4), np.uint8)
         used = C.c_float(0)
         ctx().call('mpt_get_display', C.byref(p), dn, arr.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(used))

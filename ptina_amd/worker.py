@@ -71,13 +71,13 @@ def render_preview(aa=True):
 
 
 def get_denoised(**kw):
-    '''FilmTable().get_denoised(**kw), the keywords and defaults of _lib.denoise_params: pass 0 filtered on the device, guided by the passes render_preview() fills (no reference counterpart: its add-on leaves that to Blender)'''
+    '''FilmTable().get_denoised(**kw), the keywords and defaults of _lib.denoise_params and variance=None: pass 0 filtered on the device, guided by the passes render_preview() fills and, with variance=sigma, by the film's own noise since the mark (no reference counterpart: its add-on leaves that to Blender)'''
     return FilmTable().get_denoised(**kw)
 
 
 def get_display(**kw):
     '''FilmTable().get_display(id=0, denoised=False, op='aces', transfer='srgb', layout='film', dither=True, exposure=None, key=0.18,
-    white=4.0, gamma=2.2, **denoise_kw): the film tone-mapped and quantised to 8-bit RGBA on the device (no reference counterpart)'''
+    white=4.0, gamma=2.2, variance=None, **denoise_kw): the film tone-mapped and quantised to 8-bit RGBA on the device (no reference counterpart)'''
     return FilmTable().get_display(**kw)
 
 
@@ -88,9 +88,11 @@ def get_noise(threshold, **kw):
 
 
 def render_until(noise, max_spp, **kw):
-    '''DefaultEngine().render_until(noise, max_spp, min_spp=16, fraction=0.0): render on a doubling schedule until the noise
-    estimate passes or max_spp frames are spent; expects a cleared film (no reference counterpart: its loop counts samples)'''
-    return DefaultEngine().render_until(noise, max_spp, **kw)
+    '''engine.render_until(DefaultEngine(), noise, max_spp, min_spp=16, fraction=0.0, keep_mark=False) -- DefaultEngine().render_until's
+    loop: render on a doubling schedule until the noise estimate passes or max_spp frames are spent; expects a cleared film;
+    keep_mark=True leaves the mark of the last check for get_denoised(variance=...) (no reference counterpart: its loop counts samples)'''
+    from .engine import render_until as loop
+    return loop(DefaultEngine(), noise, max_spp, **kw)
 
 
 def get_size():

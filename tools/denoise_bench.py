@@ -12,9 +12,10 @@ after two warm-up calls.  Per film size, one JSON line with
     HBM peak (8.0 TB/s by the data sheet; 6.29 TB/s is what a float4 copy reaches).
 
 and then the headline step -- render(32) + read-back at 512x512 -- as wall time per step with get_image and with get_denoised
-in its place.
+in its place.  --variance SIGMA times the variance-guided mode instead (get_denoised(variance=SIGMA)): the
+same film -- the mark is taken after 2 of the 4 frames either way -- and 72 bytes per pixel and iteration (v read and written too).
 
-    python tools/denoise_bench.py [--repeat 20] [--sizes 512 2048] [--steps 50]
+    python tools/denoise_bench.py [--repeat 20] [--sizes 512 2048] [--steps 50] [--variance 4]
 '''
 import argparse
 import json
@@ -38,16 +39,19 @@ def call_ms(film, repeat, **kw):
     return median(ms)
 
 
-def kernels(size, repeat):
+def kernels(size, repeat, variance=None):
     from ptina_amd.common import ctx
     path, preview, film = setup(size, preview=True)
-    path.render(4)
+    path.render(2)
+    film.mark()
+    path.render(2)
     preview.render(2)
     film.get_image()
-    out = {'metric': 'denoise_kernel_ms', 'scene': 's978', 'size': size, 'frames': 4, 'preview_frames': 2, 'repeat': repeat}
+    out = {'metric': 'denoise_kernel_ms', 'scene': 's978', 'size': size, 'frames': 4, 'preview_frames': 2, 'repeat': repeat,
+           'variance': variance}
     for lds in (1, 0):
         ctx().set_option('denoise_lds', lds)
-        out['ms_per_call_lds%d' % lds] = [round(call_ms(film, repeat, iterations=k), 4) for k in range(6)]
+        out['ms_per_call_lds%d' % lds] = [round(call_ms(film, repeat, iterations=k, variance=variance), 4) for k in range(6)]
     ctx().set_option('denoise_lds', 1)
     for key in ('ms_per_call_lds1', 'ms_per_call_lds0'):
         t = out[key]
@@ -59,7 +63,7 @@ def kernels(size, repeat):
     # (prologue + first iteration + epilogue) = t[1]; an iteration of stride 2^k = t[k + 1] - t[k] for k >= 1
     out['ms_first_iteration_with_prologue_and_epilogue'] = t[1]
     it = (t[5] - t[1]) / 4
-    nbytes = 64.0 * size * size
+    nbytes = (72.0 if variance else 64.0) * size * size
     out['mean_ms_per_iteration'] = round(it, 4)
     out['iteration_bytes'] = int(nbytes)
     out['iteration_bytes_per_s_over_hbm_spec'] = round(nbytes / (it * 1e-3) / HBM_SPEC, 3)
@@ -67,11 +71,13 @@ def kernels(size, repeat):
     print(json.dumps(out), flush=True)
 
 
-def headline(steps):
+def headline(steps, variance=None):
     path, preview, film = setup(512, preview=True)
     preview.render(2)
-    out = {'metric': 'headline_step_ms', 'scene': 's978', 'size': 512, 'spp': 32, 'steps': steps}
-    for name, read in (('get_image', film.get_image), ('get_denoised', film.get_denoised), ('get_image_again', film.get_image)):
+    path.render(32)
+    film.mark()
+    out = {'metric': 'headline_step_ms', 'scene': 's978', 'size': 512, 'spp': 32, 'steps': steps, 'variance': variance}
+    for name, read in (('get_image', film.get_image), ('get_denoised', lambda: film.get_denoised(variance=variance)), ('get_image_again', film.get_image)):
         for _ in range(3):
             path.render(32)
             read()
@@ -88,11 +94,12 @@ def main():
     ap.add_argument('--repeat', type=int, default=20)
     ap.add_argument('--sizes', type=int, nargs='*', default=[512, 2048])
     ap.add_argument('--steps', type=int, default=50)
+    ap.add_argument('--variance', type=float, default=None, help='time the variance-guided mode at this sigma_variance')
     args = ap.parse_args()
     for size in args.sizes:
-        kernels(size, args.repeat)
+        kernels(size, args.repeat, args.variance)
     if args.steps > 0:
-        headline(args.steps)
+        headline(args.steps, args.variance)
 
 
 if __name__ == '__main__':
