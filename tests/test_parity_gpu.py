@@ -577,7 +577,10 @@ def test_pipelined_wide_launches_keep_their_own_spill_strips(fresh, tmp_path):
     launches of different ring slots are resident together -- each slot needs its own.  A test build of the library keeps
     only 4 stack levels in LDS (libmiptina_spilltest.so, make -C ptina_amd/csrc spilltest), so every ray of the
     978-triangle scene runs through the strips: eight launches issued back to back (four in flight) must give the film
-    of eight launches issued one at a time, bit for bit'''
+    of eight launches issued one at a time, bit for bit.
+    This is a test of strip OWNERSHIP: both films come from the spilltest library, so an error of the spill path itself (push /
+    pop beyond CAP) is in both.  Its correctness is held to an exhaustive search and to the normal library's film in
+    tests/test_visibility_gpu.py::test_spilled_stacks_against_truth_and_the_normal_library'''
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -5,8 +5,10 @@ collapse on the host and on the device (wide_build.hip) are built, downloaded an
 child boxes exact and enclosing (E1-E4), 8-bit boxes rounded outwards and no looser than 1.26 steps (Q1-Q6), the LBVH
 arrays (L1-L5), and the options the LDS kernel sizes its stack by (S1) recomputed from the records.  No case renders.
 
-Still open: the binary `fnode` records that the non-default wide = 0 / lds_wide = 0 kernels walk.  The collapse drops
-their inner boxes and there is no door to download them.
+The binary `fnode` records (what the production build's preview, brute-force and Metropolis kernels and wide = 0 /
+lds_wide = 0 walk) have no door to download them and the collapse drops their inner boxes: they still have no record-level
+check.  Their walks are held to an exhaustive search instead, pixel for pixel, over the host's and the device's SAH pass:
+tests/test_visibility_gpu.py (preview, brute, Metropolis door, kernels 0 and 1).
 '''
 
 import numpy as np
