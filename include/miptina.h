@@ -457,6 +457,48 @@ int mpt_noise_eval(mpt_ctx *ctx, float threshold, const float *film_raw, const f
 /* HIP-event time (ms) of the kernels (estimate, fold) of the mpt_get_noise calls since the last call, and their count */
 int mpt_noise_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
 
+/* Adaptive sampling: render only the pixels whose noise estimate is still above the threshold -- what a Blender user means by
+ * "noise threshold": Cycles stops sampling a pixel once it passes (no reference counterpart).  A pass beside the render kernels:
+ * a selection kernel, a compacted pixel list the context keeps (THE SELECTION), and a list render kernel that traces the
+ * PathEngine's path (path_step) for the listed pixels.  With e and valid of mpt_get_noise above:
+ *   above(p)  = valid(p) and e(p) > threshold                                (>, not >=)
+ *   active(p) = valid(p) and (above(p) or (dilate == 1 and one of p's up to eight neighbours inside the film is above))
+ * A pixel that is not valid is never active: no samples on one side of the mark, which covers every column a slab or stripe split
+ * did not render -- a context only ever lists pixels of its own share.  dilate = 1 is Cycles' filter: a converged pixel beside a
+ * noisy one keeps sampling.
+ * The list holds the int32 film indices x*ny + y of the active pixels in an order that is a function of the film alone: by 16x16
+ * tile of the whole film, tile (tx, ty) before (tx, ty + 1) before (tx + 1, 0), and within a tile x - 16 tx ascending, then y.  It is
+ * made without atomics and repeats bit for bit.
+ * mpt_adapt_select: flushes what is enqueued, then selects on the main stream from pass 0 and the mark; writes no film pass and
+ *   leaves the mark alone.  stats (may be NULL) = exactly what mpt_get_noise(threshold) reports, field for field; count (may be
+ *   NULL) = the length of the list.  Fails without a mark, for a threshold mpt_get_noise refuses, for dilate outside {0, 1}.
+ * mpt_adapt_get_list: the selection's indices; out = NULL with cap = 0 asks for the count alone.  Fails when cap < count.
+ * mpt_adapt_set_list: a selection from the host (a region, a user mask; the tests' door).  The indices must be strictly ascending --
+ *   so no pixel is listed twice -- in [0, nx*ny) and in columns of the context's slab or stripes; otherwise the call fails, names
+ *   the first offender and keeps the selection there was.  count = 0 is a selection of nothing.
+ * mpt_render_selected: nframes samples for every pixel of the selection, launched at the call like mpt_render_brute and ordered
+ *   with the other engines' frames the same way.  Per launch the Sobol sampler advances exactly as for mpt_render (also when the
+ *   selection is empty) and work item f*count + k traces frame f of list entry k; a fold then adds each pixel's samples to pass 0
+ *   in frame order, (r, g, b, 1) per sample -- the PathEngine's order of additions, so the film does not depend on how the frames
+ *   were split into launches (a launch's samples stay under 64 MiB), and in the strict build the listed pixels hold exactly what
+ *   mpt_render would have added to them.  remark != 0 (needs a mark) first sets M := F for the listed pixels -- the samples of this
+ *   call are then their second group -- and does nothing when nframes = 0.  Pixels off the list keep film and mark.  Fails when
+ *   there is no selection.
+ * mpt_set_size and mpt_clear drop the selection (they change what an index means, or drop the mark); nothing else does.
+ * mpt_adapt_eval: test door in the mpt_noise_eval idiom: the SAME selection kernels on caller-supplied accumulators film_raw and
+ *   mark_raw [nx*ny][4] in buffers of its own; touches no film pass, not the context's mark and not its selection.  list_out
+ *   [cap], count and stats may each be NULL, not all three.
+ * mpt_adapt_kernel_time: HIP-event time (ms) of the selections (mpt_adapt_select) and of the list passes (mpt_render_selected, render
+ *   kernels and folds of the whole call) since the last call, and how many such calls there were (a list pass that launched
+ *   nothing is not counted); the test door is not timed. */
+int mpt_adapt_select(mpt_ctx *ctx, float threshold, int dilate, mpt_noise_stats *stats /* or NULL */, int *count /* or NULL */);
+int mpt_adapt_get_list(mpt_ctx *ctx, int32_t *out /* [cap] or NULL */, int cap, int *count /* or NULL */);
+int mpt_adapt_set_list(mpt_ctx *ctx, const int32_t *pix /* [count] */, int count);
+int mpt_render_selected(mpt_ctx *ctx, int nframes, int remark);
+int mpt_adapt_eval(mpt_ctx *ctx, float threshold, int dilate, const float *film_raw, const float *mark_raw, int nx, int ny,
+                   int32_t *list_out, int cap, int *count, mpt_noise_stats *stats);
+int mpt_adapt_kernel_time(mpt_ctx *ctx, double *select_ms, double *render_ms, int *launches);
+
 /* Page-locked host buffers for the read-backs above: into such a buffer mpt_get_image /
  * mpt_fast_export_image / mpt_get_film_raw are one DMA; any other buffer is served through a
  * page-locked staging copy.  (The reference's get_image returns a fresh numpy array,

@@ -153,6 +153,12 @@ SIGNATURES = {
     'mpt_get_mark': (_i, [_vp, _fp]),
     'mpt_noise_eval': (_i, [_vp, C.c_float, _fp, _fp, _i, _i, _fp, _fp, C.POINTER(NoiseStats)]),
     'mpt_noise_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_adapt_select': (_i, [_vp, C.c_float, _i, C.POINTER(NoiseStats), C.POINTER(_i)]),
+    'mpt_adapt_get_list': (_i, [_vp, _ip, _i, C.POINTER(_i)]),
+    'mpt_adapt_set_list': (_i, [_vp, _ip, _i]),
+    'mpt_render_selected': (_i, [_vp, _i, _i]),
+    'mpt_adapt_eval': (_i, [_vp, C.c_float, _i, _fp, _fp, _i, _i, _ip, _i, C.POINTER(_i), C.POINTER(NoiseStats)]),
+    'mpt_adapt_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     'mpt_host_alloc': (_vp, [C.c_size_t]),
     'mpt_host_free': (None, [_vp]),
     'mpt_get_counters': (_i, [_vp, C.POINTER(Counters)]),
@@ -390,6 +396,18 @@ class Context:
         self.call('mpt_noise_eval', float(threshold), fptr(f), fptr(m), int(nx), int(ny), None if e is None else fptr(e),
                   None if new is None else fptr(new), C.byref(st))
         return NoiseResult(st, e), new
+
+    def adapt_eval(self, film_raw, mark_raw, nx, ny, threshold, dilate=1):
+        '''test door (mpt_adapt_eval): FilmTable.select's kernels on the accumulators film_raw and mark_raw [nx*ny][4]; returns
+        (NoiseResult, the list int32[count])'''
+        f = np.ascontiguousarray(np.asarray(film_raw, np.float32).reshape(-1, 4))
+        m = np.ascontiguousarray(np.asarray(mark_raw, np.float32).reshape(-1, 4))
+        if f.shape[0] != int(nx) * int(ny) or m.shape != f.shape:
+            raise ValueError('film and mark hold %d and %d accumulators, the film %dx%d' % (f.shape[0], m.shape[0], nx, ny))
+        out = np.empty(f.shape[0], np.int32)
+        st, n = NoiseStats(), C.c_int(-1)
+        self.call('mpt_adapt_eval', float(threshold), int(dilate), fptr(f), fptr(m), int(nx), int(ny), iptr(out), out.size, C.byref(n), C.byref(st))
+        return NoiseResult(st), out[:n.value].copy()
 
     def counters(self):
         cnt = Counters()

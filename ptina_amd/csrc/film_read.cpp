@@ -1,6 +1,6 @@
 // film_read.cpp -- the film's read-backs behind the C ABI of include/miptina.h: clear, resolve, the image and its hint, export, the
 // raw passes; the denoised image (denoise.hip), the 8-bit display image (display.hip), the mark and the noise estimate (noise.hip),
-// the three test doors and the three features' kernel timers.  Everything here runs on the main stream behind what is enqueued: of the
+// adaptive sampling's selection (adapt_select.hip), the four test doors and the four features' kernel timers.  Everything here runs on the main stream behind what is enqueued: of the
 // launch ring (miptina.cpp) it takes mpt_flush, read_back, caller_alias and timer_readout, and it knows the early image only in
 // mpt_hint_image and mpt_get_image.
 
@@ -64,6 +64,7 @@ extern "C" int mpt_clear(mpt_ctx *c, int pass) {                               /
         if (c->fb.film[p]) HIP_TRY(hipMemsetAsync(c->fb.film[p], 0, npix * sizeof(MptVec4), c->stream));
     c->film_version++;
     c->noise.marked = false;                     // the samples the mark counted are gone
+    c->adapt.selected = false; c->adapt.count = 0;   // ... and a selection is made against a mark
     return 0;
 }
 
@@ -408,5 +409,119 @@ extern "C" int mpt_noise_eval(mpt_ctx *c, float threshold, const float *film_raw
     HIP_TRY(mpt_launch_noise(film, mark, npix, threshold, new_mark ? 1 : 0, map ? b.map.p : nullptr, b.part, c->noise.stats.dev, c->stream));
     if (noise_finish(c, b, npix, map, stats)) return 1;
     if (new_mark && read_back(c, new_mark, mark, npix * sizeof(MptVec4))) return 1;
+    return 0;
+}
+
+// ------------------------------------------------------------------ adaptive sampling: the selection (adapt_select.hip)
+// Which pixels of pass 0 still need samples, as a list the context keeps (fb.adapt.list) for mpt_render_selected (miptina.cpp).
+// Reads pass 0 and the mark, writes neither.
+static int adapt_args(const char *who, float threshold, int dilate) {
+    if (finite_arg(who, "threshold", threshold, true)) return 1;
+    if (dilate != 0 && dilate != 1) return fail("%s: dilate must be 0 or 1, got %d", who, dilate);
+    return 0;
+}
+
+// the statistics (noise.hip's own launches: its shape of the sum gives its bits) and the list of one film and mark; the main
+// stream is synchronised and the host's record read into *r
+static int adapt_launches(mpt_ctx *c, const MptVec4 *film, MptVec4 *mark, int nx, int ny, float threshold, int dilate, const MptAdaptBufs &b,
+                          MptTimedSpan *span, mpt_ctx::MptAdaptRecord *r) {
+    mpt_ctx::MptAdaptRecord *const rec = c->adapt.rec.dev;
+    HIP_TRY(mpt_launch_noise(film, mark, (size_t)nx * ny, threshold, 0, nullptr, b.part, &rec->stats, c->stream));
+    HIP_TRY(mpt_launch_adapt_select(film, mark, nx, ny, threshold, dilate, b.ballot, b.count, b.list, &rec->count, c->stream));
+    if (span) HIP_TRY(span->end());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memcpy(r, (const void *)c->adapt.rec.host.p, sizeof *r);
+    if (r->count < 0 || r->count > (long long)nx * ny) return fail("adaptive selection: the device counted %lld pixels of %lld", r->count, (long long)nx * ny);
+    return 0;
+}
+
+extern "C" int mpt_adapt_select(mpt_ctx *c, float threshold, int dilate, mpt_noise_stats *stats, int *count) {
+    if (use_ro(c)) return 1;
+    if (adapt_args("mpt_adapt_select", threshold, dilate)) return 1;
+    if (!c->noise.marked) return fail("mpt_adapt_select: no mark: call mpt_film_mark() first (mpt_clear and mpt_set_size drop the mark)");
+    return film_read(c, 0, [&] {
+        if (c->fb.reserve_adapt()) return 1;
+        c->adapt.selected = false; c->adapt.count = 0;       // (the list is about to be rewritten)
+        mpt_ctx::MptAdaptRecord r;
+        MptTimedSpan span(c->adapt.select_timer, c->stream);
+        HIP_TRY(span.begun);
+        if (adapt_launches(c, c->fb.film[0], c->fb.mark, c->nx, c->ny, threshold, dilate, c->fb.adapt, &span, &r)) return 1;
+        c->adapt.selected = true; c->adapt.count = (int)r.count;
+        if (stats) *stats = r.stats;
+        if (count) *count = (int)r.count;
+        return 0;
+    });
+}
+
+static int adapt_selected(const mpt_ctx *c, const char *who) {
+    if (!c->adapt.selected)
+        return fail("%s: no selection: call mpt_adapt_select() or mpt_adapt_set_list() first (mpt_clear and mpt_set_size drop the selection)", who);
+    return 0;
+}
+
+extern "C" int mpt_adapt_get_list(mpt_ctx *c, int32_t *out, int cap, int *count) {
+    if (use_ro(c)) return 1;
+    if (adapt_selected(c, "mpt_adapt_get_list")) return 1;
+    if (!out && !count) return fail("mpt_adapt_get_list: null list and null count");
+    if (count) *count = c->adapt.count;
+    if (!out) return 0;
+    if (cap < c->adapt.count) return fail("mpt_adapt_get_list: room for %d indices, the selection holds %d", cap, c->adapt.count);
+    if (mpt_flush(c)) return 1;
+    if (c->adapt.count == 0) return 0;
+    return read_back(c, out, c->fb.adapt.list, (size_t)c->adapt.count * sizeof(int32_t));
+}
+
+// is column x of the film one this context renders?
+static bool own_column(const mpt_ctx *c, int x) {
+    if (x < c->x0 || x >= c->x1) return false;
+    return c->stripe_w == 0 || (x / c->stripe_w) % c->stripe_mod == c->stripe_idx;
+}
+
+extern "C" int mpt_adapt_set_list(mpt_ctx *c, const int32_t *pix, int count) {
+    if (use_ro(c)) return 1;
+    if (count < 0 || (count > 0 && !pix)) return fail("mpt_adapt_set_list: %s", count < 0 ? "count must be >= 0" : "null list");
+    if (film_ready(c, 0)) return 1;
+    const long long npix = (long long)c->nx * c->ny;
+    for (int k = 0; k < count; k++) {
+        if (pix[k] < 0 || pix[k] >= npix) return fail("mpt_adapt_set_list: entry %d = %d outside the film's [0, %lld)", k, pix[k], npix);
+        if (k > 0 && pix[k] <= pix[k - 1])
+            return fail("mpt_adapt_set_list: entry %d = %d after %d: the list must be strictly ascending", k, pix[k], pix[k - 1]);
+        if (!own_column(c, pix[k] / c->ny))
+            return fail("mpt_adapt_set_list: entry %d = %d lies in column %d, outside this context's slab or stripes", k, pix[k], pix[k] / c->ny);
+    }
+    if (c->fb.reserve_adapt()) return 1;
+    c->adapt.selected = false; c->adapt.count = 0;
+    if (count > 0) HIP_TRY(hipMemcpyAsync(c->fb.adapt.list, pix, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                      // (the caller's array is free again)
+    c->adapt.selected = true; c->adapt.count = count;
+    return 0;
+}
+
+// test door: the same launches on the caller's film and mark, in buffers of its own (no film pass, not the context's mark, not its
+// selection); not timed
+extern "C" int mpt_adapt_eval(mpt_ctx *c, float threshold, int dilate, const float *film_raw, const float *mark_raw, int nx, int ny,
+                              int32_t *list_out, int cap, int *count, mpt_noise_stats *stats) {
+    if (use_ro(c)) return 1;
+    if (!film_raw || !mark_raw) return fail("mpt_adapt_eval: null input");
+    if (!list_out && !count && !stats) return fail("mpt_adapt_eval: null outputs");
+    if (adapt_args("mpt_adapt_eval", threshold, dilate)) return 1;
+    if (door_film(c, "mpt_adapt_eval", nx, ny)) return 1;
+    const size_t npix = (size_t)nx * ny;
+    MptAdaptBufs &b = c->adapt.bufs;
+    if (door_stage(c, npix, b, film_raw, mark_raw)) return 1;
+    mpt_ctx::MptAdaptRecord r;
+    if (adapt_launches(c, c->door.acc[0], c->door.acc[1], nx, ny, threshold, dilate, b, nullptr, &r)) return 1;
+    if (count) *count = (int)r.count;
+    if (stats) *stats = r.stats;
+    if (!list_out) return 0;
+    if (cap < r.count) return fail("mpt_adapt_eval: room for %d indices, the selection holds %lld", cap, r.count);
+    return r.count ? read_back(c, list_out, b.list, (size_t)r.count * sizeof(int32_t)) : 0;
+}
+
+extern "C" int mpt_adapt_kernel_time(mpt_ctx *c, double *select_ms, double *render_ms, int *launches) {
+    int selections = 0, passes = 0;
+    if (use_ro(c) || timer_readout(c, c->adapt.select_timer, select_ms, nullptr, &selections) ||
+        timer_readout(c, c->adapt.render_timer, render_ms, nullptr, &passes)) return 1;
+    if (launches) *launches = selections + passes;
     return 0;
 }

@@ -151,6 +151,7 @@ extern "C" mpt_ctx *mpt_create(const mpt_caps *caps, int device) {
     if (c->display.exposure.create(1)) return bail("pinned exposure word");
     *c->display.exposure.host = 1.0f;
     if (c->noise.stats.create(1)) return bail("pinned noise statistics");
+    if (c->adapt.rec.create(1)) return bail("pinned selection record");
     hipMemsetAsync(c->d_counters, 0, MPT_COUNTER_WORDS * sizeof(unsigned long long), c->stream);
     {   // unset materials: factor 0 (field-zero, mtllib.py:12-13), texture -1 (deviation Q6)
         std::vector<MptMaterial> z((size_t)c->caps.max_materials + 1);
@@ -342,6 +343,7 @@ extern "C" int mpt_set_size(mpt_ctx *c, int nx, int ny) {
     c->nx = nx; c->ny = ny; c->x0 = 0; c->x1 = nx; c->stripe_w = 0; c->stripe_idx = 0; c->stripe_mod = 1;
     c->film_version++;
     c->noise.marked = false;                     // a mark is a copy of the film as it was sized
+    c->adapt.selected = false; c->adapt.count = 0;   // ... and a selection's indices mean pixels of that film
     return 0;
 }
 
@@ -1219,6 +1221,62 @@ extern "C" int mpt_render_brute(mpt_ctx *c, int nframes) {                     /
 
 extern "C" int mpt_brute_kernel_time(mpt_ctx *c, double *ms, int *launches) {
     return use_ro(c) || timer_readout(c, c->brute_timer, ms, nullptr, launches);
+}
+
+// ------------------------------------------------------------------ adaptive sampling: the list pass (PathEngine.render_selected)
+// nframes samples for the pixels of the selection only (mpt_adapt_select / mpt_adapt_set_list, film_read.cpp): the list render
+// kernel leaves every sample in fb.adapt_samples, the fold adds them to pass 0 in frame order.  Launched at the call, on the main
+// stream, with mpt_render_brute's bookkeeping, so frames of every engine add to film pass 0 in call order.
+enum : size_t { MPT_ADAPT_SAMPLE_BYTES = (size_t)64 << 20 };   // a launch's samples stay under this: a call's frames are split to fit
+
+// the launches of a call: `per` frames at most each; the first fold moves the mark (remark).  An empty selection launches
+// nothing, and the sampler still advances by the call's frames
+static int selected_launches(mpt_ctx *c, int nframes, int remark, int per) {
+    const int count = c->adapt.count;
+    const int stack = gather_stack_levels(c);
+    while (nframes > 0) {
+        const int B = std::min(nframes, per);
+        MptRenderParams p;
+        if (fill_params(c, p, B)) return 1;
+        if (sobol_advance(c, B, B)) return 1;
+        if (count > 0) {
+            if (c->opt.mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_adapt_render_strict(&p, c->fb.adapt.list, count, c->fb.adapt_samples, stack, c->stream));
+            else HIP_TRY(mpt_launch_adapt_render_fast(&p, c->fb.adapt.list, count, c->fb.adapt_samples, stack, c->stream));
+            HIP_TRY(mpt_launch_adapt_fold(c->fb.film[0], remark ? c->fb.mark.p : nullptr, c->fb.adapt.list, count, c->fb.adapt_samples, B, remark,
+                                          c->stream));
+            remark = 0;
+        }
+        nframes -= B;
+    }
+    return 0;
+}
+
+extern "C" int mpt_render_selected(mpt_ctx *c, int nframes, int remark) {
+    if (!c) return fail("null context");
+    if (nframes < 0) return fail("nframes must be >= 0");
+    if (check_ready(c)) return 1;
+    if (!c->adapt.selected)
+        return fail("mpt_render_selected: no selection: call mpt_adapt_select() or mpt_adapt_set_list() first (mpt_clear and mpt_set_size drop the selection)");
+    if (remark && !c->noise.marked)
+        return fail("mpt_render_selected: no mark: call mpt_film_mark() first (mpt_clear and mpt_set_size drop the mark)");
+    if (use(c)) return 1;
+    const int count = c->adapt.count;
+    int per = MPT_MAX_BATCH;
+    if (count > 0) per = (int)std::min<size_t>(MPT_MAX_BATCH, std::max<size_t>(1, (MPT_ADAPT_SAMPLE_BYTES - 1) / (sizeof(MptVec4) * (size_t)count)));
+    if (count > 0 && nframes > 0) {
+        const size_t need = (size_t)count * (size_t)std::min(nframes, per);
+        if (need > c->fb.adapt_samples.cap) {
+            HIP_TRY(hipStreamSynchronize(c->stream));          // (a launch may still read the old buffer)
+            if (c->fb.adapt_samples.reserve(need)) return 1;
+        }
+        MptTimedSpan span(c->adapt.render_timer, c->stream);
+        HIP_TRY(span.begun);
+        if (selected_launches(c, nframes, remark ? 1 : 0, per)) return 1;
+        HIP_TRY(span.end());
+        c->film_version++;           // pass 0 has changed: an early image of an earlier PathEngine launch is stale
+    } else if (selected_launches(c, nframes, 0, per)) return 1;
+    c->main_dirty = true;            // the next PathEngine launch waits for these
+    return 0;
 }
 
 // a persistent render kernel that had to be stopped by its watchdog leaves a flag behind (in host-pinned

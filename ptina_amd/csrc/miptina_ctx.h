@@ -41,6 +41,9 @@ MPT_KERNEL_API hipError_t mpt_launch_mlt_splat(MptVec4 *film, const unsigned *ke
 // brute_kernel.hip: the brute-force engine's kernel (both builds)
 MPT_KERNEL_API hipError_t mpt_launch_brute_fast(const MptRenderParams *, int grid, int stack, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_brute_strict(const MptRenderParams *, int grid, int stack, hipStream_t);
+// adapt_kernel.hip: adaptive sampling's list render kernel (both builds); samples holds count * nframes records
+MPT_KERNEL_API hipError_t mpt_launch_adapt_render_fast(const MptRenderParams *, const int32_t *list, int count, MptVec4 *samples, int stack, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_launch_adapt_render_strict(const MptRenderParams *, const int32_t *list, int count, MptVec4 *samples, int stack, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_preview_fast(const MptRenderParams *, int grid, int stack, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_preview_strict(const MptRenderParams *, int grid, int stack, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_sobol_update(const int *X, int *Xout, const int *V, float *P, int dim, int rows, int time0,
@@ -70,6 +73,14 @@ MPT_KERNEL_API hipError_t mpt_launch_display_convert(const MptVec4 *src, uint32_
 MPT_KERNEL_API size_t mpt_noise_parts(size_t npix);
 MPT_KERNEL_API hipError_t mpt_launch_noise(const MptVec4 *film, MptVec4 *mark, size_t npix, float threshold, int remark, float *map /* or NULL */,
                                            mpt_noise_stats *part, mpt_noise_stats *stats_host, hipStream_t);
+// adapt_select.hip: the selection of the pixels that still need samples (mpt_adapt_select) and the fold of a list pass's samples
+// into the film (mpt_render_selected); ballot holds 4 words and count one int per tile, list nx * ny indices
+MPT_KERNEL_API size_t mpt_adapt_tiles(int nx, int ny);
+MPT_KERNEL_API size_t mpt_adapt_tile_bound(size_t npix);
+MPT_KERNEL_API hipError_t mpt_launch_adapt_select(const MptVec4 *film, const MptVec4 *mark, int nx, int ny, float threshold, int dilate,
+                                                  unsigned long long *ballot, int *count, int32_t *list, long long *total_host, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_launch_adapt_fold(MptVec4 *film, MptVec4 *mark /* or NULL */, const int32_t *list, int count, const MptVec4 *samples,
+                                                int nframes, int remark, hipStream_t);
 
 // on-GPU LBVH build (lbvh_build.hip)
 struct MptLbvhBuffers {
@@ -207,6 +218,23 @@ struct MPT_INTERNAL MptNoiseBufs {         // what mpt_get_noise's kernels write
     }
 };
 
+struct MPT_INTERNAL MptAdaptBufs {         // what mpt_adapt_select's kernels write, for a film of up to `cap` pixels of any shape
+    DevBuf<int32_t> list;                // the selection: film indices
+    DevBuf<unsigned long long> ballot;   // the waves' ballots of their active lanes, 4 per tile
+    DevBuf<int> count;                   // per tile: its active pixels, then its offset into the list
+    DevBuf<mpt_noise_stats> part;        // the statistics' first-stage partials (noise.hip)
+    size_t cap = 0;
+    void release() { list.release(); ballot.release(); count.release(); part.release(); cap = 0; }
+    int reserve(size_t npix) {
+        if (npix <= cap) return 0;
+        release();
+        const size_t tiles = mpt_adapt_tile_bound(npix);
+        if (list.reserve(npix) || ballot.reserve(4 * tiles) || count.reserve(tiles) || part.reserve(std::max<size_t>(mpt_noise_parts(npix), 1))) return 1;
+        cap = npix;
+        return 0;
+    }
+};
+
 struct MPT_INTERNAL MptDenoiseBufs {       // mpt_denoise_eval: the caller's guide passes and what the filter's kernels write, for a film of up to `cap` pixels
     DevBuf<MptVec4> f1, f2;              // the accumulators of passes 1 and 2 (pass 0 and the mark go through MptDoorInput)
     DevBuf<MptVec4> e[2], a, n;          // as MptFilmBufs' dn_e, dn_a, dn_n
@@ -251,7 +279,11 @@ struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set 
     // the variance-guided filter's plane v, nx*ny floats in two copies like dn_e: made by the first guided read-back
     // (reserve_variance), for `cap` pixels, and released with the rest
     DevBuf<float> dn_v[2];
+    // adaptive sampling: the selection and its workspace, made by the first selection (reserve_adapt) for `cap` pixels, and the
+    // list render kernel's samples, grown on demand (adapt_samples.cap records); released with the rest
+    MptAdaptBufs adapt; DevBuf<MptVec4> adapt_samples;
     size_t cap = 0;
+    int reserve_adapt() { return adapt.reserve(cap); }
     int reserve_mark() { return mark.reserve(cap) || noise.reserve(cap); }
     int reserve_variance() { return dn_v[0].reserve(cap) || dn_v[1].reserve(cap); }
     int reserve(size_t npix, hipStream_t stream) {     // the passes come back zeroed on `stream`
@@ -263,6 +295,7 @@ struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set 
         disp.release();
         mark.release(); noise.release();
         dn_v[0].release(); dn_v[1].release();
+        adapt.release(); adapt_samples.release();
         for (auto &b : film) {
             if (b.reserve(npix)) return 1;
             HIP_TRY(hipMemsetAsync(b, 0, npix * sizeof(MptVec4), stream));
@@ -549,6 +582,14 @@ struct mpt_ctx {
         MptLaunchTimer timer;                            // mpt_get_noise: {before the estimate, after the fold} per call
         explicit Noise(MptEventPool &ev) : timer(2, ev) {}
     } noise{events};
+    struct MptAdaptRecord { mpt_noise_stats stats; long long count; };   // what a selection leaves in the host's mapped memory
+    struct MPT_INTERNAL Adapt {                          // adaptive sampling (mpt_adapt_*, mpt_render_selected)
+        bool selected = false; int count = 0;            // fb.adapt.list[0 .. count) is the selection (mpt_clear and mpt_set_size drop it)
+        MappedBuf<MptAdaptRecord> rec;                   // the statistics and the count of the last selection
+        MptAdaptBufs bufs;                               // mpt_adapt_eval: what the kernels write for the caller's film and mark (grown on demand)
+        MptLaunchTimer select_timer, render_timer;       // mpt_adapt_select: {before the kernels, after them} per call; mpt_render_selected: the same around a call's launches
+        explicit Adapt(MptEventPool &ev) : select_timer(2, ev), render_timer(2, ev) {}
+    } adapt{events};
     MptDoorInput door;                                   // mpt_display_eval, mpt_noise_eval, mpt_denoise_eval: the caller's accumulators on the device (grown on demand)
     MptLaunchTimer render_timer{2, events};              // PathEngine launches: {kernel start, kernel end}
     MptLaunchTimer denoise_timer{2, events};             // mpt_get_denoised: {before the prologue, after the epilogue} per call

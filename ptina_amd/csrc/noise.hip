@@ -27,24 +27,10 @@
 #include "mpt_types.h"
 #include "film_ops.h"
 #include "film_fold.h"
+#include "noise_pixel.h"            // nz_pixel: e of one pixel, shared with adapt_select.hip
 
 enum { NZ_BLOCK = 256, NZ_PER_LANE = 4, NZ_RUN = NZ_BLOCK * NZ_PER_LANE };   // 1024 consecutive film elements per workgroup
 static_assert(NZ_BLOCK == FILM_FOLD_BLOCK, "the fold is written for this block");
-
-// e of one pixel; false (and e = 0) where the pixel is not valid
-__device__ __forceinline__ bool nz_pixel(const float4 F, const float4 M, float *e) {
-    const float nA = M.w, n = F.w, nB = n - nA;
-    *e = 0.0f;
-    if (!(nA > 0.0f && nB > 0.0f)) return false;
-    const float a[3] = { film_sanitise(M.x / nA), film_sanitise(M.y / nA), film_sanitise(M.z / nA) };
-    const float m[3] = { film_sanitise(F.x / n), film_sanitise(F.y / n), film_sanitise(F.z / n) };
-    const float k = sqrtf(nA / nB);
-    const float d[3] = { fabsf(m[0] - a[0]) * k, fabsf(m[1] - a[1]) * k, fabsf(m[2] - a[2]) * k };
-    const float num = ((d[0] + d[1]) + d[2]) / 3.0f;
-    const float den = 1e-4f + sqrtf(((m[0] + m[1]) + m[2]) / 3.0f);
-    *e = film_sanitise(num / den);          // (the clamp moves only a value that is not finite: saturated channels overflow the sums)
-    return true;
-}
 
 // the statistics as they are summed; a partial (mpt_launch_noise's `part`) is one of these in the room of an mpt_noise_stats
 struct NzAcc {

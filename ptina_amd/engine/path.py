@@ -28,3 +28,13 @@ class PathEngine(metaclass=Singleton):
     def render_until(self, noise, max_spp, min_spp=16, fraction=0.0):
         '''render until the film's noise estimate passes `noise` or `max_spp` frames are spent (engine.render_until)'''
         return render_until(self, noise, max_spp, min_spp, fraction)
+
+    def render_selected(self, nframes=1, remark=False):
+        '''nframes samples for the pixels of the film's selection only (FilmTable.select / set_selection; mpt_render_selected): the
+        same path as render(), traced by the list kernel (csrc/adapt_kernel.hip), launched at the call.  remark=True first moves the
+        mark of the listed pixels to their film as it is, so that this call's samples are their second group'''
+        ctx().call('mpt_render_selected', int(nframes), 1 if remark else 0)
+
+    def render_adaptive(self, noise, max_spp, min_spp=16, fraction=0.0, dilate=1, switch=None):
+        '''render until every pixel's noise estimate passes `noise`, sampling only the pixels that have not (engine.render_adaptive)'''
+        return render_adaptive(self, noise, max_spp, min_spp, fraction, dilate, switch)

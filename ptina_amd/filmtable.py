@@ -154,6 +154,51 @@ class FilmTable(metaclass=Singleton):
         '''(ms, calls): HIP-event time of the kernels of the get_noise calls since the last call'''
         return ctx().timer('mpt_noise_kernel_time')
 
+    def select(self, noise, dilate=1):
+        '''adaptive sampling's selection (mpt_adapt_select, include/miptina.h): the pixels of pass 0 that still need samples, from
+        the film and the mark, kept on the device as THE SELECTION for PathEngine.render_selected.  A pixel is above when it is
+        valid and its estimate e > noise; it is active -- listed -- when it is valid and above or, with dilate=1 (Cycles' filter), a
+        neighbour of an above pixel.  Pixels without samples on both sides of the mark (columns another GPU renders) are never
+        listed.  Returns (NoiseResult, count): exactly get_noise(noise)'s statistics, and the length of the list.  Only those 40
+        bytes cross PCIe.  clear() and set_size() drop the selection.  No reference counterpart'''
+        from ._lib import NoiseStats, NoiseResult
+        st, n = NoiseStats(), C.c_int(0)
+        ctx().call('mpt_adapt_select', float(noise), int(dilate), C.byref(st), C.byref(n))
+        return NoiseResult(st), n.value
+
+    def get_selection(self):
+        '''the selection's film indices x*ny + y, int32[count], in the device's order: by 16x16 tile (tile rows along y first), within
+        a tile by x, then y (mpt_adapt_get_list)'''
+        n = C.c_int(0)
+        ctx().call('mpt_adapt_get_list', None, 0, C.byref(n))
+        out = np.empty(n.value, np.int32)
+        if n.value:
+            ctx().call('mpt_adapt_get_list', out.ctypes.data_as(C.POINTER(C.c_int32)), out.size, None)
+        return out
+
+    def set_selection(self, pixels):
+        '''a selection from the host (mpt_adapt_set_list): a bool mask [nx, ny], or film indices x*ny + y, strictly ascending (so
+        that no pixel is listed twice), inside the film and inside this context's slab or stripes -- a region, a user mask'''
+        nx, ny = self._res()
+        a = np.asarray(pixels)
+        if a.dtype == np.bool_:
+            if a.shape != (nx, ny):
+                raise ValueError('set_selection: the mask is %s, the film (%d, %d)' % (a.shape, nx, ny))
+            a = np.flatnonzero(a.ravel())
+        if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+            raise ValueError('set_selection: an index does not fit 32 bits')
+        a = np.ascontiguousarray(a.reshape(-1), np.int32)
+        ctx().call('mpt_adapt_set_list', a.ctypes.data_as(C.POINTER(C.c_int32)), int(a.size))
+
+    def get_samples(self):
+        '''pass 0's sample weight per pixel, float32 [nx, ny]: after adaptive sampling, how many samples each pixel took'''
+        nx, ny = self._res()
+        return np.ascontiguousarray(self.get_raw(0)[:, 3]).reshape(nx, ny)
+
+    def adapt_kernel_time(self):
+        '''(select_ms, render_ms, calls): HIP-event time of the select() calls and of the render_selected() calls since the last call'''
+        return ctx().timer('mpt_adapt_kernel_time', 2)
+
     def fast_export_image(self, out, id=0):
         '''reference filmtable.py:66-79: flat RGB f32 at (y * nx + x) * 3 into the caller's buffer'''
         nx, ny = self._res()

@@ -95,6 +95,14 @@ def render_until(noise, max_spp, **kw):
     return loop(DefaultEngine(), noise, max_spp, **kw)
 
 
+def render_adaptive(noise, max_spp, **kw):
+    '''engine.render_adaptive(DefaultEngine(), noise, max_spp, min_spp=16, fraction=0.0, dilate=1, switch=None) -- DefaultEngine().render_adaptive's
+    loop: render_until's schedule, sampling only the pixels whose estimate has not passed yet; expects a cleared film; leaves a mark
+    for get_denoised(variance=...) (no reference counterpart: its loop counts samples)'''
+    from .engine import render_adaptive as loop
+    return loop(DefaultEngine(), noise, max_spp, **kw)
+
+
 def get_size():
     film = FilmTable()
     return film.nx, film.ny
