@@ -499,6 +499,47 @@ int mpt_adapt_eval(mpt_ctx *ctx, float threshold, int dilate, const float *film_
                    int32_t *list_out, int cap, int *count, mpt_noise_stats *stats);
 int mpt_adapt_kernel_time(mpt_ctx *ctx, double *select_ms, double *render_ms, int *launches);
 
+/* Scene composition on the device: what the reference's add-on does on the host at every scene change -- compose_multiple_meshes over
+ * all meshes, then load_model (blender.py:555-571; ptina/multimesh.py:9-87) -- with the meshes and the object table resident on the
+ * device.  A MESH is k faces in object space, [3k][8] f32 records pos3 nrm3 uv2 (mpt_load_model's layout); an OBJECT is a mesh, a
+ * world matrix (16 doubles, row-major as numpy holds it) and a material id.  mpt_compose writes the model mpt_build_tree reads:
+ * the objects in the order they were added, each object's faces contiguous, per vertex in f64 (multimesh.py:58-65)
+ *   ph = (p, 1) . W^T, pos = ph.xyz / ph.w;   nh = (n, 0) . W^T, nrm = nh.xyz / |nh.xyz|;   uv copied
+ * rounded to f32 once.  Normals go through W itself and a zero normal gives NaN, as in the reference.
+ * mpt_mesh_add: copies the records to the device; k = 0 is a mesh (the reference accepts one).
+ * mpt_object_add / mpt_object_set_world / mpt_object_set_material: refuse an unknown mesh or object id, a matrix entry that is not
+ *   finite, a material id outside [-1, max_materials); they change the table only.
+ * mpt_scene_clear: drops the objects, and with meshes != 0 the meshes too.  The composed model stays what it was until mpt_compose.
+ * mpt_compose: after objects were added or dropped (or mpt_load_model took the model back) it writes every face; otherwise only the
+ *   faces of the objects changed since the last call, and only those objects' table records (160 bytes each) cross to the device.  Fails with
+ *   "too many faces" when the objects' faces reach max_faces.  Leaves the model as mpt_load_model of the same arrays would --
+ *   face count, largest material id, bounding sphere -- and the tree invalid; the host's copy of the model is fetched only when
+ *   something reads it (the host tree passes, mpt_get_model).  mpt_load_model afterwards replaces the composed model as ever.
+ * mpt_compose_stats: faces of the model, faces the last mpt_compose wrote, objects it found changed, how often the host's copy of a
+ *   composed model has been fetched since mpt_create, and the model's bounding sphere as the render launches use it (it reads
+ *   whichever of mpt_load_model and mpt_compose came last).
+ * mpt_get_model: the model as loaded or composed, verts [3n][8] and mtlids [n] (either may be NULL); fails when cap_faces < n.
+ * mpt_compose_kernel_time: HIP-event time (ms) of the kernels of the mpt_compose calls since the last call, and their count.
+ * mpt_compose_plan: the layout and the launch of a composition as a pure function (no context, no GPU): faces[nobj] per object and
+ *   dirty[nobj] (NULL: all) give first[nobj + 1], the objects' first output faces and the total, and the runs of 256-vertex
+ *   workgroups of the output that overlap a dirty object with faces, merged where they touch: the first `cap` of them as
+ *   wg_begin / wg_count (any output may be NULL).  Returns the number of runs, -1 for arguments that name no layout (a negative
+ *   count, 3 x total beyond 31 bits). */
+typedef struct {
+    int64_t faces, recomposed, dirty_objects, host_fetches;
+    double scene_cen[3], scene_rad;
+} mpt_compose_info;
+int mpt_mesh_add(mpt_ctx *ctx, const float *verts /* [3k][8] */, int k, int *mesh_id);
+int mpt_object_add(mpt_ctx *ctx, int mesh_id, const double world[16], int mtlid, int *obj_id);
+int mpt_object_set_world(mpt_ctx *ctx, int obj_id, const double world[16]);
+int mpt_object_set_material(mpt_ctx *ctx, int obj_id, int mtlid);
+int mpt_scene_clear(mpt_ctx *ctx, int meshes);
+int mpt_compose(mpt_ctx *ctx);
+int mpt_compose_stats(mpt_ctx *ctx, mpt_compose_info *out);
+int mpt_get_model(mpt_ctx *ctx, float *verts, int32_t *mtlids, int cap_faces, int *nfaces);
+int mpt_compose_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
+int mpt_compose_plan(const int32_t *faces, const int32_t *dirty, int nobj, int64_t *first, int64_t *wg_begin, int64_t *wg_count, int cap);
+
 /* Page-locked host buffers for the read-backs above: into such a buffer mpt_get_image /
  * mpt_fast_export_image / mpt_get_film_raw are one DMA; any other buffer is served through a
  * page-locked staging copy.  (The reference's get_image returns a fresh numpy array,

@@ -75,6 +75,12 @@ class NoiseResult:
             self.valid, self.above, self.mean, self.max, self.fraction, self.threshold)
 
 
+class ComposeInfo(C.Structure):
+    '''mpt_compose_info (include/miptina.h): what mpt_compose_stats hands back'''
+    _fields_ = [('faces', C.c_int64), ('recomposed', C.c_int64), ('dirty_objects', C.c_int64), ('host_fetches', C.c_int64),
+                ('scene_cen', C.c_double * 3), ('scene_rad', C.c_double)]
+
+
 DISPLAY_DENOISED = -1
 TONE_OPS = {'linear': 0, 'ptina': 1, 'reinhard': 2, 'aces': 3}
 TRANSFERS = {'srgb': 0, 'gamma': 1}
@@ -159,6 +165,16 @@ SIGNATURES = {
     'mpt_render_selected': (_i, [_vp, _i, _i]),
     'mpt_adapt_eval': (_i, [_vp, C.c_float, _i, _fp, _fp, _i, _i, _ip, _i, C.POINTER(_i), C.POINTER(NoiseStats)]),
     'mpt_adapt_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_mesh_add': (_i, [_vp, _fp, _i, C.POINTER(_i)]),
+    'mpt_object_add': (_i, [_vp, _i, C.POINTER(C.c_double), _i, C.POINTER(_i)]),
+    'mpt_object_set_world': (_i, [_vp, _i, C.POINTER(C.c_double)]),
+    'mpt_object_set_material': (_i, [_vp, _i, _i]),
+    'mpt_scene_clear': (_i, [_vp, _i]),
+    'mpt_compose': (_i, [_vp]),
+    'mpt_compose_stats': (_i, [_vp, C.POINTER(ComposeInfo)]),
+    'mpt_get_model': (_i, [_vp, _fp, _ip, _i, C.POINTER(_i)]),
+    'mpt_compose_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_compose_plan': (_i, [_ip, _ip, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _i]),
     'mpt_host_alloc': (_vp, [C.c_size_t]),
     'mpt_host_free': (None, [_vp]),
     'mpt_get_counters': (_i, [_vp, C.POINTER(Counters)]),
@@ -278,6 +294,23 @@ def fptr(a):
 
 def iptr(a):
     return a.ctypes.data_as(_ip)
+
+
+def compose_plan(faces, dirty=None):
+    '''mpt_compose_plan (no context, no GPU): per-object face counts and dirty flags (None: all) -> (first faces [nobj + 1],
+    [(first workgroup, workgroups), ...] of the launch); ValueError for counts that name no layout'''
+    f = np.ascontiguousarray(faces, np.int32).reshape(-1)
+    d = None if dirty is None else np.ascontiguousarray(dirty, np.int32).reshape(-1)
+    if d is not None and d.shape != f.shape:
+        raise ValueError('%d dirty flags for %d objects' % (d.size, f.size))
+    n = int(f.size)
+    first, begin, count = np.zeros(n + 1, np.int64), np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+    p64 = C.POINTER(C.c_int64)
+    nr = load_library().mpt_compose_plan(iptr(f), None if d is None else iptr(d), n, first.ctypes.data_as(p64), begin.ctypes.data_as(p64),
+                                         count.ctypes.data_as(p64), n)
+    if nr < 0:
+        raise ValueError('face counts name no layout (negative, or more than 2^31 / 3 faces)')
+    return first, [(int(begin[r]), int(count[r])) for r in range(nr)]
 
 
 def devices_isolated():

@@ -152,6 +152,7 @@ extern "C" mpt_ctx *mpt_create(const mpt_caps *caps, int device) {
     *c->display.exposure.host = 1.0f;
     if (c->noise.stats.create(1)) return bail("pinned noise statistics");
     if (c->adapt.rec.create(1)) return bail("pinned selection record");
+    if (c->compose.bounds.create(6)) return bail("pinned scene bounds");
     hipMemsetAsync(c->d_counters, 0, MPT_COUNTER_WORDS * sizeof(unsigned long long), c->stream);
     {   // unset materials: factor 0 (field-zero, mtllib.py:12-13), texture -1 (deviation Q6)
         std::vector<MptMaterial> z((size_t)c->caps.max_materials + 1);
@@ -421,6 +422,8 @@ extern "C" int mpt_load_model(mpt_ctx *c, const float *verts, const int32_t *mtl
     }
     c->tree_valid = false;
     c->d_model_stale = true;
+    c->h_model_stale = false;                    // the device model belongs to the host copy again ...
+    c->compose.out_valid = false;                // ... so the next mpt_compose writes all of it
     return 0;
 }
 

@@ -81,6 +81,12 @@ MPT_KERNEL_API hipError_t mpt_launch_adapt_select(const MptVec4 *film, const Mpt
                                                   unsigned long long *ballot, int *count, int32_t *list, long long *total_host, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_adapt_fold(MptVec4 *film, MptVec4 *mark /* or NULL */, const int32_t *list, int count, const MptVec4 *samples,
                                                 int nframes, int remark, hipStream_t);
+// compose.hip: meshes of the pool placed by the object table, written as the model the tree builders read, and its bounding box
+// (mpt_compose); part holds 6 floats per mpt_compose_groups(vertices) workgroups
+MPT_KERNEL_API size_t mpt_compose_groups(size_t nverts);
+MPT_KERNEL_API hipError_t mpt_launch_compose(const float *pool, const MptComposeObj *objs, const int *first, int nobj, int nverts,
+                                             const MptComposeRun *runs, int nruns, int blocks, int all, unsigned epoch, float *out,
+                                             int *mtlids, float *part, float *bounds_host, hipStream_t);
 
 // on-GPU LBVH build (lbvh_build.hip)
 struct MptLbvhBuffers {
@@ -322,6 +328,26 @@ struct MPT_INTERNAL MptModelBufs {         // the device copy of the model
     }
 };
 
+// Scene composition's device memory (scene_compose.cpp): the mesh pool grows by copying into a larger buffer (grow_pool), the table
+// and the launch's workspace are sized by the objects and the output
+struct MPT_INTERNAL MptComposeBufs {
+    DevBuf<float> pool;                  // object-space records [vertex][8] of every mesh, back to back
+    DevBuf<MptComposeObj> objs;          // the object table
+    DevBuf<int> first;                   // the objects' first output faces, apart: what the lanes' binary search reads
+    DevBuf<MptComposeRun> runs;          // a partial launch's runs of workgroups
+    DevBuf<float> part;                  // 6 floats per workgroup of the output: min3, max3 of its positions
+    int reserve_table(size_t nobj) { return objs.reserve(nobj) || first.reserve(nobj) || runs.reserve(nobj); }
+    int grow_pool(size_t floats, size_t used, hipStream_t stream) {          // keeps the first `used` floats
+        if (floats <= pool.cap) return 0;
+        DevBuf<float> bigger;
+        if (bigger.reserve(std::max(floats, pool.cap * 2))) return 1;
+        if (used) HIP_TRY(hipMemcpyAsync(bigger, pool, used * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        pool.swap(bigger);
+        return 0;
+    }
+};
+
 struct MPT_INTERNAL MptLbvhBufs {          // workspace and result of the device LBVH build (lbvh_build.hip)
     DevBuf<float> d_cen; DevBuf<int> d_bounds, d_depth;
     DevBuf<unsigned long long> d_keys_in, d_keys_out;
@@ -532,6 +558,7 @@ struct mpt_ctx {
     float wide_ratio = 1.f;                           // expected fetches per ray, wide / binary (surface-area sums)
     MappedBuf<int> sah_mail;                          // [32]: the SAH pass's per-level hand-back (sah_build.hip plan kernel)
     MptSahStats sah_stats{};                          // what the last device SAH pass did
+    bool h_model_stale = false;                       // the host copy (verts, mtlids) is behind the device's, which mpt_compose wrote: model_on_host fetches it
     bool d_model_stale = true;                        // the device copy of the model (d_verts, d_mtlids) is behind the host's: the next device build uploads
     double build_phase_us[6] = { 0, 0, 0, 0, 0, 0 };   // upload | LBVH | SAH pass | triangle records | 4-wide collapse | total (host clock)
     int sah_fallback = 0;                             // last build: the device SAH pass gave up (1: error, 2: depth) and the host pass ran
@@ -590,6 +617,20 @@ struct mpt_ctx {
         MptLaunchTimer select_timer, render_timer;       // mpt_adapt_select: {before the kernels, after them} per call; mpt_render_selected: the same around a call's launches
         explicit Adapt(MptEventPool &ev) : select_timer(2, ev), render_timer(2, ev) {}
     } adapt{events};
+    struct MptComposeMesh { size_t vert; int nfaces; };  // a mesh of the pool: its first vertex and its faces
+    struct MPT_INTERNAL Compose {                        // scene composition on the device (mpt_mesh_add, mpt_object_*, mpt_compose)
+        std::vector<MptComposeMesh> meshes; size_t pool_verts = 0;
+        std::vector<MptComposeObj> objs;                 // the table as the host keeps it (first_face as of the last layout)
+        std::vector<unsigned char> dirty;                // per object: changed since the last mpt_compose
+        bool relayout = true;                            // objects were added or dropped: the next mpt_compose writes everything
+        bool out_valid = false;                          // dmodel holds the last mpt_compose's output (mpt_load_model takes the buffers back)
+        unsigned epoch = 0;                              // counts the mpt_compose calls (MptComposeObj::epoch)
+        MptComposeBufs bufs;
+        MappedBuf<float> bounds;                         // {min3, max3} of the composed positions
+        mpt_compose_info stats{};
+        MptLaunchTimer timer;                            // mpt_compose: {before the compose kernel, after the fold} per call
+        explicit Compose(MptEventPool &ev) : timer(2, ev) {}
+    } compose{events};
     MptDoorInput door;                                   // mpt_display_eval, mpt_noise_eval, mpt_denoise_eval: the caller's accumulators on the device (grown on demand)
     MptLaunchTimer render_timer{2, events};              // PathEngine launches: {kernel start, kernel end}
     MptLaunchTimer denoise_timer{2, events};             // mpt_get_denoised: {before the prologue, after the epilogue} per call
@@ -649,6 +690,9 @@ MPT_INTERNAL int check_watchdog(mpt_ctx *c);   // after a synchronise: did a per
 MPT_INTERNAL int read_back(mpt_ctx *c, void *out, const void *dev, size_t bytes);   // device -> caller buffer on the main stream, blocking
 MPT_INTERNAL void *caller_alias(const mpt_ctx *c, void *p, size_t bytes);           // the device alias of a page-locked caller array of ours, or null
 MPT_INTERNAL int timer_readout(mpt_ctx *c, MptLaunchTimer &timer, double *ms0, double *ms1, int *launches, bool render_streams = false);
+
+// scene_compose.cpp
+MPT_INTERNAL int model_on_host(mpt_ctx *c);   // before anything reads c->verts / c->mtlids: fetch them once if mpt_compose made the model
 
 // film_read.cpp
 MPT_INTERNAL int check_pass(mpt_ctx *c, int pass);

@@ -183,3 +183,16 @@ struct MptDisplayArgs {
     float exposure;                          // a manual exposure (the metered one is read from the device)
     float white2, inv_gamma;                 // white * white and 1 / gamma, in f32
 };
+
+// scene composition (compose.hip): one object of the table -- a mesh of the pool placed by a world matrix.  `epoch` names the
+// mpt_compose call that last changed the record: a partial launch rewrites the output of the objects that carry its epoch
+struct alignas(16) MptComposeObj {          // 160 bytes: the matrix is read as 16-byte words
+    int32_t first_face, nfaces;              // the object's range of output faces
+    int32_t mesh_vert;                       // its mesh's first vertex in the pool (nfaces * 3 records from there)
+    int32_t mtlid;
+    uint32_t epoch;
+    int32_t pad[3];
+    double world[16];                        // row-major, as numpy holds it
+};
+// a run of consecutive workgroups of a partial launch: output workgroups [wg, wg + next run's `block` - block) are the launch's blocks from `block`
+struct MptComposeRun { int32_t wg, block; };

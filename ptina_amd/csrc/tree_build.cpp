@@ -265,6 +265,7 @@ static int reserve_records(mpt_ctx *c, int n) {
 }
 
 static int build_tree_host(mpt_ctx *c) {
+    if (model_on_host(c)) return 1;
     const int n = c->nfaces;
     const float *V = c->verts.data();
     auto pos = [&](int f, int k) { return V + ((size_t)f * 3 + k) * 8; };
@@ -457,6 +458,7 @@ static int build_sah_device(mpt_ctx *c) {
 // SAH re-partition of the leaves for the fast build: host pass over the leaf order (exact sweep up to sah_exact_max leaves)
 static int build_sah_host(mpt_ctx *c) {
     const int n = c->nfaces, ni = n - 1;
+    if (model_on_host(c)) return 1;
     c->h_leaf.resize(n);
     HIP_TRY(hipMemcpy(c->h_leaf.data(), c->lbvh.d_leaf, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     SahBuild sb;

@@ -1,11 +1,15 @@
 '''
 triangle mesh model storage (reference model.py).  The mesh is kept on the host until
-BVHTree().build() packs it, leaf-ordered, into the device records (csrc/mpt_types.h).
+BVHTree().build() packs it, leaf-ordered, into the device records (csrc/mpt_types.h) -- or, through
+load_meshes / add_mesh / add_object / compose, object-space meshes and an object table are kept on the device
+and composed there into the model the build reads (csrc/compose.hip).
 '''
+
+import ctypes as C
 
 from .common import *                 # noqa: F401,F403
 from .common import Singleton, register, ctx, np
-from ._lib import fptr, iptr
+from ._lib import fptr, iptr, ComposeInfo
 
 
 @register
@@ -15,12 +19,19 @@ class ModelPool(metaclass=Singleton):
         self._nfaces = 0
         self._vertices = np.zeros((0, 8), np.float32)
         self._mtlids = np.zeros(0, np.int32)
+        self._composed = False           # the model is the device's composition: to_numpy fetches it
+        self._mesh_faces = []            # faces of every mesh of the device's pool
+        self._obj_mesh = []              # the mesh of every object of the device's table
 
     @property
     def nfaces(self):
         return self._nfaces
 
     def to_numpy(self, id=None):
+        if self._composed:               # (the library fetches its host copy of a composed model once, when somebody asks)
+            arr, mtlids = np.empty((self._nfaces * 3, 8), np.float32), np.empty(self._nfaces, np.int32)
+            ctx().call('mpt_get_model', fptr(arr), iptr(mtlids), self._nfaces, None)
+            return arr, mtlids
         return self._vertices.copy(), self._mtlids.copy()
 
     def from_numpy(self, arr, mtlids):
@@ -29,6 +40,108 @@ class ModelPool(metaclass=Singleton):
         ctx().call('mpt_load_model', fptr(arr), iptr(mtlids), int(mtlids.shape[0]))
         self._vertices, self._mtlids = arr, mtlids
         self._nfaces = int(mtlids.shape[0])
+        self._composed = False
+
+    # ---- composition on the device (no reference counterpart: its add-on composes on the host at every scene change,
+    #      blender.py:555-571; the arithmetic is multimesh.py:58-65)
+    @staticmethod
+    def _world(world):
+        w = np.ascontiguousarray(world, np.float64)
+        if w.shape != (4, 4):
+            raise ValueError('world matrix must be 4x4, got shape %s' % (w.shape,))
+        if not np.isfinite(w).all():
+            raise ValueError('world matrix has an entry that is not finite')
+        return w
+
+    def _object(self, obj):
+        if not 0 <= int(obj) < len(self._obj_mesh):
+            raise ValueError('unknown object %r (%d objects)' % (obj, len(self._obj_mesh)))
+        return int(obj)
+
+    def add_mesh(self, p, n, t=None):
+        '''a mesh for the device's pool: positions p [k,3,3], normals n [k,3,3], texcoords t [k,3,2] or None (zeros per corner, as
+        multimesh.compose_multiple_meshes decides), in object space.  Stored as f32: f64 input is rounded here, at the upload,
+        where compose_multiple_meshes + load round after the transform.  Returns the mesh id'''
+        p, n = np.asarray(p), np.asarray(n)
+        k = p.shape[0] if p.ndim else -1
+        if p.shape != (k, 3, 3) or n.shape != (k, 3, 3):
+            raise ValueError('positions and normals must be [k,3,3], got %s and %s' % (p.shape, n.shape))
+        t = np.zeros((k, 3, 2), np.float32) if t is None else np.asarray(t)
+        if t.shape != (k, 3, 2):
+            raise ValueError('texcoords must be [%d,3,2], got %s' % (k, t.shape))
+        if k >= self.size:
+            raise ValueError('too many faces: a mesh of %d, room for fewer than %d' % (k, self.size))
+        rec = np.ascontiguousarray(np.concatenate([p.reshape(k * 3, 3), n.reshape(k * 3, 3), t.reshape(k * 3, 2)], axis=1), np.float32)
+        mesh = C.c_int(-1)
+        ctx().call('mpt_mesh_add', fptr(rec), k, C.byref(mesh))
+        self._mesh_faces.append(k)
+        assert mesh.value == len(self._mesh_faces) - 1
+        return mesh.value
+
+    def add_object(self, mesh, world, mtlid=None):
+        '''an object of the table: mesh `mesh` placed by the 4x4 matrix `world`, with material id mtlid (None: -1, the default
+        material).  Objects are composed in the order they were added.  Returns the object id'''
+        if not 0 <= int(mesh) < len(self._mesh_faces):
+            raise ValueError('unknown mesh %r (%d meshes)' % (mesh, len(self._mesh_faces)))
+        w = self._world(world)
+        total = sum(self._mesh_faces[m] for m in self._obj_mesh) + self._mesh_faces[int(mesh)]
+        if total >= self.size:
+            raise ValueError('too many faces: %d with this object, room for fewer than %d' % (total, self.size))
+        obj = C.c_int(-1)
+        ctx().call('mpt_object_add', int(mesh), w.ctypes.data_as(C.POINTER(C.c_double)), -1 if mtlid is None else int(mtlid), C.byref(obj))
+        self._obj_mesh.append(int(mesh))
+        assert obj.value == len(self._obj_mesh) - 1
+        return obj.value
+
+    def set_world(self, obj, world):
+        '''move an object; the next compose() rewrites its faces only'''
+        obj, w = self._object(obj), self._world(world)
+        ctx().call('mpt_object_set_world', obj, w.ctypes.data_as(C.POINTER(C.c_double)))
+
+    def set_material(self, obj, mtlid):
+        obj = self._object(obj)
+        ctx().call('mpt_object_set_material', obj, -1 if mtlid is None else int(mtlid))
+
+    def clear_objects(self):
+        '''drop the objects; the meshes stay in the pool'''
+        ctx().call('mpt_scene_clear', 0)
+        self._obj_mesh = []
+
+    def clear_meshes(self):
+        '''drop the objects and the meshes'''
+        ctx().call('mpt_scene_clear', 1)
+        self._obj_mesh, self._mesh_faces = [], []
+
+    def compose(self):
+        '''write the objects, in order, as the model BVHTree().build() reads -- on the device; what load(*compose_multiple_meshes(...))
+        leaves, without the arrays crossing to the host and back.  After set_world / set_material only the changed objects' faces
+        are rewritten'''
+        ctx().call('mpt_compose')
+        self._nfaces = sum(self._mesh_faces[m] for m in self._obj_mesh)
+        self._composed = True
+
+    def compose_stats(self):
+        '''_lib.ComposeInfo: faces, faces the last compose() wrote, objects it found changed, fetches of the host copy, bounding sphere'''
+        info = ComposeInfo()
+        ctx().call('mpt_compose_stats', C.byref(info))
+        return info
+
+    def load_meshes(self, primitives):
+        '''the reference's list of (p, n, t, w, m) tuples (multimesh.compose_multiple_meshes's argument) composed on the device:
+        drops what the pool and the table held, adds a mesh per distinct (p, n, t) -- tuples that share the same array objects
+        share one mesh -- and an object per tuple, and composes.  Returns the object ids, in order'''
+        primitives = list(primitives)
+        if not primitives:
+            raise ValueError('no primitives')
+        self.clear_meshes()
+        meshes, objs = {}, []
+        for p, n, t, w, m in primitives:
+            key = (id(p), id(n), id(t))
+            if key not in meshes:
+                meshes[key] = self.add_mesh(p, n, t)
+            objs.append(self.add_object(meshes[key], w, m))
+        self.compose()
+        return objs
 
     def load(self, arr, mtlids=None):
         '''reference model.py:62-86: [3n,8] array (pos3 nrm3 uv2), or an OBJ-style dict, or a path'''

@@ -23,6 +23,9 @@ _PASS_THROUGH = {
     'set_world_light': ('WorldLight', 'set', ('fac', 'tex')),
     'add_light': ('LightPool', 'add', ('world', 'color', 'size', 'type')),
     'load_model': ('ModelPool', 'load', ('vertices', 'mtlids')),
+    # (no reference counterparts: the meshes and the object table stay on the device, model.py)
+    'load_meshes': ('ModelPool', 'load_meshes', ('primitives',)),
+    'set_object_world': ('ModelPool', 'set_world', ('obj', 'world')),
     'load_images': ('ImagePool', 'load', ('images',)),
     'load_materials': ('MaterialPool', 'load', ('materials',)),
     'build_tree': ('BVHTree', 'build', ()),
@@ -60,6 +63,12 @@ def init():
 def synchronize():
     '''the reference forces a device sync by reading a field back (worker.py:17-18); here the C ABI has the call'''
     ctx().call('mpt_synchronize')
+
+
+def compose_model():
+    '''ModelPool().compose(): after set_object_world, rewrite the moved objects' faces on the device; build_tree() follows (no
+    reference counterpart: its add-on runs compose_multiple_meshes + load_model over everything again)'''
+    ModelPool().compose()
 
 
 def render(aa=True):
