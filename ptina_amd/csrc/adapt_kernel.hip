@@ -15,12 +15,6 @@
 #include <hip/hip_runtime.h>
 #include "path_common.h"
 
-#if MPT_STRICT
-#define MPT_SUFFIX(x) x##_strict
-#else
-#define MPT_SUFFIX(x) x##_fast
-#endif
-
 template <int STACK>
 __global__ __launch_bounds__(MPT_BLOCK) void MPT_SUFFIX(adapt_render_kernel)(const MptRenderParams p, const int32_t *__restrict__ list, int count,
                                                                              MptVec4 *__restrict__ samples) {
@@ -45,7 +39,5 @@ MPT_KERNEL_API hipError_t MPT_SUFFIX(mpt_launch_adapt_render)(const MptRenderPar
     if (items <= 0) return hipSuccess;
     if (items > 0x7fffffffLL) return hipErrorInvalidConfiguration;
     const unsigned grid = (unsigned)((items + MPT_BLOCK - 1) / MPT_BLOCK);
-    if (stack <= 32) hipLaunchKernelGGL((MPT_SUFFIX(adapt_render_kernel)<32>), dim3(grid), dim3(MPT_BLOCK), 0, stream, *p, list, count, samples);
-    else hipLaunchKernelGGL((MPT_SUFFIX(adapt_render_kernel)<64>), dim3(grid), dim3(MPT_BLOCK), 0, stream, *p, list, count, samples);
-    return hipGetLastError();
+    return launch_by_stack<MPT_SUFFIX(adapt_render_kernel)<32>, MPT_SUFFIX(adapt_render_kernel)<64>>(stack, grid, stream, *p, list, count, samples);
 }

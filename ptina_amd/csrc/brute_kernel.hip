@@ -13,12 +13,6 @@
 #include <hip/hip_runtime.h>
 #include "path_common.h"
 
-#if MPT_STRICT
-#define MPT_SUFFIX(x) x##_strict
-#else
-#define MPT_SUFFIX(x) x##_fast
-#endif
-
 // BruteEngine._render, engine/brute.py:62-74, for the p.nframes frames of a batch
 template <int STACK>
 __global__ __launch_bounds__(MPT_BLOCK) void MPT_SUFFIX(brute_kernel)(const MptRenderParams p) {
@@ -40,7 +34,5 @@ __global__ __launch_bounds__(MPT_BLOCK) void MPT_SUFFIX(brute_kernel)(const MptR
 }
 
 MPT_KERNEL_API hipError_t MPT_SUFFIX(mpt_launch_brute)(const MptRenderParams *p, int grid, int stack, hipStream_t stream) {
-    if (stack <= 32) hipLaunchKernelGGL((MPT_SUFFIX(brute_kernel)<32>), dim3(grid), dim3(MPT_BLOCK), 0, stream, *p);
-    else hipLaunchKernelGGL((MPT_SUFFIX(brute_kernel)<64>), dim3(grid), dim3(MPT_BLOCK), 0, stream, *p);
-    return hipGetLastError();
+    return launch_by_stack<MPT_SUFFIX(brute_kernel)<32>, MPT_SUFFIX(brute_kernel)<64>>(stack, grid, stream, *p);
 }

@@ -99,6 +99,11 @@ static inline int mpt_lds4_fit_bytes(int n, int nwide, int wide_stack, int lds_n
     return bytes <= MPT_LDS_BUDGET ? bytes : 0;                  /* the CU's 160 KiB */
 }
 
+/* Levels of the per-lane traversal stack of the kernels that gather the binary tree -- the gather render kernels, preview, brute,
+ * Metropolis and the list pass, two instantiations each (path_common.h launch_by_stack): the sentinel and one pending sibling per
+ * level of a tree `depth` levels deep, in 32 levels if they fit and in 64 otherwise */
+MPT_LDS_FN int mpt_gather_stack_levels(int depth) { return depth + 2 <= 32 ? 32 : 64; }
+
 /* ---------------------------------------------------------------- which kernel a render launch gets
  * The values are the public "last_kernel" numbers (include/miptina.h); 3 and 4 are retired. */
 enum { MPT_KERNEL_GATHER = 0, MPT_KERNEL_LDS = 1, MPT_KERNEL_WIDE = 2, MPT_KERNEL_LDS4 = 5 };

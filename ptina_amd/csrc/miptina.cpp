@@ -2,8 +2,9 @@
 //
 // Owns the device state of one PTina "scene" (the singletons of ptina/things.py:20-28 collapsed
 // into one context), uploads the scene, advances the Sobol sampler, batches enqueued frames into
-// single launches.  The film's read-backs are in film_read.cpp, the BVH builders in tree_build.cpp,
-// the RCCL film gather in comm.cpp.  No PyTorch, no Python: plain HIP runtime calls.
+// single launches.  The engines that launch at the call (preview, Metropolis, brute force, the list pass) are in engines.cpp, the
+// film's read-backs in film_read.cpp, the measurement and test doors in measure.cpp, the BVH builders in tree_build.cpp, the RCCL
+// film gather in comm.cpp.  No PyTorch, no Python: plain HIP runtime calls.
 
 #include "miptina_ctx.h"
 
@@ -547,7 +548,7 @@ extern "C" int mpt_sobol_init(mpt_ctx *c, const int32_t *V, int rows, int dim) {
     return 0;
 }
 
-static int sobol_advance(mpt_ctx *c, int count, int keep, hipStream_t stream = nullptr, float *P = nullptr) {
+int sobol_advance(mpt_ctx *c, int count, int keep, hipStream_t stream, float *P) {
     // keep = number of trailing frames whose points are written to P[0..keep)
     if (!stream) stream = c->stream;
     if (!P) P = c->sP;
@@ -595,9 +596,9 @@ extern "C" int mpt_sobol_get(mpt_ctx *c, int32_t *X, float *P, int32_t *time) {
 
 // ------------------------------------------------------------------ rendering
 // the part of the launch parameters that describes the scene's lights, world light, camera, materials and images: what lights_hit,
-// lights_sample, image_sample, world_at, material_get and camera_generate read (fill_params; mpt_unit_eval, which needs no film,
+// lights_sample, image_sample, world_at, material_get and camera_generate read (fill_params; measure.cpp's test door of the device functions, which needs no film,
 // sampler or tree)
-static int fill_scene_params(mpt_ctx *c, MptRenderParams &p) {
+int fill_scene_params(mpt_ctx *c, MptRenderParams &p) {
     p.nlights = (int)c->h_lights.size(); p.world_tex = c->world_tex;
     memcpy(p.world_fac, c->world_fac, sizeof p.world_fac);
     memcpy(p.v2w, c->v2w, sizeof p.v2w);
@@ -616,7 +617,14 @@ static int check_ready(const mpt_ctx *c) {
     return 0;
 }
 
-static int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes) {
+// entry of the calls that render frames of the film (mpt_render; engines.cpp)
+int render_entry(mpt_ctx *c, int nframes) {
+    if (!c) return fail("null context");
+    if (nframes < 0) return fail("nframes must be >= 0");
+    return check_ready(c);
+}
+
+int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes) {
     if (check_ready(c)) return 1;
     // the production kernels address a frame's Sobol row and a triangle's shading record by 32-bit offsets from a scalar base, and
     // multiply frame x dimension in 24 bits (lane_draws, shade_rec_load)
@@ -662,13 +670,6 @@ static int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes) {
     p.watchdog = c->watchdog.dev;
     return fill_scene_params(c, p);
 }
-
-// levels of the per-lane traversal stack of the gather, preview, Metropolis and brute-force kernels (two instantiations each)
-static int gather_stack_levels(const mpt_ctx *c) {
-    return ((c->opt.mode == MPT_MODE_STRICT ? c->tree_depth : c->fast_depth) + 2 <= 32) ? 32 : 64;
-}
-
-static int mlt_flush(mpt_ctx *c);
 
 // ------------------------------------------------------------------ mpt_flush, step by step
 // where a batch runs: its slot of the ring, the stream of its render kernel and the stream its points are prepared on
@@ -933,16 +934,14 @@ static int launch_render(mpt_ctx *c, const MptRenderParams &p, const BatchSlot &
                          int wide_blocks) {
     // SHADE compiled for what the scene uses: the LDS-resident 4-wide kernel has a plain instantiation, every other kernel the generic code
     const int shade_feat = kc.kernel == MPT_KERNEL_LDS4 ? shade_feat_instantiation(scene_feat_now(c), c->opt.shade_spec) : MPT_FEAT_GENERIC;
-    const int stack = gather_stack_levels(c);
     MptTimedSpan span(c->render_timer, s.rs);
     HIP_TRY(span.begun);
     switch (kc.kernel) {
     case MPT_KERNEL_LDS4: HIP_TRY(mpt_launch_render_lds4(&p, launch_cus, lds_block, (size_t)kc.lds_bytes, c->opt.count, shade_feat, s.rs)); break;
     case MPT_KERNEL_LDS: HIP_TRY(mpt_launch_render_lds(&p, launch_cus, lds_block, (size_t)kc.lds_bytes, c->opt.count, s.rs)); break;
     case MPT_KERNEL_WIDE: HIP_TRY(mpt_launch_render_wide(&p, wide_blocks, c->opt.count, c->opt.wide_quant, s.rs)); break;
-    default:    // MPT_KERNEL_GATHER: the binary tree, in either build
-        if (!s.fast) HIP_TRY(mpt_launch_render_strict(&p, p.ntiles, stack, c->opt.count, s.rs));
-        else HIP_TRY(mpt_launch_render_fast(&p, launch_cus, stack, c->opt.count, s.rs));
+    default:    // MPT_KERNEL_GATHER: the binary tree, in either build (strict: a workgroup per tile; fast: persistent workgroups on the launch's CUs)
+        HIP_TRY(MPT_LAUNCHER(c, mpt_launch_render)(&p, s.fast ? launch_cus : p.ntiles, gather_stack_levels(c), c->opt.count, s.rs));
     }
     c->last_shade_feat = shade_feat;
     c->last_kernel = kc.kernel;
@@ -979,7 +978,7 @@ static int behind_launch(mpt_ctx *c, const MptRenderParams &p, const BatchSlot &
 
 extern "C" int mpt_flush(mpt_ctx *c) {
     if (!c) return fail("null context");
-    if (c->mlt.pending && mlt_flush(c)) return 1;    // (Metropolis iterations and PathEngine frames are never pending together)
+    if (c->mlt.pending && mlt_flush(c)) return 1;    // engines.cpp (its iterations and PathEngine frames are never pending together)
     if (c->pending == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
     const int B = c->pending;
@@ -1011,10 +1010,8 @@ extern "C" int mpt_flush(mpt_ctx *c) {
 }
 
 extern "C" int mpt_render(mpt_ctx *c, int nframes) {                           // path.py:75-77
-    if (!c) return fail("null context");
-    if (nframes < 0) return fail("nframes must be >= 0");
-    if (check_ready(c)) return 1;                     // fail at the call, not at the deferred launch
-    if (c->mlt.pending && mlt_flush(c)) return 1;     // the film sum follows call order: Metropolis iterations enqueued before go first
+    if (render_entry(c, nframes)) return 1;           // fail at the call, not at the deferred launch
+    if (c->mlt.pending && mlt_flush(c)) return 1;     // the film sum follows call order: iterations of engines.cpp's chains enqueued before go first
     while (nframes > 0) {
         int room = c->opt.batch - c->pending;
         int take = std::min(room, nframes);
@@ -1022,157 +1019,6 @@ extern "C" int mpt_render(mpt_ctx *c, int nframes) {                           /
         nframes -= take;
         if (c->pending >= c->opt.batch && mpt_flush(c)) return 1;
     }
-    return 0;
-}
-
-extern "C" int mpt_render_preview(mpt_ctx *c, int nframes) {                   // preview.py:18-41
-    if (use(c)) return 1;
-    while (nframes > 0) {
-        int B = std::min(nframes, MPT_MAX_BATCH);
-        MptRenderParams p;
-        if (fill_params(c, p, B)) return 1;
-        if (sobol_advance(c, B, B)) return 1;
-        p.chunk = B; p.nchunks = 1;
-        const int stack = gather_stack_levels(c);
-        if (p.ntiles) {
-            if (c->opt.mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_preview_strict(&p, p.ntiles, stack, c->stream));
-            else HIP_TRY(mpt_launch_preview_fast(&p, p.ntiles, stack, c->stream));
-        }
-        nframes -= B;
-    }
-    return 0;
-}
-
-// ------------------------------------------------------------------ Metropolis engine (MLTPathEngine, engine/mltpath.py)
-// Everything runs on the main stream, which every PathEngine launch is ordered behind (mpt_flush) and which the next one waits
-// for (main_dirty -> ev_main), so PathEngine frames and Metropolis iterations add to film pass 0 in call order.
-enum { MPT_MLT_SLAB_RECORDS = 1 << 24 };      // splat records per launch (20 B each, twice for the sort): larger requests are split
-
-static int mlt_check(mpt_ctx *c) {
-    if (c->mlt.n <= 0) return fail("Metropolis engine not reset: call mpt_mlt_reset first");
-    return 0;
-}
-
-// launch the enqueued iterations: chain kernel + splat pass per slab-sized piece, in iteration order
-static int mlt_flush(mpt_ctx *c) {
-    int n = c->mlt.pending;
-    c->mlt.pending = 0;
-    if (n <= 0) return 0;
-    HIP_TRY(hipSetDevice(c->device));
-    MptRenderParams p;
-    if (fill_params(c, p, 1)) return 1;
-    const int nch = c->mlt.n;
-    const int kmax = std::max(1, (int)(MPT_MLT_SLAB_RECORDS / nch));
-    const int K0 = std::min(n, kmax);
-    const size_t recs = (size_t)K0 * nch, npix = (size_t)c->nx * c->ny;
-    if (recs > c->mlt.slab.cap || npix > c->mlt.slab.runs_cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->mlt.slab.reserve(recs, npix)) return 1;
-    }
-    const int stack = gather_stack_levels(c);
-    while (n > 0) {
-        const int K = std::min(n, kmax);
-        MptMltArgs a;
-        a.X = c->mlt.X; a.L = c->mlt.L; a.bit = c->mlt.bit; a.keys = c->mlt.slab.keys; a.vals = c->mlt.slab.vals;
-        a.nchains = nch; a.t0 = c->mlt.iter; a.K = K; a.seed = c->mlt.seed; a.lsp = c->mlt.lsp; a.sigma = c->mlt.sigma;
-        MptTimedSpan span(c->mlt.timer, c->stream);
-        HIP_TRY(span.begun);
-        if (c->opt.mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_mlt_chain_strict(&p, &a, stack, c->stream));
-        else HIP_TRY(mpt_launch_mlt_chain_fast(&p, &a, stack, c->stream));
-        HIP_TRY(span.mark());
-        HIP_TRY(mpt_launch_mlt_splat(c->fb.film[0], c->mlt.slab.keys, c->mlt.slab.vals, c->mlt.slab.keys_sorted, c->mlt.slab.vals_sorted,
-                                     c->mlt.slab.tmp, c->mlt.slab.tmp.cap, c->mlt.slab.runs, K * nch, (int)npix, c->stream));
-        HIP_TRY(span.end());
-        c->mlt.iter += K;
-        n -= K;
-    }
-    c->film_version++;           // pass 0 has changed: an early image of an earlier PathEngine launch is stale
-    c->main_dirty = true;        // the next PathEngine launch waits for these
-    return 0;
-}
-
-extern "C" int mpt_mlt_reset(mpt_ctx *c, int nchains, uint32_t seed) {         // mltpath.py:31-37
-    if (use(c)) return 1;
-    if (nchains <= 0 || nchains > (1 << 24)) return fail("nchains %d outside [1, 2^24]", nchains);
-    if (nchains != c->mlt.n) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->mlt.X.release(); c->mlt.L.release(); c->mlt.bit.release(); c->mlt.n = 0;
-        if (c->mlt.X.reserve((size_t)nchains * 2 * 32) || c->mlt.L.reserve((size_t)nchains * 3) || c->mlt.bit.reserve((size_t)nchains)) return 1;
-        c->mlt.n = nchains;
-    }
-    c->mlt.seed = seed; c->mlt.iter = 0; c->mlt.pending = 0;
-    HIP_TRY(mpt_launch_mlt_reset(c->mlt.X, c->mlt.L, c->mlt.bit, nchains, seed, c->stream));
-    return 0;
-}
-
-extern "C" int mpt_mlt_set_param(mpt_ctx *c, float lsp, float sigma) {       // mltpath.py:18-27: LSP[None], Sigma[None]
-    if (use(c)) return 1;                   // iterations enqueued so far run with the parameters they were enqueued under
-    c->mlt.lsp = lsp; c->mlt.sigma = sigma;
-    return 0;
-}
-
-extern "C" int mpt_mlt_render(mpt_ctx *c, int iterations) {                    // mltpath.py:85-87
-    if (!c) return fail("null context");
-    if (iterations < 0) return fail("iterations must be >= 0");
-    if (mlt_check(c)) return 1;
-    if (c->nx <= 0) return fail("film size not set: call set_size() first");
-    if (!c->tree_valid) return fail("BVH not built: call build_tree() after load_model()");
-    if (c->stripe_w != 0 || c->x0 != 0 || c->x1 != c->nx || c->comm)
-        return fail("the Metropolis engine renders the whole film on one GPU: no slab / stripe split or communicator may be set");
-    if ((long long)c->mlt.iter + c->mlt.pending + iterations >= (1ll << 31)) return fail("Metropolis iteration counter would overflow");
-    if (c->pending && mpt_flush(c)) return 1;      // PathEngine frames enqueued before go first
-    c->mlt.pending += iterations;
-    return 0;
-}
-
-extern "C" int mpt_mlt_get_state(mpt_ctx *c, float *X, float *L, int *iteration) {
-    if (use_ro(c)) return 1;
-    if (mpt_flush(c)) return 1;
-    if (mlt_check(c)) return 1;
-    const size_t n = (size_t)c->mlt.n;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (X) {
-        std::vector<float> both(n * 2 * 32);
-        std::vector<int32_t> bit(n);
-        HIP_TRY(hipMemcpy(both.data(), c->mlt.X, both.size() * sizeof(float), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(bit.data(), c->mlt.bit, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; i++) memcpy(X + i * 32, both.data() + ((size_t)(bit[i] & 1) * n + i) * 32, 32 * sizeof(float));
-    }
-    if (L) HIP_TRY(hipMemcpy(L, c->mlt.L, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (iteration) *iteration = c->mlt.iter;
-    return 0;
-}
-
-extern "C" int mpt_mlt_set_state(mpt_ctx *c, const float *X, const float *L, int iteration) {
-    if (use(c)) return 1;
-    if (mlt_check(c)) return 1;
-    if (!X || !L || iteration < 0) return fail("mpt_mlt_set_state: X and L must be given and iteration >= 0");
-    const size_t n = (size_t)c->mlt.n;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(c->mlt.X, X, n * 32 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->mlt.L, L, n * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(c->mlt.bit, 0, n * sizeof(int32_t)));
-    HIP_TRY(hipDeviceSynchronize());
-    c->mlt.iter = iteration;
-    return 0;
-}
-
-extern "C" int mpt_mlt_trace(mpt_ctx *c, const float *X, float *rgb, int n) {
-    if (use_ro(c)) return 1;
-    if (mpt_flush(c)) return 1;
-    if (n < 0 || (n > 0 && (!X || !rgb))) return fail("mpt_mlt_trace: bad arguments");
-    if (n == 0) return 0;
-    MptRenderParams p;
-    if (fill_params(c, p, 1)) return 1;
-    DevBuf<float> dX, drgb;
-    if (dX.reserve((size_t)n * 32) || drgb.reserve((size_t)n * 3)) return 1;
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(dX, X, (size_t)n * 32 * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = c->opt.mode == MPT_MODE_STRICT ? mpt_launch_mlt_trace_strict(&p, dX, drgb, n, gather_stack_levels(c), c->stream)
-                                                        : mpt_launch_mlt_trace_fast(&p, dX, drgb, n, gather_stack_levels(c), c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(rgb, drgb, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail("mpt_mlt_trace: %s", hipGetErrorString(e));
     return 0;
 }
 
@@ -1185,100 +1031,6 @@ int timer_readout(mpt_ctx *c, MptLaunchTimer &timer, double *ms0, double *ms1, i
     if (timer.drain(seg, launches)) return 1;
     if (ms0) *ms0 = seg[0];
     if (ms1) *ms1 = seg[1];
-    return 0;
-}
-
-extern "C" int mpt_mlt_kernel_time(mpt_ctx *c, double *chain_ms, double *splat_ms, int *launches) {
-    return use_ro(c) || timer_readout(c, c->mlt.timer, chain_ms, splat_ms, launches);
-}
-
-// ------------------------------------------------------------------ brute-force engine (BruteEngine, engine/brute.py)
-// Launched at the call, on the main stream like the Metropolis passes: use() has flushed the PathEngine frames and Metropolis
-// iterations enqueued before (the main stream waits for their render streams), and the next PathEngine launch waits for
-// this one (main_dirty -> ev_main), so frames of all three engines add to film pass 0 in call order.
-extern "C" int mpt_render_brute(mpt_ctx *c, int nframes) {                     // brute.py:24-26
-    if (!c) return fail("null context");
-    if (nframes < 0) return fail("nframes must be >= 0");
-    if (check_ready(c)) return 1;
-    if (use(c)) return 1;
-    while (nframes > 0) {
-        int B = std::min(nframes, (int)MPT_MAX_BATCH);
-        MptRenderParams p;
-        if (fill_params(c, p, B)) return 1;
-        if (sobol_advance(c, B, B)) return 1;
-        p.chunk = B; p.nchunks = 1;
-        const int stack = gather_stack_levels(c);
-        if (p.ntiles) {
-            MptTimedSpan span(c->brute_timer, c->stream);
-            HIP_TRY(span.begun);
-            if (c->opt.mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_brute_strict(&p, p.ntiles, stack, c->stream));
-            else HIP_TRY(mpt_launch_brute_fast(&p, p.ntiles, stack, c->stream));
-            HIP_TRY(span.end());
-            c->film_version++;       // pass 0 has changed: an early image of an earlier PathEngine launch is stale
-        }
-        nframes -= B;
-    }
-    c->main_dirty = true;            // the next PathEngine launch waits for these
-    return 0;
-}
-
-extern "C" int mpt_brute_kernel_time(mpt_ctx *c, double *ms, int *launches) {
-    return use_ro(c) || timer_readout(c, c->brute_timer, ms, nullptr, launches);
-}
-
-// ------------------------------------------------------------------ adaptive sampling: the list pass (PathEngine.render_selected)
-// nframes samples for the pixels of the selection only (mpt_adapt_select / mpt_adapt_set_list, film_read.cpp): the list render
-// kernel leaves every sample in fb.adapt_samples, the fold adds them to pass 0 in frame order.  Launched at the call, on the main
-// stream, with mpt_render_brute's bookkeeping, so frames of every engine add to film pass 0 in call order.
-enum : size_t { MPT_ADAPT_SAMPLE_BYTES = (size_t)64 << 20 };   // a launch's samples stay under this: a call's frames are split to fit
-
-// the launches of a call: `per` frames at most each; the first fold moves the mark (remark).  An empty selection launches
-// nothing, and the sampler still advances by the call's frames
-static int selected_launches(mpt_ctx *c, int nframes, int remark, int per) {
-    const int count = c->adapt.count;
-    const int stack = gather_stack_levels(c);
-    while (nframes > 0) {
-        const int B = std::min(nframes, per);
-        MptRenderParams p;
-        if (fill_params(c, p, B)) return 1;
-        if (sobol_advance(c, B, B)) return 1;
-        if (count > 0) {
-            if (c->opt.mode == MPT_MODE_STRICT) HIP_TRY(mpt_launch_adapt_render_strict(&p, c->fb.adapt.list, count, c->fb.adapt_samples, stack, c->stream));
-            else HIP_TRY(mpt_launch_adapt_render_fast(&p, c->fb.adapt.list, count, c->fb.adapt_samples, stack, c->stream));
-            HIP_TRY(mpt_launch_adapt_fold(c->fb.film[0], remark ? c->fb.mark.p : nullptr, c->fb.adapt.list, count, c->fb.adapt_samples, B, remark,
-                                          c->stream));
-            remark = 0;
-        }
-        nframes -= B;
-    }
-    return 0;
-}
-
-extern "C" int mpt_render_selected(mpt_ctx *c, int nframes, int remark) {
-    if (!c) return fail("null context");
-    if (nframes < 0) return fail("nframes must be >= 0");
-    if (check_ready(c)) return 1;
-    if (!c->adapt.selected)
-        return fail("mpt_render_selected: no selection: call mpt_adapt_select() or mpt_adapt_set_list() first (mpt_clear and mpt_set_size drop the selection)");
-    if (remark && !c->noise.marked)
-        return fail("mpt_render_selected: no mark: call mpt_film_mark() first (mpt_clear and mpt_set_size drop the mark)");
-    if (use(c)) return 1;
-    const int count = c->adapt.count;
-    int per = MPT_MAX_BATCH;
-    if (count > 0) per = (int)std::min<size_t>(MPT_MAX_BATCH, std::max<size_t>(1, (MPT_ADAPT_SAMPLE_BYTES - 1) / (sizeof(MptVec4) * (size_t)count)));
-    if (count > 0 && nframes > 0) {
-        const size_t need = (size_t)count * (size_t)std::min(nframes, per);
-        if (need > c->fb.adapt_samples.cap) {
-            HIP_TRY(hipStreamSynchronize(c->stream));          // (a launch may still read the old buffer)
-            if (c->fb.adapt_samples.reserve(need)) return 1;
-        }
-        MptTimedSpan span(c->adapt.render_timer, c->stream);
-        HIP_TRY(span.begun);
-        if (selected_launches(c, nframes, remark ? 1 : 0, per)) return 1;
-        HIP_TRY(span.end());
-        c->film_version++;           // pass 0 has changed: an early image of an earlier PathEngine launch is stale
-    } else if (selected_launches(c, nframes, 0, per)) return 1;
-    c->main_dirty = true;            // the next PathEngine launch waits for these
     return 0;
 }
 
@@ -1297,156 +1049,4 @@ extern "C" int mpt_synchronize(mpt_ctx *c) {                                   /
     if (mpt_flush(c)) return 1;
     if (wait_all(c)) return 1;
     return check_watchdog(c);
-}
-
-// ------------------------------------------------------------------ measurement
-extern "C" int mpt_get_counters(mpt_ctx *c, mpt_counters *out) {
-    if (use_ro(c)) return 1;
-    if (mpt_flush(c)) return 1;
-    unsigned long long h[20];
-    HIP_TRY(hipMemcpyAsync(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    out->samples = h[0]; out->rays = h[1]; out->n_box = h[2]; out->n_tri = h[3];
-    out->n_shade = h[4]; out->n_draws = h[5]; out->bounces = h[6]; out->n_node = h[7];
-    out->it_node = h[8]; out->it_leaf = h[9]; out->it_shade = h[10]; out->it_new = h[11];
-    out->pl_local = h[12]; out->pl_batches = h[13]; out->pl_batch_lanes = h[14]; out->pl_prim = h[15];
-    out->pl_tidle = h[16]; out->pl_sidle = h[17]; out->pl_trips = h[18]; out->pl_taken = h[19];
-    return 0;
-}
-
-// diagnostics (option "lane_hist" = 1 and "count" = 1): out[0 .. 3 x 65) = issued NODE / LEAF / SHADE stages by the number of lanes
-// that took part; out[195 ..) = [stage][depth 0 .. 5][closest, shadow] lane-steps; out[231 .. 255) = the gather kernels' NODE
-// lane-steps by the bucket of the node's number (0 | 1 | 2-3 | 4-7 | ...).  Zeroed by mpt_reset_counters
-extern "C" int mpt_get_lane_hist(mpt_ctx *c, unsigned long long *out, int n) {
-    if (use_ro(c)) return 1;
-    if (!out || n < MPT_HIST_WORDS) return fail("mpt_get_lane_hist: the buffer must hold %d words", (int)MPT_HIST_WORDS);
-    if (mpt_flush(c)) return 1;
-    HIP_TRY(hipMemcpyAsync(out, c->d_counters + MPT_HIST_BASE, MPT_HIST_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// diagnostics: out[wave][4] = {start, scene ready, queue empty, exit} of the last LDS-kernel launch, 100 MHz ticks
-extern "C" int mpt_get_timeline(mpt_ctx *c, unsigned long long *out, int cap_waves, int *nwaves) {
-    if (use_ro(c)) return 1;
-    if (mpt_synchronize(c)) return 1;
-    if (!c->d_timeline) return fail("no timeline recorded: set option 'timeline' and render with the LDS kernel");
-    int n = std::min(cap_waves, c->timeline_waves);
-    if (out && n > 0)
-        HIP_TRY(hipMemcpy(out, c->d_timeline, (size_t)n * MPT_TIMELINE_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    if (nwaves) *nwaves = c->timeline_waves;
-    return 0;
-}
-
-// diagnostics: wall time from the launch of a one-workgroup kernel (threads lanes, lds_bytes of LDS) on a
-// stream of its own to its completion, with whatever render launches are in flight left running -- how long
-// a small foreign kernel (RCCL's) waits for a CU next to the persistent workgroups
-extern "C" int mpt_probe_kernel(mpt_ctx *c, int threads, int lds_bytes, double *usec) {
-    if (use_ro(c)) return 1;
-    if (threads < 64 || threads > 1024 || lds_bytes < 4 * threads || lds_bytes > 64 * 1024)
-        return fail("probe: threads in 64..1024, lds_bytes in 4*threads..65536");
-    if (c->probe_stream.create()) return 1;
-    auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(mpt_launch_probe(c->d_scratch + 1, threads, (size_t)lds_bytes, c->probe_stream));
-    HIP_TRY(hipStreamSynchronize(c->probe_stream));
-    auto t1 = std::chrono::steady_clock::now();
-    if (usec) *usec = std::chrono::duration<double, std::micro>(t1 - t0).count();
-    return 0;
-}
-
-// test door (tools/soak.py, the tail finalisation's soak test): `count` device-to-device copies of `mbytes` MiB enqueued on a stream
-// of their own -- HBM and L2 traffic beside the render launches, whose hand-off of samples between XCDs must not care.  Returns
-// at once; count = 0 waits for the copies enqueued so far.
-extern "C" int mpt_stress_copies(mpt_ctx *c, int mbytes, int count) {
-    if (use_ro(c)) return 1;
-    if (mbytes < 1 || mbytes > 4096 || count < 0 || count > 100000) return fail("stress_copies: mbytes in 1..4096, count in 0..100000");
-    if (c->stress_stream.create()) return 1;
-    if (count == 0) { HIP_TRY(hipStreamSynchronize(c->stress_stream)); return 0; }
-    const size_t bytes = (size_t)mbytes << 20;
-    if (bytes != c->stress_bytes) {
-        HIP_TRY(hipStreamSynchronize(c->stress_stream));
-        c->stress_buf.release(); c->stress_bytes = 0;
-        if (c->stress_buf.reserve(2 * bytes)) return 1;
-        HIP_TRY(hipMemsetAsync(c->stress_buf, 0x5a, 2 * bytes, c->stress_stream));
-        c->stress_bytes = bytes;
-    }
-    for (int k = 0; k < count; k++)
-        HIP_TRY(hipMemcpyAsync(c->stress_buf + ((k & 1) ? 0 : bytes), c->stress_buf + ((k & 1) ? bytes : 0), bytes, hipMemcpyDeviceToDevice, c->stress_stream));
-    return 0;
-}
-
-// test door: one device function of the hot path on rows of inputs (include/miptina.h, unit_eval.hip)
-extern "C" int mpt_unit_eval(mpt_ctx *c, int kind, const void *in, int in_cols, void *out, int out_cols, int n) {
-    if (use_ro(c)) return 1;
-    static const int cols[MPT_UNIT_KINDS][2] = {
-        { 1, 1 }, { 3, 1 }, { 2, 1 }, { 2, 1 }, { 2, 1 }, { 3, 3 }, { 3, 3 }, { 6, 3 }, { 2, 3 }, { 3, 2 }, { 6, 3 }, { 7, 4 },
-        { 12, 3 }, { 30, 9 }, { 10, 1 }, { 15, 4 }, { 24, 3 }, { 24, 7 }, { 2, 1 }, { 1, 1 }, { 2, 1 },
-        { 6, 6 }, { 6, 8 }, { 3, 4 }, { 3, 3 }, { 3, 22 }, { 2, 6 }, { 14, 4 } };
-    if (kind < 0 || kind >= MPT_UNIT_KINDS) return fail("unit kind %d outside [0, %d)", kind, (int)MPT_UNIT_KINDS);
-    if (in_cols != cols[kind][0] || out_cols != cols[kind][1])
-        return fail("unit kind %d takes %d input and %d output columns, got %d and %d", kind, cols[kind][0], cols[kind][1],
-                    in_cols, out_cols);
-    if (n < 0 || (n > 0 && (!in || !out))) return fail("bad unit_eval arguments");
-    if (n == 0) return 0;
-    // the scene as a render launch would see it (the scene-free kinds ignore it); film, sampler and tree stay unset
-    MptRenderParams p;
-    memset(&p, 0, sizeof p);
-    p.world_tex = -1;
-    // MPT_UNIT_FACE_SIDE: one tshade record (mpt_types.h) per row, material id -1, packed HERE -- the kind tests the normal flip of
-    // get_geometries only; mpt_load_model's packing of tshade is covered by the render-level tests, not by this door
-    std::vector<MptVec4> shade;
-    if (kind >= MPT_UNIT_LIGHT_HIT) {
-        const float *rows = (const float *)in;
-        if (fill_scene_params(c, p)) return 1;
-        if (kind == MPT_UNIT_IMAGE_SAMPLE)
-            for (int i = 0; i < n; i++) {
-                const float id = rows[(size_t)i * in_cols];
-                if (!(id >= 0.f && id < (float)c->h_images.size() && id == (float)(int)id))
-                    return fail("unit_eval: row %d samples image %g, and %d images are loaded", i, (double)id, (int)c->h_images.size());
-            }
-        if (kind == MPT_UNIT_MATERIAL_GET) {
-            if (c->max_mat_tex >= (int)c->h_images.size())
-                return fail("unit_eval: a material names texture %d, and %d images are loaded", c->max_mat_tex, (int)c->h_images.size());
-            for (int i = 0; i < n; i++) {
-                const float id = rows[(size_t)i * in_cols];
-                if (!(id >= -1.f && id < (float)c->nmats && id == (float)(int)id))
-                    return fail("unit_eval: row %d asks for material %g outside [-1, %d), the records loaded", i, (double)id, c->nmats);
-            }
-        }
-        if (kind == MPT_UNIT_FACE_SIDE) {
-            shade.resize((size_t)n * 4);
-            const int none = -1;
-            for (int i = 0; i < n; i++) {
-                const float *vn = rows + (size_t)i * in_cols + 3;
-                MptVec4 *s = &shade[(size_t)i * 4];
-                s[0] = { vn[0], vn[1], vn[2], vn[3] }; s[1] = { vn[4], vn[5], vn[6], vn[7] };
-                s[2] = { vn[8], 0.f, 0.f, 0.f }; s[3] = { 0.f, 0.f, 0.f, 0.f };
-                memcpy(&s[3].w, &none, 4);
-            }
-        }
-    }
-    DevBuf<float> d_in, d_out;
-    DevBuf<MptVec4> d_shade;
-    if (d_in.reserve((size_t)n * in_cols) || d_out.reserve((size_t)n * out_cols) || d_shade.reserve(shade.size())) return 1;
-    hipError_t e = hipMemcpyAsync(d_in, in, (size_t)n * in_cols * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && d_shade) e = hipMemcpyAsync(d_shade, shade.data(), shade.size() * sizeof(MptVec4), hipMemcpyHostToDevice, c->stream);
-    p.tshade = d_shade;
-    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, (size_t)n * out_cols * 4, c->stream);
-    if (e == hipSuccess)
-        e = c->opt.mode == MPT_MODE_STRICT ? mpt_launch_unit_eval_strict(&p, kind, d_in, in_cols, d_out, out_cols, n, c->stream)
-                                       : mpt_launch_unit_eval_fast(&p, kind, d_in, in_cols, d_out, out_cols, n, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * out_cols * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail("mpt_unit_eval: %s", hipGetErrorString(e));
-    return 0;
-}
-
-extern "C" int mpt_reset_counters(mpt_ctx *c) {
-    if (use(c)) return 1;
-    HIP_TRY(hipMemsetAsync(c->d_counters, 0, MPT_COUNTER_WORDS * sizeof(unsigned long long), c->stream));
-    return 0;
-}
-
-extern "C" int mpt_kernel_time(mpt_ctx *c, double *ms, int *launches) {
-    return use_ro(c) || timer_readout(c, c->render_timer, ms, nullptr, launches, true);
 }

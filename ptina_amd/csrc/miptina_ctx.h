@@ -20,9 +20,15 @@
 #include <string>
 #include <vector>
 
+// A launcher that both builds of a dual translation unit define (Makefile DUAL; path_common.h MPT_SUFFIX): one signature, the two
+// names.  MPT_LAUNCHER(c, name) is the one of the build the context renders with.
+#define MPT_DUAL_LAUNCHER(name, ...)                    \
+    MPT_KERNEL_API hipError_t name##_fast(__VA_ARGS__); \
+    MPT_KERNEL_API hipError_t name##_strict(__VA_ARGS__)
+#define MPT_LAUNCHER(c, name) ((c)->opt.mode == MPT_MODE_STRICT ? name##_strict : name##_fast)
+
 // kernel launchers (render_kernel.hip x2, aux_kernels.hip)
-MPT_KERNEL_API hipError_t mpt_launch_render_fast(const MptRenderParams *, int grid, int stack, int count, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_render_strict(const MptRenderParams *, int grid, int stack, int count, hipStream_t);
+MPT_DUAL_LAUNCHER(mpt_launch_render, const MptRenderParams *, int grid, int stack, int count, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_derive_materials(MptMaterial *mats, int count, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_derive_tfast(const MptVec4 *tgeo, MptVec4 *tfast, int n, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_wide_blocks(int grid, int count, int quant, int *blocks);
@@ -30,30 +36,24 @@ MPT_KERNEL_API hipError_t mpt_launch_render_wide(const MptRenderParams *, int bl
 MPT_KERNEL_API hipError_t mpt_launch_render_lds(const MptRenderParams *, int grid, int block, size_t lds_bytes, int count, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_render_lds4(const MptRenderParams *, int grid, int block, size_t lds_bytes, int count, int feat, hipStream_t);
 // mlt_kernel.hip: the Metropolis engine's chain kernel (both builds), its test door, and the build-independent passes
-MPT_KERNEL_API hipError_t mpt_launch_mlt_chain_fast(const MptRenderParams *, const MptMltArgs *, int stack, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_mlt_chain_strict(const MptRenderParams *, const MptMltArgs *, int stack, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_mlt_trace_fast(const MptRenderParams *, const float *X, float *rgb, int n, int stack, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_mlt_trace_strict(const MptRenderParams *, const float *X, float *rgb, int n, int stack, hipStream_t);
+MPT_DUAL_LAUNCHER(mpt_launch_mlt_chain, const MptRenderParams *, const MptMltArgs *, int stack, hipStream_t);
+MPT_DUAL_LAUNCHER(mpt_launch_mlt_trace, const MptRenderParams *, const float *X, float *rgb, int n, int stack, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_mlt_reset(float *X, float *L, int *bit, int nchains, unsigned seed, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_mlt_sort_bytes(int n, int npix, size_t *bytes);
 MPT_KERNEL_API hipError_t mpt_launch_mlt_splat(MptVec4 *film, const unsigned *keys, const MptVec4 *vals, unsigned *keys2, MptVec4 *vals2,
                                                void *tmp, size_t tmp_bytes, unsigned *runs, int n, int npix, hipStream_t);
 // brute_kernel.hip: the brute-force engine's kernel (both builds)
-MPT_KERNEL_API hipError_t mpt_launch_brute_fast(const MptRenderParams *, int grid, int stack, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_brute_strict(const MptRenderParams *, int grid, int stack, hipStream_t);
+MPT_DUAL_LAUNCHER(mpt_launch_brute, const MptRenderParams *, int grid, int stack, hipStream_t);
 // adapt_kernel.hip: adaptive sampling's list render kernel (both builds); samples holds count * nframes records
-MPT_KERNEL_API hipError_t mpt_launch_adapt_render_fast(const MptRenderParams *, const int32_t *list, int count, MptVec4 *samples, int stack, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_adapt_render_strict(const MptRenderParams *, const int32_t *list, int count, MptVec4 *samples, int stack, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_preview_fast(const MptRenderParams *, int grid, int stack, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_preview_strict(const MptRenderParams *, int grid, int stack, hipStream_t);
+MPT_DUAL_LAUNCHER(mpt_launch_adapt_render, const MptRenderParams *, const int32_t *list, int count, MptVec4 *samples, int stack, hipStream_t);
+MPT_DUAL_LAUNCHER(mpt_launch_preview, const MptRenderParams *, int grid, int stack, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_sobol_update(const int *X, int *Xout, const int *V, float *P, int dim, int rows, int time0,
                                               int count, int keep, int write_x, hipStream_t stream);
 MPT_KERNEL_API hipError_t mpt_launch_combine(MptVec4 *film, const MptVec4 *partial, int ny, int x0, int x1,
                                          int stripe_w, int stripe_pitch, int ccols, int nframes, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_resolve(const MptVec4 *film, MptVec4 *out, size_t npix, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_probe(double *out, int threads, size_t lds_bytes, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_unit_eval_fast(const MptRenderParams *, int kind, const float *in, int in_cols, float *out, int out_cols, int n, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_unit_eval_strict(const MptRenderParams *, int kind, const float *in, int in_cols, float *out, int out_cols, int n, hipStream_t);
+MPT_DUAL_LAUNCHER(mpt_launch_unit_eval, const MptRenderParams *, int kind, const float *in, int in_cols, float *out, int out_cols, int n, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_copy_pieces(const MptVec4 *src, MptVec4 *dst, const MptPiece *tab, int npieces,
                                              long long max_count, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_export(const MptVec4 *film, float *out, int nx, int ny, hipStream_t);
@@ -690,6 +690,17 @@ MPT_INTERNAL int check_watchdog(mpt_ctx *c);   // after a synchronise: did a per
 MPT_INTERNAL int read_back(mpt_ctx *c, void *out, const void *dev, size_t bytes);   // device -> caller buffer on the main stream, blocking
 MPT_INTERNAL void *caller_alias(const mpt_ctx *c, void *p, size_t bytes);           // the device alias of a page-locked caller array of ours, or null
 MPT_INTERNAL int timer_readout(mpt_ctx *c, MptLaunchTimer &timer, double *ms0, double *ms1, int *launches, bool render_streams = false);
+// what the engines that launch at the call (engines.cpp) and the test door of the device functions (measure.cpp) take from it
+MPT_INTERNAL int render_entry(mpt_ctx *c, int nframes);                          // null context, nframes < 0, "not set up yet": fails at the call
+MPT_INTERNAL int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes);       // the launch parameters of a batch of nframes frames
+MPT_INTERNAL int fill_scene_params(mpt_ctx *c, MptRenderParams &p);              // ... the part that describes lights, world light, camera, materials and images
+// the sampler moves by `count` frames; the points of the last `keep` go to P[0 .. keep) (default: the main stream, c->sP)
+MPT_INTERNAL int sobol_advance(mpt_ctx *c, int count, int keep, hipStream_t stream = nullptr, float *P = nullptr);
+// levels of the per-lane traversal stack of the kernels that gather the binary tree, by the tree the context's build walks
+inline int gather_stack_levels(const mpt_ctx *c) { return mpt_gather_stack_levels(c->opt.mode == MPT_MODE_FAST ? c->fast_depth : c->tree_depth); }
+
+// engines.cpp
+MPT_INTERNAL int mlt_flush(mpt_ctx *c);       // mpt_flush, mpt_render: launch the Metropolis iterations enqueued so far
 
 // scene_compose.cpp
 MPT_INTERNAL int model_on_host(mpt_ctx *c);   // before anything reads c->verts / c->mtlids: fetch them once if mpt_compose made the model

@@ -27,12 +27,6 @@
 #include "path_common.h"
 #include "film_ops.h"
 
-#if MPT_STRICT
-#define MPT_SUFFIX(x) x##_strict
-#else
-#define MPT_SUFFIX(x) x##_fast
-#endif
-
 DEV unsigned mlt_pcg(unsigned v) {
     unsigned s = v * 747796405u + 2891336453u;
     unsigned w = ((s >> ((s >> 28) + 4u)) ^ s) * 277803737u;
@@ -139,18 +133,14 @@ __global__ __launch_bounds__(MPT_BLOCK) void MPT_SUFFIX(mlt_trace_kernel)(const 
 
 MPT_KERNEL_API hipError_t MPT_SUFFIX(mpt_launch_mlt_chain)(const MptRenderParams *p, const MptMltArgs *a, int stack, hipStream_t stream) {
     const int grid = (a->nchains + MPT_BLOCK - 1) / MPT_BLOCK;
-    if (stack <= 32) hipLaunchKernelGGL((MPT_SUFFIX(mlt_chain_kernel)<32>), dim3(grid), dim3(MPT_BLOCK), 0, stream, *p, *a);
-    else hipLaunchKernelGGL((MPT_SUFFIX(mlt_chain_kernel)<64>), dim3(grid), dim3(MPT_BLOCK), 0, stream, *p, *a);
-    return hipGetLastError();
+    return launch_by_stack<MPT_SUFFIX(mlt_chain_kernel)<32>, MPT_SUFFIX(mlt_chain_kernel)<64>>(stack, grid, stream, *p, *a);
 }
 
 MPT_KERNEL_API hipError_t MPT_SUFFIX(mpt_launch_mlt_trace)(const MptRenderParams *p, const float *X, float *rgb, int n, int stack,
                                                         hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     const int grid = (n + MPT_BLOCK - 1) / MPT_BLOCK;
-    if (stack <= 32) hipLaunchKernelGGL((MPT_SUFFIX(mlt_trace_kernel)<32>), dim3(grid), dim3(MPT_BLOCK), 0, stream, *p, X, rgb, n);
-    else hipLaunchKernelGGL((MPT_SUFFIX(mlt_trace_kernel)<64>), dim3(grid), dim3(MPT_BLOCK), 0, stream, *p, X, rgb, n);
-    return hipGetLastError();
+    return launch_by_stack<MPT_SUFFIX(mlt_trace_kernel)<32>, MPT_SUFFIX(mlt_trace_kernel)<64>>(stack, grid, stream, *p, X, rgb, n);
 }
 
 #if MPT_STRICT

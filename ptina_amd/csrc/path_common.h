@@ -2,10 +2,18 @@
 // per-lane tracer each build walks it with.  Shared by the PathEngine kernels (render_kernel.hip) and the Metropolis chain
 // kernel (mlt_kernel.hip): one definition of the path, so that a chain's path and a PathEngine sample given the same
 // draws are the same path.  Also here: the brute-force engine's loop body (brute_step, engine/brute.py:29-60; brute_kernel.hip)
-// and the 16x16-tile pixel mapping of the one-lane-per-pixel kernels.
-// Included once per translation unit, after pt_device.h; MPT_STRICT selects the build.
+// and the 16x16-tile pixel mapping of the one-lane-per-pixel kernels; the name of a build's kernels and launchers (MPT_SUFFIX) and the
+// launch of a kernel of the shape they share (launch_by_stack).
+// Included once per translation unit; MPT_STRICT selects the build.
 #pragma once
 #include "pt_device.h"
+
+// what both builds define carries the build in its name: mpt_launch_brute_strict / mpt_launch_brute_fast (miptina_ctx.h MPT_DUAL_LAUNCHER)
+#if MPT_STRICT
+#define MPT_SUFFIX(x) x##_strict
+#else
+#define MPT_SUFFIX(x) x##_fast
+#endif
 
 // ---------------------------------------------------------------- one lane per pixel of a 16x16 tile (strict render, preview, brute)
 DEV int xcd_remap(int b, int nb) {
@@ -175,4 +183,18 @@ DEV bool brute_step(const MptRenderParams &p, const TR &tr, PathState &s, Cnt &c
     s.ro = hitpos;
     s.rd = brdf.outdir;
     return false;
+}
+
+// ---------------------------------------------------------------- host side: the launch of a block-tracer kernel
+// The kernels that walk through make_block_tracer are `template <int STACK>` with `__shared__ int s_stack[STACK * MPT_BLOCK]` and
+// have two instantiations each, 32 and 64 levels; `stack` is what the tree asks for (lds_layout.h mpt_gather_stack_levels).
+// Which of the two serves it: 0 or 1
+static int stack_instantiation(int stack) { return stack <= 32 ? 0 : 1; }
+
+// `grid` workgroups of MPT_BLOCK lanes of K32 or K64, the same kernel's <32> and <64>
+template <auto K32, auto K64, class... A>
+static hipError_t launch_by_stack(int stack, unsigned grid, hipStream_t stream, const A &...args) {
+    static const decltype(K32) variants[2] = { K32, K64 };
+    hipLaunchKernelGGL(variants[stack_instantiation(stack)], dim3(grid), dim3(MPT_BLOCK), 0, stream, args...);
+    return hipGetLastError();
 }

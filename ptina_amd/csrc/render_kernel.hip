@@ -26,17 +26,9 @@
 // Strict build: one lane per pixel, frames summed in a register in order, the reference's traversal;
 //   one 16x16 tile per workgroup, blockIdx remapped so an XCD's blocks cover a contiguous run of tiles.
 
-#include "pt_device.h"
+#include "path_common.h"
 #include "film_ops.h"
 #include <atomic>
-
-#if MPT_STRICT
-#define MPT_SUFFIX(x) x##_strict
-#else
-#define MPT_SUFFIX(x) x##_fast
-#endif
-
-#include "path_common.h"
 
 template <bool COUNT>
 DEV void flush_counters(const MptRenderParams &p, const Cnt &c) {
@@ -295,9 +287,9 @@ static int blocks_per_cu(K kernel) {
     return nb;
 }
 
+typedef void (*RenderKernelFn)(const MptRenderParams);
 #if !MPT_STRICT
 // occupancy answers are per device (the C ABI allows one context per GPU in a process): asked once per device and kernel variant
-typedef void (*RenderKernelFn)(const MptRenderParams);
 static hipError_t cached_blocks_per_cu(std::atomic<int> (*cache)[4], const RenderKernelFn (&variants)[4], int v, int *occ) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MPT_MAX_DEVICES) return hipErrorInvalidDevice;
@@ -314,21 +306,17 @@ static hipError_t cached_blocks_per_cu(std::atomic<int> (*cache)[4], const Rende
 // (scaled here by the blocks each CU can hold); the work items come from p->work_counter.
 MPT_KERNEL_API hipError_t MPT_SUFFIX(mpt_launch_render)(const MptRenderParams *p, int grid, int stack, int count,
                                                      hipStream_t stream) {
-#if !MPT_STRICT
-    static std::atomic<int> occ_cache[MPT_MAX_DEVICES][4];
+    // the instantiations, by (stack levels, count)
     static const RenderKernelFn variants[4] = { MPT_SUFFIX(render_kernel)<32, false>, MPT_SUFFIX(render_kernel)<32, true>,
                                                 MPT_SUFFIX(render_kernel)<64, false>, MPT_SUFFIX(render_kernel)<64, true> };
+    const int v = 2 * stack_instantiation(stack) + (count ? 1 : 0);
+#if !MPT_STRICT
+    static std::atomic<int> occ_cache[MPT_MAX_DEVICES][4];
     int occ = 0;
-    if (hipError_t e = cached_blocks_per_cu(occ_cache, variants, (stack <= 32 ? 0 : 2) + (count ? 1 : 0), &occ)) return e;
+    if (hipError_t e = cached_blocks_per_cu(occ_cache, variants, v, &occ)) return e;
     grid *= occ;
 #endif
-    if (stack <= 32) {
-        if (count) hipLaunchKernelGGL((MPT_SUFFIX(render_kernel)<32, true>), dim3(grid), dim3(MPT_BLOCK), 0, stream, *p);
-        else hipLaunchKernelGGL((MPT_SUFFIX(render_kernel)<32, false>), dim3(grid), dim3(MPT_BLOCK), 0, stream, *p);
-    } else {
-        if (count) hipLaunchKernelGGL((MPT_SUFFIX(render_kernel)<64, true>), dim3(grid), dim3(MPT_BLOCK), 0, stream, *p);
-        else hipLaunchKernelGGL((MPT_SUFFIX(render_kernel)<64, false>), dim3(grid), dim3(MPT_BLOCK), 0, stream, *p);
-    }
+    hipLaunchKernelGGL(variants[v], dim3(grid), dim3(MPT_BLOCK), 0, stream, *p);
     return hipGetLastError();
 }
 
@@ -417,7 +405,5 @@ MPT_KERNEL_API hipError_t mpt_launch_render_wide(const MptRenderParams *p, int b
 
 MPT_KERNEL_API hipError_t MPT_SUFFIX(mpt_launch_preview)(const MptRenderParams *p, int grid, int stack,
                                                       hipStream_t stream) {
-    if (stack <= 32) hipLaunchKernelGGL((MPT_SUFFIX(preview_kernel)<32>), dim3(grid), dim3(MPT_BLOCK), 0, stream, *p);
-    else hipLaunchKernelGGL((MPT_SUFFIX(preview_kernel)<64>), dim3(grid), dim3(MPT_BLOCK), 0, stream, *p);
-    return hipGetLastError();
+    return launch_by_stack<MPT_SUFFIX(preview_kernel)<32>, MPT_SUFFIX(preview_kernel)<64>>(stack, grid, stream, *p);
 }

@@ -14,15 +14,9 @@
 //
 // Rows are 4-byte words: f32, except the two hash kinds (i32).  Kinds and columns: include/miptina.h.
 
-#include "pt_device.h"
+#include "path_common.h"
 #include "tri_records.h"
 #include "../../include/miptina.h"
-
-#if MPT_STRICT
-#define MPT_SUFFIX(x) x##_strict
-#else
-#define MPT_SUFFIX(x) x##_fast
-#endif
 
 DEV V3 ld(const float *r, int k) { return v3(r[k], r[k + 1], r[k + 2]); }
 DEV void st(float *o, int k, V3 v) { o[k] = v.x; o[k + 1] = v.y; o[k + 2] = v.z; }

@@ -54,6 +54,7 @@ int t_choose(int fast, int use_lds, int lds_wide, int use_wide, int nfaces, int 
     *lds_bytes = ch.lds_bytes;
     return ch.kernel;
 }
+int t_stack_levels(int depth) { return mpt_gather_stack_levels(depth); }
 '''
 
 
@@ -212,6 +213,14 @@ def test_fit_boundaries_from_both_sides(lay):
         last, first = boundary(lambda m: fit4_py(n, nw, stack, m), list(range(0, 2000)))
         assert lay.t_fit4(n, nw, stack, last) > 0 and lay.t_fit4(n, nw, stack, first) == 0, (n, nw, stack, last, first)
     assert boundary(lambda m: fit4_py(2, 1, 1, m), list(range(0, 2000))) == (254, 255)
+
+
+def test_gather_stack_levels(lay):
+    '''the kernels that gather the binary tree keep the sentinel and one pending sibling per level: depth + 2 entries, in the
+    32-level instantiation while they fit and in the 64-level one from depth 31 on (the deepest tree that one serves: 62)'''
+    assert [lay.t_stack_levels(d) for d in (0, 30, 31, 62)] == [32, 32, 64, 64]
+    for d in (0, 30, 31, 62):
+        assert d + 2 <= lay.t_stack_levels(d)
 
 
 def test_smallest_and_largest_face_counts(lay):

@@ -15,6 +15,8 @@ checks are those of tests/test_visibility_ref_cpu.py, where the oracle's own wal
 In the production build the last three walk the binary fnode records (the strict build walks snode, the reference's own
 tree).  Up to 8192 triangles the default SAH pass is the host's; each of the three also runs with sah_build = 1, and then
 n1025 and n5000 are sizes where the device pass's binned levels wrote those records.
+7  the 64-level instantiations of every one-lane-per-item kernel -- the gather render kernels, BruteEngine, the Metropolis path
+   door and chain kernel, the list pass, PreviewEngine -- on `deep`, whose tree needs more than 32 stack levels (asserted first)
 '''
 
 import os
@@ -190,13 +192,8 @@ def test_brute_engine(fresh, name, mode, sah):
 
 
 # ---------------------------------------------------------------- 5. the Metropolis path door
-@pytest.mark.parametrize('sah', list(SAH_PASSES))
-@pytest.mark.parametrize('mode', ['strict', 'fast'])
-@pytest.mark.parametrize('name', ['n1025', 'n5000'])
-def test_metropolis_path_door(fresh, name, mode, sah):
-    from ptina_amd.engine.mltpath import mlt_trace
-    c = case(name)
-    hit, miss = c.shares()
+def _door_points(c, hit, miss):
+    '''nine screen points in each of up to 4096 classified pixels, as the door's 32-vectors -> (X, pi, pj)'''
     rng = np.random.default_rng(c.n)
     ij = np.argwhere(hit | miss)
     ij = ij[rng.permutation(ij.shape[0])[:4096]]
@@ -205,6 +202,17 @@ def test_metropolis_path_door(fresh, name, mode, sah):
     X = rng.random((pi.shape[0], 32), dtype=np.float32)
     X[:, 0] = (pi + np.tile(u, ij.shape[0])) / c.nx
     X[:, 1] = (pj + np.tile(v, ij.shape[0])) / c.ny
+    return X, pi, pj
+
+
+@pytest.mark.parametrize('sah', list(SAH_PASSES))
+@pytest.mark.parametrize('mode', ['strict', 'fast'])
+@pytest.mark.parametrize('name', ['n1025', 'n5000'])
+def test_metropolis_path_door(fresh, name, mode, sah):
+    from ptina_amd.engine.mltpath import mlt_trace
+    c = case(name)
+    hit, miss = c.shares()
+    X, pi, pj = _door_points(c, hit, miss)
     _setup(c, mode, SAH_PASSES[sah])
     rgb = mlt_trace(X)
     want = np.where(hit[pi, pj][:, None], np.zeros(3, np.float32), np.array([1, 0.5, 0.25], np.float32)).astype(np.float32)
@@ -231,3 +239,121 @@ def test_preview_names_the_nearest_material(fresh, name, mode, tree):
         PreviewEngine().render()
     bad = preview_errors(c, FilmTable().get_raw(1), 3, f'preview {mode} {name} {tree}')
     assert not bad, f'{len(bad)} wrong pixels; ' + '; '.join(bad[:4])
+
+
+# ---------------------------------------------------------------- 7. the 64-level instantiations
+def _deep(mode, scene=None):
+    '''`deep` set up in the strict build or in the production build over the LBVH (option tree = 0: the same 37 levels), with the
+    depth the launches are sized by asserted to need the 64-level instantiation -> (case, PathEngine)'''
+    from ptina_amd.common import ctx
+    c = case('deep')
+    c.shares()
+    eng = _setup(c, mode, None if mode == 'strict' else {'tree': 0}, scene)
+    depth = ctx().get_option('tree_depth' if mode == 'strict' else 'fast_depth')
+    assert depth + 2 > 32, f'deep {mode}: a tree of depth {depth} is served by the 32-level instantiation'
+    return c, eng
+
+
+def _deep_path_film(selection, count=0):
+    from ptina_amd.common import ctx
+    from ptina_amd.things import FilmTable
+    mode, opts, _, _ = SELECTIONS[selection]
+    c, eng = _deep(mode)
+    for key, value in dict(opts, count=count).items():
+        ctx().set_option(key, value)
+    eng.render(FRAMES)
+    raw = FilmTable().get_raw().copy()
+    if mode != 'strict':
+        assert ctx().get_option('last_kernel') == 0
+    return c, raw
+
+
+@pytest.mark.parametrize('count', [0, 1])
+@pytest.mark.parametrize('selection', ['strict', 'gather_binary'])
+def test_deep_path_engine(fresh, selection, count):
+    '''the gather render kernel's table of (stack levels, counters) in both builds'''
+    c, raw = _deep_path_film(selection, count)
+    assert_mask(c, raw, FRAMES, f'deep {selection} count {count}')
+
+
+@pytest.mark.parametrize('mode', ['strict', 'fast'])
+def test_deep_brute_engine(fresh, mode):
+    from ptina_amd.engine.brute import BruteEngine
+    from ptina_amd.things import FilmTable
+    c, _ = _deep(mode)
+    BruteEngine().render(FRAMES)
+    assert_mask(c, FilmTable().get_raw(), FRAMES, f'deep brute {mode}')
+
+
+@pytest.mark.parametrize('mode', ['strict', 'fast'])
+def test_deep_metropolis_path_door(fresh, mode):
+    from ptina_amd.engine.mltpath import mlt_trace
+    c = case('deep')
+    hit, miss = c.shares()
+    X, pi, pj = _door_points(c, hit, miss)
+    _deep(mode)
+    rgb = mlt_trace(X)
+    want = np.where(hit[pi, pj][:, None], np.zeros(3, np.float32), np.array([1, 0.5, 0.25], np.float32)).astype(np.float32)
+    bad = np.flatnonzero((rgb.view(np.uint32) != want.view(np.uint32)).any(axis=1))
+    assert hit[pi, pj].any() and miss[pi, pj].any()
+    assert bad.size == 0, (f'deep mlt_trace {mode}: {bad.size} of {X.shape[0]} rays wrong; first: screen point {X[bad[0], :2].tolist()} of pixel '
+                           f'({pi[bad[0]]}, {pj[bad[0]]}) gives {rgb[bad[0]].tolist()}, want {want[bad[0]].tolist()}')
+
+
+@pytest.mark.parametrize('mode', ['strict', 'fast'])
+def test_deep_metropolis_chains(fresh, mode):
+    '''LSP = 1: every proposal is a fresh uniform vector, splatted where its first two draws point.  A splat into a full-hit pixel
+    adds exactly 0 and one into a full-miss pixel exactly the world colour, whatever the chains accept'''
+    from ptina_amd.engine.mltpath import MLTPathEngine
+    from ptina_amd.things import FilmTable
+    c, _ = _deep(mode)
+    hit, miss = c.shares()
+    FilmTable().clear()
+    e = MLTPathEngine(nchains=4096, seed=7)
+    e.LSP[None] = 1.0
+    e.render(4)
+    raw = FilmTable().get_raw().reshape(c.nx, c.ny, 4)
+    assert raw[..., 3].sum() == 4096 * 4 and raw[hit][:, 3].sum() > 0 and raw[miss][:, 3].sum() > 0
+    bad = np.argwhere(hit & (raw[..., :3] != 0).any(axis=-1))
+    assert bad.shape[0] == 0, f'deep chains {mode}: {bad.shape[0]} full-hit pixels hold light; first {tuple(bad[0])}: {raw[tuple(bad[0])].tolist()}'
+    r = raw[..., 0]
+    bad = np.argwhere(miss & ((r != np.round(r)) | (raw[..., 1] != r / 2) | (raw[..., 2] != r / 4)))
+    assert bad.shape[0] == 0, f'deep chains {mode}: {bad.shape[0]} full-miss pixels are not (r, r/2, r/4); first {tuple(bad[0])}: {raw[tuple(bad[0])].tolist()}'
+
+
+@pytest.mark.parametrize('mode', ['strict', 'fast'])
+def test_deep_list_pass(fresh, mode):
+    '''every pixel listed: the list kernel renders the whole film; in the strict build it is the PathEngine's bit for bit'''
+    from ptina_amd.common import reset_all
+    from ptina_amd.things import FilmTable
+    c, eng = _deep(mode)
+    FilmTable().clear()
+    FilmTable().set_selection(np.arange(c.nx * c.ny, dtype=np.int32))
+    eng.render_selected(FRAMES)
+    raw = FilmTable().get_raw().copy()
+    assert_mask(c, raw, FRAMES, f'deep list pass {mode}')
+    if mode == 'strict':
+        reset_all()
+        _, path = _deep_path_film('strict')
+        diff = np.flatnonzero((raw.view(np.uint32) != path.view(np.uint32)).any(axis=1))
+        assert diff.size == 0, (f'deep: the list pass differs from the strict PathEngine in {diff.size} pixels; first {divmod(int(diff[0]), c.ny)}: '
+                                f'{raw[diff[0]].tolist()} against {path[diff[0]].tolist()}')
+
+
+@pytest.mark.parametrize('mode', ['strict', 'fast'])
+def test_deep_preview(fresh, mode):
+    '''one material of basecolor 0.5 on every triangle: three preview frames sum to exactly 1.5 where every ray hits'''
+    from ptina_amd import scenes
+    from ptina_amd.engine.preview import PreviewEngine
+    from ptina_amd.things import FilmTable
+    c = case('deep')
+    hit, miss = c.shares()
+    v, m, _, im = c.scene
+    _deep(mode, (v, m, [scenes.material(basecolor=(0.5, 0.5, 0.5))], im))
+    for _ in range(3):
+        PreviewEngine().render()
+    raw = FilmTable().get_raw(1).reshape(c.nx, c.ny, 4)
+    bad = np.argwhere(hit & (raw != np.array([1.5, 1.5, 1.5, 3], np.float32)).any(axis=-1))
+    assert bad.shape[0] == 0, f'deep preview {mode}: {bad.shape[0]} full-hit pixels are not (1.5, 1.5, 1.5, 3); first {tuple(bad[0])}: {raw[tuple(bad[0])].tolist()}'
+    bad = np.argwhere(miss & (raw != np.array([0, 0, 0, 3], np.float32)).any(axis=-1))
+    assert bad.shape[0] == 0, f'deep preview {mode}: {bad.shape[0]} full-miss pixels are not (0, 0, 0, 3); first {tuple(bad[0])}: {raw[tuple(bad[0])].tolist()}'

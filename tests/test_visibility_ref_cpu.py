@@ -29,10 +29,31 @@ CASES = {
     'moved': (300, 0.2, 96, 80, 'moved'),           # 8-bit planes far from the origin
     'x1024': (300, 0.2, 96, 80, 'x1024'),           # LdsWalk4::T_SCALED
     'flat': (200, 0.3, 96, 80, 'flat'),             # every box flat along z: the e == 0 branch of the quantised step, a lo == hi slab
+    'deep': (352, 0.5, 64, 64, 'deep'),             # a reference tree of 37 levels: the 64-level stacks of the one-lane-per-item kernels (deep_model)
 }
 # No scaled-down scene: at x 1/1024 the oracle itself loses every full-hit pixel to the reference's absolute epsilons
 # (test_scene_scale_dependence_is_the_references pins that); an exhaustive search is not the reference there.
 PREVIEW_CASES = ('n300', 'n1025', 'n5000')
+
+
+def deep_model(edge):
+    '''352 triangles, all facing +z, whose reference LBVH is 37 levels of inner nodes deep: 16 copies of one triangle at
+    (1, 1, 1); for k = 0 .. 11 and each axis one triangle whose centre has that coordinate at 1 - 2^-(k + 1) -- its Morton code
+    leaves the copies' at one bit, so every bit splits one leaf off on the left and the chain descends on the right -- and 300
+    fillers of edge 1e-3 near the origin, which change nothing of the chain: the reference's walk gives up after n node
+    visits (lbvh.py:324), and with the 53 triangles alone the oracle itself loses full-hit pixels.  Triangle t is
+    c + (-e, -e, 0), c + (e, -e, 0), c + (0, e, 0); every centre is moved by (-0.5, 1, -0.5) into BENCH_CAMERA's view'''
+    cen = [(1.0, 1.0, 1.0)] * 16
+    for k in range(12):
+        for a in range(3):
+            c = [1.0, 1.0, 1.0]
+            c[a] = 1.0 - 2.0 ** -(k + 1)
+            cen.append(tuple(c))
+    cen = np.concatenate([np.array(cen), np.random.default_rng(53).random((300, 3)) * 0.05]) + [-0.5, 1.0, -0.5]
+    e = np.concatenate([np.full(52, float(edge)), np.full(300, 1e-3)])[:, None, None]
+    P = cen[:, None, :] + e * np.array([[-1.0, -1.0, 0.0], [1.0, -1.0, 0.0], [0.0, 1.0, 0.0]])
+    N = np.broadcast_to([0.0, 0.0, 1.0], P.shape)
+    return scenes._pack(P, N), np.zeros(P.shape[0], np.int32)
 
 
 class Case:
@@ -40,7 +61,7 @@ class Case:
 
     def __init__(self, name, preview=False):
         n, edge, nx, ny, variant = CASES[name]
-        v, m, _, _ = scenes.scene_random_tris(n, seed=n, edge=edge)
+        v, m = deep_model(edge) if variant == 'deep' else scenes.scene_random_tris(n, seed=n, edge=edge)[:2]
         v = np.array(v, np.float32, copy=True)
         cam = np.array(scenes.BENCH_CAMERA, np.float64)
         if variant == 'moved':
@@ -148,6 +169,13 @@ def test_the_oracles_walk_agrees_in_every_classified_pixel(oracle_mod, name):
     o = _oracle(oracle_mod, c)
     o.render(4)
     assert_mask(c, o.get_film_raw(), 4, f'oracle {name}')
+
+
+def test_the_deep_case_needs_more_than_32_stack_levels(oracle_mod):
+    '''what makes the GPU's `deep` cases mean something: the reference's own walk of that tree holds more than 32 entries'''
+    o = _oracle(oracle_mod, case('deep'))
+    o.render(4)
+    assert o.counters()['max_stack'] > 32, o.counters()
 
 
 @pytest.mark.parametrize('name', ['n300', 'n1025'])
