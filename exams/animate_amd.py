@@ -3,10 +3,13 @@
 A turntable: the Cornell scene's tall box turned about its own axis over N frames, the scene kept on the device.  The walls and
 the two boxes are meshes of ModelPool's pool and objects of its table; each frame is
     ModelPool().set_world(box, matrix) -> compose() -> BVHTree().build() -> PathEngine().render() x spp -> FilmTable().get_display()
-so nothing but the matrix crosses to the device and nothing but the 8-bit picture comes back.  The reference's add-on runs
+so nothing but the matrix crosses to the device and nothing but the 8-bit picture comes back.  With --refit a frame is
+    set_world -> compose() -> BVHTree().update() -> render ...
+and update() keeps the built tree and fits its boxes to the turned box (csrc/refit.hip), building again only when the tree's
+cost has grown past --max-growth.  The reference's add-on runs
 compose_multiple_meshes + load_model + build_tree over the whole scene at every change (blender.py:555-571).
 
-    python exams/animate_amd.py [--frames 12] [--size 256] [--spp 8] [--out DIR]
+    python exams/animate_amd.py [--frames 12] [--size 256] [--spp 8] [--out DIR] [--refit [--max-growth G]]
 '''
 import argparse
 import os
@@ -25,6 +28,8 @@ ap.add_argument('--frames', type=int, default=12)
 ap.add_argument('--size', type=int, default=256)
 ap.add_argument('--spp', type=int, default=8)
 ap.add_argument('--out', default='.')
+ap.add_argument('--refit', action='store_true', help='BVHTree().update() instead of build() at every frame')
+ap.add_argument('--max-growth', type=float, default=None, help="update()'s bound (default: the library's)")
 args = ap.parse_args()
 
 ti.init(ti.cuda)
@@ -54,10 +59,16 @@ pool.compose()
 
 os.makedirs(args.out, exist_ok=True)
 t0 = time.perf_counter()
+refitted, largest = 0, 1.0
 for f in range(args.frames):
     pool.set_world(tall, placed((-0.7, 1.2, -0.6), 18.0 + 360.0 * f / args.frames))
     pool.compose()
-    BVHTree().build()
+    if args.refit:
+        how = BVHTree().update() if args.max_growth is None else BVHTree().update(args.max_growth)
+        refitted += how == 'refit'
+        largest = max(largest, BVHTree().refit_stats().growth if how == 'refit' else 1.0)
+    else:
+        BVHTree().build()
     FilmTable().clear()
     PathEngine().render(args.spp)
     img = FilmTable().get_display(layout='display')
@@ -67,3 +78,5 @@ for f in range(args.frames):
 dt = time.perf_counter() - t0
 print('%d frames of %dx%d at %d spp in %.2f s (PNG writing included), host copy of the model fetched %d times: written to %s'
       % (args.frames, args.size, args.size, args.spp, dt, pool.compose_stats().host_fetches, args.out))
+if args.refit:
+    print('%d of %d frames refitted, the others built; largest growth of a refitted tree %.3f' % (refitted, args.frames, largest))

@@ -540,6 +540,38 @@ int mpt_get_model(mpt_ctx *ctx, float *verts, int32_t *mtlids, int cap_faces, in
 int mpt_compose_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
 int mpt_compose_plan(const int32_t *faces, const int32_t *dirty, int nobj, int64_t *first, int64_t *wg_begin, int64_t *wg_count, int cap);
 
+/* Refit: after the model's faces moved (mpt_compose after mpt_object_set_world, or mpt_load_model of as many faces), keep the trees
+ * of the last mpt_build_tree and fit their boxes to the model again, on the device -- what a viewport does for a moved object instead of
+ * building (the reference's add-on builds: blender.py:555-571).
+ * mpt_refit_tree: keeps the topology of the last successful mpt_build_tree -- the hierarchy, the leaf order, every id row, tree_depth,
+ *   fast_depth, wide_nodes, wide_depth, wide_stack, wide_ratio_permille -- and writes again, from the model as it is on the device now
+ *   (uploaded first if mpt_load_model brought it), everything that build derived from vertex positions and material ids: the boxes
+ *   of the reference tree (mpt_get_tree's bmin / bmax), of the binary tree the fast build walks and of the 4-wide records exact
+ *   and quantised (mpt_get_wide), and the triangle records.  The bytes are those a build over the same topology would write.
+ *   The leaf order never changes: a scene that was rearranged wholesale keeps a valid but slow tree, which mpt_refit_stats shows.
+ *   Leaves the tree valid.  Never reads the host's copy of a composed model.  Refuses, each time naming build_tree(): when no
+ *   tree was ever built; when an option that steers the build was set since; when the last build failed; when the tree was built
+ *   with gpu_build = 0; when the model's face count is not the one the tree was built for (both numbers are named).
+ *   0 and 1 faces are legal: there are no nodes, the triangle records alone are written.
+ * mpt_refit_stats: faces the records hold a topology for (-1: none), its wide nodes, refits since the build, fetches of the model's
+ *   host copy that refits caused since mpt_create (stays 0), whether mpt_refit_tree would be allowed for the model as it stands, and the cost of the binary tree -- the sum over every child box of
+ *   every node record of area(child) / area(root), the boxes a random ray is expected to meet, summed in 2^-40 fixed point so
+ *   that the same records give the same bits -- as built (taken by the first refit after a build, from the build's records)
+ *   and as it is now; growth = cost_now / cost_built, 1 where cost_built is 0 or nothing was refitted yet.
+ * mpt_refit_kernel_time: HIP-event time (ms) of the kernels of the mpt_refit_tree calls since the last call, and their count.
+ * mpt_refit_allowed / mpt_refit_growth: the rule above and the growth figure as pure functions (no context, no GPU).  state: 0 no
+ *   tree was ever built, 1 the records hold a topology, 2 an option was set since, 3 a later build failed.  Returns 0 when a refit
+ *   is allowed, else 1 .. 5 in the order of the refusals above, with the words in why[why_size] (may be NULL). */
+typedef struct {
+    int64_t faces, wide_nodes, refits, host_fetches, allowed;
+    double cost_built, cost_now, growth;
+} mpt_refit_info;
+int mpt_refit_tree(mpt_ctx *ctx);
+int mpt_refit_stats(mpt_ctx *ctx, mpt_refit_info *out);
+int mpt_refit_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
+int mpt_refit_allowed(int state, int built_faces, int built_on_device, int nfaces, char *why, int why_size);
+double mpt_refit_growth(uint64_t cost_built, uint64_t cost_now);
+
 /* Page-locked host buffers for the read-backs above: into such a buffer mpt_get_image /
  * mpt_fast_export_image / mpt_get_film_raw are one DMA; any other buffer is served through a
  * page-locked staging copy.  (The reference's get_image returns a fresh numpy array,

@@ -81,6 +81,12 @@ class ComposeInfo(C.Structure):
                 ('scene_cen', C.c_double * 3), ('scene_rad', C.c_double)]
 
 
+class RefitInfo(C.Structure):
+    '''mpt_refit_info (include/miptina.h): what mpt_refit_stats hands back'''
+    _fields_ = [('faces', C.c_int64), ('wide_nodes', C.c_int64), ('refits', C.c_int64), ('host_fetches', C.c_int64), ('allowed', C.c_int64),
+                ('cost_built', C.c_double), ('cost_now', C.c_double), ('growth', C.c_double)]
+
+
 DISPLAY_DENOISED = -1
 TONE_OPS = {'linear': 0, 'ptina': 1, 'reinhard': 2, 'aces': 3}
 TRANSFERS = {'srgb': 0, 'gamma': 1}
@@ -175,6 +181,11 @@ SIGNATURES = {
     'mpt_get_model': (_i, [_vp, _fp, _ip, _i, C.POINTER(_i)]),
     'mpt_compose_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
     'mpt_compose_plan': (_i, [_ip, _ip, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _i]),
+    'mpt_refit_tree': (_i, [_vp]),
+    'mpt_refit_stats': (_i, [_vp, C.POINTER(RefitInfo)]),
+    'mpt_refit_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_refit_allowed': (_i, [_i, _i, _i, _i, C.c_char_p, _i]),
+    'mpt_refit_growth': (C.c_double, [C.c_uint64, C.c_uint64]),
     'mpt_host_alloc': (_vp, [C.c_size_t]),
     'mpt_host_free': (None, [_vp]),
     'mpt_get_counters': (_i, [_vp, C.POINTER(Counters)]),

@@ -203,7 +203,8 @@ __global__ __launch_bounds__(LB_BLOCK) void fit_boxes_kernel(const float *__rest
 
 __device__ __forceinline__ float asf(int v) { return __int_as_float(v); }
 
-// node records (mpt_types.h): snode = reference-shaped, fnode = both child boxes of the LBVH itself
+// node records (mpt_types.h): snode = reference-shaped, fnode = both child boxes of the LBVH itself (null: snode alone -- a refit,
+// whose fnode may hold the SAH tree)
 __global__ __launch_bounds__(LB_BLOCK) void pack_nodes_kernel(const float *__restrict__ verts, const int *__restrict__ leaf,
                                                               const int *__restrict__ child, const float *__restrict__ bmin,
                                                               const float *__restrict__ bmax, int n,
@@ -213,6 +214,7 @@ __global__ __launch_bounds__(LB_BLOCK) void pack_nodes_kernel(const float *__res
     int c0 = child[(size_t)i * 2], c1 = child[(size_t)i * 2 + 1];
     snode[(size_t)i * 2 + 0] = { bmin[(size_t)i * 3], bmin[(size_t)i * 3 + 1], bmin[(size_t)i * 3 + 2], asf(c0) };
     snode[(size_t)i * 2 + 1] = { bmax[(size_t)i * 3], bmax[(size_t)i * 3 + 1], bmax[(size_t)i * 3 + 2], asf(c1) };
+    if (!fnode) return;
     float l[2][3], h[2][3];
     int id[2];
 #pragma unroll
@@ -293,6 +295,25 @@ MPT_KERNEL_API hipError_t mpt_lbvh_build(const MptLbvhBuffers *b, hipStream_t st
                            b->bmin, b->bmax, b->arrive, b->depth);
         hipLaunchKernelGGL(pack_nodes_kernel, dim3(gl), dim3(LB_BLOCK), 0, stream, b->verts, b->leaf, b->child, b->bmin, b->bmax,
                            n, b->snode, b->fnode);
+    }
+    hipLaunchKernelGGL(pack_tris_kernel, dim3(gl), dim3(LB_BLOCK), 0, stream, b->verts, b->mtlids, b->leaf, n, b->tgeo, b->tshade);
+    return hipGetLastError();
+}
+
+// The part of the build that reads vertex positions and material ids, over the hierarchy as it stands (child, parent, leaf): the
+// boxes bottom-up, snode, tgeo and tshade.  fnode is left alone (refit.hip fits it, whichever tree it holds); b->depth keeps its
+// value (fit_boxes raises it to the depth it already holds).
+MPT_KERNEL_API hipError_t mpt_lbvh_refit(const MptLbvhBuffers *b, hipStream_t stream) {
+    const int n = b->n;
+    if (n <= 0) return hipSuccess;
+    const int gl = (n + LB_BLOCK - 1) / LB_BLOCK;
+    hipError_t e;
+    if (n > 1) {
+        if ((e = hipMemsetAsync(b->arrive, 0, (size_t)(n - 1) * sizeof(unsigned), stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(fit_boxes_kernel, dim3(gl), dim3(LB_BLOCK), 0, stream, b->verts, b->leaf, b->child, b->parent, n,
+                           b->bmin, b->bmax, b->arrive, b->depth);
+        hipLaunchKernelGGL(pack_nodes_kernel, dim3(gl), dim3(LB_BLOCK), 0, stream, b->verts, b->leaf, b->child, b->bmin, b->bmax,
+                           n, b->snode, (MptVec4 *)nullptr);
     }
     hipLaunchKernelGGL(pack_tris_kernel, dim3(gl), dim3(LB_BLOCK), 0, stream, b->verts, b->mtlids, b->leaf, n, b->tgeo, b->tshade);
     return hipGetLastError();

@@ -270,7 +270,7 @@ extern "C" int mpt_set_option(mpt_ctx *c, const char *key, int value) {
     char why[160];
     bool tree_invalid = false;
     if (mpt_option_set_row(c->opt, r, value, why, sizeof why, &tree_invalid) != MPT_OPT_OK) return fail("%s", why);
-    if (tree_invalid) c->tree_valid = false;
+    if (tree_invalid) { c->tree_valid = false; c->refit.lose(MPT_TOPO_OPTION); }
     return 0;
 }
 

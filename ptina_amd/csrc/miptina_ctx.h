@@ -6,6 +6,7 @@
 #include "mpt_types.h"
 #include "mpt_options.h"
 #include "shade_feat.h"
+#include "refit_rule.h"
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -114,6 +115,12 @@ MPT_KERNEL_API hipError_t mpt_wide_build(const MptVec4 *fnode, int n, MptVec4 *w
                                      double area[2], hipStream_t stream, volatile int *mail_host, int *mail_dev);
 MPT_KERNEL_API hipError_t mpt_lbvh_sort_bytes(int n, size_t *bytes);
 MPT_KERNEL_API hipError_t mpt_lbvh_build(const MptLbvhBuffers *b, hipStream_t stream);
+MPT_KERNEL_API hipError_t mpt_lbvh_refit(const MptLbvhBuffers *b, hipStream_t stream);     // boxes, snode, tgeo, tshade over the hierarchy as it stands
+// refit.hip: the parent slots of the binary and the wide records, their boxes fitted bottom-up to the vertices, the cost figure
+MPT_KERNEL_API hipError_t mpt_refit_link(const MptVec4 *fnode, int ni, const MptVec4 *wnode, int nw, int *bin_parent, int *wide_parent, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_refit_cost(const MptVec4 *fnode, int ni, unsigned long long *sum, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_refit_fit(const float *verts, const int *leaf, int n, MptVec4 *fnode, const int *bin_parent, MptVec4 *wnode,
+                                        MptVec4 *qnode, int nw, const int *wide_parent, unsigned *arrive, hipStream_t);
 
 // ------------------------------------------------------------------ errors (miptina.cpp)
 #define MPT_INTERNAL __attribute__((visibility("hidden")))   // shared between the .cpp files, not exported
@@ -631,6 +638,18 @@ struct mpt_ctx {
         MptLaunchTimer timer;                            // mpt_compose: {before the compose kernel, after the fold} per call
         explicit Compose(MptEventPool &ev) : timer(2, ev) {}
     } compose{events};
+    struct MPT_INTERNAL Refit {                          // mpt_refit_tree (tree_refit.cpp, refit_rule.h)
+        int topo = MPT_TOPO_NONE;                        // MptTopoState: do the node records hold a topology, and if not, why not
+        int faces = 0; bool on_device = false;           // ... for this many faces, from the device build
+        bool linked = false;                             // bin_parent / wide_parent are this build's (made by its first refit)
+        DevBuf<int> bin_parent, wide_parent;             // per binary / wide node: the slot of its parent's record its box lives in
+        DevBuf<unsigned long long> cost;                 // [2]: the cost kernel's sums, before and after
+        uint64_t cost_built = 0, cost_now = 0;           // in units of 2^-40; cost_built is taken by the first refit after a build
+        int64_t refits = 0, host_fetches = 0;            // since the build | fetches of the model's host copy refits caused, ever
+        MptLaunchTimer timer;                            // {before the refit's kernels, after them} per call
+        explicit Refit(MptEventPool &ev) : timer(2, ev) {}
+        void lose(int why) { if (topo != MPT_TOPO_NONE) topo = why; }
+    } refit{events};
     MptDoorInput door;                                   // mpt_display_eval, mpt_noise_eval, mpt_denoise_eval: the caller's accumulators on the device (grown on demand)
     MptLaunchTimer render_timer{2, events};              // PathEngine launches: {kernel start, kernel end}
     MptLaunchTimer denoise_timer{2, events};             // mpt_get_denoised: {before the prologue, after the epilogue} per call

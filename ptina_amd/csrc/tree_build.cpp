@@ -721,6 +721,7 @@ extern "C" int mpt_get_wide(mpt_ctx *c, float *wnode, float *qnode, int cap_node
 extern "C" int mpt_build_tree(mpt_ctx *c) {
     if (use(c)) return 1;
     BuildClock clk(c);
+    c->refit.lose(MPT_TOPO_BUILD_FAILED);        // until this build has succeeded: it may replace or half-write the records
     if (c->opt.gpu_build ? build_tree_gpu(c, clk) : build_tree_host(c)) return 1;
     clk.mark(2);
     // the production kernels' 48-byte triangle records, from the reference-order ones
@@ -735,6 +736,9 @@ extern "C" int mpt_build_tree(mpt_ctx *c) {
     clk.mark(3);
     if (make_wide(c)) return 1;
     clk.mark(4);
+    // the records hold a topology for nfaces faces: what mpt_refit_tree (tree_refit.cpp) keeps
+    c->refit.topo = MPT_TOPO_HELD; c->refit.faces = c->nfaces; c->refit.on_device = c->opt.gpu_build != 0;
+    c->refit.linked = false; c->refit.refits = 0; c->refit.cost_built = c->refit.cost_now = 0;
     return 0;
 }
 

@@ -25,40 +25,10 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "mpt_types.h"
+#include "wide_quant.h"      // the records taken apart, the fixed-point area, the quantisation (shared with refit.hip)
 
 #define WB_BLOCK 256
 #define WB_MAX_LEVELS 64      // levels of the wide tree the level table holds (a binary tree of depth <= 62 collapses into no more)
-
-struct WbChild { int id; float lo[3], hi[3]; };
-
-__device__ __forceinline__ int wb_asi(float f) { return __float_as_int(f); }
-__device__ __forceinline__ float wb_asf(int v) { return __int_as_float(v); }
-
-__device__ __forceinline__ void wb_children_of(const MptVec4 *__restrict__ fnode, int b, WbChild out[2]) {
-    const MptVec4 r0 = fnode[(size_t)b * 4 + 0], r1 = fnode[(size_t)b * 4 + 1], r2 = fnode[(size_t)b * 4 + 2], r3 = fnode[(size_t)b * 4 + 3];
-    out[0].id = wb_asi(r3.x); out[1].id = wb_asi(r3.y);
-    out[0].lo[0] = r0.x; out[1].lo[0] = r0.y; out[0].hi[0] = r0.z; out[1].hi[0] = r0.w;
-    out[0].lo[1] = r1.x; out[1].lo[1] = r1.y; out[0].hi[1] = r1.z; out[1].hi[1] = r1.w;
-    out[0].lo[2] = r2.x; out[1].lo[2] = r2.y; out[0].hi[2] = r2.z; out[1].hi[2] = r2.w;
-}
-
-__device__ __forceinline__ float wb_area(const WbChild &c) {
-    const float dx = fmaxf(c.hi[0] - c.lo[0], 0.f), dy = fmaxf(c.hi[1] - c.lo[1], 0.f), dz = fmaxf(c.hi[2] - c.lo[2], 0.f);
-    return dx * dy + dy * dz + dz * dx;
-}
-
-// surface areas are summed as integers in units of 2^-40 of the root's (the sum of <= 2^22 of them stays below 2^63): the
-// figure is the same bits run to run, whatever order the lanes arrive in (round-3 ADVICE: it was a double atomicAdd per lane)
-__device__ __forceinline__ unsigned long long wb_area_fixed(const MptVec4 *__restrict__ fnode, float a) {
-    WbChild ch[2];
-    wb_children_of(fnode, 0, ch);
-    WbChild root = ch[0];
-    for (int k = 0; k < 3; k++) { root.lo[k] = fminf(ch[0].lo[k], ch[1].lo[k]); root.hi[k] = fmaxf(ch[0].hi[k], ch[1].hi[k]); }
-    const double ra = (double)wb_area(root);
-    if (!(ra > 0.0)) return 0ull;
-    const double r = fmin(fmax((double)a / ra, 0.0), 1.0);
-    return (unsigned long long)(r * 1099511627776.0);
-}
 
 // expand: wide nodes [lo, lo + count) of one level.  ncount[t] = internal children of wide node lo + t (0 beyond the level)
 __global__ __launch_bounds__(WB_BLOCK) void wb_expand_kernel(const MptVec4 *__restrict__ fnode, const int *__restrict__ bin_of,
@@ -118,35 +88,8 @@ __global__ __launch_bounds__(WB_BLOCK) void wb_expand_kernel(const MptVec4 *__re
     for (int k = 0; k < 4; k++) rec[24 + k] = wb_asf(ids[k]);
     MptVec4 *wo = wnode + (size_t)w * 8;
     for (int k = 0; k < 8; k++) wo[k] = { rec[4 * k], rec[4 * k + 1], rec[4 * k + 2], rec[4 * k + 3] };
-    // ---- the quantised record: child planes as bytes over the node's own box, rounded outwards by a quarter of a step
-    // more than needed (the kernel's decode q * (scale * inv) + (origin * inv - o * inv) is off by far less)
-    float plo[3] = { INFINITY, INFINITY, INFINITY }, phi[3] = { -INFINITY, -INFINITY, -INFINITY };
-    for (int k = 0; k < cnt; k++)
-        for (int a = 0; a < 3; a++) { plo[a] = fminf(plo[a], ch[k].lo[a]); phi[a] = fmaxf(phi[a], ch[k].hi[a]); }
-    float scale[3];
-    unsigned qlo[3] = { 0, 0, 0 }, qhi[3] = { 0, 0, 0 };
-    for (int a = 0; a < 3; a++) {
-        const float e = phi[a] - plo[a];
-        float sc = e > 0.f ? e / 255.f : 0.f;
-        // 255 steps must reach the far side in f32, and a flat node still needs a positive step
-        while (e > 0.f && plo[a] + 255.f * sc < phi[a]) sc = nextafterf(sc, INFINITY);
-        if (!(sc > 0.f)) sc = fmaxf(fabsf(plo[a]) * 1e-6f, 1e-30f);
-        scale[a] = sc;
-        for (int k = 0; k < 4; k++) {
-            unsigned l = 255, h = 0;                  // unused child: an inverted box
-            if (k < cnt) {
-                const float fl = floorf((ch[k].lo[a] - plo[a]) / sc - 0.25f), fh = ceilf((ch[k].hi[a] - plo[a]) / sc + 0.25f);
-                l = (unsigned)fminf(255.f, fmaxf(0.f, fl));
-                h = (unsigned)fminf(255.f, fmaxf(0.f, fh));
-            }
-            qlo[a] |= l << (8 * k); qhi[a] |= h << (8 * k);
-        }
-    }
-    MptVec4 *qo = qnode + (size_t)w * 4;
-    qo[0] = { plo[0], plo[1], plo[2], scale[0] };
-    qo[1] = { scale[1], scale[2], wb_asf((int)qlo[0]), wb_asf((int)qhi[0]) };
-    qo[2] = { wb_asf((int)qlo[1]), wb_asf((int)qhi[1]), wb_asf((int)qlo[2]), wb_asf((int)qhi[2]) };
-    qo[3] = { wb_asf(ids[0]), wb_asf(ids[1]), wb_asf(ids[2]), wb_asf(ids[3]) };
+    // ---- the quantised record (wide_quant.h)
+    wb_quantise(ch, cnt, ids, qnode + (size_t)w * 4);
     }
     // where this node's internal children start among the workgroup's (exclusive prefix, node order), and the workgroup's total
     __shared__ int wsum[WB_BLOCK / 64];

@@ -71,6 +71,19 @@ def compose_model():
     ModelPool().compose()
 
 
+def refit_tree():
+    '''BVHTree().refit(): after compose_model() (or load_model of as many faces), keep the built trees and fit their boxes to the
+    moved model on the device; returns the growth of the tree's cost since it was built (no reference counterpart: its add-on
+    builds again)'''
+    return BVHTree().refit()
+
+
+def update_tree(max_growth=None):
+    '''BVHTree().update(max_growth): refit where that is allowed and the tree has not grown past max_growth (None: the default),
+    build otherwise; returns 'refit' or 'build', whichever ran last'''
+    return BVHTree().update() if max_growth is None else BVHTree().update(max_growth)
+
+
 def render(aa=True):
     DefaultEngine().render()
 
