@@ -572,6 +572,27 @@ int mpt_refit_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
 int mpt_refit_allowed(int state, int built_faces, int built_on_device, int nfaces, char *why, int why_size);
 double mpt_refit_growth(uint64_t cost_built, uint64_t cost_now);
 
+/* Batch ray queries on the built tree: LinearBVH.intersect(ray, avoid), ptina/tree/lbvh.py:314-347, for n rays at once, by the
+ * build the context's "mode" selects (strict: the reference tree in the reference's order; fast: the binary production tree) --
+ * ptina_amd/csrc/query_kernel.hip, DESIGN.md section 3.15.
+ * o, d: [n][3] origins and directions in world space.  A direction of any length: it is normalised for the caller, so depths are
+ *   world distances.  A ray with a non-finite component, a zero direction, or a direction whose f32 normalisation is not finite is a miss.
+ * avoid: [n] the face each ray ignores (-1, or any number that names no face: none), or NULL.
+ * mpt_query_closest: per ray hit (0 / 1), depth (1e6, the reference's inf, on a miss), index (the face; -1 on a miss), u, v (the
+ *   hit's barycentrics along the face's edges v1 - v0 and v2 - v0; 0 on a miss) and object: where mpt_compose made the model, the
+ *   object whose range of faces holds index; -1 on a miss or where mpt_load_model brought the model.  Each [n]; each may be NULL.
+ * mpt_query_occluded: occ [n] = !(hit == 0 || depth > dis), the reference's shadow test (path.py:50-51); dis [n], NULL = no limit.
+ * Rays go to the device in chunks of at most `chunk` rays (0: 2^22; rounded up to a multiple of 256), which bounds the device
+ *   memory whatever n is; the answers do not depend on it.  n = 0 succeeds and touches nothing.
+ * Launched at the call, behind everything enqueued before (a deferred render lands first), and waited for.  A query changes
+ *   nothing a render reads or writes: film, sampler, counters, selection and marks stay as they are.  Fails like mpt_render where
+ *   no tree is built for the model as it stands (after mpt_load_model, mpt_compose, or an option that steers the build).
+ * mpt_query_kernel_time: HIP-event time (ms) of the query kernels launched since the last call, and their launch count. */
+int mpt_query_closest(mpt_ctx *ctx, int n, const float *o, const float *d, const int32_t *avoid,
+                      int32_t *hit, float *depth, int32_t *index, float *u, float *v, int32_t *object, int chunk);
+int mpt_query_occluded(mpt_ctx *ctx, int n, const float *o, const float *d, const float *dis, const int32_t *avoid, int32_t *occ, int chunk);
+int mpt_query_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
+
 /* Page-locked host buffers for the read-backs above: into such a buffer mpt_get_image /
  * mpt_fast_export_image / mpt_get_film_raw are one DMA; any other buffer is served through a
  * page-locked staging copy.  (The reference's get_image returns a fresh numpy array,

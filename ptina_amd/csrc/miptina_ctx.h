@@ -48,6 +48,9 @@ MPT_DUAL_LAUNCHER(mpt_launch_brute, const MptRenderParams *, int grid, int stack
 // adapt_kernel.hip: adaptive sampling's list render kernel (both builds); samples holds count * nframes records
 MPT_DUAL_LAUNCHER(mpt_launch_adapt_render, const MptRenderParams *, const int32_t *list, int count, MptVec4 *samples, int stack, hipStream_t);
 MPT_DUAL_LAUNCHER(mpt_launch_preview, const MptRenderParams *, int grid, int stack, hipStream_t);
+// query_kernel.hip: the batch ray queries (both builds), one lane per ray of MptQueryArgs
+MPT_DUAL_LAUNCHER(mpt_launch_query_closest, const MptRenderParams *, const MptQueryArgs *, int stack, hipStream_t);
+MPT_DUAL_LAUNCHER(mpt_launch_query_occluded, const MptRenderParams *, const MptQueryArgs *, int stack, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_sobol_update(const int *X, int *Xout, const int *V, float *P, int dim, int rows, int time0,
                                               int count, int keep, int write_x, hipStream_t stream);
 MPT_KERNEL_API hipError_t mpt_launch_combine(MptVec4 *film, const MptVec4 *partial, int ny, int x0, int x1,
@@ -550,6 +553,7 @@ struct mpt_ctx {
     int tree_depth = 0;                  // reference LBVH (strict build)
     int fast_depth = 0;                  // tree the fast build walks (SAH or LBVH)
     bool host_tree_valid = false;        // h_child/h_leaf/... mirror the device tree (lazily downloaded)
+    unsigned tree_seq = 0;               // counts the successful mpt_build_tree calls: a refit keeps the leaf order, a build makes a new one
     // device-side build workspace
     MptModelBufs dmodel;
     MptLbvhBufs lbvh;
@@ -631,6 +635,7 @@ struct mpt_ctx {
         std::vector<unsigned char> dirty;                // per object: changed since the last mpt_compose
         bool relayout = true;                            // objects were added or dropped: the next mpt_compose writes everything
         bool out_valid = false;                          // dmodel holds the last mpt_compose's output (mpt_load_model takes the buffers back)
+        int out_objs = 0;                                // ... of this many objects: the rows of bufs.first (objects added since are not in it)
         unsigned epoch = 0;                              // counts the mpt_compose calls (MptComposeObj::epoch)
         MptComposeBufs bufs;
         MappedBuf<float> bounds;                         // {min3, max3} of the composed positions
@@ -650,6 +655,26 @@ struct mpt_ctx {
         explicit Refit(MptEventPool &ev) : timer(2, ev) {}
         void lose(int why) { if (topo != MPT_TOPO_NONE) topo = why; }
     } refit{events};
+    struct MPT_INTERNAL Query {                          // batch ray queries (tree_query.cpp, query_kernel.hip)
+        DevBuf<float> o, d, dis;                         // a chunk's rays on the device: [cap][3], [cap][3], [cap]
+        DevBuf<int32_t> avoid;                           // [cap]
+        DevBuf<int32_t> out_i; DevBuf<float> out_f;      // its answers: hit | index | object (or occ), depth | u | v, [3][cap] each
+        size_t cap = 0;                                  // rays the chunk buffers hold
+        DevBuf<int32_t> leaf, slot_of;                   // slot -> face and face -> slot of the tree of build tables_seq
+        unsigned tables_seq = 0;
+        MptLaunchTimer timer;                            // {before a chunk's kernel, after it} per launch
+        explicit Query(MptEventPool &ev) : timer(2, ev) {}
+        int reserve(size_t rays) {
+            if (rays <= cap) return 0;
+            cap = 0;
+            for (DevBuf<float> *b : { &o, &d, &dis, &out_f }) b->release();
+            avoid.release(); out_i.release();
+            if (o.reserve(rays * 3) || d.reserve(rays * 3) || dis.reserve(rays) || avoid.reserve(rays) || out_i.reserve(rays * 3) ||
+                out_f.reserve(rays * 3)) return 1;
+            cap = rays;
+            return 0;
+        }
+    } query{events};
     MptDoorInput door;                                   // mpt_display_eval, mpt_noise_eval, mpt_denoise_eval: the caller's accumulators on the device (grown on demand)
     MptLaunchTimer render_timer{2, events};              // PathEngine launches: {kernel start, kernel end}
     MptLaunchTimer denoise_timer{2, events};             // mpt_get_denoised: {before the prologue, after the epilogue} per call
@@ -720,6 +745,9 @@ inline int gather_stack_levels(const mpt_ctx *c) { return mpt_gather_stack_level
 
 // engines.cpp
 MPT_INTERNAL int mlt_flush(mpt_ctx *c);       // mpt_flush, mpt_render: launch the Metropolis iterations enqueued so far
+
+// tree_build.cpp
+MPT_INTERNAL int download_tree(mpt_ctx *c);   // before anything reads c->h_leaf / h_child / ...: fetch the reference-layout arrays once per build
 
 // scene_compose.cpp
 MPT_INTERNAL int model_on_host(mpt_ctx *c);   // before anything reads c->verts / c->mtlids: fetch them once if mpt_compose made the model

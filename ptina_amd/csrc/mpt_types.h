@@ -177,6 +177,20 @@ struct MptMltArgs {
     float lsp, sigma;                        // MLTPathEngine.LSP / Sigma
 };
 
+// one launch of a batch-query kernel (query_kernel.hip): n rays, what names their faces, and where the answers go.  The tracers speak
+// in leaf slots (the order of tgeo / tfast); callers speak in faces of the model: leaf and slot_of translate
+struct MptQueryArgs {
+    const float *o, *d;                      // [n][3] origins and directions (any length: the lane normalises)
+    const int32_t *avoid;                    // [n] the face each ray ignores (-1: none), or null
+    const float *dis;                        // [n] occlusion: how far each ray looks, or null (as far as MPT_INF)
+    const int32_t *leaf, *slot_of;           // [faces] slot -> face and face -> slot of the built tree
+    const int32_t *first;                    // [nobj] the objects' first faces (compose.hip), or null: the model has no object table
+    int32_t nobj, n;
+    // structure-of-arrays answers, each [n] or null: the closest kernel's ...
+    int32_t *hit; float *depth; int32_t *index; float *u, *v; int32_t *object;
+    int32_t *occ;                            // ... and the occlusion kernel's
+};
+
 // one conversion launch of mpt_get_display (display.hip): mpt_display_params as the kernels take it
 struct MptDisplayArgs {
     int32_t op, transfer, layout, dither;    // MPT_TONE_*, MPT_TRANSFER_*, MPT_LAYOUT_* of include/miptina.h

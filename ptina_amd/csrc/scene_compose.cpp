@@ -172,7 +172,7 @@ extern "C" int mpt_compose(mpt_ctx *c) {
     }
     HIP_TRY(hipStreamSynchronize(c->stream));          // (also: the uploads above read host vectors that end with this call)
     std::fill(cp.dirty.begin(), cp.dirty.end(), 0);
-    cp.relayout = false; cp.out_valid = true;
+    cp.relayout = false; cp.out_valid = true; cp.out_objs = nobj;
     c->nfaces = n;
     c->max_mtlid = -1;
     for (int o = 0; o < nobj; o++)

@@ -739,10 +739,11 @@ extern "C" int mpt_build_tree(mpt_ctx *c) {
     // the records hold a topology for nfaces faces: what mpt_refit_tree (tree_refit.cpp) keeps
     c->refit.topo = MPT_TOPO_HELD; c->refit.faces = c->nfaces; c->refit.on_device = c->opt.gpu_build != 0;
     c->refit.linked = false; c->refit.refits = 0; c->refit.cost_built = c->refit.cost_now = 0;
+    c->tree_seq++;                               // a new leaf order (tree_query.cpp keeps its tables by it)
     return 0;
 }
 
-static int download_tree(mpt_ctx *c) {
+int download_tree(mpt_ctx *c) {
     if (c->host_tree_valid) return 0;
     const int n = c->nfaces, ni = n > 1 ? n - 1 : 0;
     c->h_child.assign((size_t)std::max(ni, 1) * 2, 0); c->h_leaf.assign(std::max(n, 1), 0); c->h_mc.assign(std::max(n, 1), 0);

@@ -1,7 +1,8 @@
 '''
 linear BVH (reference tree/lbvh.py).  build() = Morton codes -> keyed sort -> Karras
 hierarchy -> boxes, packed into the traversal records (csrc/miptina.cpp mpt_build_tree);
-intersect() (lbvh.py:314-347) is csrc/pt_device.h bvh_closest / bvh_occluded.
+intersect() (lbvh.py:314-347) is csrc/pt_device.h bvh_closest / bvh_occluded inside the engines' kernels, and -- asked from
+Python for a batch of rays -- intersect() / occluded() / pick() below (csrc/query_kernel.hip).
 '''
 
 from ..common import *                # noqa: F401,F403
@@ -69,6 +70,71 @@ class LinearBVH:
         k = max(n - 1, 0)
         return dict(child=child[:k], leaf=leaf[:n], bmin=bmin[:k], bmax=bmax[:k], mc=mc[:n],
                     depth=depth.value)
+
+    # ------------------------------------------------------------ batch ray queries (reference lbvh.py:314-347, one ray per call there)
+    def intersect(self, o, d, avoid=None, chunk=0):
+        '''the closest hit of each of n rays against the built tree, by the context's build.  o and d broadcast to [n][3] (one
+        origin with many directions works); d may have any length -- it is normalised for the caller, so depth is a world
+        distance; avoid is a face (scalar or [n]; -1 or None: none) the ray ignores.  A ray with a non-finite component or a zero
+        direction is a miss.  Returns a dict of numpy arrays [n]: hit (bool), depth (f32; 1e6, the reference's inf, on a miss),
+        index (the face, -1 on a miss), u, v (the hit's barycentrics along v1 - v0 and v2 - v0) and object (the object of
+        ModelPool().load_meshes whose faces hold index; -1 on a miss or for a model that came from load()).  Raises where the
+        tree is not built for the model as it stands.  chunk: rays per launch (0: the library's default)'''
+        o, d, n = _rays(o, d)
+        av = _per_ray(avoid, n, np.int32, 'avoid')
+        out = {k: np.zeros(n, t) for k, t in (('hit', np.int32), ('depth', np.float32), ('index', np.int32), ('u', np.float32),
+                                              ('v', np.float32), ('object', np.int32))}
+        ctx().call('mpt_query_closest', n, fptr(o), fptr(d), None if av is None else iptr(av), iptr(out['hit']), fptr(out['depth']),
+                   iptr(out['index']), fptr(out['u']), fptr(out['v']), iptr(out['object']), int(chunk))
+        out['hit'] = out['hit'] != 0
+        return out
+
+    def occluded(self, o, d, dis=np.inf, avoid=None, chunk=0):
+        '''the reference's shadow test for each of n rays (path.py:50-51): is there a hit no farther than dis?  o, d and avoid as
+        intersect takes them; dis a scalar or [n] (inf: any hit counts).  Returns bool [n]'''
+        o, d, n = _rays(o, d)
+        av = _per_ray(avoid, n, np.int32, 'avoid')
+        di = None if np.ndim(dis) == 0 and dis == np.inf else _per_ray(dis, n, np.float32, 'dis')
+        occ = np.zeros(n, np.int32)
+        ctx().call('mpt_query_occluded', n, fptr(o), fptr(d), None if di is None else fptr(di), None if av is None else iptr(av),
+                   iptr(occ), int(chunk))
+        return occ != 0
+
+    def pick(self, x, y):
+        '''what the camera sees at clip point (x, y), each in [-1, 1]: (object, face, depth) of the closest hit of the camera ray
+        through it, or None.  The ray is generated on the host from the f32 matrix Camera() uploaded, as the kernels'
+        camera_generate does (reference camera.py:34-39); a convenience over intersect()'''
+        from ..camera import Camera
+        M = Camera().V2W
+        one = np.float32(1)
+        a = M @ np.array([x, y, -one, one], np.float32)
+        b = M @ np.array([x, y, one, one], np.float32)
+        o = (a[:3] / a[3]).astype(np.float32)
+        r = self.intersect(o, (b[:3] / b[3]).astype(np.float32) - o)
+        if not r['hit'][0]:
+            return None
+        return int(r['object'][0]), int(r['index'][0]), float(r['depth'][0])
+
+
+def _rays(o, d):
+    '''origins and directions broadcast against each other to contiguous f32 [n][3] -> (o, d, n)'''
+    o, d = np.asarray(o, np.float32), np.asarray(d, np.float32)
+    if o.ndim == 0 or d.ndim == 0 or o.shape[-1] != 3 or d.shape[-1] != 3:
+        raise ValueError('origins %s and directions %s: the last axis must hold 3 numbers' % (o.shape, d.shape))
+    o, d = np.broadcast_arrays(o.reshape(-1, 3), d.reshape(-1, 3))
+    return np.ascontiguousarray(o), np.ascontiguousarray(d), int(o.shape[0])
+
+
+def _per_ray(value, n, dtype, what):
+    '''None, a scalar or [n] -> None or a contiguous [n] array'''
+    if value is None:
+        return None
+    a = np.asarray(value, dtype)
+    if a.ndim == 0:
+        return np.full(n, a, dtype)
+    if a.shape != (n,):
+        raise ValueError('%s has shape %s for %d rays' % (what, a.shape, n))
+    return np.ascontiguousarray(a)
 
 
 @register

@@ -84,6 +84,23 @@ def update_tree(max_growth=None):
     return BVHTree().update() if max_growth is None else BVHTree().update(max_growth)
 
 
+def intersect(o, d, avoid=None):
+    '''BVHTree().intersect(o, d, avoid): the closest hits of a batch of rays against the built tree -- a dict of arrays hit, depth,
+    index, u, v, object (the reference asks its tree one ray at a time, inside a kernel: lbvh.py:314-347)'''
+    return BVHTree().intersect(o, d, avoid)
+
+
+def occluded(o, d, dis=float('inf'), avoid=None):
+    '''BVHTree().occluded(o, d, dis, avoid): for each ray of a batch, is anything within dis along it?'''
+    return BVHTree().occluded(o, d, dis, avoid)
+
+
+def pick(x, y):
+    '''BVHTree().pick(x, y): (object, face, depth) under clip point (x, y) of the camera, or None -- the object to hand to
+    set_object_world'''
+    return BVHTree().pick(x, y)
+
+
 def render(aa=True):
     DefaultEngine().render()
 
