@@ -608,6 +608,12 @@ int mpt_get_counters(mpt_ctx *ctx, mpt_counters *out);
  * *nwaves = waves recorded. */
 int mpt_get_timeline(mpt_ctx *ctx, unsigned long long *out /* [cap_waves][8] */, int cap_waves, int *nwaves);
 int mpt_reset_counters(mpt_ctx *ctx);
+/* Which SHADE stage the last render launch was compiled for: *feat = the feature mask (what option "shade_inst" reads: 0 plain,
+ * 31 generic), *lean = 1 when it was the lean variant of the plain instantiation -- every material the model uses, and the default
+ * material, has sheen and subsurface exactly 0 and untextured, and the kernel holds neither term -- else 0.  Both are -1 before
+ * the first launch.  The variant renders the plain and the generic kernel's film bit for bit; the environment variable
+ * MIPTINA_SHADE_LEAN=0, read when the context is created, keeps every launch off it (A/B timing). */
+int mpt_get_shade_variant(mpt_ctx *ctx, int *feat, int *lean);
 /* Diagnostics (options "lane_hist" = 1 and "count" = 1; no counterpart in the reference): out[0 .. 195) = how many NODE / LEAF / SHADE
  * stages the waves issued with k of their 64 lanes taking part ([3][65]); out[195 .. 231) = the lane-steps of those stages by bounce
  * depth and ray kind ([3][6][closest, shadow]); out[231 .. 255) = the gather kernels' NODE lane-steps by log2 bucket of the node's

@@ -194,6 +194,7 @@ SIGNATURES = {
     'mpt_get_counters': (_i, [_vp, C.POINTER(Counters)]),
     'mpt_get_timeline': (_i, [_vp, C.POINTER(C.c_ulonglong), _i, C.POINTER(_i)]),
     'mpt_reset_counters': (_i, [_vp]),
+    'mpt_get_shade_variant': (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     'mpt_get_lane_hist': (_i, [_vp, C.POINTER(C.c_uint64), _i]),
     'mpt_probe_kernel': (_i, [_vp, _i, _i, C.POINTER(C.c_double)]),
     'mpt_stress_copies': (_i, [_vp, _i, _i]),
@@ -385,6 +386,12 @@ class Context:
         v = C.c_int(0)
         self.call('mpt_get_option', key.encode(), C.byref(v))
         return v.value
+
+    def shade_variant(self):
+        '''(feature mask, lean) of the SHADE stage the last render launch ran (mpt_get_shade_variant); (-1, -1) before the first'''
+        feat, lean = C.c_int(0), C.c_int(0)
+        self.call('mpt_get_shade_variant', C.byref(feat), C.byref(lean))
+        return feat.value, lean.value
 
     def unit_eval(self, name, rows):
         '''test door (mpt_unit_eval): one device function of the hot path on rows of inputs, by the build the

@@ -166,6 +166,7 @@ extern "C" mpt_ctx *mpt_create(const mpt_caps *caps, int device) {
             fac[0] = dflt[0]; fac[1] = dflt[1]; fac[2] = dflt[2];
             for (int k = 1; k < 12; k++) fac[k * 4] = dflt[2 + k];
             c->default_feat = shade_feat_material(fac, nullptr);
+            c->default_lean = shade_lean_material(fac, nullptr);
         }
         hipMemcpyAsync(c->mats, z.data(), z.size() * sizeof(MptMaterial), hipMemcpyHostToDevice, c->stream);
         mpt_launch_derive_materials(c->mats, (int)z.size(), c->stream);
@@ -174,6 +175,8 @@ extern "C" mpt_ctx *mpt_create(const mpt_caps *caps, int device) {
     for (int i = 0; i < 16; i++) c->v2w[i] = c->w2v[i] = (i % 5 == 0) ? 1.f : 0.f;
     default_light(c);
     if (upload_lights(c)) return bail("lights upload");
+    // A/B timing of the lean SHADE variant (shade_feat.h): read here once, no option
+    if (const char *v = getenv("MIPTINA_SHADE_LEAN")) c->lean_on = atoi(v) != 0;
     return c;
 }
 
@@ -434,12 +437,25 @@ extern "C" int mpt_load_model(mpt_ctx *c, const float *verts, const int32_t *mtl
 static int scene_feat_now(const mpt_ctx *c) {
     return shade_feat_scene(c->mat_feat.data(), (int)c->mat_feat.size(), c->max_mtlid, c->default_feat, (int)c->h_lights.size(), c->world_tex);
 }
+// ... and whether the same materials leave sheen and subsurface at zero (shade_lean_scene), formed where it is used as well
+static int scene_lean_now(const mpt_ctx *c) {
+    return shade_lean_scene(c->mat_lean.data(), (int)c->mat_lean.size(), c->max_mtlid, c->default_lean);
+}
+
+// Which SHADE the last render launch ran: *feat as option "shade_inst" reports it, *lean = 1 for the lean variant of the plain
+// instantiation, 0 for any other kernel; both -1 before the first launch
+extern "C" int mpt_get_shade_variant(mpt_ctx *c, int *feat, int *lean) {
+    if (!c || !feat || !lean) return fail("null argument");
+    *feat = c->last_shade_feat;
+    *lean = c->last_shade_lean;
+    return 0;
+}
 
 extern "C" int mpt_load_materials(mpt_ctx *c, const float *fac, const int32_t *tex, int m) {
     if (use(c)) return 1;
     if (m < 0 || m > c->caps.max_materials) return fail("%d materials exceed max_materials=%d", m, c->caps.max_materials);
     std::vector<MptMaterial> h(std::max(m, 1));
-    std::vector<unsigned char> feat((size_t)m);
+    std::vector<unsigned char> feat((size_t)m), lean((size_t)m);
     int max_tex = -1;
     for (int i = 0; i < m; i++) {
         MptMaterial &M = h[i];
@@ -456,12 +472,15 @@ extern "C" int mpt_load_materials(mpt_ctx *c, const float *fac, const int32_t *t
             max_tex = std::max(max_tex, t);
         }
         feat[i] = (unsigned char)shade_feat_material(f, M.tex);
+        lean[i] = (unsigned char)shade_lean_material(f, M.tex);
     }
     c->max_mat_tex = max_tex;
     // records beyond m keep what an earlier call left in them on the device, so their bits are kept as well
     // (the scene's mask is formed from these at every launch: scene_feat_now)
     if (c->mat_feat.size() < feat.size()) c->mat_feat.resize(feat.size(), 0);
     std::copy(feat.begin(), feat.end(), c->mat_feat.begin());
+    if (c->mat_lean.size() < lean.size()) c->mat_lean.resize(lean.size(), 1);      // (a record never loaded is all-zero: lean)
+    std::copy(lean.begin(), lean.end(), c->mat_lean.begin());
     c->nmats = m;
     if (m) HIP_TRY(hipMemcpyAsync(c->mats, h.data(), (size_t)m * sizeof(MptMaterial), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(mpt_launch_derive_materials(c->mats, m, c->stream));
@@ -934,16 +953,19 @@ static int launch_render(mpt_ctx *c, const MptRenderParams &p, const BatchSlot &
                          int wide_blocks) {
     // SHADE compiled for what the scene uses: the LDS-resident 4-wide kernel has a plain instantiation, every other kernel the generic code
     const int shade_feat = kc.kernel == MPT_KERNEL_LDS4 ? shade_feat_instantiation(scene_feat_now(c), c->opt.shade_spec) : MPT_FEAT_GENERIC;
+    // ... and the plain one a lean variant, for a scene none of whose materials has sheen or subsurface
+    const int shade_lean = kc.kernel == MPT_KERNEL_LDS4 ? shade_lean_instantiation(shade_feat, scene_lean_now(c), c->lean_on) : 0;
     MptTimedSpan span(c->render_timer, s.rs);
     HIP_TRY(span.begun);
     switch (kc.kernel) {
-    case MPT_KERNEL_LDS4: HIP_TRY(mpt_launch_render_lds4(&p, launch_cus, lds_block, (size_t)kc.lds_bytes, c->opt.count, shade_feat, s.rs)); break;
+    case MPT_KERNEL_LDS4: HIP_TRY(mpt_launch_render_lds4(&p, launch_cus, lds_block, (size_t)kc.lds_bytes, c->opt.count, shade_feat, shade_lean, s.rs)); break;
     case MPT_KERNEL_LDS: HIP_TRY(mpt_launch_render_lds(&p, launch_cus, lds_block, (size_t)kc.lds_bytes, c->opt.count, s.rs)); break;
     case MPT_KERNEL_WIDE: HIP_TRY(mpt_launch_render_wide(&p, wide_blocks, c->opt.count, c->opt.wide_quant, s.rs)); break;
     default:    // MPT_KERNEL_GATHER: the binary tree, in either build (strict: a workgroup per tile; fast: persistent workgroups on the launch's CUs)
         HIP_TRY(MPT_LAUNCHER(c, mpt_launch_render)(&p, s.fast ? launch_cus : p.ntiles, gather_stack_levels(c), c->opt.count, s.rs));
     }
     c->last_shade_feat = shade_feat;
+    c->last_shade_lean = shade_lean;
     c->last_kernel = kc.kernel;
     HIP_TRY(span.end());
     return 0;

@@ -35,7 +35,7 @@ MPT_KERNEL_API hipError_t mpt_launch_derive_tfast(const MptVec4 *tgeo, MptVec4 *
 MPT_KERNEL_API hipError_t mpt_wide_blocks(int grid, int count, int quant, int *blocks);
 MPT_KERNEL_API hipError_t mpt_launch_render_wide(const MptRenderParams *, int blocks, int count, int quant, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_render_lds(const MptRenderParams *, int grid, int block, size_t lds_bytes, int count, hipStream_t);
-MPT_KERNEL_API hipError_t mpt_launch_render_lds4(const MptRenderParams *, int grid, int block, size_t lds_bytes, int count, int feat, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_launch_render_lds4(const MptRenderParams *, int grid, int block, size_t lds_bytes, int count, int feat, int lean, hipStream_t);
 // mlt_kernel.hip: the Metropolis engine's chain kernel (both builds), its test door, and the build-independent passes
 MPT_DUAL_LAUNCHER(mpt_launch_mlt_chain, const MptRenderParams *, const MptMltArgs *, int stack, hipStream_t);
 MPT_DUAL_LAUNCHER(mpt_launch_mlt_trace, const MptRenderParams *, const float *X, float *rgb, int n, int stack, hipStream_t);
@@ -538,6 +538,8 @@ struct mpt_ctx {
     int last_div = 1;                    // share of the chip the last launch took: 1/last_div of the CUs
     int last_kernel = 0;                 // what the last flush launched: MPT_KERNEL_* of lds_layout.h (0 binary gather, 1 LDS binary, 2 4-wide gather, 5 LDS 4-wide)
     int last_shade_feat = -1;            // the mask the last render launch was compiled for (MPT_FEAT_PLAIN / MPT_FEAT_GENERIC; -1: none yet)
+    int last_shade_lean = -1;            // ... and whether it was the lean variant of the plain one (mpt_get_shade_variant)
+    bool lean_on = true;                 // false: MIPTINA_SHADE_LEAN=0 was in the environment when the context was created (A/B timing)
 
     // film
     int nx = 0, ny = 0, x0 = 0, x1 = 0;
@@ -580,6 +582,8 @@ struct mpt_ctx {
     DevBuf<MptMaterial> mats;
     std::vector<unsigned char> mat_feat; // shade_feat_material of every record mpt_load_materials last loaded
     int default_feat = 0;                // ... and of the default material (mpt_create)
+    std::vector<unsigned char> mat_lean; // shade_lean_material of the same records ...
+    int default_lean = 1;                // ... and of the default material
     int nmats = 0;                       // material records mpt_load_materials last loaded (mpt_unit_eval refuses ids beyond them)
     int max_mat_tex = -1;                // largest texture id a loaded material names (-1: none): mpt_unit_eval checks it against the loaded images
     DevBuf<MptImage> images;

@@ -907,11 +907,14 @@ DEV void material_get(const MptRenderParams &p, int mtlid, float tu, float tv, D
 }
 #endif
 
-template <int FEAT = MPT_FEAT_GENERIC>
+// LEAN (shade_feat.h shade_lean_scene; with FEAT == MPT_FEAT_PLAIN only): every material has sheen and subsurface exactly zero, and
+// the diffuse lobe is built without the two terms they multiply
+template <int FEAT = MPT_FEAT_GENERIC, bool LEAN = false>
 DEV V3 disney_brdf(const Disney &m, V3 normal, float sign, V3 indir, V3 outdir) {   // disney.py:53-106
     // (a scene without the lobe has the parameter exactly zero in every material: the regions below are the ones the
     //  production build already skips per hit on "parameter == 0", and the half below the surface is a product with it)
     constexpr bool COAT = (FEAT & MPT_FEAT_CLEARCOAT) != 0, TRANS = (FEAT & MPT_FEAT_TRANSMISSION) != 0;
+    static_assert(!LEAN || (FEAT == MPT_FEAT_PLAIN && !MPT_STRICT), "the lean variant belongs to the plain instantiation of the production build");
     float etai = 1.0f, etao = m.ior;
     if (sign < 0.0f) { etai = m.ior; etao = 1.0f; }
 
@@ -935,17 +938,27 @@ DEV V3 disney_brdf(const Disney &m, V3 normal, float sign, V3 indir, V3 outdir) 
         float Fd90 = 0.5f + 2.0f * (cosoh * cosoh) * m.roughness;
         float Fd = lerpf(Fi, 1.0f, Fd90) * lerpf(Fo, 1.0f, Fd90);
 
-        float Fss90 = (cosoh * cosoh) * m.roughness;
-        float Fss = lerpf(Fi, 1.0f, Fss90) * lerpf(Fo, 1.0f, Fss90);
-        float ss = 1.25f * (Fss * (m_rcp(cosi + coso) - 0.5f) + 0.5f);
+        // LEAN: subsurface == 0 and sheen == 0 in every material.  lerpf(0, Fd, ss) is Fd * 1 + ss * 0 and Fsheen is sheencolor *
+        // (Foh * 0), so what the lean variant drops is ss * 0 and + 0: the same value whenever ss and sheencolor are finite (the rule
+        // the clearcoat and transmission skips below follow), and the same bits unless the product in front is -0, which + 0 turns
+        // into +0 (basecolor and Fd are not negative).  (The statements keep their order for the other instantiations.)
+        float ss = 0.0f;
+        if constexpr (!LEAN) {
+            float Fss90 = (cosoh * cosoh) * m.roughness;
+            float Fss = lerpf(Fi, 1.0f, Fss90) * lerpf(Fo, 1.0f, Fss90);
+            ss = 1.25f * (Fss * (m_rcp(cosi + coso) - 0.5f) + 0.5f);
+        }
 
         float Foh = schlickFresnel(cosoh);
-        V3 Fsheen = m.sheencolor * (Foh * m.sheen);
+        V3 Fsheen = v3s(0.0f);
+        if constexpr (!LEAN) Fsheen = m.sheencolor * (Foh * m.sheen);
 
         float Ds = GTR2(cosh_, m.alpha);
         V3 Fs = lerpv(Foh, m.speccolor, v3s(1.0f));
         float Gs = smithGGX_eval(cosi, m.alpha) * smithGGX_eval(coso, m.alpha);
-        V3 diffuse = m.basecolor * (MPT_INV_PI * lerpf(m.subsurface, Fd, ss)) + Fsheen;
+        V3 diffuse;
+        if constexpr (LEAN) diffuse = m.basecolor * (MPT_INV_PI * Fd);
+        else diffuse = m.basecolor * (MPT_INV_PI * lerpf(m.subsurface, Fd, ss)) + Fsheen;
 #if MPT_STRICT
         float fdf = dielectricFresnel(etao, etai, cosoh);
         float Dr = GTR1(cosh_, m.clearcoatAlpha);
@@ -963,14 +976,31 @@ DEV V3 disney_brdf(const Disney &m, V3 normal, float sign, V3 indir, V3 outdir) 
             float Fr = lerpf(Foh, 0.04f, 1.0f);
             coat = 0.25f * m.clearcoat * Gr * Fr * Dr;
         }
-        V3 specular = Fs * Gs * Ds + v3s(coat);
+        // a mask without the lobe: its parameter is the constant 0 and "+ coat" is "+ 0", which changes no result but -0 (Fs, Gs and
+        // Ds are not negative)
+        V3 specular;
+        if constexpr (COAT) specular = Fs * Gs * Ds + v3s(coat);
+        else specular = Fs * Gs * Ds;
         V3 transmit = v3s(0.0f);
         if (TRANS && m.transmission != 0.0f) transmit = m.basecolor * (MPT_INV_PI * dielectricFresnel(etao, etai, cosoh) * Ds);
 #endif
 
-        result = diffuse * (1.0f - m.metallic) * (1.0f - m.transmission);
-        result = result + transmit * (1.0f - m.metallic) * m.transmission;
-        result = result + specular * (1.0f - m.transmission);
+#if !MPT_STRICT
+        if constexpr (!TRANS) {
+            // transmission is the constant 0: x * (1 - 0) is x, and "+ transmit * (1 - metallic) * 0" is "+ 0" (no result but -0
+            // changes; every factor here is a product of non-negative terms).  What is left is diffuse * (1 - metallic) + specular
+            // with both products rounded first, as the kernels with the lobe have them -- there each is multiplied on by (1 -
+            // transmission), so neither can be the product of an fma: the sum is pinned (add_unfused), or -ffp-contract=fast
+            // fuses one of the two products into it
+            const V3 dr = diffuse * (1.0f - m.metallic);
+            result = v3(add_unfused(dr.x, specular.x), add_unfused(dr.y, specular.y), add_unfused(dr.z, specular.z));
+        } else
+#endif
+        {
+            result = diffuse * (1.0f - m.metallic) * (1.0f - m.transmission);
+            result = result + transmit * (1.0f - m.metallic) * m.transmission;
+            result = result + specular * (1.0f - m.transmission);
+        }
     }
     return result;
 }
@@ -994,9 +1024,10 @@ struct Choice {                                                               //
     }
 };
 
-template <int FEAT = MPT_FEAT_GENERIC>
+template <int FEAT = MPT_FEAT_GENERIC, bool LEAN = false>
 DEV BsdfSample disney_bounce(const Disney &m, V3 normal, float sign, V3 indir, V3 samp) {   // disney.py:115-233
     constexpr bool COAT = (FEAT & MPT_FEAT_CLEARCOAT) != 0, TRANS = (FEAT & MPT_FEAT_TRANSMISSION) != 0;
+    static_assert(!LEAN || (FEAT == MPT_FEAT_PLAIN && !MPT_STRICT), "the lean variant belongs to the plain instantiation of the production build");
     BsdfSample result;
     result.outdir = v3s(0.0f); result.pdf = 0.0f; result.color = v3s(0.0f);
 
@@ -1012,7 +1043,9 @@ DEV BsdfSample disney_bounce(const Disney &m, V3 normal, float sign, V3 indir, V
 
     const TanSpace ts = tanspace(normal);
     Choice choice; choice.pdf = 1.0f; choice.w = samp.z;
-    float specrate = lerpf(m.transmission, lerpf(m.metallic, vavg(Fs), 1.0f), 1.0f);
+    // (a mask without transmission: the parameter is the constant 0, and lerpf(0, x, 1) = x * (1 - 0) + 1 * 0 is x)
+    float specrate = lerpf(m.metallic, vavg(Fs), 1.0f);
+    if constexpr (MPT_STRICT || TRANS) specrate = lerpf(m.transmission, specrate, 1.0f);
     float coatrate = 0.04f * m.clearcoat;
 
     specrate = lerpf(specrate, 0.1f, 1.0f);
@@ -1160,11 +1193,19 @@ DEV BsdfSample disney_bounce(const Disney &m, V3 normal, float sign, V3 indir, V
                     }
                 }
             } else {
-                V3 Fs2 = lerpv(Foh, m.speccolor, v3s(1.0f));
+                float Foh_s = Foh;
+                // pinned (seam 3 of profiles/r25_ab_experiments.json): every other production kernel computes Foh above, for this lobe
+                // and the diffuse one, and subtracts the rounded Foh from 1 here.  The lean diffuse lobe has no use for Foh, its
+                // computation sank into this branch, and -ffp-contract=fast fused 1 - x * x^4 into one fma: 93 film elements of
+                // s978 at 128 x 128 x 16 moved by one ulp.  Foh is made opaque, so the difference is taken of the rounded value.
+                if constexpr (LEAN) asm("" : "+v"(Foh_s));
+                V3 Fs2 = lerpv(Foh_s, m.speccolor, v3s(1.0f));
                 result.outdir = outdir;
                 float partial = m_div(0.5f, cosoh * smithGGX(coso, m.alpha));
                 result.pdf = Ds * vavg(Fs2) * partial;
-                result.color = vdivs(Fs2 * partial * (1.0f - m.transmission), choice.pdf);
+                // (without transmission the weights of both lobes lose their factor 1 - 0: x * 1 is x)
+                if constexpr (TRANS) result.color = vdivs(Fs2 * partial * (1.0f - m.transmission), choice.pdf);
+                else result.color = vdivs(Fs2 * partial, choice.pdf);
             }
         }
     } else {
@@ -1172,14 +1213,21 @@ DEV BsdfSample disney_bounce(const Disney &m, V3 normal, float sign, V3 indir, V
         float Fo = schlickFresnel(coso);
         float Fd90 = 0.5f + 2.0f * (cosoh * cosoh) * m.roughness;
         float Fd = lerpf(Fi, 1.0f, Fd90) * lerpf(Fo, 1.0f, Fd90);
-        float Fss90 = (cosoh * cosoh) * m.roughness;
-        float Fss = lerpf(Fi, 1.0f, Fss90) * lerpf(Fo, 1.0f, Fss90);
-        float ss = 1.25f * (Fss * (m_rcp(cosi + coso) - 0.5f) + 0.5f);
-        V3 Fsheen = m.sheencolor * (Foh * m.sheen);
-        V3 diffuse = m.basecolor * (MPT_INV_PI * lerpf(m.subsurface, Fd, ss)) + Fsheen;
+        V3 diffuse;
+        if constexpr (LEAN) {
+            // the lean variant drops ss * 0 and sheencolor * (Foh * 0), as disney_brdf does and with the same reservations
+            diffuse = m.basecolor * (MPT_INV_PI * Fd);
+        } else {
+            float Fss90 = (cosoh * cosoh) * m.roughness;
+            float Fss = lerpf(Fi, 1.0f, Fss90) * lerpf(Fo, 1.0f, Fss90);
+            float ss = 1.25f * (Fss * (m_rcp(cosi + coso) - 0.5f) + 0.5f);
+            V3 Fsheen = m.sheencolor * (Foh * m.sheen);
+            diffuse = m.basecolor * (MPT_INV_PI * lerpf(m.subsurface, Fd, ss)) + Fsheen;
+        }
         result.outdir = outdir;
         result.pdf = MPT_INV_PI;
-        result.color = vdivs(diffuse * MPT_PI * (1.0f - m.metallic) * (1.0f - m.transmission), choice.pdf);
+        if constexpr (TRANS) result.color = vdivs(diffuse * MPT_PI * (1.0f - m.metallic) * (1.0f - m.transmission), choice.pdf);
+        else result.color = vdivs(diffuse * MPT_PI * (1.0f - m.metallic), choice.pdf);
     }
 #endif
     return result;

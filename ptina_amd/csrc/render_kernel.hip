@@ -200,9 +200,12 @@ __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds(const MptRend
 // Two instantiations per COUNT: FEAT = MPT_FEAT_GENERIC (every region of SHADE) and MPT_FEAT_PLAIN, launched for a plain scene
 // (untextured materials without clearcoat or transmission, one light, no environment map: the headline scene and BASELINE's
 // configs 1, 2, 3, 5): without the texture, environment-map and light-list regions and without the clearcoat and transmission
-// lobes (shade_feat.h: what keeps its film the generic one's bit for bit)
-template <bool COUNT, int FEAT>
+// lobes (shade_feat.h: what keeps its film the generic one's bit for bit).  A third, LEAN, is the plain one for a scene whose
+// materials all have sheen and subsurface exactly zero (shade_feat.h shade_lean_scene: the headline scene, s34, the default
+// material, everything a glTF file becomes): without the two terms of the diffuse lobe they multiply, the same film again
+template <bool COUNT, int FEAT, bool LEAN = false>
 __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds4(const MptRenderParams p) {
+    static_assert(!LEAN || FEAT == MPT_FEAT_PLAIN, "the lean variant is instantiated with the plain mask only");
     extern __shared__ __attribute__((aligned(16))) MptVec4 smem[];
     const MptLdsRegions lay = mpt_lds4_regions(p.n, p.nwide, p.lds_nmats);
     unsigned long long *tl = lds_timeline(p);
@@ -238,7 +241,7 @@ __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds4(const MptRen
     stk.ts = p.t_scale;
     Cnt cnt = {};
     WorkQueue wq; wq.ctr = p.work_counter; wq.nitems = p.nitems; wq.q0 = blockIdx.x & 7; wq.qoff = 0;
-    trace_stream<COUNT, FEAT>(p, w, stk, wq, cnt, tl);
+    trace_stream<COUNT, FEAT, LEAN>(p, w, stk, wq, cnt, tl);
     if (tl && (threadIdx.x & 63) == 0) tl[3] = wall_clock64();
     const int fin_tiles = finalise_tiles<MPT_FIN_GROUP_LDS>(p);
     if (tl && (threadIdx.x & 63) == 0) { tl[4] = wall_clock64(); tl[5] = (unsigned long long)fin_tiles; }
@@ -339,9 +342,14 @@ static hipError_t launch_whole_lds(const MptRenderParams *p, int grid, int block
 }
 
 // the same over the 4-wide nodes (p->wnode, p->nwide); feat: the instantiation (shade_feat.h: MPT_FEAT_PLAIN or MPT_FEAT_GENERIC --
-// there is no kernel for any other mask, and asking for one is an error, not a fall-back)
+// there is no kernel for any other mask, and asking for one is an error, not a fall-back); lean: the lean variant, which only the
+// plain mask has
 MPT_KERNEL_API hipError_t mpt_launch_render_lds4(const MptRenderParams *p, int grid, int block, size_t lds_bytes, int count, int feat,
-                                             hipStream_t stream) {
+                                             int lean, hipStream_t stream) {
+    if (lean && feat != MPT_FEAT_PLAIN) return hipErrorInvalidValue;
+    if (lean)
+        return count ? launch_whole_lds<render_kernel_lds4<true, MPT_FEAT_PLAIN, true>>(p, grid, block, lds_bytes, stream)
+                     : launch_whole_lds<render_kernel_lds4<false, MPT_FEAT_PLAIN, true>>(p, grid, block, lds_bytes, stream);
     if (feat == MPT_FEAT_PLAIN)
         return count ? launch_whole_lds<render_kernel_lds4<true, MPT_FEAT_PLAIN>>(p, grid, block, lds_bytes, stream)
                      : launch_whole_lds<render_kernel_lds4<false, MPT_FEAT_PLAIN>>(p, grid, block, lds_bytes, stream);

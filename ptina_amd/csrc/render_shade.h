@@ -20,7 +20,8 @@ enum { SH_END = 0, SH_BOUNCE = 1, SH_SHADOW = 2 };
 #define MPT_SEG(field)
 #endif   // path over (miss: world light added) | next bounce from hitpos | shadow ray first
 // FEAT: the scene's feature mask the kernel is compiled for (shade_feat.h; wave-uniform by construction: the host picks it per launch)
-template <bool COUNT, int FEAT, class WALK>
+// LEAN: the lean variant of the plain instantiation (shade_feat.h shade_lean_scene: no material has sheen or subsurface)
+template <bool COUNT, int FEAT, bool LEAN, class WALK>
 DEV int shade_core(const MptRenderParams &p, const WALK &w, LaneState &L, Cnt &cnt, V3 &hitpos, V3 &sdir, float &sdis) {
     V3 ro = L.to, rd = L.prd;
     const bool was_hit = L.hidx >= 0;
@@ -67,14 +68,14 @@ DEV int shade_core(const MptRenderParams &p, const WALK &w, LaneState &L, Cnt &c
     L.direct = v3s(0.0f);
     if (want_shadow) {
         // evaluated before the visibility is known; dropped if the shadow ray hits (path.py:50-56)
-        V3 brdf_clr = disney_brdf<FEAT>(mat, normal, sign, -rd, li.dir);
+        V3 brdf_clr = disney_brdf<FEAT, LEAN>(mat, normal, sign, -rd, li.dir);
         float brdf_pdf = vavg(brdf_clr);
         float mis = power_heuristic(li.pdf, brdf_pdf);
         V3 direct_li = li.color * mis * brdf_clr * dot_or_zero(normal, li.dir);
         L.direct = L.throughput * direct_li;
     }
     MPT_SEG(pl_prim)
-    BsdfSample brdf = disney_bounce<FEAT>(mat, normal, sign, -rd, v3(u[3], u[4], u[5]));
+    BsdfSample brdf = disney_bounce<FEAT, LEAN>(mat, normal, sign, -rd, v3(u[3], u[4], u[5]));
     L.throughput = L.throughput * brdf.color;
     L.prd = brdf.outdir;
     L.last_brdf_pdf = brdf.pdf;
@@ -205,7 +206,7 @@ DEV void step_leaf(const MptRenderParams &p, const WALK &w, typename WALK::Lifo 
     if (L.st == ST_LEAF) stage_leaf<COUNT>(w, stk, L, cnt);
 }
 
-template <bool COUNT, int FEAT, class WALK>
+template <bool COUNT, int FEAT, bool LEAN = false, class WALK>
 DEV void trace_stream(const MptRenderParams &p, const WALK &w, typename WALK::Lifo stk, WorkQueue wq, Cnt &cnt,
                       unsigned long long *tl = nullptr) {
     // work-item tiles are 2^tw_shift x 2^th_shift pixels (8x8 by default; smaller tiles shorten the
@@ -308,7 +309,7 @@ DEV void trace_stream(const MptRenderParams &p, const WALK &w, typename WALK::Li
             if (L.st == ST_DONE && !L.shadow) {
                 V3 hitpos, sdir;
                 float sdis;
-                const int nk = shade_core<COUNT, FEAT>(p, w, L, cnt, hitpos, sdir, sdis);
+                const int nk = shade_core<COUNT, FEAT, LEAN>(p, w, L, cnt, hitpos, sdir, sdis);
                 L.to = hitpos;
                 if (nk == SH_SHADOW) { L.td = sdir; L.tbest = sdis; L.st = ST_SHADOW; }
                 else L.st = ST_BOUNCE;                                       // SH_END: depth is 5, the sample is stored below

@@ -57,3 +57,29 @@ static inline int shade_feat_scene(const unsigned char *mat_bits, int nmats, int
 static inline int shade_feat_instantiation(int scene_bits, int shade_spec) {
     return (shade_spec && scene_bits == MPT_FEAT_PLAIN) ? MPT_FEAT_PLAIN : MPT_FEAT_GENERIC;
 }
+
+/* The lean variant of the plain instantiation: SHADE without the subsurface and sheen terms of the diffuse lobe (pt_device.h
+ * disney_brdf / disney_bounce, LEAN).  It is no bit of the mask above -- a scene with sheen or subsurface stays MPT_FEAT_PLAIN and
+ * takes the plain kernel as before -- but a second, independent answer the launch asks for when the instantiation is plain.
+ *
+ * A material is lean when sheen (parameter 6) and subsurface (parameter 5) are exactly zero and untextured: the dropped terms are
+ * ss * 0 and sheencolor * (Foh * 0), so -0.0 counts as zero, and any other value, a NaN included, does not. */
+static inline int shade_lean_material(const float *fac, const int32_t *tex) {
+    if (tex && (tex[5] != -1 || tex[6] != -1)) return 0;
+    return fac[5 * 4] == 0.0f && fac[6 * 4] == 0.0f;
+}
+
+/* The scene's answer: every material the model uses (records 0 .. max_mtlid; records that were never loaded are all-zero, which
+ * is lean) and the default material (always) are lean.  mat_lean[i]: shade_lean_material of record i. */
+static inline int shade_lean_scene(const unsigned char *mat_lean, int nmats, int max_mtlid, int default_lean) {
+    if (!default_lean) return 0;
+    for (int i = 0; i < nmats && i <= max_mtlid; i++)
+        if (!mat_lean[i]) return 0;
+    return 1;
+}
+
+/* Three instantiations are built: generic, plain, and plain + lean.  inst: what shade_feat_instantiation chose; lean_on: 0 keeps
+ * every plain scene on the plain kernel (A/B timing). */
+static inline int shade_lean_instantiation(int inst, int scene_lean, int lean_on) {
+    return inst == MPT_FEAT_PLAIN && scene_lean && lean_on;
+}
