@@ -209,6 +209,15 @@ int mpt_get_tree(mpt_ctx *ctx, int32_t *child /*[n-1][2]*/, int32_t *leaf /*[n]*
  * child boxes, qnode [nw][4][4] with 8-bit boxes; any pointer may be NULL; *nw = wide nodes built (0: none) */
 int mpt_get_wide(mpt_ctx *ctx, float *wnode, float *qnode, int cap_nodes, int *nw);
 
+/* test/inspection: the node and triangle records the kernels of both builds fetch, as they lie on the device (no reference
+ * counterpart), for a model of n faces: snode [n-1][2][4] f32 {bmin, child0} {bmax, child1}; fnode [n-1][4][4], three rows
+ * {lo0, lo1, hi0, hi1} and an id row {id0, id1, -, -} (id >= 0: a node, id < 0: leaf slot ~id); tgeo, tshade [n][4][4] and tfast
+ * [n+1][3][4] by leaf slot (record n of tfast: every word 0xffffffff).  Any pointer may be NULL; *nfaces = n, always.  A
+ * non-NULL array with cap_faces < n fails before anything is copied; so does a tree that is not built for the model as it
+ * stands, or an array the context does not hold.  n = 0 and n = 1 have no node records.  Changes nothing a render, a refit or
+ * a query reads. */
+int mpt_get_records(mpt_ctx *ctx, float *snode, float *fnode, float *tgeo, float *tshade, float *tfast, int cap_faces, int *nfaces);
+
 /* Pure sizing rule of the on-device SAH re-partition's workspace (no context, no GPU; the reference has no counterpart: its
  * tree is the LBVH of ptina/tree/lbvh.py:297-305).  For a model of n faces: out[0] = segments a level can hold, out[1] = words
  * of per-segment workspace the build allocates, out[2] = words a level of `nseg` segments writes, out[3] = bins per axis at

@@ -718,6 +718,30 @@ extern "C" int mpt_get_wide(mpt_ctx *c, float *wnode, float *qnode, int cap_node
     return 0;
 }
 
+// test / inspection: the records every kernel of both builds fetches, as they lie on the device -- snode [n-1][2] float4,
+// fnode [n-1][4], tgeo [n][4], tshade [n][4], tfast [n+1][3] (record n: the all-ones record of mpt_build_tree); any pointer
+// may be NULL; *nfaces = n.  Room for fewer than n faces: refused before anything is written.  Reads only
+extern "C" int mpt_get_records(mpt_ctx *c, float *snode, float *fnode, float *tgeo, float *tshade, float *tfast, int cap_faces,
+                               int *nfaces) {
+    if (use_ro(c)) return 1;
+    if (!c->tree_valid) return fail("BVH not built: call build_tree() after load_model()");
+    const int n = c->nfaces, ni = n > 1 ? n - 1 : 0;
+    if (nfaces) *nfaces = n;
+    struct { const char *name; float *out; const MptVec4 *dev; size_t held, rows; } part[5] = {
+        { "snode", snode, c->nodes.snode, c->nodes.snode.cap, (size_t)ni * 2 }, { "fnode", fnode, c->nodes.fnode, c->nodes.fnode.cap, (size_t)ni * 4 },
+        { "tgeo", tgeo, c->tris.tgeo, c->tris.tgeo.cap, (size_t)n * 4 },        { "tshade", tshade, c->tris.tshade, c->tris.tshade.cap, (size_t)n * 4 },
+        { "tfast", tfast, c->tfast, c->tfast.cap, ((size_t)n + 1) * 3 } };
+    for (const auto &p : part) {
+        if (!p.out) continue;
+        if (cap_faces < n) return fail("mpt_get_records: room for %d faces, the records hold %d", cap_faces, n);
+        if (p.rows && (!p.dev || p.held < p.rows)) return fail("mpt_get_records: the context holds no %s records for %d faces", p.name, n);
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (const auto &p : part)
+        if (p.out && p.rows) HIP_TRY(hipMemcpy(p.out, p.dev, p.rows * sizeof(MptVec4), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" int mpt_build_tree(mpt_ctx *c) {
     if (use(c)) return 1;
     BuildClock clk(c);

@@ -71,6 +71,18 @@ class LinearBVH:
         return dict(child=child[:k], leaf=leaf[:n], bmin=bmin[:k], bmax=bmax[:k], mc=mc[:n],
                     depth=depth.value)
 
+    def records(self):
+        '''the node and triangle records the kernels fetch, as they lie on the device (mpt_get_records): a dict of uint32 arrays
+        snode [n-1][2][4], fnode [n-1][4][4], tgeo [n][4][4], tshade [n][4][4] and tfast [n+1][3][4]'''
+        n = C.c_int(0)
+        ctx().call('mpt_get_records', None, None, None, None, None, 0, C.byref(n))
+        n = n.value
+        k = max(n - 1, 0)
+        out = dict(snode=np.zeros((k, 2, 4), np.float32), fnode=np.zeros((k, 4, 4), np.float32), tgeo=np.zeros((n, 4, 4), np.float32),
+                   tshade=np.zeros((n, 4, 4), np.float32), tfast=np.zeros((n + 1, 3, 4), np.float32))
+        ctx().call('mpt_get_records', *(fptr(out[key]) for key in ('snode', 'fnode', 'tgeo', 'tshade', 'tfast')), n, C.byref(C.c_int(0)))
+        return {key: a.view(np.uint32) for key, a in out.items()}
+
     # ------------------------------------------------------------ batch ray queries (reference lbvh.py:314-347, one ray per call there)
     def intersect(self, o, d, avoid=None, chunk=0):
         '''the closest hit of each of n rays against the built tree, by the context's build.  o and d broadcast to [n][3] (one

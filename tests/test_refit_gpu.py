@@ -206,8 +206,8 @@ def _same_film(a, b, what):
 
 @pytest.mark.parametrize('selection', list(ROUND_TRIP))
 def test_round_trip_gives_the_builds_bytes_and_film(fresh, selection):
-    '''s978 (32 x 32 x 4): built, refitted to the jittered scene, refitted back.  gather_binary walks fnode, whose records have no
-    door: their round trip shows in the film and in the cost, which is the same integer again'''
+    '''s978 (32 x 32 x 4): built, refitted to the jittered scene, refitted back.  gather_binary walks fnode: its round trip shows
+    here in the film and in the cost, which is the same integer again, and word for word in tests/test_records_gpu.py'''
     mode, opts = ROUND_TRIP[selection]
     eng, v, m = _engine(mode, opts)
     tv, tm = _moved_model(v, m, 'jitter', 978)

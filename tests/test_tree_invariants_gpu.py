@@ -6,8 +6,9 @@ child boxes exact and enclosing (E1-E4), 8-bit boxes rounded outwards and no loo
 arrays (L1-L5), and the options the LDS kernel sizes its stack by (S1) recomputed from the records.  No case renders.
 
 The binary `fnode` records (what the production build's preview, brute-force and Metropolis kernels and wide = 0 /
-lds_wide = 0 walk) have no door to download them and the collapse drops their inner boxes: they still have no record-level
-check.  Their walks are held to an exhaustive search instead, pixel for pixel, over the host's and the device's SAH pass:
+lds_wide = 0 walk), whose inner boxes the collapse drops, are not checked here: they are downloaded through
+BVHTree().records() and held word for word by tests/record_checks.py in tests/test_records_gpu.py, with `snode` and the
+triangle records.  Their walks are held to an exhaustive search, pixel for pixel, over the host's and the device's SAH pass:
 tests/test_visibility_gpu.py (preview, brute, Metropolis door, kernels 0 and 1).
 '''
 
