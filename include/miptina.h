@@ -602,6 +602,26 @@ int mpt_query_closest(mpt_ctx *ctx, int n, const float *o, const float *d, const
 int mpt_query_occluded(mpt_ctx *ctx, int n, const float *o, const float *d, const float *dis, const int32_t *avoid, int32_t *occ, int chunk);
 int mpt_query_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
 
+/* Test door in the mpt_unit_eval / mpt_mlt_trace idiom: n rays of the caller's through the traversal of the production PathEngine
+ * kernels -- the in-wave state machine of ptina_amd/csrc/render_lane.h over one of its five walk types, each set up and stepped by
+ * its render kernel's own code (ptina_amd/csrc/walk_eval.hip).  Production build only.
+ * walk: MPT_WALK_*.  o, d, avoid, chunk and what is no ray: as mpt_query_closest takes them (chunks hold 2^16 rays at most).
+ * dis == NULL: the closest hit.  hit (0 / 1), depth (1e6 on a miss), index (the face; -1), u, v (0): what the shading stage would
+ *   be handed, the walk's own f32 numbers, no second evaluation.  Each [n]; each may be NULL.
+ * dis [n]: the rays are shadow rays that look as far as dis; hit [n] = occluded, as the shading stage reads it; the other outputs
+ *   are not written.
+ * Fails -- it never falls back to another walk -- for a context in strict mode, where no tree is built for the model as it
+ *   stands, for a 4-wide walk where the 4-wide tree was not built, and for an LDS walk of a scene that does not fit a CU's LDS
+ *   (ptina_amd/csrc/lds_layout.h).  Launched at the call and waited for; changes nothing a render reads or writes. */
+enum { MPT_WALK_GATHER = 0,      /* binary nodes gathered from memory (render_kernel_fast; 32 or 64 stack levels by the tree's depth) */
+       MPT_WALK_LDS = 1,         /* binary nodes in LDS (render_kernel_lds) */
+       MPT_WALK_WIDE_EXACT = 2,  /* 4-wide nodes with exact boxes, gathered (render_kernel_wide, wide_quant = 0) */
+       MPT_WALK_WIDE_QUANT = 3,  /* 4-wide nodes with 8-bit boxes, gathered (render_kernel_wide) */
+       MPT_WALK_LDS4 = 4,        /* 4-wide nodes in LDS (render_kernel_lds4, the headline kernel) */
+       MPT_WALK_COUNT = 5 };
+int mpt_walk_trace(mpt_ctx *ctx, int walk, int n, const float *o, const float *d, const int32_t *avoid, const float *dis,
+                   int32_t *hit, float *depth, int32_t *index, float *u, float *v, int chunk);
+
 /* Page-locked host buffers for the read-backs above: into such a buffer mpt_get_image /
  * mpt_fast_export_image / mpt_get_film_raw are one DMA; any other buffer is served through a
  * page-locked staging copy.  (The reference's get_image returns a fresh numpy array,

@@ -190,6 +190,7 @@ SIGNATURES = {
     'mpt_query_closest': (_i, [_vp, _i, _fp, _fp, _ip, _ip, _fp, _ip, _fp, _fp, _ip, _i]),
     'mpt_query_occluded': (_i, [_vp, _i, _fp, _fp, _fp, _ip, _ip, _i]),
     'mpt_query_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_walk_trace': (_i, [_vp, _i, _i, _fp, _fp, _ip, _fp, _ip, _fp, _ip, _fp, _fp, _i]),
     'mpt_host_alloc': (_vp, [C.c_size_t]),
     'mpt_host_free': (None, [_vp]),
     'mpt_get_counters': (_i, [_vp, C.POINTER(Counters)]),

@@ -643,6 +643,32 @@ int render_entry(mpt_ctx *c, int nframes) {
     return check_ready(c);
 }
 
+// t_scale: 2^-e with 2^e no less than the farthest a ray origin -- a point of the camera's near plane or of a surface, or one of the n
+// origins o [n][3] a caller brings (mpt_walk_trace: the finite ones) -- can be from any point of the scene's bounding sphere (mpt_load_model)
+void fill_t_scale(const mpt_ctx *c, MptRenderParams &p, const float *o, int n) {
+    double reach = c->nfaces > 0 ? 2.0 * c->scene_rad : 1.0;
+    for (int corner = 0; corner < 4 && c->nfaces > 0; corner++) {
+        const double x = (corner & 1) ? 1.0 : -1.0, y = (corner & 2) ? 1.0 : -1.0;
+        const float *M = c->v2w;
+        const double a3 = M[12] * x + M[13] * y - M[14] + M[15];
+        double d2 = 0;
+        for (int k = 0; k < 3; k++) {
+            const double o = (M[4 * k] * x + M[4 * k + 1] * y - M[4 * k + 2] + M[4 * k + 3]) / a3;
+            d2 += (o - c->scene_cen[k]) * (o - c->scene_cen[k]);
+        }
+        if (std::isfinite(d2)) reach = std::max(reach, std::sqrt(d2) + c->scene_rad);
+    }
+    for (int r = 0; r < n && c->nfaces > 0; r++) {
+        double d2 = 0;
+        for (int k = 0; k < 3; k++) d2 += ((double)o[3 * (size_t)r + k] - c->scene_cen[k]) * ((double)o[3 * (size_t)r + k] - c->scene_cen[k]);
+        if (std::isfinite(d2)) reach = std::max(reach, std::sqrt(d2) + c->scene_rad);
+    }
+    int e = 0;
+    std::frexp(std::min(std::max(reach * 1.001, 1e-30), 1e30), &e);       // reach * 1.001 <= 2^e
+    p.t_scale = (float)std::ldexp(1.0, -e);
+    p.t_unscale = (float)std::ldexp(1.0, e);
+}
+
 int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes) {
     if (check_ready(c)) return 1;
     // the production kernels address a frame's Sobol row and a triangle's shading record by 32-bit offsets from a scalar base, and
@@ -660,25 +686,7 @@ int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes) {
     p.stripe_pitch = c->stripe_w ? c->stripe_w * c->stripe_mod : (1 << 30);
     p.tiles_y = (c->ny + MPT_TILE - 1) / MPT_TILE;
     p.ntiles = p.tiles_x * p.tiles_y;
-    {   // t_scale: 2^-e with 2^e no less than the farthest a ray origin -- a point of the camera's near plane or of a surface -- can be
-        // from any point of the scene's bounding sphere (mpt_load_model)
-        double reach = c->nfaces > 0 ? 2.0 * c->scene_rad : 1.0;
-        for (int corner = 0; corner < 4 && c->nfaces > 0; corner++) {
-            const double x = (corner & 1) ? 1.0 : -1.0, y = (corner & 2) ? 1.0 : -1.0;
-            const float *M = c->v2w;
-            const double a3 = M[12] * x + M[13] * y - M[14] + M[15];
-            double d2 = 0;
-            for (int k = 0; k < 3; k++) {
-                const double o = (M[4 * k] * x + M[4 * k + 1] * y - M[4 * k + 2] + M[4 * k + 3]) / a3;
-                d2 += (o - c->scene_cen[k]) * (o - c->scene_cen[k]);
-            }
-            if (std::isfinite(d2)) reach = std::max(reach, std::sqrt(d2) + c->scene_rad);
-        }
-        int e = 0;
-        std::frexp(std::min(std::max(reach * 1.001, 1e-30), 1e30), &e);       // reach * 1.001 <= 2^e
-        p.t_scale = (float)std::ldexp(1.0, -e);
-        p.t_unscale = (float)std::ldexp(1.0, e);
-    }
+    fill_t_scale(c, p, nullptr, 0);
     p.wnode = c->wnode; p.qnode = c->qnode; p.nwide = c->wide_nodes; p.stack_spill = nullptr;
     p.snode = c->nodes.snode; p.fnode = c->nodes.fnode; p.tgeo = c->tris.tgeo; p.tshade = c->tris.tshade; p.tfast = c->tfast;
     p.skip_dark = c->opt.skip_dark >= 0 ? c->opt.skip_dark : (c->opt.mode == MPT_MODE_FAST ? 1 : 0);

@@ -51,6 +51,8 @@ MPT_DUAL_LAUNCHER(mpt_launch_preview, const MptRenderParams *, int grid, int sta
 // query_kernel.hip: the batch ray queries (both builds), one lane per ray of MptQueryArgs
 MPT_DUAL_LAUNCHER(mpt_launch_query_closest, const MptRenderParams *, const MptQueryArgs *, int stack, hipStream_t);
 MPT_DUAL_LAUNCHER(mpt_launch_query_occluded, const MptRenderParams *, const MptQueryArgs *, int stack, hipStream_t);
+// walk_eval.hip: the test door through the production walks (production build only); walk: MPT_WALK_* of include/miptina.h
+MPT_KERNEL_API hipError_t mpt_launch_walk_eval(const MptRenderParams *, const MptQueryArgs *, int walk, int stack, size_t lds_bytes, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_sobol_update(const int *X, int *Xout, const int *V, float *P, int dim, int rows, int time0,
                                               int count, int keep, int write_x, hipStream_t stream);
 MPT_KERNEL_API hipError_t mpt_launch_combine(MptVec4 *film, const MptVec4 *partial, int ny, int x0, int x1,
@@ -665,6 +667,7 @@ struct mpt_ctx {
         DevBuf<int32_t> out_i; DevBuf<float> out_f;      // its answers: hit | index | object (or occ), depth | u | v, [3][cap] each
         size_t cap = 0;                                  // rays the chunk buffers hold
         DevBuf<int32_t> leaf, slot_of;                   // slot -> face and face -> slot of the tree of build tables_seq
+        DevBuf<int> walk_spill;                          // mpt_walk_trace: the spill strip of the 4-wide gather walks, 128 entries per lane of a chunk
         unsigned tables_seq = 0;
         MptLaunchTimer timer;                            // {before a chunk's kernel, after it} per launch
         explicit Query(MptEventPool &ev) : timer(2, ev) {}
@@ -741,6 +744,7 @@ MPT_INTERNAL int timer_readout(mpt_ctx *c, MptLaunchTimer &timer, double *ms0, d
 // what the engines that launch at the call (engines.cpp) and the test door of the device functions (measure.cpp) take from it
 MPT_INTERNAL int render_entry(mpt_ctx *c, int nframes);                          // null context, nframes < 0, "not set up yet": fails at the call
 MPT_INTERNAL int fill_params(mpt_ctx *c, MptRenderParams &p, int nframes);       // the launch parameters of a batch of nframes frames
+MPT_INTERNAL void fill_t_scale(const mpt_ctx *c, MptRenderParams &p, const float *o, int n);   // ... p.t_scale / t_unscale: for the camera, surfaces and n more origins
 MPT_INTERNAL int fill_scene_params(mpt_ctx *c, MptRenderParams &p);              // ... the part that describes lights, world light, camera, materials and images
 // the sampler moves by `count` frames; the points of the last `keep` go to P[0 .. keep) (default: the main stream, c->sP)
 MPT_INTERNAL int sobol_advance(mpt_ctx *c, int count, int keep, hipStream_t stream = nullptr, float *P = nullptr);

@@ -574,6 +574,20 @@ DEV bool bvh_occluded(const MptRenderParams &p, int *lds, V3 ro, V3 rd, int avoi
 
 #else  // ---------------------------------------------------------------- production traversal
 
+// 1 / d of a ray for the slab tests below and in render_lane.h, which take a plane's distance as plane * (1 / d) - o * (1 / d): with a
+// direction component that is exactly +-0 both products are infinite, their difference is a NaN or an infinity whose sign is that
+// of the PLANE's coordinate, not of plane - o, and a box the ray runs through is missed (tests/test_walks_gpu.py, set C: a light
+// straight above a hit point, a mirror on an axis).  The reciprocal is taken of d + 2^-60: a zero of either sign becomes 2^-60 and the
+// expression (plane - o) * 2^60 -- far behind the origin for the planes on one side of it and far beyond every hit for those on the
+// other, whichever sign the component is given: Box.intersect's answer for such a ray (geometries.py:30-32: inside the slab or
+// not).  A component of 2^-35 or more in size is the same number with 2^-60 added, so every other ray keeps its reciprocal bit for
+// bit; below that the planes of the axis lie beyond every distance a scene has either way.  (One value is left as it was: a
+// component of exactly -2^-60 sums to zero.)  One full-rate v_add_f32 with a literal per component where a ray starts, nothing per
+// step and no register: measured on MI355X and not kept, the reciprocal held to +-2^60 by v_med3_f32 (no literal in its three-operand
+// form on gfx950: four more VGPRs in the headline kernel) or by a v_max_f32 / v_min_f32 pair, 0.9 % of the headline each.
+#define MPT_D_MIN 8.673617379884035e-19f           // 2^-60
+DEV V3 ray_inv(V3 d) { return v3(m_rcp(d.x + MPT_D_MIN), m_rcp(d.y + MPT_D_MIN), m_rcp(d.z + MPT_D_MIN)); }
+
 // slab test against [0, tmax] with precomputed 1/d and o/d; returns entry distance
 DEV bool box_fast(float lox, float loy, float loz, float hix, float hiy, float hiz,
                   V3 inv, V3 oinv, float tmax, float *tnear) {
@@ -595,7 +609,7 @@ DEV Hit bvh_walk(const WALK &w, int n, typename WALK::Lifo st, V3 ro, V3 rd, int
     Hit ret; ret.hit = 0; ret.depth = tmax; ret.index = -1; ret.u = 0.0f; ret.v = 0.0f;
     if (COUNT) cnt.rays++;
     if (n < 2) return ret;     // lbvh.py:218,319: with one face the root box is never written
-    V3 inv = v3(m_rcp(rd.x), m_rcp(rd.y), m_rcp(rd.z));
+    V3 inv = ray_inv(rd);
     V3 oinv = ro * inv;
     st.sp = 0;
     int curr = 0;

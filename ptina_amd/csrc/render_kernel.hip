@@ -65,6 +65,7 @@ DEV void trace_pixel(const MptRenderParams &p, const TR &tr, int i, int j, int f
 #include "render_lane.h"
 #include "render_shade.h"
 #include "render_finalise.h"
+#include "render_lds_setup.h"     // the LDS copy-in and launch, shared with the test door (walk_eval.hip)
 #endif
 
 // ---------------------------------------------------------------- gather kernel: 16x16 tile x chunk per workgroup
@@ -127,36 +128,6 @@ DEV unsigned long long *lds_timeline(const MptRenderParams &p) {
     return p.timeline ? p.timeline + MPT_TIMELINE_WORDS * (size_t)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) : nullptr;
 }
 
-// What both walks hold besides their node records, from the kernel's regions: the triangles, the material records and bytes; and the
-// lane's column of the int16 stack region
-template <class WALK>
-DEV void lds_walk_regions(WALK &w, typename WALK::Lifo &stk, MptVec4 *smem, const MptLdsRegions &lay) {
-    const int nnode4 = lay.nnode4, ntri4 = lay.ntri4, nmat4 = lay.nmat4, nmtl4 = lay.nmtl4;
-    w.tgeo = (LdsVec4Ptr)(void *)(smem + nnode4);
-    w.mats = (LdsVec4Ptr)(void *)(smem + nnode4 + ntri4);
-    w.mtl = (LdsU8Ptr)(void *)(smem + nnode4 + ntri4 + nmat4);
-    stk.stack = (LdsShortPtr)(void *)(smem + nnode4 + ntri4 + nmat4 + nmtl4) + threadIdx.x;
-    stk.sp = 0;
-}
-
-// The copy-in both kernels make behind their node records: the triangles, the material records (DEFAULT_LAST: the records the model
-// uses, then the default one) and one material-record byte per triangle (no_mtl: the byte of a triangle without a material)
-template <bool DEFAULT_LAST>
-DEV void lds_copy_tris_mats(const MptRenderParams &p, MptVec4 *smem, const MptLdsRegions &lay, int no_mtl) {
-    const int nnode4 = lay.nnode4, ntri4 = lay.ntri4, nmat4 = lay.nmat4;
-    for (int k = threadIdx.x; k < ntri4; k += blockDim.x) smem[nnode4 + k] = p.tfast[k];
-    for (int k = threadIdx.x; k < nmat4; k += blockDim.x) {
-        const int rec = k / MPT_LDS_MAT_VEC4, w = k - rec * MPT_LDS_MAT_VEC4;
-        const int grec = DEFAULT_LAST && rec == p.lds_nmats ? p.default_mtl : rec;
-        smem[nnode4 + ntri4 + k] = ((const MptVec4 *)(p.mats + grec))[w < 4 ? w : w + 4];
-    }
-    unsigned char *mtl = (unsigned char *)(smem + nnode4 + ntri4 + nmat4);
-    for (int k = threadIdx.x; k < p.n; k += blockDim.x) {
-        const int id = __float_as_int(p.tshade[(size_t)k * 4 + 3].w);
-        mtl[k] = (unsigned char)(id == -1 ? no_mtl : id);
-    }
-}
-
 template <bool COUNT>
 __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds(const MptRenderParams p) {
     extern __shared__ __attribute__((aligned(16))) MptVec4 smem[];
@@ -164,16 +135,7 @@ __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds(const MptRend
     unsigned long long *tl = lds_timeline(p);
     if (tl && (threadIdx.x & 63) == 0) tl[0] = wall_clock64();
     {   // one copy of the scene per CU: coalesced 16-B loads, ds_write_b128
-        for (int k = threadIdx.x; k < (p.n - 1) * 4; k += blockDim.x) {          // 8-byte stores: the records are 8-byte aligned
-            MptVec4 v = p.fnode[k];
-            if ((k & 3) == 3) {                        // {id0, id1, -, -}: internal ids become byte offset / 8
-                const int i0 = __float_as_int(v.x), i1 = __float_as_int(v.y);
-                v.x = __int_as_float(i0 >= 0 ? i0 * (MPT_LDS_NODE_STRIDE / 8) : i0);
-                v.y = __int_as_float(i1 >= 0 ? i1 * (MPT_LDS_NODE_STRIDE / 8) : i1);
-            }
-            float *d = (float *)((char *)smem + (k >> 2) * MPT_LDS_NODE_STRIDE + (k & 3) * 16);
-            *(float2 *)d = make_float2(v.x, v.y); *(float2 *)(d + 2) = make_float2(v.z, v.w);
-        }
+        lds_copy_nodes(p, smem);
         lds_copy_tris_mats<false>(p, smem, lay, p.default_mtl);
     }
     __syncthreads();
@@ -211,26 +173,13 @@ __global__ __launch_bounds__(MPT_LDS_BLOCK) void render_kernel_lds4(const MptRen
     unsigned long long *tl = lds_timeline(p);
     if (tl && (threadIdx.x & 63) == 0) tl[0] = wall_clock64();
     {
-        for (int k = threadIdx.x; k < p.nwide * 7; k += blockDim.x) {
-            const int rec = k / 7, w = k - rec * 7;
-            MptVec4 v = p.wnode[rec * 8 + w];
-            if (w == 6) {
-                // the four ids (LdsWalk4::ODD_IDS): internal ones become the record's byte offset, leaves (slot << 4) | 1
-                const int i0 = __float_as_int(v.x), i1 = __float_as_int(v.y), i2 = __float_as_int(v.z), i3 = __float_as_int(v.w);
-#define MPT_LDS_ID(i) __int_as_float((i) >= 0 ? (i) * MPT_LDS4_NODE_STRIDE : ((~(i)) << 4) | 1)
-                v.x = MPT_LDS_ID(i0); v.y = MPT_LDS_ID(i1); v.z = MPT_LDS_ID(i2); v.w = MPT_LDS_ID(i3);
-#undef MPT_LDS_ID
-            }
-            smem[k] = v;
-        }
+        lds_copy_nodes4(p, smem);
         lds_copy_tris_mats<true>(p, smem, lay, p.lds_nmats);
     }
     __syncthreads();
     if (tl && (threadIdx.x & 63) == 0) tl[1] = wall_clock64();
 
-    if ((unsigned)(unsigned long long)(LdsBytePtr)(LdsVec4Ptr)(void *)smem != 0u) {
-        // node ids are LDS addresses counted from 0: the dynamic LDS must be all the LDS this kernel has (it is; a static __shared__
-        // object added to it one day would move smem)
+    if (!lds_starts_at_zero(smem)) {
         if (threadIdx.x == 0) __hip_atomic_store(p.watchdog, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         return;
     }
@@ -324,23 +273,6 @@ MPT_KERNEL_API hipError_t MPT_SUFFIX(mpt_launch_render)(const MptRenderParams *p
 }
 
 #if !MPT_STRICT
-// a kernel that takes the whole dynamic LDS of a CU (lds_layout.h): lds_bytes = scene records + 2 KiB per stack level; grid = one
-// persistent workgroup per CU.  One instance -- and one "attribute set" flag -- per kernel instantiation.
-template <auto KERNEL>
-static hipError_t launch_whole_lds(const MptRenderParams *p, int grid, int block, size_t lds_bytes, hipStream_t stream) {
-    // function attributes are per device: remember which devices have been told about the 160 KiB
-    static std::atomic<bool> configured[MPT_MAX_DEVICES];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MPT_MAX_DEVICES) return hipErrorInvalidDevice;
-    if (!configured[dev].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, MPT_LDS_BUDGET);
-        if (e != hipSuccess) return e;
-        configured[dev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), lds_bytes, stream, *p);
-    return hipGetLastError();
-}
-
 // the same over the 4-wide nodes (p->wnode, p->nwide); feat: the instantiation (shade_feat.h: MPT_FEAT_PLAIN or MPT_FEAT_GENERIC --
 // there is no kernel for any other mask, and asking for one is an error, not a fall-back); lean: the lean variant, which only the
 // plain mask has
@@ -348,20 +280,20 @@ MPT_KERNEL_API hipError_t mpt_launch_render_lds4(const MptRenderParams *p, int g
                                              int lean, hipStream_t stream) {
     if (lean && feat != MPT_FEAT_PLAIN) return hipErrorInvalidValue;
     if (lean)
-        return count ? launch_whole_lds<render_kernel_lds4<true, MPT_FEAT_PLAIN, true>>(p, grid, block, lds_bytes, stream)
-                     : launch_whole_lds<render_kernel_lds4<false, MPT_FEAT_PLAIN, true>>(p, grid, block, lds_bytes, stream);
+        return count ? launch_whole_lds<render_kernel_lds4<true, MPT_FEAT_PLAIN, true>>(grid, block, lds_bytes, stream, *p)
+                     : launch_whole_lds<render_kernel_lds4<false, MPT_FEAT_PLAIN, true>>(grid, block, lds_bytes, stream, *p);
     if (feat == MPT_FEAT_PLAIN)
-        return count ? launch_whole_lds<render_kernel_lds4<true, MPT_FEAT_PLAIN>>(p, grid, block, lds_bytes, stream)
-                     : launch_whole_lds<render_kernel_lds4<false, MPT_FEAT_PLAIN>>(p, grid, block, lds_bytes, stream);
+        return count ? launch_whole_lds<render_kernel_lds4<true, MPT_FEAT_PLAIN>>(grid, block, lds_bytes, stream, *p)
+                     : launch_whole_lds<render_kernel_lds4<false, MPT_FEAT_PLAIN>>(grid, block, lds_bytes, stream, *p);
     if (feat != MPT_FEAT_GENERIC) return hipErrorInvalidValue;
-    return count ? launch_whole_lds<render_kernel_lds4<true, MPT_FEAT_GENERIC>>(p, grid, block, lds_bytes, stream)
-                 : launch_whole_lds<render_kernel_lds4<false, MPT_FEAT_GENERIC>>(p, grid, block, lds_bytes, stream);
+    return count ? launch_whole_lds<render_kernel_lds4<true, MPT_FEAT_GENERIC>>(grid, block, lds_bytes, stream, *p)
+                 : launch_whole_lds<render_kernel_lds4<false, MPT_FEAT_GENERIC>>(grid, block, lds_bytes, stream, *p);
 }
 
 MPT_KERNEL_API hipError_t mpt_launch_render_lds(const MptRenderParams *p, int grid, int block, size_t lds_bytes, int count,
                                             hipStream_t stream) {
-    return count ? launch_whole_lds<render_kernel_lds<true>>(p, grid, block, lds_bytes, stream)
-                 : launch_whole_lds<render_kernel_lds<false>>(p, grid, block, lds_bytes, stream);
+    return count ? launch_whole_lds<render_kernel_lds<true>>(grid, block, lds_bytes, stream, *p)
+                 : launch_whole_lds<render_kernel_lds<false>>(grid, block, lds_bytes, stream, *p);
 }
 #endif
 

@@ -149,7 +149,7 @@ DEV int classify(int v) {      // what a popped / chosen entry means for the lan
 template <bool COUNT, class WALK>
 DEV void lane_start_ray(LaneState &L, typename WALK::Lifo &stk, V3 o, V3 d, float tmax, bool shadow, Cnt &cnt) {
     L.to = o; L.td = d;
-    L.inv = v3(m_rcp(d.x), m_rcp(d.y), m_rcp(d.z));
+    L.inv = ray_inv(d);                       // (1 / d, finite for a component that is +-0: pt_device.h)
     if constexpr (WALK::T_SCALED) { L.inv = L.inv * stk.ts; tmax *= stk.ts; }
     L.oinv = o * L.inv;
     // which of an axis' two planes the ray enters through: offset of that plane in the node record

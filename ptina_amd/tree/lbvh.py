@@ -17,6 +17,9 @@ import ctypes as C
 # (profiles/r23_refit_bench.json).
 DEFAULT_MAX_GROWTH = 1.4
 
+# the walk types of the production PathEngine kernels, by their MPT_WALK_* numbers (include/miptina.h; walk_trace())
+WALKS = ('gather', 'lds', 'wide_exact', 'wide_quant', 'lds4')
+
 
 class LinearBVH:
     def __init__(self, n=2**22):
@@ -111,6 +114,23 @@ class LinearBVH:
         ctx().call('mpt_query_occluded', n, fptr(o), fptr(d), None if di is None else fptr(di), None if av is None else iptr(av),
                    iptr(occ), int(chunk))
         return occ != 0
+
+    def walk_trace(self, walk, o, d, avoid=None, dis=None, chunk=0):
+        '''test door (mpt_walk_trace, csrc/walk_eval.hip): n rays through the traversal of the production
+        PathEngine kernels -- walk names one of WALKS ('gather', 'lds', 'wide_exact', 'wide_quant', 'lds4') or its number.  o, d
+        and avoid as intersect takes them.  dis None: the closest hit as the shading stage would be handed it -> the dict of
+        intersect() without object, depth / u / v the walk's own f32 values.  dis (a scalar or [n]): the rays are shadow rays ->
+        bool [n], occluded.  Raises -- there is no fall-back -- in strict mode, for a stale tree and for a walk that cannot serve
+        the scene'''
+        o, d, n = _rays(o, d)
+        av = _per_ray(avoid, n, np.int32, 'avoid')
+        di = _per_ray(dis, n, np.float32, 'dis')
+        kind = WALKS.index(walk) if isinstance(walk, str) else int(walk)
+        out = {k: np.zeros(n, t) for k, t in (('hit', np.int32), ('depth', np.float32), ('index', np.int32), ('u', np.float32), ('v', np.float32))}
+        ctx().call('mpt_walk_trace', kind, n, fptr(o), fptr(d), None if av is None else iptr(av), None if di is None else fptr(di),
+                   iptr(out['hit']), fptr(out['depth']), iptr(out['index']), fptr(out['u']), fptr(out['v']), int(chunk))
+        out['hit'] = out['hit'] != 0
+        return out['hit'] if di is not None else out
 
     def pick(self, x, y):
         '''what the camera sees at clip point (x, y), each in [-1, 1]: (object, face, depth) of the closest hit of the camera ray

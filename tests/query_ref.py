@@ -66,6 +66,83 @@ def rays(pos, seed, n=RAYS):
     return o.astype(np.float32), d.astype(np.float32)
 
 
+def octant(d):
+    """the direction octant of each ray, 0 .. 7: bit k set where component k has its sign bit set (as the walks read 1 / d)"""
+    sign = np.signbit(np.asarray(d, np.float32))
+    return sign[:, 0] * 1 + sign[:, 1] * 2 + sign[:, 2] * 4
+
+
+def bounce_rays(pos, o, d, ref, seed):
+    """the rays a path would trace next from the decided hits of (o, d): origins the f64 hit points rounded to f32 -- on the
+    surface, where a camera ray never starts --, avoid the face hit; the first half aimed at a Dirichlet(1, 1, 1) point of a
+    random triangle, the second half with uniform directions -> (o, d, avoid): f32 [m][3], f32 [m][3], int32 [m]"""
+    rng = np.random.default_rng(seed)
+    pos = np.asarray(pos, np.float64)
+    sel = np.flatnonzero(ref['decided'] & ref['hit'])
+    d64 = np.asarray(d, np.float32).astype(np.float64)[sel]
+    d64 /= np.linalg.norm(d64, axis=1, keepdims=True)
+    start = (np.asarray(o, np.float32).astype(np.float64)[sel] + ref['t'][sel, None] * d64).astype(np.float32)
+    m = sel.size
+    half = m // 2
+    tri = rng.integers(0, pos.shape[0], half)
+    w = rng.dirichlet([1.0, 1.0, 1.0], half)
+    target = (pos[tri] * w[:, :, None]).sum(axis=1)
+    nd = rng.normal(size=(m, 3))
+    nd /= np.linalg.norm(nd, axis=1, keepdims=True)
+    nd[:half] = target - start[:half].astype(np.float64)
+    return start, nd.astype(np.float32), ref['index'][sel].astype(np.int32)
+
+
+AXIS_RAYS = 1024
+
+
+def axis_rays(pos, seed, n=AXIS_RAYS):
+    """n f32 rays along the axes' planes: every direction has one component exactly zero and every other ray a second one
+    (1 / d is +-inf there, o / d inf or NaN); half of the zeros are -0.0.  The first half aimed: the origin is a Dirichlet point
+    of a random triangle moved back along the ray (- s d); the second half starts as rays() starts -> (o, d)"""
+    rng = np.random.default_rng(seed)
+    pos = np.asarray(pos, np.float64)
+    lo, hi = pos.reshape(-1, 3).min(axis=0), pos.reshape(-1, 3).max(axis=0)
+    cen, ext = (lo + hi) / 2, hi - lo
+    ext = np.maximum(ext, 0.1 * ext.max())
+    d = rng.normal(size=(n, 3))
+    first = rng.integers(0, 3, n)
+    second = (first + 1 + rng.integers(0, 2, n)) % 3
+    rows = np.arange(n)
+    d[rows, first] = 0.0
+    two = rows[1::2]
+    d[two, second[two]] = 0.0
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    o = cen + (rng.random((n, 3)) - 0.5) * ext * 1.5
+    half = n // 2
+    tri = rng.integers(0, pos.shape[0], half)
+    w = rng.dirichlet([1.0, 1.0, 1.0], half)
+    s = (0.05 + rng.random(half)) * ext.max()
+    o[:half] = (pos[tri] * w[:, :, None]).sum(axis=1) - s[:, None] * d[:half]
+    d = d.astype(np.float32)
+    zero = np.argwhere(d == 0)
+    minus = zero[rng.permutation(zero.shape[0])[:zero.shape[0] // 2]]
+    d[minus[:, 0], minus[:, 1]] = np.float32(-0.0)
+    return o.astype(np.float32), d
+
+
+def far_rays(pos, radii, seed, n=256):
+    """n f32 rays aimed at Dirichlet points of random triangles from `radii` bounding radii away from the model's centre"""
+    rng = np.random.default_rng(seed)
+    pos = np.asarray(pos, np.float64)
+    lo, hi = pos.reshape(-1, 3).min(axis=0), pos.reshape(-1, 3).max(axis=0)
+    cen, rad = (lo + hi) / 2, np.linalg.norm(hi - lo) / 2
+    u = rng.normal(size=(n, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    o = (cen + radii * rad * u).astype(np.float32)
+    tri = rng.integers(0, pos.shape[0], n)
+    w = rng.dirichlet([1.0, 1.0, 1.0], n)
+    target = (pos[tri] * w[:, :, None]).sum(axis=1)
+    # every other ray passes the model by: aimed at a point a radius and a half beside it
+    target[1::2] += 1.5 * rad * np.cross(u[1::2], rng.normal(size=(n // 2, 3)))
+    return o, (target - o.astype(np.float64)).astype(np.float32)
+
+
 def _terms(pos, o, d):
     '''per (ray, triangle): u, v, t, cos, and the triangle's class -> (u, v, t, sure_hit, doubtful, ta - SPHERE R)'''
     v0, e1, e2 = pos[:, 0], pos[:, 1] - pos[:, 0], pos[:, 2] - pos[:, 0]
@@ -143,6 +220,21 @@ def caps(name, ref):
     print(f'{name}: decided {dec:.3f}, decided hits {hits:.3f}, decided misses {misses:.3f} of {ref["decided"].size} rays')
     assert dec >= (0.60 if name == 'flat' else 0.90), (name, dec)
     assert hits >= 0.20 and misses >= 0.20, (name, hits, misses)
+    return dec, hits, misses
+
+
+def caps_of_set(name, which, ref):
+    """the caps of the bounce (B) and axis (C) ray sets, asserted before any kernel output is looked at: decided >= 0.90, decided
+    hits and decided misses >= 0.20 each; set C of the coplanar `flat`: decided >= 0.60, hits >= 0.10"""
+    dec = float(ref['decided'].mean())
+    hits = float((ref['decided'] & ref['hit']).mean())
+    misses = float((ref['decided'] & ~ref['hit']).mean())
+    print(f'{name} set {which}: decided {dec:.3f}, decided hits {hits:.3f}, decided misses {misses:.3f} of {ref["decided"].size} rays')
+    if name == 'flat':
+        assert which == 'C', 'set B is not used on flat: a coplanar model has no bounce hits'
+        assert dec >= 0.60 and hits >= 0.10, (name, which, dec, hits)
+    else:
+        assert dec >= 0.90 and hits >= 0.20 and misses >= 0.20, (name, which, dec, hits, misses)
     return dec, hits, misses
 
 

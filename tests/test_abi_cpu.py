@@ -207,3 +207,16 @@ def test_device_sah_workspace_holds_every_level_up_to_sah_max():
             ch = max(2048, min(16 * nb, (n // 256 + 255) // 256 * 256))       # positions per chunk when a level streams all n
             assert nb in (32, 64, 128, 256, 512, 1024) and out[2] == 24 * nb * (n // ch + nseg)
     assert lib.mpt_sah_workspace(0, 1, out) == 1 and lib.mpt_sah_workspace(10, -1, out) == 1
+
+
+def test_walk_table_mirrors_the_header_enum():
+    '''mpt_walk_trace's walks: the names BVHTree.walk_trace takes are the header's MPT_WALK_* in order, and the door is declared,
+    typed and exported like every other call'''
+    from ptina_amd import _lib
+    from ptina_amd.tree import lbvh
+    src = open(os.path.join(ROOT, 'include', 'miptina.h')).read()
+    enum = {k: int(v) for k, v in re.findall(r'\b(MPT_WALK_[A-Z0-9_]+)\s*=\s*(\d+)', src)}
+    assert enum.pop('MPT_WALK_COUNT') == len(lbvh.WALKS) == len(enum)
+    assert [k for k, _ in sorted(enum.items(), key=lambda kv: kv[1])] == ['MPT_WALK_' + w.upper() for w in lbvh.WALKS]
+    assert 'mpt_walk_trace' in header_symbols() and len(_lib.SIGNATURES['mpt_walk_trace'][1]) == 13
+    assert hasattr(_lib.load_library(), 'mpt_walk_trace')
