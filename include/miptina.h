@@ -549,6 +549,51 @@ int mpt_get_model(mpt_ctx *ctx, float *verts, int32_t *mtlids, int cap_faces, in
 int mpt_compose_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
 int mpt_compose_plan(const int32_t *faces, const int32_t *dirty, int nobj, int64_t *first, int64_t *wg_begin, int64_t *wg_count, int cap);
 
+/* Mesh deformation on the device: glTF 2.0's morph targets and linear-blend skinning for the meshes of the pool, so that a pose
+ * change costs the upload of the pose, one kernel over that object's corners, the partial mpt_compose and mpt_refit_tree.  A MESH
+ * may carry T morph targets (a position and a normal delta per corner) and a skin (four joint indices and four weights per corner,
+ * over njoints joints); an OBJECT of such a mesh carries its own pose: T weights (default 0) and njoints joint matrices (default
+ * identity; 4x4 affine, glTF's globalJoint . inverseBind, in the object's space).  Two objects of one mesh pose independently.
+ * Per corner, in f64, sums left to right without contraction, rounded to f32 once:
+ *   q = p + w_0 dp_0 + w_1 dp_1 + ...   (index order; a target whose weight is exactly 0 is skipped)      m = n + w_0 dn_0 + ...
+ *   with a skin:  M = ((a0 J[j0] + a1 J[j1]) + a2 J[j2]) + a3 J[j3]  per entry of the upper 3x4 (weights as given, not renormalised),
+ *                 q' = M . (q, 1),  m' = M . (m, 0)
+ *   nrm = m' / |m'| (always);  uv copied.
+ * The normal goes through M itself, not its inverse transpose -- the rule mpt_compose applies to the world matrix -- and a zero
+ * normal gives NaN.  The result, the object's DEFORMED COPY, is an ordinary mesh record in the pool that mpt_compose reads instead
+ * of the mesh.
+ * mpt_mesh_set_morph / mpt_mesh_set_skin: once per mesh, before the mesh has an object.  Refuse, naming the argument: an unknown
+ *   mesh; a mesh that already has an object (or already has targets / a skin); T outside [1, 64] or njoints outside [1, 256]; a
+ *   joint index >= njoints; a delta or weight that is not finite; a negative weight.
+ * mpt_object_set_morph_weights / mpt_object_set_joints (mats: [n][16] row-major): refuse an unknown object; n different from the
+ *   mesh's count; an object whose mesh has no targets / no skin; a value that is not finite; a bottom row that is not exactly
+ *   0 0 0 1.  They mark the object changed for mpt_compose.
+ * mpt_compose, for every deformable object whose pose changed: uploads the pose, launches the deform kernel (one launch for all of
+ *   them), then composes as ever.  After objects were added or dropped the copies get their room in the pool behind the meshes and
+ *   every deformable object is deformed again; mpt_mesh_add while copies exist takes their room (the next mpt_compose assigns it
+ *   again), mpt_scene_clear gives it back.  mpt_object_set_world on a deformable object recomposes it without deforming it again.
+ * mpt_get_deformed: the object's deformed copy [3k][8] as the last mpt_compose wrote it; fails for an object that is not
+ *   deformable, before the first mpt_compose, and when cap_faces < k.
+ * mpt_deform_stats: deformable objects of the table; objects and corners the last mpt_compose deformed; pool vertices held by copies.
+ * mpt_deform_kernel_time: HIP-event time (ms) of the deform kernels of the mpt_compose calls since the last call, and their count.
+ * mpt_deform_plan: the run table of a deform launch as a pure function (no context, no GPU): corners[nobj] per object and dirty[nobj]
+ *   (NULL: all) give, for every flagged object with corners, its index and its first block, blocks of 1024 corners, the first
+ *   `cap` of them (any output may be NULL), and the blocks' sum.  Returns the number of runs, -1 for arguments that name no launch.
+ * mpt_skin_check: the validation of a skin's arrays as a pure function.  Returns 0, or 1 bad arrays, 2 njoints outside [1, 256], 3 a joint
+ *   index >= njoints, 4 a weight that is not finite, 5 a negative weight, with the words in why[why_size] (may be NULL). */
+typedef struct {
+    int64_t deformable_objects, deformed_objects, deformed_corners, copy_verts;
+} mpt_deform_info;
+int mpt_mesh_set_morph(mpt_ctx *ctx, int mesh_id, const float *deltas /* [T][3k][6] */, int T);
+int mpt_mesh_set_skin(mpt_ctx *ctx, int mesh_id, const uint16_t *joints /* [3k][4] */, const float *weights /* [3k][4] */, int njoints);
+int mpt_object_set_morph_weights(mpt_ctx *ctx, int obj_id, const double *w, int n);
+int mpt_object_set_joints(mpt_ctx *ctx, int obj_id, const double *mats /* [n][16] */, int n);
+int mpt_get_deformed(mpt_ctx *ctx, int obj_id, float *verts, int cap_faces);
+int mpt_deform_stats(mpt_ctx *ctx, mpt_deform_info *out);
+int mpt_deform_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
+int mpt_deform_plan(const int32_t *corners, const int32_t *dirty, int nobj, int32_t *run_obj, int64_t *run_block, int cap, int64_t *blocks);
+int mpt_skin_check(const uint16_t *joints, const float *weights, int64_t ncorners, int njoints, char *why, int why_size);
+
 /* Refit: after the model's faces moved (mpt_compose after mpt_object_set_world, or mpt_load_model of as many faces), keep the trees
  * of the last mpt_build_tree and fit their boxes to the model again, on the device -- what a viewport does for a moved object instead of
  * building (the reference's add-on builds: blender.py:555-571).

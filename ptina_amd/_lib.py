@@ -81,6 +81,11 @@ class ComposeInfo(C.Structure):
                 ('scene_cen', C.c_double * 3), ('scene_rad', C.c_double)]
 
 
+class DeformInfo(C.Structure):
+    '''mpt_deform_info (include/miptina.h): what mpt_deform_stats hands back'''
+    _fields_ = [('deformable_objects', C.c_int64), ('deformed_objects', C.c_int64), ('deformed_corners', C.c_int64), ('copy_verts', C.c_int64)]
+
+
 class RefitInfo(C.Structure):
     '''mpt_refit_info (include/miptina.h): what mpt_refit_stats hands back'''
     _fields_ = [('faces', C.c_int64), ('wide_nodes', C.c_int64), ('refits', C.c_int64), ('host_fetches', C.c_int64), ('allowed', C.c_int64),
@@ -182,6 +187,15 @@ SIGNATURES = {
     'mpt_get_model': (_i, [_vp, _fp, _ip, _i, C.POINTER(_i)]),
     'mpt_compose_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
     'mpt_compose_plan': (_i, [_ip, _ip, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _i]),
+    'mpt_mesh_set_morph': (_i, [_vp, _i, _fp, _i]),
+    'mpt_mesh_set_skin': (_i, [_vp, _i, C.POINTER(C.c_uint16), _fp, _i]),
+    'mpt_object_set_morph_weights': (_i, [_vp, _i, C.POINTER(C.c_double), _i]),
+    'mpt_object_set_joints': (_i, [_vp, _i, C.POINTER(C.c_double), _i]),
+    'mpt_get_deformed': (_i, [_vp, _i, _fp, _i]),
+    'mpt_deform_stats': (_i, [_vp, C.POINTER(DeformInfo)]),
+    'mpt_deform_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_deform_plan': (_i, [_ip, _ip, _i, _ip, C.POINTER(C.c_int64), _i, C.POINTER(C.c_int64)]),
+    'mpt_skin_check': (_i, [C.POINTER(C.c_uint16), _fp, C.c_int64, _i, C.c_char_p, _i]),
     'mpt_refit_tree': (_i, [_vp]),
     'mpt_refit_stats': (_i, [_vp, C.POINTER(RefitInfo)]),
     'mpt_refit_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
@@ -328,6 +342,36 @@ def compose_plan(faces, dirty=None):
     if nr < 0:
         raise ValueError('face counts name no layout (negative, or more than 2^31 / 3 faces)')
     return first, [(int(begin[r]), int(count[r])) for r in range(nr)]
+
+
+DEFORM_CHUNK, DEFORM_MAX_JOINTS, DEFORM_MAX_TARGETS = 1024, 256, 64      # csrc/mpt_types.h MPT_DEFORM_*
+
+
+def deform_plan(corners, dirty=None):
+    '''mpt_deform_plan (no context, no GPU): per-object corner counts and dirty flags (None: all) -> ([(object, first block), ...] of
+    the launch, its blocks); ValueError for counts that name no launch'''
+    k = np.ascontiguousarray(corners, np.int32).reshape(-1)
+    d = None if dirty is None else np.ascontiguousarray(dirty, np.int32).reshape(-1)
+    if d is not None and d.shape != k.shape:
+        raise ValueError('%d dirty flags for %d objects' % (d.size, k.size))
+    n = int(k.size)
+    obj, block, blocks = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int64), C.c_int64(0)
+    nr = load_library().mpt_deform_plan(iptr(k), None if d is None else iptr(d), n, iptr(obj), block.ctypes.data_as(C.POINTER(C.c_int64)), n,
+                                        C.byref(blocks))
+    if nr < 0:
+        raise ValueError('corner counts name no launch (negative, or more than 2^31 - 1 blocks)')
+    return [(int(obj[r]), int(block[r])) for r in range(nr)], int(blocks.value)
+
+
+def skin_check(joints, weights, njoints):
+    '''mpt_skin_check (no context, no GPU): (verdict, words) for joints [m,4] uint16 and weights [m,4] f32 over njoints joints;
+    verdict 0 accepts'''
+    j, w = np.ascontiguousarray(joints, np.uint16), np.ascontiguousarray(weights, np.float32)
+    if j.ndim != 2 or j.shape[1] != 4 or w.shape != j.shape:
+        raise ValueError('joints and weights must be [m,4], got %s and %s' % (j.shape, w.shape))
+    why = C.create_string_buffer(200)
+    rc = load_library().mpt_skin_check(j.ctypes.data_as(C.POINTER(C.c_uint16)), fptr(w), j.shape[0], int(njoints), why, len(why))
+    return rc, why.value.decode()
 
 
 def devices_isolated():

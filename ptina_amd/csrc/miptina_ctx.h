@@ -7,6 +7,7 @@
 #include "mpt_options.h"
 #include "shade_feat.h"
 #include "refit_rule.h"
+#include "deform_rule.h"
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -93,6 +94,10 @@ MPT_KERNEL_API size_t mpt_compose_groups(size_t nverts);
 MPT_KERNEL_API hipError_t mpt_launch_compose(const float *pool, const MptComposeObj *objs, const int *first, int nobj, int nverts,
                                              const MptComposeRun *runs, int nruns, int blocks, int all, unsigned epoch, float *out,
                                              int *mtlids, float *part, float *bounds_host, hipStream_t);
+// deform.hip: the deformed copies of the objects of a launch's table, written into the pool the meshes lie in (mpt_compose)
+MPT_KERNEL_API hipError_t mpt_launch_deform(float *pool, const MptDeformObj *objs, const MptDeformRun *runs, int nruns, int blocks,
+                                            const float *deltas, const uint16_t *joints, const float *weights, const double *pose,
+                                            hipStream_t stream);
 
 // on-GPU LBVH build (lbvh_build.hip)
 struct MptLbvhBuffers {
@@ -340,6 +345,19 @@ struct MPT_INTERNAL MptModelBufs {         // the device copy of the model
     }
 };
 
+// A buffer that is appended to grows by copying into a larger one (at least twice the size): the first `used` elements are kept, the
+// stream is idle when it returns.  The mesh pool and mesh deformation's arenas grow this way
+template <class T>
+inline int grow_keeping(DevBuf<T> &buf, size_t want, size_t used, hipStream_t stream) {
+    if (want <= buf.cap) return 0;
+    DevBuf<T> bigger;
+    if (bigger.reserve(std::max(want, buf.cap * 2))) return 1;
+    if (used) HIP_TRY(hipMemcpyAsync(bigger, buf, used * sizeof(T), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    buf.swap(bigger);
+    return 0;
+}
+
 // Scene composition's device memory (scene_compose.cpp): the mesh pool grows by copying into a larger buffer (grow_pool), the table
 // and the launch's workspace are sized by the objects and the output
 struct MPT_INTERNAL MptComposeBufs {
@@ -349,15 +367,19 @@ struct MPT_INTERNAL MptComposeBufs {
     DevBuf<MptComposeRun> runs;          // a partial launch's runs of workgroups
     DevBuf<float> part;                  // 6 floats per workgroup of the output: min3, max3 of its positions
     int reserve_table(size_t nobj) { return objs.reserve(nobj) || first.reserve(nobj) || runs.reserve(nobj); }
-    int grow_pool(size_t floats, size_t used, hipStream_t stream) {          // keeps the first `used` floats
-        if (floats <= pool.cap) return 0;
-        DevBuf<float> bigger;
-        if (bigger.reserve(std::max(floats, pool.cap * 2))) return 1;
-        if (used) HIP_TRY(hipMemcpyAsync(bigger, pool, used * sizeof(float), hipMemcpyDeviceToDevice, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        pool.swap(bigger);
-        return 0;
-    }
+    int grow_pool(size_t floats, size_t used, hipStream_t stream) { return grow_keeping(pool, floats, used, stream); }   // keeps the first `used` floats
+};
+
+// Mesh deformation's device memory (scene_deform.cpp): arenas that grow by copying into a larger buffer, as the mesh pool does --
+// the meshes' deltas and skins, appended by mpt_mesh_set_morph / mpt_mesh_set_skin, and the objects' poses -- and a launch's tables
+struct MPT_INTERNAL MptDeformBufs {
+    DevBuf<float> deltas;                // [target][corner][6] f32 of every mesh with targets, back to back
+    DevBuf<uint16_t> joints;             // [corner][4] joint indices of every mesh with a skin, back to back
+    DevBuf<float> weights;               // [corner][4] their weights
+    DevBuf<double> pose;                 // per deformable object: its morph weights, then its joints' 3x4 matrices
+    DevBuf<MptDeformObj> objs;           // a launch's objects
+    DevBuf<MptDeformRun> runs;           // ... and its runs of blocks
+    int reserve_tables(size_t nobj) { return objs.reserve(nobj) || runs.reserve(nobj); }
 };
 
 struct MPT_INTERNAL MptLbvhBufs {          // workspace and result of the device LBVH build (lbvh_build.hip)
@@ -649,6 +671,27 @@ struct mpt_ctx {
         MptLaunchTimer timer;                            // mpt_compose: {before the compose kernel, after the fold} per call
         explicit Compose(MptEventPool &ev) : timer(2, ev) {}
     } compose{events};
+    struct MptDeformMesh { int ntargets = 0, njoints = 0; size_t delta_at = 0, skin_at = 0; };   // what a mesh of the pool carries (arena offsets)
+    struct MptDeformPose {                               // a deformable object: its pose as the host keeps it, and its deformed copy
+        int obj = 0, mesh = 0;
+        std::vector<double> pose;                        // ntargets weights, then njoints x 12: the layout of bufs.pose
+        size_t pose_at = 0; long long copy_vert = -1;    // where they lie on the device (copy_vert -1: no room assigned yet)
+        bool dirty = true;                               // the pose changed since the copy was written
+    };
+    struct MPT_INTERNAL Deform {                         // mesh deformation (scene_deform.cpp: mpt_mesh_set_*, mpt_object_set_*, deform_step)
+        std::vector<MptDeformMesh> meshes;               // per mesh of the pool
+        std::vector<int> obj_mesh, obj_pose;             // per object of the table: its mesh, and its row of `poses` (-1: not deformable)
+        std::vector<MptDeformPose> poses;
+        size_t deltas_used = 0, skin_used = 0;           // floats of bufs.deltas, corners of bufs.joints / weights
+        size_t copy_verts = 0;                           // pool vertices the copies hold, behind the meshes
+        bool stale = true;                               // the copies' room is not assigned, or the pool it lay in has gone
+        std::vector<MptDeformObj> h_objs;                // the last launch's tables as uploaded: they outlive the copies that read them
+        std::vector<MptDeformRun> h_runs;
+        MptDeformBufs bufs;
+        mpt_deform_info stats{};
+        MptLaunchTimer timer;                            // mpt_compose: {before the deform kernel, after it} per launch
+        explicit Deform(MptEventPool &ev) : timer(2, ev) {}
+    } deform{events};
     struct MPT_INTERNAL Refit {                          // mpt_refit_tree (tree_refit.cpp, refit_rule.h)
         int topo = MPT_TOPO_NONE;                        // MptTopoState: do the node records hold a topology, and if not, why not
         int faces = 0; bool on_device = false;           // ... for this many faces, from the device build
@@ -759,6 +802,12 @@ MPT_INTERNAL int download_tree(mpt_ctx *c);   // before anything reads c->h_leaf
 
 // scene_compose.cpp
 MPT_INTERNAL int model_on_host(mpt_ctx *c);   // before anything reads c->verts / c->mtlids: fetch them once if mpt_compose made the model
+
+// scene_deform.cpp: what scene_compose.cpp tells the deform table, and the step of mpt_compose that writes the deformed copies
+MPT_INTERNAL void deform_mesh_added(mpt_ctx *c);                 // a mesh joined the pool: the copies behind the meshes lose their room
+MPT_INTERNAL void deform_object_added(mpt_ctx *c, int mesh_id);
+MPT_INTERNAL void deform_scene_cleared(mpt_ctx *c, int meshes);
+MPT_INTERNAL int deform_step(mpt_ctx *c);                        // before compose_kernel: room, poses, the deform launch; rewrites objs' mesh_vert at a relayout
 
 // film_read.cpp
 MPT_INTERNAL int check_pass(mpt_ctx *c, int pass);

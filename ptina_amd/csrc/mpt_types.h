@@ -210,3 +210,20 @@ struct alignas(16) MptComposeObj {          // 160 bytes: the matrix is read as 
 };
 // a run of consecutive workgroups of a partial launch: output workgroups [wg, wg + next run's `block` - block) are the launch's blocks from `block`
 struct MptComposeRun { int32_t wg, block; };
+
+// mesh deformation (deform.hip): the caps of a mesh's skin and morph targets, one deformable object of a launch -- where its
+// mesh's records and its deformed copy lie in the pool, and where its mesh's deltas / skin and its own pose lie in their arenas --
+// and a run of the launch's blocks: object `obj` of the launch's table takes the blocks from `block`, MPT_DEFORM_CHUNK corners each
+#define MPT_DEFORM_MAX_JOINTS 256           // 96 bytes of LDS each: 24 KB of the CU's 160 KiB
+#define MPT_DEFORM_MAX_TARGETS 64
+#define MPT_DEFORM_CHUNK 1024               // corners per workgroup: four per lane
+struct MptDeformObj {                       // 48 bytes
+    int32_t src_vert, dst_vert;              // first pool vertex of the mesh and of the object's deformed copy
+    int32_t nverts;                          // corners: 3 x faces
+    int32_t ntargets, njoints;               // 0: no morph targets / no skin
+    int32_t pad;
+    int64_t delta_at;                        // the mesh's deltas [ntargets][nverts][6] f32: first float in the arena
+    int64_t skin_at;                         // its skin: first corner in the arenas of indices [.][4] u16 and weights [.][4] f32
+    int64_t pose_at;                         // the object's pose: ntargets weights, then njoints 3x4 matrices, f64: first double
+};
+struct MptDeformRun { int32_t obj, block; };

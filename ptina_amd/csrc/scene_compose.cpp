@@ -1,6 +1,7 @@
 // scene_compose.cpp -- scene composition behind mpt_mesh_add / mpt_object_* / mpt_compose: the mesh pool and
 // the object table on the device, the layout and launch plan (mpt_compose_plan, a pure function), the launch of compose.hip into
-// the buffers the tree builders read, and the lazy host copy of a composed model (model_on_host).
+// the buffers the tree builders read, and the lazy host copy of a composed model (model_on_host).  Objects of meshes that deform
+// are composed from their deformed copies, which scene_deform.cpp's deform_step writes first.
 
 #include "miptina_ctx.h"
 
@@ -68,6 +69,7 @@ extern "C" int mpt_mesh_add(mpt_ctx *c, const float *verts, int k, int *mesh_id)
     }
     cp.meshes.push_back({ cp.pool_verts, k });
     cp.pool_verts += (size_t)k * 3;
+    deform_mesh_added(c);
     if (mesh_id) *mesh_id = (int)cp.meshes.size() - 1;
     return 0;
 }
@@ -83,6 +85,7 @@ extern "C" int mpt_object_add(mpt_ctx *c, int mesh_id, const double world[16], i
     cp.objs.push_back(o);
     cp.dirty.push_back(1);
     cp.relayout = true;
+    deform_object_added(c, mesh_id);
     if (obj_id) *obj_id = (int)cp.objs.size() - 1;
     return 0;
 }
@@ -109,6 +112,7 @@ extern "C" int mpt_scene_clear(mpt_ctx *c, int meshes) {
     cp.objs.clear(); cp.dirty.clear();
     cp.relayout = true;
     if (meshes) { cp.meshes.clear(); cp.pool_verts = 0; }
+    deform_scene_cleared(c, meshes);
     return 0;
 }
 
@@ -135,6 +139,7 @@ extern "C" int mpt_compose(mpt_ctx *c) {
     const size_t groups = mpt_compose_groups((size_t)nverts);
     if (groups * 6 > cp.bufs.part.cap) { replaced = true; if (cp.bufs.part.reserve(groups * 6)) return 1; }
     if (nobj > 0 && (size_t)nobj > cp.bufs.objs.cap) { cp.relayout = true; if (cp.bufs.reserve_table((size_t)nobj)) return 1; }
+    if (deform_step(c)) return 1;                     // the deformed copies first: compose_kernel reads them as meshes (scene_deform.cpp)
     const bool all = cp.relayout || replaced || !cp.out_valid;
     cp.epoch++;
     int ndirty = 0; long long recomposed = 0;

@@ -2,14 +2,15 @@
 triangle mesh model storage (reference model.py).  The mesh is kept on the host until
 BVHTree().build() packs it, leaf-ordered, into the device records (csrc/mpt_types.h) -- or, through
 load_meshes / add_mesh / add_object / compose, object-space meshes and an object table are kept on the device
-and composed there into the model the build reads (csrc/compose.hip).
+and composed there into the model the build reads (csrc/compose.hip); a mesh may carry morph
+targets and a skin, and its objects a pose each, deformed there too (csrc/deform.hip).
 '''
 
 import ctypes as C
 
 from .common import *                 # noqa: F401,F403
 from .common import Singleton, register, ctx, np
-from ._lib import fptr, iptr, ComposeInfo
+from ._lib import fptr, iptr, ComposeInfo, DeformInfo, DEFORM_MAX_JOINTS, DEFORM_MAX_TARGETS
 
 
 @register
@@ -119,6 +120,83 @@ class ModelPool(metaclass=Singleton):
         ctx().call('mpt_compose')
         self._nfaces = sum(self._mesh_faces[m] for m in self._obj_mesh)
         self._composed = True
+
+    # ---- deformation on the device: glTF 2.0's morph targets and linear-blend skinning (csrc/deform.hip, DESIGN.md section 3.17;
+    #      no reference counterpart)
+    def _fresh_mesh(self, mesh):
+        if not 0 <= int(mesh) < len(self._mesh_faces):
+            raise ValueError('unknown mesh %r (%d meshes)' % (mesh, len(self._mesh_faces)))
+        if int(mesh) in self._obj_mesh:
+            raise ValueError('mesh %d already has an object: targets and skins come first' % int(mesh))
+        return int(mesh)
+
+    def add_morph_targets(self, mesh, dp, dn=None):
+        '''T morph targets for a mesh that has no object yet: position deltas dp [T,k,3,3] and normal deltas dn (None: zeros), per
+        face corner, stored as f32.  Objects of the mesh start with all weights 0'''
+        mesh = self._fresh_mesh(mesh)
+        dp = np.asarray(dp)
+        k = self._mesh_faces[mesh]
+        T = dp.shape[0] if dp.ndim == 4 else -1
+        if dp.shape != (T, k, 3, 3):
+            raise ValueError('position deltas must be [T,%d,3,3], got %s' % (k, dp.shape))
+        dn = np.zeros(dp.shape, np.float32) if dn is None else np.asarray(dn)
+        if dn.shape != dp.shape:
+            raise ValueError('normal deltas must be %s, got %s' % (dp.shape, dn.shape))
+        if not 1 <= T <= DEFORM_MAX_TARGETS:
+            raise ValueError('%d morph targets: between 1 and %d' % (T, DEFORM_MAX_TARGETS))
+        rec = np.ascontiguousarray(np.concatenate([dp.reshape(T, k * 3, 3), dn.reshape(T, k * 3, 3)], axis=2), np.float32)
+        ctx().call('mpt_mesh_set_morph', mesh, fptr(rec), T)
+
+    def add_skin(self, mesh, joints, weights, njoints=None):
+        '''a skin for a mesh that has no object yet: joint indices (any integer type) and weights [k,3,4] per face corner, over
+        njoints joints (None: the largest index + 1).  Weights are stored as f32 and used as given, not renormalised.  Objects of the
+        mesh start with identity joint matrices'''
+        mesh = self._fresh_mesh(mesh)
+        joints, weights = np.asarray(joints), np.asarray(weights)
+        k = self._mesh_faces[mesh]
+        if joints.shape != (k, 3, 4) or weights.shape != (k, 3, 4):
+            raise ValueError('joints and weights must be [%d,3,4], got %s and %s' % (k, joints.shape, weights.shape))
+        if not np.issubdtype(joints.dtype, np.integer):
+            raise ValueError('joints must be integers, got %s' % joints.dtype)
+        if njoints is None:
+            njoints = int(joints.max()) + 1 if joints.size else 1
+        njoints = int(njoints)
+        if not 1 <= njoints <= DEFORM_MAX_JOINTS:
+            raise ValueError('%d joints: between 1 and %d' % (njoints, DEFORM_MAX_JOINTS))
+        if joints.size and (int(joints.min()) < 0 or int(joints.max()) >= njoints):      # (before the cast: it would wrap)
+            raise ValueError('joint indices must lie in [0, %d), got %d .. %d' % (njoints, int(joints.min()), int(joints.max())))
+        j = np.ascontiguousarray(joints.reshape(k * 3, 4), np.uint16)
+        w = np.ascontiguousarray(weights.reshape(k * 3, 4), np.float32)
+        ctx().call('mpt_mesh_set_skin', mesh, j.ctypes.data_as(C.POINTER(C.c_uint16)), fptr(w), njoints)
+
+    def set_morph_weights(self, obj, w):
+        '''the morph weights [T] of an object; the next compose() deforms and rewrites this object only'''
+        obj = self._object(obj)
+        w = np.ascontiguousarray(w, np.float64).reshape(-1)
+        ctx().call('mpt_object_set_morph_weights', obj, w.ctypes.data_as(C.POINTER(C.c_double)), int(w.size))
+
+    def set_joints(self, obj, mats):
+        '''the joint matrices [njoints,4,4] of an object (tools.skin.joint_matrices makes them: globalJoint . inverseBind, affine, in
+        the object's space); the next compose() deforms and rewrites this object only'''
+        obj = self._object(obj)
+        m = np.ascontiguousarray(mats, np.float64)
+        if m.ndim != 3 or m.shape[1:] != (4, 4):
+            raise ValueError('joint matrices must be [njoints,4,4], got shape %s' % (m.shape,))
+        ctx().call('mpt_object_set_joints', obj, m.ctypes.data_as(C.POINTER(C.c_double)), int(m.shape[0]))
+
+    def deformed_to_numpy(self, obj):
+        '''the deformed copy of a deformable object as the last compose() wrote it: [3k,8] f32 records in object space'''
+        obj = self._object(obj)
+        k = self._mesh_faces[self._obj_mesh[obj]]
+        arr = np.empty((k * 3, 8), np.float32)
+        ctx().call('mpt_get_deformed', obj, fptr(arr), k)
+        return arr
+
+    def deform_stats(self):
+        '''_lib.DeformInfo: deformable objects, objects and corners the last compose() deformed, pool vertices the copies hold'''
+        info = DeformInfo()
+        ctx().call('mpt_deform_stats', C.byref(info))
+        return info
 
     def compose_stats(self):
         '''_lib.ComposeInfo: faces, faces the last compose() wrote, objects it found changed, fetches of the host copy, bounding sphere'''

@@ -26,6 +26,8 @@ _PASS_THROUGH = {
     # (no reference counterparts: the meshes and the object table stay on the device, model.py)
     'load_meshes': ('ModelPool', 'load_meshes', ('primitives',)),
     'set_object_world': ('ModelPool', 'set_world', ('obj', 'world')),
+    'set_object_morph_weights': ('ModelPool', 'set_morph_weights', ('obj', 'w')),
+    'set_object_joints': ('ModelPool', 'set_joints', ('obj', 'mats')),
     'load_images': ('ImagePool', 'load', ('images',)),
     'load_materials': ('MaterialPool', 'load', ('materials',)),
     'build_tree': ('BVHTree', 'build', ()),
