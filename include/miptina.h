@@ -708,7 +708,7 @@ int mpt_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
  * selects (the strict build's reference-order IEEE code or the production build's fast forms) -- the same inlined
  * functions the render kernels run.  Rows are 4-byte words (f32; i32 for the two hash kinds); the column counts
  * per kind are fixed (checked).  Holds the HIP code directly to vectors computed by the reference's own function
- * bodies (tests/golden/reference_l1.npz); each kind names the reference function it evaluates. */
+ * bodies (tests/golden/reference_l1.npz, reference_disney_cube.npz); each kind names the reference function it evaluates. */
 enum {
     MPT_UNIT_SCHLICK = 0,         /* materials/microfacet.py:9-10   in: cos                                  out: 1 */
     MPT_UNIT_DIELECTRIC = 1,      /* materials/microfacet.py:14-27  in: etai, etao, cosi                     out: 1 */
@@ -741,7 +741,16 @@ enum {
     MPT_UNIT_MATERIAL_GET = 25,   /* mtllib.py:30-38,79-95 + materials/disney.py:13-50  in: mtlid (as a float), tu, tv  out: 14 parameters, speccolor3, sheencolor3, alpha, clearcoatAlpha (22) */
     MPT_UNIT_CAMERA_GENERATE = 26,/* camera.py:34-39                in: x, y                                 out: ro3, rd3 */
     MPT_UNIT_FACE_SIDE = 27,      /* model.py:88-101                in: rd3, vn0 vn1 vn2, s, t (14)          out: the normal get_geometries returns, 1 if it flipped Face.normal; the shading record is packed by the door, not by mpt_load_model: only the flip is under test */
-    MPT_UNIT_KINDS = 28
+    /* Disney.brdf / Disney.bounce as the plain and the plain + lean instantiation of the production SHADE compile them
+     * (csrc/shade_feat.h; pt_device.h disney_brdf<MPT_FEAT_PLAIN, LEAN> / disney_bounce<...>): the columns of kinds 16 and 17.  On a
+     * material the instantiation admits (plain: clearcoat = transmission = 0; lean: sheen = subsurface = 0 as well) the output is the
+     * generic kind's word for word, up to the sign of a zero; vectors: tests/golden/reference_disney_cube.npz.  Production build only:
+     * the strict build has no such instantiation and refuses the kinds with a message. */
+    MPT_UNIT_DISNEY_BRDF_PLAIN = 28,   /* materials/disney.py:13-106     in: as kind 16 (24)                  out: rgb */
+    MPT_UNIT_DISNEY_BOUNCE_PLAIN = 29, /* materials/disney.py:13-50,115-233  in: as kind 17 (24)              out: outdir3, pdf, color3 */
+    MPT_UNIT_DISNEY_BRDF_LEAN = 30,    /* materials/disney.py:13-106     in: as kind 16 (24)                  out: rgb */
+    MPT_UNIT_DISNEY_BOUNCE_LEAN = 31,  /* materials/disney.py:13-50,115-233  in: as kind 17 (24)              out: outdir3, pdf, color3 */
+    MPT_UNIT_KINDS = 32
 };
 int mpt_unit_eval(mpt_ctx *ctx, int kind, const void *in, int in_cols, void *out, int out_cols, int n);
 

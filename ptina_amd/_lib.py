@@ -28,6 +28,8 @@ UNIT_KINDS = {
     # the kinds that read the context's scene (lights, images, materials, world light, camera)
     'light_hit': (21, 6, 6), 'light_sample': (22, 6, 8), 'image_sample': (23, 3, 4), 'world_at': (24, 3, 3),
     'material_get': (25, 3, 22), 'camera_generate': (26, 2, 6), 'face_side': (27, 14, 4),
+    # Disney.brdf / .bounce as the plain and the plain + lean SHADE instantiate them (production build only)
+    'disney_brdf_plain': (28, 24, 3), 'disney_bounce_plain': (29, 24, 7), 'disney_brdf_lean': (30, 24, 3), 'disney_bounce_lean': (31, 24, 7),
 }
 
 

@@ -81,8 +81,11 @@ extern "C" int mpt_unit_eval(mpt_ctx *c, int kind, const void *in, int in_cols, 
     static const int cols[MPT_UNIT_KINDS][2] = {
         { 1, 1 }, { 3, 1 }, { 2, 1 }, { 2, 1 }, { 2, 1 }, { 3, 3 }, { 3, 3 }, { 6, 3 }, { 2, 3 }, { 3, 2 }, { 6, 3 }, { 7, 4 },
         { 12, 3 }, { 30, 9 }, { 10, 1 }, { 15, 4 }, { 24, 3 }, { 24, 7 }, { 2, 1 }, { 1, 1 }, { 2, 1 },
-        { 6, 6 }, { 6, 8 }, { 3, 4 }, { 3, 3 }, { 3, 22 }, { 2, 6 }, { 14, 4 } };
+        { 6, 6 }, { 6, 8 }, { 3, 4 }, { 3, 3 }, { 3, 22 }, { 2, 6 }, { 14, 4 },
+        { 24, 3 }, { 24, 7 }, { 24, 3 }, { 24, 7 } };
     if (kind < 0 || kind >= MPT_UNIT_KINDS) return fail("unit kind %d outside [0, %d)", kind, (int)MPT_UNIT_KINDS);
+    if (kind >= MPT_UNIT_DISNEY_BRDF_PLAIN && kind <= MPT_UNIT_DISNEY_BOUNCE_LEAN && c->opt.mode != MPT_MODE_FAST)
+        return fail("unit kind %d is an instantiation of the production SHADE: the strict build has none (set mode to fast)", kind);
     if (in_cols != cols[kind][0] || out_cols != cols[kind][1])
         return fail("unit kind %d takes %d input and %d output columns, got %d and %d", kind, cols[kind][0], cols[kind][1],
                     in_cols, out_cols);

@@ -805,6 +805,20 @@ DEV float smithGGX_eval(float cosi, float alpha) {
     return m_rcp(cosi + m_sqrt(__builtin_fmaf(-a, b, add_unfused(a, b))));
 }
 #endif
+// pinned (seam 4): the cosines of Disney.brdf.  a.x * b.x + a.y * b.y + a.z * b.z leaves -ffp-contract=fast the choice of which of the
+// first two products it rounds and which it fuses into the sum, and it chose by what else was compiled beside them: evaluated
+// function by function (unit_eval.hip, tests/test_reference_disney_cube_gpu.py) the plain instantiation rounded x * x of the half
+// vector's length and of dot(outdir, normal) where the generic one rounded y * y -- one ulp in cosh, which GTR2 at a mirror direction
+// turns into 600 ulp (32 of 196 plain rows of tests/golden/reference_disney_cube.npz differed, 14 of 104 lean ones).  Written out the way
+// the LDS-resident 4-wide kernels already had them -- the y product rounded first, the x product first where indir is the negated ray
+// direction -- so that every instantiation forms them alike wherever it is inlined.
+#if MPT_STRICT
+DEV float dot_yxz(V3 a, V3 b) { return dot(a, b); }
+DEV float dot_xyz(V3 a, V3 b) { return dot(a, b); }
+#else
+DEV float dot_yxz(V3 a, V3 b) { return __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.x, b.x, a.y * b.y)); }
+DEV float dot_xyz(V3 a, V3 b) { return __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.y, b.y, a.x * b.x)); }
+#endif
 DEV V3 sample_GTR1(float u, float v, float alpha) {                          // :69-71 (NaN for alpha < 1, like the reference)
     u = m_div(m_sqrt(m_pow(alpha, 2.0f - 2.0f * u) - 1.0f), alpha * alpha - 1.0f);
     return spherical(u, v);
@@ -932,11 +946,12 @@ DEV V3 disney_brdf(const Disney &m, V3 normal, float sign, V3 indir, V3 outdir) 
     float etai = 1.0f, etao = m.ior;
     if (sign < 0.0f) { etai = m.ior; etao = 1.0f; }
 
-    V3 halfdir = normalized(indir + outdir);
-    float cosi = dot(indir, normal);
-    float coso = dot(outdir, normal);
-    float cosh_ = dot_or_zero(halfdir, normal);
-    float cosoh = dot_or_zero(halfdir, outdir);
+    const V3 sumdir = indir + outdir;
+    V3 halfdir = sumdir * m_rnorm(dot_yxz(sumdir, sumdir));                 // normalized(indir + outdir); the dot products: seam 4
+    float cosi = dot_xyz(indir, normal);
+    float coso = dot_yxz(outdir, normal);
+    float cosh_ = fmaxf(0.0f, dot_yxz(halfdir, normal));                    // dot_or_zero
+    float cosoh = fmaxf(0.0f, dot_yxz(halfdir, outdir));
 
     V3 result = v3s(0.0f);
     if (coso < 0.0f) {
@@ -964,15 +979,30 @@ DEV V3 disney_brdf(const Disney &m, V3 normal, float sign, V3 indir, V3 outdir) 
         }
 
         float Foh = schlickFresnel(cosoh);
-        V3 Fsheen = v3s(0.0f);
-        if constexpr (!LEAN) Fsheen = m.sheencolor * (Foh * m.sheen);
+#if MPT_STRICT
+        V3 Fsheen = m.sheencolor * (Foh * m.sheen);
+#endif
 
         float Ds = GTR2(cosh_, m.alpha);
         V3 Fs = lerpv(Foh, m.speccolor, v3s(1.0f));
         float Gs = smithGGX_eval(cosi, m.alpha) * smithGGX_eval(coso, m.alpha);
         V3 diffuse;
         if constexpr (LEAN) diffuse = m.basecolor * (MPT_INV_PI * Fd);
+#if MPT_STRICT
         else diffuse = m.basecolor * (MPT_INV_PI * lerpf(m.subsurface, Fd, ss)) + Fsheen;
+#else
+        else {
+            // pinned (seam 5): two sums of two products each -- Fd * (1 - subsurface) + ss * subsurface, and basecolor * k + sheencolor *
+            // (Foh * sheen) -- where -ffp-contract=fast rounds one product and fuses the other as the code around them suggests: evaluated
+            // function by function, 9 of 92 plain rows of tests/golden/reference_disney_cube.npz with sheen or subsurface differed from the
+            // generic instantiation in the last bits.  Written out the way every render kernel already formed them (ss * subsurface and
+            // basecolor * k rounded): their films do not move.
+            const float mix = __builtin_fmaf(Fd, 1.0f - m.subsurface, ss * m.subsurface);
+            const float k = MPT_INV_PI * mix, fs = Foh * m.sheen;
+            const V3 bk = m.basecolor * k;
+            diffuse = v3(__builtin_fmaf(m.sheencolor.x, fs, bk.x), __builtin_fmaf(m.sheencolor.y, fs, bk.y), __builtin_fmaf(m.sheencolor.z, fs, bk.z));
+        }
+#endif
 #if MPT_STRICT
         float fdf = dielectricFresnel(etao, etai, cosoh);
         float Dr = GTR1(cosh_, m.clearcoatAlpha);
@@ -1025,7 +1055,16 @@ struct Choice {                                                               //
     float pdf, w;
     DEV bool operator()(float r) {
         bool ret;
+#if MPT_STRICT
         if (w < r) {
+#else
+        // A rate of 1 (or more) always takes the branch.  The reference's w stays below 1: its division is correctly rounded.  Here
+        // w = (w - r) * v_rcp(1 - r) of an earlier decision can round up to exactly 1.0 -- samp.z the last float below 1 behind the
+        // clearcoat Choice -- and "1 < 1" then fell through a rate of exactly 1 (specrate of a full metal or at grazing incidence,
+        // reflrate under total internal reflection, transmission = 1) into the other lobe with pdf *= 1 - 1: a colour divided by
+        // zero (tests/golden/reference_disney_cube.npz row 318).  For w < 1 the added test changes no decision.
+        if (w < r || r >= 1.0f) {
+#endif
             w = m_div(w, r);
             pdf *= r;
             ret = true;

@@ -25,7 +25,10 @@ enum {
      * -ffp-contract=fast fuses the multiply-adds AROUND a removed branch as it pleases, and without the clearcoat and transmission
      * regions a few film elements moved by one ulp (MI355X, s978 128 x 128 x 16: 181 of 16384 without the clearcoat code, 5 without
      * the transmission code) until the two places where the fusing differed were written out -- pt_device.h GTR2 and smithGGX_eval;
-     * profiles/r08_ab_experiments.json lists them and how they were found.  A new region compiled out wants the same check. */
+     * profiles/r08_ab_experiments.json lists them and how they were found.  A new region compiled out wants the same check.
+     * Compiled on its own (unit_eval.hip, kinds MPT_UNIT_DISNEY_*_PLAIN / _LEAN) disney_brdf showed two more: the dot products of its
+     * cosines and the two two-product sums of its diffuse lobe (pt_device.h dot_yxz / dot_xyz, "seam 5"), written out the way the
+     * render kernels formed them all along; tests/test_reference_disney_cube_gpu.py holds the instantiations word for word. */
 };
 
 /* One material as mpt_load_materials receives it: fac[12][4] (parameter k's factor in fac[k*4], basecolor in

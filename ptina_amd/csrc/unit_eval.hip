@@ -5,7 +5,8 @@
 // build's reference-order IEEE functions, the production build's v_rcp / v_rsq / v_sin / exp2-log2 / FMA forms,
 // its 48-byte triangle records and its shared-lobe Disney.bounce.  tests/test_reference_units_gpu.py feeds it the
 // inputs of tests/golden/reference_l1.npz -- vectors computed by the reference's own function bodies -- so the HIP
-// code is held to the reference's source directly, not through the CPU oracle.
+// code is held to the reference's source directly, not through the CPU oracle.  tests/test_reference_disney_cube_gpu.py feeds the
+// Disney kinds tests/golden/reference_disney_cube.npz, and holds the PLAIN and LEAN kinds (production build) to the generic ones.
 //
 // The kinds from MPT_UNIT_LIGHT_HIT on read the context's scene through the launch parameters (mpt_unit_eval fills the part of
 // MptRenderParams that names lights, world light, camera, materials and images, and checks the ids the rows name): lights_hit,
@@ -113,6 +114,22 @@ __global__ __launch_bounds__(64) void MPT_SUFFIX(unit_eval_kernel)(const MptRend
         st(o, 0, b.outdir); o[3] = b.pdf; st(o, 4, b.color);
         break;
     }
+#if !MPT_STRICT
+    // the same two functions as the plain and the plain + lean SHADE instantiate them (shade_feat.h); mpt_unit_eval refuses these kinds
+    // in the strict build, which has neither
+    case MPT_UNIT_DISNEY_BRDF_PLAIN: st(o, 0, disney_brdf<MPT_FEAT_PLAIN, false>(disney_from14(r), ld(r, 14), r[17], ld(r, 18), ld(r, 21))); break;
+    case MPT_UNIT_DISNEY_BRDF_LEAN: st(o, 0, disney_brdf<MPT_FEAT_PLAIN, true>(disney_from14(r), ld(r, 14), r[17], ld(r, 18), ld(r, 21))); break;
+    case MPT_UNIT_DISNEY_BOUNCE_PLAIN: {
+        const BsdfSample b = disney_bounce<MPT_FEAT_PLAIN, false>(disney_from14(r), ld(r, 14), r[17], ld(r, 18), ld(r, 21));
+        st(o, 0, b.outdir); o[3] = b.pdf; st(o, 4, b.color);
+        break;
+    }
+    case MPT_UNIT_DISNEY_BOUNCE_LEAN: {
+        const BsdfSample b = disney_bounce<MPT_FEAT_PLAIN, true>(disney_from14(r), ld(r, 14), r[17], ld(r, 18), ld(r, 21));
+        st(o, 0, b.outdir); o[3] = b.pdf; st(o, 4, b.color);
+        break;
+    }
+#endif
     case MPT_UNIT_POWER_HEURISTIC: o[0] = power_heuristic(r[0], r[1]); break;                // path.py:11-15
     case MPT_UNIT_WANGHASH: o[0] = __int_as_float(wanghash(__float_as_int(r[0]))); break;    // sampling/__init__.py:9-16
     case MPT_UNIT_WANGHASH2: o[0] = __int_as_float(wanghash2(__float_as_int(r[0]), __float_as_int(r[1]))); break;   // :20-23

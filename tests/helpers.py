@@ -233,10 +233,16 @@ def stress_compare(seed, log=print):
     either film / spp; at most ceil(0.0005 x pixels) pixels may claim that, they still count as outliers, and the rel-RMSE is
     taken without them.  A pixel that is further off than one sample explains fails the scene.
     Returns (ok, fireflies, messages).'''
+    scene, lights, world, nx, ny, spp, batches = stress_scene(seed)
+    return compare_kernels(scene, lights, world, nx, ny, spp, batches, seed, log)
+
+
+def compare_kernels(scene, lights, world, nx, ny, spp, batches, seed, log=print, films=None):
+    '''stress_compare's comparison and accounting for a given scene (seed: what the log line and the messages call it).  films: a
+    dict that receives every kernel's film by name ('strict', 'lds4', ...), for a caller that holds the strict one to the oracle'''
     import math
     from ptina_amd.common import ctx, reset_all
     from ptina_amd.things import FilmTable
-    scene, lights, world, nx, ny, spp, batches = stress_scene(seed)
     imgs, kernels = {}, {}
     for (name, mode, opts), batch in zip(STRESS_KERNELS, batches):
         reset_all()
@@ -286,7 +292,57 @@ def stress_compare(seed, log=print):
     log(f'{seed} {scene[1].shape[0]} tris {nx}x{ny} {spp} spp | ' + ' | '.join(msgs) + f' | lds==bin {same} | lds4==lds on {100 * same4:.3f} % of the pixels | '
         f'fireflies {flies} of at most {kmax} | kernels {kernels}')
     reset_all()
+    if films is not None:
+        films.update(imgs)
     return ok and same, flies, msgs
+
+
+QUILT_MATERIALS = 61          # + the three wall materials = 64, the material pool's default capacity (_lib.Context: max_materials)
+
+
+def quilt_scene(kind, seed=20261020, ntri=300):
+    '''The cornell walls and `ntri` triangles of random place, size and smooth normals in general position (no two coplanar: no
+    coincident surfaces), every triangle in one of QUILT_MATERIALS materials drawn over a class of the Disney parameter cube, a
+    parameter sitting at exactly 0 or 1 in about a third of the draws:
+      'lean'   clearcoat = transmission = 0 and sheen = subsurface = 0, -0.0 among them (shade_feat.h shade_lean_material)
+      'plain'  clearcoat = transmission = 0; sheen and subsurface drawn, and pinned (at least one material each at 1)
+      'cube'   every parameter, clearcoat and transmission included, roughness down to 0, ior in [1, 2]
+    One area light and a constant world light, as the plain instantiation needs.  Returns (scene, lights, world).
+    All three quilts use these triangles rather than the 300-triangle test model with materials per face: the full-cube quilt must
+    have no coincident or coplanar surfaces, which that model's boxes have, and one geometry serves the three.'''
+    from ptina_amd.tools.matrix import translate
+    rng = np.random.default_rng(seed)
+    k = ntri
+    c = rng.uniform([-1.6, 0.3, -1.6], [1.6, 3.4, 1.2], (k, 1, 3))
+    P = c + rng.normal(0, 1, (k, 3, 3)) * rng.uniform(0.1, 0.7, (k, 1, 1))
+    fn = np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
+    fn /= np.linalg.norm(fn, axis=1, keepdims=True) + 1e-30
+    N = fn[:, None, :] + rng.normal(0, 0.25, (k, 3, 3))
+    N /= np.linalg.norm(N, axis=2, keepdims=True)
+    T = rng.uniform(0, 1, (k, 3, 2))
+    M = (3 + np.arange(k) % QUILT_MATERIALS).astype(np.int32)
+    v, m = scenes._compose([scenes.cornell_walls(), (P, N, T, M)])
+
+    def draw():
+        r = rng.random()
+        return 0.0 if r < 0.15 else 1.0 if r < 0.3 else float(rng.random())
+    mats = list(scenes.WALL_MATERIALS)
+    for i in range(QUILT_MATERIALS):
+        p = dict(basecolor=tuple(rng.uniform(0, 1, 3) * (rng.random() > 0.1)), metallic=draw(), roughness=draw(), specular=draw(),
+                 specularTint=draw(), sheenTint=draw(), clearcoatGloss=draw(), ior=float(rng.uniform(1, 2)),
+                 subsurface=draw(), sheen=draw(), clearcoat=draw(), transmission=draw())
+        if kind in ('lean', 'plain'):
+            p['clearcoat'] = p['transmission'] = 0.0
+        if kind == 'lean':
+            p['subsurface'], p['sheen'] = (float(x) for x in rng.choice([0.0, -0.0], 2))
+        if kind == 'plain' and i < 2:
+            p['subsurface' if i else 'sheen'] = 1.0
+        mats.append(scenes.material(**p))
+    rot = np.eye(4)
+    rot[:3, :3] = [[1, 0, 0], [0, 0, 1], [0, -1, 0]]
+    lights = [(translate([0.0, 3.9, 0.0]) @ rot, np.array([16.0, 14.0, 12.0]), 0.5, 'AREA')]
+    world = ([0.2, 0.25, 0.3, 1.0], -1)
+    return (v, m, mats, []), lights, world
 
 
 # ---- function-level comparisons against the reference's own vectors (tests/test_reference_units_gpu.py,

@@ -7,6 +7,13 @@ default one included, all have sheen and subsurface exactly zero runs a kernel c
 multiply.  Its film must be the generic kernel's BIT FOR BIT (raw films compared as uint32, option shade_spec = 1 against 0); a plain
 scene with sheen or subsurface keeps the plain kernel without the variant, and a scene with any feature the generic one.  Which
 variant a launch took is read through mpt_get_shade_variant (Context.shade_variant()): (feature mask, lean).
+
+The quilts (helpers.quilt_scene: 300 triangles in general position, every one in one of 61 materials drawn over a class of the
+parameter cube, parameters at exactly 0 and 1 and -0.0 among them) put the claims tests/test_reference_disney_cube_gpu.py checks
+function by function through the render kernel's own contraction context, at 64 x 64 x 8: the lean quilt must take (PLAIN, 1) and
+the plain quilt (PLAIN, 0), each rendering the generic film bit for bit; the quilt over the full cube -- clearcoat, transmission,
+roughness down to 0 -- holds the strict build to the oracle at helpers.STRICT and every production kernel to the strict film through
+the accounting of helpers.compare_kernels (helpers.FAST, at most ceil(0.0005 x pixels) single-sample fireflies, each explained).
 '''
 
 import numpy as np
@@ -66,13 +73,13 @@ def differing(a, b):
     return np.flatnonzero((a != b).reshape(a.shape[0], -1).any(axis=1))
 
 
-def special_vs_generic(scene, nx, ny, spp, what, want_variant, scene_feat=PLAIN):
+def special_vs_generic(scene, nx, ny, spp, what, want_variant, scene_feat=PLAIN, lights=None, world=None):
     '''renders `scene` with shade_spec = 1, then 0: the first launch reports `want_variant`, the second the generic kernel, and no
     film element differs'''
     from helpers import setup_engine
     from ptina_amd.common import ctx, reset_all
     reset_all()
-    eng = setup_engine(scene, nx, ny, mode='fast')
+    eng = setup_engine(scene, nx, ny, mode='fast', lights=lights, world=world)
     c = ctx()
     assert c.shade_variant() == (-1, -1), 'nothing launched yet'
     assert c.get_option('scene_feat') == scene_feat, what
@@ -139,3 +146,39 @@ def test_reloading_materials_moves_the_selection_both_ways(fresh):
     assert (variant, k) == ((PLAIN, 1), 5)
     assert differing(back, first).size == 0, 'lean -> sheen -> lean'
     reset_all()
+
+
+def quilt(kind):
+    from helpers import quilt_scene, QUILT_MATERIALS
+    scene, lights, world = quilt_scene(kind)
+    used = np.unique(scene[1])
+    assert QUILT_MATERIALS >= 32 and len(scene[2]) == 3 + QUILT_MATERIALS and used.size == len(scene[2]), 'every material is on a face'
+    return scene, lights, world
+
+
+def test_lean_quilt_takes_the_lean_variant_and_renders_the_generic_film(fresh):
+    scene, lights, world = quilt('lean')
+    sheen = np.array([m[6][0] for m in scene[2]]), np.array([m[5][0] for m in scene[2]])
+    assert all((x == 0).all() for x in sheen) and (np.signbit(sheen[0]) | np.signbit(sheen[1])).sum() >= 8, '-0.0 among the lean materials'
+    special_vs_generic(scene, 64, 64, 8, 'lean quilt 64x64 8 spp', (PLAIN, 1), lights=lights, world=world)
+
+
+def test_plain_quilt_keeps_the_plain_kernel_and_renders_the_generic_film(fresh):
+    scene, lights, world = quilt('plain')
+    sheen, subs = np.array([m[6][0] for m in scene[2]]), np.array([m[5][0] for m in scene[2]])
+    assert (sheen == 1).any() and (subs == 1).any() and (sheen[3:] == 0).any() and ((sheen > 0) & (sheen < 1)).sum() >= 8
+    special_vs_generic(scene, 64, 64, 8, 'plain quilt 64x64 8 spp', (PLAIN, 0), lights=lights, world=world)
+
+
+def test_full_cube_quilt_strict_against_the_oracle_and_production_against_strict(fresh, oracle_mod):
+    from helpers import STRICT, assert_parity, compare_kernels, setup_oracle
+    scene, lights, world = quilt('cube')
+    cc, tr, rough = (np.array([m[k][0] for m in scene[2][3:]]) for k in (8, 10, 2))
+    assert (cc > 0).sum() >= 8 and (tr > 0).sum() >= 8 and (rough == 0).any() and (tr == 1).any() and (cc == 1).any()
+    nx, ny, spp = 64, 64, 8
+    films = {}
+    ok, flies, msgs = compare_kernels(scene, lights, world, nx, ny, spp, [8, 8, 3, 8, 5], 'full-cube quilt', films=films)
+    assert ok, msgs
+    ref = setup_oracle(oracle_mod, scene, nx, ny, lights=lights, world=world)
+    ref.render(spp)
+    assert_parity(films['strict'], ref.get_image(), *STRICT, what='full-cube quilt %dx%dx%d, strict build against the oracle' % (nx, ny, spp))
