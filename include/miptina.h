@@ -667,6 +667,77 @@ enum { MPT_WALK_GATHER = 0,      /* binary nodes gathered from memory (render_ke
 int mpt_walk_trace(mpt_ctx *ctx, int walk, int n, const float *o, const float *d, const int32_t *avoid, const float *dis,
                    int32_t *hit, float *depth, int32_t *index, float *u, float *v, int chunk);
 
+/* Reprojection: after the camera or the model changed, carry film pass 0 over to the new view instead of starting from nothing --
+ * the temporal half's first step of spatiotemporal variance-guided filtering (ptina_amd/csrc/history_kernel.hip, history.hip,
+ * history_rule.h; the numpy restatement tests/reproject_ref.py).  A context remembers ONE rendered view,
+ * the history:   render ... -> mpt_history_keep -> edit the scene / camera -> mpt_compose, mpt_refit_tree -> mpt_history_reproject -> render ...
+ * The reference has nothing of the kind.  A context that never calls these entries behaves bit for bit as before.
+ * mpt_history_keep: launches what is enqueued, then remembers the view as it stands: v2w and w2v as uploaded, the film size, the
+ *   face count, a device copy of the model's vertex positions (36 bytes per face) and a G-buffer from one kernel that traces every
+ *   pixel's centre ray, camera_generate(((i + 0.5) / nx) * 2 - 1, ((j + 0.5) / ny) * 2 - 1), by the build the context's "mode"
+ *   selects: per pixel `face` (the face hit; -1 on a miss), `id` (the object of mpt_compose's table whose range of faces holds it;
+ *   0 where mpt_load_model brought the model; -1 on a miss) and `depth` (the hit's distance along the normalised ray from its
+ *   origin; 1e6 on a miss; in the production build evaluated once more in f64, as mpt_query_closest does).  Pixels outside the
+ *   context's slab or stripes hold (-1, -1, 0).  Fails like mpt_render where no tree is built for the model as it stands.  Writes
+ *   no film pass, no mark, no selection and no sampler state; a history kept before is replaced.
+ * mpt_history_reproject: launches what is enqueued, then refuses -- naming the cause, and changing nothing -- when there is no
+ *   history, when the film size or the model's face count is not the kept one, when no tree is built for the model as it
+ *   stands, when max_history is not positive or +inf, when depth_tol is not finite and positive.  Else two kernels run.
+ *   MOTION traces the centre ray of every pixel p = (i, j) of the context's share in the NEW view and scene; all arithmetic below
+ *   is f32, one rounding per operation, never contracted.  A miss: cur_id = -1, and the pixel is BACKGROUND-KEPT (fx = i, fy = j,
+ *   d_exp = 0) iff the kept and the current v2w and w2v are equal word for word; else it has no place in the kept view.  A hit on
+ *   face f at barycentrics u, v and distance depth (the production build's second evaluation; the strict build's own values), with
+ *   a, b, c the KEPT positions of f's corners: if the cameras are equal word for word and so are a, b, c and the current
+ *   corners, the pixel is STATIC: fx = i, fy = j, d_exp = depth.  Else P = ((1 - u) - v) a + u b + v c per component, summed left
+ *   to right; clip_k = ((M[k][0] P.x + M[k][1] P.y) + M[k][2] P.z) + M[k][3], M the kept w2v; no place unless clip.w > 0;
+ *   x = clip.x / clip.w, y = clip.y / clip.w; fx = ((x + 1) 0.5) nx - 0.5, fy likewise with ny (pixel q's centre is q);
+ *   o_k = ((V[k][0] x + V[k][1] y) + V[k][2] (-1)) + V[k][3], V the kept v2w, the kept camera's ray origin o.xyz / o.w;
+ *   d_exp = sqrt((dx dx + dy dy) + dz dz) of d = P - that origin.  Per pixel one mpt_history_motion record: cur_id (the hit's
+ *   object as `id` above), fx, fy, d_exp (NaN without a place) and flags (MPT_MOTION_*).  The records stay on the device until the
+ *   next keep or drop; pixels outside the share hold all-ones words.
+ *   RESAMPLE, one lane per pixel, reads the old pass 0 and writes a second buffer that then takes its place.  A pixel outside the
+ *   share gets (0, 0, 0, 0) and is not counted.  A miss keeps its own old accumulators iff it is background-kept, the kept
+ *   face there is -1 and they hold samples (background_kept), else zeros (background_reset).  A hit with no place, or with
+ *   !(fx > -1 && fx < nx && fy > -1 && fy < ny) -- no tap of positive weight in the film -- gets zeros (offscreen).  Else, with
+ *   x0 = floorf(fx), y0 = floorf(fy), tx = fx - x0, ty = fy - y0, the taps q = (x0 + a, y0 + b), a the outer loop and b the inner,
+ *   both over 0, 1, weigh bw = (a ? tx : 1 - tx) (b ? ty : 1 - ty).  A tap is used iff bw > 0, q lies inside the film,
+ *   F_old(q).w > 0, id_kept(q) == cur_id and |depth_kept(q) - d_exp| <= depth_tol d_exp.  A = sum bw F_old(q) over all four
+ *   components (so taps weigh by their sample counts), B = sum bw, both started from -0 and summed in tap order; B == 0: zeros
+ *   (disoccluded); else R = A / B per component, and if R.w > max_history then R = R (max_history / R.w): newer samples must be
+ *   able to outweigh an old view.  F_new(p) = R (kept; statics counts the static ones among them).  A static pixel whose history
+ *   is at or below the cap keeps its four accumulator words exactly.  The background-kept accumulators are capped the same way.
+ *   Afterwards passes 1 and 2 are zero, the mark and the selection are dropped as mpt_clear drops them, the Sobol sampler and an
+ *   mpt_hint_image hint are left alone, and the history is spent: the next reproject needs another keep (the G-buffer and the
+ *   motion records stay readable).  stats (may be NULL): exact counts of the share's pixels by what became of them; kept +
+ *   background_kept + disoccluded + offscreen + background_reset is the share.
+ *   params NULL: max_history = 32, depth_tol = 0.02.
+ * mpt_history_drop: forgets the history and releases its device memory (as growing the film does).
+ * mpt_history_get_motion: the records of the last reproject, [nx * ny] at element x * ny + y.  mpt_history_get_gbuffer: the
+ *   kept G-buffer, each [nx * ny] or NULL (a test door).  Both fail where there is nothing to read.
+ * mpt_history_eval: test door in the mpt_noise_eval idiom -- the SAME resample launch on the caller's arrays, for any nx, ny >= 1
+ *   with nx ny <= max_filmsize, the whole film as the share, in buffers of its own: f_old [nx * ny][4], face, id, depth, motion
+ *   [nx * ny] in; f_new [nx * ny][4] and stats out (each may be NULL).  Touches nothing of the context's film or history.
+ * mpt_history_kernel_time: HIP-event time (ms) of the kernels of the keep calls and of the reproject calls since the last call,
+ *   and the count of both.
+ * mpt_history_allowed: the refusal rule as a pure function (no context, no GPU).  Returns 0 when a reproject is allowed, else
+ *   1 .. 6 in the order of the refusals above, with the words in why[why_size] (may be NULL). */
+#define MPT_MOTION_NONE       0
+#define MPT_MOTION_STATIC     1
+#define MPT_MOTION_BACKGROUND 2
+typedef struct { float max_history, depth_tol; } mpt_history_params;
+typedef struct { int64_t kept, statics, background_kept, disoccluded, offscreen, background_reset; } mpt_history_stats;
+typedef struct { int32_t cur_id; float fx, fy, d_exp; int32_t flags; } mpt_history_motion;
+int mpt_history_keep(mpt_ctx *ctx);
+int mpt_history_reproject(mpt_ctx *ctx, const mpt_history_params *params /* NULL = the defaults above */, mpt_history_stats *stats /* or NULL */);
+int mpt_history_drop(mpt_ctx *ctx);
+int mpt_history_get_motion(mpt_ctx *ctx, mpt_history_motion *out /* [nx*ny] */);
+int mpt_history_get_gbuffer(mpt_ctx *ctx, int32_t *face, int32_t *id, float *depth);
+int mpt_history_eval(mpt_ctx *ctx, const mpt_history_params *params, const float *f_old, const int32_t *face, const int32_t *id,
+                     const float *depth, const mpt_history_motion *motion, int nx, int ny, float *f_new, mpt_history_stats *stats);
+int mpt_history_kernel_time(mpt_ctx *ctx, double *keep_ms, double *reproject_ms, int *launches);
+int mpt_history_allowed(int have_history, int kept_nx, int kept_ny, int nx, int ny, int kept_faces, int nfaces, int tree_valid,
+                        float max_history, float depth_tol, char *why, int why_size);
+
 /* Page-locked host buffers for the read-backs above: into such a buffer mpt_get_image /
  * mpt_fast_export_image / mpt_get_film_raw are one DMA; any other buffer is served through a
  * page-locked staging copy.  (The reference's get_image returns a fresh numpy array,

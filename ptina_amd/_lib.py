@@ -94,6 +94,61 @@ class RefitInfo(C.Structure):
                 ('cost_built', C.c_double), ('cost_now', C.c_double), ('growth', C.c_double)]
 
 
+class HistoryParams(C.Structure):
+    '''mpt_history_params (include/miptina.h): what FilmTable.reproject hands to mpt_history_reproject'''
+    _fields_ = [('max_history', C.c_float), ('depth_tol', C.c_float)]
+
+
+class HistoryStats(C.Structure):
+    '''mpt_history_stats (include/miptina.h): what mpt_history_reproject and mpt_history_eval hand back'''
+    _fields_ = [(k, C.c_int64) for k in ('kept', 'statics', 'background_kept', 'disoccluded', 'offscreen', 'background_reset')]
+
+
+# mpt_history_motion (include/miptina.h) as a numpy record, and its flags
+MOTION_DTYPE = np.dtype([('cur_id', np.int32), ('fx', np.float32), ('fy', np.float32), ('d_exp', np.float32), ('flags', np.int32)])
+MOTION_NONE, MOTION_STATIC, MOTION_BACKGROUND = 0, 1, 2
+
+
+class HistoryResult:
+    '''FilmTable.reproject's answer: what became of the pixels of this context's share.  `kept` took over history through the
+    taps (`static` of them word for word in place), `background_kept` kept their own sums behind an unchanged camera,
+    `disoccluded` found every tap rejected, `offscreen` lay outside the kept view, `background_reset` see nothing under a changed
+    camera; `pixels` is their sum and `kept_fraction` = (kept + background_kept) / pixels (0.0 for an empty share)'''
+    __slots__ = ('kept', 'static', 'background_kept', 'disoccluded', 'offscreen', 'background_reset')
+
+    def __init__(self, stats):
+        self.kept, self.static, self.background_kept = int(stats.kept), int(stats.statics), int(stats.background_kept)
+        self.disoccluded, self.offscreen, self.background_reset = int(stats.disoccluded), int(stats.offscreen), int(stats.background_reset)
+
+    @property
+    def pixels(self):
+        return self.kept + self.background_kept + self.disoccluded + self.offscreen + self.background_reset
+
+    @property
+    def kept_fraction(self):
+        return (self.kept + self.background_kept) / self.pixels if self.pixels else 0.0
+
+    def astuple(self):
+        return tuple(getattr(self, k) for k in self.__slots__)
+
+    def __repr__(self):
+        return 'HistoryResult(kept=%d, static=%d, background_kept=%d, disoccluded=%d, offscreen=%d, background_reset=%d)' % self.astuple()
+
+
+def history_params(max_history=32.0, depth_tol=0.02):
+    '''HistoryParams from the arguments FilmTable.reproject takes, and their defaults (include/miptina.h states the same ones
+    for a NULL mpt_history_params)'''
+    return HistoryParams(float(max_history), float(depth_tol))
+
+
+def history_allowed(have, kept_size, size, kept_faces, nfaces, tree_valid, max_history=32.0, depth_tol=0.02):
+    '''mpt_history_allowed (no context, no GPU): (verdict, words); verdict 0 allows a reproject'''
+    why = C.create_string_buffer(256)
+    rc = load_library().mpt_history_allowed(int(bool(have)), int(kept_size[0]), int(kept_size[1]), int(size[0]), int(size[1]), int(kept_faces),
+                                            int(nfaces), int(bool(tree_valid)), float(max_history), float(depth_tol), why, len(why))
+    return rc, why.value.decode()
+
+
 DISPLAY_DENOISED = -1
 TONE_OPS = {'linear': 0, 'ptina': 1, 'reinhard': 2, 'aces': 3}
 TRANSFERS = {'srgb': 0, 'gamma': 1}
@@ -207,6 +262,14 @@ SIGNATURES = {
     'mpt_query_occluded': (_i, [_vp, _i, _fp, _fp, _fp, _ip, _ip, _i]),
     'mpt_query_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
     'mpt_walk_trace': (_i, [_vp, _i, _i, _fp, _fp, _ip, _fp, _ip, _fp, _ip, _fp, _fp, _i]),
+    'mpt_history_keep': (_i, [_vp]),
+    'mpt_history_reproject': (_i, [_vp, C.POINTER(HistoryParams), C.POINTER(HistoryStats)]),
+    'mpt_history_drop': (_i, [_vp]),
+    'mpt_history_get_motion': (_i, [_vp, _vp]),
+    'mpt_history_get_gbuffer': (_i, [_vp, _ip, _ip, _fp]),
+    'mpt_history_eval': (_i, [_vp, C.POINTER(HistoryParams), _fp, _ip, _ip, _fp, _vp, _i, _i, _fp, C.POINTER(HistoryStats)]),
+    'mpt_history_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_history_allowed': (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.c_float, C.c_float, C.c_char_p, _i]),
     'mpt_host_alloc': (_vp, [C.c_size_t]),
     'mpt_host_free': (None, [_vp]),
     'mpt_get_counters': (_i, [_vp, C.POINTER(Counters)]),
@@ -510,6 +573,22 @@ class Context:
         st, n = NoiseStats(), C.c_int(-1)
         self.call('mpt_adapt_eval', float(threshold), int(dilate), fptr(f), fptr(m), int(nx), int(ny), iptr(out), out.size, C.byref(n), C.byref(st))
         return NoiseResult(st), out[:n.value].copy()
+
+    def history_eval(self, f_old, face, id, depth, motion, nx, ny, max_history=32.0, depth_tol=0.02):
+        '''test door (mpt_history_eval): FilmTable.reproject's resample launch on the accumulators f_old [nx*ny][4], a kept
+        G-buffer face, id (int32) and depth (f32) [nx*ny] and the motion records (MOTION_DTYPE [nx*ny]), the whole film as the
+        share; returns (the new accumulators [nx*ny, 4], HistoryResult)'''
+        n = int(nx) * int(ny)
+        f = np.ascontiguousarray(np.asarray(f_old, np.float32).reshape(-1, 4))
+        fa, ob = (np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1)) for a in (face, id))
+        de = np.ascontiguousarray(np.asarray(depth, np.float32).reshape(-1))
+        mo = np.ascontiguousarray(np.asarray(motion, MOTION_DTYPE).reshape(-1))
+        if not (f.shape[0] == fa.size == ob.size == de.size == mo.size == n):
+            raise ValueError('the arrays do not hold the %d pixels of the film %dx%d' % (n, nx, ny))
+        out, st = np.empty_like(f), HistoryStats()
+        self.call('mpt_history_eval', C.byref(history_params(max_history, depth_tol)), fptr(f), iptr(fa), iptr(ob), fptr(de),
+                  mo.ctypes.data_as(C.c_void_p), int(nx), int(ny), fptr(out), C.byref(st))
+        return out, HistoryResult(st)
 
     def counters(self):
         cnt = Counters()

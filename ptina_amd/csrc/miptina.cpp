@@ -341,6 +341,7 @@ extern "C" int mpt_set_size(mpt_ctx *c, int nx, int ny) {
         return fail("film %dx%d exceeds max_filmsize=%d (init_things(max_filmsize=...))", nx, ny, c->caps.max_filmsize);
     if (npix > c->fb.cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
+        c->history.gbuffer = c->history.motion = false;      // (the reprojection's buffers go with the film's)
         if (c->fb.reserve(npix, c->stream)) return 1;
     }
     // the reference keeps one flat buffer and only changes `res` (filmtable.py:41-42): stale sums

@@ -8,6 +8,7 @@
 #include "shade_feat.h"
 #include "refit_rule.h"
 #include "deform_rule.h"
+#include "history_rule.h"
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -88,6 +89,13 @@ MPT_KERNEL_API hipError_t mpt_launch_adapt_select(const MptVec4 *film, const Mpt
                                                   unsigned long long *ballot, int *count, int32_t *list, long long *total_host, hipStream_t);
 MPT_KERNEL_API hipError_t mpt_launch_adapt_fold(MptVec4 *film, MptVec4 *mark /* or NULL */, const int32_t *list, int count, const MptVec4 *samples,
                                                 int nframes, int remark, hipStream_t);
+// history_kernel.hip: the G-buffer of the view as it is kept and the motion records of the new view (both builds); history.hip: the
+// kept copy of the model's positions, and the resample launch with its fold; part holds max(mpt_history_parts(npix), 1) records
+MPT_DUAL_LAUNCHER(mpt_launch_history_gbuffer, const MptRenderParams *, const MptHistoryArgs *, int stack, hipStream_t);
+MPT_DUAL_LAUNCHER(mpt_launch_history_motion, const MptRenderParams *, const MptHistoryArgs *, int stack, hipStream_t);
+MPT_KERNEL_API size_t mpt_history_parts(size_t npix);
+MPT_KERNEL_API hipError_t mpt_launch_history_verts(const float *verts, float *kept, int n, hipStream_t);
+MPT_KERNEL_API hipError_t mpt_launch_history_resample(const MptResampleArgs *, mpt_history_stats *part, mpt_history_stats *stats_host, hipStream_t);
 // compose.hip: meshes of the pool placed by the object table, written as the model the tree builders read, and its bounding box
 // (mpt_compose); part holds 6 floats per mpt_compose_groups(vertices) workgroups
 MPT_KERNEL_API size_t mpt_compose_groups(size_t nverts);
@@ -288,6 +296,24 @@ struct MPT_INTERNAL MptDoorInput {         // the test doors' input: the caller'
     }
 };
 
+struct MPT_INTERNAL MptHistoryBufs {       // the reprojection's per-pixel buffers, for a film of up to `cap` pixels (film_history.cpp)
+    DevBuf<int32_t> face, id;            // the kept G-buffer: the face and the object each pixel's centre ray hit
+    DevBuf<float> depth;                 // ... and how far along the ray
+    DevBuf<MptMotion> motion;            // the last reproject's motion records
+    DevBuf<MptVec4> f_new;               // what the resample kernel writes: swapped with pass 0 (the film's), read back (the door's)
+    DevBuf<mpt_history_stats> part;      // the counts' first-stage partials, one record per workgroup
+    size_t cap = 0;
+    void release() { face.release(); id.release(); depth.release(); motion.release(); f_new.release(); part.release(); cap = 0; }
+    int reserve(size_t npix) {
+        if (npix <= cap) return 0;
+        release();
+        if (face.reserve(npix) || id.reserve(npix) || depth.reserve(npix) || motion.reserve(npix) || f_new.reserve(npix) ||
+            part.reserve(std::max<size_t>(mpt_history_parts(npix), 1))) return 1;
+        cap = npix;
+        return 0;
+    }
+};
+
 struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set so far
     DevBuf<MptVec4> film[3];
     DevBuf<MptVec4> resolved;            // nx*ny float4 (get_image staging on device)
@@ -305,7 +331,11 @@ struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set 
     // adaptive sampling: the selection and its workspace, made by the first selection (reserve_adapt) for `cap` pixels, and the
     // list render kernel's samples, grown on demand (adapt_samples.cap records); released with the rest
     MptAdaptBufs adapt; DevBuf<MptVec4> adapt_samples;
+    // reprojection: the kept G-buffer, the motion records and the buffer pass 0 is resampled into, made by the first
+    // mpt_history_keep (reserve_history) for `cap` pixels; released with the rest, or by mpt_history_drop
+    MptHistoryBufs hist;
     size_t cap = 0;
+    int reserve_history() { return hist.reserve(cap); }
     int reserve_adapt() { return adapt.reserve(cap); }
     int reserve_mark() { return mark.reserve(cap) || noise.reserve(cap); }
     int reserve_variance() { return dn_v[0].reserve(cap) || dn_v[1].reserve(cap); }
@@ -319,6 +349,7 @@ struct MPT_INTERNAL MptFilmBufs {          // per pixel of the largest film set 
         mark.release(); noise.release();
         dn_v[0].release(); dn_v[1].release();
         adapt.release(); adapt_samples.release();
+        hist.release();
         for (auto &b : film) {
             if (b.reserve(npix)) return 1;
             HIP_TRY(hipMemsetAsync(b, 0, npix * sizeof(MptVec4), stream));
@@ -725,7 +756,19 @@ struct mpt_ctx {
             return 0;
         }
     } query{events};
-    MptDoorInput door;                                   // mpt_display_eval, mpt_noise_eval, mpt_denoise_eval: the caller's accumulators on the device (grown on demand)
+    struct MPT_INTERNAL History {                        // reprojection (film_history.cpp: mpt_history_*); the per-pixel buffers are fb.hist
+        bool have = false;                               // a view is kept and not spent: mpt_history_reproject may run
+        bool gbuffer = false, motion = false;            // fb.hist holds a kept G-buffer / the motion records of a reproject, of a film of nx x ny
+        int nx = 0, ny = 0, faces = 0;                   // the film size and the face count of the kept view
+        float v2w[16] = {}, w2v[16] = {};                // its camera, as uploaded
+        DevBuf<float> verts;                             // [faces][3][3] the positions it saw
+        MappedBuf<mpt_history_stats> stats;              // the counts of the last resample launch
+        MptHistoryBufs bufs;                             // mpt_history_eval: the caller's G-buffer and motion records, and what the kernels write (grown on demand)
+        MptLaunchTimer keep_timer, reproject_timer;      // {before the call's kernels, after them} per call
+        explicit History(MptEventPool &ev) : keep_timer(2, ev), reproject_timer(2, ev) {}
+        void forget() { have = gbuffer = motion = false; }
+    } history{events};
+    MptDoorInput door;                                  // mpt_display_eval, mpt_noise_eval, mpt_denoise_eval: the caller's accumulators on the device (grown on demand)
     MptLaunchTimer render_timer{2, events};              // PathEngine launches: {kernel start, kernel end}
     MptLaunchTimer denoise_timer{2, events};             // mpt_get_denoised: {before the prologue, after the epilogue} per call
     float denoise_variance = 0.0f;                       // mpt_denoise_set_variance: sigma_variance of the denoised read-backs (0: the fixed filter)
@@ -800,8 +843,11 @@ MPT_INTERNAL int mlt_flush(mpt_ctx *c);       // mpt_flush, mpt_render: launch t
 // tree_build.cpp
 MPT_INTERNAL int download_tree(mpt_ctx *c);   // before anything reads c->h_leaf / h_child / ...: fetch the reference-layout arrays once per build
 
+// tree_query.cpp
+MPT_INTERNAL int query_tables(mpt_ctx *c);    // before a launch reads c->query.leaf / slot_of: slot -> face and face -> slot of the tree as built
+
 // scene_compose.cpp
-MPT_INTERNAL int model_on_host(mpt_ctx *c);   // before anything reads c->verts / c->mtlids: fetch them once if mpt_compose made the model
+MPT_INTERNAL int model_on_host(mpt_ctx *c);  // before anything reads c->verts / c->mtlids: fetch them once if mpt_compose made the model
 
 // scene_deform.cpp: what scene_compose.cpp tells the deform table, and the step of mpt_compose that writes the deformed copies
 MPT_INTERNAL void deform_mesh_added(mpt_ctx *c);                 // a mesh joined the pool: the copies behind the meshes lose their room

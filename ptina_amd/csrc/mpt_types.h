@@ -191,6 +191,31 @@ struct MptQueryArgs {
     int32_t *occ;                            // ... and the occlusion kernel's
 };
 
+// The film's reprojection.  One launch of the G-buffer or the motion kernel (history_kernel.hip): the tables
+// that name a hit's face and object, where the G-buffer goes or -- the motion kernel -- the kept view, the kept and the current
+// vertex positions and where the motion records go
+struct MptMotion;                           // history_rule.h
+struct MptHistoryArgs {
+    const int32_t *leaf;                     // [faces] slot -> face of the built tree
+    const int32_t *first;                    // [nobj] the objects' first faces (compose.hip), or null: every hit is object 0
+    int32_t nobj;
+    int32_t same_camera;                     // motion: the kept and the current camera matrices are equal word for word
+    int32_t *face, *id; float *depth;        // G-buffer: [nx * ny] each
+    const float *kept_verts;                 // motion: [faces][3][3] the positions the kept view saw
+    const float *cur_verts;                  // motion: [faces * 3][8] the model as it is on the device now
+    float kept_w2v[16], kept_v2w[16];        // motion: the kept camera, as uploaded
+    MptMotion *motion;                       // motion: [nx * ny]
+};
+// one launch of the resample kernel (history.hip): the old accumulators, the kept G-buffer, the motion records, the share of the
+// film this context renders (stripe_w = 0: the slab [x0, x1) alone) and the two parameters
+struct MptResampleArgs {
+    const MptVec4 *f_old; MptVec4 *f_new;
+    const int32_t *face, *id; const float *depth;
+    const MptMotion *motion;
+    int32_t nx, ny, x0, x1, stripe_w, stripe_idx, stripe_mod;
+    float max_history, depth_tol;
+};
+
 // one conversion launch of mpt_get_display (display.hip): mpt_display_params as the kernels take it
 struct MptDisplayArgs {
     int32_t op, transfer, layout, dither;    // MPT_TONE_*, MPT_TRANSFER_*, MPT_LAYOUT_* of include/miptina.h

@@ -14,8 +14,8 @@
 enum { MPT_QUERY_CHUNK = 1 << 22 };      // rays per launch by default: 40 bytes of input and 24 of answers each
 
 // slot -> face and face -> slot of the tree as built: the tracers name a triangle by its leaf slot, callers by its face.  A refit
-// keeps the leaf order, a build makes a new one (mpt_ctx::tree_seq)
-static int query_tables(mpt_ctx *c) {
+// keeps the leaf order, a build makes a new one (mpt_ctx::tree_seq).  (Also film_history.cpp's: its kernels name faces too.)
+int query_tables(mpt_ctx *c) {
     auto &q = c->query;
     if (q.tables_seq == c->tree_seq && q.leaf.p) return 0;
     if (download_tree(c)) return 1;

@@ -199,6 +199,65 @@ class FilmTable(metaclass=Singleton):
         '''(select_ms, render_ms, calls): HIP-event time of the select() calls and of the render_selected() calls since the last call'''
         return ctx().timer('mpt_adapt_kernel_time', 2)
 
+    # ---- reprojection (csrc/film_history.cpp, DESIGN.md section 3.18; no reference counterpart: its add-on clears the film at
+    #      every change of the view):   render ... -> keep_history() -> edit the scene / camera -> compose() -> tree.update() -> reproject() -> render ...
+    def keep_history(self):
+        '''remember the view as it stands, on the device (mpt_history_keep): the camera, the model's positions and what every
+        pixel's centre ray sees.  Needs a tree built for the model as it stands.  Writes nothing a render reads'''
+        ctx().call('mpt_history_keep')
+
+    def reproject(self, max_history=32, depth_tol=0.02):
+        '''after the camera and / or the model changed (and the tree was built or refitted for it): resample pass 0 into the new
+        view on the device (mpt_history_reproject, include/miptina.h) -- every pixel takes the accumulators of the place where the
+        surface point it sees now lay in the kept view, bilinearly from the taps that saw the same object at the expected distance
+        (depth_tol, relative); pixels whose surface was hidden, off-screen or replaced start from zero.  A pixel's history counts
+        for at most max_history samples (inf: all of it), so that new samples can outweigh the old view.  Passes 1 and 2 are
+        cleared, the mark and the selection dropped, the sampler left alone; the history is spent.  Lighting that changed -- an
+        edited light, the shadow of a moved object -- is not detected: it lags by at most max_history samples.  Returns a
+        HistoryResult.  Raises, naming the cause and leaving the film alone, without a history, after a change of the film size or
+        of the face count, with a stale tree or a bad parameter'''
+        from ._lib import HistoryStats, HistoryResult, history_params
+        st = HistoryStats()
+        ctx().call('mpt_history_reproject', C.byref(history_params(max_history, depth_tol)), C.byref(st))
+        return HistoryResult(st)
+
+    def get_motion(self):
+        '''the motion vectors of the last reproject(), as a compositor's vector pass: (vector [nx, ny, 2] f32 = where the pixel's
+        surface point lay in the kept view minus where it is now, in pixels (0 where not valid); valid [nx, ny] bool: the point
+        had a place in the kept view; static [nx, ny] bool: neither the camera nor its triangle moved)'''
+        rec = self.get_motion_records()
+        i, j = np.meshgrid(np.arange(rec.shape[0], dtype=np.float32), np.arange(rec.shape[1], dtype=np.float32), indexing='ij')
+        valid = (rec['flags'] >= 0) & np.isfinite(rec['fx']) & np.isfinite(rec['fy'])
+        vector = np.zeros(rec.shape + (2,), np.float32)
+        vector[..., 0] = np.where(valid, rec['fx'] - i, 0)
+        vector[..., 1] = np.where(valid, rec['fy'] - j, 0)
+        from ._lib import MOTION_STATIC
+        return vector, valid, valid & (rec['flags'] == MOTION_STATIC)
+
+    def get_motion_records(self):
+        '''the last reproject()'s records as the device holds them (mpt_history_get_motion): _lib.MOTION_DTYPE [nx, ny] of the
+        film as it was kept -- cur_id, fx, fy, d_exp, flags'''
+        from ._lib import MOTION_DTYPE
+        rec = np.empty(self._res(), MOTION_DTYPE)
+        ctx().call('mpt_history_get_motion', rec.ctypes.data_as(C.c_void_p))
+        return rec
+
+    def get_gbuffer(self):
+        '''test door (mpt_history_get_gbuffer): the kept view's (face, id, depth), [nx, ny] int32, int32, f32'''
+        from ._lib import iptr
+        nx, ny = self._res()
+        face, obj, depth = np.empty((nx, ny), np.int32), np.empty((nx, ny), np.int32), np.empty((nx, ny), np.float32)
+        ctx().call('mpt_history_get_gbuffer', iptr(face), iptr(obj), fptr(depth))
+        return face, obj, depth
+
+    def drop_history(self):
+        '''forget the kept view and release its device memory (mpt_history_drop)'''
+        ctx().call('mpt_history_drop')
+
+    def history_kernel_time(self):
+        '''(keep_ms, reproject_ms, calls): HIP-event time of the keep_history() and of the reproject() calls since the last call'''
+        return ctx().timer('mpt_history_kernel_time', 2)
+
     def fast_export_image(self, out, id=0):
         '''reference filmtable.py:66-79: flat RGB f32 at (y * nx + x) * 3 into the caller's buffer'''
         nx, ny = self._res()

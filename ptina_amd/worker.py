@@ -86,6 +86,18 @@ def update_tree(max_growth=None):
     return BVHTree().update() if max_growth is None else BVHTree().update(max_growth)
 
 
+def keep_history():
+    '''FilmTable().keep_history(): remember the rendered view on the device, before the scene or the camera is edited (no
+    reference counterpart: its add-on clears the film at every change)'''
+    FilmTable().keep_history()
+
+
+def reproject(max_history=32, depth_tol=0.02):
+    '''FilmTable().reproject(max_history, depth_tol): after the edit and update_tree(), carry the accumulated film over to the new
+    view instead of clear(); returns the HistoryResult (how many pixels kept their history)'''
+    return FilmTable().reproject(max_history, depth_tol)
+
+
 def intersect(o, d, avoid=None):
     '''BVHTree().intersect(o, d, avoid): the closest hits of a batch of rays against the built tree -- a dict of arrays hit, depth,
     index, u, v, object (the reference asks its tree one ray at a time, inside a kernel: lbvh.py:314-347)'''
