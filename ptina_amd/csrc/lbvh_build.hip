@@ -19,16 +19,9 @@
 #include <rocprim/rocprim.hpp>
 #include "mpt_types.h"
 #include "tri_records.h"
+#include "tree_rules.h"      // every rule that decides a byte of the tree, shared with the host pass (tree_host.h)
 
 #define LB_BLOCK 256
-
-__device__ __forceinline__ int f2ord(float f) {          // order-preserving float -> int
-    int i = __float_as_int(f);
-    return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__device__ __forceinline__ float ord2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
-
-__device__ __forceinline__ const float *vpos(const float *verts, int f, int k) { return verts + ((size_t)f * 3 + k) * 8; }
 
 // lbvh.py:161-165,173-177: centre = (v0 + v1 + v2) / 3; bmin/bmax over centres.  At most 1024 workgroups stride over the
 // triangles: six same-line atomics per WAVE of a million triangles took 1.07 ms of the build (profiles/r06_build_kernel_stats_c5_before.csv)
@@ -39,7 +32,7 @@ __global__ __launch_bounds__(LB_BLOCK) void centroid_bounds_kernel(const float *
     for (int f = blockIdx.x * LB_BLOCK + threadIdx.x; f < n; f += gridDim.x * LB_BLOCK) {
 #pragma unroll
         for (int a = 0; a < 3; a++) {
-            const float c = ((vpos(verts, f, 0)[a] + vpos(verts, f, 1)[a]) + vpos(verts, f, 2)[a]) / 3.0f;
+            const float c = centroid(verts, f, a);
             cen[(size_t)f * 3 + a] = c;
             const int o = f2ord(c);
             lo[a] = min(lo[a], o); hi[a] = max(hi[a], o);
@@ -62,39 +55,15 @@ __global__ __launch_bounds__(LB_BLOCK) void centroid_bounds_kernel(const float *
     }
 }
 
-__device__ __forceinline__ unsigned expand_bits(unsigned v) {                // lbvh.py:13-17
-    v = (v * 0x00010001u) & 0xFF0000FFu;
-    v = (v * 0x00000101u) & 0x0F00F00Fu;
-    v = (v * 0x00000011u) & 0xC30C30C3u;
-    v = (v * 0x00000005u) & 0x49249249u;
-    return v;
-}
-
-__device__ __forceinline__ int quant1024(float x) {                          // clamp(ifloor(v * 1024), 0, 1023), lbvh.py:29
-    float f = floorf(x * 1024.0f);
-    if (!(f == f) || f < 0.f) return 0;
-    if (f > 1023.f) return 1023;
-    return (int)f;
-}
-
 // lbvh.py:179-183, with the reference's initial bounds +-inf = +-1e6 folded in (lbvh.py:173)
 __global__ __launch_bounds__(LB_BLOCK) void morton_keys_kernel(const float *__restrict__ cen, const int *__restrict__ bounds,
                                                                int n, unsigned long long *__restrict__ keys) {
     int f = blockIdx.x * LB_BLOCK + threadIdx.x;
     if (f >= n) return;
-    unsigned w[3];
+    float bmin[3], bmax[3];
 #pragma unroll
-    for (int a = 0; a < 3; a++) {
-        float bmin = fminf(1e6f, ord2f(bounds[a])), bmax = fmaxf(-1e6f, ord2f(bounds[3 + a]));
-        w[a] = expand_bits((unsigned)quant1024((cen[(size_t)f * 3 + a] - bmin) / (bmax - bmin)));
-    }
-    unsigned code = w[0] * 4 + w[1] * 2 + w[2];
-    keys[f] = ((unsigned long long)code << 32) | (unsigned)f;
-}
-
-__device__ __forceinline__ int delta(const unsigned long long *key, int n, int i, int j) {
-    if (j < 0 || j >= n) return -1;
-    return __clzll((long long)(key[i] ^ key[j]));
+    for (int a = 0; a < 3; a++) { bmin[a] = fminf(1e6f, ord2f(bounds[a])); bmax[a] = fmaxf(-1e6f, ord2f(bounds[3 + a])); }
+    keys[f] = morton_key(cen + (size_t)f * 3, bmin, bmax, f);
 }
 
 // lbvh.py:212-231 (determineRange :93-146, findSplit :62-89) on unique 64-bit keys
@@ -107,42 +76,13 @@ __global__ __launch_bounds__(LB_BLOCK) void hierarchy_kernel(const unsigned long
         mc[i] = (int)(key[i] >> 32);
     }
     if (i >= n - 1) return;
-    int l, r;
-    if (i == 0) { l = 0; r = n - 1; }
-    else {
-        int d = delta(key, n, i, i + 1) > delta(key, n, i, i - 1) ? 1 : -1;
-        int dmin = delta(key, n, i, i - d);
-        int lmax = 2;
-        while (delta(key, n, i, i + lmax * d) > dmin) lmax <<= 1;
-        int s = 0;
-        for (int t = lmax >> 1; t > 0; t >>= 1)
-            if (delta(key, n, i, i + (s + t) * d) > dmin) s += t;
-        l = i; r = i + s * d;
-        if (d < 0) { int tmp = l; l = r; r = tmp; }
-    }
-    int cp = delta(key, n, l, r);
-    int m = l, s = r - l;
-    for (;;) {
-        s = (s + 1) >> 1;
-        int q = m + s;
-        if (q < r && delta(key, n, l, q) > cp) m = q;
-        if (s <= 1) break;
-    }
-    int c0 = (m == l) ? m : m + n;
-    int c1 = (m + 1 == r) ? m + 1 : m + 1 + n;
+    int c0, c1;
+    lbvh_children(key, n, i, &c0, &c1);
     child[(size_t)i * 2 + 0] = c0;
     child[(size_t)i * 2 + 1] = c1;
     parent[c0] = i;                      // parent[] is indexed by node id: leaf slot, or internal + n
     parent[c1] = i;
     if (i == 0) parent[n] = -1;
-}
-
-__device__ __forceinline__ void leaf_box(const float *verts, int f, float *lo, float *hi) {   // lbvh.py:155-158
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        lo[a] = fminf(fminf(vpos(verts, f, 0)[a], vpos(verts, f, 1)[a]), vpos(verts, f, 2)[a]);
-        hi[a] = fmaxf(fmaxf(vpos(verts, f, 0)[a], vpos(verts, f, 1)[a]), vpos(verts, f, 2)[a]);
-    }
 }
 
 // Bottom-up fit.  Boxes and flags cross workgroups inside one launch, so every word that is handed
@@ -201,8 +141,6 @@ __global__ __launch_bounds__(LB_BLOCK) void fit_boxes_kernel(const float *__rest
     }
 }
 
-__device__ __forceinline__ float asf(int v) { return __int_as_float(v); }
-
 // node records (mpt_types.h): snode = reference-shaped, fnode = both child boxes of the LBVH itself (null: snode alone -- a refit,
 // whose fnode may hold the SAH tree)
 __global__ __launch_bounds__(LB_BLOCK) void pack_nodes_kernel(const float *__restrict__ verts, const int *__restrict__ leaf,
@@ -215,21 +153,20 @@ __global__ __launch_bounds__(LB_BLOCK) void pack_nodes_kernel(const float *__res
     snode[(size_t)i * 2 + 0] = { bmin[(size_t)i * 3], bmin[(size_t)i * 3 + 1], bmin[(size_t)i * 3 + 2], asf(c0) };
     snode[(size_t)i * 2 + 1] = { bmax[(size_t)i * 3], bmax[(size_t)i * 3 + 1], bmax[(size_t)i * 3 + 2], asf(c1) };
     if (!fnode) return;
-    float l[2][3], h[2][3];
-    int id[2];
+    MptVec4 rec[4] = {};
 #pragma unroll
     for (int k = 0; k < 2; k++) {
         int ch = k ? c1 : c0;
-        if (ch < n) { leaf_box(verts, leaf[ch], l[k], h[k]); id[k] = ~ch; }
+        float l[3], h[3];
+        if (ch < n) leaf_box(verts, leaf[ch], l, h);
         else {
 #pragma unroll
-            for (int a = 0; a < 3; a++) { l[k][a] = bmin[(size_t)(ch - n) * 3 + a]; h[k][a] = bmax[(size_t)(ch - n) * 3 + a]; }
-            id[k] = ch - n;
+            for (int a = 0; a < 3; a++) { l[a] = bmin[(size_t)(ch - n) * 3 + a]; h[a] = bmax[(size_t)(ch - n) * 3 + a]; }
         }
+        fnode_write_child(rec, k, l, h, lbvh_fast_id(ch, n));
     }
 #pragma unroll
-    for (int a = 0; a < 3; a++) fnode[(size_t)i * 4 + a] = { l[0][a], l[1][a], h[0][a], h[1][a] };
-    fnode[(size_t)i * 4 + 3] = { asf(id[0]), asf(id[1]), 0.f, 0.f };
+    for (int k = 0; k < 4; k++) fnode[(size_t)i * 4 + k] = rec[k];
 }
 
 // per-leaf-slot triangle records: hoisted terms of Face.intersect (geometries.py:120-122,134-136,140)

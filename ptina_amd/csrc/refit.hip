@@ -7,8 +7,8 @@
 //          root gets -1
 //   fit    one lane per node.  A node whose children are all leaves starts a climb.  The climbing lane holds a finished node:
 //          it takes the boxes of the node's leaf children from the vertices (min / max of the triangle's three vertices,
-//          lbvh_build.hip leaf_box) and those of its internal children from the node's own record, where the lanes that
-//          finished them put them; writes the leaf children's boxes (and, for a wide node, the quantised record: wide_quant.h,
+//          tree_rules.h leaf_box) and those of its internal children from the node's own record, where the lanes that
+//          finished them put them; writes the leaf children's boxes (and, for a wide node, the quantised record: tree_rules.h,
 //          the collapse's arithmetic); stores the union into its slot of the parent's record; and takes a ticket on the parent's
 //          arrival word.  The lane whose ticket is the parent's last internal child goes on with the parent, every other lane
 //          ends.  No lane ever waits for another: there is no spin and no poll, so the kernel ends whatever the scheduling.
@@ -17,25 +17,15 @@
 //          the ticket.  Only fminf / fmaxf touch a box, and a node's union is formed by one lane in slot order, so the bytes do
 //          not depend on who arrives when.
 //   cost   the sum over every child box of every fnode record of area(child) / area(root) -- the boxes a random ray is
-//          expected to meet (SAH) -- in units of 2^-40 as integers (wide_quant.h), so the same bits in any order
+//          expected to meet (SAH) -- in units of 2^-40 as integers (tree_rules.h), so the same bits in any order
 // Compiled with -ffp-contract=off like the builders: the bytes are specified (tests/refit_ref.py).
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "mpt_types.h"
-#include "wide_quant.h"
+#include "tree_rules.h"      // the leaf box, the records' layouts, the quantisation and the fixed-point area: the builders' own
 
 #define RF_BLOCK 256
-
-__device__ __forceinline__ const float *rf_vpos(const float *verts, int f, int k) { return verts + ((size_t)f * 3 + k) * 8; }
-
-__device__ __forceinline__ void rf_leaf_box(const float *__restrict__ verts, int f, float *lo, float *hi) {   // lbvh_build.hip leaf_box
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        lo[a] = fminf(fminf(rf_vpos(verts, f, 0)[a], rf_vpos(verts, f, 1)[a]), rf_vpos(verts, f, 2)[a]);
-        hi[a] = fmaxf(fmaxf(rf_vpos(verts, f, 0)[a], rf_vpos(verts, f, 1)[a]), rf_vpos(verts, f, 2)[a]);
-    }
-}
 
 __device__ __forceinline__ float rf_load(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void rf_store(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -47,8 +37,8 @@ template <int WIDTH>
 __global__ __launch_bounds__(RF_BLOCK) void rf_link_kernel(const MptVec4 *__restrict__ rec, int count, int *__restrict__ parent_slot) {
     const int i = blockIdx.x * RF_BLOCK + threadIdx.x;
     if (i >= count) return;
-    const MptVec4 idv = rec[(size_t)i * (2 * WIDTH) + (WIDTH == 2 ? 3 : 6)];
-    const int ids[4] = { wb_asi(idv.x), wb_asi(idv.y), wb_asi(idv.z), wb_asi(idv.w) };
+    const MptVec4 idv = rec[(size_t)i * (2 * WIDTH) + (WIDTH == 2 ? FNODE_ID_ROW : WNODE_ID_ROW)];
+    const int ids[4] = { asi(idv.x), asi(idv.y), asi(idv.z), asi(idv.w) };
 #pragma unroll
     for (int k = 0; k < WIDTH; k++)
         if (ids[k] > 0 && ids[k] < count) parent_slot[ids[k]] = WIDTH * i + k;
@@ -66,7 +56,7 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_fit_bin_kernel(const float *__res
     int id[2];
     {
         const float *rec = (const float *)(fnode + (size_t)node * 4);
-        id[0] = wb_asi(rec[12]); id[1] = wb_asi(rec[13]);
+        id[0] = asi(rec[fnode_id(0)]); id[1] = asi(rec[fnode_id(1)]);
     }
     if (id[0] >= 0 || id[1] >= 0) return;                       // an internal child: whoever finishes the last of them goes on here
     for (;;) {
@@ -76,12 +66,12 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_fit_bin_kernel(const float *__res
         for (int k = 0; k < 2; k++) {
             float l[3], h[3];
             if (id[k] < 0) {
-                rf_leaf_box(verts, leaf[~id[k]], l, h);
+                leaf_box(verts, leaf[~id[k]], l, h);
 #pragma unroll
-                for (int a = 0; a < 3; a++) { rec[a * 4 + k] = l[a]; rec[a * 4 + 2 + k] = h[a]; }     // (read by later launches only)
+                for (int a = 0; a < 3; a++) { rec[fnode_lo(k, a)] = l[a]; rec[fnode_hi(k, a)] = h[a]; }     // (read by later launches only)
             } else {
 #pragma unroll
-                for (int a = 0; a < 3; a++) { l[a] = rf_load(rec + a * 4 + k); h[a] = rf_load(rec + a * 4 + 2 + k); }
+                for (int a = 0; a < 3; a++) { l[a] = rf_load(rec + fnode_lo(k, a)); h[a] = rf_load(rec + fnode_hi(k, a)); }
             }
 #pragma unroll
             for (int a = 0; a < 3; a++) { lo[a] = k ? fminf(lo[a], l[a]) : l[a]; hi[a] = k ? fmaxf(hi[a], h[a]) : h[a]; }
@@ -90,9 +80,9 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_fit_bin_kernel(const float *__res
         if (ps < 0) break;                                      // the root
         const int p = ps >> 1, k = ps & 1;
         float *prec = (float *)(fnode + (size_t)p * 4);
-        id[0] = wb_asi(prec[12]); id[1] = wb_asi(prec[13]);     // (the id row is never written here)
+        id[0] = asi(prec[fnode_id(0)]); id[1] = asi(prec[fnode_id(1)]);     // (the id row is never written here)
 #pragma unroll
-        for (int a = 0; a < 3; a++) { rf_store(prec + a * 4 + k, lo[a]); rf_store(prec + a * 4 + 2 + k, hi[a]); }
+        for (int a = 0; a < 3; a++) { rf_store(prec + fnode_lo(k, a), lo[a]); rf_store(prec + fnode_hi(k, a), hi[a]); }
         __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the box is out before the arrival is counted
         const unsigned prev = __hip_atomic_fetch_add(arrive + p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (prev + 1u != (unsigned)((id[0] >= 0) + (id[1] >= 0))) break;   // a sibling is still on its way: it will finish p
@@ -114,7 +104,7 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_fit_wide_kernel(const float *__re
     {
         const float *rec = (const float *)(wnode + (size_t)node * 8);
 #pragma unroll
-        for (int k = 0; k < 4; k++) id[k] = wb_asi(rec[24 + k]);
+        for (int k = 0; k < 4; k++) id[k] = asi(rec[wnode_id(k)]);
     }
     if (id[0] > 0 || id[1] > 0 || id[2] > 0 || id[3] > 0) return;
     for (;;) {
@@ -127,12 +117,12 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_fit_wide_kernel(const float *__re
             if (id[k] == empty_id) continue;
             cnt = k + 1;
             if (id[k] < 0) {
-                rf_leaf_box(verts, leaf[~id[k]], ch[k].lo, ch[k].hi);
+                leaf_box(verts, leaf[~id[k]], ch[k].lo, ch[k].hi);
 #pragma unroll
-                for (int a = 0; a < 3; a++) { rec[(2 * a) * 4 + k] = ch[k].lo[a]; rec[(2 * a + 1) * 4 + k] = ch[k].hi[a]; }
+                for (int a = 0; a < 3; a++) { rec[wnode_lo(k, a)] = ch[k].lo[a]; rec[wnode_hi(k, a)] = ch[k].hi[a]; }
             } else {
 #pragma unroll
-                for (int a = 0; a < 3; a++) { ch[k].lo[a] = rf_load(rec + (2 * a) * 4 + k); ch[k].hi[a] = rf_load(rec + (2 * a + 1) * 4 + k); }
+                for (int a = 0; a < 3; a++) { ch[k].lo[a] = rf_load(rec + wnode_lo(k, a)); ch[k].hi[a] = rf_load(rec + wnode_hi(k, a)); }
             }
         }
         wb_quantise(ch, cnt, id, qnode + (size_t)node * 4);
@@ -148,9 +138,9 @@ __global__ __launch_bounds__(RF_BLOCK) void rf_fit_wide_kernel(const float *__re
         float *prec = (float *)(wnode + (size_t)p * 8);
         int nint = 0;
 #pragma unroll
-        for (int q = 0; q < 4; q++) { id[q] = wb_asi(prec[24 + q]); nint += id[q] > 0; }
+        for (int q = 0; q < 4; q++) { id[q] = asi(prec[wnode_id(q)]); nint += id[q] > 0; }
 #pragma unroll
-        for (int a = 0; a < 3; a++) { rf_store(prec + (2 * a) * 4 + k, lo[a]); rf_store(prec + (2 * a + 1) * 4 + k, hi[a]); }
+        for (int a = 0; a < 3; a++) { rf_store(prec + wnode_lo(k, a), lo[a]); rf_store(prec + wnode_hi(k, a), hi[a]); }
         __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const unsigned prev = __hip_atomic_fetch_add(arrive + p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (prev + 1u != (unsigned)nint) break;

@@ -37,6 +37,7 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "mpt_types.h"
+#include "tree_rules.h"      // the leaf box, the ordered ints, the half area and the record's words: shared with every other builder
 
 #define SB_BLOCK 256
 #ifndef SB_K
@@ -80,22 +81,9 @@ __host__ __device__ __forceinline__ int sb_chunk_for(int nb, long long elems) {
     return ch > SB_CHUNK_MIN ? (int)ch : SB_CHUNK_MIN;
 }
 
-__device__ __forceinline__ int sb_f2ord(float f) { int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
-__device__ __forceinline__ float sb_ord2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
 __device__ __forceinline__ float sb_scale(int nb, float cl, float ch) { return ch > cl ? nb / (ch - cl) : 0.f; }
 __device__ __forceinline__ int sb_bin_of(float c, float cl, float scale, int nb) {
     return min(nb - 1, max(0, (int)((c - cl) * scale)));
-}
-__device__ __forceinline__ float sb_half_area(const float *l, const float *h) {
-    const float dx = fmaxf(h[0] - l[0], 0.f), dy = fmaxf(h[1] - l[1], 0.f), dz = fmaxf(h[2] - l[2], 0.f);
-    return dx * dy + dy * dz + dz * dx;
-}
-// child k (0 / 1) of node `par` has this box and id: the 64-byte record is {c0.lo.x, c1.lo.x, c0.hi.x, c1.hi.x} {y} {z} {id0, id1, 0, 0}
-__device__ __forceinline__ void sb_write_child(MptVec4 *__restrict__ fnode, int par2, const float *l, const float *h, int id) {
-    float *r = (float *)(fnode + (size_t)(par2 >> 1) * 4);
-    const int k = par2 & 1;
-    for (int a = 0; a < 3; a++) { r[a * 4 + k] = l[a]; r[a * 4 + 2 + k] = h[a]; }
-    r[12 + k] = __int_as_float(id);
 }
 
 // ------------------------------------------------------------------ records of the leaf slots + the root's centre bounds
@@ -110,11 +98,10 @@ __global__ __launch_bounds__(SB_BLOCK) void sb_prims_kernel(const float *__restr
     __shared__ int is_last;
     int cb[6] = { 0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000 };
     for (int slot = blockIdx.x * SB_BLOCK + threadIdx.x; slot < n; slot += gridDim.x * SB_BLOCK) {
-        const float *p0 = verts + (size_t)leaf[slot] * 24, *p1 = p0 + 8, *p2 = p0 + 16;
         float l[3], h[3];
+        leaf_box(verts, leaf[slot], l, h);
         for (int a = 0; a < 3; a++) {
-            l[a] = fminf(fminf(p0[a], p1[a]), p2[a]); h[a] = fmaxf(fmaxf(p0[a], p1[a]), p2[a]);
-            const int c = sb_f2ord(0.5f * (l[a] + h[a]));
+            const int c = f2ord(0.5f * (l[a] + h[a]));
             cb[a] = min(cb[a], c); cb[3 + a] = max(cb[3 + a], c);
         }
         prim[(size_t)slot * 2 + 0] = { l[0], l[1], l[2], __int_as_float(slot) };
@@ -168,7 +155,7 @@ __global__ __launch_bounds__(SB_BLOCK) void sb_bin_kernel(const MptVec4 *__restr
     const int b = S[SEG_B], e = S[SEG_E];
     const int start = b + (j - S[SEG_CHUNK0]) * CH, end = min(start + CH, e);
     float cl[3], scale[3];
-    for (int a = 0; a < 3; a++) { cl[a] = sb_ord2f(S[SEG_CB + a]); scale[a] = sb_scale(nb, cl[a], sb_ord2f(S[SEG_CB + 3 + a])); }
+    for (int a = 0; a < 3; a++) { cl[a] = ord2f(S[SEG_CB + a]); scale[a] = sb_scale(nb, cl[a], ord2f(S[SEG_CB + 3 + a])); }
     const int words = 21 * nb;
     for (int k = threadIdx.x; k < words; k += SB_BLOCK) {
         const int f = k % 7;
@@ -179,7 +166,7 @@ __global__ __launch_bounds__(SB_BLOCK) void sb_bin_kernel(const MptVec4 *__restr
         const MptVec4 lo = prim[(size_t)i * 2], hi = prim[(size_t)i * 2 + 1];
         const float l[3] = { lo.x, lo.y, lo.z }, h[3] = { hi.x, hi.y, hi.z };
         int bl[3], bh[3];
-        for (int a = 0; a < 3; a++) { bl[a] = sb_f2ord(l[a]); bh[a] = sb_f2ord(h[a]); }
+        for (int a = 0; a < 3; a++) { bl[a] = f2ord(l[a]); bh[a] = f2ord(h[a]); }
         for (int a = 0; a < 3; a++) {
             const int q = sb_bin_of(0.5f * (l[a] + h[a]), cl[a], scale[a], nb);
             int *w = lb + (a * nb + q) * 7;
@@ -219,7 +206,7 @@ __device__ __forceinline__ void sb_agg_add(SbAgg &a, const SbAgg &b) {
 __device__ __forceinline__ void sb_agg_add_bin(SbAgg &a, const int *w) {      // w: {count, lo3, hi3}, ignored when empty
     if (w[0] == 0) return;
     a.c += w[0];
-    for (int r = 0; r < 3; r++) { a.l[r] = fminf(a.l[r], sb_ord2f(w[1 + r])); a.h[r] = fmaxf(a.h[r], sb_ord2f(w[4 + r])); }
+    for (int r = 0; r < 3; r++) { a.l[r] = fminf(a.l[r], ord2f(w[1 + r])); a.h[r] = fmaxf(a.h[r], ord2f(w[4 + r])); }
 }
 __device__ __forceinline__ SbAgg sb_agg_shfl_up(const SbAgg &a, int d) {
     SbAgg o; o.c = __shfl_up(a.c, d);
@@ -262,7 +249,7 @@ __device__ __forceinline__ void sb_axis_best(const int *w0, int nb, int lane, fl
             rar[t] = 0.f; rcn[t] = 0;
             if (t < per && live) {
                 sb_agg_add_bin(acc, w0 + (q0 + t) * 7);
-                rar[t] = sb_half_area(acc.l, acc.h); rcn[t] = acc.c;
+                rar[t] = half_area(acc.l, acc.h); rcn[t] = acc.c;
             }
         }
     }
@@ -274,7 +261,7 @@ __device__ __forceinline__ void sb_axis_best(const int *w0, int nb, int lane, fl
             if (t < per && live) {
                 const int q = q0 + t;
                 if (q >= 1 && acc.c != 0 && rcn[t] != 0) {
-                    const float cost = sb_half_area(acc.l, acc.h) * acc.c + rar[t] * rcn[t];
+                    const float cost = half_area(acc.l, acc.h) * acc.c + rar[t] * rcn[t];
                     if (cost < lbest) { lbest = cost; lk = acc.c; lq = q; }
                 }
                 sb_agg_add_bin(acc, w0 + q * 7);
@@ -334,7 +321,7 @@ __global__ __launch_bounds__(SB_BLOCK) void sb_choose_kernel(const int *__restri
         for (int q = lane; q < nb; q += 64) sb_agg_add_bin(own, lb + q * 7);
         for (int d = 32; d > 0; d >>= 1)
             for (int r = 0; r < 3; r++) { own.l[r] = fminf(own.l[r], __shfl_xor(own.l[r], d)); own.h[r] = fmaxf(own.h[r], __shfl_xor(own.h[r], d)); }
-        if (lane == 0) sb_write_child(fnode, par, own.l, own.h, me);
+        if (lane == 0) fnode_write_child(fnode, par, own.l, own.h, me);
     }
     __syncthreads();
     const int cnt = e - b;
@@ -490,7 +477,7 @@ __global__ __launch_bounds__(SB_BLOCK) void sb_scatter_kernel(const MptVec4 *__r
     const int child[2] = { D[DEC_CHILD0], D[DEC_CHILD1] }, sz[2] = { m - b, e - m };
     const int start = b + (j - S[SEG_CHUNK0]) * CH, end = min(start + CH, e);
     float cl = 0.f, scale = 0.f;
-    if (axis >= 0) { cl = sb_ord2f(S[SEG_CB + axis]); scale = sb_scale(nb, cl, sb_ord2f(S[SEG_CB + 3 + axis])); }
+    if (axis >= 0) { cl = ord2f(S[SEG_CB + axis]); scale = sb_scale(nb, cl, ord2f(S[SEG_CB + 3 + axis])); }
     const int lbase = ch_left[j];
     int run = 0, it = 0;
     int cb[2][6];
@@ -520,10 +507,10 @@ __global__ __launch_bounds__(SB_BLOCK) void sb_scatter_kernel(const MptVec4 *__r
             const int dest = left ? b + lr : m + (i - b) - lr;
             dst[(size_t)dest * 2] = lo; dst[(size_t)dest * 2 + 1] = hi;
             const float l[3] = { lo.x, lo.y, lo.z }, h[3] = { hi.x, hi.y, hi.z };
-            if (sz[k] == 1) sb_write_child(fnode, me * 2 + k, l, h, ~__float_as_int(lo.w));
+            if (sz[k] == 1) fnode_write_child(fnode, me * 2 + k, l, h, ~__float_as_int(lo.w));
             else if (child[k] >= 0)
                 for (int a = 0; a < 3; a++) {
-                    const int c = sb_f2ord(0.5f * (l[a] + h[a]));
+                    const int c = f2ord(0.5f * (l[a] + h[a]));
                     cb[k][a] = min(cb[k][a], c); cb[k][3 + a] = max(cb[k][3 + a], c);
                 }
         }
@@ -814,11 +801,11 @@ __global__ __launch_bounds__(64 * SF_W) void sb_finish_kernel(int ntasks, const 
 #pragma unroll
                 for (int j = E - 1; j >= 0; j--) {
                     if (tail >> j & 1) run = bx[j]; else sf_add(run, bx[j]);
-                    sarea[j] = sb_half_area(run.l, run.h);
+                    sarea[j] = half_area(run.l, run.h);
                     // a range's own box (at its first position) goes into its parent's record
                     if (a == 0 && (head >> j & 1) && (act >> j & 1)) {
                         const int par = L.spar[pb[j] >> 1];
-                        if (par >= 0) sb_write_child(fnode, par, run.l, run.h, L.snode[pb[j] >> 1]);
+                        if (par >= 0) fnode_write_child(fnode, par, run.l, run.h, L.snode[pb[j] >> 1]);
                     }
                 }
             }
@@ -835,7 +822,7 @@ __global__ __launch_bounds__(64 * SF_W) void sb_finish_kernel(int ntasks, const 
                     cost[j] = INFINITY;
                     if ((act >> j & 1) && !(head >> j & 1)) {
                         const int k = i0 + j - pb[j];
-                        cost[j] = sb_half_area(run.l, run.h) * k + sarea[j] * (pe[j] - pb[j] - k);
+                        cost[j] = half_area(run.l, run.h) * k + sarea[j] * (pe[j] - pb[j] - k);
                     }
                     sf_add(run, bx[j]);
                 }
@@ -919,7 +906,7 @@ __global__ __launch_bounds__(64 * SF_W) void sb_finish_kernel(int ntasks, const 
                 else {
                     const int q = L.ord(cur ^ 1, 0)[i];
                     const float l[3] = { L.lo[0][q], L.lo[1][q], L.lo[2][q] }, h[3] = { L.hi[0][q], L.hi[1][q], L.hi[2][q] };
-                    sb_write_child(fnode, me[j] * 2 + k, l, h, ~L.slot[q]);
+                    fnode_write_child(fnode, me[j] * 2 + k, l, h, ~L.slot[q]);
                 }
                 if (k == 0) {                                      // the pad words of the node's record (ids come from the children)
                     float *r = (float *)(fnode + (size_t)me[j] * 4);

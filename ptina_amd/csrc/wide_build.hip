@@ -14,8 +14,8 @@
 //   The level's first node and count live in a device-side table (lv[level]); the host enqueues eight levels at a time
 //   with grids sized for the most a level can hold (4^level, at most every node) and reads the table back once per group
 //   (round 6: the read-back + rocPRIM scan per level were 0.6 of the 0.9 ms this took at 100 000 triangles).
-// The arithmetic of the quantisation is the host pass's, operation for operation, without contraction (this file
-// is compiled with -ffp-contract=off): both passes produce the same bytes (tests/test_parity_gpu.py).
+// The grow step, the exact record and the quantisation are the host pass's own functions (tree_rules.h; host_collapse in
+// tree_host.h), without contraction: both passes produce the same bytes (tests/test_parity_gpu.py, tests/test_tree_rules_gpu.py).
 // An unused child slot holds the id of leaf slot n -- one extra triangle record of NaNs that no ray can hit -- and a
 // box no ray enters; round 2 stored id 0 there, the root, which a ray along (1,1,1) could be sent back to.
 
@@ -25,7 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "mpt_types.h"
-#include "wide_quant.h"      // the records taken apart, the fixed-point area, the quantisation (shared with refit.hip)
+#include "tree_rules.h"      // the records taken apart, the grow step, the quantisation, the fixed-point area (shared with the host pass and refit.hip)
 
 #define WB_BLOCK 256
 #define WB_MAX_LEVELS 64      // levels of the wide tree the level table holds (a binary tree of depth <= 62 collapses into no more)
@@ -41,13 +41,10 @@ __global__ __launch_bounds__(WB_BLOCK) void wb_expand_kernel(const MptVec4 *__re
     const bool live = t < count;
     const int w = lo + (live ? t : 0);                        // (lanes past the level stay for the wave reduction below and add 0)
     WbChild ch[4];
-    int cnt = 2;
     wb_children_of(fnode, bin_of[w], ch);
     {   // surface area of the node this record is grown from (= the union of its two children): the collapse's share of
         // the expected fetches per ray (informational: option "wide_ratio_permille")
-        WbChild own = ch[0];
-        for (int a = 0; a < 3; a++) { own.lo[a] = fminf(ch[0].lo[a], ch[1].lo[a]); own.hi[a] = fmaxf(ch[0].hi[a], ch[1].hi[a]); }
-        const unsigned long long q = live ? wb_area_fixed(fnode, wb_area(own)) : 0ull;
+        const unsigned long long q = live ? wb_area_fixed(fnode, wb_own_area(ch)) : 0ull;
         unsigned long long tot = q;                           // one atomic per workgroup, and integers: the sum does not depend on the order
         for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);      // every lane of the wave is active here (no early return)
         __shared__ unsigned long long wtot[WB_BLOCK / 64];
@@ -60,36 +57,15 @@ __global__ __launch_bounds__(WB_BLOCK) void wb_expand_kernel(const MptVec4 *__re
         }
     }
     int nint = 0;
-    if (live) {
-    while (cnt < 4) {
-        int best = -1; float ba = -1.f;
-        for (int k = 0; k < cnt; k++)
-            if (ch[k].id >= 0) { const float a = wb_area(ch[k]); if (a > ba) { ba = a; best = k; } }
-        if (best < 0) break;
-        WbChild two[2];
-        wb_children_of(fnode, ch[best].id, two);
-        ch[best] = two[0];
-        ch[cnt++] = two[1];
-    }
-    // ---- the exact record: {lo.x[4]} {hi.x[4]} {lo.y[4]} {hi.y[4]} {lo.z[4]} {hi.z[4]} {id[4]} {-}
-    float rec[32];
-    for (int k = 0; k < 32; k++) rec[k] = 0.f;
-    int ids[4];
-    for (int k = 0; k < 4; k++) {
-        float l[3] = { 1e30f, 1e30f, 1e30f }, h[3] = { 1e30f, 1e30f, 1e30f };   // unused child: out of every ray's reach
-        ids[k] = empty_id;
-        if (k < cnt) {
-            for (int a = 0; a < 3; a++) { l[a] = ch[k].lo[a]; h[a] = ch[k].hi[a]; }
-            ids[k] = ch[k].id;                        // internal children: the BINARY node for now, numbered by wb_link
-            if (ch[k].id >= 0) nint++;
-        }
-        for (int a = 0; a < 3; a++) { rec[(2 * a) * 4 + k] = l[a]; rec[(2 * a + 1) * 4 + k] = h[a]; }
-    }
-    for (int k = 0; k < 4; k++) rec[24 + k] = wb_asf(ids[k]);
-    MptVec4 *wo = wnode + (size_t)w * 8;
-    for (int k = 0; k < 8; k++) wo[k] = { rec[4 * k], rec[4 * k + 1], rec[4 * k + 2], rec[4 * k + 3] };
-    // ---- the quantised record (wide_quant.h)
-    wb_quantise(ch, cnt, ids, qnode + (size_t)w * 4);
+    if (live) {     // the exact and the quantised record (tree_rules.h); internal children: the BINARY node for now, numbered by wb_link
+        const int cnt = wb_grow(fnode, ch);
+        int ids[4];
+        MptVec4 rec[8];
+        wb_exact_record(ch, cnt, empty_id, ids, rec);
+        for (int k = 0; k < 4; k++) nint += ids[k] >= 0;
+        MptVec4 *wo = wnode + (size_t)w * 8;
+        for (int k = 0; k < 8; k++) wo[k] = rec[k];
+        wb_quantise(ch, cnt, ids, qnode + (size_t)w * 4);
     }
     // where this node's internal children start among the workgroup's (exclusive prefix, node order), and the workgroup's total
     __shared__ int wsum[WB_BLOCK / 64];
@@ -144,15 +120,15 @@ __global__ __launch_bounds__(WB_BLOCK) void wb_link_kernel(const int *__restrict
     const int t = blockIdx.x * WB_BLOCK + threadIdx.x;
     if (t >= count) return;
     const int w = lo + t;
-    MptVec4 idv = wnode[(size_t)w * 8 + 6];
-    int ids[4] = { wb_asi(idv.x), wb_asi(idv.y), wb_asi(idv.z), wb_asi(idv.w) };
+    MptVec4 idv = wnode[(size_t)w * 8 + WNODE_ID_ROW];
+    int ids[4] = { asi(idv.x), asi(idv.y), asi(idv.z), asi(idv.w) };
     int at = next + bbase[blockIdx.x] + offset[t];
     bool any = false;
     for (int k = 0; k < 4; k++)
         if (ids[k] >= 0) { bin_of[at] = ids[k]; ids[k] = at++; any = true; }
     if (any) {
-        idv = { wb_asf(ids[0]), wb_asf(ids[1]), wb_asf(ids[2]), wb_asf(ids[3]) };
-        wnode[(size_t)w * 8 + 6] = idv;
+        idv = wb_id_row(ids);
+        wnode[(size_t)w * 8 + WNODE_ID_ROW] = idv;
         qnode[(size_t)w * 4 + 3] = idv;
     }
 }
@@ -165,9 +141,7 @@ __global__ __launch_bounds__(WB_BLOCK) void wb_area_kernel(const MptVec4 *__rest
     for (int b = blockIdx.x * WB_BLOCK + threadIdx.x; b < ni; b += gridDim.x * WB_BLOCK) {
         WbChild ch[2];
         wb_children_of(fnode, b, ch);
-        WbChild own = ch[0];
-        for (int k = 0; k < 3; k++) { own.lo[k] = fminf(ch[0].lo[k], ch[1].lo[k]); own.hi[k] = fmaxf(ch[0].hi[k], ch[1].hi[k]); }
-        a += wb_area_fixed(fnode, wb_area(own));
+        a += wb_area_fixed(fnode, wb_own_area(ch));
     }
     for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
     if ((threadIdx.x & 63) == 0) wtot[threadIdx.x >> 6] = a;

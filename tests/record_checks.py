@@ -253,7 +253,7 @@ def snode_ids(snode, n):
 
 
 def area(lo, hi):
-    '''wide_quant.h wb_area in f32: lo, hi [...][3]'''
+    '''tree_rules.h wb_area in f32: lo, hi [...][3]'''
     lo, hi = np.asarray(lo, F), np.asarray(hi, F)
     with np.errstate(all='ignore'):
         d = np.fmax(hi - lo, F(0))

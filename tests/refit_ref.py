@@ -10,7 +10,7 @@ positions and returns the arrays a refit must leave, byte for byte:
                              f32 min / max of its triangle's three vertices, an internal child's the union of the used child
                              boxes of the node it names; unused slots (id ~n) and rows 6, 7 are copied from the input
   qnode       [nw][4][4] u32 the 8-bit boxes, re-quantised from the new exact ones with the builder's f32 operations one by one
-                             (wide_build.hip wb_expand / wide_quant.h wb_quantise): origin = min of the used children's lo;
+                             (wide_build.hip wb_expand / tree_rules.h wb_quantise): origin = min of the used children's lo;
                              e = hi - origin; step = e / 255, raised one ulp at a time until origin + 255 * step >= hi in f32,
                              or max(|origin| * 1e-6f, 1e-30f) on a flat axis; bytes floor((lo - origin) / step - 0.25f) and
                              ceil((hi - origin) / step + 0.25f) clamped to 0 .. 255; an unused slot 255 / 0; id row = wnode's

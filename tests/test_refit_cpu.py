@@ -4,7 +4,7 @@ the independent checker, without a GPU.  The fixture tests/golden/refit_records.
 (tests/golden/make_refit_golden.py).
 
   * a refit to the SAME vertices gives the build's wnode, qnode, bmin and bmax back byte for byte: the restatement is the
-    builders' arithmetic (the boxes' unions and wide_quant.h's quantisation, f32 operation for operation);
+    builders' arithmetic (the boxes' unions and tree_rules.h's quantisation, f32 operation for operation);
   * a refit to MOVED vertices -- the two start kinds of tests/test_refit_gpu.py, jitter and shuffle -- passes every property of
     tests/tree_checks.py against the moved vertices;
   * the checker sees a refit that is wrong: one box value or one quantised byte altered, and it names E1 / E2 / Q4;
