@@ -594,6 +594,73 @@ int mpt_deform_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
 int mpt_deform_plan(const int32_t *corners, const int32_t *dirty, int nobj, int32_t *run_obj, int64_t *run_block, int cap, int64_t *blocks);
 int mpt_skin_check(const uint16_t *joints, const float *weights, int64_t ncorners, int njoints, char *why, int why_size);
 
+/* Loop subdivision on the device (triangles in, four triangles out per level) as a property of a mesh of the pool, evaluated inside
+ * mpt_compose behind morph targets and skinning and before composition, so that a pose change of a subdivided character costs the
+ * upload of the pose, the deform kernel, L + 2 kernels over that object, the partial mpt_compose and mpt_refit_tree: topology and face
+ * count stay constant.  The result, the SUBDIVIDED COPY, is an ordinary mesh record [3 k 4^L][8] in the pool that mpt_compose reads
+ * instead of the mesh.  A mesh that is not deformable has one copy, computed once and shared by its objects; a deformable mesh has
+ * one per object, computed again when that object's pose changes.  Face g of an object of such a mesh descends from face g >> 2L of
+ * the mesh (what mpt_pick and mpt_intersect report is the refined face).
+ * The definition.  All arithmetic is f64, every sum in the order written, without contraction; a value is rounded to f32 once, when
+ * a record is written.
+ *   Control vertices: corners whose f32 positions are equal as values (-0 equals +0) are one vertex; ids are ranks of first
+ *     appearance in corner order; a vertex's position is its FIRST corner's, read from the mesh or -- a mesh with targets or a skin
+ *     -- from the object's deformed copy.  A pose that pulls welded corners apart leaves the first corner speaking for the vertex (no
+ *     cracks).  The mesh's own normals are not used.
+ *   Level l -> l + 1: even vertices keep their ids 0 .. V_l - 1; the vertex of edge e is V_l + e, edges numbered in lexicographic
+ *     order of (lower endpoint id, higher endpoint id); face f = (v0, v1, v2) becomes faces 4f .. 4f + 3: (v0, e01, e20),
+ *     (v1, e12, e01), (v2, e20, e12), (e01, e12, e20).  Windings are kept.
+ *   Ring of a vertex: its neighbours in the order of the faces' winding (in face (v, a, b), a comes before b); an interior vertex's
+ *     ring starts at the neighbour with the lowest id, a boundary vertex's at the boundary neighbour that begins the fan.
+ *   Rules (a the lower endpoint id, b the higher; c opposite in the face that runs a -> b, d opposite in the other):
+ *     interior edge    (0.375 * (a + b)) + (0.125 * (c + d))            boundary edge    0.5 * (a + b)
+ *     interior vertex  (w * v) + (beta * s):  s = ((r_0 + r_1) + r_2) + ... the ring left to right, n its length,
+ *                      beta = 0.1875 for n = 3, else 3.0 / (8.0 * n), w = 1.0 - n * beta   (Warren's weights: rational, no cosine)
+ *     boundary vertex  (0.75 * v) + (0.125 * (p + q)), p and q the first and the last of its ring.  There is no corner rule: a corner
+ *                      of an open mesh shrinks.
+ *   Normals, per vertex of the last level, on the unrounded positions: N = 0, then for its faces (v, r_i, r_i+1) in ring order (an
+ *     interior ring closes) N += cross(r_i - v, r_i+1 - v), each component x1 y2 - x2 y1 as written;
+ *     nrm = N / sqrt((Nx Nx + Ny Ny) + Nz Nz); a zero N gives NaN.  Every corner on a vertex gets that vertex's normal.
+ *   Texcoords are face-varying (seams survive): a child face takes its corners' uv from its parent's three corner uvs by the face
+ *     rule above, midpoints 0.5 * (u_i + u_j), level by level.
+ * mpt_mesh_set_subdivision: once per mesh, before the mesh has an object; before or after mpt_mesh_set_morph / mpt_mesh_set_skin.
+ *   Builds the topology on the host.  Refuses, naming the face or the vertex: an unknown mesh; a mesh that already has an object or a
+ *   level; levels outside [1, 5]; k 4^L that reaches max_faces ("too many faces"); a position that is not finite; a face with two
+ *   corners on one vertex; an edge with more than two faces; an edge that both its faces run in the same direction; a vertex whose
+ *   faces are not one fan (a bow-tie).
+ * mpt_object_add / mpt_compose count k 4^L faces for an object of such a mesh.  mpt_compose, behind the deform kernel: after objects
+ *   were added or dropped the copies get their room in the pool behind the meshes and the deformed copies and every copy is made
+ *   again; else the copies of the objects whose pose changed.  One refine launch per level, one for the normals, one for the
+ *   records, whatever the number of copies.  mpt_object_set_world / mpt_object_set_material alone subdivide nothing.  mpt_mesh_add
+ *   while copies exist takes their room (the next mpt_compose assigns it again), mpt_scene_clear gives it back.
+ * mpt_get_subdivided: the object's subdivided copy [3 k 4^L][8] as the last mpt_compose wrote it; fails for an object whose mesh has
+ *   no level, before the first mpt_compose, and when cap_faces < k 4^L.
+ * mpt_subdiv_stats: objects of subdivided meshes; copies; copies and faces the last mpt_compose refined; pool vertices the copies hold.
+ * mpt_subdiv_kernel_time: HIP-event times (ms) of the refine launches, the normals and the records of the mpt_compose calls since
+ *   the last call (any may be NULL), and the number of kernels launched.
+ * mpt_subdiv_topology: the topology as a pure function (no context, no GPU) of verts [3k][8] and levels: counts [levels + 1][3]
+ *   (vertices, edges, faces per level), and ONE block of 32-bit words, the layout the device reads -- offsets[0..5]: [0] the first
+ *   corner of every control vertex, [l] the rules of the vertices of level l, two words each, { kind | n << 2, ring }: kind 0 an
+ *   interior vertex with its n neighbours at word `ring`, 1 a boundary vertex with its n neighbours (first to last), 2 an interior
+ *   edge (a b c d), 3 a boundary edge (a b), ids of level l - 1; offsets[6]: the rules of the last level's rings (kinds 0 and 1);
+ *   offsets[7]: the last level's faces [F][3]; offsets[8] = *need_words: the words of the block, which is written when cap_words holds
+ *   it.  Returns 0, or 1 bad arguments, 2 levels outside [1, 5], 3 more than 2^24 faces, 4 a position that is not finite, 5 a face
+ *   with two corners on one vertex, 6 an edge with more than two faces, 7 an edge run twice in one direction, 8 a bow-tie, with the
+ *   words in why[why_size] (may be NULL).
+ * mpt_subdiv_plan: the run table of one of the launches as a pure function: items[njobs] per job (0: the job sits the launch out)
+ *   and dirty[njobs] (NULL: all) give, for every flagged job with items, its index and its first block, blocks of 256 items, the
+ *   first `cap` of them (any output may be NULL), and the blocks' sum.  Returns the number of runs, -1 for arguments that name no launch. */
+typedef struct {
+    int64_t subdivided_objects, copies, refined_copies, refined_faces, copy_verts;
+} mpt_subdiv_info;
+int mpt_mesh_set_subdivision(mpt_ctx *ctx, int mesh_id, int levels);
+int mpt_get_subdivided(mpt_ctx *ctx, int obj_id, float *verts, int cap_faces);
+int mpt_subdiv_stats(mpt_ctx *ctx, mpt_subdiv_info *out);
+int mpt_subdiv_kernel_time(mpt_ctx *ctx, double *refine_ms, double *normals_ms, double *records_ms, int *launches);
+int mpt_subdiv_topology(const float *verts /* [3k][8] */, int k, int levels, int64_t *counts, int32_t *offsets /* [9] */, int32_t *words,
+                        int64_t cap_words, int64_t *need_words, char *why, int why_size);
+int mpt_subdiv_plan(const int32_t *items, const int32_t *dirty, int njobs, int32_t *run_job, int64_t *run_block, int cap, int64_t *blocks);
+
 /* Refit: after the model's faces moved (mpt_compose after mpt_object_set_world, or mpt_load_model of as many faces), keep the trees
  * of the last mpt_build_tree and fit their boxes to the model again, on the device -- what a viewport does for a moved object instead of
  * building (the reference's add-on builds: blender.py:555-571).

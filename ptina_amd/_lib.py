@@ -88,6 +88,12 @@ class DeformInfo(C.Structure):
     _fields_ = [('deformable_objects', C.c_int64), ('deformed_objects', C.c_int64), ('deformed_corners', C.c_int64), ('copy_verts', C.c_int64)]
 
 
+class SubdivInfo(C.Structure):
+    '''mpt_subdiv_info (include/miptina.h): what mpt_subdiv_stats hands back'''
+    _fields_ = [('subdivided_objects', C.c_int64), ('copies', C.c_int64), ('refined_copies', C.c_int64), ('refined_faces', C.c_int64),
+                ('copy_verts', C.c_int64)]
+
+
 class RefitInfo(C.Structure):
     '''mpt_refit_info (include/miptina.h): what mpt_refit_stats hands back'''
     _fields_ = [('faces', C.c_int64), ('wide_nodes', C.c_int64), ('refits', C.c_int64), ('host_fetches', C.c_int64), ('allowed', C.c_int64),
@@ -253,6 +259,12 @@ SIGNATURES = {
     'mpt_deform_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
     'mpt_deform_plan': (_i, [_ip, _ip, _i, _ip, C.POINTER(C.c_int64), _i, C.POINTER(C.c_int64)]),
     'mpt_skin_check': (_i, [C.POINTER(C.c_uint16), _fp, C.c_int64, _i, C.c_char_p, _i]),
+    'mpt_mesh_set_subdivision': (_i, [_vp, _i, _i]),
+    'mpt_get_subdivided': (_i, [_vp, _i, _fp, _i]),
+    'mpt_subdiv_stats': (_i, [_vp, C.POINTER(SubdivInfo)]),
+    'mpt_subdiv_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_subdiv_topology': (_i, [_fp, _i, _i, C.POINTER(C.c_int64), _ip, _ip, C.c_int64, C.POINTER(C.c_int64), C.c_char_p, _i]),
+    'mpt_subdiv_plan': (_i, [_ip, _ip, _i, _ip, C.POINTER(C.c_int64), _i, C.POINTER(C.c_int64)]),
     'mpt_refit_tree': (_i, [_vp]),
     'mpt_refit_stats': (_i, [_vp, C.POINTER(RefitInfo)]),
     'mpt_refit_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
@@ -437,6 +449,53 @@ def skin_check(joints, weights, njoints):
     why = C.create_string_buffer(200)
     rc = load_library().mpt_skin_check(j.ctypes.data_as(C.POINTER(C.c_uint16)), fptr(w), j.shape[0], int(njoints), why, len(why))
     return rc, why.value.decode()
+
+
+SUBDIV_CHUNK, SUBDIV_MAX_LEVELS = 256, 5                                # csrc/mpt_types.h MPT_SUBDIV_*
+
+
+def subdiv_plan(items, dirty=None):
+    '''mpt_subdiv_plan (no context, no GPU): per-job item counts of one launch and dirty flags (None: all) -> ([(job, first block),
+    ...], its blocks); ValueError for counts that name no launch'''
+    k = np.ascontiguousarray(items, np.int32).reshape(-1)
+    d = None if dirty is None else np.ascontiguousarray(dirty, np.int32).reshape(-1)
+    if d is not None and d.shape != k.shape:
+        raise ValueError('%d dirty flags for %d jobs' % (d.size, k.size))
+    n = int(k.size)
+    job, block, blocks = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int64), C.c_int64(0)
+    nr = load_library().mpt_subdiv_plan(iptr(k), None if d is None else iptr(d), n, iptr(job), block.ctypes.data_as(C.POINTER(C.c_int64)), n,
+                                        C.byref(blocks))
+    if nr < 0:
+        raise ValueError('item counts name no launch (negative, or more than 2^31 - 1 blocks)')
+    return [(int(job[r]), int(block[r])) for r in range(nr)], int(blocks.value)
+
+
+def subdiv_topology(rec, levels):
+    '''mpt_subdiv_topology (no context, no GPU) of the records rec [3k,8] f32: (verdict, words, tables).  verdict 0 accepts, and
+    tables is then a dict: counts [levels+1,3] (vertices, edges, faces), first_corner [V_0], rules[l] for l = 1..levels -- a list
+    of (kind, [ids of level l-1]) per vertex of level l --, rings -- the same for the last level's vertices --, faces [F_L,3]'''
+    rec = np.ascontiguousarray(rec, np.float32)
+    if rec.ndim != 2 or rec.shape[1] != 8 or rec.shape[0] % 3:
+        raise ValueError('records must be [3k,8], got %s' % (rec.shape,))
+    k, levels = rec.shape[0] // 3, int(levels)
+    lib = load_library()
+    why = C.create_string_buffer(240)
+    counts, off, need = np.zeros((max(levels, 0) + 1, 3), np.int64), np.zeros(9, np.int32), C.c_int64(0)
+    cp = counts.ctypes.data_as(C.POINTER(C.c_int64))
+    rc = lib.mpt_subdiv_topology(fptr(rec), k, levels, cp, iptr(off), None, 0, C.byref(need), why, len(why))
+    if rc:
+        return rc, why.value.decode(), None
+    w = np.zeros(max(int(need.value), 1), np.int32)
+    rc = lib.mpt_subdiv_topology(fptr(rec), k, levels, cp, iptr(off), iptr(w), int(need.value), C.byref(need), why, len(why))
+    assert rc == 0
+
+    def rules(at, n):
+        head, ring = w[at:at + 2 * n:2], w[at + 1:at + 2 * n:2]
+        return [(int(h) & 3, w[int(r):int(r) + (int(h) >> 2)].tolist()) for h, r in zip(head, ring)]
+    nf = int(counts[levels, 2])
+    return 0, '', dict(counts=counts, first_corner=w[:int(counts[0, 0])].copy(),
+                       rules={l: rules(int(off[l]), int(counts[l, 0])) for l in range(1, levels + 1)},
+                       rings=rules(int(off[6]), int(counts[levels, 0])), faces=w[int(off[7]):int(off[7]) + 3 * nf].reshape(nf, 3).copy())
 
 
 def devices_isolated():

@@ -8,6 +8,7 @@
 #include "shade_feat.h"
 #include "refit_rule.h"
 #include "deform_rule.h"
+#include "subdiv_rule.h"
 #include "history_rule.h"
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
@@ -106,6 +107,13 @@ MPT_KERNEL_API hipError_t mpt_launch_compose(const float *pool, const MptCompose
 MPT_KERNEL_API hipError_t mpt_launch_deform(float *pool, const MptDeformObj *objs, const MptDeformRun *runs, int nruns, int blocks,
                                             const float *deltas, const uint16_t *joints, const float *weights, const double *pose,
                                             hipStream_t stream);
+// subdiv.hip: the subdivided copies of a launch's jobs -- one refine launch per level, the last level's normals, the records (mpt_compose)
+MPT_KERNEL_API hipError_t mpt_launch_subdiv_refine(const float *pool, const MptSubdivJob *jobs, const MptSubdivRun *runs, int nruns, int blocks,
+                                                   int level, const int32_t *topo, double *work, hipStream_t stream);
+MPT_KERNEL_API hipError_t mpt_launch_subdiv_normals(const MptSubdivJob *jobs, const MptSubdivRun *runs, int nruns, int blocks, const int32_t *topo,
+                                                    double *work, hipStream_t stream);
+MPT_KERNEL_API hipError_t mpt_launch_subdiv_emit(float *pool, const MptSubdivJob *jobs, const MptSubdivRun *runs, int nruns, int blocks,
+                                                 const int32_t *topo, const double *work, hipStream_t stream);
 
 // on-GPU LBVH build (lbvh_build.hip)
 struct MptLbvhBuffers {
@@ -411,6 +419,16 @@ struct MPT_INTERNAL MptDeformBufs {
     DevBuf<MptDeformObj> objs;           // a launch's objects
     DevBuf<MptDeformRun> runs;           // ... and its runs of blocks
     int reserve_tables(size_t nobj) { return objs.reserve(nobj) || runs.reserve(nobj); }
+};
+
+// Loop subdivision's device memory (scene_subdiv.cpp): the arena of the meshes' topology blocks, appended by mpt_mesh_set_subdivision
+// (it grows by copying, as the mesh pool does), the jobs' f64 workspace and a launch's tables
+struct MPT_INTERNAL MptSubdivBufs {
+    DevBuf<int32_t> topo;                // every subdivided mesh's block of words (subdiv_rule.h), back to back
+    DevBuf<double> work;                 // per job: the positions of levels 1..L, then the last level's vertex records
+    DevBuf<MptSubdivJob> jobs;           // a compose's jobs
+    DevBuf<MptSubdivRun> runs;           // ... and the runs of its launches, (MPT_SUBDIV_MAX_LEVELS + 2) tables of up to a run per job
+    int reserve_tables(size_t njobs) { return jobs.reserve(njobs) || runs.reserve(njobs * (MPT_SUBDIV_MAX_LEVELS + 2)); }
 };
 
 struct MPT_INTERNAL MptLbvhBufs {          // workspace and result of the device LBVH build (lbvh_build.hip)
@@ -723,6 +741,32 @@ struct mpt_ctx {
         MptLaunchTimer timer;                            // mpt_compose: {before the deform kernel, after it} per launch
         explicit Deform(MptEventPool &ev) : timer(2, ev) {}
     } deform{events};
+    struct MptSubdivMesh {                               // what a mesh of the pool carries: its level and where its topology lies
+        int levels = 0; size_t topo_at = 0;
+        int64_t nv[MPT_SUBDIV_MAX_LEVELS + 1] = {};
+        int32_t rule_at[MPT_SUBDIV_MAX_LEVELS + 1] = {}, nrule_at = 0, face_at = 0;
+        int job = -1;                                    // the shared copy of a mesh that is not deformable (-1: no object yet)
+    };
+    struct MptSubdivCopy {                               // a subdivided copy: of a mesh that is not deformable, or of one object of a mesh that is
+        int mesh = 0, obj = -1;                          // obj -1: shared by the mesh's objects
+        long long copy_vert = -1; size_t work_at = 0;    // where the copy and its workspace lie (copy_vert -1: no room assigned yet)
+        bool dirty = true;                               // the control records changed since the copy was written
+    };
+    struct MPT_INTERNAL Subdiv {                         // Loop subdivision (scene_subdiv.cpp: mpt_mesh_set_subdivision, subdiv_step)
+        std::vector<MptSubdivMesh> meshes;               // per mesh of the pool
+        std::vector<int> obj_copy;                       // per object of the table: its row of `copies` (-1: its mesh is not subdivided)
+        std::vector<MptSubdivCopy> copies;
+        size_t topo_used = 0;                            // words of bufs.topo
+        size_t copy_verts = 0;                           // pool vertices the copies hold, behind the meshes and the deformed copies
+        bool stale = true;                               // the copies' room is not assigned, or the pool it lay in has gone
+        std::vector<MptSubdivJob> h_jobs;                // the last compose's tables as uploaded: they outlive the copies that read them
+        std::vector<MptSubdivRun> h_runs;
+        MptSubdivBufs bufs;
+        mpt_subdiv_info stats{};
+        int launches = 0;                                // kernels launched since mpt_subdiv_kernel_time last asked
+        MptLaunchTimer refine_timer, normal_timer, emit_timer;   // mpt_compose: {before, after} the refine launches, the normals, the records
+        explicit Subdiv(MptEventPool &ev) : refine_timer(2, ev), normal_timer(2, ev), emit_timer(2, ev) {}
+    } subdiv{events};
     struct MPT_INTERNAL Refit {                          // mpt_refit_tree (tree_refit.cpp, refit_rule.h)
         int topo = MPT_TOPO_NONE;                        // MptTopoState: do the node records hold a topology, and if not, why not
         int faces = 0; bool on_device = false;           // ... for this many faces, from the device build
@@ -854,6 +898,14 @@ MPT_INTERNAL void deform_mesh_added(mpt_ctx *c);                 // a mesh joine
 MPT_INTERNAL void deform_object_added(mpt_ctx *c, int mesh_id);
 MPT_INTERNAL void deform_scene_cleared(mpt_ctx *c, int meshes);
 MPT_INTERNAL int deform_step(mpt_ctx *c);                        // before compose_kernel: room, poses, the deform launch; rewrites objs' mesh_vert at a relayout
+
+// scene_subdiv.cpp: what scene_compose.cpp and scene_deform.cpp tell the subdivision table, and the step of mpt_compose behind deform_step
+MPT_INTERNAL void subdiv_mesh_added(mpt_ctx *c);                 // a mesh joined the pool: the copies behind the meshes lose their room
+MPT_INTERNAL int subdiv_object_faces(const mpt_ctx *c, int mesh_id);   // the faces an object of this mesh has: k * 4^L
+MPT_INTERNAL void subdiv_object_added(mpt_ctx *c, int mesh_id);
+MPT_INTERNAL void subdiv_pose_changed(mpt_ctx *c, int obj_id);   // mpt_object_set_morph_weights / mpt_object_set_joints
+MPT_INTERNAL void subdiv_scene_cleared(mpt_ctx *c, int meshes);
+MPT_INTERNAL int subdiv_step(mpt_ctx *c);                        // behind deform_step: room, the launches; rewrites objs' mesh_vert at a relayout
 
 // film_read.cpp
 MPT_INTERNAL int check_pass(mpt_ctx *c, int pass);

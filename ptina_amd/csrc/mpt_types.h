@@ -252,3 +252,24 @@ struct MptDeformObj {                       // 48 bytes
     int64_t pose_at;                         // the object's pose: ntargets weights, then njoints 3x4 matrices, f64: first double
 };
 struct MptDeformRun { int32_t obj, block; };
+
+// Loop subdivision (subdiv.hip): the caps, the kinds of a vertex rule (subdiv_rule.h), one job of a launch -- a subdivided copy: where
+// its control records and the copy lie in the pool, where its mesh's topology block lies in the arena of words and its own f64
+// vertices in the workspace -- and a run of a launch's blocks: job `job` takes the blocks from `block`, MPT_SUBDIV_CHUNK items each
+#define MPT_SUBDIV_MAX_LEVELS 5
+#define MPT_SUBDIV_MAX_FACES (1 << 24)      // faces of a last level the topology function takes (the context's max_faces is lower)
+#define MPT_SUBDIV_CHUNK 256                // items (vertices or faces) per workgroup: one per lane
+enum { MPT_SUBDIV_VERT_INT = 0, MPT_SUBDIV_VERT_BND = 1, MPT_SUBDIV_EDGE_INT = 2, MPT_SUBDIV_EDGE_BND = 3 };
+struct MptSubdivJob {                       // 128 bytes
+    int32_t src_vert, dst_vert;              // first pool vertex of the control records (the mesh or a deformed copy) and of the subdivided copy
+    int32_t levels, nfaces;                  // L, and the faces of the last level: k * 4^L
+    int64_t topo_at;                         // the mesh's topology block: first word in the arena
+    int64_t work_at;                         // the job's workspace: first double (even)
+    int32_t nv[MPT_SUBDIV_MAX_LEVELS + 1];   // vertices of level 0..L
+    int32_t rule_at[MPT_SUBDIV_MAX_LEVELS + 1];   // words from topo_at: [l] the rules of level l's vertices ([0]: the first corners)
+    int32_t pos_at[MPT_SUBDIV_MAX_LEVELS + 1];    // doubles from work_at: [l] the positions [V_l][3] of level l ([0] unused: level 0 is read from the pool)
+    int32_t nrule_at, face_at;               // words from topo_at: the last level's rings, its faces' vertex ids
+    int32_t vrec_at;                         // doubles from work_at (even): the last level's vertex records, 32 bytes each: pos3 nrm3 as f32, 8 bytes unused
+    int32_t pad[3];
+};
+struct MptSubdivRun { int32_t job, block; };

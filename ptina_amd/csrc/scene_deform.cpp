@@ -120,6 +120,7 @@ extern "C" int mpt_object_set_morph_weights(mpt_ctx *c, int obj_id, const double
     memcpy(p->pose.data(), w, (size_t)T * sizeof(double));
     p->dirty = true;
     c->compose.dirty[obj_id] = 1;
+    subdiv_pose_changed(c, obj_id);
     return 0;
 }
 
@@ -141,6 +142,7 @@ extern "C" int mpt_object_set_joints(mpt_ctx *c, int obj_id, const double *mats,
     for (int j = 0; j < nj; j++) memcpy(p->pose.data() + T + (size_t)j * 12, mats + 16 * j, 12 * sizeof(double));
     p->dirty = true;
     c->compose.dirty[obj_id] = 1;
+    subdiv_pose_changed(c, obj_id);
     return 0;
 }
 

@@ -1,0 +1,262 @@
+// scene_subdiv.cpp -- Loop subdivision behind mpt_mesh_set_subdivision: the meshes' topology blocks on the
+// device (subdiv_rule.h makes them, a pure function), the table of subdivided copies beside scene_compose.cpp's object table and
+// scene_deform.cpp's poses, the run tables of a compose's launches (mpt_subdiv_plan, a pure function), and subdiv_step: the part of
+// mpt_compose behind deform_step that gives the copies their room in the pool and launches subdiv.hip before compose_kernel.
+
+#include "miptina_ctx.h"
+
+extern "C" int mpt_subdiv_plan(const int32_t *items, const int32_t *dirty, int njobs, int32_t *run_job, int64_t *run_block, int cap, int64_t *blocks) {
+    return mpt_subdiv_plan_of(items, dirty, njobs, run_job, run_block, cap, blocks);
+}
+
+extern "C" int mpt_subdiv_topology(const float *verts, int k, int levels, int64_t *counts, int32_t *offsets, int32_t *words, int64_t cap_words,
+                                   int64_t *need_words, char *why, int why_size) {
+    MptSubdivTopo t;
+    const MptSubdivVerdict v = mpt_subdiv_topology_of(verts, k, levels, t, why, why_size > 0 ? (size_t)why_size : 0);
+    if (v != MPT_SUBDIV_OK) return (int)v;
+    if (counts)
+        for (int l = 0; l <= levels; l++) { counts[3 * l] = t.nv[l]; counts[3 * l + 1] = t.ne[l]; counts[3 * l + 2] = t.nf[l]; }
+    if (offsets) {
+        for (int l = 0; l <= MPT_SUBDIV_MAX_LEVELS; l++) offsets[l] = l <= levels ? t.rule_at[l] : 0;
+        offsets[6] = t.nrule_at; offsets[7] = t.face_at; offsets[8] = (int32_t)t.words.size();
+    }
+    if (need_words) *need_words = (int64_t)t.words.size();
+    if (words && cap_words >= (int64_t)t.words.size()) memcpy(words, t.words.data(), t.words.size() * sizeof(int32_t));
+    return 0;
+}
+
+// ---------------------------------------------------------------- what scene_compose.cpp and scene_deform.cpp tell the table
+void subdiv_mesh_added(mpt_ctx *c) {
+    auto &sd = c->subdiv;
+    sd.meshes.resize(c->compose.meshes.size());
+    if (sd.copy_verts == 0) return;
+    sd.copy_verts = 0; sd.stale = true;                // the new mesh lies where the copies lay
+    for (auto &p : sd.copies) p.copy_vert = -1;
+    c->compose.relayout = true;
+}
+
+int subdiv_object_faces(const mpt_ctx *c, int mesh_id) {
+    const int k = c->compose.meshes[mesh_id].nfaces;
+    const auto &sd = c->subdiv;
+    return (size_t)mesh_id < sd.meshes.size() ? k << (2 * sd.meshes[mesh_id].levels) : k;
+}
+
+void subdiv_object_added(mpt_ctx *c, int mesh_id) {
+    auto &sd = c->subdiv;
+    sd.meshes.resize(c->compose.meshes.size());
+    const int obj = (int)sd.obj_copy.size();
+    auto &m = sd.meshes[mesh_id];
+    if (m.levels == 0) { sd.obj_copy.push_back(-1); return; }
+    const bool deformable = c->deform.obj_pose[obj] >= 0;
+    if (deformable || m.job < 0) {
+        mpt_ctx::MptSubdivCopy p;
+        p.mesh = mesh_id; p.obj = deformable ? obj : -1;
+        sd.copies.push_back(p);
+        if (!deformable) m.job = (int)sd.copies.size() - 1;
+    }
+    sd.obj_copy.push_back(deformable ? (int)sd.copies.size() - 1 : m.job);
+    sd.stale = true;
+}
+
+void subdiv_pose_changed(mpt_ctx *c, int obj_id) {
+    auto &sd = c->subdiv;
+    if ((size_t)obj_id < sd.obj_copy.size() && sd.obj_copy[obj_id] >= 0) sd.copies[sd.obj_copy[obj_id]].dirty = true;
+}
+
+void subdiv_scene_cleared(mpt_ctx *c, int meshes) {
+    auto &sd = c->subdiv;
+    sd.obj_copy.clear(); sd.copies.clear();
+    for (auto &m : sd.meshes) m.job = -1;
+    sd.copy_verts = 0; sd.stale = true;
+    if (meshes) { sd.meshes.clear(); sd.topo_used = 0; }
+}
+
+// ---------------------------------------------------------------- the meshes' levels
+extern "C" int mpt_mesh_set_subdivision(mpt_ctx *c, int mesh_id, int levels) {
+    if (use(c)) return 1;
+    auto &sd = c->subdiv;
+    auto &cp = c->compose;
+    if (mesh_id < 0 || (size_t)mesh_id >= cp.meshes.size()) return fail("mpt_mesh_set_subdivision: unknown mesh %d (%zu meshes)", mesh_id, cp.meshes.size());
+    for (size_t o = 0; o < c->deform.obj_mesh.size(); o++)
+        if (c->deform.obj_mesh[o] == mesh_id) return fail("mpt_mesh_set_subdivision: mesh %d already has an object (object %zu)", mesh_id, o);
+    sd.meshes.resize(cp.meshes.size());
+    if (sd.meshes[mesh_id].levels) return fail("mpt_mesh_set_subdivision: mesh %d already has a subdivision level", mesh_id);
+    if (levels < 1 || levels > MPT_SUBDIV_MAX_LEVELS) return fail("mpt_mesh_set_subdivision: levels %d outside [1, %d]", levels, MPT_SUBDIV_MAX_LEVELS);
+    const int k = cp.meshes[mesh_id].nfaces;
+    if (((long long)k << (2 * levels)) >= c->caps.max_faces)
+        return fail("mpt_mesh_set_subdivision: too many faces: %lld at level %d", (long long)k << (2 * levels), levels);
+    std::vector<float> rec((size_t)k * 24);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (k > 0) HIP_TRY(hipMemcpy(rec.data(), cp.bufs.pool + cp.meshes[mesh_id].vert * 8, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
+    MptSubdivTopo t;
+    char why[200];
+    if (mpt_subdiv_topology_of(rec.data(), k, levels, t, why, sizeof why) != MPT_SUBDIV_OK) return fail("mpt_mesh_set_subdivision: mesh %d: %s", mesh_id, why);
+    const size_t words = t.words.size();
+    if (grow_keeping(sd.bufs.topo, sd.topo_used + words, sd.topo_used, c->stream)) return 1;
+    if (words > 0) {
+        HIP_TRY(hipMemcpyAsync(sd.bufs.topo + sd.topo_used, t.words.data(), words * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    auto &m = sd.meshes[mesh_id];
+    m.levels = levels; m.topo_at = sd.topo_used; m.job = -1;
+    for (int l = 0; l <= levels; l++) { m.nv[l] = t.nv[l]; m.rule_at[l] = t.rule_at[l]; }
+    m.nrule_at = t.nrule_at; m.face_at = t.face_at;
+    sd.topo_used += words;
+    return 0;
+}
+
+// ---------------------------------------------------------------- the step of mpt_compose
+// the doubles of a copy's workspace: the positions of levels 1..L (each level from an even offset), then the last level's records
+static size_t work_layout(const mpt_ctx::MptSubdivMesh &m, MptSubdivJob *job) {
+    size_t at = 0;
+    for (int l = 1; l <= m.levels; l++) {
+        if (job) job->pos_at[l] = (int32_t)at;
+        at += ((size_t)m.nv[l] * 3 + 1) & ~(size_t)1;
+    }
+    if (job) job->vrec_at = (int32_t)at;
+    return at + (size_t)m.nv[m.levels] * 4;
+}
+
+// Called with deform_step's launch (if any) queued.  At a relayout (objects added or dropped, or the copies lost their room) the
+// copies are laid out behind the meshes and the deformed copies, the pool grows to hold them, the objects' mesh_vert is pointed at
+// them -- mpt_compose then uploads the whole table -- and every copy is subdivided; else the copies of the objects whose pose
+// changed.  Nothing here waits for the device, except a pool that has to grow.
+int subdiv_step(mpt_ctx *c) {
+    auto &cp = c->compose;
+    auto &sd = c->subdiv;
+    auto &df = c->deform;
+    sd.stats.refined_copies = sd.stats.refined_faces = 0;
+    const int n = (int)sd.copies.size();
+    if (n == 0) { sd.stats.copy_verts = 0; return 0; }
+    const bool all = cp.relayout || sd.stale;
+    if (all) {
+        const size_t base = cp.pool_verts + df.copy_verts;
+        size_t at = base, work = 0;
+        for (auto &p : sd.copies) {
+            at += (size_t)subdiv_object_faces(c, p.mesh) * 3;
+            work += work_layout(sd.meshes[p.mesh], nullptr);
+        }
+        if (at > 0x7fffffffu) return fail("mesh pool full: %zu vertices with the subdivided copies", at);   // (MptComposeObj::mesh_vert)
+        if (cp.bufs.grow_pool(at * 8, base * 8, c->stream)) return 1;     // (keeps the meshes and the deformed copies; waits for the deform launch)
+        if (sd.bufs.work.reserve(std::max(work, (size_t)2)) || sd.bufs.reserve_tables((size_t)n)) return 1;
+        at = base; work = 0;
+        for (auto &p : sd.copies) {
+            p.copy_vert = (long long)at; p.work_at = work;
+            at += (size_t)subdiv_object_faces(c, p.mesh) * 3;
+            work += work_layout(sd.meshes[p.mesh], nullptr);
+        }
+        for (size_t o = 0; o < sd.obj_copy.size(); o++)
+            if (sd.obj_copy[o] >= 0) cp.objs[o].mesh_vert = (int32_t)sd.copies[sd.obj_copy[o]].copy_vert;
+        sd.copy_verts = at - base;
+        cp.relayout = true;                            // the table's mesh_vert changed: all of it goes up
+        sd.stale = false;
+    }
+    sd.stats.copy_verts = (int64_t)sd.copy_verts;
+    std::vector<MptSubdivJob> &jobs = sd.h_jobs;
+    jobs.assign((size_t)n, MptSubdivJob{});
+    std::vector<int32_t> dirty((size_t)n);
+    int lmax = 0, ndirty = 0;
+    for (int j = 0; j < n; j++) {
+        const auto &p = sd.copies[j];
+        const auto &m = sd.meshes[p.mesh];
+        MptSubdivJob &t = jobs[j];
+        t.src_vert = p.obj >= 0 ? (int32_t)df.poses[df.obj_pose[p.obj]].copy_vert : (int32_t)cp.meshes[p.mesh].vert;
+        t.dst_vert = (int32_t)p.copy_vert;
+        t.levels = m.levels; t.nfaces = subdiv_object_faces(c, p.mesh);
+        t.topo_at = (int64_t)m.topo_at; t.work_at = (int64_t)p.work_at;
+        for (int l = 0; l <= m.levels; l++) { t.nv[l] = (int32_t)m.nv[l]; t.rule_at[l] = m.rule_at[l]; }
+        t.nrule_at = m.nrule_at; t.face_at = m.face_at;
+        work_layout(m, &t);
+        dirty[j] = all || p.dirty;
+        if (!dirty[j] || t.nfaces == 0) continue;
+        ndirty++; lmax = std::max(lmax, m.levels);
+        sd.stats.refined_copies++; sd.stats.refined_faces += t.nfaces;
+    }
+    for (auto &p : sd.copies) p.dirty = false;
+    if (ndirty == 0) return 0;
+    // the run tables: launch t = 0 .. lmax - 1 refines to level t + 1, then the normals, then the records
+    const int ntables = lmax + 2;
+    std::vector<MptSubdivRun> &runs = sd.h_runs;
+    runs.assign((size_t)ntables * (size_t)n, MptSubdivRun{});
+    std::vector<int> nruns((size_t)ntables), blocks((size_t)ntables);
+    std::vector<int32_t> items((size_t)n), run_job((size_t)n);
+    std::vector<int64_t> run_block((size_t)n);
+    for (int t = 0; t < ntables; t++) {
+        for (int j = 0; j < n; j++)
+            items[j] = t < lmax ? (jobs[j].levels > t ? jobs[j].nv[t + 1] : 0) : t == lmax ? jobs[j].nv[jobs[j].levels] : jobs[j].nfaces;
+        int64_t b = 0;
+        nruns[t] = mpt_subdiv_plan_of(items.data(), dirty.data(), n, run_job.data(), run_block.data(), n, &b);
+        if (nruns[t] < 0) return fail("too many faces to subdivide");
+        blocks[t] = (int)b;
+        for (int r = 0; r < nruns[t]; r++) runs[(size_t)t * (size_t)n + (size_t)r] = { run_job[r], (int32_t)run_block[r] };
+    }
+    HIP_TRY(hipMemcpyAsync(sd.bufs.jobs, jobs.data(), (size_t)n * sizeof(MptSubdivJob), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(sd.bufs.runs, runs.data(), runs.size() * sizeof(MptSubdivRun), hipMemcpyHostToDevice, c->stream));
+    {
+        MptTimedSpan span(sd.refine_timer, c->stream);
+        HIP_TRY(span.begun);
+        for (int t = 0; t < lmax; t++) {
+            HIP_TRY(mpt_launch_subdiv_refine(cp.bufs.pool, sd.bufs.jobs, sd.bufs.runs + (size_t)t * (size_t)n, nruns[t], blocks[t], t + 1, sd.bufs.topo,
+                                             sd.bufs.work, c->stream));
+            sd.launches++;
+        }
+        HIP_TRY(span.end());
+    }
+    {
+        MptTimedSpan span(sd.normal_timer, c->stream);
+        HIP_TRY(span.begun);
+        HIP_TRY(mpt_launch_subdiv_normals(sd.bufs.jobs, sd.bufs.runs + (size_t)lmax * (size_t)n, nruns[lmax], blocks[lmax], sd.bufs.topo, sd.bufs.work,
+                                          c->stream));
+        sd.launches++;
+        HIP_TRY(span.end());
+    }
+    {
+        MptTimedSpan span(sd.emit_timer, c->stream);
+        HIP_TRY(span.begun);
+        HIP_TRY(mpt_launch_subdiv_emit(cp.bufs.pool, sd.bufs.jobs, sd.bufs.runs + (size_t)(lmax + 1) * (size_t)n, nruns[lmax + 1], blocks[lmax + 1],
+                                       sd.bufs.topo, sd.bufs.work, c->stream));
+        sd.launches++;
+        HIP_TRY(span.end());
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- read-backs
+extern "C" int mpt_get_subdivided(mpt_ctx *c, int obj_id, float *verts, int cap_faces) {
+    if (use_ro(c)) return 1;
+    auto &sd = c->subdiv;
+    if (obj_id < 0 || (size_t)obj_id >= sd.obj_copy.size()) return fail("mpt_get_subdivided: unknown object %d (%zu objects)", obj_id, sd.obj_copy.size());
+    if (sd.obj_copy[obj_id] < 0) return fail("mpt_get_subdivided: the mesh of object %d has no subdivision level", obj_id);
+    const auto &p = sd.copies[sd.obj_copy[obj_id]];
+    if (p.copy_vert < 0 || sd.stale) return fail("mpt_get_subdivided: object %d has no subdivided copy yet: call mpt_compose", obj_id);
+    const int k = subdiv_object_faces(c, p.mesh);
+    if (cap_faces < k) return fail("mpt_get_subdivided: room for %d faces, the subdivided mesh of object %d has %d", cap_faces, obj_id, k);
+    if (k > 0 && !verts) return fail("mpt_get_subdivided: null verts");
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (k > 0) HIP_TRY(hipMemcpy(verts, c->compose.bufs.pool + (size_t)p.copy_vert * 8, (size_t)k * 24 * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int mpt_subdiv_stats(mpt_ctx *c, mpt_subdiv_info *out) {
+    if (!c || !out) return fail("null argument");
+    *out = c->subdiv.stats;
+    out->subdivided_objects = 0;
+    for (int j : c->subdiv.obj_copy) out->subdivided_objects += j >= 0;
+    out->copies = (int64_t)c->subdiv.copies.size();
+    out->copy_verts = (int64_t)c->subdiv.copy_verts;
+    return 0;
+}
+
+extern "C" int mpt_subdiv_kernel_time(mpt_ctx *c, double *refine_ms, double *normals_ms, double *records_ms, int *launches) {
+    if (use_ro(c)) return 1;
+    auto &sd = c->subdiv;
+    double seg[3] = { 0, 0, 0 };
+    if (timer_readout(c, sd.refine_timer, &seg[0], nullptr, nullptr) || timer_readout(c, sd.normal_timer, &seg[1], nullptr, nullptr) ||
+        timer_readout(c, sd.emit_timer, &seg[2], nullptr, nullptr)) return 1;
+    if (refine_ms) *refine_ms = seg[0];
+    if (normals_ms) *normals_ms = seg[1];
+    if (records_ms) *records_ms = seg[2];
+    if (launches) *launches = sd.launches;
+    sd.launches = 0;
+    return 0;
+}

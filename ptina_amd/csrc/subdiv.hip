@@ -1,0 +1,197 @@
+// subdiv.hip -- Loop subdivision on the device: a mesh of the pool that carries a subdivision level L gets a
+// SUBDIVIDED COPY, an ordinary object-space mesh record [3 k 4^L][8] (pos3 nrm3 uv2, f32) that compose_kernel then reads as it reads
+// any mesh.  It is evaluated behind morph targets and skinning (deform.hip) and before composition.
+//
+// The definition (also include/miptina.h).  All arithmetic is f64, every sum in the order written, without contraction
+// (-ffp-contract=off, the Makefile's rule for this file); a value is rounded to f32 once, when a record is written.
+//   Control vertices: corners whose f32 positions are equal as values (-0 equals +0) are one vertex; ids are ranks of first
+//     appearance in corner order; a vertex's position is its FIRST corner's, widened to f64, read from the mesh or -- a mesh with
+//     targets or a skin -- from the object's deformed copy.  A pose that pulls welded corners apart leaves the first corner
+//     speaking for the vertex: no cracks.  The mesh's own normals are not used.
+//   Level l -> l + 1: even vertices keep their ids 0 .. V_l - 1; the vertex of edge e is V_l + e, edges numbered in lexicographic
+//     order of (lower endpoint id, higher endpoint id); face f = (v0, v1, v2) becomes faces 4f .. 4f + 3:
+//     (v0, e01, e20), (v1, e12, e01), (v2, e20, e12), (e01, e12, e20).
+//   Ring of a vertex: its neighbours in the order of the faces' winding (in face (v, a, b), a comes before b); an interior vertex's
+//     ring starts at the neighbour with the lowest id, a boundary vertex's at the boundary neighbour that begins the fan.
+//   Rules (a the lower endpoint id, b the higher; c opposite in the face that runs a -> b, d opposite in the other):
+//     interior edge      (0.375 * (a + b)) + (0.125 * (c + d))
+//     boundary edge      0.5 * (a + b)
+//     interior vertex    (w * v) + (beta * s),  s = ((r_0 + r_1) + r_2) + ... the ring left to right,  n its length,
+//                        beta = 0.1875 for n = 3, else 3.0 / (8.0 * n);  w = 1.0 - n * beta    (Warren's weights)
+//     boundary vertex    (0.75 * v) + (0.125 * (p + q)),  p and q the first and the last of its ring.  There is no corner rule: a
+//                        corner of an open mesh shrinks.
+//   Normals, per vertex of the last level, on the unrounded positions: N = 0; for the vertex's faces (v, r_i, r_i+1) in ring order
+//     (an interior ring closes, a boundary ring does not): A = r_i - v, B = r_i+1 - v,
+//     N += (Ay Bz - Az By, Az Bx - Ax Bz, Ax By - Ay Bx);  nrm = N / sqrt((Nx Nx + Ny Ny) + Nz Nz).  A zero N gives NaN.  Every
+//     corner on a vertex gets that vertex's normal: the surface is smooth.
+//   Texcoords are face-varying: a child face takes its corners' uv from its parent's three corner uvs by the face rule above, the
+//     midpoints m_ij = 0.5 * (u_i + u_j) in f64, level by level.
+//
+// Three kernels, each one lane per item (a workgroup of 256 lanes takes MPT_SUBDIV_CHUNK items of ONE job; a run table maps blocks to
+// (job, chunk): compose_kernel's and deform_kernel's idiom), so the number of launches of an mpt_compose is L_max + 2 whatever the
+// number of copies; a job of fewer levels has no blocks in the later refine launches.  Levels are separate launches: nothing is
+// handed from workgroup to workgroup inside a launch.
+//   subdiv_refine_kernel   level l - 1 -> l: a lane reads its vertex's rule (two words), gathers 2 to n + 1 positions of the level
+//                          below -- level 0 from the pool through the first-corner table, else 24-byte f64 records of the
+//                          workspace -- and writes one.
+//   subdiv_normal_kernel   the last level: a lane walks its vertex's ring and writes the vertex record (pos3 nrm3 as f32: the one
+//                          rounding), 32 bytes, two 16-byte stores.
+//   subdiv_emit_kernel     a lane per refined face: three vertex ids, three 32-byte gathers (a vertex is shared by six corners, so
+//                          they hit in L2), the parent's three uvs and L midpoint steps, six 16-byte stores: 96 bytes.
+// Vector stores only, no atomics, no LDS.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <math.h>
+#include "mpt_types.h"
+
+enum { SD_BLOCK = MPT_SUBDIV_CHUNK };
+static_assert(sizeof(MptSubdivJob) == 128, "the job record is 128 bytes");
+
+struct SdVec { double x, y, z; };
+static __device__ __forceinline__ SdVec sd_add(SdVec a, SdVec b) { return { a.x + b.x, a.y + b.y, a.z + b.z }; }
+static __device__ __forceinline__ SdVec sd_sub(SdVec a, SdVec b) { return { a.x - b.x, a.y - b.y, a.z - b.z }; }
+static __device__ __forceinline__ SdVec sd_mul(double s, SdVec a) { return { s * a.x, s * a.y, s * a.z }; }
+
+// the run a block belongs to (uniform), as deform_kernel finds it
+static __device__ __forceinline__ int sd_run(const MptSubdivRun *__restrict__ runs, int nruns) {
+    int a = 0, b = nruns - 1;
+    while (a < b) { const int m = (a + b + 1) >> 1; if (runs[m].block <= (int)blockIdx.x) a = m; else b = m - 1; }
+    return a;
+}
+
+// the position of vertex v of the level below `level`
+static __device__ __forceinline__ SdVec sd_pos(const MptSubdivJob &o, int level, const float4 *pool, const int32_t *__restrict__ T,
+                                               const double *work, int v) {
+    if (level == 1) {
+        const float4 q = pool[((size_t)o.src_vert + (size_t)T[v]) * 2];
+        return { (double)q.x, (double)q.y, (double)q.z };
+    }
+    const double *p = work + o.work_at + o.pos_at[level - 1] + (size_t)v * 3;
+    return { p[0], p[1], p[2] };
+}
+
+__global__ __launch_bounds__(SD_BLOCK) void subdiv_refine_kernel(const float4 *pool, const MptSubdivJob *__restrict__ jobs,
+                                                                 const MptSubdivRun *__restrict__ runs, int nruns, int level,
+                                                                 const int32_t *__restrict__ topo, double *work) {
+    const int r = sd_run(runs, nruns);
+    const MptSubdivJob &o = jobs[runs[r].job];          // (fields read through the scalar cache: a copy indexed by the level would live in scratch)
+    const int i = ((int)blockIdx.x - runs[r].block) * SD_BLOCK + (int)threadIdx.x;
+    if (i >= o.nv[level]) return;
+    const int32_t *__restrict__ T = topo + o.topo_at;
+    const int32_t head = T[o.rule_at[level] + 2 * i], at = T[o.rule_at[level] + 2 * i + 1];
+    const int kind = head & 3, n = head >> 2;
+    const int32_t *__restrict__ ring = T + at;
+    SdVec out;
+    if (kind == MPT_SUBDIV_EDGE_INT) {
+        const SdVec a = sd_pos(o, level, pool, T, work, ring[0]), b = sd_pos(o, level, pool, T, work, ring[1]);
+        const SdVec c = sd_pos(o, level, pool, T, work, ring[2]), d = sd_pos(o, level, pool, T, work, ring[3]);
+        out = sd_add(sd_mul(0.375, sd_add(a, b)), sd_mul(0.125, sd_add(c, d)));
+    } else if (kind == MPT_SUBDIV_EDGE_BND) {
+        const SdVec a = sd_pos(o, level, pool, T, work, ring[0]), b = sd_pos(o, level, pool, T, work, ring[1]);
+        out = sd_mul(0.5, sd_add(a, b));
+    } else if (kind == MPT_SUBDIV_VERT_BND) {
+        const SdVec v = sd_pos(o, level, pool, T, work, i);
+        const SdVec p = sd_pos(o, level, pool, T, work, ring[0]), q = sd_pos(o, level, pool, T, work, ring[n - 1]);
+        out = sd_add(sd_mul(0.75, v), sd_mul(0.125, sd_add(p, q)));
+    } else {
+        const SdVec v = sd_pos(o, level, pool, T, work, i);
+        SdVec s = sd_pos(o, level, pool, T, work, ring[0]);
+        for (int k = 1; k < n; k++) s = sd_add(s, sd_pos(o, level, pool, T, work, ring[k]));
+        const double beta = n == 3 ? 0.1875 : 3.0 / (8.0 * (double)n), w = 1.0 - (double)n * beta;
+        out = sd_add(sd_mul(w, v), sd_mul(beta, s));
+    }
+    double *dst = work + o.work_at + o.pos_at[level] + (size_t)i * 3;
+    dst[0] = out.x; dst[1] = out.y; dst[2] = out.z;
+}
+
+__global__ __launch_bounds__(SD_BLOCK) void subdiv_normal_kernel(const MptSubdivJob *__restrict__ jobs, const MptSubdivRun *__restrict__ runs,
+                                                                 int nruns, const int32_t *__restrict__ topo, const double *work_in, double *work_out) {
+    const int r = sd_run(runs, nruns);
+    const MptSubdivJob &o = jobs[runs[r].job];          // (fields read through the scalar cache: a copy indexed by the level would live in scratch)
+    const int i = ((int)blockIdx.x - runs[r].block) * SD_BLOCK + (int)threadIdx.x;
+    if (i >= o.nv[o.levels]) return;
+    const int32_t *__restrict__ T = topo + o.topo_at;
+    const int32_t head = T[o.nrule_at + 2 * i], at = T[o.nrule_at + 2 * i + 1];
+    const int kind = head & 3, n = head >> 2;
+    const int32_t *__restrict__ ring = T + at;
+    const double *P = work_in + o.work_at + o.pos_at[o.levels];
+    const SdVec v = { P[(size_t)i * 3], P[(size_t)i * 3 + 1], P[(size_t)i * 3 + 2] };
+    const int nfaces = kind == MPT_SUBDIV_VERT_BND ? n - 1 : n;
+    SdVec N = { 0.0, 0.0, 0.0 };
+    const int32_t r0 = ring[0];
+    const SdVec A0 = sd_sub({ P[(size_t)r0 * 3], P[(size_t)r0 * 3 + 1], P[(size_t)r0 * 3 + 2] }, v);
+    SdVec A = A0;
+    for (int k = 0; k < nfaces; k++) {
+        SdVec B = A0;
+        if (k + 1 < n) {
+            const int32_t rb = ring[k + 1];
+            B = sd_sub({ P[(size_t)rb * 3], P[(size_t)rb * 3 + 1], P[(size_t)rb * 3 + 2] }, v);
+        }
+        const SdVec X = { A.y * B.z - A.z * B.y, A.z * B.x - A.x * B.z, A.x * B.y - A.y * B.x };
+        N = sd_add(N, X);
+        A = B;
+    }
+    const double len = sqrt((N.x * N.x + N.y * N.y) + N.z * N.z);
+    float4 *dst = (float4 *)(work_out + o.work_at + o.vrec_at) + (size_t)i * 2;
+    dst[0] = make_float4((float)v.x, (float)v.y, (float)v.z, (float)(N.x / len));
+    dst[1] = make_float4((float)(N.y / len), (float)(N.z / len), 0.0f, 0.0f);
+}
+
+__global__ __launch_bounds__(SD_BLOCK) void subdiv_emit_kernel(const float4 *pool_in, float4 *pool_out, const MptSubdivJob *__restrict__ jobs,
+                                                               const MptSubdivRun *__restrict__ runs, int nruns, const int32_t *__restrict__ topo,
+                                                               const double *__restrict__ work) {
+    const int r = sd_run(runs, nruns);
+    const MptSubdivJob &o = jobs[runs[r].job];          // (fields read through the scalar cache: a copy indexed by the level would live in scratch)
+    const int g = ((int)blockIdx.x - runs[r].block) * SD_BLOCK + (int)threadIdx.x;
+    if (g >= o.nfaces) return;
+    const int32_t *__restrict__ F = topo + o.topo_at + o.face_at + (size_t)g * 3;
+    const float4 *__restrict__ vrec = (const float4 *)(work + o.work_at + o.vrec_at);
+    const int32_t i0 = F[0], i1 = F[1], i2 = F[2];
+    const float4 a0 = vrec[(size_t)i0 * 2], a1 = vrec[(size_t)i0 * 2 + 1];
+    const float4 b0 = vrec[(size_t)i1 * 2], b1 = vrec[(size_t)i1 * 2 + 1];
+    const float4 c0 = vrec[(size_t)i2 * 2], c1 = vrec[(size_t)i2 * 2 + 1];
+    // the uvs: from the cage face g >> 2L down the digits of g in base 4, the most significant first
+    const size_t parent = ((size_t)o.src_vert + (size_t)(g >> (2 * o.levels)) * 3) * 2;
+    const float4 p0 = pool_in[parent + 1], p1 = pool_in[parent + 3], p2 = pool_in[parent + 5];
+    double u0 = p0.z, v0 = p0.w, u1 = p1.z, v1 = p1.w, u2 = p2.z, v2 = p2.w;
+    for (int s = o.levels - 1; s >= 0; s--) {
+        const int d = (g >> (2 * s)) & 3;
+        const double m01u = 0.5 * (u0 + u1), m01v = 0.5 * (v0 + v1), m12u = 0.5 * (u1 + u2), m12v = 0.5 * (v1 + v2);
+        const double m20u = 0.5 * (u2 + u0), m20v = 0.5 * (v2 + v0);
+        const double n0u = d == 0 ? u0 : d == 1 ? u1 : d == 2 ? u2 : m01u, n0v = d == 0 ? v0 : d == 1 ? v1 : d == 2 ? v2 : m01v;
+        const double n1u = d == 0 ? m01u : d == 1 ? m12u : d == 2 ? m20u : m12u, n1v = d == 0 ? m01v : d == 1 ? m12v : d == 2 ? m20v : m12v;
+        const double n2u = d == 0 ? m20u : d == 1 ? m01u : d == 2 ? m12u : m20u, n2v = d == 0 ? m20v : d == 1 ? m01v : d == 2 ? m12v : m20v;
+        u0 = n0u; v0 = n0v; u1 = n1u; v1 = n1v; u2 = n2u; v2 = n2v;
+    }
+    float4 *dst = pool_out + ((size_t)o.dst_vert + (size_t)g * 3) * 2;
+    dst[0] = a0; dst[1] = make_float4(a1.x, a1.y, (float)u0, (float)v0);
+    dst[2] = b0; dst[3] = make_float4(b1.x, b1.y, (float)u1, (float)v1);
+    dst[4] = c0; dst[5] = make_float4(c1.x, c1.y, (float)u2, (float)v2);
+}
+
+// ---------------------------------------------------------------- launchers
+// runs[nruns] and blocks: mpt_subdiv_plan's table over the jobs' items of this launch and the sum of its blocks.  The pool is read
+// at the jobs' src_vert and written at their dst_vert, the workspace read at one level and written at the next: ranges that never
+// overlap
+MPT_KERNEL_API hipError_t mpt_launch_subdiv_refine(const float *pool, const MptSubdivJob *jobs, const MptSubdivRun *runs, int nruns, int blocks,
+                                                   int level, const int32_t *topo, double *work, hipStream_t stream) {
+    if (nruns < 1 || blocks < 1 || level < 1 || level > MPT_SUBDIV_MAX_LEVELS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(subdiv_refine_kernel, dim3((unsigned)blocks), dim3(SD_BLOCK), 0, stream, (const float4 *)pool, jobs, runs, nruns, level, topo, work);
+    return hipGetLastError();
+}
+
+MPT_KERNEL_API hipError_t mpt_launch_subdiv_normals(const MptSubdivJob *jobs, const MptSubdivRun *runs, int nruns, int blocks, const int32_t *topo,
+                                                    double *work, hipStream_t stream) {
+    if (nruns < 1 || blocks < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(subdiv_normal_kernel, dim3((unsigned)blocks), dim3(SD_BLOCK), 0, stream, jobs, runs, nruns, topo, (const double *)work, work);
+    return hipGetLastError();
+}
+
+MPT_KERNEL_API hipError_t mpt_launch_subdiv_emit(float *pool, const MptSubdivJob *jobs, const MptSubdivRun *runs, int nruns, int blocks,
+                                                 const int32_t *topo, const double *work, hipStream_t stream) {
+    if (nruns < 1 || blocks < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(subdiv_emit_kernel, dim3((unsigned)blocks), dim3(SD_BLOCK), 0, stream, (const float4 *)pool, (float4 *)pool, jobs, runs, nruns, topo,
+                       work);
+    return hipGetLastError();
+}

@@ -3,14 +3,15 @@ triangle mesh model storage (reference model.py).  The mesh is kept on the host 
 BVHTree().build() packs it, leaf-ordered, into the device records (csrc/mpt_types.h) -- or, through
 load_meshes / add_mesh / add_object / compose, object-space meshes and an object table are kept on the device
 and composed there into the model the build reads (csrc/compose.hip); a mesh may carry morph
-targets and a skin, and its objects a pose each, deformed there too (csrc/deform.hip).
+targets and a skin, and its objects a pose each, deformed there too (csrc/deform.hip), and a Loop
+subdivision level, evaluated there behind the deformation (csrc/subdiv.hip).
 '''
 
 import ctypes as C
 
 from .common import *                 # noqa: F401,F403
 from .common import Singleton, register, ctx, np
-from ._lib import fptr, iptr, ComposeInfo, DeformInfo, DEFORM_MAX_JOINTS, DEFORM_MAX_TARGETS
+from ._lib import fptr, iptr, ComposeInfo, DeformInfo, SubdivInfo, DEFORM_MAX_JOINTS, DEFORM_MAX_TARGETS, SUBDIV_MAX_LEVELS
 
 
 @register
@@ -22,6 +23,7 @@ class ModelPool(metaclass=Singleton):
         self._mtlids = np.zeros(0, np.int32)
         self._composed = False           # the model is the device's composition: to_numpy fetches it
         self._mesh_faces = []            # faces of every mesh of the device's pool
+        self._mesh_levels = {}           # mesh -> its subdivision level, where it has one: an object of it has faces * 4^level
         self._obj_mesh = []              # the mesh of every object of the device's table
 
     @property
@@ -85,7 +87,7 @@ class ModelPool(metaclass=Singleton):
         if not 0 <= int(mesh) < len(self._mesh_faces):
             raise ValueError('unknown mesh %r (%d meshes)' % (mesh, len(self._mesh_faces)))
         w = self._world(world)
-        total = sum(self._mesh_faces[m] for m in self._obj_mesh) + self._mesh_faces[int(mesh)]
+        total = sum(self._object_faces(m) for m in self._obj_mesh) + self._object_faces(int(mesh))
         if total >= self.size:
             raise ValueError('too many faces: %d with this object, room for fewer than %d' % (total, self.size))
         obj = C.c_int(-1)
@@ -111,14 +113,14 @@ class ModelPool(metaclass=Singleton):
     def clear_meshes(self):
         '''drop the objects and the meshes'''
         ctx().call('mpt_scene_clear', 1)
-        self._obj_mesh, self._mesh_faces = [], []
+        self._obj_mesh, self._mesh_faces, self._mesh_levels = [], [], {}
 
     def compose(self):
         '''write the objects, in order, as the model BVHTree().build() reads -- on the device; what load(*compose_multiple_meshes(...))
         leaves, without the arrays crossing to the host and back.  After set_world / set_material only the changed objects' faces
         are rewritten'''
         ctx().call('mpt_compose')
-        self._nfaces = sum(self._mesh_faces[m] for m in self._obj_mesh)
+        self._nfaces = sum(self._object_faces(m) for m in self._obj_mesh)
         self._composed = True
 
     # ---- deformation on the device: glTF 2.0's morph targets and linear-blend skinning (csrc/deform.hip, DESIGN.md section 3.17;
@@ -196,6 +198,43 @@ class ModelPool(metaclass=Singleton):
         '''_lib.DeformInfo: deformable objects, objects and corners the last compose() deformed, pool vertices the copies hold'''
         info = DeformInfo()
         ctx().call('mpt_deform_stats', C.byref(info))
+        return info
+
+    # ---- Loop subdivision on the device, behind the deformation (csrc/subdiv.hip, DESIGN.md section 3.19; the reference's add-on
+    #      is handed Blender's evaluated mesh instead)
+    def _object_faces(self, mesh):
+        return self._mesh_faces[mesh] << (2 * self._mesh_levels.get(mesh, 0))
+
+    def add_subdivision(self, mesh, levels):
+        '''`levels` (1 to 5) levels of Loop subdivision for a mesh that has no object yet, before or after its targets and skin: an
+        object of it then has 4^levels times the faces, smooth normals and the mesh's texcoords carried down face by face; face g of
+        such an object descends from face g >> 2 * levels of the mesh.  Corners with equal positions are one control vertex; the
+        mesh must be a manifold with consistent winding (open boundaries are fine), else the library says which face or vertex is
+        not'''
+        mesh, levels = self._fresh_mesh(mesh), int(levels)
+        if not 1 <= levels <= SUBDIV_MAX_LEVELS:
+            raise ValueError('%d levels: between 1 and %d' % (levels, SUBDIV_MAX_LEVELS))
+        if mesh in self._mesh_levels:
+            raise ValueError('mesh %d already has a subdivision level' % mesh)
+        if self._mesh_faces[mesh] << (2 * levels) >= self.size:
+            raise ValueError('too many faces: %d at level %d, room for fewer than %d' % (self._mesh_faces[mesh] << (2 * levels), levels, self.size))
+        ctx().call('mpt_mesh_set_subdivision', mesh, levels)
+        self._mesh_levels[mesh] = levels
+
+    def subdivided_to_numpy(self, obj):
+        '''the subdivided copy of an object of a subdivided mesh as the last compose() wrote it: [3 k 4^levels, 8] f32 records in
+        object space'''
+        obj = self._object(obj)
+        k = self._object_faces(self._obj_mesh[obj])
+        arr = np.empty((k * 3, 8), np.float32)
+        ctx().call('mpt_get_subdivided', obj, fptr(arr), k)
+        return arr
+
+    def subdiv_stats(self):
+        '''_lib.SubdivInfo: objects of subdivided meshes, copies, copies and faces the last compose() refined, pool vertices the
+        copies hold'''
+        info = SubdivInfo()
+        ctx().call('mpt_subdiv_stats', C.byref(info))
         return info
 
     def compose_stats(self):

@@ -28,6 +28,7 @@ _PASS_THROUGH = {
     'set_object_world': ('ModelPool', 'set_world', ('obj', 'world')),
     'set_object_morph_weights': ('ModelPool', 'set_morph_weights', ('obj', 'w')),
     'set_object_joints': ('ModelPool', 'set_joints', ('obj', 'mats')),
+    'set_mesh_subdivision': ('ModelPool', 'add_subdivision', ('mesh', 'levels')),
     'load_images': ('ImagePool', 'load', ('images',)),
     'load_materials': ('MaterialPool', 'load', ('materials',)),
     'build_tree': ('BVHTree', 'build', ()),

@@ -1,0 +1,227 @@
+// subdiv_rule_check.cpp -- the pure host pieces of Loop subdivision (ptina_amd/csrc/subdiv_rule.h: the topology of a mesh and its
+// refinements, and the run table of a launch) exercised by a stand-alone program, so that they can run under the host sanitizers
+// without a GPU and without loading anything into an interpreter:
+//
+//     c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/subdiv_rule_check.cpp -o subdiv_rule_check && ./subdiv_rule_check
+//
+// Every fixture topology of tests/subdiv_ref.py (built here procedurally: triangle, pair, tetrahedron, octahedron, icosahedron,
+// closed fans of valence 7 and 12, the open 5 x 5 grid, the open cylinder) at levels 1 to 4, from record arrays that are exactly as
+// long as the function may read: counts (Euler's number on the closed ones, four faces per face), every id of every table inside
+// its level, every ring inside the block; every refusal, with message buffers of every size (cut, terminated, never overrun); the
+// plan over layouts with jobs that sit out, with output tables of every capacity from none to ample (never written past `cap`).
+
+#include "../ptina_amd/csrc/subdiv_rule.h"
+#include <cstdlib>
+#include <limits>
+#include <string>
+
+static int failures = 0;
+#define CHECK(x) do { if (!(x)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #x); failures++; } } while (0)
+
+static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
+static unsigned rnd(unsigned n) {
+    rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
+    return (unsigned)(rng_state >> 33) % n;
+}
+
+struct Mesh { std::string name; std::vector<float> v; std::vector<int> f; bool closed; };
+
+// records [3k][8] on the heap, exactly 24 k floats
+static std::vector<float> records(const Mesh &m) {
+    std::vector<float> rec(m.f.size() * 8, 0.0f);
+    for (size_t s = 0; s < m.f.size(); s++) {
+        for (int a = 0; a < 3; a++) rec[s * 8 + a] = m.v[(size_t)m.f[s] * 3 + a];
+        rec[s * 8 + 5] = 1.0f;
+    }
+    return rec;
+}
+
+static Mesh bipyramid(int n) {
+    Mesh m{ "fan" + std::to_string(n), { 0, 0, 1.0f, 0, 0, -0.8f }, {}, true };
+    for (int i = 0; i < n; i++) { const double a = 6.283185307179586 * i / n; m.v.insert(m.v.end(), { (float)std::cos(a), (float)std::sin(a), 0.1f * (float)std::cos(3 * a) }); }
+    for (int i = 0; i < n; i++) { const int a = 2 + i, b = 2 + (i + 1) % n; m.f.insert(m.f.end(), { 0, a, b, 1, b, a }); }
+    return m;
+}
+
+static Mesh grid(int nx, int ny) {
+    Mesh m{ "grid", {}, {}, false };
+    for (int y = 0; y <= ny; y++) for (int x = 0; x <= nx; x++) m.v.insert(m.v.end(), { x - nx / 2.0f, y - ny / 2.0f, 0.15f * (float)std::sin(1.3 * x + 0.7 * y) });
+    for (int y = 0; y < ny; y++)
+        for (int x = 0; x < nx; x++) {
+            const int a = y * (nx + 1) + x, b = a + 1, c = a + nx + 2, d = a + nx + 1;
+            m.f.insert(m.f.end(), { a, b, c, a, c, d });
+        }
+    return m;
+}
+
+static Mesh cylinder(int n, int rings) {
+    Mesh m{ "cylinder", {}, {}, false };
+    for (int r = 0; r < rings; r++) for (int i = 0; i < n; i++) { const double a = 6.283185307179586 * i / n; m.v.insert(m.v.end(), { (float)std::cos(a), (float)std::sin(a), 0.7f * r }); }
+    for (int r = 0; r + 1 < rings; r++)
+        for (int i = 0; i < n; i++) {
+            const int a = r * n + i, b = r * n + (i + 1) % n;
+            m.f.insert(m.f.end(), { a, b, b + n, a, b + n, a + n });
+        }
+    return m;
+}
+
+static std::vector<Mesh> fixtures() {
+    const float t = 1.618034f;
+    std::vector<Mesh> out;
+    out.push_back({ "triangle", { 0, 0, 0, 1, 0, 0.25f, 0.25f, 1, 0 }, { 0, 1, 2 }, false });
+    out.push_back({ "pair", { 0, 0, 0, 1, 0, 0.25f, 1, 1, 0, -0.0f, 1, 0.5f }, { 0, 1, 2, 0, 2, 3 }, false });
+    out.push_back({ "tetrahedron", { 1, 1, 1, 1, -1, -1, -1, 1, -1, -1, -1, 1 }, { 0, 1, 2, 0, 3, 1, 0, 2, 3, 1, 3, 2 }, true });
+    {
+        Mesh m{ "octahedron", { 1, 0, 0, -1, 0, 0, 0, 1, 0, 0, -1, 0, 0, 0, 1, 0, 0, -1 }, {}, true };
+        for (int sx = 0; sx < 2; sx++) for (int sy = 0; sy < 2; sy++) for (int sz = 0; sz < 2; sz++) {
+            const int x = sx, y = 2 + sy, z = 4 + sz;
+            if ((sx + sy + sz) % 2 == 0) m.f.insert(m.f.end(), { x, y, z }); else m.f.insert(m.f.end(), { x, z, y });
+        }
+        out.push_back(m);
+    }
+    out.push_back({ "icosahedron", { -1, t, 0, 1, t, 0, -1, -t, 0, 1, -t, 0, 0, -1, t, 0, 1, t, 0, -1, -t, 0, 1, -t, t, 0, -1, t, 0, 1, -t, 0, -1, -t, 0, 1 },
+                    { 0, 11, 5, 0, 5, 1, 0, 1, 7, 0, 7, 10, 0, 10, 11, 1, 5, 9, 5, 11, 4, 11, 10, 2, 10, 7, 6, 7, 1, 8,
+                      3, 9, 4, 3, 4, 2, 3, 2, 6, 3, 6, 8, 3, 8, 9, 4, 9, 5, 2, 4, 11, 6, 2, 10, 8, 6, 7, 9, 8, 1 }, true });
+    out.push_back(bipyramid(7));
+    out.push_back(bipyramid(12));
+    out.push_back(grid(5, 5));
+    out.push_back(cylinder(8, 3));
+    return out;
+}
+
+// rules [n] at word `at` of the block: every ring inside the block, every id below `ids`, the kinds those of `edges` or of vertices
+static void check_rules(const MptSubdivTopo &t, int32_t at, int64_t n, int64_t nverts, int64_t ids, bool closed) {
+    const int64_t W = (int64_t)t.words.size();
+    CHECK(at >= 0 && at + 2 * n <= W);
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t head = t.words[(size_t)(at + 2 * i)], ring = t.words[(size_t)(at + 2 * i + 1)];
+        const int kind = head & 3, len = head >> 2;
+        CHECK(ring >= 0 && (int64_t)ring + len <= W);
+        CHECK(i < nverts ? kind == MPT_SUBDIV_VERT_INT || kind == MPT_SUBDIV_VERT_BND : kind == MPT_SUBDIV_EDGE_INT || kind == MPT_SUBDIV_EDGE_BND);
+        if (closed) CHECK(kind == MPT_SUBDIV_VERT_INT || kind == MPT_SUBDIV_EDGE_INT);
+        CHECK(kind == MPT_SUBDIV_EDGE_INT ? len == 4 : kind == MPT_SUBDIV_EDGE_BND ? len == 2 : len >= 2);
+        for (int k = 0; k < len && (int64_t)ring + len <= W; k++) CHECK(t.words[(size_t)ring + (size_t)k] >= 0 && t.words[(size_t)ring + (size_t)k] < ids);
+    }
+}
+
+static MptSubdivVerdict refusal(const std::vector<float> &rec, int levels, const char *words) {
+    MptSubdivTopo t;
+    const int k = (int)(rec.size() / 24);
+    const MptSubdivVerdict want = mpt_subdiv_topology_of(rec.data(), k, levels, t, nullptr, 0);
+    CHECK(mpt_subdiv_topology_of(rec.data(), k, levels, t, nullptr, 64) == want);
+    for (size_t cap = 0; cap <= 240; cap += cap < 8 ? 1 : 29) {
+        std::vector<char> why(cap, 'x');
+        CHECK(mpt_subdiv_topology_of(rec.data(), k, levels, t, cap ? why.data() : nullptr, cap) == want);
+        if (!cap) continue;
+        CHECK(std::memchr(why.data(), 0, cap) != nullptr);
+        if (want == MPT_SUBDIV_OK) CHECK(why[0] == 0);
+        else if (cap >= 200) CHECK(!std::strncmp(why.data(), "subdivision: ", 13) && std::strstr(why.data(), words) != nullptr);
+    }
+    return want;
+}
+
+static std::vector<float> soup(std::initializer_list<int> pts) {       // triangles over the points A..F below, a corner per entry
+    static const float P[6][3] = { { 0, 0, 0 }, { 1, 0, 0 }, { 0, 1, 0 }, { 0, 0, 1 }, { 1, 1, 1 }, { 2, 0, 1 } };
+    std::vector<float> rec(pts.size() * 8, 0.0f);
+    size_t s = 0;
+    for (int p : pts) { for (int a = 0; a < 3; a++) rec[s * 8 + a] = P[p][a]; s++; }
+    return rec;
+}
+
+int main() {
+    int topologies = 0;
+    for (const Mesh &m : fixtures()) {
+        const std::vector<float> rec = records(m);
+        const int k = (int)(m.f.size() / 3);
+        for (int levels = 1; levels <= 4; levels++) {
+            MptSubdivTopo t;
+            char why[64];
+            const MptSubdivVerdict v = mpt_subdiv_topology_of(rec.data(), k, levels, t, why, sizeof why);
+            CHECK(v == MPT_SUBDIV_OK && why[0] == 0);
+            if (v != MPT_SUBDIV_OK) { std::fprintf(stderr, "%s at level %d: %s\n", m.name.c_str(), levels, why); continue; }
+            topologies++;
+            CHECK(t.levels == levels && t.nv[0] == (int64_t)(m.v.size() / 3));
+            for (int64_t c = 0; c < t.nv[0]; c++) CHECK(t.words[(size_t)c] >= 0 && t.words[(size_t)c] < 3 * k);
+            for (int l = 0; l <= levels; l++) {
+                CHECK(t.nf[l] == ((int64_t)k << (2 * l)));
+                if (m.closed) CHECK(t.nv[l] - t.ne[l] + t.nf[l] == 2);
+                if (l > 0) { CHECK(t.nv[l] == t.nv[l - 1] + t.ne[l - 1]); check_rules(t, t.rule_at[l], t.nv[l], t.nv[l - 1], t.nv[l - 1], m.closed); }
+            }
+            check_rules(t, t.nrule_at, t.nv[levels], t.nv[levels], t.nv[levels], m.closed);
+            CHECK((int64_t)t.face_at + 3 * t.nf[levels] == (int64_t)t.words.size());
+            for (int64_t s = 0; s < 3 * t.nf[levels]; s++) CHECK(t.words[(size_t)t.face_at + (size_t)s] >= 0 && t.words[(size_t)t.face_at + (size_t)s] < t.nv[levels]);
+        }
+    }
+    {   // k = 0 is a mesh and stays one
+        MptSubdivTopo t;
+        CHECK(mpt_subdiv_topology_of(nullptr, 0, 3, t, nullptr, 0) == MPT_SUBDIV_OK && t.words.empty() && t.nf[3] == 0);
+    }
+
+    int refusals = 0;
+    const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
+    {
+        std::vector<float> rec = soup({ 0, 1, 2, 0, 2, 4 });
+        CHECK(refusal(rec, 2, "") == MPT_SUBDIV_OK);
+        for (float bad : { inf, -inf, nan })
+            for (size_t where : { (size_t)0, rec.size() - 8 + 2 }) {             // the first and the last position read
+                std::vector<float> r = rec;
+                r[where] = bad;
+                CHECK(refusal(r, 2, "is not finite") == MPT_SUBDIV_NOT_FINITE); refusals++;
+            }
+        rec[rec.size() - 1] = nan; rec[3] = inf;                                 // normals and texcoords are not read
+        CHECK(refusal(rec, 2, "") == MPT_SUBDIV_OK);
+    }
+    CHECK(refusal(soup({ 0, 1, 2, 0, 3, 0 }), 2, "face 1 has two corners on one vertex") == MPT_SUBDIV_DEGENERATE); refusals++;
+    CHECK(refusal(soup({ 0, 1, 2, 1, 0, 3, 0, 1, 4 }), 2, "face 2 is the third on the edge") == MPT_SUBDIV_EDGE_FACES); refusals++;
+    CHECK(refusal(soup({ 0, 1, 2, 0, 1, 3 }), 2, "same direction") == MPT_SUBDIV_EDGE_DIRECTION); refusals++;
+    CHECK(refusal(soup({ 0, 1, 2, 0, 3, 4 }), 2, "of vertex 0 are not one fan") == MPT_SUBDIV_FAN); refusals++;
+    CHECK(refusal(soup({ 0, 1, 2, 0, 2, 1, 0, 3, 4, 0, 4, 3 }), 1, "not one fan") == MPT_SUBDIV_FAN); refusals++;   // two closed fans on one vertex
+    CHECK(refusal(soup({ 0, 1, 2 }), 0, "levels 0 outside [1, 5]") == MPT_SUBDIV_LEVELS); refusals++;
+    CHECK(refusal(soup({ 0, 1, 2 }), 6, "levels 6 outside") == MPT_SUBDIV_LEVELS); refusals++;
+    {
+        MptSubdivTopo t;
+        CHECK(mpt_subdiv_topology_of(nullptr, 1, 1, t, nullptr, 0) == MPT_SUBDIV_ARGS);
+        CHECK(mpt_subdiv_topology_of(nullptr, -1, 1, t, nullptr, 0) == MPT_SUBDIV_ARGS);
+        const float one[24] = {};
+        CHECK(mpt_subdiv_topology_of(one, 20000, 5, t, nullptr, 0) == MPT_SUBDIV_TOO_MANY);      // refused before anything is read
+    }
+
+    const int C = MPT_SUBDIV_CHUNK;
+    const int sizes[] = { 0, 1, 63, C - 1, C, C + 1, 2 * C, 9600, 5 * C + 21 };
+    int plans = 0;
+    for (int round = 0; round < 400; round++) {
+        const int n = (int)rnd(9);
+        std::vector<int32_t> items((size_t)n), dirty((size_t)n);
+        for (int o = 0; o < n; o++) { items[o] = sizes[rnd(sizeof sizes / sizeof *sizes)]; dirty[o] = (int32_t)rnd(2); }
+        const bool flags = rnd(3) != 0;
+        std::vector<int32_t> want_job; std::vector<int64_t> want_block;
+        int64_t at = 0;
+        for (int o = 0; o < n; o++) {
+            if (items[o] == 0 || (flags && !dirty[o])) continue;
+            want_job.push_back(o); want_block.push_back(at);
+            at += (items[o] + C - 1) / C;
+        }
+        for (int cap = 0; cap <= n + 1; cap++) {
+            std::vector<int32_t> run_job((size_t)cap, -7); std::vector<int64_t> run_block((size_t)cap, -7);
+            int64_t blocks = -1;
+            const int nr = mpt_subdiv_plan_of(n ? items.data() : nullptr, flags ? dirty.data() : nullptr, n, cap ? run_job.data() : nullptr,
+                                              cap ? run_block.data() : nullptr, cap, &blocks);
+            plans++;
+            CHECK(nr == (int)want_job.size() && blocks == at);
+            for (int r = 0; r < cap; r++) {
+                if (r < nr) CHECK(run_job[r] == want_job[r] && run_block[r] == want_block[r]);
+                else CHECK(run_job[r] == -7 && run_block[r] == -7);
+            }
+        }
+    }
+    {
+        const int32_t neg[2] = { 5, -1 };
+        CHECK(mpt_subdiv_plan_of(neg, nullptr, 2, nullptr, nullptr, 0, nullptr) == -1);
+        CHECK(mpt_subdiv_plan_of(nullptr, nullptr, 1, nullptr, nullptr, 0, nullptr) == -1);
+        CHECK(mpt_subdiv_plan_of(nullptr, nullptr, -1, nullptr, nullptr, 0, nullptr) == -1);
+        std::vector<int32_t> huge(300, 2147483647);                       // 300 x 2^23 blocks: past 31 bits
+        CHECK(mpt_subdiv_plan_of(huge.data(), nullptr, (int)huge.size(), nullptr, nullptr, 0, nullptr) == -1);
+    }
+    std::printf("subdiv_rule_check: %d topologies, %d refusals, %d plans, %d failures\n", topologies, refusals, plans, failures);
+    return failures ? EXIT_FAILURE : EXIT_SUCCESS;
+}
