@@ -424,20 +424,25 @@ def compose_plan(faces, dirty=None):
 DEFORM_CHUNK, DEFORM_MAX_JOINTS, DEFORM_MAX_TARGETS = 1024, 256, 64      # csrc/mpt_types.h MPT_DEFORM_*
 
 
+def _run_plan(symbol, counts, dirty, rows, what):
+    '''the run table of a launch (csrc/run_table.h) through the door `symbol`; `rows` and `what` name the table's rows in the refusals'''
+    k = np.ascontiguousarray(counts, np.int32).reshape(-1)
+    d = None if dirty is None else np.ascontiguousarray(dirty, np.int32).reshape(-1)
+    if d is not None and d.shape != k.shape:
+        raise ValueError('%d dirty flags for %d %s' % (d.size, k.size, rows))
+    n = int(k.size)
+    item, block, blocks = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int64), C.c_int64(0)
+    nr = getattr(load_library(), symbol)(iptr(k), None if d is None else iptr(d), n, iptr(item), block.ctypes.data_as(C.POINTER(C.c_int64)), n,
+                                         C.byref(blocks))
+    if nr < 0:
+        raise ValueError('%s counts name no launch (negative, or more than 2^31 - 1 blocks)' % what)
+    return [(int(item[r]), int(block[r])) for r in range(nr)], int(blocks.value)
+
+
 def deform_plan(corners, dirty=None):
     '''mpt_deform_plan (no context, no GPU): per-object corner counts and dirty flags (None: all) -> ([(object, first block), ...] of
     the launch, its blocks); ValueError for counts that name no launch'''
-    k = np.ascontiguousarray(corners, np.int32).reshape(-1)
-    d = None if dirty is None else np.ascontiguousarray(dirty, np.int32).reshape(-1)
-    if d is not None and d.shape != k.shape:
-        raise ValueError('%d dirty flags for %d objects' % (d.size, k.size))
-    n = int(k.size)
-    obj, block, blocks = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int64), C.c_int64(0)
-    nr = load_library().mpt_deform_plan(iptr(k), None if d is None else iptr(d), n, iptr(obj), block.ctypes.data_as(C.POINTER(C.c_int64)), n,
-                                        C.byref(blocks))
-    if nr < 0:
-        raise ValueError('corner counts name no launch (negative, or more than 2^31 - 1 blocks)')
-    return [(int(obj[r]), int(block[r])) for r in range(nr)], int(blocks.value)
+    return _run_plan('mpt_deform_plan', corners, dirty, 'objects', 'corner')
 
 
 def skin_check(joints, weights, njoints):
@@ -457,17 +462,7 @@ SUBDIV_CHUNK, SUBDIV_MAX_LEVELS = 256, 5                                # csrc/m
 def subdiv_plan(items, dirty=None):
     '''mpt_subdiv_plan (no context, no GPU): per-job item counts of one launch and dirty flags (None: all) -> ([(job, first block),
     ...], its blocks); ValueError for counts that name no launch'''
-    k = np.ascontiguousarray(items, np.int32).reshape(-1)
-    d = None if dirty is None else np.ascontiguousarray(dirty, np.int32).reshape(-1)
-    if d is not None and d.shape != k.shape:
-        raise ValueError('%d dirty flags for %d jobs' % (d.size, k.size))
-    n = int(k.size)
-    job, block, blocks = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int64), C.c_int64(0)
-    nr = load_library().mpt_subdiv_plan(iptr(k), None if d is None else iptr(d), n, iptr(job), block.ctypes.data_as(C.POINTER(C.c_int64)), n,
-                                        C.byref(blocks))
-    if nr < 0:
-        raise ValueError('item counts name no launch (negative, or more than 2^31 - 1 blocks)')
-    return [(int(job[r]), int(block[r])) for r in range(nr)], int(blocks.value)
+    return _run_plan('mpt_subdiv_plan', items, dirty, 'jobs', 'item')
 
 
 def subdiv_topology(rec, levels):

@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "mpt_types.h"
+#include "run_table.h"
 
 enum { CP_BLOCK = 256, CP_WAVE = 64, CP_WAVES = CP_BLOCK / CP_WAVE, CP_FOLD = 1024, CP_FOLD_WAVES = CP_FOLD / CP_WAVE };
 
@@ -64,14 +65,13 @@ __device__ static inline float4 compose_vertex(const float4 *__restrict__ pool, 
 
 __global__ __launch_bounds__(CP_BLOCK) void compose_kernel(const float4 *__restrict__ pool, const MptComposeObj *__restrict__ objs,
                                                            const int *__restrict__ first, int nobj, int nverts,
-                                                           const MptComposeRun *__restrict__ runs, int nruns, int all, unsigned epoch,
+                                                           const MptRun *__restrict__ runs, int nruns, int all, unsigned epoch,
                                                            float4 *__restrict__ out, int *__restrict__ mtlids, float *__restrict__ part) {
     __shared__ float s_part[CP_WAVES][6];
     int wg = (int)blockIdx.x;
-    if (!all) {                                                               // the run this block belongs to (uniform)
-        int a = 0, b = nruns - 1;
-        while (a < b) { const int m = (a + b + 1) >> 1; if (runs[m].block <= (int)blockIdx.x) a = m; else b = m - 1; }
-        wg = runs[a].wg + ((int)blockIdx.x - runs[a].block);
+    if (!all) {
+        const int r = mpt_run_of(runs, nruns);
+        wg = runs[r].item + ((int)blockIdx.x - runs[r].block);
     }
     const int v = wg * CP_BLOCK + (int)threadIdx.x;
     float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
@@ -112,7 +112,7 @@ MPT_KERNEL_API size_t mpt_compose_groups(size_t nverts) { return (nverts + CP_BL
 // holds their first output workgroup and first block); part: 6 floats per output workgroup; bounds_host: the device alias of the
 // host's mapped {min3, max3}
 MPT_KERNEL_API hipError_t mpt_launch_compose(const float *pool, const MptComposeObj *objs, const int *first, int nobj, int nverts,
-                                             const MptComposeRun *runs, int nruns, int blocks, int all, unsigned epoch, float *out,
+                                             const MptRun *runs, int nruns, int blocks, int all, unsigned epoch, float *out,
                                              int *mtlids, float *part, float *bounds_host, hipStream_t stream) {
     if (nobj < 1 || nverts < 1 || (!all && blocks > 0 && nruns < 1)) return hipErrorInvalidValue;
     if (blocks > 0)

@@ -16,8 +16,8 @@
 // (-ffp-contract=off, the Makefile's rule for this file), rounded to f32 once, at the store.
 //
 // deform_kernel: ONE launch per mpt_compose covers every object whose pose changed.  A workgroup of 256 lanes takes one chunk of
-// MPT_DEFORM_CHUNK = 1024 corners of one object, four per lane; the run table maps blocks to (object, chunk) -- compose_kernel's
-// idiom -- and since every object's runs start at a block of its own, a workgroup lies in exactly one object.  It stages that
+// MPT_DEFORM_CHUNK = 1024 corners of one object, four per lane; the run table maps blocks to (object, chunk) -- run_table.h
+// -- and since every object's runs start at a block of its own, a workgroup lies in exactly one object.  It stages that
 // object's joint palette into LDS (96 bytes per joint: at 64 joints 6 bytes per corner, against 88 streamed): each lane gathers
 // four joints per corner, which from global memory would be several times the stream on the divergent-gather path.  The morph
 // weights are read through the scalar cache (their address depends on the block alone) and the skip of a zero weight is a uniform
@@ -28,19 +28,19 @@
 #include <stdint.h>
 #include <math.h>
 #include "mpt_types.h"
+#include "run_table.h"
 
 enum { DF_BLOCK = 256, DF_PER_LANE = MPT_DEFORM_CHUNK / DF_BLOCK };
 static_assert(DF_PER_LANE * DF_BLOCK == MPT_DEFORM_CHUNK, "a chunk is a whole number of corners per lane");
 
 __global__ __launch_bounds__(DF_BLOCK) void deform_kernel(const float4 *pool_in, float4 *pool_out, const MptDeformObj *__restrict__ objs,
-                                                          const MptDeformRun *__restrict__ runs, int nruns, const float *__restrict__ deltas,
+                                                          const MptRun *__restrict__ runs, int nruns, const float *__restrict__ deltas,
                                                           const uint16_t *__restrict__ joints, const float *__restrict__ weights,
                                                           const double *__restrict__ pose) {
     __shared__ double s_pal[MPT_DEFORM_MAX_JOINTS * 12];
-    int a = 0, b = nruns - 1;                                                 // the run this block belongs to (uniform)
-    while (a < b) { const int m = (a + b + 1) >> 1; if (runs[m].block <= (int)blockIdx.x) a = m; else b = m - 1; }
-    const MptDeformObj o = objs[runs[a].obj];
-    const int chunk = (int)blockIdx.x - runs[a].block;
+    const int r = mpt_run_of(runs, nruns);
+    const MptDeformObj o = objs[runs[r].item];
+    const int chunk = (int)blockIdx.x - runs[r].block;
     const double *__restrict__ w = pose + o.pose_at;                          // [ntargets], then the palette [njoints][12]
     for (int k = (int)threadIdx.x; k < o.njoints * 12; k += DF_BLOCK) s_pal[k] = w[o.ntargets + k];
     __syncthreads();
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(DF_BLOCK) void deform_kernel(const float4 *pool_in,
 // ---------------------------------------------------------------- launcher
 // pool: the mesh pool, read at the objects' src_vert and written at their dst_vert (ranges that never overlap); runs[nruns] and
 // blocks: mpt_deform_plan's table over objs and the sum of its blocks
-MPT_KERNEL_API hipError_t mpt_launch_deform(float *pool, const MptDeformObj *objs, const MptDeformRun *runs, int nruns, int blocks,
+MPT_KERNEL_API hipError_t mpt_launch_deform(float *pool, const MptDeformObj *objs, const MptRun *runs, int nruns, int blocks,
                                             const float *deltas, const uint16_t *joints, const float *weights, const double *pose,
                                             hipStream_t stream) {
     if (nruns < 1 || blocks < 1) return hipErrorInvalidValue;

@@ -1,6 +1,6 @@
-// deform_rule.h -- the two pure pieces of mesh deformation's host side (scene_deform.cpp): the run table of a deform launch and the
-// validation of a skin's arrays.  Plain C++17 with nothing of HIP and no context (as refit_rule.h), so that a stand-alone program
-// can run them under a sanitizer (tools/deform_rule_check.cpp); the C ABI has them as mpt_deform_plan and mpt_skin_check.
+// deform_rule.h -- the pure piece of mesh deformation's host side (scene_deform.cpp): the validation of a skin's arrays (the run
+// table of a deform launch is run_table.h's).  Plain C++17 with nothing of HIP and no context (as refit_rule.h), so that a
+// stand-alone program can run it under a sanitizer (tools/deform_rule_check.cpp); the C ABI has it as mpt_skin_check.
 #pragma once
 
 #include <cmath>
@@ -8,30 +8,6 @@
 #include <cstdint>
 #include <cstdio>
 #include "mpt_types.h"          // MPT_DEFORM_* (plain structures and constants)
-
-// The blocks of one deform launch: every object with corners whose flag is set (dirty null: all) takes ceil(corners / MPT_DEFORM_CHUNK)
-// consecutive blocks, in object order, so a block lies in exactly one object.  The first `cap` runs go to run_obj / run_block
-// (either may be null), the sum of the blocks to *blocks (may be null).  Returns the number of runs; -1 for arguments that name
-// no launch (a negative count, more than 2^31 - 1 blocks).
-inline int mpt_deform_plan_of(const int32_t *corners, const int32_t *dirty, int nobj, int32_t *run_obj, int64_t *run_block, int cap,
-                              int64_t *blocks) {
-    if (nobj < 0 || (nobj > 0 && !corners)) return -1;
-    int nr = 0;
-    long long at = 0;
-    for (int o = 0; o < nobj; o++) {
-        if (corners[o] < 0) return -1;
-        if (corners[o] == 0 || (dirty && !dirty[o])) continue;
-        if (nr < cap) {
-            if (run_obj) run_obj[nr] = o;
-            if (run_block) run_block[nr] = at;
-        }
-        nr++;
-        at += ((long long)corners[o] + MPT_DEFORM_CHUNK - 1) / MPT_DEFORM_CHUNK;
-    }
-    if (at > 0x7fffffffLL) return -1;
-    if (blocks) *blocks = at;
-    return nr;
-}
 
 enum MptSkinVerdict { MPT_SKIN_OK = 0, MPT_SKIN_ARGS, MPT_SKIN_NJOINTS, MPT_SKIN_INDEX, MPT_SKIN_NOT_FINITE, MPT_SKIN_NEGATIVE };
 

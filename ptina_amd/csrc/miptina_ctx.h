@@ -7,6 +7,7 @@
 #include "mpt_options.h"
 #include "shade_feat.h"
 #include "refit_rule.h"
+#include "run_table.h"
 #include "deform_rule.h"
 #include "subdiv_rule.h"
 #include "history_rule.h"
@@ -101,18 +102,18 @@ MPT_KERNEL_API hipError_t mpt_launch_history_resample(const MptResampleArgs *, m
 // (mpt_compose); part holds 6 floats per mpt_compose_groups(vertices) workgroups
 MPT_KERNEL_API size_t mpt_compose_groups(size_t nverts);
 MPT_KERNEL_API hipError_t mpt_launch_compose(const float *pool, const MptComposeObj *objs, const int *first, int nobj, int nverts,
-                                             const MptComposeRun *runs, int nruns, int blocks, int all, unsigned epoch, float *out,
+                                             const MptRun *runs, int nruns, int blocks, int all, unsigned epoch, float *out,
                                              int *mtlids, float *part, float *bounds_host, hipStream_t);
 // deform.hip: the deformed copies of the objects of a launch's table, written into the pool the meshes lie in (mpt_compose)
-MPT_KERNEL_API hipError_t mpt_launch_deform(float *pool, const MptDeformObj *objs, const MptDeformRun *runs, int nruns, int blocks,
+MPT_KERNEL_API hipError_t mpt_launch_deform(float *pool, const MptDeformObj *objs, const MptRun *runs, int nruns, int blocks,
                                             const float *deltas, const uint16_t *joints, const float *weights, const double *pose,
                                             hipStream_t stream);
 // subdiv.hip: the subdivided copies of a launch's jobs -- one refine launch per level, the last level's normals, the records (mpt_compose)
-MPT_KERNEL_API hipError_t mpt_launch_subdiv_refine(const float *pool, const MptSubdivJob *jobs, const MptSubdivRun *runs, int nruns, int blocks,
+MPT_KERNEL_API hipError_t mpt_launch_subdiv_refine(const float *pool, const MptSubdivJob *jobs, const MptRun *runs, int nruns, int blocks,
                                                    int level, const int32_t *topo, double *work, hipStream_t stream);
-MPT_KERNEL_API hipError_t mpt_launch_subdiv_normals(const MptSubdivJob *jobs, const MptSubdivRun *runs, int nruns, int blocks, const int32_t *topo,
+MPT_KERNEL_API hipError_t mpt_launch_subdiv_normals(const MptSubdivJob *jobs, const MptRun *runs, int nruns, int blocks, const int32_t *topo,
                                                     double *work, hipStream_t stream);
-MPT_KERNEL_API hipError_t mpt_launch_subdiv_emit(float *pool, const MptSubdivJob *jobs, const MptSubdivRun *runs, int nruns, int blocks,
+MPT_KERNEL_API hipError_t mpt_launch_subdiv_emit(float *pool, const MptSubdivJob *jobs, const MptRun *runs, int nruns, int blocks,
                                                  const int32_t *topo, const double *work, hipStream_t stream);
 
 // on-GPU LBVH build (lbvh_build.hip)
@@ -403,7 +404,7 @@ struct MPT_INTERNAL MptComposeBufs {
     DevBuf<float> pool;                  // object-space records [vertex][8] of every mesh, back to back
     DevBuf<MptComposeObj> objs;          // the object table
     DevBuf<int> first;                   // the objects' first output faces, apart: what the lanes' binary search reads
-    DevBuf<MptComposeRun> runs;          // a partial launch's runs of workgroups
+    DevBuf<MptRun> runs;                 // a partial launch's runs of workgroups
     DevBuf<float> part;                  // 6 floats per workgroup of the output: min3, max3 of its positions
     int reserve_table(size_t nobj) { return objs.reserve(nobj) || first.reserve(nobj) || runs.reserve(nobj); }
     int grow_pool(size_t floats, size_t used, hipStream_t stream) { return grow_keeping(pool, floats, used, stream); }   // keeps the first `used` floats
@@ -417,7 +418,7 @@ struct MPT_INTERNAL MptDeformBufs {
     DevBuf<float> weights;               // [corner][4] their weights
     DevBuf<double> pose;                 // per deformable object: its morph weights, then its joints' 3x4 matrices
     DevBuf<MptDeformObj> objs;           // a launch's objects
-    DevBuf<MptDeformRun> runs;           // ... and its runs of blocks
+    DevBuf<MptRun> runs;                 // ... and its runs of blocks
     int reserve_tables(size_t nobj) { return objs.reserve(nobj) || runs.reserve(nobj); }
 };
 
@@ -427,7 +428,7 @@ struct MPT_INTERNAL MptSubdivBufs {
     DevBuf<int32_t> topo;                // every subdivided mesh's block of words (subdiv_rule.h), back to back
     DevBuf<double> work;                 // per job: the positions of levels 1..L, then the last level's vertex records
     DevBuf<MptSubdivJob> jobs;           // a compose's jobs
-    DevBuf<MptSubdivRun> runs;           // ... and the runs of its launches, (MPT_SUBDIV_MAX_LEVELS + 2) tables of up to a run per job
+    DevBuf<MptRun> runs;                 // ... and the runs of its launches, (MPT_SUBDIV_MAX_LEVELS + 2) tables of up to a run per job
     int reserve_tables(size_t njobs) { return jobs.reserve(njobs) || runs.reserve(njobs * (MPT_SUBDIV_MAX_LEVELS + 2)); }
 };
 
@@ -720,6 +721,18 @@ struct mpt_ctx {
         MptLaunchTimer timer;                            // mpt_compose: {before the compose kernel, after the fold} per call
         explicit Compose(MptEventPool &ev) : timer(2, ev) {}
     } compose{events};
+    // The room of derived copies behind the meshes in the pool, as mesh deformation and Loop subdivision each keep it for theirs (a
+    // copy is a row with a copy_vert: its first pool vertex, -1 while it has no room).  lay_copies (below) assigns the room
+    struct MptCopyRoom {
+        size_t copy_verts = 0;                           // pool vertices the copies hold
+        bool stale = true;                               // the room is not assigned, or the pool it lay in has gone
+        template <class Copies>
+        void lose(Copies &copies, bool &relayout) {      // a mesh joined the pool: it lies where the copies lay
+            if (copy_verts == 0) return;
+            copy_verts = 0; stale = relayout = true;
+            for (auto &p : copies) p.copy_vert = -1;
+        }
+    };
     struct MptDeformMesh { int ntargets = 0, njoints = 0; size_t delta_at = 0, skin_at = 0; };   // what a mesh of the pool carries (arena offsets)
     struct MptDeformPose {                               // a deformable object: its pose as the host keeps it, and its deformed copy
         int obj = 0, mesh = 0;
@@ -732,10 +745,9 @@ struct mpt_ctx {
         std::vector<int> obj_mesh, obj_pose;             // per object of the table: its mesh, and its row of `poses` (-1: not deformable)
         std::vector<MptDeformPose> poses;
         size_t deltas_used = 0, skin_used = 0;           // floats of bufs.deltas, corners of bufs.joints / weights
-        size_t copy_verts = 0;                           // pool vertices the copies hold, behind the meshes
-        bool stale = true;                               // the copies' room is not assigned, or the pool it lay in has gone
+        MptCopyRoom room;                                // the deformed copies' room, behind the meshes
         std::vector<MptDeformObj> h_objs;                // the last launch's tables as uploaded: they outlive the copies that read them
-        std::vector<MptDeformRun> h_runs;
+        std::vector<MptRun> h_runs;
         MptDeformBufs bufs;
         mpt_deform_info stats{};
         MptLaunchTimer timer;                            // mpt_compose: {before the deform kernel, after it} per launch
@@ -757,10 +769,9 @@ struct mpt_ctx {
         std::vector<int> obj_copy;                       // per object of the table: its row of `copies` (-1: its mesh is not subdivided)
         std::vector<MptSubdivCopy> copies;
         size_t topo_used = 0;                            // words of bufs.topo
-        size_t copy_verts = 0;                           // pool vertices the copies hold, behind the meshes and the deformed copies
-        bool stale = true;                               // the copies' room is not assigned, or the pool it lay in has gone
+        MptCopyRoom room;                                // the subdivided copies' room, behind the meshes and the deformed copies
         std::vector<MptSubdivJob> h_jobs;                // the last compose's tables as uploaded: they outlive the copies that read them
-        std::vector<MptSubdivRun> h_runs;
+        std::vector<MptRun> h_runs;
         MptSubdivBufs bufs;
         mpt_subdiv_info stats{};
         int launches = 0;                                // kernels launched since mpt_subdiv_kernel_time last asked
@@ -892,15 +903,38 @@ MPT_INTERNAL int query_tables(mpt_ctx *c);    // before a launch reads c->query.
 
 // scene_compose.cpp
 MPT_INTERNAL int model_on_host(mpt_ctx *c);  // before anything reads c->verts / c->mtlids: fetch them once if mpt_compose made the model
+// ... and what the owners of derived copies in the pool (scene_deform.cpp, scene_subdiv.cpp) take from it
+MPT_INTERNAL int check_fresh_mesh(const mpt_ctx *c, int mesh_id, const char *who);   // the mesh argument of the mpt_mesh_set_* calls: a mesh of the pool, without an object yet
+// the read-back of a copy of `k` faces that lies at copy_vert: `noun` names the copies, `mesh` what has the k faces
+MPT_INTERNAL int read_copy(mpt_ctx *c, long long copy_vert, bool stale, int k, int obj_id, float *verts, int cap_faces, const char *who,
+                           const char *noun, const char *mesh);
+
+// The room of a list of copies (rows with a copy_vert), laid out back to back from pool vertex `base`; verts_of(copy) is a copy's
+// vertices.  Refuses a pool past 2^31 - 1 vertices (MptComposeObj::mesh_vert) and grows the pool, keeping what lies below `base` --
+// for the subdivided copies that includes the deformed ones, and it is this grow_pool that waits for the queued deform launch.
+// The caller points the objects' mesh_vert at the copies (the table changes: all of it goes up, relayout) and clears room.stale
+// once the copies' side arenas have their room too
+template <class Copies, class VertsOf>
+inline int lay_copies(mpt_ctx *c, mpt_ctx::MptCopyRoom &room, Copies &copies, size_t base, VertsOf verts_of, const char *noun) {
+    size_t at = base;
+    for (auto &p : copies) at += verts_of(p);
+    if (at > 0x7fffffffu) return fail("mesh pool full: %zu vertices with the %s copies", at, noun);
+    if (c->compose.bufs.grow_pool(at * 8, base * 8, c->stream)) return 1;
+    at = base;
+    for (auto &p : copies) { p.copy_vert = (long long)at; at += verts_of(p); }
+    room.copy_verts = at - base;
+    c->compose.relayout = true;
+    return 0;
+}
 
 // scene_deform.cpp: what scene_compose.cpp tells the deform table, and the step of mpt_compose that writes the deformed copies
-MPT_INTERNAL void deform_mesh_added(mpt_ctx *c);                 // a mesh joined the pool: the copies behind the meshes lose their room
+MPT_INTERNAL void deform_mesh_added(mpt_ctx *c);                 // a mesh joined the pool: the copies behind the meshes lose their room (MptCopyRoom::lose)
 MPT_INTERNAL void deform_object_added(mpt_ctx *c, int mesh_id);
 MPT_INTERNAL void deform_scene_cleared(mpt_ctx *c, int meshes);
 MPT_INTERNAL int deform_step(mpt_ctx *c);                        // before compose_kernel: room, poses, the deform launch; rewrites objs' mesh_vert at a relayout
 
 // scene_subdiv.cpp: what scene_compose.cpp and scene_deform.cpp tell the subdivision table, and the step of mpt_compose behind deform_step
-MPT_INTERNAL void subdiv_mesh_added(mpt_ctx *c);                 // a mesh joined the pool: the copies behind the meshes lose their room
+MPT_INTERNAL void subdiv_mesh_added(mpt_ctx *c);                 // ... as deform_mesh_added
 MPT_INTERNAL int subdiv_object_faces(const mpt_ctx *c, int mesh_id);   // the faces an object of this mesh has: k * 4^L
 MPT_INTERNAL void subdiv_object_added(mpt_ctx *c, int mesh_id);
 MPT_INTERNAL void subdiv_pose_changed(mpt_ctx *c, int obj_id);   // mpt_object_set_morph_weights / mpt_object_set_joints

@@ -223,6 +223,11 @@ struct MptDisplayArgs {
     float white2, inv_gamma;                 // white * white and 1 / gamma, in f32
 };
 
+// A run of a launch's blocks (run_table.h: the plan of a table of them, the lookup a block does in it).  For the deform and subdivision
+// launches `item` is a row of the launch's table -- an object, a job -- and the run takes the blocks from `block`, a chunk of the row's items
+// each; for compose_kernel `item` is the run's first output workgroup: [item, item + next run's `block` - block) are the blocks from `block`
+struct MptRun { int32_t item, block; };
+
 // scene composition (compose.hip): one object of the table -- a mesh of the pool placed by a world matrix.  `epoch` names the
 // mpt_compose call that last changed the record: a partial launch rewrites the output of the objects that carry its epoch
 struct alignas(16) MptComposeObj {          // 160 bytes: the matrix is read as 16-byte words
@@ -233,12 +238,9 @@ struct alignas(16) MptComposeObj {          // 160 bytes: the matrix is read as 
     int32_t pad[3];
     double world[16];                        // row-major, as numpy holds it
 };
-// a run of consecutive workgroups of a partial launch: output workgroups [wg, wg + next run's `block` - block) are the launch's blocks from `block`
-struct MptComposeRun { int32_t wg, block; };
 
-// mesh deformation (deform.hip): the caps of a mesh's skin and morph targets, one deformable object of a launch -- where its
-// mesh's records and its deformed copy lie in the pool, and where its mesh's deltas / skin and its own pose lie in their arenas --
-// and a run of the launch's blocks: object `obj` of the launch's table takes the blocks from `block`, MPT_DEFORM_CHUNK corners each
+// mesh deformation (deform.hip): the caps of a mesh's skin and morph targets and one deformable object of a launch -- where its
+// mesh's records and its deformed copy lie in the pool, and where its mesh's deltas / skin and its own pose lie in their arenas
 #define MPT_DEFORM_MAX_JOINTS 256           // 96 bytes of LDS each: 24 KB of the CU's 160 KiB
 #define MPT_DEFORM_MAX_TARGETS 64
 #define MPT_DEFORM_CHUNK 1024               // corners per workgroup: four per lane
@@ -251,11 +253,10 @@ struct MptDeformObj {                       // 48 bytes
     int64_t skin_at;                         // its skin: first corner in the arenas of indices [.][4] u16 and weights [.][4] f32
     int64_t pose_at;                         // the object's pose: ntargets weights, then njoints 3x4 matrices, f64: first double
 };
-struct MptDeformRun { int32_t obj, block; };
 
 // Loop subdivision (subdiv.hip): the caps, the kinds of a vertex rule (subdiv_rule.h), one job of a launch -- a subdivided copy: where
 // its control records and the copy lie in the pool, where its mesh's topology block lies in the arena of words and its own f64
-// vertices in the workspace -- and a run of a launch's blocks: job `job` takes the blocks from `block`, MPT_SUBDIV_CHUNK items each
+// vertices in the workspace
 #define MPT_SUBDIV_MAX_LEVELS 5
 #define MPT_SUBDIV_MAX_FACES (1 << 24)      // faces of a last level the topology function takes (the context's max_faces is lower)
 #define MPT_SUBDIV_CHUNK 256                // items (vertices or faces) per workgroup: one per lane
@@ -272,4 +273,3 @@ struct MptSubdivJob {                       // 128 bytes
     int32_t vrec_at;                         // doubles from work_at (even): the last level's vertex records, 32 bytes each: pos3 nrm3 as f32, 8 bytes unused
     int32_t pad[3];
 };
-struct MptSubdivRun { int32_t job, block; };

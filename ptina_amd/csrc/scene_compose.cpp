@@ -56,6 +56,14 @@ static int check_object(const mpt_ctx *c, int obj_id) {
     return 0;
 }
 
+int check_fresh_mesh(const mpt_ctx *c, int mesh_id, const char *who) {
+    const size_t meshes = c->compose.meshes.size();
+    if (mesh_id < 0 || (size_t)mesh_id >= meshes) return fail("%s: unknown mesh %d (%zu meshes)", who, mesh_id, meshes);
+    for (size_t o = 0; o < c->deform.obj_mesh.size(); o++)
+        if (c->deform.obj_mesh[o] == mesh_id) return fail("%s: mesh %d already has an object (object %zu)", who, mesh_id, o);
+    return 0;
+}
+
 extern "C" int mpt_mesh_add(mpt_ctx *c, const float *verts, int k, int *mesh_id) {
     if (use(c)) return 1;
     if (k < 0 || (k > 0 && !verts)) return fail("bad mesh arguments");
@@ -168,11 +176,11 @@ extern "C" int mpt_compose(mpt_ctx *c) {
             if (cp.dirty[o])
                 HIP_TRY(hipMemcpyAsync(cp.bufs.objs + o, &cp.objs[o], sizeof(MptComposeObj), hipMemcpyHostToDevice, c->stream));
     }
-    std::vector<MptComposeRun> runs((size_t)std::max(nruns, 1));
+    std::vector<MptRun> runs((size_t)std::max(nruns, 1));
     int blocks = 0;
     for (int r = 0; r < nruns; r++) { runs[r] = { (int32_t)wg_begin[r], blocks }; blocks += (int)wg_count[r]; }
     if (!all && nruns > 0)
-        HIP_TRY(hipMemcpyAsync(cp.bufs.runs, runs.data(), (size_t)nruns * sizeof(MptComposeRun), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(cp.bufs.runs, runs.data(), (size_t)nruns * sizeof(MptRun), hipMemcpyHostToDevice, c->stream));
     if (n > 0) {
         MptTimedSpan span(cp.timer, c->stream);
         HIP_TRY(span.begun);
@@ -236,6 +244,16 @@ extern "C" int mpt_get_model(mpt_ctx *c, float *verts, int32_t *mtlids, int cap_
     if (model_on_host(c)) return 1;
     if (verts) memcpy(verts, c->verts.data(), (size_t)c->nfaces * 24 * sizeof(float));
     if (mtlids) memcpy(mtlids, c->mtlids.data(), (size_t)c->nfaces * sizeof(int32_t));
+    return 0;
+}
+
+int read_copy(mpt_ctx *c, long long copy_vert, bool stale, int k, int obj_id, float *verts, int cap_faces, const char *who, const char *noun,
+              const char *mesh) {
+    if (copy_vert < 0 || stale) return fail("%s: object %d has no %s copy yet: call mpt_compose", who, obj_id, noun);
+    if (cap_faces < k) return fail("%s: room for %d faces, the %s of object %d has %d", who, cap_faces, mesh, obj_id, k);
+    if (k > 0 && !verts) return fail("%s: null verts", who);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (k > 0) HIP_TRY(hipMemcpy(verts, c->compose.bufs.pool + (size_t)copy_vert * 8, (size_t)k * 24 * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -1,12 +1,12 @@
 // scene_deform.cpp -- mesh deformation behind mpt_mesh_set_morph / mpt_mesh_set_skin / mpt_object_set_morph_weights /
 // mpt_object_set_joints: the meshes' deltas and skins and the objects' poses on the device, the deform
-// table beside scene_compose.cpp's object table, the run table of a launch (mpt_deform_plan, a pure function), and deform_step:
+// table beside scene_compose.cpp's object table, the run table of a launch (mpt_deform_plan: run_table.h's rule), and deform_step:
 // the part of mpt_compose that gives the deformed copies their room in the pool and launches deform.hip before compose_kernel.
 
 #include "miptina_ctx.h"
 
 extern "C" int mpt_deform_plan(const int32_t *corners, const int32_t *dirty, int nobj, int32_t *run_obj, int64_t *run_block, int cap, int64_t *blocks) {
-    return mpt_deform_plan_of(corners, dirty, nobj, run_obj, run_block, cap, blocks);
+    return mpt_run_plan_of(corners, dirty, nobj, MPT_DEFORM_CHUNK, run_obj, run_block, cap, blocks);
 }
 
 extern "C" int mpt_skin_check(const uint16_t *joints, const float *weights, int64_t ncorners, int njoints, char *why, int why_size) {
@@ -17,10 +17,7 @@ extern "C" int mpt_skin_check(const uint16_t *joints, const float *weights, int6
 void deform_mesh_added(mpt_ctx *c) {
     auto &df = c->deform;
     df.meshes.resize(c->compose.meshes.size());
-    if (df.copy_verts == 0) return;
-    df.copy_verts = 0; df.stale = true;                // the new mesh lies where the copies lay
-    for (auto &p : df.poses) p.copy_vert = -1;
-    c->compose.relayout = true;
+    df.room.lose(df.poses, c->compose.relayout);
 }
 
 void deform_object_added(mpt_ctx *c, int mesh_id) {
@@ -36,30 +33,22 @@ void deform_object_added(mpt_ctx *c, int mesh_id) {
         for (int r = 0; r < 3; r++) p.pose[(size_t)m.ntargets + (size_t)j * 12 + 4 * r + r] = 1.0;
     df.obj_pose.push_back((int)df.poses.size());
     df.poses.push_back(std::move(p));
-    df.stale = true;
+    df.room.stale = true;
 }
 
 void deform_scene_cleared(mpt_ctx *c, int meshes) {
     auto &df = c->deform;
     df.obj_mesh.clear(); df.obj_pose.clear(); df.poses.clear();
-    df.copy_verts = 0; df.stale = true;
+    df.room.copy_verts = 0; df.room.stale = true;
     if (meshes) { df.meshes.clear(); df.deltas_used = 0; df.skin_used = 0; }
 }
 
 // ---------------------------------------------------------------- the meshes' targets and skins
-static int check_mesh(mpt_ctx *c, int mesh_id, const char *who) {
-    auto &df = c->deform;
-    if (mesh_id < 0 || (size_t)mesh_id >= c->compose.meshes.size()) return fail("%s: unknown mesh %d (%zu meshes)", who, mesh_id, c->compose.meshes.size());
-    for (size_t o = 0; o < df.obj_mesh.size(); o++)
-        if (df.obj_mesh[o] == mesh_id) return fail("%s: mesh %d already has an object (object %zu)", who, mesh_id, o);
-    df.meshes.resize(c->compose.meshes.size());
-    return 0;
-}
-
 extern "C" int mpt_mesh_set_morph(mpt_ctx *c, int mesh_id, const float *deltas, int T) {
     if (use(c)) return 1;
-    if (check_mesh(c, mesh_id, "mpt_mesh_set_morph")) return 1;
+    if (check_fresh_mesh(c, mesh_id, "mpt_mesh_set_morph")) return 1;
     auto &df = c->deform;
+    df.meshes.resize(c->compose.meshes.size());
     if (df.meshes[mesh_id].ntargets) return fail("mpt_mesh_set_morph: mesh %d already has morph targets", mesh_id);
     if (T < 1 || T > MPT_DEFORM_MAX_TARGETS) return fail("mpt_mesh_set_morph: T %d outside [1, %d]", T, MPT_DEFORM_MAX_TARGETS);
     const size_t corners = (size_t)c->compose.meshes[mesh_id].nfaces * 3, floats = (size_t)T * corners * 6;
@@ -79,8 +68,9 @@ extern "C" int mpt_mesh_set_morph(mpt_ctx *c, int mesh_id, const float *deltas, 
 
 extern "C" int mpt_mesh_set_skin(mpt_ctx *c, int mesh_id, const uint16_t *joints, const float *weights, int njoints) {
     if (use(c)) return 1;
-    if (check_mesh(c, mesh_id, "mpt_mesh_set_skin")) return 1;
+    if (check_fresh_mesh(c, mesh_id, "mpt_mesh_set_skin")) return 1;
     auto &df = c->deform;
+    df.meshes.resize(c->compose.meshes.size());
     if (df.meshes[mesh_id].njoints) return fail("mpt_mesh_set_skin: mesh %d already has a skin", mesh_id);
     const size_t corners = (size_t)c->compose.meshes[mesh_id].nfaces * 3;
     char why[160];
@@ -159,28 +149,19 @@ int deform_step(mpt_ctx *c) {
     df.stats.deformable_objects = (int64_t)df.poses.size();
     const int np = (int)df.poses.size();
     if (np == 0) { df.stats.copy_verts = 0; return 0; }
-    const bool all = cp.relayout || df.stale;
+    const bool all = cp.relayout || df.room.stale;
     if (all) {
-        size_t at = cp.pool_verts, pose_at = 0;
+        if (lay_copies(c, df.room, df.poses, cp.pool_verts, [&](const auto &p) { return (size_t)cp.meshes[p.mesh].nfaces * 3; }, "deformed")) return 1;
+        size_t pose_at = 0;
         for (auto &p : df.poses) {
-            at += (size_t)cp.meshes[p.mesh].nfaces * 3;
+            cp.objs[p.obj].mesh_vert = (int32_t)p.copy_vert;
+            p.pose_at = pose_at;
             pose_at += p.pose.size();
         }
-        if (at > 0x7fffffffu) return fail("mesh pool full: %zu vertices with the deformed copies", at);   // (MptComposeObj::mesh_vert)
-        if (cp.bufs.grow_pool(at * 8, cp.pool_verts * 8, c->stream)) return 1;
         if (df.bufs.pose.reserve(pose_at) || df.bufs.reserve_tables((size_t)np)) return 1;
-        at = cp.pool_verts; pose_at = 0;
-        for (auto &p : df.poses) {
-            p.copy_vert = (long long)at; p.pose_at = pose_at;
-            cp.objs[p.obj].mesh_vert = (int32_t)at;
-            at += (size_t)cp.meshes[p.mesh].nfaces * 3;
-            pose_at += p.pose.size();
-        }
-        df.copy_verts = at - cp.pool_verts;
-        cp.relayout = true;                            // the table's mesh_vert changed: all of it goes up
-        df.stale = false;
+        df.room.stale = false;
     }
-    df.stats.copy_verts = (int64_t)df.copy_verts;
+    df.stats.copy_verts = (int64_t)df.room.copy_verts;
     std::vector<MptDeformObj> &table = df.h_objs;
     table.resize((size_t)np);
     std::vector<int32_t> corners((size_t)np), dirty((size_t)np);
@@ -194,10 +175,9 @@ int deform_step(mpt_ctx *c) {
         t.delta_at = (int64_t)m.delta_at; t.skin_at = (int64_t)m.skin_at; t.pose_at = (int64_t)p.pose_at;
         corners[k] = t.nverts; dirty[k] = all || p.dirty;
     }
-    std::vector<int32_t> run_obj((size_t)np);
-    std::vector<int64_t> run_block((size_t)np);
-    int64_t blocks = 0;
-    const int nruns = mpt_deform_plan_of(corners.data(), dirty.data(), np, run_obj.data(), run_block.data(), np, &blocks);
+    df.h_runs.resize((size_t)np);
+    int blocks = 0;
+    const int nruns = mpt_run_plan_into(corners.data(), dirty.data(), np, MPT_DEFORM_CHUNK, df.h_runs.data(), &blocks);
     if (nruns < 0) return fail("too many corners to deform");
     for (int k = 0; k < np; k++) {
         auto &p = df.poses[k];
@@ -207,14 +187,11 @@ int deform_step(mpt_ctx *c) {
             HIP_TRY(hipMemcpyAsync(df.bufs.pose + p.pose_at, p.pose.data(), p.pose.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
     if (nruns > 0) {
-        std::vector<MptDeformRun> &runs = df.h_runs;
-        runs.resize((size_t)nruns);
-        for (int r = 0; r < nruns; r++) runs[r] = { run_obj[r], (int32_t)run_block[r] };
         HIP_TRY(hipMemcpyAsync(df.bufs.objs, table.data(), (size_t)np * sizeof(MptDeformObj), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(df.bufs.runs, runs.data(), (size_t)nruns * sizeof(MptDeformRun), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(df.bufs.runs, df.h_runs.data(), (size_t)nruns * sizeof(MptRun), hipMemcpyHostToDevice, c->stream));
         MptTimedSpan span(df.timer, c->stream);
         HIP_TRY(span.begun);
-        HIP_TRY(mpt_launch_deform(cp.bufs.pool, df.bufs.objs, df.bufs.runs, nruns, (int)blocks, df.bufs.deltas, df.bufs.joints, df.bufs.weights,
+        HIP_TRY(mpt_launch_deform(cp.bufs.pool, df.bufs.objs, df.bufs.runs, nruns, blocks, df.bufs.deltas, df.bufs.joints, df.bufs.weights,
                                   df.bufs.pose, c->stream));
         HIP_TRY(span.end());
     }
@@ -228,20 +205,14 @@ extern "C" int mpt_get_deformed(mpt_ctx *c, int obj_id, float *verts, int cap_fa
     mpt_ctx::MptDeformPose *p = nullptr;
     if (pose_of(c, obj_id, "mpt_get_deformed", &p)) return 1;
     if (!p) return fail("mpt_get_deformed: the mesh of object %d has neither morph targets nor a skin", obj_id);
-    if (p->copy_vert < 0 || c->deform.stale) return fail("mpt_get_deformed: object %d has no deformed copy yet: call mpt_compose", obj_id);
-    const int k = c->compose.meshes[p->mesh].nfaces;
-    if (cap_faces < k) return fail("mpt_get_deformed: room for %d faces, the mesh of object %d has %d", cap_faces, obj_id, k);
-    if (k > 0 && !verts) return fail("mpt_get_deformed: null verts");
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (k > 0) HIP_TRY(hipMemcpy(verts, c->compose.bufs.pool + (size_t)p->copy_vert * 8, (size_t)k * 24 * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    return read_copy(c, p->copy_vert, c->deform.room.stale, c->compose.meshes[p->mesh].nfaces, obj_id, verts, cap_faces, "mpt_get_deformed", "deformed", "mesh");
 }
 
 extern "C" int mpt_deform_stats(mpt_ctx *c, mpt_deform_info *out) {
     if (!c || !out) return fail("null argument");
     *out = c->deform.stats;
     out->deformable_objects = (int64_t)c->deform.poses.size();
-    out->copy_verts = (int64_t)c->deform.copy_verts;
+    out->copy_verts = (int64_t)c->deform.room.copy_verts;
     return 0;
 }
 

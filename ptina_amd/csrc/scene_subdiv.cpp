@@ -1,12 +1,12 @@
 // scene_subdiv.cpp -- Loop subdivision behind mpt_mesh_set_subdivision: the meshes' topology blocks on the
 // device (subdiv_rule.h makes them, a pure function), the table of subdivided copies beside scene_compose.cpp's object table and
-// scene_deform.cpp's poses, the run tables of a compose's launches (mpt_subdiv_plan, a pure function), and subdiv_step: the part of
+// scene_deform.cpp's poses, the run tables of a compose's launches (mpt_subdiv_plan: run_table.h's rule), and subdiv_step: the part of
 // mpt_compose behind deform_step that gives the copies their room in the pool and launches subdiv.hip before compose_kernel.
 
 #include "miptina_ctx.h"
 
 extern "C" int mpt_subdiv_plan(const int32_t *items, const int32_t *dirty, int njobs, int32_t *run_job, int64_t *run_block, int cap, int64_t *blocks) {
-    return mpt_subdiv_plan_of(items, dirty, njobs, run_job, run_block, cap, blocks);
+    return mpt_run_plan_of(items, dirty, njobs, MPT_SUBDIV_CHUNK, run_job, run_block, cap, blocks);
 }
 
 extern "C" int mpt_subdiv_topology(const float *verts, int k, int levels, int64_t *counts, int32_t *offsets, int32_t *words, int64_t cap_words,
@@ -29,10 +29,7 @@ extern "C" int mpt_subdiv_topology(const float *verts, int k, int levels, int64_
 void subdiv_mesh_added(mpt_ctx *c) {
     auto &sd = c->subdiv;
     sd.meshes.resize(c->compose.meshes.size());
-    if (sd.copy_verts == 0) return;
-    sd.copy_verts = 0; sd.stale = true;                // the new mesh lies where the copies lay
-    for (auto &p : sd.copies) p.copy_vert = -1;
-    c->compose.relayout = true;
+    sd.room.lose(sd.copies, c->compose.relayout);
 }
 
 int subdiv_object_faces(const mpt_ctx *c, int mesh_id) {
@@ -55,7 +52,7 @@ void subdiv_object_added(mpt_ctx *c, int mesh_id) {
         if (!deformable) m.job = (int)sd.copies.size() - 1;
     }
     sd.obj_copy.push_back(deformable ? (int)sd.copies.size() - 1 : m.job);
-    sd.stale = true;
+    sd.room.stale = true;
 }
 
 void subdiv_pose_changed(mpt_ctx *c, int obj_id) {
@@ -67,7 +64,7 @@ void subdiv_scene_cleared(mpt_ctx *c, int meshes) {
     auto &sd = c->subdiv;
     sd.obj_copy.clear(); sd.copies.clear();
     for (auto &m : sd.meshes) m.job = -1;
-    sd.copy_verts = 0; sd.stale = true;
+    sd.room.copy_verts = 0; sd.room.stale = true;
     if (meshes) { sd.meshes.clear(); sd.topo_used = 0; }
 }
 
@@ -76,9 +73,7 @@ extern "C" int mpt_mesh_set_subdivision(mpt_ctx *c, int mesh_id, int levels) {
     if (use(c)) return 1;
     auto &sd = c->subdiv;
     auto &cp = c->compose;
-    if (mesh_id < 0 || (size_t)mesh_id >= cp.meshes.size()) return fail("mpt_mesh_set_subdivision: unknown mesh %d (%zu meshes)", mesh_id, cp.meshes.size());
-    for (size_t o = 0; o < c->deform.obj_mesh.size(); o++)
-        if (c->deform.obj_mesh[o] == mesh_id) return fail("mpt_mesh_set_subdivision: mesh %d already has an object (object %zu)", mesh_id, o);
+    if (check_fresh_mesh(c, mesh_id, "mpt_mesh_set_subdivision")) return 1;
     sd.meshes.resize(cp.meshes.size());
     if (sd.meshes[mesh_id].levels) return fail("mpt_mesh_set_subdivision: mesh %d already has a subdivision level", mesh_id);
     if (levels < 1 || levels > MPT_SUBDIV_MAX_LEVELS) return fail("mpt_mesh_set_subdivision: levels %d outside [1, %d]", levels, MPT_SUBDIV_MAX_LEVELS);
@@ -128,30 +123,22 @@ int subdiv_step(mpt_ctx *c) {
     sd.stats.refined_copies = sd.stats.refined_faces = 0;
     const int n = (int)sd.copies.size();
     if (n == 0) { sd.stats.copy_verts = 0; return 0; }
-    const bool all = cp.relayout || sd.stale;
+    const bool all = cp.relayout || sd.room.stale;
     if (all) {
-        const size_t base = cp.pool_verts + df.copy_verts;
-        size_t at = base, work = 0;
+        // (behind the deformed copies, which the pool keeps as it grows: a pool that grows here waits for the deform launch)
+        const size_t base = cp.pool_verts + df.room.copy_verts;
+        if (lay_copies(c, sd.room, sd.copies, base, [&](const auto &p) { return (size_t)subdiv_object_faces(c, p.mesh) * 3; }, "subdivided")) return 1;
+        size_t work = 0;
         for (auto &p : sd.copies) {
-            at += (size_t)subdiv_object_faces(c, p.mesh) * 3;
+            p.work_at = work;
             work += work_layout(sd.meshes[p.mesh], nullptr);
         }
-        if (at > 0x7fffffffu) return fail("mesh pool full: %zu vertices with the subdivided copies", at);   // (MptComposeObj::mesh_vert)
-        if (cp.bufs.grow_pool(at * 8, base * 8, c->stream)) return 1;     // (keeps the meshes and the deformed copies; waits for the deform launch)
         if (sd.bufs.work.reserve(std::max(work, (size_t)2)) || sd.bufs.reserve_tables((size_t)n)) return 1;
-        at = base; work = 0;
-        for (auto &p : sd.copies) {
-            p.copy_vert = (long long)at; p.work_at = work;
-            at += (size_t)subdiv_object_faces(c, p.mesh) * 3;
-            work += work_layout(sd.meshes[p.mesh], nullptr);
-        }
         for (size_t o = 0; o < sd.obj_copy.size(); o++)
             if (sd.obj_copy[o] >= 0) cp.objs[o].mesh_vert = (int32_t)sd.copies[sd.obj_copy[o]].copy_vert;
-        sd.copy_verts = at - base;
-        cp.relayout = true;                            // the table's mesh_vert changed: all of it goes up
-        sd.stale = false;
+        sd.room.stale = false;
     }
-    sd.stats.copy_verts = (int64_t)sd.copy_verts;
+    sd.stats.copy_verts = (int64_t)sd.room.copy_verts;
     std::vector<MptSubdivJob> &jobs = sd.h_jobs;
     jobs.assign((size_t)n, MptSubdivJob{});
     std::vector<int32_t> dirty((size_t)n);
@@ -176,22 +163,18 @@ int subdiv_step(mpt_ctx *c) {
     if (ndirty == 0) return 0;
     // the run tables: launch t = 0 .. lmax - 1 refines to level t + 1, then the normals, then the records
     const int ntables = lmax + 2;
-    std::vector<MptSubdivRun> &runs = sd.h_runs;
-    runs.assign((size_t)ntables * (size_t)n, MptSubdivRun{});
+    std::vector<MptRun> &runs = sd.h_runs;
+    runs.assign((size_t)ntables * (size_t)n, MptRun{});
     std::vector<int> nruns((size_t)ntables), blocks((size_t)ntables);
-    std::vector<int32_t> items((size_t)n), run_job((size_t)n);
-    std::vector<int64_t> run_block((size_t)n);
+    std::vector<int32_t> items((size_t)n);
     for (int t = 0; t < ntables; t++) {
         for (int j = 0; j < n; j++)
             items[j] = t < lmax ? (jobs[j].levels > t ? jobs[j].nv[t + 1] : 0) : t == lmax ? jobs[j].nv[jobs[j].levels] : jobs[j].nfaces;
-        int64_t b = 0;
-        nruns[t] = mpt_subdiv_plan_of(items.data(), dirty.data(), n, run_job.data(), run_block.data(), n, &b);
+        nruns[t] = mpt_run_plan_into(items.data(), dirty.data(), n, MPT_SUBDIV_CHUNK, runs.data() + (size_t)t * (size_t)n, &blocks[t]);
         if (nruns[t] < 0) return fail("too many faces to subdivide");
-        blocks[t] = (int)b;
-        for (int r = 0; r < nruns[t]; r++) runs[(size_t)t * (size_t)n + (size_t)r] = { run_job[r], (int32_t)run_block[r] };
     }
     HIP_TRY(hipMemcpyAsync(sd.bufs.jobs, jobs.data(), (size_t)n * sizeof(MptSubdivJob), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(sd.bufs.runs, runs.data(), runs.size() * sizeof(MptSubdivRun), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(sd.bufs.runs, runs.data(), runs.size() * sizeof(MptRun), hipMemcpyHostToDevice, c->stream));
     {
         MptTimedSpan span(sd.refine_timer, c->stream);
         HIP_TRY(span.begun);
@@ -228,13 +211,8 @@ extern "C" int mpt_get_subdivided(mpt_ctx *c, int obj_id, float *verts, int cap_
     if (obj_id < 0 || (size_t)obj_id >= sd.obj_copy.size()) return fail("mpt_get_subdivided: unknown object %d (%zu objects)", obj_id, sd.obj_copy.size());
     if (sd.obj_copy[obj_id] < 0) return fail("mpt_get_subdivided: the mesh of object %d has no subdivision level", obj_id);
     const auto &p = sd.copies[sd.obj_copy[obj_id]];
-    if (p.copy_vert < 0 || sd.stale) return fail("mpt_get_subdivided: object %d has no subdivided copy yet: call mpt_compose", obj_id);
     const int k = subdiv_object_faces(c, p.mesh);
-    if (cap_faces < k) return fail("mpt_get_subdivided: room for %d faces, the subdivided mesh of object %d has %d", cap_faces, obj_id, k);
-    if (k > 0 && !verts) return fail("mpt_get_subdivided: null verts");
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (k > 0) HIP_TRY(hipMemcpy(verts, c->compose.bufs.pool + (size_t)p.copy_vert * 8, (size_t)k * 24 * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    return read_copy(c, p.copy_vert, sd.room.stale, k, obj_id, verts, cap_faces, "mpt_get_subdivided", "subdivided", "subdivided mesh");
 }
 
 extern "C" int mpt_subdiv_stats(mpt_ctx *c, mpt_subdiv_info *out) {
@@ -243,7 +221,7 @@ extern "C" int mpt_subdiv_stats(mpt_ctx *c, mpt_subdiv_info *out) {
     out->subdivided_objects = 0;
     for (int j : c->subdiv.obj_copy) out->subdivided_objects += j >= 0;
     out->copies = (int64_t)c->subdiv.copies.size();
-    out->copy_verts = (int64_t)c->subdiv.copy_verts;
+    out->copy_verts = (int64_t)c->subdiv.room.copy_verts;
     return 0;
 }
 

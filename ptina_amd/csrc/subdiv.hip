@@ -28,7 +28,7 @@
 //     midpoints m_ij = 0.5 * (u_i + u_j) in f64, level by level.
 //
 // Three kernels, each one lane per item (a workgroup of 256 lanes takes MPT_SUBDIV_CHUNK items of ONE job; a run table maps blocks to
-// (job, chunk): compose_kernel's and deform_kernel's idiom), so the number of launches of an mpt_compose is L_max + 2 whatever the
+// (job, chunk): run_table.h), so the number of launches of an mpt_compose is L_max + 2 whatever the
 // number of copies; a job of fewer levels has no blocks in the later refine launches.  Levels are separate launches: nothing is
 // handed from workgroup to workgroup inside a launch.
 //   subdiv_refine_kernel   level l - 1 -> l: a lane reads its vertex's rule (two words), gathers 2 to n + 1 positions of the level
@@ -44,6 +44,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "mpt_types.h"
+#include "run_table.h"
 
 enum { SD_BLOCK = MPT_SUBDIV_CHUNK };
 static_assert(sizeof(MptSubdivJob) == 128, "the job record is 128 bytes");
@@ -52,13 +53,6 @@ struct SdVec { double x, y, z; };
 static __device__ __forceinline__ SdVec sd_add(SdVec a, SdVec b) { return { a.x + b.x, a.y + b.y, a.z + b.z }; }
 static __device__ __forceinline__ SdVec sd_sub(SdVec a, SdVec b) { return { a.x - b.x, a.y - b.y, a.z - b.z }; }
 static __device__ __forceinline__ SdVec sd_mul(double s, SdVec a) { return { s * a.x, s * a.y, s * a.z }; }
-
-// the run a block belongs to (uniform), as deform_kernel finds it
-static __device__ __forceinline__ int sd_run(const MptSubdivRun *__restrict__ runs, int nruns) {
-    int a = 0, b = nruns - 1;
-    while (a < b) { const int m = (a + b + 1) >> 1; if (runs[m].block <= (int)blockIdx.x) a = m; else b = m - 1; }
-    return a;
-}
 
 // the position of vertex v of the level below `level`
 static __device__ __forceinline__ SdVec sd_pos(const MptSubdivJob &o, int level, const float4 *pool, const int32_t *__restrict__ T,
@@ -72,10 +66,10 @@ static __device__ __forceinline__ SdVec sd_pos(const MptSubdivJob &o, int level,
 }
 
 __global__ __launch_bounds__(SD_BLOCK) void subdiv_refine_kernel(const float4 *pool, const MptSubdivJob *__restrict__ jobs,
-                                                                 const MptSubdivRun *__restrict__ runs, int nruns, int level,
+                                                                 const MptRun *__restrict__ runs, int nruns, int level,
                                                                  const int32_t *__restrict__ topo, double *work) {
-    const int r = sd_run(runs, nruns);
-    const MptSubdivJob &o = jobs[runs[r].job];          // (fields read through the scalar cache: a copy indexed by the level would live in scratch)
+    const int r = mpt_run_of(runs, nruns);
+    const MptSubdivJob &o = jobs[runs[r].item];          // (fields read through the scalar cache: a copy indexed by the level would live in scratch)
     const int i = ((int)blockIdx.x - runs[r].block) * SD_BLOCK + (int)threadIdx.x;
     if (i >= o.nv[level]) return;
     const int32_t *__restrict__ T = topo + o.topo_at;
@@ -105,10 +99,10 @@ __global__ __launch_bounds__(SD_BLOCK) void subdiv_refine_kernel(const float4 *p
     dst[0] = out.x; dst[1] = out.y; dst[2] = out.z;
 }
 
-__global__ __launch_bounds__(SD_BLOCK) void subdiv_normal_kernel(const MptSubdivJob *__restrict__ jobs, const MptSubdivRun *__restrict__ runs,
+__global__ __launch_bounds__(SD_BLOCK) void subdiv_normal_kernel(const MptSubdivJob *__restrict__ jobs, const MptRun *__restrict__ runs,
                                                                  int nruns, const int32_t *__restrict__ topo, const double *work_in, double *work_out) {
-    const int r = sd_run(runs, nruns);
-    const MptSubdivJob &o = jobs[runs[r].job];          // (fields read through the scalar cache: a copy indexed by the level would live in scratch)
+    const int r = mpt_run_of(runs, nruns);
+    const MptSubdivJob &o = jobs[runs[r].item];          // (fields read through the scalar cache: a copy indexed by the level would live in scratch)
     const int i = ((int)blockIdx.x - runs[r].block) * SD_BLOCK + (int)threadIdx.x;
     if (i >= o.nv[o.levels]) return;
     const int32_t *__restrict__ T = topo + o.topo_at;
@@ -139,10 +133,10 @@ __global__ __launch_bounds__(SD_BLOCK) void subdiv_normal_kernel(const MptSubdiv
 }
 
 __global__ __launch_bounds__(SD_BLOCK) void subdiv_emit_kernel(const float4 *pool_in, float4 *pool_out, const MptSubdivJob *__restrict__ jobs,
-                                                               const MptSubdivRun *__restrict__ runs, int nruns, const int32_t *__restrict__ topo,
+                                                               const MptRun *__restrict__ runs, int nruns, const int32_t *__restrict__ topo,
                                                                const double *__restrict__ work) {
-    const int r = sd_run(runs, nruns);
-    const MptSubdivJob &o = jobs[runs[r].job];          // (fields read through the scalar cache: a copy indexed by the level would live in scratch)
+    const int r = mpt_run_of(runs, nruns);
+    const MptSubdivJob &o = jobs[runs[r].item];          // (fields read through the scalar cache: a copy indexed by the level would live in scratch)
     const int g = ((int)blockIdx.x - runs[r].block) * SD_BLOCK + (int)threadIdx.x;
     if (g >= o.nfaces) return;
     const int32_t *__restrict__ F = topo + o.topo_at + o.face_at + (size_t)g * 3;
@@ -174,21 +168,21 @@ __global__ __launch_bounds__(SD_BLOCK) void subdiv_emit_kernel(const float4 *poo
 // runs[nruns] and blocks: mpt_subdiv_plan's table over the jobs' items of this launch and the sum of its blocks.  The pool is read
 // at the jobs' src_vert and written at their dst_vert, the workspace read at one level and written at the next: ranges that never
 // overlap
-MPT_KERNEL_API hipError_t mpt_launch_subdiv_refine(const float *pool, const MptSubdivJob *jobs, const MptSubdivRun *runs, int nruns, int blocks,
+MPT_KERNEL_API hipError_t mpt_launch_subdiv_refine(const float *pool, const MptSubdivJob *jobs, const MptRun *runs, int nruns, int blocks,
                                                    int level, const int32_t *topo, double *work, hipStream_t stream) {
     if (nruns < 1 || blocks < 1 || level < 1 || level > MPT_SUBDIV_MAX_LEVELS) return hipErrorInvalidValue;
     hipLaunchKernelGGL(subdiv_refine_kernel, dim3((unsigned)blocks), dim3(SD_BLOCK), 0, stream, (const float4 *)pool, jobs, runs, nruns, level, topo, work);
     return hipGetLastError();
 }
 
-MPT_KERNEL_API hipError_t mpt_launch_subdiv_normals(const MptSubdivJob *jobs, const MptSubdivRun *runs, int nruns, int blocks, const int32_t *topo,
+MPT_KERNEL_API hipError_t mpt_launch_subdiv_normals(const MptSubdivJob *jobs, const MptRun *runs, int nruns, int blocks, const int32_t *topo,
                                                     double *work, hipStream_t stream) {
     if (nruns < 1 || blocks < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(subdiv_normal_kernel, dim3((unsigned)blocks), dim3(SD_BLOCK), 0, stream, jobs, runs, nruns, topo, (const double *)work, work);
     return hipGetLastError();
 }
 
-MPT_KERNEL_API hipError_t mpt_launch_subdiv_emit(float *pool, const MptSubdivJob *jobs, const MptSubdivRun *runs, int nruns, int blocks,
+MPT_KERNEL_API hipError_t mpt_launch_subdiv_emit(float *pool, const MptSubdivJob *jobs, const MptRun *runs, int nruns, int blocks,
                                                  const int32_t *topo, const double *work, hipStream_t stream) {
     if (nruns < 1 || blocks < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(subdiv_emit_kernel, dim3((unsigned)blocks), dim3(SD_BLOCK), 0, stream, (const float4 *)pool, (float4 *)pool, jobs, runs, nruns, topo,

@@ -1,8 +1,8 @@
-// subdiv_rule.h -- the two pure pieces of Loop subdivision's host side (scene_subdiv.cpp): the topology of a
-// mesh and of its refinements -- the tables subdiv.hip gathers through -- and the run table of one of its launches.  Plain C++17
-// with nothing of HIP and no context (as deform_rule.h), so that a stand-alone program can run them under a sanitizer
-// (tools/subdiv_rule_check.cpp); the C ABI has them as mpt_subdiv_topology and mpt_subdiv_plan.  The definition they follow is
-// stated in include/miptina.h and at the top of subdiv.hip.
+// subdiv_rule.h -- the pure piece of Loop subdivision's host side (scene_subdiv.cpp): the topology of a
+// mesh and of its refinements, the tables subdiv.hip gathers through (the run tables of its launches are run_table.h's).  Plain
+// C++17 with nothing of HIP and no context (as deform_rule.h), so that a stand-alone program can run it under a sanitizer
+// (tools/subdiv_rule_check.cpp); the C ABI has it as mpt_subdiv_topology.  The definition it follows is stated in
+// include/miptina.h and at the top of subdiv.hip.
 #pragma once
 
 #include <algorithm>
@@ -14,30 +14,6 @@
 #include <unordered_map>
 #include <vector>
 #include "mpt_types.h"          // MPT_SUBDIV_* (plain structures and constants)
-
-// The blocks of one subdivision launch: every job with items whose flag is set (dirty null: all) takes ceil(items / MPT_SUBDIV_CHUNK)
-// consecutive blocks, in job order, so a block lies in exactly one job (mpt_deform_plan_of's rule with another chunk).  A job that
-// sits a launch out -- fewer levels than the launch's -- has 0 items there.  Returns the number of runs; -1 for arguments that
-// name no launch.
-inline int mpt_subdiv_plan_of(const int32_t *items, const int32_t *dirty, int njobs, int32_t *run_job, int64_t *run_block, int cap,
-                              int64_t *blocks) {
-    if (njobs < 0 || (njobs > 0 && !items)) return -1;
-    int nr = 0;
-    long long at = 0;
-    for (int o = 0; o < njobs; o++) {
-        if (items[o] < 0) return -1;
-        if (items[o] == 0 || (dirty && !dirty[o])) continue;
-        if (nr < cap) {
-            if (run_job) run_job[nr] = o;
-            if (run_block) run_block[nr] = at;
-        }
-        nr++;
-        at += ((long long)items[o] + MPT_SUBDIV_CHUNK - 1) / MPT_SUBDIV_CHUNK;
-    }
-    if (at > 0x7fffffffLL) return -1;
-    if (blocks) *blocks = at;
-    return nr;
-}
 
 enum MptSubdivVerdict {
     MPT_SUBDIV_OK = 0, MPT_SUBDIV_ARGS, MPT_SUBDIV_LEVELS, MPT_SUBDIV_TOO_MANY, MPT_SUBDIV_NOT_FINITE, MPT_SUBDIV_DEGENERATE,

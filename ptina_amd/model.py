@@ -186,13 +186,17 @@ class ModelPool(metaclass=Singleton):
             raise ValueError('joint matrices must be [njoints,4,4], got shape %s' % (m.shape,))
         ctx().call('mpt_object_set_joints', obj, m.ctypes.data_as(C.POINTER(C.c_double)), int(m.shape[0]))
 
+    def _copy_to_numpy(self, symbol, obj, faces_of):
+        '''the read-back of an object's derived copy in the pool: [3 faces_of(its mesh), 8] f32'''
+        obj = self._object(obj)
+        k = faces_of(self._obj_mesh[obj])
+        arr = np.empty((k * 3, 8), np.float32)
+        ctx().call(symbol, obj, fptr(arr), k)
+        return arr
+
     def deformed_to_numpy(self, obj):
         '''the deformed copy of a deformable object as the last compose() wrote it: [3k,8] f32 records in object space'''
-        obj = self._object(obj)
-        k = self._mesh_faces[self._obj_mesh[obj]]
-        arr = np.empty((k * 3, 8), np.float32)
-        ctx().call('mpt_get_deformed', obj, fptr(arr), k)
-        return arr
+        return self._copy_to_numpy('mpt_get_deformed', obj, lambda mesh: self._mesh_faces[mesh])
 
     def deform_stats(self):
         '''_lib.DeformInfo: deformable objects, objects and corners the last compose() deformed, pool vertices the copies hold'''
@@ -224,11 +228,7 @@ class ModelPool(metaclass=Singleton):
     def subdivided_to_numpy(self, obj):
         '''the subdivided copy of an object of a subdivided mesh as the last compose() wrote it: [3 k 4^levels, 8] f32 records in
         object space'''
-        obj = self._object(obj)
-        k = self._object_faces(self._obj_mesh[obj])
-        arr = np.empty((k * 3, 8), np.float32)
-        ctx().call('mpt_get_subdivided', obj, fptr(arr), k)
-        return arr
+        return self._copy_to_numpy('mpt_get_subdivided', obj, self._object_faces)
 
     def subdiv_stats(self):
         '''_lib.SubdivInfo: objects of subdivided meshes, copies, copies and faces the last compose() refined, pool vertices the

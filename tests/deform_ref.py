@@ -55,7 +55,7 @@ def split(rec):
 
 
 def plan(corners, dirty=None, chunk=1024):
-    '''mpt_deform_plan restated: ([(object, first block), ...], blocks)'''
+    '''mpt_deform_plan restated (csrc/run_table.h's rule; subdiv_ref.plan passes its chunk): ([(object, first block), ...], blocks)'''
     runs, at = [], 0
     for o, k in enumerate(corners):
         if k == 0 or (dirty is not None and not dirty[o]):

@@ -16,6 +16,8 @@ import functools
 
 import numpy as np
 
+import deform_ref
+
 VERT_INT, VERT_BND, EDGE_INT, EDGE_BND = 0, 1, 2, 3
 CHUNK = 256
 
@@ -188,14 +190,8 @@ def subdivide(rec, levels, topo=None, control=None):
 
 
 def plan(items, dirty=None, chunk=CHUNK):
-    '''mpt_subdiv_plan restated: ([(job, first block), ...], blocks)'''
-    runs, at = [], 0
-    for o, k in enumerate(items):
-        if k == 0 or (dirty is not None and not dirty[o]):
-            continue
-        runs.append((o, at))
-        at += -(-int(k) // chunk)
-    return runs, at
+    '''mpt_subdiv_plan restated: ([(job, first block), ...], blocks) -- deform_ref.plan's rule with this chunk'''
+    return deform_ref.plan(items, dirty, chunk)
 
 
 # ---------------------------------------------------------------- fixtures

@@ -1,14 +1,13 @@
-// subdiv_rule_check.cpp -- the pure host pieces of Loop subdivision (ptina_amd/csrc/subdiv_rule.h: the topology of a mesh and its
-// refinements, and the run table of a launch) exercised by a stand-alone program, so that they can run under the host sanitizers
-// without a GPU and without loading anything into an interpreter:
+// subdiv_rule_check.cpp -- the pure host piece of Loop subdivision (ptina_amd/csrc/subdiv_rule.h: the topology of a mesh and its
+// refinements; the run table of a launch is tools/run_table_check.cpp's) exercised by a stand-alone program, so that it can run
+// under the host sanitizers without a GPU and without loading anything into an interpreter:
 //
 //     c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/subdiv_rule_check.cpp -o subdiv_rule_check && ./subdiv_rule_check
 //
 // Every fixture topology of tests/subdiv_ref.py (built here procedurally: triangle, pair, tetrahedron, octahedron, icosahedron,
 // closed fans of valence 7 and 12, the open 5 x 5 grid, the open cylinder) at levels 1 to 4, from record arrays that are exactly as
 // long as the function may read: counts (Euler's number on the closed ones, four faces per face), every id of every table inside
-// its level, every ring inside the block; every refusal, with message buffers of every size (cut, terminated, never overrun); the
-// plan over layouts with jobs that sit out, with output tables of every capacity from none to ample (never written past `cap`).
+// its level, every ring inside the block; every refusal, with message buffers of every size (cut, terminated, never overrun).
 
 #include "../ptina_amd/csrc/subdiv_rule.h"
 #include <cstdlib>
@@ -17,12 +16,6 @@
 
 static int failures = 0;
 #define CHECK(x) do { if (!(x)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #x); failures++; } } while (0)
-
-static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
-static unsigned rnd(unsigned n) {
-    rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-    return (unsigned)(rng_state >> 33) % n;
-}
 
 struct Mesh { std::string name; std::vector<float> v; std::vector<int> f; bool closed; };
 
@@ -186,42 +179,6 @@ int main() {
         CHECK(mpt_subdiv_topology_of(one, 20000, 5, t, nullptr, 0) == MPT_SUBDIV_TOO_MANY);      // refused before anything is read
     }
 
-    const int C = MPT_SUBDIV_CHUNK;
-    const int sizes[] = { 0, 1, 63, C - 1, C, C + 1, 2 * C, 9600, 5 * C + 21 };
-    int plans = 0;
-    for (int round = 0; round < 400; round++) {
-        const int n = (int)rnd(9);
-        std::vector<int32_t> items((size_t)n), dirty((size_t)n);
-        for (int o = 0; o < n; o++) { items[o] = sizes[rnd(sizeof sizes / sizeof *sizes)]; dirty[o] = (int32_t)rnd(2); }
-        const bool flags = rnd(3) != 0;
-        std::vector<int32_t> want_job; std::vector<int64_t> want_block;
-        int64_t at = 0;
-        for (int o = 0; o < n; o++) {
-            if (items[o] == 0 || (flags && !dirty[o])) continue;
-            want_job.push_back(o); want_block.push_back(at);
-            at += (items[o] + C - 1) / C;
-        }
-        for (int cap = 0; cap <= n + 1; cap++) {
-            std::vector<int32_t> run_job((size_t)cap, -7); std::vector<int64_t> run_block((size_t)cap, -7);
-            int64_t blocks = -1;
-            const int nr = mpt_subdiv_plan_of(n ? items.data() : nullptr, flags ? dirty.data() : nullptr, n, cap ? run_job.data() : nullptr,
-                                              cap ? run_block.data() : nullptr, cap, &blocks);
-            plans++;
-            CHECK(nr == (int)want_job.size() && blocks == at);
-            for (int r = 0; r < cap; r++) {
-                if (r < nr) CHECK(run_job[r] == want_job[r] && run_block[r] == want_block[r]);
-                else CHECK(run_job[r] == -7 && run_block[r] == -7);
-            }
-        }
-    }
-    {
-        const int32_t neg[2] = { 5, -1 };
-        CHECK(mpt_subdiv_plan_of(neg, nullptr, 2, nullptr, nullptr, 0, nullptr) == -1);
-        CHECK(mpt_subdiv_plan_of(nullptr, nullptr, 1, nullptr, nullptr, 0, nullptr) == -1);
-        CHECK(mpt_subdiv_plan_of(nullptr, nullptr, -1, nullptr, nullptr, 0, nullptr) == -1);
-        std::vector<int32_t> huge(300, 2147483647);                       // 300 x 2^23 blocks: past 31 bits
-        CHECK(mpt_subdiv_plan_of(huge.data(), nullptr, (int)huge.size(), nullptr, nullptr, 0, nullptr) == -1);
-    }
-    std::printf("subdiv_rule_check: %d topologies, %d refusals, %d plans, %d failures\n", topologies, refusals, plans, failures);
+    std::printf("subdiv_rule_check: %d topologies, %d refusals, %d failures\n", topologies, refusals, failures);
     return failures ? EXIT_FAILURE : EXIT_SUCCESS;
 }
