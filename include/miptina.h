@@ -661,6 +661,57 @@ int mpt_subdiv_topology(const float *verts /* [3k][8] */, int k, int levels, int
                         int64_t cap_words, int64_t *need_words, char *why, int why_size);
 int mpt_subdiv_plan(const int32_t *items, const int32_t *dirty, int njobs, int32_t *run_job, int64_t *run_block, int cap, int64_t *blocks);
 
+/* Texture displacement on the device as a property of a SUBDIVIDED mesh of the pool: the third step of the modifier stack armature ->
+ * subdivision surface -> displace.  mpt_compose evaluates it on the vertices of the mesh's last level, behind the last refine launch
+ * and before the normals, so the subdivided copy's normals are the displaced surface's.  Topology and face count stay constant: a
+ * change of strength costs one vertex kernel, the normals, the records, the partial mpt_compose and mpt_refit_tree.
+ * The definition.  All arithmetic is f64, every sum and product in the order written, without contraction; a value is rounded to
+ * f32 once, when a record is written.
+ *   Vertex uv: the FIRST CORNER of a last-level vertex i is the lowest index 3 g + c into the last level's face table with
+ *     F[g][c] == i.  The vertex's uv is that corner's face-varying uv by the texcoord rule above: from the control records (the mesh
+ *     or the object's deformed copy), down the base-4 digits of g, midpoints 0.5 * (u_i + u_j), unrounded.  The first corner to
+ *     touch a vertex speaks for it (Blender's Displace modifier with UV coordinates; the weld rule above): a uv seam cannot crack
+ *     the surface.
+ *   Height: the image [nx][ny] holds f32 rgba texels at base + x * ny + y, x and y wrapped by Python's modulo (the reference's
+ *     Image.subscript and Image.__call__, ptina/image.py:137-148).  px = u * (nx - 1), py = v * (ny - 1); fx = floor(px),
+ *     fy = floor(py), the integer parts 64-bit; x0 = px - fx, x1 = py - fy, y0 = 1 - x0, y1 = 1 - x1; per channel
+ *     t = (((t11 * x0) * x1 + (t10 * x0) * y1) + (t00 * y0) * y1) + (t01 * y0) * x1 with the texels widened to f64, t11 the texel
+ *     at (fx + 1, fy + 1), t10 at (fx + 1, fy), t00 at (fx, fy), t01 at (fx, fy + 1).  Channel 0 to 3 picks r, g, b or a; channel
+ *     4 is ((r + g) + b) / 3.0.
+ *   MPT_DISPLACE_NORMAL: p' = p + (strength * (h - midlevel)) * n, n = N / sqrt((Nx Nx + Ny Ny) + Nz Nz) the unrounded smooth
+ *     normal of the UNDISPLACED last level by the normal rule above.  A zero N gives a NaN position, as it gives a NaN normal.
+ *   MPT_DISPLACE_VECTOR: p' = p + strength * ((r, g, b) - midlevel), component by component in object space; channel is ignored.
+ *   The copy's normals are the normal rule evaluated on p'.  Texcoords are untouched.
+ * mpt_mesh_set_displacement: once per mesh, after mpt_mesh_set_subdivision and before the mesh has an object; before or after its
+ *   targets and skin.  The image need not be loaded yet.  Refuses: an unknown mesh; a mesh without a subdivision level
+ *   ("displacement needs a subdivided mesh"); a mesh that already has an object or a displacement; a mode or a channel outside the
+ *   enums; image_id < 0; a strength or midlevel that is not finite; a corner uv of the mesh that is not finite or exceeds 2^20 in
+ *   magnitude, naming the corner (midpoints of admitted uvs are admitted, and px stays far inside 64-bit integers).
+ * mpt_mesh_set_displacement_params: any time.  Every copy of the mesh is displaced again by the next mpt_compose and every object of
+ *   the mesh composed again (the objects of a rigid mesh share one copy).
+ * mpt_compose displaces a displaced copy again with the copies it subdivides again (a relayout, a pose change), after
+ *   mpt_mesh_set_displacement_params, and when mpt_load_image or mpt_reset_images ran since it was last displaced (they bump an
+ *   image generation).  Before anything else it checks that the image of every copy it will displace is loaded: if not it fails,
+ *   naming mesh and image, and leaves the scene as it was; it succeeds once the image is there.  One displacement launch whatever
+ *   the number of copies: L_max + 3 kernels with a displaced copy among those written, L_max + 2 without.
+ * mpt_displace_stats: displaced meshes; copies of displaced meshes; copies and vertices the last mpt_compose displaced; the image
+ *   generation.
+ * mpt_displace_kernel_time: HIP-event time (ms) of the displacement launches of the mpt_compose calls since the last call (may be
+ *   NULL) and their number.  mpt_subdiv_kernel_time counts its own three kinds of launch only.
+ * mpt_displace_corners: the first-corner table as a pure function (no context, no GPU) of faces [nfaces][3] over nverts vertices:
+ *   corner[nverts].  Returns 0, or 1 for arguments that name no table, 2 for an id outside [0, nverts), 3 for a vertex no face
+ *   touches. */
+enum { MPT_DISPLACE_NORMAL = 0, MPT_DISPLACE_VECTOR = 1 };
+enum { MPT_DISPLACE_R = 0, MPT_DISPLACE_G = 1, MPT_DISPLACE_B = 2, MPT_DISPLACE_A = 3, MPT_DISPLACE_MEAN = 4 };
+typedef struct {
+    int64_t displaced_meshes, copies, displaced_copies, displaced_verts, image_generation;
+} mpt_displace_info;
+int mpt_mesh_set_displacement(mpt_ctx *ctx, int mesh_id, int image_id, int mode, int channel, double strength, double midlevel);
+int mpt_mesh_set_displacement_params(mpt_ctx *ctx, int mesh_id, double strength, double midlevel);
+int mpt_displace_stats(mpt_ctx *ctx, mpt_displace_info *out);
+int mpt_displace_kernel_time(mpt_ctx *ctx, double *displace_ms, int *launches);
+int mpt_displace_corners(const int32_t *faces /* [nfaces][3] */, int64_t nfaces, int32_t nverts, int32_t *corner /* [nverts] */);
+
 /* Refit: after the model's faces moved (mpt_compose after mpt_object_set_world, or mpt_load_model of as many faces), keep the trees
  * of the last mpt_build_tree and fit their boxes to the model again, on the device -- what a viewport does for a moved object instead of
  * building (the reference's add-on builds: blender.py:555-571).

@@ -94,6 +94,12 @@ class SubdivInfo(C.Structure):
                 ('copy_verts', C.c_int64)]
 
 
+class DisplaceInfo(C.Structure):
+    '''mpt_displace_info (include/miptina.h): what mpt_displace_stats hands back'''
+    _fields_ = [('displaced_meshes', C.c_int64), ('copies', C.c_int64), ('displaced_copies', C.c_int64), ('displaced_verts', C.c_int64),
+                ('image_generation', C.c_int64)]
+
+
 class RefitInfo(C.Structure):
     '''mpt_refit_info (include/miptina.h): what mpt_refit_stats hands back'''
     _fields_ = [('faces', C.c_int64), ('wide_nodes', C.c_int64), ('refits', C.c_int64), ('host_fetches', C.c_int64), ('allowed', C.c_int64),
@@ -265,6 +271,11 @@ SIGNATURES = {
     'mpt_subdiv_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     'mpt_subdiv_topology': (_i, [_fp, _i, _i, C.POINTER(C.c_int64), _ip, _ip, C.c_int64, C.POINTER(C.c_int64), C.c_char_p, _i]),
     'mpt_subdiv_plan': (_i, [_ip, _ip, _i, _ip, C.POINTER(C.c_int64), _i, C.POINTER(C.c_int64)]),
+    'mpt_mesh_set_displacement': (_i, [_vp, _i, _i, _i, _i, C.c_double, C.c_double]),
+    'mpt_mesh_set_displacement_params': (_i, [_vp, _i, C.c_double, C.c_double]),
+    'mpt_displace_stats': (_i, [_vp, C.POINTER(DisplaceInfo)]),
+    'mpt_displace_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_displace_corners': (_i, [_ip, C.c_int64, C.c_int32, _ip]),
     'mpt_refit_tree': (_i, [_vp]),
     'mpt_refit_stats': (_i, [_vp, C.POINTER(RefitInfo)]),
     'mpt_refit_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
@@ -491,6 +502,20 @@ def subdiv_topology(rec, levels):
     return 0, '', dict(counts=counts, first_corner=w[:int(counts[0, 0])].copy(),
                        rules={l: rules(int(off[l]), int(counts[l, 0])) for l in range(1, levels + 1)},
                        rings=rules(int(off[6]), int(counts[levels, 0])), faces=w[int(off[7]):int(off[7]) + 3 * nf].reshape(nf, 3).copy())
+
+
+DISPLACE_MODES = ('normal', 'vector')                                    # include/miptina.h MPT_DISPLACE_NORMAL, _VECTOR
+DISPLACE_CHANNELS = ('r', 'g', 'b', 'a', 'mean')                         # ... MPT_DISPLACE_R .. MPT_DISPLACE_MEAN
+DISPLACE_MAX_UV = 2.0 ** 20                                              # csrc/displace_rule.h MPT_DISPLACE_MAX_UV
+
+
+def displace_corners(faces, nverts):
+    '''mpt_displace_corners (no context, no GPU): (verdict, corner [nverts]) of faces [F,3] -- per vertex the lowest index 3 g + c
+    with faces[g][c] the vertex; verdict 0 accepts, 2 names an id out of range, 3 a vertex no face touches'''
+    f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    corner = np.zeros(max(int(nverts), 1), np.int32)
+    rc = load_library().mpt_displace_corners(iptr(f), f.shape[0], int(nverts), iptr(corner))
+    return rc, corner[:max(int(nverts), 0)]
 
 
 def devices_isolated():

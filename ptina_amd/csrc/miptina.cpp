@@ -493,6 +493,7 @@ extern "C" int mpt_reset_images(mpt_ctx *c) {                                  /
     if (use(c)) return 1;
     c->h_images.clear();
     c->texels_used = 0;
+    c->image_gen++;
     return 0;
 }
 
@@ -506,6 +507,7 @@ extern "C" int mpt_load_image(mpt_ctx *c, const float *rgba, int nx, int ny, int
     MptImage im = { nx, ny, (int32_t)c->texels_used, 0 };
     c->h_images.push_back(im);
     c->texels_used += need;
+    c->image_gen++;
     HIP_TRY(hipMemcpyAsync(c->images, c->h_images.data(), c->h_images.size() * sizeof(MptImage),
                            hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

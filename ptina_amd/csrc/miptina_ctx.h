@@ -10,6 +10,7 @@
 #include "run_table.h"
 #include "deform_rule.h"
 #include "subdiv_rule.h"
+#include "displace_rule.h"
 #include "history_rule.h"
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
@@ -113,6 +114,9 @@ MPT_KERNEL_API hipError_t mpt_launch_subdiv_refine(const float *pool, const MptS
                                                    int level, const int32_t *topo, double *work, hipStream_t stream);
 MPT_KERNEL_API hipError_t mpt_launch_subdiv_normals(const MptSubdivJob *jobs, const MptRun *runs, int nruns, int blocks, const int32_t *topo,
                                                     double *work, hipStream_t stream);
+// displace.hip: the displaced positions of a launch's displaced jobs, between the last refine launch and the normals (mpt_compose)
+MPT_KERNEL_API hipError_t mpt_launch_displace(const float *pool, const MptSubdivJob *jobs, const MptDisplaceJob *djobs, const MptRun *runs, int nruns,
+                                              int blocks, const int32_t *topo, const MptVec4 *texels, double *work, hipStream_t stream);
 MPT_KERNEL_API hipError_t mpt_launch_subdiv_emit(float *pool, const MptSubdivJob *jobs, const MptRun *runs, int nruns, int blocks,
                                                  const int32_t *topo, const double *work, hipStream_t stream);
 
@@ -425,11 +429,12 @@ struct MPT_INTERNAL MptDeformBufs {
 // Loop subdivision's device memory (scene_subdiv.cpp): the arena of the meshes' topology blocks, appended by mpt_mesh_set_subdivision
 // (it grows by copying, as the mesh pool does), the jobs' f64 workspace and a launch's tables
 struct MPT_INTERNAL MptSubdivBufs {
-    DevBuf<int32_t> topo;                // every subdivided mesh's block of words (subdiv_rule.h), back to back
-    DevBuf<double> work;                 // per job: the positions of levels 1..L, then the last level's vertex records
+    DevBuf<int32_t> topo;                // every subdivided mesh's block of words (subdiv_rule.h), back to back; a displaced mesh's first-corner table (displace_rule.h) is a block of its own behind them
+    DevBuf<double> work;                 // per job: the positions of levels 1..L, then the last level's vertex records, then a displaced copy's displaced positions
     DevBuf<MptSubdivJob> jobs;           // a compose's jobs
-    DevBuf<MptRun> runs;                 // ... and the runs of its launches, (MPT_SUBDIV_MAX_LEVELS + 2) tables of up to a run per job
-    int reserve_tables(size_t njobs) { return jobs.reserve(njobs) || runs.reserve(njobs * (MPT_SUBDIV_MAX_LEVELS + 2)); }
+    DevBuf<MptDisplaceJob> djobs;        // ... the displacement of each (rows of copies without one are not read)
+    DevBuf<MptRun> runs;                 // ... and the runs of its launches, (MPT_SUBDIV_MAX_LEVELS + 3) tables of up to a run per job
+    int reserve_tables(size_t njobs) { return jobs.reserve(njobs) || djobs.reserve(njobs) || runs.reserve(njobs * (MPT_SUBDIV_MAX_LEVELS + 3)); }
 };
 
 struct MPT_INTERNAL MptLbvhBufs {          // workspace and result of the device LBVH build (lbvh_build.hip)
@@ -664,6 +669,7 @@ struct mpt_ctx {
     std::vector<MptImage> h_images;
     DevBuf<MptVec4> texels;
     size_t texels_used = 0;
+    unsigned long long image_gen = 1;    // counts mpt_load_image and mpt_reset_images: a displaced copy is displaced again when it moved (scene_subdiv.cpp)
     DevBuf<MptLight> lights;
     std::vector<MptLight> h_lights;
     float world_fac[4] = { 0.1f, 0.1f, 0.1f, 0.1f };   // light/world.py:14-16
@@ -758,11 +764,17 @@ struct mpt_ctx {
         int64_t nv[MPT_SUBDIV_MAX_LEVELS + 1] = {};
         int32_t rule_at[MPT_SUBDIV_MAX_LEVELS + 1] = {}, nrule_at = 0, face_at = 0;
         int job = -1;                                    // the shared copy of a mesh that is not deformable (-1: no object yet)
+        // its texture displacement (mpt_mesh_set_displacement)
+        bool displaced = false;
+        int image = -1, mode = 0, channel = 0;           // the image of the image pool, MPT_DISPLACE_NORMAL / _VECTOR, MPT_DISPLACE_R .. _MEAN
+        double strength = 0.0, midlevel = 0.0;
+        size_t corner_at = 0;                            // the first-corner table of its last level: first word in bufs.topo
     };
     struct MptSubdivCopy {                               // a subdivided copy: of a mesh that is not deformable, or of one object of a mesh that is
         int mesh = 0, obj = -1;                          // obj -1: shared by the mesh's objects
         long long copy_vert = -1; size_t work_at = 0;    // where the copy and its workspace lie (copy_vert -1: no room assigned yet)
-        bool dirty = true;                               // the control records changed since the copy was written
+        bool dirty = true;                               // the control records or the displacement's parameters changed since the copy was written
+        unsigned long long image_gen = 0;                // a displaced copy: the image generation it was last displaced at (0: never)
     };
     struct MPT_INTERNAL Subdiv {                         // Loop subdivision (scene_subdiv.cpp: mpt_mesh_set_subdivision, subdiv_step)
         std::vector<MptSubdivMesh> meshes;               // per mesh of the pool
@@ -776,7 +788,12 @@ struct mpt_ctx {
         mpt_subdiv_info stats{};
         int launches = 0;                                // kernels launched since mpt_subdiv_kernel_time last asked
         MptLaunchTimer refine_timer, normal_timer, emit_timer;   // mpt_compose: {before, after} the refine launches, the normals, the records
-        explicit Subdiv(MptEventPool &ev) : refine_timer(2, ev), normal_timer(2, ev), emit_timer(2, ev) {}
+        // texture displacement of the copies
+        std::vector<MptDisplaceJob> h_djobs;             // as h_jobs
+        int64_t displaced_copies = 0, displaced_verts = 0;   // what the last mpt_compose displaced
+        int displace_launches = 0;                       // displacement launches since mpt_displace_kernel_time last asked
+        MptLaunchTimer displace_timer;                   // mpt_compose: {before, after} the displacement launch
+        explicit Subdiv(MptEventPool &ev) : refine_timer(2, ev), normal_timer(2, ev), emit_timer(2, ev), displace_timer(2, ev) {}
     } subdiv{events};
     struct MPT_INTERNAL Refit {                          // mpt_refit_tree (tree_refit.cpp, refit_rule.h)
         int topo = MPT_TOPO_NONE;                        // MptTopoState: do the node records hold a topology, and if not, why not
@@ -939,6 +956,7 @@ MPT_INTERNAL int subdiv_object_faces(const mpt_ctx *c, int mesh_id);   // the fa
 MPT_INTERNAL void subdiv_object_added(mpt_ctx *c, int mesh_id);
 MPT_INTERNAL void subdiv_pose_changed(mpt_ctx *c, int obj_id);   // mpt_object_set_morph_weights / mpt_object_set_joints
 MPT_INTERNAL void subdiv_scene_cleared(mpt_ctx *c, int meshes);
+MPT_INTERNAL int subdiv_images_ready(mpt_ctx *c);                // before deform_step: a displaced copy that will be displaced has its image loaded, else mpt_compose refuses and changes nothing
 MPT_INTERNAL int subdiv_step(mpt_ctx *c);                        // behind deform_step: room, the launches; rewrites objs' mesh_vert at a relayout
 
 // film_read.cpp

@@ -268,8 +268,19 @@ struct MptSubdivJob {                       // 128 bytes
     int64_t work_at;                         // the job's workspace: first double (even)
     int32_t nv[MPT_SUBDIV_MAX_LEVELS + 1];   // vertices of level 0..L
     int32_t rule_at[MPT_SUBDIV_MAX_LEVELS + 1];   // words from topo_at: [l] the rules of level l's vertices ([0]: the first corners)
-    int32_t pos_at[MPT_SUBDIV_MAX_LEVELS + 1];    // doubles from work_at: [l] the positions [V_l][3] of level l ([0] unused: level 0 is read from the pool)
+    int32_t pos_at[MPT_SUBDIV_MAX_LEVELS + 1];    // doubles from work_at: [l] the positions [V_l][3] of level l ([0]: level 0 is read from the pool; a displaced copy's displaced positions [V_L][3])
     int32_t nrule_at, face_at;               // words from topo_at: the last level's rings, its faces' vertex ids
     int32_t vrec_at;                         // doubles from work_at (even): the last level's vertex records, 32 bytes each: pos3 nrm3 as f32, 8 bytes unused
-    int32_t pad[3];
+    int32_t npos_at;                         // doubles from work_at: the positions the normals are taken of -- pos_at[L], or pos_at[0] of a displaced copy
+    int32_t pad[2];
+};
+
+// Texture displacement of a subdivided copy (displace.hip): the row of the displacement launch's table beside the copy's MptSubdivJob
+// (same index) -- the image as the host knows it, the first-corner table of the mesh's last level and the parameters
+struct MptDisplaceJob {                     // 48 bytes
+    int32_t mode, channel;                   // MPT_DISPLACE_NORMAL / _VECTOR, MPT_DISPLACE_R .. _MEAN of include/miptina.h
+    int32_t nx, ny;                          // the image [nx][ny] ...
+    int64_t texel_at;                        // ... its first texel in the arena of rgba f32 texels
+    int64_t corner_at;                       // first word in the arena of topology words: [V_L] the first corner 3 g + c of every last-level vertex
+    double strength, midlevel;
 };

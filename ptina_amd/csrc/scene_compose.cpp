@@ -144,6 +144,7 @@ extern "C" int mpt_compose(mpt_ctx *c) {
     long long total = 0;
     for (int o = 0; o < nobj; o++) { faces[o] = cp.objs[o].nfaces; total += faces[o]; }
     if (total >= c->caps.max_faces) return fail("too many faces");            // model.py:84
+    if (subdiv_images_ready(c)) return 1;             // (a displaced copy whose image is not loaded: nothing has changed yet)
     const int n = (int)total, nverts = n * 3;
     HIP_TRY(hipStreamSynchronize(c->stream));
     bool replaced = false;

@@ -2,6 +2,9 @@
 // device (subdiv_rule.h makes them, a pure function), the table of subdivided copies beside scene_compose.cpp's object table and
 // scene_deform.cpp's poses, the run tables of a compose's launches (mpt_subdiv_plan: run_table.h's rule), and subdiv_step: the part of
 // mpt_compose behind deform_step that gives the copies their room in the pool and launches subdiv.hip before compose_kernel.
+// Texture displacement of the copies lives here too: mpt_mesh_set_displacement and its first-corner table
+// (displace_rule.h makes it, a pure function), and displace.hip's launch inside subdiv_step, between the last refine level and the
+// normals.
 
 #include "miptina_ctx.h"
 
@@ -100,8 +103,75 @@ extern "C" int mpt_mesh_set_subdivision(mpt_ctx *c, int mesh_id, int levels) {
     return 0;
 }
 
+// ---------------------------------------------------------------- the meshes' displacements
+extern "C" int mpt_displace_corners(const int32_t *faces, int64_t nfaces, int32_t nverts, int32_t *corner) {
+    return mpt_displace_corners_of(faces, nfaces, nverts, corner);
+}
+
+static int check_displace_params(const char *who, double strength, double midlevel) {
+    if (!std::isfinite(strength)) return fail("%s: strength is not finite", who);
+    if (!std::isfinite(midlevel)) return fail("%s: midlevel is not finite", who);
+    return 0;
+}
+
+extern "C" int mpt_mesh_set_displacement(mpt_ctx *c, int mesh_id, int image_id, int mode, int channel, double strength, double midlevel) {
+    if (use(c)) return 1;
+    const char *who = "mpt_mesh_set_displacement";
+    auto &sd = c->subdiv;
+    auto &cp = c->compose;
+    if (mesh_id < 0 || (size_t)mesh_id >= cp.meshes.size()) return fail("%s: unknown mesh %d (%zu meshes)", who, mesh_id, cp.meshes.size());
+    sd.meshes.resize(cp.meshes.size());
+    auto &m = sd.meshes[mesh_id];
+    if (m.levels == 0) return fail("%s: displacement needs a subdivided mesh: mesh %d has no subdivision level", who, mesh_id);
+    if (check_fresh_mesh(c, mesh_id, who)) return 1;
+    if (m.displaced) return fail("%s: mesh %d already has a displacement", who, mesh_id);
+    if (mode != MPT_DISPLACE_NORMAL && mode != MPT_DISPLACE_VECTOR) return fail("%s: mode %d outside [0, 1]", who, mode);
+    if (channel < MPT_DISPLACE_R || channel > MPT_DISPLACE_MEAN) return fail("%s: channel %d outside [0, 4]", who, channel);
+    if (image_id < 0) return fail("%s: image id %d is negative", who, image_id);
+    if (check_displace_params(who, strength, midlevel)) return 1;
+    const int k = cp.meshes[mesh_id].nfaces;
+    const int64_t nf = (int64_t)k << (2 * m.levels), nv = m.nv[m.levels];
+    std::vector<float> rec((size_t)k * 24);
+    std::vector<int32_t> faces((size_t)nf * 3), corner((size_t)nv);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (k > 0) {
+        HIP_TRY(hipMemcpy(rec.data(), cp.bufs.pool + cp.meshes[mesh_id].vert * 8, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(faces.data(), sd.bufs.topo + m.topo_at + (size_t)m.face_at, faces.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    char why[200];
+    if (mpt_displace_uv_check_of(rec.data(), k, why, sizeof why)) return fail("%s: mesh %d: %s", who, mesh_id, why);
+    if (mpt_displace_corners_of(faces.data(), nf, (int32_t)nv, corner.data())) return fail("%s: mesh %d: its topology names no first corner for every vertex", who, mesh_id);
+    if (grow_keeping(sd.bufs.topo, sd.topo_used + corner.size(), sd.topo_used, c->stream)) return 1;
+    if (nv > 0) {
+        HIP_TRY(hipMemcpyAsync(sd.bufs.topo + sd.topo_used, corner.data(), corner.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    m.displaced = true; m.image = image_id; m.mode = mode; m.channel = channel; m.strength = strength; m.midlevel = midlevel;
+    m.corner_at = sd.topo_used;
+    sd.topo_used += corner.size();
+    return 0;
+}
+
+extern "C" int mpt_mesh_set_displacement_params(mpt_ctx *c, int mesh_id, double strength, double midlevel) {
+    if (use(c)) return 1;
+    const char *who = "mpt_mesh_set_displacement_params";
+    auto &sd = c->subdiv;
+    if (mesh_id < 0 || (size_t)mesh_id >= c->compose.meshes.size()) return fail("%s: unknown mesh %d (%zu meshes)", who, mesh_id, c->compose.meshes.size());
+    if ((size_t)mesh_id >= sd.meshes.size() || !sd.meshes[mesh_id].displaced) return fail("%s: mesh %d has no displacement", who, mesh_id);
+    if (check_displace_params(who, strength, midlevel)) return 1;
+    sd.meshes[mesh_id].strength = strength; sd.meshes[mesh_id].midlevel = midlevel;
+    // every copy of the mesh is displaced again, and every object that reads one is composed again (a rigid mesh's share one copy)
+    for (size_t o = 0; o < sd.obj_copy.size(); o++) {
+        if (sd.obj_copy[o] < 0 || sd.copies[sd.obj_copy[o]].mesh != mesh_id) continue;
+        sd.copies[sd.obj_copy[o]].dirty = true;
+        c->compose.dirty[o] = 1;
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------- the step of mpt_compose
-// the doubles of a copy's workspace: the positions of levels 1..L (each level from an even offset), then the last level's records
+// the doubles of a copy's workspace: the positions of levels 1..L (each level from an even offset), then the last level's records,
+// then -- a displaced copy -- the displaced positions of the last level
 static size_t work_layout(const mpt_ctx::MptSubdivMesh &m, MptSubdivJob *job) {
     size_t at = 0;
     for (int l = 1; l <= m.levels; l++) {
@@ -109,7 +179,32 @@ static size_t work_layout(const mpt_ctx::MptSubdivMesh &m, MptSubdivJob *job) {
         at += ((size_t)m.nv[l] * 3 + 1) & ~(size_t)1;
     }
     if (job) job->vrec_at = (int32_t)at;
-    return at + (size_t)m.nv[m.levels] * 4;
+    at += (size_t)m.nv[m.levels] * 4;
+    if (job) job->npos_at = job->pos_at[m.levels];
+    if (!m.displaced) return at;
+    if (job) job->pos_at[0] = job->npos_at = (int32_t)at;
+    return at + (((size_t)m.nv[m.levels] * 3 + 1) & ~(size_t)1);
+}
+
+// does the next subdiv_step write this copy?  (`all`: a relayout writes every copy)
+static bool copy_is_dirty(const mpt_ctx *c, const mpt_ctx::MptSubdivCopy &p, bool all) {
+    return all || p.dirty || (c->subdiv.meshes[p.mesh].displaced && p.image_gen != c->image_gen);
+}
+
+// The first thing mpt_compose asks, before anything is queued or changed: the image of every displaced copy that the step below
+// will write is loaded.  (A copy it will not write was displaced at this image generation: its image is there.)
+int subdiv_images_ready(mpt_ctx *c) {
+    const auto &sd = c->subdiv;
+    const bool all = c->compose.relayout || sd.room.stale || c->deform.room.stale;
+    for (const auto &p : sd.copies) {
+        const auto &m = sd.meshes[p.mesh];
+        if (!m.displaced || m.nv[m.levels] == 0 || !copy_is_dirty(c, p, all)) continue;
+        if ((size_t)m.image >= c->h_images.size())
+            return fail("mpt_compose: the displacement of mesh %d reads image %d, and %zu images are loaded", p.mesh, m.image, c->h_images.size());
+        const MptImage &im = c->h_images[m.image];
+        if (im.nx < 1 || im.ny < 1) return fail("mpt_compose: the displacement of mesh %d reads image %d, which is empty (%d x %d)", p.mesh, m.image, im.nx, im.ny);
+    }
+    return 0;
 }
 
 // Called with deform_step's launch (if any) queued.  At a relayout (objects added or dropped, or the copies lost their room) the
@@ -121,6 +216,7 @@ int subdiv_step(mpt_ctx *c) {
     auto &sd = c->subdiv;
     auto &df = c->deform;
     sd.stats.refined_copies = sd.stats.refined_faces = 0;
+    sd.displaced_copies = sd.displaced_verts = 0;
     const int n = (int)sd.copies.size();
     if (n == 0) { sd.stats.copy_verts = 0; return 0; }
     const bool all = cp.relayout || sd.room.stale;
@@ -141,8 +237,10 @@ int subdiv_step(mpt_ctx *c) {
     sd.stats.copy_verts = (int64_t)sd.room.copy_verts;
     std::vector<MptSubdivJob> &jobs = sd.h_jobs;
     jobs.assign((size_t)n, MptSubdivJob{});
-    std::vector<int32_t> dirty((size_t)n);
-    int lmax = 0, ndirty = 0;
+    std::vector<MptDisplaceJob> &djobs = sd.h_djobs;
+    djobs.assign((size_t)n, MptDisplaceJob{});
+    std::vector<int32_t> dirty((size_t)n), displace((size_t)n);
+    int lmax = 0, ndirty = 0, ndisplaced = 0;
     for (int j = 0; j < n; j++) {
         const auto &p = sd.copies[j];
         const auto &m = sd.meshes[p.mesh];
@@ -154,27 +252,41 @@ int subdiv_step(mpt_ctx *c) {
         for (int l = 0; l <= m.levels; l++) { t.nv[l] = (int32_t)m.nv[l]; t.rule_at[l] = m.rule_at[l]; }
         t.nrule_at = m.nrule_at; t.face_at = m.face_at;
         work_layout(m, &t);
-        dirty[j] = all || p.dirty;
+        dirty[j] = copy_is_dirty(c, p, all);
         if (!dirty[j] || t.nfaces == 0) continue;
         ndirty++; lmax = std::max(lmax, m.levels);
         sd.stats.refined_copies++; sd.stats.refined_faces += t.nfaces;
+        if (!m.displaced) continue;
+        const MptImage &im = c->h_images[m.image];            // (loaded: subdiv_images_ready)
+        djobs[j] = { m.mode, m.channel, im.nx, im.ny, (int64_t)im.base, (int64_t)m.corner_at, m.strength, m.midlevel };
+        displace[j] = 1; ndisplaced++;
+        sd.displaced_copies++; sd.displaced_verts += t.nv[m.levels];
     }
-    for (auto &p : sd.copies) p.dirty = false;
+    // a copy displaced again because the images changed: the objects that read it are composed again
+    for (size_t o = 0; o < sd.obj_copy.size(); o++)
+        if (sd.obj_copy[o] >= 0 && displace[sd.obj_copy[o]]) cp.dirty[o] = 1;
+    for (int j = 0; j < n; j++) {
+        sd.copies[j].dirty = false;
+        if (displace[j]) sd.copies[j].image_gen = c->image_gen;
+    }
     if (ndirty == 0) return 0;
-    // the run tables: launch t = 0 .. lmax - 1 refines to level t + 1, then the normals, then the records
-    const int ntables = lmax + 2;
+    // the run tables: launch t = 0 .. lmax - 1 refines to level t + 1, then the normals, then the records; behind them the
+    // displacement's, over the displaced copies among the dirty ones (it is launched between the last refine level and the normals)
+    const int ntables = lmax + 2 + (ndisplaced ? 1 : 0);
     std::vector<MptRun> &runs = sd.h_runs;
     runs.assign((size_t)ntables * (size_t)n, MptRun{});
     std::vector<int> nruns((size_t)ntables), blocks((size_t)ntables);
     std::vector<int32_t> items((size_t)n);
     for (int t = 0; t < ntables; t++) {
         for (int j = 0; j < n; j++)
-            items[j] = t < lmax ? (jobs[j].levels > t ? jobs[j].nv[t + 1] : 0) : t == lmax ? jobs[j].nv[jobs[j].levels] : jobs[j].nfaces;
+            items[j] = t < lmax ? (jobs[j].levels > t ? jobs[j].nv[t + 1] : 0) : t == lmax ? jobs[j].nv[jobs[j].levels] : t == lmax + 1 ? jobs[j].nfaces
+                     : displace[j] ? jobs[j].nv[jobs[j].levels] : 0;
         nruns[t] = mpt_run_plan_into(items.data(), dirty.data(), n, MPT_SUBDIV_CHUNK, runs.data() + (size_t)t * (size_t)n, &blocks[t]);
         if (nruns[t] < 0) return fail("too many faces to subdivide");
     }
     HIP_TRY(hipMemcpyAsync(sd.bufs.jobs, jobs.data(), (size_t)n * sizeof(MptSubdivJob), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(sd.bufs.runs, runs.data(), runs.size() * sizeof(MptRun), hipMemcpyHostToDevice, c->stream));
+    if (ndisplaced) HIP_TRY(hipMemcpyAsync(sd.bufs.djobs, djobs.data(), (size_t)n * sizeof(MptDisplaceJob), hipMemcpyHostToDevice, c->stream));
     {
         MptTimedSpan span(sd.refine_timer, c->stream);
         HIP_TRY(span.begun);
@@ -183,6 +295,14 @@ int subdiv_step(mpt_ctx *c) {
                                              sd.bufs.work, c->stream));
             sd.launches++;
         }
+        HIP_TRY(span.end());
+    }
+    if (ndisplaced && nruns[lmax + 2] > 0) {
+        MptTimedSpan span(sd.displace_timer, c->stream);
+        HIP_TRY(span.begun);
+        HIP_TRY(mpt_launch_displace(cp.bufs.pool, sd.bufs.jobs, sd.bufs.djobs, sd.bufs.runs + (size_t)(lmax + 2) * (size_t)n, nruns[lmax + 2], blocks[lmax + 2],
+                                    sd.bufs.topo, c->texels, sd.bufs.work, c->stream));
+        sd.displace_launches++;
         HIP_TRY(span.end());
     }
     {
@@ -236,5 +356,28 @@ extern "C" int mpt_subdiv_kernel_time(mpt_ctx *c, double *refine_ms, double *nor
     if (records_ms) *records_ms = seg[2];
     if (launches) *launches = sd.launches;
     sd.launches = 0;
+    return 0;
+}
+
+extern "C" int mpt_displace_stats(mpt_ctx *c, mpt_displace_info *out) {
+    if (!c || !out) return fail("null argument");
+    const auto &sd = c->subdiv;
+    *out = mpt_displace_info{};
+    for (const auto &m : sd.meshes) out->displaced_meshes += m.displaced;
+    for (const auto &p : sd.copies) out->copies += sd.meshes[p.mesh].displaced;
+    out->displaced_copies = sd.displaced_copies;
+    out->displaced_verts = sd.displaced_verts;
+    out->image_generation = (int64_t)c->image_gen;
+    return 0;
+}
+
+extern "C" int mpt_displace_kernel_time(mpt_ctx *c, double *displace_ms, int *launches) {
+    if (use_ro(c)) return 1;
+    auto &sd = c->subdiv;
+    double ms = 0;
+    if (timer_readout(c, sd.displace_timer, &ms, nullptr, nullptr)) return 1;
+    if (displace_ms) *displace_ms = ms;
+    if (launches) *launches = sd.displace_launches;
+    sd.displace_launches = 0;
     return 0;
 }

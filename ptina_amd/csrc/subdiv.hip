@@ -35,7 +35,9 @@
 //                          below -- level 0 from the pool through the first-corner table, else 24-byte f64 records of the
 //                          workspace -- and writes one.
 //   subdiv_normal_kernel   the last level: a lane walks its vertex's ring and writes the vertex record (pos3 nrm3 as f32: the one
-//                          rounding), 32 bytes, two 16-byte stores.
+//                          rounding), 32 bytes, two 16-byte stores.  The positions are those the job points at (npos_at): the
+//                          last level's, or the displaced ones of a copy that carries a displacement (displace.hip, launched
+//                          between the last refine level and this kernel; section 3.20).
 //   subdiv_emit_kernel     a lane per refined face: three vertex ids, three 32-byte gathers (a vertex is shared by six corners, so
 //                          they hit in L2), the parent's three uvs and L midpoint steps, six 16-byte stores: 96 bytes.
 // Vector stores only, no atomics, no LDS.
@@ -45,14 +47,10 @@
 #include <math.h>
 #include "mpt_types.h"
 #include "run_table.h"
+#include "subdiv_walk.h"
 
 enum { SD_BLOCK = MPT_SUBDIV_CHUNK };
 static_assert(sizeof(MptSubdivJob) == 128, "the job record is 128 bytes");
-
-struct SdVec { double x, y, z; };
-static __device__ __forceinline__ SdVec sd_add(SdVec a, SdVec b) { return { a.x + b.x, a.y + b.y, a.z + b.z }; }
-static __device__ __forceinline__ SdVec sd_sub(SdVec a, SdVec b) { return { a.x - b.x, a.y - b.y, a.z - b.z }; }
-static __device__ __forceinline__ SdVec sd_mul(double s, SdVec a) { return { s * a.x, s * a.y, s * a.z }; }
 
 // the position of vertex v of the level below `level`
 static __device__ __forceinline__ SdVec sd_pos(const MptSubdivJob &o, int level, const float4 *pool, const int32_t *__restrict__ T,
@@ -106,26 +104,9 @@ __global__ __launch_bounds__(SD_BLOCK) void subdiv_normal_kernel(const MptSubdiv
     const int i = ((int)blockIdx.x - runs[r].block) * SD_BLOCK + (int)threadIdx.x;
     if (i >= o.nv[o.levels]) return;
     const int32_t *__restrict__ T = topo + o.topo_at;
-    const int32_t head = T[o.nrule_at + 2 * i], at = T[o.nrule_at + 2 * i + 1];
-    const int kind = head & 3, n = head >> 2;
-    const int32_t *__restrict__ ring = T + at;
-    const double *P = work_in + o.work_at + o.pos_at[o.levels];
-    const SdVec v = { P[(size_t)i * 3], P[(size_t)i * 3 + 1], P[(size_t)i * 3 + 2] };
-    const int nfaces = kind == MPT_SUBDIV_VERT_BND ? n - 1 : n;
-    SdVec N = { 0.0, 0.0, 0.0 };
-    const int32_t r0 = ring[0];
-    const SdVec A0 = sd_sub({ P[(size_t)r0 * 3], P[(size_t)r0 * 3 + 1], P[(size_t)r0 * 3 + 2] }, v);
-    SdVec A = A0;
-    for (int k = 0; k < nfaces; k++) {
-        SdVec B = A0;
-        if (k + 1 < n) {
-            const int32_t rb = ring[k + 1];
-            B = sd_sub({ P[(size_t)rb * 3], P[(size_t)rb * 3 + 1], P[(size_t)rb * 3 + 2] }, v);
-        }
-        const SdVec X = { A.y * B.z - A.z * B.y, A.z * B.x - A.x * B.z, A.x * B.y - A.y * B.x };
-        N = sd_add(N, X);
-        A = B;
-    }
+    const double *P = work_in + o.work_at + o.npos_at;       // (a displaced copy's normals are the displaced surface's: displace.hip)
+    const SdVec v = sd_at(P, i);
+    const SdVec N = sd_ring_normal(T, o.nrule_at, P, i, v);
     const double len = sqrt((N.x * N.x + N.y * N.y) + N.z * N.z);
     float4 *dst = (float4 *)(work_out + o.work_at + o.vrec_at) + (size_t)i * 2;
     dst[0] = make_float4((float)v.x, (float)v.y, (float)v.z, (float)(N.x / len));
@@ -145,19 +126,8 @@ __global__ __launch_bounds__(SD_BLOCK) void subdiv_emit_kernel(const float4 *poo
     const float4 a0 = vrec[(size_t)i0 * 2], a1 = vrec[(size_t)i0 * 2 + 1];
     const float4 b0 = vrec[(size_t)i1 * 2], b1 = vrec[(size_t)i1 * 2 + 1];
     const float4 c0 = vrec[(size_t)i2 * 2], c1 = vrec[(size_t)i2 * 2 + 1];
-    // the uvs: from the cage face g >> 2L down the digits of g in base 4, the most significant first
-    const size_t parent = ((size_t)o.src_vert + (size_t)(g >> (2 * o.levels)) * 3) * 2;
-    const float4 p0 = pool_in[parent + 1], p1 = pool_in[parent + 3], p2 = pool_in[parent + 5];
-    double u0 = p0.z, v0 = p0.w, u1 = p1.z, v1 = p1.w, u2 = p2.z, v2 = p2.w;
-    for (int s = o.levels - 1; s >= 0; s--) {
-        const int d = (g >> (2 * s)) & 3;
-        const double m01u = 0.5 * (u0 + u1), m01v = 0.5 * (v0 + v1), m12u = 0.5 * (u1 + u2), m12v = 0.5 * (v1 + v2);
-        const double m20u = 0.5 * (u2 + u0), m20v = 0.5 * (v2 + v0);
-        const double n0u = d == 0 ? u0 : d == 1 ? u1 : d == 2 ? u2 : m01u, n0v = d == 0 ? v0 : d == 1 ? v1 : d == 2 ? v2 : m01v;
-        const double n1u = d == 0 ? m01u : d == 1 ? m12u : d == 2 ? m20u : m12u, n1v = d == 0 ? m01v : d == 1 ? m12v : d == 2 ? m20v : m12v;
-        const double n2u = d == 0 ? m20u : d == 1 ? m01u : d == 2 ? m12u : m20u, n2v = d == 0 ? m20v : d == 1 ? m01v : d == 2 ? m12v : m20v;
-        u0 = n0u; v0 = n0v; u1 = n1u; v1 = n1v; u2 = n2u; v2 = n2v;
-    }
+    const SdFaceUv t = sd_face_uv(pool_in, o.src_vert, o.levels, g);
+    const double u0 = t.u0, v0 = t.v0, u1 = t.u1, v1 = t.v1, u2 = t.u2, v2 = t.v2;
     float4 *dst = pool_out + ((size_t)o.dst_vert + (size_t)g * 3) * 2;
     dst[0] = a0; dst[1] = make_float4(a1.x, a1.y, (float)u0, (float)v0);
     dst[2] = b0; dst[3] = make_float4(b1.x, b1.y, (float)u1, (float)v1);

@@ -4,14 +4,16 @@ BVHTree().build() packs it, leaf-ordered, into the device records (csrc/mpt_type
 load_meshes / add_mesh / add_object / compose, object-space meshes and an object table are kept on the device
 and composed there into the model the build reads (csrc/compose.hip); a mesh may carry morph
 targets and a skin, and its objects a pose each, deformed there too (csrc/deform.hip), and a Loop
-subdivision level, evaluated there behind the deformation (csrc/subdiv.hip).
+subdivision level, evaluated there behind the deformation (csrc/subdiv.hip), and a subdivided mesh a
+texture displacement behind that (csrc/displace.hip).
 '''
 
 import ctypes as C
 
 from .common import *                 # noqa: F401,F403
 from .common import Singleton, register, ctx, np
-from ._lib import fptr, iptr, ComposeInfo, DeformInfo, SubdivInfo, DEFORM_MAX_JOINTS, DEFORM_MAX_TARGETS, SUBDIV_MAX_LEVELS
+from ._lib import fptr, iptr, ComposeInfo, DeformInfo, SubdivInfo, DisplaceInfo, DEFORM_MAX_JOINTS, DEFORM_MAX_TARGETS, SUBDIV_MAX_LEVELS
+from ._lib import DISPLACE_MODES, DISPLACE_CHANNELS
 
 
 @register
@@ -24,6 +26,7 @@ class ModelPool(metaclass=Singleton):
         self._composed = False           # the model is the device's composition: to_numpy fetches it
         self._mesh_faces = []            # faces of every mesh of the device's pool
         self._mesh_levels = {}           # mesh -> its subdivision level, where it has one: an object of it has faces * 4^level
+        self._mesh_displace = {}         # mesh -> [strength, midlevel] of its displacement, where it has one
         self._obj_mesh = []              # the mesh of every object of the device's table
 
     @property
@@ -113,7 +116,7 @@ class ModelPool(metaclass=Singleton):
     def clear_meshes(self):
         '''drop the objects and the meshes'''
         ctx().call('mpt_scene_clear', 1)
-        self._obj_mesh, self._mesh_faces, self._mesh_levels = [], [], {}
+        self._obj_mesh, self._mesh_faces, self._mesh_levels, self._mesh_displace = [], [], {}, {}
 
     def compose(self):
         '''write the objects, in order, as the model BVHTree().build() reads -- on the device; what load(*compose_multiple_meshes(...))
@@ -225,9 +228,55 @@ class ModelPool(metaclass=Singleton):
         ctx().call('mpt_mesh_set_subdivision', mesh, levels)
         self._mesh_levels[mesh] = levels
 
+    # ---- texture displacement of a subdivided mesh on the device (csrc/displace.hip, DESIGN.md section 3.20: Blender's Displace
+    #      modifier with UV coordinates behind its subdivision surface; the reference's add-on is handed the evaluated mesh)
+    def add_displacement(self, mesh, image, strength=1.0, midlevel=0.5, mode='normal', channel='mean'):
+        '''a displacement for a subdivided mesh that has no object yet: the vertices of its last level move by image `image` of
+        ImagePool (it need not be loaded yet; compose() needs it), sampled bilinearly at the uv of the vertex's first corner --
+        mode 'normal': along the smooth normal by strength * (h - midlevel), h the channel 'r', 'g', 'b', 'a' or 'mean' (of r, g,
+        b); mode 'vector': by strength * (rgb - midlevel) in object space.  The copy's normals are the displaced surface's'''
+        mesh = self._fresh_mesh(mesh)
+        if mesh not in self._mesh_levels:
+            raise ValueError('displacement needs a subdivided mesh: mesh %d has no subdivision level' % mesh)
+        if mesh in self._mesh_displace:
+            raise ValueError('mesh %d already has a displacement' % mesh)
+        if mode not in DISPLACE_MODES:
+            raise ValueError('mode %r: one of %s' % (mode, ', '.join(DISPLACE_MODES)))
+        if channel not in DISPLACE_CHANNELS:
+            raise ValueError('channel %r: one of %s' % (channel, ', '.join(DISPLACE_CHANNELS)))
+        image = int(getattr(image, 'id', image))                        # (an image.Image, or its id)
+        if image < 0:
+            raise ValueError('image id %d is negative' % image)
+        strength, midlevel = self._displace_params(strength, midlevel)
+        ctx().call('mpt_mesh_set_displacement', mesh, image, DISPLACE_MODES.index(mode), DISPLACE_CHANNELS.index(channel), strength, midlevel)
+        self._mesh_displace[mesh] = [strength, midlevel]
+
+    @staticmethod
+    def _displace_params(strength, midlevel):
+        strength, midlevel = float(strength), float(midlevel)
+        if not (np.isfinite(strength) and np.isfinite(midlevel)):
+            raise ValueError('strength %r and midlevel %r must be finite' % (strength, midlevel))
+        return strength, midlevel
+
+    def set_displacement(self, mesh, strength, midlevel=None):
+        '''the strength (and the midlevel; None keeps it) of a displaced mesh, at any time; the next compose() displaces the copies
+        of this mesh again and rewrites its objects only'''
+        if int(mesh) not in self._mesh_displace:
+            raise ValueError('mesh %r has no displacement' % (mesh,))
+        mesh = int(mesh)
+        strength, midlevel = self._displace_params(strength, self._mesh_displace[mesh][1] if midlevel is None else midlevel)
+        ctx().call('mpt_mesh_set_displacement_params', mesh, strength, midlevel)
+        self._mesh_displace[mesh] = [strength, midlevel]
+
+    def displace_stats(self):
+        '''_lib.DisplaceInfo: displaced meshes, their copies, copies and vertices the last compose() displaced, the image generation'''
+        info = DisplaceInfo()
+        ctx().call('mpt_displace_stats', C.byref(info))
+        return info
+
     def subdivided_to_numpy(self, obj):
-        '''the subdivided copy of an object of a subdivided mesh as the last compose() wrote it: [3 k 4^levels, 8] f32 records in
-        object space'''
+        '''the subdivided copy of an object of a subdivided mesh as the last compose() wrote it -- displaced, if the mesh carries a
+        displacement: [3 k 4^levels, 8] f32 records in object space'''
         return self._copy_to_numpy('mpt_get_subdivided', obj, self._object_faces)
 
     def subdiv_stats(self):

@@ -29,6 +29,8 @@ _PASS_THROUGH = {
     'set_object_morph_weights': ('ModelPool', 'set_morph_weights', ('obj', 'w')),
     'set_object_joints': ('ModelPool', 'set_joints', ('obj', 'mats')),
     'set_mesh_subdivision': ('ModelPool', 'add_subdivision', ('mesh', 'levels')),
+    'set_mesh_displacement': ('ModelPool', 'add_displacement', ('mesh', 'image', ('strength', 1.0), ('midlevel', 0.5), ('mode', 'normal'), ('channel', 'mean'))),
+    'set_mesh_displacement_params': ('ModelPool', 'set_displacement', ('mesh', 'strength', ('midlevel', None))),
     'load_images': ('ImagePool', 'load', ('images',)),
     'load_materials': ('MaterialPool', 'load', ('materials',)),
     'build_tree': ('BVHTree', 'build', ()),
