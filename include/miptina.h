@@ -712,6 +712,85 @@ int mpt_displace_stats(mpt_ctx *ctx, mpt_displace_info *out);
 int mpt_displace_kernel_time(mpt_ctx *ctx, double *displace_ms, int *launches);
 int mpt_displace_corners(const int32_t *faces /* [nfaces][3] */, int64_t nfaces, int32_t nverts, int32_t *corner /* [nverts] */);
 
+/* Scatter: N instances of a mesh placed over a SURFACE object of the table on the device -- grass on a displaced terrain, rivets on a
+ * skinned character (Blender's "distribute points on faces" + "instance on points").  The instances are ordinary objects of the
+ * table with contiguous ids; their world matrices are written on the device, inside mpt_compose, and they are STICKY: an instance
+ * remembers the face and the barycentric point it was born on, so that when the surface is posed, displaced or moved again only the
+ * placement kernel runs again.  Instance and face counts stay constant: mpt_refit_tree refits.
+ * The definition.  All arithmetic is f64, every sum and product in the order written, without contraction.
+ *   Draws: mix(z) is SplitMix64's finaliser: z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *     z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31, all modulo 2^64.  draw(i, k) = mix(mix(seed) + 16 i + k);
+ *     unit(i, k) = ((draw(i, k) >> 11) + 0.5) * 2^-53.
+ *   World points: corner c of face g of the surface S is record 3 g + c of S's final object-space copy in the pool -- the mesh, or
+ *     its deformed / subdivided / displaced copy: what mpt_compose reads for S -- placed by S's world matrix W with the composition's
+ *     expressions for a position, ph = (p, 1) . W^T, P = ph.xyz / ph.w, NOT rounded to f32.
+ *   Weights: area(g) = 0.5 * |cross(P1 - P0, P2 - P0)|.  dens(g) = 1 without a density image; with one, its channel (the
+ *     displacement's codes) sampled at the mean ((u0 + u1) + u2) / 3.0 of the face's three corner uvs by the displacement's bilinear
+ *     rule, clamped to [0, 1], NaN counting as 0.  w(g) = area(g) * dens(g), 0 where that is not finite; wmax the largest;
+ *     q(g) = (uint32) floor(w(g) / wmax * 2^24): integer shares make the scan exact whatever its shape.  A face whose weight is below
+ *     2^-24 of the largest gets no instance.
+ *   Selection: cdf is the exclusive scan of q in 64 bits, T = cdf[F].  For instance i: t = draw(i, 0) mod T, g the largest face with
+ *     cdf[g] <= t; su = sqrt(unit(i, 1)), v = unit(i, 2), b1 = su * (1 - v), b2 = su * v, b0 = (1 - b1) - b2;
+ *     scale = smin + (smax - smin) * unit(i, 3).  Yaw is a unit vector without trigonometry: for j = 0..7, x = 2 unit(i, 4 + 2j) - 1,
+ *     y = 2 unit(i, 5 + 2j) - 1; the first pair with 2^-20 < x x + y y <= 1 gives (cy, sy) = (x, y) / sqrt(x x + y y); none, or
+ *     random_yaw off: (1, 0).  The sticky record of an instance is {g, b1, b2, scale, cy, sy}.
+ *   Placement: P = (b0 P0 + b1 P1) + b2 P2.  align MPT_SCATTER_ALIGN_NORMAL: N = cross(P1 - P0, P2 - P0) / its length, the geometric
+ *     normal of the face as it is now (a collapsed face gives NaN); MPT_SCATTER_ALIGN_UP: N = up / |up|, normalised once.  Tangent and
+ *     bitangent by Duff et al., "Building an Orthonormal Basis, Revisited": s = copysign(1, N.z), a = -1 / (s + N.z), b = (N.x N.y) a,
+ *     B0 = (1 + (s (N.x N.x)) a, s b, -(s N.x)), T0 = (b, s + (N.y N.y) a, -N.y); Tn = cy T0 + sy B0, Bn = cy B0 - sy T0.  The
+ *     instance's world matrix has the columns scale Tn, scale N, scale Bn, P and the bottom row 0 0 0 1: local +Y is the instance
+ *     mesh's "up".
+ * mpt_scatter_add: appends `count` objects of mesh_id with material mtlid; *first_obj is the first of their contiguous ids.  The mesh
+ *   may be subdivided and displaced (the instances share its one copy).  Refuses, leaving the scene as it was: an unknown surface
+ *   object or mesh; a surface that is itself an instance of a scatter; count < 1; a count that takes the scene to max_faces; smin or
+ *   smax not finite, or smin > smax; an `up` that is zero or not finite; an align outside the enum; a mesh with morph targets or a
+ *   skin (a deformable mesh has one copy per object); a density image id outside [-1, max_textures); a density channel outside the
+ *   displacement's codes; with a density image, a corner uv of the surface's mesh that the displacement would refuse.
+ * mpt_scatter_set_params: new parameters for a scatter (checked alike); the next mpt_compose selects and places again.
+ * mpt_scatter_rescatter: a new seed; the next mpt_compose selects and places again.  The old seed on the same surface gives the old
+ *   records bit for bit.
+ * mpt_compose, with scatters: weights, scan and selection run for a scatter that is new or was changed by the two calls above;
+ *   placement runs for the scatters that selected, for those whose surface is composed again in this call, and for all after
+ *   objects were added or dropped; the instances placed are composed again with their surface.  One weight, one selection and one
+ *   placement launch whatever the number of scatters.  Before anything changes it refuses a surface without faces and a density
+ *   image that is not loaded, naming scatter, object and image; a surface whose largest weight is 0 is refused when the weights are
+ *   there, and the scene and the composed model stay as they were.  A density image that changes later moves nothing until a rescatter.
+ * mpt_object_set_world on an instance is refused, naming the scatter; mpt_object_set_material is allowed.  mpt_scene_clear drops the
+ *   scatters with the objects.  The host's copy of an instance's matrix is not kept: mpt_scatter_get fetches the device's.
+ * mpt_scatter_stats: scatters and their instances; what the last mpt_compose did: scatters that selected, scatters and instances
+ *   placed, its weight / scan / selection / placement launches, and its reads of the largest weights by the host.
+ * mpt_scatter_kernel_time: HIP-event times (ms) of the selection (weights, scan, records) and of the placement launches of the
+ *   mpt_compose calls since the last call (either may be NULL), and the kernels launched.
+ * mpt_scatter_get: the sticky records [count], the world matrices [count][16] and the shares q [F] of a scatter as the last
+ *   mpt_compose left them on the device (any may be NULL); fails before that mpt_compose.
+ * mpt_scatter_rule: selection and placement as a pure function (no context, no GPU): for world corners [nfaces][3][3], shares
+ *   q [nfaces] and parameters (the density fields are not read), the records [count] and matrices [count][16] of instances
+ *   first .. first + count - 1.  Returns 0, or 1 for arguments that name no scatter, 2 for shares that sum to 0. */
+enum { MPT_SCATTER_ALIGN_NORMAL = 0, MPT_SCATTER_ALIGN_UP = 1 };
+typedef struct {
+    double smin, smax;                  /* the range of the instances' scale */
+    double up[3];                       /* MPT_SCATTER_ALIGN_UP: the instances' up direction (any length) */
+    int32_t align, random_yaw;
+    int32_t density_image, channel;     /* an image of the image pool (-1: none) and MPT_DISPLACE_R .. MPT_DISPLACE_MEAN */
+} mpt_scatter_params;
+typedef struct {
+    int32_t face, pad;
+    double b1, b2, scale, cy, sy;
+} mpt_scatter_point;
+typedef struct {
+    int64_t scatters, instances, selected_scatters, placed_scatters, placed_instances;
+    int64_t weight_launches, scan_launches, select_launches, place_launches, host_fetches;
+} mpt_scatter_info;
+int mpt_scatter_add(mpt_ctx *ctx, int surface_obj, int mesh_id, int count, uint64_t seed, int mtlid, const mpt_scatter_params *params,
+                    int *scatter_id, int *first_obj);
+int mpt_scatter_set_params(mpt_ctx *ctx, int scatter_id, const mpt_scatter_params *params);
+int mpt_scatter_rescatter(mpt_ctx *ctx, int scatter_id, uint64_t seed);
+int mpt_scatter_stats(mpt_ctx *ctx, mpt_scatter_info *out);
+int mpt_scatter_kernel_time(mpt_ctx *ctx, double *select_ms, double *place_ms, int *launches);
+int mpt_scatter_get(mpt_ctx *ctx, int scatter_id, mpt_scatter_point *points, double *worlds /* [count][16] */, uint32_t *q /* [F] */);
+int mpt_scatter_rule(const double *corners /* [nfaces][3][3] */, const uint32_t *q, int64_t nfaces, const mpt_scatter_params *params,
+                     uint64_t seed, int64_t first, int64_t count, mpt_scatter_point *points, double *worlds /* [count][16] */);
+
 /* Refit: after the model's faces moved (mpt_compose after mpt_object_set_world, or mpt_load_model of as many faces), keep the trees
  * of the last mpt_build_tree and fit their boxes to the model again, on the device -- what a viewport does for a moved object instead of
  * building (the reference's add-on builds: blender.py:555-571).

@@ -94,6 +94,19 @@ class SubdivInfo(C.Structure):
                 ('copy_verts', C.c_int64)]
 
 
+class ScatterParams(C.Structure):
+    '''mpt_scatter_params (include/miptina.h)'''
+    _fields_ = [('smin', C.c_double), ('smax', C.c_double), ('up', C.c_double * 3), ('align', C.c_int32), ('random_yaw', C.c_int32),
+                ('density_image', C.c_int32), ('channel', C.c_int32)]
+
+
+class ScatterInfo(C.Structure):
+    '''mpt_scatter_info (include/miptina.h): what mpt_scatter_stats hands back'''
+    _fields_ = [('scatters', C.c_int64), ('instances', C.c_int64), ('selected_scatters', C.c_int64), ('placed_scatters', C.c_int64),
+                ('placed_instances', C.c_int64), ('weight_launches', C.c_int64), ('scan_launches', C.c_int64), ('select_launches', C.c_int64),
+                ('place_launches', C.c_int64), ('host_fetches', C.c_int64)]
+
+
 class DisplaceInfo(C.Structure):
     '''mpt_displace_info (include/miptina.h): what mpt_displace_stats hands back'''
     _fields_ = [('displaced_meshes', C.c_int64), ('copies', C.c_int64), ('displaced_copies', C.c_int64), ('displaced_verts', C.c_int64),
@@ -276,6 +289,14 @@ SIGNATURES = {
     'mpt_displace_stats': (_i, [_vp, C.POINTER(DisplaceInfo)]),
     'mpt_displace_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
     'mpt_displace_corners': (_i, [_ip, C.c_int64, C.c_int32, _ip]),
+    'mpt_scatter_add': (_i, [_vp, _i, _i, _i, C.c_uint64, _i, C.POINTER(ScatterParams), C.POINTER(_i), C.POINTER(_i)]),
+    'mpt_scatter_set_params': (_i, [_vp, _i, C.POINTER(ScatterParams)]),
+    'mpt_scatter_rescatter': (_i, [_vp, _i, C.c_uint64]),
+    'mpt_scatter_stats': (_i, [_vp, C.POINTER(ScatterInfo)]),
+    'mpt_scatter_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_scatter_get': (_i, [_vp, _i, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
+    'mpt_scatter_rule': (_i, [C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_int64, C.POINTER(ScatterParams), C.c_uint64, C.c_int64, C.c_int64,
+                              C.c_void_p, C.POINTER(C.c_double)]),
     'mpt_refit_tree': (_i, [_vp]),
     'mpt_refit_stats': (_i, [_vp, C.POINTER(RefitInfo)]),
     'mpt_refit_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
@@ -516,6 +537,44 @@ def displace_corners(faces, nverts):
     corner = np.zeros(max(int(nverts), 1), np.int32)
     rc = load_library().mpt_displace_corners(iptr(f), f.shape[0], int(nverts), iptr(corner))
     return rc, corner[:max(int(nverts), 0)]
+
+
+SCATTER_ALIGNS = ('normal', 'up')                                        # include/miptina.h MPT_SCATTER_ALIGN_NORMAL, _UP
+# mpt_scatter_point (include/miptina.h): the sticky record of an instance, 48 bytes
+SCATTER_POINT_DTYPE = np.dtype([('face', np.int32), ('pad', np.int32), ('b1', np.float64), ('b2', np.float64), ('scale', np.float64),
+                                ('cy', np.float64), ('sy', np.float64)])
+
+
+def scatter_params(scale=(1, 1), align='normal', up=(0, 1, 0), random_yaw=True, density=None, channel='mean'):
+    '''mpt_scatter_params from ModelPool.add_scatter's keywords: the words are checked here, the numbers by the library'''
+    if align not in SCATTER_ALIGNS:
+        raise ValueError('align %r: one of %s' % (align, ', '.join(SCATTER_ALIGNS)))
+    if channel not in DISPLACE_CHANNELS:
+        raise ValueError('channel %r: one of %s' % (channel, ', '.join(DISPLACE_CHANNELS)))
+    smin, smax = (float(scale), float(scale)) if np.ndim(scale) == 0 else (float(scale[0]), float(scale[1]))
+    up = np.asarray(up, np.float64).reshape(-1)
+    if up.size != 3:
+        raise ValueError('up must have 3 components, got %d' % up.size)
+    image = -1 if density is None else int(getattr(density, 'id', density))  # (an image.Image, or its id)
+    if density is not None and image < 0:
+        raise ValueError('density image id %d is negative' % image)
+    return ScatterParams(smin, smax, (C.c_double * 3)(*up.tolist()), SCATTER_ALIGNS.index(align), int(bool(random_yaw)), image,
+                         DISPLACE_CHANNELS.index(channel))
+
+
+def scatter_rule(corners, q, seed, count, first=0, **params):
+    '''mpt_scatter_rule (no context, no GPU): (verdict, records [count] of SCATTER_POINT_DTYPE, matrices [count,4,4]) of instances
+    first .. first + count - 1 over world corners [F,3,3] with shares q [F]; the keywords of scatter_params'''
+    p = scatter_params(**params)
+    corners = np.ascontiguousarray(corners, np.float64).reshape(-1, 3, 3)
+    q = np.ascontiguousarray(q, np.uint32).reshape(-1)
+    if q.size != corners.shape[0]:
+        raise ValueError('%d shares for %d faces' % (q.size, corners.shape[0]))
+    points, worlds = np.zeros(max(int(count), 0), SCATTER_POINT_DTYPE), np.zeros((max(int(count), 0), 4, 4), np.float64)
+    rc = load_library().mpt_scatter_rule(corners.ctypes.data_as(C.POINTER(C.c_double)), q.ctypes.data_as(C.POINTER(C.c_uint32)), corners.shape[0],
+                                         C.byref(p), int(seed) & (2 ** 64 - 1), int(first), int(count), points.ctypes.data_as(C.c_void_p),
+                                         worlds.ctypes.data_as(C.POINTER(C.c_double)))
+    return rc, points, worlds
 
 
 def devices_isolated():

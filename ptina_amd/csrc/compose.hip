@@ -22,6 +22,7 @@
 #include <math.h>
 #include "mpt_types.h"
 #include "run_table.h"
+#include "compose_rule.h"
 
 enum { CP_BLOCK = 256, CP_WAVE = 64, CP_WAVES = CP_BLOCK / CP_WAVE, CP_FOLD = 1024, CP_FOLD_WAVES = CP_FOLD / CP_WAVE };
 
@@ -52,7 +53,7 @@ __device__ static inline float4 compose_vertex(const float4 *__restrict__ pool, 
     const double p[3] = { q0.x, q0.y, q0.z }, n[3] = { q0.w, q1.x, q1.y };
     double ph[4], nh[3];
 #pragma unroll
-    for (int j = 0; j < 4; j++) ph[j] = ((p[0] * o->world[4 * j] + p[1] * o->world[4 * j + 1]) + p[2] * o->world[4 * j + 2]) + o->world[4 * j + 3];
+    for (int j = 0; j < 4; j++) ph[j] = mpt_place_row(p, o->world, j);        // (compose_rule.h: scatter.hip places the corners of a surface by it too)
 #pragma unroll
     for (int j = 0; j < 3; j++) nh[j] = (n[0] * o->world[4 * j] + n[1] * o->world[4 * j + 1]) + n[2] * o->world[4 * j + 2];
     const double len = sqrt((nh[0] * nh[0] + nh[1] * nh[1]) + nh[2] * nh[2]);

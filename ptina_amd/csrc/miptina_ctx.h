@@ -11,6 +11,7 @@
 #include "deform_rule.h"
 #include "subdiv_rule.h"
 #include "displace_rule.h"
+#include "scatter_rule.h"
 #include "history_rule.h"
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
@@ -119,6 +120,17 @@ MPT_KERNEL_API hipError_t mpt_launch_displace(const float *pool, const MptSubdiv
                                               int blocks, const int32_t *topo, const MptVec4 *texels, double *work, hipStream_t stream);
 MPT_KERNEL_API hipError_t mpt_launch_subdiv_emit(float *pool, const MptSubdivJob *jobs, const MptRun *runs, int nruns, int blocks,
                                                  const int32_t *topo, const double *work, hipStream_t stream);
+// scatter.hip: the weights of the selecting scatters' faces with their largest, the faces' integer shares scanned, the instances'
+// sticky records, and the instances' world matrices written into the object table (mpt_compose)
+MPT_KERNEL_API hipError_t mpt_launch_scatter_weights(const float *pool, const MptComposeObj *objs, const MptScatterJob *jobs, const MptRun *runs, int nruns,
+                                                     int blocks, const MptVec4 *texels, double *w, double *part, double *wmax, double *wmax_host,
+                                                     hipStream_t stream);
+MPT_KERNEL_API hipError_t mpt_launch_scatter_scan(const MptScatterJob *jobs, const MptRun *runs, int nruns, int blocks, const double *w, const double *wmax,
+                                                  uint32_t *q, uint64_t *cdf, uint64_t *bsum, hipStream_t stream);
+MPT_KERNEL_API hipError_t mpt_launch_scatter_select(const MptScatterJob *jobs, const MptRun *runs, int nruns, int blocks, const uint64_t *cdf,
+                                                    MptScatterPoint *points, hipStream_t stream);
+MPT_KERNEL_API hipError_t mpt_launch_scatter_place(const float *pool, MptComposeObj *objs, const MptScatterJob *jobs, const MptRun *runs, int nruns,
+                                                   int blocks, const MptScatterPoint *points, unsigned epoch, hipStream_t stream);
 
 // on-GPU LBVH build (lbvh_build.hip)
 struct MptLbvhBuffers {
@@ -795,6 +807,32 @@ struct mpt_ctx {
         MptLaunchTimer displace_timer;                   // mpt_compose: {before, after} the displacement launch
         explicit Subdiv(MptEventPool &ev) : refine_timer(2, ev), normal_timer(2, ev), emit_timer(2, ev), displace_timer(2, ev) {}
     } subdiv{events};
+    struct MptScatterRow {                               // a scatter: `count` instances of `mesh` over the surface object `surf`
+        int surf = 0, mesh = 0, first_obj = 0, count = 0;
+        uint64_t seed = 0;
+        mpt_scatter_params par{};                        // as given, `up` at unit length
+        int faces = 0;                                   // the surface's faces (an object keeps its count): weights, shares and cdf have faces + 1 entries
+        size_t face_at = 0, point_at = 0;                // where they and the sticky records lie in the arenas
+        bool select = true;                              // weights, scan and selection are due: a new scatter, mpt_scatter_rescatter, mpt_scatter_set_params
+        bool placed = false;                             // the rows of the device's table hold the instances' matrices (mpt_scatter_get)
+    };
+    struct MPT_INTERNAL Scatter {                        // scatters (scene_scatter.cpp: mpt_scatter_*, scatter_mark, scatter_step)
+        std::vector<MptScatterRow> rows;
+        std::vector<int> obj_scatter;                    // per object of the table: the scatter it is an instance of (-1: none)
+        size_t faces_used = 0, points_used = 0;          // entries of the arenas
+        DevBuf<double> w; DevBuf<uint32_t> q; DevBuf<uint64_t> cdf;   // per face of every scatter's surface (and one entry behind them): weight, share, exclusive scan
+        DevBuf<MptScatterPoint> points;                  // the sticky records of every scatter, back to back
+        DevBuf<MptScatterJob> jobs; DevBuf<MptRun> runs; // a compose's table of scatters and its three run tables: faces and instances of the selecting ones, instances of the placing ones
+        DevBuf<double> part; DevBuf<uint64_t> bsum;      // per workgroup of the weight launch: its largest weight, the sum of its shares
+        DevBuf<double> wmax; MappedBuf<double> wmax_host; size_t wmax_cap = 0;   // per scatter: the largest weight, on the device and where the host reads it
+        std::vector<MptScatterJob> h_jobs;               // the last compose's tables as uploaded: they outlive the rows that made them
+        std::vector<MptRun> h_runs;
+        std::vector<unsigned char> selects, places;      // per scatter: what the compose under way does (scatter_mark decides, scatter_step launches)
+        mpt_scatter_info stats{};
+        int launches = 0;                                // kernels launched since mpt_scatter_kernel_time last asked
+        MptLaunchTimer select_timer, place_timer;        // mpt_compose: {before, after} weights + scan + selection, and the placement
+        explicit Scatter(MptEventPool &ev) : select_timer(2, ev), place_timer(2, ev) {}
+    } scatter{events};
     struct MPT_INTERNAL Refit {                          // mpt_refit_tree (tree_refit.cpp, refit_rule.h)
         int topo = MPT_TOPO_NONE;                        // MptTopoState: do the node records hold a topology, and if not, why not
         int faces = 0; bool on_device = false;           // ... for this many faces, from the device build
@@ -958,6 +996,15 @@ MPT_INTERNAL void subdiv_pose_changed(mpt_ctx *c, int obj_id);   // mpt_object_s
 MPT_INTERNAL void subdiv_scene_cleared(mpt_ctx *c, int meshes);
 MPT_INTERNAL int subdiv_images_ready(mpt_ctx *c);                // before deform_step: a displaced copy that will be displaced has its image loaded, else mpt_compose refuses and changes nothing
 MPT_INTERNAL int subdiv_step(mpt_ctx *c);                        // behind deform_step: room, the launches; rewrites objs' mesh_vert at a relayout
+
+// scene_scatter.cpp: what scene_compose.cpp tells the scatters, and their steps of mpt_compose
+MPT_INTERNAL void scatter_object_added(mpt_ctx *c);              // mpt_object_add: the new object is no instance
+MPT_INTERNAL int scatter_of_object(const mpt_ctx *c, int obj_id);   // the scatter the object is an instance of, or -1
+MPT_INTERNAL void scatter_scene_cleared(mpt_ctx *c);             // the scatters go with the objects
+MPT_INTERNAL int scatter_ready(mpt_ctx *c);                      // before deform_step: a surface has faces, a density image that will be sampled is loaded, else mpt_compose refuses and changes nothing
+MPT_INTERNAL bool scatter_selection_due(const mpt_ctx *c);       // ... and will the compose under way select (and so may refuse a surface without weight)?
+MPT_INTERNAL void scatter_mark(mpt_ctx *c);                      // behind subdiv_step: which scatters select and place; flags their instances (bit 1 of compose.dirty: placed on the device)
+MPT_INTERNAL int scatter_step(mpt_ctx *c);                       // behind the table's upload, before compose_kernel: the launches
 
 // film_read.cpp
 MPT_INTERNAL int check_pass(mpt_ctx *c, int pass);

@@ -284,3 +284,27 @@ struct MptDisplaceJob {                     // 48 bytes
     int64_t corner_at;                       // first word in the arena of topology words: [V_L] the first corner 3 g + c of every last-level vertex
     double strength, midlevel;
 };
+
+// Scatter (scatter.hip): instances of a mesh placed over a surface object of the table.  MptScatterPoint is the STICKY RECORD of an
+// instance -- the face it was born on, its barycentric point there, its scale and its yaw as a unit vector -- which the placement
+// kernel turns into the instance's world matrix whenever the surface moves.  MptScatterJob is one scatter of a compose's launches:
+// the rows of the object table it reads and writes, where its faces' weights and its records lie in their arenas, its parameters
+struct MptScatterPoint {                    // 48 bytes (include/miptina.h has it as mpt_scatter_point)
+    int32_t face, pad;
+    double b1, b2;                           // the barycentric weights of corners 1 and 2 (b0 = (1 - b1) - b2)
+    double scale, cy, sy;
+};
+enum { MPT_SCATTER_CHUNK = 256 };           // items (faces or instances) per workgroup: one per lane
+struct MptScatterJob {                      // 112 bytes
+    int32_t surf_obj, first_obj;             // rows of the object table: the surface, the first instance
+    int32_t nfaces, count;                   // F of the surface, N instances
+    int64_t face_at;                         // first entry of the arenas w, q and cdf (F + 1 entries each)
+    int64_t point_at;                        // first sticky record in the arena of points
+    uint64_t key;                            // mix(seed)
+    int32_t align, random_yaw;               // MPT_SCATTER_ALIGN_NORMAL / _UP of include/miptina.h
+    int32_t density, channel;                // 1: a density image is sampled; MPT_DISPLACE_R .. _MEAN
+    int32_t nx, ny;                          // the image [nx][ny] ...
+    int64_t texel_at;                        // ... its first texel in the arena of rgba f32 texels
+    double smin, smax;
+    double up[3];                            // unit length (the host normalises it once)
+};

@@ -97,6 +97,7 @@ extern "C" int mpt_object_add(mpt_ctx *c, int mesh_id, const double world[16], i
     cp.relayout = true;
     deform_object_added(c, mesh_id);
     subdiv_object_added(c, mesh_id);
+    scatter_object_added(c);
     if (obj_id) *obj_id = (int)cp.objs.size() - 1;
     return 0;
 }
@@ -104,6 +105,8 @@ extern "C" int mpt_object_add(mpt_ctx *c, int mesh_id, const double world[16], i
 extern "C" int mpt_object_set_world(mpt_ctx *c, int obj_id, const double world[16]) {
     if (use(c)) return 1;
     if (check_object(c, obj_id) || check_world(world)) return 1;
+    if (scatter_of_object(c, obj_id) >= 0)
+        return fail("mpt_object_set_world: object %d is an instance of scatter %d, which places it on its surface", obj_id, scatter_of_object(c, obj_id));
     memcpy(c->compose.objs[obj_id].world, world, sizeof(double) * 16);
     c->compose.dirty[obj_id] = 1;
     return 0;
@@ -125,6 +128,7 @@ extern "C" int mpt_scene_clear(mpt_ctx *c, int meshes) {
     if (meshes) { cp.meshes.clear(); cp.pool_verts = 0; }
     deform_scene_cleared(c, meshes);
     subdiv_scene_cleared(c, meshes);
+    scatter_scene_cleared(c);
     return 0;
 }
 
@@ -145,15 +149,23 @@ extern "C" int mpt_compose(mpt_ctx *c) {
     for (int o = 0; o < nobj; o++) { faces[o] = cp.objs[o].nfaces; total += faces[o]; }
     if (total >= c->caps.max_faces) return fail("too many faces");            // model.py:84
     if (subdiv_images_ready(c)) return 1;             // (a displaced copy whose image is not loaded: nothing has changed yet)
+    if (scatter_ready(c)) return 1;                   // (a scatter whose surface has no faces or whose density image is not loaded: the same)
     const int n = (int)total, nverts = n * 3;
     HIP_TRY(hipStreamSynchronize(c->stream));
     bool replaced = false;
+    // A compose that selects may still refuse a surface without weight once the weights are there: a model that has to grow keeps
+    // its old buffers until then, and takes them back at a refusal (the composed model stays as it was)
+    MptModelBufs kept;
+    if (scatter_selection_due(c) && (size_t)std::max(n, 1) > c->dmodel.cap) {
+        kept.d_verts.swap(c->dmodel.d_verts); kept.d_mtlids.swap(c->dmodel.d_mtlids); std::swap(kept.cap, c->dmodel.cap);
+    }
     if (c->dmodel.reserve(std::max(n, 1), &replaced)) return 1;
     const size_t groups = mpt_compose_groups((size_t)nverts);
     if (groups * 6 > cp.bufs.part.cap) { replaced = true; if (cp.bufs.part.reserve(groups * 6)) return 1; }
     if (nobj > 0 && (size_t)nobj > cp.bufs.objs.cap) { cp.relayout = true; if (cp.bufs.reserve_table((size_t)nobj)) return 1; }
     if (deform_step(c)) return 1;                     // the deformed copies first: compose_kernel reads them as meshes (scene_deform.cpp)
     if (subdiv_step(c)) return 1;                     // ... then the subdivided copies, of meshes and of deformed copies (scene_subdiv.cpp)
+    scatter_mark(c);                                  // ... and the instances of the scatters that place are composed again (scene_scatter.cpp)
     const bool all = cp.relayout || replaced || !cp.out_valid;
     cp.epoch++;
     int ndirty = 0; long long recomposed = 0;
@@ -174,7 +186,7 @@ extern "C" int mpt_compose(mpt_ctx *c) {
         HIP_TRY(hipMemcpyAsync(cp.bufs.first, first32.data(), (size_t)nobj * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     } else {
         for (int o = 0; o < nobj; o++)
-            if (cp.dirty[o])
+            if (cp.dirty[o] & 1)                     // (bit 1 alone: an instance its scatter places, whose row the device writes)
                 HIP_TRY(hipMemcpyAsync(cp.bufs.objs + o, &cp.objs[o], sizeof(MptComposeObj), hipMemcpyHostToDevice, c->stream));
     }
     std::vector<MptRun> runs((size_t)std::max(nruns, 1));
@@ -182,6 +194,11 @@ extern "C" int mpt_compose(mpt_ctx *c) {
     for (int r = 0; r < nruns; r++) { runs[r] = { (int32_t)wg_begin[r], blocks }; blocks += (int)wg_count[r]; }
     if (!all && nruns > 0)
         HIP_TRY(hipMemcpyAsync(cp.bufs.runs, runs.data(), (size_t)nruns * sizeof(MptRun), hipMemcpyHostToDevice, c->stream));
+    // the scatters' launches: behind the table's upload, which would overwrite the matrices they write, and before the composition
+    if (scatter_step(c)) {
+        if (kept.cap) { kept.d_verts.swap(c->dmodel.d_verts); kept.d_mtlids.swap(c->dmodel.d_mtlids); std::swap(kept.cap, c->dmodel.cap); }
+        return 1;
+    }
     if (n > 0) {
         MptTimedSpan span(cp.timer, c->stream);
         HIP_TRY(span.begun);

@@ -1,0 +1,319 @@
+// scene_scatter.cpp -- scatters behind mpt_scatter_* (DESIGN.md section 3.21): instances of a mesh placed over a surface object of
+// the table on the device.  The table of scatters beside scene_compose.cpp's object table; the arenas of the surfaces' weights,
+// shares and scans and of the instances' sticky records; and the steps of mpt_compose: scatter_ready (its refusals, before anything
+// changes), scatter_mark (behind subdiv_step: which scatters select and which place, their instances flagged for the composition)
+// and scatter_step (behind the upload of the object table, which would overwrite matrices written earlier, and before
+// compose_kernel: the launches of scatter.hip).  The rule itself is scatter_rule.h's, which mpt_scatter_rule evaluates on the host.
+
+#include "miptina_ctx.h"
+#include <cstddef>
+
+static_assert(sizeof(mpt_scatter_point) == sizeof(MptScatterPoint) && offsetof(mpt_scatter_point, sy) == offsetof(MptScatterPoint, sy),
+              "include/miptina.h and mpt_types.h hold the sticky record alike");
+
+// the parameters as a scatter keeps them: checked, `up` at unit length.  Words of a refusal go to why (always terminated)
+static int scatter_params_of(const mpt_scatter_params *in, mpt_scatter_params *out, char *why, size_t why_size) {
+    why[0] = 0;
+    if (!in) { snprintf(why, why_size, "null parameters"); return 1; }
+    *out = *in;
+    if (!std::isfinite(in->smin) || !std::isfinite(in->smax)) { snprintf(why, why_size, "the scale range is not finite"); return 1; }
+    if (in->smin > in->smax) { snprintf(why, why_size, "the scale range is empty: smin %g above smax %g", in->smin, in->smax); return 1; }
+    if (in->align != MPT_SCATTER_ALIGN_NORMAL && in->align != MPT_SCATTER_ALIGN_UP) { snprintf(why, why_size, "align %d outside [0, 1]", in->align); return 1; }
+    if (!std::isfinite(in->up[0]) || !std::isfinite(in->up[1]) || !std::isfinite(in->up[2])) { snprintf(why, why_size, "up is not finite"); return 1; }
+    mpt_scatter_normalise(in->up, out->up);
+    if (!std::isfinite(out->up[0]) || !std::isfinite(out->up[1]) || !std::isfinite(out->up[2])) {
+        snprintf(why, why_size, "up (%g, %g, %g) has no direction", in->up[0], in->up[1], in->up[2]);
+        return 1;
+    }
+    out->random_yaw = in->random_yaw != 0;
+    return 0;
+}
+
+extern "C" int mpt_scatter_rule(const double *corners, const uint32_t *q, int64_t nfaces, const mpt_scatter_params *params, uint64_t seed, int64_t first,
+                                int64_t count, mpt_scatter_point *points, double *worlds) {
+    mpt_scatter_params par;
+    char why[160];
+    if (nfaces < 1 || nfaces > MPT_SUBDIV_MAX_FACES || count < 0 || first < 0 || !corners || !q || scatter_params_of(params, &par, why, sizeof why)) return 1;
+    std::vector<uint64_t> cdf((size_t)nfaces + 1);
+    uint64_t at = 0;
+    for (int64_t g = 0; g < nfaces; g++) { cdf[(size_t)g] = at; at += q[g]; }
+    cdf[(size_t)nfaces] = at;
+    if (at == 0) return 2;
+    const uint64_t key = mpt_scatter_mix(seed);
+    for (int64_t k = 0; k < count; k++) {
+        MptScatterPoint r;
+        mpt_scatter_select(cdf.data(), nfaces, key, (uint64_t)(first + k), par.smin, par.smax, par.random_yaw, &r);
+        if (points) memcpy(points + k, &r, sizeof r);
+        const double *P = corners + (size_t)r.face * 9;
+        if (worlds) mpt_scatter_place(P, P + 3, P + 6, r, par.align, par.up, worlds + (size_t)k * 16);
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- what scene_compose.cpp tells the table
+void scatter_object_added(mpt_ctx *c) { c->scatter.obj_scatter.push_back(-1); }
+
+int scatter_of_object(const mpt_ctx *c, int obj_id) {
+    const auto &os = c->scatter.obj_scatter;
+    return obj_id >= 0 && (size_t)obj_id < os.size() ? os[obj_id] : -1;
+}
+
+void scatter_scene_cleared(mpt_ctx *c) {
+    auto &sc = c->scatter;
+    sc.rows.clear(); sc.obj_scatter.clear();
+    sc.faces_used = sc.points_used = 0;
+}
+
+// ---------------------------------------------------------------- the scatters
+static int check_scatter(const mpt_ctx *c, int id, const char *who) {
+    if (id < 0 || (size_t)id >= c->scatter.rows.size()) return fail("%s: unknown scatter %d (%zu scatters)", who, id, c->scatter.rows.size());
+    return 0;
+}
+
+// the parameters of a scatter over surface object `surf`, checked against the context as well
+static int check_params(mpt_ctx *c, const char *who, int surf, const mpt_scatter_params *in, mpt_scatter_params *out) {
+    char why[160];
+    if (scatter_params_of(in, out, why, sizeof why)) return fail("%s: %s", who, why);
+    if (in->density_image < -1 || in->density_image >= c->caps.max_textures)
+        return fail("%s: density image %d outside [-1, %d)", who, in->density_image, c->caps.max_textures);
+    if (in->density_image < 0) return 0;
+    if (in->channel < MPT_DISPLACE_R || in->channel > MPT_DISPLACE_MEAN) return fail("%s: channel %d outside [0, 4]", who, in->channel);
+    // the uvs the density is sampled at are means of midpoints of the corner uvs of the surface's mesh: admitted with them
+    const int mesh = c->deform.obj_mesh[surf], k = c->compose.meshes[mesh].nfaces;
+    std::vector<float> rec((size_t)k * 24);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (k > 0) HIP_TRY(hipMemcpy(rec.data(), c->compose.bufs.pool + c->compose.meshes[mesh].vert * 8, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
+    if (mpt_displace_uv_check_of(rec.data(), k, why, sizeof why)) return fail("%s: the surface, object %d of mesh %d: %s", who, surf, mesh, why);
+    return 0;
+}
+
+extern "C" int mpt_scatter_add(mpt_ctx *c, int surface_obj, int mesh_id, int count, uint64_t seed, int mtlid, const mpt_scatter_params *params,
+                               int *scatter_id, int *first_obj) {
+    if (use(c)) return 1;
+    const char *who = "mpt_scatter_add";
+    auto &cp = c->compose;
+    auto &sc = c->scatter;
+    if (surface_obj < 0 || (size_t)surface_obj >= cp.objs.size()) return fail("%s: unknown surface object %d (%zu objects)", who, surface_obj, cp.objs.size());
+    if (mesh_id < 0 || (size_t)mesh_id >= cp.meshes.size()) return fail("%s: unknown mesh %d (%zu meshes)", who, mesh_id, cp.meshes.size());
+    if (scatter_of_object(c, surface_obj) >= 0)
+        return fail("%s: the surface, object %d, is itself an instance of scatter %d", who, surface_obj, scatter_of_object(c, surface_obj));
+    if (count < 1) return fail("%s: count %d is below 1", who, count);
+    if (mtlid < -1 || mtlid >= c->caps.max_materials) return fail("%s: material id %d outside [-1, %d)", who, mtlid, c->caps.max_materials);
+    if ((size_t)mesh_id < c->deform.meshes.size() && (c->deform.meshes[mesh_id].ntargets || c->deform.meshes[mesh_id].njoints))
+        return fail("%s: mesh %d carries morph targets or a skin: a deformable mesh has one copy per object and cannot be instanced", who, mesh_id);
+    long long total = 0;
+    for (const auto &o : cp.objs) total += o.nfaces;
+    const int k = subdiv_object_faces(c, mesh_id);
+    if (total + (long long)count * k >= c->caps.max_faces)
+        return fail("%s: too many faces: %lld with %d instances of mesh %d, room for fewer than %d", who, total + (long long)count * k, count, mesh_id, c->caps.max_faces);
+    mpt_ctx::MptScatterRow row;
+    if (check_params(c, who, surface_obj, params, &row.par)) return 1;
+    row.surf = surface_obj; row.mesh = mesh_id; row.first_obj = (int)cp.objs.size(); row.count = count; row.seed = seed;
+    row.faces = cp.objs[surface_obj].nfaces;
+    row.face_at = sc.faces_used; row.point_at = sc.points_used;
+    sc.faces_used += (size_t)row.faces + 1; sc.points_used += (size_t)count;
+    sc.obj_scatter.resize(cp.objs.size(), -1);
+    MptComposeObj o{};
+    o.nfaces = k; o.mesh_vert = (int32_t)cp.meshes[mesh_id].vert; o.mtlid = mtlid;
+    for (int d = 0; d < 4; d++) o.world[5 * d] = 1.0;     // (the host's copy of an instance's matrix is a placeholder)
+    for (int i = 0; i < count; i++) {
+        cp.objs.push_back(o);
+        cp.dirty.push_back(1);
+        deform_object_added(c, mesh_id);
+        subdiv_object_added(c, mesh_id);
+        sc.obj_scatter.push_back((int)sc.rows.size());
+    }
+    cp.relayout = true;
+    sc.rows.push_back(row);
+    if (scatter_id) *scatter_id = (int)sc.rows.size() - 1;
+    if (first_obj) *first_obj = row.first_obj;
+    return 0;
+}
+
+extern "C" int mpt_scatter_set_params(mpt_ctx *c, int scatter_id, const mpt_scatter_params *params) {
+    if (use(c)) return 1;
+    if (check_scatter(c, scatter_id, "mpt_scatter_set_params")) return 1;
+    auto &row = c->scatter.rows[scatter_id];
+    mpt_scatter_params par;
+    if (check_params(c, "mpt_scatter_set_params", row.surf, params, &par)) return 1;
+    row.par = par; row.select = true;
+    return 0;
+}
+
+extern "C" int mpt_scatter_rescatter(mpt_ctx *c, int scatter_id, uint64_t seed) {
+    if (use(c)) return 1;
+    if (check_scatter(c, scatter_id, "mpt_scatter_rescatter")) return 1;
+    c->scatter.rows[scatter_id].seed = seed;
+    c->scatter.rows[scatter_id].select = true;
+    return 0;
+}
+
+// ---------------------------------------------------------------- the steps of mpt_compose
+bool scatter_selection_due(const mpt_ctx *c) {
+    for (const auto &r : c->scatter.rows)
+        if (r.select) return true;
+    return false;
+}
+
+int scatter_ready(mpt_ctx *c) {
+    const auto &sc = c->scatter;
+    for (size_t id = 0; id < sc.rows.size(); id++) {
+        const auto &r = sc.rows[id];
+        // (an object keeps its face count while it exists -- a mesh with an object takes no subdivision level: should a road to
+        // another count open, the scatter has to select again in new room, and says so here until it does)
+        if (r.faces != c->compose.objs[r.surf].nfaces)
+            return fail("mpt_compose: scatter %zu: its surface, object %d, has %d faces and had %d when the scatter was added", id, r.surf,
+                        c->compose.objs[r.surf].nfaces, r.faces);
+        if (!r.select) continue;
+        if (c->compose.objs[r.surf].nfaces < 1) return fail("mpt_compose: scatter %zu: its surface, object %d, has no faces", id, r.surf);
+        const int im = r.par.density_image;
+        if (im < 0) continue;
+        if ((size_t)im >= c->h_images.size())
+            return fail("mpt_compose: the density of scatter %zu reads image %d, and %zu images are loaded", id, im, c->h_images.size());
+        if (c->h_images[im].nx < 1 || c->h_images[im].ny < 1)
+            return fail("mpt_compose: the density of scatter %zu reads image %d, which is empty (%d x %d)", id, im, c->h_images[im].nx, c->h_images[im].ny);
+    }
+    return 0;
+}
+
+void scatter_mark(mpt_ctx *c) {
+    auto &cp = c->compose;
+    auto &sc = c->scatter;
+    const size_t n = sc.rows.size();
+    sc.selects.assign(n, 0); sc.places.assign(n, 0);
+    for (size_t id = 0; id < n; id++) {
+        auto &r = sc.rows[id];
+        sc.selects[id] = r.select;
+        bool place = r.select || !r.placed || cp.relayout || cp.dirty[r.surf];
+        // a row of an instance that goes up from the host's table (bit 0: its material changed, or the copy of its mesh was
+        // displaced again -- mpt_mesh_set_displacement_params, a new image generation in subdiv_step) takes the placeholder
+        // matrix with it: its scatter places again
+        for (int i = 0; i < r.count && !place; i++) place = (cp.dirty[r.first_obj + i] & 1) != 0;
+        sc.places[id] = place;
+        if (!place) continue;
+        r.placed = false;
+        for (int i = 0; i < r.count; i++) cp.dirty[r.first_obj + i] |= 2;
+    }
+}
+
+int scatter_step(mpt_ctx *c) {
+    auto &cp = c->compose;
+    auto &sc = c->scatter;
+    auto &st = sc.stats;
+    st.selected_scatters = st.placed_scatters = st.placed_instances = 0;
+    st.weight_launches = st.scan_launches = st.select_launches = st.place_launches = st.host_fetches = 0;
+    const int n = (int)sc.rows.size();
+    if (n == 0) return 0;
+    std::vector<int32_t> faces((size_t)n), counts((size_t)n), sel((size_t)n), plc((size_t)n);
+    int nsel = 0, nplc = 0;
+    for (int j = 0; j < n; j++) {
+        const auto &r = sc.rows[j];
+        sel[j] = sc.selects[j]; plc[j] = sc.places[j];
+        faces[j] = r.faces; counts[j] = r.count;
+        nsel += sel[j]; nplc += plc[j];
+    }
+    if (nplc == 0) return 0;
+    std::vector<MptScatterJob> &jobs = sc.h_jobs;
+    jobs.assign((size_t)n, MptScatterJob{});
+    for (int j = 0; j < n; j++) {
+        const auto &r = sc.rows[j];
+        MptScatterJob &t = jobs[j];
+        t.surf_obj = r.surf; t.first_obj = r.first_obj; t.nfaces = r.faces; t.count = r.count;
+        t.face_at = (int64_t)r.face_at; t.point_at = (int64_t)r.point_at;
+        t.key = mpt_scatter_mix(r.seed);
+        t.align = r.par.align; t.random_yaw = r.par.random_yaw;
+        t.smin = r.par.smin; t.smax = r.par.smax;
+        for (int k = 0; k < 3; k++) t.up[k] = r.par.up[k];
+        if (sel[j] && r.par.density_image >= 0) {
+            const MptImage &im = c->h_images[r.par.density_image];        // (loaded: scatter_ready)
+            t.density = 1; t.channel = r.par.channel; t.nx = im.nx; t.ny = im.ny; t.texel_at = (int64_t)im.base;
+        }
+    }
+    std::vector<MptRun> &runs = sc.h_runs;
+    runs.assign((size_t)3 * (size_t)n, MptRun{});
+    int nruns[3] = { 0, 0, 0 }, blocks[3] = { 0, 0, 0 };
+    nruns[0] = mpt_run_plan_into(faces.data(), sel.data(), n, MPT_SCATTER_CHUNK, runs.data(), &blocks[0]);
+    nruns[1] = mpt_run_plan_into(counts.data(), sel.data(), n, MPT_SCATTER_CHUNK, runs.data() + (size_t)n, &blocks[1]);
+    nruns[2] = mpt_run_plan_into(counts.data(), plc.data(), n, MPT_SCATTER_CHUNK, runs.data() + 2 * (size_t)n, &blocks[2]);
+    if (nruns[0] < 0 || nruns[1] < 0 || nruns[2] < 0) return fail("too many faces or instances to scatter");
+    // room: the arenas keep what they hold (the records and shares of the scatters that stay as they are)
+    if (grow_keeping(sc.w, sc.faces_used, sc.w.cap, c->stream) || grow_keeping(sc.q, sc.faces_used, sc.q.cap, c->stream) ||
+        grow_keeping(sc.cdf, sc.faces_used, sc.cdf.cap, c->stream) || grow_keeping(sc.points, sc.points_used, sc.points.cap, c->stream)) return 1;
+    if (sc.jobs.reserve((size_t)n) || sc.runs.reserve((size_t)3 * (size_t)n) || sc.wmax.reserve((size_t)n)) return 1;
+    if ((size_t)n > sc.wmax_cap) {
+        const size_t cap = std::max((size_t)n, 2 * sc.wmax_cap);
+        if (sc.wmax_host.create(cap)) return 1;
+        sc.wmax_cap = cap;
+    }
+    if (sc.part.reserve((size_t)std::max(blocks[0], 1)) || sc.bsum.reserve((size_t)std::max(blocks[0], 1))) return 1;
+    HIP_TRY(hipMemcpyAsync(sc.jobs, jobs.data(), (size_t)n * sizeof(MptScatterJob), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(sc.runs, runs.data(), runs.size() * sizeof(MptRun), hipMemcpyHostToDevice, c->stream));
+    if (nsel > 0) {
+        MptTimedSpan span(sc.select_timer, c->stream);
+        HIP_TRY(span.begun);
+        HIP_TRY(mpt_launch_scatter_weights(cp.bufs.pool, cp.bufs.objs, sc.jobs, sc.runs, nruns[0], blocks[0], c->texels, sc.w, sc.part, sc.wmax,
+                                           sc.wmax_host.dev, c->stream));
+        st.weight_launches = 1; sc.launches += 2;
+        // the one place a compose with scatters waits for the device: a surface without weight is refused before its shares are made
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        st.host_fetches = 1;
+        for (int j = 0; j < n; j++)
+            if (sel[j] && !(sc.wmax_host.host[j] > 0.0))
+                return fail("mpt_compose: scatter %d: its surface, object %d, has no face with a weight above 0 (area times density)", j, sc.rows[j].surf);
+        HIP_TRY(mpt_launch_scatter_scan(sc.jobs, sc.runs, nruns[0], blocks[0], sc.w, sc.wmax, sc.q, sc.cdf, sc.bsum, c->stream));
+        st.scan_launches = 3; sc.launches += 3;
+        HIP_TRY(mpt_launch_scatter_select(sc.jobs, sc.runs + (size_t)n, nruns[1], blocks[1], sc.cdf, sc.points, c->stream));
+        st.select_launches = 1; sc.launches += 1;
+        HIP_TRY(span.end());
+    }
+    {
+        MptTimedSpan span(sc.place_timer, c->stream);
+        HIP_TRY(span.begun);
+        HIP_TRY(mpt_launch_scatter_place(cp.bufs.pool, cp.bufs.objs, sc.jobs, sc.runs + 2 * (size_t)n, nruns[2], blocks[2], sc.points, cp.epoch, c->stream));
+        st.place_launches = 1; sc.launches += 1;
+        HIP_TRY(span.end());
+    }
+    for (int j = 0; j < n; j++) {
+        auto &r = sc.rows[j];
+        if (sel[j]) { r.select = false; st.selected_scatters++; }
+        if (plc[j]) { r.placed = true; st.placed_scatters++; st.placed_instances += r.count; }
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- read-backs
+extern "C" int mpt_scatter_stats(mpt_ctx *c, mpt_scatter_info *out) {
+    if (!c || !out) return fail("null argument");
+    *out = c->scatter.stats;
+    out->scatters = (int64_t)c->scatter.rows.size();
+    out->instances = 0;
+    for (const auto &r : c->scatter.rows) out->instances += r.count;
+    return 0;
+}
+
+extern "C" int mpt_scatter_kernel_time(mpt_ctx *c, double *select_ms, double *place_ms, int *launches) {
+    if (use_ro(c)) return 1;
+    auto &sc = c->scatter;
+    double seg[2] = { 0, 0 };
+    if (timer_readout(c, sc.select_timer, &seg[0], nullptr, nullptr) || timer_readout(c, sc.place_timer, &seg[1], nullptr, nullptr)) return 1;
+    if (select_ms) *select_ms = seg[0];
+    if (place_ms) *place_ms = seg[1];
+    if (launches) *launches = sc.launches;
+    sc.launches = 0;
+    return 0;
+}
+
+extern "C" int mpt_scatter_get(mpt_ctx *c, int scatter_id, mpt_scatter_point *points, double *worlds, uint32_t *q) {
+    if (use_ro(c)) return 1;
+    if (check_scatter(c, scatter_id, "mpt_scatter_get")) return 1;
+    const auto &sc = c->scatter;
+    const auto &r = sc.rows[scatter_id];
+    if (!r.placed || r.select) return fail("mpt_scatter_get: scatter %d has not been placed yet: call mpt_compose", scatter_id);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (points) HIP_TRY(hipMemcpy(points, sc.points + r.point_at, (size_t)r.count * sizeof(MptScatterPoint), hipMemcpyDeviceToHost));
+    if (worlds)
+        HIP_TRY(hipMemcpy2D(worlds, 16 * sizeof(double), (const char *)(c->compose.bufs.objs + r.first_obj) + offsetof(MptComposeObj, world), sizeof(MptComposeObj),
+                            16 * sizeof(double), (size_t)r.count, hipMemcpyDeviceToHost));
+    if (q) HIP_TRY(hipMemcpy(q, sc.q + r.face_at, (size_t)r.faces * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}

@@ -5,7 +5,8 @@ load_meshes / add_mesh / add_object / compose, object-space meshes and an object
 and composed there into the model the build reads (csrc/compose.hip); a mesh may carry morph
 targets and a skin, and its objects a pose each, deformed there too (csrc/deform.hip), and a Loop
 subdivision level, evaluated there behind the deformation (csrc/subdiv.hip), and a subdivided mesh a
-texture displacement behind that (csrc/displace.hip).
+texture displacement behind that (csrc/displace.hip); and instances of a mesh may be scattered over an
+object, placed there on the device and placed again when the object moves (csrc/scatter.hip).
 '''
 
 import ctypes as C
@@ -13,7 +14,7 @@ import ctypes as C
 from .common import *                 # noqa: F401,F403
 from .common import Singleton, register, ctx, np
 from ._lib import fptr, iptr, ComposeInfo, DeformInfo, SubdivInfo, DisplaceInfo, DEFORM_MAX_JOINTS, DEFORM_MAX_TARGETS, SUBDIV_MAX_LEVELS
-from ._lib import DISPLACE_MODES, DISPLACE_CHANNELS
+from ._lib import DISPLACE_MODES, DISPLACE_CHANNELS, ScatterInfo, SCATTER_POINT_DTYPE, scatter_params
 
 
 @register
@@ -28,6 +29,8 @@ class ModelPool(metaclass=Singleton):
         self._mesh_levels = {}           # mesh -> its subdivision level, where it has one: an object of it has faces * 4^level
         self._mesh_displace = {}         # mesh -> [strength, midlevel] of its displacement, where it has one
         self._obj_mesh = []              # the mesh of every object of the device's table
+        self._sum = (None, 0, 0)         # (that list, how many of its objects are counted, their faces): _faces_of_objects
+        self._scatters = []              # per scatter: its surface, its mesh, its range of objects, its seed and parameters
 
     @property
     def nfaces(self):
@@ -90,7 +93,7 @@ class ModelPool(metaclass=Singleton):
         if not 0 <= int(mesh) < len(self._mesh_faces):
             raise ValueError('unknown mesh %r (%d meshes)' % (mesh, len(self._mesh_faces)))
         w = self._world(world)
-        total = sum(self._object_faces(m) for m in self._obj_mesh) + self._object_faces(int(mesh))
+        total = self._faces_of_objects() + self._object_faces(int(mesh))
         if total >= self.size:
             raise ValueError('too many faces: %d with this object, room for fewer than %d' % (total, self.size))
         obj = C.c_int(-1)
@@ -111,19 +114,19 @@ class ModelPool(metaclass=Singleton):
     def clear_objects(self):
         '''drop the objects; the meshes stay in the pool'''
         ctx().call('mpt_scene_clear', 0)
-        self._obj_mesh = []
+        self._obj_mesh, self._scatters = [], []
 
     def clear_meshes(self):
         '''drop the objects and the meshes'''
         ctx().call('mpt_scene_clear', 1)
-        self._obj_mesh, self._mesh_faces, self._mesh_levels, self._mesh_displace = [], [], {}, {}
+        self._obj_mesh, self._mesh_faces, self._mesh_levels, self._mesh_displace, self._scatters = [], [], {}, {}, []
 
     def compose(self):
         '''write the objects, in order, as the model BVHTree().build() reads -- on the device; what load(*compose_multiple_meshes(...))
         leaves, without the arrays crossing to the host and back.  After set_world / set_material only the changed objects' faces
         are rewritten'''
         ctx().call('mpt_compose')
-        self._nfaces = sum(self._object_faces(m) for m in self._obj_mesh)
+        self._nfaces = self._faces_of_objects()
         self._composed = True
 
     # ---- deformation on the device: glTF 2.0's morph targets and linear-blend skinning (csrc/deform.hip, DESIGN.md section 3.17;
@@ -212,6 +215,16 @@ class ModelPool(metaclass=Singleton):
     def _object_faces(self, mesh):
         return self._mesh_faces[mesh] << (2 * self._mesh_levels.get(mesh, 0))
 
+    def _faces_of_objects(self):
+        '''the faces of all objects.  A mesh with an object keeps its face count and objects only join the list, so the sum is
+        carried along: a scatter adds thousands of objects, and compose() asks every time'''
+        objs, n, total = self._sum
+        if objs is not self._obj_mesh or n > len(self._obj_mesh):
+            n, total = 0, 0
+        total += sum(self._object_faces(m) for m in self._obj_mesh[n:])
+        self._sum = (self._obj_mesh, len(self._obj_mesh), total)
+        return total
+
     def add_subdivision(self, mesh, levels):
         '''`levels` (1 to 5) levels of Loop subdivision for a mesh that has no object yet, before or after its targets and skin: an
         object of it then has 4^levels times the faces, smooth normals and the mesh's texcoords carried down face by face; face g of
@@ -272,6 +285,88 @@ class ModelPool(metaclass=Singleton):
         '''_lib.DisplaceInfo: displaced meshes, their copies, copies and vertices the last compose() displaced, the image generation'''
         info = DisplaceInfo()
         ctx().call('mpt_displace_stats', C.byref(info))
+        return info
+
+    # ---- scatter: instances of a mesh placed over a surface object on the device, sticky when the surface moves
+    #      (csrc/scatter.hip, DESIGN.md section 3.21; Blender's "distribute points on faces" + "instance on points")
+    def _scatter(self, scatter):
+        if not 0 <= int(scatter) < len(self._scatters):
+            raise ValueError('unknown scatter %r (%d scatters)' % (scatter, len(self._scatters)))
+        return int(scatter)
+
+    def add_scatter(self, surface, mesh, count, seed=0, mtlid=None, scale=(1, 1), align='normal', up=(0, 1, 0), random_yaw=True, density=None,
+                    channel='mean'):
+        '''`count` instances of mesh `mesh` (it may be subdivided and displaced, not deformable) scattered over the faces of object
+        `surface` in proportion to their world area -- times, with density=an image of ImagePool, its `channel` at the faces' mean
+        uv, clamped to [0, 1]; a face below 2^-24 of the largest weight gets none.  Each instance gets a scale drawn from
+        scale=(min, max), a random yaw about its up axis (its local +Y) unless random_yaw=False, and stands along the face's
+        geometric normal (align='normal') or along `up` (align='up').  The instances are objects with contiguous ids and material
+        mtlid; they remember their face and their point on it, so that compose() after the surface was posed, displaced or moved
+        again places them again on the device.  Returns (scatter id, range of object ids)'''
+        surface = self._object(surface)
+        if not 0 <= int(mesh) < len(self._mesh_faces):
+            raise ValueError('unknown mesh %r (%d meshes)' % (mesh, len(self._mesh_faces)))
+        mesh, count = int(mesh), int(count)
+        if count < 1:
+            raise ValueError('count %d is below 1' % count)
+        if self.scatter_of(surface) is not None:
+            raise ValueError('the surface, object %d, is itself an instance of scatter %d' % (surface, self.scatter_of(surface)[0]))
+        total = self._faces_of_objects() + count * self._object_faces(mesh)
+        if total >= self.size:
+            raise ValueError('too many faces: %d with %d instances, room for fewer than %d' % (total, count, self.size))
+        p = scatter_params(scale, align, up, random_yaw, density, channel)
+        sid, first = C.c_int(-1), C.c_int(-1)
+        ctx().call('mpt_scatter_add', surface, mesh, count, int(seed) & (2 ** 64 - 1), -1 if mtlid is None else int(mtlid), C.byref(p), C.byref(sid),
+                   C.byref(first))
+        assert first.value == len(self._obj_mesh) and sid.value == len(self._scatters)
+        self._obj_mesh.extend([mesh] * count)
+        self._scatters.append(dict(surface=surface, mesh=mesh, objects=range(first.value, first.value + count), seed=int(seed),
+                                   params=dict(scale=scale, align=align, up=up, random_yaw=random_yaw, density=density, channel=channel)))
+        return sid.value, self._scatters[-1]['objects']
+
+    def set_scatter(self, scatter, **params):
+        '''new parameters (add_scatter's keywords scale ... channel; the others keep their values) for a scatter; the next compose()
+        selects and places its instances again'''
+        s = self._scatters[self._scatter(scatter)]
+        unknown = set(params) - set(s['params'])
+        if unknown:
+            raise ValueError('unknown scatter parameters: %s' % ', '.join(sorted(unknown)))
+        merged = dict(s['params'], **params)
+        p = scatter_params(**merged)
+        ctx().call('mpt_scatter_set_params', int(scatter), C.byref(p))
+        s['params'] = merged
+
+    def rescatter(self, scatter, seed=None):
+        '''scatter again with a new seed (None: the old seed + 1); the next compose() selects and places the instances again.  The
+        old seed on the same surface gives the old instances back bit for bit'''
+        s = self._scatters[self._scatter(scatter)]
+        seed = s['seed'] + 1 if seed is None else int(seed)
+        ctx().call('mpt_scatter_rescatter', int(scatter), seed & (2 ** 64 - 1))
+        s['seed'] = seed
+
+    def scatter_of(self, obj):
+        '''(scatter id, instance index) of an object id -- as BVHTree().pick() and intersect() report it -- or None for an object
+        that is no instance'''
+        for sid, s in enumerate(self._scatters):
+            if int(obj) in s['objects']:
+                return sid, int(obj) - s['objects'].start
+        return None
+
+    def scatter_to_numpy(self, scatter):
+        '''(records [count] of _lib.SCATTER_POINT_DTYPE, world matrices [count,4,4] f64, shares q [F] uint32) of a scatter as the last
+        compose() left them on the device'''
+        s = self._scatters[self._scatter(scatter)]
+        n, F = len(s['objects']), self._object_faces(self._obj_mesh[s['surface']])
+        points, worlds, q = np.zeros(n, SCATTER_POINT_DTYPE), np.zeros((n, 4, 4), np.float64), np.zeros(F, np.uint32)
+        ctx().call('mpt_scatter_get', int(scatter), points.ctypes.data_as(C.c_void_p), worlds.ctypes.data_as(C.POINTER(C.c_double)),
+                   q.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return points, worlds, q
+
+    def scatter_stats(self):
+        '''_lib.ScatterInfo: scatters and instances; scatters that selected, scatters and instances placed, the weight / scan /
+        selection / placement launches and the host's reads of the last compose()'''
+        info = ScatterInfo()
+        ctx().call('mpt_scatter_stats', C.byref(info))
         return info
 
     def subdivided_to_numpy(self, obj):

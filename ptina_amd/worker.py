@@ -31,6 +31,9 @@ _PASS_THROUGH = {
     'set_mesh_subdivision': ('ModelPool', 'add_subdivision', ('mesh', 'levels')),
     'set_mesh_displacement': ('ModelPool', 'add_displacement', ('mesh', 'image', ('strength', 1.0), ('midlevel', 0.5), ('mode', 'normal'), ('channel', 'mean'))),
     'set_mesh_displacement_params': ('ModelPool', 'set_displacement', ('mesh', 'strength', ('midlevel', None))),
+    'add_scatter': ('ModelPool', 'add_scatter', ('surface', 'mesh', 'count', ('seed', 0), ('mtlid', None), ('scale', (1, 1)), ('align', 'normal'), ('up', (0, 1, 0)),
+                                                 ('random_yaw', True), ('density', None), ('channel', 'mean'))),
+    'rescatter': ('ModelPool', 'rescatter', ('scatter', ('seed', None))),
     'load_images': ('ImagePool', 'load', ('images',)),
     'load_materials': ('MaterialPool', 'load', ('materials',)),
     'build_tree': ('BVHTree', 'build', ()),
