@@ -724,11 +724,36 @@ struct mpt_ctx {
         MptLaunchTimer select_timer, render_timer;       // mpt_adapt_select: {before the kernels, after them} per call; mpt_render_selected: the same around a call's launches
         explicit Adapt(MptEventPool &ev) : select_timer(2, ev), render_timer(2, ev) {}
     } adapt{events};
-    struct MptComposeMesh { size_t vert; int nfaces; };  // a mesh of the pool: its first vertex and its faces
+    // The scene side's two host tables, both Compose's (below): a row per mesh of the pool, which mpt_mesh_add alone adds, and a row per
+    // object beside the device's record of it, which add_object (scene_compose.cpp) alone adds.  mpt_scene_clear clears both
+    struct MptDeformMesh { int ntargets = 0, njoints = 0; size_t delta_at = 0, skin_at = 0; };   // what mesh deformation keeps for a mesh (arena offsets)
+    struct MptSubdivMesh {                               // what Loop subdivision keeps for a mesh: its level and where its topology lies
+        int levels = 0; size_t topo_at = 0;
+        int64_t nv[MPT_SUBDIV_MAX_LEVELS + 1] = {};
+        int32_t rule_at[MPT_SUBDIV_MAX_LEVELS + 1] = {}, nrule_at = 0, face_at = 0;
+        int job = -1;                                    // the shared copy of a mesh that is not deformable (-1: no object yet)
+        // its texture displacement (mpt_mesh_set_displacement; DESIGN.md section 3.20)
+        bool displaced = false;
+        int image = -1, mode = 0, channel = 0;           // the image of the image pool, MPT_DISPLACE_NORMAL / _VECTOR, MPT_DISPLACE_R .. _MEAN
+        double strength = 0.0, midlevel = 0.0;
+        size_t corner_at = 0;                            // the first-corner table of its last level: first word in bufs.topo
+    };
+    struct MptMeshRow { size_t vert = 0; int nfaces = 0; MptDeformMesh deform; MptSubdivMesh subdiv; };   // a mesh: its first pool vertex, its faces, what the features keep
+    enum MptObjDirty : unsigned char {                   // why the next mpt_compose composes an object again
+        MPT_OBJ_CLEAN = 0,
+        MPT_OBJ_UPLOAD = 1,                              // its record changed on the host: it goes up
+        MPT_OBJ_PLACED = 2,                              // an instance whose scatter places: scatter.hip writes its record on the device
+        MPT_OBJ_COMPOSE = MPT_OBJ_UPLOAD | MPT_OBJ_PLACED,   // either
+    };
+    struct MptObjRow {                                   // an object: what the host alone keeps of it
+        int mesh = 0;
+        int pose = -1, copy = -1, scatter = -1;          // its rows of deform.poses and subdiv.copies, the scatter it is an instance of (-1: none)
+        unsigned char dirty = MPT_OBJ_UPLOAD;            // MptObjDirty flags, cleared by mpt_compose
+    };
     struct MPT_INTERNAL Compose {                        // scene composition on the device (mpt_mesh_add, mpt_object_*, mpt_compose)
-        std::vector<MptComposeMesh> meshes; size_t pool_verts = 0;
+        std::vector<MptMeshRow> meshes; size_t pool_verts = 0;
         std::vector<MptComposeObj> objs;                 // the table as the host keeps it (first_face as of the last layout)
-        std::vector<unsigned char> dirty;                // per object: changed since the last mpt_compose
+        std::vector<MptObjRow> rows;                     // ... and the host's row of each of its objects
         bool relayout = true;                            // objects were added or dropped: the next mpt_compose writes everything
         bool out_valid = false;                          // dmodel holds the last mpt_compose's output (mpt_load_model takes the buffers back)
         int out_objs = 0;                                // ... of this many objects: the rows of bufs.first (objects added since are not in it)
@@ -751,7 +776,6 @@ struct mpt_ctx {
             for (auto &p : copies) p.copy_vert = -1;
         }
     };
-    struct MptDeformMesh { int ntargets = 0, njoints = 0; size_t delta_at = 0, skin_at = 0; };   // what a mesh of the pool carries (arena offsets)
     struct MptDeformPose {                               // a deformable object: its pose as the host keeps it, and its deformed copy
         int obj = 0, mesh = 0;
         std::vector<double> pose;                        // ntargets weights, then njoints x 12: the layout of bufs.pose
@@ -759,8 +783,6 @@ struct mpt_ctx {
         bool dirty = true;                               // the pose changed since the copy was written
     };
     struct MPT_INTERNAL Deform {                         // mesh deformation (scene_deform.cpp: mpt_mesh_set_*, mpt_object_set_*, deform_step)
-        std::vector<MptDeformMesh> meshes;               // per mesh of the pool
-        std::vector<int> obj_mesh, obj_pose;             // per object of the table: its mesh, and its row of `poses` (-1: not deformable)
         std::vector<MptDeformPose> poses;
         size_t deltas_used = 0, skin_used = 0;           // floats of bufs.deltas, corners of bufs.joints / weights
         MptCopyRoom room;                                // the deformed copies' room, behind the meshes
@@ -771,17 +793,6 @@ struct mpt_ctx {
         MptLaunchTimer timer;                            // mpt_compose: {before the deform kernel, after it} per launch
         explicit Deform(MptEventPool &ev) : timer(2, ev) {}
     } deform{events};
-    struct MptSubdivMesh {                               // what a mesh of the pool carries: its level and where its topology lies
-        int levels = 0; size_t topo_at = 0;
-        int64_t nv[MPT_SUBDIV_MAX_LEVELS + 1] = {};
-        int32_t rule_at[MPT_SUBDIV_MAX_LEVELS + 1] = {}, nrule_at = 0, face_at = 0;
-        int job = -1;                                    // the shared copy of a mesh that is not deformable (-1: no object yet)
-        // its texture displacement (mpt_mesh_set_displacement; DESIGN.md section 3.20)
-        bool displaced = false;
-        int image = -1, mode = 0, channel = 0;           // the image of the image pool, MPT_DISPLACE_NORMAL / _VECTOR, MPT_DISPLACE_R .. _MEAN
-        double strength = 0.0, midlevel = 0.0;
-        size_t corner_at = 0;                            // the first-corner table of its last level: first word in bufs.topo
-    };
     struct MptSubdivCopy {                               // a subdivided copy: of a mesh that is not deformable, or of one object of a mesh that is
         int mesh = 0, obj = -1;                          // obj -1: shared by the mesh's objects
         long long copy_vert = -1; size_t work_at = 0;    // where the copy and its workspace lie (copy_vert -1: no room assigned yet)
@@ -789,8 +800,6 @@ struct mpt_ctx {
         unsigned long long image_gen = 0;                // a displaced copy: the image generation it was last displaced at (0: never)
     };
     struct MPT_INTERNAL Subdiv {                         // Loop subdivision (scene_subdiv.cpp: mpt_mesh_set_subdivision, subdiv_step)
-        std::vector<MptSubdivMesh> meshes;               // per mesh of the pool
-        std::vector<int> obj_copy;                       // per object of the table: its row of `copies` (-1: its mesh is not subdivided)
         std::vector<MptSubdivCopy> copies;
         size_t topo_used = 0;                            // words of bufs.topo
         MptCopyRoom room;                                // the subdivided copies' room, behind the meshes and the deformed copies
@@ -818,7 +827,6 @@ struct mpt_ctx {
     };
     struct MPT_INTERNAL Scatter {                        // scatters (scene_scatter.cpp: mpt_scatter_*, scatter_mark, scatter_step)
         std::vector<MptScatterRow> rows;
-        std::vector<int> obj_scatter;                    // per object of the table: the scatter it is an instance of (-1: none)
         size_t faces_used = 0, points_used = 0;          // entries of the arenas
         DevBuf<double> w; DevBuf<uint32_t> q; DevBuf<uint64_t> cdf;   // per face of every scatter's surface (and one entry behind them): weight, share, exclusive scan
         DevBuf<MptScatterPoint> points;                  // the sticky records of every scatter, back to back
@@ -958,8 +966,15 @@ MPT_INTERNAL int query_tables(mpt_ctx *c);    // before a launch reads c->query.
 
 // scene_compose.cpp
 MPT_INTERNAL int model_on_host(mpt_ctx *c);  // before anything reads c->verts / c->mtlids: fetch them once if mpt_compose made the model
-// ... and what the owners of derived copies in the pool (scene_deform.cpp, scene_subdiv.cpp) take from it
+// ... and what the other scene files take from it.  The checks of a mesh or an object argument word their refusal with "who: " in
+// front, or bare where who is null
+MPT_INTERNAL int check_mesh(const mpt_ctx *c, int mesh_id, const char *who);
+MPT_INTERNAL int check_object(const mpt_ctx *c, int obj_id, const char *who);
 MPT_INTERNAL int check_fresh_mesh(const mpt_ctx *c, int mesh_id, const char *who);   // the mesh argument of the mpt_mesh_set_* calls: a mesh of the pool, without an object yet
+MPT_INTERNAL int fetch_mesh(mpt_ctx *c, int mesh_id, std::vector<float> &rec);       // the mesh's records [face][3][8] as the pool holds them; the stream is idle behind it
+// The one place an object is added: its record of the table (world null: the identity, an instance's placeholder), its host row, and
+// through deform_object_added and subdiv_object_added its pose and its copy.  Returns its id
+MPT_INTERNAL int add_object(mpt_ctx *c, int mesh_id, const double *world, int mtlid, int scatter);
 // the read-back of a copy of `k` faces that lies at copy_vert: `noun` names the copies, `mesh` what has the k faces
 MPT_INTERNAL int read_copy(mpt_ctx *c, long long copy_vert, bool stale, int k, int obj_id, float *verts, int cap_faces, const char *who,
                            const char *noun, const char *mesh);
@@ -982,28 +997,24 @@ inline int lay_copies(mpt_ctx *c, mpt_ctx::MptCopyRoom &room, Copies &copies, si
     return 0;
 }
 
-// scene_deform.cpp: what scene_compose.cpp tells the deform table, and the step of mpt_compose that writes the deformed copies
-MPT_INTERNAL void deform_mesh_added(mpt_ctx *c);                 // a mesh joined the pool: the copies behind the meshes lose their room (MptCopyRoom::lose)
-MPT_INTERNAL void deform_object_added(mpt_ctx *c, int mesh_id);
+// scene_deform.cpp: what add_object and mpt_scene_clear tell the deform table, and the step of mpt_compose that writes the deformed copies
+MPT_INTERNAL void deform_object_added(mpt_ctx *c, int obj_id);   // (called by add_object alone, as subdiv_object_added behind it)
 MPT_INTERNAL void deform_scene_cleared(mpt_ctx *c, int meshes);
 MPT_INTERNAL int deform_step(mpt_ctx *c);                        // before compose_kernel: room, poses, the deform launch; rewrites objs' mesh_vert at a relayout
 
 // scene_subdiv.cpp: what scene_compose.cpp and scene_deform.cpp tell the subdivision table, and the step of mpt_compose behind deform_step
-MPT_INTERNAL void subdiv_mesh_added(mpt_ctx *c);                 // ... as deform_mesh_added
 MPT_INTERNAL int subdiv_object_faces(const mpt_ctx *c, int mesh_id);   // the faces an object of this mesh has: k * 4^L
-MPT_INTERNAL void subdiv_object_added(mpt_ctx *c, int mesh_id);
+MPT_INTERNAL void subdiv_object_added(mpt_ctx *c, int obj_id);
 MPT_INTERNAL void subdiv_pose_changed(mpt_ctx *c, int obj_id);   // mpt_object_set_morph_weights / mpt_object_set_joints
 MPT_INTERNAL void subdiv_scene_cleared(mpt_ctx *c, int meshes);
 MPT_INTERNAL int subdiv_images_ready(mpt_ctx *c);                // before deform_step: a displaced copy that will be displaced has its image loaded, else mpt_compose refuses and changes nothing
 MPT_INTERNAL int subdiv_step(mpt_ctx *c);                        // behind deform_step: room, the launches; rewrites objs' mesh_vert at a relayout
 
 // scene_scatter.cpp: what scene_compose.cpp tells the scatters, and their steps of mpt_compose
-MPT_INTERNAL void scatter_object_added(mpt_ctx *c);              // mpt_object_add: the new object is no instance
-MPT_INTERNAL int scatter_of_object(const mpt_ctx *c, int obj_id);   // the scatter the object is an instance of, or -1
 MPT_INTERNAL void scatter_scene_cleared(mpt_ctx *c);             // the scatters go with the objects
 MPT_INTERNAL int scatter_ready(mpt_ctx *c);                      // before deform_step: a surface has faces, a density image that will be sampled is loaded, else mpt_compose refuses and changes nothing
 MPT_INTERNAL bool scatter_selection_due(const mpt_ctx *c);       // ... and will the compose under way select (and so may refuse a surface without weight)?
-MPT_INTERNAL void scatter_mark(mpt_ctx *c);                      // behind subdiv_step: which scatters select and place; flags their instances (bit 1 of compose.dirty: placed on the device)
+MPT_INTERNAL void scatter_mark(mpt_ctx *c);                      // behind subdiv_step: which scatters select and place; flags their instances MPT_OBJ_PLACED
 MPT_INTERNAL int scatter_step(mpt_ctx *c);                       // behind the table's upload, before compose_kernel: the launches
 
 // film_read.cpp

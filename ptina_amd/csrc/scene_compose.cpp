@@ -51,16 +51,28 @@ static int check_mtlid(const mpt_ctx *c, int mtlid) {
     return 0;
 }
 
-static int check_object(const mpt_ctx *c, int obj_id) {
-    if (obj_id < 0 || (size_t)obj_id >= c->compose.objs.size()) return fail("unknown object %d (%zu objects)", obj_id, c->compose.objs.size());
+// "[who: ]unknown <noun> <id> (<n> <nouns>)" unless 0 <= id < n
+static int check_id(int id, size_t n, const char *who, const char *noun, const char *nouns) {
+    if (id >= 0 && (size_t)id < n) return 0;
+    return fail("%s%sunknown %s %d (%zu %s)", who ? who : "", who ? ": " : "", noun, id, n, nouns);
+}
+
+int check_mesh(const mpt_ctx *c, int mesh_id, const char *who) { return check_id(mesh_id, c->compose.meshes.size(), who, "mesh", "meshes"); }
+int check_object(const mpt_ctx *c, int obj_id, const char *who) { return check_id(obj_id, c->compose.rows.size(), who, "object", "objects"); }
+
+int check_fresh_mesh(const mpt_ctx *c, int mesh_id, const char *who) {
+    if (check_mesh(c, mesh_id, who)) return 1;
+    const auto &rows = c->compose.rows;
+    for (size_t o = 0; o < rows.size(); o++)
+        if (rows[o].mesh == mesh_id) return fail("%s: mesh %d already has an object (object %zu)", who, mesh_id, o);
     return 0;
 }
 
-int check_fresh_mesh(const mpt_ctx *c, int mesh_id, const char *who) {
-    const size_t meshes = c->compose.meshes.size();
-    if (mesh_id < 0 || (size_t)mesh_id >= meshes) return fail("%s: unknown mesh %d (%zu meshes)", who, mesh_id, meshes);
-    for (size_t o = 0; o < c->deform.obj_mesh.size(); o++)
-        if (c->deform.obj_mesh[o] == mesh_id) return fail("%s: mesh %d already has an object (object %zu)", who, mesh_id, o);
+int fetch_mesh(mpt_ctx *c, int mesh_id, std::vector<float> &rec) {
+    const auto &m = c->compose.meshes[mesh_id];
+    rec.resize((size_t)m.nfaces * 24);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (m.nfaces > 0) HIP_TRY(hipMemcpy(rec.data(), c->compose.bufs.pool + m.vert * 8, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -76,54 +88,60 @@ extern "C" int mpt_mesh_add(mpt_ctx *c, const float *verts, int k, int *mesh_id)
         HIP_TRY(hipMemcpyAsync(cp.bufs.pool + cp.pool_verts * 8, verts, floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));      // the caller's array is borrowed for the call
     }
-    cp.meshes.push_back({ cp.pool_verts, k });
+    cp.meshes.push_back({ cp.pool_verts, k, {}, {} });       // its whole row: no targets, no skin, no level yet
     cp.pool_verts += (size_t)k * 3;
-    deform_mesh_added(c);
-    subdiv_mesh_added(c);
+    c->deform.room.lose(c->deform.poses, cp.relayout);     // it lies where the copies behind the meshes lay
+    c->subdiv.room.lose(c->subdiv.copies, cp.relayout);
     if (mesh_id) *mesh_id = (int)cp.meshes.size() - 1;
     return 0;
 }
 
-extern "C" int mpt_object_add(mpt_ctx *c, int mesh_id, const double world[16], int mtlid, int *obj_id) {
-    if (use(c)) return 1;
+int add_object(mpt_ctx *c, int mesh_id, const double *world, int mtlid, int scatter) {
     auto &cp = c->compose;
-    if (mesh_id < 0 || (size_t)mesh_id >= cp.meshes.size()) return fail("unknown mesh %d (%zu meshes)", mesh_id, cp.meshes.size());
-    if (check_world(world) || check_mtlid(c, mtlid)) return 1;
+    const int obj = (int)cp.objs.size();
     MptComposeObj o{};
     o.nfaces = subdiv_object_faces(c, mesh_id); o.mesh_vert = (int32_t)cp.meshes[mesh_id].vert; o.mtlid = mtlid;
-    memcpy(o.world, world, sizeof o.world);
+    if (world) memcpy(o.world, world, sizeof o.world);
+    else for (int d = 0; d < 4; d++) o.world[5 * d] = 1.0;
     cp.objs.push_back(o);
-    cp.dirty.push_back(1);
+    cp.rows.push_back({ mesh_id, -1, -1, scatter, mpt_ctx::MPT_OBJ_UPLOAD });
     cp.relayout = true;
-    deform_object_added(c, mesh_id);
-    subdiv_object_added(c, mesh_id);
-    scatter_object_added(c);
-    if (obj_id) *obj_id = (int)cp.objs.size() - 1;
+    deform_object_added(c, obj);
+    subdiv_object_added(c, obj);
+    return obj;
+}
+
+extern "C" int mpt_object_add(mpt_ctx *c, int mesh_id, const double world[16], int mtlid, int *obj_id) {
+    if (use(c)) return 1;
+    if (check_mesh(c, mesh_id, nullptr) || check_world(world) || check_mtlid(c, mtlid)) return 1;
+    const int obj = add_object(c, mesh_id, world, mtlid, -1);
+    if (obj_id) *obj_id = obj;
     return 0;
 }
 
 extern "C" int mpt_object_set_world(mpt_ctx *c, int obj_id, const double world[16]) {
     if (use(c)) return 1;
-    if (check_object(c, obj_id) || check_world(world)) return 1;
-    if (scatter_of_object(c, obj_id) >= 0)
-        return fail("mpt_object_set_world: object %d is an instance of scatter %d, which places it on its surface", obj_id, scatter_of_object(c, obj_id));
+    if (check_object(c, obj_id, nullptr) || check_world(world)) return 1;
+    auto &row = c->compose.rows[obj_id];
+    if (row.scatter >= 0)
+        return fail("mpt_object_set_world: object %d is an instance of scatter %d, which places it on its surface", obj_id, row.scatter);
     memcpy(c->compose.objs[obj_id].world, world, sizeof(double) * 16);
-    c->compose.dirty[obj_id] = 1;
+    row.dirty = mpt_ctx::MPT_OBJ_UPLOAD;
     return 0;
 }
 
 extern "C" int mpt_object_set_material(mpt_ctx *c, int obj_id, int mtlid) {
     if (use(c)) return 1;
-    if (check_object(c, obj_id) || check_mtlid(c, mtlid)) return 1;
+    if (check_object(c, obj_id, nullptr) || check_mtlid(c, mtlid)) return 1;
     c->compose.objs[obj_id].mtlid = mtlid;
-    c->compose.dirty[obj_id] = 1;
+    c->compose.rows[obj_id].dirty = mpt_ctx::MPT_OBJ_UPLOAD;
     return 0;
 }
 
 extern "C" int mpt_scene_clear(mpt_ctx *c, int meshes) {
     if (use(c)) return 1;
     auto &cp = c->compose;
-    cp.objs.clear(); cp.dirty.clear();
+    cp.objs.clear(); cp.rows.clear();
     cp.relayout = true;
     if (meshes) { cp.meshes.clear(); cp.pool_verts = 0; }
     deform_scene_cleared(c, meshes);
@@ -140,6 +158,17 @@ static void bounding_sphere(mpt_ctx *c, int n, const double lo[3], const double 
     if (!std::isfinite(c->scene_rad)) c->scene_rad = 1e30;
 }
 
+// The model's buffers, set aside by take() while mpt_compose grows new ones and may still refuse: they come back when the scope ends,
+// unless drop() let them go first
+struct KeptModel : MptNoCopy {
+    MptModelBufs &model; MptModelBufs kept; bool taken = false;
+    explicit KeptModel(MptModelBufs &m) : model(m) {}
+    ~KeptModel() { if (taken) exchange(); }
+    void exchange() { kept.d_verts.swap(model.d_verts); kept.d_mtlids.swap(model.d_mtlids); std::swap(kept.cap, model.cap); }
+    void take() { exchange(); taken = true; }
+    void drop() { taken = false; }
+};
+
 extern "C" int mpt_compose(mpt_ctx *c) {
     if (use(c)) return 1;
     auto &cp = c->compose;
@@ -155,10 +184,8 @@ extern "C" int mpt_compose(mpt_ctx *c) {
     bool replaced = false;
     // A compose that selects may still refuse a surface without weight once the weights are there: a model that has to grow keeps
     // its old buffers until then, and takes them back at a refusal (the composed model stays as it was)
-    MptModelBufs kept;
-    if (scatter_selection_due(c) && (size_t)std::max(n, 1) > c->dmodel.cap) {
-        kept.d_verts.swap(c->dmodel.d_verts); kept.d_mtlids.swap(c->dmodel.d_mtlids); std::swap(kept.cap, c->dmodel.cap);
-    }
+    KeptModel kept(c->dmodel);
+    if (scatter_selection_due(c) && (size_t)std::max(n, 1) > c->dmodel.cap) kept.take();
     if (c->dmodel.reserve(std::max(n, 1), &replaced)) return 1;
     const size_t groups = mpt_compose_groups((size_t)nverts);
     if (groups * 6 > cp.bufs.part.cap) { replaced = true; if (cp.bufs.part.reserve(groups * 6)) return 1; }
@@ -170,7 +197,7 @@ extern "C" int mpt_compose(mpt_ctx *c) {
     cp.epoch++;
     int ndirty = 0; long long recomposed = 0;
     for (int o = 0; o < nobj; o++) {
-        dirty[o] = all || cp.dirty[o];
+        dirty[o] = all || (cp.rows[o].dirty & mpt_ctx::MPT_OBJ_COMPOSE);
         if (!dirty[o]) continue;
         ndirty++; recomposed += faces[o];
         cp.objs[o].epoch = cp.epoch;
@@ -186,7 +213,7 @@ extern "C" int mpt_compose(mpt_ctx *c) {
         HIP_TRY(hipMemcpyAsync(cp.bufs.first, first32.data(), (size_t)nobj * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     } else {
         for (int o = 0; o < nobj; o++)
-            if (cp.dirty[o] & 1)                     // (bit 1 alone: an instance its scatter places, whose row the device writes)
+            if (cp.rows[o].dirty & mpt_ctx::MPT_OBJ_UPLOAD)   // (MPT_OBJ_PLACED alone: an instance its scatter places, whose row the device writes)
                 HIP_TRY(hipMemcpyAsync(cp.bufs.objs + o, &cp.objs[o], sizeof(MptComposeObj), hipMemcpyHostToDevice, c->stream));
     }
     std::vector<MptRun> runs((size_t)std::max(nruns, 1));
@@ -195,10 +222,8 @@ extern "C" int mpt_compose(mpt_ctx *c) {
     if (!all && nruns > 0)
         HIP_TRY(hipMemcpyAsync(cp.bufs.runs, runs.data(), (size_t)nruns * sizeof(MptRun), hipMemcpyHostToDevice, c->stream));
     // the scatters' launches: behind the table's upload, which would overwrite the matrices they write, and before the composition
-    if (scatter_step(c)) {
-        if (kept.cap) { kept.d_verts.swap(c->dmodel.d_verts); kept.d_mtlids.swap(c->dmodel.d_mtlids); std::swap(kept.cap, c->dmodel.cap); }
-        return 1;
-    }
+    if (scatter_step(c)) return 1;
+    kept.drop();
     if (n > 0) {
         MptTimedSpan span(cp.timer, c->stream);
         HIP_TRY(span.begun);
@@ -207,12 +232,13 @@ extern "C" int mpt_compose(mpt_ctx *c) {
         HIP_TRY(span.end());
     }
     HIP_TRY(hipStreamSynchronize(c->stream));          // (also: the uploads above read host vectors that end with this call)
-    std::fill(cp.dirty.begin(), cp.dirty.end(), 0);
     cp.relayout = false; cp.out_valid = true; cp.out_objs = nobj;
     c->nfaces = n;
     c->max_mtlid = -1;
-    for (int o = 0; o < nobj; o++)
+    for (int o = 0; o < nobj; o++) {
+        cp.rows[o].dirty = mpt_ctx::MPT_OBJ_CLEAN;
         if (faces[o] > 0) c->max_mtlid = std::max(c->max_mtlid, (int)cp.objs[o].mtlid);
+    }
     {   // mpt_load_model's box: a loop that starts from +-1e300 and never takes a NaN; the device's starts from +-infinity
         double lo[3], hi[3];
         for (int k = 0; k < 3; k++) {

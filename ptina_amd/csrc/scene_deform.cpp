@@ -14,33 +14,26 @@ extern "C" int mpt_skin_check(const uint16_t *joints, const float *weights, int6
 }
 
 // ---------------------------------------------------------------- what scene_compose.cpp tells the table
-void deform_mesh_added(mpt_ctx *c) {
+void deform_object_added(mpt_ctx *c, int obj_id) {
     auto &df = c->deform;
-    df.meshes.resize(c->compose.meshes.size());
-    df.room.lose(df.poses, c->compose.relayout);
-}
-
-void deform_object_added(mpt_ctx *c, int mesh_id) {
-    auto &df = c->deform;
-    df.meshes.resize(c->compose.meshes.size());
-    df.obj_mesh.push_back(mesh_id);
-    const auto &m = df.meshes[mesh_id];
-    if (m.ntargets == 0 && m.njoints == 0) { df.obj_pose.push_back(-1); return; }
+    auto &row = c->compose.rows[obj_id];
+    const auto &m = c->compose.meshes[row.mesh].deform;
+    if (m.ntargets == 0 && m.njoints == 0) return;
     mpt_ctx::MptDeformPose p;
-    p.obj = (int)df.obj_mesh.size() - 1; p.mesh = mesh_id;
+    p.obj = obj_id; p.mesh = row.mesh;
     p.pose.assign((size_t)m.ntargets + (size_t)m.njoints * 12, 0.0);
     for (int j = 0; j < m.njoints; j++)
         for (int r = 0; r < 3; r++) p.pose[(size_t)m.ntargets + (size_t)j * 12 + 4 * r + r] = 1.0;
-    df.obj_pose.push_back((int)df.poses.size());
+    row.pose = (int)df.poses.size();
     df.poses.push_back(std::move(p));
     df.room.stale = true;
 }
 
 void deform_scene_cleared(mpt_ctx *c, int meshes) {
     auto &df = c->deform;
-    df.obj_mesh.clear(); df.obj_pose.clear(); df.poses.clear();
+    df.poses.clear();
     df.room.copy_verts = 0; df.room.stale = true;
-    if (meshes) { df.meshes.clear(); df.deltas_used = 0; df.skin_used = 0; }
+    if (meshes) { df.deltas_used = 0; df.skin_used = 0; }
 }
 
 // ---------------------------------------------------------------- the meshes' targets and skins
@@ -48,10 +41,10 @@ extern "C" int mpt_mesh_set_morph(mpt_ctx *c, int mesh_id, const float *deltas, 
     if (use(c)) return 1;
     if (check_fresh_mesh(c, mesh_id, "mpt_mesh_set_morph")) return 1;
     auto &df = c->deform;
-    df.meshes.resize(c->compose.meshes.size());
-    if (df.meshes[mesh_id].ntargets) return fail("mpt_mesh_set_morph: mesh %d already has morph targets", mesh_id);
+    auto &m = c->compose.meshes[mesh_id];
+    if (m.deform.ntargets) return fail("mpt_mesh_set_morph: mesh %d already has morph targets", mesh_id);
     if (T < 1 || T > MPT_DEFORM_MAX_TARGETS) return fail("mpt_mesh_set_morph: T %d outside [1, %d]", T, MPT_DEFORM_MAX_TARGETS);
-    const size_t corners = (size_t)c->compose.meshes[mesh_id].nfaces * 3, floats = (size_t)T * corners * 6;
+    const size_t corners = (size_t)m.nfaces * 3, floats = (size_t)T * corners * 6;
     if (floats > 0 && !deltas) return fail("mpt_mesh_set_morph: null deltas");
     for (size_t k = 0; k < floats; k++)
         if (!std::isfinite(deltas[k]))
@@ -61,7 +54,7 @@ extern "C" int mpt_mesh_set_morph(mpt_ctx *c, int mesh_id, const float *deltas, 
         HIP_TRY(hipMemcpyAsync(df.bufs.deltas + df.deltas_used, deltas, floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));      // the caller's array is borrowed for the call
     }
-    df.meshes[mesh_id].ntargets = T; df.meshes[mesh_id].delta_at = df.deltas_used;
+    m.deform.ntargets = T; m.deform.delta_at = df.deltas_used;
     df.deltas_used += floats;
     return 0;
 }
@@ -70,9 +63,9 @@ extern "C" int mpt_mesh_set_skin(mpt_ctx *c, int mesh_id, const uint16_t *joints
     if (use(c)) return 1;
     if (check_fresh_mesh(c, mesh_id, "mpt_mesh_set_skin")) return 1;
     auto &df = c->deform;
-    df.meshes.resize(c->compose.meshes.size());
-    if (df.meshes[mesh_id].njoints) return fail("mpt_mesh_set_skin: mesh %d already has a skin", mesh_id);
-    const size_t corners = (size_t)c->compose.meshes[mesh_id].nfaces * 3;
+    auto &m = c->compose.meshes[mesh_id];
+    if (m.deform.njoints) return fail("mpt_mesh_set_skin: mesh %d already has a skin", mesh_id);
+    const size_t corners = (size_t)m.nfaces * 3;
     char why[160];
     if (mpt_skin_rule(joints, weights, (int64_t)corners, njoints, why, sizeof why) != MPT_SKIN_OK) return fail("mpt_mesh_set_skin: %s", why);
     if (grow_keeping(df.bufs.joints, (df.skin_used + corners) * 4, df.skin_used * 4, c->stream) ||
@@ -82,7 +75,7 @@ extern "C" int mpt_mesh_set_skin(mpt_ctx *c, int mesh_id, const uint16_t *joints
         HIP_TRY(hipMemcpyAsync(df.bufs.weights + df.skin_used * 4, weights, corners * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    df.meshes[mesh_id].njoints = njoints; df.meshes[mesh_id].skin_at = df.skin_used;
+    m.deform.njoints = njoints; m.deform.skin_at = df.skin_used;
     df.skin_used += corners;
     return 0;
 }
@@ -91,9 +84,9 @@ extern "C" int mpt_mesh_set_skin(mpt_ctx *c, int mesh_id, const uint16_t *joints
 // the entry check of the calls that name an object: refuses an unknown one; *pose is the object's pose, null for an object that
 // is not deformable (the caller words that refusal: what its mesh lacks)
 static int pose_of(mpt_ctx *c, int obj_id, const char *who, mpt_ctx::MptDeformPose **pose) {
-    auto &df = c->deform;
-    if (obj_id < 0 || (size_t)obj_id >= df.obj_pose.size()) return fail("%s: unknown object %d (%zu objects)", who, obj_id, df.obj_pose.size());
-    *pose = df.obj_pose[obj_id] < 0 ? nullptr : &df.poses[df.obj_pose[obj_id]];
+    if (check_object(c, obj_id, who)) return 1;
+    const int row = c->compose.rows[obj_id].pose;
+    *pose = row < 0 ? nullptr : &c->deform.poses[row];
     return 0;
 }
 
@@ -101,7 +94,7 @@ extern "C" int mpt_object_set_morph_weights(mpt_ctx *c, int obj_id, const double
     if (use(c)) return 1;
     mpt_ctx::MptDeformPose *p = nullptr;
     if (pose_of(c, obj_id, "mpt_object_set_morph_weights", &p)) return 1;
-    const int T = p ? c->deform.meshes[p->mesh].ntargets : 0;
+    const int T = p ? c->compose.meshes[p->mesh].deform.ntargets : 0;
     if (T == 0) return fail("mpt_object_set_morph_weights: the mesh of object %d has no morph targets", obj_id);
     if (n != T) return fail("mpt_object_set_morph_weights: n %d, the mesh of object %d has %d morph targets", n, obj_id, T);
     if (!w) return fail("mpt_object_set_morph_weights: null w");
@@ -109,7 +102,7 @@ extern "C" int mpt_object_set_morph_weights(mpt_ctx *c, int obj_id, const double
         if (!std::isfinite(w[t])) return fail("mpt_object_set_morph_weights: w[%d] is not finite", t);
     memcpy(p->pose.data(), w, (size_t)T * sizeof(double));
     p->dirty = true;
-    c->compose.dirty[obj_id] = 1;
+    c->compose.rows[obj_id].dirty = mpt_ctx::MPT_OBJ_UPLOAD;
     subdiv_pose_changed(c, obj_id);
     return 0;
 }
@@ -118,7 +111,7 @@ extern "C" int mpt_object_set_joints(mpt_ctx *c, int obj_id, const double *mats,
     if (use(c)) return 1;
     mpt_ctx::MptDeformPose *p = nullptr;
     if (pose_of(c, obj_id, "mpt_object_set_joints", &p)) return 1;
-    const int nj = p ? c->deform.meshes[p->mesh].njoints : 0, T = nj ? c->deform.meshes[p->mesh].ntargets : 0;
+    const int nj = p ? c->compose.meshes[p->mesh].deform.njoints : 0, T = nj ? c->compose.meshes[p->mesh].deform.ntargets : 0;
     if (nj == 0) return fail("mpt_object_set_joints: the mesh of object %d has no skin", obj_id);
     if (n != nj) return fail("mpt_object_set_joints: n %d, the skin of the mesh of object %d has %d joints", n, obj_id, nj);
     if (!mats) return fail("mpt_object_set_joints: null mats");
@@ -131,7 +124,7 @@ extern "C" int mpt_object_set_joints(mpt_ctx *c, int obj_id, const double *mats,
     }
     for (int j = 0; j < nj; j++) memcpy(p->pose.data() + T + (size_t)j * 12, mats + 16 * j, 12 * sizeof(double));
     p->dirty = true;
-    c->compose.dirty[obj_id] = 1;
+    c->compose.rows[obj_id].dirty = mpt_ctx::MPT_OBJ_UPLOAD;
     subdiv_pose_changed(c, obj_id);
     return 0;
 }
@@ -167,7 +160,7 @@ int deform_step(mpt_ctx *c) {
     std::vector<int32_t> corners((size_t)np), dirty((size_t)np);
     for (int k = 0; k < np; k++) {
         const auto &p = df.poses[k];
-        const auto &m = df.meshes[p.mesh];
+        const auto &m = cp.meshes[p.mesh].deform;
         MptDeformObj &t = table[k];
         t = MptDeformObj{};
         t.src_vert = (int32_t)cp.meshes[p.mesh].vert; t.dst_vert = (int32_t)p.copy_vert; t.nverts = cp.meshes[p.mesh].nfaces * 3;

@@ -51,16 +51,9 @@ extern "C" int mpt_scatter_rule(const double *corners, const uint32_t *q, int64_
 }
 
 // ---------------------------------------------------------------- what scene_compose.cpp tells the table
-void scatter_object_added(mpt_ctx *c) { c->scatter.obj_scatter.push_back(-1); }
-
-int scatter_of_object(const mpt_ctx *c, int obj_id) {
-    const auto &os = c->scatter.obj_scatter;
-    return obj_id >= 0 && (size_t)obj_id < os.size() ? os[obj_id] : -1;
-}
-
 void scatter_scene_cleared(mpt_ctx *c) {
     auto &sc = c->scatter;
-    sc.rows.clear(); sc.obj_scatter.clear();
+    sc.rows.clear();
     sc.faces_used = sc.points_used = 0;
 }
 
@@ -79,11 +72,10 @@ static int check_params(mpt_ctx *c, const char *who, int surf, const mpt_scatter
     if (in->density_image < 0) return 0;
     if (in->channel < MPT_DISPLACE_R || in->channel > MPT_DISPLACE_MEAN) return fail("%s: channel %d outside [0, 4]", who, in->channel);
     // the uvs the density is sampled at are means of midpoints of the corner uvs of the surface's mesh: admitted with them
-    const int mesh = c->deform.obj_mesh[surf], k = c->compose.meshes[mesh].nfaces;
-    std::vector<float> rec((size_t)k * 24);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (k > 0) HIP_TRY(hipMemcpy(rec.data(), c->compose.bufs.pool + c->compose.meshes[mesh].vert * 8, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
-    if (mpt_displace_uv_check_of(rec.data(), k, why, sizeof why)) return fail("%s: the surface, object %d of mesh %d: %s", who, surf, mesh, why);
+    const int mesh = c->compose.rows[surf].mesh;
+    std::vector<float> rec;
+    if (fetch_mesh(c, mesh, rec)) return 1;
+    if (mpt_displace_uv_check_of(rec.data(), c->compose.meshes[mesh].nfaces, why, sizeof why)) return fail("%s: the surface, object %d of mesh %d: %s", who, surf, mesh, why);
     return 0;
 }
 
@@ -94,12 +86,12 @@ extern "C" int mpt_scatter_add(mpt_ctx *c, int surface_obj, int mesh_id, int cou
     auto &cp = c->compose;
     auto &sc = c->scatter;
     if (surface_obj < 0 || (size_t)surface_obj >= cp.objs.size()) return fail("%s: unknown surface object %d (%zu objects)", who, surface_obj, cp.objs.size());
-    if (mesh_id < 0 || (size_t)mesh_id >= cp.meshes.size()) return fail("%s: unknown mesh %d (%zu meshes)", who, mesh_id, cp.meshes.size());
-    if (scatter_of_object(c, surface_obj) >= 0)
-        return fail("%s: the surface, object %d, is itself an instance of scatter %d", who, surface_obj, scatter_of_object(c, surface_obj));
+    if (check_mesh(c, mesh_id, who)) return 1;
+    if (cp.rows[surface_obj].scatter >= 0)
+        return fail("%s: the surface, object %d, is itself an instance of scatter %d", who, surface_obj, cp.rows[surface_obj].scatter);
     if (count < 1) return fail("%s: count %d is below 1", who, count);
     if (mtlid < -1 || mtlid >= c->caps.max_materials) return fail("%s: material id %d outside [-1, %d)", who, mtlid, c->caps.max_materials);
-    if ((size_t)mesh_id < c->deform.meshes.size() && (c->deform.meshes[mesh_id].ntargets || c->deform.meshes[mesh_id].njoints))
+    if (cp.meshes[mesh_id].deform.ntargets || cp.meshes[mesh_id].deform.njoints)
         return fail("%s: mesh %d carries morph targets or a skin: a deformable mesh has one copy per object and cannot be instanced", who, mesh_id);
     long long total = 0;
     for (const auto &o : cp.objs) total += o.nfaces;
@@ -112,18 +104,7 @@ extern "C" int mpt_scatter_add(mpt_ctx *c, int surface_obj, int mesh_id, int cou
     row.faces = cp.objs[surface_obj].nfaces;
     row.face_at = sc.faces_used; row.point_at = sc.points_used;
     sc.faces_used += (size_t)row.faces + 1; sc.points_used += (size_t)count;
-    sc.obj_scatter.resize(cp.objs.size(), -1);
-    MptComposeObj o{};
-    o.nfaces = k; o.mesh_vert = (int32_t)cp.meshes[mesh_id].vert; o.mtlid = mtlid;
-    for (int d = 0; d < 4; d++) o.world[5 * d] = 1.0;     // (the host's copy of an instance's matrix is a placeholder)
-    for (int i = 0; i < count; i++) {
-        cp.objs.push_back(o);
-        cp.dirty.push_back(1);
-        deform_object_added(c, mesh_id);
-        subdiv_object_added(c, mesh_id);
-        sc.obj_scatter.push_back((int)sc.rows.size());
-    }
-    cp.relayout = true;
+    for (int i = 0; i < count; i++) add_object(c, mesh_id, nullptr, mtlid, (int)sc.rows.size());   // (the host's copy of an instance's matrix is a placeholder)
     sc.rows.push_back(row);
     if (scatter_id) *scatter_id = (int)sc.rows.size() - 1;
     if (first_obj) *first_obj = row.first_obj;
@@ -184,15 +165,15 @@ void scatter_mark(mpt_ctx *c) {
     for (size_t id = 0; id < n; id++) {
         auto &r = sc.rows[id];
         sc.selects[id] = r.select;
-        bool place = r.select || !r.placed || cp.relayout || cp.dirty[r.surf];
-        // a row of an instance that goes up from the host's table (bit 0: its material changed, or the copy of its mesh was
+        bool place = r.select || !r.placed || cp.relayout || (cp.rows[r.surf].dirty & mpt_ctx::MPT_OBJ_COMPOSE);
+        // a row of an instance that goes up from the host's table (MPT_OBJ_UPLOAD: its material changed, or the copy of its mesh was
         // displaced again -- mpt_mesh_set_displacement_params, a new image generation in subdiv_step) takes the placeholder
         // matrix with it: its scatter places again
-        for (int i = 0; i < r.count && !place; i++) place = (cp.dirty[r.first_obj + i] & 1) != 0;
+        for (int i = 0; i < r.count && !place; i++) place = (cp.rows[r.first_obj + i].dirty & mpt_ctx::MPT_OBJ_UPLOAD) != 0;
         sc.places[id] = place;
         if (!place) continue;
         r.placed = false;
-        for (int i = 0; i < r.count; i++) cp.dirty[r.first_obj + i] |= 2;
+        for (int i = 0; i < r.count; i++) cp.rows[r.first_obj + i].dirty |= mpt_ctx::MPT_OBJ_PLACED;
     }
 }
 

@@ -29,46 +29,38 @@ extern "C" int mpt_subdiv_topology(const float *verts, int k, int levels, int64_
 }
 
 // ---------------------------------------------------------------- what scene_compose.cpp and scene_deform.cpp tell the table
-void subdiv_mesh_added(mpt_ctx *c) {
-    auto &sd = c->subdiv;
-    sd.meshes.resize(c->compose.meshes.size());
-    sd.room.lose(sd.copies, c->compose.relayout);
-}
-
 int subdiv_object_faces(const mpt_ctx *c, int mesh_id) {
-    const int k = c->compose.meshes[mesh_id].nfaces;
-    const auto &sd = c->subdiv;
-    return (size_t)mesh_id < sd.meshes.size() ? k << (2 * sd.meshes[mesh_id].levels) : k;
+    const auto &m = c->compose.meshes[mesh_id];
+    return m.nfaces << (2 * m.subdiv.levels);
 }
 
-void subdiv_object_added(mpt_ctx *c, int mesh_id) {
+void subdiv_object_added(mpt_ctx *c, int obj_id) {
     auto &sd = c->subdiv;
-    sd.meshes.resize(c->compose.meshes.size());
-    const int obj = (int)sd.obj_copy.size();
-    auto &m = sd.meshes[mesh_id];
-    if (m.levels == 0) { sd.obj_copy.push_back(-1); return; }
-    const bool deformable = c->deform.obj_pose[obj] >= 0;
+    auto &row = c->compose.rows[obj_id];
+    auto &m = c->compose.meshes[row.mesh].subdiv;
+    if (m.levels == 0) return;
+    const bool deformable = row.pose >= 0;
     if (deformable || m.job < 0) {
         mpt_ctx::MptSubdivCopy p;
-        p.mesh = mesh_id; p.obj = deformable ? obj : -1;
+        p.mesh = row.mesh; p.obj = deformable ? obj_id : -1;
         sd.copies.push_back(p);
         if (!deformable) m.job = (int)sd.copies.size() - 1;
     }
-    sd.obj_copy.push_back(deformable ? (int)sd.copies.size() - 1 : m.job);
+    row.copy = deformable ? (int)sd.copies.size() - 1 : m.job;
     sd.room.stale = true;
 }
 
 void subdiv_pose_changed(mpt_ctx *c, int obj_id) {
-    auto &sd = c->subdiv;
-    if ((size_t)obj_id < sd.obj_copy.size() && sd.obj_copy[obj_id] >= 0) sd.copies[sd.obj_copy[obj_id]].dirty = true;
+    const int copy = c->compose.rows[obj_id].copy;
+    if (copy >= 0) c->subdiv.copies[copy].dirty = true;
 }
 
 void subdiv_scene_cleared(mpt_ctx *c, int meshes) {
     auto &sd = c->subdiv;
-    sd.obj_copy.clear(); sd.copies.clear();
-    for (auto &m : sd.meshes) m.job = -1;
+    sd.copies.clear();
+    for (auto &m : c->compose.meshes) m.subdiv.job = -1;
     sd.room.copy_verts = 0; sd.room.stale = true;
-    if (meshes) { sd.meshes.clear(); sd.topo_used = 0; }
+    if (meshes) sd.topo_used = 0;
 }
 
 // ---------------------------------------------------------------- the meshes' levels
@@ -77,15 +69,14 @@ extern "C" int mpt_mesh_set_subdivision(mpt_ctx *c, int mesh_id, int levels) {
     auto &sd = c->subdiv;
     auto &cp = c->compose;
     if (check_fresh_mesh(c, mesh_id, "mpt_mesh_set_subdivision")) return 1;
-    sd.meshes.resize(cp.meshes.size());
-    if (sd.meshes[mesh_id].levels) return fail("mpt_mesh_set_subdivision: mesh %d already has a subdivision level", mesh_id);
+    auto &m = cp.meshes[mesh_id].subdiv;
+    if (m.levels) return fail("mpt_mesh_set_subdivision: mesh %d already has a subdivision level", mesh_id);
     if (levels < 1 || levels > MPT_SUBDIV_MAX_LEVELS) return fail("mpt_mesh_set_subdivision: levels %d outside [1, %d]", levels, MPT_SUBDIV_MAX_LEVELS);
     const int k = cp.meshes[mesh_id].nfaces;
     if (((long long)k << (2 * levels)) >= c->caps.max_faces)
         return fail("mpt_mesh_set_subdivision: too many faces: %lld at level %d", (long long)k << (2 * levels), levels);
-    std::vector<float> rec((size_t)k * 24);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (k > 0) HIP_TRY(hipMemcpy(rec.data(), cp.bufs.pool + cp.meshes[mesh_id].vert * 8, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<float> rec;
+    if (fetch_mesh(c, mesh_id, rec)) return 1;
     MptSubdivTopo t;
     char why[200];
     if (mpt_subdiv_topology_of(rec.data(), k, levels, t, why, sizeof why) != MPT_SUBDIV_OK) return fail("mpt_mesh_set_subdivision: mesh %d: %s", mesh_id, why);
@@ -95,7 +86,6 @@ extern "C" int mpt_mesh_set_subdivision(mpt_ctx *c, int mesh_id, int levels) {
         HIP_TRY(hipMemcpyAsync(sd.bufs.topo + sd.topo_used, t.words.data(), words * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    auto &m = sd.meshes[mesh_id];
     m.levels = levels; m.topo_at = sd.topo_used; m.job = -1;
     for (int l = 0; l <= levels; l++) { m.nv[l] = t.nv[l]; m.rule_at[l] = t.rule_at[l]; }
     m.nrule_at = t.nrule_at; m.face_at = t.face_at;
@@ -119,9 +109,8 @@ extern "C" int mpt_mesh_set_displacement(mpt_ctx *c, int mesh_id, int image_id, 
     const char *who = "mpt_mesh_set_displacement";
     auto &sd = c->subdiv;
     auto &cp = c->compose;
-    if (mesh_id < 0 || (size_t)mesh_id >= cp.meshes.size()) return fail("%s: unknown mesh %d (%zu meshes)", who, mesh_id, cp.meshes.size());
-    sd.meshes.resize(cp.meshes.size());
-    auto &m = sd.meshes[mesh_id];
+    if (check_mesh(c, mesh_id, who)) return 1;
+    auto &m = cp.meshes[mesh_id].subdiv;
     if (m.levels == 0) return fail("%s: displacement needs a subdivided mesh: mesh %d has no subdivision level", who, mesh_id);
     if (check_fresh_mesh(c, mesh_id, who)) return 1;
     if (m.displaced) return fail("%s: mesh %d already has a displacement", who, mesh_id);
@@ -131,13 +120,10 @@ extern "C" int mpt_mesh_set_displacement(mpt_ctx *c, int mesh_id, int image_id, 
     if (check_displace_params(who, strength, midlevel)) return 1;
     const int k = cp.meshes[mesh_id].nfaces;
     const int64_t nf = (int64_t)k << (2 * m.levels), nv = m.nv[m.levels];
-    std::vector<float> rec((size_t)k * 24);
+    std::vector<float> rec;
     std::vector<int32_t> faces((size_t)nf * 3), corner((size_t)nv);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (k > 0) {
-        HIP_TRY(hipMemcpy(rec.data(), cp.bufs.pool + cp.meshes[mesh_id].vert * 8, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(faces.data(), sd.bufs.topo + m.topo_at + (size_t)m.face_at, faces.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
+    if (fetch_mesh(c, mesh_id, rec)) return 1;
+    if (k > 0) HIP_TRY(hipMemcpy(faces.data(), sd.bufs.topo + m.topo_at + (size_t)m.face_at, faces.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     char why[200];
     if (mpt_displace_uv_check_of(rec.data(), k, why, sizeof why)) return fail("%s: mesh %d: %s", who, mesh_id, why);
     if (mpt_displace_corners_of(faces.data(), nf, (int32_t)nv, corner.data())) return fail("%s: mesh %d: its topology names no first corner for every vertex", who, mesh_id);
@@ -155,16 +141,16 @@ extern "C" int mpt_mesh_set_displacement(mpt_ctx *c, int mesh_id, int image_id, 
 extern "C" int mpt_mesh_set_displacement_params(mpt_ctx *c, int mesh_id, double strength, double midlevel) {
     if (use(c)) return 1;
     const char *who = "mpt_mesh_set_displacement_params";
-    auto &sd = c->subdiv;
-    if (mesh_id < 0 || (size_t)mesh_id >= c->compose.meshes.size()) return fail("%s: unknown mesh %d (%zu meshes)", who, mesh_id, c->compose.meshes.size());
-    if ((size_t)mesh_id >= sd.meshes.size() || !sd.meshes[mesh_id].displaced) return fail("%s: mesh %d has no displacement", who, mesh_id);
+    if (check_mesh(c, mesh_id, who)) return 1;
+    auto &m = c->compose.meshes[mesh_id].subdiv;
+    if (!m.displaced) return fail("%s: mesh %d has no displacement", who, mesh_id);
     if (check_displace_params(who, strength, midlevel)) return 1;
-    sd.meshes[mesh_id].strength = strength; sd.meshes[mesh_id].midlevel = midlevel;
+    m.strength = strength; m.midlevel = midlevel;
     // every copy of the mesh is displaced again, and every object that reads one is composed again (a rigid mesh's share one copy)
-    for (size_t o = 0; o < sd.obj_copy.size(); o++) {
-        if (sd.obj_copy[o] < 0 || sd.copies[sd.obj_copy[o]].mesh != mesh_id) continue;
-        sd.copies[sd.obj_copy[o]].dirty = true;
-        c->compose.dirty[o] = 1;
+    for (auto &row : c->compose.rows) {
+        if (row.copy < 0 || row.mesh != mesh_id) continue;
+        c->subdiv.copies[row.copy].dirty = true;
+        row.dirty = mpt_ctx::MPT_OBJ_UPLOAD;
     }
     return 0;
 }
@@ -188,7 +174,7 @@ static size_t work_layout(const mpt_ctx::MptSubdivMesh &m, MptSubdivJob *job) {
 
 // does the next subdiv_step write this copy?  (`all`: a relayout writes every copy)
 static bool copy_is_dirty(const mpt_ctx *c, const mpt_ctx::MptSubdivCopy &p, bool all) {
-    return all || p.dirty || (c->subdiv.meshes[p.mesh].displaced && p.image_gen != c->image_gen);
+    return all || p.dirty || (c->compose.meshes[p.mesh].subdiv.displaced && p.image_gen != c->image_gen);
 }
 
 // The first thing mpt_compose asks, before anything is queued or changed: the image of every displaced copy that the step below
@@ -197,7 +183,7 @@ int subdiv_images_ready(mpt_ctx *c) {
     const auto &sd = c->subdiv;
     const bool all = c->compose.relayout || sd.room.stale || c->deform.room.stale;
     for (const auto &p : sd.copies) {
-        const auto &m = sd.meshes[p.mesh];
+        const auto &m = c->compose.meshes[p.mesh].subdiv;
         if (!m.displaced || m.nv[m.levels] == 0 || !copy_is_dirty(c, p, all)) continue;
         if ((size_t)m.image >= c->h_images.size())
             return fail("mpt_compose: the displacement of mesh %d reads image %d, and %zu images are loaded", p.mesh, m.image, c->h_images.size());
@@ -227,11 +213,11 @@ int subdiv_step(mpt_ctx *c) {
         size_t work = 0;
         for (auto &p : sd.copies) {
             p.work_at = work;
-            work += work_layout(sd.meshes[p.mesh], nullptr);
+            work += work_layout(cp.meshes[p.mesh].subdiv, nullptr);
         }
         if (sd.bufs.work.reserve(std::max(work, (size_t)2)) || sd.bufs.reserve_tables((size_t)n)) return 1;
-        for (size_t o = 0; o < sd.obj_copy.size(); o++)
-            if (sd.obj_copy[o] >= 0) cp.objs[o].mesh_vert = (int32_t)sd.copies[sd.obj_copy[o]].copy_vert;
+        for (size_t o = 0; o < cp.rows.size(); o++)
+            if (cp.rows[o].copy >= 0) cp.objs[o].mesh_vert = (int32_t)sd.copies[cp.rows[o].copy].copy_vert;
         sd.room.stale = false;
     }
     sd.stats.copy_verts = (int64_t)sd.room.copy_verts;
@@ -243,9 +229,9 @@ int subdiv_step(mpt_ctx *c) {
     int lmax = 0, ndirty = 0, ndisplaced = 0;
     for (int j = 0; j < n; j++) {
         const auto &p = sd.copies[j];
-        const auto &m = sd.meshes[p.mesh];
+        const auto &m = c->compose.meshes[p.mesh].subdiv;
         MptSubdivJob &t = jobs[j];
-        t.src_vert = p.obj >= 0 ? (int32_t)df.poses[df.obj_pose[p.obj]].copy_vert : (int32_t)cp.meshes[p.mesh].vert;
+        t.src_vert = p.obj >= 0 ? (int32_t)df.poses[cp.rows[p.obj].pose].copy_vert : (int32_t)cp.meshes[p.mesh].vert;
         t.dst_vert = (int32_t)p.copy_vert;
         t.levels = m.levels; t.nfaces = subdiv_object_faces(c, p.mesh);
         t.topo_at = (int64_t)m.topo_at; t.work_at = (int64_t)p.work_at;
@@ -263,8 +249,8 @@ int subdiv_step(mpt_ctx *c) {
         sd.displaced_copies++; sd.displaced_verts += t.nv[m.levels];
     }
     // a copy displaced again because the images changed: the objects that read it are composed again
-    for (size_t o = 0; o < sd.obj_copy.size(); o++)
-        if (sd.obj_copy[o] >= 0 && displace[sd.obj_copy[o]]) cp.dirty[o] = 1;
+    for (auto &row : cp.rows)
+        if (row.copy >= 0 && displace[row.copy]) row.dirty = mpt_ctx::MPT_OBJ_UPLOAD;
     for (int j = 0; j < n; j++) {
         sd.copies[j].dirty = false;
         if (displace[j]) sd.copies[j].image_gen = c->image_gen;
@@ -328,9 +314,10 @@ int subdiv_step(mpt_ctx *c) {
 extern "C" int mpt_get_subdivided(mpt_ctx *c, int obj_id, float *verts, int cap_faces) {
     if (use_ro(c)) return 1;
     auto &sd = c->subdiv;
-    if (obj_id < 0 || (size_t)obj_id >= sd.obj_copy.size()) return fail("mpt_get_subdivided: unknown object %d (%zu objects)", obj_id, sd.obj_copy.size());
-    if (sd.obj_copy[obj_id] < 0) return fail("mpt_get_subdivided: the mesh of object %d has no subdivision level", obj_id);
-    const auto &p = sd.copies[sd.obj_copy[obj_id]];
+    if (check_object(c, obj_id, "mpt_get_subdivided")) return 1;
+    const int copy = c->compose.rows[obj_id].copy;
+    if (copy < 0) return fail("mpt_get_subdivided: the mesh of object %d has no subdivision level", obj_id);
+    const auto &p = sd.copies[copy];
     const int k = subdiv_object_faces(c, p.mesh);
     return read_copy(c, p.copy_vert, sd.room.stale, k, obj_id, verts, cap_faces, "mpt_get_subdivided", "subdivided", "subdivided mesh");
 }
@@ -339,7 +326,7 @@ extern "C" int mpt_subdiv_stats(mpt_ctx *c, mpt_subdiv_info *out) {
     if (!c || !out) return fail("null argument");
     *out = c->subdiv.stats;
     out->subdivided_objects = 0;
-    for (int j : c->subdiv.obj_copy) out->subdivided_objects += j >= 0;
+    for (const auto &row : c->compose.rows) out->subdivided_objects += row.copy >= 0;
     out->copies = (int64_t)c->subdiv.copies.size();
     out->copy_verts = (int64_t)c->subdiv.room.copy_verts;
     return 0;
@@ -363,8 +350,8 @@ extern "C" int mpt_displace_stats(mpt_ctx *c, mpt_displace_info *out) {
     if (!c || !out) return fail("null argument");
     const auto &sd = c->subdiv;
     *out = mpt_displace_info{};
-    for (const auto &m : sd.meshes) out->displaced_meshes += m.displaced;
-    for (const auto &p : sd.copies) out->copies += sd.meshes[p.mesh].displaced;
+    for (const auto &m : c->compose.meshes) out->displaced_meshes += m.subdiv.displaced;
+    for (const auto &p : sd.copies) out->copies += c->compose.meshes[p.mesh].subdiv.displaced;
     out->displaced_copies = sd.displaced_copies;
     out->displaced_verts = sd.displaced_verts;
     out->image_generation = (int64_t)c->image_gen;

@@ -553,6 +553,73 @@ def test_clear_and_mesh_add_while_scatters_exist(fresh):
     assert pool.nfaces == 8 + 12
 
 
+# ---------------------------------------------------------------- 8b: the books of a scene built in pieces
+def test_a_scene_built_in_pieces_equals_the_same_scene_built_at_once(fresh):
+    '''a scene whose objects use every per-object fact the host keeps -- a mesh, a pose, a subdivided copy, a scatter -- built in an
+    awkward order (a mesh joins behind an object, its rig and level come later, a plain object stands behind the instances), composed,
+    cleared and added again in another order: everything read back equals, bit for bit, what a fresh context makes of the final
+    scene added once.  Row bookkeeping is what can go wrong here; the arithmetic is the other tests' '''
+    rig, pose = _rig('fan7', 5), _pose(44)
+    kw = dict(seed=11, mtlid=2, scale=(0.05, 0.2))
+
+    def meshes(pool, between=lambda mesh: None):
+        plain = _plain(pool, 'octahedron')
+        between(plain)
+        soft = _plain(pool, 'fan7')                                       # behind the first object: the copies lose their room
+        pool.add_morph_targets(soft, rig['dp'], rig['dn'])
+        pool.add_skin(soft, rig['jt'], rig['wt'], rig['nj'])
+        pool.add_subdivision(soft, 1)
+        return plain, soft
+
+    def rigged(pool, soft):
+        obj = pool.add_object(soft, _world(31), 1)
+        _set_pose(pool, obj, pose)
+        return obj
+
+    def read(pool, sid, soft_obj):
+        model, mtlids = pool.to_numpy()
+        points, worlds, q = pool.scatter_to_numpy(sid)
+        return dict(model=model, mtlids=mtlids, points=points.view(np.uint8), worlds=worlds.view(u64), q=q,
+                    subdivided=pool.subdivided_to_numpy(soft_obj), deformed=pool.deformed_to_numpy(soft_obj))
+
+    # in pieces
+    pool = _start()
+    first = []
+    plain, soft = meshes(pool, lambda mesh: first.append(pool.add_object(mesh, sc.BENT, 0)))
+    soft_obj = rigged(pool, soft)
+    knob = dg._add(pool, 'octahedron', 1, None)
+    sid, objs = pool.add_scatter(first[0], knob, 3, **kw)
+    ico = _plain(pool, 'icosahedron')
+    late = pool.add_object(ico, _world(32), 1)                            # a plain object behind the instances
+    assert (first[0], soft_obj, list(objs), late) == (0, 1, [2, 3, 4], 5)
+    pool.compose()
+    assert pool.nfaces == 8 + 56 + 3 * 32 + 20
+    pool.clear_objects()
+    late = pool.add_object(ico, _world(32), 1)                            # ... the plain object first this time
+    surf = pool.add_object(plain, sc.BENT, 0)
+    soft_obj = rigged(pool, soft)
+    sid, objs = pool.add_scatter(surf, knob, 3, **kw)
+    assert (late, surf, soft_obj, sid, list(objs)) == (0, 1, 2, 0, [3, 4, 5])
+    pool.compose()
+    got = read(pool, sid, soft_obj)
+    assert pool.nfaces == 20 + 8 + 56 + 3 * 32 and pool.subdiv_stats().copies == 2 and pool.deform_stats().deformable_objects == 1
+
+    # at once, in a fresh context
+    pool = _start()
+    plain, soft = meshes(pool)
+    knob = dg._add(pool, 'octahedron', 1, None)
+    ico = _plain(pool, 'icosahedron')
+    late = pool.add_object(ico, _world(32), 1)
+    surf = pool.add_object(plain, sc.BENT, 0)
+    soft_obj = rigged(pool, soft)
+    sid, objs = pool.add_scatter(surf, knob, 3, **kw)
+    pool.compose()
+    want = read(pool, sid, soft_obj)
+    for k in want:
+        assert _same(got[k], want[k]), k
+    assert got['model'].shape[0] == 3 * 180 and got['subdivided'].shape[0] == 3 * 56 and got['deformed'].shape[0] == 3 * 14
+
+
 # ---------------------------------------------------------------- 9: the worker facade
 def test_worker_facade_through_the_thread_proxy(fresh):
     import threading
