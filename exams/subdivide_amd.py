@@ -6,8 +6,11 @@ subdivision level standing in the Cornell room, the scene kept on the device.  E
 so nothing but the pose (8 matrices) crosses to the device: the cage's corners are skinned there (csrc/deform.hip), the posed cage
 is subdivided there (csrc/subdiv.hip: 128 x 4^levels faces with smooth normals), the tube's faces are composed again and the built
 tree is fitted to them (csrc/refit.hip) -- topology and face count never change.  With --levels 0 the cage itself is rendered.
+With --creases two cubes of 12 triangles stand beside the tube: one with Blender's edge crease 1 on its 12 edges
+(tools.crease.blender_crease: sharpness inf), which stays a cube with a flat normal per face, and one without, which comes out a
+blob.
 
-    python exams/subdivide_amd.py [--frames 12] [--levels 3] [--size 256] [--spp 8] [--out DIR]
+    python exams/subdivide_amd.py [--frames 12] [--levels 3] [--size 256] [--spp 8] [--out DIR] [--creases]
 '''
 import argparse
 import os
@@ -20,6 +23,7 @@ from ptina_amd.things import *              # noqa: E402,F401,F403
 from ptina_amd.engine.path import *         # noqa: E402,F401,F403
 from ptina_amd.image import write_png       # noqa: E402
 from ptina_amd.tools.skin import joint_matrices   # noqa: E402
+from ptina_amd.tools.crease import blender_crease   # noqa: E402
 from ptina_amd import scenes                # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -28,6 +32,7 @@ ap.add_argument('--levels', type=int, default=3)
 ap.add_argument('--size', type=int, default=256)
 ap.add_argument('--spp', type=int, default=8)
 ap.add_argument('--out', default='.')
+ap.add_argument('--creases', action='store_true', help='a creased cube beside a smooth one')
 args = ap.parse_args()
 
 JOINTS, HEIGHT, RADIUS, RINGS, SIDES = 8, 2.4, 0.25, 8, 8
@@ -54,6 +59,18 @@ def cage():
                 jt.append([[j0[a], j1[a], 0, 0] for a, b in tri])
                 wt.append([[1.0 - f[a], f[a], 0, 0] for a, b in tri])
     return np.array(p, np.float32), np.array(n, np.float32), np.array(jt), np.array(wt, np.float32)
+
+
+def cube(half):
+    '''(p, n [12,3,3], crease [12,3]): a cube of 12 triangles and Blender's crease 1 on its 12 edges -- a face edge whose ends
+    differ in one coordinate; the diagonals of its faces stay smooth'''
+    v = np.float32([(x, y, z) for z in (-half, half) for y in (-half, half) for x in (-half, half)])
+    quads = [(0, 2, 3, 1), (4, 5, 7, 6), (0, 1, 5, 4), (2, 6, 7, 3), (0, 4, 6, 2), (1, 3, 7, 5)]
+    faces = np.array([tri for a, b, c, d in quads for tri in ((a, b, c), (a, c, d))])
+    p = v[faces]
+    along = (p != np.roll(p, -1, axis=1)).sum(axis=2) == 1
+    n = np.repeat(np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])[:, None], 3, axis=1)
+    return p, np.float32(n / np.linalg.norm(n, axis=2, keepdims=True)), np.where(along, blender_crease(1.0), np.float32(0))
 
 
 def shift(x, y, z):
@@ -92,6 +109,12 @@ pool.add_skin(mesh, joints, weights, JOINTS)
 if args.levels:
     pool.add_subdivision(mesh, args.levels)
 obj = pool.add_object(mesh, shift(0.0, 0.0, -0.3), 3)
+if args.creases and args.levels:
+    cp, cn, crease = cube(0.3)
+    for x, creases in ((-0.8, crease), (0.8, None)):
+        m = pool.add_mesh(cp, cn)
+        pool.add_subdivision(m, args.levels, creases=creases)
+        pool.add_object(m, shift(x, 0.3, 0.2), 3)
 pool.compose()
 BVHTree().build()
 

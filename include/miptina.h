@@ -661,6 +661,46 @@ int mpt_subdiv_topology(const float *verts /* [3k][8] */, int k, int levels, int
                         int64_t cap_words, int64_t *need_words, char *why, int why_size);
 int mpt_subdiv_plan(const int32_t *items, const int32_t *dirty, int njobs, int32_t *run_job, int64_t *run_block, int cap, int64_t *blocks);
 
+/* Semi-sharp creases, corners and hard edges of Loop subdivision (Blender's edge crease; the sharpness of OpenSubdiv).
+ * mpt_mesh_set_subdivision_creased is mpt_mesh_set_subdivision with crease [k][3] f32, one sharpness per face edge -- edge j of face
+ * f runs from corner j to corner (j + 1) % 3; in subdivision levels, 0 smooth, inf always sharp; the two faces on an edge may state
+ * different values, the edge takes the larger -- and corner [k][3] bytes, one flag per face corner: a control vertex is a corner if any
+ * of its welded corners is flagged.  Either may be NULL: all zero, none flagged.  They are fixed with the level.  A mesh whose
+ * sharpnesses are all zero and that has no corner flagged is the mesh of mpt_mesh_set_subdivision, word for word and bit for bit.
+ * Refuses what mpt_mesh_set_subdivision refuses, and a negative sharpness or a NaN, naming the face and the edge.
+ * The definition.  Weld, ids, edge numbering, face split, uv rule and arithmetic are those of above.
+ *   Sharpness per level: an edge of cage sharpness s0 (widened to f64) has at level l s_l = s0 - l if that is positive, else 0; inf
+ *     stays inf.  Both halves of a split edge inherit s_{l+1}; the three edges new inside a face have 0; a boundary edge counts as inf
+ *     everywhere.  Corner flags pass to even vertices only.
+ *   Edge point of an interior edge of sharpness s at the level below, E the interior rule of above, H = 0.5 * (a + b):
+ *     s == 0: E;  s >= 1: H;  else ((1 - s) * E) + (s * H), componentwise.  A boundary edge keeps its rule.
+ *   Vertex point: S the sharpnesses > 0 of its incident edges in ring order from the ring's start, k their number, M the interior
+ *     rule of above.  A flagged corner: v.  k <= 1 (a dart's end): M.  k == 2, p and q the far ends of the two sharp edges,
+ *     C = (0.75 * v) + (0.125 * (p + q)), f = 0.5 * (s1 + s2): C if f >= 1, else ((1 - f) * M) + (f * C).  k >= 3,
+ *     f = ((s1 + s2) + s3 + ...) / k: v if f >= 1, else ((1 - f) * M) + (f * v).  Where f >= 1 the blend is not evaluated.  A boundary
+ *     vertex has k >= 2 with an inf in S: with its two boundary edges alone it is the boundary rule of above; a crease that reaches
+ *     the boundary makes it a corner.
+ *   Normals at the last level L: an edge is HARD if its sharpness at level L is > 0 (s0 > L, inf, or a boundary edge).  The hard
+ *     edges cut a vertex's fan into sectors; a corner of face (v, r_i, r_i+1) takes the normal sum of above over the faces of its own
+ *     sector, in ring order from the sector's first hard edge.  A vertex without a hard interior edge keeps its single normal, in the
+ *     order of above; an interior vertex with one hard edge has one sector of all its faces, starting behind that edge.
+ *   A displacement keeps taking its direction from the whole ring (a creased surface does not crack); the sector normals are then
+ *     taken on the displaced positions.
+ * mpt_subdiv_topology_creased: mpt_subdiv_topology with crease and corner (either may be NULL) and offsets [11].  A head is
+ *   kind | n << 2 | variant << 28; variant 0 is the plain rule, and a creased mesh also has: kind 0 variant 1, the n neighbours, then p
+ *   q, then the f64 f (low word first): ((1 - f) * M) + (f * C); kind 0 variant 2, the n neighbours, then the f64 f:
+ *   ((1 - f) * M) + (f * v); kind 0 variant 3, n = 0: the vertex stays; kind 2 variant 1, a b c d, then the f64 s:
+ *   ((1 - s) * E) + (s * H).  A vertex with f >= 1 on two sharp edges is a plain kind 1 of n = 2, p q; an interior edge with s >= 1 a
+ *   plain kind 3.  offsets[6] stays the rules of the last level's whole rings.  offsets[9]: the rules of the last level's RECORDS,
+ *   offsets[10] = R of them, then R vertex ids, then the sectors' rings; offsets[7]: the faces [F][3] as RECORD ids.  Record v < V_L
+ *   is vertex v's first sector, or its whole ring where no interior edge of it is hard (its rule is then that at offsets[6]); the
+ *   further sectors follow V_L in the order of the vertices, then of the ring.  A sector's rule is kind 1 with the neighbours from
+ *   its first hard edge to its last.  An uncreased mesh has offsets[9] = 0, offsets[10] = V_L and the block of mpt_subdiv_topology.
+ *   Returns what mpt_subdiv_topology returns, or 9: a sharpness that is negative or not a number. */
+int mpt_mesh_set_subdivision_creased(mpt_ctx *ctx, int mesh_id, int levels, const float *crease /* [k][3] or NULL */, const uint8_t *corner /* [k][3] or NULL */);
+int mpt_subdiv_topology_creased(const float *verts /* [3k][8] */, int k, int levels, const float *crease, const uint8_t *corner, int64_t *counts,
+                                int32_t *offsets /* [11] */, int32_t *words, int64_t cap_words, int64_t *need_words, char *why, int why_size);
+
 /* Texture displacement on the device as a property of a SUBDIVIDED mesh of the pool: the third step of the modifier stack armature ->
  * subdivision surface -> displace.  mpt_compose evaluates it on the vertices of the mesh's last level, behind the last refine launch
  * and before the normals, so the subdivided copy's normals are the displaced surface's.  Topology and face count stay constant: a

@@ -283,6 +283,8 @@ SIGNATURES = {
     'mpt_subdiv_stats': (_i, [_vp, C.POINTER(SubdivInfo)]),
     'mpt_subdiv_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)]),
     'mpt_subdiv_topology': (_i, [_fp, _i, _i, C.POINTER(C.c_int64), _ip, _ip, C.c_int64, C.POINTER(C.c_int64), C.c_char_p, _i]),
+    'mpt_mesh_set_subdivision_creased': (_i, [_vp, _i, _i, _fp, C.POINTER(C.c_uint8)]),
+    'mpt_subdiv_topology_creased': (_i, [_fp, _i, _i, _fp, C.POINTER(C.c_uint8), C.POINTER(C.c_int64), _ip, _ip, C.c_int64, C.POINTER(C.c_int64), C.c_char_p, _i]),
     'mpt_subdiv_plan': (_i, [_ip, _ip, _i, _ip, C.POINTER(C.c_int64), _i, C.POINTER(C.c_int64)]),
     'mpt_mesh_set_displacement': (_i, [_vp, _i, _i, _i, _i, C.c_double, C.c_double]),
     'mpt_mesh_set_displacement_params': (_i, [_vp, _i, C.c_double, C.c_double]),
@@ -523,6 +525,57 @@ def subdiv_topology(rec, levels):
     return 0, '', dict(counts=counts, first_corner=w[:int(counts[0, 0])].copy(),
                        rules={l: rules(int(off[l]), int(counts[l, 0])) for l in range(1, levels + 1)},
                        rings=rules(int(off[6]), int(counts[levels, 0])), faces=w[int(off[7]):int(off[7]) + 3 * nf].reshape(nf, 3).copy())
+
+
+SUBDIV_VARIANTS = ('plain', 'blend_crease', 'blend_corner', 'fixed')      # csrc/mpt_types.h MPT_SUBDIV_PLAIN .. _FIXED (on an edge, 1 is MPT_SUBDIV_BLEND_EDGE)
+
+
+def subdiv_topology_creased(rec, levels, creases=None, corners=None):
+    '''mpt_subdiv_topology_creased (no context, no GPU) of the records rec [3k,8] f32, the sharpnesses creases [k,3] and the flags
+    corners [k,3] (either None): (verdict, words, tables) -- a refusal's verdict with the words of the refusal and None, else 0 with
+    the block of 32-bit words and the tables decoded from it.  A rule is (kind, variant, [ids], parameter) -- the
+    parameter the f64 f or s of a blending variant, else None; rules[l] and rings as subdiv_topology has them; records -- per record
+    of the last level (vertex, kind, [ids]) --; faces [F_L,3] of record ids; words: the whole block'''
+    rec = np.ascontiguousarray(rec, np.float32)
+    if rec.ndim != 2 or rec.shape[1] != 8 or rec.shape[0] % 3:
+        raise ValueError('records must be [3k,8], got %s' % (rec.shape,))
+    k, levels = rec.shape[0] // 3, int(levels)
+    cr = None if creases is None else np.ascontiguousarray(creases, np.float32).reshape(k, 3)
+    co = None if corners is None else np.ascontiguousarray(np.asarray(corners) != 0, np.uint8).reshape(k, 3)
+    crp = None if cr is None else fptr(cr)
+    cop = None if co is None else co.ctypes.data_as(C.POINTER(C.c_uint8))
+    lib = load_library()
+    why = C.create_string_buffer(240)
+    counts, off, need = np.zeros((max(levels, 0) + 1, 3), np.int64), np.zeros(11, np.int32), C.c_int64(0)
+    cp = counts.ctypes.data_as(C.POINTER(C.c_int64))
+    rc = lib.mpt_subdiv_topology_creased(fptr(rec), k, levels, crp, cop, cp, iptr(off), None, 0, C.byref(need), why, len(why))
+    if rc:
+        return rc, why.value.decode(), None
+    w = np.zeros(max(int(need.value), 1), np.int32)
+    rc = lib.mpt_subdiv_topology_creased(fptr(rec), k, levels, crp, cop, cp, iptr(off), iptr(w), int(need.value), C.byref(need), why, len(why))
+    assert rc == 0
+
+    def rule(h, r):
+        kind, variant, n = h & 3, h >> 28 & 7, h >> 2 & (1 << 26) - 1
+        extra = 2 if (kind, variant) == (0, 1) else 0
+        ids = w[r:r + n + extra].tolist()
+        blends = (kind, variant) in ((0, 1), (0, 2), (2, 1))
+        return kind, variant, ids, float(w[r + n + extra:r + n + extra + 2].view(np.float64)[0]) if blends else None
+
+    def rules(at, n):
+        return [rule(int(h), int(r)) for h, r in zip(w[at:at + 2 * n:2], w[at + 1:at + 2 * n:2])]
+    nf, vl = int(counts[levels, 2]), int(counts[levels, 0])
+    rings = [(kind, ids) for kind, _, ids, _ in rules(int(off[6]), vl)]
+    nrec = int(off[10])
+    if off[9]:
+        vert = w[int(off[9]) + 2 * nrec:int(off[9]) + 3 * nrec].tolist()
+        records = [(v, kind, ids) for v, (kind, _, ids, _) in zip(vert, rules(int(off[9]), nrec))]
+    else:
+        records = [(v, kind, ids) for v, (kind, ids) in enumerate(rings)]
+    return 0, w[:int(need.value)].copy(), dict(counts=counts, first_corner=w[:int(counts[0, 0])].copy(),
+                                               rules={l: rules(int(off[l]), int(counts[l, 0])) for l in range(1, levels + 1)},
+                                               rings=rings, records=records, faces=w[int(off[7]):int(off[7]) + 3 * nf].reshape(nf, 3).copy(),
+                                               offsets=off.copy())
 
 
 DISPLACE_MODES = ('normal', 'vector')                                    # include/miptina.h MPT_DISPLACE_NORMAL, _VECTOR

@@ -731,6 +731,7 @@ struct mpt_ctx {
         int levels = 0; size_t topo_at = 0;
         int64_t nv[MPT_SUBDIV_MAX_LEVELS + 1] = {};
         int32_t rule_at[MPT_SUBDIV_MAX_LEVELS + 1] = {}, nrule_at = 0, face_at = 0;
+        int32_t srule_at = 0; int64_t nrec = 0;          // the last level's records: nrule_at and nv[levels], or a creased mesh's sectors (section 3.19.1)
         int job = -1;                                    // the shared copy of a mesh that is not deformable (-1: no object yet)
         // its texture displacement (mpt_mesh_set_displacement)
         bool displaced = false;

@@ -261,6 +261,12 @@ struct MptDeformObj {                       // 48 bytes
 #define MPT_SUBDIV_MAX_FACES (1 << 24)      // faces of a last level the topology function takes (the context's max_faces is lower)
 #define MPT_SUBDIV_CHUNK 256                // items (vertices or faces) per workgroup: one per lane
 enum { MPT_SUBDIV_VERT_INT = 0, MPT_SUBDIV_VERT_BND = 1, MPT_SUBDIV_EDGE_INT = 2, MPT_SUBDIV_EDGE_BND = 3 };
+// A rule's head is kind | n << 2 | variant << 28.  Variant 0 is the plain rule, all an uncreased mesh has; a creased mesh (section
+// 3.19.1) has beside it, on kind VERT_INT, a vertex of two sharp edges that blends, one of three or more that blends, one that stays,
+// and on kind EDGE_INT an edge of fractional sharpness
+#define MPT_SUBDIV_VARIANT_SHIFT 28
+#define MPT_SUBDIV_N_MASK ((1 << 26) - 1)
+enum { MPT_SUBDIV_PLAIN = 0, MPT_SUBDIV_BLEND_CREASE = 1, MPT_SUBDIV_BLEND_CORNER = 2, MPT_SUBDIV_FIXED = 3, MPT_SUBDIV_BLEND_EDGE = 1 };
 struct MptSubdivJob {                       // 128 bytes
     int32_t src_vert, dst_vert;              // first pool vertex of the control records (the mesh or a deformed copy) and of the subdivided copy
     int32_t levels, nfaces;                  // L, and the faces of the last level: k * 4^L
@@ -270,9 +276,9 @@ struct MptSubdivJob {                       // 128 bytes
     int32_t rule_at[MPT_SUBDIV_MAX_LEVELS + 1];   // words from topo_at: [l] the rules of level l's vertices ([0]: the first corners)
     int32_t pos_at[MPT_SUBDIV_MAX_LEVELS + 1];    // doubles from work_at: [l] the positions [V_l][3] of level l ([0]: level 0 is read from the pool; a displaced copy's displaced positions [V_L][3])
     int32_t nrule_at, face_at;               // words from topo_at: the last level's rings, its faces' vertex ids
-    int32_t vrec_at;                         // doubles from work_at (even): the last level's vertex records, 32 bytes each: pos3 nrm3 as f32, 8 bytes unused
+    int32_t vrec_at;                         // doubles from work_at (even): the last level's records (one per vertex, or per sector of a creased mesh), 32 bytes each: pos3 nrm3 as f32, 8 bytes unused
     int32_t npos_at;                         // doubles from work_at: the positions the normals are taken of -- pos_at[L], or pos_at[0] of a displaced copy
-    int32_t pad[2];
+    int32_t srule_at, nrec;                  // words from topo_at: the rules of the last level's records, and their number -- nrule_at and V_L, or a creased mesh's sectors
 };
 
 // Texture displacement of a subdivided copy (displace.hip): the row of the displacement launch's table beside the copy's MptSubdivJob

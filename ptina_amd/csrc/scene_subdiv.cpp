@@ -12,20 +12,34 @@ extern "C" int mpt_subdiv_plan(const int32_t *items, const int32_t *dirty, int n
     return mpt_run_plan_of(items, dirty, njobs, MPT_SUBDIV_CHUNK, run_job, run_block, cap, blocks);
 }
 
-extern "C" int mpt_subdiv_topology(const float *verts, int k, int levels, int64_t *counts, int32_t *offsets, int32_t *words, int64_t cap_words,
-                                   int64_t *need_words, char *why, int why_size) {
-    MptSubdivTopo t;
-    const MptSubdivVerdict v = mpt_subdiv_topology_of(verts, k, levels, t, why, why_size > 0 ? (size_t)why_size : 0);
-    if (v != MPT_SUBDIV_OK) return (int)v;
+// what both topology entry points hand back of an accepted mesh (offsets: 9 words, or 11 with the records' rules and number)
+static int topology_out(const MptSubdivTopo &t, int levels, int64_t *counts, int32_t *offsets, bool records, int32_t *words, int64_t cap_words, int64_t *need_words) {
     if (counts)
         for (int l = 0; l <= levels; l++) { counts[3 * l] = t.nv[l]; counts[3 * l + 1] = t.ne[l]; counts[3 * l + 2] = t.nf[l]; }
     if (offsets) {
         for (int l = 0; l <= MPT_SUBDIV_MAX_LEVELS; l++) offsets[l] = l <= levels ? t.rule_at[l] : 0;
         offsets[6] = t.nrule_at; offsets[7] = t.face_at; offsets[8] = (int32_t)t.words.size();
+        if (records) { offsets[9] = t.srule_at; offsets[10] = (int32_t)t.nrec; }
     }
     if (need_words) *need_words = (int64_t)t.words.size();
     if (words && cap_words >= (int64_t)t.words.size()) memcpy(words, t.words.data(), t.words.size() * sizeof(int32_t));
     return 0;
+}
+
+extern "C" int mpt_subdiv_topology(const float *verts, int k, int levels, int64_t *counts, int32_t *offsets, int32_t *words, int64_t cap_words,
+                                   int64_t *need_words, char *why, int why_size) {
+    MptSubdivTopo t;
+    const MptSubdivVerdict v = mpt_subdiv_topology_of(verts, k, levels, t, why, why_size > 0 ? (size_t)why_size : 0);
+    if (v != MPT_SUBDIV_OK) return (int)v;
+    return topology_out(t, levels, counts, offsets, false, words, cap_words, need_words);
+}
+
+extern "C" int mpt_subdiv_topology_creased(const float *verts, int k, int levels, const float *crease, const uint8_t *corner, int64_t *counts, int32_t *offsets,
+                                           int32_t *words, int64_t cap_words, int64_t *need_words, char *why, int why_size) {
+    MptSubdivTopo t;
+    const MptSubdivVerdict v = mpt_subdiv_topology_creased_of(verts, k, levels, crease, corner, t, why, why_size > 0 ? (size_t)why_size : 0);
+    if (v != MPT_SUBDIV_OK) return (int)v;
+    return topology_out(t, levels, counts, offsets, true, words, cap_words, need_words);
 }
 
 // ---------------------------------------------------------------- what scene_compose.cpp and scene_deform.cpp tell the table
@@ -64,22 +78,23 @@ void subdiv_scene_cleared(mpt_ctx *c, int meshes) {
 }
 
 // ---------------------------------------------------------------- the meshes' levels
-extern "C" int mpt_mesh_set_subdivision(mpt_ctx *c, int mesh_id, int levels) {
+// crease [k][3] and corner [k][3] of the mesh's faces, either may be null
+static int set_subdivision(mpt_ctx *c, const char *who, int mesh_id, int levels, const float *crease, const uint8_t *corner) {
     if (use(c)) return 1;
     auto &sd = c->subdiv;
     auto &cp = c->compose;
-    if (check_fresh_mesh(c, mesh_id, "mpt_mesh_set_subdivision")) return 1;
+    if (check_fresh_mesh(c, mesh_id, who)) return 1;
     auto &m = cp.meshes[mesh_id].subdiv;
-    if (m.levels) return fail("mpt_mesh_set_subdivision: mesh %d already has a subdivision level", mesh_id);
-    if (levels < 1 || levels > MPT_SUBDIV_MAX_LEVELS) return fail("mpt_mesh_set_subdivision: levels %d outside [1, %d]", levels, MPT_SUBDIV_MAX_LEVELS);
+    if (m.levels) return fail("%s: mesh %d already has a subdivision level", who, mesh_id);
+    if (levels < 1 || levels > MPT_SUBDIV_MAX_LEVELS) return fail("%s: levels %d outside [1, %d]", who, levels, MPT_SUBDIV_MAX_LEVELS);
     const int k = cp.meshes[mesh_id].nfaces;
     if (((long long)k << (2 * levels)) >= c->caps.max_faces)
-        return fail("mpt_mesh_set_subdivision: too many faces: %lld at level %d", (long long)k << (2 * levels), levels);
+        return fail("%s: too many faces: %lld at level %d", who, (long long)k << (2 * levels), levels);
     std::vector<float> rec;
     if (fetch_mesh(c, mesh_id, rec)) return 1;
     MptSubdivTopo t;
     char why[200];
-    if (mpt_subdiv_topology_of(rec.data(), k, levels, t, why, sizeof why) != MPT_SUBDIV_OK) return fail("mpt_mesh_set_subdivision: mesh %d: %s", mesh_id, why);
+    if (mpt_subdiv_topology_creased_of(rec.data(), k, levels, crease, corner, t, why, sizeof why) != MPT_SUBDIV_OK) return fail("%s: mesh %d: %s", who, mesh_id, why);
     const size_t words = t.words.size();
     if (grow_keeping(sd.bufs.topo, sd.topo_used + words, sd.topo_used, c->stream)) return 1;
     if (words > 0) {
@@ -89,8 +104,17 @@ extern "C" int mpt_mesh_set_subdivision(mpt_ctx *c, int mesh_id, int levels) {
     m.levels = levels; m.topo_at = sd.topo_used; m.job = -1;
     for (int l = 0; l <= levels; l++) { m.nv[l] = t.nv[l]; m.rule_at[l] = t.rule_at[l]; }
     m.nrule_at = t.nrule_at; m.face_at = t.face_at;
+    m.srule_at = t.srule_at ? t.srule_at : t.nrule_at; m.nrec = t.nrec;
     sd.topo_used += words;
     return 0;
+}
+
+extern "C" int mpt_mesh_set_subdivision(mpt_ctx *c, int mesh_id, int levels) {
+    return set_subdivision(c, "mpt_mesh_set_subdivision", mesh_id, levels, nullptr, nullptr);
+}
+
+extern "C" int mpt_mesh_set_subdivision_creased(mpt_ctx *c, int mesh_id, int levels, const float *crease, const uint8_t *corner) {
+    return set_subdivision(c, "mpt_mesh_set_subdivision_creased", mesh_id, levels, crease, corner);
 }
 
 // ---------------------------------------------------------------- the meshes' displacements
@@ -126,6 +150,11 @@ extern "C" int mpt_mesh_set_displacement(mpt_ctx *c, int mesh_id, int image_id, 
     if (k > 0) HIP_TRY(hipMemcpy(faces.data(), sd.bufs.topo + m.topo_at + (size_t)m.face_at, faces.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     char why[200];
     if (mpt_displace_uv_check_of(rec.data(), k, why, sizeof why)) return fail("%s: mesh %d: %s", who, mesh_id, why);
+    if (m.srule_at != m.nrule_at && nf > 0) {            // a creased mesh's face table indexes records: back to their vertices
+        std::vector<int32_t> vert((size_t)m.nrec);
+        HIP_TRY(hipMemcpy(vert.data(), sd.bufs.topo + m.topo_at + (size_t)m.srule_at + (size_t)m.nrec * 2, vert.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (auto &f : faces) f = vert[(size_t)f];
+    }
     if (mpt_displace_corners_of(faces.data(), nf, (int32_t)nv, corner.data())) return fail("%s: mesh %d: its topology names no first corner for every vertex", who, mesh_id);
     if (grow_keeping(sd.bufs.topo, sd.topo_used + corner.size(), sd.topo_used, c->stream)) return 1;
     if (nv > 0) {
@@ -157,7 +186,7 @@ extern "C" int mpt_mesh_set_displacement_params(mpt_ctx *c, int mesh_id, double 
 
 // ---------------------------------------------------------------- the step of mpt_compose
 // the doubles of a copy's workspace: the positions of levels 1..L (each level from an even offset), then the last level's records,
-// then -- a displaced copy -- the displaced positions of the last level
+// one per vertex or, of a creased mesh, per sector, then -- a displaced copy -- the displaced positions of the last level
 static size_t work_layout(const mpt_ctx::MptSubdivMesh &m, MptSubdivJob *job) {
     size_t at = 0;
     for (int l = 1; l <= m.levels; l++) {
@@ -165,7 +194,7 @@ static size_t work_layout(const mpt_ctx::MptSubdivMesh &m, MptSubdivJob *job) {
         at += ((size_t)m.nv[l] * 3 + 1) & ~(size_t)1;
     }
     if (job) job->vrec_at = (int32_t)at;
-    at += (size_t)m.nv[m.levels] * 4;
+    at += (size_t)m.nrec * 4;
     if (job) job->npos_at = job->pos_at[m.levels];
     if (!m.displaced) return at;
     if (job) job->pos_at[0] = job->npos_at = (int32_t)at;
@@ -237,6 +266,7 @@ int subdiv_step(mpt_ctx *c) {
         t.topo_at = (int64_t)m.topo_at; t.work_at = (int64_t)p.work_at;
         for (int l = 0; l <= m.levels; l++) { t.nv[l] = (int32_t)m.nv[l]; t.rule_at[l] = m.rule_at[l]; }
         t.nrule_at = m.nrule_at; t.face_at = m.face_at;
+        t.srule_at = m.srule_at; t.nrec = (int32_t)m.nrec;
         work_layout(m, &t);
         dirty[j] = copy_is_dirty(c, p, all);
         if (!dirty[j] || t.nfaces == 0) continue;
@@ -265,7 +295,7 @@ int subdiv_step(mpt_ctx *c) {
     std::vector<int32_t> items((size_t)n);
     for (int t = 0; t < ntables; t++) {
         for (int j = 0; j < n; j++)
-            items[j] = t < lmax ? (jobs[j].levels > t ? jobs[j].nv[t + 1] : 0) : t == lmax ? jobs[j].nv[jobs[j].levels] : t == lmax + 1 ? jobs[j].nfaces
+            items[j] = t < lmax ? (jobs[j].levels > t ? jobs[j].nv[t + 1] : 0) : t == lmax ? jobs[j].nrec : t == lmax + 1 ? jobs[j].nfaces
                      : displace[j] ? jobs[j].nv[jobs[j].levels] : 0;
         nruns[t] = mpt_run_plan_into(items.data(), dirty.data(), n, MPT_SUBDIV_CHUNK, runs.data() + (size_t)t * (size_t)n, &blocks[t]);
         if (nruns[t] < 0) return fail("too many faces to subdivide");

@@ -27,6 +27,32 @@
 //   Texcoords are face-varying: a child face takes its corners' uv from its parent's three corner uvs by the face rule above, the
 //     midpoints m_ij = 0.5 * (u_i + u_j) in f64, level by level.
 //
+// Semi-sharp creases, corners and hard edges (also include/miptina.h).  Weld, ids, edge numbering, face
+// split, uv rule and arithmetic are those of above; a mesh may state a sharpness per face edge and a flag per face corner.
+//   Sharpness per level: an edge of cage sharpness s0 (f32 widened to f64; the larger of what its two faces state) has at level l
+//     s_l = s0 - l if that is positive, else 0; inf stays inf.  Both halves of a split edge inherit s_{l+1}; the three edges new
+//     inside a face have 0; a boundary edge counts as inf everywhere.  Corner flags pass to even vertices only.
+//   Edge point (interior edge, sharpness s at the level below; E the interior rule above, H = 0.5 * (a + b)):
+//     s == 0: E        s >= 1: H        otherwise ((1 - s) * E) + (s * H), componentwise.   A boundary edge keeps its rule.
+//   Vertex point.  S: the sharpnesses > 0 of its incident edges in ring order from the ring's start, k = |S|, M the interior rule:
+//     a flagged corner   v
+//     k <= 1             M   (a dart's end included)
+//     k == 2             p, q the far ends of the two sharp edges, C = (0.75 * v) + (0.125 * (p + q)), f = 0.5 * (s1 + s2):
+//                        C if f >= 1, else ((1 - f) * M) + (f * C)
+//     k >= 3             f = ((s1 + s2) + s3 + ...) / k:  v if f >= 1, else ((1 - f) * M) + (f * v)
+//     Where f >= 1 the blend is not evaluated (no 0 * inf, no signed zeros).  A boundary vertex has k >= 2 with an inf in S: with
+//     its two boundary edges alone it is the boundary rule above exactly; a crease that reaches the boundary makes it a corner.
+//   Normals at the last level L: an edge is HARD if its sharpness at level L is > 0 (s0 > L, inf, or a boundary edge).  The hard
+//     edges cut a vertex's fan into sectors; a corner of face (v, r_i, r_i+1) takes the normal sum above over the faces of its own
+//     sector, in ring order from the sector's first hard edge.  A vertex without a hard interior edge keeps its single normal in
+//     the order above; an interior vertex with one hard edge has one sector of all its faces, starting behind that edge.
+//   A displacement (section 3.20) keeps taking its direction from the whole ring, so a creased surface does not crack; the sector
+//     normals are then taken on the displaced positions.
+// The host decides every case (subdiv_rule.h, which documents the words): the kernels see a rule's variant in its head, the blend's
+// f or s as an f64 behind the rule's ids, and, for the last level of a creased mesh, one rule per RECORD -- a sector, an open ring
+// as a boundary vertex's is, with its vertex's id in a table behind the rules -- which the face table then indexes.  An uncreased
+// mesh has variant 0 everywhere and its vertices for records: the words and the results of before.
+//
 // Three kernels, each one lane per item (a workgroup of 256 lanes takes MPT_SUBDIV_CHUNK items of ONE job; a run table maps blocks to
 // (job, chunk): run_table.h), so the number of launches of an mpt_compose is L_max + 2 whatever the
 // number of copies; a job of fewer levels has no blocks in the later refine launches.  Levels are separate launches: nothing is
@@ -34,11 +60,11 @@
 //   subdiv_refine_kernel   level l - 1 -> l: a lane reads its vertex's rule (two words), gathers 2 to n + 1 positions of the level
 //                          below -- level 0 from the pool through the first-corner table, else 24-byte f64 records of the
 //                          workspace -- and writes one.
-//   subdiv_normal_kernel   the last level: a lane walks its vertex's ring and writes the vertex record (pos3 nrm3 as f32: the one
-//                          rounding), 32 bytes, two 16-byte stores.  The positions are those the job points at (npos_at): the
+//   subdiv_normal_kernel   the last level: a lane walks its vertex's ring (a creased mesh: its record's sector) and writes the record
+//                          (pos3 nrm3 as f32: the one rounding), 32 bytes, two 16-byte stores.  The positions are those the job points at (npos_at): the
 //                          last level's, or the displaced ones of a copy that carries a displacement (displace.hip, launched
 //                          between the last refine level and this kernel; section 3.20).
-//   subdiv_emit_kernel     a lane per refined face: three vertex ids, three 32-byte gathers (a vertex is shared by six corners, so
+//   subdiv_emit_kernel     a lane per refined face: three record ids, three 32-byte gathers (a vertex is shared by six corners, so
 //                          they hit in L2), the parent's three uvs and L midpoint steps, six 16-byte stores: 96 bytes.
 // Vector stores only, no atomics, no LDS.
 
@@ -72,13 +98,17 @@ __global__ __launch_bounds__(SD_BLOCK) void subdiv_refine_kernel(const float4 *p
     if (i >= o.nv[level]) return;
     const int32_t *__restrict__ T = topo + o.topo_at;
     const int32_t head = T[o.rule_at[level] + 2 * i], at = T[o.rule_at[level] + 2 * i + 1];
-    const int kind = head & 3, n = head >> 2;
+    const int kind = head & 3, variant = head >> MPT_SUBDIV_VARIANT_SHIFT & 7, n = head >> 2 & MPT_SUBDIV_N_MASK;
     const int32_t *__restrict__ ring = T + at;
     SdVec out;
     if (kind == MPT_SUBDIV_EDGE_INT) {
         const SdVec a = sd_pos(o, level, pool, T, work, ring[0]), b = sd_pos(o, level, pool, T, work, ring[1]);
         const SdVec c = sd_pos(o, level, pool, T, work, ring[2]), d = sd_pos(o, level, pool, T, work, ring[3]);
         out = sd_add(sd_mul(0.375, sd_add(a, b)), sd_mul(0.125, sd_add(c, d)));
+        if (variant == MPT_SUBDIV_BLEND_EDGE) {
+            const double s = __hiloint2double(ring[5], ring[4]);
+            out = sd_add(sd_mul(1.0 - s, out), sd_mul(s, sd_mul(0.5, sd_add(a, b))));
+        }
     } else if (kind == MPT_SUBDIV_EDGE_BND) {
         const SdVec a = sd_pos(o, level, pool, T, work, ring[0]), b = sd_pos(o, level, pool, T, work, ring[1]);
         out = sd_mul(0.5, sd_add(a, b));
@@ -86,12 +116,23 @@ __global__ __launch_bounds__(SD_BLOCK) void subdiv_refine_kernel(const float4 *p
         const SdVec v = sd_pos(o, level, pool, T, work, i);
         const SdVec p = sd_pos(o, level, pool, T, work, ring[0]), q = sd_pos(o, level, pool, T, work, ring[n - 1]);
         out = sd_add(sd_mul(0.75, v), sd_mul(0.125, sd_add(p, q)));
+    } else if (variant == MPT_SUBDIV_FIXED) {
+        out = sd_pos(o, level, pool, T, work, i);
     } else {
         const SdVec v = sd_pos(o, level, pool, T, work, i);
         SdVec s = sd_pos(o, level, pool, T, work, ring[0]);
         for (int k = 1; k < n; k++) s = sd_add(s, sd_pos(o, level, pool, T, work, ring[k]));
         const double beta = n == 3 ? 0.1875 : 3.0 / (8.0 * (double)n), w = 1.0 - (double)n * beta;
         out = sd_add(sd_mul(w, v), sd_mul(beta, s));
+        if (variant == MPT_SUBDIV_BLEND_CREASE) {
+            const SdVec p = sd_pos(o, level, pool, T, work, ring[n]), q = sd_pos(o, level, pool, T, work, ring[n + 1]);
+            const double f = __hiloint2double(ring[n + 3], ring[n + 2]);
+            const SdVec C = sd_add(sd_mul(0.75, v), sd_mul(0.125, sd_add(p, q)));
+            out = sd_add(sd_mul(1.0 - f, out), sd_mul(f, C));
+        } else if (variant == MPT_SUBDIV_BLEND_CORNER) {
+            const double f = __hiloint2double(ring[n + 1], ring[n]);
+            out = sd_add(sd_mul(1.0 - f, out), sd_mul(f, v));
+        }
     }
     double *dst = work + o.work_at + o.pos_at[level] + (size_t)i * 3;
     dst[0] = out.x; dst[1] = out.y; dst[2] = out.z;
@@ -102,11 +143,13 @@ __global__ __launch_bounds__(SD_BLOCK) void subdiv_normal_kernel(const MptSubdiv
     const int r = mpt_run_of(runs, nruns);
     const MptSubdivJob &o = jobs[runs[r].item];          // (fields read through the scalar cache: a copy indexed by the level would live in scratch)
     const int i = ((int)blockIdx.x - runs[r].block) * SD_BLOCK + (int)threadIdx.x;
-    if (i >= o.nv[o.levels]) return;
+    if (i >= o.nrec) return;
     const int32_t *__restrict__ T = topo + o.topo_at;
     const double *P = work_in + o.work_at + o.npos_at;       // (a displaced copy's normals are the displaced surface's: displace.hip)
-    const SdVec v = sd_at(P, i);
-    const SdVec N = sd_ring_normal(T, o.nrule_at, P, i, v);
+    // record i is vertex i's; a creased mesh's record is a sector's, whose vertex stands in the table behind the sectors' rules
+    const int32_t vert = o.srule_at == o.nrule_at ? i : T[o.srule_at + 2 * o.nrec + i];
+    const SdVec v = sd_at(P, vert);
+    const SdVec N = sd_ring_normal(T, o.srule_at, P, i, v);
     const double len = sqrt((N.x * N.x + N.y * N.y) + N.z * N.z);
     float4 *dst = (float4 *)(work_out + o.work_at + o.vrec_at) + (size_t)i * 2;
     dst[0] = make_float4((float)v.x, (float)v.y, (float)v.z, (float)(N.x / len));

@@ -1,8 +1,8 @@
 // subdiv_rule.h -- the pure piece of Loop subdivision's host side (scene_subdiv.cpp): the topology of a
 // mesh and of its refinements, the tables subdiv.hip gathers through (the run tables of its launches are run_table.h's).  Plain
 // C++17 with nothing of HIP and no context (as deform_rule.h), so that a stand-alone program can run it under a sanitizer
-// (tools/subdiv_rule_check.cpp); the C ABI has it as mpt_subdiv_topology.  The definition it follows is stated in
-// include/miptina.h and at the top of subdiv.hip.
+// (tools/subdiv_rule_check.cpp); the C ABI has it as mpt_subdiv_topology and, with creases and corners,
+// as mpt_subdiv_topology_creased.  The definition it follows is stated in include/miptina.h and at the top of subdiv.hip.
 #pragma once
 
 #include <algorithm>
@@ -11,13 +11,14 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <unordered_map>
 #include <vector>
 #include "mpt_types.h"          // MPT_SUBDIV_* (plain structures and constants)
 
 enum MptSubdivVerdict {
     MPT_SUBDIV_OK = 0, MPT_SUBDIV_ARGS, MPT_SUBDIV_LEVELS, MPT_SUBDIV_TOO_MANY, MPT_SUBDIV_NOT_FINITE, MPT_SUBDIV_DEGENERATE,
-    MPT_SUBDIV_EDGE_FACES, MPT_SUBDIV_EDGE_DIRECTION, MPT_SUBDIV_FAN
+    MPT_SUBDIV_EDGE_FACES, MPT_SUBDIV_EDGE_DIRECTION, MPT_SUBDIV_FAN, MPT_SUBDIV_CREASE
 };
 
 // What the topology function hands back: per level 0..levels the counts, and ONE block of 32-bit words, the layout the device reads
@@ -30,10 +31,29 @@ enum MptSubdivVerdict {
 //   MPT_SUBDIV_VERT_INT   the n neighbours of an interior vertex in winding order, from the lowest id
 //   MPT_SUBDIV_VERT_BND   the n neighbours of a boundary vertex, from the boundary neighbour that begins the fan to the one that ends it
 //   MPT_SUBDIV_EDGE_INT   a b c d of an interior edge          MPT_SUBDIV_EDGE_BND   a b of a boundary edge
+// The rings of a launch's rules lie behind its rules in the rules' order.
+//
+// A CREASED mesh (a sharpness above zero or a flagged corner; section 3.19.1) has the same block with more in it.  A head is
+// kind | n << 2 | variant << 28, and beside variant 0, the plain rules above, there are
+//   MPT_SUBDIV_VERT_INT | MPT_SUBDIV_BLEND_CREASE   the n neighbours, then p q, the far ends of the vertex's two sharp edges, then the
+//                                                   f64 f (low word first):  ((1 - f) * M) + (f * C)
+//   MPT_SUBDIV_VERT_INT | MPT_SUBDIV_BLEND_CORNER   the n neighbours, then the f64 f:  ((1 - f) * M) + (f * v)
+//   MPT_SUBDIV_VERT_INT | MPT_SUBDIV_FIXED          n = 0: the vertex stays (a flagged corner; three or more sharp edges with f >= 1)
+//   MPT_SUBDIV_EDGE_INT | MPT_SUBDIV_BLEND_EDGE     a b c d, then the f64 s:  ((1 - s) * E) + (s * H)
+// A vertex of two sharp edges with f >= 1 is a plain MPT_SUBDIV_VERT_BND of n = 2, p q; an interior edge with s >= 1 a plain
+// MPT_SUBDIV_EDGE_BND: the crease rules are the boundary's.  Behind the last level's rings (nrule_at: whole rings, as above, which
+// the displacement's direction is taken of) lie
+//   srule_at                      R rules of the last level's RECORDS, then R vertex ids, then the rings of the sectors
+//   face_at                       [F_L][3] RECORD ids
+// The hard edges of the last level cut a vertex's fan into sectors.  Record v < V_L is vertex v's first sector (from the ring's
+// start), or its whole ring where no interior edge of it is hard -- then its rule is the nrule's, ring and all; a further sector is
+// a record from V_L on, in the order of the vertices and then of the ring.  A sector's rule is a MPT_SUBDIV_VERT_BND of the
+// neighbours from its first hard edge to its last (an interior vertex with one hard edge: n + 1 of them, the first again at the
+// end).  An uncreased mesh has nrec = V_L, srule_at = 0 and the block of above, word for word.
 struct MptSubdivTopo {
     int levels = 0;
-    int64_t nv[MPT_SUBDIV_MAX_LEVELS + 1] = {}, ne[MPT_SUBDIV_MAX_LEVELS + 1] = {}, nf[MPT_SUBDIV_MAX_LEVELS + 1] = {};
-    int32_t rule_at[MPT_SUBDIV_MAX_LEVELS + 1] = {}, nrule_at = 0, face_at = 0;
+    int64_t nv[MPT_SUBDIV_MAX_LEVELS + 1] = {}, ne[MPT_SUBDIV_MAX_LEVELS + 1] = {}, nf[MPT_SUBDIV_MAX_LEVELS + 1] = {}, nrec = 0;
+    int32_t rule_at[MPT_SUBDIV_MAX_LEVELS + 1] = {}, nrule_at = 0, face_at = 0, srule_at = 0;
     std::vector<int32_t> words;
 };
 
@@ -137,15 +157,32 @@ inline MptSubdivVerdict build_level(const std::vector<int32_t> &face, int64_t V,
     return MPT_SUBDIV_OK;
 }
 
+struct Spoke { double s; int32_t far; };         // a sharp edge of a vertex: its sharpness at the level, its far end
+
+// the edge of vertices p and q of a level (its edges are sorted by (lower id, higher id))
+inline int64_t edge_of(const Level &lv, int32_t p, int32_t q) {
+    const int32_t lo = std::min(p, q), hi = std::max(p, q);
+    int64_t a = 0, b = (int64_t)lv.edge.size() / 4;
+    while (a < b) {
+        const int64_t m = (a + b) / 2;
+        const int32_t *e = &lv.edge[(size_t)m * 4];
+        if (e[0] < lo || (e[0] == lo && e[1] < hi)) a = m + 1; else b = m;
+    }
+    return a;
+}
+
 struct KeyHash {
     size_t operator()(const uint64_t &k) const { return (size_t)(k * 0x9E3779B97F4A7C15ull >> 17); }
 };
 
 }  // namespace mpt_subdiv_detail
 
-// The topology of the mesh verts [3k][8] (pos3 nrm3 uv2, f32; only the positions are read) and of `levels` Loop refinements of it.
-// A refusal writes its words, which name the face or the vertex, to `why` (always terminated) and leaves `out` unspecified.
-inline MptSubdivVerdict mpt_subdiv_topology_of(const float *verts, int k, int levels, MptSubdivTopo &out, char *why, size_t why_size) {
+// The topology of the mesh verts [3k][8] (pos3 nrm3 uv2, f32; only the positions are read) and of `levels` Loop refinements of it,
+// with the sharpnesses crease [k][3] (edge j of face f runs from corner j to corner (j + 1) % 3; null: all zero) and the corner
+// flags corner [k][3] (null: none).  A refusal writes its words, which name the face and the edge or the vertex, to `why` (always
+// terminated) and leaves `out` unspecified.
+inline MptSubdivVerdict mpt_subdiv_topology_creased_of(const float *verts, int k, int levels, const float *crease, const uint8_t *corner, MptSubdivTopo &out,
+                                                       char *why, size_t why_size) {
     using namespace mpt_subdiv_detail;
     const Say say{ why, why_size };
     if (why && why_size) why[0] = 0;
@@ -153,6 +190,14 @@ inline MptSubdivVerdict mpt_subdiv_topology_of(const float *verts, int k, int le
     if (levels < 1 || levels > MPT_SUBDIV_MAX_LEVELS) return say(MPT_SUBDIV_LEVELS, "subdivision: levels %lld outside [1, %lld]", levels, MPT_SUBDIV_MAX_LEVELS);
     if (((long long)k << (2 * levels)) > MPT_SUBDIV_MAX_FACES)
         return say(MPT_SUBDIV_TOO_MANY, "subdivision: too many faces: %lld at level %lld, at most %lld", (long long)k << (2 * levels), levels, MPT_SUBDIV_MAX_FACES);
+    bool creased = false;
+    for (int64_t s = 0; crease && s < (int64_t)k * 3; s++) {
+        const float x = crease[(size_t)s];
+        if (std::isnan(x)) return say(MPT_SUBDIV_CREASE, "subdivision: the crease of edge %lld of face %lld is not a number", s % 3, s / 3);
+        if (x < 0.0f) return say(MPT_SUBDIV_CREASE, "subdivision: the crease of edge %lld of face %lld is negative", s % 3, s / 3);
+        creased = creased || x > 0.0f;
+    }
+    for (int64_t s = 0; corner && s < (int64_t)k * 3; s++) creased = creased || corner[(size_t)s] != 0;
     // control vertices: corners whose positions are equal as values (-0 is +0), numbered by first appearance
     std::vector<int32_t> face((size_t)k * 3), first_corner;
     {
@@ -183,29 +228,153 @@ inline MptSubdivVerdict mpt_subdiv_topology_of(const float *verts, int k, int le
     std::vector<int32_t> &W = out.words;
     W.assign(first_corner.begin(), first_corner.end());
     int64_t V = (int64_t)first_corner.size();
+    // a control vertex is a corner if any of its welded corners is flagged; the flags pass to even vertices only (their ids stay)
+    std::vector<char> flagged((size_t)V, 0);
+    for (int64_t s = 0; corner && s < (int64_t)k * 3; s++)
+        if (corner[(size_t)s]) flagged[(size_t)face[(size_t)s]] = 1;
+    const double inf = std::numeric_limits<double>::infinity();
+    std::vector<double> cage, below;            // per edge of the level: the CAGE sharpness it inherits (0: an edge new inside a face)
+    std::vector<Spoke> S;
+    std::vector<int32_t> ids, rec_at, cut;
+    int64_t V_below = 0;
     Level lv;
     for (int l = 0; l <= levels; l++) {
         const MptSubdivVerdict verdict = build_level(face, V, lv, say);
         if (verdict != MPT_SUBDIV_OK) return verdict;
         const int64_t E = (int64_t)lv.edge.size() / 4, F = (int64_t)face.size() / 3;
         out.nv[l] = V; out.ne[l] = E; out.nf[l] = F;
+        below.swap(cage);
+        cage.assign((size_t)E, 0.0);
+        if (l == 0) {                           // the two faces on an edge may state different values: the edge takes the larger
+            for (int64_t s = 0; crease && s < F * 3; s++) {
+                double &c = cage[(size_t)lv.face_edge[(size_t)s]];
+                c = std::max(c, (double)crease[(size_t)s]);
+            }
+        } else if (creased) {                   // both halves of a split edge inherit; an edge between two edge vertices is new
+            for (int64_t e = 0; e < E; e++) {
+                const int32_t lo = lv.edge[(size_t)e * 4], hi = lv.edge[(size_t)e * 4 + 1];
+                if (lo < V_below) cage[(size_t)e] = below[(size_t)(hi - V_below)];
+            }
+        }
+        // the sharpness of edge e at this level: s0 - l where that is positive, else 0; a boundary edge counts as inf
+        const auto sharp = [&](int64_t e) {
+            if (lv.edge[(size_t)e * 4 + 3] < 0) return inf;
+            const double s = cage[(size_t)e] - (double)l;
+            return s > 0.0 ? s : 0.0;
+        };
         const bool last = l == levels;
         const int64_t nrules = last ? V : V + E;
-        const size_t rules = W.size(), rings = rules + (size_t)nrules * 2;
+        const size_t rules = W.size();
         if (last) out.nrule_at = (int32_t)rules; else out.rule_at[l + 1] = (int32_t)rules;
-        W.resize(rings + lv.ring.size() + (last ? 0 : (size_t)E * 4));
-        std::copy(lv.ring.begin(), lv.ring.end(), W.begin() + (std::ptrdiff_t)rings);
+        W.resize(rules + (size_t)nrules * 2);
+        // a rule's ids (and the f64 parameter some variants end with, low word first) are appended in the rules' order
+        const auto put = [&](size_t at, int64_t i, int kind, int variant, int64_t n, const std::vector<int32_t> &words) {
+            W[at + (size_t)i * 2] = (int32_t)(kind | n << 2 | variant << MPT_SUBDIV_VARIANT_SHIFT);
+            W[at + (size_t)i * 2 + 1] = (int32_t)W.size();
+            W.insert(W.end(), words.begin(), words.end());
+        };
+        const auto push_f64 = [&](double x) { int32_t w[2]; memcpy(w, &x, 8); ids.push_back(w[0]); ids.push_back(w[1]); };
         for (int64_t v = 0; v < V; v++) {
-            W[rules + (size_t)v * 2] = lv.ring_kind[(size_t)v] | lv.ring_n[(size_t)v] << 2;
-            W[rules + (size_t)v * 2 + 1] = (int32_t)(rings + (size_t)lv.ring_at[(size_t)v]);
+            const int32_t *ring = &lv.ring[(size_t)lv.ring_at[(size_t)v]];
+            const int64_t n = lv.ring_n[(size_t)v];
+            const int kind = lv.ring_kind[(size_t)v];
+            ids.assign(ring, ring + n);
+            if (last || !creased) { put(rules, v, kind, MPT_SUBDIV_PLAIN, n, ids); continue; }
+            S.clear();
+            for (int64_t i = 0; i < n; i++) {
+                const double s = sharp(edge_of(lv, (int32_t)v, ring[i]));
+                if (s > 0.0) S.push_back({ s, ring[i] });
+            }
+            const size_t ks = S.size();
+            const bool bnd = kind == MPT_SUBDIV_VERT_BND;
+            if (v < (int64_t)flagged.size() && flagged[(size_t)v]) { ids.clear(); put(rules, v, MPT_SUBDIV_VERT_INT, MPT_SUBDIV_FIXED, 0, ids); }
+            else if (ks <= 1 || (bnd && ks == 2)) put(rules, v, kind, MPT_SUBDIV_PLAIN, n, ids);       // (a boundary vertex's two boundary edges: today's rule)
+            else if (ks == 2) {
+                const double f = 0.5 * (S[0].s + S[1].s);
+                if (f >= 1.0) { ids = { S[0].far, S[1].far }; put(rules, v, MPT_SUBDIV_VERT_BND, MPT_SUBDIV_PLAIN, 2, ids); }
+                else { ids.push_back(S[0].far); ids.push_back(S[1].far); push_f64(f); put(rules, v, MPT_SUBDIV_VERT_INT, MPT_SUBDIV_BLEND_CREASE, n, ids); }
+            } else {
+                double f = S[0].s + S[1].s;
+                for (size_t i = 2; i < ks; i++) f = f + S[i].s;
+                f = f / (double)ks;
+                if (f >= 1.0) { ids.clear(); put(rules, v, MPT_SUBDIV_VERT_INT, MPT_SUBDIV_FIXED, 0, ids); }
+                else { push_f64(f); put(rules, v, MPT_SUBDIV_VERT_INT, MPT_SUBDIV_BLEND_CORNER, n, ids); }
+            }
         }
-        if (last) break;
-        const size_t erings = rings + lv.ring.size();
+        if (last) {
+            out.nrec = V; out.srule_at = 0;
+            if (!creased) break;
+            // the records of a creased mesh: the hard edges (sharpness > 0 at this level, or a boundary) cut a vertex's fan into
+            // sectors, each an open ring from one hard edge to the next.  Record v is vertex v's first sector -- its whole ring
+            // where no interior edge of it is hard -- and the others follow V_L in the vertices' order
+            const size_t srules = W.size();
+            std::vector<int32_t> sector_of(lv.ring.size(), -1);        // per ring slot i of a vertex: the record of its face (v, r_i, r_i+1)
+            std::vector<int32_t> svert, shead, sring;                  // per record: its vertex, its rule's head, its ring's word (-1: appended below)
+            std::vector<std::vector<int32_t>> extra;
+            svert.resize((size_t)V); shead.resize((size_t)V); sring.resize((size_t)V);
+            for (int64_t v = 0; v < V; v++) {
+                const size_t at = (size_t)lv.ring_at[(size_t)v];
+                const int32_t *ring = &lv.ring[at];
+                const int64_t n = lv.ring_n[(size_t)v];
+                const bool bnd = lv.ring_kind[(size_t)v] == MPT_SUBDIV_VERT_BND;
+                const int64_t nfaces = bnd ? n - 1 : n;
+                cut.clear();
+                for (int64_t i = bnd ? 1 : 0; i < (bnd ? n - 1 : n); i++)
+                    if (sharp(edge_of(lv, (int32_t)v, ring[i])) > 0.0) cut.push_back((int32_t)i);
+                svert[(size_t)v] = (int32_t)v;
+                if (cut.empty()) {
+                    shead[(size_t)v] = W[(size_t)out.nrule_at + (size_t)v * 2]; sring[(size_t)v] = W[(size_t)out.nrule_at + (size_t)v * 2 + 1];
+                    for (int64_t i = 0; i < nfaces; i++) sector_of[at + (size_t)i] = (int32_t)v;
+                    continue;
+                }
+                if (bnd) { cut.insert(cut.begin(), 0); cut.push_back((int32_t)(n - 1)); }
+                const size_t nsectors = bnd ? cut.size() - 1 : cut.size();
+                for (size_t j = 0; j < nsectors; j++) {
+                    const int64_t from = cut[j];
+                    int64_t span = bnd || j + 1 < cut.size() ? cut[j + 1] - from : cut[0] + n - from;
+                    std::vector<int32_t> open;
+                    for (int64_t i = 0; i <= span; i++) open.push_back(ring[(size_t)((from + i) % n)]);
+                    int32_t rec = (int32_t)v;
+                    if (j > 0) { rec = (int32_t)svert.size(); svert.push_back((int32_t)v); shead.push_back(0); sring.push_back(0); }
+                    shead[(size_t)rec] = (int32_t)(MPT_SUBDIV_VERT_BND | (span + 1) << 2);
+                    sring[(size_t)rec] = -1 - (int32_t)extra.size();
+                    extra.push_back(std::move(open));
+                    for (int64_t i = 0; i < span; i++) sector_of[at + (size_t)((from + i) % n)] = rec;
+                }
+            }
+            const size_t R = svert.size();
+            out.srule_at = (int32_t)srules; out.nrec = (int64_t)R;
+            W.resize(srules + R * 2);
+            W.insert(W.end(), svert.begin(), svert.end());
+            for (size_t r = 0; r < R; r++) {
+                W[srules + r * 2] = shead[r];
+                if (sring[r] >= 0) { W[srules + r * 2 + 1] = sring[r]; continue; }
+                W[srules + r * 2 + 1] = (int32_t)W.size();
+                const std::vector<int32_t> &open = extra[(size_t)(-1 - sring[r])];
+                W.insert(W.end(), open.begin(), open.end());
+            }
+            // the face table of a creased mesh indexes records: corner j of a face is the record of its vertex's sector that holds the face
+            std::vector<int32_t> by_record((size_t)F * 3);
+            for (int64_t s = 0; s < F * 3; s++) {
+                const int32_t v = face[(size_t)s], a = face[(size_t)(s - s % 3 + (s + 1) % 3)];
+                const size_t at = (size_t)lv.ring_at[(size_t)v];
+                const int64_t n = lv.ring_n[(size_t)v];
+                int64_t i = 0;
+                while (i < n && lv.ring[at + (size_t)i] != a) i++;
+                by_record[(size_t)s] = sector_of[at + (size_t)i];
+            }
+            face.swap(by_record);
+            break;
+        }
         for (int64_t e = 0; e < E; e++) {
             const bool inner = lv.edge[(size_t)e * 4 + 3] >= 0;
-            for (int a = 0; a < 4; a++) W[erings + (size_t)e * 4 + (size_t)a] = inner || a < 2 ? lv.edge[(size_t)e * 4 + (size_t)a] : 0;
-            W[rules + (size_t)(V + e) * 2] = inner ? (MPT_SUBDIV_EDGE_INT | 4 << 2) : (MPT_SUBDIV_EDGE_BND | 2 << 2);
-            W[rules + (size_t)(V + e) * 2 + 1] = (int32_t)(erings + (size_t)e * 4);
+            const double s = creased ? sharp(e) : 0.0;
+            const bool half = !inner || s >= 1.0;            // 0.5 * (a + b): a boundary edge, and an edge that is sharp at this level
+            ids.assign(4, 0);
+            for (int a = 0; a < 4; a++) ids[(size_t)a] = !half || a < 2 ? lv.edge[(size_t)e * 4 + (size_t)a] : 0;
+            if (half) put(rules, V + e, MPT_SUBDIV_EDGE_BND, MPT_SUBDIV_PLAIN, 2, ids);
+            else if (s == 0.0) put(rules, V + e, MPT_SUBDIV_EDGE_INT, MPT_SUBDIV_PLAIN, 4, ids);
+            else { push_f64(s); put(rules, V + e, MPT_SUBDIV_EDGE_INT, MPT_SUBDIV_BLEND_EDGE, 4, ids); }
         }
         // face f = (v0, v1, v2) becomes (v0, e01, e20), (v1, e12, e01), (v2, e20, e12), (e01, e12, e20)
         std::vector<int32_t> next((size_t)F * 12);
@@ -217,9 +386,15 @@ inline MptSubdivVerdict mpt_subdiv_topology_of(const float *verts, int k, int le
             std::copy(child, child + 12, next.begin() + (std::ptrdiff_t)f * 12);
         }
         face.swap(next);
+        V_below = V;
         V += E;
     }
     out.face_at = (int32_t)W.size();
     W.insert(W.end(), face.begin(), face.end());
     return MPT_SUBDIV_OK;
+}
+
+// The topology of an uncreased mesh: no sharpness, no corner
+inline MptSubdivVerdict mpt_subdiv_topology_of(const float *verts, int k, int levels, MptSubdivTopo &out, char *why, size_t why_size) {
+    return mpt_subdiv_topology_creased_of(verts, k, levels, nullptr, nullptr, out, why, why_size);
 }

@@ -225,12 +225,18 @@ class ModelPool(metaclass=Singleton):
         self._sum = (self._obj_mesh, len(self._obj_mesh), total)
         return total
 
-    def add_subdivision(self, mesh, levels):
+    def add_subdivision(self, mesh, levels, creases=None, corners=None):
         '''`levels` (1 to 5) levels of Loop subdivision for a mesh that has no object yet, before or after its targets and skin: an
         object of it then has 4^levels times the faces, smooth normals and the mesh's texcoords carried down face by face; face g of
         such an object descends from face g >> 2 * levels of the mesh.  Corners with equal positions are one control vertex; the
         mesh must be a manifold with consistent winding (open boundaries are fine), else the library says which face or vertex is
-        not'''
+        not.
+
+        `creases` [k,3]: a sharpness per face edge (edge j of face f runs from corner j to corner (j + 1) % 3) in subdivision levels,
+        as OpenSubdiv's -- 0 smooth, inf always sharp, tools.crease.blender_crease maps Blender's 0..1; an edge takes the larger of
+        what its two faces state; a negative value or a NaN is refused.  `corners` [k,3]: a flag per face corner; a control vertex
+        with a flagged corner stays where it is.  An edge still sharp at the last level (and every boundary edge) splits the normals
+        of the vertices on it.  Both are fixed with the level'''
         mesh, levels = self._fresh_mesh(mesh), int(levels)
         if not 1 <= levels <= SUBDIV_MAX_LEVELS:
             raise ValueError('%d levels: between 1 and %d' % (levels, SUBDIV_MAX_LEVELS))
@@ -238,7 +244,17 @@ class ModelPool(metaclass=Singleton):
             raise ValueError('mesh %d already has a subdivision level' % mesh)
         if self._mesh_faces[mesh] << (2 * levels) >= self.size:
             raise ValueError('too many faces: %d at level %d, room for fewer than %d' % (self._mesh_faces[mesh] << (2 * levels), levels, self.size))
-        ctx().call('mpt_mesh_set_subdivision', mesh, levels)
+        k = self._mesh_faces[mesh]
+        if creases is None and corners is None:
+            ctx().call('mpt_mesh_set_subdivision', mesh, levels)
+        else:
+            cr = None if creases is None else np.ascontiguousarray(creases, np.float32)
+            co = None if corners is None else np.ascontiguousarray(np.asarray(corners) != 0, np.uint8)
+            for name, a in (('creases', cr), ('corners', co)):
+                if a is not None and a.shape != (k, 3):
+                    raise ValueError('%s must be [%d,3], one per face %s, got %s' % (name, k, 'edge' if a is cr else 'corner', a.shape))
+            ctx().call('mpt_mesh_set_subdivision_creased', mesh, levels, None if cr is None else fptr(cr),
+                       None if co is None else co.ctypes.data_as(C.POINTER(C.c_uint8)))
         self._mesh_levels[mesh] = levels
 
     # ---- texture displacement of a subdivided mesh on the device (csrc/displace.hip, DESIGN.md section 3.20: Blender's Displace

@@ -13,8 +13,11 @@ cages: cut into 64 runs of faces they are not manifold).  Every mesh carries a 6
      topology made beforehand) of that object on the host, numpy composition of it, ModelPool().load of the whole model +
      build()                                                (numpy on THIS host's CPU)
   the host time of mpt_mesh_set_subdivision (the topology of one cage, on the host) per mesh.
+With --creases every size is measured twice, a JSON line each: with every grid line (the quads' edges, not
+their diagonals) at sharpness inf, and with none (the uncreased call); the lines also name the records of the last level against
+its vertices, and road b subdivides by tests/subdiv_crease_ref.py.
 
-    python tools/subdiv_bench.py [--quads 7 22] [--levels 2] [--repeat 10] [--repeat-host 2] [--copies 50]
+    python tools/subdiv_bench.py [--quads 7 22] [--levels 2] [--repeat 10] [--repeat-host 2] [--copies 50] [--creases]
 '''
 import argparse
 import json
@@ -31,11 +34,19 @@ from compose_bench import world
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
 import deform_ref                                                             # noqa: E402
 import subdiv_ref                                                             # noqa: E402
+import subdiv_crease_ref                                                      # noqa: E402
 
 JOINTS, NOBJ = 64, 64
 
 
-def bench(quads, levels, repeat, repeat_host, copies):
+def grid_lines(quads):
+    '''[k,3] f32: inf on every edge of subdiv_ref.grid(quads, quads) that is a grid line -- its ends differ by 1 or by quads + 1'''
+    faces = np.array(subdiv_ref.grid(quads, quads)[1])
+    step = np.abs(faces - np.roll(faces, -1, axis=1))
+    return np.where((step == 1) | (step == quads + 1), np.float32(np.inf), np.float32(0)).astype(np.float32)
+
+
+def bench(quads, levels, repeat, repeat_host, copies, creases=None):
     from ptina_amd import _lib
     from ptina_amd.common import ctx, reset_all
     from ptina_amd.multimesh import compose_multiple_meshes
@@ -47,6 +58,7 @@ def bench(quads, levels, repeat, repeat_host, copies):
     sync = lambda: c.call('mpt_synchronize')                                   # noqa: E731
     rec = subdiv_ref.mesh_records(*subdiv_ref.grid(quads, quads))
     k = rec.shape[0] // 3
+    lines = grid_lines(quads) if creases == 'lines' else None
     rigs, worlds, set_ms = [], [], []
     for o in range(NOBJ):
         mesh = pool.add_mesh(*deform_ref.split(rec))
@@ -55,7 +67,10 @@ def bench(quads, levels, repeat, repeat_host, copies):
         wt = (wt / wt.sum(axis=2, keepdims=True)).astype(np.float32)
         pool.add_skin(mesh, jt, wt, JOINTS)
         t0 = time.perf_counter()
-        pool.add_subdivision(mesh, levels)
+        if lines is None:
+            pool.add_subdivision(mesh, levels)
+        else:
+            pool.add_subdivision(mesh, levels, creases=lines)
         set_ms.append((time.perf_counter() - t0) * 1e3)
         worlds.append(world(g))
         pool.add_object(mesh, worlds[-1], -1)
@@ -74,6 +89,10 @@ def bench(quads, levels, repeat, repeat_host, copies):
     size = pool.nfaces
     out = {'metric': 'subdivided_pose_change_ms', 'cage_faces': k * NOBJ, 'faces': size, 'objects': NOBJ, 'levels': levels, 'joints': JOINTS,
            'chunk_items': _lib.SUBDIV_CHUNK, 'repeat': repeat, 'host': platform.processor() or platform.machine(), 'columns': ['wall median', 'wall min']}
+    if creases is not None:
+        _, _, tables = _lib.subdiv_topology_creased(rec, levels, lines)
+        out['creases'] = 'every grid line inf' if creases == 'lines' else 'none'
+        out['records, vertices of the last level (one cage)'] = [len(tables['records']), int(tables['counts'][levels, 0])]
     out['mpt_mesh_set_subdivision of one cage of %d faces (host ms: median, least)' % k] = [round(median(set_ms), 3), round(min(set_ms), 3)]
     emit = {}
     for name, objs in (('every object', range(NOBJ)), ('one object', [NOBJ // 2])):
@@ -121,17 +140,21 @@ def bench(quads, levels, repeat, repeat_host, copies):
     model_v, model_m = pool.to_numpy()
     per = size // NOBJ
     jt, wt = rigs[one]
-    topo = subdiv_ref.topology(rec, levels)
+    topo = subdiv_ref.topology(rec, levels) if creases is None else subdiv_crease_ref.topology(rec, levels, lines)
 
     def host_road():
         copy = deform_ref.deform(rec, None, None, jt.reshape(k * 3, 4), wt.reshape(k * 3, 4), palette())
-        fine = subdiv_ref.subdivide(rec, levels, topo, control=copy)
+        if creases is None:
+            fine = subdiv_ref.subdivide(rec, levels, topo, control=copy)
+        else:
+            fine = subdiv_crease_ref.subdivide(rec, levels, topo=topo, control=copy)
         v, _ = compose_multiple_meshes([(*deform_ref.split(fine), worlds[one], -1)])
         model_v[3 * per * one:3 * per * (one + 1)] = v
         pool.load(model_v, model_m)
         tree.build()
         sync()
-    out['b numpy skinning + numpy subdivision + load + build (host CPU: %s)' % out['host']] = list(wall_ms(host_road, repeat_host))
+    if repeat_host > 0:
+        out['b numpy skinning + numpy subdivision + load + build (host CPU: %s)' % out['host']] = list(wall_ms(host_road, repeat_host))
     print(json.dumps(out), flush=True)
     reset_all()
 
@@ -143,9 +166,11 @@ def main():
     ap.add_argument('--repeat', type=int, default=10)
     ap.add_argument('--repeat-host', type=int, default=2)
     ap.add_argument('--copies', type=int, default=50)
+    ap.add_argument('--creases', action='store_true', help='measure every size with every grid line at sharpness inf, and with none')
     args = ap.parse_args()
     for quads in args.quads:
-        bench(quads, args.levels, args.repeat, args.repeat_host, args.copies)
+        for creases in (('lines', 'none') if args.creases else (None,)):
+            bench(quads, args.levels, args.repeat, args.repeat_host, args.copies, creases)
 
 
 if __name__ == '__main__':

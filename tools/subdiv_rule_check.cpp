@@ -8,6 +8,11 @@
 // closed fans of valence 7 and 12, the open 5 x 5 grid, the open cylinder) at levels 1 to 4, from record arrays that are exactly as
 // long as the function may read: counts (Euler's number on the closed ones, four faces per face), every id of every table inside
 // its level, every ring inside the block; every refusal, with message buffers of every size (cut, terminated, never overrun).
+// The same fixtures CREASED, from crease and corner arrays that are exactly as long as the function may
+// read -- every edge inf; a pattern of 0, 0.25, 0.5, 1, 1.5, 2.5 and inf that the two faces on an edge state differently, with every
+// seventh corner flagged --: every variant's ids and parameter inside the block, a blend's parameter inside (0, 1), every record's
+// vertex and ring inside the last level, every face corner in a sector of its own vertex that holds the face; all-zero arrays give
+// the uncreased block, word for word; a negative sharpness and a NaN are refused by face and edge.
 
 #include "../ptina_amd/csrc/subdiv_rule.h"
 #include <cstdlib>
@@ -97,6 +102,82 @@ static void check_rules(const MptSubdivTopo &t, int32_t at, int64_t n, int64_t n
     }
 }
 
+// the rules of a creased mesh: as check_rules, with the variants, their further ids and their parameters
+static void check_creased_rules(const MptSubdivTopo &t, int32_t at, int64_t n, int64_t nverts, int64_t ids) {
+    const int64_t W = (int64_t)t.words.size();
+    CHECK(at >= 0 && at + 2 * n <= W);
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t head = t.words[(size_t)(at + 2 * i)], ring = t.words[(size_t)(at + 2 * i + 1)];
+        const int kind = head & 3, variant = head >> MPT_SUBDIV_VARIANT_SHIFT & 7, len = head >> 2 & MPT_SUBDIV_N_MASK;
+        CHECK(head >= 0 && variant <= MPT_SUBDIV_FIXED);
+        CHECK(i < nverts ? kind == MPT_SUBDIV_VERT_INT || kind == MPT_SUBDIV_VERT_BND : kind == MPT_SUBDIV_EDGE_INT || kind == MPT_SUBDIV_EDGE_BND);
+        const bool vert = kind == MPT_SUBDIV_VERT_INT, edge = kind == MPT_SUBDIV_EDGE_INT;
+        CHECK(variant == MPT_SUBDIV_PLAIN || vert || (edge && variant == MPT_SUBDIV_BLEND_EDGE));
+        const int more = vert && variant == MPT_SUBDIV_BLEND_CREASE ? 2 : 0;
+        const bool blends = (vert && (variant == MPT_SUBDIV_BLEND_CREASE || variant == MPT_SUBDIV_BLEND_CORNER)) || (edge && variant == MPT_SUBDIV_BLEND_EDGE);
+        const int64_t words = len + more + (blends ? 2 : 0);
+        CHECK(ring >= 0 && (int64_t)ring + words <= W);
+        if (ring < 0 || (int64_t)ring + words > W) continue;
+        CHECK(vert && variant == MPT_SUBDIV_FIXED ? len == 0 : edge ? len == 4 : len >= 2);
+        for (int k = 0; k < len + more; k++) CHECK(t.words[(size_t)ring + (size_t)k] >= 0 && t.words[(size_t)ring + (size_t)k] < ids);
+        if (blends) {
+            double f;
+            std::memcpy(&f, &t.words[(size_t)ring + (size_t)(len + more)], 8);
+            CHECK(f > 0.0 && f < 1.0);
+        }
+    }
+}
+
+static void check_creased(const Mesh &m, const std::vector<float> &rec, int levels, const std::vector<float> &crease, const std::vector<uint8_t> &corner, bool hard) {
+    const int k = (int)(m.f.size() / 3);
+    MptSubdivTopo t, plain;
+    char why[64];
+    const MptSubdivVerdict v = mpt_subdiv_topology_creased_of(rec.data(), k, levels, crease.data(), corner.empty() ? nullptr : corner.data(), t, why, sizeof why);
+    CHECK(v == MPT_SUBDIV_OK && why[0] == 0);
+    if (v != MPT_SUBDIV_OK) { std::fprintf(stderr, "%s creased at level %d: %s\n", m.name.c_str(), levels, why); return; }
+    CHECK(mpt_subdiv_topology_of(rec.data(), k, levels, plain, nullptr, 0) == MPT_SUBDIV_OK);
+    const int64_t V = t.nv[levels], W = (int64_t)t.words.size();
+    for (int l = 0; l <= levels; l++) {
+        CHECK(t.nv[l] == plain.nv[l] && t.ne[l] == plain.ne[l] && t.nf[l] == plain.nf[l]);
+        if (l > 0) check_creased_rules(t, t.rule_at[l], t.nv[l], t.nv[l - 1], t.nv[l - 1]);
+    }
+    check_rules(t, t.nrule_at, V, V, V, m.closed);
+    CHECK(t.srule_at > t.nrule_at && t.nrec >= V && (int64_t)t.srule_at + 3 * t.nrec <= W);
+    if (hard && k > 1) CHECK(t.nrec > V);                          // (an interior edge that stays hard splits the vertices on it)
+    if (t.srule_at <= 0 || (int64_t)t.srule_at + 3 * t.nrec > W) return;
+    check_rules(t, t.srule_at, t.nrec, t.nrec, V, false);
+    const int32_t *vert = &t.words[(size_t)t.srule_at + (size_t)t.nrec * 2];
+    for (int64_t r = 0; r < t.nrec; r++) CHECK(r < V ? vert[r] == r : vert[r] >= 0 && vert[r] < V);
+    CHECK((int64_t)t.face_at + 3 * t.nf[levels] == W);
+    const int32_t *pf = &plain.words[(size_t)plain.face_at];
+    for (int64_t s = 0; s < 3 * t.nf[levels]; s++) {
+        const int32_t r = t.words[(size_t)t.face_at + (size_t)s];
+        CHECK(r >= 0 && r < t.nrec);
+        if (r < 0 || r >= t.nrec) continue;
+        CHECK(vert[r] == pf[s]);                                     // the record is of the corner's own vertex ...
+        const int32_t head = t.words[(size_t)t.srule_at + (size_t)r * 2], ring = t.words[(size_t)t.srule_at + (size_t)r * 2 + 1];
+        const int len = head >> 2, faces = (head & 3) == MPT_SUBDIV_VERT_BND ? len - 1 : len;
+        const int32_t a = pf[s - s % 3 + (s + 1) % 3], b = pf[s - s % 3 + (s + 2) % 3];
+        bool held = false;                                            // ... and its sector holds the face (v, a, b)
+        for (int i = 0; i < faces && !held; i++) held = t.words[(size_t)ring + (size_t)i] == a && t.words[(size_t)ring + (size_t)((i + 1) % len)] == b;
+        CHECK(held);
+    }
+}
+
+static MptSubdivVerdict crease_refusal(const std::vector<float> &rec, const std::vector<float> &crease, const char *words) {
+    MptSubdivTopo t;
+    const int k = (int)(rec.size() / 24);
+    const MptSubdivVerdict want = mpt_subdiv_topology_creased_of(rec.data(), k, 2, crease.data(), nullptr, t, nullptr, 0);
+    for (size_t cap = 0; cap <= 240; cap += cap < 8 ? 1 : 29) {
+        std::vector<char> why(cap, 'x');
+        CHECK(mpt_subdiv_topology_creased_of(rec.data(), k, 2, crease.data(), nullptr, t, cap ? why.data() : nullptr, cap) == want);
+        if (!cap) continue;
+        CHECK(std::memchr(why.data(), 0, cap) != nullptr);
+        if (cap >= 200) CHECK(!std::strncmp(why.data(), "subdivision: ", 13) && std::strstr(why.data(), words) != nullptr);
+    }
+    return want;
+}
+
 static MptSubdivVerdict refusal(const std::vector<float> &rec, int levels, const char *words) {
     MptSubdivTopo t;
     const int k = (int)(rec.size() / 24);
@@ -145,6 +226,24 @@ int main() {
             for (int64_t s = 0; s < 3 * t.nf[levels]; s++) CHECK(t.words[(size_t)t.face_at + (size_t)s] >= 0 && t.words[(size_t)t.face_at + (size_t)s] < t.nv[levels]);
         }
     }
+    int creased = 0;
+    for (const Mesh &m : fixtures()) {
+        const std::vector<float> rec = records(m);
+        const size_t n = m.f.size();                                  // 3 k: one sharpness per face edge, one flag per face corner
+        const float inf = std::numeric_limits<float>::infinity();
+        static const float some[7] = { 0.0f, 0.25f, 0.5f, 1.0f, 1.5f, 2.5f, inf };
+        std::vector<float> every(n, inf), pattern(n), zero(n, 0.0f);
+        std::vector<uint8_t> flags(n, 0), none(n, 0);
+        for (size_t s = 0; s < n; s++) { pattern[s] = some[(s * 5 + s / 3) % 7]; flags[s] = s % 7 == 3; }
+        for (int levels = 1; levels <= 4; levels++) {
+            check_creased(m, rec, levels, every, {}, true); creased++;
+            check_creased(m, rec, levels, pattern, flags, false); creased++;
+            MptSubdivTopo plain, t;
+            CHECK(mpt_subdiv_topology_of(rec.data(), (int)(n / 3), levels, plain, nullptr, 0) == MPT_SUBDIV_OK);
+            CHECK(mpt_subdiv_topology_creased_of(rec.data(), (int)(n / 3), levels, zero.data(), none.data(), t, nullptr, 0) == MPT_SUBDIV_OK);
+            CHECK(t.words == plain.words && t.srule_at == 0 && t.nrec == plain.nv[levels] && t.nrule_at == plain.nrule_at && t.face_at == plain.face_at);
+        }
+    }
     {   // k = 0 is a mesh and stays one
         MptSubdivTopo t;
         CHECK(mpt_subdiv_topology_of(nullptr, 0, 3, t, nullptr, 0) == MPT_SUBDIV_OK && t.words.empty() && t.nf[3] == 0);
@@ -172,6 +271,21 @@ int main() {
     CHECK(refusal(soup({ 0, 1, 2 }), 0, "levels 0 outside [1, 5]") == MPT_SUBDIV_LEVELS); refusals++;
     CHECK(refusal(soup({ 0, 1, 2 }), 6, "levels 6 outside") == MPT_SUBDIV_LEVELS); refusals++;
     {
+        const std::vector<float> rec = soup({ 0, 1, 2, 0, 2, 4 });
+        for (size_t where : { (size_t)0, (size_t)5 }) {                          // the first and the last sharpness read
+            std::vector<float> crease(6, 0.5f);
+            const std::string edge = "the crease of edge " + std::to_string(where % 3) + " of face " + std::to_string(where / 3);
+            crease[where] = -0.25f;
+            CHECK(crease_refusal(rec, crease, (edge + " is negative").c_str()) == MPT_SUBDIV_CREASE); refusals++;
+            crease[where] = -inf;
+            CHECK(crease_refusal(rec, crease, (edge + " is negative").c_str()) == MPT_SUBDIV_CREASE); refusals++;
+            crease[where] = nan;
+            CHECK(crease_refusal(rec, crease, (edge + " is not a number").c_str()) == MPT_SUBDIV_CREASE); refusals++;
+        }
+        MptSubdivTopo t;
+        CHECK(mpt_subdiv_topology_creased_of(nullptr, 0, 2, nullptr, nullptr, t, nullptr, 0) == MPT_SUBDIV_OK && t.words.empty());
+    }
+    {
         MptSubdivTopo t;
         CHECK(mpt_subdiv_topology_of(nullptr, 1, 1, t, nullptr, 0) == MPT_SUBDIV_ARGS);
         CHECK(mpt_subdiv_topology_of(nullptr, -1, 1, t, nullptr, 0) == MPT_SUBDIV_ARGS);
@@ -179,6 +293,6 @@ int main() {
         CHECK(mpt_subdiv_topology_of(one, 20000, 5, t, nullptr, 0) == MPT_SUBDIV_TOO_MANY);      // refused before anything is read
     }
 
-    std::printf("subdiv_rule_check: %d topologies, %d refusals, %d failures\n", topologies, refusals, failures);
+    std::printf("subdiv_rule_check: %d topologies, %d creased, %d refusals, %d failures\n", topologies, creased, refusals, failures);
     return failures ? EXIT_FAILURE : EXIT_SUCCESS;
 }
