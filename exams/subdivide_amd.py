@@ -9,8 +9,10 @@ tree is fitted to them (csrc/refit.hip) -- topology and face count never change.
 With --creases two cubes of 12 triangles stand beside the tube: one with Blender's edge crease 1 on its 12 edges
 (tools.crease.blender_crease: sharpness inf), which stays a cube with a flat normal per face, and one without, which comes out a
 blob.
+With --scheme catmull-clark the tube's 64 quads and the cubes' six are the cages (each quad is stored as the fan of two triangles it
+already is), subdivided as Blender's Subdivision Surface modifier does: no diagonal shows.
 
-    python exams/subdivide_amd.py [--frames 12] [--levels 3] [--size 256] [--spp 8] [--out DIR] [--creases]
+    python exams/subdivide_amd.py [--frames 12] [--levels 3] [--size 256] [--spp 8] [--out DIR] [--creases] [--scheme catmull-clark]
 '''
 import argparse
 import os
@@ -33,7 +35,9 @@ ap.add_argument('--size', type=int, default=256)
 ap.add_argument('--spp', type=int, default=8)
 ap.add_argument('--out', default='.')
 ap.add_argument('--creases', action='store_true', help='a creased cube beside a smooth one')
+ap.add_argument('--scheme', default='loop', choices=('loop', 'catmull-clark'))
 args = ap.parse_args()
+CC = args.scheme == 'catmull-clark'
 
 JOINTS, HEIGHT, RADIUS, RINGS, SIDES = 8, 2.4, 0.25, 8, 8
 
@@ -107,13 +111,17 @@ p, n, joints, weights = cage()
 mesh = pool.add_mesh(p, n)
 pool.add_skin(mesh, joints, weights, JOINTS)
 if args.levels:
-    pool.add_subdivision(mesh, args.levels)
+    pool.add_subdivision(mesh, args.levels, scheme=args.scheme, polys=np.full(RINGS * SIDES, 4, np.int32) if CC else None)
 obj = pool.add_object(mesh, shift(0.0, 0.0, -0.3), 3)
 if args.creases and args.levels:
     cp, cn, crease = cube(0.3)
     for x, creases in ((-0.8, crease), (0.8, None)):
         m = pool.add_mesh(cp, cn)
-        pool.add_subdivision(m, args.levels, creases=creases)
+        if CC:                                # the six quads: their four edges each, all of Blender's crease 1
+            pool.add_subdivision(m, args.levels, creases=None if creases is None else np.full(24, blender_crease(1.0)), scheme=args.scheme,
+                                 polys=np.full(6, 4, np.int32))
+        else:
+            pool.add_subdivision(m, args.levels, creases=creases)
         pool.add_object(m, shift(x, 0.3, 0.2), 3)
 pool.compose()
 BVHTree().build()

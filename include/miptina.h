@@ -701,6 +701,54 @@ int mpt_mesh_set_subdivision_creased(mpt_ctx *ctx, int mesh_id, int levels, cons
 int mpt_subdiv_topology_creased(const float *verts /* [3k][8] */, int k, int levels, const float *crease, const uint8_t *corner, int64_t *counts,
                                 int32_t *offsets /* [11] */, int32_t *words, int64_t cap_words, int64_t *need_words, char *why, int why_size);
 
+/* Catmull-Clark subdivision of a cage of quads and polygons (Blender's Subdivision Surface modifier), the second scheme a mesh of the
+ * pool may carry: what is said of the subdivided copy, of mpt_compose and of the read-backs above holds for it, a displacement and a
+ * scatter stand behind it as behind a Loop mesh, and the creases and corners are those of above.
+ * mpt_mesh_set_subdivision_cc: polys [m] holds the corner count n_j of each polygon, 3 <= n_j <= 64, sum (n_j - 2) = k.  Polygon j
+ *   is stored as n_j - 2 consecutive triangles of the mesh, a fan about its first corner: triangle i is (c_0, c_i+1, c_i+2).  NULL:
+ *   every triangle is a polygon (m is ignored).  crease and corner are flat [sum n_j]: entry i of polygon j is the edge from corner i
+ *   to corner (i + 1) % n_j, respectively corner i; either may be NULL.  An object of the mesh has F = 2 (sum n_j) 4^(L - 1) faces
+ *   (an all-quad cage: k 4^L).  Refuses what mpt_mesh_set_subdivision_creased refuses (a crease is named by polygon and edge), and:
+ *   polys that do not hold k triangles; an n outside [3, 64]; a triangle that does not continue its polygon's fan, named by face and
+ *   polygon; a polygon with two corners on one vertex.  The mesh stays as it was.
+ * The definition.  Arithmetic, weld, first-corner rule, ids of control vertices and edge numbering are those of above.
+ *   Level l -> l + 1, ids: even vertices keep their ids; the edge point of edge e is V_l + e; the face point of face j is
+ *     V_l + E_l + j.
+ *   Face split: polygon or quad j of corners c_0 .. c_n-1 becomes n quads, quad i (c_i, e(c_i, c_i+1), f_j, e(c_i-1, c_i)); windings
+ *     are kept.  At level 1 the quads of polygon j start at the sum of n_j' over j' < j; from level 1 on quad q becomes 4q .. 4q + 3.
+ *   Emitted triangles: quad q = (v0, v1, v2, v3) of the last level is faces 2q (v0, v1, v2) and 2q + 1 (v0, v2, v3): face g of an
+ *     object descends from level-1 quad (g >> 1) >> 2 (L - 1).
+ *   Face point: F = (((c_0 + c_1) + c_2) + ...) / n.
+ *   Edges (a the lower endpoint id, b the higher, F1 the point of the face that runs a -> b, F2 of the other):
+ *     interior edge    E = 0.25 * ((a + b) + (F1 + F2))                  boundary edge    0.5 * (a + b)
+ *   Ring of a vertex: its edge neighbours in winding order (in face (v, a, ..., b), a comes before b), the start as above.
+ *   Interior vertex of valence n:  M = (((n - 2.0) / n) * v) + ((1.0 / (n * n)) * (S_r + S_f)),  S_r = ((r_0 + r_1) + r_2) + ... the
+ *     ring left to right, S_f = ((F_0 + F_1) + F_2) + ... the face points in the same order, F_i the face between r_i and r_i+1.
+ *   Boundary vertex: (0.75 * v) + (0.125 * (p + q)), p and q the first and the last of its ring; no corner rule unless it is flagged.
+ *   A face point in an edge's or a vertex's rule is the value the face rule gives, bit for bit (a lane evaluates it again).
+ *   Creases and corners: the text of above with E and M as here.  The halves of a split edge inherit, the edges new inside a face
+ *     (edge point to face point) have sharpness 0, boundary edges count as inf; H, C, the blends by s and f and the cases k <= 1, 2 and
+ *     >= 3 are those of above; a flagged vertex stays; where f >= 1 or s >= 1 no blend is evaluated.
+ *   Normals at the last level: the sum of above over the ring of EDGE neighbours, N += cross(r_i - v, r_i+1 - v), one term per quad
+ *     on the vertex, cut into sectors by the hard edges as above.  A displacement takes its direction from the whole ring.
+ *   Texcoords are face-varying: a face point's uv is ((u_0 + u_1) + ...) / n, an edge's 0.5 * (u_i + u_j); a child quad takes its uvs
+ *     by the split rule, level by level from the polygon's corner uvs.  Corner c_0's and c_1's uv are read from triangle 0 of the fan,
+ *     corner c_i+2's from corner 2 of triangle i.
+ * mpt_subdiv_topology_cc: the topology as a pure function, with offsets [12].  counts holds vertices, edges and faces per level
+ *   (polygons at level 0, quads from level 1).  The block is mpt_subdiv_topology_creased's with these differences.  offsets[l]: the
+ *   V + E + F rules of level l - 1's vertices, edges and then FACES.  A boundary vertex (kind 1), a boundary edge or one with s >= 1
+ *   (kind 3, variant 0), a vertex that stays (kind 0 variant 3) and every rule of the last level's rings and records are as above;
+ *   Catmull-Clark's own rules have bit 2 of the variant (4) set beside the blend: kind 3 variant 4, a face point, its n corners in
+ *   the face's order; kind 2 variant 4 (4 | 1: then the f64 s), n = 4: a b, then the ids at level l of the face points F1 and F2 --
+ *   a face point's rule is rule `id` of the same level; kind 0 variant 4, the n neighbours, then n face point ids (4 | 1: then p q
+ *   and the f64 f; 4 | 2: then the f64 f).  offsets[11]: [Q_1][2], per quad of level 1 the first triangle of its polygon in the
+ *   mesh and n | i << 8.  offsets[7]: [2 Q_L][3] record ids, the emitted triangles.  Returns what mpt_subdiv_topology_creased
+ *   returns, or 10: polys that are not the mesh's triangles, an n outside [3, 64] or a triangle that does not continue its fan. */
+int mpt_mesh_set_subdivision_cc(mpt_ctx *ctx, int mesh_id, int levels, const int32_t *polys /* [m] or NULL */, int m, const float *crease /* [sum n_j] or NULL */,
+                                const uint8_t *corner /* [sum n_j] or NULL */);
+int mpt_subdiv_topology_cc(const float *verts /* [3k][8] */, int k, int levels, const int32_t *polys, int m, const float *crease, const uint8_t *corner,
+                           int64_t *counts, int32_t *offsets /* [12] */, int32_t *words, int64_t cap_words, int64_t *need_words, char *why, int why_size);
+
 /* Texture displacement on the device as a property of a SUBDIVIDED mesh of the pool: the third step of the modifier stack armature ->
  * subdivision surface -> displace.  mpt_compose evaluates it on the vertices of the mesh's last level, behind the last refine launch
  * and before the normals, so the subdivided copy's normals are the displaced surface's.  Topology and face count stay constant: a

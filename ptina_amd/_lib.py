@@ -285,6 +285,8 @@ SIGNATURES = {
     'mpt_subdiv_topology': (_i, [_fp, _i, _i, C.POINTER(C.c_int64), _ip, _ip, C.c_int64, C.POINTER(C.c_int64), C.c_char_p, _i]),
     'mpt_mesh_set_subdivision_creased': (_i, [_vp, _i, _i, _fp, C.POINTER(C.c_uint8)]),
     'mpt_subdiv_topology_creased': (_i, [_fp, _i, _i, _fp, C.POINTER(C.c_uint8), C.POINTER(C.c_int64), _ip, _ip, C.c_int64, C.POINTER(C.c_int64), C.c_char_p, _i]),
+    'mpt_mesh_set_subdivision_cc': (_i, [_vp, _i, _i, _ip, _i, _fp, C.POINTER(C.c_uint8)]),
+    'mpt_subdiv_topology_cc': (_i, [_fp, _i, _i, _ip, _i, _fp, C.POINTER(C.c_uint8), C.POINTER(C.c_int64), _ip, _ip, C.c_int64, C.POINTER(C.c_int64), C.c_char_p, _i]),
     'mpt_subdiv_plan': (_i, [_ip, _ip, _i, _ip, C.POINTER(C.c_int64), _i, C.POINTER(C.c_int64)]),
     'mpt_mesh_set_displacement': (_i, [_vp, _i, _i, _i, _i, C.c_double, C.c_double]),
     'mpt_mesh_set_displacement_params': (_i, [_vp, _i, C.c_double, C.c_double]),
@@ -578,7 +580,70 @@ def subdiv_topology_creased(rec, levels, creases=None, corners=None):
                                                offsets=off.copy())
 
 
-DISPLACE_MODES = ('normal', 'vector')                                    # include/miptina.h MPT_DISPLACE_NORMAL, _VECTOR
+SUBDIV_CC, SUBDIV_MAX_CORNERS = 4, 64                                    # csrc/mpt_types.h MPT_SUBDIV_CC (a bit of the variant), MPT_SUBDIV_MAX_CORNERS
+SUBDIV_SCHEMES = ('loop', 'catmull-clark')
+
+
+def subdiv_topology_cc(rec, levels, polys=None, creases=None, corners=None):
+    '''mpt_subdiv_topology_cc (no context, no GPU) of the records rec [3k,8] f32 -- the fans of the polygons polys [m] (None: every
+    triangle a polygon) --, the sharpnesses creases and the flags corners, flat over the polygons' corners (either None):
+    (verdict, words, tables) as subdiv_topology_creased.  counts [levels+1,3] are vertices, edges and faces (polygons at level 0,
+    quads from level 1); rules[l] holds the vertices', the edges' and then the faces' rules of level l - 1 as (kind, variant, [ids],
+    parameter), a Catmull-Clark rule with SUBDIV_CC in its variant: a face point's ids are its corners, an interior edge's a b and
+    two face point ids, an interior vertex's its n neighbours, n face point ids and, blending between two creases, p q; quads1
+    [Q_1,2] is the table of level-1 quads (first triangle of the polygon, n | i << 8); faces [2 Q_L,3] of record ids'''
+    rec = np.ascontiguousarray(rec, np.float32)
+    if rec.ndim != 2 or rec.shape[1] != 8 or rec.shape[0] % 3:
+        raise ValueError('records must be [3k,8], got %s' % (rec.shape,))
+    k, levels = rec.shape[0] // 3, int(levels)
+    po = None if polys is None else np.ascontiguousarray(polys, np.int32).reshape(-1)
+    m = k if po is None else int(po.size)
+    ncorners = 3 * k if po is None else int(np.clip(po, 0, None).sum())
+    cr = None if creases is None else np.ascontiguousarray(creases, np.float32).reshape(-1)
+    co = None if corners is None else np.ascontiguousarray(np.asarray(corners).reshape(-1) != 0, np.uint8)
+    for name, a in (('creases', cr), ('corners', co)):
+        if a is not None and a.size != ncorners:
+            raise ValueError('%s must hold %d values, one per polygon corner, got %d' % (name, ncorners, a.size))
+    args = (fptr(rec), k, levels, None if po is None else iptr(po), m, None if cr is None else fptr(cr),
+            None if co is None else co.ctypes.data_as(C.POINTER(C.c_uint8)))
+    lib = load_library()
+    why = C.create_string_buffer(240)
+    counts, off, need = np.zeros((max(levels, 0) + 1, 3), np.int64), np.zeros(12, np.int32), C.c_int64(0)
+    cp = counts.ctypes.data_as(C.POINTER(C.c_int64))
+    rc = lib.mpt_subdiv_topology_cc(*args, cp, iptr(off), None, 0, C.byref(need), why, len(why))
+    if rc:
+        return rc, why.value.decode(), None
+    w = np.zeros(max(int(need.value), 1), np.int32)
+    rc = lib.mpt_subdiv_topology_cc(*args, cp, iptr(off), iptr(w), int(need.value), C.byref(need), why, len(why))
+    assert rc == 0
+
+    def rule(h, r):
+        kind, variant, n = h & 3, h >> 28 & 7, h >> 2 & (1 << 26) - 1
+        cc, blend = variant & SUBDIV_CC, variant & 3
+        nids = n
+        if cc and kind == 0:
+            nids = 2 * n + (2 if blend == 1 else 0)
+        blends = cc and ((kind == 0 and blend in (1, 2)) or (kind == 2 and blend == 1))
+        return kind, variant, w[r:r + nids].tolist(), float(w[r + nids:r + nids + 2].view(np.float64)[0]) if blends else None
+
+    def rules(at, n):
+        return [rule(int(h), int(r)) for h, r in zip(w[at:at + 2 * n:2], w[at + 1:at + 2 * n:2])]
+    vl, nq = int(counts[levels, 0]), int(counts[levels, 2])
+    rings = [(kind, ids) for kind, _, ids, _ in rules(int(off[6]), vl)]
+    nrec = int(off[10])
+    if off[9]:
+        vert = w[int(off[9]) + 2 * nrec:int(off[9]) + 3 * nrec].tolist()
+        records = [(v, kind, ids) for v, (kind, _, ids, _) in zip(vert, rules(int(off[9]), nrec))]
+    else:
+        records = [(v, kind, ids) for v, (kind, ids) in enumerate(rings)]
+    nq1 = int(counts[1, 2])
+    return 0, w[:int(need.value)].copy(), dict(counts=counts, first_corner=w[:int(counts[0, 0])].copy(),
+                                               rules={l: rules(int(off[l]), int(counts[l, 0])) for l in range(1, levels + 1)},
+                                               rings=rings, records=records, quads1=w[int(off[11]):int(off[11]) + 2 * nq1].reshape(nq1, 2).copy(),
+                                               faces=w[int(off[7]):int(off[7]) + 6 * nq].reshape(2 * nq, 3).copy(), offsets=off.copy())
+
+
+DISPLACE_MODES = ('normal', 'vector')                                   # include/miptina.h MPT_DISPLACE_NORMAL, _VECTOR
 DISPLACE_CHANNELS = ('r', 'g', 'b', 'a', 'mean')                         # ... MPT_DISPLACE_R .. MPT_DISPLACE_MEAN
 DISPLACE_MAX_UV = 2.0 ** 20                                              # csrc/displace_rule.h MPT_DISPLACE_MAX_UV
 

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(DP_BLOCK) void displace_kernel(const float4 *__rest
     // the height: the first corner's uv, then the four texels around it
     const int32_t corner = topo[q.corner_at + i];
     const int g = corner / 3, c = corner - 3 * g;
-    const SdFaceUv t = sd_face_uv(pool, o.src_vert, o.levels, g);
+    const SdFaceUv t = sd_copy_face_uv(pool, o, topo, g);            // (by the mesh's scheme: a Catmull-Clark copy's quads, section 3.19.2)
     const double u = c == 0 ? t.u0 : c == 1 ? t.u1 : t.u2, v = c == 0 ? t.v0 : c == 1 ? t.v1 : t.v2;
     const double px = u * (double)(q.nx - 1), py = v * (double)(q.ny - 1);
     const double fx = floor(px), fy = floor(py);

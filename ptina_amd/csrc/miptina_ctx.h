@@ -112,7 +112,7 @@ MPT_KERNEL_API hipError_t mpt_launch_deform(float *pool, const MptDeformObj *obj
                                             hipStream_t stream);
 // subdiv.hip: the subdivided copies of a launch's jobs -- one refine launch per level, the last level's normals, the records (mpt_compose)
 MPT_KERNEL_API hipError_t mpt_launch_subdiv_refine(const float *pool, const MptSubdivJob *jobs, const MptRun *runs, int nruns, int blocks,
-                                                   int level, const int32_t *topo, double *work, hipStream_t stream);
+                                                   int level, int cc, const int32_t *topo, double *work, hipStream_t stream);
 MPT_KERNEL_API hipError_t mpt_launch_subdiv_normals(const MptSubdivJob *jobs, const MptRun *runs, int nruns, int blocks, const int32_t *topo,
                                                     double *work, hipStream_t stream);
 // displace.hip: the displaced positions of a launch's displaced jobs, between the last refine launch and the normals (mpt_compose)
@@ -732,6 +732,7 @@ struct mpt_ctx {
         int64_t nv[MPT_SUBDIV_MAX_LEVELS + 1] = {};
         int32_t rule_at[MPT_SUBDIV_MAX_LEVELS + 1] = {}, nrule_at = 0, face_at = 0;
         int32_t srule_at = 0; int64_t nrec = 0;          // the last level's records: nrule_at and nv[levels], or a creased mesh's sectors (section 3.19.1)
+        int32_t quad_at = 0; int64_t out_faces = 0;      // a Catmull-Clark mesh's table of level-1 quads (0: Loop; section 3.19.2); the faces of the last level
         int job = -1;                                    // the shared copy of a mesh that is not deformable (-1: no object yet)
         // its texture displacement (mpt_mesh_set_displacement)
         bool displaced = false;
@@ -1004,7 +1005,7 @@ MPT_INTERNAL void deform_scene_cleared(mpt_ctx *c, int meshes);
 MPT_INTERNAL int deform_step(mpt_ctx *c);                        // before compose_kernel: room, poses, the deform launch; rewrites objs' mesh_vert at a relayout
 
 // scene_subdiv.cpp: what scene_compose.cpp and scene_deform.cpp tell the subdivision table, and the step of mpt_compose behind deform_step
-MPT_INTERNAL int subdiv_object_faces(const mpt_ctx *c, int mesh_id);   // the faces an object of this mesh has: k * 4^L
+MPT_INTERNAL int subdiv_object_faces(const mpt_ctx *c, int mesh_id);   // the faces an object of this mesh has: k * 4^L (Catmull-Clark: 2 quads' worth per quad of level L)
 MPT_INTERNAL void subdiv_object_added(mpt_ctx *c, int obj_id);
 MPT_INTERNAL void subdiv_pose_changed(mpt_ctx *c, int obj_id);   // mpt_object_set_morph_weights / mpt_object_set_joints
 MPT_INTERNAL void subdiv_scene_cleared(mpt_ctx *c, int meshes);

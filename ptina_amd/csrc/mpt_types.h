@@ -267,13 +267,18 @@ enum { MPT_SUBDIV_VERT_INT = 0, MPT_SUBDIV_VERT_BND = 1, MPT_SUBDIV_EDGE_INT = 2
 #define MPT_SUBDIV_VARIANT_SHIFT 28
 #define MPT_SUBDIV_N_MASK ((1 << 26) - 1)
 enum { MPT_SUBDIV_PLAIN = 0, MPT_SUBDIV_BLEND_CREASE = 1, MPT_SUBDIV_BLEND_CORNER = 2, MPT_SUBDIV_FIXED = 3, MPT_SUBDIV_BLEND_EDGE = 1 };
-struct MptSubdivJob {                       // 128 bytes
+// Catmull-Clark (section 3.19.2): a rule that is Catmull-Clark's and not Loop's has this bit in its variant, beside the blend -- on
+// kind VERT_INT the interior vertex (ring, then its faces' points), on EDGE_INT the interior edge (a b, then two face points), on
+// EDGE_BND the face point (its corners).  A Loop mesh has no such head
+#define MPT_SUBDIV_CC 4
+#define MPT_SUBDIV_MAX_CORNERS 64           // corners of a polygon of a Catmull-Clark cage
+struct MptSubdivJob {                       // 128 bytes, and no more: with a word added the refine launches measured slower
     int32_t src_vert, dst_vert;              // first pool vertex of the control records (the mesh or a deformed copy) and of the subdivided copy
     int32_t levels, nfaces;                  // L, and the faces of the last level: k * 4^L
     int64_t topo_at;                         // the mesh's topology block: first word in the arena
     int64_t work_at;                         // the job's workspace: first double (even)
     int32_t nv[MPT_SUBDIV_MAX_LEVELS + 1];   // vertices of level 0..L
-    int32_t rule_at[MPT_SUBDIV_MAX_LEVELS + 1];   // words from topo_at: [l] the rules of level l's vertices ([0]: the first corners)
+    int32_t rule_at[MPT_SUBDIV_MAX_LEVELS + 1];   // words from topo_at: [l] the rules of level l's vertices; [0] (the first corners are the block's first words): a Catmull-Clark mesh's table of level-1 quads (the polygon's first triangle, n | i << 8), 0 for a Loop mesh
     int32_t pos_at[MPT_SUBDIV_MAX_LEVELS + 1];    // doubles from work_at: [l] the positions [V_l][3] of level l ([0]: level 0 is read from the pool; a displaced copy's displaced positions [V_L][3])
     int32_t nrule_at, face_at;               // words from topo_at: the last level's rings, its faces' vertex ids
     int32_t vrec_at;                         // doubles from work_at (even): the last level's records (one per vertex, or per sector of a creased mesh), 32 bytes each: pos3 nrm3 as f32, 8 bytes unused

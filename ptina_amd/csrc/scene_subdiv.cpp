@@ -2,6 +2,8 @@
 // device (subdiv_rule.h makes them, a pure function), the table of subdivided copies beside scene_compose.cpp's object table and
 // scene_deform.cpp's poses, the run tables of a compose's launches (mpt_subdiv_plan: run_table.h's rule), and subdiv_step: the part of
 // mpt_compose behind deform_step that gives the copies their room in the pool and launches subdiv.hip before compose_kernel.
+// A Catmull-Clark mesh (mpt_mesh_set_subdivision_cc) is a row of the same tables and a job of the same
+// launches: its block has other rules in it, its job names the table of level-1 quads, and its objects have another face count.
 // Texture displacement of the copies lives here too: mpt_mesh_set_displacement and its first-corner table
 // (displace_rule.h makes it, a pure function), and displace.hip's launch inside subdiv_step, between the last refine level and the
 // normals.
@@ -34,6 +36,15 @@ extern "C" int mpt_subdiv_topology(const float *verts, int k, int levels, int64_
     return topology_out(t, levels, counts, offsets, false, words, cap_words, need_words);
 }
 
+extern "C" int mpt_subdiv_topology_cc(const float *verts, int k, int levels, const int32_t *polys, int m, const float *crease, const uint8_t *corner,
+                                      int64_t *counts, int32_t *offsets, int32_t *words, int64_t cap_words, int64_t *need_words, char *why, int why_size) {
+    MptSubdivTopoCC t;
+    const MptSubdivVerdict v = mpt_subdiv_topology_cc_of(verts, k, levels, polys, m, crease, corner, t, why, why_size > 0 ? (size_t)why_size : 0);
+    if (v != MPT_SUBDIV_OK) return (int)v;
+    if (offsets) offsets[11] = t.quad_at;
+    return topology_out(t, levels, counts, offsets, true, words, cap_words, need_words);
+}
+
 extern "C" int mpt_subdiv_topology_creased(const float *verts, int k, int levels, const float *crease, const uint8_t *corner, int64_t *counts, int32_t *offsets,
                                            int32_t *words, int64_t cap_words, int64_t *need_words, char *why, int why_size) {
     MptSubdivTopo t;
@@ -45,7 +56,7 @@ extern "C" int mpt_subdiv_topology_creased(const float *verts, int k, int levels
 // ---------------------------------------------------------------- what scene_compose.cpp and scene_deform.cpp tell the table
 int subdiv_object_faces(const mpt_ctx *c, int mesh_id) {
     const auto &m = c->compose.meshes[mesh_id];
-    return m.nfaces << (2 * m.subdiv.levels);
+    return m.subdiv.levels ? (int)m.subdiv.out_faces : m.nfaces;
 }
 
 void subdiv_object_added(mpt_ctx *c, int obj_id) {
@@ -78,8 +89,10 @@ void subdiv_scene_cleared(mpt_ctx *c, int meshes) {
 }
 
 // ---------------------------------------------------------------- the meshes' levels
-// crease [k][3] and corner [k][3] of the mesh's faces, either may be null
-static int set_subdivision(mpt_ctx *c, const char *who, int mesh_id, int levels, const float *crease, const uint8_t *corner) {
+// crease [k][3] and corner [k][3] of the mesh's faces, either may be null.  cc: Catmull-Clark over the m
+// polygons polys (null: the triangles), crease and corner then flat over the polygons' corners (section 3.19.2)
+static int set_subdivision(mpt_ctx *c, const char *who, int mesh_id, int levels, const float *crease, const uint8_t *corner, bool cc = false,
+                           const int32_t *polys = nullptr, int npolys = 0) {
     if (use(c)) return 1;
     auto &sd = c->subdiv;
     auto &cp = c->compose;
@@ -88,13 +101,21 @@ static int set_subdivision(mpt_ctx *c, const char *who, int mesh_id, int levels,
     if (m.levels) return fail("%s: mesh %d already has a subdivision level", who, mesh_id);
     if (levels < 1 || levels > MPT_SUBDIV_MAX_LEVELS) return fail("%s: levels %d outside [1, %d]", who, levels, MPT_SUBDIV_MAX_LEVELS);
     const int k = cp.meshes[mesh_id].nfaces;
-    if (((long long)k << (2 * levels)) >= c->caps.max_faces)
-        return fail("%s: too many faces: %lld at level %d", who, (long long)k << (2 * levels), levels);
+    // the faces an object of the mesh will have: k 4^L, or of m polygons of n_j corners 2 (sum n_j) 4^(L - 1)
+    long long out_faces = (long long)k << (2 * levels);
+    if (cc) {
+        long long corners = 3LL * k;
+        if (polys) { corners = 0; for (int j = 0; j < npolys; j++) corners += std::max(polys[j], 0); }
+        out_faces = (2 * corners) << (2 * (levels - 1));
+    }
+    if (out_faces >= c->caps.max_faces) return fail("%s: too many faces: %lld at level %d", who, out_faces, levels);
     std::vector<float> rec;
     if (fetch_mesh(c, mesh_id, rec)) return 1;
-    MptSubdivTopo t;
+    MptSubdivTopoCC t;
     char why[200];
-    if (mpt_subdiv_topology_creased_of(rec.data(), k, levels, crease, corner, t, why, sizeof why) != MPT_SUBDIV_OK) return fail("%s: mesh %d: %s", who, mesh_id, why);
+    const MptSubdivVerdict verdict = cc ? mpt_subdiv_topology_cc_of(rec.data(), k, levels, polys, npolys, crease, corner, t, why, sizeof why)
+                                        : mpt_subdiv_topology_creased_of(rec.data(), k, levels, crease, corner, t, why, sizeof why);
+    if (verdict != MPT_SUBDIV_OK) return fail("%s: mesh %d: %s", who, mesh_id, why);
     const size_t words = t.words.size();
     if (grow_keeping(sd.bufs.topo, sd.topo_used + words, sd.topo_used, c->stream)) return 1;
     if (words > 0) {
@@ -105,6 +126,7 @@ static int set_subdivision(mpt_ctx *c, const char *who, int mesh_id, int levels,
     for (int l = 0; l <= levels; l++) { m.nv[l] = t.nv[l]; m.rule_at[l] = t.rule_at[l]; }
     m.nrule_at = t.nrule_at; m.face_at = t.face_at;
     m.srule_at = t.srule_at ? t.srule_at : t.nrule_at; m.nrec = t.nrec;
+    m.quad_at = t.quad_at; m.out_faces = cc ? 2 * t.nf[levels] : t.nf[levels];
     sd.topo_used += words;
     return 0;
 }
@@ -115,6 +137,10 @@ extern "C" int mpt_mesh_set_subdivision(mpt_ctx *c, int mesh_id, int levels) {
 
 extern "C" int mpt_mesh_set_subdivision_creased(mpt_ctx *c, int mesh_id, int levels, const float *crease, const uint8_t *corner) {
     return set_subdivision(c, "mpt_mesh_set_subdivision_creased", mesh_id, levels, crease, corner);
+}
+
+extern "C" int mpt_mesh_set_subdivision_cc(mpt_ctx *c, int mesh_id, int levels, const int32_t *polys, int m, const float *crease, const uint8_t *corner) {
+    return set_subdivision(c, "mpt_mesh_set_subdivision_cc", mesh_id, levels, crease, corner, true, polys, m);
 }
 
 // ---------------------------------------------------------------- the meshes' displacements
@@ -143,7 +169,7 @@ extern "C" int mpt_mesh_set_displacement(mpt_ctx *c, int mesh_id, int image_id, 
     if (image_id < 0) return fail("%s: image id %d is negative", who, image_id);
     if (check_displace_params(who, strength, midlevel)) return 1;
     const int k = cp.meshes[mesh_id].nfaces;
-    const int64_t nf = (int64_t)k << (2 * m.levels), nv = m.nv[m.levels];
+    const int64_t nf = m.out_faces, nv = m.nv[m.levels];
     std::vector<float> rec;
     std::vector<int32_t> faces((size_t)nf * 3), corner((size_t)nv);
     if (fetch_mesh(c, mesh_id, rec)) return 1;
@@ -255,7 +281,7 @@ int subdiv_step(mpt_ctx *c) {
     std::vector<MptDisplaceJob> &djobs = sd.h_djobs;
     djobs.assign((size_t)n, MptDisplaceJob{});
     std::vector<int32_t> dirty((size_t)n), displace((size_t)n);
-    int lmax = 0, ndirty = 0, ndisplaced = 0;
+    int lmax = 0, ndirty = 0, ndisplaced = 0, any_cc = 0;                // (any_cc: a dirty copy is of a Catmull-Clark mesh)
     for (int j = 0; j < n; j++) {
         const auto &p = sd.copies[j];
         const auto &m = c->compose.meshes[p.mesh].subdiv;
@@ -267,10 +293,11 @@ int subdiv_step(mpt_ctx *c) {
         for (int l = 0; l <= m.levels; l++) { t.nv[l] = (int32_t)m.nv[l]; t.rule_at[l] = m.rule_at[l]; }
         t.nrule_at = m.nrule_at; t.face_at = m.face_at;
         t.srule_at = m.srule_at; t.nrec = (int32_t)m.nrec;
+        t.rule_at[0] = m.quad_at;                         // (the record has no word to spare: MptSubdivJob)
         work_layout(m, &t);
         dirty[j] = copy_is_dirty(c, p, all);
         if (!dirty[j] || t.nfaces == 0) continue;
-        ndirty++; lmax = std::max(lmax, m.levels);
+        ndirty++; lmax = std::max(lmax, m.levels); any_cc |= m.quad_at != 0;
         sd.stats.refined_copies++; sd.stats.refined_faces += t.nfaces;
         if (!m.displaced) continue;
         const MptImage &im = c->h_images[m.image];            // (loaded: subdiv_images_ready)
@@ -307,7 +334,7 @@ int subdiv_step(mpt_ctx *c) {
         MptTimedSpan span(sd.refine_timer, c->stream);
         HIP_TRY(span.begun);
         for (int t = 0; t < lmax; t++) {
-            HIP_TRY(mpt_launch_subdiv_refine(cp.bufs.pool, sd.bufs.jobs, sd.bufs.runs + (size_t)t * (size_t)n, nruns[t], blocks[t], t + 1, sd.bufs.topo,
+            HIP_TRY(mpt_launch_subdiv_refine(cp.bufs.pool, sd.bufs.jobs, sd.bufs.runs + (size_t)t * (size_t)n, nruns[t], blocks[t], t + 1, any_cc, sd.bufs.topo,
                                              sd.bufs.work, c->stream));
             sd.launches++;
         }

@@ -53,19 +53,50 @@
 // as a boundary vertex's is, with its vertex's id in a table behind the rules -- which the face table then indexes.  An uncreased
 // mesh has variant 0 everywhere and its vertices for records: the words and the results of before.
 //
+// Catmull-Clark subdivision of a cage of quads and polygons (also include/miptina.h), the second scheme a
+// mesh may carry.  Arithmetic, weld, first-corner rule, ids of control vertices and edge numbering are those of above.  Polygon j of
+// n_j corners (3 to 64) is stored as n_j - 2 consecutive triangles of the mesh, a fan about its first corner: (c_0, c_i+1, c_i+2).
+//   Level l -> l + 1, ids: even vertices keep their ids; the edge point of edge e is V_l + e; the face point of face j is
+//     V_l + E_l + j.
+//   Face split: polygon or quad j of corners c_0 .. c_n-1 becomes n quads, quad i (c_i, e(c_i, c_i+1), f_j, e(c_i-1, c_i)); at level
+//     1 the quads of polygon j start at the sum of n_j' over j' < j, from level 1 on quad q becomes 4q .. 4q + 3.  Windings are kept.
+//   Emitted triangles: quad q = (v0, v1, v2, v3) of the last level is faces 2q (v0, v1, v2) and 2q + 1 (v0, v2, v3), so face g of an
+//     object descends from level-1 quad (g >> 1) >> 2 (L - 1), and an object has 2 (sum n_j) 4^(L - 1) faces.
+//   Face point         F = (((c_0 + c_1) + c_2) + ...) / n
+//   interior edge      E = 0.25 * ((a + b) + (F1 + F2)),  a the lower endpoint id, b the higher, F1 the face that runs a -> b
+//   boundary edge      0.5 * (a + b)
+//   Ring of a vertex: its EDGE neighbours in winding order (in face (v, a, ..., b), a comes before b), the start as above.
+//   interior vertex    M = (((n - 2.0) / n) * v) + ((1.0 / (n * n)) * (S_r + S_f)),  S_r the ring summed left to right, S_f the face
+//                      points summed in the same order, F_i the face between r_i and r_i+1
+//   boundary vertex    (0.75 * v) + (0.125 * (p + q)); no corner rule unless the corner is flagged.
+//   A face point in an edge's or a vertex's rule is the value the face rule gives, bit for bit: the lane evaluates the face rule
+//     again (sd_face_point) from the same words in the same order, so that face points need no launch of their own.
+//   Creases and corners: the text of above with E and M as here; the edges new inside a face (edge point to face point) have
+//     sharpness 0.  Normals at the last level: the sum of above over the ring of edge neighbours, one term per quad on the vertex,
+//     cut into sectors by the hard edges as above; a displacement takes its direction from the whole ring.
+//   Texcoords are face-varying: a face point's uv is ((u_0 + u_1) + ...) / n, an edge's 0.5 * (u_i + u_j); a child quad takes its uvs
+//     by the split rule, level by level from the polygon's corner uvs -- c_0's and c_1's read from triangle 0 of the fan, c_i+2's
+//     from corner 2 of triangle i (subdiv_walk.h: sd_quad_uv, through the mesh's table of level-1 quads).
+// The rules that are Catmull-Clark's own carry MPT_SUBDIV_CC in their head's variant (subdiv_rule.h): the face point (its lane is
+// item V_l + E_l + j of the refine launch), the interior edge, the interior vertex; a boundary vertex, a boundary or sharp edge, a
+// vertex that stays and every rule of the last level are Loop's words, and the normal kernel does not know the scheme.  The job
+// names the table of level-1 quads (rule_at[0]; 0: a Loop mesh), by which the record kernel and displace.hip pick the uv walk.
+//
 // Three kernels, each one lane per item (a workgroup of 256 lanes takes MPT_SUBDIV_CHUNK items of ONE job; a run table maps blocks to
 // (job, chunk): run_table.h), so the number of launches of an mpt_compose is L_max + 2 whatever the
 // number of copies; a job of fewer levels has no blocks in the later refine launches.  Levels are separate launches: nothing is
 // handed from workgroup to workgroup inside a launch.
 //   subdiv_refine_kernel   level l - 1 -> l: a lane reads its vertex's rule (two words), gathers 2 to n + 1 positions of the level
 //                          below -- level 0 from the pool through the first-corner table, else 24-byte f64 records of the
-//                          workspace -- and writes one.
+//                          workspace -- and writes one.  (Catmull-Clark: the lanes are the vertices, the edges and then the faces
+//                          of the level below; an interior vertex gathers its n neighbours and the corners of its n faces.)
 //   subdiv_normal_kernel   the last level: a lane walks its vertex's ring (a creased mesh: its record's sector) and writes the record
 //                          (pos3 nrm3 as f32: the one rounding), 32 bytes, two 16-byte stores.  The positions are those the job points at (npos_at): the
 //                          last level's, or the displaced ones of a copy that carries a displacement (displace.hip, launched
 //                          between the last refine level and this kernel; section 3.20).
 //   subdiv_emit_kernel     a lane per refined face: three record ids, three 32-byte gathers (a vertex is shared by six corners, so
-//                          they hit in L2), the parent's three uvs and L midpoint steps, six 16-byte stores: 96 bytes.
+//                          they hit in L2), the parent's three uvs and L midpoint steps (a Catmull-Clark copy: its polygon's n uvs
+//                          and L - 1 quad steps), six 16-byte stores: 96 bytes.
 // Vector stores only, no atomics, no LDS.
 
 #include <hip/hip_runtime.h>
@@ -89,6 +120,22 @@ static __device__ __forceinline__ SdVec sd_pos(const MptSubdivJob &o, int level,
     return { p[0], p[1], p[2] };
 }
 
+// Catmull-Clark: the point of the face whose rule is rule `id` of this launch, F = (((c_0 + c_1) + c_2) + ...) / n -- evaluated by every
+// lane that needs it, the face's own lane included, so that it is one value bit for bit
+static __device__ __forceinline__ SdVec sd_face_point(const MptSubdivJob &o, int level, const float4 *pool, const int32_t *__restrict__ T,
+                                                      const double *work, int32_t id) {
+    const int32_t head = T[o.rule_at[level] + 2 * id], at = T[o.rule_at[level] + 2 * id + 1];
+    const int n = head >> 2 & MPT_SUBDIV_N_MASK;
+    const int32_t *__restrict__ c = T + at;
+    SdVec s = sd_add(sd_pos(o, level, pool, T, work, c[0]), sd_pos(o, level, pool, T, work, c[1]));
+    for (int k = 2; k < n; k++) s = sd_add(s, sd_pos(o, level, pool, T, work, c[k]));
+    const double nd = (double)n;
+    return { s.x / nd, s.y / nd, s.z / nd };
+}
+
+// CC: the launch has a Catmull-Clark job.  One without is built without those rules -- Loop's kernel as it was, so that a scene of
+// Loop meshes does not pay for their registers and code (DESIGN.md section 3.19.2 has the measurement)
+template <bool CC>
 __global__ __launch_bounds__(SD_BLOCK) void subdiv_refine_kernel(const float4 *pool, const MptSubdivJob *__restrict__ jobs,
                                                                  const MptRun *__restrict__ runs, int nruns, int level,
                                                                  const int32_t *__restrict__ topo, double *work) {
@@ -101,7 +148,39 @@ __global__ __launch_bounds__(SD_BLOCK) void subdiv_refine_kernel(const float4 *p
     const int kind = head & 3, variant = head >> MPT_SUBDIV_VARIANT_SHIFT & 7, n = head >> 2 & MPT_SUBDIV_N_MASK;
     const int32_t *__restrict__ ring = T + at;
     SdVec out;
-    if (kind == MPT_SUBDIV_EDGE_INT) {
+    if (CC && (variant & MPT_SUBDIV_CC)) {
+        // Catmull-Clark's own rules (the boundary vertex, the boundary or sharp edge and the vertex that stays are the branches below)
+        const int blend = variant & 3;
+        if (kind == MPT_SUBDIV_EDGE_BND) {
+            out = sd_face_point(o, level, pool, T, work, i);
+        } else if (kind == MPT_SUBDIV_EDGE_INT) {
+            const SdVec a = sd_pos(o, level, pool, T, work, ring[0]), b = sd_pos(o, level, pool, T, work, ring[1]);
+            const SdVec F1 = sd_face_point(o, level, pool, T, work, ring[2]), F2 = sd_face_point(o, level, pool, T, work, ring[3]);
+            out = sd_mul(0.25, sd_add(sd_add(a, b), sd_add(F1, F2)));
+            if (blend == MPT_SUBDIV_BLEND_EDGE) {
+                const double s = __hiloint2double(ring[5], ring[4]);
+                out = sd_add(sd_mul(1.0 - s, out), sd_mul(s, sd_mul(0.5, sd_add(a, b))));
+            }
+        } else {
+            const SdVec v = sd_pos(o, level, pool, T, work, i);
+            SdVec sr = sd_pos(o, level, pool, T, work, ring[0]), sf = sd_face_point(o, level, pool, T, work, ring[n]);
+            for (int k = 1; k < n; k++) {
+                sr = sd_add(sr, sd_pos(o, level, pool, T, work, ring[k]));
+                sf = sd_add(sf, sd_face_point(o, level, pool, T, work, ring[n + k]));
+            }
+            const double nd = (double)n;
+            out = sd_add(sd_mul((nd - 2.0) / nd, v), sd_mul(1.0 / (nd * nd), sd_add(sr, sf)));
+            if (blend == MPT_SUBDIV_BLEND_CREASE) {
+                const SdVec p = sd_pos(o, level, pool, T, work, ring[2 * n]), q = sd_pos(o, level, pool, T, work, ring[2 * n + 1]);
+                const double f = __hiloint2double(ring[2 * n + 3], ring[2 * n + 2]);
+                const SdVec C = sd_add(sd_mul(0.75, v), sd_mul(0.125, sd_add(p, q)));
+                out = sd_add(sd_mul(1.0 - f, out), sd_mul(f, C));
+            } else if (blend == MPT_SUBDIV_BLEND_CORNER) {
+                const double f = __hiloint2double(ring[2 * n + 1], ring[2 * n]);
+                out = sd_add(sd_mul(1.0 - f, out), sd_mul(f, v));
+            }
+        }
+    } else if (kind == MPT_SUBDIV_EDGE_INT) {
         const SdVec a = sd_pos(o, level, pool, T, work, ring[0]), b = sd_pos(o, level, pool, T, work, ring[1]);
         const SdVec c = sd_pos(o, level, pool, T, work, ring[2]), d = sd_pos(o, level, pool, T, work, ring[3]);
         out = sd_add(sd_mul(0.375, sd_add(a, b)), sd_mul(0.125, sd_add(c, d)));
@@ -169,7 +248,7 @@ __global__ __launch_bounds__(SD_BLOCK) void subdiv_emit_kernel(const float4 *poo
     const float4 a0 = vrec[(size_t)i0 * 2], a1 = vrec[(size_t)i0 * 2 + 1];
     const float4 b0 = vrec[(size_t)i1 * 2], b1 = vrec[(size_t)i1 * 2 + 1];
     const float4 c0 = vrec[(size_t)i2 * 2], c1 = vrec[(size_t)i2 * 2 + 1];
-    const SdFaceUv t = sd_face_uv(pool_in, o.src_vert, o.levels, g);
+    const SdFaceUv t = sd_copy_face_uv(pool_in, o, topo, g);
     const double u0 = t.u0, v0 = t.v0, u1 = t.u1, v1 = t.v1, u2 = t.u2, v2 = t.v2;
     float4 *dst = pool_out + ((size_t)o.dst_vert + (size_t)g * 3) * 2;
     dst[0] = a0; dst[1] = make_float4(a1.x, a1.y, (float)u0, (float)v0);
@@ -178,13 +257,14 @@ __global__ __launch_bounds__(SD_BLOCK) void subdiv_emit_kernel(const float4 *poo
 }
 
 // ---------------------------------------------------------------- launchers
-// runs[nruns] and blocks: mpt_subdiv_plan's table over the jobs' items of this launch and the sum of its blocks.  The pool is read
-// at the jobs' src_vert and written at their dst_vert, the workspace read at one level and written at the next: ranges that never
-// overlap
+// runs[nruns] and blocks: mpt_subdiv_plan's table over the jobs' items of this launch and the sum of its blocks; cc: one of the
+// launch's jobs is of a Catmull-Clark mesh.  The pool is read at the jobs' src_vert and written at their dst_vert, the workspace
+// read at one level and written at the next: ranges that never overlap
 MPT_KERNEL_API hipError_t mpt_launch_subdiv_refine(const float *pool, const MptSubdivJob *jobs, const MptRun *runs, int nruns, int blocks,
-                                                   int level, const int32_t *topo, double *work, hipStream_t stream) {
+                                                   int level, int cc, const int32_t *topo, double *work, hipStream_t stream) {
     if (nruns < 1 || blocks < 1 || level < 1 || level > MPT_SUBDIV_MAX_LEVELS) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(subdiv_refine_kernel, dim3((unsigned)blocks), dim3(SD_BLOCK), 0, stream, (const float4 *)pool, jobs, runs, nruns, level, topo, work);
+    if (cc) hipLaunchKernelGGL(subdiv_refine_kernel<true>, dim3((unsigned)blocks), dim3(SD_BLOCK), 0, stream, (const float4 *)pool, jobs, runs, nruns, level, topo, work);
+    else hipLaunchKernelGGL(subdiv_refine_kernel<false>, dim3((unsigned)blocks), dim3(SD_BLOCK), 0, stream, (const float4 *)pool, jobs, runs, nruns, level, topo, work);
     return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // subdiv_walk.h -- the two walks of the last level that subdiv.hip and displace.hip both do (DESIGN.md sections 3.19, 3.20), each
 // stated once: a vertex's ring walk for its normal sum, and a face's walk down the base-4 digits of its index for its corners'
-// face-varying uvs.  Device code only; f64, every sum in the order written (the files that include it are built with
-// -ffp-contract=off).
+// face-varying uvs -- for a Catmull-Clark copy (section 3.19.2) a quad's walk, from its polygon's fan.  Device code only; f64, every
+// sum in the order written (the files that include it are built with -ffp-contract=off).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -52,4 +52,47 @@ static __device__ __forceinline__ SdFaceUv sd_face_uv(const float4 *pool, int32_
         u0 = n0u; v0 = n0v; u1 = n1u; v1 = n1v; u2 = n2u; v2 = n2v;
     }
     return { u0, v0, u1, v1, u2, v2 };
+}
+
+// Catmull-Clark.  The uvs of the three corners of emitted face g of level `levels`: g is half of quad
+// q = g >> 1 of the last level, which descends from quad q >> 2 (levels - 1) of level 1, and that one is quad i of a polygon of n
+// corners whose fan starts at triangle `first` of the control records (Q, the mesh's table of level-1 quads: first, n | i << 8).
+// Corner j of the polygon has its uv at corner j of the first triangle for j < 2, else at corner 2 of triangle j - 2.  A face
+// point's uv is ((u_0 + u_1) + ...) / n in the face's own order, an edge's 0.5 * (u_i + u_j); quad (c_0 .. c_3) has child d
+// (c_d, e(c_d, c_d+1), f, e(c_d-1, c_d)), down the base-4 digits of q; the halves of a quad are (0, 1, 2) and (0, 2, 3)
+struct SdUv { double u, v; };
+static __device__ __forceinline__ SdUv sd_poly_uv(const float4 *pool, int32_t src_vert, int32_t first, int j) {
+    const size_t corner = j < 2 ? (size_t)first * 3 + (size_t)j : ((size_t)first + (size_t)(j - 2)) * 3 + 2;
+    const float4 p = pool[((size_t)src_vert + corner) * 2 + 1];
+    return { (double)p.z, (double)p.w };
+}
+static __device__ __forceinline__ SdUv sd_uv_mid(SdUv a, SdUv b) { return { 0.5 * (a.u + b.u), 0.5 * (a.v + b.v) }; }
+static __device__ __forceinline__ SdFaceUv sd_quad_uv(const float4 *pool, int32_t src_vert, const int32_t *__restrict__ Q, int levels, int g) {
+    const int q = g >> 1, q1 = q >> (2 * (levels - 1));
+    const int32_t first = Q[2 * q1], ni = Q[2 * q1 + 1];
+    const int n = ni & 255, i = ni >> 8;
+    const SdUv c0 = sd_poly_uv(pool, src_vert, first, 0), c1 = sd_poly_uv(pool, src_vert, first, 1);
+    SdUv s = { c0.u + c1.u, c0.v + c1.v };
+    for (int j = 2; j < n; j++) {
+        const SdUv c = sd_poly_uv(pool, src_vert, first, j);
+        s = { s.u + c.u, s.v + c.v };
+    }
+    const SdUv ci = sd_poly_uv(pool, src_vert, first, i), cn = sd_poly_uv(pool, src_vert, first, i + 1 < n ? i + 1 : 0);
+    const SdUv cp = sd_poly_uv(pool, src_vert, first, i > 0 ? i - 1 : n - 1);
+    SdUv a0 = ci, a1 = sd_uv_mid(ci, cn), a2 = { s.u / (double)n, s.v / (double)n }, a3 = sd_uv_mid(cp, ci);
+    for (int t = levels - 2; t >= 0; t--) {
+        const int d = (q >> (2 * t)) & 3;
+        const SdUv f = { (((a0.u + a1.u) + a2.u) + a3.u) / 4.0, (((a0.v + a1.v) + a2.v) + a3.v) / 4.0 };
+        const SdUv c = d == 0 ? a0 : d == 1 ? a1 : d == 2 ? a2 : a3, nx = d == 0 ? a1 : d == 1 ? a2 : d == 2 ? a3 : a0;
+        const SdUv pv = d == 0 ? a3 : d == 1 ? a0 : d == 2 ? a1 : a2;
+        a0 = c; a1 = sd_uv_mid(c, nx); a2 = f; a3 = sd_uv_mid(pv, c);
+    }
+    if (g & 1) return { a0.u, a0.v, a2.u, a2.v, a3.u, a3.v };
+    return { a0.u, a0.v, a1.u, a1.v, a2.u, a2.v };
+}
+
+// The uvs of face g of a copy's last level by its mesh's scheme (uniform in a job, so in a workgroup)
+static __device__ __forceinline__ SdFaceUv sd_copy_face_uv(const float4 *pool, const MptSubdivJob &o, const int32_t *__restrict__ topo, int g) {
+    if (o.rule_at[0]) return sd_quad_uv(pool, o.src_vert, topo + o.topo_at + o.rule_at[0], o.levels, g);
+    return sd_face_uv(pool, o.src_vert, o.levels, g);
 }

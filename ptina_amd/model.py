@@ -14,7 +14,7 @@ import ctypes as C
 from .common import *                 # noqa: F401,F403
 from .common import Singleton, register, ctx, np
 from ._lib import fptr, iptr, ComposeInfo, DeformInfo, SubdivInfo, DisplaceInfo, DEFORM_MAX_JOINTS, DEFORM_MAX_TARGETS, SUBDIV_MAX_LEVELS
-from ._lib import DISPLACE_MODES, DISPLACE_CHANNELS, ScatterInfo, SCATTER_POINT_DTYPE, scatter_params
+from ._lib import SUBDIV_SCHEMES, DISPLACE_MODES, DISPLACE_CHANNELS, ScatterInfo, SCATTER_POINT_DTYPE, scatter_params
 
 
 @register
@@ -27,6 +27,7 @@ class ModelPool(metaclass=Singleton):
         self._composed = False           # the model is the device's composition: to_numpy fetches it
         self._mesh_faces = []            # faces of every mesh of the device's pool
         self._mesh_levels = {}           # mesh -> its subdivision level, where it has one: an object of it has faces * 4^level
+        self._mesh_corners = {}          # mesh -> the corners of its polygons, where its scheme is Catmull-Clark: an object has 2 * corners * 4^(level - 1) faces
         self._mesh_displace = {}         # mesh -> [strength, midlevel] of its displacement, where it has one
         self._obj_mesh = []              # the mesh of every object of the device's table
         self._sum = (None, 0, 0)         # (that list, how many of its objects are counted, their faces): _faces_of_objects
@@ -120,6 +121,7 @@ class ModelPool(metaclass=Singleton):
         '''drop the objects and the meshes'''
         ctx().call('mpt_scene_clear', 1)
         self._obj_mesh, self._mesh_faces, self._mesh_levels, self._mesh_displace, self._scatters = [], [], {}, {}, []
+        self._mesh_corners = {}
 
     def compose(self):
         '''write the objects, in order, as the model BVHTree().build() reads -- on the device; what load(*compose_multiple_meshes(...))
@@ -213,6 +215,8 @@ class ModelPool(metaclass=Singleton):
     # ---- Loop subdivision on the device, behind the deformation (csrc/subdiv.hip; the reference's add-on
     #      is handed Blender's evaluated mesh instead)
     def _object_faces(self, mesh):
+        if mesh in self._mesh_corners:
+            return 2 * self._mesh_corners[mesh] << (2 * (self._mesh_levels[mesh] - 1))
         return self._mesh_faces[mesh] << (2 * self._mesh_levels.get(mesh, 0))
 
     def _faces_of_objects(self):
@@ -225,7 +229,7 @@ class ModelPool(metaclass=Singleton):
         self._sum = (self._obj_mesh, len(self._obj_mesh), total)
         return total
 
-    def add_subdivision(self, mesh, levels, creases=None, corners=None):
+    def add_subdivision(self, mesh, levels, creases=None, corners=None, scheme='loop', polys=None):
         '''`levels` (1 to 5) levels of Loop subdivision for a mesh that has no object yet, before or after its targets and skin: an
         object of it then has 4^levels times the faces, smooth normals and the mesh's texcoords carried down face by face; face g of
         such an object descends from face g >> 2 * levels of the mesh.  Corners with equal positions are one control vertex; the
@@ -236,7 +240,20 @@ class ModelPool(metaclass=Singleton):
         as OpenSubdiv's -- 0 smooth, inf always sharp, tools.crease.blender_crease maps Blender's 0..1; an edge takes the larger of
         what its two faces state; a negative value or a NaN is refused.  `corners` [k,3]: a flag per face corner; a control vertex
         with a flagged corner stays where it is.  An edge still sharp at the last level (and every boundary edge) splits the normals
-        of the vertices on it.  Both are fixed with the level'''
+        of the vertices on it.  Both are fixed with the level.
+
+        scheme='catmull-clark' (Blender's Subdivision Surface modifier) subdivides a cage of polygons:
+        `polys` [m] int32 holds the corner count n_j (3 to 64) of each, and polygon j is n_j - 2 consecutive triangles of the
+        mesh, a fan about its first corner -- triangle i is (c_0, c_i+1, c_i+2); tools.polys.fan writes such a mesh; None makes every
+        triangle a polygon.  `creases` and `corners` are then flat [sum n_j]: entry i of polygon j is the edge from its corner i to
+        corner (i + 1) % n_j, respectively its corner i.  An object has 2 (sum n_j) 4^(levels - 1) faces: two per quad of the
+        last level, face g descending from level-1 quad (g >> 1) >> 2 (levels - 1)'''
+        if scheme not in SUBDIV_SCHEMES:
+            raise ValueError('scheme %r: one of %s' % (scheme, ', '.join(SUBDIV_SCHEMES)))
+        if scheme == 'loop' and polys is not None:
+            raise ValueError("polys are the polygons of scheme 'catmull-clark': scheme 'loop' subdivides the triangles")
+        if scheme == 'catmull-clark':
+            return self._add_subdivision_cc(mesh, levels, creases, corners, polys)
         mesh, levels = self._fresh_mesh(mesh), int(levels)
         if not 1 <= levels <= SUBDIV_MAX_LEVELS:
             raise ValueError('%d levels: between 1 and %d' % (levels, SUBDIV_MAX_LEVELS))
@@ -256,6 +273,30 @@ class ModelPool(metaclass=Singleton):
             ctx().call('mpt_mesh_set_subdivision_creased', mesh, levels, None if cr is None else fptr(cr),
                        None if co is None else co.ctypes.data_as(C.POINTER(C.c_uint8)))
         self._mesh_levels[mesh] = levels
+
+    def _add_subdivision_cc(self, mesh, levels, creases, corners, polys):
+        mesh, levels = self._fresh_mesh(mesh), int(levels)
+        if not 1 <= levels <= SUBDIV_MAX_LEVELS:
+            raise ValueError('%d levels: between 1 and %d' % (levels, SUBDIV_MAX_LEVELS))
+        if mesh in self._mesh_levels:
+            raise ValueError('mesh %d already has a subdivision level' % mesh)
+        k = self._mesh_faces[mesh]
+        po = np.full(k, 3, np.int32) if polys is None else np.ascontiguousarray(polys, np.int32)
+        if po.ndim != 1:
+            raise ValueError('polys must be [m], one corner count per polygon, got %s' % (po.shape,))
+        ncorners = int(np.clip(po, 0, None).astype(np.int64).sum())         # (the library refuses polygons that are not the mesh's fans)
+        faces = 2 * ncorners << (2 * (levels - 1))
+        if faces >= self.size:
+            raise ValueError('too many faces: %d at level %d, room for fewer than %d' % (faces, levels, self.size))
+        cr = None if creases is None else np.ascontiguousarray(creases, np.float32)
+        co = None if corners is None else np.ascontiguousarray(np.asarray(corners) != 0, np.uint8)
+        for name, a in (('creases', cr), ('corners', co)):
+            if a is not None and a.shape != (ncorners,):
+                raise ValueError('%s must be [%d], one per polygon %s, got %s' % (name, ncorners, 'edge' if a is cr else 'corner', a.shape))
+        ctx().call('mpt_mesh_set_subdivision_cc', mesh, levels, iptr(po), int(po.size), None if cr is None else fptr(cr),
+                   None if co is None else co.ctypes.data_as(C.POINTER(C.c_uint8)))
+        self._mesh_levels[mesh] = levels
+        self._mesh_corners[mesh] = ncorners
 
     # ---- texture displacement of a subdivided mesh on the device (csrc/displace.hip, DESIGN.md section 3.20: Blender's Displace
     #      modifier with UV coordinates behind its subdivision surface; the reference's add-on is handed the evaluated mesh)
@@ -387,7 +428,7 @@ class ModelPool(metaclass=Singleton):
 
     def subdivided_to_numpy(self, obj):
         '''the subdivided copy of an object of a subdivided mesh as the last compose() wrote it -- displaced, if the mesh carries a
-        displacement: [3 k 4^levels, 8] f32 records in object space'''
+        displacement: [3 k 4^levels, 8] f32 records in object space (a Catmull-Clark copy: [3 * 2 (sum n_j) 4^(levels - 1), 8])'''
         return self._copy_to_numpy('mpt_get_subdivided', obj, self._object_faces)
 
     def subdiv_stats(self):

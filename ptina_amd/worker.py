@@ -28,7 +28,7 @@ _PASS_THROUGH = {
     'set_object_world': ('ModelPool', 'set_world', ('obj', 'world')),
     'set_object_morph_weights': ('ModelPool', 'set_morph_weights', ('obj', 'w')),
     'set_object_joints': ('ModelPool', 'set_joints', ('obj', 'mats')),
-    'set_mesh_subdivision': ('ModelPool', 'add_subdivision', ('mesh', 'levels', ('creases', None), ('corners', None))),
+    'set_mesh_subdivision': ('ModelPool', 'add_subdivision', ('mesh', 'levels', ('creases', None), ('corners', None), ('scheme', 'loop'), ('polys', None))),
     'set_mesh_displacement': ('ModelPool', 'add_displacement', ('mesh', 'image', ('strength', 1.0), ('midlevel', 0.5), ('mode', 'normal'), ('channel', 'mean'))),
     'set_mesh_displacement_params': ('ModelPool', 'set_displacement', ('mesh', 'strength', ('midlevel', None))),
     'add_scatter': ('ModelPool', 'add_scatter', ('surface', 'mesh', 'count', ('seed', 0), ('mtlid', None), ('scale', (1, 1)), ('align', 'normal'), ('up', (0, 1, 0)),

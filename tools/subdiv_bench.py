@@ -16,8 +16,10 @@ cages: cut into 64 runs of faces they are not manifold).  Every mesh carries a 6
 With --creases every size is measured twice, a JSON line each: with every grid line (the quads' edges, not
 their diagonals) at sharpness inf, and with none (the uncreased call); the lines also name the records of the last level against
 its vertices, and road b subdivides by tests/subdiv_crease_ref.py.
+With --scheme catmull-clark the same grids are cages of quads -- each quad the fan of two triangles it
+already is -- so that the face counts are those of above; road b subdivides by tests/subdiv_cc_ref.py.
 
-    python tools/subdiv_bench.py [--quads 7 22] [--levels 2] [--repeat 10] [--repeat-host 2] [--copies 50] [--creases]
+    python tools/subdiv_bench.py [--quads 7 22] [--levels 2] [--repeat 10] [--repeat-host 2] [--copies 50] [--creases] [--scheme catmull-clark]
 '''
 import argparse
 import json
@@ -35,6 +37,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import deform_ref                                                             # noqa: E402
 import subdiv_ref                                                             # noqa: E402
 import subdiv_crease_ref                                                      # noqa: E402
+import subdiv_cc_ref                                                          # noqa: E402
 
 JOINTS, NOBJ = 64, 64
 
@@ -46,7 +49,7 @@ def grid_lines(quads):
     return np.where((step == 1) | (step == quads + 1), np.float32(np.inf), np.float32(0)).astype(np.float32)
 
 
-def bench(quads, levels, repeat, repeat_host, copies, creases=None):
+def bench(quads, levels, repeat, repeat_host, copies, creases=None, scheme='loop'):
     from ptina_amd import _lib
     from ptina_amd.common import ctx, reset_all
     from ptina_amd.multimesh import compose_multiple_meshes
@@ -59,6 +62,10 @@ def bench(quads, levels, repeat, repeat_host, copies, creases=None):
     rec = subdiv_ref.mesh_records(*subdiv_ref.grid(quads, quads))
     k = rec.shape[0] // 3
     lines = grid_lines(quads) if creases == 'lines' else None
+    cc = scheme == 'catmull-clark'
+    polys = np.full(quads * quads, 4, np.int32) if cc else None
+    if cc and lines is not None:                                               # per quad (a, b, c, d): all four edges are grid lines
+        lines = np.full(4 * quads * quads, np.inf, np.float32)
     rigs, worlds, set_ms = [], [], []
     for o in range(NOBJ):
         mesh = pool.add_mesh(*deform_ref.split(rec))
@@ -67,7 +74,9 @@ def bench(quads, levels, repeat, repeat_host, copies, creases=None):
         wt = (wt / wt.sum(axis=2, keepdims=True)).astype(np.float32)
         pool.add_skin(mesh, jt, wt, JOINTS)
         t0 = time.perf_counter()
-        if lines is None:
+        if cc:
+            pool.add_subdivision(mesh, levels, creases=lines, scheme=scheme, polys=polys)
+        elif lines is None:
             pool.add_subdivision(mesh, levels)
         else:
             pool.add_subdivision(mesh, levels, creases=lines)
@@ -88,9 +97,9 @@ def bench(quads, levels, repeat, repeat_host, copies, creases=None):
     sync()
     size = pool.nfaces
     out = {'metric': 'subdivided_pose_change_ms', 'cage_faces': k * NOBJ, 'faces': size, 'objects': NOBJ, 'levels': levels, 'joints': JOINTS,
-           'chunk_items': _lib.SUBDIV_CHUNK, 'repeat': repeat, 'host': platform.processor() or platform.machine(), 'columns': ['wall median', 'wall min']}
+           'scheme': scheme, 'chunk_items': _lib.SUBDIV_CHUNK, 'repeat': repeat, 'host': platform.processor() or platform.machine(), 'columns': ['wall median', 'wall min']}
     if creases is not None:
-        _, _, tables = _lib.subdiv_topology_creased(rec, levels, lines)
+        _, _, tables = _lib.subdiv_topology_cc(rec, levels, polys, lines) if cc else _lib.subdiv_topology_creased(rec, levels, lines)
         out['creases'] = 'every grid line inf' if creases == 'lines' else 'none'
         out['records, vertices of the last level (one cage)'] = [len(tables['records']), int(tables['counts'][levels, 0])]
     out['mpt_mesh_set_subdivision of one cage of %d faces (host ms: median, least)' % k] = [round(median(set_ms), 3), round(min(set_ms), 3)]
@@ -140,11 +149,16 @@ def bench(quads, levels, repeat, repeat_host, copies, creases=None):
     model_v, model_m = pool.to_numpy()
     per = size // NOBJ
     jt, wt = rigs[one]
-    topo = subdiv_ref.topology(rec, levels) if creases is None else subdiv_crease_ref.topology(rec, levels, lines)
+    if cc:
+        topo = subdiv_cc_ref.topology(rec, levels, polys, lines)
+    else:
+        topo = subdiv_ref.topology(rec, levels) if creases is None else subdiv_crease_ref.topology(rec, levels, lines)
 
     def host_road():
         copy = deform_ref.deform(rec, None, None, jt.reshape(k * 3, 4), wt.reshape(k * 3, 4), palette())
-        if creases is None:
+        if cc:
+            fine = subdiv_cc_ref.subdivide(rec, levels, topo=topo, control=copy)
+        elif creases is None:
             fine = subdiv_ref.subdivide(rec, levels, topo, control=copy)
         else:
             fine = subdiv_crease_ref.subdivide(rec, levels, topo=topo, control=copy)
@@ -167,10 +181,11 @@ def main():
     ap.add_argument('--repeat-host', type=int, default=2)
     ap.add_argument('--copies', type=int, default=50)
     ap.add_argument('--creases', action='store_true', help='measure every size with every grid line at sharpness inf, and with none')
+    ap.add_argument('--scheme', default='loop', choices=('loop', 'catmull-clark'))
     args = ap.parse_args()
     for quads in args.quads:
         for creases in (('lines', 'none') if args.creases else (None,)):
-            bench(quads, args.levels, args.repeat, args.repeat_host, args.copies, creases)
+            bench(quads, args.levels, args.repeat, args.repeat_host, args.copies, creases, args.scheme)
 
 
 if __name__ == '__main__':
