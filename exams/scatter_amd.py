@@ -8,8 +8,10 @@ so nothing but two numbers crosses to the device: the pond is displaced again th
 on the face and at the barycentric point it was born on, along the face's normal as it is now (csrc/scatter.hip: the placement
 kernel alone; weights, scan and selection ran once, in the first compose), the pond's and the tufts' faces are composed again and
 the built tree is fitted to them (csrc/refit.hip) -- instance count, topology and face count never change.
+--min-distance R keeps the tufts at least R apart where they are born (csrc/scatter_space.hip: four times --count candidates, the
+greedy elimination in the first compose; 0.02 suits the default count): no two of them stand in each other.
 
-    python exams/scatter_amd.py [--frames 12] [--levels 4] [--count 2000] [--size 256] [--spp 8] [--image 256] [--out DIR]
+    python exams/scatter_amd.py [--frames 12] [--levels 4] [--count 2000] [--min-distance 0] [--size 256] [--spp 8] [--image 256] [--out DIR]
 '''
 import argparse
 import os
@@ -27,6 +29,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--frames', type=int, default=12)
 ap.add_argument('--levels', type=int, default=4)
 ap.add_argument('--count', type=int, default=2000)
+ap.add_argument('--min-distance', type=float, default=0.0)
 ap.add_argument('--size', type=int, default=256)
 ap.add_argument('--spp', type=int, default=8)
 ap.add_argument('--image', type=int, default=256)
@@ -96,8 +99,12 @@ mesh = pool.add_mesh(*cage())
 pool.add_subdivision(mesh, args.levels)
 pool.add_displacement(mesh, ripple, strength=0.0, midlevel=0.5, mode='normal', channel='r')
 pond = pool.add_object(mesh, shift(0.0, 0.25, -0.2), 3)
-scatter, tufts = pool.add_scatter(pond, pool.add_mesh(*tuft()), args.count, seed=1, mtlid=1, scale=(0.03, 0.07), density=ripple, channel='r')
+scatter, tufts = pool.add_scatter(pond, pool.add_mesh(*tuft()), args.count, seed=1, mtlid=1, scale=(0.03, 0.07), density=ripple, channel='r',
+                                   min_distance=args.min_distance)
 pool.compose()
+if args.min_distance > 0:
+    m, kept, rounds, _, _ = pool.scatter_spacing(scatter)
+    print('%d of %d candidates stand at least %g apart (%d rounds on the device): the first %d are the tufts' % (kept, m, args.min_distance, rounds, args.count))
 s = pool.scatter_stats()
 print('%d tufts (objects %d .. %d) scattered over %d faces: %d weight, %d scan, %d selection and %d placement launches'
       % (s.instances, tufts.start, tufts.stop - 1, pool._object_faces(mesh), s.weight_launches, s.scan_launches, s.select_launches, s.place_launches))

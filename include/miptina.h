@@ -853,7 +853,48 @@ int mpt_displace_corners(const int32_t *faces /* [nfaces][3] */, int64_t nfaces,
  *   mpt_compose left them on the device (any may be NULL); fails before that mpt_compose.
  * mpt_scatter_rule: selection and placement as a pure function (no context, no GPU): for world corners [nfaces][3][3], shares
  *   q [nfaces] and parameters (the density fields are not read), the records [count] and matrices [count][16] of instances
- *   first .. first + count - 1.  Returns 0, or 1 for arguments that name no scatter, 2 for shares that sum to 0. */
+ *   first .. first + count - 1.  Returns 0, or 1 for arguments that name no scatter, 2 for shares that sum to 0.
+ *
+ * Spacing: a scatter with a minimum distance (Blender's "Poisson Disk" mode of "distribute points on faces").  A SPACED scatter has a
+ * minimum distance r > 0 and a candidate count M >= count.  All of it is f64, every sum and product in the order written, without
+ * contraction, as the rest of the definition.
+ *   Candidates: candidate j (0 <= j < M) is, bit for bit, instance j of the selection above (draw(j, k), face, b1, b2, scale, yaw)
+ *     over the same shares and cdf: a spaced scatter of `count` from M candidates and a plain scatter of M share their records.
+ *   Position: the placement's point P_j = (b0 P0 + b1 P1) + b2 P2, the world corners those of the surface as it stands in this
+ *     mpt_compose, unrounded.
+ *   Conflict: d2 = ((dx dx) + (dy dy)) + (dz dz), r2 = r r; j and k conflict iff d2 < r2.  A distance of exactly r is allowed.  A
+ *     coordinate that is not finite makes every comparison false: such a point conflicts with nothing.
+ *   Elimination: in candidate order, j is kept iff no kept k < j conflicts with it -- the greedy pass over the list of points, the
+ *     lexicographically first maximal independent set; candidate order is the priority, and the draws make it a random one.
+ *   Instances: the first `count` kept candidates in candidate order; instance i's sticky record is that candidate's.  Placement,
+ *     stickiness, refit and every later call are unchanged: when the surface deforms the instances keep their faces and points, so
+ *     their distances follow the surface (stickiness wins, as with a density image); mpt_scatter_rescatter draws and eliminates again.
+ *   Refusal: fewer than `count` kept: mpt_compose refuses, naming the scatter, the number kept, M, r and count; scene and composed
+ *     model stay as they were, as for a surface without weight, and the scatters that were due stay due.
+ * On the device the greedy pass runs as rounds over a state per candidate (undecided, kept, rejected): an undecided j looks at its
+ *   conflicting lower-index neighbours; any kept: rejected; else none undecided: kept; else it waits.  A round is a launch; the host
+ *   looks after every batch of rounds whether a scatter still waits.  Neighbours are found through a uniform grid, which is no
+ *   part of the rule.  One launch of each kind per mpt_compose whatever the number of spaced scatters; a compose in which no
+ *   spaced scatter selects launches none of it.
+ * mpt_scatter_set_spacing: the minimum distance and the candidates of a scatter; min_distance == 0 makes it plain again (candidates
+ *   is not read).  Refuses, naming them, a distance that is negative or not finite and candidates below the scatter's count or above
+ *   2^24.  The next mpt_compose selects and places again.
+ * mpt_scatter_get_spacing: the scatter's last elimination: candidates M, the number kept, the rounds it took on the device (at most
+ *   the synchronous count of mpt_scatter_space_rule: states are updated in place), kept_flags [M] (1 or 0) and index [count], the
+ *   candidate that became instance i (any may be NULL).  Fails before that mpt_compose and for a plain scatter.
+ * mpt_scatter_spacing_stats: of the last mpt_compose: the spaced scatters that selected, their candidates and kept candidates, the
+ *   most rounds one of them took, the grid kernels (5: positions, box, count, scan, fill), round kernels and compaction kernels
+ *   launched, and the host's waits for the elimination (one per batch of rounds and one for the kept counts; mpt_scatter_stats
+ *   counts them among its host_fetches).  All zero when no spaced scatter selected.
+ * mpt_scatter_spacing_kernel_time: the HIP-event time (ms) of the eliminations of the mpt_compose calls since the last call -- from
+ *   before the grid to behind the compaction, the host's waits between the batches of rounds included; it is part of the selection's
+ *   time of mpt_scatter_kernel_time -- and their number.
+ * mpt_scatter_space_rule: the elimination as a pure function (no context, no GPU) over points [n][3]: kept [n] (1 or 0) and *rounds,
+ *   the rounds of the synchronous form, in which every candidate reads the states the round before left (either may be NULL).  All
+ *   pairs are tested.  Returns 0, or 1 for n < 0, n > 0 without points, or an r that is negative or NaN.
+ * mpt_scatter_space_points: a test door (as mpt_walk_trace): the device's grid and round kernels on explicit points [n][3], n up to
+ *   2^24; kept [n] and *rounds as the device made them.  It follows a query's contract: launched at the call on the main stream
+ *   and waited for; it changes nothing else in the context. */
 enum { MPT_SCATTER_ALIGN_NORMAL = 0, MPT_SCATTER_ALIGN_UP = 1 };
 typedef struct {
     double smin, smax;                  /* the range of the instances' scale */
@@ -878,6 +919,17 @@ int mpt_scatter_kernel_time(mpt_ctx *ctx, double *select_ms, double *place_ms, i
 int mpt_scatter_get(mpt_ctx *ctx, int scatter_id, mpt_scatter_point *points, double *worlds /* [count][16] */, uint32_t *q /* [F] */);
 int mpt_scatter_rule(const double *corners /* [nfaces][3][3] */, const uint32_t *q, int64_t nfaces, const mpt_scatter_params *params,
                      uint64_t seed, int64_t first, int64_t count, mpt_scatter_point *points, double *worlds /* [count][16] */);
+typedef struct {
+    int64_t scatters, candidates, kept, rounds;
+    int64_t grid_launches, round_launches, compact_launches, host_reads;
+} mpt_scatter_spacing_info;
+int mpt_scatter_set_spacing(mpt_ctx *ctx, int scatter_id, double min_distance, int64_t candidates);
+int mpt_scatter_get_spacing(mpt_ctx *ctx, int scatter_id, int64_t *candidates, int64_t *kept, int32_t *rounds, uint8_t *kept_flags /* [candidates] */,
+                            int64_t *index /* [count] */);
+int mpt_scatter_spacing_stats(mpt_ctx *ctx, mpt_scatter_spacing_info *out);
+int mpt_scatter_spacing_kernel_time(mpt_ctx *ctx, double *ms, int *eliminations);
+int mpt_scatter_space_rule(const double *points /* [n][3] */, int64_t n, double r, uint8_t *kept, int32_t *rounds);
+int mpt_scatter_space_points(mpt_ctx *ctx, const double *points /* [n][3] */, int64_t n, double r, uint8_t *kept, int32_t *rounds);
 
 /* Refit: after the model's faces moved (mpt_compose after mpt_object_set_world, or mpt_load_model of as many faces), keep the trees
  * of the last mpt_build_tree and fit their boxes to the model again, on the device -- what a viewport does for a moved object instead of

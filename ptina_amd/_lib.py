@@ -107,6 +107,12 @@ class ScatterInfo(C.Structure):
                 ('place_launches', C.c_int64), ('host_fetches', C.c_int64)]
 
 
+class ScatterSpacingInfo(C.Structure):
+    '''mpt_scatter_spacing_info (include/miptina.h): what mpt_scatter_spacing_stats hands back'''
+    _fields_ = [('scatters', C.c_int64), ('candidates', C.c_int64), ('kept', C.c_int64), ('rounds', C.c_int64), ('grid_launches', C.c_int64),
+                ('round_launches', C.c_int64), ('compact_launches', C.c_int64), ('host_reads', C.c_int64)]
+
+
 class DisplaceInfo(C.Structure):
     '''mpt_displace_info (include/miptina.h): what mpt_displace_stats hands back'''
     _fields_ = [('displaced_meshes', C.c_int64), ('copies', C.c_int64), ('displaced_copies', C.c_int64), ('displaced_verts', C.c_int64),
@@ -301,6 +307,12 @@ SIGNATURES = {
     'mpt_scatter_get': (_i, [_vp, _i, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     'mpt_scatter_rule': (_i, [C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_int64, C.POINTER(ScatterParams), C.c_uint64, C.c_int64, C.c_int64,
                               C.c_void_p, C.POINTER(C.c_double)]),
+    'mpt_scatter_set_spacing': (_i, [_vp, _i, C.c_double, C.c_int64]),
+    'mpt_scatter_get_spacing': (_i, [_vp, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int64)]),
+    'mpt_scatter_spacing_stats': (_i, [_vp, C.POINTER(ScatterSpacingInfo)]),
+    'mpt_scatter_spacing_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_scatter_space_rule': (_i, [C.POINTER(C.c_double), C.c_int64, C.c_double, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
+    'mpt_scatter_space_points': (_i, [_vp, C.POINTER(C.c_double), C.c_int64, C.c_double, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
     'mpt_refit_tree': (_i, [_vp]),
     'mpt_refit_stats': (_i, [_vp, C.POINTER(RefitInfo)]),
     'mpt_refit_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
@@ -693,6 +705,39 @@ def scatter_rule(corners, q, seed, count, first=0, **params):
                                          C.byref(p), int(seed) & (2 ** 64 - 1), int(first), int(count), points.ctypes.data_as(C.c_void_p),
                                          worlds.ctypes.data_as(C.POINTER(C.c_double)))
     return rc, points, worlds
+
+
+SPACE_MAX_CANDIDATES = 1 << 24                                           # csrc/scatter_rule.h MPT_SPACE_MAX_CANDIDATES
+
+
+def scatter_spacing(count, min_distance=0.0, candidates=None):
+    '''(min_distance, candidates) of ModelPool.add_scatter's keywords as mpt_scatter_set_spacing takes them; candidates=None: 4 * count'''
+    r = float(min_distance)
+    if not np.isfinite(r) or r < 0:
+        raise ValueError('the minimum distance %r is negative or not finite' % (min_distance,))
+    m = 4 * int(count) if candidates is None else int(candidates)
+    if r > 0 and not int(count) <= m <= SPACE_MAX_CANDIDATES:
+        raise ValueError('%d candidates outside [%d, %d], the count and 2^24' % (m, count, SPACE_MAX_CANDIDATES))
+    return r, m
+
+
+def scatter_space_rule(points, r):
+    '''mpt_scatter_space_rule (no context, no GPU): (verdict, kept [n] uint8, rounds of the synchronous form) of the elimination of
+    points [n,3] at the minimum distance r'''
+    points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    kept, rounds = np.zeros(points.shape[0], np.uint8), C.c_int32(0)
+    rc = load_library().mpt_scatter_space_rule(points.ctypes.data_as(C.POINTER(C.c_double)), points.shape[0], float(r),
+                                               kept.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(rounds))
+    return rc, kept, rounds.value
+
+
+def scatter_space_points(context, points, r):
+    '''mpt_scatter_space_points, the test door: (kept [n] uint8, rounds) as the device's grid and round kernels make them'''
+    points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    kept, rounds = np.zeros(points.shape[0], np.uint8), C.c_int32(0)
+    context.call('mpt_scatter_space_points', points.ctypes.data_as(C.POINTER(C.c_double)), points.shape[0], float(r),
+                 kept.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(rounds))
+    return kept, rounds.value
 
 
 def devices_isolated():

@@ -131,6 +131,17 @@ MPT_KERNEL_API hipError_t mpt_launch_scatter_select(const MptScatterJob *jobs, c
                                                     MptScatterPoint *points, hipStream_t stream);
 MPT_KERNEL_API hipError_t mpt_launch_scatter_place(const float *pool, MptComposeObj *objs, const MptScatterJob *jobs, const MptRun *runs, int nruns,
                                                    int blocks, const MptScatterPoint *points, unsigned epoch, hipStream_t stream);
+// scatter_space.hip: the elimination of the spaced scatters' candidates -- their positions and the grid over them (five kernels),
+// `n` rounds, and the first `count` kept records compacted into the sticky arena
+MPT_KERNEL_API hipError_t mpt_launch_space_grid(const float *pool, const MptComposeObj *objs, const MptScatterJob *jobs, const MptSpaceJob *sjobs,
+                                                const MptRun *runs, int nruns, int blocks, const MptScatterPoint *records, double *pos, double *part,
+                                                MptSpaceGrid *grids, int32_t *state, uint32_t *cursor, uint32_t *start, int32_t *items, hipStream_t stream);
+MPT_KERNEL_API hipError_t mpt_launch_space_rounds(const MptSpaceJob *sjobs, const MptSpaceGrid *grids, const MptRun *runs, int nruns, int blocks,
+                                                  const double *pos, const uint32_t *start, const uint32_t *cursor, const int32_t *items, int32_t *state,
+                                                  uint32_t *left_host, unsigned first, int n, hipStream_t stream);
+MPT_KERNEL_API hipError_t mpt_launch_space_compact(const MptSpaceJob *sjobs, const MptRun *runs, int nruns, const int32_t *state,
+                                                   const MptScatterPoint *records, MptScatterPoint *points, int32_t *index, uint32_t *kept_host,
+                                                   hipStream_t stream);
 
 // on-GPU LBVH build (lbvh_build.hip)
 struct MptLbvhBuffers {
@@ -826,6 +837,10 @@ struct mpt_ctx {
         size_t face_at = 0, point_at = 0;                // where they and the sticky records lie in the arenas
         bool select = true;                              // weights, scan and selection are due: a new scatter, mpt_scatter_rescatter, mpt_scatter_set_params
         bool placed = false;                             // the rows of the device's table hold the instances' matrices (mpt_scatter_get)
+        // spacing (mpt_scatter_set_spacing): the minimum distance (0: a plain scatter), the candidates, where
+        // their states lie in their arena, and what the scatter's last elimination came to (mpt_scatter_get_spacing)
+        double min_distance = 0; int64_t candidates = 0; size_t state_at = 0;
+        int64_t kept = 0; int32_t rounds = 0;
     };
     struct MPT_INTERNAL Scatter {                        // scatters (scene_scatter.cpp: mpt_scatter_*, scatter_mark, scatter_step)
         std::vector<MptScatterRow> rows;
@@ -841,7 +856,19 @@ struct mpt_ctx {
         mpt_scatter_info stats{};
         int launches = 0;                                // kernels launched since mpt_scatter_kernel_time last asked
         MptLaunchTimer select_timer, place_timer;        // mpt_compose: {before, after} weights + scan + selection, and the placement
-        explicit Scatter(MptEventPool &ev) : select_timer(2, ev), place_timer(2, ev) {}
+        MptLaunchTimer space_timer;                      // ... and, inside the selection's, {before, after} the elimination of the spaced scatters
+        struct MPT_INTERNAL Space {                      // the spaced scatters' elimination (scatter_space.hip; space_eliminate)
+            size_t states_used = 0;                      // entries of the arena of states that scatters own
+            DevBuf<int32_t> state;                       // per candidate of every spaced scatter: undecided, kept or rejected; behind them a door call's
+            DevBuf<int32_t> index;                       // beside the sticky records: the candidate each instance came from
+            // an elimination's workspace: positions [3] and bucket-sorted items per candidate, cursor and start per bucket, the box
+            // partials per workgroup, and its tables
+            DevBuf<double> pos, part; DevBuf<int32_t> items; DevBuf<uint32_t> cursor, start;
+            DevBuf<MptSpaceJob> jobs; DevBuf<MptSpaceGrid> grids; DevBuf<MptRun> runs;
+            MappedBuf<uint32_t> words; size_t words_cap = 0;   // per scatter of an elimination: the last round a lane waited in, then the number kept
+            mpt_scatter_spacing_info stats{};            // the last mpt_compose's
+        } space;
+        explicit Scatter(MptEventPool &ev) : select_timer(2, ev), place_timer(2, ev), space_timer(2, ev) {}
     } scatter{events};
     struct MPT_INTERNAL Refit {                          // mpt_refit_tree (tree_refit.cpp, refit_rule.h)
         int topo = MPT_TOPO_NONE;                        // MptTopoState: do the node records hold a topology, and if not, why not

@@ -319,3 +319,21 @@ struct MptScatterJob {                      // 112 bytes
     double smin, smax;
     double up[3];                            // unit length (the host normalises it once)
 };
+// Spacing (scatter_space.hip): MptSpaceJob is one spaced scatter of a compose's elimination launches -- or the explicit points of
+// mpt_scatter_space_points -- and MptSpaceGrid the uniform grid the fold kernel lays over its candidates' positions
+struct MptSpaceJob {                        // 72 bytes
+    int32_t job;                             // its row of the compose's table of scatters (-1: explicit points, nothing is selected or compacted)
+    int32_t m, count;                        // M candidates, the first `count` kept become the instances
+    uint32_t mask;                           // buckets of its hash table - 1 (a power of two)
+    int64_t cand_at;                         // its candidates' records in the arena of records (behind the sticky ones)
+    int64_t at;                              // its first entry of the workspace arrays: positions (3 each) and items
+    int64_t bucket_at;                       // its first bucket
+    int64_t state_at;                        // its candidates' states, which stay until its next elimination
+    int64_t point_at;                        // its sticky records, and beside them the candidates they came from
+    double r, r2;                            // the minimum distance and r r
+};
+struct MptSpaceGrid {                       // 48 bytes
+    double lo[3], h;                         // the corner of the finite positions' box and the cell edge
+    int32_t n[3], pad;                       // cells along each axis
+};
+enum { MPT_SPACE_BATCH = 8 };               // rounds launched between two looks of the host at the scatters still undecided

@@ -2,7 +2,8 @@
 // scatter.hip): the draws, the weight of a face, its integer share, the choice of a face and a point on it, and the world matrix of
 // an instance on the surface as it is now.  Plain C++17 with nothing of HIP and no context (as history_rule.h), so that a
 // stand-alone program can run all of it under a sanitizer (tools/scatter_rule_check.cpp); under hipcc the same functions are the
-// kernels' arithmetic.  The C ABI has selection and placement as mpt_scatter_rule.
+// kernels' arithmetic.  The C ABI has selection and placement as mpt_scatter_rule, and the elimination of a spaced scatter -- a
+// minimum distance, the last section but one -- as mpt_scatter_space_rule.
 //
 // Arithmetic: f64, one correctly rounded operation per operator in the order written, never contracted (the pragma below in every
 // function that computes, for a host compiler; -ffp-contract=off for scatter.hip, the Makefile's rule), so that
@@ -140,11 +141,19 @@ MPT_HD void mpt_scatter_basis(const double N[3], double T0[3], double B0[3]) {
 // The world matrix (row-major) of an instance with record r on the face with world corners P0 P1 P2 as they are now: columns
 // scale Tn, scale N, scale Bn, P; bottom row 0 0 0 1.  align 0: N is the face's geometric normal (a collapsed face gives NaN);
 // else N is `up`, of unit length
+// the point of record r on the face with world corners P0 P1 P2: P = (b0 P0 + b1 P1) + b2 P2, b0 = (1 - b1) - b2.  The fourth column
+// of the matrix below, and the position a spaced scatter's candidates are held apart by
+MPT_HD void mpt_scatter_point_of(const double P0[3], const double P1[3], const double P2[3], const MptScatterPoint &r, double P[3]) {
+    MPT_NO_CONTRACT
+    const double b0 = (1.0 - r.b1) - r.b2;
+    for (int k = 0; k < 3; k++) P[k] = (b0 * P0[k] + r.b1 * P1[k]) + r.b2 * P2[k];
+}
+
 MPT_HD void mpt_scatter_place(const double P0[3], const double P1[3], const double P2[3], const MptScatterPoint &r, int align, const double up[3],
                               double world[16]) {
     MPT_NO_CONTRACT
-    const double b0 = (1.0 - r.b1) - r.b2;
-    double N[3], T0[3], B0[3];
+    double N[3], T0[3], B0[3], P[3];
+    mpt_scatter_point_of(P0, P1, P2, r, P);
     if (align == 0) {
         double c[3];
         mpt_scatter_cross(P0, P1, P2, c);
@@ -158,7 +167,81 @@ MPT_HD void mpt_scatter_place(const double P0[3], const double P1[3], const doub
         world[4 * k] = r.scale * Tn;
         world[4 * k + 1] = r.scale * N[k];
         world[4 * k + 2] = r.scale * Bn;
-        world[4 * k + 3] = (b0 * P0[k] + r.b1 * P1[k]) + r.b2 * P2[k];
+        world[4 * k + 3] = P[k];
     }
     world[12] = 0.0; world[13] = 0.0; world[14] = 0.0; world[15] = 1.0;
+}
+
+// ------------------------------------------------------------------ spacing
+// A SPACED scatter has a minimum distance r > 0 and M >= count candidates.  Candidate j is, bit for bit, instance j of the
+// selection above; its position P_j is mpt_scatter_point_of on the surface as it stands.  j and k CONFLICT iff
+// d2 = ((dx dx) + (dy dy)) + (dz dz) < r2 = r r: a distance of exactly r is allowed, and a coordinate that is not finite makes the
+// comparison false, so such a point conflicts with nothing.  In candidate order, j is KEPT iff no kept k < j conflicts with it
+// (the greedy pass, the lexicographically first maximal independent set); the instances are the first `count` kept candidates.
+enum { MPT_SPACE_UNDECIDED = 0, MPT_SPACE_KEPT = 1, MPT_SPACE_REJECTED = 2 };
+enum : int64_t { MPT_SPACE_MAX_CANDIDATES = (int64_t)1 << 24 };
+
+MPT_HD bool mpt_scatter_conflict(const double a[3], const double b[3], double r2) {
+    MPT_NO_CONTRACT
+    const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+    const double d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
+    return d2 < r2;
+}
+
+// What an undecided candidate makes of one look at its conflicting lower neighbours' states (a round of the device): any kept ->
+// rejected; else none undecided -> kept; else it waits.  States only move from undecided to their final value, and the lowest
+// undecided candidate always decides, so rounds in any interleaving end in the greedy set
+MPT_HD int mpt_scatter_space_decide(bool any_kept, bool any_undecided) {
+    return any_kept ? MPT_SPACE_REJECTED : any_undecided ? MPT_SPACE_UNDECIDED : MPT_SPACE_KEPT;
+}
+
+// The elimination over pos [n][3] on the host: kept [n] (1 or 0) by the greedy pass, and the number of rounds the SYNCHRONOUS form
+// of the rounds takes (every candidate reads the states the round before left): candidate j decides in round t(j) -- a rejected one
+// in the round after the first of its conflicting kept lower neighbours was kept, a kept one in the round after the last of its
+// conflicting lower neighbours decided (round 1 without any) -- and the count is the largest t.  All pairs are looked at: n^2 / 2
+// tests, for tests and tools.  t [n] is the caller's scratch.
+inline int32_t mpt_scatter_space_of(const double *pos, int64_t n, double r, uint8_t *kept, int32_t *t) {
+    MPT_NO_CONTRACT
+    const double r2 = r * r;
+    int32_t rounds = 0;
+    for (int64_t j = 0; j < n; j++) {
+        int32_t first_kept = 0, last = 0;
+        for (int64_t k = 0; k < j; k++) {
+            if (!mpt_scatter_conflict(pos + 3 * j, pos + 3 * k, r2)) continue;
+            if (kept[k] && (first_kept == 0 || t[k] < first_kept)) first_kept = t[k];
+            if (t[k] > last) last = t[k];
+        }
+        kept[j] = first_kept == 0;
+        t[j] = (first_kept ? first_kept : last) + 1;
+        if (t[j] > rounds) rounds = t[j];
+    }
+    return rounds;
+}
+
+// ------------------------------------------------------------------ the device's search structure (no part of the rule)
+// A uniform grid over the box [lo, hi] of the finite positions, so that a candidate looks at the 27 cells around its own instead of
+// at everybody.  (scatter_space.hip's header has the argument that no conflicting pair is missed.)
+//   edge: h = max(r (1 + 2^-20), 2^-20 times the largest extent, 2^-1000) -- a hair above r, at most 2^20 cells along an axis so that
+//     cell coordinates are small exact integers whatever the extent, and well inside the normal numbers.  A box whose extent is not
+//     finite has h = +inf and the one cell 0: every pair is tested
+//   cell: c(x) = (int) floor((x - lo) / h), each operation rounded once: a monotone function of x, 0 at lo
+MPT_HD double mpt_space_edge(double r, const double lo[3], const double hi[3]) {
+    MPT_NO_CONTRACT
+    double ext = 0.0;
+    for (int k = 0; k < 3; k++) { const double e = hi[k] - lo[k]; if (!(e <= ext)) ext = e; }      // (NaN or +inf takes it)
+    double h = r * (1.0 + 0x1p-20);
+    const double he = ext * 0x1p-20;
+    if (!(he <= h)) h = he;
+    if (!(h >= 0x1p-1000)) h = 0x1p-1000;
+    return std::isfinite(h) ? h : INFINITY;
+}
+MPT_HD int32_t mpt_space_cell(double x, double lo, double h) {
+    MPT_NO_CONTRACT
+    if (!(h < INFINITY)) return 0;
+    const double u = std::floor((x - lo) / h);
+    return u >= 0.0 ? (u <= 0x1p21 ? (int32_t)u : (int32_t)0x1p21) : 0;                           // (finite x in [lo, hi]: 0 <= u <= 2^20 + 1)
+}
+// the bucket of cell (cx, cy, cz), each below 2^21 + 1: SplitMix64's finaliser over the packed coordinates
+MPT_HD uint32_t mpt_space_bucket(int32_t cx, int32_t cy, int32_t cz, uint32_t mask) {
+    return (uint32_t)mpt_scatter_mix((uint64_t)cx | (uint64_t)cy << 22 | (uint64_t)cz << 44) & mask;
 }

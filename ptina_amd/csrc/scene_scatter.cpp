@@ -55,6 +55,7 @@ void scatter_scene_cleared(mpt_ctx *c) {
     auto &sc = c->scatter;
     sc.rows.clear();
     sc.faces_used = sc.points_used = 0;
+    sc.space.states_used = 0;
 }
 
 // ---------------------------------------------------------------- the scatters
@@ -129,6 +130,91 @@ extern "C" int mpt_scatter_rescatter(mpt_ctx *c, int scatter_id, uint64_t seed) 
     return 0;
 }
 
+extern "C" int mpt_scatter_set_spacing(mpt_ctx *c, int scatter_id, double min_distance, int64_t candidates) {
+    if (use(c)) return 1;
+    const char *who = "mpt_scatter_set_spacing";
+    if (check_scatter(c, scatter_id, who)) return 1;
+    auto &row = c->scatter.rows[scatter_id];
+    if (!std::isfinite(min_distance) || min_distance < 0.0) return fail("%s: scatter %d: the minimum distance %g is negative or not finite", who, scatter_id, min_distance);
+    if (min_distance == 0.0) { row.min_distance = 0.0; row.select = true; return 0; }
+    if (candidates < row.count || candidates > MPT_SPACE_MAX_CANDIDATES)
+        return fail("%s: scatter %d: %lld candidates outside [%d, %lld], its count and 2^24", who, scatter_id, (long long)candidates, row.count,
+                    (long long)MPT_SPACE_MAX_CANDIDATES);
+    if (candidates != row.candidates) {       // new room for its states (the old room stays behind until the scene is cleared)
+        row.state_at = c->scatter.space.states_used;
+        c->scatter.space.states_used += (size_t)candidates;
+    }
+    row.min_distance = min_distance; row.candidates = candidates; row.select = true;
+    return 0;
+}
+
+// ---------------------------------------------------------------- the elimination of spaced scatters (scatter_space.hip)
+// The rows sj of one elimination: their room in the workspace, the launches, the host's looks.  records: the candidates' records
+// (rows of a compose) -- explicit points (rows with job < 0) come from host_pos [sum of m][3] instead.  `compact`: the kept records
+// go to points and their candidates to index.  rounds and kept (per row, kept only with compact) and st are what it came to.
+static int space_eliminate(mpt_ctx *c, std::vector<MptSpaceJob> &sj, const double *host_pos, const MptScatterPoint *records, MptScatterPoint *points,
+                           bool compact, std::vector<int32_t> &rounds, std::vector<int64_t> &kept, mpt_scatter_spacing_info &st) {
+    auto &sc = c->scatter;
+    auto &sp = sc.space;
+    const int n = (int)sj.size();
+    std::vector<int32_t> ms((size_t)n);
+    size_t cands = 0, buckets = 0, states = sp.states_used;
+    int32_t most = 0;
+    for (int s = 0; s < n; s++) {
+        MptSpaceJob &t = sj[s];
+        uint32_t nb = 1;
+        while ((int64_t)nb < t.m) nb <<= 1;
+        t.mask = nb - 1; t.at = (int64_t)cands; t.bucket_at = (int64_t)buckets;
+        t.r2 = t.r * t.r;
+        cands += (size_t)t.m; buckets += nb;
+        states = std::max(states, (size_t)t.state_at + (size_t)t.m);
+        ms[s] = t.m; most = std::max(most, t.m);
+    }
+    std::vector<MptRun> runs((size_t)n);
+    int blocks = 0;
+    const int nruns = mpt_run_plan_into(ms.data(), nullptr, n, MPT_SCATTER_CHUNK, runs.data(), &blocks);
+    if (nruns != n) return fail("a spaced scatter without candidates");
+    if (grow_keeping(sp.state, states, sp.state.cap, c->stream)) return 1;
+    if (sp.pos.reserve(cands * 3) || sp.items.reserve(cands) || sp.cursor.reserve(buckets) || sp.start.reserve(buckets) ||
+        sp.part.reserve((size_t)blocks * 6) || sp.jobs.reserve((size_t)n) || sp.grids.reserve((size_t)n) || sp.runs.reserve((size_t)n)) return 1;
+    if ((size_t)n > sp.words_cap) {
+        const size_t cap = std::max((size_t)n, 2 * sp.words_cap);
+        if (sp.words.create(2 * cap)) return 1;
+        sp.words_cap = cap;
+    }
+    uint32_t *left = sp.words.host, *kept_word = sp.words.host + sp.words_cap;
+    for (int s = 0; s < n; s++) left[s] = kept_word[s] = 0;
+    HIP_TRY(hipMemcpyAsync(sp.jobs, sj.data(), (size_t)n * sizeof(MptSpaceJob), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(sp.runs, runs.data(), (size_t)n * sizeof(MptRun), hipMemcpyHostToDevice, c->stream));
+    if (host_pos) HIP_TRY(hipMemcpyAsync(sp.pos, host_pos, cands * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(sp.cursor, 0, buckets * sizeof(uint32_t), c->stream));
+    HIP_TRY(mpt_launch_space_grid(c->compose.bufs.pool, c->compose.bufs.objs, sc.jobs, sp.jobs, sp.runs, nruns, blocks, records, sp.pos, sp.part, sp.grids,
+                                  sp.state, sp.cursor, sp.start, sp.items, c->stream));
+    st.grid_launches += 5; sc.launches += 5;
+    // the rounds, a batch at a time: the lowest undecided candidate decides in every round, so a scatter takes at most m of them
+    unsigned done = 0;
+    for (bool waits = true; waits;) {
+        if ((int64_t)done >= (int64_t)most + MPT_SPACE_BATCH) return fail("the elimination of a spaced scatter did not settle in %u rounds", done);
+        HIP_TRY(mpt_launch_space_rounds(sp.jobs, sp.grids, sp.runs, nruns, blocks, sp.pos, sp.start, sp.cursor, sp.items, sp.state, sp.words.dev, done + 1,
+                                        MPT_SPACE_BATCH, c->stream));
+        done += MPT_SPACE_BATCH;
+        st.round_launches += MPT_SPACE_BATCH; sc.launches += MPT_SPACE_BATCH;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        st.host_reads++;
+        waits = false;
+        for (int s = 0; s < n; s++) waits |= left[s] == done;
+    }
+    rounds.assign((size_t)n, 0); kept.assign((size_t)n, 0);
+    for (int s = 0; s < n; s++) { rounds[s] = (int32_t)left[s] + 1; st.rounds = std::max<int64_t>(st.rounds, rounds[s]); }
+    if (!compact) return 0;
+    HIP_TRY(mpt_launch_space_compact(sp.jobs, sp.runs, nruns, sp.state, records, points, sp.index, sp.words.dev + sp.words_cap, c->stream));
+    st.compact_launches += 1; sc.launches += 1;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    st.host_reads++;
+    for (int s = 0; s < n; s++) { kept[s] = kept_word[s]; st.kept += kept[s]; }
+    return 0;
+}
+
 // ---------------------------------------------------------------- the steps of mpt_compose
 bool scatter_selection_due(const mpt_ctx *c) {
     for (const auto &r : c->scatter.rows)
@@ -183,6 +269,7 @@ int scatter_step(mpt_ctx *c) {
     auto &st = sc.stats;
     st.selected_scatters = st.placed_scatters = st.placed_instances = 0;
     st.weight_launches = st.scan_launches = st.select_launches = st.place_launches = st.host_fetches = 0;
+    sc.space.stats = mpt_scatter_spacing_info{};
     const int n = (int)sc.rows.size();
     if (n == 0) return 0;
     std::vector<int32_t> faces((size_t)n), counts((size_t)n), sel((size_t)n), plc((size_t)n);
@@ -194,8 +281,24 @@ int scatter_step(mpt_ctx *c) {
         nsel += sel[j]; nplc += plc[j];
     }
     if (nplc == 0) return 0;
+    // the spaced scatters that select: the selection makes their candidates, behind the sticky records of all, and the elimination
+    // picks the instances from them.  Without one the compose takes the plain path, launch for launch
+    std::vector<MptSpaceJob> spaced;
+    std::vector<int32_t> drawn(counts);                                   // records the selection makes per scatter
+    size_t cands = 0;
+    for (int j = 0; j < n; j++) {
+        const auto &r = sc.rows[j];
+        if (!sel[j] || !(r.min_distance > 0.0)) continue;
+        MptSpaceJob t{};
+        t.job = j; t.m = (int32_t)r.candidates; t.count = r.count; t.r = r.min_distance;
+        t.cand_at = (int64_t)(sc.points_used + cands); t.state_at = (int64_t)r.state_at; t.point_at = (int64_t)r.point_at;
+        cands += (size_t)r.candidates;
+        drawn[j] = t.m;
+        spaced.push_back(t);
+    }
+    const size_t views = spaced.empty() ? 0 : (size_t)n;                  // the selection's views of the jobs: rows n .. 2 n - 1
     std::vector<MptScatterJob> &jobs = sc.h_jobs;
-    jobs.assign((size_t)n, MptScatterJob{});
+    jobs.assign((size_t)n + views, MptScatterJob{});
     for (int j = 0; j < n; j++) {
         const auto &r = sc.rows[j];
         MptScatterJob &t = jobs[j];
@@ -214,20 +317,26 @@ int scatter_step(mpt_ctx *c) {
     runs.assign((size_t)3 * (size_t)n, MptRun{});
     int nruns[3] = { 0, 0, 0 }, blocks[3] = { 0, 0, 0 };
     nruns[0] = mpt_run_plan_into(faces.data(), sel.data(), n, MPT_SCATTER_CHUNK, runs.data(), &blocks[0]);
-    nruns[1] = mpt_run_plan_into(counts.data(), sel.data(), n, MPT_SCATTER_CHUNK, runs.data() + (size_t)n, &blocks[1]);
+    nruns[1] = mpt_run_plan_into(drawn.data(), sel.data(), n, MPT_SCATTER_CHUNK, runs.data() + (size_t)n, &blocks[1]);
     nruns[2] = mpt_run_plan_into(counts.data(), plc.data(), n, MPT_SCATTER_CHUNK, runs.data() + 2 * (size_t)n, &blocks[2]);
     if (nruns[0] < 0 || nruns[1] < 0 || nruns[2] < 0) return fail("too many faces or instances to scatter");
+    if (views) {                                                          // a spaced scatter draws m records into its candidates' room
+        for (int j = 0; j < n; j++) jobs[(size_t)n + j] = jobs[j];
+        for (const MptSpaceJob &t : spaced) { jobs[(size_t)n + t.job].count = t.m; jobs[(size_t)n + t.job].point_at = t.cand_at; }
+        for (int r = 0; r < nruns[1]; r++) runs[(size_t)n + r].item += n;
+    }
     // room: the arenas keep what they hold (the records and shares of the scatters that stay as they are)
     if (grow_keeping(sc.w, sc.faces_used, sc.w.cap, c->stream) || grow_keeping(sc.q, sc.faces_used, sc.q.cap, c->stream) ||
-        grow_keeping(sc.cdf, sc.faces_used, sc.cdf.cap, c->stream) || grow_keeping(sc.points, sc.points_used, sc.points.cap, c->stream)) return 1;
-    if (sc.jobs.reserve((size_t)n) || sc.runs.reserve((size_t)3 * (size_t)n) || sc.wmax.reserve((size_t)n)) return 1;
+        grow_keeping(sc.cdf, sc.faces_used, sc.cdf.cap, c->stream) || grow_keeping(sc.points, sc.points_used + cands, sc.points.cap, c->stream)) return 1;
+    if (views && grow_keeping(sc.space.index, sc.points_used, sc.space.index.cap, c->stream)) return 1;
+    if (sc.jobs.reserve((size_t)n + views) || sc.runs.reserve((size_t)3 * (size_t)n) || sc.wmax.reserve((size_t)n)) return 1;
     if ((size_t)n > sc.wmax_cap) {
         const size_t cap = std::max((size_t)n, 2 * sc.wmax_cap);
         if (sc.wmax_host.create(cap)) return 1;
         sc.wmax_cap = cap;
     }
     if (sc.part.reserve((size_t)std::max(blocks[0], 1)) || sc.bsum.reserve((size_t)std::max(blocks[0], 1))) return 1;
-    HIP_TRY(hipMemcpyAsync(sc.jobs, jobs.data(), (size_t)n * sizeof(MptScatterJob), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(sc.jobs, jobs.data(), jobs.size() * sizeof(MptScatterJob), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(sc.runs, runs.data(), runs.size() * sizeof(MptRun), hipMemcpyHostToDevice, c->stream));
     if (nsel > 0) {
         MptTimedSpan span(sc.select_timer, c->stream);
@@ -245,6 +354,25 @@ int scatter_step(mpt_ctx *c) {
         st.scan_launches = 3; sc.launches += 3;
         HIP_TRY(mpt_launch_scatter_select(sc.jobs, sc.runs + (size_t)n, nruns[1], blocks[1], sc.cdf, sc.points, c->stream));
         st.select_launches = 1; sc.launches += 1;
+        if (!spaced.empty()) {
+            auto &ss = sc.space.stats;
+            std::vector<int32_t> rounds;
+            std::vector<int64_t> kept;
+            ss.scatters = (int64_t)spaced.size(); ss.candidates = (int64_t)cands;
+            MptTimedSpan inner(sc.space_timer, c->stream);
+            HIP_TRY(inner.begun);
+            const int rc = space_eliminate(c, spaced, nullptr, sc.points, sc.points, true, rounds, kept, ss);
+            st.host_fetches += ss.host_reads;
+            if (rc) return 1;
+            HIP_TRY(inner.end());
+            for (size_t s = 0; s < spaced.size(); s++) {
+                auto &r = sc.rows[spaced[s].job];
+                r.kept = kept[s]; r.rounds = rounds[s];
+                if (kept[s] < r.count)
+                    return fail("mpt_compose: scatter %d: %lld of its %lld candidates are kept at the minimum distance %g, fewer than its count %d", spaced[s].job,
+                                (long long)kept[s], (long long)r.candidates, r.min_distance, r.count);
+            }
+        }
         HIP_TRY(span.end());
     }
     {
@@ -296,5 +424,76 @@ extern "C" int mpt_scatter_get(mpt_ctx *c, int scatter_id, mpt_scatter_point *po
         HIP_TRY(hipMemcpy2D(worlds, 16 * sizeof(double), (const char *)(c->compose.bufs.objs + r.first_obj) + offsetof(MptComposeObj, world), sizeof(MptComposeObj),
                             16 * sizeof(double), (size_t)r.count, hipMemcpyDeviceToHost));
     if (q) HIP_TRY(hipMemcpy(q, sc.q + r.face_at, (size_t)r.faces * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int mpt_scatter_spacing_stats(mpt_ctx *c, mpt_scatter_spacing_info *out) {
+    if (!c || !out) return fail("null argument");
+    *out = c->scatter.space.stats;
+    return 0;
+}
+
+extern "C" int mpt_scatter_spacing_kernel_time(mpt_ctx *c, double *ms, int *launches) {
+    return use_ro(c) || timer_readout(c, c->scatter.space_timer, ms, nullptr, launches);
+}
+
+extern "C" int mpt_scatter_get_spacing(mpt_ctx *c, int scatter_id, int64_t *candidates, int64_t *kept, int32_t *rounds, uint8_t *kept_flags, int64_t *index) {
+    if (use_ro(c)) return 1;
+    const char *who = "mpt_scatter_get_spacing";
+    if (check_scatter(c, scatter_id, who)) return 1;
+    const auto &sc = c->scatter;
+    const auto &r = sc.rows[scatter_id];
+    if (!(r.min_distance > 0.0)) return fail("%s: scatter %d is a plain scatter: it has no minimum distance", who, scatter_id);
+    if (!r.placed || r.select) return fail("%s: scatter %d has not been placed yet: call mpt_compose", who, scatter_id);
+    if (candidates) *candidates = r.candidates;
+    if (kept) *kept = r.kept;
+    if (rounds) *rounds = r.rounds;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<int32_t> tmp((size_t)std::max<int64_t>(r.candidates, r.count));
+    if (kept_flags) {
+        HIP_TRY(hipMemcpy(tmp.data(), sc.space.state + r.state_at, (size_t)r.candidates * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int64_t j = 0; j < r.candidates; j++) kept_flags[j] = tmp[(size_t)j] == MPT_SPACE_KEPT;
+    }
+    if (index) {
+        HIP_TRY(hipMemcpy(tmp.data(), sc.space.index + r.point_at, (size_t)r.count * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int i = 0; i < r.count; i++) index[i] = tmp[(size_t)i];
+    }
+    return 0;
+}
+
+static int space_rule_args(const double *points, int64_t n, double r) { return n < 0 || (n > 0 && !points) || !(r >= 0.0); }
+
+extern "C" int mpt_scatter_space_rule(const double *points, int64_t n, double r, uint8_t *kept, int32_t *rounds) {
+    if (space_rule_args(points, n, r)) return 1;
+    std::vector<uint8_t> flags((size_t)n);
+    std::vector<int32_t> t((size_t)n);
+    const int32_t took = mpt_scatter_space_of(points, n, r, flags.data(), t.data());
+    if (kept && n > 0) memcpy(kept, flags.data(), (size_t)n);
+    if (rounds) *rounds = took;
+    return 0;
+}
+
+extern "C" int mpt_scatter_space_points(mpt_ctx *c, const double *points, int64_t n, double r, uint8_t *kept, int32_t *rounds) {
+    if (use_ro(c)) return 1;
+    const char *who = "mpt_scatter_space_points";
+    if (space_rule_args(points, n, r) || n > MPT_SPACE_MAX_CANDIDATES)
+        return fail("%s: bad arguments: %lld points (%s; at most 2^24) at the distance %g", who, (long long)n, points ? "given" : "null", r);
+    if (rounds) *rounds = 0;
+    if (n == 0) return 0;
+    auto &sc = c->scatter;
+    std::vector<MptSpaceJob> sj(1);
+    sj[0].job = -1; sj[0].m = (int32_t)n; sj[0].r = r; sj[0].state_at = (int64_t)sc.space.states_used;   // behind the states that scatters own
+    std::vector<int32_t> took;
+    std::vector<int64_t> none;
+    mpt_scatter_spacing_info st{};
+    const int launched = sc.launches;
+    const int rc = space_eliminate(c, sj, points, nullptr, nullptr, false, took, none, st);
+    sc.launches = launched;                                               // (mpt_scatter_kernel_time counts the composes' kernels)
+    if (rc) return 1;
+    if (rounds) *rounds = took[0];
+    if (!kept) return 0;
+    std::vector<int32_t> state((size_t)n);
+    HIP_TRY(hipMemcpy(state.data(), sc.space.state + sj[0].state_at, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int64_t j = 0; j < n; j++) kept[j] = state[(size_t)j] == MPT_SPACE_KEPT;
     return 0;
 }

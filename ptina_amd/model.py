@@ -14,7 +14,7 @@ import ctypes as C
 from .common import *                 # noqa: F401,F403
 from .common import Singleton, register, ctx, np
 from ._lib import fptr, iptr, ComposeInfo, DeformInfo, SubdivInfo, DisplaceInfo, DEFORM_MAX_JOINTS, DEFORM_MAX_TARGETS, SUBDIV_MAX_LEVELS
-from ._lib import SUBDIV_SCHEMES, DISPLACE_MODES, DISPLACE_CHANNELS, ScatterInfo, SCATTER_POINT_DTYPE, scatter_params
+from ._lib import SUBDIV_SCHEMES, DISPLACE_MODES, DISPLACE_CHANNELS, ScatterInfo, ScatterSpacingInfo, SCATTER_POINT_DTYPE, scatter_params, scatter_spacing
 
 
 @register
@@ -352,14 +352,17 @@ class ModelPool(metaclass=Singleton):
         return int(scatter)
 
     def add_scatter(self, surface, mesh, count, seed=0, mtlid=None, scale=(1, 1), align='normal', up=(0, 1, 0), random_yaw=True, density=None,
-                    channel='mean'):
+                    channel='mean', min_distance=0.0, candidates=None):
         '''`count` instances of mesh `mesh` (it may be subdivided and displaced, not deformable) scattered over the faces of object
         `surface` in proportion to their world area -- times, with density=an image of ImagePool, its `channel` at the faces' mean
         uv, clamped to [0, 1]; a face below 2^-24 of the largest weight gets none.  Each instance gets a scale drawn from
         scale=(min, max), a random yaw about its up axis (its local +Y) unless random_yaw=False, and stands along the face's
         geometric normal (align='normal') or along `up` (align='up').  The instances are objects with contiguous ids and material
         mtlid; they remember their face and their point on it, so that compose() after the surface was posed, displaced or moved
-        again places them again on the device.  Returns (scatter id, range of object ids)'''
+        again places them again on the device.  min_distance > 0 keeps the instances at least that far apart, through space, where
+        they are born (Blender's "Poisson Disk"): `candidates` points (None: 4 * count) are drawn as above, in their order one is kept
+        iff no kept one before it lies closer, and the first `count` kept are the instances; compose() refuses when fewer are kept.
+        Returns (scatter id, range of object ids)'''
         surface = self._object(surface)
         if not 0 <= int(mesh) < len(self._mesh_faces):
             raise ValueError('unknown mesh %r (%d meshes)' % (mesh, len(self._mesh_faces)))
@@ -372,26 +375,35 @@ class ModelPool(metaclass=Singleton):
         if total >= self.size:
             raise ValueError('too many faces: %d with %d instances, room for fewer than %d' % (total, count, self.size))
         p = scatter_params(scale, align, up, random_yaw, density, channel)
+        r, m = scatter_spacing(count, min_distance, candidates)
         sid, first = C.c_int(-1), C.c_int(-1)
         ctx().call('mpt_scatter_add', surface, mesh, count, int(seed) & (2 ** 64 - 1), -1 if mtlid is None else int(mtlid), C.byref(p), C.byref(sid),
                    C.byref(first))
         assert first.value == len(self._obj_mesh) and sid.value == len(self._scatters)
+        if r > 0:
+            ctx().call('mpt_scatter_set_spacing', sid.value, r, m)
         self._obj_mesh.extend([mesh] * count)
         self._scatters.append(dict(surface=surface, mesh=mesh, objects=range(first.value, first.value + count), seed=int(seed),
-                                   params=dict(scale=scale, align=align, up=up, random_yaw=random_yaw, density=density, channel=channel)))
+                                   params=dict(scale=scale, align=align, up=up, random_yaw=random_yaw, density=density, channel=channel),
+                                   spacing=dict(min_distance=min_distance, candidates=candidates)))
         return sid.value, self._scatters[-1]['objects']
 
     def set_scatter(self, scatter, **params):
-        '''new parameters (add_scatter's keywords scale ... channel; the others keep their values) for a scatter; the next compose()
-        selects and places its instances again'''
+        '''new parameters (add_scatter's keywords scale ... channel, min_distance and candidates; the others keep their values) for a
+        scatter; the next compose() selects and places its instances again'''
         s = self._scatters[self._scatter(scatter)]
-        unknown = set(params) - set(s['params'])
+        unknown = set(params) - set(s['params']) - set(s['spacing'])
         if unknown:
             raise ValueError('unknown scatter parameters: %s' % ', '.join(sorted(unknown)))
-        merged = dict(s['params'], **params)
+        merged = dict(s['params'], **{k: v for k, v in params.items() if k in s['params']})
+        spacing = dict(s['spacing'], **{k: v for k, v in params.items() if k in s['spacing']})
         p = scatter_params(**merged)
-        ctx().call('mpt_scatter_set_params', int(scatter), C.byref(p))
-        s['params'] = merged
+        r, m = scatter_spacing(len(s['objects']), **spacing)
+        if not all(k in s['spacing'] for k in params) or not params:
+            ctx().call('mpt_scatter_set_params', int(scatter), C.byref(p))
+        if any(k in s['spacing'] for k in params):
+            ctx().call('mpt_scatter_set_spacing', int(scatter), r, m)
+        s['params'], s['spacing'] = merged, spacing
 
     def rescatter(self, scatter, seed=None):
         '''scatter again with a new seed (None: the old seed + 1); the next compose() selects and places the instances again.  The
@@ -424,6 +436,25 @@ class ModelPool(metaclass=Singleton):
         selection / placement launches and the host's reads of the last compose()'''
         info = ScatterInfo()
         ctx().call('mpt_scatter_stats', C.byref(info))
+        return info
+
+    def scatter_spacing(self, scatter):
+        '''(candidates, kept, rounds, kept_flags [candidates] bool, index [count] int64) of a spaced scatter's last elimination:
+        the candidates drawn, how many of them were kept, the rounds the device took, which were kept, and the candidate that became
+        each instance'''
+        s = self._scatters[self._scatter(scatter)]
+        m, kept, rounds = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        ctx().call('mpt_scatter_get_spacing', int(scatter), C.byref(m), C.byref(kept), C.byref(rounds), None, None)
+        flags, index = np.zeros(m.value, np.uint8), np.zeros(len(s['objects']), np.int64)
+        ctx().call('mpt_scatter_get_spacing', int(scatter), None, None, None, flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+                   index.ctypes.data_as(C.POINTER(C.c_int64)))
+        return m.value, kept.value, rounds.value, flags.astype(bool), index
+
+    def scatter_spacing_stats(self):
+        '''_lib.ScatterSpacingInfo of the last compose(): the spaced scatters that selected, their candidates and kept candidates,
+        the most rounds one took, the grid / round / compaction kernels launched and the host's waits; all zero without one'''
+        info = ScatterSpacingInfo()
+        ctx().call('mpt_scatter_spacing_stats', C.byref(info))
         return info
 
     def subdivided_to_numpy(self, obj):

@@ -32,7 +32,7 @@ _PASS_THROUGH = {
     'set_mesh_displacement': ('ModelPool', 'add_displacement', ('mesh', 'image', ('strength', 1.0), ('midlevel', 0.5), ('mode', 'normal'), ('channel', 'mean'))),
     'set_mesh_displacement_params': ('ModelPool', 'set_displacement', ('mesh', 'strength', ('midlevel', None))),
     'add_scatter': ('ModelPool', 'add_scatter', ('surface', 'mesh', 'count', ('seed', 0), ('mtlid', None), ('scale', (1, 1)), ('align', 'normal'), ('up', (0, 1, 0)),
-                                                 ('random_yaw', True), ('density', None), ('channel', 'mean'))),
+                                                 ('random_yaw', True), ('density', None), ('channel', 'mean'), ('min_distance', 0.0), ('candidates', None))),
     'rescatter': ('ModelPool', 'rescatter', ('scatter', ('seed', None))),
     'load_images': ('ImagePool', 'load', ('images',)),
     'load_materials': ('MaterialPool', 'load', ('materials',)),

@@ -13,7 +13,16 @@ Per scene one JSON line with the median and the least wall time (ms, through mpt
 and beside them the HIP-event times of the scatter's launches (selection = weights, scan and records; placement) and of the
 composition kernel in a and b.  The lines are also written to --out as a JSON list.
 
-    python tools/scatter_bench.py [--scenes terrain floor] [--repeat 10] [--repeat-host 3] [--out FILE]
+--min-distance R (or `auto`: the distance at which about half of the candidates are rejected, found by bisection through the test
+door mpt_scatter_space_points) adds, per scene, a line for the SPACED scatter of the same count from M = 4 x count candidates
+(csrc/scatter_space.hip) behind the plain scatter's line, which stands beside it as what spacing costs over:
+  a  the first compose(): selection, elimination (grid, rounds, compaction: the rounds one scatter took and those launched, the
+     host's waits) and placement by their HIP events, the elimination's being part of the selection's
+  b  the edit + compose(): no elimination launch (asserted), to be compared with the plain scatter's b
+  c  the host comparator: the M candidates' records and the surface fetched, their positions and the greedy elimination of
+     tests/scatter_space_ref.py in numpy on this host's CPU, the placement in numpy and `count` set_world calls, compose()
+
+    python tools/scatter_bench.py [--scenes terrain floor] [--repeat 10] [--repeat-host 3] [--min-distance R|auto] [--out FILE]
 '''
 import argparse
 import json
@@ -30,6 +39,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import deform_ref                                                             # noqa: E402
 import displace_ref                                                           # noqa: E402
 import scatter_ref                                                            # noqa: E402
+import scatter_space_ref                                                      # noqa: E402
 import subdiv_ref                                                             # noqa: E402
 
 SCALE = (0.01, 0.03)
@@ -84,9 +94,66 @@ def scene(pool, name):
     return floor, world, (lambda turn: pool.set_world(floor, world(turn))), v[:6]
 
 
-def bench(name, count, repeat, repeat_host):
+def candidates_of(name, m):
+    '''the positions [m,3] of the m candidates of the scene's scatter, as the host can get at them: a plain scatter of m small
+    instances, its records and the surface fetched, the placement's point in numpy.  Also (pool, scatter, surface records, world)'''
+    pool, c = fresh()
+    surf, world, edit, rec = scene(pool, name)
+    sid, _ = pool.add_scatter(surf, pool.add_mesh(*deform_ref.split(subdiv_ref.fixture('tetrahedron'))), m, seed=1, mtlid=1, scale=SCALE)
+    pool.compose()
+
+    def fetch():
+        surface = pool.subdivided_to_numpy(surf) if rec is None else rec
+        corners = scatter_ref.world_corners(surface, world(0))
+        points = pool.scatter_to_numpy(sid)[0]
+        return scatter_space_ref.positions(corners, points), corners, points
+    return pool, c, fetch
+
+
+def half_distance(name, m):
+    '''the distance at which about half of the m candidates are rejected: bisection through the test door'''
+    from ptina_amd import _lib
+    pool, c, fetch = candidates_of(name, m)
+    pos = fetch()[0]
+    lo, hi = 0.0, float(np.ptp(pos, axis=0).max())
+    for _ in range(24):
+        r = 0.5 * (lo + hi)
+        rejected = 1.0 - _lib.scatter_space_points(c, pos, r)[0].mean()
+        if abs(rejected - 0.5) < 0.01:
+            break
+        lo, hi = (r, hi) if rejected < 0.5 else (lo, r)
+    return r, rejected
+
+
+def host_comparator(name, count, m, r, repeat_host):
+    '''c of a spaced scatter: wall ms (median, min) of the elimination and placement on the host'''
+    pool, c, fetch = candidates_of(name, m)
+    tuft = subdiv_ref.fixture_subdivided('tetrahedron', 2)
+    mesh = pool.add_mesh(*deform_ref.split(tuft))
+    hand = [pool.add_object(mesh, np.eye(4), 1) for _ in range(count)]
+    pool.compose()
+    kept_total = []
+
+    def road():
+        pos, corners, points = fetch()
+        kept = scatter_space_ref.greedy_of_points(pos, r)
+        kept_total.append(int(kept.sum()))
+        chosen = points[np.flatnonzero(kept)[:count]]
+        for obj, w in zip(hand, scatter_ref.place(corners, chosen)):
+            pool.set_world(obj, w)
+        pool.compose()
+    ms = []
+    for _ in range(repeat_host):                                           # (seconds a call on the terrain: no warm-up calls)
+        t0 = time.perf_counter()
+        road()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return [round(median(ms), 4), round(min(ms), 4)], kept_total[-1]
+
+
+def bench(name, count, repeat, repeat_host, spacing=None):
     tuft = subdiv_ref.fixture_subdivided('tetrahedron', 2)                     # 64 faces
-    out = {'metric': 'scatter_ms', 'scene': name, 'instances': count, 'tuft_faces': tuft.shape[0] // 3, 'repeat': repeat,
+    spaced = {} if spacing is None else dict(min_distance=spacing[0], candidates=spacing[1])
+    out = {'metric': 'scatter_ms' if spacing is None else 'spaced_scatter_ms', 'scene': name, 'instances': count, 'tuft_faces': tuft.shape[0] // 3, 'repeat': repeat,
            'host': platform.processor() or platform.machine(), 'columns': ['wall median', 'wall min']}
     # ---- a: the first compose with the scatter (a fresh context each time: the pool, the arenas and the model are allocated in it)
     first, kernels = [], []
@@ -94,17 +161,25 @@ def bench(name, count, repeat, repeat_host):
         pool, c = fresh()
         surf, world, edit, rec = scene(pool, name)
         pool.compose()
-        sid, objs = pool.add_scatter(surf, pool.add_mesh(*deform_ref.split(tuft)), count, seed=1, mtlid=1, scale=SCALE)
+        sid, objs = pool.add_scatter(surf, pool.add_mesh(*deform_ref.split(tuft)), count, seed=1, mtlid=1, scale=SCALE, **spaced)
         c.timer('mpt_scatter_kernel_time', 2)
         c.timer('mpt_compose_kernel_time')
+        c.timer('mpt_scatter_spacing_kernel_time')
         t0 = time.perf_counter()
         pool.compose()
         first.append((time.perf_counter() - t0) * 1e3)
-        kernels.append(c.timer('mpt_scatter_kernel_time', 2)[:2] + c.timer('mpt_compose_kernel_time')[:1])
+        kernels.append(c.timer('mpt_scatter_kernel_time', 2)[:2] + c.timer('mpt_compose_kernel_time')[:1] + c.timer('mpt_scatter_spacing_kernel_time')[:1])
     out['faces'] = pool.nfaces
     out['surface_faces'] = pool._object_faces(pool._obj_mesh[surf])
     out['a first compose with the scatter'] = [round(median(first), 4), round(min(first), 4)]
     out['a kernels (ms: selection, placement, composition)'] = [round(median([k[s] for k in kernels]), 4) for s in range(3)]
+    if spacing is not None:
+        sp, st = pool.scatter_spacing_stats(), pool.scatter_stats()
+        out['min_distance'], out['candidates'], out['kept'] = spacing[0], spacing[1], sp.kept
+        out['a elimination (ms by HIP events, inside the selection: grid, rounds, waits, compaction)'] = round(median([k[3] for k in kernels]), 4)
+        out['a elimination: rounds taken, round kernels launched, grid kernels, compaction kernels, host waits'] = [
+            sp.rounds, sp.round_launches, sp.grid_launches, sp.compact_launches, sp.host_reads]
+        out['a host_fetches of the scatter step'] = st.host_fetches
     # ---- b: the edit + compose, in the last context
     turn = [0]
 
@@ -123,9 +198,19 @@ def bench(name, count, repeat, repeat_host):
         ks.append(c.timer('mpt_scatter_kernel_time', 2)[:2] + c.timer('mpt_compose_kernel_time')[:1])
     s, cs = pool.scatter_stats(), pool.compose_stats()
     assert (s.select_launches, s.place_launches, s.placed_instances) == (0, 1, count) and cs.dirty_objects == count + 1
+    sp = pool.scatter_spacing_stats()
+    assert (sp.scatters, sp.grid_launches, sp.round_launches, sp.compact_launches, sp.host_reads) == (0, 0, 0, 0, 0)   # no elimination in b
     out['b edit + compose'] = [round(median(ms), 4), round(min(ms), 4)]
     out['b kernels (ms: selection, placement, composition)'] = [round(median([k[s] for k in ks]), 4) for s in range(3)]
     points, worlds, _ = pool.scatter_to_numpy(sid)
+    if spacing is not None:
+        key = 'c records and surface fetched + numpy positions, greedy elimination and placement + set_world per instance + compose (host CPU: %s)' % out['host']
+        out[key], kept = host_comparator(name, count, spacing[1], spacing[0], repeat_host)
+        assert kept == out['kept'], (kept, out['kept'])                    # the host's pass keeps what the device kept
+        print(json.dumps(out), flush=True)
+        from ptina_amd.common import reset_all
+        reset_all()
+        return out
     # ---- c: the same on the interface without scatters
     pool, c = fresh()
     surf, world, edit, rec = scene(pool, name)
@@ -157,9 +242,21 @@ def main():
     ap.add_argument('--scenes', nargs='*', default=['terrain', 'floor'])
     ap.add_argument('--repeat', type=int, default=10)
     ap.add_argument('--repeat-host', type=int, default=3)
+    ap.add_argument('--min-distance', default=None, help="a distance, or 'auto': the one that rejects about half of 4 x count candidates")
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
-    lines = [bench(name, 20000 if name == 'terrain' else 2000, args.repeat, args.repeat_host) for name in args.scenes]
+    lines = []
+    for name in args.scenes:
+        count = 20000 if name == 'terrain' else 2000
+        lines.append(bench(name, count, args.repeat, args.repeat_host))
+        if args.min_distance is None:
+            continue
+        if args.min_distance == 'auto':
+            r, rejected = half_distance(name, 4 * count)
+            print('%s: %.1f %% of %d candidates are rejected at the distance %.6g' % (name, 100 * rejected, 4 * count, r), flush=True)
+        else:
+            r = float(args.min_distance)
+        lines.append(bench(name, count, args.repeat, args.repeat_host, (r, 4 * count)))
     if args.out:
         with open(args.out, 'w') as f:
             json.dump(lines, f, indent=1)

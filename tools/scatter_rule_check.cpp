@@ -9,6 +9,10 @@
 // axis in both directions -- N = (0, 0, -1) is the construction's special case -- and for random unit vectors; the yaw's fallback
 // (an instance whose eight pairs all miss the disc, found by search, and the pairs' own admission rule); densities over images
 // exactly nx x ny texels large with uvs that wrap on both sides; weights that are not finite; shares at and above the largest.
+// The elimination of a spaced scatter (`scatter_rule_check space` runs it alone): the greedy pass and its synchronous round count
+// against a plain simulation of the rounds on a chain, coincident points, a pair exactly r apart and an f64 closer, NaN and infinite
+// coordinates and uniform points; and the device's grid -- edge, cell, bucket -- on boxes from a point to 2^30 r and beyond the
+// finite numbers: cells are monotone and inside their counts, and no conflicting pair lies more than a cell apart.
 
 #include "../ptina_amd/csrc/scatter_rule.h"
 #include <cstdio>
@@ -65,7 +69,122 @@ static void check_frame(const double N[3]) {
     delete[] T0; delete[] B0;
 }
 
-int main() {
+// kept flags and rounds by simulating the synchronous rounds over all pairs
+static int32_t rounds_by_simulation(const std::vector<double> &pos, double r, std::vector<uint8_t> &kept) {
+    const int64_t n = (int64_t)(pos.size() / 3);
+    std::vector<int> state((size_t)n, MPT_SPACE_UNDECIDED), next;
+    int32_t rounds = 0;
+    for (bool open = n > 0; open; rounds++) {
+        next = state;
+        open = false;
+        for (int64_t j = 0; j < n; j++) {
+            if (state[(size_t)j] != MPT_SPACE_UNDECIDED) continue;
+            bool any_kept = false, any_undecided = false;
+            for (int64_t k = 0; k < j; k++) {
+                if (!mpt_scatter_conflict(&pos[(size_t)j * 3], &pos[(size_t)k * 3], r * r)) continue;
+                any_kept |= state[(size_t)k] == MPT_SPACE_KEPT;
+                any_undecided |= state[(size_t)k] == MPT_SPACE_UNDECIDED;
+            }
+            next[(size_t)j] = mpt_scatter_space_decide(any_kept, any_undecided);
+            open |= next[(size_t)j] == MPT_SPACE_UNDECIDED;
+        }
+        state = next;
+    }
+    kept.resize((size_t)n);
+    for (int64_t j = 0; j < n; j++) kept[(size_t)j] = state[(size_t)j] == MPT_SPACE_KEPT;
+    return rounds;
+}
+
+static int32_t check_space(const std::vector<double> &pos, double r, std::vector<uint8_t> *out = nullptr) {
+    const int64_t n = (int64_t)(pos.size() / 3);
+    std::vector<uint8_t> kept((size_t)n), want;
+    std::vector<int32_t> t((size_t)n);
+    const int32_t rounds = mpt_scatter_space_of(pos.data(), n, r, kept.data(), t.data());
+    CHECK(rounds == rounds_by_simulation(pos, r, want));
+    CHECK(kept == want);
+    // the grid: every point of the box in a cell inside the counts, and conflicting pairs at most a cell apart
+    double lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    auto finite = [&](int64_t j) { return std::isfinite(pos[(size_t)j * 3]) && std::isfinite(pos[(size_t)j * 3 + 1]) && std::isfinite(pos[(size_t)j * 3 + 2]); };
+    for (int64_t j = 0; j < n; j++)
+        for (int k = 0; k < 3 && finite(j); k++) { lo[k] = std::fmin(lo[k], pos[(size_t)j * 3 + k]); hi[k] = std::fmax(hi[k], pos[(size_t)j * 3 + k]); }
+    if (lo[0] <= hi[0]) {
+        const double h = mpt_space_edge(r, lo, hi);
+        CHECK(h > r || !std::isfinite(r));
+        std::vector<int32_t> cell((size_t)n * 3, 0);
+        for (int64_t j = 0; j < n; j++)
+            for (int k = 0; k < 3 && finite(j); k++) {
+                const int32_t c = cell[(size_t)j * 3 + k] = mpt_space_cell(pos[(size_t)j * 3 + k], lo[k], h);
+                CHECK(c >= 0 && c <= mpt_space_cell(hi[k], lo[k], h) && c <= (1 << 20) + 1 && mpt_space_cell(lo[k], lo[k], h) == 0);
+            }
+        for (int64_t j = 0; j < n; j++)
+            for (int64_t k = 0; k < j; k++) {
+                for (int a = 0; a < 3 && finite(j) && finite(k); a++)      // monotone
+                    CHECK((pos[(size_t)j * 3 + a] <= pos[(size_t)k * 3 + a]) == (cell[(size_t)j * 3 + a] <= cell[(size_t)k * 3 + a]) ||
+                          cell[(size_t)j * 3 + a] == cell[(size_t)k * 3 + a]);
+                if (!mpt_scatter_conflict(&pos[(size_t)j * 3], &pos[(size_t)k * 3], r * r)) continue;
+                for (int a = 0; a < 3; a++) CHECK(std::abs(cell[(size_t)j * 3 + a] - cell[(size_t)k * 3 + a]) <= 1);
+            }
+        CHECK(mpt_space_bucket(1 << 20, (1 << 20) + 1, 0, 1023) < 1024 && mpt_space_bucket(0, 0, 0, 0) == 0);
+    }
+    if (out) *out = kept;
+    return rounds;
+}
+
+static int space_checks() {
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<uint8_t> kept;
+    {   // a chain 0.6 r apart in index order, and in reverse: every second one, and as many rounds as points
+        std::vector<double> chain(40 * 3, 0.0), back(40 * 3, 0.0);
+        for (int j = 0; j < 40; j++) { chain[(size_t)j * 3] = 0.6 * j; back[(size_t)j * 3] = 0.6 * (39 - j); }
+        CHECK(check_space(chain, 1.0, &kept) == 40);
+        for (int j = 0; j < 40; j++) CHECK(kept[(size_t)j] == (j % 2 == 0));
+        CHECK(check_space(back, 1.0, &kept) == 40);
+        for (int j = 0; j < 40; j++) CHECK(kept[(size_t)j] == (j % 2 == 0));
+    }
+    {   // coincident points: the first alone; a single point; no point
+        std::vector<double> same(64 * 3, 0.25);
+        CHECK(check_space(same, 0.5, &kept) == 2 && kept[0] == 1);
+        for (int j = 1; j < 64; j++) CHECK(kept[(size_t)j] == 0);
+        CHECK(check_space({ 1.0, 2.0, 3.0 }, 0.5, &kept) == 1 && kept[0] == 1);
+        CHECK(check_space({}, 0.5) == 0);
+        CHECK(check_space(same, 0.0, &kept) == 1 && kept[63] == 1);          // r = 0: nothing conflicts
+    }
+    {   // exactly r apart: (3, 4, 12) / 16 at r = 13 / 16, every operation exact -- allowed; an f64 closer -- a conflict
+        std::vector<double> pair = { 0.25, -0.5, 1.0, 0.25 + 3.0 / 16, -0.5 + 4.0 / 16, 1.0 + 12.0 / 16 };
+        CHECK(check_space(pair, 13.0 / 16, &kept) == 1 && kept[1] == 1);
+        for (int k = 0; k < 8; k++) pair[3] = std::nextafter(pair[3], -inf);
+        CHECK(check_space(pair, 13.0 / 16, &kept) == 2 && kept[1] == 0);
+    }
+    {   // coordinates that are not finite conflict with nothing; an r whose square overflows conflicts with every finite distance
+        std::vector<double> pts = { 0, 0, 0, nan, 0, 0, 0.1, 0, 0, inf, 0, 0, inf, 0, 0, 0, -inf, 0 };
+        CHECK(check_space(pts, 0.5, &kept) == 2);
+        CHECK(kept[0] == 1 && kept[1] == 1 && kept[2] == 0 && kept[3] == 1 && kept[4] == 1 && kept[5] == 1);
+        CHECK(check_space({ 0, 0, 0, 1e150, 0, 0, -1e300, 1e300, 0 }, 1e200, &kept) == 2 && kept[1] == 0 && kept[2] == 1);   // (d2 of the third overflows too)
+        CHECK(check_space({ -1e308, 0, 0, 1e308, 0, 0, 1e308, 1.0, 0 }, 2.0, &kept) == 2 && kept[2] == 0);                    // an extent beyond the finite numbers
+    }
+    {   // uniform points in a unit cube, at distances that reject from a few to nearly all; extents of 2^30 r and of a subnormal r
+        uint64_t s = 7;
+        for (int n : { 2, 63, 257, 600 })
+            for (double r : { 0.02, 0.09, 0.3, 2.0 }) {
+                std::vector<double> pts((size_t)n * 3);
+                for (double &x : pts) { s = mpt_scatter_mix(s); x = mpt_scatter_unit(s); }
+                check_space(pts, r);
+                for (int k = 0; k < 3; k++) pts[(size_t)(n - 1) * 3 + k] = 0x1p30 * r;
+                pts[0] = pts[(size_t)(n - 1) * 3] - 0.5 * r; pts[1] = pts[2] = 0x1p30 * r;
+                check_space(pts, r);
+                check_space(pts, 0x1p-1070);
+            }
+    }
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    space_checks();
+    if (argc > 1 && !std::strcmp(argv[1], "space")) {
+        if (failures) { std::fprintf(stderr, "scatter_rule_check space: %d checks failed\n", failures); return 1; }
+        std::printf("scatter_rule_check space: ok\n");
+        return 0;
+    }
     // ---- draws
     CHECK(mpt_scatter_mix(0) == 0xE220A8397B1DCDAFull);
     CHECK(mpt_scatter_unit(0) == 0x1p-54 && mpt_scatter_unit(~0ull) == 1.0 && mpt_scatter_unit(1ull << 62) == 0.25 + 0x1p-54);
