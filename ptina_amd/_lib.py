@@ -513,35 +513,73 @@ def subdiv_plan(items, dirty=None):
     return _run_plan('mpt_subdiv_plan', items, dirty, 'jobs', 'item')
 
 
+SUBDIV_VARIANTS = ('plain', 'blend_crease', 'blend_corner', 'fixed')      # csrc/mpt_types.h MPT_SUBDIV_PLAIN .. _FIXED (on an edge, 1 is MPT_SUBDIV_BLEND_EDGE)
+SUBDIV_CC, SUBDIV_MAX_CORNERS = 4, 64                                    # csrc/mpt_types.h MPT_SUBDIV_CC (a bit of the variant), MPT_SUBDIV_MAX_CORNERS
+SUBDIV_SCHEMES = ('loop', 'catmull-clark')
+
+
+def _subdiv_records(rec):
+    rec = np.ascontiguousarray(rec, np.float32)
+    if rec.ndim != 2 or rec.shape[1] != 8 or rec.shape[0] % 3:
+        raise ValueError('records must be [3k,8], got %s' % (rec.shape,))
+    return rec
+
+
+def _subdiv_call(entry, args, levels, noffsets):
+    '''a topology entry point (args: what it takes in front of counts), called twice: for the number of words, then for the words.
+    (verdict, the words of the refusal), else (0, (counts [levels+1,3], offsets [noffsets], the block))'''
+    call = getattr(load_library(), entry)
+    why = C.create_string_buffer(240)
+    counts, off, need = np.zeros((max(levels, 0) + 1, 3), np.int64), np.zeros(noffsets, np.int32), C.c_int64(0)
+    cp = counts.ctypes.data_as(C.POINTER(C.c_int64))
+    rc = call(*args, cp, iptr(off), None, 0, C.byref(need), why, len(why))
+    if rc:
+        return rc, why.value.decode()
+    w = np.zeros(max(int(need.value), 1), np.int32)
+    rc = call(*args, cp, iptr(off), iptr(w), int(need.value), C.byref(need), why, len(why))
+    assert rc == 0
+    return 0, (counts, off, w[:int(need.value)])
+
+
+def _subdiv_decode(counts, off, w, levels):
+    '''the tables of a block of words w (csrc/subdiv_rule.h documents it): a rule is (kind, variant, [ids], parameter)'''
+    def rule(h, r):
+        kind, variant, n = h & 3, h >> 28 & 7, h >> 2 & (1 << 26) - 1
+        cc, blend = variant & SUBDIV_CC, variant & 3
+        nids = n
+        if kind == 0:                                                   # an interior vertex: n face point ids, p q
+            nids += (n if cc else 0) + (2 if blend == 1 else 0)
+        blends = (kind == 0 and blend in (1, 2)) or (kind == 2 and blend == 1)
+        return kind, variant, w[r:r + nids].tolist(), float(w[r + nids:r + nids + 2].view(np.float64)[0]) if blends else None
+
+    def rules(at, n):
+        return [rule(int(h), int(r)) for h, r in zip(w[at:at + 2 * n:2], w[at + 1:at + 2 * n:2])]
+    t = dict(counts=counts, first_corner=w[:int(counts[0, 0])].copy(), rules={l: rules(int(off[l]), int(counts[l, 0])) for l in range(1, levels + 1)},
+             rings=[(kind, ids) for kind, _, ids, _ in rules(int(off[6]), int(counts[levels, 0]))], faces=w[int(off[7]):int(off[8])].reshape(-1, 3).copy(),
+             offsets=off.copy())
+    if len(off) > 9:                                                    # the last level's records
+        nrec = int(off[10])
+        t['records'] = [(v, kind, ids) for v, (kind, ids) in enumerate(t['rings'])]
+        if off[9]:
+            vert = w[int(off[9]) + 2 * nrec:int(off[9]) + 3 * nrec].tolist()
+            t['records'] = [(v, kind, ids) for v, (kind, _, ids, _) in zip(vert, rules(int(off[9]), nrec))]
+    if len(off) > 11:                                                   # the table of level-1 quads
+        nq1 = int(counts[1, 2])
+        t['quads1'] = w[int(off[11]):int(off[11]) + 2 * nq1].reshape(nq1, 2).copy()
+    return t
+
+
 def subdiv_topology(rec, levels):
     '''mpt_subdiv_topology (no context, no GPU) of the records rec [3k,8] f32: (verdict, words, tables).  verdict 0 accepts, and
     tables is then a dict: counts [levels+1,3] (vertices, edges, faces), first_corner [V_0], rules[l] for l = 1..levels -- a list
     of (kind, [ids of level l-1]) per vertex of level l --, rings -- the same for the last level's vertices --, faces [F_L,3]'''
-    rec = np.ascontiguousarray(rec, np.float32)
-    if rec.ndim != 2 or rec.shape[1] != 8 or rec.shape[0] % 3:
-        raise ValueError('records must be [3k,8], got %s' % (rec.shape,))
-    k, levels = rec.shape[0] // 3, int(levels)
-    lib = load_library()
-    why = C.create_string_buffer(240)
-    counts, off, need = np.zeros((max(levels, 0) + 1, 3), np.int64), np.zeros(9, np.int32), C.c_int64(0)
-    cp = counts.ctypes.data_as(C.POINTER(C.c_int64))
-    rc = lib.mpt_subdiv_topology(fptr(rec), k, levels, cp, iptr(off), None, 0, C.byref(need), why, len(why))
+    rec, levels = _subdiv_records(rec), int(levels)
+    rc, got = _subdiv_call('mpt_subdiv_topology', (fptr(rec), rec.shape[0] // 3, levels), levels, 9)
     if rc:
-        return rc, why.value.decode(), None
-    w = np.zeros(max(int(need.value), 1), np.int32)
-    rc = lib.mpt_subdiv_topology(fptr(rec), k, levels, cp, iptr(off), iptr(w), int(need.value), C.byref(need), why, len(why))
-    assert rc == 0
-
-    def rules(at, n):
-        head, ring = w[at:at + 2 * n:2], w[at + 1:at + 2 * n:2]
-        return [(int(h) & 3, w[int(r):int(r) + (int(h) >> 2)].tolist()) for h, r in zip(head, ring)]
-    nf = int(counts[levels, 2])
-    return 0, '', dict(counts=counts, first_corner=w[:int(counts[0, 0])].copy(),
-                       rules={l: rules(int(off[l]), int(counts[l, 0])) for l in range(1, levels + 1)},
-                       rings=rules(int(off[6]), int(counts[levels, 0])), faces=w[int(off[7]):int(off[7]) + 3 * nf].reshape(nf, 3).copy())
-
-
-SUBDIV_VARIANTS = ('plain', 'blend_crease', 'blend_corner', 'fixed')      # csrc/mpt_types.h MPT_SUBDIV_PLAIN .. _FIXED (on an edge, 1 is MPT_SUBDIV_BLEND_EDGE)
+        return rc, got, None
+    t = _subdiv_decode(*got, levels)
+    return 0, '', dict(counts=t['counts'], first_corner=t['first_corner'], rules={l: [(kind, ids) for kind, _, ids, _ in r] for l, r in t['rules'].items()},
+                       rings=t['rings'], faces=t['faces'])
 
 
 def subdiv_topology_creased(rec, levels, creases=None, corners=None):
@@ -550,50 +588,15 @@ def subdiv_topology_creased(rec, levels, creases=None, corners=None):
     the block of 32-bit words and the tables decoded from it.  A rule is (kind, variant, [ids], parameter) -- the
     parameter the f64 f or s of a blending variant, else None; rules[l] and rings as subdiv_topology has them; records -- per record
     of the last level (vertex, kind, [ids]) --; faces [F_L,3] of record ids; words: the whole block'''
-    rec = np.ascontiguousarray(rec, np.float32)
-    if rec.ndim != 2 or rec.shape[1] != 8 or rec.shape[0] % 3:
-        raise ValueError('records must be [3k,8], got %s' % (rec.shape,))
-    k, levels = rec.shape[0] // 3, int(levels)
+    rec, levels = _subdiv_records(rec), int(levels)
+    k = rec.shape[0] // 3
     cr = None if creases is None else np.ascontiguousarray(creases, np.float32).reshape(k, 3)
     co = None if corners is None else np.ascontiguousarray(np.asarray(corners) != 0, np.uint8).reshape(k, 3)
-    crp = None if cr is None else fptr(cr)
-    cop = None if co is None else co.ctypes.data_as(C.POINTER(C.c_uint8))
-    lib = load_library()
-    why = C.create_string_buffer(240)
-    counts, off, need = np.zeros((max(levels, 0) + 1, 3), np.int64), np.zeros(11, np.int32), C.c_int64(0)
-    cp = counts.ctypes.data_as(C.POINTER(C.c_int64))
-    rc = lib.mpt_subdiv_topology_creased(fptr(rec), k, levels, crp, cop, cp, iptr(off), None, 0, C.byref(need), why, len(why))
+    args = (fptr(rec), k, levels, None if cr is None else fptr(cr), None if co is None else co.ctypes.data_as(C.POINTER(C.c_uint8)))
+    rc, got = _subdiv_call('mpt_subdiv_topology_creased', args, levels, 11)
     if rc:
-        return rc, why.value.decode(), None
-    w = np.zeros(max(int(need.value), 1), np.int32)
-    rc = lib.mpt_subdiv_topology_creased(fptr(rec), k, levels, crp, cop, cp, iptr(off), iptr(w), int(need.value), C.byref(need), why, len(why))
-    assert rc == 0
-
-    def rule(h, r):
-        kind, variant, n = h & 3, h >> 28 & 7, h >> 2 & (1 << 26) - 1
-        extra = 2 if (kind, variant) == (0, 1) else 0
-        ids = w[r:r + n + extra].tolist()
-        blends = (kind, variant) in ((0, 1), (0, 2), (2, 1))
-        return kind, variant, ids, float(w[r + n + extra:r + n + extra + 2].view(np.float64)[0]) if blends else None
-
-    def rules(at, n):
-        return [rule(int(h), int(r)) for h, r in zip(w[at:at + 2 * n:2], w[at + 1:at + 2 * n:2])]
-    nf, vl = int(counts[levels, 2]), int(counts[levels, 0])
-    rings = [(kind, ids) for kind, _, ids, _ in rules(int(off[6]), vl)]
-    nrec = int(off[10])
-    if off[9]:
-        vert = w[int(off[9]) + 2 * nrec:int(off[9]) + 3 * nrec].tolist()
-        records = [(v, kind, ids) for v, (kind, _, ids, _) in zip(vert, rules(int(off[9]), nrec))]
-    else:
-        records = [(v, kind, ids) for v, (kind, ids) in enumerate(rings)]
-    return 0, w[:int(need.value)].copy(), dict(counts=counts, first_corner=w[:int(counts[0, 0])].copy(),
-                                               rules={l: rules(int(off[l]), int(counts[l, 0])) for l in range(1, levels + 1)},
-                                               rings=rings, records=records, faces=w[int(off[7]):int(off[7]) + 3 * nf].reshape(nf, 3).copy(),
-                                               offsets=off.copy())
-
-
-SUBDIV_CC, SUBDIV_MAX_CORNERS = 4, 64                                    # csrc/mpt_types.h MPT_SUBDIV_CC (a bit of the variant), MPT_SUBDIV_MAX_CORNERS
-SUBDIV_SCHEMES = ('loop', 'catmull-clark')
+        return rc, got, None
+    return 0, got[2].copy(), _subdiv_decode(*got, levels)
 
 
 def subdiv_topology_cc(rec, levels, polys=None, creases=None, corners=None):
@@ -604,10 +607,8 @@ def subdiv_topology_cc(rec, levels, polys=None, creases=None, corners=None):
     parameter), a Catmull-Clark rule with SUBDIV_CC in its variant: a face point's ids are its corners, an interior edge's a b and
     two face point ids, an interior vertex's its n neighbours, n face point ids and, blending between two creases, p q; quads1
     [Q_1,2] is the table of level-1 quads (first triangle of the polygon, n | i << 8); faces [2 Q_L,3] of record ids'''
-    rec = np.ascontiguousarray(rec, np.float32)
-    if rec.ndim != 2 or rec.shape[1] != 8 or rec.shape[0] % 3:
-        raise ValueError('records must be [3k,8], got %s' % (rec.shape,))
-    k, levels = rec.shape[0] // 3, int(levels)
+    rec, levels = _subdiv_records(rec), int(levels)
+    k = rec.shape[0] // 3
     po = None if polys is None else np.ascontiguousarray(polys, np.int32).reshape(-1)
     m = k if po is None else int(po.size)
     ncorners = 3 * k if po is None else int(np.clip(po, 0, None).sum())
@@ -618,41 +619,10 @@ def subdiv_topology_cc(rec, levels, polys=None, creases=None, corners=None):
             raise ValueError('%s must hold %d values, one per polygon corner, got %d' % (name, ncorners, a.size))
     args = (fptr(rec), k, levels, None if po is None else iptr(po), m, None if cr is None else fptr(cr),
             None if co is None else co.ctypes.data_as(C.POINTER(C.c_uint8)))
-    lib = load_library()
-    why = C.create_string_buffer(240)
-    counts, off, need = np.zeros((max(levels, 0) + 1, 3), np.int64), np.zeros(12, np.int32), C.c_int64(0)
-    cp = counts.ctypes.data_as(C.POINTER(C.c_int64))
-    rc = lib.mpt_subdiv_topology_cc(*args, cp, iptr(off), None, 0, C.byref(need), why, len(why))
+    rc, got = _subdiv_call('mpt_subdiv_topology_cc', args, levels, 12)
     if rc:
-        return rc, why.value.decode(), None
-    w = np.zeros(max(int(need.value), 1), np.int32)
-    rc = lib.mpt_subdiv_topology_cc(*args, cp, iptr(off), iptr(w), int(need.value), C.byref(need), why, len(why))
-    assert rc == 0
-
-    def rule(h, r):
-        kind, variant, n = h & 3, h >> 28 & 7, h >> 2 & (1 << 26) - 1
-        cc, blend = variant & SUBDIV_CC, variant & 3
-        nids = n
-        if cc and kind == 0:
-            nids = 2 * n + (2 if blend == 1 else 0)
-        blends = cc and ((kind == 0 and blend in (1, 2)) or (kind == 2 and blend == 1))
-        return kind, variant, w[r:r + nids].tolist(), float(w[r + nids:r + nids + 2].view(np.float64)[0]) if blends else None
-
-    def rules(at, n):
-        return [rule(int(h), int(r)) for h, r in zip(w[at:at + 2 * n:2], w[at + 1:at + 2 * n:2])]
-    vl, nq = int(counts[levels, 0]), int(counts[levels, 2])
-    rings = [(kind, ids) for kind, _, ids, _ in rules(int(off[6]), vl)]
-    nrec = int(off[10])
-    if off[9]:
-        vert = w[int(off[9]) + 2 * nrec:int(off[9]) + 3 * nrec].tolist()
-        records = [(v, kind, ids) for v, (kind, _, ids, _) in zip(vert, rules(int(off[9]), nrec))]
-    else:
-        records = [(v, kind, ids) for v, (kind, ids) in enumerate(rings)]
-    nq1 = int(counts[1, 2])
-    return 0, w[:int(need.value)].copy(), dict(counts=counts, first_corner=w[:int(counts[0, 0])].copy(),
-                                               rules={l: rules(int(off[l]), int(counts[l, 0])) for l in range(1, levels + 1)},
-                                               rings=rings, records=records, quads1=w[int(off[11]):int(off[11]) + 2 * nq1].reshape(nq1, 2).copy(),
-                                               faces=w[int(off[7]):int(off[7]) + 6 * nq].reshape(2 * nq, 3).copy(), offsets=off.copy())
+        return rc, got, None
+    return 0, got[2].copy(), _subdiv_decode(*got, levels)
 
 
 DISPLACE_MODES = ('normal', 'vector')                                   # include/miptina.h MPT_DISPLACE_NORMAL, _VECTOR

@@ -739,11 +739,9 @@ struct mpt_ctx {
     // object beside the device's record of it, which add_object (scene_compose.cpp) alone adds.  mpt_scene_clear clears both
     struct MptDeformMesh { int ntargets = 0, njoints = 0; size_t delta_at = 0, skin_at = 0; };   // what mesh deformation keeps for a mesh (arena offsets)
     struct MptSubdivMesh {                               // what Loop subdivision keeps for a mesh: its level and where its topology lies
-        int levels = 0; size_t topo_at = 0;
-        int64_t nv[MPT_SUBDIV_MAX_LEVELS + 1] = {};
-        int32_t rule_at[MPT_SUBDIV_MAX_LEVELS + 1] = {}, nrule_at = 0, face_at = 0;
-        int32_t srule_at = 0; int64_t nrec = 0;          // the last level's records: nrule_at and nv[levels], or a creased mesh's sectors (section 3.19.1)
-        int32_t quad_at = 0; int64_t out_faces = 0;      // a Catmull-Clark mesh's table of level-1 quads (0: Loop; section 3.19.2); the faces of the last level
+        MptSubdivHead head;                              // its block's header (subdiv_rule.h; levels 0: no subdivision), with srule_at = nrule_at where the mesh is uncreased: the records' rules are then the rings'
+        size_t topo_at = 0;                              // the block's first word in bufs.topo
+        int64_t out_faces = 0;                           // the triangles an object of the mesh has
         int job = -1;                                    // the shared copy of a mesh that is not deformable (-1: no object yet)
         // its texture displacement (mpt_mesh_set_displacement)
         bool displaced = false;

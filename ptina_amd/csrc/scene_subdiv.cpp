@@ -14,14 +14,15 @@ extern "C" int mpt_subdiv_plan(const int32_t *items, const int32_t *dirty, int n
     return mpt_run_plan_of(items, dirty, njobs, MPT_SUBDIV_CHUNK, run_job, run_block, cap, blocks);
 }
 
-// what both topology entry points hand back of an accepted mesh (offsets: 9 words, or 11 with the records' rules and number)
-static int topology_out(const MptSubdivTopo &t, int levels, int64_t *counts, int32_t *offsets, bool records, int32_t *words, int64_t cap_words, int64_t *need_words) {
+// what the topology entry points hand back of an accepted mesh (offsets: 9 words, 11 with the records' rules and number, 12 with the table of level-1 quads)
+static int topology_out(const MptSubdivTopo &t, int levels, int64_t *counts, int32_t *offsets, int noffsets, int32_t *words, int64_t cap_words, int64_t *need_words) {
     if (counts)
         for (int l = 0; l <= levels; l++) { counts[3 * l] = t.nv[l]; counts[3 * l + 1] = t.ne[l]; counts[3 * l + 2] = t.nf[l]; }
     if (offsets) {
         for (int l = 0; l <= MPT_SUBDIV_MAX_LEVELS; l++) offsets[l] = l <= levels ? t.rule_at[l] : 0;
         offsets[6] = t.nrule_at; offsets[7] = t.face_at; offsets[8] = (int32_t)t.words.size();
-        if (records) { offsets[9] = t.srule_at; offsets[10] = (int32_t)t.nrec; }
+        if (noffsets > 9) { offsets[9] = t.srule_at; offsets[10] = (int32_t)t.nrec; }
+        if (noffsets > 11) offsets[11] = t.quad_at;
     }
     if (need_words) *need_words = (int64_t)t.words.size();
     if (words && cap_words >= (int64_t)t.words.size()) memcpy(words, t.words.data(), t.words.size() * sizeof(int32_t));
@@ -33,7 +34,7 @@ extern "C" int mpt_subdiv_topology(const float *verts, int k, int levels, int64_
     MptSubdivTopo t;
     const MptSubdivVerdict v = mpt_subdiv_topology_of(verts, k, levels, t, why, why_size > 0 ? (size_t)why_size : 0);
     if (v != MPT_SUBDIV_OK) return (int)v;
-    return topology_out(t, levels, counts, offsets, false, words, cap_words, need_words);
+    return topology_out(t, levels, counts, offsets, 9, words, cap_words, need_words);
 }
 
 extern "C" int mpt_subdiv_topology_cc(const float *verts, int k, int levels, const int32_t *polys, int m, const float *crease, const uint8_t *corner,
@@ -41,8 +42,7 @@ extern "C" int mpt_subdiv_topology_cc(const float *verts, int k, int levels, con
     MptSubdivTopoCC t;
     const MptSubdivVerdict v = mpt_subdiv_topology_cc_of(verts, k, levels, polys, m, crease, corner, t, why, why_size > 0 ? (size_t)why_size : 0);
     if (v != MPT_SUBDIV_OK) return (int)v;
-    if (offsets) offsets[11] = t.quad_at;
-    return topology_out(t, levels, counts, offsets, true, words, cap_words, need_words);
+    return topology_out(t, levels, counts, offsets, 12, words, cap_words, need_words);
 }
 
 extern "C" int mpt_subdiv_topology_creased(const float *verts, int k, int levels, const float *crease, const uint8_t *corner, int64_t *counts, int32_t *offsets,
@@ -50,20 +50,20 @@ extern "C" int mpt_subdiv_topology_creased(const float *verts, int k, int levels
     MptSubdivTopo t;
     const MptSubdivVerdict v = mpt_subdiv_topology_creased_of(verts, k, levels, crease, corner, t, why, why_size > 0 ? (size_t)why_size : 0);
     if (v != MPT_SUBDIV_OK) return (int)v;
-    return topology_out(t, levels, counts, offsets, true, words, cap_words, need_words);
+    return topology_out(t, levels, counts, offsets, 11, words, cap_words, need_words);
 }
 
 // ---------------------------------------------------------------- what scene_compose.cpp and scene_deform.cpp tell the table
 int subdiv_object_faces(const mpt_ctx *c, int mesh_id) {
     const auto &m = c->compose.meshes[mesh_id];
-    return m.subdiv.levels ? (int)m.subdiv.out_faces : m.nfaces;
+    return m.subdiv.head.levels ? (int)m.subdiv.out_faces : m.nfaces;
 }
 
 void subdiv_object_added(mpt_ctx *c, int obj_id) {
     auto &sd = c->subdiv;
     auto &row = c->compose.rows[obj_id];
     auto &m = c->compose.meshes[row.mesh].subdiv;
-    if (m.levels == 0) return;
+    if (m.head.levels == 0) return;
     const bool deformable = row.pose >= 0;
     if (deformable || m.job < 0) {
         mpt_ctx::MptSubdivCopy p;
@@ -98,7 +98,7 @@ static int set_subdivision(mpt_ctx *c, const char *who, int mesh_id, int levels,
     auto &cp = c->compose;
     if (check_fresh_mesh(c, mesh_id, who)) return 1;
     auto &m = cp.meshes[mesh_id].subdiv;
-    if (m.levels) return fail("%s: mesh %d already has a subdivision level", who, mesh_id);
+    if (m.head.levels) return fail("%s: mesh %d already has a subdivision level", who, mesh_id);
     if (levels < 1 || levels > MPT_SUBDIV_MAX_LEVELS) return fail("%s: levels %d outside [1, %d]", who, levels, MPT_SUBDIV_MAX_LEVELS);
     const int k = cp.meshes[mesh_id].nfaces;
     // the faces an object of the mesh will have: k 4^L, or of m polygons of n_j corners 2 (sum n_j) 4^(L - 1)
@@ -122,11 +122,10 @@ static int set_subdivision(mpt_ctx *c, const char *who, int mesh_id, int levels,
         HIP_TRY(hipMemcpyAsync(sd.bufs.topo + sd.topo_used, t.words.data(), words * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    m.levels = levels; m.topo_at = sd.topo_used; m.job = -1;
-    for (int l = 0; l <= levels; l++) { m.nv[l] = t.nv[l]; m.rule_at[l] = t.rule_at[l]; }
-    m.nrule_at = t.nrule_at; m.face_at = t.face_at;
-    m.srule_at = t.srule_at ? t.srule_at : t.nrule_at; m.nrec = t.nrec;
-    m.quad_at = t.quad_at; m.out_faces = cc ? 2 * t.nf[levels] : t.nf[levels];
+    m.head = t;
+    if (!t.srule_at) m.head.srule_at = t.nrule_at;       // (an uncreased mesh: the records' rules are the rings')
+    m.topo_at = sd.topo_used; m.job = -1;
+    m.out_faces = cc ? 2 * t.nf[levels] : t.nf[levels];
     sd.topo_used += words;
     return 0;
 }
@@ -161,7 +160,7 @@ extern "C" int mpt_mesh_set_displacement(mpt_ctx *c, int mesh_id, int image_id, 
     auto &cp = c->compose;
     if (check_mesh(c, mesh_id, who)) return 1;
     auto &m = cp.meshes[mesh_id].subdiv;
-    if (m.levels == 0) return fail("%s: displacement needs a subdivided mesh: mesh %d has no subdivision level", who, mesh_id);
+    if (m.head.levels == 0) return fail("%s: displacement needs a subdivided mesh: mesh %d has no subdivision level", who, mesh_id);
     if (check_fresh_mesh(c, mesh_id, who)) return 1;
     if (m.displaced) return fail("%s: mesh %d already has a displacement", who, mesh_id);
     if (mode != MPT_DISPLACE_NORMAL && mode != MPT_DISPLACE_VECTOR) return fail("%s: mode %d outside [0, 1]", who, mode);
@@ -169,16 +168,16 @@ extern "C" int mpt_mesh_set_displacement(mpt_ctx *c, int mesh_id, int image_id, 
     if (image_id < 0) return fail("%s: image id %d is negative", who, image_id);
     if (check_displace_params(who, strength, midlevel)) return 1;
     const int k = cp.meshes[mesh_id].nfaces;
-    const int64_t nf = m.out_faces, nv = m.nv[m.levels];
+    const int64_t nf = m.out_faces, nv = m.head.nv[m.head.levels];
     std::vector<float> rec;
     std::vector<int32_t> faces((size_t)nf * 3), corner((size_t)nv);
     if (fetch_mesh(c, mesh_id, rec)) return 1;
-    if (k > 0) HIP_TRY(hipMemcpy(faces.data(), sd.bufs.topo + m.topo_at + (size_t)m.face_at, faces.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (k > 0) HIP_TRY(hipMemcpy(faces.data(), sd.bufs.topo + m.topo_at + (size_t)m.head.face_at, faces.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     char why[200];
     if (mpt_displace_uv_check_of(rec.data(), k, why, sizeof why)) return fail("%s: mesh %d: %s", who, mesh_id, why);
-    if (m.srule_at != m.nrule_at && nf > 0) {            // a creased mesh's face table indexes records: back to their vertices
-        std::vector<int32_t> vert((size_t)m.nrec);
-        HIP_TRY(hipMemcpy(vert.data(), sd.bufs.topo + m.topo_at + (size_t)m.srule_at + (size_t)m.nrec * 2, vert.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (m.head.srule_at != m.head.nrule_at && nf > 0) {  // a creased mesh's face table indexes records: back to their vertices
+        std::vector<int32_t> vert((size_t)m.head.nrec);
+        HIP_TRY(hipMemcpy(vert.data(), sd.bufs.topo + m.topo_at + (size_t)m.head.srule_at + (size_t)m.head.nrec * 2, vert.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         for (auto &f : faces) f = vert[(size_t)f];
     }
     if (mpt_displace_corners_of(faces.data(), nf, (int32_t)nv, corner.data())) return fail("%s: mesh %d: its topology names no first corner for every vertex", who, mesh_id);
@@ -214,17 +213,27 @@ extern "C" int mpt_mesh_set_displacement_params(mpt_ctx *c, int mesh_id, double 
 // the doubles of a copy's workspace: the positions of levels 1..L (each level from an even offset), then the last level's records,
 // one per vertex or, of a creased mesh, per sector, then -- a displaced copy -- the displaced positions of the last level
 static size_t work_layout(const mpt_ctx::MptSubdivMesh &m, MptSubdivJob *job) {
+    const MptSubdivHead &h = m.head;
     size_t at = 0;
-    for (int l = 1; l <= m.levels; l++) {
+    for (int l = 1; l <= h.levels; l++) {
         if (job) job->pos_at[l] = (int32_t)at;
-        at += ((size_t)m.nv[l] * 3 + 1) & ~(size_t)1;
+        at += ((size_t)h.nv[l] * 3 + 1) & ~(size_t)1;
     }
     if (job) job->vrec_at = (int32_t)at;
-    at += (size_t)m.nrec * 4;
-    if (job) job->npos_at = job->pos_at[m.levels];
+    at += (size_t)h.nrec * 4;
+    if (job) job->npos_at = job->pos_at[h.levels];
     if (!m.displaced) return at;
     if (job) job->pos_at[0] = job->npos_at = (int32_t)at;
-    return at + (((size_t)m.nv[m.levels] * 3 + 1) & ~(size_t)1);
+    return at + (((size_t)h.nv[h.levels] * 3 + 1) & ~(size_t)1);
+}
+
+// the part of a job that is the block's header (a mesh's row keeps it normalised: set_subdivision)
+static void job_head(const MptSubdivHead &h, MptSubdivJob &t) {
+    t.levels = h.levels;
+    for (int l = 0; l <= h.levels; l++) { t.nv[l] = (int32_t)h.nv[l]; t.rule_at[l] = h.rule_at[l]; }
+    t.nrule_at = h.nrule_at; t.face_at = h.face_at;
+    t.srule_at = h.srule_at; t.nrec = (int32_t)h.nrec;
+    t.rule_at[0] = h.quad_at;                             // (the record has no word to spare: MptSubdivJob)
 }
 
 // does the next subdiv_step write this copy?  (`all`: a relayout writes every copy)
@@ -239,7 +248,7 @@ int subdiv_images_ready(mpt_ctx *c) {
     const bool all = c->compose.relayout || sd.room.stale || c->deform.room.stale;
     for (const auto &p : sd.copies) {
         const auto &m = c->compose.meshes[p.mesh].subdiv;
-        if (!m.displaced || m.nv[m.levels] == 0 || !copy_is_dirty(c, p, all)) continue;
+        if (!m.displaced || m.head.nv[m.head.levels] == 0 || !copy_is_dirty(c, p, all)) continue;
         if ((size_t)m.image >= c->h_images.size())
             return fail("mpt_compose: the displacement of mesh %d reads image %d, and %zu images are loaded", p.mesh, m.image, c->h_images.size());
         const MptImage &im = c->h_images[m.image];
@@ -288,22 +297,19 @@ int subdiv_step(mpt_ctx *c) {
         MptSubdivJob &t = jobs[j];
         t.src_vert = p.obj >= 0 ? (int32_t)df.poses[cp.rows[p.obj].pose].copy_vert : (int32_t)cp.meshes[p.mesh].vert;
         t.dst_vert = (int32_t)p.copy_vert;
-        t.levels = m.levels; t.nfaces = subdiv_object_faces(c, p.mesh);
+        t.nfaces = subdiv_object_faces(c, p.mesh);
         t.topo_at = (int64_t)m.topo_at; t.work_at = (int64_t)p.work_at;
-        for (int l = 0; l <= m.levels; l++) { t.nv[l] = (int32_t)m.nv[l]; t.rule_at[l] = m.rule_at[l]; }
-        t.nrule_at = m.nrule_at; t.face_at = m.face_at;
-        t.srule_at = m.srule_at; t.nrec = (int32_t)m.nrec;
-        t.rule_at[0] = m.quad_at;                         // (the record has no word to spare: MptSubdivJob)
+        job_head(m.head, t);
         work_layout(m, &t);
         dirty[j] = copy_is_dirty(c, p, all);
         if (!dirty[j] || t.nfaces == 0) continue;
-        ndirty++; lmax = std::max(lmax, m.levels); any_cc |= m.quad_at != 0;
+        ndirty++; lmax = std::max(lmax, m.head.levels); any_cc |= m.head.quad_at != 0;
         sd.stats.refined_copies++; sd.stats.refined_faces += t.nfaces;
         if (!m.displaced) continue;
         const MptImage &im = c->h_images[m.image];            // (loaded: subdiv_images_ready)
         djobs[j] = { m.mode, m.channel, im.nx, im.ny, (int64_t)im.base, (int64_t)m.corner_at, m.strength, m.midlevel };
         displace[j] = 1; ndisplaced++;
-        sd.displaced_copies++; sd.displaced_verts += t.nv[m.levels];
+        sd.displaced_copies++; sd.displaced_verts += t.nv[m.head.levels];
     }
     // a copy displaced again because the images changed: the objects that read it are composed again
     for (auto &row : cp.rows)

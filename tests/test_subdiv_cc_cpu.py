@@ -2,10 +2,14 @@
 CPU tests of Catmull-Clark subdivision: the pure function of the host runtime (mpt_subdiv_topology_cc:
 no context, no GPU), decoded by the documented layout, against the independent numpy restatement the GPU tests hold the kernels to
 (tests/subdiv_cc_ref.py); the restatement itself against values worked out by hand and against the uniform bicubic B-spline, a
-yardstick with no topology in it; and Loop's two topology functions against the words they gave before this scheme existed.
+yardstick with no topology in it; both schemes' topology functions against the words they gave before they shared their code; and
+that code under the host sanitizers, in a stand-alone program.
 '''
 
 import hashlib
+import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -17,6 +21,7 @@ import test_subdiv_cpu as loop_cpu
 
 u32 = np.uint32
 LEVELS = (1, 2, 3)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _topology(rec, levels, polys=None, creases=None, corners=None):
@@ -154,7 +159,7 @@ def test_levels_and_sizes_are_refused():
         _lib.subdiv_topology_cc(rec, 1, polys, np.zeros(6))
 
 
-# ---------------------------------------------------------------- Loop is untouched
+# ---------------------------------------------------------------- the words are what they were
 def _loop_digest():
     '''sha256 over the blocks of words mpt_subdiv_topology and mpt_subdiv_topology_creased give for test_subdiv_cpu's and
     test_subdiv_crease_cpu's fixtures at levels 1 to 3'''
@@ -176,9 +181,24 @@ def _loop_digest():
     return h.hexdigest()
 
 
+def _cc_digest():
+    '''sha256 over the whole blocks of words mpt_subdiv_topology_cc gives for every fixture of subdiv_cc_ref at levels 1 to 3 (the
+    tables compared above do not pin the order of the rings inside the block; this does)'''
+    h = hashlib.sha256()
+    for name in ref.NAMES + ref.CREASED:
+        rec, polys, creases, corners = ref.fixture(name)
+        for levels in LEVELS:
+            rc, words, _ = _topology(rec, levels, polys, creases, corners)
+            assert rc == 0
+            h.update(np.ascontiguousarray(words, np.int32).tobytes())
+    return h.hexdigest()
+
+
 def test_loop_topologies_are_word_for_word_what_they_were():
-    '''recorded on the commit before Catmull-Clark; the tables are also still the Loop restatements' '''
+    '''LOOP_DIGEST was recorded on the commit before Catmull-Clark, CC_DIGEST on the commit before the two schemes shared one level
+    builder and one set of crease rules; the tables are also still the Loop restatements' '''
     assert _loop_digest() == LOOP_DIGEST
+    assert _cc_digest() == CC_DIGEST
     from ptina_amd import _lib
     for name in subdiv_ref.NAMES:
         rc, _, got = _lib.subdiv_topology(subdiv_ref.fixture(name), 2)
@@ -197,6 +217,21 @@ def test_loop_topologies_are_word_for_word_what_they_were():
 
 
 LOOP_DIGEST = '30519cbaf5cfea60411fa968f07115e83bfdbe0aa17fc93f2cace02f2839af70'
+CC_DIGEST = '84ac9de44e6ebf252bd8dbac00285821fa04b762ad3133e3c0336a779278aa6e'
+
+
+# ---------------------------------------------------------------- the rules under the host sanitizers
+def test_rule_check_program_builds_and_passes(tmp_path):
+    cxx = shutil.which('c++') or shutil.which('g++') or shutil.which('clang++')
+    assert cxx, 'no host C++ compiler'
+    exe = str(tmp_path / 'subdiv_rule_check')
+    subprocess.run([cxx, '-std=c++17', '-g', '-O1', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', os.path.join(ROOT, 'tools', 'subdiv_rule_check.cpp'),
+                    '-o', exe], check=True, capture_output=True, text=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    print(run.stdout, run.stderr)
+    assert run.returncode == 0, run.stderr[-2000:]
+    assert run.stdout.splitlines() == ['subdiv_rule_check: 36 topologies, 72 creased, 19 refusals, 0 failures',
+                                       'subdiv_rule_check: Catmull-Clark: 48 topologies, 96 creased, 19 refusals']
 
 
 # ---------------------------------------------------------------- the restatement against what is known by hand
