@@ -1,0 +1,117 @@
+#!/usr/bin/env python3
+'''
+A crowd that sways: many objects of ONE skinned tube (8 joints, a morph target that bulges its middle) standing in the Cornell room,
+all bound to one clip at different offsets, the scene kept on the device.  Skeleton and clip are given once; each frame is
+    ModelPool().set_time(t) -> compose() -> BVHTree().update() -> PathEngine().render() x spp
+so nothing but the time crosses to the device: every object's pose is evaluated there (csrc/anim.hip), in one launch, the corners
+are skinned there (csrc/deform.hip), the faces composed again and the built tree fitted to them (csrc/refit.hip).
+
+    python exams/crowd_amd.py [--objects 24] [--frames 12] [--size 256] [--spp 8] [--out DIR]
+'''
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from ptina_amd.things import *              # noqa: E402,F401,F403
+from ptina_amd.engine.path import *         # noqa: E402,F401,F403
+from ptina_amd.image import write_png       # noqa: E402
+from ptina_amd.tools.anim import quaternion, rest_pose, track   # noqa: E402
+from ptina_amd import scenes                # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument('--objects', type=int, default=24)
+ap.add_argument('--frames', type=int, default=12)
+ap.add_argument('--size', type=int, default=256)
+ap.add_argument('--spp', type=int, default=8)
+ap.add_argument('--out', default='.')
+args = ap.parse_args()
+
+JOINTS, HEIGHT, RADIUS, RINGS, SIDES, PERIOD = 8, 0.9, 0.05, 24, 12, 2.0
+
+
+def tube():
+    '''(p, n [k,3,3], joints, weights [k,3,4], bulge dp [1,k,3,3]): rings of quads round the y axis, each corner bound to the two
+    joints its height lies between'''
+    y = np.linspace(0.0, HEIGHT, RINGS + 1)
+    a = np.linspace(0.0, 2 * np.pi, SIDES + 1)
+    yy, aa = np.meshgrid(y, a, indexing='ij')
+    nrm = np.stack([np.cos(aa), np.zeros_like(aa), np.sin(aa)], axis=-1)
+    pos = RADIUS * nrm + np.stack([np.zeros_like(yy), yy, np.zeros_like(yy)], axis=-1)
+    at = np.clip(yy / HEIGHT * JOINTS - 0.5, 0.0, JOINTS - 1.0)
+    j0 = np.floor(at).astype(np.int64)
+    f = at - j0
+    jt = np.stack([j0, np.minimum(j0 + 1, JOINTS - 1), np.zeros_like(j0), np.zeros_like(j0)], axis=-1)
+    wt = np.stack([1.0 - f, f, np.zeros_like(f), np.zeros_like(f)], axis=-1)
+    dp = 0.8 * RADIUS * np.exp(-((yy - 0.5 * HEIGHT) / (0.12 * HEIGHT)) ** 2)[..., None] * nrm
+
+    def tris(x):
+        c = x[:-1, :-1], x[1:, :-1], x[1:, 1:], x[:-1, 1:]
+        return np.concatenate([np.stack([c[0], c[1], c[2]], axis=-2).reshape(-1, 3, x.shape[-1]),
+                               np.stack([c[0], c[2], c[3]], axis=-2).reshape(-1, 3, x.shape[-1])])
+    return tris(pos), tris(nrm), tris(jt), tris(wt), tris(dp)[None]
+
+
+def shift(x, y, z):
+    m = np.eye(4)
+    m[:3, 3] = [x, y, z]
+    return m
+
+
+ti.init(ti.cuda)
+init_things()
+PathEngine()
+FilmTable().set_size(args.size, args.size)
+_, _, materials, images = scenes.scene_s34()
+MaterialPool().load(materials)
+ImagePool().load(images)
+Camera().set_perspective(scenes.BENCH_CAMERA)
+
+wp, wn, wt, wm = scenes.cornell_walls()
+pool = ModelPool()
+for mtl in (0, 1, 2):
+    pick = wm == mtl
+    pool.add_object(pool.add_mesh(wp[pick], wn[pick], wt[pick]), np.eye(4), mtl)
+p, n, joints, weights, dp = tube()
+mesh = pool.add_mesh(p, n)
+pool.add_morph_targets(mesh, dp)
+pool.add_skin(mesh, joints, weights, JOINTS)
+# the skeleton: a chain up the tube, at rest straight; the clip: every joint sways about z, the root hops, the bulge breathes
+seg = HEIGHT / JOINTS
+t, r, s = rest_pose(JOINTS)
+t[1:, 1] = seg
+pool.add_skeleton(mesh, np.arange(JOINTS) - 1, t, r, s, np.stack([shift(0, -j * seg, 0) for j in range(JOINTS)]))
+times = np.linspace(0.0, PERIOD, 17)
+phase = 2 * np.pi * times / PERIOD
+tracks = [track(j, 'R', times, [quaternion([0, 0, 1], 1.2 * np.sin(a) / JOINTS) for a in phase]) for j in range(JOINTS)]
+tracks.append(track(0, 'T', times, np.stack([0 * times, 0.08 * np.abs(np.sin(phase)), 0 * times], axis=1)))
+tracks.append(track(None, 'W', times, (0.5 - 0.5 * np.cos(phase))[:, None]))
+clip = pool.add_clip(mesh, tracks)
+g = np.random.default_rng(1)
+side = int(np.ceil(np.sqrt(args.objects)))
+for o in range(args.objects):
+    x, z = (o % side + 0.5) / side, (o // side + 0.5) / side
+    obj = pool.add_object(mesh, shift(-0.8 + 1.6 * x, 0.0, -0.9 + 1.4 * z), 3)
+    pool.set_animation(obj, clip, offset=g.uniform(0.0, PERIOD), speed=g.uniform(0.8, 1.25))
+pool.compose()
+BVHTree().build()
+
+os.makedirs(args.out, exist_ok=True)
+t0 = time.perf_counter()
+refitted = 0
+for f in range(args.frames):
+    pool.set_time(PERIOD * f / args.frames)
+    pool.compose()
+    refitted += BVHTree().update() == 'refit'
+    FilmTable().clear()
+    PathEngine().render(args.spp)
+    img = FilmTable().get_display(layout='display')
+    write_png(os.path.join(args.out, 'crowd_%03d.png' % f), img)
+    a, d, c = pool.anim_stats(), pool.deform_stats(), pool.compose_stats()
+    print('frame %d: %d objects posed on the device, %d corners deformed, %d of %d faces recomposed, mean byte %.2f'
+          % (f, a.evaluated_objects, d.deformed_corners, c.recomposed, c.faces, float(img[..., :3].mean())))
+dt = time.perf_counter() - t0
+print('%d frames of %dx%d at %d spp in %.2f s (PNG writing included), %d refitted: written to %s'
+      % (args.frames, args.size, args.size, args.spp, dt, refitted, args.out))

@@ -594,6 +594,70 @@ int mpt_deform_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
 int mpt_deform_plan(const int32_t *corners, const int32_t *dirty, int nobj, int32_t *run_obj, int64_t *run_block, int cap, int64_t *blocks);
 int mpt_skin_check(const uint16_t *joints, const float *weights, int64_t ncorners, int njoints, char *why, int why_size);
 
+/* Keyframe animation on the device: glTF 2.0's animations (samplers, channels, joint hierarchy) for the deformable meshes of the pool,
+ * so that a frame of any number of animated objects costs mpt_scene_set_time -- one double -- and one kernel that writes their poses
+ * where the deform kernel reads them.  Reading animations from files is not part of it.  The rule (csrc/anim_rule.h states it once,
+ * for host and device; f64, every sum in one written order, no contraction):
+ *   SKELETON of a mesh with a skin: parents[j] in [-1, j) (parents come before children), a rest pose per joint (rest [j][10]:
+ *     translation3, rotation4 x y z w, scale3) and inverse_bind [j][12] (3x4 row-major).  Its joint count is the skin's.
+ *   CLIP of a mesh: tracks, each (target, path, interpolation, nkeys): target a joint, or -1 for the morph weights; path 0 T, 1 R, 2 S,
+ *     3 W; interpolation 0 STEP, 1 LINEAR, 2 CUBICSPLINE; f32 key times, finite and strictly increasing; f32 values, C = 3, 4, 3 or
+ *     ntargets per key, three times that for CUBICSPLINE (in-tangent, value, out-tangent, as glTF lays them out).  At most one track per
+ *     (target, path).  A key's rotation is used as given, not renormalised; a zero one is refused.  The clip's span [t0, t1]: the least
+ *     first key to the greatest last key.  A mesh with targets and no skin has no skeleton and may have clips of W tracks.
+ *   BINDING of an object: (clip, offset, speed, loop).  Local time at scene time t: tau = (t - offset) * speed; with loop and t1 > t0,
+ *     tau = t0 + (x - floor(x / d) * d), x = tau - t0, d = t1 - t0; otherwise as it is: each track clamps for itself.
+ *   A TRACK at tau: one key, or tau <= the first key: the first value; tau >= the last key: the last; else k the largest index with
+ *     time[k] <= tau, dt = time[k+1] - time[k], u = (tau - time[k]) / dt, and STEP v_k; LINEAR v_k + u (v_k+1 - v_k), for R the slerp:
+ *     d = dot(a, b); d < 0: b = -b, d = -d; d > 0.9995: normalise(a + u (b - a)); else theta = acos d,
+ *     (sin((1 - u) theta) a + sin(u theta) b) / sin theta; CUBICSPLINE glTF's Hermite form with the tangents scaled by dt
+ *     (coefficients: anim_rule.h), an R result normalised.
+ *   A joint's T, R or S without a track is its rest value; local = [R(q) diag(s) | t]; global[j] = local[j] for a root, else
+ *     global[parent] . local[j] (affine 3x4 product, each entry ((a0 b0 + a1 b1) + a2 b2) (+ a3)); palette[j] = global[j] . inverse_bind[j].
+ *     Morph weights without a W track are 0.  The pose: ntargets weights, then njoints x 12 doubles.
+ *   Only the slerp's theta branch calls library functions (acos, sin); everything else is + - * / sqrt floor and reproducible bit for bit.
+ * mpt_mesh_set_skeleton: once per mesh, behind mpt_mesh_set_skin and before the mesh has an object.  mpt_mesh_add_clip: any number
+ *   per mesh, before the mesh has an object; tracks [ntracks][4], times and values the tracks' arrays back to back; *clip_id counts over
+ *   the scene.  They refuse, naming the argument: an unknown mesh or one that has an object; a mesh without a skin, or njoints not the
+ *   skin's; parents out of order; a value that is not finite; a zero rotation; key times that are not finite or not increasing; a track
+ *   on a joint beyond njoints; a W track on a mesh without targets; two tracks on one (target, path).
+ * mpt_object_set_animation: binds a deformable object to a clip of its mesh (refuses a clip of another mesh; offset and speed finite);
+ *   clip -1 unbinds: the pose is again what mpt_object_set_joints / mpt_object_set_morph_weights last gave, and while an object is
+ *   bound those two refuse it (unbind first).  mpt_scene_set_time: the scene's time (0 at first; finite); marks every bound object
+ *   changed for mpt_compose, as mpt_object_set_joints marks one; the same time again marks nothing.
+ * mpt_compose: the changed bound objects' poses are not uploaded but evaluated, all in one launch in front of the deform kernel; after
+ *   objects were added or dropped every bound object is evaluated again.  A scene without a binding is composed as ever.
+ * mpt_get_pose: a deformable object's pose as it lies on the device after the last mpt_compose (ntargets + 12 njoints doubles; cap: the
+ *   room of `pose` in doubles), bound or not.
+ * mpt_anim_stats: skeletons, clips and tracks of the scene; bound objects; objects the last mpt_compose evaluated.
+ * mpt_anim_kernel_time: HIP-event time (ms) of the animation kernels of the mpt_compose calls since the last call, and their count.
+ * mpt_anim_rule: the whole evaluation of one object's pose as a pure function (no context, no GPU) from flat arrays, at scene time t;
+ *   returns 0, or 100 + mpt_clip_check's verdict, or 200 + the skeleton's (1 bad arrays, 2 njoints outside [1, 256], 3 parents out of
+ *   order, 4 a value not finite, 5 a zero rest rotation); njoints 0: no skeleton.
+ * mpt_clip_check: the validation of a clip's arrays as a pure function.  Returns 0, or 1 bad arrays, 2 an unknown path or interpolation,
+ *   3 a track on a joint beyond njoints (or a W track whose target is not -1), 4 a W track without targets, 5 nkeys < 1, 6 a key time not
+ *   finite, 7 key times not increasing, 8 two tracks on one (target, path), 9 a zero key rotation, 10 a value not finite, with the
+ *   words in why[why_size] (may be NULL).
+ * mpt_anim_trig: the measurement door of the slerp's library functions: acos and sin of x [n] as the device evaluates them. */
+typedef struct {
+    int64_t skeletons, clips, tracks, bound_objects, evaluated_objects;
+} mpt_anim_info;
+int mpt_mesh_set_skeleton(mpt_ctx *ctx, int mesh_id, int njoints, const int32_t *parents, const double *rest /* [njoints][10] */,
+                          const double *inverse_bind /* [njoints][12] */);
+int mpt_mesh_add_clip(mpt_ctx *ctx, int mesh_id, int ntracks, const int32_t *tracks /* [ntracks][4] */, const float *times, int64_t ntimes,
+                      const float *values, int64_t nvalues, int *clip_id);
+int mpt_object_set_animation(mpt_ctx *ctx, int obj_id, int clip_id, double offset, double speed, int loop);
+int mpt_scene_set_time(mpt_ctx *ctx, double t);
+int mpt_get_pose(mpt_ctx *ctx, int obj_id, double *pose, int cap);
+int mpt_anim_stats(mpt_ctx *ctx, mpt_anim_info *out);
+int mpt_anim_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
+int mpt_anim_rule(int njoints, int ntargets, const int32_t *parents, const double *rest, const double *inverse_bind, int ntracks,
+                  const int32_t *tracks, const float *times, int64_t ntimes, const float *values, int64_t nvalues, double offset, double speed,
+                  int loop, double t, double *pose /* [ntargets + 12 njoints] */);
+int mpt_clip_check(int njoints, int ntargets, int ntracks, const int32_t *tracks, const float *times, int64_t ntimes, const float *values,
+                   int64_t nvalues, char *why, int why_size);
+int mpt_anim_trig(mpt_ctx *ctx, const double *x, int n, double *acos_out, double *sin_out);
+
 /* Loop subdivision on the device (triangles in, four triangles out per level) as a property of a mesh of the pool, evaluated inside
  * mpt_compose behind morph targets and skinning and before composition, so that a pose change of a subdivided character costs the
  * upload of the pose, the deform kernel, L + 2 kernels over that object, the partial mpt_compose and mpt_refit_tree: topology and face

@@ -88,6 +88,11 @@ class DeformInfo(C.Structure):
     _fields_ = [('deformable_objects', C.c_int64), ('deformed_objects', C.c_int64), ('deformed_corners', C.c_int64), ('copy_verts', C.c_int64)]
 
 
+class AnimInfo(C.Structure):
+    '''mpt_anim_info (include/miptina.h): what mpt_anim_stats hands back'''
+    _fields_ = [('skeletons', C.c_int64), ('clips', C.c_int64), ('tracks', C.c_int64), ('bound_objects', C.c_int64), ('evaluated_objects', C.c_int64)]
+
+
 class SubdivInfo(C.Structure):
     '''mpt_subdiv_info (include/miptina.h): what mpt_subdiv_stats hands back'''
     _fields_ = [('subdivided_objects', C.c_int64), ('copies', C.c_int64), ('refined_copies', C.c_int64), ('refined_faces', C.c_int64),
@@ -284,6 +289,17 @@ SIGNATURES = {
     'mpt_deform_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
     'mpt_deform_plan': (_i, [_ip, _ip, _i, _ip, C.POINTER(C.c_int64), _i, C.POINTER(C.c_int64)]),
     'mpt_skin_check': (_i, [C.POINTER(C.c_uint16), _fp, C.c_int64, _i, C.c_char_p, _i]),
+    'mpt_mesh_set_skeleton': (_i, [_vp, _i, _i, _ip, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    'mpt_mesh_add_clip': (_i, [_vp, _i, _i, _ip, _fp, C.c_int64, _fp, C.c_int64, C.POINTER(_i)]),
+    'mpt_object_set_animation': (_i, [_vp, _i, _i, C.c_double, C.c_double, _i]),
+    'mpt_scene_set_time': (_i, [_vp, C.c_double]),
+    'mpt_get_pose': (_i, [_vp, _i, C.POINTER(C.c_double), _i]),
+    'mpt_anim_stats': (_i, [_vp, C.POINTER(AnimInfo)]),
+    'mpt_anim_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_anim_rule': (_i, [_i, _i, _ip, C.POINTER(C.c_double), C.POINTER(C.c_double), _i, _ip, _fp, C.c_int64, _fp, C.c_int64, C.c_double, C.c_double, _i,
+                           C.c_double, C.POINTER(C.c_double)]),
+    'mpt_clip_check': (_i, [_i, _i, _i, _ip, _fp, C.c_int64, _fp, C.c_int64, C.c_char_p, _i]),
+    'mpt_anim_trig': (_i, [_vp, C.POINTER(C.c_double), _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     'mpt_mesh_set_subdivision': (_i, [_vp, _i, _i]),
     'mpt_get_subdivided': (_i, [_vp, _i, _fp, _i]),
     'mpt_subdiv_stats': (_i, [_vp, C.POINTER(SubdivInfo)]),
@@ -502,6 +518,47 @@ def skin_check(joints, weights, njoints):
     why = C.create_string_buffer(200)
     rc = load_library().mpt_skin_check(j.ctypes.data_as(C.POINTER(C.c_uint16)), fptr(w), j.shape[0], int(njoints), why, len(why))
     return rc, why.value.decode()
+
+
+ANIM_PATHS = ('T', 'R', 'S', 'W')                                        # csrc/mpt_types.h MPT_ANIM_T .. _W
+ANIM_INTERPOLATIONS = ('STEP', 'LINEAR', 'CUBICSPLINE')                  # ... MPT_ANIM_STEP .. _CUBICSPLINE
+
+
+def _dptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _clip_arrays(spec, times, values):
+    spec = np.ascontiguousarray(spec, np.int32).reshape(-1, 4)
+    return spec, np.ascontiguousarray(times, np.float32).reshape(-1), np.ascontiguousarray(values, np.float32).reshape(-1)
+
+
+def clip_check(njoints, ntargets, spec, times, values):
+    '''mpt_clip_check (no context, no GPU): (verdict, words) for a clip's packed arrays (tools.anim.pack_clip: spec [n,4] of target,
+    path, interpolation, nkeys; the tracks' times and values back to back) on a mesh of njoints joints and ntargets morph targets;
+    verdict 0 accepts'''
+    spec, times, values = _clip_arrays(spec, times, values)
+    why = C.create_string_buffer(200)
+    rc = load_library().mpt_clip_check(int(njoints), int(ntargets), spec.shape[0], iptr(spec), fptr(times), times.size, fptr(values), values.size,
+                                       why, len(why))
+    return rc, why.value.decode()
+
+
+def anim_rule(parents, rest, inverse_bind, ntargets, spec, times, values, offset, speed, loop, t):
+    '''mpt_anim_rule (no context, no GPU): the pose (weights [ntargets], palette [nj,3,4]) of one object at scene time t -- skeleton
+    parents [nj], rest [nj,10] (translation3 rotation4 xyzw scale3), inverse_bind [nj,3,4] (nj 0: no skeleton), the clip's packed
+    arrays and the binding; ValueError with the verdict for arrays the rule refuses'''
+    parents = np.ascontiguousarray(parents, np.int32).reshape(-1)
+    nj = int(parents.size)
+    rest = np.ascontiguousarray(rest, np.float64).reshape(nj, 10)
+    inverse_bind = np.ascontiguousarray(inverse_bind, np.float64).reshape(nj, 12)
+    spec, times, values = _clip_arrays(spec, times, values)
+    pose = np.zeros(int(ntargets) + 12 * nj, np.float64)
+    rc = load_library().mpt_anim_rule(nj, int(ntargets), iptr(parents), _dptr(rest), _dptr(inverse_bind), spec.shape[0], iptr(spec), fptr(times), times.size,
+                                      fptr(values), values.size, float(offset), float(speed), int(bool(loop)), float(t), _dptr(pose))
+    if rc:
+        raise ValueError('mpt_anim_rule refuses its arrays: verdict %d' % rc)
+    return pose[:int(ntargets)].copy(), pose[int(ntargets):].reshape(nj, 3, 4).copy()
 
 
 SUBDIV_CHUNK, SUBDIV_MAX_LEVELS = 256, 5                                # csrc/mpt_types.h MPT_SUBDIV_*

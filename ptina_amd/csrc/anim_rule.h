@@ -1,0 +1,280 @@
+// anim_rule.h -- the rule of keyframe animation (summarised in include/miptina.h): the validation of a
+// skeleton's and a clip's arrays, a binding's local time, a track at that time, a joint's local matrix, the hierarchy and the palette.
+// Plain C++17 with nothing of HIP and no context (as deform_rule.h and scatter_rule.h), so that a stand-alone program can run all of
+// it under a sanitizer (tools/anim_rule_check.cpp); under hipcc the MPT_HD functions are anim.hip's arithmetic.  The C ABI has the
+// whole evaluation of one object's pose as mpt_anim_rule and the validation of a clip as mpt_clip_check.
+//
+// Arithmetic: f64, one correctly rounded operation per operator in the order written, never contracted (the pragma below in every
+// function that computes, for a host compiler; -ffp-contract=off for anim.hip, the Makefile's rule), so that tests/anim_ref.py
+// restates every pose bit for bit -- except through the one branch of the slerp that calls acos and sin, the only library functions
+// here: there host, device and numpy each have their own, and the tests hold them to a bound (tests/anim_ref.py, error_bound).
+// Key times and values are f32 and widen exactly.
+#pragma once
+
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+#include <vector>
+#include "mpt_types.h"         // MptAnimTrack, MPT_ANIM_*, MPT_DEFORM_MAX_* (plain structures and constants)
+#include "compose_rule.h"      // MPT_HD, MPT_NO_CONTRACT
+
+// ------------------------------------------------------------------ what may be a skeleton, what may be a clip
+enum MptSkeletonVerdict { MPT_SKELETON_OK = 0, MPT_SKELETON_ARGS, MPT_SKELETON_NJOINTS, MPT_SKELETON_PARENT, MPT_SKELETON_NOT_FINITE, MPT_SKELETON_ZERO_ROTATION };
+enum MptClipVerdict { MPT_CLIP_OK = 0, MPT_CLIP_ARGS, MPT_CLIP_KIND, MPT_CLIP_TARGET, MPT_CLIP_NO_TARGETS, MPT_CLIP_NKEYS, MPT_CLIP_TIME_NOT_FINITE,
+                      MPT_CLIP_TIME_ORDER, MPT_CLIP_DUPLICATE, MPT_CLIP_ZERO_ROTATION, MPT_CLIP_VALUE_NOT_FINITE };
+
+// the values of one key of a track: 3, 4, 3 or ntargets
+MPT_HD int mpt_anim_components(int path, int ntargets) { return path == MPT_ANIM_R ? 4 : path == MPT_ANIM_W ? ntargets : 3; }
+// ... and the floats a key holds of them: CUBICSPLINE keeps in-tangent, value, out-tangent
+MPT_HD int mpt_anim_key_floats(int path, int interp, int ntargets) { return (interp == MPT_ANIM_CUBICSPLINE ? 3 : 1) * mpt_anim_components(path, ntargets); }
+
+// May parents [njoints], rest [njoints][10] (translation3 rotation4 xyzw scale3) and inverse_bind [njoints][12] be a skeleton?  A
+// refusal writes its words, which name the argument, to `why` (always terminated).
+inline MptSkeletonVerdict mpt_skeleton_rule(int njoints, const int32_t *parents, const double *rest, const double *inverse_bind, char *why, size_t why_size) {
+    auto say = [&](MptSkeletonVerdict v, const char *fmt, long long a, long long b) {
+        if (why && why_size) snprintf(why, why_size, fmt, a, b);
+        return v;
+    };
+    if (why && why_size) why[0] = 0;
+    if (njoints < 1 || njoints > MPT_DEFORM_MAX_JOINTS) return say(MPT_SKELETON_NJOINTS, "skeleton: njoints %lld outside [1, %lld]", njoints, MPT_DEFORM_MAX_JOINTS);
+    if (!parents || !rest || !inverse_bind) return say(MPT_SKELETON_ARGS, "skeleton: parents, rest and inverse_bind must hold %lld joints", njoints, 0);
+    for (int j = 0; j < njoints; j++) {
+        if (parents[j] < -1 || parents[j] >= j)
+            return say(MPT_SKELETON_PARENT, "skeleton: parents[%lld] is %lld: parents come before their children (-1: a root)", j, parents[j]);
+        for (int k = 0; k < MPT_ANIM_REST; k++)
+            if (!std::isfinite(rest[(size_t)j * MPT_ANIM_REST + k])) return say(MPT_SKELETON_NOT_FINITE, "skeleton: rest[%lld][%lld] is not finite", j, k);
+        for (int k = 0; k < 12; k++)
+            if (!std::isfinite(inverse_bind[(size_t)j * 12 + k])) return say(MPT_SKELETON_NOT_FINITE, "skeleton: inverse_bind[%lld][%lld] is not finite", j, k);
+        const double *q = rest + (size_t)j * MPT_ANIM_REST + 3;
+        if (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0) return say(MPT_SKELETON_ZERO_ROTATION, "skeleton: the rest rotation rest[%lld][3..6] is zero", j, 0);
+    }
+    return MPT_SKELETON_OK;
+}
+
+// depth[j] of every joint (a root: 0); returns the greatest.  The skeleton has passed mpt_skeleton_rule
+inline int mpt_anim_depths(int njoints, const int32_t *parents, int32_t *depth) {
+    int levels = 0;
+    for (int j = 0; j < njoints; j++) {
+        depth[j] = parents[j] < 0 ? 0 : depth[parents[j]] + 1;
+        if (depth[j] > levels) levels = depth[j];
+    }
+    return levels;
+}
+
+// May spec [ntracks][4] (target, path, interpolation, nkeys per track), times [ntimes] (the tracks' key times, back to back) and
+// values [nvalues] (their values, back to back) be a clip of a mesh of njoints joints (0: no skeleton) and ntargets morph targets?
+inline MptClipVerdict mpt_clip_rule(int njoints, int ntargets, int ntracks, const int32_t *spec, const float *times, int64_t ntimes, const float *values,
+                                    int64_t nvalues, char *why, size_t why_size) {
+    auto say = [&](MptClipVerdict v, const char *fmt, long long a, long long b, long long c) {
+        if (why && why_size) snprintf(why, why_size, fmt, a, b, c);
+        return v;
+    };
+    if (why && why_size) why[0] = 0;
+    if (ntracks < 0 || ntimes < 0 || nvalues < 0 || (ntracks > 0 && !spec) || (ntimes > 0 && !times) || (nvalues > 0 && !values))
+        return say(MPT_CLIP_ARGS, "clip: tracks must hold [%lld][4] words, times %lld and values %lld floats", ntracks, ntimes, nvalues);
+    int64_t time_at = 0, value_at = 0;
+    for (int r = 0; r < ntracks; r++) {
+        const int target = spec[4 * r], path = spec[4 * r + 1], interp = spec[4 * r + 2], nkeys = spec[4 * r + 3];
+        if (path < MPT_ANIM_T || path > MPT_ANIM_W) return say(MPT_CLIP_KIND, "clip: tracks[%lld] has path %lld (0 T, 1 R, 2 S, 3 W)", r, path, 0);
+        if (interp < MPT_ANIM_STEP || interp > MPT_ANIM_CUBICSPLINE)
+            return say(MPT_CLIP_KIND, "clip: tracks[%lld] has interpolation %lld (0 STEP, 1 LINEAR, 2 CUBICSPLINE)", r, interp, 0);
+        if (path == MPT_ANIM_W) {
+            if (ntargets < 1) return say(MPT_CLIP_NO_TARGETS, "clip: tracks[%lld] animates the morph weights of a mesh without morph targets", r, 0, 0);
+            if (target != -1) return say(MPT_CLIP_TARGET, "clip: tracks[%lld] animates the morph weights: its target must be -1, not %lld", r, target, 0);
+        } else if (target < 0 || target >= njoints)
+            return say(MPT_CLIP_TARGET, "clip: tracks[%lld] names joint %lld, beyond njoints %lld", r, target, njoints);
+        if (nkeys < 1) return say(MPT_CLIP_NKEYS, "clip: tracks[%lld] has %lld keys: at least 1", r, nkeys, 0);
+        for (int q = 0; q < r; q++)
+            if (spec[4 * q] == target && spec[4 * q + 1] == path)
+                return say(MPT_CLIP_DUPLICATE, "clip: tracks[%lld] and tracks[%lld] animate the same target and path", q, r, 0);
+        const int64_t kf = mpt_anim_key_floats(path, interp, ntargets), floats = kf * nkeys;
+        if (time_at + nkeys > ntimes || value_at + floats > nvalues)
+            return say(MPT_CLIP_ARGS, "clip: times and values end before tracks[%lld] does (%lld times, %lld values)", r, ntimes, nvalues);
+        for (int k = 0; k < nkeys; k++) {
+            if (!std::isfinite(times[time_at + k])) return say(MPT_CLIP_TIME_NOT_FINITE, "clip: times[%lld] of tracks[%lld] is not finite", k, r, 0);
+            if (k > 0 && !(times[time_at + k] > times[time_at + k - 1]))
+                return say(MPT_CLIP_TIME_ORDER, "clip: times[%lld] of tracks[%lld] is not above the key before: key times must increase strictly", k, r, 0);
+        }
+        for (int64_t k = 0; k < floats; k++)
+            if (!std::isfinite(values[value_at + k])) return say(MPT_CLIP_VALUE_NOT_FINITE, "clip: values[%lld] of tracks[%lld] is not finite", k, r, 0);
+        if (path == MPT_ANIM_R)
+            for (int k = 0; k < nkeys; k++) {
+                const float *q = values + value_at + (int64_t)k * kf + (interp == MPT_ANIM_CUBICSPLINE ? 4 : 0);
+                if (q[0] == 0.0f && q[1] == 0.0f && q[2] == 0.0f && q[3] == 0.0f)
+                    return say(MPT_CLIP_ZERO_ROTATION, "clip: the rotation values of key %lld of tracks[%lld] are zero", k, r, 0);
+            }
+        time_at += nkeys; value_at += floats;
+    }
+    if (time_at != ntimes || value_at != nvalues)
+        return say(MPT_CLIP_ARGS, "clip: the tracks hold %lld times and %lld values, not what was given", time_at, value_at, 0);
+    return MPT_CLIP_OK;
+}
+
+// The tracks of a checked clip as the arenas hold them, with time_at / value_at counted from the clip's first time and value; the
+// span [t0, t1]: the least first key to the greatest last key (0, 0 for a clip without tracks)
+inline void mpt_anim_tracks(int ntargets, int ntracks, const int32_t *spec, const float *times, MptAnimTrack *tracks, double *t0, double *t1) {
+    int64_t time_at = 0, value_at = 0;
+    *t0 = *t1 = 0.0;
+    for (int r = 0; r < ntracks; r++) {
+        MptAnimTrack &tr = tracks[r];
+        tr.target = spec[4 * r]; tr.path = spec[4 * r + 1]; tr.interp = spec[4 * r + 2]; tr.nkeys = spec[4 * r + 3];
+        tr.time_at = time_at; tr.value_at = value_at;
+        const double first = times[time_at], last = times[time_at + tr.nkeys - 1];
+        if (r == 0 || first < *t0) *t0 = first;
+        if (r == 0 || last > *t1) *t1 = last;
+        time_at += tr.nkeys; value_at += (int64_t)mpt_anim_key_floats(tr.path, tr.interp, ntargets) * tr.nkeys;
+    }
+}
+
+// ------------------------------------------------------------------ a binding's local time
+// tau = (t - offset) * speed; with `loop` and t1 > t0 wrapped into the span: t0 + (x - floor(x / d) * d), x = tau - t0, d = t1 - t0.
+// Otherwise left as it is: each track clamps for itself
+MPT_HD double mpt_anim_local_time(double t, double offset, double speed, int loop, double t0, double t1) {
+    MPT_NO_CONTRACT
+    double tau = (t - offset) * speed;
+    if (loop && t1 > t0) {
+        const double x = tau - t0, d = t1 - t0;
+        tau = t0 + (x - std::floor(x / d) * d);
+    }
+    return tau;
+}
+
+// ------------------------------------------------------------------ a track at tau
+// Where tau lies among the key times T [nkeys].  Returns 0: at key *k itself (one key; tau at or before the first: key 0; at or behind
+// the last: key nkeys - 1; a tau that is not a number counts as before the first); 1: between keys *k and *k + 1, *k the largest
+// index with T[k] <= tau by binary search, *dt = T[k + 1] - T[k] and *u = (tau - T[k]) / dt
+MPT_HD int mpt_anim_key(const float *T, int nkeys, double tau, int *k, double *dt, double *u) {
+    MPT_NO_CONTRACT
+    *k = 0;
+    if (nkeys == 1 || !(tau > (double)T[0])) return 0;
+    if (tau >= (double)T[nkeys - 1]) { *k = nkeys - 1; return 0; }
+    int lo = 0, hi = nkeys - 1;                                   // T[lo] <= tau < T[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((double)T[mid] <= tau) lo = mid; else hi = mid;
+    }
+    *k = lo;
+    *dt = (double)T[lo + 1] - (double)T[lo];
+    *u = (tau - (double)T[lo]) / *dt;
+    return 1;
+}
+
+MPT_HD void mpt_anim_normalise4(double q[4]) {
+    MPT_NO_CONTRACT
+    const double len = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    for (int c = 0; c < 4; c++) q[c] = q[c] / len;
+}
+
+// LINEAR between the rotations a and b (xyzw, used as given): the shorter arc; nlerp above d = 0.9995, the slerp with acos and sin
+// -- the rule's only library functions -- below
+MPT_HD void mpt_anim_slerp(const double a[4], const double b_in[4], double u, double q[4]) {
+    MPT_NO_CONTRACT
+    double b[4] = { b_in[0], b_in[1], b_in[2], b_in[3] };
+    double d = ((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3];
+    if (d < 0.0) {
+        for (int c = 0; c < 4; c++) b[c] = -b[c];
+        d = -d;
+    }
+    if (d > 0.9995) {
+        for (int c = 0; c < 4; c++) q[c] = a[c] + u * (b[c] - a[c]);
+        mpt_anim_normalise4(q);
+        return;
+    }
+    const double theta = std::acos(d);
+    const double sa = std::sin((1.0 - u) * theta), sb = std::sin(u * theta), s = std::sin(theta);
+    for (int c = 0; c < 4; c++) q[c] = (sa * a[c] + sb * b[c]) / s;
+}
+
+// The C = mpt_anim_components values of track tr at tau, to out [C] (T, S, W: componentwise; R: a rotation xyzw).  times and values
+// are the arenas the track's time_at and value_at count in.
+//   at a key (mpt_anim_key 0), or STEP: the key's values
+//   LINEAR: v0 + u * (v1 - v0) per component; R: mpt_anim_slerp
+//   CUBICSPLINE, glTF's Hermite form with the tangents scaled by dt, b0 the out-tangent of key k and a1 the in-tangent of key k + 1:
+//       u2 = u * u, u3 = u2 * u
+//       h00 = (2 u3 - 3 u2) + 1,  h10 = (u3 - 2 u2) + u,  h01 = 3 u2 - 2 u3,  h11 = u3 - u2
+//       p = ((h00 * v0 + (h10 * dt) * b0) + h01 * v1) + (h11 * dt) * a1          per component; R: normalised
+MPT_HD void mpt_anim_sample(const MptAnimTrack &tr, const float *times, const float *values, int ntargets, double tau, double *out) {
+    MPT_NO_CONTRACT
+    const int C = mpt_anim_components(tr.path, ntargets);
+    const bool cubic = tr.interp == MPT_ANIM_CUBICSPLINE;
+    const int stride = cubic ? 3 * C : C;
+    int k;
+    double dt = 0.0, u = 0.0;
+    const int between = mpt_anim_key(times + tr.time_at, tr.nkeys, tau, &k, &dt, &u);
+    const float *v0 = values + tr.value_at + (int64_t)k * stride + (cubic ? C : 0);
+    if (!between || tr.interp == MPT_ANIM_STEP) {
+        for (int c = 0; c < C; c++) out[c] = (double)v0[c];
+        return;
+    }
+    const float *v1 = v0 + stride;
+    if (!cubic) {
+        if (tr.path != MPT_ANIM_R) {
+            for (int c = 0; c < C; c++) out[c] = (double)v0[c] + u * ((double)v1[c] - (double)v0[c]);
+            return;
+        }
+        const double a[4] = { v0[0], v0[1], v0[2], v0[3] }, b[4] = { v1[0], v1[1], v1[2], v1[3] };
+        double q[4];
+        mpt_anim_slerp(a, b, u, q);
+        for (int c = 0; c < 4; c++) out[c] = q[c];
+        return;
+    }
+    const float *b0 = v0 + C, *a1 = v1 - C;
+    const double u2 = u * u, u3 = u2 * u;
+    const double h00 = (2.0 * u3 - 3.0 * u2) + 1.0, h10 = (u3 - 2.0 * u2) + u, h01 = 3.0 * u2 - 2.0 * u3, h11 = u3 - u2;
+    const double g10 = h10 * dt, g11 = h11 * dt;
+    if (tr.path != MPT_ANIM_R) {
+        for (int c = 0; c < C; c++) out[c] = ((h00 * (double)v0[c] + g10 * (double)b0[c]) + h01 * (double)v1[c]) + g11 * (double)a1[c];
+        return;
+    }
+    double q[4];
+    for (int c = 0; c < 4; c++) q[c] = ((h00 * (double)v0[c] + g10 * (double)b0[c]) + h01 * (double)v1[c]) + g11 * (double)a1[c];
+    mpt_anim_normalise4(q);
+    for (int c = 0; c < 4; c++) out[c] = q[c];
+}
+
+// ------------------------------------------------------------------ a joint's local matrix, the hierarchy and the palette
+// [R(q) diag(s) | t] as 3x4 row-major of trs = translation3 rotation4 (x y z w) scale3
+MPT_HD void mpt_anim_local(const double *trs, double *M) {
+    MPT_NO_CONTRACT
+    const double x = trs[3], y = trs[4], z = trs[5], w = trs[6];
+    const double R[9] = { 1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w), 2.0 * (x * z + y * w),
+                          2.0 * (x * y + z * w), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w),
+                          2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y) };
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) M[4 * r + c] = R[3 * r + c] * trs[7 + c];
+        M[4 * r + 3] = trs[r];
+    }
+}
+
+// C = A . B of affine 3x4 matrices, the bottom rows 0 0 0 1 implied; C may be A or B
+MPT_HD void mpt_anim_mul(const double *A, const double *B, double *C) {
+    MPT_NO_CONTRACT
+    double out[12];
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) out[4 * r + c] = (A[4 * r] * B[c] + A[4 * r + 1] * B[4 + c]) + A[4 * r + 2] * B[8 + c];
+        out[4 * r + 3] = ((A[4 * r] * B[3] + A[4 * r + 1] * B[7]) + A[4 * r + 2] * B[11]) + A[4 * r + 3];
+    }
+    for (int k = 0; k < 12; k++) C[k] = out[k];
+}
+
+// The pose of an object at local time tau: pose [ntargets + 12 njoints], the layout deform.hip reads -- the morph weights (0 without
+// a W track), then palette[j] = global[j] . inverse_bind[j] with global[j] = local[j] for a root, else global[parent] . local[j], and
+// local[j] by mpt_anim_local of the joint's T, R and S: its track at tau, else its rest value.  Skeleton and clip have passed their
+// rules; tracks count their times and values from `times` and `values`
+inline void mpt_anim_pose(int njoints, int ntargets, const int32_t *parents, const double *rest, const double *inverse_bind, int ntracks,
+                          const MptAnimTrack *tracks, const float *times, const float *values, double tau, double *pose) {
+    std::vector<double> trs(rest, rest + (size_t)njoints * MPT_ANIM_REST), global((size_t)njoints * 12);
+    for (int t = 0; t < ntargets; t++) pose[t] = 0.0;
+    for (int r = 0; r < ntracks; r++) {
+        const MptAnimTrack &tr = tracks[r];
+        static const int at[3] = { 0, 3, 7 };
+        mpt_anim_sample(tr, times, values, ntargets, tau, tr.path == MPT_ANIM_W ? pose : trs.data() + (size_t)tr.target * MPT_ANIM_REST + at[tr.path]);
+    }
+    for (int j = 0; j < njoints; j++) {
+        double *G = global.data() + (size_t)j * 12;
+        mpt_anim_local(trs.data() + (size_t)j * MPT_ANIM_REST, G);
+        if (parents[j] >= 0) mpt_anim_mul(global.data() + (size_t)parents[j] * 12, G, G);
+        mpt_anim_mul(G, inverse_bind + (size_t)j * 12, pose + ntargets + (size_t)j * 12);
+    }
+}

@@ -9,6 +9,7 @@
 #include "refit_rule.h"
 #include "run_table.h"
 #include "deform_rule.h"
+#include "anim_rule.h"
 #include "subdiv_rule.h"
 #include "displace_rule.h"
 #include "scatter_rule.h"
@@ -106,6 +107,11 @@ MPT_KERNEL_API size_t mpt_compose_groups(size_t nverts);
 MPT_KERNEL_API hipError_t mpt_launch_compose(const float *pool, const MptComposeObj *objs, const int *first, int nobj, int nverts,
                                              const MptRun *runs, int nruns, int blocks, int all, unsigned epoch, float *out,
                                              int *mtlids, float *part, float *bounds_host, hipStream_t);
+// anim.hip: the poses of a launch's bound objects at scene time t, written where deform.hip reads them; the door of its acos and sin
+MPT_KERNEL_API hipError_t mpt_launch_anim(const MptAnimObj *objs, int nobj, double t, const int32_t *parents, const int32_t *depths, const double *rest,
+                                          const double *inverse_bind, const MptAnimTrack *tracks, const float *times, const float *values, double *pose,
+                                          hipStream_t stream);
+MPT_KERNEL_API hipError_t mpt_launch_anim_trig(const double *x, int n, double *acos_out, double *sin_out, hipStream_t stream);
 // deform.hip: the deformed copies of the objects of a launch's table, written into the pool the meshes lie in (mpt_compose)
 MPT_KERNEL_API hipError_t mpt_launch_deform(float *pool, const MptDeformObj *objs, const MptRun *runs, int nruns, int blocks,
                                             const float *deltas, const uint16_t *joints, const float *weights, const double *pose,
@@ -449,6 +455,17 @@ struct MPT_INTERNAL MptDeformBufs {
     int reserve_tables(size_t nobj) { return objs.reserve(nobj) || runs.reserve(nobj); }
 };
 
+// Keyframe animation's device memory (scene_anim.cpp): the arenas of the meshes' skeletons and clips, appended by mpt_mesh_set_skeleton /
+// mpt_mesh_add_clip (they grow by copying, as the mesh pool does), and a launch's table
+struct MPT_INTERNAL MptAnimBufs {
+    DevBuf<int32_t> parents, depths;     // per joint of every skeleton, back to back: its parent within the skeleton (-1: a root), its depth
+    DevBuf<double> rest;                 // [joint][10]: translation3 rotation4 scale3
+    DevBuf<double> inverse_bind;         // [joint][12]
+    DevBuf<MptAnimTrack> tracks;         // every clip's tracks, back to back (time_at / value_at count in the arenas below)
+    DevBuf<float> times, values;         // the tracks' key times and values
+    DevBuf<MptAnimObj> objs;             // a launch's objects
+};
+
 // Loop subdivision's device memory (scene_subdiv.cpp): the arena of the meshes' topology blocks, appended by mpt_mesh_set_subdivision
 // (it grows by copying, as the mesh pool does), the jobs' f64 workspace and a launch's tables
 struct MPT_INTERNAL MptSubdivBufs {
@@ -737,7 +754,10 @@ struct mpt_ctx {
     } adapt{events};
     // The scene side's two host tables, both Compose's (below): a row per mesh of the pool, which mpt_mesh_add alone adds, and a row per
     // object beside the device's record of it, which add_object (scene_compose.cpp) alone adds.  mpt_scene_clear clears both
-    struct MptDeformMesh { int ntargets = 0, njoints = 0; size_t delta_at = 0, skin_at = 0; };   // what mesh deformation keeps for a mesh (arena offsets)
+    struct MptDeformMesh {                               // what mesh deformation keeps for a mesh (arena offsets)
+        int ntargets = 0, njoints = 0; size_t delta_at = 0, skin_at = 0;
+        bool skeleton = false; size_t joint_at = 0; int levels = 0;   // its skeleton (scene_anim.cpp): first joint in the arenas, the greatest depth of a joint
+    };
     struct MptSubdivMesh {                               // what Loop subdivision keeps for a mesh: its level and where its topology lies
         MptSubdivHead head;                              // its block's header (subdiv_rule.h; levels 0: no subdivision), with srule_at = nrule_at where the mesh is uncreased: the records' rules are then the rings'
         size_t topo_at = 0;                              // the block's first word in bufs.topo
@@ -792,6 +812,8 @@ struct mpt_ctx {
         std::vector<double> pose;                        // ntargets weights, then njoints x 12: the layout of bufs.pose
         size_t pose_at = 0; long long copy_vert = -1;    // where they lie on the device (copy_vert -1: no room assigned yet)
         bool dirty = true;                               // the pose changed since the copy was written
+        int clip = -1;                                   // the clip it is bound to (scene_anim.cpp; -1: none, the pose above goes up): the device evaluates its pose
+        double offset = 0.0, speed = 1.0; int loop = 1;  // ... and the binding
     };
     struct MPT_INTERNAL Deform {                         // mesh deformation (scene_deform.cpp: mpt_mesh_set_*, mpt_object_set_*, deform_step)
         std::vector<MptDeformPose> poses;
@@ -804,6 +826,18 @@ struct mpt_ctx {
         MptLaunchTimer timer;                            // mpt_compose: {before the deform kernel, after it} per launch
         explicit Deform(MptEventPool &ev) : timer(2, ev) {}
     } deform{events};
+    struct MptAnimClip { int mesh = 0, ntracks = 0; size_t track_at = 0; double t0 = 0.0, t1 = 0.0; };   // a clip: its mesh, its tracks in the arena, its span
+    struct MPT_INTERNAL Anim {                           // keyframe animation (scene_anim.cpp: mpt_mesh_set_skeleton, mpt_mesh_add_clip, mpt_object_set_animation, mpt_scene_set_time, anim_step)
+        std::vector<MptAnimClip> clips;
+        size_t joints_used = 0, tracks_used = 0, times_used = 0, values_used = 0;   // elements of the arenas
+        int skeletons = 0;
+        double time = 0.0;                               // the scene's time
+        std::vector<MptAnimObj> h_objs;                  // the last launch's table as uploaded: it outlives the copy that reads it
+        MptAnimBufs bufs;
+        mpt_anim_info stats{};
+        MptLaunchTimer timer;                            // mpt_compose: {before the anim kernel, after it} per launch
+        explicit Anim(MptEventPool &ev) : timer(2, ev) {}
+    } anim{events};
     struct MptSubdivCopy {                               // a subdivided copy: of a mesh that is not deformable, or of one object of a mesh that is
         int mesh = 0, obj = -1;                          // obj -1: shared by the mesh's objects
         long long copy_vert = -1; size_t work_at = 0;    // where the copy and its workspace lie (copy_vert -1: no room assigned yet)
@@ -1028,6 +1062,10 @@ inline int lay_copies(mpt_ctx *c, mpt_ctx::MptCopyRoom &room, Copies &copies, si
 MPT_INTERNAL void deform_object_added(mpt_ctx *c, int obj_id);   // (called by add_object alone, as subdiv_object_added behind it)
 MPT_INTERNAL void deform_scene_cleared(mpt_ctx *c, int meshes);
 MPT_INTERNAL int deform_step(mpt_ctx *c);                        // before compose_kernel: room, poses, the deform launch; rewrites objs' mesh_vert at a relayout
+
+// scene_anim.cpp: what mpt_scene_clear tells keyframe animation, and what deform_step asks of it
+MPT_INTERNAL void anim_scene_cleared(mpt_ctx *c, int meshes);    // the bindings go with the poses (scene_deform.cpp); skeletons and clips go with the meshes
+MPT_INTERNAL int anim_step(mpt_ctx *c, const std::vector<int> &poses);   // inside deform_step, before the deform launch: evaluates these rows of deform.poses (bound objects) on the device
 
 // scene_subdiv.cpp: what scene_compose.cpp and scene_deform.cpp tell the subdivision table, and the step of mpt_compose behind deform_step
 MPT_INTERNAL int subdiv_object_faces(const mpt_ctx *c, int mesh_id);   // the faces an object of this mesh has: k * 4^L (Catmull-Clark: 2 quads' worth per quad of level L)

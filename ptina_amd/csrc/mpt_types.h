@@ -254,6 +254,26 @@ struct MptDeformObj {                       // 48 bytes
     int64_t pose_at;                         // the object's pose: ntargets weights, then njoints 3x4 matrices, f64: first double
 };
 
+// keyframe animation (anim.hip, anim_rule.h): a track of a clip as the arenas hold it, and one bound object of a launch -- where its
+// mesh's skeleton, its clip's tracks and its own pose lie in their arenas, and its binding
+enum { MPT_ANIM_T = 0, MPT_ANIM_R = 1, MPT_ANIM_S = 2, MPT_ANIM_W = 3 };            // a track's path: translation, rotation, scale, morph weights
+enum { MPT_ANIM_STEP = 0, MPT_ANIM_LINEAR = 1, MPT_ANIM_CUBICSPLINE = 2 };          // ... and its interpolation
+#define MPT_ANIM_REST 10                    // doubles of a joint's rest pose: translation3 rotation4 (xyzw) scale3
+struct MptAnimTrack {                       // 32 bytes
+    int32_t target, path, interp, nkeys;     // the joint (-1: the morph weights), MPT_ANIM_T .. _W, MPT_ANIM_STEP .. _CUBICSPLINE, keys >= 1
+    int64_t time_at;                         // its key times [nkeys] f32: first float in the arena of times
+    int64_t value_at;                        // its values [nkeys][C] f32 (CUBICSPLINE: [nkeys][3][C], in-tangent value out-tangent): first float
+};
+struct MptAnimObj {                         // 80 bytes
+    int32_t njoints, ntargets;               // of its mesh (0: no skeleton / no targets)
+    int32_t ntracks, loop;                   // of its clip; of its binding
+    int32_t levels, pad;                     // the greatest depth of a joint of the skeleton (a root: 0)
+    int64_t joint_at;                        // the skeleton: first joint in the arenas of parents, depths, rest poses [.][10] and inverse binds [.][12]
+    int64_t track_at;                        // the clip: first track in the arena of tracks
+    int64_t pose_at;                         // the object's pose (MptDeformObj::pose_at): what the kernel writes
+    double offset, speed, t0, t1;            // the binding, and the clip's span
+};
+
 // Loop subdivision (subdiv.hip): the caps, the kinds of a vertex rule (subdiv_rule.h), one job of a launch -- a subdivided copy: where
 // its control records and the copy lie in the pool, where its mesh's topology block lies in the arena of words and its own f64
 // vertices in the workspace

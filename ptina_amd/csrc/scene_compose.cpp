@@ -145,6 +145,7 @@ extern "C" int mpt_scene_clear(mpt_ctx *c, int meshes) {
     cp.relayout = true;
     if (meshes) { cp.meshes.clear(); cp.pool_verts = 0; }
     deform_scene_cleared(c, meshes);
+    anim_scene_cleared(c, meshes);
     subdiv_scene_cleared(c, meshes);
     scatter_scene_cleared(c);
     return 0;

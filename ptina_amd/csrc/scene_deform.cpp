@@ -98,6 +98,7 @@ extern "C" int mpt_object_set_morph_weights(mpt_ctx *c, int obj_id, const double
     if (T == 0) return fail("mpt_object_set_morph_weights: the mesh of object %d has no morph targets", obj_id);
     if (n != T) return fail("mpt_object_set_morph_weights: n %d, the mesh of object %d has %d morph targets", n, obj_id, T);
     if (!w) return fail("mpt_object_set_morph_weights: null w");
+    if (p->clip >= 0) return fail("mpt_object_set_morph_weights: object %d is bound to clip %d, which gives its pose: unbind it first (mpt_object_set_animation with clip -1)", obj_id, p->clip);
     for (int t = 0; t < T; t++)
         if (!std::isfinite(w[t])) return fail("mpt_object_set_morph_weights: w[%d] is not finite", t);
     memcpy(p->pose.data(), w, (size_t)T * sizeof(double));
@@ -115,6 +116,7 @@ extern "C" int mpt_object_set_joints(mpt_ctx *c, int obj_id, const double *mats,
     if (nj == 0) return fail("mpt_object_set_joints: the mesh of object %d has no skin", obj_id);
     if (n != nj) return fail("mpt_object_set_joints: n %d, the skin of the mesh of object %d has %d joints", n, obj_id, nj);
     if (!mats) return fail("mpt_object_set_joints: null mats");
+    if (p->clip >= 0) return fail("mpt_object_set_joints: object %d is bound to clip %d, which gives its pose: unbind it first (mpt_object_set_animation with clip -1)", obj_id, p->clip);
     static const double bottom[4] = { 0, 0, 0, 1 };
     for (int j = 0; j < nj; j++) {
         for (int k = 0; k < 16; k++)
@@ -135,9 +137,12 @@ extern "C" int mpt_object_set_joints(mpt_ctx *c, int obj_id, const double *mats,
 // objects' mesh_vert is pointed at them -- mpt_compose then uploads the whole table -- and every deformable object is deformed;
 // else the objects whose pose changed.  Nothing here waits for the device: the uploads read the poses and the tables the context
 // keeps (h_objs, h_runs), which are next written by the next call, behind mpt_compose's closing synchronise.
+// An object bound to a clip (scene_anim.cpp) has no pose to upload: anim_step evaluates the poses of all such objects on the device,
+// in one launch between the uploads and the deform kernel.
 int deform_step(mpt_ctx *c) {
     auto &cp = c->compose;
     auto &df = c->deform;
+    c->anim.stats.evaluated_objects = 0;
     df.stats.deformed_objects = df.stats.deformed_corners = 0;
     df.stats.deformable_objects = (int64_t)df.poses.size();
     const int np = (int)df.poses.size();
@@ -172,13 +177,16 @@ int deform_step(mpt_ctx *c) {
     int blocks = 0;
     const int nruns = mpt_run_plan_into(corners.data(), dirty.data(), np, MPT_DEFORM_CHUNK, df.h_runs.data(), &blocks);
     if (nruns < 0) return fail("too many corners to deform");
+    std::vector<int> bound;
     for (int k = 0; k < np; k++) {
         auto &p = df.poses[k];
         if (!dirty[k]) continue;
         df.stats.deformed_objects++; df.stats.deformed_corners += corners[k];
+        if (p.clip >= 0) { bound.push_back(k); continue; }
         if (!p.pose.empty())
             HIP_TRY(hipMemcpyAsync(df.bufs.pose + p.pose_at, p.pose.data(), p.pose.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
+    if (!bound.empty() && anim_step(c, bound)) return 1;
     if (nruns > 0) {
         HIP_TRY(hipMemcpyAsync(df.bufs.objs, table.data(), (size_t)np * sizeof(MptDeformObj), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(df.bufs.runs, df.h_runs.data(), (size_t)nruns * sizeof(MptRun), hipMemcpyHostToDevice, c->stream));

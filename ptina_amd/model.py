@@ -13,7 +13,7 @@ import ctypes as C
 
 from .common import *                 # noqa: F401,F403
 from .common import Singleton, register, ctx, np
-from ._lib import fptr, iptr, ComposeInfo, DeformInfo, SubdivInfo, DisplaceInfo, DEFORM_MAX_JOINTS, DEFORM_MAX_TARGETS, SUBDIV_MAX_LEVELS
+from ._lib import fptr, iptr, ComposeInfo, DeformInfo, AnimInfo, SubdivInfo, DisplaceInfo, DEFORM_MAX_JOINTS, DEFORM_MAX_TARGETS, SUBDIV_MAX_LEVELS
 from ._lib import SUBDIV_SCHEMES, DISPLACE_MODES, DISPLACE_CHANNELS, ScatterInfo, ScatterSpacingInfo, SCATTER_POINT_DTYPE, scatter_params, scatter_spacing
 
 
@@ -32,6 +32,7 @@ class ModelPool(metaclass=Singleton):
         self._obj_mesh = []              # the mesh of every object of the device's table
         self._sum = (None, 0, 0)         # (that list, how many of its objects are counted, their faces): _faces_of_objects
         self._scatters = []              # per scatter: its surface, its mesh, its range of objects, its seed and parameters
+        self._mesh_pose = {}             # mesh -> (morph targets, joints of its skin), where it is deformable: the shape of an object's pose
 
     @property
     def nfaces(self):
@@ -121,7 +122,7 @@ class ModelPool(metaclass=Singleton):
         '''drop the objects and the meshes'''
         ctx().call('mpt_scene_clear', 1)
         self._obj_mesh, self._mesh_faces, self._mesh_levels, self._mesh_displace, self._scatters = [], [], {}, {}, []
-        self._mesh_corners = {}
+        self._mesh_corners, self._mesh_pose = {}, {}
 
     def compose(self):
         '''write the objects, in order, as the model BVHTree().build() reads -- on the device; what load(*compose_multiple_meshes(...))
@@ -156,6 +157,7 @@ class ModelPool(metaclass=Singleton):
             raise ValueError('%d morph targets: between 1 and %d' % (T, DEFORM_MAX_TARGETS))
         rec = np.ascontiguousarray(np.concatenate([dp.reshape(T, k * 3, 3), dn.reshape(T, k * 3, 3)], axis=2), np.float32)
         ctx().call('mpt_mesh_set_morph', mesh, fptr(rec), T)
+        self._mesh_pose[mesh] = (T, self._mesh_pose.get(mesh, (0, 0))[1])
 
     def add_skin(self, mesh, joints, weights, njoints=None):
         '''a skin for a mesh that has no object yet: joint indices (any integer type) and weights [k,3,4] per face corner, over
@@ -178,6 +180,7 @@ class ModelPool(metaclass=Singleton):
         j = np.ascontiguousarray(joints.reshape(k * 3, 4), np.uint16)
         w = np.ascontiguousarray(weights.reshape(k * 3, 4), np.float32)
         ctx().call('mpt_mesh_set_skin', mesh, j.ctypes.data_as(C.POINTER(C.c_uint16)), fptr(w), njoints)
+        self._mesh_pose[mesh] = (self._mesh_pose.get(mesh, (0, 0))[0], njoints)
 
     def set_morph_weights(self, obj, w):
         '''the morph weights [T] of an object; the next compose() deforms and rewrites this object only'''
@@ -210,6 +213,69 @@ class ModelPool(metaclass=Singleton):
         '''_lib.DeformInfo: deformable objects, objects and corners the last compose() deformed, pool vertices the copies hold'''
         info = DeformInfo()
         ctx().call('mpt_deform_stats', C.byref(info))
+        return info
+
+    # ---- keyframe animation on the device: glTF 2.0's animations, evaluated where the poses lie (csrc/anim.hip, DESIGN.md section
+    #      3.17.1; no reference counterpart).  tools/anim.py writes clips by hand; reading them from files is not part of it
+    def add_skeleton(self, mesh, parents, rest_translation, rest_rotation, rest_scale, inverse_bind):
+        '''the skeleton of a skinned mesh that has no object yet, behind add_skin: parents [nj] (-1: a root; parents come before their
+        children), the joints' rest pose -- translations [nj,3], rotations [nj,4] as x y z w, scales [nj,3] -- and the skin's inverse
+        bind matrices [nj,4,4] (affine) or [nj,3,4], all f64'''
+        mesh = self._fresh_mesh(mesh)
+        parents = np.asarray(parents)
+        if parents.ndim != 1 or (parents.size and not np.issubdtype(parents.dtype, np.integer)):
+            raise ValueError('parents must be [nj] integers, got %s of %s' % (parents.shape, parents.dtype))
+        nj = int(parents.size)
+        t, r, sc = (np.asarray(a, np.float64) for a in (rest_translation, rest_rotation, rest_scale))
+        if t.shape != (nj, 3) or r.shape != (nj, 4) or sc.shape != (nj, 3):
+            raise ValueError('the rest pose must be [%d,3], [%d,4] and [%d,3], got %s, %s and %s' % (nj, nj, nj, t.shape, r.shape, sc.shape))
+        ib = np.asarray(inverse_bind, np.float64)
+        if ib.shape == (nj, 4, 4):
+            if not np.array_equal(ib[:, 3], np.tile([0.0, 0.0, 0.0, 1.0], (nj, 1))):
+                raise ValueError('the bottom row of an inverse_bind matrix is not 0 0 0 1 (not affine)')
+            ib = ib[:, :3]
+        if ib.shape != (nj, 3, 4):
+            raise ValueError('inverse_bind must be [%d,4,4] or [%d,3,4], got %s' % (nj, nj, ib.shape))
+        rest = np.ascontiguousarray(np.concatenate([t, r, sc], axis=1))
+        ib = np.ascontiguousarray(ib)
+        dp = C.POINTER(C.c_double)
+        ctx().call('mpt_mesh_set_skeleton', mesh, nj, iptr(np.ascontiguousarray(parents, np.int32)), rest.ctypes.data_as(dp), ib.ctypes.data_as(dp))
+
+    def add_clip(self, mesh, tracks):
+        '''a clip for a deformable mesh that has no object yet (a skinned one: behind add_skeleton): a list of tools.anim.track(...)
+        -- at most one per (target, path).  Returns the clip id, which counts over all meshes'''
+        from .tools.anim import pack_clip
+        mesh = self._fresh_mesh(mesh)
+        spec, times, values = pack_clip(tracks)
+        clip = C.c_int(-1)
+        ctx().call('mpt_mesh_add_clip', mesh, spec.shape[0], iptr(spec), fptr(times), times.size, fptr(values), values.size, C.byref(clip))
+        return clip.value
+
+    def set_animation(self, obj, clip, offset=0.0, speed=1.0, loop=True):
+        '''bind an object to a clip of its mesh: at scene time t it is posed at the clip's time (t - offset) * speed, wrapped into the
+        clip's span if loop, else clamped track by track.  clip=None unbinds: the pose is again what set_joints / set_morph_weights
+        last gave (which refuse a bound object).  The next compose() poses, deforms and rewrites this object'''
+        obj = self._object(obj)
+        ctx().call('mpt_object_set_animation', obj, -1 if clip is None else int(clip), float(offset), float(speed), int(bool(loop)))
+
+    def set_time(self, t):
+        '''the scene's time: the next compose() poses every bound object there, in one launch on the device; the same time again
+        changes nothing'''
+        ctx().call('mpt_scene_set_time', float(t))
+
+    def pose_to_numpy(self, obj):
+        '''(weights [T], palette [nj,3,4]) f64: a deformable object's pose as it lies on the device after the last compose(), bound
+        to a clip or not'''
+        obj = self._object(obj)
+        T, nj = self._mesh_pose.get(self._obj_mesh[obj], (0, 0))
+        pose = np.zeros(max(T + 12 * nj, 1), np.float64)
+        ctx().call('mpt_get_pose', obj, pose.ctypes.data_as(C.POINTER(C.c_double)), T + 12 * nj)
+        return pose[:T].copy(), pose[T:T + 12 * nj].reshape(nj, 3, 4).copy()
+
+    def anim_stats(self):
+        '''_lib.AnimInfo: skeletons, clips and tracks of the scene, bound objects, objects the last compose() posed on the device'''
+        info = AnimInfo()
+        ctx().call('mpt_anim_stats', C.byref(info))
         return info
 
     # ---- Loop subdivision on the device, behind the deformation (csrc/subdiv.hip, DESIGN.md section 3.19; the reference's add-on

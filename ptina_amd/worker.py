@@ -28,6 +28,10 @@ _PASS_THROUGH = {
     'set_object_world': ('ModelPool', 'set_world', ('obj', 'world')),
     'set_object_morph_weights': ('ModelPool', 'set_morph_weights', ('obj', 'w')),
     'set_object_joints': ('ModelPool', 'set_joints', ('obj', 'mats')),
+    'set_mesh_skeleton': ('ModelPool', 'add_skeleton', ('mesh', 'parents', 'rest_translation', 'rest_rotation', 'rest_scale', 'inverse_bind')),
+    'add_mesh_clip': ('ModelPool', 'add_clip', ('mesh', 'tracks')),
+    'set_object_animation': ('ModelPool', 'set_animation', ('obj', 'clip', ('offset', 0.0), ('speed', 1.0), ('loop', True))),
+    'set_scene_time': ('ModelPool', 'set_time', ('t',)),
     'set_mesh_subdivision': ('ModelPool', 'add_subdivision', ('mesh', 'levels', ('creases', None), ('corners', None), ('scheme', 'loop'), ('polys', None))),
     'set_mesh_displacement': ('ModelPool', 'add_displacement', ('mesh', 'image', ('strength', 1.0), ('midlevel', 0.5), ('mode', 'normal'), ('channel', 'mean'))),
     'set_mesh_displacement_params': ('ModelPool', 'set_displacement', ('mesh', 'strength', ('midlevel', None))),
