@@ -6,7 +6,11 @@ all bound to one clip at different offsets, the scene kept on the device.  Skele
 so nothing but the time crosses to the device: every object's pose is evaluated there (csrc/anim.hip), in one launch, the corners
 are skinned there (csrc/deform.hip), the faces composed again and the built tree fitted to them (csrc/refit.hip).
 
-    python exams/crowd_amd.py [--objects 24] [--frames 12] [--size 256] [--spp 8] [--out DIR]
+    python exams/crowd_amd.py [--objects 24] [--frames 12] [--size 256] [--spp 8] [--out DIR] [--blend]
+
+--blend: every object gets a second clip -- a faster, wider sway: the walk turns into a run -- blended in by
+a cross-fade whose start is staggered over the crowd, and a few rigid props circle above it on object clips (set_motion).  Still
+nothing but the time crosses to the device.
 '''
 import argparse
 import os
@@ -27,6 +31,7 @@ ap.add_argument('--frames', type=int, default=12)
 ap.add_argument('--size', type=int, default=256)
 ap.add_argument('--spp', type=int, default=8)
 ap.add_argument('--out', default='.')
+ap.add_argument('--blend', action='store_true', help='cross-fade every object from the walk to a run, staggered; rigid props on object clips')
 args = ap.parse_args()
 
 JOINTS, HEIGHT, RADIUS, RINGS, SIDES, PERIOD = 8, 0.9, 0.05, 24, 12, 2.0
@@ -89,12 +94,26 @@ tracks = [track(j, 'R', times, [quaternion([0, 0, 1], 1.2 * np.sin(a) / JOINTS) 
 tracks.append(track(0, 'T', times, np.stack([0 * times, 0.08 * np.abs(np.sin(phase)), 0 * times], axis=1)))
 tracks.append(track(None, 'W', times, (0.5 - 0.5 * np.cos(phase))[:, None]))
 clip = pool.add_clip(mesh, tracks)
+if args.blend:                                     # the run: half the period, twice the sway, a higher hop
+    fast = np.linspace(0.0, 0.5 * PERIOD, 17)
+    run = [track(j, 'R', fast, [quaternion([0, 0, 1], 2.4 * np.sin(a) / JOINTS) for a in phase]) for j in range(JOINTS)]
+    run.append(track(0, 'T', fast, np.stack([0 * fast, 0.16 * np.abs(np.sin(phase)), 0 * fast], axis=1)))
+    run_clip = pool.add_clip(mesh, run)
 g = np.random.default_rng(1)
 side = int(np.ceil(np.sqrt(args.objects)))
 for o in range(args.objects):
     x, z = (o % side + 0.5) / side, (o // side + 0.5) / side
     obj = pool.add_object(mesh, shift(-0.8 + 1.6 * x, 0.0, -0.9 + 1.4 * z), 3)
     pool.set_animation(obj, clip, offset=g.uniform(0.0, PERIOD), speed=g.uniform(0.8, 1.25))
+    if args.blend:                                 # the fade runs across the crowd: the first object starts at once, the last at half the period
+        pool.set_animation_blend(obj, run_clip, offset=g.uniform(0.0, PERIOD), weight=(0.0, 1.0), fade=(0.5 * PERIOD * o / args.objects, 0.4 * PERIOD))
+if args.blend:
+    prop = pool.add_mesh(0.06 * (p - [0, 0.5 * HEIGHT, 0]) / RADIUS * [1, RADIUS / HEIGHT, 1], n)      # the tube squashed to a drum
+    turn = [quaternion([0, 1, 0], a) for a in phase]
+    for k in range(4):
+        orbit = pool.add_object_clip([track(0, 'R', times, turn), track(0, 'T', times, np.stack([0 * times, 0.05 * np.sin(phase + k), 0 * times], axis=1))])
+        pool.set_motion(pool.add_object(prop, np.eye(4), 1 + k % 2), orbit, offset=0.25 * k * PERIOD,
+                        base=shift(0, 1.2, -0.2) @ shift(*(0.45 * np.array([np.cos(1.57 * k), 0, np.sin(1.57 * k)]))))
 pool.compose()
 BVHTree().build()
 
@@ -109,9 +128,9 @@ for f in range(args.frames):
     PathEngine().render(args.spp)
     img = FilmTable().get_display(layout='display')
     write_png(os.path.join(args.out, 'crowd_%03d.png' % f), img)
-    a, d, c = pool.anim_stats(), pool.deform_stats(), pool.compose_stats()
-    print('frame %d: %d objects posed on the device, %d corners deformed, %d of %d faces recomposed, mean byte %.2f'
-          % (f, a.evaluated_objects, d.deformed_corners, c.recomposed, c.faces, float(img[..., :3].mean())))
+    a, d, c, b = pool.anim_stats(), pool.deform_stats(), pool.compose_stats(), pool.anim_blend_stats()
+    print('frame %d: %d objects posed on the device (%d blended), %d moved there, %d corners deformed, %d of %d faces recomposed, mean byte %.2f'
+          % (f, a.evaluated_objects, b.evaluated_blended, b.evaluated_moved, d.deformed_corners, c.recomposed, c.faces, float(img[..., :3].mean())))
 dt = time.perf_counter() - t0
 print('%d frames of %dx%d at %d spp in %.2f s (PNG writing included), %d refitted: written to %s'
       % (args.frames, args.size, args.size, args.spp, dt, refitted, args.out))

@@ -658,6 +658,61 @@ int mpt_clip_check(int njoints, int ntargets, int ntracks, const int32_t *tracks
                    int64_t nvalues, char *why, int why_size);
 int mpt_anim_trig(mpt_ctx *ctx, const double *x, int n, double *acos_out, double *sin_out);
 
+/* Two clips blended, and objects moved by clips (the rule stands once in csrc/anim_rule.h, f64 in one written
+ * order without contraction, and adds no library call to the slerp's acos and sin).
+ *   A SECOND BINDING of a bound deformable object: (clip_b, offset, speed, loop, w0, w1, fade_start, fade_duration); clip_b a clip of the
+ *     object's mesh, offset, speed and fade_start finite, fade_duration finite and >= 0, w0 and w1 in [0, 1].  The weight at SCENE time t:
+ *     with fade_duration > 0, x = (t - fade_start) / fade_duration, s = 0 below 0, 1 above 1, else x; with fade_duration == 0, s = 1 from
+ *     fade_start on, else 0; s == 0: w = w0 itself, s == 1: w = w1 itself, else w = w0 + s (w1 - w0).  A constant weight is w0 = w1.
+ *     Each clip has its own local time, from its own binding and span.  Every joint's T, R, S and the morph weights are evaluated for both
+ *     clips (a from A, b from B; without a track the rest value, 0 for the weights).  w == 0: a, bit for bit; w == 1: b, bit for bit; else
+ *     T, S, W: a + w (b - a) per component; R the normalised lerp over the shorter arc: d = ((a0 b0 + a1 b1) + a2 b2) + a3 b3; d < 0:
+ *     b = -b; q = a + w (b - a); q / |q|.  Then local matrices, hierarchy and palette as for one clip.
+ *   An OBJECT CLIP has no mesh: its tracks name target 0, the object's node, on the paths T, R and S (a W track is refused); clip ids
+ *     count on in the scene's one list.  A MOTION BINDING of an object -- any object that is not an instance of a scatter -- holds (clip,
+ *     offset, speed, loop, rest [10], base [16]): rest translation3 rotation4 xyzw scale3, finite with a rotation that is not zero (NULL:
+ *     0 0 0, 0 0 0 1, 1 1 1); base a finite row-major 4x4, the node's static parents (NULL: the identity).  trs = rest, overwritten by the
+ *     clip's tracks at the local time; L = local(trs), 3x4; world = base . [L; 0 0 0 1], every row r of the four by
+ *     W[r][c] = (B[r][0] L[0][c] + B[r][1] L[1][c]) + B[r][2] L[2][c], c < 3, and W[r][3] = ((B[r][0] L[0][3] + B[r][1] L[1][3]) + B[r][2] L[2][3]) + B[r][3].
+ * mpt_object_set_animation_blend: the second binding of an object that mpt_object_set_animation has bound; clip_b -1 removes it;
+ *   mpt_object_set_animation with clip -1 removes both, and binding A again leaves B.  Refuses an unbound object, an object clip, a clip
+ *   of another mesh, w0 or w1 outside [0, 1], a negative duration, a value that is not finite.  Blended objects are evaluated in the same
+ *   one launch as the others.
+ * mpt_scene_add_object_clip: at any time; the clips go with mpt_scene_clear(1), every binding with any mpt_scene_clear.
+ * mpt_object_set_motion: binds; clip -1 unbinds, and the object returns to the matrix mpt_object_add / mpt_object_set_world last gave.
+ *   While an object is bound mpt_object_set_world refuses it (unbind first).  Refuses an instance of a scatter, a mesh's clip (and
+ *   mpt_object_set_animation refuses an object clip), a value that is not finite, a zero rest rotation.  mpt_scene_set_time marks the
+ *   bound objects; mpt_compose evaluates the marked ones, those whose row goes up for another reason, and after a change of layout all,
+ *   in one launch of a lane per object behind the table's upload and in front of the scatters and the composition.  The same time again
+ *   marks nothing.
+ * mpt_get_object_world: an object's matrix [16] as it lies on the device after the last mpt_compose, moved or not; refuses before it.
+ * mpt_anim_blend_stats: object clips; objects with a second binding; objects with a motion binding; how many of each the last
+ *   mpt_compose evaluated.  mpt_motion_kernel_time: as mpt_anim_kernel_time, of the motion kernel.
+ * mpt_anim_blend_rule / mpt_motion_rule: the whole evaluation of one blended pose / one world matrix at scene time t as pure functions
+ *   (no context, no GPU).  They return 0; 201 for bad arrays; 100 + mpt_clip_check's verdict of clip A (of the object clip, checked as a
+ *   clip of one joint and no targets); 300 + that of clip B; 200 + the skeleton's; 400 + the second binding's (1 a value not finite,
+ *   2 a negative duration, 3 a weight outside [0, 1]); 500 + the motion binding's (1 rest not finite, 2 a zero rest rotation, 3 base not
+ *   finite, 4 offset or speed not finite). */
+typedef struct {
+    int64_t object_clips, blended_objects, moved_objects, evaluated_blended, evaluated_moved;
+} mpt_anim_blend_info;
+int mpt_object_set_animation_blend(mpt_ctx *ctx, int obj_id, int clip_b, double offset, double speed, int loop, double w0, double w1,
+                                   double fade_start, double fade_duration);
+int mpt_scene_add_object_clip(mpt_ctx *ctx, int ntracks, const int32_t *tracks /* [ntracks][4] */, const float *times, int64_t ntimes,
+                              const float *values, int64_t nvalues, int *clip_id);
+int mpt_object_set_motion(mpt_ctx *ctx, int obj_id, int clip_id, double offset, double speed, int loop, const double *rest /* [10] or NULL */,
+                          const double *base /* [16] or NULL */);
+int mpt_get_object_world(mpt_ctx *ctx, int obj_id, double *world /* [16] */);
+int mpt_anim_blend_stats(mpt_ctx *ctx, mpt_anim_blend_info *out);
+int mpt_motion_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
+int mpt_anim_blend_rule(int njoints, int ntargets, const int32_t *parents, const double *rest, const double *inverse_bind, int ntracks_a,
+                        const int32_t *tracks_a, const float *times_a, int64_t ntimes_a, const float *values_a, int64_t nvalues_a, double offset_a,
+                        double speed_a, int loop_a, int ntracks_b, const int32_t *tracks_b, const float *times_b, int64_t ntimes_b,
+                        const float *values_b, int64_t nvalues_b, double offset_b, double speed_b, int loop_b, double w0, double w1,
+                        double fade_start, double fade_duration, double t, double *pose /* [ntargets + 12 njoints] */);
+int mpt_motion_rule(int ntracks, const int32_t *tracks, const float *times, int64_t ntimes, const float *values, int64_t nvalues, double offset,
+                    double speed, int loop, const double *rest, const double *base, double t, double *world /* [16] */);
+
 /* Loop subdivision on the device (triangles in, four triangles out per level) as a property of a mesh of the pool, evaluated inside
  * mpt_compose behind morph targets and skinning and before composition, so that a pose change of a subdivided character costs the
  * upload of the pose, the deform kernel, L + 2 kernels over that object, the partial mpt_compose and mpt_refit_tree: topology and face

@@ -93,6 +93,12 @@ class AnimInfo(C.Structure):
     _fields_ = [('skeletons', C.c_int64), ('clips', C.c_int64), ('tracks', C.c_int64), ('bound_objects', C.c_int64), ('evaluated_objects', C.c_int64)]
 
 
+class AnimBlendInfo(C.Structure):
+    '''mpt_anim_blend_info (include/miptina.h): what mpt_anim_blend_stats hands back'''
+    _fields_ = [('object_clips', C.c_int64), ('blended_objects', C.c_int64), ('moved_objects', C.c_int64), ('evaluated_blended', C.c_int64),
+                ('evaluated_moved', C.c_int64)]
+
+
 class SubdivInfo(C.Structure):
     '''mpt_subdiv_info (include/miptina.h): what mpt_subdiv_stats hands back'''
     _fields_ = [('subdivided_objects', C.c_int64), ('copies', C.c_int64), ('refined_copies', C.c_int64), ('refined_faces', C.c_int64),
@@ -300,6 +306,18 @@ SIGNATURES = {
                            C.c_double, C.POINTER(C.c_double)]),
     'mpt_clip_check': (_i, [_i, _i, _i, _ip, _fp, C.c_int64, _fp, C.c_int64, C.c_char_p, _i]),
     'mpt_anim_trig': (_i, [_vp, C.POINTER(C.c_double), _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    'mpt_object_set_animation_blend': (_i, [_vp, _i, _i, C.c_double, C.c_double, _i, C.c_double, C.c_double, C.c_double, C.c_double]),
+    'mpt_scene_add_object_clip': (_i, [_vp, _i, _ip, _fp, C.c_int64, _fp, C.c_int64, C.POINTER(_i)]),
+    'mpt_object_set_motion': (_i, [_vp, _i, _i, C.c_double, C.c_double, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    'mpt_get_object_world': (_i, [_vp, _i, C.POINTER(C.c_double)]),
+    'mpt_anim_blend_stats': (_i, [_vp, C.POINTER(AnimBlendInfo)]),
+    'mpt_motion_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_anim_blend_rule': (_i, [_i, _i, _ip, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                 _i, _ip, _fp, C.c_int64, _fp, C.c_int64, C.c_double, C.c_double, _i,
+                                 _i, _ip, _fp, C.c_int64, _fp, C.c_int64, C.c_double, C.c_double, _i,
+                                 C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    'mpt_motion_rule': (_i, [_i, _ip, _fp, C.c_int64, _fp, C.c_int64, C.c_double, C.c_double, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                             C.POINTER(C.c_double)]),
     'mpt_mesh_set_subdivision': (_i, [_vp, _i, _i]),
     'mpt_get_subdivided': (_i, [_vp, _i, _fp, _i]),
     'mpt_subdiv_stats': (_i, [_vp, C.POINTER(SubdivInfo)]),
@@ -559,6 +577,49 @@ def anim_rule(parents, rest, inverse_bind, ntargets, spec, times, values, offset
     if rc:
         raise ValueError('mpt_anim_rule refuses its arrays: verdict %d' % rc)
     return pose[:int(ntargets)].copy(), pose[int(ntargets):].reshape(nj, 3, 4).copy()
+
+
+def blend_weights(weight, fade):
+    '''(w0, w1, fade_start, fade_duration) of a second binding: `weight` a number or (w0, w1), `fade` (start, duration) or None -- the
+    weight is then w1 from the first'''
+    w0, w1 = (float(weight), float(weight)) if np.ndim(weight) == 0 else (float(weight[0]), float(weight[1]))
+    start, duration = (0.0, 0.0) if fade is None else (float(fade[0]), float(fade[1]))
+    return w0, w1, start, duration
+
+
+def anim_blend_rule(parents, rest, inverse_bind, ntargets, clip_a, binding_a, clip_b, binding_b, fade, t):
+    '''mpt_anim_blend_rule (no context, no GPU): the pose (weights [ntargets], palette [nj,3,4]) at scene time t of one object with two
+    bindings -- clip_a and clip_b packed clips (tools.anim.pack_clip), binding_a and binding_b (offset, speed, loop), fade (w0, w1,
+    fade_start, fade_duration); ValueError with the verdict for what the rule refuses'''
+    parents = np.ascontiguousarray(parents, np.int32).reshape(-1)
+    nj = int(parents.size)
+    rest = np.ascontiguousarray(rest, np.float64).reshape(nj, 10)
+    inverse_bind = np.ascontiguousarray(inverse_bind, np.float64).reshape(nj, 12)
+    sa, ta, va = _clip_arrays(*clip_a)
+    sb, tb, vb = _clip_arrays(*clip_b)
+    pose = np.zeros(int(ntargets) + 12 * nj, np.float64)
+    rc = load_library().mpt_anim_blend_rule(nj, int(ntargets), iptr(parents), _dptr(rest), _dptr(inverse_bind),
+                                            sa.shape[0], iptr(sa), fptr(ta), ta.size, fptr(va), va.size, float(binding_a[0]), float(binding_a[1]), int(bool(binding_a[2])),
+                                            sb.shape[0], iptr(sb), fptr(tb), tb.size, fptr(vb), vb.size, float(binding_b[0]), float(binding_b[1]), int(bool(binding_b[2])),
+                                            *[float(x) for x in fade], float(t), _dptr(pose))
+    if rc:
+        raise ValueError('mpt_anim_blend_rule refuses its arguments: verdict %d' % rc)
+    return pose[:int(ntargets)].copy(), pose[int(ntargets):].reshape(nj, 3, 4).copy()
+
+
+def motion_rule(clip, binding, rest, base, t):
+    '''mpt_motion_rule (no context, no GPU): the world matrix [4,4] at scene time t of an object bound to the packed object clip `clip`
+    by binding (offset, speed, loop), rest [10] or None and base [4,4] or None; ValueError with the verdict for what the rule refuses'''
+    spec, times, values = _clip_arrays(*clip)
+    rest = None if rest is None else np.ascontiguousarray(rest, np.float64).reshape(10)
+    base = None if base is None else np.ascontiguousarray(base, np.float64).reshape(16)
+    world = np.zeros(16, np.float64)
+    rc = load_library().mpt_motion_rule(spec.shape[0], iptr(spec), fptr(times), times.size, fptr(values), values.size, float(binding[0]), float(binding[1]),
+                                        int(bool(binding[2])), None if rest is None else _dptr(rest), None if base is None else _dptr(base), float(t),
+                                        _dptr(world))
+    if rc:
+        raise ValueError('mpt_motion_rule refuses its arguments: verdict %d' % rc)
+    return world.reshape(4, 4)
 
 
 SUBDIV_CHUNK, SUBDIV_MAX_LEVELS = 256, 5                                # csrc/mpt_types.h MPT_SUBDIV_*

@@ -1,5 +1,6 @@
 // anim_rule.h -- the rule of keyframe animation (summarised in include/miptina.h): the validation of a
-// skeleton's and a clip's arrays, a binding's local time, a track at that time, a joint's local matrix, the hierarchy and the palette.
+// skeleton's and a clip's arrays, a binding's local time, a track at that time, a joint's local matrix, the hierarchy and the palette;
+// and, at the end of the file (section 3.17.2), two clips blended on one object and an object moved as a whole by an object clip.
 // Plain C++17 with nothing of HIP and no context (as deform_rule.h and scatter_rule.h), so that a stand-alone program can run all of
 // it under a sanitizer (tools/anim_rule_check.cpp); under hipcc the MPT_HD functions are anim.hip's arithmetic.  The C ABI has the
 // whole evaluation of one object's pose as mpt_anim_rule and the validation of a clip as mpt_clip_check.
@@ -277,4 +278,146 @@ inline void mpt_anim_pose(int njoints, int ntargets, const int32_t *parents, con
         if (parents[j] >= 0) mpt_anim_mul(global.data() + (size_t)parents[j] * 12, G, G);
         mpt_anim_mul(G, inverse_bind + (size_t)j * 12, pose + ntargets + (size_t)j * 12);
     }
+}
+
+// ================================================================== two clips blended, and an object moved by a clip
+// ------------------------------------------------------------------ A. the second binding of a bound object
+// The weight of the second binding at SCENE time t: with fade_duration > 0, x = (t - fade_start) / fade_duration and s = 0 below 0,
+// 1 above 1, else x; with fade_duration == 0, s = 1 from fade_start on, else 0.  s == 0: w0 itself; s == 1: w1 itself; else
+// w0 + s * (w1 - w0)
+MPT_HD double mpt_anim_blend_weight(double t, double w0, double w1, double fade_start, double fade_duration) {
+    MPT_NO_CONTRACT
+    double s;
+    if (fade_duration > 0.0) {
+        const double x = (t - fade_start) / fade_duration;
+        s = x < 0.0 ? 0.0 : x > 1.0 ? 1.0 : x;
+    } else
+        s = t >= fade_start ? 1.0 : 0.0;
+    if (s == 0.0) return w0;
+    if (s == 1.0) return w1;
+    return w0 + s * (w1 - w0);
+}
+
+// n values of T, S or W: a + w * (b - a) per component, into a
+MPT_HD void mpt_anim_blend_values(double *a, const double *b, double w, int n) {
+    MPT_NO_CONTRACT
+    for (int c = 0; c < n; c++) a[c] = a[c] + w * (b[c] - a[c]);
+}
+
+// R: the normalised lerp over the shorter arc, into a.  No library function
+MPT_HD void mpt_anim_blend_rotation(double a[4], const double b_in[4], double w) {
+    MPT_NO_CONTRACT
+    double b[4] = { b_in[0], b_in[1], b_in[2], b_in[3] };
+    const double d = ((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3];
+    if (d < 0.0)
+        for (int c = 0; c < 4; c++) b[c] = -b[c];
+    for (int c = 0; c < 4; c++) a[c] = a[c] + w * (b[c] - a[c]);
+    mpt_anim_normalise4(a);
+}
+
+// A joint's T R S of clip A (a [10]) and of clip B (b [10]) blended into a, 0 < w < 1 (at w == 0 the result is a and at w == 1 it is
+// b, bit for bit: the callers copy)
+MPT_HD void mpt_anim_blend_joint(double *a, const double *b, double w) {
+    mpt_anim_blend_values(a, b, w, 3);
+    mpt_anim_blend_rotation(a + 3, b + 3, w);
+    mpt_anim_blend_values(a + 7, b + 7, w, 3);
+}
+
+// What may be a second binding
+enum MptBlendVerdict { MPT_BLEND_OK = 0, MPT_BLEND_NOT_FINITE, MPT_BLEND_DURATION, MPT_BLEND_WEIGHT };
+inline MptBlendVerdict mpt_blend_rule(double offset, double speed, double w0, double w1, double fade_start, double fade_duration, char *why, size_t why_size) {
+    auto say = [&](MptBlendVerdict v, const char *words) {
+        if (why && why_size) snprintf(why, why_size, "%s", words);
+        return v;
+    };
+    if (why && why_size) why[0] = 0;
+    if (!std::isfinite(offset)) return say(MPT_BLEND_NOT_FINITE, "offset is not finite");
+    if (!std::isfinite(speed)) return say(MPT_BLEND_NOT_FINITE, "speed is not finite");
+    if (!std::isfinite(fade_start)) return say(MPT_BLEND_NOT_FINITE, "fade_start is not finite");
+    if (!std::isfinite(fade_duration)) return say(MPT_BLEND_NOT_FINITE, "fade_duration is not finite");
+    if (fade_duration < 0.0) return say(MPT_BLEND_DURATION, "fade_duration is negative");
+    if (!(w0 >= 0.0 && w0 <= 1.0)) return say(MPT_BLEND_WEIGHT, "w0 lies outside [0, 1]");
+    if (!(w1 >= 0.0 && w1 <= 1.0)) return say(MPT_BLEND_WEIGHT, "w1 lies outside [0, 1]");
+    return MPT_BLEND_OK;
+}
+
+// T R S [njoints][10] and the weights [ntargets] of one clip at tau: a track's values, else the rest value, 0 for the weights
+inline void mpt_anim_sample_clip(int njoints, int ntargets, const double *rest, int ntracks, const MptAnimTrack *tracks, const float *times, const float *values,
+                                 double tau, double *trs, double *weights) {
+    for (size_t k = 0; k < (size_t)njoints * MPT_ANIM_REST; k++) trs[k] = rest[k];
+    for (int t = 0; t < ntargets; t++) weights[t] = 0.0;
+    for (int r = 0; r < ntracks; r++) {
+        const MptAnimTrack &tr = tracks[r];
+        static const int at[3] = { 0, 3, 7 };
+        mpt_anim_sample(tr, times, values, ntargets, tau, tr.path == MPT_ANIM_W ? weights : trs + (size_t)tr.target * MPT_ANIM_REST + at[tr.path]);
+    }
+}
+
+// The pose of an object with two bindings: clip A at tau_a and clip B at tau_b (each with its own tracks, times and values), blended by
+// w, then the local matrices, the hierarchy and the palette exactly as mpt_anim_pose does them
+inline void mpt_anim_pose_blend(int njoints, int ntargets, const int32_t *parents, const double *rest, const double *inverse_bind, int ntracks_a,
+                                const MptAnimTrack *tracks_a, const float *times_a, const float *values_a, double tau_a, int ntracks_b,
+                                const MptAnimTrack *tracks_b, const float *times_b, const float *values_b, double tau_b, double w, double *pose) {
+    const size_t n = (size_t)njoints * MPT_ANIM_REST;
+    std::vector<double> A(n), B(n), wb((size_t)ntargets), global((size_t)njoints * 12);
+    mpt_anim_sample_clip(njoints, ntargets, rest, ntracks_a, tracks_a, times_a, values_a, tau_a, A.data(), pose);
+    mpt_anim_sample_clip(njoints, ntargets, rest, ntracks_b, tracks_b, times_b, values_b, tau_b, B.data(), wb.data());
+    if (w == 1.0) {
+        A = B;
+        for (int t = 0; t < ntargets; t++) pose[t] = wb[t];
+    } else if (!(w == 0.0)) {
+        for (int j = 0; j < njoints; j++) mpt_anim_blend_joint(A.data() + (size_t)j * MPT_ANIM_REST, B.data() + (size_t)j * MPT_ANIM_REST, w);
+        mpt_anim_blend_values(pose, wb.data(), w, ntargets);
+    }
+    for (int j = 0; j < njoints; j++) {
+        double *G = global.data() + (size_t)j * 12;
+        mpt_anim_local(A.data() + (size_t)j * MPT_ANIM_REST, G);
+        if (parents[j] >= 0) mpt_anim_mul(global.data() + (size_t)parents[j] * 12, G, G);
+        mpt_anim_mul(G, inverse_bind + (size_t)j * 12, pose + ntargets + (size_t)j * 12);
+    }
+}
+
+// ------------------------------------------------------------------ B. the motion of an object
+// An OBJECT CLIP is a clip without a mesh: its tracks name target 0, the object's node, on the paths T, R and S (mpt_clip_rule with
+// njoints 1 and ntargets 0, which refuses a W track).  A MOTION BINDING holds rest [10] (translation3 rotation4 xyzw scale3) and base
+// [16] (row-major 4x4: the node's static parents)
+enum MptMotionVerdict { MPT_MOTION_OK = 0, MPT_MOTION_REST_NOT_FINITE, MPT_MOTION_ZERO_ROTATION, MPT_MOTION_BASE_NOT_FINITE, MPT_MOTION_NOT_FINITE };
+inline MptMotionVerdict mpt_motion_binding_rule(double offset, double speed, const double *rest, const double *base, char *why, size_t why_size) {
+    auto say = [&](MptMotionVerdict v, const char *fmt, long long a) {
+        if (why && why_size) snprintf(why, why_size, fmt, a);
+        return v;
+    };
+    if (why && why_size) why[0] = 0;
+    if (!std::isfinite(offset)) return say(MPT_MOTION_NOT_FINITE, "offset is not finite", 0);
+    if (!std::isfinite(speed)) return say(MPT_MOTION_NOT_FINITE, "speed is not finite", 0);
+    for (int k = 0; rest && k < MPT_ANIM_REST; k++)
+        if (!std::isfinite(rest[k])) return say(MPT_MOTION_REST_NOT_FINITE, "rest[%lld] is not finite", k);
+    if (rest && rest[3] == 0.0 && rest[4] == 0.0 && rest[5] == 0.0 && rest[6] == 0.0) return say(MPT_MOTION_ZERO_ROTATION, "the rest rotation rest[3..6] is zero", 0);
+    for (int k = 0; base && k < 16; k++)
+        if (!std::isfinite(base[k])) return say(MPT_MOTION_BASE_NOT_FINITE, "base[%lld] is not finite", k);
+    return MPT_MOTION_OK;
+}
+
+// world = base . [L; 0 0 0 1] for a row-major 4x4 base and a 3x4 L, all four rows by the one expression:
+//   W[r][c] = (B[r][0] L[0][c] + B[r][1] L[1][c]) + B[r][2] L[2][c], c < 3;  W[r][3] = ((B[r][0] L[0][3] + B[r][1] L[1][3]) + B[r][2] L[2][3]) + B[r][3]
+MPT_HD void mpt_anim_world(const double *B, const double *L, double *W) {
+    MPT_NO_CONTRACT
+    for (int r = 0; r < 4; r++) {
+        for (int c = 0; c < 3; c++) W[4 * r + c] = (B[4 * r] * L[c] + B[4 * r + 1] * L[4 + c]) + B[4 * r + 2] * L[8 + c];
+        W[4 * r + 3] = ((B[4 * r] * L[3] + B[4 * r + 1] * L[7]) + B[4 * r + 2] * L[11]) + B[4 * r + 3];
+    }
+}
+
+// The world matrix [16] of an object bound to an object clip, at local time tau: trs [10] starts as the binding's rest -- the caller
+// has copied it there; it is the function's workspace, so that the device keeps it where a track's values can be written by index --
+// and is overwritten by the clip's (at most three) tracks
+MPT_HD void mpt_anim_motion(int ntracks, const MptAnimTrack *tracks, const float *times, const float *values, double tau, double *trs, const double *base,
+                            double *world) {
+    for (int r = 0; r < ntracks; r++) {
+        const MptAnimTrack tr = tracks[r];
+        mpt_anim_sample(tr, times, values, 0, tau, trs + (tr.path == MPT_ANIM_T ? 0 : tr.path == MPT_ANIM_R ? 3 : 7));
+    }
+    double L[12];
+    mpt_anim_local(trs, L);
+    mpt_anim_world(base, L, world);
 }

@@ -111,6 +111,9 @@ MPT_KERNEL_API hipError_t mpt_launch_compose(const float *pool, const MptCompose
 MPT_KERNEL_API hipError_t mpt_launch_anim(const MptAnimObj *objs, int nobj, double t, const int32_t *parents, const int32_t *depths, const double *rest,
                                           const double *inverse_bind, const MptAnimTrack *tracks, const float *times, const float *values, double *pose,
                                           hipStream_t stream);
+// ... and the world matrices of the objects that object clips move, written into their rows of the object table
+MPT_KERNEL_API hipError_t mpt_launch_motion(const MptMotionObj *objs, int n, double t, const MptAnimTrack *tracks, const float *times, const float *values,
+                                            MptComposeObj *rows, int nrows, unsigned epoch, hipStream_t stream);
 MPT_KERNEL_API hipError_t mpt_launch_anim_trig(const double *x, int n, double *acos_out, double *sin_out, hipStream_t stream);
 // deform.hip: the deformed copies of the objects of a launch's table, written into the pool the meshes lie in (mpt_compose)
 MPT_KERNEL_API hipError_t mpt_launch_deform(float *pool, const MptDeformObj *objs, const MptRun *runs, int nruns, int blocks,
@@ -464,6 +467,7 @@ struct MPT_INTERNAL MptAnimBufs {
     DevBuf<MptAnimTrack> tracks;         // every clip's tracks, back to back (time_at / value_at count in the arenas below)
     DevBuf<float> times, values;         // the tracks' key times and values
     DevBuf<MptAnimObj> objs;             // a launch's objects
+    DevBuf<MptMotionObj> moved;          // ... and the objects that object clips move (motion_kernel)
 };
 
 // Loop subdivision's device memory (scene_subdiv.cpp): the arena of the meshes' topology blocks, appended by mpt_mesh_set_subdivision
@@ -774,12 +778,14 @@ struct mpt_ctx {
         MPT_OBJ_CLEAN = 0,
         MPT_OBJ_UPLOAD = 1,                              // its record changed on the host: it goes up
         MPT_OBJ_PLACED = 2,                              // an instance whose scatter places: scatter.hip writes its record on the device
-        MPT_OBJ_COMPOSE = MPT_OBJ_UPLOAD | MPT_OBJ_PLACED,   // either
+        MPT_OBJ_MOVED = 4,                               // an object bound to an object clip (scene_anim.cpp): anim.hip's motion_kernel writes its matrix on the device
+        MPT_OBJ_COMPOSE = MPT_OBJ_UPLOAD | MPT_OBJ_PLACED | MPT_OBJ_MOVED,   // any of them
     };
     struct MptObjRow {                                   // an object: what the host alone keeps of it
         int mesh = 0;
         int pose = -1, copy = -1, scatter = -1;          // its rows of deform.poses and subdiv.copies, the scatter it is an instance of (-1: none)
         unsigned char dirty = MPT_OBJ_UPLOAD;            // MptObjDirty flags, cleared by mpt_compose
+        int motion = -1;                                 // its row of anim.motions (-1: no object clip has ever moved it)
     };
     struct MPT_INTERNAL Compose {                        // scene composition on the device (mpt_mesh_add, mpt_object_*, mpt_compose)
         std::vector<MptMeshRow> meshes; size_t pool_verts = 0;
@@ -814,6 +820,10 @@ struct mpt_ctx {
         bool dirty = true;                               // the pose changed since the copy was written
         int clip = -1;                                   // the clip it is bound to (scene_anim.cpp; -1: none, the pose above goes up): the device evaluates its pose
         double offset = 0.0, speed = 1.0; int loop = 1;  // ... and the binding
+        // its second binding: the clip blended in (-1: none), its own offset, speed and loop, the weight's fade
+        int clip_b = -1;
+        double offset_b = 0.0, speed_b = 1.0; int loop_b = 1;
+        double w0 = 1.0, w1 = 1.0, fade_start = 0.0, fade_duration = 0.0;
     };
     struct MPT_INTERNAL Deform {                         // mesh deformation (scene_deform.cpp: mpt_mesh_set_*, mpt_object_set_*, deform_step)
         std::vector<MptDeformPose> poses;
@@ -826,17 +836,28 @@ struct mpt_ctx {
         MptLaunchTimer timer;                            // mpt_compose: {before the deform kernel, after it} per launch
         explicit Deform(MptEventPool &ev) : timer(2, ev) {}
     } deform{events};
-    struct MptAnimClip { int mesh = 0, ntracks = 0; size_t track_at = 0; double t0 = 0.0, t1 = 0.0; };   // a clip: its mesh, its tracks in the arena, its span
+    struct MptAnimClip { int mesh = 0, ntracks = 0; size_t track_at = 0; double t0 = 0.0, t1 = 0.0; };   // a clip: its mesh (-1: an object clip), its tracks in the arena, its span
+    struct MptMotion {                                   // a motion binding: the object, its object clip (-1: unbound, the row is kept for the next binding), the binding
+        int obj = 0, clip = -1;
+        double offset = 0.0, speed = 1.0; int loop = 1;
+        double rest[MPT_ANIM_REST] = { 0, 0, 0, 0, 0, 0, 1, 1, 1, 1 };
+        double base[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+    };
     struct MPT_INTERNAL Anim {                           // keyframe animation (scene_anim.cpp: mpt_mesh_set_skeleton, mpt_mesh_add_clip, mpt_object_set_animation, mpt_scene_set_time, anim_step)
         std::vector<MptAnimClip> clips;
         size_t joints_used = 0, tracks_used = 0, times_used = 0, values_used = 0;   // elements of the arenas
         int skeletons = 0;
         double time = 0.0;                               // the scene's time
         std::vector<MptAnimObj> h_objs;                  // the last launch's table as uploaded: it outlives the copy that reads it
+        std::vector<MptMotion> motions;                  // the motion bindings (an object's row names its own); cleared by mpt_scene_clear
+        int moved = 0;                                   // ... of which bound
+        std::vector<MptMotionObj> h_moved;               // the last motion launch's table as uploaded
         MptAnimBufs bufs;
         mpt_anim_info stats{};
+        int64_t evaluated_blended = 0, evaluated_moved = 0;   // of the last mpt_compose (mpt_anim_blend_stats)
         MptLaunchTimer timer;                            // mpt_compose: {before the anim kernel, after it} per launch
-        explicit Anim(MptEventPool &ev) : timer(2, ev) {}
+        MptLaunchTimer motion_timer;                     // ... {before the motion kernel, after it}
+        explicit Anim(MptEventPool &ev) : timer(2, ev), motion_timer(2, ev) {}
     } anim{events};
     struct MptSubdivCopy {                               // a subdivided copy: of a mesh that is not deformable, or of one object of a mesh that is
         int mesh = 0, obj = -1;                          // obj -1: shared by the mesh's objects
@@ -1065,6 +1086,7 @@ MPT_INTERNAL int deform_step(mpt_ctx *c);                        // before compo
 
 // scene_anim.cpp: what mpt_scene_clear tells keyframe animation, and what deform_step asks of it
 MPT_INTERNAL void anim_scene_cleared(mpt_ctx *c, int meshes);    // the bindings go with the poses (scene_deform.cpp); skeletons and clips go with the meshes
+MPT_INTERNAL int motion_step(mpt_ctx *c);                        // inside mpt_compose, behind the table's upload and in front of scatter_step: the moved objects' matrices
 MPT_INTERNAL int anim_step(mpt_ctx *c, const std::vector<int> &poses);   // inside deform_step, before the deform launch: evaluates these rows of deform.poses (bound objects) on the device
 
 // scene_subdiv.cpp: what scene_compose.cpp and scene_deform.cpp tell the subdivision table, and the step of mpt_compose behind deform_step

@@ -264,14 +264,28 @@ struct MptAnimTrack {                       // 32 bytes
     int64_t time_at;                         // its key times [nkeys] f32: first float in the arena of times
     int64_t value_at;                        // its values [nkeys][C] f32 (CUBICSPLINE: [nkeys][3][C], in-tangent value out-tangent): first float
 };
-struct MptAnimObj {                         // 80 bytes
+struct MptAnimObj {                         // 160 bytes
     int32_t njoints, ntargets;               // of its mesh (0: no skeleton / no targets)
     int32_t ntracks, loop;                   // of its clip; of its binding
-    int32_t levels, pad;                     // the greatest depth of a joint of the skeleton (a root: 0)
+    int32_t levels, blend;                   // the greatest depth of a joint of the skeleton (a root: 0); 1: it has a second binding (the fields below)
     int64_t joint_at;                        // the skeleton: first joint in the arenas of parents, depths, rest poses [.][10] and inverse binds [.][12]
     int64_t track_at;                        // the clip: first track in the arena of tracks
     int64_t pose_at;                         // the object's pose (MptDeformObj::pose_at): what the kernel writes
     double offset, speed, t0, t1;            // the binding, and the clip's span
+    // the second binding: its clip, its own offset, speed, loop and span, and the weight's fade
+    int32_t ntracks_b, loop_b;
+    int64_t track_b_at;
+    double offset_b, speed_b, t0_b, t1_b;
+    double w0, w1, fade_start, fade_duration;
+};
+// ... and one object of a launch that an object clip moves (motion_kernel): its row of the object table, its clip and its binding
+struct MptMotionObj {                       // 264 bytes
+    int32_t obj, ntracks;                    // the row of the object table whose world matrix the kernel writes; the clip's tracks (T, R, S of target 0: at most 3)
+    int32_t loop, pad;
+    int64_t track_at;
+    double offset, speed, t0, t1;
+    double rest[MPT_ANIM_REST];              // translation3 rotation4 (xyzw) scale3: what a path without a track keeps
+    double base[16];                         // row-major 4x4: world = base . local
 };
 
 // Loop subdivision (subdiv.hip): the caps, the kinds of a vertex rule (subdiv_rule.h), one job of a launch -- a subdivided copy: where

@@ -1,7 +1,9 @@
 // scene_anim.cpp -- keyframe animation behind mpt_mesh_set_skeleton / mpt_mesh_add_clip / mpt_object_set_animation / mpt_scene_set_time
 // (DESIGN.md section 3.17.1): the meshes' skeletons and clips in arenas on the device, the objects' bindings beside their poses
 // (scene_deform.cpp's table), and anim_step: the part of deform_step that evaluates the bound objects' poses with anim.hip where it
-// would upload them.  The rule itself is anim_rule.h's; the C ABI has it whole as mpt_anim_rule and a clip's validation as
+// would upload them.  Behind mpt_object_set_animation_blend / mpt_scene_add_object_clip / mpt_object_set_motion (section 3.17.2): an
+// object's second binding beside its first, object clips in the same arenas and list, the motion bindings, and motion_step: the part of
+// mpt_compose that writes the moved objects' matrices into the object table with anim.hip's motion_kernel.  The rule itself is anim_rule.h's; the C ABI has it whole as mpt_anim_rule and a clip's validation as
 // mpt_clip_check (no context, no GPU).
 
 #include "miptina_ctx.h"
@@ -29,9 +31,57 @@ extern "C" int mpt_anim_rule(int njoints, int ntargets, const int32_t *parents, 
     return 0;
 }
 
+// The whole evaluation of one pose of two blended clips (A's arrays, then B's) at scene time t.  0, or 100 + the verdict of clip A, 300 +
+// that of clip B, 200 + the skeleton's, 400 + the second binding's (mpt_blend_rule), 201 for bad arrays
+extern "C" int mpt_anim_blend_rule(int njoints, int ntargets, const int32_t *parents, const double *rest, const double *inverse_bind, int ntracks_a,
+                                   const int32_t *tracks_a, const float *times_a, int64_t ntimes_a, const float *values_a, int64_t nvalues_a, double offset_a,
+                                   double speed_a, int loop_a, int ntracks_b, const int32_t *tracks_b, const float *times_b, int64_t ntimes_b,
+                                   const float *values_b, int64_t nvalues_b, double offset_b, double speed_b, int loop_b, double w0, double w1,
+                                   double fade_start, double fade_duration, double t, double *pose) {
+    if (njoints < 0 || ntargets < 0 || ntargets > MPT_DEFORM_MAX_TARGETS || !pose) return 201;
+    if (njoints > 0) {
+        const MptSkeletonVerdict v = mpt_skeleton_rule(njoints, parents, rest, inverse_bind, nullptr, 0);
+        if (v != MPT_SKELETON_OK) return 200 + (int)v;
+    }
+    MptClipVerdict v = mpt_clip_rule(njoints, ntargets, ntracks_a, tracks_a, times_a, ntimes_a, values_a, nvalues_a, nullptr, 0);
+    if (v != MPT_CLIP_OK) return 100 + (int)v;
+    v = mpt_clip_rule(njoints, ntargets, ntracks_b, tracks_b, times_b, ntimes_b, values_b, nvalues_b, nullptr, 0);
+    if (v != MPT_CLIP_OK) return 300 + (int)v;
+    const MptBlendVerdict bv = mpt_blend_rule(offset_b, speed_b, w0, w1, fade_start, fade_duration, nullptr, 0);
+    if (bv != MPT_BLEND_OK) return 400 + (int)bv;
+    std::vector<MptAnimTrack> ta((size_t)ntracks_a), tb((size_t)ntracks_b);
+    double a0, a1, b0, b1;
+    mpt_anim_tracks(ntargets, ntracks_a, tracks_a, times_a, ta.data(), &a0, &a1);
+    mpt_anim_tracks(ntargets, ntracks_b, tracks_b, times_b, tb.data(), &b0, &b1);
+    mpt_anim_pose_blend(njoints, ntargets, parents, rest, inverse_bind, ntracks_a, ta.data(), times_a, values_a,
+                        mpt_anim_local_time(t, offset_a, speed_a, loop_a, a0, a1), ntracks_b, tb.data(), times_b, values_b,
+                        mpt_anim_local_time(t, offset_b, speed_b, loop_b, b0, b1), mpt_anim_blend_weight(t, w0, w1, fade_start, fade_duration), pose);
+    return 0;
+}
+
+// ... and of one world matrix of an object moved by an object clip.  0, or 100 + the clip's verdict (as a clip of one joint and no targets),
+// 500 + the binding's (mpt_motion_binding_rule), 201 for a null world
+extern "C" int mpt_motion_rule(int ntracks, const int32_t *tracks, const float *times, int64_t ntimes, const float *values, int64_t nvalues, double offset,
+                               double speed, int loop, const double *rest, const double *base, double t, double *world) {
+    if (!world) return 201;
+    const MptClipVerdict v = mpt_clip_rule(1, 0, ntracks, tracks, times, ntimes, values, nvalues, nullptr, 0);
+    if (v != MPT_CLIP_OK) return 100 + (int)v;
+    const MptMotionVerdict mv = mpt_motion_binding_rule(offset, speed, rest, base, nullptr, 0);
+    if (mv != MPT_MOTION_OK) return 500 + (int)mv;
+    mpt_ctx::MptMotion m;                                // (the defaults: rest at the origin, the identity as base)
+    if (rest) memcpy(m.rest, rest, sizeof m.rest);
+    if (base) memcpy(m.base, base, sizeof m.base);
+    std::vector<MptAnimTrack> tr((size_t)ntracks);
+    double t0, t1;
+    mpt_anim_tracks(0, ntracks, tracks, times, tr.data(), &t0, &t1);
+    mpt_anim_motion(ntracks, tr.data(), times, values, mpt_anim_local_time(t, offset, speed, loop, t0, t1), m.rest, m.base, world);
+    return 0;
+}
+
 // ---------------------------------------------------------------- what scene_compose.cpp tells the table
 void anim_scene_cleared(mpt_ctx *c, int meshes) {
-    auto &an = c->anim;                                  // (the bindings went with deform.poses)
+    auto &an = c->anim;                                  // (the bindings of poses went with deform.poses)
+    an.motions.clear(); an.moved = 0;
     if (!meshes) return;
     an.clips.clear();
     an.joints_used = an.tracks_used = an.times_used = an.values_used = 0;
@@ -46,6 +96,23 @@ static int append(mpt_ctx *c, DevBuf<T> &buf, size_t used, const T *src, size_t 
     if (grow_keeping(buf, used + n, used, c->stream)) return 1;
     HIP_TRY(hipMemcpyAsync(buf + used, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// a checked clip of mesh `mesh` (-1: an object clip) goes behind the others in the arenas and the list
+static int append_clip(mpt_ctx *c, int mesh, int ntargets, int ntracks, const int32_t *tracks, const float *times, int64_t ntimes, const float *values,
+                       int64_t nvalues, int *clip_id) {
+    auto &an = c->anim;
+    mpt_ctx::MptAnimClip clip;
+    clip.mesh = mesh; clip.ntracks = ntracks; clip.track_at = an.tracks_used;
+    std::vector<MptAnimTrack> tr((size_t)ntracks);
+    mpt_anim_tracks(ntargets, ntracks, tracks, times, tr.data(), &clip.t0, &clip.t1);
+    for (auto &r : tr) { r.time_at += (int64_t)an.times_used; r.value_at += (int64_t)an.values_used; }
+    if (append(c, an.bufs.tracks, an.tracks_used, tr.data(), tr.size()) || append(c, an.bufs.times, an.times_used, times, (size_t)ntimes) ||
+        append(c, an.bufs.values, an.values_used, values, (size_t)nvalues)) return 1;
+    an.tracks_used += tr.size(); an.times_used += (size_t)ntimes; an.values_used += (size_t)nvalues;
+    *clip_id = (int)an.clips.size();
+    an.clips.push_back(clip);
     return 0;
 }
 
@@ -81,17 +148,17 @@ extern "C" int mpt_mesh_add_clip(mpt_ctx *c, int mesh_id, int ntracks, const int
     char why[200];
     if (mpt_clip_rule(m.njoints, m.ntargets, ntracks, tracks, times, ntimes, values, nvalues, why, sizeof why) != MPT_CLIP_OK)
         return fail("mpt_mesh_add_clip: %s", why);
-    mpt_ctx::MptAnimClip clip;
-    clip.mesh = mesh_id; clip.ntracks = ntracks; clip.track_at = an.tracks_used;
-    std::vector<MptAnimTrack> tr((size_t)ntracks);
-    mpt_anim_tracks(m.ntargets, ntracks, tracks, times, tr.data(), &clip.t0, &clip.t1);
-    for (auto &r : tr) { r.time_at += (int64_t)an.times_used; r.value_at += (int64_t)an.values_used; }
-    if (append(c, an.bufs.tracks, an.tracks_used, tr.data(), tr.size()) || append(c, an.bufs.times, an.times_used, times, (size_t)ntimes) ||
-        append(c, an.bufs.values, an.values_used, values, (size_t)nvalues)) return 1;
-    an.tracks_used += tr.size(); an.times_used += (size_t)ntimes; an.values_used += (size_t)nvalues;
-    *clip_id = (int)an.clips.size();
-    an.clips.push_back(clip);
-    return 0;
+    return append_clip(c, mesh_id, m.ntargets, ntracks, tracks, times, ntimes, values, nvalues, clip_id);
+}
+
+extern "C" int mpt_scene_add_object_clip(mpt_ctx *c, int ntracks, const int32_t *tracks, const float *times, int64_t ntimes, const float *values,
+                                         int64_t nvalues, int *clip_id) {
+    if (use(c)) return 1;
+    if (!clip_id) return fail("mpt_scene_add_object_clip: null clip_id");
+    char why[200];
+    if (mpt_clip_rule(1, 0, ntracks, tracks, times, ntimes, values, nvalues, why, sizeof why) != MPT_CLIP_OK)
+        return fail("mpt_scene_add_object_clip: %s (an object clip animates target 0, the object's node, on the paths T, R and S)", why);
+    return append_clip(c, -1, 0, ntracks, tracks, times, ntimes, values, nvalues, clip_id);
 }
 
 // ---------------------------------------------------------------- the objects' bindings and the scene's time
@@ -110,18 +177,84 @@ extern "C" int mpt_object_set_animation(mpt_ctx *c, int obj_id, int clip_id, dou
     auto &p = c->deform.poses[row];
     if (clip_id == -1) {
         if (p.clip < 0) return 0;
-        p.clip = -1;
+        p.clip = p.clip_b = -1;                          // (both bindings)
         pose_changed(c, p);
         return 0;
     }
     const auto &clips = c->anim.clips;
     if (clip_id < 0 || (size_t)clip_id >= clips.size()) return fail("mpt_object_set_animation: unknown clip %d (%zu clips)", clip_id, clips.size());
+    if (clips[clip_id].mesh < 0)
+        return fail("mpt_object_set_animation: clip %d is an object clip, which moves an object (mpt_object_set_motion) and poses none", clip_id);
     if (clips[clip_id].mesh != p.mesh)
         return fail("mpt_object_set_animation: clip %d is a clip of mesh %d, object %d an object of mesh %d", clip_id, clips[clip_id].mesh, obj_id, p.mesh);
     if (!std::isfinite(offset)) return fail("mpt_object_set_animation: offset is not finite");
     if (!std::isfinite(speed)) return fail("mpt_object_set_animation: speed is not finite");
     p.clip = clip_id; p.offset = offset; p.speed = speed; p.loop = loop != 0;
     pose_changed(c, p);
+    return 0;
+}
+
+extern "C" int mpt_object_set_animation_blend(mpt_ctx *c, int obj_id, int clip_b, double offset, double speed, int loop, double w0, double w1,
+                                              double fade_start, double fade_duration) {
+    if (use(c)) return 1;
+    if (check_object(c, obj_id, "mpt_object_set_animation_blend")) return 1;
+    const int row = c->compose.rows[obj_id].pose;
+    if (row < 0) return fail("mpt_object_set_animation_blend: the mesh of object %d has neither morph targets nor a skin", obj_id);
+    auto &p = c->deform.poses[row];
+    if (clip_b == -1) {
+        if (p.clip_b < 0) return 0;
+        p.clip_b = -1;
+        pose_changed(c, p);
+        return 0;
+    }
+    if (p.clip < 0)
+        return fail("mpt_object_set_animation_blend: object %d is not bound to a clip: mpt_object_set_animation gives the first binding", obj_id);
+    const auto &clips = c->anim.clips;
+    if (clip_b < 0 || (size_t)clip_b >= clips.size()) return fail("mpt_object_set_animation_blend: unknown clip %d (%zu clips)", clip_b, clips.size());
+    if (clips[clip_b].mesh < 0)
+        return fail("mpt_object_set_animation_blend: clip %d is an object clip, which moves an object (mpt_object_set_motion) and poses none", clip_b);
+    if (clips[clip_b].mesh != p.mesh)
+        return fail("mpt_object_set_animation_blend: clip %d is a clip of mesh %d, object %d an object of mesh %d", clip_b, clips[clip_b].mesh, obj_id, p.mesh);
+    char why[80];
+    if (mpt_blend_rule(offset, speed, w0, w1, fade_start, fade_duration, why, sizeof why) != MPT_BLEND_OK)
+        return fail("mpt_object_set_animation_blend: %s", why);
+    p.clip_b = clip_b; p.offset_b = offset; p.speed_b = speed; p.loop_b = loop != 0;
+    p.w0 = w0; p.w1 = w1; p.fade_start = fade_start; p.fade_duration = fade_duration;
+    pose_changed(c, p);
+    return 0;
+}
+
+extern "C" int mpt_object_set_motion(mpt_ctx *c, int obj_id, int clip_id, double offset, double speed, int loop, const double *rest, const double *base) {
+    if (use(c)) return 1;
+    if (check_object(c, obj_id, "mpt_object_set_motion")) return 1;
+    auto &an = c->anim;
+    auto &row = c->compose.rows[obj_id];
+    if (clip_id == -1) {                                 // back to the matrix mpt_object_add / mpt_object_set_world last gave: the host's row goes up
+        if (row.motion < 0 || an.motions[row.motion].clip < 0) return 0;
+        an.motions[row.motion].clip = -1; an.moved--;
+        row.dirty |= mpt_ctx::MPT_OBJ_UPLOAD;
+        return 0;
+    }
+    if (row.scatter >= 0)
+        return fail("mpt_object_set_motion: object %d is an instance of scatter %d, which places it on its surface", obj_id, row.scatter);
+    if (clip_id < 0 || (size_t)clip_id >= an.clips.size()) return fail("mpt_object_set_motion: unknown clip %d (%zu clips)", clip_id, an.clips.size());
+    if (an.clips[clip_id].mesh >= 0)
+        return fail("mpt_object_set_motion: clip %d is a clip of mesh %d, which poses an object (mpt_object_set_animation) and moves none: "
+                    "mpt_scene_add_object_clip makes an object clip", clip_id, an.clips[clip_id].mesh);
+    char why[80];
+    if (mpt_motion_binding_rule(offset, speed, rest, base, why, sizeof why) != MPT_MOTION_OK) return fail("mpt_object_set_motion: %s", why);
+    if (row.motion < 0) {
+        row.motion = (int)an.motions.size();
+        an.motions.emplace_back();
+        an.motions.back().obj = obj_id;
+    }
+    auto &m = an.motions[row.motion];
+    if (m.clip < 0) an.moved++;
+    const mpt_ctx::MptMotion fresh;
+    m.clip = clip_id; m.offset = offset; m.speed = speed; m.loop = loop != 0;
+    memcpy(m.rest, rest ? rest : fresh.rest, sizeof m.rest);
+    memcpy(m.base, base ? base : fresh.base, sizeof m.base);
+    row.dirty |= mpt_ctx::MPT_OBJ_MOVED;
     return 0;
 }
 
@@ -132,6 +265,8 @@ extern "C" int mpt_scene_set_time(mpt_ctx *c, double t) {
     c->anim.time = t;
     for (auto &p : c->deform.poses)
         if (p.clip >= 0) pose_changed(c, p);
+    for (const auto &m : c->anim.motions)                // (behind the poses: pose_changed sets an object's flags, this adds one)
+        if (m.clip >= 0) c->compose.rows[m.obj].dirty |= mpt_ctx::MPT_OBJ_MOVED;
     return 0;
 }
 
@@ -141,6 +276,7 @@ extern "C" int mpt_scene_set_time(mpt_ctx *c, double t) {
 int anim_step(mpt_ctx *c, const std::vector<int> &rows) {
     auto &an = c->anim;
     an.stats.evaluated_objects = (int64_t)rows.size();
+    an.evaluated_blended = 0;
     if (rows.empty()) return 0;
     an.h_objs.resize(rows.size());
     for (size_t k = 0; k < rows.size(); k++) {
@@ -152,6 +288,13 @@ int anim_step(mpt_ctx *c, const std::vector<int> &rows) {
         o.njoints = m.njoints; o.ntargets = m.ntargets; o.ntracks = clip.ntracks; o.loop = p.loop; o.levels = m.levels;
         o.joint_at = (int64_t)m.joint_at; o.track_at = (int64_t)clip.track_at; o.pose_at = (int64_t)p.pose_at;
         o.offset = p.offset; o.speed = p.speed; o.t0 = clip.t0; o.t1 = clip.t1;
+        if (p.clip_b >= 0) {
+            const auto &b = an.clips[p.clip_b];
+            o.blend = 1; o.ntracks_b = b.ntracks; o.loop_b = p.loop_b; o.track_b_at = (int64_t)b.track_at;
+            o.offset_b = p.offset_b; o.speed_b = p.speed_b; o.t0_b = b.t0; o.t1_b = b.t1;
+            o.w0 = p.w0; o.w1 = p.w1; o.fade_start = p.fade_start; o.fade_duration = p.fade_duration;
+            an.evaluated_blended++;
+        }
     }
     if (an.bufs.objs.reserve(rows.size())) return 1;
     HIP_TRY(hipMemcpyAsync(an.bufs.objs, an.h_objs.data(), rows.size() * sizeof(MptAnimObj), hipMemcpyHostToDevice, c->stream));
@@ -163,7 +306,64 @@ int anim_step(mpt_ctx *c, const std::vector<int> &rows) {
     return 0;
 }
 
+// The objects that object clips move: inside mpt_compose behind the upload of the object table, whose rows would overwrite what the
+// kernel writes, and in front of scatter_step and the composition, which read the matrices from the table.  A bound object is evaluated
+// when the table went up whole (a relayout), when its own row went up (its material changed, say) or when mpt_scene_set_time or
+// mpt_object_set_motion marked it; one launch for all of them, a lane each.  Without a motion binding in the scene nothing is called
+int motion_step(mpt_ctx *c) {
+    auto &an = c->anim;
+    auto &cp = c->compose;
+    an.evaluated_moved = 0;
+    if (an.moved == 0) return 0;
+    an.h_moved.clear();
+    for (const auto &m : an.motions) {
+        if (m.clip < 0) continue;
+        if (!cp.relayout && !(cp.rows[m.obj].dirty & (mpt_ctx::MPT_OBJ_MOVED | mpt_ctx::MPT_OBJ_UPLOAD))) continue;
+        const auto &clip = an.clips[m.clip];
+        MptMotionObj o{};
+        o.obj = m.obj; o.ntracks = clip.ntracks; o.loop = m.loop; o.track_at = (int64_t)clip.track_at;
+        o.offset = m.offset; o.speed = m.speed; o.t0 = clip.t0; o.t1 = clip.t1;
+        memcpy(o.rest, m.rest, sizeof o.rest); memcpy(o.base, m.base, sizeof o.base);
+        an.h_moved.push_back(o);
+    }
+    const size_t n = an.h_moved.size();
+    an.evaluated_moved = (int64_t)n;
+    if (n == 0) return 0;
+    if (an.bufs.moved.reserve(n)) return 1;
+    HIP_TRY(hipMemcpyAsync(an.bufs.moved, an.h_moved.data(), n * sizeof(MptMotionObj), hipMemcpyHostToDevice, c->stream));
+    MptTimedSpan span(an.motion_timer, c->stream);
+    HIP_TRY(span.begun);
+    HIP_TRY(mpt_launch_motion(an.bufs.moved, (int)n, an.time, an.bufs.tracks, an.bufs.times, an.bufs.values, cp.bufs.objs, (int)cp.objs.size(), cp.epoch, c->stream));
+    HIP_TRY(span.end());
+    return 0;
+}
+
 // ---------------------------------------------------------------- read-backs
+extern "C" int mpt_get_object_world(mpt_ctx *c, int obj_id, double *world) {
+    if (use_ro(c)) return 1;
+    if (check_object(c, obj_id, "mpt_get_object_world")) return 1;
+    if (!world) return fail("mpt_get_object_world: null world");
+    const auto &cp = c->compose;
+    if (!cp.out_valid || cp.relayout || obj_id >= cp.out_objs)
+        return fail("mpt_get_object_world: object %d has no row on the device yet: call mpt_compose", obj_id);
+    return read_back(c, world, (const char *)(cp.bufs.objs + obj_id) + offsetof(MptComposeObj, world), 16 * sizeof(double));
+}
+
+extern "C" int mpt_anim_blend_stats(mpt_ctx *c, mpt_anim_blend_info *out) {
+    if (!c || !out) return fail("null argument");
+    const auto &an = c->anim;
+    *out = mpt_anim_blend_info{};
+    for (const auto &clip : an.clips) out->object_clips += clip.mesh < 0;
+    for (const auto &p : c->deform.poses) out->blended_objects += p.clip >= 0 && p.clip_b >= 0;
+    out->moved_objects = an.moved;
+    out->evaluated_blended = an.evaluated_blended; out->evaluated_moved = an.evaluated_moved;
+    return 0;
+}
+
+extern "C" int mpt_motion_kernel_time(mpt_ctx *c, double *ms, int *launches) {
+    return use_ro(c) || timer_readout(c, c->anim.motion_timer, ms, nullptr, launches);
+}
+
 extern "C" int mpt_get_pose(mpt_ctx *c, int obj_id, double *pose, int cap) {
     if (use_ro(c)) return 1;
     if (check_object(c, obj_id, "mpt_get_pose")) return 1;

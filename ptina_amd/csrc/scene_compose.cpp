@@ -125,6 +125,9 @@ extern "C" int mpt_object_set_world(mpt_ctx *c, int obj_id, const double world[1
     auto &row = c->compose.rows[obj_id];
     if (row.scatter >= 0)
         return fail("mpt_object_set_world: object %d is an instance of scatter %d, which places it on its surface", obj_id, row.scatter);
+    if (row.motion >= 0 && c->anim.motions[row.motion].clip >= 0)
+        return fail("mpt_object_set_world: object %d is bound to object clip %d, which gives its matrix: unbind it first (mpt_object_set_motion with clip -1)",
+                    obj_id, c->anim.motions[row.motion].clip);
     memcpy(c->compose.objs[obj_id].world, world, sizeof(double) * 16);
     row.dirty = mpt_ctx::MPT_OBJ_UPLOAD;
     return 0;
@@ -214,7 +217,7 @@ extern "C" int mpt_compose(mpt_ctx *c) {
         HIP_TRY(hipMemcpyAsync(cp.bufs.first, first32.data(), (size_t)nobj * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     } else {
         for (int o = 0; o < nobj; o++)
-            if (cp.rows[o].dirty & mpt_ctx::MPT_OBJ_UPLOAD)   // (MPT_OBJ_PLACED alone: an instance its scatter places, whose row the device writes)
+            if (cp.rows[o].dirty & mpt_ctx::MPT_OBJ_UPLOAD)   // (MPT_OBJ_PLACED or _MOVED alone: a row whose matrix the device writes)
                 HIP_TRY(hipMemcpyAsync(cp.bufs.objs + o, &cp.objs[o], sizeof(MptComposeObj), hipMemcpyHostToDevice, c->stream));
     }
     std::vector<MptRun> runs((size_t)std::max(nruns, 1));
@@ -222,6 +225,9 @@ extern "C" int mpt_compose(mpt_ctx *c) {
     for (int r = 0; r < nruns; r++) { runs[r] = { (int32_t)wg_begin[r], blocks }; blocks += (int)wg_count[r]; }
     if (!all && nruns > 0)
         HIP_TRY(hipMemcpyAsync(cp.bufs.runs, runs.data(), (size_t)nruns * sizeof(MptRun), hipMemcpyHostToDevice, c->stream));
+    // the moved objects' matrices (scene_anim.cpp): behind the table's upload, which would overwrite them, and in front of the scatters,
+    // whose kernels read their surfaces' matrices from the table
+    if (motion_step(c)) return 1;
     // the scatters' launches: behind the table's upload, which would overwrite the matrices they write, and before the composition
     if (scatter_step(c)) return 1;
     kept.drop();

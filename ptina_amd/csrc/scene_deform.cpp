@@ -142,7 +142,7 @@ extern "C" int mpt_object_set_joints(mpt_ctx *c, int obj_id, const double *mats,
 int deform_step(mpt_ctx *c) {
     auto &cp = c->compose;
     auto &df = c->deform;
-    c->anim.stats.evaluated_objects = 0;
+    c->anim.stats.evaluated_objects = 0; c->anim.evaluated_blended = 0;
     df.stats.deformed_objects = df.stats.deformed_corners = 0;
     df.stats.deformable_objects = (int64_t)df.poses.size();
     const int np = (int)df.poses.size();

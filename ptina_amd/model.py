@@ -278,6 +278,59 @@ class ModelPool(metaclass=Singleton):
         ctx().call('mpt_anim_stats', C.byref(info))
         return info
 
+    # ---- two clips blended, and objects moved by clips
+    def set_animation_blend(self, obj, clip, offset=0.0, speed=1.0, loop=True, weight=1.0, fade=None):
+        '''the second binding of an object that set_animation has bound: `clip`, another clip of its mesh, is evaluated at its own
+        (t - offset) * speed and mixed in by a weight in [0, 1] -- `weight` a number, or (w0, w1) with fade=(start, duration): w0 until
+        scene time `start`, then linearly to w1 over `duration` (0: at once), so that a cross-fade costs nothing per frame but
+        set_time.  Weight 0 is the first clip's pose, 1 this one's, bit for bit.  clip=None or -1 removes the second binding;
+        set_animation(obj, None) removes both'''
+        from ._lib import blend_weights
+        obj = self._object(obj)
+        ctx().call('mpt_object_set_animation_blend', obj, -1 if clip is None else int(clip), float(offset), float(speed), int(bool(loop)),
+                   *blend_weights(weight, fade))
+
+    def add_object_clip(self, tracks):
+        '''a clip that moves objects, at any time: a list of tools.anim.track(0, 'T' | 'R' | 'S', ...), target 0 being the object's
+        node -- at most one per path.  Returns the clip id, which counts on over the meshes' clips'''
+        from .tools.anim import pack_clip
+        spec, times, values = pack_clip(tracks)
+        clip = C.c_int(-1)
+        ctx().call('mpt_scene_add_object_clip', spec.shape[0], iptr(spec), fptr(times), times.size, fptr(values), values.size, C.byref(clip))
+        return clip.value
+
+    def set_motion(self, obj, clip, offset=0.0, speed=1.0, loop=True, rest=None, base=None):
+        '''bind an object -- any but an instance of a scatter -- to an object clip: at scene time t its world matrix is
+        base . T R S, with T, R and S the clip's tracks at (t - offset) * speed and, for a path without a track, those of `rest`
+        (translation3 rotation4 xyzw scale3; None: 0 0 0, 0 0 0 1, 1 1 1); `base` [4,4] is the node's static parents (None: the
+        identity).  The device writes the matrix: set_world refuses the object until clip=None or -1 unbinds it, which returns it to
+        the matrix add_object / set_world last gave'''
+        obj = self._object(obj)
+        dp = C.POINTER(C.c_double)
+        rest = None if rest is None else np.ascontiguousarray(rest, np.float64).reshape(-1)
+        base = None if base is None else np.ascontiguousarray(base, np.float64).reshape(-1)
+        if rest is not None and rest.size != 10:
+            raise ValueError('rest must hold 10 numbers (translation3 rotation4 scale3), got %d' % rest.size)
+        if base is not None and base.size != 16:
+            raise ValueError('base must be [4,4], got %d numbers' % base.size)
+        ctx().call('mpt_object_set_motion', obj, -1 if clip is None else int(clip), float(offset), float(speed), int(bool(loop)),
+                   None if rest is None else rest.ctypes.data_as(dp), None if base is None else base.ctypes.data_as(dp))
+
+    def world_to_numpy(self, obj):
+        '''[4,4] f64: an object's world matrix as it lies on the device after the last compose(), moved by a clip or not'''
+        obj = self._object(obj)
+        world = np.zeros((4, 4), np.float64)
+        ctx().call('mpt_get_object_world', obj, world.ctypes.data_as(C.POINTER(C.c_double)))
+        return world
+
+    def anim_blend_stats(self):
+        '''_lib.AnimBlendInfo: object clips, objects with a second binding, objects with a motion binding, and how many of each the last
+        compose() evaluated on the device'''
+        from ._lib import AnimBlendInfo
+        info = AnimBlendInfo()
+        ctx().call('mpt_anim_blend_stats', C.byref(info))
+        return info
+
     # ---- Loop subdivision on the device, behind the deformation (csrc/subdiv.hip; the reference's add-on
     #      is handed Blender's evaluated mesh instead)
     def _object_faces(self, mesh):

@@ -32,6 +32,9 @@ _PASS_THROUGH = {
     'add_mesh_clip': ('ModelPool', 'add_clip', ('mesh', 'tracks')),
     'set_object_animation': ('ModelPool', 'set_animation', ('obj', 'clip', ('offset', 0.0), ('speed', 1.0), ('loop', True))),
     'set_scene_time': ('ModelPool', 'set_time', ('t',)),
+    'set_object_animation_blend': ('ModelPool', 'set_animation_blend', ('obj', 'clip', ('offset', 0.0), ('speed', 1.0), ('loop', True), ('weight', 1.0), ('fade', None))),
+    'add_object_clip': ('ModelPool', 'add_object_clip', ('tracks',)),
+    'set_object_motion': ('ModelPool', 'set_motion', ('obj', 'clip', ('offset', 0.0), ('speed', 1.0), ('loop', True), ('rest', None), ('base', None))),
     'set_mesh_subdivision': ('ModelPool', 'add_subdivision', ('mesh', 'levels', ('creases', None), ('corners', None), ('scheme', 'loop'), ('polys', None))),
     'set_mesh_displacement': ('ModelPool', 'add_displacement', ('mesh', 'image', ('strength', 1.0), ('midlevel', 0.5), ('mode', 'normal'), ('channel', 'mean'))),
     'set_mesh_displacement_params': ('ModelPool', 'set_displacement', ('mesh', 'strength', ('midlevel', None))),
