@@ -6,11 +6,15 @@ all bound to one clip at different offsets, the scene kept on the device.  Skele
 so nothing but the time crosses to the device: every object's pose is evaluated there (csrc/anim.hip), in one launch, the corners
 are skinned there (csrc/deform.hip), the faces composed again and the built tree fitted to them (csrc/refit.hip).
 
-    python exams/crowd_amd.py [--objects 24] [--frames 12] [--size 256] [--spp 8] [--out DIR] [--blend]
+    python exams/crowd_amd.py [--objects 24] [--frames 12] [--size 256] [--spp 8] [--out DIR] [--blend] [--props]
 
 --blend: every object gets a second clip -- a faster, wider sway: the walk turns into a run -- blended in by
 a cross-fade whose start is staggered over the crowd, and a few rigid props circle above it on object clips (set_motion).  Still
 nothing but the time crosses to the device.
+
+--props (section 3.17.3): every character carries a rigid prop, a small drum, on its top joint (set_parent with a joint, the joint's
+bind matrix folded in with tools.skin.attach): the prop's matrix is world(character) . palette[top] . local, written on the device by
+csrc/hierarchy.hip behind the poses.
 '''
 import argparse
 import os
@@ -23,6 +27,7 @@ from ptina_amd.things import *              # noqa: E402,F401,F403
 from ptina_amd.engine.path import *         # noqa: E402,F401,F403
 from ptina_amd.image import write_png       # noqa: E402
 from ptina_amd.tools.anim import quaternion, rest_pose, track   # noqa: E402
+from ptina_amd.tools.skin import attach     # noqa: E402
 from ptina_amd import scenes                # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -32,6 +37,7 @@ ap.add_argument('--size', type=int, default=256)
 ap.add_argument('--spp', type=int, default=8)
 ap.add_argument('--out', default='.')
 ap.add_argument('--blend', action='store_true', help='cross-fade every object from the walk to a run, staggered; rigid props on object clips')
+ap.add_argument('--props', action='store_true', help='a rigid prop on the top joint of every character (set_parent)')
 args = ap.parse_args()
 
 JOINTS, HEIGHT, RADIUS, RINGS, SIDES, PERIOD = 8, 0.9, 0.05, 24, 12, 2.0
@@ -87,7 +93,8 @@ pool.add_skin(mesh, joints, weights, JOINTS)
 seg = HEIGHT / JOINTS
 t, r, s = rest_pose(JOINTS)
 t[1:, 1] = seg
-pool.add_skeleton(mesh, np.arange(JOINTS) - 1, t, r, s, np.stack([shift(0, -j * seg, 0) for j in range(JOINTS)]))
+inverse_bind = np.stack([shift(0, -j * seg, 0) for j in range(JOINTS)])
+pool.add_skeleton(mesh, np.arange(JOINTS) - 1, t, r, s, inverse_bind)
 times = np.linspace(0.0, PERIOD, 17)
 phase = 2 * np.pi * times / PERIOD
 tracks = [track(j, 'R', times, [quaternion([0, 0, 1], 1.2 * np.sin(a) / JOINTS) for a in phase]) for j in range(JOINTS)]
@@ -101,14 +108,20 @@ if args.blend:                                     # the run: half the period, t
     run_clip = pool.add_clip(mesh, run)
 g = np.random.default_rng(1)
 side = int(np.ceil(np.sqrt(args.objects)))
+if args.props or args.blend:
+    prop = pool.add_mesh(0.06 * (p - [0, 0.5 * HEIGHT, 0]) / RADIUS * [1, RADIUS / HEIGHT, 1], n)      # the tube squashed to a drum
+characters = []
 for o in range(args.objects):
     x, z = (o % side + 0.5) / side, (o // side + 0.5) / side
     obj = pool.add_object(mesh, shift(-0.8 + 1.6 * x, 0.0, -0.9 + 1.4 * z), 3)
     pool.set_animation(obj, clip, offset=g.uniform(0.0, PERIOD), speed=g.uniform(0.8, 1.25))
+    characters.append(obj)
     if args.blend:                                 # the fade runs across the crowd: the first object starts at once, the last at half the period
         pool.set_animation_blend(obj, run_clip, offset=g.uniform(0.0, PERIOD), weight=(0.0, 1.0), fade=(0.5 * PERIOD * o / args.objects, 0.4 * PERIOD))
+if args.props:                                     # a drum a little above the top joint's origin, in that joint's frame
+    for o, obj in enumerate(characters):
+        pool.set_parent(pool.add_object(prop, attach(inverse_bind[JOINTS - 1], shift(0, seg + 0.04, 0)), 1 + o % 2), obj, JOINTS - 1)
 if args.blend:
-    prop = pool.add_mesh(0.06 * (p - [0, 0.5 * HEIGHT, 0]) / RADIUS * [1, RADIUS / HEIGHT, 1], n)      # the tube squashed to a drum
     turn = [quaternion([0, 1, 0], a) for a in phase]
     for k in range(4):
         orbit = pool.add_object_clip([track(0, 'R', times, turn), track(0, 'T', times, np.stack([0 * times, 0.05 * np.sin(phase + k), 0 * times], axis=1))])
@@ -128,9 +141,9 @@ for f in range(args.frames):
     PathEngine().render(args.spp)
     img = FilmTable().get_display(layout='display')
     write_png(os.path.join(args.out, 'crowd_%03d.png' % f), img)
-    a, d, c, b = pool.anim_stats(), pool.deform_stats(), pool.compose_stats(), pool.anim_blend_stats()
-    print('frame %d: %d objects posed on the device (%d blended), %d moved there, %d corners deformed, %d of %d faces recomposed, mean byte %.2f'
-          % (f, a.evaluated_objects, b.evaluated_blended, b.evaluated_moved, d.deformed_corners, c.recomposed, c.faces, float(img[..., :3].mean())))
+    a, d, c, b, h = pool.anim_stats(), pool.deform_stats(), pool.compose_stats(), pool.anim_blend_stats(), pool.hierarchy_stats()
+    print('frame %d: %d objects posed on the device (%d blended), %d moved there, %d carried by a parent, %d corners deformed, %d of %d faces recomposed, mean byte %.2f'
+          % (f, a.evaluated_objects, b.evaluated_blended, b.evaluated_moved, h.evaluated, d.deformed_corners, c.recomposed, c.faces, float(img[..., :3].mean())))
 dt = time.perf_counter() - t0
 print('%d frames of %dx%d at %d spp in %.2f s (PNG writing included), %d refitted: written to %s'
       % (args.frames, args.size, args.size, args.spp, dt, refitted, args.out))

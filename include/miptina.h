@@ -713,6 +713,52 @@ int mpt_anim_blend_rule(int njoints, int ntargets, const int32_t *parents, const
 int mpt_motion_rule(int ntracks, const int32_t *tracks, const float *times, int64_t ntimes, const float *values, int64_t nvalues, double offset,
                     double speed, int loop, const double *rest, const double *base, double t, double *world /* [16] */);
 
+/* Objects parented to objects and to joints (the rule stands once at the end of csrc/anim_rule.h, f64 in one
+ * written order without contraction, no new library call).
+ *   A PARENT BINDING of an object is (parent, joint): another object of the table, and -1 or a joint of the skin of the parent's mesh.
+ *   Once bound, the object's own matrix is its LOCAL matrix: what mpt_object_add / mpt_object_set_world gave (mpt_object_set_world stays
+ *   allowed and sets it), or with a motion binding base . T R S exactly as above.  Then
+ *     joint -1:  world(child) = world(parent) . local
+ *     joint j:   world(child) = world(parent) . ([M_j; 0 0 0 1] . local), the inner product first,
+ *   M_j the 3x4 entry j of the parent's pose as it lies in the device's pose buffer this compose (what mpt_get_pose returns: the skinning
+ *   matrix global . inverse bind, set by mpt_object_set_joints, by one clip or by two blended), so that the child moves as a vertex
+ *   skinned to j with weight 1.  Every product is W[r][c] = ((A[r][0] B[0][c] + A[r][1] B[1][c]) + A[r][2] B[2][c]) + A[r][3] B[3][c];
+ *   neither factor need be affine.
+ * mpt_object_set_parent: binds; parent -1 unparents, and the object's matrix is read as its world again.  It refuses, by the number
+ *   mpt_parent_check returns, and changes nothing: 1 an unknown object or parent; 2 an object as its own ancestor; 3 a child or a parent
+ *   that is an instance of a scatter; 4 joint >= 0 when the parent's mesh has no skin; 5 a joint outside the parent's joints; 6 a chain
+ *   deeper than 64 (a child of a root has depth 1).  A child may be a scatter's surface, deformable, subdivided, or of a mesh without
+ *   faces.  The bindings go with any mpt_scene_clear.
+ * mpt_compose first marks, level by level, every child whose parent's row is dirty for any reason, or that names a joint of a parent
+ *   whose pose is dirty; then, behind the moved objects and in front of the scatters and the composition, hierarchy.hip's kernel, a lane
+ *   per child, evaluates the marked children, after a change of layout all, and any whose own row went up: in one launch while they are
+ *   at most 1024, else in one launch per level evaluated.  A bound child with a motion binding is evaluated there and not by the motion
+ *   kernel.  The same time again marks nothing and launches nothing.
+ * mpt_object_get_parent: the binding (-1, -1: none).  mpt_hierarchy_stats: bound children and the deepest chain; children evaluated,
+ *   levels and launches of the last mpt_compose.  mpt_hierarchy_kernel_time: as mpt_anim_kernel_time, of the hierarchy kernel.
+ * mpt_parent_check: the refusals above as a pure function of the bindings as they stand (parents [nobj]), instance [nobj] (not 0: an
+ *   instance of a scatter) and njoints [nobj] (of each object's mesh's skin).
+ * mpt_hierarchy_rule: one object's world matrix at scene time t as a pure function (no context, no GPU) of its chain of n links, link 0
+ *   the root and link n - 1 the object: locals [n][16] (a link's local matrix, or its motion binding's base); ntracks [n] (-1: no motion
+ *   binding; else the tracks of the link's object clip, which stand back to back in tracks, times and values; ntimes [n] and nvalues [n]
+ *   say how many of each are the link's); bindings [n][3] (offset, speed, loop != 0) and rests [n][10] of the motion bindings (NULL with
+ *   no motion binding in the chain); joints [n] (joints[k] >= 0: link k follows a palette entry) and palette [n][12] (the entries; NULL
+ *   when no joint is named).  It returns 0; 601 for bad arrays; 602 for n outside [1, 65]; 603 for a local matrix and 604 for a named
+ *   palette entry that is not finite; 100 + mpt_clip_check's verdict of a link's object clip; 500 + the motion binding's, as
+ *   mpt_motion_rule. */
+typedef struct {
+    int64_t bound_children, deepest, evaluated, levels, launches;
+} mpt_hierarchy_info;
+int mpt_object_set_parent(mpt_ctx *ctx, int obj_id, int parent_id, int joint);
+int mpt_object_get_parent(mpt_ctx *ctx, int obj_id, int *parent_id, int *joint);
+int mpt_hierarchy_stats(mpt_ctx *ctx, mpt_hierarchy_info *out);
+int mpt_hierarchy_kernel_time(mpt_ctx *ctx, double *ms, int *launches);
+int mpt_parent_check(int nobj, const int32_t *parents, const int32_t *instance, const int32_t *njoints, int obj, int parent, int joint, char *why,
+                     int why_size);
+int mpt_hierarchy_rule(int n, const double *locals, const int32_t *ntracks, const int32_t *tracks, const float *times, const int64_t *ntimes,
+                       const float *values, const int64_t *nvalues, const double *bindings, const double *rests, const int32_t *joints,
+                       const double *palette, double t, double *world /* [16] */);
+
 /* Loop subdivision on the device (triangles in, four triangles out per level) as a property of a mesh of the pool, evaluated inside
  * mpt_compose behind morph targets and skinning and before composition, so that a pose change of a subdivided character costs the
  * upload of the pose, the deform kernel, L + 2 kernels over that object, the partial mpt_compose and mpt_refit_tree: topology and face

@@ -146,6 +146,11 @@ class HistoryStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ('kept', 'statics', 'background_kept', 'disoccluded', 'offscreen', 'background_reset')]
 
 
+class HierarchyInfo(C.Structure):
+    '''mpt_hierarchy_info (include/miptina.h): what mpt_hierarchy_stats hands back'''
+    _fields_ = [('bound_children', C.c_int64), ('deepest', C.c_int64), ('evaluated', C.c_int64), ('levels', C.c_int64), ('launches', C.c_int64)]
+
+
 # mpt_history_motion (include/miptina.h) as a numpy record, and its flags
 MOTION_DTYPE = np.dtype([('cur_id', np.int32), ('fx', np.float32), ('fy', np.float32), ('d_exp', np.float32), ('flags', np.int32)])
 MOTION_NONE, MOTION_STATIC, MOTION_BACKGROUND = 0, 1, 2
@@ -318,6 +323,13 @@ SIGNATURES = {
                                  C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
     'mpt_motion_rule': (_i, [_i, _ip, _fp, C.c_int64, _fp, C.c_int64, C.c_double, C.c_double, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                              C.POINTER(C.c_double)]),
+    'mpt_object_set_parent': (_i, [_vp, _i, _i, _i]),
+    'mpt_object_get_parent': (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i)]),
+    'mpt_hierarchy_stats': (_i, [_vp, C.POINTER(HierarchyInfo)]),
+    'mpt_hierarchy_kernel_time': (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
+    'mpt_parent_check': (_i, [_i, _ip, _ip, _ip, _i, _i, _i, C.c_char_p, _i]),
+    'mpt_hierarchy_rule': (_i, [_i, C.POINTER(C.c_double), _ip, _ip, _fp, C.POINTER(C.c_int64), _fp, C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                                C.POINTER(C.c_double), _ip, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double)]),
     'mpt_mesh_set_subdivision': (_i, [_vp, _i, _i]),
     'mpt_get_subdivided': (_i, [_vp, _i, _fp, _i]),
     'mpt_subdiv_stats': (_i, [_vp, C.POINTER(SubdivInfo)]),
@@ -619,6 +631,59 @@ def motion_rule(clip, binding, rest, base, t):
                                         _dptr(world))
     if rc:
         raise ValueError('mpt_motion_rule refuses its arguments: verdict %d' % rc)
+    return world.reshape(4, 4)
+
+
+HIER_MAX_DEPTH, HIER_ONE_GROUP = 64, 1024                                # csrc/mpt_types.h MPT_HIER_*
+PARENT_REFUSALS = ('ok', 'unknown', 'cycle', 'instance', 'no skin', 'joint', 'depth')     # csrc/anim_rule.h MptParentVerdict
+
+
+def parent_check(parents, instance, njoints, obj, parent, joint=None):
+    '''mpt_parent_check (no context, no GPU): (verdict, words) for binding object obj to (parent, joint) in a table whose bindings stand
+    as parents [n] (-1: a root), with instance [n] (true: an instance of a scatter) and njoints [n] (of each object's mesh's skin);
+    verdict 0 accepts, the others index PARENT_REFUSALS'''
+    parents = np.ascontiguousarray(parents, np.int32).reshape(-1)
+    instance = np.ascontiguousarray(np.asarray(instance) != 0, np.int32).reshape(-1)
+    njoints = np.ascontiguousarray(njoints, np.int32).reshape(-1)
+    if not parents.size == instance.size == njoints.size:
+        raise ValueError('parents, instance and njoints must have one length')
+    why = C.create_string_buffer(200)
+    rc = load_library().mpt_parent_check(int(parents.size), iptr(parents), iptr(instance), iptr(njoints), int(obj), -1 if parent is None else int(parent),
+                                         -1 if joint is None else int(joint), why, len(why))
+    return rc, why.value.decode()
+
+
+def hierarchy_rule(chain, t):
+    '''mpt_hierarchy_rule (no context, no GPU): the world matrix [4,4] at scene time t of the last link of `chain`, a list of links
+    from the root down; a link is a dict of local [4,4] (its local matrix) or motion=(packed object clip, (offset, speed, loop), rest
+    [10] or None, base [4,4] or None), and, below the root, pal [3,4] or None: the palette entry it follows.  ValueError with the
+    verdict for what the rule refuses'''
+    n = len(chain)
+    locals_, ntracks, joints = np.zeros((n, 16)), np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+    bindings, rests, palette = np.zeros((n, 3)), np.tile(np.float64([0, 0, 0, 0, 0, 0, 1, 1, 1, 1]), (n, 1)), np.zeros((n, 12))
+    ntimes, nvalues = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    specs, times, values = [np.zeros((0, 4), np.int32)], [np.zeros(0, np.float32)], [np.zeros(0, np.float32)]
+    for k, ln in enumerate(chain):
+        if ln.get('motion') is not None:
+            clip, binding, rest, base = ln['motion']
+            sp, ti, va = _clip_arrays(*clip)
+            specs.append(sp), times.append(ti), values.append(va)
+            ntracks[k], ntimes[k], nvalues[k] = sp.shape[0], ti.size, va.size
+            bindings[k] = float(binding[0]), float(binding[1]), float(bool(binding[2]))
+            if rest is not None:
+                rests[k] = np.asarray(rest, np.float64).reshape(10)
+            locals_[k] = np.eye(4).reshape(16) if base is None else np.asarray(base, np.float64).reshape(16)
+        else:
+            locals_[k] = np.asarray(ln['local'], np.float64).reshape(16)
+        if ln.get('pal') is not None:
+            joints[k], palette[k] = 0, np.asarray(ln['pal'], np.float64).reshape(12)
+    spec, ti, va = np.ascontiguousarray(np.concatenate(specs)), np.ascontiguousarray(np.concatenate(times)), np.ascontiguousarray(np.concatenate(values))
+    world = np.zeros(16, np.float64)
+    i64 = C.POINTER(C.c_int64)
+    rc = load_library().mpt_hierarchy_rule(n, _dptr(locals_), iptr(ntracks), iptr(spec), fptr(ti), ntimes.ctypes.data_as(i64), fptr(va),
+                                           nvalues.ctypes.data_as(i64), _dptr(bindings), _dptr(rests), iptr(joints), _dptr(palette), float(t), _dptr(world))
+    if rc:
+        raise ValueError('mpt_hierarchy_rule refuses its arguments: verdict %d' % rc)
     return world.reshape(4, 4)
 
 

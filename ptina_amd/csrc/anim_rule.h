@@ -1,6 +1,7 @@
 // anim_rule.h -- the rule of keyframe animation (summarised in include/miptina.h): the validation of a
 // skeleton's and a clip's arrays, a binding's local time, a track at that time, a joint's local matrix, the hierarchy and the palette;
-// and, at the end of the file (section 3.17.2), two clips blended on one object and an object moved as a whole by an object clip.
+// and, at the end of the file, two clips blended on one object and an object moved as a whole by an object clip (section 3.17.2), and
+// objects parented to objects and to joints (section 3.17.3).
 // Plain C++17 with nothing of HIP and no context (as deform_rule.h and scatter_rule.h), so that a stand-alone program can run all of
 // it under a sanitizer (tools/anim_rule_check.cpp); under hipcc the MPT_HD functions are anim.hip's arithmetic.  The C ABI has the
 // whole evaluation of one object's pose as mpt_anim_rule and the validation of a clip as mpt_clip_check.
@@ -420,4 +421,104 @@ MPT_HD void mpt_anim_motion(int ntracks, const MptAnimTrack *tracks, const float
     double L[12];
     mpt_anim_local(trs, L);
     mpt_anim_world(base, L, world);
+}
+
+// ================================================================== objects parented to objects and to joints
+// A PARENT BINDING of an object is (parent, joint): another object of the table, and -1 or a joint of the skin of the parent's mesh.
+// A bound object's own matrix -- what mpt_object_add / mpt_object_set_world gave, or base . T R S of its motion binding, exactly as
+// mpt_anim_motion computes it -- is its LOCAL matrix, and
+//   joint -1:  world(child) = world(parent) . local
+//   joint j:   world(child) = world(parent) . ([M_j; 0 0 0 1] . local),  the inner product first
+// with M_j the 3x4 entry j of the parent's pose as it lies in the pose buffer (the skinning matrix global . inverse bind: the child
+// moves as a vertex skinned to j with weight 1 does).  Every product is mpt_mat4_mul; neither factor need be affine.
+
+// W = A . B of row-major 4x4 matrices, W[r][c] = ((A[r][0] B[0][c] + A[r][1] B[1][c]) + A[r][2] B[2][c]) + A[r][3] B[3][c]; W is
+// neither A nor B
+MPT_HD void mpt_mat4_mul(const double *A, const double *B, double *W) {
+    MPT_NO_CONTRACT
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++)
+            W[4 * r + c] = ((A[4 * r] * B[c] + A[4 * r + 1] * B[4 + c]) + A[4 * r + 2] * B[8 + c]) + A[4 * r + 3] * B[12 + c];
+}
+
+// world(child) [16] of world(parent) P [16], the palette entry M [12] (null: joint -1) and the child's local matrix L [16]
+MPT_HD void mpt_hier_world(const double *P, const double *M, const double *L, double *world) {
+    if (!M) { mpt_mat4_mul(P, L, world); return; }
+    double M4[16], X[16];
+    for (int k = 0; k < 12; k++) M4[k] = M[k];
+    M4[12] = 0.0; M4[13] = 0.0; M4[14] = 0.0; M4[15] = 1.0;
+    mpt_mat4_mul(M4, L, X);
+    mpt_mat4_mul(P, X, world);
+}
+
+// May object `obj` of a table of nobj objects be bound to (parent, joint)?  parent_of(o): the bindings as they stand (-1: a root);
+// instance_of(o): not 0 for an instance of a scatter; njoints_of(o): the joints of the skin of the object's mesh (0: no skin);
+// childless: the caller knows that nothing is bound to obj, so that the search for the height of its subtree, the one step that
+// looks at every object, is left out.  parent -1 unparents and is refused for an unknown object alone.  The numbers are the C ABI's
+// (mpt_parent_check)
+enum MptParentVerdict { MPT_PARENT_OK = 0, MPT_PARENT_UNKNOWN = 1, MPT_PARENT_CYCLE = 2, MPT_PARENT_INSTANCE = 3, MPT_PARENT_NO_SKIN = 4, MPT_PARENT_JOINT = 5,
+                        MPT_PARENT_DEPTH = 6 };
+template <class ParentOf, class InstanceOf, class JointsOf>
+inline MptParentVerdict mpt_parent_rule_of(int nobj, ParentOf parent_of, InstanceOf instance_of, JointsOf njoints_of, bool childless, int obj, int parent, int joint,
+                                           char *why, size_t why_size) {
+    auto say = [&](MptParentVerdict v, const char *fmt, long long a, long long b) {
+        if (why && why_size) snprintf(why, why_size, fmt, a, b);
+        return v;
+    };
+    if (why && why_size) why[0] = 0;
+    if (obj < 0 || obj >= nobj) return say(MPT_PARENT_UNKNOWN, "unknown object %lld (%lld objects)", obj, nobj);
+    if (parent == -1) return MPT_PARENT_OK;
+    if (parent < 0 || parent >= nobj) return say(MPT_PARENT_UNKNOWN, "unknown parent %lld (%lld objects)", parent, nobj);
+    if (instance_of(obj)) return say(MPT_PARENT_INSTANCE, "object %lld is an instance of a scatter, which places it on its surface", obj, 0);
+    if (instance_of(parent)) return say(MPT_PARENT_INSTANCE, "the parent, object %lld, is an instance of a scatter, whose matrix is written behind the hierarchy", parent, 0);
+    int above = 0;                                                    // the parent's depth: its ancestors (the bindings as they stand have no cycle)
+    for (int a = parent; a >= 0 && above <= nobj; a = parent_of(a), above++)
+        if (a == obj) return say(MPT_PARENT_CYCLE, "object %lld would be its own ancestor through object %lld", obj, parent);
+    above--;
+    if (joint < -1) return say(MPT_PARENT_JOINT, "joint %lld: -1, or a joint of the parent's skin", joint, 0);
+    if (joint >= 0 && njoints_of(parent) == 0) return say(MPT_PARENT_NO_SKIN, "joint %lld named, and the mesh of the parent, object %lld, has no skin", joint, parent);
+    if (joint >= njoints_of(parent) && joint >= 0) return say(MPT_PARENT_JOINT, "joint %lld outside the %lld joints of the parent's skin", joint, njoints_of(parent));
+    int below = 0;                                                    // the height of obj's own subtree
+    for (int o = 0; o < nobj && !childless; o++) {
+        int d = 0, a = o;
+        while (a >= 0 && a != obj && d <= nobj) { a = parent_of(a); d++; }
+        if (a == obj && d > below) below = d;
+    }
+    if (above + 1 + below > MPT_HIER_MAX_DEPTH)
+        return say(MPT_PARENT_DEPTH, "the chain would be %lld deep: at most %lld", above + 1 + below, MPT_HIER_MAX_DEPTH);
+    return MPT_PARENT_OK;
+}
+
+// ... over arrays: parents, instance and njoints [nobj]
+inline MptParentVerdict mpt_parent_rule(int nobj, const int32_t *parents, const int32_t *instance, const int32_t *njoints, int obj, int parent, int joint,
+                                        char *why, size_t why_size) {
+    if (nobj < 0 || (nobj > 0 && (!parents || !instance || !njoints))) {
+        if (why && why_size) snprintf(why, why_size, "parents, instance and njoints must hold %d objects", nobj);
+        return MPT_PARENT_UNKNOWN;
+    }
+    return mpt_parent_rule_of(nobj, [&](int o) { return parents[o]; }, [&](int o) { return instance[o]; }, [&](int o) { return njoints[o]; }, false, obj, parent,
+                              joint, why, why_size);
+}
+
+// The world matrix [16] of the last link of a chain of n links, link 0 the root, at scene time t.  Link k has local [16] -- its local
+// matrix, or with ntracks[k] >= 0 the base of its motion binding (offset, speed, loop) = binding [k][3], rest [k][10], whose object
+// clip's ntracks[k] tracks stand at tracks + track_at[k] and count their times and values from times[k] and values[k] -- and, for
+// k > 0, pal[k]: null, or the twelve doubles of the palette entry it follows.  The arrays have passed mpt_hierarchy_rule's checks
+struct MptHierLink {
+    const double *local; int ntracks; const MptAnimTrack *tracks; const float *times, *values; double t0, t1;
+    double offset, speed; int loop; const double *rest; const double *pal;
+};
+inline void mpt_hier_chain(int n, const MptHierLink *links, double t, double *world) {
+    double W[16], L[16], trs[MPT_ANIM_REST];
+    for (int k = 0; k < n; k++) {
+        const MptHierLink &ln = links[k];
+        if (ln.ntracks >= 0) {
+            for (int i = 0; i < MPT_ANIM_REST; i++) trs[i] = ln.rest[i];
+            mpt_anim_motion(ln.ntracks, ln.tracks, ln.times, ln.values, mpt_anim_local_time(t, ln.offset, ln.speed, ln.loop, ln.t0, ln.t1), trs, ln.local, L);
+        } else
+            for (int i = 0; i < 16; i++) L[i] = ln.local[i];
+        if (k == 0) { for (int i = 0; i < 16; i++) world[i] = L[i]; continue; }
+        for (int i = 0; i < 16; i++) W[i] = world[i];
+        mpt_hier_world(W, ln.pal, L, world);
+    }
 }

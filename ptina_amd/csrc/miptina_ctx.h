@@ -115,6 +115,13 @@ MPT_KERNEL_API hipError_t mpt_launch_anim(const MptAnimObj *objs, int nobj, doub
 MPT_KERNEL_API hipError_t mpt_launch_motion(const MptMotionObj *objs, int n, double t, const MptAnimTrack *tracks, const float *times, const float *values,
                                             MptComposeObj *rows, int nrows, unsigned epoch, hipStream_t stream);
 MPT_KERNEL_API hipError_t mpt_launch_anim_trig(const double *x, int n, double *acos_out, double *sin_out, hipStream_t stream);
+// hierarchy.hip
+MPT_KERNEL_API hipError_t mpt_launch_hierarchy_walk(const MptHierObj *items, const MptHierLevels *lv, int nlevels, double t, const MptAnimTrack *tracks,
+                                                    const float *times, const float *values, const double *pose, int64_t npose, MptComposeObj *rows,
+                                                    int nrows, unsigned epoch, hipStream_t stream);
+MPT_KERNEL_API hipError_t mpt_launch_hierarchy_level(const MptHierObj *items, int begin, int end, double t, const MptAnimTrack *tracks, const float *times,
+                                                     const float *values, const double *pose, int64_t npose, MptComposeObj *rows, int nrows, unsigned epoch,
+                                                     hipStream_t stream);
 // deform.hip: the deformed copies of the objects of a launch's table, written into the pool the meshes lie in (mpt_compose)
 MPT_KERNEL_API hipError_t mpt_launch_deform(float *pool, const MptDeformObj *objs, const MptRun *runs, int nruns, int blocks,
                                             const float *deltas, const uint16_t *joints, const float *weights, const double *pose,
@@ -468,6 +475,7 @@ struct MPT_INTERNAL MptAnimBufs {
     DevBuf<float> times, values;         // the tracks' key times and values
     DevBuf<MptAnimObj> objs;             // a launch's objects
     DevBuf<MptMotionObj> moved;          // ... and the objects that object clips move (motion_kernel)
+    DevBuf<MptHierObj> hier;             // ... and the bound children (hierarchy_kernel)
 };
 
 // Loop subdivision's device memory (scene_subdiv.cpp): the arena of the meshes' topology blocks, appended by mpt_mesh_set_subdivision
@@ -778,7 +786,7 @@ struct mpt_ctx {
         MPT_OBJ_CLEAN = 0,
         MPT_OBJ_UPLOAD = 1,                              // its record changed on the host: it goes up
         MPT_OBJ_PLACED = 2,                              // an instance whose scatter places: scatter.hip writes its record on the device
-        MPT_OBJ_MOVED = 4,                               // an object bound to an object clip (scene_anim.cpp): anim.hip's motion_kernel writes its matrix on the device
+        MPT_OBJ_MOVED = 4,                               // an object bound to an object clip (scene_anim.cpp): anim.hip's motion_kernel writes its matrix on the device; or a bound child (hierarchy.hip's kernel does)
         MPT_OBJ_COMPOSE = MPT_OBJ_UPLOAD | MPT_OBJ_PLACED | MPT_OBJ_MOVED,   // any of them
     };
     struct MptObjRow {                                   // an object: what the host alone keeps of it
@@ -786,6 +794,8 @@ struct mpt_ctx {
         int pose = -1, copy = -1, scatter = -1;          // its rows of deform.poses and subdiv.copies, the scatter it is an instance of (-1: none)
         unsigned char dirty = MPT_OBJ_UPLOAD;            // MptObjDirty flags, cleared by mpt_compose
         int motion = -1;                                 // its row of anim.motions (-1: no object clip has ever moved it)
+        int parent = -1, joint = -1;                     // its parent binding (scene_anim.cpp): the object it follows (-1: a root), the joint of that object's pose (-1: the object itself)
+        int children = 0;                                // the objects bound to it
     };
     struct MPT_INTERNAL Compose {                        // scene composition on the device (mpt_mesh_add, mpt_object_*, mpt_compose)
         std::vector<MptMeshRow> meshes; size_t pool_verts = 0;
@@ -857,7 +867,15 @@ struct mpt_ctx {
         int64_t evaluated_blended = 0, evaluated_moved = 0;   // of the last mpt_compose (mpt_anim_blend_stats)
         MptLaunchTimer timer;                            // mpt_compose: {before the anim kernel, after it} per launch
         MptLaunchTimer motion_timer;                     // ... {before the motion kernel, after it}
-        explicit Anim(MptEventPool &ev) : timer(2, ev), motion_timer(2, ev) {}
+        // parent bindings (the bindings themselves stand in the objects' rows)
+        int bound_children = 0;
+        bool order_stale = true;                         // a binding changed since `order` was made
+        std::vector<int> order, depth;                   // the bound children by depth, then id; every object's depth (a root: 0)
+        int deepest = 0;
+        std::vector<MptHierObj> h_hier;                  // the last hierarchy launch's table as uploaded
+        mpt_hierarchy_info hier_stats{};                 // of the last mpt_compose
+        MptLaunchTimer hier_timer;                       // ... {before the hierarchy kernel's launches, after them}
+        explicit Anim(MptEventPool &ev) : timer(2, ev), motion_timer(2, ev), hier_timer(2, ev) {}
     } anim{events};
     struct MptSubdivCopy {                               // a subdivided copy: of a mesh that is not deformable, or of one object of a mesh that is
         int mesh = 0, obj = -1;                          // obj -1: shared by the mesh's objects
@@ -1086,6 +1104,8 @@ MPT_INTERNAL int deform_step(mpt_ctx *c);                        // before compo
 
 // scene_anim.cpp: what mpt_scene_clear tells keyframe animation, and what deform_step asks of it
 MPT_INTERNAL void anim_scene_cleared(mpt_ctx *c, int meshes);    // the bindings go with the poses (scene_deform.cpp); skeletons and clips go with the meshes
+MPT_INTERNAL void hierarchy_mark(mpt_ctx *c);                    // at the head of mpt_compose: a dirty parent, or a dirty pose under a joint binding, marks its children MPT_OBJ_MOVED, level by level
+MPT_INTERNAL int hierarchy_step(mpt_ctx *c);                     // inside mpt_compose, behind motion_step and in front of scatter_step: the bound children's matrices
 MPT_INTERNAL int motion_step(mpt_ctx *c);                        // inside mpt_compose, behind the table's upload and in front of scatter_step: the moved objects' matrices
 MPT_INTERNAL int anim_step(mpt_ctx *c, const std::vector<int> &poses);   // inside deform_step, before the deform launch: evaluates these rows of deform.poses (bound objects) on the device
 

@@ -287,6 +287,20 @@ struct MptMotionObj {                       // 264 bytes
     double rest[MPT_ANIM_REST];              // translation3 rotation4 (xyzw) scale3: what a path without a track keeps
     double base[16];                         // row-major 4x4: world = base . local
 };
+// ... and one bound child of a launch of hierarchy_kernel (hierarchy.hip): its row of the object table, its
+// parent's, the palette entry it follows, and its local matrix -- as it stands, or as a motion binding gives it
+#define MPT_HIER_MAX_DEPTH 64               // the deepest chain: a child of a root has depth 1
+#define MPT_HIER_ONE_GROUP 1024             // up to this many children to evaluate, one workgroup walks the levels in one launch
+struct MptHierObj {                         // 272 bytes
+    int32_t obj, parent;                     // the row whose world matrix the kernel writes; the row it reads the parent's from
+    int32_t ntracks, loop;                   // -1: no motion binding, `local` is the local matrix; else the clip's tracks, and local = `local` . T R S
+    int64_t track_at;
+    int64_t joint_at;                        // -1: world = world(parent) . local; else the first double of the palette entry M_j in the pose buffer
+    double offset, speed, t0, t1;
+    double rest[MPT_ANIM_REST];
+    double local[16];                        // row-major 4x4: the local matrix, or the motion binding's base
+};
+struct MptHierLevels { int32_t at[MPT_HIER_MAX_DEPTH + 1]; };   // a launch's items are ordered by depth: level l holds the items [at[l], at[l + 1])
 
 // Loop subdivision (subdiv.hip): the caps, the kinds of a vertex rule (subdiv_rule.h), one job of a launch -- a subdivided copy: where
 // its control records and the copy lie in the pool, where its mesh's topology block lies in the arena of words and its own f64

@@ -4,7 +4,8 @@
 // would upload them.  Behind mpt_object_set_animation_blend / mpt_scene_add_object_clip / mpt_object_set_motion (section 3.17.2): an
 // object's second binding beside its first, object clips in the same arenas and list, the motion bindings, and motion_step: the part of
 // mpt_compose that writes the moved objects' matrices into the object table with anim.hip's motion_kernel.  The rule itself is anim_rule.h's; the C ABI has it whole as mpt_anim_rule and a clip's validation as
-// mpt_clip_check (no context, no GPU).
+// mpt_clip_check (no context, no GPU).  Behind mpt_object_set_parent (section 3.17.3): the parent bindings in the objects' rows,
+// hierarchy_mark and hierarchy_step, which writes the bound children's matrices with hierarchy.hip; whole as mpt_hierarchy_rule.
 
 #include "miptina_ctx.h"
 
@@ -82,6 +83,7 @@ extern "C" int mpt_motion_rule(int ntracks, const int32_t *tracks, const float *
 void anim_scene_cleared(mpt_ctx *c, int meshes) {
     auto &an = c->anim;                                  // (the bindings of poses went with deform.poses)
     an.motions.clear(); an.moved = 0;
+    an.bound_children = 0; an.order.clear(); an.depth.clear(); an.order_stale = true;   // (the parent bindings went with the objects' rows)
     if (!meshes) return;
     an.clips.clear();
     an.joints_used = an.tracks_used = an.times_used = an.values_used = 0;
@@ -309,7 +311,8 @@ int anim_step(mpt_ctx *c, const std::vector<int> &rows) {
 // The objects that object clips move: inside mpt_compose behind the upload of the object table, whose rows would overwrite what the
 // kernel writes, and in front of scatter_step and the composition, which read the matrices from the table.  A bound object is evaluated
 // when the table went up whole (a relayout), when its own row went up (its material changed, say) or when mpt_scene_set_time or
-// mpt_object_set_motion marked it; one launch for all of them, a lane each.  Without a motion binding in the scene nothing is called
+// mpt_object_set_motion marked it; one launch for all of them, a lane each.  Without a motion binding in the scene nothing is called.
+// A moved object that has a parent binding is hierarchy_step's
 int motion_step(mpt_ctx *c) {
     auto &an = c->anim;
     auto &cp = c->compose;
@@ -318,6 +321,7 @@ int motion_step(mpt_ctx *c) {
     an.h_moved.clear();
     for (const auto &m : an.motions) {
         if (m.clip < 0) continue;
+        if (cp.rows[m.obj].parent >= 0) continue;        // (a bound child: hierarchy_step evaluates its binding, and its matrix is written once)
         if (!cp.relayout && !(cp.rows[m.obj].dirty & (mpt_ctx::MPT_OBJ_MOVED | mpt_ctx::MPT_OBJ_UPLOAD))) continue;
         const auto &clip = an.clips[m.clip];
         MptMotionObj o{};
@@ -336,6 +340,205 @@ int motion_step(mpt_ctx *c) {
     HIP_TRY(mpt_launch_motion(an.bufs.moved, (int)n, an.time, an.bufs.tracks, an.bufs.times, an.bufs.values, cp.bufs.objs, (int)cp.objs.size(), cp.epoch, c->stream));
     HIP_TRY(span.end());
     return 0;
+}
+
+// ---------------------------------------------------------------- parent bindings
+extern "C" int mpt_parent_check(int nobj, const int32_t *parents, const int32_t *instance, const int32_t *njoints, int obj, int parent, int joint, char *why,
+                                int why_size) {
+    return (int)mpt_parent_rule(nobj, parents, instance, njoints, obj, parent, joint, why, why_size > 0 ? (size_t)why_size : 0);
+}
+
+// The whole evaluation of one object's world matrix down its chain of ancestors.  0, or 601 for bad arrays, 602 for a chain outside
+// [1, 65] links, 603 / 604 for a local matrix / a named palette entry that is not finite, 100 + a link's clip's verdict, 500 + its
+// motion binding's
+extern "C" int mpt_hierarchy_rule(int n, const double *locals, const int32_t *ntracks, const int32_t *tracks, const float *times, const int64_t *ntimes,
+                                  const float *values, const int64_t *nvalues, const double *bindings, const double *rests, const int32_t *joints,
+                                  const double *palette, double t, double *world) {
+    if (n < 1 || n > MPT_HIER_MAX_DEPTH + 1) return 602;
+    if (!locals || !ntracks || !world) return 601;
+    static const mpt_ctx::MptMotion fresh;               // (the default rest)
+    std::vector<MptHierLink> links((size_t)n);
+    std::vector<std::vector<MptAnimTrack>> tr((size_t)n);
+    int64_t track_at = 0, time_at = 0, value_at = 0;
+    for (int k = 0; k < n; k++) {
+        MptHierLink &ln = links[k];
+        ln = MptHierLink{};
+        ln.local = locals + (size_t)k * 16; ln.ntracks = -1;
+        for (int i = 0; i < 16; i++)
+            if (!std::isfinite(ln.local[i])) return 603;
+        if (k > 0 && joints && joints[k] >= 0) {
+            if (!palette) return 601;
+            ln.pal = palette + (size_t)k * 12;
+            for (int i = 0; i < 12; i++)
+                if (!std::isfinite(ln.pal[i])) return 604;
+        }
+        if (ntracks[k] < 0) continue;
+        if (!ntimes || !nvalues || !bindings || ntimes[k] < 0 || nvalues[k] < 0) return 601;
+        const int32_t *spec = tracks ? tracks + 4 * track_at : nullptr;
+        const float *T = times ? times + time_at : nullptr, *V = values ? values + value_at : nullptr;
+        const MptClipVerdict v = mpt_clip_rule(1, 0, ntracks[k], spec, T, ntimes[k], V, nvalues[k], nullptr, 0);
+        if (v != MPT_CLIP_OK) return 100 + (int)v;
+        const double *b = bindings + (size_t)k * 3;
+        ln.rest = rests ? rests + (size_t)k * MPT_ANIM_REST : fresh.rest;
+        const MptMotionVerdict mv = mpt_motion_binding_rule(b[0], b[1], ln.rest, ln.local, nullptr, 0);
+        if (mv != MPT_MOTION_OK) return 500 + (int)mv;
+        tr[k].resize((size_t)ntracks[k]);
+        mpt_anim_tracks(0, ntracks[k], spec, T, tr[k].data(), &ln.t0, &ln.t1);
+        ln.ntracks = ntracks[k]; ln.tracks = tr[k].data(); ln.times = T; ln.values = V;
+        ln.offset = b[0]; ln.speed = b[1]; ln.loop = b[2] != 0.0;
+        track_at += ntracks[k]; time_at += ntimes[k]; value_at += nvalues[k];
+    }
+    mpt_hier_chain(n, links.data(), t, world);
+    return 0;
+}
+
+extern "C" int mpt_object_set_parent(mpt_ctx *c, int obj_id, int parent_id, int joint) {
+    if (use(c)) return 1;
+    auto &cp = c->compose;
+    auto &an = c->anim;
+    const int nobj = (int)cp.rows.size();
+    char why[200];
+    // (over the rows themselves; an object nothing is bound to -- a tree bound from its root down binds no other -- costs its parent's depth)
+    const bool childless = obj_id >= 0 && obj_id < nobj && cp.rows[obj_id].children == 0;
+    const MptParentVerdict v = mpt_parent_rule_of(nobj, [&](int o) { return cp.rows[o].parent; }, [&](int o) { return cp.rows[o].scatter >= 0; },
+                                                  [&](int o) { return cp.meshes[cp.rows[o].mesh].deform.njoints; }, childless, obj_id, parent_id, joint, why, sizeof why);
+    if (v != MPT_PARENT_OK) return fail("mpt_object_set_parent: %s (refusal %d)", why, (int)v);
+    auto &row = cp.rows[obj_id];
+    if (parent_id == -1) {                               // its matrix is its world again: the host's row goes up (and a motion binding is motion_kernel's again)
+        if (row.parent < 0) return 0;
+        cp.rows[row.parent].children--;
+        row.parent = row.joint = -1;
+        an.bound_children--; an.order_stale = true;
+        row.dirty |= mpt_ctx::MPT_OBJ_UPLOAD;
+        return 0;
+    }
+    if (row.parent >= 0) cp.rows[row.parent].children--;
+    else an.bound_children++;
+    row.parent = parent_id; row.joint = joint;
+    cp.rows[parent_id].children++;
+    an.order_stale = true;
+    row.dirty |= mpt_ctx::MPT_OBJ_MOVED;
+    return 0;
+}
+
+extern "C" int mpt_object_get_parent(mpt_ctx *c, int obj_id, int *parent_id, int *joint) {
+    if (use_ro(c)) return 1;
+    if (check_object(c, obj_id, "mpt_object_get_parent")) return 1;
+    if (parent_id) *parent_id = c->compose.rows[obj_id].parent;
+    if (joint) *joint = c->compose.rows[obj_id].joint;
+    return 0;
+}
+
+// every object's depth and the bound children by depth, then id: made again behind a change of the bindings
+static void hierarchy_order(mpt_ctx *c) {
+    auto &an = c->anim;
+    const auto &rows = c->compose.rows;
+    if (!an.order_stale && an.depth.size() == rows.size()) return;   // (objects added since have no binding, and a depth all the same)
+    const int nobj = (int)rows.size();
+    an.depth.assign((size_t)nobj, 0);
+    an.deepest = 0;
+    std::vector<int> count(MPT_HIER_MAX_DEPTH + 2, 0);
+    for (int o = 0; o < nobj; o++) {
+        int d = 0;
+        for (int a = rows[o].parent; a >= 0 && d < MPT_HIER_MAX_DEPTH; a = rows[a].parent) d++;
+        an.depth[o] = d;
+        if (d > 0) count[d + 1]++;
+        an.deepest = std::max(an.deepest, d);
+    }
+    for (size_t d = 1; d < count.size(); d++) count[d] += count[d - 1];   // count[d]: the first place of depth d
+    an.order.assign((size_t)an.bound_children, 0);
+    for (int o = 0; o < nobj; o++)
+        if (an.depth[o] > 0) an.order[(size_t)count[an.depth[o]]++] = o;
+    an.order_stale = false;
+}
+
+// At the head of mpt_compose, before anything reads the dirty flags: a child is marked MPT_OBJ_MOVED when its parent's row is dirty
+// for any reason -- so the marks run down a subtree, the children being walked in depth order -- or when it names a joint and the
+// parent's pose is dirty.  One mpt_object_set_world, mpt_object_set_joints or mpt_scene_set_time moves a whole subtree and nothing else
+void hierarchy_mark(mpt_ctx *c) {
+    auto &an = c->anim;
+    if (an.bound_children == 0) return;
+    hierarchy_order(c);
+    auto &rows = c->compose.rows;
+    for (const int o : an.order) {
+        const auto &parent = rows[rows[o].parent];
+        if (parent.dirty || (rows[o].joint >= 0 && parent.pose >= 0 && c->deform.poses[parent.pose].dirty)) rows[o].dirty |= mpt_ctx::MPT_OBJ_MOVED;
+    }
+}
+
+// The bound children: inside mpt_compose behind motion_step, so that every root's matrix is in the table, and behind deform_step, so
+// that the palettes are in the pose buffer; in front of scatter_step and the composition, which read the matrices from the table.  A
+// child is evaluated when hierarchy_mark or a call marked it, when its own row went up (the host's row holds its local matrix), and
+// after a relayout.  The items go up ordered by depth; up to MPT_HIER_ONE_GROUP of them one launch walks the levels, above it each
+// level evaluated is a launch.  Without a parent binding in the scene nothing is called
+int hierarchy_step(mpt_ctx *c) {
+    auto &an = c->anim;
+    auto &cp = c->compose;
+    an.hier_stats.evaluated = an.hier_stats.levels = an.hier_stats.launches = 0;
+    if (an.bound_children == 0) return 0;
+    hierarchy_order(c);
+    an.h_hier.clear();
+    MptHierLevels lv{};
+    int nlevels = 0, depth = 0;
+    for (const int obj : an.order) {
+        const auto &row = cp.rows[obj];
+        if (!cp.relayout && !(row.dirty & (mpt_ctx::MPT_OBJ_MOVED | mpt_ctx::MPT_OBJ_UPLOAD))) continue;
+        if (an.depth[obj] != depth) { depth = an.depth[obj]; lv.at[nlevels++] = (int32_t)an.h_hier.size(); }
+        MptHierObj o{};
+        o.obj = obj; o.parent = row.parent; o.ntracks = -1; o.joint_at = -1;
+        memcpy(o.local, cp.objs[obj].world, sizeof o.local);
+        if (row.motion >= 0 && an.motions[row.motion].clip >= 0) {
+            const auto &m = an.motions[row.motion];
+            const auto &clip = an.clips[m.clip];
+            o.ntracks = clip.ntracks; o.loop = m.loop; o.track_at = (int64_t)clip.track_at;
+            o.offset = m.offset; o.speed = m.speed; o.t0 = clip.t0; o.t1 = clip.t1;
+            memcpy(o.rest, m.rest, sizeof o.rest); memcpy(o.local, m.base, sizeof o.local);
+        }
+        if (row.joint >= 0) {
+            const auto &p = c->deform.poses[cp.rows[row.parent].pose];
+            o.joint_at = (int64_t)p.pose_at + cp.meshes[p.mesh].deform.ntargets + (int64_t)row.joint * 12;
+        }
+        an.h_hier.push_back(o);
+    }
+    const size_t n = an.h_hier.size();
+    if (n == 0) return 0;
+    lv.at[nlevels] = (int32_t)n;
+    if (an.bufs.hier.reserve(n)) return 1;
+    HIP_TRY(hipMemcpyAsync(an.bufs.hier, an.h_hier.data(), n * sizeof(MptHierObj), hipMemcpyHostToDevice, c->stream));
+    const int64_t npose = (int64_t)c->deform.bufs.pose.cap;
+    MptTimedSpan span(an.hier_timer, c->stream);
+    HIP_TRY(span.begun);
+    if (n <= MPT_HIER_ONE_GROUP) {
+        HIP_TRY(mpt_launch_hierarchy_walk(an.bufs.hier, &lv, nlevels, an.time, an.bufs.tracks, an.bufs.times, an.bufs.values, c->deform.bufs.pose, npose,
+                                          cp.bufs.objs, (int)cp.objs.size(), cp.epoch, c->stream));
+        an.hier_stats.launches = 1;
+    } else
+        for (int l = 0; l < nlevels; l++) {
+            HIP_TRY(mpt_launch_hierarchy_level(an.bufs.hier, lv.at[l], lv.at[l + 1], an.time, an.bufs.tracks, an.bufs.times, an.bufs.values,
+                                               c->deform.bufs.pose, npose, cp.bufs.objs, (int)cp.objs.size(), cp.epoch, c->stream));
+            an.hier_stats.launches++;
+        }
+    HIP_TRY(span.end());
+    an.hier_stats.evaluated = (int64_t)n; an.hier_stats.levels = nlevels;
+    return 0;
+}
+
+extern "C" int mpt_hierarchy_stats(mpt_ctx *c, mpt_hierarchy_info *out) {
+    if (use_ro(c)) return 1;
+    if (!out) return fail("null argument");
+    const auto &rows = c->compose.rows;
+    *out = c->anim.hier_stats;
+    out->bound_children = c->anim.bound_children; out->deepest = 0;
+    for (size_t o = 0; o < rows.size() && c->anim.bound_children; o++) {       // (nothing of the context changes)
+        int64_t d = 0;
+        for (int a = rows[o].parent; a >= 0 && d < MPT_HIER_MAX_DEPTH; a = rows[a].parent) d++;
+        out->deepest = std::max(out->deepest, d);
+    }
+    return 0;
+}
+
+extern "C" int mpt_hierarchy_kernel_time(mpt_ctx *c, double *ms, int *launches) {
+    return use_ro(c) || timer_readout(c, c->anim.hier_timer, ms, nullptr, launches);
 }
 
 // ---------------------------------------------------------------- read-backs

@@ -177,6 +177,7 @@ extern "C" int mpt_compose(mpt_ctx *c) {
     if (use(c)) return 1;
     auto &cp = c->compose;
     const int nobj = (int)cp.objs.size();
+    hierarchy_mark(c);                                // a dirty parent's children are dirty (scene_anim.cpp): before anything reads the flags
     std::vector<int32_t> faces(nobj), dirty(nobj);
     long long total = 0;
     for (int o = 0; o < nobj; o++) { faces[o] = cp.objs[o].nfaces; total += faces[o]; }
@@ -228,6 +229,8 @@ extern "C" int mpt_compose(mpt_ctx *c) {
     // the moved objects' matrices (scene_anim.cpp): behind the table's upload, which would overwrite them, and in front of the scatters,
     // whose kernels read their surfaces' matrices from the table
     if (motion_step(c)) return 1;
+    // ... and the bound children's, level by level: behind their roots' matrices and the palettes, which deform_step left in the pose buffer
+    if (hierarchy_step(c)) return 1;
     // the scatters' launches: behind the table's upload, which would overwrite the matrices they write, and before the composition
     if (scatter_step(c)) return 1;
     kept.drop();

@@ -331,6 +331,34 @@ class ModelPool(metaclass=Singleton):
         ctx().call('mpt_anim_blend_stats', C.byref(info))
         return info
 
+    # ---- objects parented to objects and to joints (csrc/hierarchy.hip)
+    def set_parent(self, obj, parent, joint=None):
+        '''bind an object -- any but an instance of a scatter -- to a parent object, and with `joint` to joint `joint` of the parent's
+        pose.  The object's own matrix (add_object / set_world, which stays allowed; or its motion binding's base . T R S) is from then
+        on its LOCAL matrix, and compose() writes world(child) = world(parent) . local, or world(parent) . (M_joint . local) with the
+        skinning matrix pose_to_numpy(parent) returns, on the device: the child moves as a vertex skinned to the joint with weight 1
+        (tools.skin.attach folds the joint's bind matrix into a local given in the joint's frame).  One set_world, set_joints or
+        set_time moves a whole subtree.  parent=None unparents: the object's matrix is its world again.  Refused: a cycle, an instance
+        of a scatter on either side, a joint the parent's skin does not have, a chain deeper than 64'''
+        obj = self._object(obj)
+        parent = -1 if parent is None else self._object(parent)
+        ctx().call('mpt_object_set_parent', obj, parent, -1 if joint is None else int(joint))
+
+    def parent_of(self, obj):
+        '''(parent, joint) of a bound object, joint None for the parent itself; None for an object without a parent'''
+        obj = self._object(obj)
+        parent, joint = C.c_int(-1), C.c_int(-1)
+        ctx().call('mpt_object_get_parent', obj, C.byref(parent), C.byref(joint))
+        return None if parent.value < 0 else (parent.value, None if joint.value < 0 else joint.value)
+
+    def hierarchy_stats(self):
+        '''_lib.HierarchyInfo: bound children and the deepest chain; the children the last compose() evaluated on the device, over how
+        many levels, in how many launches'''
+        from ._lib import HierarchyInfo
+        info = HierarchyInfo()
+        ctx().call('mpt_hierarchy_stats', C.byref(info))
+        return info
+
     # ---- Loop subdivision on the device, behind the deformation (csrc/subdiv.hip; the reference's add-on
     #      is handed Blender's evaluated mesh instead)
     def _object_faces(self, mesh):

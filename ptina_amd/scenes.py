@@ -287,3 +287,136 @@ SCENES = {'s34': scene_s34, 's978': scene_s978, 'c4': scene_c4, 'c5': scene_rand
 
 def get_scene(name, **kw):
     return SCENES[name](**kw)
+
+
+# ---------------------------------------------------------------- animated glTF files into ModelPool
+class GltfScene:
+    '''what load_gltf_scene hands back: objects {node: [object ids]} (a node with several primitives has several; a node without a mesh
+    one, of the shared zero-face mesh), animations [names], and play()'''
+
+    def __init__(self, pool, desc):
+        self.pool, self.desc, self.objects, self.animations = pool, desc, {}, [a['name'] for a in desc['animations']]
+        self.mesh_clips, self.node_clips, self.motion = {}, {}, {}      # {object: {animation: clip}}, {node: {animation: clip}}, {node: (rest, base)}
+        self.rigid, self.skinned = {}, set()                            # {node: the object its children follow}; the skinned objects
+
+    def play(self, animation, offset=0.0, speed=1.0, loop=True):
+        '''bind every mesh clip and every object clip of `animation` (a name or an index; None unbinds everything)'''
+        a = None if animation is None else self.animations.index(animation) if isinstance(animation, str) else int(animation)
+        for obj, clips in self.mesh_clips.items():
+            self.pool.set_animation(obj, clips.get(a), offset, speed, loop)
+        for node, clips in self.node_clips.items():
+            rest, base = self.motion[node]
+            for obj in self.objects[node]:
+                if obj in self.skinned:
+                    continue                                            # (a skinned object stands at its skeleton's parent, not at its node)
+                self.pool.set_motion(obj, clips.get(a), offset, speed, loop, rest=rest, base=base)
+
+
+def load_gltf_scene(path):
+    '''an animated glTF 2.0 file into ModelPool() through the calls that exist: add_mesh, add_morph_targets, add_skin, add_skeleton,
+    add_clip, add_object_clip, add_object, set_motion (at play()), set_parent.  Every node on a path to a mesh becomes an object whose
+    local matrix is the node's, a child node a set_parent; a primitive is a pool mesh; a skin a skeleton over its joint nodes, its
+    object standing under the node above the skeleton's roots (the skinned node's own transform is ignored, as the specification
+    says); a node under a joint node follows that joint of the skinned object, the joint's bind matrix folded into its local
+    (tools.skin.attach); channels on joints and 'weights' channels go into the mesh's clip, channels on other nodes into one
+    object clip per node.  Returns a GltfScene; compose() is the caller's'''
+    from .things import ModelPool
+    from .tools.anim import track
+    from .tools.readgltf import read_gltf_scene
+    from .tools.skin import attach
+    desc = read_gltf_scene(path)
+    pool = ModelPool()
+    nodes, skins, joint_of = desc['nodes'], desc['skins'], desc['joint_of']
+    H = GltfScene(pool, desc)
+    eye = np.eye(4)
+    empty = []
+
+    def empty_mesh():
+        if not empty:
+            empty.append(pool.add_mesh(np.zeros((0, 3, 3), np.float32), np.zeros((0, 3, 3), np.float32)))
+        return empty[0]
+
+    def tracks_of(anim, pick):
+        return [track(target, ch['path'], ch['times'], ch['values'], ch['interpolation']) for ch in anim['channels'] for target in [pick(ch)] if target is not None]
+
+    def pool_mesh(node, pr):
+        '''the pool mesh of one primitive of a node with its rig and its clips: (mesh, {animation: clip})'''
+        mesh = pool.add_mesh(pr['p'], pr['n'], pr['t'])
+        T = 0 if pr['dp'] is None else pr['dp'].shape[0]
+        if T:
+            pool.add_morph_targets(mesh, pr['dp'], pr['dn'])
+        skin = skins[nodes[node]['skin']] if nodes[node]['skin'] >= 0 and pr['joints'] is not None else None
+        if skin is not None:
+            js = skin['joints']
+            pool.add_skin(mesh, pr['joints'], pr['weights'], len(js))
+            pool.add_skeleton(mesh, skin['parents'], np.stack([nodes[j]['translation'] for j in js]), np.stack([nodes[j]['rotation'] for j in js]),
+                              np.stack([nodes[j]['scale'] for j in js]), skin['inverse_bind'])
+        clips = {}
+        if T or skin is not None:
+            for a, anim in enumerate(desc['animations']):
+                def pick(ch):
+                    if ch['path'] == 'weights':
+                        return -1 if T and ch['node'] == node else None
+                    return skin['joints'].index(ch['node']) if skin is not None and ch['node'] in skin['joints'] else None
+                tr = tracks_of(anim, pick)
+                if tr:
+                    clips[a] = pool.add_clip(mesh, tr)
+        return mesh, clips
+    # where a node's local matrix stands: under a joint, the joint's bind matrix is folded in
+    def base_of(node):      # noqa: E306
+        p = nodes[node]['parent']
+        return attach(skins[joint_of[p][0]]['inverse_bind'][joint_of[p][1]], eye) if p in joint_of else None
+    skinned_obj = {}
+    for node in desc['carriers']:
+        n = nodes[node]
+        base = base_of(node)
+        local = n['local'] if base is None else base @ n['local']
+        prims = desc['meshes'][n['mesh']]['primitives'] if n['mesh'] >= 0 and n['skin'] < 0 else []
+        ids = []
+        for pr in prims:
+            mesh, clips = pool_mesh(node, pr)
+            ids.append(pool.add_object(mesh, local, None if pr['material'] < 0 else pr['material']))
+            if clips:
+                H.mesh_clips[ids[-1]] = clips
+        if not ids:
+            ids.append(pool.add_object(empty_mesh(), local))
+        H.objects[node], H.rigid[node] = ids, ids[0]
+        H.motion[node] = (np.concatenate([n['translation'], n['rotation'], n['scale']]), base)
+    for node, n in enumerate(nodes):
+        if n['mesh'] >= 0 and n['skin'] >= 0:                               # skinned: at the node above the skeleton's roots
+            for pr in desc['meshes'][n['mesh']]['primitives']:
+                mesh, clips = pool_mesh(node, pr)
+                obj = pool.add_object(mesh, eye, None if pr['material'] < 0 else pr['material'])
+                H.objects.setdefault(node, []).append(obj)
+                H.mesh_clips[obj] = clips
+                H.skinned.add(obj)
+                if pr['joints'] is not None:
+                    skinned_obj.setdefault(n['skin'], obj)
+                rp = skins[n['skin']]['root_parent']
+                if rp >= 0:
+                    pool.set_parent(obj, H.rigid[rp])
+    for node, n in enumerate(nodes):
+        if node in joint_of and n['mesh'] >= 0 and n['skin'] < 0:           # a joint node that carries a mesh: on its own joint
+            si, j = joint_of[node]
+            for pr in desc['meshes'][n['mesh']]['primitives']:
+                mesh, clips = pool_mesh(node, pr)
+                obj = pool.add_object(mesh, attach(skins[si]['inverse_bind'][j], eye), None if pr['material'] < 0 else pr['material'])
+                H.objects.setdefault(node, []).append(obj)
+                if clips:
+                    H.mesh_clips[obj] = clips
+                pool.set_parent(obj, skinned_obj[si], j)
+    for node in desc['carriers']:
+        p = nodes[node]['parent']
+        for obj in H.objects[node][:len(H.objects[node]) if nodes[node]['skin'] < 0 else 1]:
+            if p in joint_of:
+                pool.set_parent(obj, skinned_obj[joint_of[p][0]], joint_of[p][1])
+            elif p >= 0:
+                pool.set_parent(obj, H.rigid[p])
+    for a, anim in enumerate(desc['animations']):
+        for node in desc['carriers']:
+            tr = tracks_of(anim, lambda ch: 0 if ch['node'] == node and ch['path'] != 'weights' else None)
+            if tr:
+                if nodes[node]['matrix'] is not None:
+                    raise NotImplementedError('%s: an animated node with a matrix (node %d)' % (path, node))
+                H.node_clips.setdefault(node, {})[a] = pool.add_object_clip(tr)
+    return H

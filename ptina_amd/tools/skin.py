@@ -25,3 +25,15 @@ def joint_matrices(parents, local, inverse_bind):
             raise ValueError('joint %d has parent %d: parents must come before their children (-1: a root)' % (j, p))
         glob[j] = local[j] if p < 0 else glob[p] @ local[j]
     return np.stack([glob[j] @ inverse_bind[j] for j in range(n)]) if n else glob
+
+
+def attach(inverse_bind_j, local):
+    '''the local matrix [4,4] f64 to give an object that ModelPool().set_parent binds to a joint, for `local` given in the joint's own
+    frame: inverse(inverse_bind_j) . local.  The device multiplies a bound child by the joint's skinning matrix global . inverseBind
+    (DESIGN.md section 3.17.3); with the bind matrix folded in, the child sits at global . local'''
+    ib, local = np.asarray(inverse_bind_j, np.float64), np.asarray(local, np.float64)
+    if ib.shape == (3, 4):
+        ib = np.concatenate([ib, [[0.0, 0.0, 0.0, 1.0]]])
+    if ib.shape != (4, 4) or local.shape != (4, 4):
+        raise ValueError('inverse_bind_j [4,4] (or [3,4]) and local [4,4] expected, got %s and %s' % (ib.shape, local.shape))
+    return np.linalg.inv(ib) @ local

@@ -35,6 +35,7 @@ _PASS_THROUGH = {
     'set_object_animation_blend': ('ModelPool', 'set_animation_blend', ('obj', 'clip', ('offset', 0.0), ('speed', 1.0), ('loop', True), ('weight', 1.0), ('fade', None))),
     'add_object_clip': ('ModelPool', 'add_object_clip', ('tracks',)),
     'set_object_motion': ('ModelPool', 'set_motion', ('obj', 'clip', ('offset', 0.0), ('speed', 1.0), ('loop', True), ('rest', None), ('base', None))),
+    'set_object_parent': ('ModelPool', 'set_parent', ('obj', 'parent', ('joint', None))),
     'set_mesh_subdivision': ('ModelPool', 'add_subdivision', ('mesh', 'levels', ('creases', None), ('corners', None), ('scheme', 'loop'), ('polys', None))),
     'set_mesh_displacement': ('ModelPool', 'add_displacement', ('mesh', 'image', ('strength', 1.0), ('midlevel', 0.5), ('mode', 'normal'), ('channel', 'mean'))),
     'set_mesh_displacement_params': ('ModelPool', 'set_displacement', ('mesh', 'strength', ('midlevel', None))),
